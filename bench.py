@@ -2,6 +2,7 @@
 """Headline benchmark: batched differential-IK solves/sec on MI355X.
 
   python bench.py --gpus N --steps K --warmup W [--config g1_c3|ur5e_c2|g1_full|shadow_c4] [--batch B]
+                  [--dump-outputs DIR] [--full]
 
 Default workload (BASELINE.json metric, configs[2]): Unitree G1 (nq=44, nv=43), 4 FrameTasks
 (feet + palms) + PostureTask + ConfigurationLimit + VelocityLimit box limits, batch
@@ -10,15 +11,18 @@ lines carry the same fields).  A "step" is one batched solve_ik over the residen
 (inputs already in HBM).
 
 N > 1: one rank per GPU.  The driver launches the ranks itself through torch.distributed.run; when
-WORLD_SIZE is not set, `python bench.py --gpus N` re-executes itself under torch.distributed.run with N
-ranks (and refuses to run if the box has fewer than N GPUs) — a line is never printed with n_gpus != --gpus.
+WORLD_SIZE is not set, `python bench.py --gpus N` runs itself under torch.distributed.run with N ranks as a
+child process (and refuses to run if the box has fewer than N GPUs) — a line is never printed with n_gpus != --gpus.
 The batch shards by rank (weak scaling, configs[4] = 8 x 65 536) with no data-path collective: the
-instances are independent, v stays on the GPU that produced it.  After the compute-only timed region a
-second timed region of the same K steps ends every step with the RCCL gather of v to rank 0 that BASELINE
-configs[4] mentions; it is reported separately under "gather" (never as `value`).
+instances are independent, v stays on the GPU that produced it.
 
-Prints ONE JSON line (rank 0) with the whole-job solves/sec, the HBM roofline of the kernel (algorithmic
-bytes / launch duration from HIP events on the launch stream) and CPU baselines.
+Prints ONE JSON line (rank 0) with the whole-job solves/sec and the HBM roofline of the kernel (algorithmic
+bytes / launch duration from HIP events on the launch stream).  A plain run does only that: set-up, W warm-up
+steps, K timed steps, the line.  --dump-outputs DIR also writes what the last timed step computed (v, status) as
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.  --full adds every other
+measurement: the CPU baselines, the fused-loop and PCIe-inclusive legs, the batch sweep, the other named workloads
+and, for N > 1, a second timed region of the same K steps that ends every step with the RCCL gather of v to rank 0
+that BASELINE configs[4] mentions, reported separately under "gather" (never as `value`).
 """
 
 import argparse
@@ -442,8 +446,27 @@ def _free_port() -> int:
         return s.getsockname()[1]
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: each array (rows = the instances of the batch) as <path>/<name>.npy in float64.  Above `limit` bytes in
+    all, the same fixed, seeded sample of rows from every array, and their indices as rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(a, dtype=np.float64) for k, a in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a[:1].nbytes for a in arrays.values())
+    if n * row_bytes > limit:
+        rows = np.sort(np.random.default_rng(seed).choice(n, limit // (row_bytes + 8), replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def self_launch(args) -> None:
-    """`python bench.py --gpus N` without a launcher: become N ranks under torch.distributed.run."""
+    """`python bench.py --gpus N` without a launcher: run N ranks under torch.distributed.run in a child process (this
+    process may have initialised HIP to count the devices, so it is not replaced) and exit with the child's status."""
     share = os.environ.get("MKH_BENCH_SHARE_GPU") == "1"
     if not share:
         from mink_amd import _native as nat
@@ -454,7 +477,7 @@ def self_launch(args) -> None:
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(REPO, "bench.py")] + sys.argv[1:]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
-    os.execve(sys.executable, cmd, env)
+    sys.exit(subprocess.run(cmd, env=env).returncode)
 
 
 def main():
@@ -466,11 +489,17 @@ def main():
                     help="BASELINE config (default: the headline G1 config 3), or one of the two general routes of the "
                          "boundary: g1_plugin (caller-defined Task + Limit rows, mkh_solve_dense), ur5e_convex (a collision "
                          "pair on the general convex routine)")
+    ap.add_argument("--full", action="store_true",
+                    help="every measurement besides the headline: CPU baselines, fused-loop and PCIe-inclusive legs, batch sweep, "
+                         "`other_configs`, and for N > 1 the timed region with the RCCL gather (the --no-* options below trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (v, status; rank 0's shard) as DIR/<name>.npy, "
+                         "float64, at most 64 MB (a fixed seeded sample of the rows beyond that, their indices in rows.npy)")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="default g1_c3 line only: skip the `other_configs` records (every other named workload, 20 steps each)")
     ap.add_argument("--batch", type=int, default=None, help="problems per GPU (default: the config's BASELINE batch)")
     ap.add_argument("--gather", action="store_true",
-                    help="(kept for compatibility) N>1 always reports the RCCL-gather variant in the 'gather' object")
+                    help="(kept for compatibility) N>1 with --full always reports the RCCL-gather variant in the 'gather' object")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-loop-legs", action="store_true",
                     help="skip the fused-loop figures (loop20_targets_per_s, converged_targets): tools/profile.sh's trace pass, whose "
@@ -482,6 +511,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)                                 # does not return
 
@@ -609,8 +640,11 @@ def main():
     gc.collect()
     gc.disable()
     elapsed, kern_list, _ = timed_region(False)
+    status = st.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"v": v.cpu().numpy(), "status": status})
     gather = None
-    if world > 1:
+    if world > 1 and args.full:
         g_el, _, g_list = timed_region(True)
         gather = {"value": world * B * args.steps / g_el, "unit": "solves/s", "ms_per_step": 1e3 * g_el / args.steps,
                   "gather_ms_rank0_median": statistics.median(g_list) if g_list else None,
@@ -629,7 +663,6 @@ def main():
     if os.environ.get("MKH_BENCH_DEBUG"):
         print("kernel ms per step:", [round(x, 3) for x in kern_list], file=sys.stderr)
 
-    status = st.cpu().numpy()
     n_bad = int(((status & ~1) != 0).sum())
     if rank == 0:
         total = world * B * args.steps
@@ -710,7 +743,7 @@ def main():
         res = kernel_resources(kernel)
         if res is not None:
             out["kernel_resources"] = res
-        if world == 1 and plain and not args.no_loop_legs:
+        if args.full and world == 1 and plain and not args.no_loop_legs:
             out["loop20_targets_per_s"] = loop_targets(prob, q, tg, pt, ct, dt, damping, B, max_iters=20)
             # ... and a figure that deserves the name: targets that lie inside the joint ranges (the SURVEY §8(d) distribution of
             # the headline batch leaves most G1 targets just outside them, workloads.make_batch), the iteration budget raised
@@ -730,11 +763,11 @@ def main():
                 out["pcie_inclusive_value"] = pcie_inclusive(prob, q_h, tg_h, pt_h, ct_h, dt, damping)
                 if args.config == "g1_c3" and args.batch is None:
                     out["batch_sweep"] = batch_sweep(prob, q, tg, pt, ct, dt, damping, v, st)
-        if world == 1 and args.config == "g1_c3" and args.batch is None and not args.no_other_configs:
+        if args.full and world == 1 and args.config == "g1_c3" and args.batch is None and not args.no_other_configs:
             # every other named workload behind the boundary, measured by the same command (20 launches each, < 0.2 s of
             # GPU time per config): the three other single-GPU BASELINE configs and the two general routes
             out["other_configs"] = [measure_side_config(name, dev) for name in SIDE_CONFIGS]
-        if world == 1 and plain and not args.no_cpu_baseline:
+        if args.full and world == 1 and plain and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.config, q_h, tg_h, pt_h, ct_h)
             # mink's real dispatch pattern (per-call Python over numpy), next to the optimistic C port
             out["cpu_baseline_python"] = (out["cpu_baseline"] if "numpy" in out["cpu_baseline"]["sample"]
@@ -750,7 +783,7 @@ def main():
                                                      "converged_targets", "pcie_inclusive_value", "batch_sweep", "other_configs"],
                                      "from_the_single_gpu_profile": ["roofline.traffic", "roofline.valu_issue_view", "roofline.binding_resource"],
                                      "measured_by_this_run": ["value", "ms_per_step", "roofline.kernel_ms (rank 0)", "roofline.achieved", "per_rank",
-                                                              "scaling_view", "gather"]}
+                                                              "scaling_view"] + (["gather"] if gather is not None else [])}
         print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()

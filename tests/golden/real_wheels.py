@@ -90,8 +90,8 @@ def _names(mj, m, kind, n):
 
 
 def _configs(mj, mink, examples: str):
-    """The four BASELINE configurations exactly as make_golden.py::main builds them (kept in step by
-    tests/test_real_wheels.py::test_the_checker_itself_reproduces_the_fixtures_over_the_stubs)."""
+    """The four BASELINE configurations exactly as make_golden.py::main builds them (kept in step by a run with `--allow-stubs`
+    against the mink checkout: over oracle/stubs every `worst` it prints is 0)."""
     out = {}
     m = mj.MjModel.from_xml_path(os.path.join(examples, "universal_robots_ur5e", "scene.xml"))
     ft = mink.FrameTask("attachment_site", "site", position_cost=1.0, orientation_cost=1.0, lm_damping=1.0)

@@ -80,6 +80,31 @@ def test_bench_helpers():
     assert b.kernel_keys("ik_solve_kernel_48_72+redo_64+wide") == ["ik_solve_kernel_48_72", "ik_solve_kernel_64_72", "ik_wide_kernel"]
 
 
+def test_dump_outputs_writes_float64_and_samples_past_the_limit(tmp_path):
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(REPO, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    assert b.DUMP_LIMIT_BYTES == 64 << 20
+    v = np.arange(1000 * 3, dtype=np.float64).reshape(1000, 3)
+    st = np.arange(1000, dtype=np.int32) % 3
+    b.dump_outputs(str(tmp_path / "all"), {"v": v, "status": st})
+    assert sorted(os.listdir(tmp_path / "all")) == ["status.npy", "v.npy"]
+    assert np.array_equal(np.load(tmp_path / "all" / "v.npy"), v)
+    s = np.load(tmp_path / "all" / "status.npy")
+    assert s.dtype == np.float64 and np.array_equal(s, st)
+    # past the limit: the same seeded rows of every array, their indices alongside, the whole within the limit
+    limit = 100 * (3 * 8 + 8 + 8)               # v, status and the row index: 40 bytes a row
+    for run in ("a", "b"):
+        b.dump_outputs(str(tmp_path / run), {"v": v, "status": st}, limit=limit)
+    rows = np.load(tmp_path / "a" / "rows.npy")
+    assert len(rows) == 100 and np.array_equal(rows, np.load(tmp_path / "b" / "rows.npy"))
+    assert np.all(np.diff(rows) > 0) and rows.max() < 1000
+    r = rows.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "v.npy"), v[r]) and np.array_equal(np.load(tmp_path / "a" / "status.npy"), st[r])
+    assert sum(np.load(tmp_path / "a" / f).nbytes for f in os.listdir(tmp_path / "a")) <= limit
+
+
 def test_counters_are_only_replayed_from_a_profile_of_the_code_that_ran(monkeypatch, tmp_path):
     """`roofline.traffic` / `valu_issue_view` come from profiles/ (counters cannot be read inside a timed run): a summary is
     used only when its provenance stamp (tools/rocprof_summary.py) names the kernels of this run with the sha256 of the

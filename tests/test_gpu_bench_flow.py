@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -22,7 +23,7 @@ def _env(**kw):
 
 def test_self_launched_two_rank_line():
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--batch", "4096", "--no-cpu-baseline"], env=_env(MKH_BENCH_SHARE_GPU="1"), capture_output=True,
+                        "--batch", "4096", "--full", "--no-cpu-baseline"], env=_env(MKH_BENCH_SHARE_GPU="1"), capture_output=True,
                        text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -38,6 +39,32 @@ def test_self_launched_two_rank_line():
     # the counters of the line are either a profile of the code that ran, or absent and flagged
     rf = d["roofline"]
     assert rf["stale_profile"] == (rf["traffic"] is None) and rf["profile_check"]["kernels_ran"]
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A run without --full times exactly --steps steps and measures nothing else; --dump-outputs writes what the last step
+    computed, and the same arguments give the same inputs, so two runs dump the same arrays."""
+    full_only = ("cpu_baseline", "cpu_baseline_python", "cpu_reference_recorded", "loop20_targets_per_s", "converged_targets",
+                 "pcie_inclusive_value", "batch_sweep", "other_configs", "gather")
+    dumps = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--batch", "4096", "--dump-outputs", str(tmp_path / run)], env=_env(), capture_output=True,
+                           text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["unit"] == "solves/s" and d["dtype"] == "f64"
+        assert d["higher_is_better"] is True and d["value"] > 0 and d["ms_per_step"] > 0
+        assert abs(d["value"] * d["ms_per_step"] * 1e-3 - 4096) < 1e-6 * 4096
+        assert not [k for k in full_only if k in d], list(d)
+        dumps.append({k: np.load(tmp_path / run / f"{k}.npy") for k in ("v", "status")})
+    a, b = dumps
+    assert a["v"].shape == (4096, 43) and a["status"].shape == (4096,)
+    assert a["v"].dtype == np.float64 and a["status"].dtype == np.float64
+    assert np.isfinite(a["v"]).all() and (np.abs(a["v"]).max() > 0) and ((a["status"].astype(np.int64) & ~1) == 0).all()
+    assert np.array_equal(a["v"], b["v"]) and np.array_equal(a["status"], b["status"])
 
 
 def test_two_gpu_line_is_refused_on_one_gpu():

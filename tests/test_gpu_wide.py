@@ -210,7 +210,7 @@ def _g1_with_contacts(B):
     return model, prob, pairs, q, tg, stand
 
 
-def test_g1_with_more_contacts_than_tableau_rows_gets_every_row():
+def test_g1_with_more_contacts_than_tableau_rows_gets_every_row(tmp_path):
     """G1 (nv 43) holds 21 half-space rows on the wavefront kernel.  With 40+ contacts in range at once the wavefront launch
     keeps the tightest 21, checks the rest at its solution and flags the instances where one of them is violated; the wide
     redo launch solves those with EVERY detected contact a row — mink's answer (solve_ik.py:25-40 stacks them all), held against
@@ -232,10 +232,10 @@ with nat.diag_options(nat.DIAG_NO_WIDE_REDO):
 v, st = prob.solve(q, tg, stand[None, :], None, 5e-2, 1e-1)
 print("FLAGGED", int(((st & 16) != 0).sum()), prob.last_kernel())
 np.save(%r, st)
-""" % (REPO, os.path.join(REPO, "tests"), B, "/tmp/mkh_wide_st.npy")
+""" % (REPO, os.path.join(REPO, "tests"), B, str(tmp_path / "st.npy"))
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
-    flagged = np.flatnonzero(np.load("/tmp/mkh_wide_st.npy") & 16)
+    flagged = np.flatnonzero(np.load(tmp_path / "st.npy") & 16)
     print(r.stdout.strip().splitlines()[-1])
     assert len(flagged) >= 16, len(flagged)
     # EVERY re-solved instance (and a few others) against the numpy oracle with all rows, over the host's cores
@@ -267,7 +267,7 @@ def _all_rows_oracle(args):
     return vs, most, cfg.q.copy()
 
 
-def test_fused_loop_and_taps_with_more_contacts_than_tableau_rows():
+def test_fused_loop_and_taps_with_more_contacts_than_tableau_rows(tmp_path):
     """Round 5: the fused loops and calls with taps no longer report MKH_ST_ROW_OVERFLOW (round 4: SolverError where the reference
     stacks every row, mink/solve_ik.py:25-40).  An instance the wavefront kernel flags inside mkh_solve_steps keeps its q
     (which q_out may alias) and runs its whole loop again on the workgroup-per-problem kernel; a call with taps gets the
@@ -290,10 +290,10 @@ with nat.diag_options(nat.DIAG_NO_WIDE_REDO):
     model, prob, pairs, q, tg, stand = T._g1_with_contacts(%d)
 qK, vK, st = prob.solve(q, tg, stand[None, :], None, 5e-2, 1e-1, n_steps=%d)
 np.save(%r, st)
-""" % (REPO, os.path.join(REPO, "tests"), B, K, "/tmp/mkh_wide_st_loop.npy")
+""" % (REPO, os.path.join(REPO, "tests"), B, K, str(tmp_path / "st.npy"))
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
-    flagged = np.flatnonzero(np.load("/tmp/mkh_wide_st_loop.npy") & 16)
+    flagged = np.flatnonzero(np.load(tmp_path / "st.npy") & 16)
     assert len(flagged) >= 2, len(flagged)
     idx = [int(i) for i in flagged[:24]] + [int(j) for j in np.setdiff1d(np.arange(B), flagged)[:4]]
     with mp.get_context("fork").Pool(min(16, os.cpu_count() or 1)) as pool:
