@@ -105,7 +105,8 @@ extern "C" {
                                      * variant behind it) — parity/diagnostic switch */
 #define MKH_FLAG_QUAD_KERNEL 256    /* use the row-per-problem kernel of small robots (16 lanes per problem, nv <= 16) whenever the problem
                                      * qualifies, whatever the batch size (default: plain solves below 73728 instances, fused
-                                     * loops below 28672; parity/diagnostic switch) */
+                                     * loops below 28672; the fused loops of a floating base under frame / posture tasks alone on
+                                     * its two-row build, which the default leaves on the wavefront kernel; parity/diagnostic switch) */
 
 /* frame types (mink/constants.py:3 SUPPORTED_FRAMES) */
 #define MKH_FRAME_BODY 0

@@ -154,6 +154,7 @@ struct MkhProblem {
   // lane-per-problem kernel for small arms (lane_kernel.h): template size (0 = the problem does not qualify)
   int lane_nv = 0, lane_lds = 0;   // lane kernel's template size (0: not eligible)
   int quad_nt = 0;                 // row kernel's column registers, 8 or 16 (0: not eligible)
+  bool quad_loop_ok = true;        // two-row build: its fused loop can integrate every coordinate (a free joint is a link)
   LaneProblem* d_lane = nullptr;
   LaneDims lane_dims{};
   char last_kernel[64] = "";
@@ -1335,6 +1336,13 @@ int32_t mkh_problem_create_diag(MkhModel* m, const MkhProblemDesc* d, int32_t ma
     p->lane_nv = small_cls <= 8 ? small_cls : 0;
     p->quad_nt = small_cls ? (small_cls <= 8 ? 8 : (small_cls == 32 ? 32 : 16)) : 0;
     if (dbg_env("MKH_DEBUG_NO_PAIR_ROWS") && p->quad_nt == 32) p->quad_nt = 0;   // (A/B switch: 17 … 32-dof robots back on the wavefront kernel)
+    // (the two-row loop carries a free joint's quaternion on the link of its rotation; a free body on no task chain — the loose
+    //  object of a hand scene — has no link, and its loops stay on the wavefront kernel, which integrates every joint)
+    if (small_cls == 32 && lp.nq != lp.nv) {
+      bool linked = false;
+      for (int k = 0; k < lp.nlink; ++k) linked = linked || lp.link[k].jtype == JNT_BALL;
+      p->quad_loop_ok = linked;
+    }
     if (small_cls) {
       p->lane_lds = lane_lds_bytes(lp.nlink);
       bool ident = true;
@@ -1607,14 +1615,23 @@ static int32_t launch(MkhProblem* p, const SolveArgs& a_in, const TapArgs* taps,
   //  kernel of that size to hand over to)
   // (MKH_FLAG_WARM_START: the row kernel keeps its partition in the handle's warm-start buffer like the wavefront kernels)
   // (17 … 32 dofs or links, floating bases — H1, Go1, Spot, Allegro: the row kernel on TWO DPP rows per problem, two problems per
-  //  wavefront; single solves only — the fused loops of such robots integrate a quaternion and stay on the wavefront kernel)
-  if (p->quad_nt && small_ok && !(p->quad_nt == 32 && loop) && !((flags & MKH_FLAG_LANE_KERNEL) && p->lane_nv) &&
+  //  wavefront; its fused loop carries the floating base's quaternion from step to step.  Fused loops, kernel ms two-row against
+  //  wavefront kernel, 10 fixed steps / threshold loop, 4 096 … 65 536 instances (tools/bench_two_row_loop.py,
+  //  profiles/r07_two_row_loop.txt): H1 with its ComTask 3.2 … 3.7x faster, H1 with RelativeFrameTasks 2.4 … 3.0x (the
+  //  wavefront kernel needs its all-feature build for both), the Shadow hand without contacts 1.10 … 1.21x; a floating base under frame / posture tasks alone runs the
+  //  wavefront kernel's low-rank loop build faster — H1 0.87 … 0.95x, Go1 0.82 … 1.06x — and stays there.
+  //  MKH_FLAG_QUAD_KERNEL forces the two-row loop where it can run: not for a free joint that is no link, see quad_loop_ok.)
+  const bool two_row_loop_slower = p->quad_nt == 32 && loop && p->dev.nq != p->dev.nv && !p->has_relative && p->dev.n_com == 0 &&
+                                   !(flags & MKH_FLAG_QUAD_KERNEL);
+  const bool two_row_loop_bad = p->quad_nt == 32 && loop && !p->quad_loop_ok;
+  if (p->quad_nt && small_ok && !two_row_loop_slower && !two_row_loop_bad && !((flags & MKH_FLAG_LANE_KERNEL) && p->lane_nv) &&
       (!p->lane_nv || a.B < (loop ? mkh::kLaneMinBatchLoop : mkh::kLaneMinBatch) || (flags & MKH_FLAG_QUAD_KERNEL))) {
     const int per_wave = p->quad_nt == 32 ? 2 : 4;
     const int grid = (a.B + per_wave - 1) / per_wave;
     p->last_grid = grid; p->last_nt = p->quad_nt;
     snprintf(p->last_kernel, sizeof(p->last_kernel), p->quad_nt == 8 ? (loop ? "ik_quad_kernel_loop" : "ik_quad_kernel")
-                                                     : (p->quad_nt == 32 ? "ik_quad_kernel_32" : (loop ? "ik_quad_kernel_16_loop" : "ik_quad_kernel_16")));
+                                                     : (p->quad_nt == 32 ? (loop ? "ik_quad_kernel_32_loop" : "ik_quad_kernel_32")
+                                                                         : (loop ? "ik_quad_kernel_16_loop" : "ik_quad_kernel_16")));
     SolveArgs aq = a;
     HIP_OK(clk_begin(p, aq, stream));
     p->last_lds = mkh::launch_quad(p->quad_nt, loop, grid, stream, p->d_lane, p->lane_dims, aq);

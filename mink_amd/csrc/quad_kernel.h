@@ -40,10 +40,13 @@ namespace mkh {
 // from lane i is taken from `ua` = (own u on row 0, the other row's u on row 1) for i < 16 and from `ub` (the other way round) for
 // i ≥ 16: one ds_swizzle exchange of the rows (lane ⊕ 16) per broadcast vector, then 16 + 16 `row_newbcast` FMAs.
 constexpr int kQuadTaskDoubles = 28;                          // per frame task: A1 (9), A2 (9), frame position (3), W·e (6), μ
-// poses [component][link], ancestors, task blocks; two-row build: + m·com of every link and the subtree centres of mass (ComTask)
-__host__ __device__ constexpr int quad_row_doubles(int lp) { return 7 * lp + lp / 2 + kLaneMaxFrames * kQuadTaskDoubles + (lp == 32 ? 6 * lp : 0); }
+// poses [component][link], ancestors, task blocks; two-row build: + m·com of every link and the subtree centres of mass (ComTask),
+// and in its fused loop the floating base's quaternion carried from step to step (w, x, y, z)
+__host__ __device__ constexpr int quad_row_doubles(int lp, bool loop = false) {
+  return 7 * lp + lp / 2 + kLaneMaxFrames * kQuadTaskDoubles + (lp == 32 ? 6 * lp : 0) + (lp == 32 && loop ? 4 : 0);
+}
 static_assert(kLaneMaxLinks <= 16 && kLaneDescDofs <= 16 && kLaneMaxLinks2 <= 32 && kLaneDescDofs2 <= 32, "a problem must fit one / two DPP rows");
-__host__ __device__ inline int quad_lds_bytes(int lp = 16) { return (kWave / lp) * quad_row_doubles(lp) * (int)sizeof(double); }
+__host__ __device__ inline int quad_lds_bytes(int lp = 16, bool loop = false) { return (kWave / lp) * quad_row_doubles(lp, loop) * (int)sizeof(double); }
 
 // ---------------------------------------------------------------- DPP row primitives (all 64 lanes must be active)
 // s_nop 4: a DPP operand must not be read within 5 wait states of an EXEC write (and 2 of a VALU write of that register)
@@ -233,12 +236,22 @@ __device__ __forceinline__ bool quad_pivot(double (&T)[NT], double& cc, const in
 
 // LOOP: the fused caller loop (mkh_solve_steps / mkh_solve_until; lane_kernel.h, same semantics): every ROW iterates
 // (solve, q ← q + Δq) on its own problem until its frame tasks are within the thresholds or the budget is spent; rows
-// that are finished idle through the remaining iterations of their wavefront (masked commits).
-// NT: column registers per lane = the largest nv the instantiation takes (8: arms; 16: hands, mobile arms).
+// that are finished idle through the remaining iterations of their wavefront (masked commits).  On two rows the loop also
+// integrates a floating base: the free joint's quaternion is a per-problem state in the row's LDS slice, read from q once and
+// advanced by mju_quatIntegrate with the Δq of its three rotational dofs (the wavefront kernel's arithmetic, ik_kernel.h).
+// NT: column registers per lane = the largest nv the instantiation takes (8: arms; 16: hands, mobile arms; 32: two rows).
+// The two-row loop build runs at two waves per SIMD, spill-free in 256 VGPRs.  Capped at three (the single-solve build's 163 of 168)
+// it spills: 97 VGPRs (20 with MachineLICM off; kernel resource remarks).  MKH_QUAD2_LOOP_WAVES=3 builds that variant
+// for a same-box A/B (tools/bench_two_row_loop.py, profiles/r07_two_row_loop.txt).
+#ifndef MKH_QUAD2_LOOP_WAVES
+#define MKH_QUAD2_LOOP_WAVES 2
+#endif
 template <int NT, bool LOOP, int LP = 16>
-__global__ __launch_bounds__(64) void ik_quad_kernel(const LaneProblemT<LP, LP>* __restrict__ Pg, const LaneDims D, const SolveArgs A) {
-  static_assert((LP == 16 && NT <= 16) || (LP == 32 && NT == 32 && !LOOP), "one DPP row: ≤ 16 column registers; two rows: 32, single solves");
-  constexpr int kQuadRow = LP, kQuadPerWave = kWave / LP, kQuadPoseDoubles = 7 * LP, kQuadAncDoubles = LP / 2, kQuadRowDoubles = quad_row_doubles(LP);
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LOOP && LP == 32 ? MKH_QUAD2_LOOP_WAVES : 1)))
+void ik_quad_kernel(const LaneProblemT<LP, LP>* __restrict__ Pg, const LaneDims D, const SolveArgs A) {
+  static_assert((LP == 16 && NT <= 16) || (LP == 32 && NT == 32), "one DPP row: ≤ 16 column registers; two rows: 32");
+  constexpr int kQuadRow = LP, kQuadPerWave = kWave / LP, kQuadPoseDoubles = 7 * LP, kQuadAncDoubles = LP / 2, kQuadRowDoubles = quad_row_doubles(LP, LOOP);
+  constexpr bool kBase = LOOP && LP == 32;           // fused loop on two rows: a floating base's quaternion is carried in LDS
   constexpr unsigned long long kRowBits = LP == 32 ? 0xffffffffull : 0xffffull;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const LaneProblemT<LP, LP>& P = *Pg;
@@ -279,14 +292,28 @@ __global__ __launch_bounds__(64) void ik_quad_kernel(const LaneProblemT<LP, LP>*
 #pragma unroll
   for (int t = 0; t < kMaxPostureTasks; ++t) {
     ptq[t] = 0.0; pcost[t] = 0.0;
-    if (t < D.n_posture) {
+    if (!kBase && t < D.n_posture) {                 // (two-row loop: read every step, below)
       const double* tq = A.posture_target + (A.posture_batched ? ((size_t)pb * D.n_posture + t) * nq : (size_t)t * nq);
       ptq[t] = tq[qadr];
       pcost[t] = dv ? P.posture_cost[t][ld] : 0.0;
     }
   }
   const double* const tgp = A.frame_targets + ((size_t)pb * nf + (l < nf ? l : 0)) * 7;
-  const SE3 Tt{Q4{tgp[0], tgp[1], tgp[2], tgp[3]}, V3{tgp[4], tgp[5], tgp[6]}};
+  SE3 Tt{Q4{tgp[0], tgp[1], tgp[2], tgp[3]}, V3{tgp[4], tgp[5], tgp[6]}};
+  // (fused loop on two rows: the free joint's quaternion, w x y z — the link lane of its rotation loads it from q here and is the
+  //  only lane that touches it afterwards; mj_integratePos advances it below, q is not read again)
+  double* const sQb = S + quad_row_doubles(LP);
+  unsigned long long rot_m = 0, ball_m = 0;          // lanes: the free joint's rotational dofs / the link of its rotation (SGPRs)
+  if constexpr (kBase) {
+    const LaneLink& Lk = P.link[l < nlink ? l : 0];
+    const int dl0 = dv ? P.dof_link[ld] : -1;
+    rot_m = __ballot(dl0 >= 0 && P.link[dl0 >= 0 ? dl0 : 0].jtype == JNT_BALL);
+    ball_m = __ballot(l < nlink && Lk.jtype == JNT_BALL);
+    if (l < nlink && Lk.jtype == JNT_BALL) {
+      const double* qq = A.q + (size_t)pb * nq + Lk.qadr;
+      sQb[0] = qq[0]; sQb[1] = qq[1]; sQb[2] = qq[2]; sQb[3] = qq[3];
+    }
+  }
   const bool until = LOOP && A.pos_threshold >= 0.0;
   const int n_steps = LOOP ? A.n_steps : 1;
   bool fin = false;                                  // this row's loop is over (converged / failed / budget spent)
@@ -295,6 +322,24 @@ __global__ __launch_bounds__(64) void ik_quad_kernel(const LaneProblemT<LP, LP>*
   int st = 1;                                        // QP partition: 0 free, 1 at lower, 2 at upper (padded lanes: bound at 0, never flip)
   for (int step = 0; step < n_steps + (until ? 1 : 0); ++step) {
   if (LOOP && !__ballot(!fin)) break;
+  // (two-row loop: the descriptor and the per-call inputs are read again every step — hoisted out of the loop, they stayed in
+  //  registers across the QP: 52 spilled VGPRs at two waves per SIMD; the empty asm keeps the compiler from hoisting them)
+  const LaneProblemT<LP, LP>* Pl = Pg;
+  if constexpr (kBase) {
+    const double *ptg = A.posture_target, *ftg = A.frame_targets;
+    asm volatile("" : "+s"(Pl), "+s"(ptg), "+s"(ftg));
+#pragma unroll
+    for (int t = 0; t < kMaxPostureTasks; ++t) {
+      ptq[t] = 0.0; pcost[t] = 0.0;
+      if (t < D.n_posture) {
+        ptq[t] = ptg[(A.posture_batched ? ((size_t)pb * D.n_posture + t) * nq : (size_t)t * nq) + qadr];
+        pcost[t] = dv ? Pl->posture_cost[t][ld] : 0.0;
+      }
+    }
+    const double* const tg = ftg + ((size_t)pb * nf + (l < nf ? l : 0)) * 7;
+    Tt = SE3{Q4{tg[0], tg[1], tg[2], tg[3]}, V3{tg[4], tg[5], tg[6]}};
+  }
+  const LaneProblemT<LP, LP>& P = *Pl;
   status = 0;
   // Configuration.check_limits (mink/configuration.py:77-110), tol = 1e-6
   if (row_mask(dv && (qd < P.range_lo[ld] - 1e-6 || qd > P.range_hi[ld] + 1e-6))) status |= 1;
@@ -345,8 +390,12 @@ __global__ __launch_bounds__(64) void ik_quad_kernel(const LaneProblemT<LP, LP>*
     Q4 xq{L.quat[0], L.quat[1], L.quat[2], L.quat[3]};
     if (LP == 32 && jt == JNT_BALL) {
       // the rotation of a free joint: the body's orientation is the (normalised) quaternion of q (mj_kinematics)
-      const double* qq = A.q + (size_t)pb * nq + L.qadr;
-      xq = Q4{qq[0], qq[1], qq[2], qq[3]};
+      if constexpr (kBase) {
+        xq = Q4{sQb[0], sQb[1], sQb[2], sQb[3]};
+      } else {
+        const double* qq = A.q + (size_t)pb * nq + L.qadr;
+        xq = Q4{qq[0], qq[1], qq[2], qq[3]};
+      }
     } else if (jt >= 0) {
       const V3 ax{L.axis[0], L.axis[1], L.axis[2]};
       if (jt == JNT_SLIDE) {
@@ -690,13 +739,31 @@ __global__ __launch_bounds__(64) void ik_quad_kernel(const LaneProblemT<LP, LP>*
   if (!done) status |= 8;
   if (!LOOP && A.warm != nullptr && live && dv) A.warm[(size_t)pb * nv + l] = (int8_t)((status & 14) ? 0 : st);
   if (!LOOP) { status_all = status; break; }
+  // floating base: ω = the Δq of the free joint's rotational dofs (lanes dof … dof + 2 of its rotation's link), fetched with every
+  // lane active; those three lanes hold no coordinate of their own (their q entries are the quaternion's x, y, z)
+  V3 wb{0.0, 0.0, 0.0};
+  const bool rot = kBase && ((rot_m >> lane) & 1) != 0, ball = kBase && ((ball_m >> lane) & 1) != 0;
+  if constexpr (kBase) {
+    const int src = rbase + (ball ? P.link[l].dof : 0);
+    wb = V3{bperm_f64(x, src), bperm_f64(x, src + 1), bperm_f64(x, src + 2)};
+  }
   if (!fin) {                                        // commit this iteration
     status_all |= status;
     if (status & 14) {
       fin = true;                                    // an instance stops at the first step whose QP fails
     } else {
-      vlast = x / A.dt;
-      qd += x;                                       // mj_integratePos for hinge / slide joints (configuration.py:228-236)
+      if constexpr (kBase) { if (live && dv) A.v_out[(size_t)pb * nv + l] = x / A.dt; }    // (v of every step: no register for it)
+      else vlast = x / A.dt;
+      if (!rot) qd += x;                             // mj_integratePos for hinge / slide joints (configuration.py:228-236)
+      if (ball) {
+        // ... and for the free joint's rotation: mju_quatIntegrate, q ← normalize(q) ⊗ axisangle(ω̂, |ω|) (ik_kernel.h, the same
+        // arithmetic; its three translations are world-frame slide links: q += Δq above)
+        const double n = sqrt(dot(wb, wb));
+        const V3 ax = (n < 1e-15) ? V3{1.0, 0.0, 0.0} : (1.0 / n) * wb;
+        const Q4 qr = (n == 0.0) ? Q4{1, 0, 0, 0} : axis_angle(ax, n);
+        const Q4 r = qmul(qnormalize(Q4{sQb[0], sQb[1], sQb[2], sQb[3]}), qr);
+        sQb[0] = r.w; sQb[1] = r.x; sQb[2] = r.y; sQb[3] = r.z;
+      }
       if (!until) { it_done = step + 1; fin = step + 1 == n_steps; }
     }
   }
@@ -714,8 +781,14 @@ __global__ __launch_bounds__(64) void ik_quad_kernel(const LaneProblemT<LP, LP>*
   if (live) {
     if (dv) {
       const double vd = LOOP ? vlast : x / A.dt;                                              // v = Δq / dt (solve_ik.py:104)
-      A.v_out[(size_t)pb * nv + l] = (status_all & 14) ? __builtin_nan("") : vd;
-      if (LOOP && A.q_out) A.q_out[(size_t)pb * nq + qadr] = qd;
+      if (!kBase || (status_all & 14)) A.v_out[(size_t)pb * nv + l] = (status_all & 14) ? __builtin_nan("") : vd;
+      if (LOOP && A.q_out && !(kBase && ((rot_m >> lane) & 1))) A.q_out[(size_t)pb * nq + qadr] = qd;
+    }
+    if constexpr (kBase) {
+      if (A.q_out && ((ball_m >> lane) & 1)) {                      // the quaternion: from the carried state
+        double* qo = A.q_out + (size_t)pb * nq + P.link[l].qadr;
+        qo[0] = sQb[0]; qo[1] = sQb[1]; qo[2] = sQb[2]; qo[3] = sQb[3];
+      }
     }
     if (l == 0) {
       if (A.status_out) A.status_out[pb] = status_all;

@@ -304,7 +304,11 @@ def solve_ik_steps(configuration: Configuration, tasks: Sequence, dt: float, n_s
 
     With `pos_threshold` / `ori_threshold` the loop is the callers' real one — it breaks, per instance, as soon as
     every frame task's error is within the thresholds after the integration (arm_ur5e_actuators.py:93-97), `n_steps`
-    is max_iters — and the return value is (q_final, v_last, iters, converged)."""
+    is max_iters — and the return value is (q_final, v_last, iters, converged).
+
+    Robots of 17 … 32 dofs or links loop on the row kernel's two-row build, floating base included, where that measured faster
+    than the wavefront kernel's loop (a ComTask or RelativeFrameTask, or no floating base), and where every free
+    joint is on a task chain."""
     until = None
     if pos_threshold is not None or ori_threshold is not None:
         until = (float(pos_threshold if pos_threshold is not None else np.inf),
