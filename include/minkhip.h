@@ -47,7 +47,9 @@ extern "C" {
  * no longer report MKH_ST_ROW_OVERFLOW below 448 rows per instance (the flagged instances run again with every row).
  * 108 (round 6): + mkh_problem_create_diag and the MKH_DIAG_* bits (per-handle parity / measurement switches that used to be
  * MKH_DEBUG_* environment variables: the product library no longer reads its environment); MKH_ST_DEGENERATE documented.  No
- * struct and no existing signature changed. */
+ * struct and no existing signature changed.
+ * Still 108: + mkh_solve_multistart and MkhMultistartIO (many starts per target, the best solution picked on the device).
+ * Purely additive — no struct, signature, kernel or result of an existing entry point changed — so the number stays. */
 #define MKH_VERSION 108
 
 /* return codes */
@@ -382,6 +384,65 @@ int32_t mkh_solve_until(MkhProblem *problem, int32_t B, const double *q, const d
                         int32_t max_iters, double pos_threshold, double ori_threshold, double *q_out, double *v_out,
                         int32_t *status_out, int32_t *iters_out, int32_t *converged_out, int32_t flags,
                         void *hip_stream);
+
+/*
+ * Multi-start IK: the loop of mkh_solve_until from n_seeds = S starts per target, the best solution picked on the device —
+ * one call, no B·S rows over the bus.  No counterpart in the reference: it is what a caller writes around a local method
+ * with box limits (which stops at a joint limit or a singularity for a good share of far targets) — draw starts, repeat the
+ * targets, run the loop, keep the converged result closest to a reference posture.
+ *
+ * Instance layout: instance i = b·S + s (the seeds of a target are contiguous).  SEED 0 OF EVERY TARGET IS THE CALLER'S OWN
+ * q[b], bit for bit: the result is never worse than mkh_solve_until from q.  The problem needs max_batch >= B·S.
+ *
+ * Random numbers.  u(rng_seed, t, s, k) in [0, 1) is a pure function of the call's rng_seed, the GLOBAL target index
+ * t = target_index0 + b, the seed index s and a draw index k — no state, no dependence on launch shape, chunking or sharding
+ * (a caller that splits its targets passes the offset of row 0 as target_index0).  With 64-bit wrapping arithmetic and
+ *   mix(z):  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)
+ *   G = 0x9E3779B97F4A7C15
+ *   h = mix(rng_seed + G);  h = mix((h ^ t) + G);  h = mix((h ^ ((s << 32) | k)) + G);  u = (h >> 11) * 2^-53
+ * (the splitmix64 finaliser, three times; the top 53 bits make the double).
+ *
+ * Seeding rule for s >= 1, per joint (qa = jnt_qposadr; every sum below is a rounded product followed by a rounded sum, never
+ * a fused multiply-add, so a restatement in numpy reproduces hinge / slide entries bit for bit):
+ *   limited hinge / slide   range_lo + (range_hi - range_lo) * u(.., k = qa)
+ *   unlimited hinge         (q[b][qa] - pi) + (2 pi) * u(.., k = qa)
+ *   unlimited slide, free   the caller's value (a loose object or a floating base is not thrown around)
+ *   ball                    z = 2 u1 - 1, r = sqrt(1 - z z), phi = (2 pi) u2, half = 0.5 (theta_max u3) with u1, u2, u3 =
+ *                           u(.., k = qa), u(.., qa + 1), u(.., qa + 2) and theta_max = range[1] when limited, else pi:
+ *                           quaternion (cos half, (r cos phi) sin half, (r sin phi) sin half, z sin half)
+ * With io->seeds the caller's (B, S, nq) starts are used instead (row 0 of every target is still replaced by q[b]).
+ *
+ * Selection, per target: among the seeds whose loop converged with no failure bit (status & ~MKH_ST_OUTSIDE_LIMITS == 0) the one
+ * with the smallest d = sum_k w_k ((q_s (-) q_ref)_k)^2, (-) = mj_differentiatePos at dt = 1 (the tangent-space difference),
+ * q_ref = io->q_ref[b] or the caller's q[b], w = io->weights or ones; ties go to the lowest seed index.  If no seed converged the
+ * result is seed 0's — what mkh_solve_until returns from q — with converged = 0.  A QP failure of one seed discards that seed;
+ * it is not an error of the call.
+ *
+ * Pointers in MkhMultistartIO follow the call's convention (device pointers with MKH_FLAG_DEVICE_PTRS, else host); outputs must
+ * not alias inputs or each other.  The per-target outputs are required, everything else may be NULL.
+ */
+typedef struct MkhMultistartIO {
+  const double *seeds;      /* (B, S, nq) caller-defined starts, or NULL: drawn by the rule above                     */
+  const double *q_ref;      /* (B, nq) reference posture of the selection, or NULL: q                                 */
+  const double *weights;    /* (nv,) weights of the selection, or NULL: ones                                          */
+  double *q_best;           /* (B, nq)  final configuration of the chosen seed                                        */
+  double *v_best;           /* (B, nv)  its last velocity                                                             */
+  int32_t *iters;           /* (B,)     its iteration count                                                           */
+  int32_t *status;          /* (B,)     its MKH_ST_* bits                                                             */
+  int32_t *converged;       /* (B,)     1 when a seed converged without a failure bit                                 */
+  int32_t *seed_index;      /* (B,)     the chosen s (0 when nothing converged)                                       */
+  int32_t *n_converged;     /* (B,)     how many of the S seeds converged without a failure bit                       */
+  double *q_all;            /* (B*S, nq) optional: every instance's final configuration                               */
+  int32_t *converged_all;   /* (B*S,)    optional: the loop's converged flag per instance                             */
+  int32_t *iters_all;       /* (B*S,)    optional                                                                     */
+  int32_t *status_all;      /* (B*S,)    optional                                                                     */
+  double *seeds_out;        /* (B*S, nq) optional: the starts the loop ran from                                       */
+} MkhMultistartIO;
+int32_t mkh_solve_multistart(MkhProblem *problem, int32_t B, const double *q, const double *frame_targets,
+                             const double *posture_target, const double *com_target, double dt, double damping,
+                             int32_t max_iters, double pos_threshold, double ori_threshold, int32_t n_seeds,
+                             uint64_t rng_seed, int64_t target_index0, const MkhMultistartIO *io, int32_t flags,
+                             void *hip_stream);
 
 /* Same inputs; additionally writes the requested intermediates (build_ik / compute_error /
  * compute_jacobian / get_transform_frame_to_world parity taps).  v_out/status_out may be NULL

@@ -12,7 +12,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import threading
-from typing import Dict, Optional, Sequence
+from typing import Dict, NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -125,6 +125,31 @@ class MkhProblemDesc(C.Structure):
     ]
 
 
+MULTISTART_IO_FIELDS = ("seeds", "q_ref", "weights", "q_best", "v_best", "iters", "status", "converged", "seed_index",
+                        "n_converged", "q_all", "converged_all", "iters_all", "status_all", "seeds_out")
+
+
+class MkhMultistartIO(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in MULTISTART_IO_FIELDS]
+
+
+class MultistartOut(NamedTuple):
+    """What NativeProblem.solve_multistart returns (arrays of the caller's kind: numpy or torch).  The *_all fields and
+    `seeds` are None unless asked for with return_all."""
+    q: object
+    v: object
+    converged: object
+    seed_index: object
+    n_converged: object
+    iters: object
+    status: object
+    q_all: object = None
+    converged_all: object = None
+    iters_all: object = None
+    status_all: object = None
+    seeds: object = None
+
+
 TAP_NAMES = ("xpos", "xquat", "frame_pose", "subtree_com", "task_e", "task_J", "H", "c", "box_lo",
              "box_hi", "coll_G", "coll_h", "qp_iters", "cycles")
 
@@ -178,6 +203,9 @@ def lib() -> C.CDLL:
     L.mkh_eval.argtypes = common + [C.POINTER(MkhTaps), C.c_int32, C.c_void_p]
     L.mkh_solve_until.argtypes = common[:8] + [C.c_int32, C.c_double, C.c_double] + [C.c_void_p] * 5 + [C.c_int32, C.c_void_p]
     L.mkh_solve_until.restype = C.c_int32
+    L.mkh_solve_multistart.argtypes = common[:8] + [C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_uint64, C.c_int64,
+                                                    C.POINTER(MkhMultistartIO), C.c_int32, C.c_void_p]
+    L.mkh_solve_multistart.restype = C.c_int32
     L.mkh_solve_dense.argtypes = common[:6] + [C.POINTER(MkhDenseRows), C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                                C.POINTER(MkhTaps), C.c_int32, C.c_void_p]
     L.mkh_solve_dense.restype = C.c_int32
@@ -202,7 +230,7 @@ EXPORTED_SYMBOLS = (
     "mkh_problem_create", "mkh_problem_destroy", "mkh_problem_num_task_rows",
     "mkh_problem_num_collision_pairs", "mkh_solve", "mkh_eval", "mkh_integrate", "mkh_problem_launch_info",
     "mkh_solve_steps", "mkh_problem_last_kernel", "mkh_lie_eval", "mkh_solve_dense", "mkh_solve_until",
-    "mkh_geom_distance_eval", "mkh_problem_create_diag",
+    "mkh_geom_distance_eval", "mkh_problem_create_diag", "mkh_solve_multistart",
 )
 
 LIE_OPS = {"se3_log": (0, 7, 0, (6,)), "se3_jlog": (1, 7, 0, (6, 6)), "se3_ljacinv": (2, 6, 0, (6, 6)),
@@ -588,3 +616,101 @@ class NativeProblem:
             return v, st, tapbufs
         _check(lib().mkh_solve(*args, flags, stream))
         return v, st
+
+    # ------------------------------------------------------------ multi-start
+    def solve_multistart(self, q, frame_targets=None, posture_target=None, com_target=None, dt: float = 1e-2,
+                         damping: float = 1e-12, *, n_seeds: int, max_iters: int, pos_threshold: float, ori_threshold: float,
+                         rng_seed: int = 0, target_index0: int = 0, seeds=None, reference=None, weights=None,
+                         return_all: bool = False, wave_kernel: bool = False, lane_kernel: bool = False,
+                         quad_kernel: bool = False) -> MultistartOut:
+        """mkh_solve_multistart: the threshold-terminated loop from `n_seeds` starts per row of q (seed 0 = the row itself, the
+        others drawn on the device or taken from `seeds` (B, S, nq)), the converged result closest to `reference` (default q)
+        picked on the device.  numpy in → numpy out (synchronous); torch CUDA tensors in → torch tensors out, asynchronous on
+        the current stream, no host copy.  The handle needs max_batch >= B·n_seeds."""
+        with self._lock:
+            return self._solve_multistart(q, frame_targets, posture_target, com_target, dt, damping, int(n_seeds), int(max_iters),
+                                          float(pos_threshold), float(ori_threshold), int(rng_seed), int(target_index0), seeds,
+                                          reference, weights, return_all, wave_kernel, lane_kernel, quad_kernel)
+
+    def _solve_multistart(self, q, frame_targets, posture_target, com_target, dt, damping, S, max_iters, pos_thr, ori_thr,
+                          rng_seed, target_index0, seeds, reference, weights, return_all, wave_kernel, lane_kernel, quad_kernel):
+        m = self.nmodel.model
+        use_torch = _is_torch(q)
+        B = int(q.shape[0])
+        if S < 1:
+            raise ValueError("n_seeds must be >= 1")
+        if max_iters < 1:
+            raise ValueError("max_iters must be >= 1")
+        if B * S > self.max_batch:
+            raise MinkHipError(f"B*n_seeds={B * S} exceeds max_batch={self.max_batch} of this problem")
+        if self.n_dense_rows or self.n_dense_limit_rows or self.dense_limit_box:
+            raise ValueError("dense (plugin) rows are evaluated by the caller at q: no fused loop, no multi-start")
+        flags = (FLAG_WAVE_KERNEL if wave_kernel else 0) | (FLAG_LANE_KERNEL if lane_kernel else 0) | \
+            (FLAG_QUAD_KERNEL if quad_kernel else 0)
+        if use_torch:
+            import torch
+            dev = q.device
+
+            def prep(x):
+                if x is None or (x.dtype is torch.float64 and x.device == dev and x.is_contiguous()):
+                    return x
+                return torch.as_tensor(x).to(device=dev, dtype=torch.float64).contiguous()
+
+            def empty(shape, dtype):
+                return torch.empty(shape, dtype=torch.float64 if dtype is np.float64 else torch.int32, device=dev)
+
+            ptr = lambda x: None if x is None else x.data_ptr()
+            flags |= FLAG_DEVICE_PTRS
+            stream = _raw_stream(torch, dev)
+        else:
+            prep = lambda x: None if x is None else _f64(x)
+            empty = lambda shape, dtype: np.empty(shape, dtype=dtype)
+            ptr = lambda x: None if x is None else x.ctypes.data
+            stream = None
+        q, frame_targets, posture_target, com_target = prep(q), prep(frame_targets), prep(posture_target), prep(com_target)
+        seeds, reference, weights = prep(seeds), prep(reference), prep(weights)
+        if tuple(q.shape) != (B, m.nq):
+            raise ValueError(f"q must have shape (B, {m.nq}), got {tuple(q.shape)}")
+        if not self.n_frame:
+            raise ValueError("multi-start needs at least one frame task to test the thresholds on")
+        if frame_targets is None or tuple(frame_targets.shape) != (B, self.n_frame, 7):
+            raise ValueError(f"frame_targets must have shape ({B}, {self.n_frame}, 7)")
+        if self.n_posture:
+            if posture_target is None:
+                raise ValueError("posture_target is required")
+            if tuple(posture_target.shape) == (B, self.n_posture, m.nq):
+                flags |= FLAG_POSTURE_BATCHED
+            elif tuple(posture_target.shape) != (self.n_posture, m.nq):
+                raise ValueError(f"posture_target must have shape ({self.n_posture}, {m.nq}) or (B, ...)")
+        if self.n_com:
+            if com_target is None:
+                raise ValueError("com_target is required")
+            if tuple(com_target.shape) == (B, self.n_com, 3):
+                flags |= FLAG_COM_BATCHED
+            elif tuple(com_target.shape) != (self.n_com, 3):
+                raise ValueError(f"com_target must have shape ({self.n_com}, 3) or (B, ...)")
+        if seeds is not None and tuple(seeds.shape) != (B, S, m.nq):
+            raise ValueError(f"seeds must have shape ({B}, {S}, {m.nq}), got {tuple(seeds.shape)}")
+        if reference is not None and tuple(reference.shape) != (B, m.nq):
+            raise ValueError(f"reference must have shape ({B}, {m.nq}), got {tuple(reference.shape)}")
+        if weights is not None and tuple(weights.shape) != (m.nv,):
+            raise ValueError(f"weights must have shape ({m.nv},), got {tuple(weights.shape)}")
+        f, i = np.float64, np.int32
+        out = {"q_best": empty((B, m.nq), f), "v_best": empty((B, m.nv), f), "iters": empty((B,), i), "status": empty((B,), i),
+               "converged": empty((B,), i), "seed_index": empty((B,), i), "n_converged": empty((B,), i)}
+        if return_all:
+            out.update({"q_all": empty((B * S, m.nq), f), "converged_all": empty((B * S,), i), "iters_all": empty((B * S,), i),
+                        "status_all": empty((B * S,), i), "seeds_out": empty((B * S, m.nq), f)})
+        io = MkhMultistartIO()
+        io.seeds, io.q_ref, io.weights = ptr(seeds), ptr(reference), ptr(weights)
+        for n, x in out.items():
+            setattr(io, n, ptr(x))
+        _check(lib().mkh_solve_multistart(self.handle, B, ptr(q), ptr(frame_targets), ptr(posture_target), ptr(com_target),
+                                          float(dt), float(damping), max_iters, pos_thr, ori_thr, S, rng_seed & (2 ** 64 - 1),
+                                          target_index0, C.byref(io), flags, stream))
+        extra = ()
+        if return_all:
+            extra = (out["q_all"].reshape(B, S, m.nq), out["converged_all"].reshape(B, S), out["iters_all"].reshape(B, S),
+                     out["status_all"].reshape(B, S), out["seeds_out"].reshape(B, S, m.nq))
+        return MultistartOut(out["q_best"], out["v_best"], out["converged"], out["seed_index"], out["n_converged"],
+                             out["iters"], out["status"], *extra)

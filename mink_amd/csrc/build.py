@@ -368,6 +368,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     jobs.append((os.path.join(HERE, "lane_variants.hip"), os.path.join(BUILD, "lane_variants.o")))
     jobs.append((os.path.join(HERE, "wide_variants.hip"), os.path.join(BUILD, "wide_variants.o")))
     jobs.append((os.path.join(HERE, "convex_pre.hip"), os.path.join(BUILD, "convex_pre.o")))
+    jobs.append((os.path.join(HERE, "multistart.hip"), os.path.join(BUILD, "multistart.o")))   # seeding / fan-out / selection of mkh_solve_multistart
 
     def compile_one(job):
         src, obj = job

@@ -83,6 +83,23 @@ struct PinnedScratch {
   void release() { if (host) (void)hipHostFree(host); host = dev = nullptr; }
 };
 
+// A device buffer of mkh_solve_multistart's workspace: grown to what a call needs (never beyond what max_batch allows),
+// kept for the next call.
+struct GrowBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  hipError_t need(size_t bytes) {
+    if (bytes <= cap && p) return hipSuccess;
+    (void)hipFree(p); p = nullptr; cap = 0;
+    const hipError_t e = hipMalloc(&p, bytes ? bytes : 8);
+    if (e == hipSuccess) cap = bytes; else p = nullptr;
+    return e;
+  }
+  void release() { (void)hipFree(p); p = nullptr; cap = 0; }
+  double* f64() const { return (double*)p; }
+  int32_t* i32() const { return (int32_t*)p; }
+};
+
 struct MkhModel {
   int device = 0;
   PinnedScratch small;             // mkh_integrate, host pointers
@@ -188,6 +205,12 @@ struct MkhProblem {
   int32_t* s_iters = nullptr;      // [2][max_batch]: iterations, converged (mkh_solve_until, host-pointer calls)
   size_t s_pt_cap = 0, s_ct_cap = 0;
   double *s_de = nullptr, *s_dJ = nullptr, *s_dG = nullptr, *s_dh = nullptr, *s_dbox = nullptr;   // dense (plugin) rows
+  // mkh_solve_multistart: the seeding / joint tables (built at the first call) and the workspace of the B·S instances
+  // (seeds → loop results in place, replicated targets, per-instance loop outputs), plus the staging of host-pointer calls
+  bool ms_tables = false;
+  GrowBuf ms_seed_i, ms_seed_f, ms_jnt;
+  GrowBuf ms_q, ms_seeds, ms_ft, ms_pt, ms_ct, ms_v, ms_i32;                   // B·S rows (ms_i32: status | iters | converged)
+  GrowBuf ms_in_q, ms_in_ft, ms_in_pt, ms_in_ct, ms_in_ref, ms_in_w, ms_out_q, ms_out_v, ms_out_i32;   // B rows
 };
 
 // Kernel variants live in their own translation units (mink_amd/csrc/build.py generates one
@@ -200,6 +223,14 @@ int launch_lane(int nv_max, bool loop, int grid, int lds_bytes, hipStream_t stre
 int launch_quad(int nt, bool loop, int grid, hipStream_t stream, const void* P, const LaneDims& dims, const SolveArgs& a);   // returns its LDS bytes per wavefront
 int launch_wide(int grid, int lds_bytes, hipStream_t stream, const WideProblem* P, const SolveArgs& a, const TapArgs* taps, bool convex);
 int launch_convex_pre(hipStream_t stream, const WideProblem* P, const CvPre& C, int B, const double* q, double* out);
+// multi-start IK (multistart.hip): seeding, target fan-out, selection — the kernels around the loop of mkh_solve_multistart
+hipError_t launch_ms_seed(hipStream_t stream, const int32_t* seed_i, const double* seed_f, int B, int S, int nq, const double* q,
+                          const double* user_seeds, unsigned long long rng_seed, long long target_index0, double* q_seeds);
+hipError_t launch_ms_fanout(hipStream_t stream, const double* src, double* dst, int B, int S, int width);
+hipError_t launch_ms_select(hipStream_t stream, int B, int S, int nq, int nv, int njnt, const int32_t* jnt, const double* q_all,
+                            const double* v_all, const int32_t* status_all, const int32_t* iters_all, const int32_t* converged_all,
+                            const double* q_ref, const double* weights, double* q_best, double* v_best, int32_t* iters,
+                            int32_t* status, int32_t* converged, int32_t* seed_index, int32_t* n_converged);
 constexpr int kLaneMinBatchLoop = 28672;  // fused loops of a small arm: row kernel below, lane kernel from here (M targets/s at 16 384: 39.7 vs 24.1, at 32 768: 42.4 vs 48.2)
 constexpr int kLaneMinBatch = 73728;  // plain solves of a small arm: row kernel below, lane kernel from here (launch())
 }
@@ -1449,6 +1480,10 @@ void mkh_problem_destroy(MkhProblem* p) {
   for (void* w : p->wide_allocs) (void)hipFree(w);
   (void)hipFree(p->d_wide);
   (void)hipFree(p->s_q); (void)hipFree(p->s_ft); (void)hipFree(p->s_pt); (void)hipFree(p->s_ct); (void)hipFree(p->s_v); (void)hipFree(p->s_status);
+  for (GrowBuf* g : {&p->ms_seed_i, &p->ms_seed_f, &p->ms_jnt, &p->ms_q, &p->ms_seeds, &p->ms_ft, &p->ms_pt, &p->ms_ct, &p->ms_v,
+                     &p->ms_i32, &p->ms_in_q, &p->ms_in_ft, &p->ms_in_pt, &p->ms_in_ct, &p->ms_in_ref, &p->ms_in_w, &p->ms_out_q,
+                     &p->ms_out_v, &p->ms_out_i32})
+    g->release();
   p->small.release();
   if (p->st_in) (void)hipStreamDestroy(p->st_in);
   if (p->st_out) (void)hipStreamDestroy(p->st_out);
@@ -2122,6 +2157,159 @@ int32_t mkh_solve_until(MkhProblem* p, int32_t B, const double* q, const double*
   if (!(pos_threshold >= 0.0) || !(ori_threshold >= 0.0)) return fail(MKH_E_INVALID, "thresholds must be >= 0");
   return run(p, B, q, frame_targets, posture_target, com_target, dt, damping, v_out, status_out, nullptr, flags,
              hip_stream, max_iters, q_out, nullptr, pos_threshold, ori_threshold, iters_out, converged_out);
+}
+
+}  // extern "C"
+
+// The per-qpos-address seeding table and the joint list of the selection's tangent-space difference (multistart.hip).
+static int32_t ms_build_tables(MkhProblem* p) {
+  if (p->ms_tables) return MKH_OK;
+  const MkhModel* m = p->model;
+  const int nq = m->nq, njnt = m->njnt;
+  std::vector<int32_t> si(3 * (size_t)nq, 0), jn(3 * (size_t)njnt, 0);
+  std::vector<double> sf(2 * (size_t)nq, 0.0);
+  for (int j = 0; j < njnt; ++j) {
+    const int jt = m->jnt_type[j], qa = m->jnt_qposadr[j];
+    jn[3 * j] = jt; jn[3 * j + 1] = qa; jn[3 * j + 2] = m->jnt_dofadr[j];
+    const bool limited = m->jnt_limited[j] != 0;
+    const double lo = m->jnt_range[2 * j], hi = m->jnt_range[2 * j + 1];
+    if (jt == 2 || jt == 3) {                          // slide / hinge
+      si[3 * qa + 2] = qa;
+      if (limited) { si[3 * qa] = 1; sf[2 * qa] = lo; sf[2 * qa + 1] = hi - lo; }
+      else if (jt == 3) si[3 * qa] = 2;                // unlimited hinge: around the caller's value (unlimited slide: kept)
+    } else if (jt == 1) {                              // ball: four addresses, one draw triple
+      for (int c = 0; c < 4; ++c) {
+        si[3 * (qa + c)] = 3; si[3 * (qa + c) + 1] = c; si[3 * (qa + c) + 2] = qa;
+        sf[2 * (qa + c) + 1] = limited ? hi : M_PI;
+      }
+    }                                                  // free joint: the caller's value (zeros)
+  }
+  HIP_OK(p->ms_seed_i.need(si.size() * sizeof(int32_t)));
+  HIP_OK(p->ms_seed_f.need(sf.size() * sizeof(double)));
+  HIP_OK(p->ms_jnt.need(jn.size() * sizeof(int32_t)));
+  HIP_OK(hipMemcpy(p->ms_seed_i.p, si.data(), si.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(p->ms_seed_f.p, sf.data(), sf.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(p->ms_jnt.p, jn.data(), jn.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  p->ms_tables = true;
+  return MKH_OK;
+}
+
+extern "C" {
+
+int32_t mkh_solve_multistart(MkhProblem* p, int32_t B, const double* q, const double* frame_targets,
+                             const double* posture_target, const double* com_target, double dt, double damping,
+                             int32_t max_iters, double pos_threshold, double ori_threshold, int32_t n_seeds,
+                             uint64_t rng_seed, int64_t target_index0, const MkhMultistartIO* io, int32_t flags,
+                             void* hip_stream) {
+  if (!p) return fail(MKH_E_INVALID, "null problem");
+  if (B < 1) return fail(MKH_E_INVALID, "B must be >= 1");
+  if (n_seeds < 1) return fail(MKH_E_INVALID, "n_seeds must be >= 1");
+  if (max_iters < 1) return fail(MKH_E_INVALID, "max_iters must be >= 1");
+  if (target_index0 < 0) return fail(MKH_E_INVALID, "target_index0 must be >= 0");
+  if (!(pos_threshold >= 0.0) || !(ori_threshold >= 0.0)) return fail(MKH_E_INVALID, "thresholds must be >= 0");
+  if (!io || !io->q_best || !io->v_best || !io->iters || !io->status || !io->converged || !io->seed_index || !io->n_converged)
+    return fail(MKH_E_INVALID, "io and its per-target outputs (q_best, v_best, iters, status, converged, seed_index, n_converged) are required");
+  const DeviceProblem& P = p->dev;
+  if (!q) return fail(MKH_E_INVALID, "q is null");
+  if (P.n_frame < 1) return fail(MKH_E_INVALID, "mkh_solve_multistart needs at least one frame task to test the thresholds on");
+  if (!frame_targets) return fail(MKH_E_INVALID, "frame_targets is null (TargetNotSet)");
+  if (P.n_posture > 0 && !posture_target) return fail(MKH_E_INVALID, "posture_target is null (TargetNotSet)");
+  if (P.n_com > 0 && !com_target) return fail(MKH_E_INVALID, "com_target is null (TargetNotSet)");
+  if (P.n_dense_rows || P.n_dense_limit_rows || P.dense_box)
+    return fail(MKH_E_INVALID, "dense (plugin) rows are evaluated by the caller at q: no fused loop, no multi-start");
+  const long long N = (long long)B * n_seeds;
+  if (N > p->max_batch)
+    return fail(MKH_E_INVALID, "B * n_seeds = %lld exceeds max_batch=%d of this problem", N, p->max_batch);
+  HIP_OK(hipSetDevice(p->model->device));
+  if (const int32_t rc = ms_build_tables(p)) return rc;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
+  const bool pbat = (flags & MKH_FLAG_POSTURE_BATCHED) != 0, cbat = (flags & MKH_FLAG_COM_BATCHED) != 0;
+  const int S = n_seeds;
+  const size_t Bz = B, Nz = (size_t)N, nq = P.nq, nv = P.nv, f8 = sizeof(double), i4 = sizeof(int32_t);
+  const size_t ft_w = (size_t)P.n_frame * 7, pt_w = (size_t)P.n_posture * nq, ct_w = (size_t)P.n_com * 3;
+
+  // ---- inputs on the device
+  const double *d_q = q, *d_ft = frame_targets, *d_pt = posture_target, *d_ct = com_target;
+  const double *d_user = io->seeds, *d_ref = io->q_ref, *d_w = io->weights;
+  if (!devp) {
+    auto up = [&](GrowBuf& g, const double* src, size_t n) -> hipError_t {
+      if (hipError_t e = g.need(n * f8)) return e;
+      return hipMemcpyAsync(g.p, src, n * f8, hipMemcpyHostToDevice, stream);
+    };
+    HIP_OK(up(p->ms_in_q, q, Bz * nq)); d_q = p->ms_in_q.f64();
+    HIP_OK(up(p->ms_in_ft, frame_targets, Bz * ft_w)); d_ft = p->ms_in_ft.f64();
+    if (pt_w) { HIP_OK(up(p->ms_in_pt, posture_target, pt_w * (pbat ? Bz : 1))); d_pt = p->ms_in_pt.f64(); }
+    if (ct_w) { HIP_OK(up(p->ms_in_ct, com_target, ct_w * (cbat ? Bz : 1))); d_ct = p->ms_in_ct.f64(); }
+    if (io->q_ref) { HIP_OK(up(p->ms_in_ref, io->q_ref, Bz * nq)); d_ref = p->ms_in_ref.f64(); }
+    if (io->weights) { HIP_OK(up(p->ms_in_w, io->weights, nv)); d_w = p->ms_in_w.f64(); }
+  }
+  // ---- workspace of the B·S instances
+  HIP_OK(p->ms_q.need(Nz * nq * f8));
+  HIP_OK(p->ms_ft.need(Nz * ft_w * f8));
+  HIP_OK(p->ms_v.need(Nz * nv * f8));
+  HIP_OK(p->ms_i32.need(3 * Nz * i4));
+  if (pt_w && pbat) HIP_OK(p->ms_pt.need(Nz * pt_w * f8));
+  if (ct_w && cbat) HIP_OK(p->ms_ct.need(Nz * ct_w * f8));
+  if (!devp && (io->seeds || io->seeds_out)) HIP_OK(p->ms_seeds.need(Nz * nq * f8));
+  if (!devp && io->seeds) {           // the caller's seeds, staged beside the workspace (the seed kernel reads them once)
+    HIP_OK(hipMemcpyAsync(p->ms_seeds.p, io->seeds, Nz * nq * f8, hipMemcpyHostToDevice, stream));
+    d_user = p->ms_seeds.f64();
+  }
+  // seeds: into the caller's seeds_out when it is a device buffer (the loop then reads them there), else into the workspace,
+  // where the loop runs in place
+  double* d_seeds = p->ms_q.f64();
+  if (devp && io->seeds_out) d_seeds = io->seeds_out;
+  double* const d_q_all = (devp && io->q_all) ? io->q_all : p->ms_q.f64();
+  int32_t* const d_status = (devp && io->status_all) ? io->status_all : p->ms_i32.i32();
+  int32_t* const d_iters = (devp && io->iters_all) ? io->iters_all : p->ms_i32.i32() + Nz;
+  int32_t* const d_conv = (devp && io->converged_all) ? io->converged_all : p->ms_i32.i32() + 2 * Nz;
+  HIP_OK(launch_ms_seed(stream, p->ms_seed_i.i32(), p->ms_seed_f.f64(), B, S, (int)nq, d_q, d_user, (unsigned long long)rng_seed,
+                        (long long)target_index0, d_seeds));
+  if (!devp && io->seeds_out) {       // (host caller: the seeds are set aside before the loop overwrites them in place)
+    HIP_OK(hipMemcpyAsync(p->ms_seeds.p, d_seeds, Nz * nq * f8, hipMemcpyDeviceToDevice, stream));
+  }
+  // ---- target fan-out: every per-instance target S times (the solve kernels index targets by instance)
+  HIP_OK(launch_ms_fanout(stream, d_ft, p->ms_ft.f64(), B, S, (int)ft_w));
+  if (pt_w && pbat) { HIP_OK(launch_ms_fanout(stream, d_pt, p->ms_pt.f64(), B, S, (int)pt_w)); d_pt = p->ms_pt.f64(); }
+  if (ct_w && cbat) { HIP_OK(launch_ms_fanout(stream, d_ct, p->ms_ct.f64(), B, S, (int)ct_w)); d_ct = p->ms_ct.f64(); }
+  // ---- the loop: mkh_solve_until's own path and dispatch on the B·S instances
+  const int32_t loop_flags = (flags & ~MKH_FLAG_WARM_START) | MKH_FLAG_DEVICE_PTRS;
+  if (const int32_t rc = run(p, (int32_t)N, d_seeds, p->ms_ft.f64(), d_pt, d_ct, dt, damping, p->ms_v.f64(), d_status, nullptr,
+                             loop_flags, hip_stream, max_iters, d_q_all, nullptr, pos_threshold, ori_threshold, d_iters, d_conv))
+    return rc;
+  // ---- selection
+  double *o_q = io->q_best, *o_v = io->v_best;
+  int32_t *o_it = io->iters, *o_st = io->status, *o_cv = io->converged, *o_si = io->seed_index, *o_nc = io->n_converged;
+  if (!devp) {
+    HIP_OK(p->ms_out_q.need(Bz * nq * f8));
+    HIP_OK(p->ms_out_v.need(Bz * nv * f8));
+    HIP_OK(p->ms_out_i32.need(5 * Bz * i4));
+    o_q = p->ms_out_q.f64(); o_v = p->ms_out_v.f64();
+    o_it = p->ms_out_i32.i32(); o_st = o_it + Bz; o_cv = o_it + 2 * Bz; o_si = o_it + 3 * Bz; o_nc = o_it + 4 * Bz;
+  }
+  HIP_OK(launch_ms_select(stream, B, S, (int)nq, (int)nv, p->model->njnt, p->ms_jnt.i32(), d_q_all, p->ms_v.f64(), d_status, d_iters,
+                          d_conv, d_ref ? d_ref : d_q, d_w, o_q, o_v, o_it, o_st, o_cv, o_si, o_nc));
+  if (devp) return MKH_OK;
+  auto down = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
+    return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream) : hipSuccess;
+  };
+  hipError_t e = down(io->q_best, o_q, Bz * nq * f8);
+  if (e == hipSuccess) e = down(io->v_best, o_v, Bz * nv * f8);
+  if (e == hipSuccess) e = down(io->iters, o_it, Bz * i4);
+  if (e == hipSuccess) e = down(io->status, o_st, Bz * i4);
+  if (e == hipSuccess) e = down(io->converged, o_cv, Bz * i4);
+  if (e == hipSuccess) e = down(io->seed_index, o_si, Bz * i4);
+  if (e == hipSuccess) e = down(io->n_converged, o_nc, Bz * i4);
+  if (e == hipSuccess) e = down(io->q_all, d_q_all, Nz * nq * f8);
+  if (e == hipSuccess) e = down(io->status_all, d_status, Nz * i4);
+  if (e == hipSuccess) e = down(io->iters_all, d_iters, Nz * i4);
+  if (e == hipSuccess) e = down(io->converged_all, d_conv, Nz * i4);
+  if (e == hipSuccess && io->seeds_out) e = down(io->seeds_out, p->ms_seeds.p, Nz * nq * f8);
+  const hipError_t e2 = hipStreamSynchronize(stream);       // (a failed call still drains what it started)
+  if (e == hipSuccess) e = e2;
+  if (e != hipSuccess) return fail(MKH_E_HIP, "multistart: %s", hipGetErrorString(e));
+  return MKH_OK;
 }
 
 int32_t mkh_integrate(MkhModel* m, int32_t B, const double* q, const double* v, double dt, double* q_out,

@@ -14,6 +14,7 @@ import numpy as np
 from . import _native as nat
 from . import exceptions
 from .configuration import Configuration
+from .distributed import shard_bounds
 from .flatmodel import JNT_FREE
 
 DEVICE_SOLVERS = ("mi355x", "hip", "quadprog")
@@ -182,6 +183,9 @@ def _compile(configuration: Configuration, tasks: Sequence, limits: Optional[Seq
     for old in [k for k in cache if k not in pinned][:max(0, len(cache) - PROBLEM_CACHE_SIZE)]:
         cache.pop(old).close()
     layout["cache_key"] = key
+    layout["native_kwargs"] = dict(frame_tasks=groups["frame"], posture_tasks=groups["posture"], com_tasks=groups["com"],
+                                   configuration_limits=groups["cfg"], velocity_limits=groups["vel"],
+                                   collision_limits=groups["col"])      # (further handles of this call site: multi-start shards)
     if memo_key is not None:
         if len(configuration._compile_memo) >= 4 * PROBLEM_CACHE_SIZE:
             configuration._compile_memo.clear()
@@ -342,3 +346,168 @@ def solve_ik_steps(configuration: Configuration, tasks: Sequence, dt: float, n_s
         return (configuration._unbatch(q), configuration._unbatch(v), configuration._unbatch(res[3]),
                 configuration._unbatch(res[4].astype(bool)))
     return configuration._unbatch(q), configuration._unbatch(v)
+
+
+class MultistartResult(NamedTuple):
+    """Result of solve_ik_multistart: per target the chosen seed's final configuration `q`, its last velocity `v`, whether any
+    seed `converged`, the chosen `seed_index` (0 when none did), `n_converged` of the S seeds, and the chosen seed's `iters`
+    and `status`.  With return_all also every instance's `q_all` (B, S, nq), `converged_all`, `iters_all`, `status_all`
+    (B, S) and the `seeds` (B, S, nq) the loops started from; None otherwise."""
+    q: np.ndarray
+    v: np.ndarray
+    converged: np.ndarray
+    seed_index: np.ndarray
+    n_converged: np.ndarray
+    iters: np.ndarray
+    status: np.ndarray
+    q_all: Optional[np.ndarray] = None
+    converged_all: Optional[np.ndarray] = None
+    iters_all: Optional[np.ndarray] = None
+    status_all: Optional[np.ndarray] = None
+    seeds: Optional[np.ndarray] = None
+
+
+def _host_array(x, name: str):
+    """An optional array argument as float64 numpy (a torch tensor, wherever it lives, is brought to the host: the
+    Configuration holds its q there)."""
+    if x is None:
+        return None
+    if nat._is_torch(x):
+        x = x.detach().cpu().numpy()
+    try:
+        return np.ascontiguousarray(x, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"{name} must be an array of numbers") from e
+
+
+def solve_ik_multistart(configuration: Configuration, tasks: Sequence, dt: float, n_seeds: int, max_iters: int,
+                        pos_threshold: float, ori_threshold: float, solver: str = "mi355x", damping: float = 1e-12,
+                        limits: Optional[Sequence] = None, rng_seed: int = 0, seeds=None, reference=None, weights=None,
+                        update: bool = True, return_all: bool = False, max_instances: int = 1 << 20) -> MultistartResult:
+    """Global IK by multi-start: the threshold-terminated loop of solve_ik_steps from `n_seeds` starts per target, the best
+    solution picked on the device — seeding, target fan-out and selection happen there, in one call.
+
+    Seed 0 of every target is the configuration's own q, so the result is never worse than solve_ik_steps from it.  The other
+    starts are drawn per joint (limited hinge / slide: uniform in its range; unlimited hinge: within ±π of q; ball: a random
+    rotation of at most its range; free joints and unlimited slides keep the caller's value) by a stateless generator — a pure
+    function of (rng_seed, target index, seed index, joint): the result does not depend on `max_instances`, the device list or
+    the batch around a target — or taken from `seeds`, (S, nq) or (B, S, nq) (row 0 is still replaced by q).
+
+    Among the seeds that converged without a QP failure the one closest to `reference` (default: q) wins: smallest
+    Σ_k weights_k·(q_s ⊖ reference)_k² in the tangent space, ties to the lowest index.  A target none of whose seeds converged
+    returns seed 0's result with converged = False — exactly what solve_ik_steps returns from q.  Failures are reported for
+    the CHOSEN seeds only, like solve_ik_steps reports them: a warning for configuration limits, SolverError for a QP failure
+    (which can only be seed 0's, of a target where nothing converged); a failed random seed is just discarded.
+
+    When B·n_seeds exceeds `max_instances` the targets are walked in chunks; a multi-device configuration shards by target."""
+    del solver
+    S, max_iters = int(n_seeds), int(max_iters)
+    if S < 1:
+        raise ValueError("n_seeds must be >= 1")
+    if max_iters < 1:
+        raise ValueError("max_iters must be >= 1")
+    if int(max_instances) < 1:
+        raise ValueError("max_instances must be >= 1")
+    B, nq, nv = configuration.batch_size, configuration.nq, configuration.nv
+    seeds = _host_array(seeds, "seeds")
+    if seeds is not None:
+        if seeds.shape == (S, nq):
+            seeds = np.ascontiguousarray(np.broadcast_to(seeds, (B, S, nq)))
+        elif seeds.shape != (B, S, nq):
+            raise ValueError(f"seeds must have shape ({S}, {nq}) or ({B}, {S}, {nq}), got {seeds.shape}")
+    reference = _host_array(reference, "reference")
+    if reference is not None:
+        if reference.shape == (nq,):
+            reference = np.ascontiguousarray(np.broadcast_to(reference, (B, nq)))
+        elif reference.shape != (B, nq):
+            raise ValueError(f"reference must have shape ({nq},) or ({B}, {nq}), got {reference.shape}")
+    weights = _host_array(weights, "weights")
+    if weights is not None and weights.shape != (nv,):
+        raise ValueError(f"weights must have shape ({nv},), got {weights.shape}")
+    # targets per chunk: as many as fit max_instances; devices share a chunk by target
+    devices = configuration.devices
+    per_chunk = max(1, int(max_instances) // S)
+    n_dev = len(devices) if (len(devices) > 1 and min(B, per_chunk) >= len(devices)) else 1
+    chunk = min(B, per_chunk)
+    shard = -(-chunk // n_dev)
+    # one handle per shard, sized for its instances (the single-device handle lives in the configuration's cache)
+    prob, layout = _compile_single(configuration, tasks, limits, shard * S, dt)
+    if layout["dense"] or layout["dense_limits"]:
+        raise exceptions.TaskDefinitionError(
+            "solve_ik_multistart fuses the outer loop on the device; caller-defined Task / Limit subclasses are evaluated on "
+            "the host at every step: call solve_ik + integrate_inplace in a loop instead")
+    ft, pt, ct = _gather_targets(configuration, layout)
+    q = configuration.q_batch
+    kw = dict(n_seeds=S, max_iters=max_iters, pos_threshold=float(pos_threshold), ori_threshold=float(ori_threshold),
+              rng_seed=int(rng_seed), return_all=bool(return_all))
+
+    def rows(x, per, lo, hi):
+        return None if x is None else (np.ascontiguousarray(x[lo:hi]) if x.ndim == per + 1 else x)
+
+    def job(handle, lo, hi):
+        return handle.solve_multistart(q[lo:hi], rows(ft, 2, lo, hi), rows(pt, 2, lo, hi), rows(ct, 2, lo, hi), dt, damping,
+                                       target_index0=lo, seeds=rows(seeds, 2, lo, hi), reference=rows(reference, 1, lo, hi),
+                                       weights=weights, **kw)
+
+    parts = []
+    with _pin(configuration, layout):
+        # (a ShardedProblem cached by solve_ik_steps for the same tasks and batch size cannot serve: it splits rows without
+        #  telling a shard its global offset — every handle is then built here)
+        first = [prob] if isinstance(prob, nat.NativeProblem) else []
+        handles = first if (n_dev == 1 and first) else _multistart_shards(configuration, layout, first, devices[:n_dev], shard * S)
+        for c0 in range(0, B, chunk):
+            c1 = min(B, c0 + chunk)
+            bounds = [(c0 + lo, c0 + hi) for lo, hi in (shard_bounds(c1 - c0, n_dev, r) for r in range(n_dev))]
+            bounds = [(lo, hi) for lo, hi in bounds if hi > lo]
+            if len(bounds) == 1:
+                parts.append(job(handles[0], *bounds[0]))
+            else:
+                from concurrent.futures import ThreadPoolExecutor
+                with ThreadPoolExecutor(max_workers=len(bounds)) as pool:      # (a libminkhip call releases the GIL)
+                    parts += [f.result() for f in [pool.submit(job, h, lo, hi) for h, (lo, hi) in zip(handles, bounds)]]
+    res = MultistartResult(*[None if parts[0][k] is None else np.concatenate([p[k] for p in parts], axis=0)
+                             for k in range(len(MultistartResult._fields))])
+    status = res.status
+    if (status & nat.ST_OUTSIDE_LIMITS).any():
+        logging.warning("solve_ik_multistart: %d chosen instance(s) were outside their configuration limits at some fused step",
+                        int(((status & nat.ST_OUTSIDE_LIMITS) != 0).sum()))
+    bad = np.nonzero(status & ~nat.ST_OUTSIDE_LIMITS)[0]
+    if len(bad):
+        raise exceptions.SolverError(f"QP failed for the chosen seed of {len(bad)} of {len(status)} targets "
+                                     f"(first: index {int(bad[0])}, status {int(status[bad[0]])}); none of their seeds converged")
+    if update:
+        configuration.update(res.q if configuration.batched else res.q[0])
+    un = configuration._unbatch
+    return MultistartResult(un(res.q), un(res.v), un(res.converged.astype(bool)), un(res.seed_index), un(res.n_converged),
+                            un(res.iters), un(res.status),
+                            *[None if x is None else un(x.astype(bool) if k == 1 else x)
+                              for k, x in enumerate((res.q_all, res.converged_all, res.iters_all, res.status_all, res.seeds))])
+
+
+def _compile_single(configuration: Configuration, tasks, limits, batch: int, dt: float):
+    """_compile for ONE device whatever the configuration's device list says (multi-start shards by target itself: every shard
+    has to know its global target offset, which ShardedProblem's row split does not pass on)."""
+    devices = configuration.devices
+    configuration.devices = devices[:1]
+    try:
+        return _compile(configuration, tasks, limits, batch, dt)
+    finally:
+        configuration.devices = devices
+
+
+def _multistart_shards(configuration: Configuration, layout, first, devices, max_batch: int):
+    """One handle per listed device for a multi-start call (a device may be listed more than once: problem handles of one
+    model are independent).  `first` holds the cached single-device handle (or nothing); the others are built from the same
+    descriptors and kept on the configuration until the call site or the shard size changes."""
+    from .configuration import native_model
+
+    key = (layout["cache_key"], tuple(devices), max_batch, len(first))
+    held = configuration._multistart_shards
+    if held.get("key") != key:
+        for h in held.get("handles", []):
+            h.close()
+        held.clear()
+        held["key"] = key
+        held["handles"] = [nat.NativeProblem(native_model(configuration.model, d), max_batch=max_batch, **layout["native_kwargs"])
+                           for d in devices[len(first):]]
+    return list(first) + held["handles"]
