@@ -85,7 +85,7 @@ def gen(nt: int, total: int = 0, name: str = "Tab") -> str:
     out.append("  struct Regs {};   // (the column is not a compiler-visible value)")
     # zero
     out.append("  __device__ static __forceinline__ void zero(Regs& t) {")
-    out.append(stmt(J(f"v_mov_b32 v{r}, 0" for r in range(t0, t1))))
+    out.append(stmt(J(f"v_mov_b64 v[{r}:{r + 1}], 0" for r in range(t0, t1, 2))))      # (t0 is even: aligned pairs; fp64 DPP exists for v_fmac and v_mov only, so a first update cannot write a product)
     out.append("  }")
     # rank1 = prefetch (the four plane loads) + body; the split lets the caller put the reciprocal / multiplier
     # arithmetic between them so that the LDS latency is hidden.

@@ -908,6 +908,19 @@ __device__ MKH_PRE_ATTR DirectPairs direct_pairs(const DeviceProblem* Pq) {
 // Outputs per dof lane: D = −H⁻¹[j][j] = σ²(Σ_r z_r²/d_r − 1),  x0 = −H⁻¹c = z − σ·Σ_r z_r·ω_r/d_r  (ω = L⁻¹w, w = Jw·z − r).
 struct WoodOut { double hdiag, dsq, x, D, rown; int status, clamp; };
 
+// 1/d_r and ω_r of elimination step r to LDS (doubles O0 and O1 behind `addr`), stored by the one lane that holds ω_r in a
+// vector register already — S lane SRC, whose w entry is final when its step begins; 1/d_r is the same in every lane.  The
+// lane is picked by writing EXEC here (saved and restored): as a C++ lane condition the store cost a compare or, from lane 0,
+// two moves of the wave-uniform values into vector registers in each of the 36 steps of a cold G1 solve.
+template <int SRC, int O0, int O1>
+__device__ __forceinline__ void wood_store_pivot(unsigned addr, double inv, double om) {
+  static_assert(SRC >= 0 && SRC < kWave && O0 >= 0 && O0 < 256 && O1 >= 0 && O1 < 256, "lane / ds_write2 offsets");
+  unsigned long long sv;
+  asm volatile("s_mov_b64 %[sv], exec\n\ts_lshl_b64 exec, 1, %[src]\n\tds_write2_b64 %[a], %[x], %[y] offset0:%[o0] offset1:%[o1]\n\t"
+               "s_mov_b64 exec, %[sv]"
+               : [sv] "=&s"(sv) : [a] "v"(addr), [x] "v"(inv), [y] "v"(om), [src] "n"(SRC), [o0] "n"(O0), [o1] "n"(O1) : "memory", "scc");   // (the shift writes SCC)
+}
+
 // cold-start refinement of wood_eliminate (single-pass lane layout): bounds, the dof's closed-form point and scales
 struct WoodRefine { bool on; int nv; double lo, hi, zfree, dsq, sqdg, zsq; };
 template <int K, bool DUAL>
@@ -936,12 +949,20 @@ __device__ __forceinline__ void wood_eliminate(int n_mu, int NR, int lane, doubl
       if (lane < NR) sJ[n_mu * NR + lane] = q;                           // parked in LDS (the right-hand-side row of the product
     }                                                                    // is dead), not in two registers through the loop
     double* const sOm = sDinv + kMuBig;
+    // (the steps' guards test a scalar copy of n_μ the compiler can neither merge with the lane conditions of the loads above nor
+    //  evaluate ahead of the passes: evaluated ahead, every `r < n_μ` lived through both passes as a 64-bit lane mask — 36 scalar
+    //  registers, which pushed wood_start into the callee-saved range, 33 scalars moved through lanes on entry and again on
+    //  exit, and its caller, the kernel body, into 26 spilled scalars of its own)
+    int n_mu_s = uni(n_mu);
+    unsigned dinv_addr = lds_addr(sDinv);
+    asm volatile("" : "+v"(dinv_addr));                                  // (one register through the loop, not a move per step)
 #pragma nounroll
     for (int pass = 0;; ++pass) {
       quad = 0.0; zw = 0.0;
+      asm volatile("" : "+s"(n_mu_s));                                   // (re-read in every pass: not hoisted out of the pass loop either)
       static_for<K>([&](auto rc) {
         constexpr int r = decltype(rc)::value;
-        if (r < n_mu) {
+        if (r < n_mu_s) {
           // row r of S straight from the S lanes' registers: d_r and ω_r by v_readlane (the reciprocal starts at once),
           // the two 16-lane planes through the LDS crossbar (a store → wait → load round trip per step doubled the chain)
           const double d = readlane_f64(z[r], NR + r), om = readlane_f64(ws, NR + r);
@@ -949,9 +970,8 @@ __device__ __forceinline__ void wood_eliminate(int n_mu, int NR, int lane, doubl
           // (unconditional: a permute under a lane condition would not see the source lanes the condition switches off)
           const double p1 = (K > 16) ? bperm_f64(z[r], (NR + 16 + (int)plane_off) & 63) : 0.0;   // rows ≥ n_μ: never used
           if (lane < NR) sJ[r * NR + lane] = z[r];                       // row r of Z, final (read after the loop)
-          if (!(d > 0.0)) status |= 4;
           const double inv = fast_rcp(d);
-          if (lane == 0) { sDinv[r] = inv; sOm[r] = om; }
+          wood_store_pivot<(MKH_NT + r) % kWave, r, kMuBig + r>(dinv_addr, inv, ws);   // sDinv[r] = 1/d_r, sOm[r] = ω_r  (NR = MKH_NT)
           const double zi = z[r] * inv;
           quad = fma(z[r], zi, quad);
           zw = fma(om, zi, zw);
@@ -959,6 +979,10 @@ __device__ __forceinline__ void wood_eliminate(int n_mu, int NR, int lane, doubl
           ws = fma(-zi, om, ws);                                         // w_c −= S[c][r]·ω_r/d  (S lanes; harmless on dof lanes)
         }
       });
+      // d_r > 0 for every r, tested once per pass on the stored reciprocals (lane r its own) instead of on d_r in every step:
+      // 1/d from fast_rcp is positive exactly when d is positive, finite and normal — d = +inf or subnormal, which only a
+      // broken S = I + Jh·Jhᵀ ≥ I reaches, comes back NaN and is reported too
+      if (lane < n_mu && !(sDinv[lane] > 0.0)) status |= 4;
       if (pass == 1 || !rf.on) break;
       // ---- cold start: the bounds the unconstrained minimiser x⁰ violates are (nearly) the optimal active set — block
       // principal pivoting would put exactly these dofs on their bounds, one un-sweep pivot of the whole tableau each.

@@ -47,8 +47,8 @@ def check(src: str):
     import gen_tab_asm as gen
     nt = int(re.search(r"variant_(\d+)_", os.path.basename(src)).group(1))
     # (_w3: the high-occupancy build — TabW3, 168 registers, for NT > 24; TabW4, 128 registers, for NT ≤ 24)
-    top = (128 if nt <= 24 else 168) if os.path.basename(src).endswith("_w3.hip") else gen.total_for(nt)
-    w3 = os.path.basename(src).endswith("_w3.hip")
+    w3 = os.path.basename(src).endswith(("_w3.hip", "_w3o.hip"))     # (_w3o: the one-problem-per-workgroup twin, same map)
+    top = (128 if nt <= 24 else 168) if w3 else gen.total_for(nt)
     cap = top - 2 * nt - (2 * ((nt + 15) // 16) if w3 else gen.ntmp_for(nt))
     out = subprocess.run([hipbuild._hipcc()] + hipbuild.FLAGS + hipbuild.KERNEL_FLAGS +
                          ["-S", "--cuda-device-only", "-o", "-", src], check=True, capture_output=True, text=True).stdout

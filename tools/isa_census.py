@@ -3,7 +3,10 @@
 -DMKH_MARKERS): VALU / SALU / LDS / VMEM / other instruction counts per region, in program order.  Loop bodies
 appear once (multiply by the trip count by hand: 18 phase-0 pivots and 13.5 active-set iterations for G1).
 
-    python tools/isa_census.py 62_32_r44
+    python tools/isa_census.py [44_32_r44_w3o]       (default: the headline's one-problem-per-workgroup build)
+
+The second table counts static VALU instructions per function and class; the third gives each function's code bytes (symbol
+sizes in the gfx950 code object).
 """
 import os
 import re
@@ -95,8 +98,10 @@ def class_table(asm: str):
 
 
 def main():
-    name = sys.argv[1] if len(sys.argv) > 1 else "62_32_r44"
+    name = sys.argv[1] if len(sys.argv) > 1 else "44_32_r44_w3o"
     src = os.path.join(hipbuild.BUILD, f"variant_{name}.hip")
+    if not os.path.exists(src):
+        hipbuild._generate()               # (the generated translation units; nothing is compiled)
     asm = subprocess.run([hipbuild._hipcc()] + hipbuild.FLAGS + hipbuild.KERNEL_FLAGS +
                          ["-DMKH_MARKERS", "-S", "--cuda-device-only", "-o", "-", src], check=True,
                          capture_output=True, text=True).stdout
@@ -122,6 +127,28 @@ def main():
     for r in order:
         print("%-28s" % r + "".join("%9d" % counts[r].get(k, 0) for k in kinds))
     class_table(asm)
+    code_bytes(src)
+
+
+def code_bytes(src: str):
+    """Code bytes per function of the translation unit's gfx950 code object (symbol sizes of its .text)."""
+    import tempfile
+    with tempfile.TemporaryDirectory() as d:
+        co = os.path.join(d, "x.co")
+        subprocess.run([hipbuild._hipcc()] + hipbuild.FLAGS + hipbuild.KERNEL_FLAGS + ["--cuda-device-only", "--no-gpu-bundle-output", "-c", "-o", co, src],
+                       check=True, capture_output=True, text=True)
+        out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--symbols", "--wide", co], capture_output=True, text=True).stdout
+    print()
+    print("code bytes by function")
+    total, seen = 0, set()
+    for line in out.split("\n"):
+        f = line.split()
+        if len(f) == 8 and f[3] == "FUNC" and f[7] not in seen:     # Num: Value Size Type Bind Vis Ndx Name (.dynsym and .symtab)
+            seen.add(f[7])
+            short = re.split(r"EPK|EPKNS", re.sub(r"^_ZN3mkhL?\d+", "", f[7]))[0]
+            print("  %-36s %7d" % (short, int(f[2])))
+            total += int(f[2])
+    print("  %-36s %7d" % ("all", total))
 
 
 if __name__ == "__main__":
