@@ -2,9 +2,9 @@
 
     python -m mink_amd.csrc.build            # or: python mink_amd/csrc/build.py [--force]
 
-Each kernel variant ik_solve_kernel<NT, FEAT> is compiled in its own generated translation unit
-(_build/variant_<NT>_<FEAT>.hip) so that the variants build in parallel; minkhip.hip holds the host
-side of the C ABI.  The shared library is written next to the Python package
+Each kernel variant of VARIANTS below is compiled in its own generated translation unit
+(_build/variant_<name>.hip) so that the variants build in parallel, and _build/dispatch.hip holds the
+table of them that the host side of the C ABI (minkhip.hip) queries and launches through (variants.h).  The shared library is written next to the Python package
 (mink_amd/libminkhip.so) so that it travels with the repo snapshot; it is git-ignored (*.so).
 """
 
@@ -15,6 +15,7 @@ import re
 import shutil
 import subprocess
 import sys
+from typing import NamedTuple
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
@@ -32,25 +33,68 @@ def _sources() -> list:
     return fs + [os.path.join(HERE, "..", "..", "include", "minkhip.h")]
 
 
-NTS = (8, 16, 24, 32, 44, 48, 64)          # tableau rows per lane (must match kVariants in minkhip.hip)
+NTS = (8, 16, 24, 32, 44, 48, 64)          # tableau rows per lane
 FEATS = (0, 16, 6, 8, 72, 88, 136, 30, 31, 256)      # lean, + fused step loop, RelativeFrameTask/ComTask, collision rows only, collision rows with plane / sphere / capsule pairs only, the same + fused step loop, collision rows with general convex pairs (GJK), every feature but taps, everything, dense (plugin) rows only (ik_kernel.h F_*)
 # low-rank ("Woodbury") start: (NT, NR) = (tableau rows ≥ nv + task rows, dof rows ≥ nv); F_WOOD = 32
-WOOD = ((16, 16), (24, 24), (32, 32), (44, 44), (48, 48))   # (NT, NR): the task residuals are eliminated outside the tableau (ik_kernel.h wood_start), NT = NR ≥ nv; must match kWoodVariants in minkhip.hip
+WOOD = ((16, 16), (24, 24), (32, 32), (44, 44), (48, 48))   # (NT, NR): the task residuals are eliminated outside the tableau (ik_kernel.h wood_start), NT = NR ≥ nv
 # 3-waves-per-SIMD register map (TabW3 in tab_asm.inc, 168 VGPRs, compact LDS layout): (NT, FEAT) without collision rows
-W3 = ((44, 0),)                        # must match kW3Variants in minkhip.hip
+W3 = ((44, 0),)                        # (44_6 and 44_16 still spill 34–76 VGPRs at 74 registers: scratch traffic makes them slower than their 2-waves builds)
 W3_WOOD = ((44, 44, 32), (44, 44, 48), (32, 32, 32), (32, 32, 48),    # (NT, NR, FEAT) of the low-rank start with the 3-waves map
            (24, 24, 32), (24, 24, 48), (16, 16, 32), (16, 16, 48),    # ... and, for NT ≤ 24, the 4-waves map (TabW4; same suffix _w3: "one more wave")
            (44, 44, 36), (44, 44, 52))                                # F_COM (ComTask rows / up to 24 task rows) and its fused loops: round 5, ik_kernel.h MKH_WOOD_SPLIT
 # one problem per workgroup (round 6; ik_kernel.h MKH_ONE_SHOT): a twin of the humanoid-size one-more-wave build WITHOUT the persistent
-# loop's machinery (ticket draws, double-buffered inputs, loop-carried scalars) — launched when the grid is the batch (minkhip.hip launch()).
+# loop's machinery (ticket draws, double-buffered inputs, loop-carried scalars) — launched when the grid is the batch (minkhip.hip plan_launch()).
 # Measured: `44_32_r44_w3o` 0.713 -> 0.703 ms on the headline; the F_COM twin `44_36_r44_w3o` (12 spilled VGPRs) 0.350 -> 0.352 ms at
 # 16 384 instances of the G1 full example — not built.
 W3_WOOD_ONE_SHOT = ((44, 44, 32),)
 WOOD_FEATS = (32, 48, 33, 36, 52)      # F_WOOD, | F_STEPS, | F_TAPS (cycle-counter profiling only), | F_COM, | F_COM | F_STEPS
 # low-rank start WITH half-space rows (round 6; ik_kernel.h wood_start "half-space rows"): (NT, NR, FEAT) on the 2-waves map,
-# NR = NT (the rows' columns of the elimination sit behind the dofs in the tableau-wide rows of Jh); must match kWoodRowVariants
-# in minkhip.hip.  40 = F_WOOD | F_COLL (analytic pairs, phases as calls)
+# NR = NT (the rows' columns of the elimination sit behind the dofs in the tableau-wide rows of Jh).
+# 40 = F_WOOD | F_COLL (analytic pairs, phases as calls)
 WOOD_ROWS = ((48, 48, 40),)
+
+
+class Variant(NamedTuple):
+    """One compiled ik_solve_kernel build.  Its name — "44_32_r44_w3o" — names the translation unit (variant_<name>.hip), the
+    launcher (launch_<name>) and the kernel (ik_solve_kernel_<name>)."""
+    nt: int
+    feat: int
+    nr: int = 0
+    w3: bool = False
+    one_shot: bool = False
+
+    @property
+    def name(self) -> str:
+        return f"{self.nt}_{self.feat}" + (f"_r{self.nr}" if self.nr else "") + ("_w3" if self.w3 else "") + ("o" if self.one_shot else "")
+
+    def translation_unit(self) -> str:
+        defs = [f"MKH_NT {self.nt}"] + ([f"MKH_NR {self.nr}"] if self.nr else []) + [f"MKH_FEAT {self.feat}"]
+        if self.w3:
+            defs.append("MKH_W3 1")
+            if self.nr and self.nt <= 24 and not self.one_shot:
+                defs.append("MKH_W4 1")            # (the 4-waves map of the small low-rank builds, W3_WOOD)
+        if self.one_shot:
+            defs.append("MKH_ONE_SHOT 1")
+        if self.name != f"{self.nt}_{self.feat}":  # (ik_kernel.h composes the plain builds' kernel name itself)
+            defs.append(f"MKH_KERNEL_NAME ik_solve_kernel_{self.name}")
+        return "// generated by build.py\n" + "".join(f"#define {d}\n" for d in defs) + f"""#include "../ik_kernel.h"
+namespace mkh {{
+void launch_{self.name}(int grid, int lds_bytes, hipStream_t stream, const DeviceProblem* P, const SolveArgs& a,
+                      const TapArgs* taps) {{
+  hipLaunchKernelGGL(ik_solve_kernel_{self.name}, dim3(grid), dim3(kWave), lds_bytes, stream, P, a, taps);
+}}
+}}  // namespace mkh
+"""
+
+
+# every compiled build, once: the translation units, the host's table (_build/dispatch.hip → variants.h) and
+# kernel_resources.json all follow from this list
+VARIANTS = tuple([Variant(nt, ft) for nt in NTS for ft in FEATS]
+                 + [Variant(nt, ft, nr) for nt, nr in WOOD for ft in WOOD_FEATS]
+                 + [Variant(nt, ft, nr) for nt, nr, ft in WOOD_ROWS]
+                 + [Variant(nt, ft, w3=True) for nt, ft in W3]
+                 + [Variant(nt, ft, nr, w3=True) for nt, nr, ft in W3_WOOD]
+                 + [Variant(nt, ft, nr, w3=True, one_shot=True) for nt, nr, ft in W3_WOOD_ONE_SHOT])
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-null-conversion"]
 # experiments: extra compiler flags for every translation unit (e.g. MKH_EXTRA_FLAGS="-DMKH_FORCE_COLL_CALL"); part of the
 # per-object command tag, so changing it recompiles
@@ -213,141 +257,24 @@ def _generate() -> list:
     os.makedirs(BUILD, exist_ok=True)
     subprocess.run([sys.executable, os.path.join(HERE, "gen_tab_asm.py")], check=True)
     srcs = []
-    for nt in NTS:
-        for ft in FEATS:
-            name = f"variant_{nt}_{ft}"
-            _write_if_changed(os.path.join(BUILD, name + ".hip"), f"""// generated by build.py
-#define MKH_NT {nt}
-#define MKH_FEAT {ft}
-#include "../ik_kernel.h"
-namespace mkh {{
-void launch_{nt}_{ft}(int grid, int lds_bytes, hipStream_t stream, const DeviceProblem* P, const SolveArgs& a,
-                      const TapArgs* taps) {{
-  hipLaunchKernelGGL(ik_solve_kernel_{nt}_{ft}, dim3(grid), dim3(kWave), lds_bytes, stream, P, a, taps);
-}}
-}}  // namespace mkh
-""")
-            srcs.append(name)
-    for nt, nr in WOOD:
-        for ft in WOOD_FEATS:
-            name = f"variant_{nt}_{ft}_r{nr}"
-            _write_if_changed(os.path.join(BUILD, name + ".hip"), f"""// generated by build.py
-#define MKH_NT {nt}
-#define MKH_NR {nr}
-#define MKH_FEAT {ft}
-#define MKH_KERNEL_NAME ik_solve_kernel_{nt}_{ft}_r{nr}
-#include "../ik_kernel.h"
-namespace mkh {{
-void launch_{nt}_{ft}_r{nr}(int grid, int lds_bytes, hipStream_t stream, const DeviceProblem* P, const SolveArgs& a,
-                      const TapArgs* taps) {{
-  hipLaunchKernelGGL(ik_solve_kernel_{nt}_{ft}_r{nr}, dim3(grid), dim3(kWave), lds_bytes, stream, P, a, taps);
-}}
-}}  // namespace mkh
-""")
-            srcs.append(name)
-    for nt, nr, ft in WOOD_ROWS:
-        name = f"variant_{nt}_{ft}_r{nr}"
-        _write_if_changed(os.path.join(BUILD, name + ".hip"), f"""// generated by build.py
-#define MKH_NT {nt}
-#define MKH_NR {nr}
-#define MKH_FEAT {ft}
-#define MKH_KERNEL_NAME ik_solve_kernel_{nt}_{ft}_r{nr}
-#include "../ik_kernel.h"
-namespace mkh {{
-void launch_{nt}_{ft}_r{nr}(int grid, int lds_bytes, hipStream_t stream, const DeviceProblem* P, const SolveArgs& a,
-                      const TapArgs* taps) {{
-  hipLaunchKernelGGL(ik_solve_kernel_{nt}_{ft}_r{nr}, dim3(grid), dim3(kWave), lds_bytes, stream, P, a, taps);
-}}
-}}  // namespace mkh
-""")
-        srcs.append(name)
-    for nt, ft in W3:
-        name = f"variant_{nt}_{ft}_w3"
-        _write_if_changed(os.path.join(BUILD, name + ".hip"), f"""// generated by build.py
-#define MKH_NT {nt}
-#define MKH_FEAT {ft}
-#define MKH_W3 1
-#define MKH_KERNEL_NAME ik_solve_kernel_{nt}_{ft}_w3
-#include "../ik_kernel.h"
-namespace mkh {{
-void launch_{nt}_{ft}_w3(int grid, int lds_bytes, hipStream_t stream, const DeviceProblem* P, const SolveArgs& a,
-                      const TapArgs* taps) {{
-  hipLaunchKernelGGL(ik_solve_kernel_{nt}_{ft}_w3, dim3(grid), dim3(kWave), lds_bytes, stream, P, a, taps);
-}}
-}}  // namespace mkh
-""")
-        srcs.append(name)
-    for nt, nr, ft in W3_WOOD:
-        name = f"variant_{nt}_{ft}_r{nr}_w3"
-        _write_if_changed(os.path.join(BUILD, name + ".hip"), f"""// generated by build.py
-#define MKH_NT {nt}
-#define MKH_NR {nr}
-#define MKH_FEAT {ft}
-#define MKH_W3 1
-{"#define MKH_W4 1" if nt <= 24 else ""}
-#define MKH_KERNEL_NAME ik_solve_kernel_{nt}_{ft}_r{nr}_w3
-#include "../ik_kernel.h"
-namespace mkh {{
-void launch_{nt}_{ft}_r{nr}_w3(int grid, int lds_bytes, hipStream_t stream, const DeviceProblem* P, const SolveArgs& a,
-                      const TapArgs* taps) {{
-  hipLaunchKernelGGL(ik_solve_kernel_{nt}_{ft}_r{nr}_w3, dim3(grid), dim3(kWave), lds_bytes, stream, P, a, taps);
-}}
-}}  // namespace mkh
-""")
-        srcs.append(name)
-    for nt, nr, ft in W3_WOOD_ONE_SHOT:
-        name = f"variant_{nt}_{ft}_r{nr}_w3o"
-        _write_if_changed(os.path.join(BUILD, name + ".hip"), f"""// generated by build.py
-#define MKH_NT {nt}
-#define MKH_NR {nr}
-#define MKH_FEAT {ft}
-#define MKH_W3 1
-#define MKH_ONE_SHOT 1
-#define MKH_KERNEL_NAME ik_solve_kernel_{nt}_{ft}_r{nr}_w3o
-#include "../ik_kernel.h"
-namespace mkh {{
-void launch_{nt}_{ft}_r{nr}_w3o(int grid, int lds_bytes, hipStream_t stream, const DeviceProblem* P, const SolveArgs& a,
-                      const TapArgs* taps) {{
-  hipLaunchKernelGGL(ik_solve_kernel_{nt}_{ft}_r{nr}_w3o, dim3(grid), dim3(kWave), lds_bytes, stream, P, a, taps);
-}}
-}}  // namespace mkh
-""")
-        srcs.append(name)
-    decls = "\n".join(f"void launch_{nt}_{ft}(int, int, hipStream_t, const DeviceProblem*, const SolveArgs&, const TapArgs*);"
-                      for nt in NTS for ft in FEATS)
-    decls += "\n" + "\n".join(f"void launch_{nt}_{ft}_r{nr}_w3o(int, int, hipStream_t, const DeviceProblem*, const SolveArgs&, const TapArgs*);"
-                             for nt, nr, ft in W3_WOOD_ONE_SHOT)
-    decls += "\n" + "\n".join(f"void launch_{nt}_{ft}_r{nr}(int, int, hipStream_t, const DeviceProblem*, const SolveArgs&, const TapArgs*);"
-                             for nt, nr in WOOD for ft in WOOD_FEATS)
-    decls += "\n" + "\n".join(f"void launch_{nt}_{ft}_r{nr}(int, int, hipStream_t, const DeviceProblem*, const SolveArgs&, const TapArgs*);"
-                             for nt, nr, ft in WOOD_ROWS)
-    decls += "\n" + "\n".join(f"void launch_{nt}_{ft}_w3(int, int, hipStream_t, const DeviceProblem*, const SolveArgs&, const TapArgs*);"
-                             for nt, ft in W3)
-    decls += "\n" + "\n".join(f"void launch_{nt}_{ft}_r{nr}_w3(int, int, hipStream_t, const DeviceProblem*, const SolveArgs&, const TapArgs*);"
-                             for nt, nr, ft in W3_WOOD)
-    cases0 = "\n".join(f"  if (one_shot && w3 && nt == {nt} && nr == {nr} && feat == {ft}) {{ launch_{nt}_{ft}_r{nr}_w3o(grid, lds_bytes, stream, P, a, taps); return 0; }}"
-                       for nt, nr, ft in W3_WOOD_ONE_SHOT)
-    cases0 += "\n  if (one_shot) return -1;\n"
-    cases0 += "\n".join(f"  if (w3 && nt == {nt} && nr == {nr} && feat == {ft}) {{ launch_{nt}_{ft}_r{nr}_w3(grid, lds_bytes, stream, P, a, taps); return 0; }}"
-                       for nt, nr, ft in W3_WOOD)
-    cases = cases0 + "\n" + "\n".join(f"  if (w3 && nt == {nt} && nr == 0 && feat == {ft}) {{ launch_{nt}_{ft}_w3(grid, lds_bytes, stream, P, a, taps); return 0; }}"
-                      for nt, ft in W3)
-    cases += "\n" + "\n".join(f"  if (nt == {nt} && nr == 0 && feat == {ft}) {{ launch_{nt}_{ft}(grid, lds_bytes, stream, P, a, taps); return 0; }}"
-                      for nt in NTS for ft in FEATS)
-    cases += "\n" + "\n".join(f"  if (nt == {nt} && nr == {nr} && feat == {ft}) {{ launch_{nt}_{ft}_r{nr}(grid, lds_bytes, stream, P, a, taps); return 0; }}"
-                              for nt, nr in WOOD for ft in WOOD_FEATS)
-    cases += "\n" + "\n".join(f"  if (nt == {nt} && nr == {nr} && feat == {ft}) {{ launch_{nt}_{ft}_r{nr}(grid, lds_bytes, stream, P, a, taps); return 0; }}"
-                              for nt, nr, ft in WOOD_ROWS)
-    _write_if_changed(os.path.join(BUILD, "dispatch.hip"), f"""// generated by build.py
+    for v in VARIANTS:
+        _write_if_changed(os.path.join(BUILD, f"variant_{v.name}.hip"), v.translation_unit())
+        srcs.append(f"variant_{v.name}")
+    decls = "\n".join(f"void launch_{v.name}(int, int, hipStream_t, const DeviceProblem*, const SolveArgs&, const TapArgs*);" for v in VARIANTS)
+    rows = "\n".join(f'    {{{v.nt}, {v.nr}, {v.feat}, {str(v.w3).lower()}, {str(v.one_shot).lower()}, "ik_solve_kernel_{v.name}", &launch_{v.name}}},'
+                     for v in VARIANTS)
+    _write_if_changed(os.path.join(BUILD, "dispatch.hip"), f"""// generated by build.py: the table of compiled kernel variants (variants.h)
 #include <hip/hip_runtime.h>
-#include "../mkh_types.h"
+#include "../variants.h"
 namespace mkh {{
 {decls}
-int launch_variant(int nt, int nr, int feat, bool w3, int grid, int lds_bytes, hipStream_t stream, const DeviceProblem* P,
-                   const SolveArgs& a, const TapArgs* taps, bool one_shot) {{
-{cases}
-  return -1;
+const VariantRow* variant_table() {{
+  static const VariantRow table[] = {{
+{rows}
+  }};
+  return table;
 }}
+const int kNumVariants = {len(VARIANTS)};
 }}  // namespace mkh
 """)
     srcs.append("dispatch")
@@ -379,7 +306,6 @@ def build(force: bool = False, verbose: bool = True) -> str:
             return obj, False
         r = subprocess.run(cmd + ["-MD", "-MF", obj + ".d", "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", obj],
                            stdout=subprocess.DEVNULL if not verbose else None, stderr=subprocess.PIPE, text=True)
-        rest = [ln for ln in r.stderr.split("\n") if "kernel-resource-usage" not in ln]
         if r.returncode != 0:
             sys.stderr.write(r.stderr)
             raise subprocess.CalledProcessError(r.returncode, cmd)
@@ -387,12 +313,15 @@ def build(force: bool = False, verbose: bool = True) -> str:
             json.dump(_parse_resource_remarks(r.stderr), fh)
         with open(obj + ".cmd", "w") as fh:
             fh.write(tag)
-        del rest
         return obj, True
 
     if verbose:
         print(f"[mink_amd] {len(jobs)} translation units for gfx950 (recompiling what changed) ...", flush=True)
-    with concurrent.futures.ThreadPoolExecutor(max_workers=os.cpu_count() or 4) as ex:
+    # (MAX_JOBS, when set: what a shared machine allows this build — os.cpu_count() is the whole machine)
+    workers = os.cpu_count() or 4
+    if os.environ.get("MAX_JOBS", "").isdigit() and int(os.environ["MAX_JOBS"]) > 0:
+        workers = min(workers, int(os.environ["MAX_JOBS"]))
+    with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as ex:
         res = list(ex.map(compile_one, jobs))
     objs = [o for o, _ in res]
     if verbose:

@@ -64,7 +64,7 @@
 // real and rarely taken call of its own: overlap_pair).  Measured on `ur5e_convex` (4 096 instances, one cylinder–box pair):
 // the phase INLINED on the 32-row map 0.178 ms / 27 MB of HBM traffic; as a call on the 32-row map 0.186 ms / 88 MB (its
 // prologue still saves ≈50 callee-saved VGPRs per problem); as a call on the 16-row three-waves map 0.156 ms — kept
-// (minkhip.hip launch(): calls_nt_min).  -DMKH_INLINE_136 builds the inlined variant for A/B runs.
+// (minkhip.hip plan_launch(): calls_nt_min).  -DMKH_INLINE_136 builds the inlined variant for A/B runs.
 #if defined(MKH_W3) || (defined(MKH_FEAT) && (MKH_FEAT & 8) && !(MKH_FEAT & 1) && !(MKH_FEAT & 64) && (!(MKH_FEAT & 128) || !defined(MKH_INLINE_136)))
 #define MKH_CALLS 1
 #endif
@@ -351,6 +351,38 @@ constexpr bool kTapIsProf_t_xpos = false, kTapIsProf_t_xquat = false, kTapIsProf
 enum : int { F_TAPS = 1, F_REL = 2, F_COM = 4, F_COLL = 8, F_STEPS = 16, F_ALL = 31, F_WOOD = 32, F_SIMPLE_COLL = 64, F_CONVEX_COLL = 128,
               F_DENSE = 256 };   // F_DENSE alone: the lean build of the plugin route (dense task / limit rows next to frame + posture tasks and box limits)
 
+// The LDS layout of ONE BUILD (NT, NR, FEAT, one-more-wave map) for a descriptor P0: the kernel indexes it (kernel_lds_layout,
+// with its compile-time constants) and the host reserves its `total` (minkhip.hip lds_bytes_of) — one statement, so the two
+// cannot disagree.  `prefetch` (second input buffers) and `compact` (the compact layout of a two-waves low-rank build) are the
+// two choices the host tries both ways, 0 / 1, before it fixes them in the descriptor; kFromDescriptor: as fixed there — which
+// of the descriptor's prefetch flags belongs to which layout is part of this statement (layout_prefetch).
+// (The descriptor's fields are read in the order of lds_layout's arguments, the two choices included: the order of these scalar
+//  loads decides the compiler's schedule of the kernels' prologues, and the device code is pinned by hash.)
+constexpr int kFromDescriptor = -1;
+template <class PT>
+__host__ __device__ __forceinline__ bool layout_prefetch(const PT& P0, int feat, bool w3) {
+  const bool wood = (feat & F_WOOD) != 0;
+  const bool wood_rows = wood && (feat & (F_COLL | F_DENSE)) != 0;    // low-rank start with half-space rows: its own layout
+  if (w3) return (wood ? P0.prefetch_w3w : P0.prefetch_w3) != 0;
+  return ((wood_rows || (wood && P0.wood_compact != 0)) ? P0.prefetch_wc : P0.prefetch) != 0;
+}
+template <class PT>
+__host__ __device__ __forceinline__ LdsLayout build_lds_layout(const PT& P0, int nt, int nr, int feat, bool w3, int prefetch = kFromDescriptor,
+                                                               int compact = kFromDescriptor) {
+  const bool wood = (feat & F_WOOD) != 0;
+  const bool wood_rows = wood && (feat & (F_COLL | F_DENSE)) != 0;
+  return lds_layout(P0.nq, P0.nv, P0.nbody, P0.njnt, P0.n_frame, P0.n_posture, P0.n_com, P0.max_rows,
+                    wood ? P0.n_jrows + 1 : 6, wood ? nr : j_stride_direct(P0.nv, nt),
+                    // the S block: in the dof stash where it fits — never with half-space rows (collision_phase reads the axes again after the QP)
+                    (wood && (wood_rows || !wood_s_aliases_dof(P0.nv, P0.n_jrows, lds_even(P0.n_jrows), P0.n_com > 0 ? P0.nbody : 0)))
+                        ? P0.n_jrows * (lds_even(P0.n_jrows) + 1) : 0,
+                    prefetch < 0 ? layout_prefetch(P0, feat, w3) : prefetch != 0,
+                    !wood_rows && (w3 || (wood && (compact < 0 ? P0.wood_compact != 0 : compact != 0))), wood,
+                    (feat & F_COLL) ? P0.n_hsel : 0,        // (a compile-time 0 without collision rows: one value less to keep)
+                    wood_rows || (w3 && wood && (feat & F_COM) != 0),   // (piv_small: ... and the F_COM builds with one more resident wave)
+                    wood_rows);
+}
+
 // P lives in device memory (not in the kernarg segment): hipcc materialises every by-value kernel
 // argument field in SGPRs at kernel entry and keeps it there, which starved the QP loop of SGPRs
 // (580 SGPR spills, v_readlane results serialised through one SGPR pair).
@@ -450,37 +482,18 @@ __device__ __forceinline__ bool kernel_prefetch(const PT& P0) {
   return ((kWoodRows || (kWood && P0.wood_compact != 0)) ? P0.prefetch_wc : P0.prefetch) != 0;
 #endif
 }
-template <class PT>
-__device__ __forceinline__ LdsLayout kernel_lds_layout(const PT& P0) {
-  constexpr int NT = MKH_NT, FEAT = MKH_FEAT;
-  constexpr bool kWood = (FEAT & F_WOOD) != 0;
+// this build's layout (build_lds_layout, one call deep: a wrapper function of its own changed the 48-row kernels' code)
 #ifdef MKH_NR
-  constexpr int NR = MKH_NR;
+#define MKH_LAYOUT_NR MKH_NR
 #else
-  constexpr int NR = NT;
+#define MKH_LAYOUT_NR MKH_NT
 #endif
 #ifdef MKH_W3
-  constexpr bool kCompact = true;            // LDS ranges aliased by phase (lds_layout): 12 waves per CU need ≤ 13.3 KB each
+#define MKH_LAYOUT_W3 true
 #else
-  constexpr bool kCompact = false;
+#define MKH_LAYOUT_W3 false
 #endif
-  constexpr bool kWoodRows = kWood && (FEAT & (F_COLL | F_DENSE)) != 0;
-  if constexpr (kWoodRows)     // (S never shares the dof stash here: collision_phase reads the axes again after the QP)
-    return lds_layout(P0.nq, P0.nv, P0.nbody, P0.njnt, P0.n_frame, P0.n_posture, P0.n_com, P0.max_rows, P0.n_jrows + 1, NR,
-                      P0.n_jrows * (lds_even(P0.n_jrows) + 1), kernel_prefetch(P0), false, true, (FEAT & F_COLL) ? P0.n_hsel : 0, true, true);
-  return lds_layout(P0.nq, P0.nv, P0.nbody, P0.njnt, P0.n_frame, P0.n_posture, P0.n_com, P0.max_rows,
-                    kWood ? P0.n_jrows + 1 : 6, kWood ? NR : j_stride_direct(P0.nv, NT),
-                    (kWood && !wood_s_aliases_dof(P0.nv, P0.n_jrows, lds_even(P0.n_jrows), P0.n_com > 0 ? P0.nbody : 0))
-                        ? P0.n_jrows * (lds_even(P0.n_jrows) + 1) : 0,
-                    kernel_prefetch(P0), kCompact || (kWood && P0.wood_compact != 0), kWood,
-                    (FEAT & F_COLL) ? P0.n_hsel : 0,        // (a compile-time 0 without collision rows: one value less to keep)
-#if defined(MKH_W3) && (MKH_FEAT & 4) && (MKH_FEAT & 32)
-                    true
-#else
-                    false
-#endif
-                    );
-}
+#define kernel_lds_layout(P0) build_lds_layout(P0, MKH_NT, MKH_LAYOUT_NR, MKH_FEAT, MKH_LAYOUT_W3)
 __device__ MKH_PRE_ATTR PreOut pre_phases(const DeviceProblem* Pq, const TapArgs* tp, int pb, int oz, int off_q, int off_tgt,
                                           bool until, double pos_thr, double ori_thr MKH_PRE_TC_PARAMS) {
   constexpr int FEAT = MKH_FEAT;

@@ -20,6 +20,7 @@
 
 #include "ik_kernel.h"
 #include "lane_kernel.h"
+#include "variants.h"
 #include "wide_types.h"
 
 namespace mkh {
@@ -213,12 +214,10 @@ struct MkhProblem {
   GrowBuf ms_in_q, ms_in_ft, ms_in_pt, ms_in_ct, ms_in_ref, ms_in_w, ms_out_q, ms_out_v, ms_out_i32;   // B rows
 };
 
-// Kernel variants live in their own translation units (mink_amd/csrc/build.py generates one
-// variant_<NT>_<FEAT>.hip per compiled combination so that they build in parallel); this is the
-// generated dispatcher.
+// The wavefront kernel's variants live in their own translation units (mink_amd/csrc/build.py generates one variant_<name>.hip
+// per compiled combination so that they build in parallel) and are reached through the generated table of variants.h; these are
+// the launchers of the other kernels.
 namespace mkh {
-int launch_variant(int nt, int nr, int feat, bool w3, int grid, int lds_bytes, hipStream_t stream, const DeviceProblem* P,
-                   const SolveArgs& a, const TapArgs* taps, bool one_shot = false);
 int launch_lane(int nv_max, bool loop, int grid, int lds_bytes, hipStream_t stream, const LaneProblem* P, const SolveArgs& a);
 int launch_quad(int nt, bool loop, int grid, hipStream_t stream, const void* P, const LaneDims& dims, const SolveArgs& a);   // returns its LDS bytes per wavefront
 int launch_wide(int grid, int lds_bytes, hipStream_t stream, const WideProblem* P, const SolveArgs& a, const TapArgs* taps, bool convex);
@@ -232,7 +231,7 @@ hipError_t launch_ms_select(hipStream_t stream, int B, int S, int nq, int nv, in
                             const double* q_ref, const double* weights, double* q_best, double* v_best, int32_t* iters,
                             int32_t* status, int32_t* converged, int32_t* seed_index, int32_t* n_converged);
 constexpr int kLaneMinBatchLoop = 28672;  // fused loops of a small arm: row kernel below, lane kernel from here (M targets/s at 16 384: 39.7 vs 24.1, at 32 768: 42.4 vs 48.2)
-constexpr int kLaneMinBatch = 73728;  // plain solves of a small arm: row kernel below, lane kernel from here (launch())
+constexpr int kLaneMinBatch = 73728;  // plain solves of a small arm: row kernel below, lane kernel from here (plan_launch())
 }
 
 // Descriptor of the row- and lane-per-problem kernels (quad_kernel.h, lane_kernel.h) of a problem that qualifies: nv ≤ 16
@@ -451,6 +450,16 @@ static int waves_per_cu(int nt, int lds_bytes, bool w3 = false) {
   const int w = by_lds < by_regs ? by_lds : by_regs;
   return w < 1 ? 1 : w;
 }
+
+// LDS bytes per wavefront of one build (nt, nr, feat, one-more-wave map) on descriptor D: the `total` of the layout that build's
+// kernel indexes (ik_kernel.h build_lds_layout — kernel_lds_layout calls the same function with its compile-time constants).
+// (prefetch, compact: 0 / 1 while mkh_problem_create tries them; kFromDescriptor once they are fixed in D)
+static int lds_bytes_of(const DeviceProblem& D, int nt, int nr, int feat, bool w3, int prefetch = kFromDescriptor, int compact = kFromDescriptor) {
+  return build_lds_layout(D, nt, nr, feat, w3, prefetch, compact).total * (int)sizeof(double);
+}
+// The two-waves direct-start builds share one reservation per tableau size, whatever their features: the one with collision
+// rows, whose layout ends with the pair-selection block (DeviceProblem::n_hsel — 0 in a problem without pairs).
+constexpr int kDirectFeat = F_COLL;
 
 template <class T>
 static hipError_t ensure(T** buf, size_t n) {
@@ -1154,11 +1163,8 @@ int32_t mkh_problem_create_diag(MkhModel* m, const MkhProblemDesc* d, int32_t ma
     if (p->use_cull) P.n_hsel += lds_even((P.n_pairs + 3) / 4);
   }
   const int ntab = m->nv + P.max_rows;
-  {
-    static const int kVariants[] = {8, 16, 24, 32, 44, 48, 64};
-    p->nt = 64;
-    for (int v : kVariants) if (ntab <= v) { p->nt = v; break; }
-  }
+  p->nt = size_class(ntab, 0);       // (ntab ≤ kWave by the cap on max_rows above: the largest build holds it)
+  if (!p->nt) return bail(fail(MKH_E_LIMIT, "no kernel variant with %d tableau rows", ntab));
 
   hipError_t e = hipSuccess;
   if (e == hipSuccess) e = upload(ft, &p->d_frame);
@@ -1179,10 +1185,7 @@ int32_t mkh_problem_create_diag(MkhModel* m, const MkhProblemDesc* d, int32_t ma
   p->nt_full = p->nt < 32 ? 32 : p->nt;
   // Second LDS buffers for the next problem's inputs (ik_kernel.h "load inputs") only where they do not cost a
   // resident wave in the lean or the all-feature variant of this problem (the low-rank variant is checked below).
-  auto lds_of = [&](int nt, bool pre) {
-    return lds_layout(P.nq, P.nv, P.nbody, P.njnt, P.n_frame, P.n_posture, P.n_com, P.max_rows, 6, j_stride_direct(P.nv, nt), 0, pre, false, false, P.n_hsel).total *
-           (int)sizeof(double);
-  };
+  auto lds_of = [&](int nt, bool pre) { return lds_bytes_of(P, nt, 0, kDirectFeat, false, pre); };
   P.prefetch = (waves_per_cu(p->nt, lds_of(p->nt, true)) == waves_per_cu(p->nt, lds_of(p->nt, false)) &&
                 waves_per_cu(p->nt_full, lds_of(p->nt_full, true)) == waves_per_cu(p->nt_full, lds_of(p->nt_full, false))) ? 1 : 0;
   p->lds_bytes = lds_of(p->nt, P.prefetch != 0);
@@ -1190,14 +1193,11 @@ int32_t mkh_problem_create_diag(MkhModel* m, const MkhProblemDesc* d, int32_t ma
   p->blocks_per_cu = waves_per_cu(p->nt, p->lds_bytes);
   p->lds_bytes_full = lds_of(p->nt_full, P.prefetch != 0);
   if (p->blocks_per_cu < 1) p->blocks_per_cu = 1;
-  // 3 waves per SIMD: tableau sizes with a TabW3 map (build.py W3), no half-space rows (the compact layout lets the
+  // 3 waves per SIMD: tableau sizes with a lean build on the TabW3 map, no half-space rows (the compact layout lets the
   // Jacobian rows reuse the body poses, which the collision phase still reads), and 12 wavefronts' LDS must fit the CU
   P.prefetch_w3 = 0;
-  if (p->nt == 44 && P.max_rows == 0 && P.n_dense_rows == 0) {
-    auto lds_w3 = [&](bool pre) {
-      return lds_layout(P.nq, P.nv, P.nbody, P.njnt, P.n_frame, P.n_posture, P.n_com, P.max_rows, 6, j_stride_direct(P.nv, p->nt), 0,
-                        pre, true).total * (int)sizeof(double);
-    };
+  if (find_variant(p->nt, 0, 0, true) && P.max_rows == 0 && P.n_dense_rows == 0) {
+    auto lds_w3 = [&](bool pre) { return lds_bytes_of(P, p->nt, 0, 0, true, pre); };
     if (waves_per_cu(p->nt, lds_w3(false), true) == 12) {
       P.prefetch_w3 = waves_per_cu(p->nt, lds_w3(true), true) == 12 ? 1 : 0;
       p->lds_bytes_w3 = lds_w3(P.prefetch_w3 != 0);
@@ -1258,7 +1258,7 @@ int32_t mkh_problem_create_diag(MkhModel* m, const MkhProblemDesc* d, int32_t ma
     }
     return true;
   };
-  // what the low-rank start's stability criterion compares (launch(): damping + the smallest posture diagonal against the largest
+  // what the low-rank start's stability criterion compares (plan_launch(): damping + the smallest posture diagonal against the largest
   // task cost²)
   auto wood_scales = [&]() {
     double mn = __builtin_huge_val();
@@ -1280,10 +1280,9 @@ int32_t mkh_problem_create_diag(MkhModel* m, const MkhProblemDesc* d, int32_t ma
       P.n_dense_limit_rows == 0 && P.n_jrows <= kMuBig) {
     // (NT = NR: the task residuals are eliminated outside the tableau, one column of [S | Jh] per lane — wood_start; the
     //  S columns sit on lanes [NR, NR + n_μ) or, when those do not exist, on lanes [0, n_μ) in a second register set)
-    static const int kWoodVariants[] = {16, 24, 32, 44, 48};
     int cand = 0;
-    for (int v : kWoodVariants)
-      if (m->nv <= v && (v + P.n_jrows <= kWave || P.n_jrows <= v)) { cand = v; break; }
+    for (int v = size_class(m->nv, F_WOOD, true); v && !cand; v = size_class(v + 1, F_WOOD, true))
+      if (v + P.n_jrows <= kWave || P.n_jrows <= v) cand = v;
     const bool big = P.n_jrows > kMu || cand + P.n_jrows > kWave;
     // When it pays.  Fewer task rows than dofs by a margin — half, three quarters for humanoid-size tableaus — measured in
     // rounds 1-2 on arms, hands and the G1; round 4 (tools/bench_wood_criterion.py, H1 / Go1 / Spot / Allegro / Shadow with
@@ -1295,50 +1294,45 @@ int32_t mkh_problem_create_diag(MkhModel* m, const MkhProblemDesc* d, int32_t ma
     if (cand && pays) { p->wood_nt = cand; p->wood_nr = cand; }
     if (p->wood_nt) {
       p->wood_big = P.n_jrows > kMu || p->wood_nr + P.n_jrows > kWave;
-      const int sp = lds_even(P.n_jrows);
-      auto lds_wood = [&](bool pre, bool compact, bool piv_small = false) {
-        return lds_layout(P.nq, P.nv, P.nbody, P.njnt, P.n_frame, P.n_posture, P.n_com, P.max_rows, P.n_jrows + 1, p->wood_nr,
-                          wood_s_aliases_dof(P.nv, P.n_jrows, sp, P.n_com > 0 ? P.nbody : 0) ? 0 : P.n_jrows * (sp + 1),
-                          pre, compact, true, 0, piv_small);
-      };
+      // (two-waves map: plain or compact layout; one-more-wave map: always compact, one pivot buffer on the F_COM builds)
+      auto lds_wood = [&](bool pre, bool compact) { return lds_bytes_of(P, p->wood_nt, p->wood_nr, F_WOOD, false, pre, compact); };
+      auto lds_wood_w3 = [&](int feat, bool pre) { return lds_bytes_of(P, p->wood_nt, p->wood_nr, feat, true, pre); };
       // 2-waves map: the plain layout, or — when that would cost a resident wave and the pair lanes need one pass only (the
       // compact layout lets the Jacobian rows overwrite the task blocks) — the compact one
       P.wood_compact = 0; P.prefetch_wc = 0;
       P.wood_refine = (p->diag & MKH_DIAG_NO_COLD_REFINE) ? 0 : 1;
       {
-        auto bytes = [&](bool pre, bool compact) { return lds_wood(pre, compact).total * (int)sizeof(double); };
-        if (waves_per_cu(p->wood_nt, bytes(false, false)) < waves_per_cu(p->wood_nt, 1) && P.n_jrows > 0) {
+        if (waves_per_cu(p->wood_nt, lds_wood(false, false)) < waves_per_cu(p->wood_nt, 1) && P.n_jrows > 0) {
           int n_jp = 0;
           for (size_t t = 0; t < ft.size(); ++t) n_jp += __builtin_popcountll(ft[t].dof_mask);
-          if (n_jp <= kWave && waves_per_cu(p->wood_nt, bytes(false, true)) > waves_per_cu(p->wood_nt, bytes(false, false))) {
+          if (n_jp <= kWave && waves_per_cu(p->wood_nt, lds_wood(false, true)) > waves_per_cu(p->wood_nt, lds_wood(false, false))) {
             P.wood_compact = 1;
-            P.prefetch_wc = waves_per_cu(p->wood_nt, bytes(true, true)) == waves_per_cu(p->wood_nt, bytes(false, true)) ? 1 : 0;
+            P.prefetch_wc = waves_per_cu(p->wood_nt, lds_wood(true, true)) == waves_per_cu(p->wood_nt, lds_wood(false, true)) ? 1 : 0;
           }
         }
       }
-      const LdsLayout Lw = P.wood_compact ? lds_wood(P.prefetch_wc != 0, true) : lds_wood(P.prefetch != 0, false);
+      p->wood_lds_bytes = P.wood_compact ? lds_wood(P.prefetch_wc != 0, true) : lds_wood(P.prefetch != 0, false);
       if (!wood_tables()) p->wood_nt = 0;
-      p->wood_lds_bytes = Lw.total * (int)sizeof(double);
       if (p->wood_lds_bytes * 8 > 160 * 1024) p->wood_nt = 0;      // would cost residency
       // 3 waves per SIMD (compact layout: the Jacobian rows overwrite the task blocks, so the pair lanes need one pass)
       P.prefetch_w3w = 0;
-      if (p->wood_nt != 48 && P.n_jpairs <= kWave && P.n_com == 0 && !p->wood_big) {   // (build.py W3_WOOD: 16, 24, 32, 44)
+      if (find_variant(p->wood_nt, p->wood_nr, F_WOOD, true) && P.n_jpairs <= kWave && P.n_com == 0 && !p->wood_big) {
         const int full = waves_per_cu(p->wood_nt, 1, true);     // 16 waves per CU for NT ≤ 24, else 12
-        if (waves_per_cu(p->wood_nt, lds_wood(false, true).total * (int)sizeof(double), true) == full) {
-          P.prefetch_w3w = waves_per_cu(p->wood_nt, lds_wood(true, true).total * (int)sizeof(double), true) == full ? 1 : 0;
-          p->wood_lds_bytes_w3 = lds_wood(P.prefetch_w3w != 0, true).total * (int)sizeof(double);
+        if (waves_per_cu(p->wood_nt, lds_wood_w3(F_WOOD, false), true) == full) {
+          P.prefetch_w3w = waves_per_cu(p->wood_nt, lds_wood_w3(F_WOOD, true), true) == full ? 1 : 0;
+          p->wood_lds_bytes_w3 = lds_wood_w3(F_WOOD, P.prefetch_w3w != 0);
         }
       }
       // ... and the F_COM builds of a humanoid-size robot (ComTask rows and / or up to 24 task rows: `44_36_r44_w3`, round 5).
       // Their 25 rows of Jh take 8.8 KB of the compact layout — 15.4 KB for the G1 full example, 10 wavefronts per CU instead
       // of 8 — so the bar is "more resident wavefronts than the two-waves map", not all twelve.
       static const bool no_com_w3 = dbg_env("MKH_DEBUG_NO_COM_W3") != nullptr;       // (A/B switch)
-      if (!no_com_w3 && p->wood_nt == 44 && P.n_jpairs <= kWave && (P.n_com > 0 || p->wood_big)) {
+      if (!no_com_w3 && find_variant(p->wood_nt, p->wood_nr, F_WOOD | F_COM, true) && P.n_jpairs <= kWave && (P.n_com > 0 || p->wood_big)) {
         const int two = waves_per_cu(p->wood_nt, 1, false);     // 8
-        const int w = waves_per_cu(p->wood_nt, lds_wood(false, true, true).total * (int)sizeof(double), true);
+        const int w = waves_per_cu(p->wood_nt, lds_wood_w3(F_WOOD | F_COM, false), true);
         if (w >= two + 2) {                                   // (nine per CU — 3 + 2 + 2 + 2 — measured SLOWER than eight: 1.51 vs 1.44 ms)
-          P.prefetch_w3w = waves_per_cu(p->wood_nt, lds_wood(true, true, true).total * (int)sizeof(double), true) == w ? 1 : 0;
-          p->wood_lds_bytes_w3 = lds_wood(P.prefetch_w3w != 0, true, true).total * (int)sizeof(double);
+          P.prefetch_w3w = waves_per_cu(p->wood_nt, lds_wood_w3(F_WOOD | F_COM, true), true) == w ? 1 : 0;
+          p->wood_lds_bytes_w3 = lds_wood_w3(F_WOOD | F_COM, P.prefetch_w3w != 0);
         }
       }
       wood_scales();
@@ -1353,10 +1347,7 @@ int32_t mkh_problem_create_diag(MkhModel* m, const MkhProblemDesc* d, int32_t ma
       P.n_dense_limit_rows == 0 && !P.dense_box && !p->simple_pairs && !p->convex_pairs) {
     if (wood_tables() && P.n_jpairs <= kWave) { p->woodr_tables = true; wood_scales(); }
   }
-  auto woodr_bytes = [&](const DeviceProblem& D, bool pre) {
-    return lds_layout(D.nq, D.nv, D.nbody, D.njnt, D.n_frame, D.n_posture, D.n_com, D.max_rows, D.n_jrows + 1, 48,
-                      D.n_jrows * (lds_even(D.n_jrows) + 1), pre, false, true, D.n_hsel, true, true).total * (int)sizeof(double);
-  };
+  auto woodr_bytes = [&](const DeviceProblem& D, bool pre) { return lds_bytes_of(D, 48, 48, F_WOOD | F_COLL, false, pre); };
   if (p->woodr_tables && p->nt == 48 && P.max_rows <= 8) {
     P.prefetch_wc = waves_per_cu(48, woodr_bytes(P, true)) == waves_per_cu(48, woodr_bytes(P, false)) ? 1 : 0;
     p->woodr_lds = woodr_bytes(P, P.prefetch_wc != 0);
@@ -1409,10 +1400,7 @@ int32_t mkh_problem_create_diag(MkhModel* m, const MkhProblemDesc* d, int32_t ma
       T.max_rows = cap;
       T.n_hsel = lds_even(T.n_pairs) + (p->use_cull ? lds_even((T.n_pairs + 3) / 4) : 0);
       T.nt = 48;
-      auto lds_t = [&](bool pre) {
-        return lds_layout(T.nq, T.nv, T.nbody, T.njnt, T.n_frame, T.n_posture, T.n_com, T.max_rows, 6, j_stride_direct(T.nv, 48), 0, pre,
-                          false, false, T.n_hsel).total * (int)sizeof(double);
-      };
+      auto lds_t = [&](bool pre) { return lds_bytes_of(T, 48, 0, kDirectFeat, false, pre); };
       T.prefetch = waves_per_cu(48, lds_t(true)) == waves_per_cu(48, lds_t(false)) ? 1 : 0;
       p->nt_tight = 48;
       p->lds_tight = lds_t(T.prefetch != 0);
@@ -1500,13 +1488,6 @@ static int grid_for(const MkhProblem* p, int B) {
   int g = p->model->num_cus * p->blocks_per_cu;
   return B < g ? B : g;
 }
-// LDS bytes of the plain (direct-start) layout of this problem with an nt-row tableau (the kernel computes the same layout
-// from its own NT: ik_kernel.h kernel_lds_layout)
-static int lds_for_nt(const MkhProblem* p, int nt) {
-  const DeviceProblem& P = p->dev;
-  return lds_layout(P.nq, P.nv, P.nbody, P.njnt, P.n_frame, P.n_posture, P.n_com, P.max_rows, 6, j_stride_direct(P.nv, nt), 0,
-                    P.prefetch != 0, false, false, P.n_hsel).total * (int)sizeof(double);
-}
 
 // Static rounds of a wavefront kernel's problem distribution (ik_kernel.h): each wavefront first walks `static` problems of its
 // XCD's contiguous row range, the rest of the batch goes through the ticket counter.  Static rows share cache lines inside one
@@ -1586,49 +1567,48 @@ static hipError_t clk_end(MkhProblem* p, int B, hipStream_t stream) {
   return hipSuccess;
 }
 
-static int32_t launch(MkhProblem* p, const SolveArgs& a_in, const TapArgs* taps, hipStream_t stream, int32_t flags) {
-  // (the kernel choice must not depend on whether the caller wants the status: a call without status_out on a handle with a
-  //  tight-rows build keeps it in a buffer of the handle — round-3 advisor finding)
-  SolveArgs a = a_in;
-  if (!a.status_out && p->d_status_tight && a.do_qp) a.status_out = p->d_status_tight;
+// ---- launch planning: what a call runs (kernel family, build, grid, LDS bytes, ticket share), decided apart from running it
+enum class Family { WideOnly, Row, Lane, Wave };
+struct WaveLaunch {                // one launch of an ik_solve_kernel build
+  int nt = 0, nr = 0, feat = 0;
+  bool w3 = false, one_shot = false;
+  int grid = 0, lds = 0, static_rounds = INT32_MAX;
+  const VariantRow* v = nullptr;   // its row of the table (variants.h); null: not compiled — launch() reports it
+};
+struct LaunchPlan {
+  Family family = Family::Wave;
+  bool loop = false;               // row / lane kernels: the fused caller loop (steps / until) build
+  WaveLaunch main;                 // wavefront family: the launch on the handle's descriptor ...
+  WaveLaunch tight;                // ... and, when has_tight, the tight-rows launch in front of it (p->d_dev_tight)
+  bool has_tight = false, tight_redo = false;   // tight_redo: `main` follows as the redo launch of what `tight` flagged
+  bool cv_split = false;           // convex_contacts_kernel in front of the analytic collision build
+  bool wide_redo = false;          // the workgroup-per-problem kernel behind, on the flagged instances
+  bool keep_q = false;             // ... which then needs the call's q as it came (q_out aliases it)
+  char last_kernel[64] = "";       // what mkh_problem_last_kernel / mkh_problem_launch_info report after the call
+  int last_grid = 0, last_lds = 0, last_nt = 0, last_block = kWave;
+};
+
+static void plan_name(LaunchPlan& L, const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(L.last_kernel, sizeof L.last_kernel, fmt, ap);
+  va_end(ap);
+}
+static const char* wave_name(const WaveLaunch& w) { return w.v ? w.v->kernel : "(not compiled)"; }
+
+// Fills the plan of one call.  Calls nothing of HIP and writes nothing to the handle: launch() below executes it.
+// (`taps`: the host copy of the call's tap pointers, or null)
+static int32_t plan_launch(const MkhProblem& P_, const SolveArgs& a, const TapArgs* taps, int32_t flags, LaunchPlan& L) {
+  const MkhProblem* p = &P_;
   if (p->wide_only) {
     if (taps && taps->t_cycles)
       return fail(MKH_E_INVALID, "models beyond one wavefront (more than 64 bodies or dofs) run on the workgroup-per-problem kernel, "
                                  "which has no cycle-counter tap");
-    const TapArgs* dt_ = nullptr;
-    if (taps) {
-      HIP_OK(hipMemcpyAsync(p->d_taps, taps, sizeof(TapArgs), hipMemcpyHostToDevice, stream));
-      HIP_OK(hipStreamSynchronize(stream));
-      dt_ = p->d_taps;
-    }
-    snprintf(p->last_kernel, sizeof(p->last_kernel), "ik_wide_kernel");
-    p->last_grid = p->wide_grid < a.B ? p->wide_grid : a.B; p->last_lds = p->wide_lds; p->last_nt = p->wide.nv + p->wide.max_rows;
-    p->last_block = kWideThreads;
-    HIP_OK(clk_begin(p, a, stream));                         // (MKH_DEBUG_CLOCKS=<file>: phase stamps of every problem, tools/wide_phase_clocks.py)
-    const int32_t rcw = launch_wide_kernel(p, a, stream, 0, dt_);
-    if (rcw == MKH_OK) HIP_OK(clk_end(p, a.B, stream));
-    return rcw;
-  }
-  // A problem whose rows can outnumber the tableau's: the flagged instances once more, with every row — plain solves, calls
-  // with taps (the workgroup-per-problem kernel writes every tap but the cycle counters) and, round 5, the fused loops: an
-  // instance that overflows at some step runs its whole loop again from its ORIGINAL q, of which the handle keeps a copy for
-  // the duration of the call (q_out may alias q) — a device-to-device copy of B·nq doubles in front of the launch
-  const bool wide_redo = p->d_wide && a.do_qp && a.status_out && !(taps && taps->t_cycles);
-  const double* q_redo = a.q;
-  // (only when q_out really aliases q: otherwise the redo reads the caller's q, which the first launch did not touch — the copy
-  //  was a latency cost of every small-batch control loop with collision limits, round-5 advisor finding)
-  if (wide_redo && a.q_out && a.q_out == a.q) {
-    HIP_OK(ensure(&p->d_qkeep, (size_t)p->max_batch * p->dev.nq));
-    HIP_OK(hipMemcpyAsync(p->d_qkeep, a.q, (size_t)a.B * p->dev.nq * sizeof(double), hipMemcpyDefault, stream));
-    q_redo = p->d_qkeep;
-  }
-  p->last_block = kWave;
-  (void)hipGetLastError();          // a stale error of an unrelated earlier runtime call must not be blamed on this launch
-  const TapArgs* dtaps = nullptr;
-  if (taps) {
-    HIP_OK(hipMemcpyAsync(p->d_taps, taps, sizeof(TapArgs), hipMemcpyHostToDevice, stream));
-    HIP_OK(hipStreamSynchronize(stream));   // taps are a debug path: keep the host struct's lifetime simple
-    dtaps = p->d_taps;
+    L.family = Family::WideOnly;
+    plan_name(L, "ik_wide_kernel");
+    L.last_grid = p->wide_grid < a.B ? p->wide_grid : a.B; L.last_lds = p->wide_lds; L.last_nt = p->wide.nv + p->wide.max_rows;
+    L.last_block = kWideThreads;
+    return MKH_OK;
   }
   // Small arms (nv ≤ 8, hinge / slide joints, box limits) have two kernels of their own (plain solves without taps):
   //   * a 16-lane ROW per problem (quad_kernel.h): four problems per wavefront, so 4 096 problems put one wavefront on
@@ -1646,6 +1626,7 @@ static int32_t launch(MkhProblem* p, const SolveArgs& a_in, const TapArgs* taps,
   const bool small_ok = !taps && a.do_qp && !(flags & MKH_FLAG_WAVE_KERNEL);
   const bool small_arm = p->lane_nv && small_ok;                               // (nv ≤ 8: both kernels)
   const bool loop = a.n_steps > 1 || a.q_out || a.pos_threshold >= 0.0;       // fused caller loop (steps / until)
+  L.loop = loop;
   // (9 … 16 dofs — hands, mobile arms: the row kernel with sixteen column registers, whatever the batch; there is no lane
   //  kernel of that size to hand over to)
   // (MKH_FLAG_WARM_START: the row kernel keeps its partition in the handle's warm-start buffer like the wavefront kernels)
@@ -1661,43 +1642,44 @@ static int32_t launch(MkhProblem* p, const SolveArgs& a_in, const TapArgs* taps,
   const bool two_row_loop_bad = p->quad_nt == 32 && loop && !p->quad_loop_ok;
   if (p->quad_nt && small_ok && !two_row_loop_slower && !two_row_loop_bad && !((flags & MKH_FLAG_LANE_KERNEL) && p->lane_nv) &&
       (!p->lane_nv || a.B < (loop ? mkh::kLaneMinBatchLoop : mkh::kLaneMinBatch) || (flags & MKH_FLAG_QUAD_KERNEL))) {
+    L.family = Family::Row;
     const int per_wave = p->quad_nt == 32 ? 2 : 4;
-    const int grid = (a.B + per_wave - 1) / per_wave;
-    p->last_grid = grid; p->last_nt = p->quad_nt;
-    snprintf(p->last_kernel, sizeof(p->last_kernel), p->quad_nt == 8 ? (loop ? "ik_quad_kernel_loop" : "ik_quad_kernel")
-                                                     : (p->quad_nt == 32 ? (loop ? "ik_quad_kernel_32_loop" : "ik_quad_kernel_32")
-                                                                         : (loop ? "ik_quad_kernel_16_loop" : "ik_quad_kernel_16")));
-    SolveArgs aq = a;
-    HIP_OK(clk_begin(p, aq, stream));
-    p->last_lds = mkh::launch_quad(p->quad_nt, loop, grid, stream, p->d_lane, p->lane_dims, aq);
-    HIP_OK(hipGetLastError());
-    HIP_OK(clk_end(p, a.B, stream));
+    L.last_grid = (a.B + per_wave - 1) / per_wave; L.last_nt = p->quad_nt;   // (last_lds: what launch_quad returns)
+    plan_name(L, p->quad_nt == 8 ? (loop ? "ik_quad_kernel_loop" : "ik_quad_kernel")
+                                 : (p->quad_nt == 32 ? (loop ? "ik_quad_kernel_32_loop" : "ik_quad_kernel_32")
+                                                     : (loop ? "ik_quad_kernel_16_loop" : "ik_quad_kernel_16")));
     return MKH_OK;
   }
   if (small_arm && (a.B >= (loop ? mkh::kLaneMinBatchLoop : mkh::kLaneMinBatch) || (flags & MKH_FLAG_LANE_KERNEL))) {
-    const int grid = (a.B + kWave - 1) / kWave;
-    p->last_grid = grid; p->last_lds = p->lane_lds; p->last_nt = p->lane_nv;
-    snprintf(p->last_kernel, sizeof(p->last_kernel), loop ? "ik_lane_kernel_%d_loop" : "ik_lane_kernel_%d", p->lane_nv);
-    if (mkh::launch_lane(p->lane_nv, loop, grid, p->lane_lds, stream, p->d_lane, a) != 0)
-      return fail(MKH_E_INVALID, "no kernel variant %s", p->last_kernel);
-    HIP_OK(hipGetLastError());
+    L.family = Family::Lane;
+    L.last_grid = (a.B + kWave - 1) / kWave; L.last_lds = p->lane_lds; L.last_nt = p->lane_nv;
+    plan_name(L, loop ? "ik_lane_kernel_%d_loop" : "ik_lane_kernel_%d", p->lane_nv);
     return MKH_OK;
   }
+  // A problem whose rows can outnumber the tableau's: the flagged instances once more, with every row — plain solves, calls
+  // with taps (the workgroup-per-problem kernel writes every tap but the cycle counters) and, round 5, the fused loops: an
+  // instance that overflows at some step runs its whole loop again from its ORIGINAL q, of which the handle keeps a copy for
+  // the duration of the call (q_out may alias q) — a device-to-device copy of B·nq doubles in front of the launch
+  L.wide_redo = p->d_wide && a.do_qp && a.status_out && !(taps && taps->t_cycles);
+  // (only when q_out really aliases q: otherwise the redo reads the caller's q, which the first launch did not touch — the copy
+  //  was a latency cost of every small-batch control loop with collision limits, round-5 advisor finding)
+  L.keep_q = L.wide_redo && a.q_out && a.q_out == a.q;
   // lean production variant unless the call needs a feature it leaves out
   int need = 0;
   if (taps) need |= F_TAPS;
   if (p->has_relative) need |= F_REL;
   if (p->dev.n_com > 0) need |= F_COM;
   if (p->dev.n_pairs > 0) need |= F_COLL;
-  if (a.n_steps > 1 || a.q_out || a.pos_threshold >= 0.0) need |= F_STEPS;
+  if (loop) need |= F_STEPS;
   const bool dense = p->dev.n_dense_rows > 0 || p->dev.n_dense_limit_rows > 0 || p->dev.dense_box;
   if (dense) need |= 64;                                              // plugin rows: only the all-feature variants have them
-  // (general convex pairs of a plain solve: their contacts come from convex_contacts_kernel, launched below in front of the
+  // (general convex pairs of a plain solve: their contacts come from convex_contacts_kernel, launched in front of the
   //  ANALYTIC build — round 5; without the pre-pass buffers, the build with the routine inside)
   // Measured (ur5e_convex, one cylinder–box pair; in-kernel routine / split): 4 096 instances 0.165 / 0.207 ms, 16 384 0.463 / 0.505,
   // 65 536 1.270 / 0.970: GJK is one long dependent chain per lane — in front of a small batch its latency adds to the solve's, on
   // a large one 64 busy lanes per wavefront beat one busy lane per problem.  The split from 32 768 (instance, pair) items on.
   const bool cv_split = need == F_COLL && p->convex_pairs && p->d_cv != nullptr && (long long)a.B * p->cv.n_cv >= 32768;
+  L.cv_split = cv_split;
   int feat;
   if (need == 0) feat = 0;
   else if (need == 64) feat = F_DENSE;                                // plugin rows next to frame / posture tasks and box limits: lean build
@@ -1720,9 +1702,10 @@ static int32_t launch(MkhProblem* p, const SolveArgs& a_in, const TapArgs* taps,
   const int calls_nt_min = dbg_min ? dbg_min : 16;
   const bool calls = feat == F_COLL || feat == (F_ALL & ~F_TAPS) || feat == (F_COLL | F_CONVEX_COLL);
   if (calls && p->nt < 32) {
-    static const int kV[] = {8, 16, 24, 32};
-    for (int v : kV) if (v >= p->nt && v >= calls_nt_min) { nt = v; break; }
-    lds = nt == p->nt ? p->lds_bytes : lds_for_nt(p, nt);
+    // (the smallest compiled size that holds the problem and the minimum, up to the 32 rows of nt_full)
+    const int v = size_class(p->nt > calls_nt_min ? p->nt : calls_nt_min, feat);
+    if (v && v <= nt) nt = v;
+    lds = nt == p->nt ? p->lds_bytes : lds_bytes_of(p->dev, nt, 0, kDirectFeat, false);
   }
   // Low-rank start when the problem qualifies and the diagonal part of H is not tiny against JwᵀJw
   // (error amplification of the quasi-definite elimination ≈ eps·max cost²/min Dg ≤ 1e-9).
@@ -1741,46 +1724,28 @@ static int32_t launch(MkhProblem* p, const SolveArgs& a_in, const TapArgs* taps,
   // rows"): the launch that does the work of a plain collision solve — the tight-rows one where it exists, else the main one
   const bool woodr_ok = a.do_qp && !taps && feat == F_COLL && !(flags & MKH_FLAG_DIRECT_QP) && dg_min > 0.0 && dg_min >= 1e-7 * p->wood_max_cost2;
   if (woodr_ok && p->woodr_lds && !p->d_dev_tight && nt == 48) { nr = 48; lds = p->woodr_lds; feat = F_WOOD | F_COLL; }
-  // three resident waves per SIMD where a variant exists (FrameTask / PostureTask / RelativeFrameTask / ComTask, box limits)
-  static const int kW3Variants[][2] = {{44, 0}};   // (44_6 and 44_16 still spill 34–76 VGPRs at 74 registers: scratch traffic makes them slower than their 2-waves builds)
-  bool w3 = false;
-  if (!nr && p->lds_bytes_w3 && !(flags & MKH_FLAG_TWO_WAVES))
-    for (const auto& v : kW3Variants) w3 = w3 || (v[0] == nt && v[1] == feat);
-  if (w3) lds = p->lds_bytes_w3;
-  if (nr && p->wood_lds_bytes_w3 && !(flags & MKH_FLAG_TWO_WAVES) &&
-      (feat == F_WOOD || feat == (F_WOOD | F_STEPS) || ((feat == (F_WOOD | F_COM) || feat == (F_WOOD | F_COM | F_STEPS)) && nt == 44))) {
-    w3 = true; lds = p->wood_lds_bytes_w3;
-  }
+  // three resident waves per SIMD where a variant exists (FrameTask / PostureTask / RelativeFrameTask / ComTask, box limits) and
+  // the handle found its LDS layout worth it (mkh_problem_create: lds_bytes_w3 / wood_lds_bytes_w3)
+  const int w3_lds = nr ? p->wood_lds_bytes_w3 : p->lds_bytes_w3;
+  const bool w3 = w3_lds && !(flags & MKH_FLAG_TWO_WAVES) && find_variant(nt, nr, feat, true);
+  if (w3) lds = w3_lds;
   // tight rows first (see mkh_problem_create): plain solves on the capsule-only collision build whose caller takes the status
   const bool tight = p->d_dev_tight && (feat == (F_COLL | F_SIMPLE_COLL) || feat == F_COLL) && !nr && !w3 && a.do_qp && a.status_out && !taps &&
                      !(flags & MKH_FLAG_FULL_ROWS);
-  // (the tight launch itself on the low-rank start: same descriptor, its own LDS layout)
-  const bool tight_wood = tight && woodr_ok && p->woodr_lds_tight != 0;
-  const int t_feat = tight_wood ? (feat | F_WOOD) : feat, t_nr = tight_wood ? 48 : 0, t_lds = tight_wood ? p->woodr_lds_tight : p->lds_tight;
-  const bool no_redo = (p->diag & MKH_DIAG_NO_TIGHT_REDO) != 0;              // (tests: what the tight launch alone leaves flagged)
-  char t_name[48];
-  snprintf(t_name, sizeof t_name, t_nr ? "ik_solve_kernel_%d_%d_r%d" : "ik_solve_kernel_%d_%d", p->nt_tight, t_feat, t_nr);
-  if (tight && no_redo) {
-    const int gt = grid_for_variant(p, a.B, p->nt_tight, t_lds, false);
-    SolveArgs at = a;
-    at.work_counter = p->d_work;
-    at.static_rounds = INT32_MAX;
-    if (mkh::launch_variant(p->nt_tight, t_nr, t_feat, false, gt, t_lds, stream, p->d_dev_tight, at, nullptr) != 0)
-      return fail(MKH_E_INVALID, "no kernel variant %s", t_name);
-    HIP_OK(hipGetLastError());
-    snprintf(p->last_kernel, sizeof(p->last_kernel), "%s", t_name);
-    return MKH_OK;
-  }
+  const int num_cus = p->model->num_cus;
   if (tight) {
-    const int gt = grid_for_variant(p, a.B, p->nt_tight, t_lds, false);
-    SolveArgs at = a;
-    at.work_counter = p->d_work;
-    const int pw = a.B / gt;
-    at.static_rounds = (pw >= kMinRoundsForTickets) ? static_rounds_for(pw, gt % p->model->num_cus == 0 && ((gt / p->model->num_cus) & 3) != 0) : INT32_MAX;
-    HIP_OK(clk_begin(p, at, stream));                 // (clock builds: the stamps of the launch that does the work)
-    if (mkh::launch_variant(p->nt_tight, t_nr, t_feat, false, gt, t_lds, stream, p->d_dev_tight, at, nullptr) != 0)
-      return fail(MKH_E_INVALID, "no kernel variant %s", t_name);
-    HIP_OK(hipGetLastError());
+    // (the tight launch itself on the low-rank start: same descriptor, its own LDS layout)
+    const bool tight_wood = woodr_ok && p->woodr_lds_tight != 0;
+    WaveLaunch& t = L.tight;
+    L.has_tight = true;
+    L.tight_redo = !(p->diag & MKH_DIAG_NO_TIGHT_REDO);            // (tests: what the tight launch alone leaves flagged)
+    t.nt = p->nt_tight; t.nr = tight_wood ? 48 : 0; t.feat = tight_wood ? (feat | F_WOOD) : feat;
+    t.lds = tight_wood ? p->woodr_lds_tight : p->lds_tight;
+    t.grid = grid_for_variant(p, a.B, t.nt, t.lds, false);
+    const int pw = a.B / t.grid;
+    if (L.tight_redo && pw >= kMinRoundsForTickets)
+      t.static_rounds = static_rounds_for(pw, t.grid % num_cus == 0 && ((t.grid / num_cus) & 3) != 0);
+    t.v = find_variant(t.nt, t.nr, t.feat);
   }
   int grid = grid_for_variant(p, a.B, nt, lds, w3);
   // One problem per workgroup instead of persistent wavefronts, for the humanoid-size builds of the one-more-wave map between
@@ -1798,22 +1763,13 @@ static int32_t launch(MkhProblem* p, const SolveArgs& a_in, const TapArgs* taps,
   // one per workgroup on the twin: 12 288 instances 0.166 / 0.151, 65 536 0.737 / 0.701, 73 728 0.817 / 0.786, 131 072 1.400 / 1.379,
   // 262 144 2.750 / 2.728 (below 3.5 rounds the persistent shape stays: 10 240 instances 0.145 on both).
   static const int os_max = dbg_env("MKH_DEBUG_ONE_SHOT_MAX") ? atoi(dbg_env("MKH_DEBUG_ONE_SHOT_MAX")) : 22;    // (A/B switch: upper end of the range, in rounds)
-  const bool has_twin = w3 && nt == 44 && nr == 44 && feat == F_WOOD && !dtaps;
+  const bool has_twin = w3 && !taps && find_variant(nt, nr, feat, true, true);
   if (!persistent_only && !tight && w3 && nt == 44 && a.n_steps <= 1 && a.B > grid && 2 * (long long)a.B >= 7LL * grid &&
       (has_twin || a.B <= (long long)os_max * grid))
     grid = a.B;
   // ... and, round 6, on a build WITHOUT the persistent loop's machinery where one exists (`44_32_r44_w3o`: build.py W3_WOOD_ONE_SHOT,
   // ik_kernel.h MKH_ONE_SHOT — 78 → 32 spilled SGPRs in the kernel body, headline 0.713 → 0.703 ms; the F_COM twin measured no gain)
   const bool one_shot = grid == a.B && has_twin;
-  p->last_grid = grid; p->last_lds = lds; p->last_nt = nt;
-  snprintf(p->last_kernel, sizeof(p->last_kernel), nr ? (w3 ? (one_shot ? "ik_solve_kernel_%d_%d_r%d_w3o" : "ik_solve_kernel_%d_%d_r%d_w3") : "ik_solve_kernel_%d_%d_r%d") : (w3 ? "ik_solve_kernel_%d_%d_w3" : "ik_solve_kernel_%d_%d"), nt, feat, nr);
-  SolveArgs al = a;
-  al.work_counter = p->d_work;
-  if (tight) {
-    al.redo_mask = MKH_ST_ROW_OVERFLOW;              // the full-row build: only what the tight launch flagged
-    snprintf(p->last_kernel, sizeof(p->last_kernel), "%s+redo_%d", t_name, nt);
-    p->last_nt = p->nt_tight; p->last_lds = t_lds; p->last_grid = grid_for_variant(p, a.B, p->nt_tight, t_lds, false);
-  }
   // Distribution (ik_kernel.h): most of each wave's share is static — one contiguous row range per XCD — and the tail
   // of the batch goes through the ticket counter (how much: static_rounds_for above).  Round 1, on G1 (kernel ms by static
   // sixteenths): 16 → 1.283, 15 → 1.233, 14 → 1.183, 12 → 1.185, 8 → 1.193, 4 → 1.195, 0 → 1.264: every wave opening with an
@@ -1821,24 +1777,88 @@ static int32_t launch(MkhProblem* p, const SolveArgs& a_in, const TapArgs* taps,
   const int per_wave = a.B / grid;
   // (fused loops: problems of very different length — the ticket tail from four rounds on, as before)
   const bool dynamic = nt > 8 && per_wave >= (a.n_steps > 1 ? 4 : kMinRoundsForTickets) && !tight;   // (a redo launch walks its static share, ik_kernel.h)
-  al.static_rounds = dynamic ? static_rounds_for(per_wave, grid % p->model->num_cus == 0 && ((grid / p->model->num_cus) & 3) != 0, a.n_steps > 1) : INT32_MAX;
-  if (!tight) HIP_OK(clk_begin(p, al, stream));
-  if (cv_split) {
+  WaveLaunch& w = L.main;
+  w.nt = nt; w.nr = nr; w.feat = feat; w.w3 = w3; w.one_shot = one_shot; w.grid = grid; w.lds = lds;
+  if (dynamic) w.static_rounds = static_rounds_for(per_wave, grid % num_cus == 0 && ((grid / num_cus) & 3) != 0, a.n_steps > 1);
+  w.v = find_variant(nt, nr, feat, w3, one_shot);
+  // what the call reports: the launch that does the work — the tight one where there is one; "convex_pre+": the pre-pass launch
+  // in front, "+redo_<rows>" / "+wide": the launches behind
+  const WaveLaunch& rep = tight ? L.tight : L.main;
+  L.last_grid = rep.grid; L.last_lds = rep.lds; L.last_nt = rep.nt;
+  char redo[16] = "";
+  if (tight && L.tight_redo) snprintf(redo, sizeof redo, "+redo_%d", nt);
+  if (tight && !L.tight_redo) L.wide_redo = L.keep_q = false;      // (the tight launch alone: nothing behind it)
+  plan_name(L, "%s%s%s%s", L.cv_split ? "convex_pre+" : "", wave_name(rep), redo, L.wide_redo ? "+wide" : "");
+  return MKH_OK;
+}
+
+static int32_t launch_wave(MkhProblem* p, const WaveLaunch& w, const DeviceProblem* d_dev, SolveArgs a, hipStream_t stream, const TapArgs* dtaps) {
+  if (!w.v)
+    return fail(MKH_E_INVALID, "no kernel variant for %d tableau rows, %d dof rows, features %d%s%s", w.nt, w.nr, w.feat, w.w3 ? ", one more wave" : "",
+                w.one_shot ? ", one problem per workgroup" : "");
+  a.work_counter = p->d_work;
+  a.static_rounds = w.static_rounds;
+  w.v->launch(w.grid, w.lds, stream, d_dev, a, dtaps);
+  HIP_OK(hipGetLastError());
+  return MKH_OK;
+}
+
+static int32_t launch(MkhProblem* p, const SolveArgs& a_in, const TapArgs* taps, hipStream_t stream, int32_t flags) {
+  // (the kernel choice must not depend on whether the caller wants the status: a call without status_out on a handle with a
+  //  tight-rows build keeps it in a buffer of the handle — round-3 advisor finding)
+  SolveArgs a = a_in;
+  if (!a.status_out && p->d_status_tight && a.do_qp) a.status_out = p->d_status_tight;
+  LaunchPlan L;
+  if (const int32_t rc = plan_launch(*p, a, taps, flags, L)) return rc;
+  memcpy(p->last_kernel, L.last_kernel, sizeof p->last_kernel);
+  p->last_grid = L.last_grid; p->last_lds = L.last_lds; p->last_nt = L.last_nt; p->last_block = L.last_block;
+  (void)hipGetLastError();          // a stale error of an unrelated earlier runtime call must not be blamed on this launch
+  const TapArgs* dtaps = nullptr;
+  if (taps) {
+    HIP_OK(hipMemcpyAsync(p->d_taps, taps, sizeof(TapArgs), hipMemcpyHostToDevice, stream));
+    HIP_OK(hipStreamSynchronize(stream));   // taps are a debug path: keep the host struct's lifetime simple
+    dtaps = p->d_taps;
+  }
+  if (L.family == Family::WideOnly) {
+    HIP_OK(clk_begin(p, a, stream));                         // (MKH_DEBUG_CLOCKS=<file>: phase stamps of every problem, tools/wide_phase_clocks.py)
+    const int32_t rcw = launch_wide_kernel(p, a, stream, 0, dtaps);
+    if (rcw == MKH_OK) HIP_OK(clk_end(p, a.B, stream));
+    return rcw;
+  }
+  if (L.family == Family::Row) {
+    HIP_OK(clk_begin(p, a, stream));
+    p->last_lds = mkh::launch_quad(p->quad_nt, L.loop, L.last_grid, stream, p->d_lane, p->lane_dims, a);
+    HIP_OK(hipGetLastError());
+    HIP_OK(clk_end(p, a.B, stream));
+    return MKH_OK;
+  }
+  if (L.family == Family::Lane) {
+    if (mkh::launch_lane(p->lane_nv, L.loop, L.last_grid, p->lane_lds, stream, p->d_lane, a) != 0)
+      return fail(MKH_E_INVALID, "no kernel variant %s", p->last_kernel);
+    HIP_OK(hipGetLastError());
+    return MKH_OK;
+  }
+  const double* q_redo = a.q;
+  if (L.keep_q) {
+    HIP_OK(ensure(&p->d_qkeep, (size_t)p->max_batch * p->dev.nq));
+    HIP_OK(hipMemcpyAsync(p->d_qkeep, a.q, (size_t)a.B * p->dev.nq * sizeof(double), hipMemcpyDefault, stream));
+    q_redo = p->d_qkeep;
+  }
+  SolveArgs al = a;
+  HIP_OK(clk_begin(p, al, stream));                          // (clock builds: the stamps of the launch that does the work)
+  if (L.has_tight) {
+    if (const int32_t rc = launch_wave(p, L.tight, p->d_dev_tight, al, stream, nullptr)) return rc;
+    if (!L.tight_redo) return MKH_OK;
+    al = a;
+    al.redo_mask = MKH_ST_ROW_OVERFLOW;              // the full-row build: only what the tight launch flagged
+  }
+  if (L.cv_split) {
     const int rc = mkh::launch_convex_pre(stream, p->d_wide, p->cv, a.B, a.q, p->d_cv);
     if (rc != 0) return fail(MKH_E_HIP, "convex pre-pass: %s", hipGetErrorString((hipError_t)rc));
   }
-  if (mkh::launch_variant(nt, nr, feat, w3, grid, lds, stream, p->d_dev, al, dtaps, one_shot) != 0)
-    return fail(MKH_E_INVALID, "no kernel variant %s", p->last_kernel);
-  HIP_OK(hipGetLastError());
+  if (const int32_t rc = launch_wave(p, L.main, p->d_dev, al, stream, dtaps)) return rc;
   HIP_OK(clk_end(p, a.B, stream));
-  if (cv_split) {                                          // ("convex_pre+": the pre-pass launch in front)
-    char tmp[64];
-    snprintf(tmp, sizeof tmp, "convex_pre+%s", p->last_kernel);
-    snprintf(p->last_kernel, sizeof(p->last_kernel), "%s", tmp);
-  }
-  if (wide_redo) {
-    const size_t len = strlen(p->last_kernel);
-    snprintf(p->last_kernel + len, sizeof(p->last_kernel) - len, "+wide");
+  if (L.wide_redo) {
     SolveArgs ar = a;
     ar.q = q_redo;
     HIP_OK(clk_begin(p, ar, stream));                      // (MKH_DEBUG_CLOCKS: the stamps of the redo launch overwrite the main kernel's)
