@@ -444,6 +444,56 @@ int32_t mkh_solve_multistart(MkhProblem *problem, int32_t B, const double *q, co
                              uint64_t rng_seed, int64_t target_index0, const MkhMultistartIO *io, int32_t flags,
                              void *hip_stream);
 
+/*
+ * Trajectory IK: every instance follows its own time sequence of T waypoints, each solved from where the previous one ended —
+ * what a caller writes as a loop of mkh_solve_until (motion retargeting, Cartesian path tracing, a horizon of goals), in one
+ * call with nothing coming back to the host between waypoints.  No counterpart in the reference.
+ *
+ * For t = 0 .. T-1, every instance b runs the fused loop from q_{t-1}[b] (q_{-1} = q) against waypoint t's targets:
+ *   pos_threshold >= 0 and ori_threshold >= 0   mkh_solve_until's loop with max_iters = n_steps
+ *   pos_threshold <  0 and ori_threshold <  0   mkh_solve_steps' fixed count of n_steps; iters and converged must be NULL
+ * (one threshold negative and the other not: MKH_E_INVALID).  q_traj[b, t], v_traj[b, t], status[b, t], iters[b, t] and
+ * converged[b, t] are exactly what that loop returns: T launches of the same kernels, stream-ordered, bitwise the caller's loop.
+ *
+ * A FAILING WAYPOINT DOES NOT STOP THE TRAJECTORY.  A waypoint whose loop did not converge, or whose status carries a QP
+ * failure bit, is reported in status[b, t] / converged[b, t] and nowhere else: waypoint t + 1 of that instance starts from
+ * whatever q_out the loop left (an instance's loop stops at the first step whose QP fails), and the call returns MKH_OK.
+ *
+ * Layout.  Batch-major by default: frame_targets (B, T, n_frame, 7), outputs (B, T, .).  Posture targets are (n_posture, nq), or
+ * (B, n_posture, nq) with MKH_FLAG_POSTURE_BATCHED; with posture_per_waypoint a T axis comes after B — (B, T, n_posture, nq) —
+ * and leads when the target is not batched: (T, n_posture, nq).  The same rule holds for com_target with MKH_FLAG_COM_BATCHED and
+ * com_per_waypoint.  With time_major = 1 the T axis moves to the front of every array of the call that has one: frame_targets
+ * (T, B, n_frame, 7), posture (T, B, n_posture, nq), outputs (T, B, .); q stays (B, nq).  Time-major is the layout the loops run
+ * on: with MKH_FLAG_DEVICE_PTRS they read the caller's target slabs and write the caller's output slabs directly — no extra
+ * kernel, no copy, no workspace.  Batch-major arrays are transposed on the device before and after the loops.
+ *
+ * qvel (optional): qvel[b, t] = mj_differentiatePos(q_{t-1}[b], q_traj[b, t]) at waypoint_dt — per hinge / slide coordinate
+ * (q_t - q_{t-1}) / waypoint_dt, a rounded difference followed by a rounded quotient, so that a numpy restatement reproduces it
+ * bit for bit; free joint: the same for the three position coordinates, then, as for a ball joint, the rotation vector of
+ * conj(q_{t-1}) q_t over waypoint_dt (mju_subQuat: body frame, angle in (-pi, pi]).
+ *
+ * MKH_FLAG_WARM_START is passed to every loop unchanged: the handle's warm state behaves as under T consecutive
+ * mkh_solve_until calls with the flag.  Host pointers: inputs are staged once, the trajectory runs on the device, outputs come
+ * back once at the end.  Outputs must not alias inputs or each other.  Every argument error is reported before any device work;
+ * an error of a loop launch in mid-trajectory returns its code after the stream has drained.
+ */
+typedef struct MkhTrajectoryIO {
+  double *q_traj;       /* (B, T, nq)  configuration at the end of every waypoint's loop                 required  */
+  double *v_traj;       /* (B, T, nv)  last velocity of every waypoint's loop                            required  */
+  int32_t *status;      /* (B, T)      MKH_ST_* bits of every waypoint's loop                            required  */
+  int32_t *iters;       /* (B, T)      iterations performed; threshold mode only, may be NULL                     */
+  int32_t *converged;   /* (B, T)      1 when the loop ended on the thresholds; threshold mode only, may be NULL  */
+  double *qvel;         /* (B, T, nv)  optional: (q_t (-) q_{t-1}) / waypoint_dt, q_{-1} = q                      */
+  double waypoint_dt;   /* > 0 when qvel is given                                                                 */
+  int32_t posture_per_waypoint;   /* 0: the posture target is held over the trajectory; 1: it has a T axis        */
+  int32_t com_per_waypoint;       /* the same for the CoM target                                                   */
+  int32_t time_major;   /* 1: every (B, T, .) array of the call, inputs included, is (T, B, .) instead            */
+} MkhTrajectoryIO;
+int32_t mkh_solve_trajectory(MkhProblem *problem, int32_t B, int32_t T, const double *q, const double *frame_targets,
+                             const double *posture_target, const double *com_target, double dt, double damping,
+                             int32_t n_steps, double pos_threshold, double ori_threshold, const MkhTrajectoryIO *io,
+                             int32_t flags, void *hip_stream);
+
 /* Same inputs; additionally writes the requested intermediates (build_ik / compute_error /
  * compute_jacobian / get_transform_frame_to_world parity taps).  v_out/status_out may be NULL
  * to skip the QP. */

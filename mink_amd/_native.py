@@ -150,6 +150,26 @@ class MultistartOut(NamedTuple):
     seeds: object = None
 
 
+TRAJECTORY_IO_FIELDS = ("q_traj", "v_traj", "status", "iters", "converged", "qvel", "waypoint_dt", "posture_per_waypoint",
+                        "com_per_waypoint", "time_major")
+
+
+class MkhTrajectoryIO(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in TRAJECTORY_IO_FIELDS[:6]] + [("waypoint_dt", C.c_double)] + \
+        [(n, C.c_int32) for n in TRAJECTORY_IO_FIELDS[7:]]
+
+
+class TrajectoryOut(NamedTuple):
+    """What NativeProblem.solve_trajectory returns (arrays of the caller's kind: numpy or torch), (B, T, ·) — (T, B, ·) with
+    time_major.  `iters` / `converged` are None in fixed-count mode, `qvel` unless qvel_dt was given."""
+    q: object
+    v: object
+    status: object
+    iters: object = None
+    converged: object = None
+    qvel: object = None
+
+
 TAP_NAMES = ("xpos", "xquat", "frame_pose", "subtree_com", "task_e", "task_J", "H", "c", "box_lo",
              "box_hi", "coll_G", "coll_h", "qp_iters", "cycles")
 
@@ -206,6 +226,9 @@ def lib() -> C.CDLL:
     L.mkh_solve_multistart.argtypes = common[:8] + [C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_uint64, C.c_int64,
                                                     C.POINTER(MkhMultistartIO), C.c_int32, C.c_void_p]
     L.mkh_solve_multistart.restype = C.c_int32
+    L.mkh_solve_trajectory.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + common[2:8] + \
+        [C.c_int32, C.c_double, C.c_double, C.POINTER(MkhTrajectoryIO), C.c_int32, C.c_void_p]
+    L.mkh_solve_trajectory.restype = C.c_int32
     L.mkh_solve_dense.argtypes = common[:6] + [C.POINTER(MkhDenseRows), C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                                C.POINTER(MkhTaps), C.c_int32, C.c_void_p]
     L.mkh_solve_dense.restype = C.c_int32
@@ -231,6 +254,7 @@ EXPORTED_SYMBOLS = (
     "mkh_problem_num_collision_pairs", "mkh_solve", "mkh_eval", "mkh_integrate", "mkh_problem_launch_info",
     "mkh_solve_steps", "mkh_problem_last_kernel", "mkh_lie_eval", "mkh_solve_dense", "mkh_solve_until",
     "mkh_geom_distance_eval", "mkh_problem_create_diag", "mkh_solve_multistart",
+    "mkh_solve_trajectory",
 )
 
 LIE_OPS = {"se3_log": (0, 7, 0, (6,)), "se3_jlog": (1, 7, 0, (6, 6)), "se3_ljacinv": (2, 6, 0, (6, 6)),
@@ -714,3 +738,115 @@ class NativeProblem:
                      out["status_all"].reshape(B, S), out["seeds_out"].reshape(B, S, m.nq))
         return MultistartOut(out["q_best"], out["v_best"], out["converged"], out["seed_index"], out["n_converged"],
                              out["iters"], out["status"], *extra)
+
+    # ------------------------------------------------------------- trajectory
+    def solve_trajectory(self, q, frame_targets=None, posture_target=None, com_target=None, dt: float = 1e-2,
+                         damping: float = 1e-12, n_steps: int = 1, until: Optional[tuple] = None,
+                         qvel_dt: Optional[float] = None, time_major: bool = False, warm_start: bool = False,
+                         wave_kernel: bool = False, lane_kernel: bool = False, quad_kernel: bool = False) -> TrajectoryOut:
+        """mkh_solve_trajectory: every row of q follows its own T waypoints, waypoint t solved by the fused loop from where
+        waypoint t − 1 ended — `until` = (pos_threshold, ori_threshold): the threshold-terminated loop with max_iters = n_steps;
+        None: n_steps fixed steps.  frame_targets (B, T, n_frame, 7); posture / CoM targets as in solve(), or with a T axis
+        after B (leading when the target has no B axis; a 3-d target whose first axis equals B is read as (B, ...)).  time_major: T leads every array that has one, outputs included.
+        numpy in → numpy out (synchronous); torch CUDA tensors in → torch tensors out, asynchronous on the current stream, no
+        host copy.  A failing waypoint does not stop its trajectory (include/minkhip.h)."""
+        with self._lock:
+            return self._solve_trajectory(q, frame_targets, posture_target, com_target, dt, damping, int(n_steps), until, qvel_dt,
+                                          bool(time_major), warm_start, wave_kernel, lane_kernel, quad_kernel)
+
+    def _solve_trajectory(self, q, frame_targets, posture_target, com_target, dt, damping, n_steps, until, qvel_dt, tm,
+                          warm_start, wave_kernel, lane_kernel, quad_kernel):
+        m = self.nmodel.model
+        use_torch = _is_torch(q)
+        B = int(q.shape[0])
+        if n_steps < 1:
+            raise ValueError("n_steps must be >= 1")
+        if qvel_dt is not None and not float(qvel_dt) > 0.0:
+            raise ValueError("qvel_dt must be > 0")
+        if B > self.max_batch:
+            raise MinkHipError(f"B={B} exceeds max_batch={self.max_batch} of this problem")
+        if self.n_dense_rows or self.n_dense_limit_rows or self.dense_limit_box:
+            raise ValueError("dense (plugin) rows are evaluated by the caller at q: no fused loop, no trajectory")
+        if until is not None and not self.n_frame:
+            raise ValueError("threshold mode needs at least one frame task to test the thresholds on")
+        flags = (FLAG_WAVE_KERNEL if wave_kernel else 0) | (FLAG_LANE_KERNEL if lane_kernel else 0) | \
+            (FLAG_QUAD_KERNEL if quad_kernel else 0) | (FLAG_WARM_START if warm_start else 0)
+        if use_torch:
+            import torch
+            dev = q.device
+
+            def prep(x):
+                if x is None or (x.dtype is torch.float64 and x.device == dev and x.is_contiguous()):
+                    return x
+                return torch.as_tensor(x).to(device=dev, dtype=torch.float64).contiguous()
+
+            def empty(shape, dtype):
+                return torch.empty(shape, dtype=torch.float64 if dtype is np.float64 else torch.int32, device=dev)
+
+            ptr = lambda x: None if x is None else x.data_ptr()
+            flags |= FLAG_DEVICE_PTRS
+            stream = _raw_stream(torch, dev)
+        else:
+            prep = lambda x: None if x is None else _f64(x)
+            empty = lambda shape, dtype: np.empty(shape, dtype=dtype)
+            ptr = lambda x: None if x is None else x.ctypes.data
+            stream = None
+        q, frame_targets, posture_target, com_target = prep(q), prep(frame_targets), prep(posture_target), prep(com_target)
+        if tuple(q.shape) != (B, m.nq):
+            raise ValueError(f"q must have shape (B, {m.nq}), got {tuple(q.shape)}")
+        T = None
+        if self.n_frame:
+            if frame_targets is None or frame_targets.ndim != 4:
+                raise ValueError(f"frame_targets must have shape (B, T, {self.n_frame}, 7)" + (" — (T, B, ...) time-major" if tm else ""))
+            T = int(frame_targets.shape[0 if tm else 1])
+            want = (T, B, self.n_frame, 7) if tm else (B, T, self.n_frame, 7)
+            if T < 1 or tuple(frame_targets.shape) != want:
+                raise ValueError(f"frame_targets must have shape {want}, got {tuple(frame_targets.shape)}")
+
+        def held_or_timed(x, n, w, name, flag):
+            """(per_waypoint, flags bit) of a posture / CoM target from its shape."""
+            nonlocal T
+            if x is None:
+                raise ValueError(f"{name} is required")
+            shp = tuple(x.shape)
+            if shp == (n, w):
+                return 0, 0
+            if len(shp) == 4:                                  # (B, T, n, w) / (T, B, n, w)
+                Tx = shp[0 if tm else 1]
+                T = Tx if T is None else T
+                if shp == ((T, B, n, w) if tm else (B, T, n, w)):
+                    return 1, flag
+            elif len(shp) == 3 and shp[1:] == (n, w):          # (B, n, w) as in solve(), else (T, n, w); T == B reads as (B, ...)
+                if shp[0] == B:
+                    return 0, flag
+                T = shp[0] if T is None else T
+                if shp[0] == T:
+                    return 1, 0
+            raise ValueError(f"{name} must have shape ({n}, {w}), (B, {n}, {w}), (T, {n}, {w}) or "
+                             f"{'(T, B' if tm else '(B, T'}, {n}, {w}), got {shp}")
+
+        p_time = c_time = 0
+        if self.n_posture:
+            p_time, f = held_or_timed(posture_target, self.n_posture, m.nq, "posture_target", FLAG_POSTURE_BATCHED)
+            flags |= f
+        if self.n_com:
+            c_time, f = held_or_timed(com_target, self.n_com, 3, "com_target", FLAG_COM_BATCHED)
+            flags |= f
+        if T is None:
+            raise ValueError("no target has a T axis: nothing says how many waypoints there are")
+        f8, i4 = np.float64, np.int32
+        lead = (T, B) if tm else (B, T)
+        out_q, out_v, out_st = empty(lead + (m.nq,), f8), empty(lead + (m.nv,), f8), empty(lead, i4)
+        out_it = out_cv = out_qvel = None
+        if until is not None:
+            out_it, out_cv = empty(lead, i4), empty(lead, i4)
+        if qvel_dt is not None:
+            out_qvel = empty(lead + (m.nv,), f8)
+        io = MkhTrajectoryIO()
+        io.q_traj, io.v_traj, io.status, io.iters, io.converged, io.qvel = (ptr(x) for x in (out_q, out_v, out_st, out_it, out_cv, out_qvel))
+        io.waypoint_dt = float(qvel_dt) if qvel_dt is not None else 0.0
+        io.posture_per_waypoint, io.com_per_waypoint, io.time_major = p_time, c_time, int(tm)
+        thr = (float(until[0]), float(until[1])) if until is not None else (-1.0, -1.0)
+        _check(lib().mkh_solve_trajectory(self.handle, B, T, ptr(q), ptr(frame_targets), ptr(posture_target), ptr(com_target),
+                                          float(dt), float(damping), n_steps, thr[0], thr[1], C.byref(io), flags, stream))
+        return TrajectoryOut(out_q, out_v, out_st, out_it, out_cv, out_qvel)

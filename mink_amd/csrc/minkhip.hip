@@ -212,6 +212,10 @@ struct MkhProblem {
   GrowBuf ms_seed_i, ms_seed_f, ms_jnt;
   GrowBuf ms_q, ms_seeds, ms_ft, ms_pt, ms_ct, ms_v, ms_i32;                   // B·S rows (ms_i32: status | iters | converged)
   GrowBuf ms_in_q, ms_in_ft, ms_in_pt, ms_in_ct, ms_in_ref, ms_in_w, ms_out_q, ms_out_v, ms_out_i32;   // B rows
+  // mkh_solve_trajectory: time-major copies of batch-major targets, the loops' time-major results of a batch-major call
+  // (tj_i32: status | iters | converged), and the staging of host-pointer calls (tj_out_*: in the caller's layout)
+  GrowBuf tj_ft, tj_pt, tj_ct, tj_q, tj_v, tj_i32;
+  GrowBuf tj_in_q, tj_in_ft, tj_in_pt, tj_in_ct, tj_out_q, tj_out_v, tj_out_i32, tj_out_qvel;
 };
 
 // The wavefront kernel's variants live in their own translation units (mink_amd/csrc/build.py generates one variant_<name>.hip
@@ -230,6 +234,14 @@ hipError_t launch_ms_select(hipStream_t stream, int B, int S, int nq, int nv, in
                             const double* v_all, const int32_t* status_all, const int32_t* iters_all, const int32_t* converged_all,
                             const double* q_ref, const double* weights, double* q_best, double* v_best, int32_t* iters,
                             int32_t* status, int32_t* converged, int32_t* seed_index, int32_t* n_converged);
+// trajectory IK (trajectory.hip): (B, T, W) ↔ (T, B, W) transposes and the joint velocity between waypoints — the kernels
+// around the T loop launches of mkh_solve_trajectory
+hipError_t launch_tj_gather(hipStream_t stream, const double* src, double* dst, int B, int T, int W);
+hipError_t launch_tj_scatter(hipStream_t stream, const double* src, double* dst, int B, int T, int W);
+hipError_t launch_tj_scatter_i32(hipStream_t stream, const int32_t* src, int32_t* dst, int B, int T);
+hipError_t launch_tj_qvel(hipStream_t stream, const int32_t* jnt, int njnt, int B, int T, int nq, const double* q0,
+                          const double* q_traj, long long q_sb, long long q_st, double dt, double* qvel, long long v_sb,
+                          long long v_st, int time_major);
 constexpr int kLaneMinBatchLoop = 28672;  // fused loops of a small arm: row kernel below, lane kernel from here (M targets/s at 16 384: 39.7 vs 24.1, at 32 768: 42.4 vs 48.2)
 constexpr int kLaneMinBatch = 73728;  // plain solves of a small arm: row kernel below, lane kernel from here (plan_launch())
 }
@@ -1470,7 +1482,8 @@ void mkh_problem_destroy(MkhProblem* p) {
   (void)hipFree(p->s_q); (void)hipFree(p->s_ft); (void)hipFree(p->s_pt); (void)hipFree(p->s_ct); (void)hipFree(p->s_v); (void)hipFree(p->s_status);
   for (GrowBuf* g : {&p->ms_seed_i, &p->ms_seed_f, &p->ms_jnt, &p->ms_q, &p->ms_seeds, &p->ms_ft, &p->ms_pt, &p->ms_ct, &p->ms_v,
                      &p->ms_i32, &p->ms_in_q, &p->ms_in_ft, &p->ms_in_pt, &p->ms_in_ct, &p->ms_in_ref, &p->ms_in_w, &p->ms_out_q,
-                     &p->ms_out_v, &p->ms_out_i32})
+                     &p->ms_out_v, &p->ms_out_i32, &p->tj_ft, &p->tj_pt, &p->tj_ct, &p->tj_q, &p->tj_v, &p->tj_i32, &p->tj_in_q,
+                     &p->tj_in_ft, &p->tj_in_pt, &p->tj_in_ct, &p->tj_out_q, &p->tj_out_v, &p->tj_out_i32, &p->tj_out_qvel})
     g->release();
   p->small.release();
   if (p->st_in) (void)hipStreamDestroy(p->st_in);
@@ -2329,6 +2342,143 @@ int32_t mkh_solve_multistart(MkhProblem* p, int32_t B, const double* q, const do
   const hipError_t e2 = hipStreamSynchronize(stream);       // (a failed call still drains what it started)
   if (e == hipSuccess) e = e2;
   if (e != hipSuccess) return fail(MKH_E_HIP, "multistart: %s", hipGetErrorString(e));
+  return MKH_OK;
+}
+
+int32_t mkh_solve_trajectory(MkhProblem* p, int32_t B, int32_t T, const double* q, const double* frame_targets,
+                             const double* posture_target, const double* com_target, double dt, double damping,
+                             int32_t n_steps, double pos_threshold, double ori_threshold, const MkhTrajectoryIO* io,
+                             int32_t flags, void* hip_stream) {
+  // (what can be judged from the arguments alone comes first: it needs neither a handle nor a device)
+  if (B < 1) return fail(MKH_E_INVALID, "B must be >= 1");
+  if (T < 1) return fail(MKH_E_INVALID, "T must be >= 1");
+  if (n_steps < 1) return fail(MKH_E_INVALID, "n_steps must be >= 1");
+  if (!(dt > 0.0)) return fail(MKH_E_INVALID, "dt must be > 0");
+  const bool until = pos_threshold >= 0.0 && ori_threshold >= 0.0;
+  if (!until && !(pos_threshold < 0.0 && ori_threshold < 0.0))
+    return fail(MKH_E_INVALID, "thresholds must both be >= 0 (threshold mode) or both be < 0 (fixed count)");
+  if (!io || !io->q_traj || !io->v_traj || !io->status)
+    return fail(MKH_E_INVALID, "io and its outputs q_traj, v_traj, status are required");
+  if (!until && (io->iters || io->converged))
+    return fail(MKH_E_INVALID, "iters / converged are outputs of threshold mode: they must be NULL with a fixed count");
+  if (io->qvel && !(io->waypoint_dt > 0.0)) return fail(MKH_E_INVALID, "qvel needs waypoint_dt > 0");
+  if (!p) return fail(MKH_E_INVALID, "null problem");
+  const DeviceProblem& P = p->dev;
+  if (!q) return fail(MKH_E_INVALID, "q is null");
+  if (until && P.n_frame < 1)
+    return fail(MKH_E_INVALID, "mkh_solve_trajectory needs at least one frame task to test the thresholds on");
+  if (P.n_frame > 0 && !frame_targets) return fail(MKH_E_INVALID, "frame_targets is null (TargetNotSet)");
+  if (P.n_posture > 0 && !posture_target) return fail(MKH_E_INVALID, "posture_target is null (TargetNotSet)");
+  if (P.n_com > 0 && !com_target) return fail(MKH_E_INVALID, "com_target is null (TargetNotSet)");
+  if (P.n_dense_rows || P.n_dense_limit_rows || P.dense_box)
+    return fail(MKH_E_INVALID, "dense (plugin) rows are evaluated by the caller at q: no fused loop, no trajectory");
+  if (B > p->max_batch) return fail(MKH_E_INVALID, "B=%d exceeds max_batch=%d of this problem", B, p->max_batch);
+  HIP_OK(hipSetDevice(p->model->device));
+  if (io->qvel)
+    if (const int32_t rc = ms_build_tables(p)) return rc;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0, tm = io->time_major != 0;
+  const bool pbat = (flags & MKH_FLAG_POSTURE_BATCHED) != 0, cbat = (flags & MKH_FLAG_COM_BATCHED) != 0;
+  const bool ptime = io->posture_per_waypoint != 0 && P.n_posture > 0, ctime = io->com_per_waypoint != 0 && P.n_com > 0;
+  const size_t Bz = B, Tz = T, N = Bz * Tz, nq = P.nq, nv = P.nv, f8 = sizeof(double), i4 = sizeof(int32_t);
+  const size_t ft_w = (size_t)P.n_frame * 7, pt_w = (size_t)P.n_posture * nq, ct_w = (size_t)P.n_com * 3;
+  const size_t pt_n = pt_w * (pbat ? Bz : 1) * (ptime ? Tz : 1), ct_n = ct_w * (cbat ? Bz : 1) * (ctime ? Tz : 1);
+
+  // ---- inputs and the caller-layout outputs on the device
+  const double *d_q = q, *d_ft = frame_targets, *d_pt = posture_target, *d_ct = com_target;
+  double *o_q = io->q_traj, *o_v = io->v_traj, *o_qvel = io->qvel;
+  int32_t *o_st = io->status, *o_it = io->iters, *o_cv = io->converged;
+  if (!devp) {
+    auto up = [&](GrowBuf& g, const double* src, size_t n) -> hipError_t {
+      if (hipError_t e = g.need(n * f8)) return e;
+      return hipMemcpyAsync(g.p, src, n * f8, hipMemcpyHostToDevice, stream);
+    };
+    HIP_OK(p->tj_out_q.need(N * nq * f8));
+    HIP_OK(p->tj_out_v.need(N * nv * f8));
+    HIP_OK(p->tj_out_i32.need(3 * N * i4));
+    if (io->qvel) HIP_OK(p->tj_out_qvel.need(N * nv * f8));
+    HIP_OK(up(p->tj_in_q, q, Bz * nq)); d_q = p->tj_in_q.f64();
+    if (ft_w) { HIP_OK(up(p->tj_in_ft, frame_targets, N * ft_w)); d_ft = p->tj_in_ft.f64(); }
+    if (pt_w) { HIP_OK(up(p->tj_in_pt, posture_target, pt_n)); d_pt = p->tj_in_pt.f64(); }
+    if (ct_w) { HIP_OK(up(p->tj_in_ct, com_target, ct_n)); d_ct = p->tj_in_ct.f64(); }
+    o_q = p->tj_out_q.f64(); o_v = p->tj_out_v.f64(); o_qvel = io->qvel ? p->tj_out_qvel.f64() : nullptr;
+    o_st = p->tj_out_i32.i32();
+    o_it = io->iters ? o_st + N : nullptr;
+    o_cv = io->converged ? o_st + 2 * N : nullptr;
+  }
+  // ---- what the loops read and write: time-major slabs.  A time-major call: the caller's own arrays; a batch-major call:
+  //      transposed copies of the targets and a workspace for the results
+  double *l_q = o_q, *l_v = o_v;
+  int32_t *l_st = o_st, *l_it = o_it, *l_cv = o_cv;
+  if (!tm) {
+    HIP_OK(p->tj_q.need(N * nq * f8));
+    HIP_OK(p->tj_v.need(N * nv * f8));
+    HIP_OK(p->tj_i32.need(3 * N * i4));
+    l_q = p->tj_q.f64(); l_v = p->tj_v.f64();
+    l_st = p->tj_i32.i32();
+    l_it = o_it ? l_st + N : nullptr;
+    l_cv = o_cv ? l_st + 2 * N : nullptr;
+    if (ft_w) {
+      HIP_OK(p->tj_ft.need(N * ft_w * f8));
+      HIP_OK(launch_tj_gather(stream, d_ft, p->tj_ft.f64(), B, T, (int)ft_w));
+      d_ft = p->tj_ft.f64();
+    }
+    if (ptime && pbat) {             // (a target without a B axis has its T axis in front already)
+      HIP_OK(p->tj_pt.need(N * pt_w * f8));
+      HIP_OK(launch_tj_gather(stream, d_pt, p->tj_pt.f64(), B, T, (int)pt_w));
+      d_pt = p->tj_pt.f64();
+    }
+    if (ctime && cbat) {
+      HIP_OK(p->tj_ct.need(N * ct_w * f8));
+      HIP_OK(launch_tj_gather(stream, d_ct, p->tj_ct.f64(), B, T, (int)ct_w));
+      d_ct = p->tj_ct.f64();
+    }
+  }
+  // ---- the waypoints: one loop launch each on the caller's stream, slab t - 1 → slab t, nothing in between
+  const int32_t loop_flags = flags | MKH_FLAG_DEVICE_PTRS;
+  const size_t pt_step = ptime ? pt_w * (pbat ? Bz : 1) : 0, ct_step = ctime ? ct_w * (cbat ? Bz : 1) : 0;
+  int32_t rc = MKH_OK;
+  for (size_t t = 0; t < Tz && rc == MKH_OK; ++t) {
+    const double* const q_in = t ? l_q + (t - 1) * Bz * nq : d_q;
+    rc = run(p, B, q_in, d_ft ? d_ft + t * Bz * ft_w : nullptr, d_pt ? d_pt + t * pt_step : nullptr,
+             d_ct ? d_ct + t * ct_step : nullptr, dt, damping, l_v + t * Bz * nv, l_st + t * Bz, nullptr, loop_flags, hip_stream,
+             n_steps, l_q + t * Bz * nq, nullptr, until ? pos_threshold : -1.0, until ? ori_threshold : -1.0,
+             l_it ? l_it + t * Bz : nullptr, l_cv ? l_cv + t * Bz : nullptr);
+  }
+  if (rc != MKH_OK) {
+    (void)hipStreamSynchronize(stream);                       // (a failed call still drains what it started)
+    return rc;
+  }
+  hipError_t e = hipSuccess;
+  if (!tm) {
+    e = launch_tj_scatter(stream, l_q, o_q, B, T, (int)nq);
+    if (e == hipSuccess) e = launch_tj_scatter(stream, l_v, o_v, B, T, (int)nv);
+    if (e == hipSuccess) e = launch_tj_scatter_i32(stream, l_st, o_st, B, T);
+    if (e == hipSuccess && o_it) e = launch_tj_scatter_i32(stream, l_it, o_it, B, T);
+    if (e == hipSuccess && o_cv) e = launch_tj_scatter_i32(stream, l_cv, o_cv, B, T);
+  }
+  if (e == hipSuccess && o_qvel) {
+    // (instance, waypoint) strides in elements: the loops' time-major q, the caller's layout for qvel
+    const long long v_sb = tm ? (long long)nv : (long long)(Tz * nv), v_st = tm ? (long long)(Bz * nv) : (long long)nv;
+    e = launch_tj_qvel(stream, p->ms_jnt.i32(), p->model->njnt, B, T, (int)nq, d_q, l_q, (long long)nq, (long long)(Bz * nq),
+                       io->waypoint_dt, o_qvel, v_sb, v_st, tm ? 1 : 0);
+  }
+  if (devp) {
+    if (e != hipSuccess) { (void)hipStreamSynchronize(stream); return fail(MKH_E_HIP, "trajectory: %s", hipGetErrorString(e)); }
+    return MKH_OK;
+  }
+  auto down = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
+    return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream) : hipSuccess;
+  };
+  if (e == hipSuccess) e = down(io->q_traj, o_q, N * nq * f8);
+  if (e == hipSuccess) e = down(io->v_traj, o_v, N * nv * f8);
+  if (e == hipSuccess) e = down(io->status, o_st, N * i4);
+  if (e == hipSuccess) e = down(io->iters, o_it, N * i4);
+  if (e == hipSuccess) e = down(io->converged, o_cv, N * i4);
+  if (e == hipSuccess) e = down(io->qvel, o_qvel, N * nv * f8);
+  const hipError_t e2 = hipStreamSynchronize(stream);         // (a failed call still drains what it started)
+  if (e == hipSuccess) e = e2;
+  if (e != hipSuccess) return fail(MKH_E_HIP, "trajectory: %s", hipGetErrorString(e));
   return MKH_OK;
 }
 

@@ -484,6 +484,153 @@ def solve_ik_multistart(configuration: Configuration, tasks: Sequence, dt: float
                               for k, x in enumerate((res.q_all, res.converged_all, res.iters_all, res.status_all, res.seeds))])
 
 
+class TrajectoryResult(NamedTuple):
+    """Result of solve_ik_trajectory, (B, T, ·) — (T, ·) for an unbatched configuration: the configuration `q` at the end of
+    every waypoint's loop, the loop's last velocity `v`, its `status` bits, and in threshold mode its `iters` and `converged`
+    (None with a fixed step count); `qvel` = (q_t ⊖ q_{t−1}) / waypoint_dt when waypoint_dt was given, else None."""
+    q: np.ndarray
+    v: np.ndarray
+    status: np.ndarray
+    iters: Optional[np.ndarray] = None
+    converged: Optional[np.ndarray] = None
+    qvel: Optional[np.ndarray] = None
+
+
+def _trajectory_targets(configuration: Configuration, tasks: Sequence, targets):
+    """{id(task): (B, T, w) array} and T from the caller's mapping — shapes checked, nothing touched on a device."""
+    from .tasks import ComTask, FrameTask, PostureTask
+
+    items = list(targets.items()) if hasattr(targets, "items") else list(targets or ())
+    if not items:
+        raise ValueError("targets is empty: at least one task needs a (T, ...) sequence of targets")
+    B, T, out = configuration.batch_size, None, {}
+    for task, arr in items:
+        if not any(task is t for t in tasks):
+            raise ValueError(f"targets names a {type(task).__name__} that is not in `tasks`")
+        if isinstance(task, FrameTask):                      # (RelativeFrameTask included)
+            w, what = 7, "wxyz_xyz poses"
+        elif isinstance(task, PostureTask):
+            w, what = configuration.nq, "postures"
+        elif isinstance(task, ComTask):
+            w, what = 3, "CoM positions"
+        else:
+            raise ValueError(f"targets: a {type(task).__name__} takes no target sequence (FrameTask, RelativeFrameTask, "
+                             "PostureTask and ComTask do)")
+        arr = _host_array(getattr(arr, "wxyz_xyz", arr), f"targets[{type(task).__name__}]")
+        if arr.ndim == 2 and arr.shape[1] == w and arr.shape[0] >= 1:
+            arr = np.broadcast_to(arr, (B,) + arr.shape)
+        elif not (arr.ndim == 3 and arr.shape[0] == B and arr.shape[2] == w and arr.shape[1] >= 1):
+            raise ValueError(f"targets[{type(task).__name__}] must have shape (T, {w}) or ({B}, T, {w}) ({what}), got {arr.shape}")
+        if T is not None and arr.shape[1] != T:
+            raise ValueError(f"targets disagree on the number of waypoints T: {T} and {arr.shape[1]}")
+        T = arr.shape[1]
+        out[id(task)] = arr
+    return out, T
+
+
+def solve_ik_trajectory(configuration: Configuration, tasks: Sequence, dt: float, targets, n_steps: int = 1,
+                        solver: str = "mi355x", damping: float = 1e-12, limits: Optional[Sequence] = None,
+                        pos_threshold: Optional[float] = None, ori_threshold: Optional[float] = None,
+                        waypoint_dt: Optional[float] = None, warm_start: bool = False, update: bool = True,
+                        max_instances: int = 1 << 20) -> TrajectoryResult:
+    """Follow a time sequence of targets: every instance has T waypoints, waypoint t is solved by the fused loop of
+    solve_ik_steps from where waypoint t − 1 ended — in one call, nothing crossing the bus between waypoints.
+
+    `targets` maps task objects of `tasks` to their sequences: FrameTask / RelativeFrameTask (T, 7) or (B, T, 7) wxyz_xyz,
+    PostureTask (T, nq) or (B, T, nq), ComTask (T, 3) or (B, T, 3).  A task absent from the mapping keeps its set_target value
+    for the whole trajectory.  `n_steps` is the loop length per waypoint (1: tracking mode, one differential step per frame);
+    with `pos_threshold` / `ori_threshold` it is max_iters of the threshold-terminated loop and the result carries `iters` and
+    `converged` per waypoint.  `waypoint_dt`: also return the joint velocity between consecutive waypoints.
+
+    A waypoint that does not converge does NOT stop its trajectory: the next one starts from where the loop ended, and
+    `converged[b, t]` says what happened.  Limits warnings and SolverError follow solve_ik_steps' rules on the OR of the
+    statuses over the trajectory (the error names the first (instance, waypoint)).  With `update` the configuration is left
+    at q[:, -1].  When B exceeds `max_instances` the trajectories are walked in chunks of instances; a multi-device
+    configuration shards by trajectory."""
+    del solver
+    n_steps = int(n_steps)
+    if n_steps < 1:
+        raise ValueError("n_steps must be >= 1")
+    if int(max_instances) < 1:
+        raise ValueError("max_instances must be >= 1")
+    if waypoint_dt is not None and not float(waypoint_dt) > 0.0:
+        raise ValueError("waypoint_dt must be > 0")
+    seqs, T = _trajectory_targets(configuration, tasks, targets)
+    until = None
+    if pos_threshold is not None or ori_threshold is not None:
+        until = (float(pos_threshold if pos_threshold is not None else np.inf),
+                 float(ori_threshold if ori_threshold is not None else np.inf))
+        if until[0] < 0.0 or until[1] < 0.0:
+            raise ValueError("thresholds must be >= 0")
+    B = configuration.batch_size
+    devices = configuration.devices
+    chunk = min(B, int(max_instances))
+    n_dev = len(devices) if (len(devices) > 1 and chunk >= len(devices)) else 1
+    shard = -(-chunk // n_dev)
+    prob, layout = _compile_single(configuration, tasks, limits, shard, dt)
+    if layout["dense"] or layout["dense_limits"]:
+        raise exceptions.TaskDefinitionError(
+            "solve_ik_trajectory fuses the outer loop on the device; caller-defined Task / Limit subclasses are evaluated on "
+            "the host at every step: call solve_ik + integrate_inplace in a loop instead")
+
+    def stack(group, w, timed=False):
+        """Targets of one task group: per waypoint (B, T, n, w) when any of its tasks has a sequence (frame targets: always),
+        else as solve_ik_steps passes them."""
+        if not group:
+            return None
+        held = [np.asarray(t._native_target(configuration)) if id(t) not in seqs else None for t in group]
+        if not timed and not any(id(t) in seqs for t in group):
+            if all(h.ndim == 1 for h in held):
+                return np.stack(held, axis=0)
+            return np.stack([np.broadcast_to(h, (B, w)) for h in held], axis=1)
+        rows = [seqs[id(t)] if h is None else np.broadcast_to(np.broadcast_to(h, (B, w))[:, None, :], (B, T, w))
+                for t, h in zip(group, held)]
+        return np.ascontiguousarray(np.stack(rows, axis=2))
+
+    ft, pt, ct = stack(layout["frame"], 7, timed=True), stack(layout["posture"], configuration.nq), stack(layout["com"], 3)
+    q = configuration.q_batch
+
+    def rows(x, held_ndim, lo, hi):
+        return None if x is None else (x if x.ndim == held_ndim else np.ascontiguousarray(x[lo:hi]))
+
+    def job(handle, lo, hi):
+        return handle.solve_trajectory(q[lo:hi], rows(ft, 0, lo, hi), rows(pt, 2, lo, hi), rows(ct, 2, lo, hi), dt, damping,
+                                       n_steps=n_steps, until=until, qvel_dt=waypoint_dt, warm_start=bool(warm_start))
+
+    parts = []
+    with _pin(configuration, layout):
+        first = [prob] if isinstance(prob, nat.NativeProblem) else []
+        handles = first if (n_dev == 1 and first) else _multistart_shards(configuration, layout, first, devices[:n_dev], shard)
+        for c0 in range(0, B, chunk):
+            c1 = min(B, c0 + chunk)
+            bounds = [(c0 + lo, c0 + hi) for lo, hi in (shard_bounds(c1 - c0, n_dev, r) for r in range(n_dev))]
+            bounds = [(lo, hi) for lo, hi in bounds if hi > lo]
+            if len(bounds) == 1:
+                parts.append(job(handles[0], *bounds[0]))
+            else:
+                from concurrent.futures import ThreadPoolExecutor
+                with ThreadPoolExecutor(max_workers=len(bounds)) as pool:      # (a libminkhip call releases the GIL)
+                    parts += [f.result() for f in [pool.submit(job, h, lo, hi) for h, (lo, hi) in zip(handles, bounds)]]
+    res = TrajectoryResult(*[None if parts[0][k] is None else np.concatenate([p[k] for p in parts], axis=0)
+                             for k in range(len(TrajectoryResult._fields))])
+    status = res.status
+    outside = ((status & nat.ST_OUTSIDE_LIMITS) != 0).any(axis=1)
+    if outside.any():
+        logging.warning("solve_ik_trajectory: %d instance(s) were outside their configuration limits at some fused step",
+                        int(outside.sum()))
+    bad = np.argwhere((status & ~nat.ST_OUTSIDE_LIMITS) != 0)
+    if len(bad):
+        b0, t0 = (int(x) for x in bad[0])
+        raise exceptions.SolverError(f"QP failed at {len(bad)} of {status.size} waypoints "
+                                     f"(first: (instance, waypoint) = ({b0}, {t0}), status {int(status[b0, t0])})")
+    if update:
+        configuration.update(res.q[:, -1] if configuration.batched else res.q[0, -1])
+    un = configuration._unbatch
+    return TrajectoryResult(un(res.q), un(res.v), un(res.status), None if res.iters is None else un(res.iters),
+                            None if res.converged is None else un(res.converged.astype(bool)),
+                            None if res.qvel is None else un(res.qvel))
+
+
 def _compile_single(configuration: Configuration, tasks, limits, batch: int, dt: float):
     """_compile for ONE device whatever the configuration's device list says (multi-start shards by target itself: every shard
     has to know its global target offset, which ShardedProblem's row split does not pass on)."""
