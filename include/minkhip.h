@@ -494,6 +494,71 @@ int32_t mkh_solve_trajectory(MkhProblem *problem, int32_t B, int32_t T, const do
                              int32_t n_steps, double pos_threshold, double ori_threshold, const MkhTrajectoryIO *io,
                              int32_t flags, void *hip_stream);
 
+/*
+ * Keyframed trajectory IK: mkh_solve_trajectory whose T waypoint targets are interpolated on the device from K sparse
+ * keyframes per instance — a motion clip recorded at 30-120 Hz and tracked at the solver's dt, a Cartesian move given as two
+ * poses and a duration, a handful of via-points.  The keyframes cross the bus, not the waypoints, and the target workspace
+ * of the handle does not grow with T.  No counterpart in the reference.
+ *
+ * THE RULE.  key_times (K) and waypoint_times (T) are HOST arrays shared by the batch, whatever `flags` says about the
+ * other pointers.  key_times[0] < ... < key_times[K-1]; waypoint times are non-decreasing and every one lies inside
+ * [key_times[0], key_times[K-1]].  A waypoint time outside that range, key times that do not increase, waypoint times that
+ * decrease, or a NaN in either array: MKH_E_INVALID before any device work — no extrapolation, no silent clamping.
+ *
+ * For waypoint time tau the host picks the segment: k = the largest index with key_times[k] <= tau.
+ *   k == K-1   the waypoint IS keyframe K-1, copied bit for bit
+ *   otherwise  u = (tau - key_times[k]) / (key_times[k+1] - key_times[k]), in [0, 1): one rounded subtraction over one
+ *              rounded subtraction, one rounded quotient
+ *   u == 0     the waypoint IS keyframe k, copied bit for bit
+ * For 0 < u < 1, between keyframes a = key[k] and b = key[k+1]:
+ *   frame targets (wxyz_xyz)
+ *     rotation     normalize(q_a * exp(u * log(q_a^-1 * q_b))) with the reference's SO3.log — sign-invariant, angle in
+ *                  [0, pi]: the shortest arc whatever the sign of either quaternion — and SO3.exp, small-angle (Taylor)
+ *                  branches included
+ *     translation  p_a + u * (p_b - p_a): a rounded difference, a rounded product, a rounded sum, never an FMA
+ *     Rotation and translation are blended apart (what a retargeting or Cartesian-move caller means), not along the SE3 screw.
+ *   posture targets   q_a (+) u * (q_b (-) q_a), (-) = mj_differentiatePos at dt = 1, (+) = mj_integratePos:
+ *     hinge / slide coordinates, free-joint positions   a + u * (b - a), rounded as above
+ *     ball joints, free-joint rotations   mju_quatIntegrate(q_a, mju_quat2Vel(conj(q_a) * q_b, 1), u), then normalised
+ *   CoM targets       a + u * (b - a), rounded as above
+ * k and u are scalars of the kernel launches of waypoint t, which sit on the caller's stream directly in front of waypoint
+ * t's loop launch and write ONE (B, .) slab per target group that every waypoint reuses.
+ *
+ * Layout.  frame_keys (B, K, n_frame, 7).  posture_keys / com_keys: with posture_keyframed = 0 the held target of
+ * mkh_solve_trajectory — (n_posture, nq), or (B, n_posture, nq) with MKH_FLAG_POSTURE_BATCHED — and nothing is launched for
+ * it; with posture_keyframed = 1 a K axis sits where posture_per_waypoint puts the T axis: (B, K, n_posture, nq) batched,
+ * (K, n_posture, nq) otherwise.  The same for com_keys, com_keyframed and MKH_FLAG_COM_BATCHED.  With time_major = 1 the K
+ * axis of every input and the T axis of every output lead: frame_keys (K, B, n_frame, 7), q_traj (T, B, nq).  Keyframes are
+ * read in place through (instance, keyframe) strides: neither layout is transposed.
+ *
+ * frame_targets_out (B, T, n_frame, 7), posture_targets_out and com_targets_out (optional) receive the interpolated targets in
+ * the layout mkh_solve_trajectory takes them in with the same flags, *_per_waypoint = *_keyframed and the same time_major:
+ * the path the caller asked for.  posture_targets_out / com_targets_out must be NULL for a group that is held.  The call IS
+ * mkh_solve_trajectory on those arrays: same launches of the same loops, bitwise the same outputs.
+ *
+ * Everything else — the waypoint loop, threshold / fixed-count modes, the failing-waypoint rule, MKH_FLAG_WARM_START, host /
+ * device pointers, qvel over the uniform waypoint_dt, error ordering — is mkh_solve_trajectory's.
+ */
+typedef struct MkhKeyframeIO {
+  double *q_traj;               /* (B, T, nq)  as MkhTrajectoryIO                                                 required  */
+  double *v_traj;               /* (B, T, nv)                                                                     required  */
+  int32_t *status;              /* (B, T)                                                                         required  */
+  int32_t *iters;               /* (B, T)      threshold mode only, may be NULL                                             */
+  int32_t *converged;           /* (B, T)      threshold mode only, may be NULL                                             */
+  double *qvel;                 /* (B, T, nv)  optional: (q_t (-) q_{t-1}) / waypoint_dt, q_{-1} = q                        */
+  double *frame_targets_out;    /* (B, T, n_frame, 7)  optional: the interpolated frame targets                             */
+  double *posture_targets_out;  /* optional, posture_keyframed = 1 only: the interpolated posture targets                   */
+  double *com_targets_out;      /* optional, com_keyframed = 1 only: the interpolated CoM targets                           */
+  double waypoint_dt;           /* > 0 when qvel is given                                                                   */
+  int32_t posture_keyframed;    /* 0: posture_keys is a held target; 1: it has a K axis                                     */
+  int32_t com_keyframed;        /* the same for com_keys                                                                    */
+  int32_t time_major;           /* 1: the K axis of every input and the T axis of every output lead                         */
+} MkhKeyframeIO;
+int32_t mkh_solve_keyframes(MkhProblem *problem, int32_t B, int32_t K, int32_t T, const double *q, const double *frame_keys,
+                            const double *posture_keys, const double *com_keys, const double *key_times,
+                            const double *waypoint_times, double dt, double damping, int32_t n_steps, double pos_threshold,
+                            double ori_threshold, const MkhKeyframeIO *io, int32_t flags, void *hip_stream);
+
 /* Same inputs; additionally writes the requested intermediates (build_ik / compute_error /
  * compute_jacobian / get_transform_frame_to_world parity taps).  v_out/status_out may be NULL
  * to skip the QP. */

@@ -170,6 +170,47 @@ class TrajectoryOut(NamedTuple):
     qvel: object = None
 
 
+KEYFRAME_IO_FIELDS = ("q_traj", "v_traj", "status", "iters", "converged", "qvel", "frame_targets_out", "posture_targets_out",
+                      "com_targets_out", "waypoint_dt", "posture_keyframed", "com_keyframed", "time_major")
+
+
+class MkhKeyframeIO(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in KEYFRAME_IO_FIELDS[:9]] + [("waypoint_dt", C.c_double)] + \
+        [(n, C.c_int32) for n in KEYFRAME_IO_FIELDS[10:]]
+
+
+class KeyframesOut(NamedTuple):
+    """What NativeProblem.solve_keyframes returns: the TrajectoryOut of the T waypoints and, with return_targets, the
+    interpolated targets in the layout solve_trajectory takes them in (None for a group that is held or absent)."""
+    trajectory: TrajectoryOut
+    frame_targets: object = None
+    posture_targets: object = None
+    com_targets: object = None
+
+
+def check_keyframe_times(key_times, waypoint_times):
+    """The checks of include/minkhip.h "THE RULE" on the two time arrays, with no device in sight: float64 (K,) and (T,) arrays, or
+    ValueError — key times strictly increasing, waypoint times non-decreasing and inside the keyframes' range, no NaN."""
+    try:
+        kt = np.ascontiguousarray(key_times, dtype=np.float64)
+        wt = np.ascontiguousarray(waypoint_times, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError("keyframe_times and waypoint_times must be arrays of numbers") from e
+    if kt.ndim != 1 or kt.size < 1:
+        raise ValueError(f"keyframe_times must have shape (K,) with K >= 1, got {kt.shape}")
+    if wt.ndim != 1 or wt.size < 1:
+        raise ValueError(f"waypoint_times must have shape (T,) with T >= 1, got {wt.shape}")
+    if np.isnan(kt).any() or np.isnan(wt).any():
+        raise ValueError("keyframe_times / waypoint_times contain NaN")
+    if (np.diff(kt) <= 0.0).any():
+        raise ValueError("keyframe_times must be strictly increasing")
+    if (np.diff(wt) < 0.0).any():
+        raise ValueError("waypoint_times must be non-decreasing")
+    if wt[0] < kt[0] or wt[-1] > kt[-1]:
+        raise ValueError(f"waypoint_times must lie inside the keyframes' range [{kt[0]}, {kt[-1]}]: there is no extrapolation")
+    return kt, wt
+
+
 TAP_NAMES = ("xpos", "xquat", "frame_pose", "subtree_com", "task_e", "task_J", "H", "c", "box_lo",
              "box_hi", "coll_G", "coll_h", "qp_iters", "cycles")
 
@@ -229,6 +270,9 @@ def lib() -> C.CDLL:
     L.mkh_solve_trajectory.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + common[2:8] + \
         [C.c_int32, C.c_double, C.c_double, C.POINTER(MkhTrajectoryIO), C.c_int32, C.c_void_p]
     L.mkh_solve_trajectory.restype = C.c_int32
+    L.mkh_solve_keyframes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + common[2:6] + [C.c_void_p, C.c_void_p] + \
+        common[6:8] + [C.c_int32, C.c_double, C.c_double, C.POINTER(MkhKeyframeIO), C.c_int32, C.c_void_p]
+    L.mkh_solve_keyframes.restype = C.c_int32
     L.mkh_solve_dense.argtypes = common[:6] + [C.POINTER(MkhDenseRows), C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                                C.POINTER(MkhTaps), C.c_int32, C.c_void_p]
     L.mkh_solve_dense.restype = C.c_int32
@@ -254,7 +298,7 @@ EXPORTED_SYMBOLS = (
     "mkh_problem_num_collision_pairs", "mkh_solve", "mkh_eval", "mkh_integrate", "mkh_problem_launch_info",
     "mkh_solve_steps", "mkh_problem_last_kernel", "mkh_lie_eval", "mkh_solve_dense", "mkh_solve_until",
     "mkh_geom_distance_eval", "mkh_problem_create_diag", "mkh_solve_multistart",
-    "mkh_solve_trajectory",
+    "mkh_solve_trajectory", "mkh_solve_keyframes",
 )
 
 LIE_OPS = {"se3_log": (0, 7, 0, (6,)), "se3_jlog": (1, 7, 0, (6, 6)), "se3_ljacinv": (2, 6, 0, (6, 6)),
@@ -754,8 +798,25 @@ class NativeProblem:
             return self._solve_trajectory(q, frame_targets, posture_target, com_target, dt, damping, int(n_steps), until, qvel_dt,
                                           bool(time_major), warm_start, wave_kernel, lane_kernel, quad_kernel)
 
+    def solve_keyframes(self, q, keyframe_times, waypoint_times, frame_keys=None, posture_keys=None, com_keys=None,
+                        dt: float = 1e-2, damping: float = 1e-12, n_steps: int = 1, until: Optional[tuple] = None,
+                        qvel_dt: Optional[float] = None, time_major: bool = False, return_targets: bool = False,
+                        warm_start: bool = False, wave_kernel: bool = False, lane_kernel: bool = False,
+                        quad_kernel: bool = False) -> KeyframesOut:
+        """mkh_solve_keyframes: solve_trajectory whose T = len(waypoint_times) waypoint targets are interpolated on the device
+        from K = len(keyframe_times) keyframes (the rule: include/minkhip.h).  The target arrays are solve_trajectory's with a
+        K axis where that call has its T axis — frame_keys (B, K, n_frame, 7); posture / CoM keys held as in solve(), or with
+        a K axis; time_major: K leads the inputs, T the outputs.  The two time arrays are host sequences shared by the batch.
+        return_targets: also the interpolated targets, in the layout solve_trajectory takes them in.  numpy in → numpy out;
+        torch CUDA tensors in → torch tensors out on the current stream, no host copy."""
+        kt, wt = check_keyframe_times(keyframe_times, waypoint_times)
+        with self._lock:
+            return self._solve_trajectory(q, frame_keys, posture_keys, com_keys, dt, damping, int(n_steps), until, qvel_dt,
+                                          bool(time_major), warm_start, wave_kernel, lane_kernel, quad_kernel,
+                                          keys=(kt, wt, bool(return_targets)))
+
     def _solve_trajectory(self, q, frame_targets, posture_target, com_target, dt, damping, n_steps, until, qvel_dt, tm,
-                          warm_start, wave_kernel, lane_kernel, quad_kernel):
+                          warm_start, wave_kernel, lane_kernel, quad_kernel, keys=None):
         m = self.nmodel.model
         use_torch = _is_torch(q)
         B = int(q.shape[0])
@@ -835,6 +896,10 @@ class NativeProblem:
         if T is None:
             raise ValueError("no target has a T axis: nothing says how many waypoints there are")
         f8, i4 = np.float64, np.int32
+        if keys is not None:                                   # (the axis read off the shapes is the keyframes'; T is the waypoints')
+            K, T = T, len(keys[1])
+            if K != len(keys[0]):
+                raise ValueError(f"the targets have {K} keyframes, keyframe_times has {len(keys[0])}")
         lead = (T, B) if tm else (B, T)
         out_q, out_v, out_st = empty(lead + (m.nq,), f8), empty(lead + (m.nv,), f8), empty(lead, i4)
         out_it = out_cv = out_qvel = None
@@ -847,6 +912,26 @@ class NativeProblem:
         io.waypoint_dt = float(qvel_dt) if qvel_dt is not None else 0.0
         io.posture_per_waypoint, io.com_per_waypoint, io.time_major = p_time, c_time, int(tm)
         thr = (float(until[0]), float(until[1])) if until is not None else (-1.0, -1.0)
+        if keys is not None:
+            kt, wt, want = keys
+            out_ft = out_pt = out_ct = None
+            if want:
+                group = lambda batched: lead if batched else (T,)
+                if self.n_frame:
+                    out_ft = empty(lead + (self.n_frame, 7), f8)
+                if p_time:
+                    out_pt = empty(group(flags & FLAG_POSTURE_BATCHED) + (self.n_posture, m.nq), f8)
+                if c_time:
+                    out_ct = empty(group(flags & FLAG_COM_BATCHED) + (self.n_com, 3), f8)
+            kio = MkhKeyframeIO()
+            for n in TRAJECTORY_IO_FIELDS[:7] + ("time_major",):       # the outputs, waypoint_dt and the layout: as set above
+                setattr(kio, n, getattr(io, n))
+            kio.frame_targets_out, kio.posture_targets_out, kio.com_targets_out = ptr(out_ft), ptr(out_pt), ptr(out_ct)
+            kio.posture_keyframed, kio.com_keyframed = p_time, c_time
+            _check(lib().mkh_solve_keyframes(self.handle, B, K, T, ptr(q), ptr(frame_targets), ptr(posture_target), ptr(com_target),
+                                             kt.ctypes.data, wt.ctypes.data, float(dt), float(damping), n_steps, thr[0], thr[1],
+                                             C.byref(kio), flags, stream))
+            return KeyframesOut(TrajectoryOut(out_q, out_v, out_st, out_it, out_cv, out_qvel), out_ft, out_pt, out_ct)
         _check(lib().mkh_solve_trajectory(self.handle, B, T, ptr(q), ptr(frame_targets), ptr(posture_target), ptr(com_target),
                                           float(dt), float(damping), n_steps, thr[0], thr[1], C.byref(io), flags, stream))
         return TrajectoryOut(out_q, out_v, out_st, out_it, out_cv, out_qvel)

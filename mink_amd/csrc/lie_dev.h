@@ -5,6 +5,7 @@
 //   SO3.ljacinv    mink/lie/so3.py:214-226      SE3.ljacinv  mink/lie/se3.py:210-218
 //   _getQ          mink/lie/se3.py:222-249      jlog         mink/lie/base.py:150-156
 //   inverse / multiply / apply of both groups   so3.py:136-151, se3.py:136-157
+//   SO3.exp        mink/lie/so3.py:158-173      (keyframes.hip: the blend of frame targets between keyframes)
 // including the reference's branch thresholds (1e-10 on θ² resp. θ) so that the
 // same inputs take the same branch.  Quaternions are (w,x,y,z).
 #pragma once
@@ -127,6 +128,23 @@ __device__ __forceinline__ V3 so3_log(Q4 q) {
     }
   }
   return {factor * q.x, factor * q.y, factor * q.z};
+}
+
+// SO3.exp (mink/lie/so3.py:158-173), with the reference's Taylor branch below θ² = 1e-10.
+__device__ __forceinline__ Q4 so3_exp(V3 w) {
+  const double th2 = w.x * w.x + w.y * w.y + w.z * w.z;
+  double re, im;
+  if (th2 < 1e-10) {
+    const double th4 = th2 * th2;
+    re = 1.0 - th2 / 8.0 + th4 / 384.0;
+    im = 0.5 - th2 / 48.0 + th4 / 3840.0;
+  } else {
+    const double th = sqrt(th2);
+    double s;
+    sincos_cw(0.5 * th, &s, &re);
+    im = s / th;
+  }
+  return {re, im * w.x, im * w.y, im * w.z};
 }
 
 // mju_quat2Vel(quat, dt = 1): rotation vector of a (not necessarily unit) quaternion — axis = normalised vector part

@@ -216,6 +216,9 @@ struct MkhProblem {
   // (tj_i32: status | iters | converged), and the staging of host-pointer calls (tj_out_*: in the caller's layout)
   GrowBuf tj_ft, tj_pt, tj_ct, tj_q, tj_v, tj_i32;
   GrowBuf tj_in_q, tj_in_ft, tj_in_pt, tj_in_ct, tj_out_q, tj_out_v, tj_out_i32, tj_out_qvel;
+  // mkh_solve_keyframes: ONE (B, .) slab per target group, rewritten in front of every waypoint's loop, and the staging of
+  // the interpolated targets a host-pointer call asked for (the only buffers of the call's targets that grow with T)
+  GrowBuf kf_ft, kf_pt, kf_ct, kf_out_ft, kf_out_pt, kf_out_ct;
 };
 
 // The wavefront kernel's variants live in their own translation units (mink_amd/csrc/build.py generates one variant_<name>.hip
@@ -242,6 +245,14 @@ hipError_t launch_tj_scatter_i32(hipStream_t stream, const int32_t* src, int32_t
 hipError_t launch_tj_qvel(hipStream_t stream, const int32_t* jnt, int njnt, int B, int T, int nq, const double* q0,
                           const double* q_traj, long long q_sb, long long q_st, double dt, double* qvel, long long v_sb,
                           long long v_st, int time_major);
+// keyframed trajectory IK (keyframes.hip): waypoint t's targets blended from keyframes k and k + 1 at parameter u, read in place
+// through (instance, keyframe) strides, written to the loop's slab and (optionally) to waypoint t of the caller's *_targets_out
+hipError_t launch_kf_frames(hipStream_t stream, const double* keys, long long s_b, long long s_k, int k, double u, int rows,
+                            int n_frame, double* slab, double* out, long long o_sb);
+hipError_t launch_kf_posture(hipStream_t stream, const int32_t* jnt, int njnt, const double* keys, long long s_b, long long s_k,
+                             int k, double u, int rows, int n_posture, int nq, double* slab, double* out, long long o_sb);
+hipError_t launch_kf_com(hipStream_t stream, const double* keys, long long s_b, long long s_k, int k, double u, int rows,
+                         int width, double* slab, double* out, long long o_sb);
 constexpr int kLaneMinBatchLoop = 28672;  // fused loops of a small arm: row kernel below, lane kernel from here (M targets/s at 16 384: 39.7 vs 24.1, at 32 768: 42.4 vs 48.2)
 constexpr int kLaneMinBatch = 73728;  // plain solves of a small arm: row kernel below, lane kernel from here (plan_launch())
 }
@@ -1483,7 +1494,8 @@ void mkh_problem_destroy(MkhProblem* p) {
   for (GrowBuf* g : {&p->ms_seed_i, &p->ms_seed_f, &p->ms_jnt, &p->ms_q, &p->ms_seeds, &p->ms_ft, &p->ms_pt, &p->ms_ct, &p->ms_v,
                      &p->ms_i32, &p->ms_in_q, &p->ms_in_ft, &p->ms_in_pt, &p->ms_in_ct, &p->ms_in_ref, &p->ms_in_w, &p->ms_out_q,
                      &p->ms_out_v, &p->ms_out_i32, &p->tj_ft, &p->tj_pt, &p->tj_ct, &p->tj_q, &p->tj_v, &p->tj_i32, &p->tj_in_q,
-                     &p->tj_in_ft, &p->tj_in_pt, &p->tj_in_ct, &p->tj_out_q, &p->tj_out_v, &p->tj_out_i32, &p->tj_out_qvel})
+                     &p->tj_in_ft, &p->tj_in_pt, &p->tj_in_ct, &p->tj_out_q, &p->tj_out_v, &p->tj_out_i32, &p->tj_out_qvel, &p->kf_ft,
+                     &p->kf_pt, &p->kf_ct, &p->kf_out_ft, &p->kf_out_pt, &p->kf_out_ct})
     g->release();
   p->small.release();
   if (p->st_in) (void)hipStreamDestroy(p->st_in);
@@ -2345,10 +2357,54 @@ int32_t mkh_solve_multistart(MkhProblem* p, int32_t B, const double* q, const do
   return MKH_OK;
 }
 
-int32_t mkh_solve_trajectory(MkhProblem* p, int32_t B, int32_t T, const double* q, const double* frame_targets,
-                             const double* posture_target, const double* com_target, double dt, double damping,
-                             int32_t n_steps, double pos_threshold, double ori_threshold, const MkhTrajectoryIO* io,
-                             int32_t flags, void* hip_stream) {
+}  // extern "C"
+
+// What mkh_solve_keyframes adds to a trajectory call: the targets have a K axis where the trajectory call has its T axis, and
+// waypoint t's targets are blended from keyframes seg_k[t], seg_k[t] + 1 at seg_u[t] in front of its loop (keyframes.hip).
+struct KeyframeSpec {
+  int32_t K;
+  const double *key_times, *waypoint_times;                // host
+  double *ft_out, *pt_out, *ct_out;                        // the caller's optional *_targets_out
+  std::vector<int32_t> seg_k;
+  std::vector<double> seg_u;
+};
+
+// The segment of every waypoint (include/minkhip.h "THE RULE"), or the first thing wrong with the two time arrays.
+static int32_t kf_segments(KeyframeSpec* kf, int32_t T) {
+  const int32_t K = kf->K;
+  const double *kt = kf->key_times, *wt = kf->waypoint_times;
+  if (K < 1) return fail(MKH_E_INVALID, "K must be >= 1");
+  if (!kt || !wt) return fail(MKH_E_INVALID, "key_times and waypoint_times are required (host arrays)");
+  for (int32_t k = 0; k < K; ++k) {
+    if (kt[k] != kt[k]) return fail(MKH_E_INVALID, "key_times[%d] is NaN", k);
+    if (k && !(kt[k - 1] < kt[k])) return fail(MKH_E_INVALID, "key_times must be strictly increasing (at index %d)", k);
+  }
+  kf->seg_k.resize(T);
+  kf->seg_u.resize(T);
+  int32_t k = 0;
+  for (int32_t t = 0; t < T; ++t) {
+    const double tau = wt[t];
+    if (tau != tau) return fail(MKH_E_INVALID, "waypoint_times[%d] is NaN", t);
+    if (t && tau < wt[t - 1]) return fail(MKH_E_INVALID, "waypoint_times must be non-decreasing (at index %d)", t);
+    if (tau < kt[0] || tau > kt[K - 1])
+      return fail(MKH_E_INVALID, "waypoint_times[%d] = %g lies outside the keyframes' range [%g, %g]: no extrapolation", t, tau,
+                  kt[0], kt[K - 1]);
+    while (k + 1 < K && kt[k + 1] <= tau) ++k;             // (waypoint times do not decrease: k never goes back)
+    double u = 0.0;
+    if (k < K - 1)
+      u = (tau - kt[k]) / (kt[k + 1] - kt[k]);
+    kf->seg_k[t] = k;
+    kf->seg_u[t] = u;
+  }
+  return MKH_OK;
+}
+
+// mkh_solve_trajectory and, with `kf`, mkh_solve_keyframes: the T stream-ordered loop launches between slabs of time-major
+// buffers and everything around them.  `who` names the entry point in messages.
+static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double* q, const double* frame_targets,
+                               const double* posture_target, const double* com_target, double dt, double damping,
+                               int32_t n_steps, double pos_threshold, double ori_threshold, const MkhTrajectoryIO* io,
+                               int32_t flags, void* hip_stream, KeyframeSpec* kf, const char* who) {
   // (what can be judged from the arguments alone comes first: it needs neither a handle nor a device)
   if (B < 1) return fail(MKH_E_INVALID, "B must be >= 1");
   if (T < 1) return fail(MKH_E_INVALID, "T must be >= 1");
@@ -2362,11 +2418,16 @@ int32_t mkh_solve_trajectory(MkhProblem* p, int32_t B, int32_t T, const double* 
   if (!until && (io->iters || io->converged))
     return fail(MKH_E_INVALID, "iters / converged are outputs of threshold mode: they must be NULL with a fixed count");
   if (io->qvel && !(io->waypoint_dt > 0.0)) return fail(MKH_E_INVALID, "qvel needs waypoint_dt > 0");
+  if (kf) {
+    if (const int32_t rc = kf_segments(kf, T)) return rc;
+    if ((kf->pt_out && !io->posture_per_waypoint) || (kf->ct_out && !io->com_per_waypoint))
+      return fail(MKH_E_INVALID, "posture_targets_out / com_targets_out must be NULL for a target that is held");
+  }
   if (!p) return fail(MKH_E_INVALID, "null problem");
   const DeviceProblem& P = p->dev;
   if (!q) return fail(MKH_E_INVALID, "q is null");
   if (until && P.n_frame < 1)
-    return fail(MKH_E_INVALID, "mkh_solve_trajectory needs at least one frame task to test the thresholds on");
+    return fail(MKH_E_INVALID, "%s needs at least one frame task to test the thresholds on", who);
   if (P.n_frame > 0 && !frame_targets) return fail(MKH_E_INVALID, "frame_targets is null (TargetNotSet)");
   if (P.n_posture > 0 && !posture_target) return fail(MKH_E_INVALID, "posture_target is null (TargetNotSet)");
   if (P.n_com > 0 && !com_target) return fail(MKH_E_INVALID, "com_target is null (TargetNotSet)");
@@ -2374,7 +2435,7 @@ int32_t mkh_solve_trajectory(MkhProblem* p, int32_t B, int32_t T, const double* 
     return fail(MKH_E_INVALID, "dense (plugin) rows are evaluated by the caller at q: no fused loop, no trajectory");
   if (B > p->max_batch) return fail(MKH_E_INVALID, "B=%d exceeds max_batch=%d of this problem", B, p->max_batch);
   HIP_OK(hipSetDevice(p->model->device));
-  if (io->qvel)
+  if (io->qvel || (kf && io->posture_per_waypoint && P.n_posture > 0))
     if (const int32_t rc = ms_build_tables(p)) return rc;
   hipStream_t stream = (hipStream_t)hip_stream;
   const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0, tm = io->time_major != 0;
@@ -2382,7 +2443,8 @@ int32_t mkh_solve_trajectory(MkhProblem* p, int32_t B, int32_t T, const double* 
   const bool ptime = io->posture_per_waypoint != 0 && P.n_posture > 0, ctime = io->com_per_waypoint != 0 && P.n_com > 0;
   const size_t Bz = B, Tz = T, N = Bz * Tz, nq = P.nq, nv = P.nv, f8 = sizeof(double), i4 = sizeof(int32_t);
   const size_t ft_w = (size_t)P.n_frame * 7, pt_w = (size_t)P.n_posture * nq, ct_w = (size_t)P.n_com * 3;
-  const size_t pt_n = pt_w * (pbat ? Bz : 1) * (ptime ? Tz : 1), ct_n = ct_w * (cbat ? Bz : 1) * (ctime ? Tz : 1);
+  const size_t Kz = kf ? (size_t)kf->K : Tz;                 // the length of the targets' time axis
+  const size_t pt_n = pt_w * (pbat ? Bz : 1) * (ptime ? Kz : 1), ct_n = ct_w * (cbat ? Bz : 1) * (ctime ? Kz : 1);
 
   // ---- inputs and the caller-layout outputs on the device
   const double *d_q = q, *d_ft = frame_targets, *d_pt = posture_target, *d_ct = com_target;
@@ -2398,13 +2460,27 @@ int32_t mkh_solve_trajectory(MkhProblem* p, int32_t B, int32_t T, const double* 
     HIP_OK(p->tj_out_i32.need(3 * N * i4));
     if (io->qvel) HIP_OK(p->tj_out_qvel.need(N * nv * f8));
     HIP_OK(up(p->tj_in_q, q, Bz * nq)); d_q = p->tj_in_q.f64();
-    if (ft_w) { HIP_OK(up(p->tj_in_ft, frame_targets, N * ft_w)); d_ft = p->tj_in_ft.f64(); }
+    if (ft_w) { HIP_OK(up(p->tj_in_ft, frame_targets, Bz * Kz * ft_w)); d_ft = p->tj_in_ft.f64(); }
     if (pt_w) { HIP_OK(up(p->tj_in_pt, posture_target, pt_n)); d_pt = p->tj_in_pt.f64(); }
     if (ct_w) { HIP_OK(up(p->tj_in_ct, com_target, ct_n)); d_ct = p->tj_in_ct.f64(); }
     o_q = p->tj_out_q.f64(); o_v = p->tj_out_v.f64(); o_qvel = io->qvel ? p->tj_out_qvel.f64() : nullptr;
     o_st = p->tj_out_i32.i32();
     o_it = io->iters ? o_st + N : nullptr;
     o_cv = io->converged ? o_st + 2 * N : nullptr;
+  }
+  // ---- keyframes: one slab per target group for all waypoints; the interpolated targets, where asked for, in the caller's layout
+  double *k_ft_out = nullptr, *k_pt_out = nullptr, *k_ct_out = nullptr;
+  const size_t pt_rows = pbat ? Bz : 1, ct_rows = cbat ? Bz : 1;
+  if (kf) {
+    k_ft_out = ft_w ? kf->ft_out : nullptr; k_pt_out = ptime ? kf->pt_out : nullptr; k_ct_out = ctime ? kf->ct_out : nullptr;
+    if (ft_w) HIP_OK(p->kf_ft.need(Bz * ft_w * f8));
+    if (ptime) HIP_OK(p->kf_pt.need(pt_rows * pt_w * f8));
+    if (ctime) HIP_OK(p->kf_ct.need(ct_rows * ct_w * f8));
+    if (!devp) {
+      if (k_ft_out) { HIP_OK(p->kf_out_ft.need(N * ft_w * f8)); k_ft_out = p->kf_out_ft.f64(); }
+      if (k_pt_out) { HIP_OK(p->kf_out_pt.need(Tz * pt_rows * pt_w * f8)); k_pt_out = p->kf_out_pt.f64(); }
+      if (k_ct_out) { HIP_OK(p->kf_out_ct.need(Tz * ct_rows * ct_w * f8)); k_ct_out = p->kf_out_ct.f64(); }
+    }
   }
   // ---- what the loops read and write: time-major slabs.  A time-major call: the caller's own arrays; a batch-major call:
   //      transposed copies of the targets and a workspace for the results
@@ -2418,17 +2494,17 @@ int32_t mkh_solve_trajectory(MkhProblem* p, int32_t B, int32_t T, const double* 
     l_st = p->tj_i32.i32();
     l_it = o_it ? l_st + N : nullptr;
     l_cv = o_cv ? l_st + 2 * N : nullptr;
-    if (ft_w) {
+    if (ft_w && !kf) {                // (keyframes are read in place through strides: no transposed copy)
       HIP_OK(p->tj_ft.need(N * ft_w * f8));
       HIP_OK(launch_tj_gather(stream, d_ft, p->tj_ft.f64(), B, T, (int)ft_w));
       d_ft = p->tj_ft.f64();
     }
-    if (ptime && pbat) {             // (a target without a B axis has its T axis in front already)
+    if (ptime && pbat && !kf) {      // (a target without a B axis has its T axis in front already)
       HIP_OK(p->tj_pt.need(N * pt_w * f8));
       HIP_OK(launch_tj_gather(stream, d_pt, p->tj_pt.f64(), B, T, (int)pt_w));
       d_pt = p->tj_pt.f64();
     }
-    if (ctime && cbat) {
+    if (ctime && cbat && !kf) {
       HIP_OK(p->tj_ct.need(N * ct_w * f8));
       HIP_OK(launch_tj_gather(stream, d_ct, p->tj_ct.f64(), B, T, (int)ct_w));
       d_ct = p->tj_ct.f64();
@@ -2438,10 +2514,44 @@ int32_t mkh_solve_trajectory(MkhProblem* p, int32_t B, int32_t T, const double* 
   const int32_t loop_flags = flags | MKH_FLAG_DEVICE_PTRS;
   const size_t pt_step = ptime ? pt_w * (pbat ? Bz : 1) : 0, ct_step = ctime ? ct_w * (cbat ? Bz : 1) : 0;
   int32_t rc = MKH_OK;
+  // (instance, keyframe) strides of a keyframe array and the (instance stride, waypoint stride) of a *_targets_out, in
+  // elements, for a group of `rows` rows of width w
+  auto key_sb = [&](size_t rows, size_t w) { return (long long)(rows == 1 ? 0 : (tm ? w : Kz * w)); };
+  auto key_sk = [&](size_t rows, size_t w) { return (long long)(tm ? rows * w : w); };
+  auto out_sb = [&](size_t rows, size_t w) { return (long long)(rows == 1 ? 0 : (tm ? w : Tz * w)); };
+  auto out_st = [&](size_t rows, size_t w) { return tm ? rows * w : w; };
   for (size_t t = 0; t < Tz && rc == MKH_OK; ++t) {
     const double* const q_in = t ? l_q + (t - 1) * Bz * nq : d_q;
-    rc = run(p, B, q_in, d_ft ? d_ft + t * Bz * ft_w : nullptr, d_pt ? d_pt + t * pt_step : nullptr,
-             d_ct ? d_ct + t * ct_step : nullptr, dt, damping, l_v + t * Bz * nv, l_st + t * Bz, nullptr, loop_flags, hip_stream,
+    const double *t_ft = nullptr, *t_pt = d_pt, *t_ct = d_ct;       // (held targets: the same array for every waypoint)
+    if (!kf) {
+      t_ft = d_ft ? d_ft + t * Bz * ft_w : nullptr;
+      t_pt = d_pt ? d_pt + t * pt_step : nullptr;
+      t_ct = d_ct ? d_ct + t * ct_step : nullptr;
+    } else {
+      const int k = kf->seg_k[t];
+      const double u = kf->seg_u[t];
+      hipError_t ke = hipSuccess;
+      if (ft_w) {
+        ke = launch_kf_frames(stream, d_ft, key_sb(Bz, ft_w), key_sk(Bz, ft_w), k, u, B, P.n_frame, p->kf_ft.f64(),
+                              k_ft_out ? k_ft_out + t * out_st(Bz, ft_w) : nullptr, out_sb(Bz, ft_w));
+        t_ft = p->kf_ft.f64();
+      }
+      if (ptime) {
+        if (ke == hipSuccess)
+          ke = launch_kf_posture(stream, p->ms_jnt.i32(), p->model->njnt, d_pt, key_sb(pt_rows, pt_w), key_sk(pt_rows, pt_w), k, u,
+                                 (int)pt_rows, P.n_posture, (int)nq, p->kf_pt.f64(),
+                                 k_pt_out ? k_pt_out + t * out_st(pt_rows, pt_w) : nullptr, out_sb(pt_rows, pt_w));
+        t_pt = p->kf_pt.f64();
+      }
+      if (ctime) {
+        if (ke == hipSuccess)
+          ke = launch_kf_com(stream, d_ct, key_sb(ct_rows, ct_w), key_sk(ct_rows, ct_w), k, u, (int)ct_rows, (int)ct_w,
+                             p->kf_ct.f64(), k_ct_out ? k_ct_out + t * out_st(ct_rows, ct_w) : nullptr, out_sb(ct_rows, ct_w));
+        t_ct = p->kf_ct.f64();
+      }
+      if (ke != hipSuccess) { rc = fail(MKH_E_HIP, "%s: %s", who, hipGetErrorString(ke)); break; }
+    }
+    rc = run(p, B, q_in, t_ft, t_pt, t_ct, dt, damping, l_v + t * Bz * nv, l_st + t * Bz, nullptr, loop_flags, hip_stream,
              n_steps, l_q + t * Bz * nq, nullptr, until ? pos_threshold : -1.0, until ? ori_threshold : -1.0,
              l_it ? l_it + t * Bz : nullptr, l_cv ? l_cv + t * Bz : nullptr);
   }
@@ -2464,7 +2574,7 @@ int32_t mkh_solve_trajectory(MkhProblem* p, int32_t B, int32_t T, const double* 
                        io->waypoint_dt, o_qvel, v_sb, v_st, tm ? 1 : 0);
   }
   if (devp) {
-    if (e != hipSuccess) { (void)hipStreamSynchronize(stream); return fail(MKH_E_HIP, "trajectory: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) { (void)hipStreamSynchronize(stream); return fail(MKH_E_HIP, "%s: %s", who, hipGetErrorString(e)); }
     return MKH_OK;
   }
   auto down = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
@@ -2476,10 +2586,44 @@ int32_t mkh_solve_trajectory(MkhProblem* p, int32_t B, int32_t T, const double* 
   if (e == hipSuccess) e = down(io->iters, o_it, N * i4);
   if (e == hipSuccess) e = down(io->converged, o_cv, N * i4);
   if (e == hipSuccess) e = down(io->qvel, o_qvel, N * nv * f8);
+  if (kf) {
+    if (e == hipSuccess) e = down(kf->ft_out, k_ft_out, N * ft_w * f8);
+    if (e == hipSuccess) e = down(kf->pt_out, k_pt_out, Tz * pt_rows * pt_w * f8);
+    if (e == hipSuccess) e = down(kf->ct_out, k_ct_out, Tz * ct_rows * ct_w * f8);
+  }
   const hipError_t e2 = hipStreamSynchronize(stream);         // (a failed call still drains what it started)
   if (e == hipSuccess) e = e2;
-  if (e != hipSuccess) return fail(MKH_E_HIP, "trajectory: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fail(MKH_E_HIP, "%s: %s", who, hipGetErrorString(e));
   return MKH_OK;
+}
+
+extern "C" {
+
+int32_t mkh_solve_trajectory(MkhProblem* p, int32_t B, int32_t T, const double* q, const double* frame_targets,
+                             const double* posture_target, const double* com_target, double dt, double damping,
+                             int32_t n_steps, double pos_threshold, double ori_threshold, const MkhTrajectoryIO* io,
+                             int32_t flags, void* hip_stream) {
+  return trajectory_core(p, B, T, q, frame_targets, posture_target, com_target, dt, damping, n_steps, pos_threshold,
+                         ori_threshold, io, flags, hip_stream, nullptr, "mkh_solve_trajectory");
+}
+
+int32_t mkh_solve_keyframes(MkhProblem* p, int32_t B, int32_t K, int32_t T, const double* q, const double* frame_keys,
+                            const double* posture_keys, const double* com_keys, const double* key_times,
+                            const double* waypoint_times, double dt, double damping, int32_t n_steps, double pos_threshold,
+                            double ori_threshold, const MkhKeyframeIO* io, int32_t flags, void* hip_stream) {
+  // the trajectory call's view of the struct: same outputs, a K axis where *_per_waypoint puts the T axis
+  MkhTrajectoryIO tio;
+  KeyframeSpec kf;
+  kf.K = K; kf.key_times = key_times; kf.waypoint_times = waypoint_times;
+  kf.ft_out = kf.pt_out = kf.ct_out = nullptr;
+  if (io) {
+    tio.q_traj = io->q_traj; tio.v_traj = io->v_traj; tio.status = io->status; tio.iters = io->iters;
+    tio.converged = io->converged; tio.qvel = io->qvel; tio.waypoint_dt = io->waypoint_dt;
+    tio.posture_per_waypoint = io->posture_keyframed; tio.com_per_waypoint = io->com_keyframed; tio.time_major = io->time_major;
+    kf.ft_out = io->frame_targets_out; kf.pt_out = io->posture_targets_out; kf.ct_out = io->com_targets_out;
+  }
+  return trajectory_core(p, B, T, q, frame_keys, posture_keys, com_keys, dt, damping, n_steps, pos_threshold, ori_threshold,
+                         io ? &tio : nullptr, flags, hip_stream, &kf, "mkh_solve_keyframes");
 }
 
 int32_t mkh_integrate(MkhModel* m, int32_t B, const double* q, const double* v, double dt, double* q_out,

@@ -496,8 +496,9 @@ class TrajectoryResult(NamedTuple):
     qvel: Optional[np.ndarray] = None
 
 
-def _trajectory_targets(configuration: Configuration, tasks: Sequence, targets):
-    """{id(task): (B, T, w) array} and T from the caller's mapping — shapes checked, nothing touched on a device."""
+def _trajectory_targets(configuration: Configuration, tasks: Sequence, targets, axis: str = "waypoints T"):
+    """{id(task): (B, T, w) array} and T from the caller's mapping — shapes checked, nothing touched on a device.  (`axis`
+    names the sequences' axis in messages: the keyframed call's sequences have K keyframes there.)"""
     from .tasks import ComTask, FrameTask, PostureTask
 
     items = list(targets.items()) if hasattr(targets, "items") else list(targets or ())
@@ -522,7 +523,7 @@ def _trajectory_targets(configuration: Configuration, tasks: Sequence, targets):
         elif not (arr.ndim == 3 and arr.shape[0] == B and arr.shape[2] == w and arr.shape[1] >= 1):
             raise ValueError(f"targets[{type(task).__name__}] must have shape (T, {w}) or ({B}, T, {w}) ({what}), got {arr.shape}")
         if T is not None and arr.shape[1] != T:
-            raise ValueError(f"targets disagree on the number of waypoints T: {T} and {arr.shape[1]}")
+            raise ValueError(f"targets disagree on the number of {axis}: {T} and {arr.shape[1]}")
         T = arr.shape[1]
         out[id(task)] = arr
     return out, T
@@ -532,7 +533,8 @@ def solve_ik_trajectory(configuration: Configuration, tasks: Sequence, dt: float
                         solver: str = "mi355x", damping: float = 1e-12, limits: Optional[Sequence] = None,
                         pos_threshold: Optional[float] = None, ori_threshold: Optional[float] = None,
                         waypoint_dt: Optional[float] = None, warm_start: bool = False, update: bool = True,
-                        max_instances: int = 1 << 20) -> TrajectoryResult:
+                        max_instances: int = 1 << 20, keyframe_times=None, waypoint_times=None,
+                        return_targets: bool = False):
     """Follow a time sequence of targets: every instance has T waypoints, waypoint t is solved by the fused loop of
     solve_ik_steps from where waypoint t − 1 ended — in one call, nothing crossing the bus between waypoints.
 
@@ -541,6 +543,17 @@ def solve_ik_trajectory(configuration: Configuration, tasks: Sequence, dt: float
     for the whole trajectory.  `n_steps` is the loop length per waypoint (1: tracking mode, one differential step per frame);
     with `pos_threshold` / `ori_threshold` it is max_iters of the threshold-terminated loop and the result carries `iters` and
     `converged` per waypoint.  `waypoint_dt`: also return the joint velocity between consecutive waypoints.
+
+    Keyframes.  With `keyframe_times` (K strictly increasing times) the sequences of `targets` are K sparse KEYFRAMES, and
+    the T = len(waypoint_times) waypoint targets are interpolated from them on the device: only the keyframes cross the bus.
+    `waypoint_times` (required then) are non-decreasing and lie inside [keyframe_times[0], keyframe_times[-1]] — there is no
+    extrapolation and no clamping.  A waypoint at a keyframe's time IS that keyframe, bit for bit; in between, with
+    u = (τ − t_k) / (t_{k+1} − t_k): frame targets blend rotation and translation apart — the shortest arc
+    q_a·exp(u·log(q_a⁻¹·q_b)) and p_a + u·(p_b − p_a), not the SE3 screw; postures q_a ⊕ u·(q_b ⊖ q_a) per joint type
+    (mj_differentiatePos / mj_integratePos); CoM targets a + u·(b − a) (the rule in full: include/minkhip.h).  Both time
+    arrays are shared by the batch; `waypoint_dt` stays one uniform step.  `return_targets=True` returns
+    (TrajectoryResult, {task: (B, T, w) array}) — the interpolated path of every task of `targets`, as the loops read it.
+    Without `keyframe_times`, `waypoint_times` or `return_targets` raise ValueError.
 
     A waypoint that does not converge does NOT stop its trajectory: the next one starts from where the loop ended, and
     `converged[b, t]` says what happened.  Limits warnings and SolverError follow solve_ik_steps' rules on the OR of the
@@ -555,7 +568,18 @@ def solve_ik_trajectory(configuration: Configuration, tasks: Sequence, dt: float
         raise ValueError("max_instances must be >= 1")
     if waypoint_dt is not None and not float(waypoint_dt) > 0.0:
         raise ValueError("waypoint_dt must be > 0")
-    seqs, T = _trajectory_targets(configuration, tasks, targets)
+    kt = wt = None
+    if keyframe_times is None:
+        if waypoint_times is not None or return_targets:
+            raise ValueError("waypoint_times and return_targets belong to the keyframed call: they need keyframe_times")
+        seqs, L = _trajectory_targets(configuration, tasks, targets)      # L: the length of the sequences' axis
+    else:
+        if waypoint_times is None:
+            raise ValueError("keyframe_times needs waypoint_times: the times at which the keyframes are sampled")
+        kt, wt = nat.check_keyframe_times(_host_array(keyframe_times, "keyframe_times"), _host_array(waypoint_times, "waypoint_times"))
+        seqs, L = _trajectory_targets(configuration, tasks, targets, axis="keyframes K")
+        if L != len(kt):
+            raise ValueError(f"targets have {L} keyframes, keyframe_times has {len(kt)}")
     until = None
     if pos_threshold is not None or ori_threshold is not None:
         until = (float(pos_threshold if pos_threshold is not None else np.inf),
@@ -583,7 +607,7 @@ def solve_ik_trajectory(configuration: Configuration, tasks: Sequence, dt: float
             if all(h.ndim == 1 for h in held):
                 return np.stack(held, axis=0)
             return np.stack([np.broadcast_to(h, (B, w)) for h in held], axis=1)
-        rows = [seqs[id(t)] if h is None else np.broadcast_to(np.broadcast_to(h, (B, w))[:, None, :], (B, T, w))
+        rows = [seqs[id(t)] if h is None else np.broadcast_to(np.broadcast_to(h, (B, w))[:, None, :], (B, L, w))
                 for t, h in zip(group, held)]
         return np.ascontiguousarray(np.stack(rows, axis=2))
 
@@ -594,8 +618,11 @@ def solve_ik_trajectory(configuration: Configuration, tasks: Sequence, dt: float
         return None if x is None else (x if x.ndim == held_ndim else np.ascontiguousarray(x[lo:hi]))
 
     def job(handle, lo, hi):
-        return handle.solve_trajectory(q[lo:hi], rows(ft, 0, lo, hi), rows(pt, 2, lo, hi), rows(ct, 2, lo, hi), dt, damping,
-                                       n_steps=n_steps, until=until, qvel_dt=waypoint_dt, warm_start=bool(warm_start))
+        kw = dict(n_steps=n_steps, until=until, qvel_dt=waypoint_dt, warm_start=bool(warm_start))
+        if kt is None:
+            return handle.solve_trajectory(q[lo:hi], rows(ft, 0, lo, hi), rows(pt, 2, lo, hi), rows(ct, 2, lo, hi), dt, damping, **kw)
+        return handle.solve_keyframes(q[lo:hi], kt, wt, rows(ft, 0, lo, hi), rows(pt, 2, lo, hi), rows(ct, 2, lo, hi), dt, damping,
+                                      return_targets=bool(return_targets), **kw)
 
     parts = []
     with _pin(configuration, layout):
@@ -611,6 +638,11 @@ def solve_ik_trajectory(configuration: Configuration, tasks: Sequence, dt: float
                 from concurrent.futures import ThreadPoolExecutor
                 with ThreadPoolExecutor(max_workers=len(bounds)) as pool:      # (a libminkhip call releases the GIL)
                     parts += [f.result() for f in [pool.submit(job, h, lo, hi) for h, (lo, hi) in zip(handles, bounds)]]
+    paths = None
+    if kt is not None:                                         # (parts: KeyframesOut — the trajectory and the interpolated targets)
+        if return_targets:
+            paths = [None if parts[0][k] is None else np.concatenate([p[k] for p in parts], axis=0) for k in (1, 2, 3)]
+        parts = [p.trajectory for p in parts]
     res = TrajectoryResult(*[None if parts[0][k] is None else np.concatenate([p[k] for p in parts], axis=0)
                              for k in range(len(TrajectoryResult._fields))])
     status = res.status
@@ -626,9 +658,18 @@ def solve_ik_trajectory(configuration: Configuration, tasks: Sequence, dt: float
     if update:
         configuration.update(res.q[:, -1] if configuration.batched else res.q[0, -1])
     un = configuration._unbatch
-    return TrajectoryResult(un(res.q), un(res.v), un(res.status), None if res.iters is None else un(res.iters),
-                            None if res.converged is None else un(res.converged.astype(bool)),
-                            None if res.qvel is None else un(res.qvel))
+    res = TrajectoryResult(un(res.q), un(res.v), un(res.status), None if res.iters is None else un(res.iters),
+                           None if res.converged is None else un(res.converged.astype(bool)),
+                           None if res.qvel is None else un(res.qvel))
+    if paths is None:
+        return res
+    # the interpolated path of every task of `targets`: its column of its group's (B, T, n, w) array
+    by_task = {}
+    for group, arr in zip((layout["frame"], layout["posture"], layout["com"]), paths):
+        for n, t in enumerate(group):
+            if id(t) in seqs:
+                by_task[t] = un(np.ascontiguousarray(arr[:, :, n]))
+    return res, by_task
 
 
 def _compile_single(configuration: Configuration, tasks, limits, batch: int, dt: float):
