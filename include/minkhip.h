@@ -559,6 +559,87 @@ int32_t mkh_solve_keyframes(MkhProblem *problem, int32_t B, int32_t K, int32_t T
                             const double *waypoint_times, double dt, double damping, int32_t n_steps, double pos_threshold,
                             double ori_threshold, const MkhKeyframeIO *io, int32_t flags, void *hip_stream);
 
+/*
+ * Multi-start trajectory IK: mkh_solve_trajectory from n_seeds = S candidate starts per instance — S candidate trajectories,
+ * each continuous by construction (waypoint t starts from the same candidate's waypoint t - 1) —, scored over the whole path,
+ * one of them chosen and gathered on the device: one call, no B·S·T rows over the bus.  It is what a caller writes around
+ * mkh_solve_trajectory when the path's first pose lies far from the current posture, or when the single start lands on an IK
+ * branch that runs into a joint limit half-way along the path.  No counterpart in the reference.
+ *
+ * THE RULE.
+ * Candidates.  Candidate i = b·S + s (the candidates of an instance are contiguous).  Their starts are mkh_solve_multistart's:
+ * the same generator u(rng_seed, target_index0 + b, s, k), the same per-joint seeding rule, io->seeds (B, S, nq) as the
+ * alternative.  CANDIDATE 0 OF EVERY INSTANCE STARTS AT THE CALLER'S OWN q[b], bit for bit: it is mkh_solve_trajectory's
+ * trajectory.  The problem needs max_batch >= B·S.
+ *
+ * Tracking.  Every candidate follows the T waypoints of its instance exactly as mkh_solve_trajectory does on B·S instances
+ * whose targets are those of instance b repeated S times: the same loops with the same flags (MKH_FLAG_WARM_START included),
+ * the same target layouts, posture_per_waypoint, com_per_waypoint and time_major.  The repetition happens on the device:
+ * waypoint t's (B, .) slab of a target group is fanned out into ONE (B·S, .) slab per group in front of waypoint t's loop,
+ * reused by every waypoint (the target workspace does not grow with T).  A batched target that is held is fanned out once; a
+ * target without a B axis is read where it is and launches nothing.  Threshold mode only: both thresholds >= 0, n_steps is
+ * max_iters per waypoint (a fixed count leaves nothing to score: MKH_E_INVALID).  At least one frame task; no dense rows.
+ *
+ * Score, per candidate.  Waypoint t is TRACKED when converged[t] != 0 && (status[t] & ~MKH_ST_OUTSIDE_LIMITS) == 0.
+ *   n_tracked = the number of tracked waypoints
+ *   length    = sum over t = 0 .. T-1, in ascending t, of d(q_t, q_{t-1}), d(a, b) = sum_k w_k ((a (-) b)_k)^2 — multi-start's
+ *               distance: (-) = mj_differentiatePos at dt = 1, w = io->weights or ones.  The weights
+ *               must be >= 0 (a length is a sum of non-negative terms; one that comes out negative ranks last, like NaN).  Each d is computed as multi-start's
+ *               selection computes it and added to the running sum, which starts at 0, by one rounded addition — never fused
+ *               into the products inside d.  q_{-1} IS THE CALLER'S q[b] FOR EVERY CANDIDATE, not the seed: the jump from the
+ *               current posture to the seed's first solution is part of what the robot pays.
+ * Selection, per instance: (1) the largest n_tracked; (2) among those the smallest length, a length that is NaN or infinite
+ * ranking behind every finite one; (3) among those the lowest s.  Nothing is discarded: a candidate that lost a waypoint can
+ * win when none tracked more.  If no candidate tracked any waypoint, candidate 0 wins — mkh_solve_trajectory's result — and
+ * n_tracked = 0.
+ *
+ * Outputs.  q_traj, v_traj, status, iters, converged: the chosen candidate's, in the call's layout ((B, T, .), or (T, B, .)
+ * with time_major), bitwise rows of the loops.  seed_index (B,) the chosen s; n_tracked (B,) its count; n_complete (B,) how
+ * many of the S candidates tracked all T waypoints; path_length (B,) its length.  qvel (optional, with waypoint_dt): the
+ * chosen trajectory's, by mkh_solve_trajectory's rule with q_{-1} = q.  seeds_out (B·S, nq): the starts.  q_all (T, B·S, nq),
+ * v_all (T, B·S, nv), status_all, iters_all, converged_all (T, B·S): every candidate's results, ALWAYS time-major whatever
+ * time_major says — the layout the loops run on.
+ *
+ * Workspace.  The loops' results live in a workspace of the handle of T·B·S·((nq + nv)·8 + 12) bytes (q, v and three int32
+ * per candidate and waypoint), grown on demand and kept; with MKH_FLAG_DEVICE_PTRS a given *_all array is written by the loops
+ * directly and takes no workspace for that array.  Beside it: the starts (B·S·nq·8 bytes, or the caller's seeds_out) and one
+ * (B·S, .) slab per fanned-out target group.  An allocation that fails: MKH_E_HIP, the message carries the size.
+ *
+ * n_seeds = 1 IS mkh_solve_trajectory: the same loop launches, bitwise the same outputs (seed_index = 0).  Pointers follow the
+ * call's convention (device pointers with MKH_FLAG_DEVICE_PTRS, else host: inputs staged once, outputs back once at the end);
+ * outputs must not alias inputs or each other.  Every argument error is reported before any device work; an error in
+ * mid-trajectory returns its code after the stream has drained.
+ */
+typedef struct MkhTrajectoryMultistartIO {
+  const double *seeds;      /* (B, S, nq) caller-defined starts, or NULL: drawn by multi-start's rule                        */
+  const double *weights;    /* (nv,) weights of the path length, each >= 0, or NULL: ones                                    */
+  double *q_traj;           /* (B, T, nq)  the chosen candidate's configurations                                   required  */
+  double *v_traj;           /* (B, T, nv)  its last velocities                                                     required  */
+  int32_t *status;          /* (B, T)      its MKH_ST_* bits                                                       required  */
+  int32_t *iters;           /* (B, T)      its iteration counts                                                    required  */
+  int32_t *converged;       /* (B, T)      its loops' converged flags                                              required  */
+  int32_t *seed_index;      /* (B,)        the chosen s                                                            required  */
+  int32_t *n_tracked;       /* (B,)        tracked waypoints of the chosen candidate                               required  */
+  int32_t *n_complete;      /* (B,)        candidates that tracked all T waypoints                                 required  */
+  double *path_length;      /* (B,)        length of the chosen candidate's path                                   required  */
+  double *qvel;             /* (B, T, nv)  optional: (q_t (-) q_{t-1}) / waypoint_dt of the chosen path, q_{-1} = q          */
+  double *seeds_out;        /* (B*S, nq)   optional: the starts the candidates ran from                                      */
+  double *q_all;            /* (T, B*S, nq) optional: every candidate's configurations, time-major                           */
+  double *v_all;            /* (T, B*S, nv) optional                                                                         */
+  int32_t *status_all;      /* (T, B*S)    optional                                                                          */
+  int32_t *iters_all;       /* (T, B*S)    optional                                                                          */
+  int32_t *converged_all;   /* (T, B*S)    optional                                                                          */
+  double waypoint_dt;       /* > 0 when qvel is given                                                                        */
+  int32_t posture_per_waypoint;   /* as MkhTrajectoryIO                                                                      */
+  int32_t com_per_waypoint;
+  int32_t time_major;       /* 1: every (B, T, .) array of the call, inputs included, is (T, B, .) instead (not the *_all)   */
+} MkhTrajectoryMultistartIO;
+int32_t mkh_solve_trajectory_multistart(MkhProblem *problem, int32_t B, int32_t T, int32_t n_seeds, const double *q,
+                                        const double *frame_targets, const double *posture_target, const double *com_target,
+                                        double dt, double damping, int32_t n_steps, double pos_threshold, double ori_threshold,
+                                        uint64_t rng_seed, int64_t target_index0, const MkhTrajectoryMultistartIO *io,
+                                        int32_t flags, void *hip_stream);
+
 /* Same inputs; additionally writes the requested intermediates (build_ik / compute_error /
  * compute_jacobian / get_transform_frame_to_world parity taps).  v_out/status_out may be NULL
  * to skip the QP. */

@@ -188,6 +188,40 @@ class KeyframesOut(NamedTuple):
     com_targets: object = None
 
 
+TRAJECTORY_MULTISTART_IO_FIELDS = ("seeds", "weights", "q_traj", "v_traj", "status", "iters", "converged", "seed_index", "n_tracked",
+                                   "n_complete", "path_length", "qvel", "seeds_out", "q_all", "v_all", "status_all", "iters_all",
+                                   "converged_all", "waypoint_dt", "posture_per_waypoint", "com_per_waypoint", "time_major")
+
+
+class MkhTrajectoryMultistartIO(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in TRAJECTORY_MULTISTART_IO_FIELDS[:18]] + [("waypoint_dt", C.c_double)] + \
+        [(n, C.c_int32) for n in TRAJECTORY_MULTISTART_IO_FIELDS[19:]]
+
+
+class TrajectoryMultistartOut(NamedTuple):
+    """What NativeProblem.solve_trajectory_multistart returns (arrays of the caller's kind: numpy or torch).  The chosen
+    candidate's trajectory `q`, `v`, `status`, `iters`, `converged` (B, T, ·) — (T, B, ·) with time_major; per instance (B,) the
+    chosen `seed_index`, its `n_tracked` waypoints, `n_complete` of the S candidates, its `path_length`; `qvel` unless qvel_dt
+    was not given.  With return_all every candidate's results, time-major whatever time_major says — `q_all` (T, B·S, nq),
+    `v_all` (T, B·S, nv), `status_all`, `iters_all`, `converged_all` (T, B·S) — and the `seeds` (B·S, nq); None otherwise."""
+    q: object
+    v: object
+    status: object
+    iters: object
+    converged: object
+    seed_index: object
+    n_tracked: object
+    n_complete: object
+    path_length: object
+    qvel: object = None
+    q_all: object = None
+    v_all: object = None
+    status_all: object = None
+    iters_all: object = None
+    converged_all: object = None
+    seeds: object = None
+
+
 def check_keyframe_times(key_times, waypoint_times):
     """The checks of include/minkhip.h "THE RULE" on the two time arrays, with no device in sight: float64 (K,) and (T,) arrays, or
     ValueError — key times strictly increasing, waypoint times non-decreasing and inside the keyframes' range, no NaN."""
@@ -273,6 +307,9 @@ def lib() -> C.CDLL:
     L.mkh_solve_keyframes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + common[2:6] + [C.c_void_p, C.c_void_p] + \
         common[6:8] + [C.c_int32, C.c_double, C.c_double, C.POINTER(MkhKeyframeIO), C.c_int32, C.c_void_p]
     L.mkh_solve_keyframes.restype = C.c_int32
+    L.mkh_solve_trajectory_multistart.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + common[2:8] + \
+        [C.c_int32, C.c_double, C.c_double, C.c_uint64, C.c_int64, C.POINTER(MkhTrajectoryMultistartIO), C.c_int32, C.c_void_p]
+    L.mkh_solve_trajectory_multistart.restype = C.c_int32
     L.mkh_solve_dense.argtypes = common[:6] + [C.POINTER(MkhDenseRows), C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                                C.POINTER(MkhTaps), C.c_int32, C.c_void_p]
     L.mkh_solve_dense.restype = C.c_int32
@@ -298,7 +335,7 @@ EXPORTED_SYMBOLS = (
     "mkh_problem_num_collision_pairs", "mkh_solve", "mkh_eval", "mkh_integrate", "mkh_problem_launch_info",
     "mkh_solve_steps", "mkh_problem_last_kernel", "mkh_lie_eval", "mkh_solve_dense", "mkh_solve_until",
     "mkh_geom_distance_eval", "mkh_problem_create_diag", "mkh_solve_multistart",
-    "mkh_solve_trajectory", "mkh_solve_keyframes",
+    "mkh_solve_trajectory", "mkh_solve_keyframes", "mkh_solve_trajectory_multistart",
 )
 
 LIE_OPS = {"se3_log": (0, 7, 0, (6,)), "se3_jlog": (1, 7, 0, (6, 6)), "se3_ljacinv": (2, 6, 0, (6, 6)),
@@ -815,8 +852,26 @@ class NativeProblem:
                                           bool(time_major), warm_start, wave_kernel, lane_kernel, quad_kernel,
                                           keys=(kt, wt, bool(return_targets)))
 
+    def solve_trajectory_multistart(self, q, frame_targets=None, posture_target=None, com_target=None, dt: float = 1e-2,
+                                    damping: float = 1e-12, *, n_seeds: int, n_steps: int, pos_threshold: float,
+                                    ori_threshold: float, rng_seed: int = 0, target_index0: int = 0, seeds=None, weights=None,
+                                    qvel_dt: Optional[float] = None, time_major: bool = False, warm_start: bool = False,
+                                    return_all: bool = False, wave_kernel: bool = False, lane_kernel: bool = False,
+                                    quad_kernel: bool = False) -> TrajectoryMultistartOut:
+        """mkh_solve_trajectory_multistart: solve_trajectory's threshold-terminated loops from `n_seeds` candidate starts per row
+        of q (candidate 0 = the row itself, the others drawn on the device as in solve_multistart or taken from `seeds`
+        (B, S, nq)); per row the candidate that tracked the most waypoints, then the one with the shortest path from q
+        (Σ_t Σ_k weights_k·(q_t ⊖ q_{t−1})_k²), is picked and gathered on the device (the rule: include/minkhip.h).  Targets
+        and time_major as in solve_trajectory.  numpy in → numpy out (synchronous); torch CUDA tensors in → torch tensors out,
+        asynchronous on the current stream, no host copy.  The handle needs max_batch >= B·n_seeds."""
+        with self._lock:
+            return self._solve_trajectory(q, frame_targets, posture_target, com_target, dt, damping, int(n_steps),
+                                          (float(pos_threshold), float(ori_threshold)), qvel_dt, bool(time_major), warm_start,
+                                          wave_kernel, lane_kernel, quad_kernel,
+                                          cands=(int(n_seeds), int(rng_seed), int(target_index0), seeds, weights, bool(return_all)))
+
     def _solve_trajectory(self, q, frame_targets, posture_target, com_target, dt, damping, n_steps, until, qvel_dt, tm,
-                          warm_start, wave_kernel, lane_kernel, quad_kernel, keys=None):
+                          warm_start, wave_kernel, lane_kernel, quad_kernel, keys=None, cands=None):
         m = self.nmodel.model
         use_torch = _is_torch(q)
         B = int(q.shape[0])
@@ -824,6 +879,13 @@ class NativeProblem:
             raise ValueError("n_steps must be >= 1")
         if qvel_dt is not None and not float(qvel_dt) > 0.0:
             raise ValueError("qvel_dt must be > 0")
+        if cands is not None:
+            if cands[0] < 1:
+                raise ValueError("n_seeds must be >= 1")
+            if not (until[0] >= 0.0 and until[1] >= 0.0):
+                raise ValueError("thresholds must be >= 0: multi-start trajectories run in threshold mode only")
+            if B * cands[0] > self.max_batch:
+                raise MinkHipError(f"B*n_seeds={B * cands[0]} exceeds max_batch={self.max_batch} of this problem")
         if B > self.max_batch:
             raise MinkHipError(f"B={B} exceeds max_batch={self.max_batch} of this problem")
         if self.n_dense_rows or self.n_dense_limit_rows or self.dense_limit_box:
@@ -912,6 +974,33 @@ class NativeProblem:
         io.waypoint_dt = float(qvel_dt) if qvel_dt is not None else 0.0
         io.posture_per_waypoint, io.com_per_waypoint, io.time_major = p_time, c_time, int(tm)
         thr = (float(until[0]), float(until[1])) if until is not None else (-1.0, -1.0)
+        if cands is not None:
+            S, rng_seed, target_index0, seeds, weights, want_all = cands
+            seeds, weights = prep(seeds), prep(weights)
+            if seeds is not None and tuple(seeds.shape) != (B, S, m.nq):
+                raise ValueError(f"seeds must have shape ({B}, {S}, {m.nq}), got {tuple(seeds.shape)}")
+            if weights is not None and tuple(weights.shape) != (m.nv,):
+                raise ValueError(f"weights must have shape ({m.nv},), got {tuple(weights.shape)}")
+            R = B * S
+            per = {"seed_index": empty((B,), i4), "n_tracked": empty((B,), i4), "n_complete": empty((B,), i4),
+                   "path_length": empty((B,), f8)}
+            every = {}
+            if want_all:
+                every = {"q_all": empty((T, R, m.nq), f8), "v_all": empty((T, R, m.nv), f8), "status_all": empty((T, R), i4),
+                         "iters_all": empty((T, R), i4), "converged_all": empty((T, R), i4), "seeds_out": empty((R, m.nq), f8)}
+            cio = MkhTrajectoryMultistartIO()
+            for n in TRAJECTORY_IO_FIELDS:                             # the chosen outputs, waypoint_dt and the layout: as set above
+                setattr(cio, n, getattr(io, n))
+            cio.seeds, cio.weights = ptr(seeds), ptr(weights)
+            for n, x in {**per, **every}.items():
+                setattr(cio, n, ptr(x))
+            _check(lib().mkh_solve_trajectory_multistart(self.handle, B, T, S, ptr(q), ptr(frame_targets), ptr(posture_target),
+                                                         ptr(com_target), float(dt), float(damping), n_steps, thr[0], thr[1],
+                                                         rng_seed & (2 ** 64 - 1), target_index0, C.byref(cio), flags, stream))
+            return TrajectoryMultistartOut(out_q, out_v, out_st, out_it, out_cv, per["seed_index"], per["n_tracked"],
+                                           per["n_complete"], per["path_length"], out_qvel,
+                                           *[every.get(n) for n in ("q_all", "v_all", "status_all", "iters_all", "converged_all",
+                                                                    "seeds_out")])
         if keys is not None:
             kt, wt, want = keys
             out_ft = out_pt = out_ct = None

@@ -219,6 +219,12 @@ struct MkhProblem {
   // mkh_solve_keyframes: ONE (B, .) slab per target group, rewritten in front of every waypoint's loop, and the staging of
   // the interpolated targets a host-pointer call asked for (the only buffers of the call's targets that grow with T)
   GrowBuf kf_ft, kf_pt, kf_ct, kf_out_ft, kf_out_pt, kf_out_ct;
+  // mkh_solve_trajectory_multistart: the candidates' starts, ONE (B·S, .) slab per fanned-out target group, the loops'
+  // time-major results of the B·S candidates (the workspace whose size the header states; one buffer per array, so that a
+  // caller's *_all array replaces its own), and the staging of host-pointer calls (tms_out_i32: seed_index | n_tracked |
+  // n_complete)
+  GrowBuf tms_seeds, tms_ft, tms_pt, tms_ct, tms_q, tms_v, tms_st, tms_it, tms_cv;
+  GrowBuf tms_in_seeds, tms_in_w, tms_out_i32, tms_out_len;
 };
 
 // The wavefront kernel's variants live in their own translation units (mink_amd/csrc/build.py generates one variant_<name>.hip
@@ -253,6 +259,15 @@ hipError_t launch_kf_posture(hipStream_t stream, const int32_t* jnt, int njnt, c
                              int k, double u, int rows, int n_posture, int nq, double* slab, double* out, long long o_sb);
 hipError_t launch_kf_com(hipStream_t stream, const double* keys, long long s_b, long long s_k, int k, double u, int rows,
                          int width, double* slab, double* out, long long o_sb);
+// multi-start trajectory IK (trajectory_multistart.hip): every candidate scored over its path and one chosen per instance, the
+// chosen candidate's rows of the time-major (T, B·S, .) results gathered through the (instance, waypoint) strides of `out`
+hipError_t launch_tms_score(hipStream_t stream, int B, int S, int T, int nq, int njnt, const int32_t* jnt, const double* q0,
+                            const double* q_all, const int32_t* status_all, const int32_t* converged_all, const double* weights,
+                            int32_t* seed_index, int32_t* n_tracked, int32_t* n_complete, double* path_length);
+hipError_t launch_tms_gather(hipStream_t stream, const double* all, double* out, const int32_t* seed_index, int B, int S, int T,
+                             int W, long long o_sb, long long o_st);
+hipError_t launch_tms_gather_i32(hipStream_t stream, const int32_t* all, int32_t* out, const int32_t* seed_index, int B, int S,
+                                 int T, long long o_sb, long long o_st);
 constexpr int kLaneMinBatchLoop = 28672;  // fused loops of a small arm: row kernel below, lane kernel from here (M targets/s at 16 384: 39.7 vs 24.1, at 32 768: 42.4 vs 48.2)
 constexpr int kLaneMinBatch = 73728;  // plain solves of a small arm: row kernel below, lane kernel from here (plan_launch())
 }
@@ -1495,7 +1510,9 @@ void mkh_problem_destroy(MkhProblem* p) {
                      &p->ms_i32, &p->ms_in_q, &p->ms_in_ft, &p->ms_in_pt, &p->ms_in_ct, &p->ms_in_ref, &p->ms_in_w, &p->ms_out_q,
                      &p->ms_out_v, &p->ms_out_i32, &p->tj_ft, &p->tj_pt, &p->tj_ct, &p->tj_q, &p->tj_v, &p->tj_i32, &p->tj_in_q,
                      &p->tj_in_ft, &p->tj_in_pt, &p->tj_in_ct, &p->tj_out_q, &p->tj_out_v, &p->tj_out_i32, &p->tj_out_qvel, &p->kf_ft,
-                     &p->kf_pt, &p->kf_ct, &p->kf_out_ft, &p->kf_out_pt, &p->kf_out_ct})
+                     &p->kf_pt, &p->kf_ct, &p->kf_out_ft, &p->kf_out_pt, &p->kf_out_ct, &p->tms_seeds, &p->tms_ft, &p->tms_pt, &p->tms_ct,
+                     &p->tms_q, &p->tms_v, &p->tms_st, &p->tms_it, &p->tms_cv, &p->tms_in_seeds, &p->tms_in_w, &p->tms_out_i32,
+                     &p->tms_out_len})
     g->release();
   p->small.release();
   if (p->st_in) (void)hipStreamDestroy(p->st_in);
@@ -2399,22 +2416,44 @@ static int32_t kf_segments(KeyframeSpec* kf, int32_t T) {
   return MKH_OK;
 }
 
-// mkh_solve_trajectory and, with `kf`, mkh_solve_keyframes: the T stream-ordered loop launches between slabs of time-major
-// buffers and everything around them.  `who` names the entry point in messages.
+// What mkh_solve_trajectory_multistart adds to a trajectory call: the loops run on B·S candidate rows — instance b's targets
+// fanned out S times in front of every waypoint's loop, the starts drawn by multi-start's seed kernel — into time-major
+// (T, B·S, .) results of their own, and the call's (B, T, .) outputs are the rows of one candidate per instance, chosen by the
+// score over the whole path (trajectory_multistart.hip).
+struct CandidateSpec {
+  int32_t S;
+  uint64_t rng_seed;
+  int64_t target_index0;
+  const double *seeds, *weights;                           // optional inputs: (B, S, nq) starts, (nv,) weights of the length
+  int32_t *seed_index, *n_tracked, *n_complete;            // (B,) required
+  double* path_length;                                     // (B,) required
+  double *seeds_out, *q_all, *v_all;                       // optional: (B·S, nq), (T, B·S, nq), (T, B·S, nv)
+  int32_t *status_all, *iters_all, *converged_all;         // optional: (T, B·S)
+};
+
+// mkh_solve_trajectory and, with `kf`, mkh_solve_keyframes, or, with `cs`, mkh_solve_trajectory_multistart: the T
+// stream-ordered loop launches between slabs of time-major buffers and everything around them.  `who` names the entry point
+// in messages.
 static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double* q, const double* frame_targets,
                                const double* posture_target, const double* com_target, double dt, double damping,
                                int32_t n_steps, double pos_threshold, double ori_threshold, const MkhTrajectoryIO* io,
-                               int32_t flags, void* hip_stream, KeyframeSpec* kf, const char* who) {
+                               int32_t flags, void* hip_stream, KeyframeSpec* kf, const CandidateSpec* cs, const char* who) {
   // (what can be judged from the arguments alone comes first: it needs neither a handle nor a device)
   if (B < 1) return fail(MKH_E_INVALID, "B must be >= 1");
   if (T < 1) return fail(MKH_E_INVALID, "T must be >= 1");
   if (n_steps < 1) return fail(MKH_E_INVALID, "n_steps must be >= 1");
+  if (cs && cs->S < 1) return fail(MKH_E_INVALID, "n_seeds must be >= 1");
+  if (cs && cs->target_index0 < 0) return fail(MKH_E_INVALID, "target_index0 must be >= 0");
   if (!(dt > 0.0)) return fail(MKH_E_INVALID, "dt must be > 0");
   const bool until = pos_threshold >= 0.0 && ori_threshold >= 0.0;
   if (!until && !(pos_threshold < 0.0 && ori_threshold < 0.0))
     return fail(MKH_E_INVALID, "thresholds must both be >= 0 (threshold mode) or both be < 0 (fixed count)");
+  if (cs && !until)
+    return fail(MKH_E_INVALID, "%s runs in threshold mode only: a fixed count leaves nothing to score (both thresholds must be >= 0)", who);
   if (!io || !io->q_traj || !io->v_traj || !io->status)
     return fail(MKH_E_INVALID, "io and its outputs q_traj, v_traj, status are required");
+  if (cs && (!io->iters || !io->converged || !cs->seed_index || !cs->n_tracked || !cs->n_complete || !cs->path_length))
+    return fail(MKH_E_INVALID, "io's outputs iters, converged, seed_index, n_tracked, n_complete, path_length are required");
   if (!until && (io->iters || io->converged))
     return fail(MKH_E_INVALID, "iters / converged are outputs of threshold mode: they must be NULL with a fixed count");
   if (io->qvel && !(io->waypoint_dt > 0.0)) return fail(MKH_E_INVALID, "qvel needs waypoint_dt > 0");
@@ -2434,8 +2473,10 @@ static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double
   if (P.n_dense_rows || P.n_dense_limit_rows || P.dense_box)
     return fail(MKH_E_INVALID, "dense (plugin) rows are evaluated by the caller at q: no fused loop, no trajectory");
   if (B > p->max_batch) return fail(MKH_E_INVALID, "B=%d exceeds max_batch=%d of this problem", B, p->max_batch);
+  if (cs && (long long)B * cs->S > p->max_batch)
+    return fail(MKH_E_INVALID, "B * n_seeds = %lld exceeds max_batch=%d of this problem", (long long)B * cs->S, p->max_batch);
   HIP_OK(hipSetDevice(p->model->device));
-  if (io->qvel || (kf && io->posture_per_waypoint && P.n_posture > 0))
+  if (cs || io->qvel || (kf && io->posture_per_waypoint && P.n_posture > 0))
     if (const int32_t rc = ms_build_tables(p)) return rc;
   hipStream_t stream = (hipStream_t)hip_stream;
   const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0, tm = io->time_major != 0;
@@ -2444,6 +2485,8 @@ static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double
   const size_t Bz = B, Tz = T, N = Bz * Tz, nq = P.nq, nv = P.nv, f8 = sizeof(double), i4 = sizeof(int32_t);
   const size_t ft_w = (size_t)P.n_frame * 7, pt_w = (size_t)P.n_posture * nq, ct_w = (size_t)P.n_com * 3;
   const size_t Kz = kf ? (size_t)kf->K : Tz;                 // the length of the targets' time axis
+  const int S = cs ? cs->S : 1;
+  const size_t Rz = Bz * (size_t)S, NR = Tz * Rz;            // rows of a loop launch (the candidates, or the instances), of all T
   const size_t pt_n = pt_w * (pbat ? Bz : 1) * (ptime ? Kz : 1), ct_n = ct_w * (cbat ? Bz : 1) * (ctime ? Kz : 1);
 
   // ---- inputs and the caller-layout outputs on the device
@@ -2468,6 +2511,36 @@ static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double
     o_it = io->iters ? o_st + N : nullptr;
     o_cv = io->converged ? o_st + 2 * N : nullptr;
   }
+  // ---- candidates: optional inputs and the per-instance outputs on the device
+  const double *d_user = nullptr, *d_w = nullptr;
+  int32_t *o_si = nullptr, *o_nt = nullptr, *o_nc = nullptr;
+  double* o_len = nullptr;
+  // a buffer of the candidates: a failed allocation drains what the call has enqueued and reports the size
+  auto tms_alloc = [&](GrowBuf& g, size_t bytes) -> bool {
+    if (g.need(bytes) == hipSuccess) return true;
+    (void)hipStreamSynchronize(stream);
+    (void)fail(MKH_E_HIP, "%s: no device memory for a buffer of %zu bytes (the candidates' results take T*B*S*((nq+nv)*8+12) = %zu bytes)",
+               who, bytes, NR * ((nq + nv) * f8 + 3 * i4));
+    return false;
+  };
+  if (cs) {
+    d_user = cs->seeds; d_w = cs->weights;
+    o_si = cs->seed_index; o_nt = cs->n_tracked; o_nc = cs->n_complete; o_len = cs->path_length;
+    if (!devp) {
+      if (cs->seeds) {
+        if (!tms_alloc(p->tms_in_seeds, Rz * nq * f8)) return MKH_E_HIP;
+        HIP_OK(hipMemcpyAsync(p->tms_in_seeds.p, cs->seeds, Rz * nq * f8, hipMemcpyHostToDevice, stream));
+        d_user = p->tms_in_seeds.f64();
+      }
+      if (cs->weights) {
+        if (!tms_alloc(p->tms_in_w, nv * f8)) return MKH_E_HIP;
+        HIP_OK(hipMemcpyAsync(p->tms_in_w.p, cs->weights, nv * f8, hipMemcpyHostToDevice, stream));
+        d_w = p->tms_in_w.f64();
+      }
+      if (!tms_alloc(p->tms_out_i32, 3 * Bz * i4) || !tms_alloc(p->tms_out_len, Bz * f8)) return MKH_E_HIP;
+      o_si = p->tms_out_i32.i32(); o_nt = o_si + Bz; o_nc = o_si + 2 * Bz; o_len = p->tms_out_len.f64();
+    }
+  }
   // ---- keyframes: one slab per target group for all waypoints; the interpolated targets, where asked for, in the caller's layout
   double *k_ft_out = nullptr, *k_pt_out = nullptr, *k_ct_out = nullptr;
   const size_t pt_rows = pbat ? Bz : 1, ct_rows = cbat ? Bz : 1;
@@ -2484,9 +2557,28 @@ static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double
   }
   // ---- what the loops read and write: time-major slabs.  A time-major call: the caller's own arrays; a batch-major call:
   //      transposed copies of the targets and a workspace for the results
+  //      Candidates: the loops' results are (T, B·S, .) arrays of their own — the caller's *_all where they are device
+  //      buffers, else the handle's workspace —, the starts sit beside them
   double *l_q = o_q, *l_v = o_v;
   int32_t *l_st = o_st, *l_it = o_it, *l_cv = o_cv;
-  if (!tm) {
+  double* d_seeds = nullptr;
+  if (cs) {
+    auto ws = [&](GrowBuf& g, size_t bytes, void* given) -> void* {
+      if (devp && given) return given;
+      return tms_alloc(g, bytes) ? g.p : nullptr;
+    };
+    if (!(l_q = (double*)ws(p->tms_q, NR * nq * f8, cs->q_all))) return MKH_E_HIP;
+    if (!(l_v = (double*)ws(p->tms_v, NR * nv * f8, cs->v_all))) return MKH_E_HIP;
+    if (!(l_st = (int32_t*)ws(p->tms_st, NR * i4, cs->status_all))) return MKH_E_HIP;
+    if (!(l_it = (int32_t*)ws(p->tms_it, NR * i4, cs->iters_all))) return MKH_E_HIP;
+    if (!(l_cv = (int32_t*)ws(p->tms_cv, NR * i4, cs->converged_all))) return MKH_E_HIP;
+    if (!(d_seeds = (double*)ws(p->tms_seeds, Rz * nq * f8, cs->seeds_out))) return MKH_E_HIP;
+    if (S > 1) {
+      if (ft_w && !tms_alloc(p->tms_ft, Rz * ft_w * f8)) return MKH_E_HIP;
+      if (pt_w && pbat && !tms_alloc(p->tms_pt, Rz * pt_w * f8)) return MKH_E_HIP;
+      if (ct_w && cbat && !tms_alloc(p->tms_ct, Rz * ct_w * f8)) return MKH_E_HIP;
+    }
+  } else if (!tm) {
     HIP_OK(p->tj_q.need(N * nq * f8));
     HIP_OK(p->tj_v.need(N * nv * f8));
     HIP_OK(p->tj_i32.need(3 * N * i4));
@@ -2494,6 +2586,8 @@ static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double
     l_st = p->tj_i32.i32();
     l_it = o_it ? l_st + N : nullptr;
     l_cv = o_cv ? l_st + 2 * N : nullptr;
+  }
+  if (!tm) {
     if (ft_w && !kf) {                // (keyframes are read in place through strides: no transposed copy)
       HIP_OK(p->tj_ft.need(N * ft_w * f8));
       HIP_OK(launch_tj_gather(stream, d_ft, p->tj_ft.f64(), B, T, (int)ft_w));
@@ -2520,8 +2614,22 @@ static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double
   auto key_sk = [&](size_t rows, size_t w) { return (long long)(tm ? rows * w : w); };
   auto out_sb = [&](size_t rows, size_t w) { return (long long)(rows == 1 ? 0 : (tm ? w : Tz * w)); };
   auto out_st = [&](size_t rows, size_t w) { return tm ? rows * w : w; };
+  if (cs) {
+    // the starts (candidate 0: q[b] itself), and a batched target that is held: fanned out once, in front of waypoint 0
+    hipError_t ce = launch_ms_seed(stream, p->ms_seed_i.i32(), p->ms_seed_f.f64(), B, S, (int)nq, d_q, d_user,
+                                   (unsigned long long)cs->rng_seed, (long long)cs->target_index0, d_seeds);
+    if (ce == hipSuccess && S > 1 && pt_w && pbat && !ptime) {
+      ce = launch_ms_fanout(stream, d_pt, p->tms_pt.f64(), B, S, (int)pt_w);
+      d_pt = p->tms_pt.f64();
+    }
+    if (ce == hipSuccess && S > 1 && ct_w && cbat && !ctime) {
+      ce = launch_ms_fanout(stream, d_ct, p->tms_ct.f64(), B, S, (int)ct_w);
+      d_ct = p->tms_ct.f64();
+    }
+    if (ce != hipSuccess) { (void)hipStreamSynchronize(stream); return fail(MKH_E_HIP, "%s: %s", who, hipGetErrorString(ce)); }
+  }
   for (size_t t = 0; t < Tz && rc == MKH_OK; ++t) {
-    const double* const q_in = t ? l_q + (t - 1) * Bz * nq : d_q;
+    const double* const q_in = t ? l_q + (t - 1) * Rz * nq : (cs ? d_seeds : d_q);
     const double *t_ft = nullptr, *t_pt = d_pt, *t_ct = d_ct;       // (held targets: the same array for every waypoint)
     if (!kf) {
       t_ft = d_ft ? d_ft + t * Bz * ft_w : nullptr;
@@ -2551,23 +2659,51 @@ static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double
       }
       if (ke != hipSuccess) { rc = fail(MKH_E_HIP, "%s: %s", who, hipGetErrorString(ke)); break; }
     }
-    rc = run(p, B, q_in, t_ft, t_pt, t_ct, dt, damping, l_v + t * Bz * nv, l_st + t * Bz, nullptr, loop_flags, hip_stream,
-             n_steps, l_q + t * Bz * nq, nullptr, until ? pos_threshold : -1.0, until ? ori_threshold : -1.0,
-             l_it ? l_it + t * Bz : nullptr, l_cv ? l_cv + t * Bz : nullptr);
+    if (cs && S > 1) {
+      // waypoint t's (B, .) slabs repeated for the S candidates of every instance, into the ONE (B·S, .) slab of each group
+      hipError_t fe = hipSuccess;
+      if (ft_w) { fe = launch_ms_fanout(stream, t_ft, p->tms_ft.f64(), B, S, (int)ft_w); t_ft = p->tms_ft.f64(); }
+      if (ptime && pbat) {
+        if (fe == hipSuccess) fe = launch_ms_fanout(stream, t_pt, p->tms_pt.f64(), B, S, (int)pt_w);
+        t_pt = p->tms_pt.f64();
+      }
+      if (ctime && cbat) {
+        if (fe == hipSuccess) fe = launch_ms_fanout(stream, t_ct, p->tms_ct.f64(), B, S, (int)ct_w);
+        t_ct = p->tms_ct.f64();
+      }
+      if (fe != hipSuccess) { rc = fail(MKH_E_HIP, "%s: %s", who, hipGetErrorString(fe)); break; }
+    }
+    rc = run(p, (int32_t)Rz, q_in, t_ft, t_pt, t_ct, dt, damping, l_v + t * Rz * nv, l_st + t * Rz, nullptr, loop_flags, hip_stream,
+             n_steps, l_q + t * Rz * nq, nullptr, until ? pos_threshold : -1.0, until ? ori_threshold : -1.0,
+             l_it ? l_it + t * Rz : nullptr, l_cv ? l_cv + t * Rz : nullptr);
   }
   if (rc != MKH_OK) {
     (void)hipStreamSynchronize(stream);                       // (a failed call still drains what it started)
     return rc;
   }
   hipError_t e = hipSuccess;
-  if (!tm) {
+  if (cs) {
+    // the score over every candidate's path and the choice, then the chosen rows into the caller's layout: (instance,
+    // waypoint) strides in elements of an output of width w
+    auto sb = [&](size_t w) { return (long long)(tm ? w : Tz * w); };
+    auto st = [&](size_t w) { return (long long)(tm ? Bz * w : w); };
+    e = launch_tms_score(stream, B, S, T, (int)nq, p->model->njnt, p->ms_jnt.i32(), d_q, l_q, l_st, l_cv, d_w, o_si, o_nt, o_nc, o_len);
+    if (e == hipSuccess) e = launch_tms_gather(stream, l_q, o_q, o_si, B, S, T, (int)nq, sb(nq), st(nq));
+    if (e == hipSuccess) e = launch_tms_gather(stream, l_v, o_v, o_si, B, S, T, (int)nv, sb(nv), st(nv));
+    if (e == hipSuccess) e = launch_tms_gather_i32(stream, l_st, o_st, o_si, B, S, T, sb(1), st(1));
+    if (e == hipSuccess) e = launch_tms_gather_i32(stream, l_it, o_it, o_si, B, S, T, sb(1), st(1));
+    if (e == hipSuccess) e = launch_tms_gather_i32(stream, l_cv, o_cv, o_si, B, S, T, sb(1), st(1));
+    if (e == hipSuccess && o_qvel)
+      e = launch_tj_qvel(stream, p->ms_jnt.i32(), p->model->njnt, B, T, (int)nq, d_q, o_q, sb(nq), st(nq), io->waypoint_dt, o_qvel,
+                         sb(nv), st(nv), tm ? 1 : 0);
+  } else if (!tm) {
     e = launch_tj_scatter(stream, l_q, o_q, B, T, (int)nq);
     if (e == hipSuccess) e = launch_tj_scatter(stream, l_v, o_v, B, T, (int)nv);
     if (e == hipSuccess) e = launch_tj_scatter_i32(stream, l_st, o_st, B, T);
     if (e == hipSuccess && o_it) e = launch_tj_scatter_i32(stream, l_it, o_it, B, T);
     if (e == hipSuccess && o_cv) e = launch_tj_scatter_i32(stream, l_cv, o_cv, B, T);
   }
-  if (e == hipSuccess && o_qvel) {
+  if (e == hipSuccess && o_qvel && !cs) {
     // (instance, waypoint) strides in elements: the loops' time-major q, the caller's layout for qvel
     const long long v_sb = tm ? (long long)nv : (long long)(Tz * nv), v_st = tm ? (long long)(Bz * nv) : (long long)nv;
     e = launch_tj_qvel(stream, p->ms_jnt.i32(), p->model->njnt, B, T, (int)nq, d_q, l_q, (long long)nq, (long long)(Bz * nq),
@@ -2591,6 +2727,18 @@ static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double
     if (e == hipSuccess) e = down(kf->pt_out, k_pt_out, Tz * pt_rows * pt_w * f8);
     if (e == hipSuccess) e = down(kf->ct_out, k_ct_out, Tz * ct_rows * ct_w * f8);
   }
+  if (cs) {
+    if (e == hipSuccess) e = down(cs->seed_index, o_si, Bz * i4);
+    if (e == hipSuccess) e = down(cs->n_tracked, o_nt, Bz * i4);
+    if (e == hipSuccess) e = down(cs->n_complete, o_nc, Bz * i4);
+    if (e == hipSuccess) e = down(cs->path_length, o_len, Bz * f8);
+    if (e == hipSuccess) e = down(cs->seeds_out, d_seeds, Rz * nq * f8);
+    if (e == hipSuccess) e = down(cs->q_all, l_q, NR * nq * f8);
+    if (e == hipSuccess) e = down(cs->v_all, l_v, NR * nv * f8);
+    if (e == hipSuccess) e = down(cs->status_all, l_st, NR * i4);
+    if (e == hipSuccess) e = down(cs->iters_all, l_it, NR * i4);
+    if (e == hipSuccess) e = down(cs->converged_all, l_cv, NR * i4);
+  }
   const hipError_t e2 = hipStreamSynchronize(stream);         // (a failed call still drains what it started)
   if (e == hipSuccess) e = e2;
   if (e != hipSuccess) return fail(MKH_E_HIP, "%s: %s", who, hipGetErrorString(e));
@@ -2604,7 +2752,7 @@ int32_t mkh_solve_trajectory(MkhProblem* p, int32_t B, int32_t T, const double* 
                              int32_t n_steps, double pos_threshold, double ori_threshold, const MkhTrajectoryIO* io,
                              int32_t flags, void* hip_stream) {
   return trajectory_core(p, B, T, q, frame_targets, posture_target, com_target, dt, damping, n_steps, pos_threshold,
-                         ori_threshold, io, flags, hip_stream, nullptr, "mkh_solve_trajectory");
+                         ori_threshold, io, flags, hip_stream, nullptr, nullptr, "mkh_solve_trajectory");
 }
 
 int32_t mkh_solve_keyframes(MkhProblem* p, int32_t B, int32_t K, int32_t T, const double* q, const double* frame_keys,
@@ -2623,7 +2771,29 @@ int32_t mkh_solve_keyframes(MkhProblem* p, int32_t B, int32_t K, int32_t T, cons
     kf.ft_out = io->frame_targets_out; kf.pt_out = io->posture_targets_out; kf.ct_out = io->com_targets_out;
   }
   return trajectory_core(p, B, T, q, frame_keys, posture_keys, com_keys, dt, damping, n_steps, pos_threshold, ori_threshold,
-                         io ? &tio : nullptr, flags, hip_stream, &kf, "mkh_solve_keyframes");
+                         io ? &tio : nullptr, flags, hip_stream, &kf, nullptr, "mkh_solve_keyframes");
+}
+
+int32_t mkh_solve_trajectory_multistart(MkhProblem* p, int32_t B, int32_t T, int32_t n_seeds, const double* q,
+                                        const double* frame_targets, const double* posture_target, const double* com_target,
+                                        double dt, double damping, int32_t n_steps, double pos_threshold, double ori_threshold,
+                                        uint64_t rng_seed, int64_t target_index0, const MkhTrajectoryMultistartIO* io,
+                                        int32_t flags, void* hip_stream) {
+  // the trajectory call's view of the struct: the chosen candidate's outputs; everything about the candidates beside it
+  MkhTrajectoryIO tio;
+  CandidateSpec cs{};
+  cs.S = n_seeds; cs.rng_seed = rng_seed; cs.target_index0 = target_index0;
+  if (io) {
+    tio.q_traj = io->q_traj; tio.v_traj = io->v_traj; tio.status = io->status; tio.iters = io->iters;
+    tio.converged = io->converged; tio.qvel = io->qvel; tio.waypoint_dt = io->waypoint_dt;
+    tio.posture_per_waypoint = io->posture_per_waypoint; tio.com_per_waypoint = io->com_per_waypoint; tio.time_major = io->time_major;
+    cs.seeds = io->seeds; cs.weights = io->weights;
+    cs.seed_index = io->seed_index; cs.n_tracked = io->n_tracked; cs.n_complete = io->n_complete; cs.path_length = io->path_length;
+    cs.seeds_out = io->seeds_out; cs.q_all = io->q_all; cs.v_all = io->v_all;
+    cs.status_all = io->status_all; cs.iters_all = io->iters_all; cs.converged_all = io->converged_all;
+  }
+  return trajectory_core(p, B, T, q, frame_targets, posture_target, com_target, dt, damping, n_steps, pos_threshold, ori_threshold,
+                         io ? &tio : nullptr, flags, hip_stream, nullptr, &cs, "mkh_solve_trajectory_multistart");
 }
 
 int32_t mkh_integrate(MkhModel* m, int32_t B, const double* q, const double* v, double dt, double* q_out,

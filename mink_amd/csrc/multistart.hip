@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "lie_dev.h"
+#include "ms_distance.h"
 #include "wave_ops.h"
 
 namespace mkh {
@@ -17,7 +18,6 @@ enum : int32_t {
   MS_AROUND = 2,   // (q[b] − π) + 2π·u(draw): unlimited hinge
   MS_BALL = 3,     // one component of the quaternion of a random rotation vector; draws draw, draw + 1, draw + 2
 };
-enum : int32_t { MS_JNT_FREE = 0, MS_JNT_BALL = 1 };       // mjtJoint (2 / 3: slide / hinge)
 
 // The generator of include/minkhip.h "Random numbers": stateless, a function of (rng_seed, target, seed, draw) alone.
 __device__ __forceinline__ unsigned long long ms_mix(unsigned long long z) {
@@ -82,32 +82,6 @@ __global__ __launch_bounds__(256) void multistart_fanout_kernel(const double* __
   const long long i = e / width;
   const int k = (int)(e % width);
   dst[e] = src[(size_t)(i / S) * width + k];
-}
-
-// d = Σ_k w_k·(q ⊖ r)_k², ⊖ = mj_differentiatePos at dt = 1
-__device__ __forceinline__ double ms_distance(const int32_t* __restrict__ jnt, int njnt, const double* __restrict__ q,
-                                              const double* __restrict__ r, const double* __restrict__ w) {
-  double d = 0.0;
-  for (int j = 0; j < njnt; ++j) {
-    const int jt = jnt[3 * j];
-    int qa = jnt[3 * j + 1], va = jnt[3 * j + 2];
-    if (jt != MS_JNT_FREE && jt != MS_JNT_BALL) {
-      const double dv = q[qa] - r[qa];
-      d += (w ? w[va] : 1.0) * dv * dv;
-      continue;
-    }
-    if (jt == MS_JNT_FREE) {
-      for (int k = 0; k < 3; ++k) {
-        const double dv = q[qa + k] - r[qa + k];
-        d += (w ? w[va + k] : 1.0) * dv * dv;
-      }
-      qa += 3; va += 3;
-    }
-    // mju_subQuat: rotation vector of conj(r)·q
-    const V3 dw = quat2vel(qmul(qconj(Q4{r[qa], r[qa + 1], r[qa + 2], r[qa + 3]}), Q4{q[qa], q[qa + 1], q[qa + 2], q[qa + 3]}));
-    d += (w ? w[va] : 1.0) * dw.x * dw.x + (w ? w[va + 1] : 1.0) * dw.y * dw.y + (w ? w[va + 2] : 1.0) * dw.z * dw.z;
-  }
-  return d;
 }
 
 // One wavefront per target: lane l looks at seeds l, l + 64, ...; the wave agrees on the closest converged one.

@@ -449,22 +449,7 @@ def solve_ik_multistart(configuration: Configuration, tasks: Sequence, dt: float
                                        target_index0=lo, seeds=rows(seeds, 2, lo, hi), reference=rows(reference, 1, lo, hi),
                                        weights=weights, **kw)
 
-    parts = []
-    with _pin(configuration, layout):
-        # (a ShardedProblem cached by solve_ik_steps for the same tasks and batch size cannot serve: it splits rows without
-        #  telling a shard its global offset — every handle is then built here)
-        first = [prob] if isinstance(prob, nat.NativeProblem) else []
-        handles = first if (n_dev == 1 and first) else _multistart_shards(configuration, layout, first, devices[:n_dev], shard * S)
-        for c0 in range(0, B, chunk):
-            c1 = min(B, c0 + chunk)
-            bounds = [(c0 + lo, c0 + hi) for lo, hi in (shard_bounds(c1 - c0, n_dev, r) for r in range(n_dev))]
-            bounds = [(lo, hi) for lo, hi in bounds if hi > lo]
-            if len(bounds) == 1:
-                parts.append(job(handles[0], *bounds[0]))
-            else:
-                from concurrent.futures import ThreadPoolExecutor
-                with ThreadPoolExecutor(max_workers=len(bounds)) as pool:      # (a libminkhip call releases the GIL)
-                    parts += [f.result() for f in [pool.submit(job, h, lo, hi) for h, (lo, hi) in zip(handles, bounds)]]
+    parts = _chunks_and_shards(configuration, layout, prob, B, chunk, n_dev, shard * S, job)
     res = MultistartResult(*[None if parts[0][k] is None else np.concatenate([p[k] for p in parts], axis=0)
                              for k in range(len(MultistartResult._fields))])
     status = res.status
@@ -527,6 +512,26 @@ def _trajectory_targets(configuration: Configuration, tasks: Sequence, targets, 
         T = arr.shape[1]
         out[id(task)] = arr
     return out, T
+
+
+def _stacked_targets(configuration: Configuration, layout, seqs, L: int):
+    """(frame, posture, CoM) target arrays of a trajectory call from the sequences of _trajectory_targets: a group is per
+    waypoint — (B, L, n, w) — when any of its tasks has a sequence (frame targets: always), else as solve_ik_steps passes it."""
+    B = configuration.batch_size
+
+    def stack(group, w, timed=False):
+        if not group:
+            return None
+        held = [np.asarray(t._native_target(configuration)) if id(t) not in seqs else None for t in group]
+        if not timed and not any(id(t) in seqs for t in group):
+            if all(h.ndim == 1 for h in held):
+                return np.stack(held, axis=0)
+            return np.stack([np.broadcast_to(h, (B, w)) for h in held], axis=1)
+        rows = [seqs[id(t)] if h is None else np.broadcast_to(np.broadcast_to(h, (B, w))[:, None, :], (B, L, w))
+                for t, h in zip(group, held)]
+        return np.ascontiguousarray(np.stack(rows, axis=2))
+
+    return stack(layout["frame"], 7, timed=True), stack(layout["posture"], configuration.nq), stack(layout["com"], 3)
 
 
 def solve_ik_trajectory(configuration: Configuration, tasks: Sequence, dt: float, targets, n_steps: int = 1,
@@ -596,22 +601,7 @@ def solve_ik_trajectory(configuration: Configuration, tasks: Sequence, dt: float
         raise exceptions.TaskDefinitionError(
             "solve_ik_trajectory fuses the outer loop on the device; caller-defined Task / Limit subclasses are evaluated on "
             "the host at every step: call solve_ik + integrate_inplace in a loop instead")
-
-    def stack(group, w, timed=False):
-        """Targets of one task group: per waypoint (B, T, n, w) when any of its tasks has a sequence (frame targets: always),
-        else as solve_ik_steps passes them."""
-        if not group:
-            return None
-        held = [np.asarray(t._native_target(configuration)) if id(t) not in seqs else None for t in group]
-        if not timed and not any(id(t) in seqs for t in group):
-            if all(h.ndim == 1 for h in held):
-                return np.stack(held, axis=0)
-            return np.stack([np.broadcast_to(h, (B, w)) for h in held], axis=1)
-        rows = [seqs[id(t)] if h is None else np.broadcast_to(np.broadcast_to(h, (B, w))[:, None, :], (B, L, w))
-                for t, h in zip(group, held)]
-        return np.ascontiguousarray(np.stack(rows, axis=2))
-
-    ft, pt, ct = stack(layout["frame"], 7, timed=True), stack(layout["posture"], configuration.nq), stack(layout["com"], 3)
+    ft, pt, ct = _stacked_targets(configuration, layout, seqs, L)
     q = configuration.q_batch
 
     def rows(x, held_ndim, lo, hi):
@@ -624,20 +614,7 @@ def solve_ik_trajectory(configuration: Configuration, tasks: Sequence, dt: float
         return handle.solve_keyframes(q[lo:hi], kt, wt, rows(ft, 0, lo, hi), rows(pt, 2, lo, hi), rows(ct, 2, lo, hi), dt, damping,
                                       return_targets=bool(return_targets), **kw)
 
-    parts = []
-    with _pin(configuration, layout):
-        first = [prob] if isinstance(prob, nat.NativeProblem) else []
-        handles = first if (n_dev == 1 and first) else _multistart_shards(configuration, layout, first, devices[:n_dev], shard)
-        for c0 in range(0, B, chunk):
-            c1 = min(B, c0 + chunk)
-            bounds = [(c0 + lo, c0 + hi) for lo, hi in (shard_bounds(c1 - c0, n_dev, r) for r in range(n_dev))]
-            bounds = [(lo, hi) for lo, hi in bounds if hi > lo]
-            if len(bounds) == 1:
-                parts.append(job(handles[0], *bounds[0]))
-            else:
-                from concurrent.futures import ThreadPoolExecutor
-                with ThreadPoolExecutor(max_workers=len(bounds)) as pool:      # (a libminkhip call releases the GIL)
-                    parts += [f.result() for f in [pool.submit(job, h, lo, hi) for h, (lo, hi) in zip(handles, bounds)]]
+    parts = _chunks_and_shards(configuration, layout, prob, B, chunk, n_dev, shard, job)
     paths = None
     if kt is not None:                                         # (parts: KeyframesOut — the trajectory and the interpolated targets)
         if return_targets:
@@ -670,6 +647,153 @@ def solve_ik_trajectory(configuration: Configuration, tasks: Sequence, dt: float
             if id(t) in seqs:
                 by_task[t] = un(np.ascontiguousarray(arr[:, :, n]))
     return res, by_task
+
+
+class TrajectoryMultistartResult(NamedTuple):
+    """Result of solve_ik_trajectory_multistart.  The chosen candidate's trajectory, (B, T, ·) — (T, ·) for an unbatched
+    configuration —: `q`, `v`, `status`, `iters`, `converged` as in TrajectoryResult; per instance the chosen `seed_index`, the
+    number `n_tracked` of waypoints it tracked, `n_complete` of the S candidates that tracked all T, and its `path_length`;
+    `qvel` when waypoint_dt was given.  With return_all every candidate's `q_all` (B, S, T, nq), `v_all` (B, S, T, nv),
+    `status_all`, `iters_all`, `converged_all` (B, S, T) and the `seeds` (B, S, nq) they started from; None otherwise."""
+    q: np.ndarray
+    v: np.ndarray
+    status: np.ndarray
+    iters: np.ndarray
+    converged: np.ndarray
+    seed_index: np.ndarray
+    n_tracked: np.ndarray
+    n_complete: np.ndarray
+    path_length: np.ndarray
+    qvel: Optional[np.ndarray] = None
+    q_all: Optional[np.ndarray] = None
+    v_all: Optional[np.ndarray] = None
+    status_all: Optional[np.ndarray] = None
+    iters_all: Optional[np.ndarray] = None
+    converged_all: Optional[np.ndarray] = None
+    seeds: Optional[np.ndarray] = None
+
+
+def solve_ik_trajectory_multistart(configuration: Configuration, tasks: Sequence, dt: float, targets, n_seeds: int, n_steps: int,
+                                   pos_threshold: float, ori_threshold: float, solver: str = "mi355x", damping: float = 1e-12,
+                                   limits: Optional[Sequence] = None, rng_seed: int = 0, seeds=None, weights=None,
+                                   waypoint_dt: Optional[float] = None, warm_start: bool = False, update: bool = True,
+                                   return_all: bool = False, max_instances: int = 1 << 20) -> TrajectoryMultistartResult:
+    """Track a time sequence of targets globally: `n_seeds` candidate trajectories per instance, seeded like
+    solve_ik_multistart and each tracked like solve_ik_trajectory (waypoint t from the same candidate's waypoint t − 1, so a
+    candidate is continuous by construction), scored over the whole path, one chosen and gathered on the device — in one call.
+
+    `targets` as in solve_ik_trajectory (no keyframes here).  `n_steps` is max_iters of the threshold-terminated loop of every
+    waypoint; both thresholds are required (there is nothing to score after a fixed count).  Candidate 0 starts at the
+    configuration's own q: it is solve_ik_trajectory's trajectory; the others start as solve_ik_multistart's seeds do (same
+    stateless generator, same `seeds` argument).
+
+    A waypoint is tracked when its loop converged without a QP failure.  Per instance the candidate that tracked the most
+    waypoints wins; among those the shortest path Σ_t Σ_k weights_k·(q_t ⊖ q_{t−1})_k², q_{−1} = the configuration's q for every
+    candidate (the jump to a far seed counts); ties go to the lowest index; when nobody tracked anything, candidate 0.  Limits
+    warnings and SolverError follow solve_ik_trajectory's rules on the CHOSEN candidate only.  With `update` the configuration
+    is left at the chosen q[:, -1].  When B·n_seeds exceeds `max_instances` the instances are walked in chunks; a multi-device
+    configuration shards by instance; the result depends on neither."""
+    del solver
+    S, n_steps = int(n_seeds), int(n_steps)
+    if S < 1:
+        raise ValueError("n_seeds must be >= 1")
+    if n_steps < 1:
+        raise ValueError("n_steps must be >= 1")
+    if int(max_instances) < 1:
+        raise ValueError("max_instances must be >= 1")
+    if waypoint_dt is not None and not float(waypoint_dt) > 0.0:
+        raise ValueError("waypoint_dt must be > 0")
+    if pos_threshold is None or ori_threshold is None or not (float(pos_threshold) >= 0.0 and float(ori_threshold) >= 0.0):
+        raise ValueError("thresholds must be >= 0: multi-start trajectories run in threshold mode only")
+    B, nq, nv = configuration.batch_size, configuration.nq, configuration.nv
+    seqs, T = _trajectory_targets(configuration, tasks, targets)
+    seeds = _host_array(seeds, "seeds")
+    if seeds is not None:
+        if seeds.shape == (S, nq):
+            seeds = np.ascontiguousarray(np.broadcast_to(seeds, (B, S, nq)))
+        elif seeds.shape != (B, S, nq):
+            raise ValueError(f"seeds must have shape ({S}, {nq}) or ({B}, {S}, {nq}), got {seeds.shape}")
+    weights = _host_array(weights, "weights")
+    if weights is not None and weights.shape != (nv,):
+        raise ValueError(f"weights must have shape ({nv},), got {weights.shape}")
+    if weights is not None and not (weights >= 0.0).all():
+        raise ValueError("weights must be >= 0 (no NaN): the path length is a sum of non-negative terms")
+    # instances per chunk: as many as fit max_instances with their S candidates; devices share a chunk by instance
+    devices = configuration.devices
+    per_chunk = max(1, int(max_instances) // S)
+    n_dev = len(devices) if (len(devices) > 1 and min(B, per_chunk) >= len(devices)) else 1
+    chunk = min(B, per_chunk)
+    shard = -(-chunk // n_dev)
+    prob, layout = _compile_single(configuration, tasks, limits, shard * S, dt)
+    if layout["dense"] or layout["dense_limits"]:
+        raise exceptions.TaskDefinitionError(
+            "solve_ik_trajectory_multistart fuses the outer loop on the device; caller-defined Task / Limit subclasses are "
+            "evaluated on the host at every step: call solve_ik + integrate_inplace in a loop instead")
+    ft, pt, ct = _stacked_targets(configuration, layout, seqs, T)
+    q = configuration.q_batch
+    kw = dict(n_seeds=S, n_steps=n_steps, pos_threshold=float(pos_threshold), ori_threshold=float(ori_threshold),
+              rng_seed=int(rng_seed), weights=weights, qvel_dt=waypoint_dt, warm_start=bool(warm_start), return_all=bool(return_all))
+
+    def rows(x, held_ndim, lo, hi):
+        return None if x is None else (x if x.ndim == held_ndim else np.ascontiguousarray(x[lo:hi]))
+
+    def job(handle, lo, hi):
+        out = handle.solve_trajectory_multistart(q[lo:hi], rows(ft, 0, lo, hi), rows(pt, 2, lo, hi), rows(ct, 2, lo, hi), dt, damping,
+                                                 target_index0=lo, seeds=rows(seeds, 0, lo, hi), **kw)
+        if not return_all:
+            return out
+        # every candidate's results, time-major (T, n·S, ·) → (n, S, T, ·), so that chunks and shards concatenate by instance
+        n = hi - lo
+        by_inst = lambda x: np.ascontiguousarray(np.moveaxis(x.reshape((T, n, S) + x.shape[2:]), 0, 2))
+        return out._replace(q_all=by_inst(out.q_all), v_all=by_inst(out.v_all), status_all=by_inst(out.status_all),
+                            iters_all=by_inst(out.iters_all), converged_all=by_inst(out.converged_all),
+                            seeds=out.seeds.reshape(n, S, nq))
+
+    parts = _chunks_and_shards(configuration, layout, prob, B, chunk, n_dev, shard * S, job)
+    res = TrajectoryMultistartResult(*[None if parts[0][k] is None else np.concatenate([p[k] for p in parts], axis=0)
+                                       for k in range(len(TrajectoryMultistartResult._fields))])
+    status = res.status
+    outside = ((status & nat.ST_OUTSIDE_LIMITS) != 0).any(axis=1)
+    if outside.any():
+        logging.warning("solve_ik_trajectory_multistart: %d chosen trajectorie(s) were outside their configuration limits at some "
+                        "fused step", int(outside.sum()))
+    bad = np.argwhere((status & ~nat.ST_OUTSIDE_LIMITS) != 0)
+    if len(bad):
+        b0, t0 = (int(x) for x in bad[0])
+        raise exceptions.SolverError(f"QP failed at {len(bad)} of {status.size} waypoints of the chosen candidates "
+                                     f"(first: (instance, waypoint) = ({b0}, {t0}), status {int(status[b0, t0])})")
+    if update:
+        configuration.update(res.q[:, -1] if configuration.batched else res.q[0, -1])
+    un = configuration._unbatch
+    opt = lambda x, as_bool=False: None if x is None else un(x.astype(bool) if as_bool else x)
+    return TrajectoryMultistartResult(un(res.q), un(res.v), un(res.status), un(res.iters), un(res.converged.astype(bool)),
+                                      un(res.seed_index), un(res.n_tracked), un(res.n_complete), un(res.path_length),
+                                      opt(res.qvel), opt(res.q_all), opt(res.v_all), opt(res.status_all), opt(res.iters_all),
+                                      opt(res.converged_all, True), opt(res.seeds))
+
+
+def _chunks_and_shards(configuration: Configuration, layout, prob, B: int, chunk: int, n_dev: int, max_batch: int, job):
+    """[job(handle, lo, hi), ...] over the rows [0, B): chunks of `chunk` rows, each split among `n_dev` handles (one per listed
+    device, `max_batch` instances each) that run side by side.  The one driver of solve_ik_multistart, solve_ik_trajectory and
+    solve_ik_trajectory_multistart: a job is told its global row offset `lo`, so results do not depend on chunks or shards.
+    (A ShardedProblem cached by solve_ik_steps for the same tasks and batch size cannot serve: it splits rows without telling a
+    shard its global offset — every handle but the cached single-device one is built here.)"""
+    devices = configuration.devices
+    parts = []
+    with _pin(configuration, layout):
+        first = [prob] if isinstance(prob, nat.NativeProblem) else []
+        handles = first if (n_dev == 1 and first) else _multistart_shards(configuration, layout, first, devices[:n_dev], max_batch)
+        for c0 in range(0, B, chunk):
+            c1 = min(B, c0 + chunk)
+            bounds = [(c0 + lo, c0 + hi) for lo, hi in (shard_bounds(c1 - c0, n_dev, r) for r in range(n_dev))]
+            bounds = [(lo, hi) for lo, hi in bounds if hi > lo]
+            if len(bounds) == 1:
+                parts.append(job(handles[0], *bounds[0]))
+            else:
+                from concurrent.futures import ThreadPoolExecutor
+                with ThreadPoolExecutor(max_workers=len(bounds)) as pool:      # (a libminkhip call releases the GIL)
+                    parts += [f.result() for f in [pool.submit(job, h, lo, hi) for h, (lo, hi) in zip(handles, bounds)]]
+    return parts
 
 
 def _compile_single(configuration: Configuration, tasks, limits, batch: int, dt: float):
