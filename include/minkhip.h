@@ -261,7 +261,10 @@ typedef struct MkhProblemDesc {
 
 /* Per-call arrays of the plugin route (same host/device pointer convention as q).  K = Σ k over the dense tasks (in
  * descriptor order), M = n_dense_limit_rows.  A limit row with h = +inf is inactive (mink's Constraint.inactive,
- * limit.py:19-23, per row); at most 64 − nv rows (collision + dense) can be active in one instance. */
+ * limit.py:19-23, per row); at most 64 − nv rows (collision + dense) can be active in one instance.  A row of zeros with
+ * h ≥ 0 is a row like any other: it holds a place and never binds.  limit_lo / limit_hi are intersected with the built-in box; single-entry rows that contradict each other (or the
+ * box) arrive as limit_lo > limit_hi on that dof and give MKH_ST_INFEASIBLE with v = NaN, as the reference's QP would
+ * (tests/test_gpu_qp_degenerate.py). */
 typedef struct MkhDenseRows {
   const double *task_e; /* (B, K)      compute_error per instance                    */
   const double *task_J; /* (B, K, nv)  compute_jacobian per instance                 */

@@ -111,3 +111,20 @@ def chain_mjcf(ndof, seed=0, sites_every=25):
         lines.append("  " * (i + 2) + "</body>")
     lines += ['  </worldbody>', '</mujoco>']
     return "\n".join(lines), sites
+
+
+def hinge_chain_mjcf(n_links, seed=0):
+    """A serial chain of `n_links` hinges about random axes (range ±1.5) with a site `tip` on the last link: nv = n_links,
+    n_links + 1 bodies with the world — the sizes around the one-wavefront limit of 64."""
+    rng = np.random.default_rng(seed)
+    xml = ['<mujoco><compiler angle="radian"/><worldbody>']
+    for i in range(n_links):
+        ax = rng.normal(size=3)
+        ax /= np.linalg.norm(ax)
+        xml.append(f'<body name="b{i}" pos="{0.03 + 0.02 * rng.uniform():.4f} {0.01 * rng.normal():.4f} {0.01 * rng.normal():.4f}">'
+                   f'<joint name="j{i}" type="hinge" axis="{ax[0]:.5f} {ax[1]:.5f} {ax[2]:.5f}" range="-1.5 1.5"/>'
+                   f'<geom type="sphere" size="0.01" mass="0.1"/>')
+    xml.append('<site name="tip" pos="0.02 0 0"/>')
+    xml.append("</body>" * n_links)
+    xml.append("</worldbody></mujoco>")
+    return "".join(xml)

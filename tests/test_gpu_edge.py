@@ -6,6 +6,7 @@ import pytest
 
 import mink_amd as mink
 import oracle_configs as oc
+from random_models import hinge_chain_mjcf as _chain_xml
 from mink_amd import _native as nat
 from mink_amd import workloads
 from oracle import ik as oik
@@ -195,21 +196,6 @@ def test_ticket_counter_survives_many_launches_and_odd_batches():
         np.testing.assert_array_equal(st, st_ref[:n])
     fresh, _ = nc.build("g1_c3", nm, B)[0].solve(q, tg, stand[None, :], None, dt, damping)
     np.testing.assert_array_equal(fresh, ref)
-
-
-def _chain_xml(n_links, seed=0):
-    rng = np.random.default_rng(seed)
-    xml = ['<mujoco><compiler angle="radian"/><worldbody>']
-    for i in range(n_links):
-        ax = rng.normal(size=3)
-        ax /= np.linalg.norm(ax)
-        xml.append(f'<body name="b{i}" pos="{0.03 + 0.02 * rng.uniform():.4f} {0.01 * rng.normal():.4f} {0.01 * rng.normal():.4f}">'
-                   f'<joint name="j{i}" type="hinge" axis="{ax[0]:.5f} {ax[1]:.5f} {ax[2]:.5f}" range="-1.5 1.5"/>'
-                   f'<geom type="sphere" size="0.01" mass="0.1"/>')
-    xml.append('<site name="tip" pos="0.02 0 0"/>')
-    xml.append("</body>" * n_links)
-    xml.append("</worldbody></mujoco>")
-    return "".join(xml)
 
 
 def test_maximum_sizes_of_one_wavefront():
