@@ -113,6 +113,46 @@ def chain_mjcf(ndof, seed=0, sites_every=25):
     return "\n".join(lines), sites
 
 
+def ball_chain_mjcf(n_ball=18, n_hinge=8, seed=0, limited_every=4, n_sites=3):
+    """A serial chain behind a free root: `n_ball` ball and `n_hinge` hinge links in shuffled order, every
+    `limited_every`-th ball joint limited (range 0 … 0.9), hinges within ±1.2, `n_sites` sites spread along it and at the
+    tip.  The defaults give nv = 6 + 3·18 + 8 = 68 and 28 bodies with the world: past one wavefront in dofs."""
+    rng = np.random.default_rng(seed)
+
+    def fmt(v):
+        return " ".join(f"{x:.6f}" for x in v)
+
+    kinds = ["ball"] * n_ball + ["hinge"] * n_hinge
+    rng.shuffle(kinds)
+    n = len(kinds)
+    at = {int(round((k + 1) * n / n_sites)) - 1 for k in range(n_sites)}
+    sites = []
+    lines = ['<mujoco>', '  <compiler angle="radian" autolimits="true"/>', '  <worldbody>',
+             '    <body name="root" pos="0 0 0.5">', '      <inertial pos="0 0 0" mass="1" diaginertia="1 1 1"/>',
+             '      <freejoint name="root"/>']
+    n_b = 0
+    for i, kind in enumerate(kinds):
+        pad = "  " * (i + 3)
+        pos = np.array([0.0, 0.0, 0.04]) + rng.normal(scale=0.01, size=3)
+        quat = olie.so3_exp(rng.normal(scale=0.3, size=3))
+        lines.append(f'{pad}<body name="b{i}" pos="{fmt(pos)}" quat="{fmt(quat)}">')
+        lines.append(f'{pad}  <inertial pos="0 0 0.02" mass="{rng.uniform(0.1, 0.5):.4f}" diaginertia="1 1 1"/>')
+        if kind == "ball":
+            lim = ' range="0 0.9"' if n_b % limited_every == limited_every - 1 else ""
+            n_b += 1
+            lines.append(f'{pad}  <joint name="j{i}" type="ball" pos="{fmt(rng.normal(scale=0.005, size=3))}"{lim}/>')
+        else:
+            ax = rng.normal(size=3); ax /= np.linalg.norm(ax)
+            lines.append(f'{pad}  <joint name="j{i}" type="hinge" axis="{fmt(ax)}" range="-1.2 1.2"/>')
+        if i in at:
+            sites.append(f"s{i}")
+            lines.append(f'{pad}  <site name="s{i}" pos="0.01 0 0.03" quat="{fmt(olie.so3_exp(rng.normal(size=3)))}"/>')
+    for i in reversed(range(n)):
+        lines.append("  " * (i + 3) + "</body>")
+    lines += ['    </body>', '  </worldbody>', '</mujoco>']
+    return "\n".join(lines), sites
+
+
 def hinge_chain_mjcf(n_links, seed=0):
     """A serial chain of `n_links` hinges about random axes (range ±1.5) with a site `tip` on the last link: nv = n_links,
     n_links + 1 bodies with the world — the sizes around the one-wavefront limit of 64."""

@@ -9,47 +9,10 @@ import mink_amd as mink
 from mink_amd import _native as nat
 from oracle import ik as oik
 from oracle import lie as olie
+from quat_cases import MIXED
 
 pytestmark = pytest.mark.gpu
 
-MIXED = """
-<mujoco>
-  <compiler angle="radian"/>
-  <worldbody>
-    <body name="b1" pos="0 0 0.1">
-      <inertial pos="0 0 0.05" mass="1" diaginertia="1 1 1"/>
-      <joint name="hinge" type="hinge" axis="0 1 0" range="-1.2 1.2" pos="0 0 0.02"/>
-      <body name="b2" pos="0.1 0 .3" quat="0.9 0.1 0 0.4">
-        <inertial pos="0 0.02 0" mass="0.7" diaginertia="1 1 1"/>
-        <joint name="ball" type="ball" pos="0.01 0 0"/>
-        <body name="b3" pos="0 0.05 .3">
-          <inertial pos="0.03 0 0" mass="0.4" diaginertia="1 1 1"/>
-          <joint name="slide" type="slide" axis="1 0.2 0" range="-0.2 0.3"/>
-          <site name="tip" pos="0.02 0.01 0.1" quat="0.8 0 0.6 0"/>
-          <body name="b4" pos="0 0 .2">
-            <inertial pos="0 0 0.1" mass="0.3" diaginertia="1 1 1"/>
-            <joint name="px" type="slide" axis="1 0 0"/>
-            <joint name="py" type="slide" axis="0 1 0"/>
-            <joint name="yaw" type="hinge" axis="0 0 1" pos="0.01 0.02 0"/>
-            <joint name="pitch" type="hinge" axis="0 1 0" range="-1 1"/>
-            <site name="multi" pos="0.05 0 0.05"/>
-          </body>
-        </body>
-      </body>
-    </body>
-    <body name="floating" pos="1 0 0.5" quat="0.7 0.1 0.2 0.3">
-      <inertial pos="0.01 0.02 0.03" mass="2" diaginertia="1 1 1"/>
-      <freejoint name="free"/>
-      <site name="fs" pos="0.1 0 0" quat="0.5 0.5 0.5 0.5"/>
-      <body name="arm" pos="0 0 0.2">
-        <inertial pos="0 0 0.1" mass="0.5" diaginertia="1 1 1"/>
-        <joint name="elbow" type="hinge" axis="1 0 0" range="-2 2"/>
-        <site name="hand" pos="0 0 0.25"/>
-      </body>
-    </body>
-  </worldbody>
-</mujoco>
-"""
 
 
 def _rand_q(m, rng):
