@@ -388,6 +388,42 @@ def _is_torch(x) -> bool:
     return type(x).__module__.split(".")[0] == "torch"
 
 
+def _call_kit(q):
+    """(prep, empty, ptr, stream, flag) of an outer-loop call, from the kind of its q.  numpy: float64 host arrays, the default
+    stream, no flag; torch: float64 tensors on q's device, the current stream's handle, FLAG_DEVICE_PTRS.  prep(x) brings an
+    optional input into that form, empty(shape, np.float64 | np.int32) makes an output, ptr(x) is its address (None for None)."""
+    if not _is_torch(q):
+        return ((lambda x: None if x is None else _f64(x)), (lambda shape, dtype: np.empty(shape, dtype=dtype)),
+                (lambda x: None if x is None else x.ctypes.data), None, 0)
+    import torch
+    dev = q.device
+
+    def prep(x):
+        if x is None or (x.dtype is torch.float64 and x.device == dev and x.is_contiguous()):
+            return x
+        return torch.as_tensor(x).to(device=dev, dtype=torch.float64).contiguous()
+
+    def empty(shape, dtype):
+        return torch.empty(shape, dtype=torch.float64 if dtype is np.float64 else torch.int32, device=dev)
+
+    return prep, empty, (lambda x: None if x is None else x.data_ptr()), _raw_stream(torch, dev), FLAG_DEVICE_PTRS
+
+
+def _held_or_batched(x, B: int, n: int, w: int, name: str, flag: int, strict: bool = True):
+    """The flag bit of a posture / CoM target from its shape: 0 for one target held for the batch, (n, w); `flag` for one per
+    instance, (B, n, w).  Any other shape raises — or, not `strict`, returns None for the caller to read further."""
+    if x is None:
+        raise ValueError(f"{name} is required")
+    shp = tuple(x.shape)
+    if shp == (n, w):
+        return 0
+    if shp == (B, n, w):
+        return flag
+    if strict:
+        raise ValueError(f"{name} must have shape ({n}, {w}) or (B, ...)")
+    return None
+
+
 def _raw_stream(torch, dev) -> int:
     """hipStream_t of torch's current stream on `dev` (the private accessor costs a tenth of building a Stream object)."""
     try:
@@ -599,12 +635,6 @@ class NativeProblem:
             (FLAG_WARM_START if warm_start else 0) | (FLAG_QUAD_KERNEL if quad_kernel else 0) | \
             (FLAG_FULL_ROWS if full_rows else 0)
 
-        def tgt(x, per, name):
-            nonlocal flags
-            if x is None:
-                return None
-            return x
-
         if use_torch:
             import torch
             dev = q.device
@@ -740,7 +770,6 @@ class NativeProblem:
     def _solve_multistart(self, q, frame_targets, posture_target, com_target, dt, damping, S, max_iters, pos_thr, ori_thr,
                           rng_seed, target_index0, seeds, reference, weights, return_all, wave_kernel, lane_kernel, quad_kernel):
         m = self.nmodel.model
-        use_torch = _is_torch(q)
         B = int(q.shape[0])
         if S < 1:
             raise ValueError("n_seeds must be >= 1")
@@ -752,26 +781,8 @@ class NativeProblem:
             raise ValueError("dense (plugin) rows are evaluated by the caller at q: no fused loop, no multi-start")
         flags = (FLAG_WAVE_KERNEL if wave_kernel else 0) | (FLAG_LANE_KERNEL if lane_kernel else 0) | \
             (FLAG_QUAD_KERNEL if quad_kernel else 0)
-        if use_torch:
-            import torch
-            dev = q.device
-
-            def prep(x):
-                if x is None or (x.dtype is torch.float64 and x.device == dev and x.is_contiguous()):
-                    return x
-                return torch.as_tensor(x).to(device=dev, dtype=torch.float64).contiguous()
-
-            def empty(shape, dtype):
-                return torch.empty(shape, dtype=torch.float64 if dtype is np.float64 else torch.int32, device=dev)
-
-            ptr = lambda x: None if x is None else x.data_ptr()
-            flags |= FLAG_DEVICE_PTRS
-            stream = _raw_stream(torch, dev)
-        else:
-            prep = lambda x: None if x is None else _f64(x)
-            empty = lambda shape, dtype: np.empty(shape, dtype=dtype)
-            ptr = lambda x: None if x is None else x.ctypes.data
-            stream = None
+        prep, empty, ptr, stream, devp = _call_kit(q)
+        flags |= devp
         q, frame_targets, posture_target, com_target = prep(q), prep(frame_targets), prep(posture_target), prep(com_target)
         seeds, reference, weights = prep(seeds), prep(reference), prep(weights)
         if tuple(q.shape) != (B, m.nq):
@@ -781,19 +792,9 @@ class NativeProblem:
         if frame_targets is None or tuple(frame_targets.shape) != (B, self.n_frame, 7):
             raise ValueError(f"frame_targets must have shape ({B}, {self.n_frame}, 7)")
         if self.n_posture:
-            if posture_target is None:
-                raise ValueError("posture_target is required")
-            if tuple(posture_target.shape) == (B, self.n_posture, m.nq):
-                flags |= FLAG_POSTURE_BATCHED
-            elif tuple(posture_target.shape) != (self.n_posture, m.nq):
-                raise ValueError(f"posture_target must have shape ({self.n_posture}, {m.nq}) or (B, ...)")
+            flags |= _held_or_batched(posture_target, B, self.n_posture, m.nq, "posture_target", FLAG_POSTURE_BATCHED)
         if self.n_com:
-            if com_target is None:
-                raise ValueError("com_target is required")
-            if tuple(com_target.shape) == (B, self.n_com, 3):
-                flags |= FLAG_COM_BATCHED
-            elif tuple(com_target.shape) != (self.n_com, 3):
-                raise ValueError(f"com_target must have shape ({self.n_com}, 3) or (B, ...)")
+            flags |= _held_or_batched(com_target, B, self.n_com, 3, "com_target", FLAG_COM_BATCHED)
         if seeds is not None and tuple(seeds.shape) != (B, S, m.nq):
             raise ValueError(f"seeds must have shape ({B}, {S}, {m.nq}), got {tuple(seeds.shape)}")
         if reference is not None and tuple(reference.shape) != (B, m.nq):
@@ -873,7 +874,6 @@ class NativeProblem:
     def _solve_trajectory(self, q, frame_targets, posture_target, com_target, dt, damping, n_steps, until, qvel_dt, tm,
                           warm_start, wave_kernel, lane_kernel, quad_kernel, keys=None, cands=None):
         m = self.nmodel.model
-        use_torch = _is_torch(q)
         B = int(q.shape[0])
         if n_steps < 1:
             raise ValueError("n_steps must be >= 1")
@@ -894,26 +894,8 @@ class NativeProblem:
             raise ValueError("threshold mode needs at least one frame task to test the thresholds on")
         flags = (FLAG_WAVE_KERNEL if wave_kernel else 0) | (FLAG_LANE_KERNEL if lane_kernel else 0) | \
             (FLAG_QUAD_KERNEL if quad_kernel else 0) | (FLAG_WARM_START if warm_start else 0)
-        if use_torch:
-            import torch
-            dev = q.device
-
-            def prep(x):
-                if x is None or (x.dtype is torch.float64 and x.device == dev and x.is_contiguous()):
-                    return x
-                return torch.as_tensor(x).to(device=dev, dtype=torch.float64).contiguous()
-
-            def empty(shape, dtype):
-                return torch.empty(shape, dtype=torch.float64 if dtype is np.float64 else torch.int32, device=dev)
-
-            ptr = lambda x: None if x is None else x.data_ptr()
-            flags |= FLAG_DEVICE_PTRS
-            stream = _raw_stream(torch, dev)
-        else:
-            prep = lambda x: None if x is None else _f64(x)
-            empty = lambda shape, dtype: np.empty(shape, dtype=dtype)
-            ptr = lambda x: None if x is None else x.ctypes.data
-            stream = None
+        prep, empty, ptr, stream, devp = _call_kit(q)
+        flags |= devp
         q, frame_targets, posture_target, com_target = prep(q), prep(frame_targets), prep(posture_target), prep(com_target)
         if tuple(q.shape) != (B, m.nq):
             raise ValueError(f"q must have shape (B, {m.nq}), got {tuple(q.shape)}")
@@ -929,19 +911,16 @@ class NativeProblem:
         def held_or_timed(x, n, w, name, flag):
             """(per_waypoint, flags bit) of a posture / CoM target from its shape."""
             nonlocal T
-            if x is None:
-                raise ValueError(f"{name} is required")
+            held = _held_or_batched(x, B, n, w, name, flag, strict=False)      # (n, w) / (B, n, w) as in solve(): no T axis
+            if held is not None:
+                return 0, held
             shp = tuple(x.shape)
-            if shp == (n, w):
-                return 0, 0
             if len(shp) == 4:                                  # (B, T, n, w) / (T, B, n, w)
                 Tx = shp[0 if tm else 1]
                 T = Tx if T is None else T
                 if shp == ((T, B, n, w) if tm else (B, T, n, w)):
                     return 1, flag
-            elif len(shp) == 3 and shp[1:] == (n, w):          # (B, n, w) as in solve(), else (T, n, w); T == B reads as (B, ...)
-                if shp[0] == B:
-                    return 0, flag
+            elif len(shp) == 3 and shp[1:] == (n, w):          # (T, n, w); T == B was read as (B, ...) above
                 T = shp[0] if T is None else T
                 if shp[0] == T:
                     return 1, 0

@@ -56,7 +56,6 @@ class Configuration:
         self._problems = {}
         self._compile_memo = {}          # (task / limit fingerprints, batch) → (cache key, layout): solve_ik._compile's shortcut
         self._default_limits = None      # the [ConfigurationLimit(model)] of solve_ik(limits=None), built once
-        self._multistart_shards = {}     # solve_ik_multistart on several devices: the handles beside the cached one
         self._pinned_problems = {}       # cache key → nesting count of callers about to solve on that handle (never evicted)
         self._q = None
         self.update(q if q is not None else self.model.qpos0)

@@ -1,6 +1,6 @@
 // Keyframed trajectory IK (mkh_solve_keyframes, include/minkhip.h "The rule"): the kernels that blend waypoint t's targets from
 // keyframes k and k + 1, launched on the caller's stream directly in front of waypoint t's fused loop — and their launchers
-// (declared in minkhip.hip next to the other launchers).  Segment k and parameter u are chosen on the host and are scalars of
+// (declared in outer_launch.h).  Segment k and parameter u are chosen on the host and are scalars of
 // the launch.  The keyframe arrays are read in place through (instance, keyframe) strides in elements, so batch-major
 // (B, K, ·) and time-major (K, B, ·) cost no transpose; the result goes to the (rows, ·) slab the loop reads and, when the
 // caller asked for the interpolated targets, to waypoint t of that array as well.  Bandwidth kernels: one thread per pose /
@@ -9,6 +9,7 @@
 #include <cstdint>
 
 #include "lie_dev.h"
+#include "outer_launch.h"
 
 namespace mkh {
 
@@ -111,20 +112,13 @@ __global__ __launch_bounds__(256) void keyframe_com_kernel(const double* __restr
   if (out) out[b * o_sb + n] = r;
 }
 
-static bool kf_grid(long long total, int block, unsigned* grid) {
-  const long long g = (total + block - 1) / block;
-  if (g > 0x7fffffffLL) return false;
-  *grid = (unsigned)g;
-  return true;
-}
-
 hipError_t launch_kf_frames(hipStream_t stream, const double* keys, long long s_b, long long s_k, int k, double u, int rows,
                             int n_frame, double* slab, double* out, long long o_sb) {
   const long long total = (long long)rows * n_frame;
   if (total == 0) return hipSuccess;
   unsigned grid;
-  if (!kf_grid(total, 256, &grid)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(keyframe_frames_kernel, dim3(grid), dim3(256), 0, stream, keys, s_b, s_k, k, u, rows, n_frame, slab, out, o_sb);
+  if (!grid_1d(total, &grid)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(keyframe_frames_kernel, dim3(grid), dim3(kOuterBlock), 0, stream, keys, s_b, s_k, k, u, rows, n_frame, slab, out, o_sb);
   return hipGetLastError();
 }
 
@@ -133,8 +127,8 @@ hipError_t launch_kf_posture(hipStream_t stream, const int32_t* jnt, int njnt, c
   const long long total = (long long)rows * n_posture * njnt;
   if (total == 0) return hipSuccess;
   unsigned grid;
-  if (!kf_grid(total, 256, &grid)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(keyframe_posture_kernel, dim3(grid), dim3(256), 0, stream, jnt, njnt, keys, s_b, s_k, k, u, rows, n_posture,
+  if (!grid_1d(total, &grid)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(keyframe_posture_kernel, dim3(grid), dim3(kOuterBlock), 0, stream, jnt, njnt, keys, s_b, s_k, k, u, rows, n_posture,
                      nq, slab, out, o_sb);
   return hipGetLastError();
 }
@@ -144,8 +138,8 @@ hipError_t launch_kf_com(hipStream_t stream, const double* keys, long long s_b, 
   const long long total = (long long)rows * width;
   if (total == 0) return hipSuccess;
   unsigned grid;
-  if (!kf_grid(total, 256, &grid)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(keyframe_com_kernel, dim3(grid), dim3(256), 0, stream, keys, s_b, s_k, k, u, rows, width, slab, out, o_sb);
+  if (!grid_1d(total, &grid)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(keyframe_com_kernel, dim3(grid), dim3(kOuterBlock), 0, stream, keys, s_b, s_k, k, u, rows, width, slab, out, o_sb);
   return hipGetLastError();
 }
 

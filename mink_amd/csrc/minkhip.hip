@@ -20,6 +20,7 @@
 
 #include "ik_kernel.h"
 #include "lane_kernel.h"
+#include "outer_launch.h"
 #include "variants.h"
 #include "wide_types.h"
 
@@ -84,8 +85,8 @@ struct PinnedScratch {
   void release() { if (host) (void)hipHostFree(host); host = dev = nullptr; }
 };
 
-// A device buffer of mkh_solve_multistart's workspace: grown to what a call needs (never beyond what max_batch allows),
-// kept for the next call.
+// A device buffer of the outer-loop entry points' workspace (MkhProblem::ws): grown to what a call needs (never beyond what
+// max_batch allows), kept for the next call, never shrunk.
 struct GrowBuf {
   void* p = nullptr;
   size_t cap = 0;
@@ -99,6 +100,29 @@ struct GrowBuf {
   void release() { (void)hipFree(p); p = nullptr; cap = 0; }
   double* f64() const { return (double*)p; }
   int32_t* i32() const { return (int32_t*)p; }
+};
+
+// The slots of that workspace, named by what a buffer HOLDS, not by the entry point that asked for it: one call is in flight
+// per handle (include/minkhip.h), so mkh_solve_multistart, mkh_solve_trajectory, mkh_solve_keyframes and
+// mkh_solve_trajectory_multistart share them.  Two roles that one call needs at the same time are two slots.
+enum WsRole {
+  // the per-qpos-address seeding table and the joint list (ms_build_tables, at the first call that needs them)
+  WS_SEED_I, WS_SEED_F, WS_JNT,
+  // inputs of a host-pointer call, staged as they came
+  WS_IN_Q, WS_IN_FT, WS_IN_PT, WS_IN_CT, WS_IN_SEEDS, WS_IN_REF, WS_IN_W,
+  // the B·S candidate rows: what the loops read and write (time-major (T, B·S, .) for a trajectory; one buffer per array, so
+  // that a caller's *_all array replaces its own), the starts, and ONE fanned-out (B·S, .) slab per target group
+  WS_C_Q, WS_C_V, WS_C_ST, WS_C_IT, WS_C_CV, WS_C_STARTS, WS_C_FT, WS_C_PT, WS_C_CT,
+  // a batch-major trajectory call: time-major copies of its targets, the loops' time-major results (TM_I32: status | iters |
+  // converged)
+  WS_TM_FT, WS_TM_PT, WS_TM_CT, WS_TM_Q, WS_TM_V, WS_TM_I32,
+  // keyframes: ONE (B, .) slab per target group, rewritten in front of every waypoint's loop
+  WS_KF_FT, WS_KF_PT, WS_KF_CT,
+  // outputs of a host-pointer call in the caller's layout, until they are copied back (OUT_I32: status | iters | converged
+  // per row; OUT_PICK: the per-instance integers of a selection; OUT_LEN: path lengths; OUT_FT / PT / CT: the interpolated
+  // targets a keyframed call was asked for — the only buffers of a call's targets that grow with T)
+  WS_OUT_Q, WS_OUT_V, WS_OUT_I32, WS_OUT_QVEL, WS_OUT_PICK, WS_OUT_LEN, WS_OUT_FT, WS_OUT_PT, WS_OUT_CT,
+  WS_COUNT
 };
 
 struct MkhModel {
@@ -206,68 +230,19 @@ struct MkhProblem {
   int32_t* s_iters = nullptr;      // [2][max_batch]: iterations, converged (mkh_solve_until, host-pointer calls)
   size_t s_pt_cap = 0, s_ct_cap = 0;
   double *s_de = nullptr, *s_dJ = nullptr, *s_dG = nullptr, *s_dh = nullptr, *s_dbox = nullptr;   // dense (plugin) rows
-  // mkh_solve_multistart: the seeding / joint tables (built at the first call) and the workspace of the B·S instances
-  // (seeds → loop results in place, replicated targets, per-instance loop outputs), plus the staging of host-pointer calls
-  bool ms_tables = false;
-  GrowBuf ms_seed_i, ms_seed_f, ms_jnt;
-  GrowBuf ms_q, ms_seeds, ms_ft, ms_pt, ms_ct, ms_v, ms_i32;                   // B·S rows (ms_i32: status | iters | converged)
-  GrowBuf ms_in_q, ms_in_ft, ms_in_pt, ms_in_ct, ms_in_ref, ms_in_w, ms_out_q, ms_out_v, ms_out_i32;   // B rows
-  // mkh_solve_trajectory: time-major copies of batch-major targets, the loops' time-major results of a batch-major call
-  // (tj_i32: status | iters | converged), and the staging of host-pointer calls (tj_out_*: in the caller's layout)
-  GrowBuf tj_ft, tj_pt, tj_ct, tj_q, tj_v, tj_i32;
-  GrowBuf tj_in_q, tj_in_ft, tj_in_pt, tj_in_ct, tj_out_q, tj_out_v, tj_out_i32, tj_out_qvel;
-  // mkh_solve_keyframes: ONE (B, .) slab per target group, rewritten in front of every waypoint's loop, and the staging of
-  // the interpolated targets a host-pointer call asked for (the only buffers of the call's targets that grow with T)
-  GrowBuf kf_ft, kf_pt, kf_ct, kf_out_ft, kf_out_pt, kf_out_ct;
-  // mkh_solve_trajectory_multistart: the candidates' starts, ONE (B·S, .) slab per fanned-out target group, the loops'
-  // time-major results of the B·S candidates (the workspace whose size the header states; one buffer per array, so that a
-  // caller's *_all array replaces its own), and the staging of host-pointer calls (tms_out_i32: seed_index | n_tracked |
-  // n_complete)
-  GrowBuf tms_seeds, tms_ft, tms_pt, tms_ct, tms_q, tms_v, tms_st, tms_it, tms_cv;
-  GrowBuf tms_in_seeds, tms_in_w, tms_out_i32, tms_out_len;
+  // the outer-loop entry points' workspace, by role (WsRole)
+  bool ws_tables = false;
+  GrowBuf ws[WS_COUNT];
 };
 
 // The wavefront kernel's variants live in their own translation units (mink_amd/csrc/build.py generates one variant_<name>.hip
 // per compiled combination so that they build in parallel) and are reached through the generated table of variants.h; these are
-// the launchers of the other kernels.
+// the launchers of the other kernels (those of the outer-loop entry points' small kernels: outer_launch.h).
 namespace mkh {
 int launch_lane(int nv_max, bool loop, int grid, int lds_bytes, hipStream_t stream, const LaneProblem* P, const SolveArgs& a);
 int launch_quad(int nt, bool loop, int grid, hipStream_t stream, const void* P, const LaneDims& dims, const SolveArgs& a);   // returns its LDS bytes per wavefront
 int launch_wide(int grid, int lds_bytes, hipStream_t stream, const WideProblem* P, const SolveArgs& a, const TapArgs* taps, bool convex);
 int launch_convex_pre(hipStream_t stream, const WideProblem* P, const CvPre& C, int B, const double* q, double* out);
-// multi-start IK (multistart.hip): seeding, target fan-out, selection — the kernels around the loop of mkh_solve_multistart
-hipError_t launch_ms_seed(hipStream_t stream, const int32_t* seed_i, const double* seed_f, int B, int S, int nq, const double* q,
-                          const double* user_seeds, unsigned long long rng_seed, long long target_index0, double* q_seeds);
-hipError_t launch_ms_fanout(hipStream_t stream, const double* src, double* dst, int B, int S, int width);
-hipError_t launch_ms_select(hipStream_t stream, int B, int S, int nq, int nv, int njnt, const int32_t* jnt, const double* q_all,
-                            const double* v_all, const int32_t* status_all, const int32_t* iters_all, const int32_t* converged_all,
-                            const double* q_ref, const double* weights, double* q_best, double* v_best, int32_t* iters,
-                            int32_t* status, int32_t* converged, int32_t* seed_index, int32_t* n_converged);
-// trajectory IK (trajectory.hip): (B, T, W) ↔ (T, B, W) transposes and the joint velocity between waypoints — the kernels
-// around the T loop launches of mkh_solve_trajectory
-hipError_t launch_tj_gather(hipStream_t stream, const double* src, double* dst, int B, int T, int W);
-hipError_t launch_tj_scatter(hipStream_t stream, const double* src, double* dst, int B, int T, int W);
-hipError_t launch_tj_scatter_i32(hipStream_t stream, const int32_t* src, int32_t* dst, int B, int T);
-hipError_t launch_tj_qvel(hipStream_t stream, const int32_t* jnt, int njnt, int B, int T, int nq, const double* q0,
-                          const double* q_traj, long long q_sb, long long q_st, double dt, double* qvel, long long v_sb,
-                          long long v_st, int time_major);
-// keyframed trajectory IK (keyframes.hip): waypoint t's targets blended from keyframes k and k + 1 at parameter u, read in place
-// through (instance, keyframe) strides, written to the loop's slab and (optionally) to waypoint t of the caller's *_targets_out
-hipError_t launch_kf_frames(hipStream_t stream, const double* keys, long long s_b, long long s_k, int k, double u, int rows,
-                            int n_frame, double* slab, double* out, long long o_sb);
-hipError_t launch_kf_posture(hipStream_t stream, const int32_t* jnt, int njnt, const double* keys, long long s_b, long long s_k,
-                             int k, double u, int rows, int n_posture, int nq, double* slab, double* out, long long o_sb);
-hipError_t launch_kf_com(hipStream_t stream, const double* keys, long long s_b, long long s_k, int k, double u, int rows,
-                         int width, double* slab, double* out, long long o_sb);
-// multi-start trajectory IK (trajectory_multistart.hip): every candidate scored over its path and one chosen per instance, the
-// chosen candidate's rows of the time-major (T, B·S, .) results gathered through the (instance, waypoint) strides of `out`
-hipError_t launch_tms_score(hipStream_t stream, int B, int S, int T, int nq, int njnt, const int32_t* jnt, const double* q0,
-                            const double* q_all, const int32_t* status_all, const int32_t* converged_all, const double* weights,
-                            int32_t* seed_index, int32_t* n_tracked, int32_t* n_complete, double* path_length);
-hipError_t launch_tms_gather(hipStream_t stream, const double* all, double* out, const int32_t* seed_index, int B, int S, int T,
-                             int W, long long o_sb, long long o_st);
-hipError_t launch_tms_gather_i32(hipStream_t stream, const int32_t* all, int32_t* out, const int32_t* seed_index, int B, int S,
-                                 int T, long long o_sb, long long o_st);
 constexpr int kLaneMinBatchLoop = 28672;  // fused loops of a small arm: row kernel below, lane kernel from here (M targets/s at 16 384: 39.7 vs 24.1, at 32 768: 42.4 vs 48.2)
 constexpr int kLaneMinBatch = 73728;  // plain solves of a small arm: row kernel below, lane kernel from here (plan_launch())
 }
@@ -1506,14 +1481,7 @@ void mkh_problem_destroy(MkhProblem* p) {
   for (void* w : p->wide_allocs) (void)hipFree(w);
   (void)hipFree(p->d_wide);
   (void)hipFree(p->s_q); (void)hipFree(p->s_ft); (void)hipFree(p->s_pt); (void)hipFree(p->s_ct); (void)hipFree(p->s_v); (void)hipFree(p->s_status);
-  for (GrowBuf* g : {&p->ms_seed_i, &p->ms_seed_f, &p->ms_jnt, &p->ms_q, &p->ms_seeds, &p->ms_ft, &p->ms_pt, &p->ms_ct, &p->ms_v,
-                     &p->ms_i32, &p->ms_in_q, &p->ms_in_ft, &p->ms_in_pt, &p->ms_in_ct, &p->ms_in_ref, &p->ms_in_w, &p->ms_out_q,
-                     &p->ms_out_v, &p->ms_out_i32, &p->tj_ft, &p->tj_pt, &p->tj_ct, &p->tj_q, &p->tj_v, &p->tj_i32, &p->tj_in_q,
-                     &p->tj_in_ft, &p->tj_in_pt, &p->tj_in_ct, &p->tj_out_q, &p->tj_out_v, &p->tj_out_i32, &p->tj_out_qvel, &p->kf_ft,
-                     &p->kf_pt, &p->kf_ct, &p->kf_out_ft, &p->kf_out_pt, &p->kf_out_ct, &p->tms_seeds, &p->tms_ft, &p->tms_pt, &p->tms_ct,
-                     &p->tms_q, &p->tms_v, &p->tms_st, &p->tms_it, &p->tms_cv, &p->tms_in_seeds, &p->tms_in_w, &p->tms_out_i32,
-                     &p->tms_out_len})
-    g->release();
+  for (GrowBuf& g : p->ws) g.release();
   p->small.release();
   if (p->st_in) (void)hipStreamDestroy(p->st_in);
   if (p->st_out) (void)hipStreamDestroy(p->st_out);
@@ -1917,6 +1885,23 @@ struct TapBuf {
   void* host; void* dev; size_t bytes;
 };
 
+// What every solve refuses about its inputs, in this order: a NULL q, a threshold loop without a frame task to test (`until_who`
+// names the entry point; NULL: no thresholds), a NULL target of a task group the problem has, and — for the entry points that
+// cannot serve plugin rows at all — those (`no_plugin` ends the message: what besides the fused loop they rule out; NULL: the
+// caller has its own rules for them).
+static int32_t refuse_inputs(const DeviceProblem& P, const double* q, const double* frame_targets, const double* posture_target,
+                             const double* com_target, const char* until_who, const char* no_plugin) {
+  if (!q) return fail(MKH_E_INVALID, "q is null");
+  if (until_who && P.n_frame < 1)
+    return fail(MKH_E_INVALID, "%s needs at least one frame task to test the thresholds on", until_who);
+  if (P.n_frame > 0 && !frame_targets) return fail(MKH_E_INVALID, "frame_targets is null (TargetNotSet)");
+  if (P.n_posture > 0 && !posture_target) return fail(MKH_E_INVALID, "posture_target is null (TargetNotSet)");
+  if (P.n_com > 0 && !com_target) return fail(MKH_E_INVALID, "com_target is null (TargetNotSet)");
+  if (no_plugin && (P.n_dense_rows || P.n_dense_limit_rows || P.dense_box))
+    return fail(MKH_E_INVALID, "dense (plugin) rows are evaluated by the caller at q: no fused loop, no %s", no_plugin);
+  return MKH_OK;
+}
+
 static int32_t run(MkhProblem* p, int32_t B, const double* q, const double* frame_targets, const double* posture_target,
                    const double* com_target, double dt, double damping, double* v_out, int32_t* status_out,
                    const MkhTaps* taps, int32_t flags, void* hip_stream, int32_t n_steps, double* q_out,
@@ -1925,10 +1910,7 @@ static int32_t run(MkhProblem* p, int32_t B, const double* q, const double* fram
   if (!p) return fail(MKH_E_INVALID, "null problem");
   if (B < 1) return fail(MKH_E_INVALID, "B must be >= 1");
   const DeviceProblem& P = p->dev;
-  if (!q) return fail(MKH_E_INVALID, "q is null");
-  if (P.n_frame > 0 && !frame_targets) return fail(MKH_E_INVALID, "frame_targets is null (TargetNotSet)");
-  if (P.n_posture > 0 && !posture_target) return fail(MKH_E_INVALID, "posture_target is null (TargetNotSet)");
-  if (P.n_com > 0 && !com_target) return fail(MKH_E_INVALID, "com_target is null (TargetNotSet)");
+  if (const int32_t rc = refuse_inputs(P, q, frame_targets, posture_target, com_target, nullptr, nullptr)) return rc;
   if (!(dt > 0.0)) return fail(MKH_E_INVALID, "dt must be > 0");
   if (n_steps < 1) return fail(MKH_E_INVALID, "n_steps must be >= 1");
   const size_t Kd = P.n_dense_rows, Md = P.n_dense_limit_rows;
@@ -2225,7 +2207,7 @@ int32_t mkh_solve_until(MkhProblem* p, int32_t B, const double* q, const double*
 
 // The per-qpos-address seeding table and the joint list of the selection's tangent-space difference (multistart.hip).
 static int32_t ms_build_tables(MkhProblem* p) {
-  if (p->ms_tables) return MKH_OK;
+  if (p->ws_tables) return MKH_OK;
   const MkhModel* m = p->model;
   const int nq = m->nq, njnt = m->njnt;
   std::vector<int32_t> si(3 * (size_t)nq, 0), jn(3 * (size_t)njnt, 0);
@@ -2246,15 +2228,65 @@ static int32_t ms_build_tables(MkhProblem* p) {
       }
     }                                                  // free joint: the caller's value (zeros)
   }
-  HIP_OK(p->ms_seed_i.need(si.size() * sizeof(int32_t)));
-  HIP_OK(p->ms_seed_f.need(sf.size() * sizeof(double)));
-  HIP_OK(p->ms_jnt.need(jn.size() * sizeof(int32_t)));
-  HIP_OK(hipMemcpy(p->ms_seed_i.p, si.data(), si.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(p->ms_seed_f.p, sf.data(), sf.size() * sizeof(double), hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(p->ms_jnt.p, jn.data(), jn.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  p->ms_tables = true;
+  HIP_OK(p->ws[WS_SEED_I].need(si.size() * sizeof(int32_t)));
+  HIP_OK(p->ws[WS_SEED_F].need(sf.size() * sizeof(double)));
+  HIP_OK(p->ws[WS_JNT].need(jn.size() * sizeof(int32_t)));
+  HIP_OK(hipMemcpy(p->ws[WS_SEED_I].p, si.data(), si.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(p->ws[WS_SEED_F].p, sf.data(), sf.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(p->ws[WS_JNT].p, jn.data(), jn.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  p->ws_tables = true;
   return MKH_OK;
 }
+
+// One outer-loop call's traffic with the workspace and with the caller's arrays.  The first HIP error is latched and everything
+// after it is skipped; finish() is the only way out once something is enqueued: a host-pointer call may have copies from or to
+// the caller's arrays in flight, so it drains the stream before it returns, whatever happened.
+struct Stager {
+  MkhProblem* p;
+  hipStream_t stream;
+  bool devp;                         // MKH_FLAG_DEVICE_PTRS: the caller's arrays are used in place, nothing is staged
+  const char* who;                   // the entry point, in messages
+  hipError_t err = hipSuccess;
+  size_t oom_bytes = 0;              // the size of the allocation that failed, if one did
+  size_t cand_bytes = 0;             // a call with candidates: what their results take (the out-of-memory message states it)
+
+  bool ok() const { return err == hipSuccess; }
+  void latch(hipError_t e) { if (err == hipSuccess) err = e; }
+  // slot `role` grown to `bytes`; NULL when that failed (or an error is latched already)
+  void* need(WsRole role, size_t bytes) {
+    if (!ok()) return nullptr;
+    GrowBuf& g = p->ws[role];
+    if ((err = g.need(bytes)) != hipSuccess) { oom_bytes = bytes; return nullptr; }
+    return g.p;
+  }
+  double* f64(WsRole role, size_t n) { return (double*)need(role, n * sizeof(double)); }
+  int32_t* i32(WsRole role, size_t n) { return (int32_t*)need(role, n * sizeof(int32_t)); }
+  // `n` doubles of a caller's input on the device: `src` itself, or its staged copy in slot `role`
+  const double* up(WsRole role, const double* src, size_t n) {
+    if (devp || !src) return src;
+    double* const d = f64(role, n);
+    if (d) latch(hipMemcpyAsync(d, src, n * sizeof(double), hipMemcpyHostToDevice, stream));
+    return d;
+  }
+  // rows the loops write: the caller's own array where it is a device buffer, else slot `role`
+  void* given_or(WsRole role, void* given, size_t bytes) { return (devp && given) ? given : need(role, bytes); }
+  // a result back into a host caller's array (an output the caller did not ask for: dst == NULL)
+  void down(void* dst, const void* src, size_t bytes) {
+    if (dst && ok()) latch(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream));
+  }
+  // the way out: `rc` != MKH_OK is a refusal or failure of a loop launch, whose message stands
+  int32_t finish(int32_t rc = MKH_OK) {
+    if (devp && ok() && rc == MKH_OK) return MKH_OK;         // (asynchronous on the caller's stream)
+    latch(hipStreamSynchronize(stream));                     // (a failed call still drains what it started)
+    if (rc != MKH_OK || ok()) return rc;
+    if (oom_bytes && cand_bytes)
+      return fail(MKH_E_HIP, "%s: no device memory for a buffer of %zu bytes (the candidates' results take T*B*S*((nq+nv)*8+12) = %zu bytes)",
+                  who, oom_bytes, cand_bytes);
+    return fail(MKH_E_HIP, "%s: %s", who, hipGetErrorString(err));
+  }
+};
+// a launcher's hipError_t into the latch; not launched at all behind an earlier error
+#define ST_LAUNCH(st, call) do { if ((st).ok()) (st).latch(call); } while (0)
 
 extern "C" {
 
@@ -2272,106 +2304,84 @@ int32_t mkh_solve_multistart(MkhProblem* p, int32_t B, const double* q, const do
   if (!io || !io->q_best || !io->v_best || !io->iters || !io->status || !io->converged || !io->seed_index || !io->n_converged)
     return fail(MKH_E_INVALID, "io and its per-target outputs (q_best, v_best, iters, status, converged, seed_index, n_converged) are required");
   const DeviceProblem& P = p->dev;
-  if (!q) return fail(MKH_E_INVALID, "q is null");
-  if (P.n_frame < 1) return fail(MKH_E_INVALID, "mkh_solve_multistart needs at least one frame task to test the thresholds on");
-  if (!frame_targets) return fail(MKH_E_INVALID, "frame_targets is null (TargetNotSet)");
-  if (P.n_posture > 0 && !posture_target) return fail(MKH_E_INVALID, "posture_target is null (TargetNotSet)");
-  if (P.n_com > 0 && !com_target) return fail(MKH_E_INVALID, "com_target is null (TargetNotSet)");
-  if (P.n_dense_rows || P.n_dense_limit_rows || P.dense_box)
-    return fail(MKH_E_INVALID, "dense (plugin) rows are evaluated by the caller at q: no fused loop, no multi-start");
+  if (const int32_t rc = refuse_inputs(P, q, frame_targets, posture_target, com_target, "mkh_solve_multistart", "multi-start"))
+    return rc;
   const long long N = (long long)B * n_seeds;
   if (N > p->max_batch)
     return fail(MKH_E_INVALID, "B * n_seeds = %lld exceeds max_batch=%d of this problem", N, p->max_batch);
   HIP_OK(hipSetDevice(p->model->device));
   if (const int32_t rc = ms_build_tables(p)) return rc;
-  hipStream_t stream = (hipStream_t)hip_stream;
   const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
   const bool pbat = (flags & MKH_FLAG_POSTURE_BATCHED) != 0, cbat = (flags & MKH_FLAG_COM_BATCHED) != 0;
+  Stager st{p, (hipStream_t)hip_stream, devp, "multistart"};
+  hipStream_t stream = st.stream;
+  GrowBuf* const ws = p->ws;
   const int S = n_seeds;
   const size_t Bz = B, Nz = (size_t)N, nq = P.nq, nv = P.nv, f8 = sizeof(double), i4 = sizeof(int32_t);
   const size_t ft_w = (size_t)P.n_frame * 7, pt_w = (size_t)P.n_posture * nq, ct_w = (size_t)P.n_com * 3;
 
   // ---- inputs on the device
-  const double *d_q = q, *d_ft = frame_targets, *d_pt = posture_target, *d_ct = com_target;
-  const double *d_user = io->seeds, *d_ref = io->q_ref, *d_w = io->weights;
-  if (!devp) {
-    auto up = [&](GrowBuf& g, const double* src, size_t n) -> hipError_t {
-      if (hipError_t e = g.need(n * f8)) return e;
-      return hipMemcpyAsync(g.p, src, n * f8, hipMemcpyHostToDevice, stream);
-    };
-    HIP_OK(up(p->ms_in_q, q, Bz * nq)); d_q = p->ms_in_q.f64();
-    HIP_OK(up(p->ms_in_ft, frame_targets, Bz * ft_w)); d_ft = p->ms_in_ft.f64();
-    if (pt_w) { HIP_OK(up(p->ms_in_pt, posture_target, pt_w * (pbat ? Bz : 1))); d_pt = p->ms_in_pt.f64(); }
-    if (ct_w) { HIP_OK(up(p->ms_in_ct, com_target, ct_w * (cbat ? Bz : 1))); d_ct = p->ms_in_ct.f64(); }
-    if (io->q_ref) { HIP_OK(up(p->ms_in_ref, io->q_ref, Bz * nq)); d_ref = p->ms_in_ref.f64(); }
-    if (io->weights) { HIP_OK(up(p->ms_in_w, io->weights, nv)); d_w = p->ms_in_w.f64(); }
-  }
-  // ---- workspace of the B·S instances
-  HIP_OK(p->ms_q.need(Nz * nq * f8));
-  HIP_OK(p->ms_ft.need(Nz * ft_w * f8));
-  HIP_OK(p->ms_v.need(Nz * nv * f8));
-  HIP_OK(p->ms_i32.need(3 * Nz * i4));
-  if (pt_w && pbat) HIP_OK(p->ms_pt.need(Nz * pt_w * f8));
-  if (ct_w && cbat) HIP_OK(p->ms_ct.need(Nz * ct_w * f8));
-  if (!devp && (io->seeds || io->seeds_out)) HIP_OK(p->ms_seeds.need(Nz * nq * f8));
-  if (!devp && io->seeds) {           // the caller's seeds, staged beside the workspace (the seed kernel reads them once)
-    HIP_OK(hipMemcpyAsync(p->ms_seeds.p, io->seeds, Nz * nq * f8, hipMemcpyHostToDevice, stream));
-    d_user = p->ms_seeds.f64();
-  }
+  const double* const d_q = st.up(WS_IN_Q, q, Bz * nq);
+  const double* const d_ft = st.up(WS_IN_FT, frame_targets, Bz * ft_w);
+  const double* d_pt = pt_w ? st.up(WS_IN_PT, posture_target, pt_w * (pbat ? Bz : 1)) : posture_target;
+  const double* d_ct = ct_w ? st.up(WS_IN_CT, com_target, ct_w * (cbat ? Bz : 1)) : com_target;
+  const double* const d_ref = st.up(WS_IN_REF, io->q_ref, Bz * nq);
+  const double* const d_w = st.up(WS_IN_W, io->weights, nv);
+  const double* const d_user = st.up(WS_IN_SEEDS, io->seeds, Nz * nq);       // (the seed kernel reads them once)
+  // ---- workspace of the B·S instances: the caller's *_all arrays where they are device buffers
+  double* const c_q = st.f64(WS_C_Q, Nz * nq);
+  double* const c_v = st.f64(WS_C_V, Nz * nv);
+  int32_t* const d_status = (int32_t*)st.given_or(WS_C_ST, io->status_all, Nz * i4);
+  int32_t* const d_iters = (int32_t*)st.given_or(WS_C_IT, io->iters_all, Nz * i4);
+  int32_t* const d_conv = (int32_t*)st.given_or(WS_C_CV, io->converged_all, Nz * i4);
   // seeds: into the caller's seeds_out when it is a device buffer (the loop then reads them there), else into the workspace,
   // where the loop runs in place
-  double* d_seeds = p->ms_q.f64();
-  if (devp && io->seeds_out) d_seeds = io->seeds_out;
-  double* const d_q_all = (devp && io->q_all) ? io->q_all : p->ms_q.f64();
-  int32_t* const d_status = (devp && io->status_all) ? io->status_all : p->ms_i32.i32();
-  int32_t* const d_iters = (devp && io->iters_all) ? io->iters_all : p->ms_i32.i32() + Nz;
-  int32_t* const d_conv = (devp && io->converged_all) ? io->converged_all : p->ms_i32.i32() + 2 * Nz;
-  HIP_OK(launch_ms_seed(stream, p->ms_seed_i.i32(), p->ms_seed_f.f64(), B, S, (int)nq, d_q, d_user, (unsigned long long)rng_seed,
-                        (long long)target_index0, d_seeds));
-  if (!devp && io->seeds_out) {       // (host caller: the seeds are set aside before the loop overwrites them in place)
-    HIP_OK(hipMemcpyAsync(p->ms_seeds.p, d_seeds, Nz * nq * f8, hipMemcpyDeviceToDevice, stream));
-  }
+  double* const d_seeds = (devp && io->seeds_out) ? io->seeds_out : c_q;
+  double* const d_q_all = (devp && io->q_all) ? io->q_all : c_q;
+  ST_LAUNCH(st, launch_ms_seed(stream, ws[WS_SEED_I].i32(), ws[WS_SEED_F].f64(), B, S, (int)nq, d_q, d_user,
+                               (unsigned long long)rng_seed, (long long)target_index0, d_seeds));
+  double* kept_seeds = nullptr;       // (host caller: the seeds are set aside before the loop overwrites them in place)
+  if (!devp && io->seeds_out && (kept_seeds = st.f64(WS_C_STARTS, Nz * nq)))
+    st.latch(hipMemcpyAsync(kept_seeds, d_seeds, Nz * nq * f8, hipMemcpyDeviceToDevice, stream));
   // ---- target fan-out: every per-instance target S times (the solve kernels index targets by instance)
-  HIP_OK(launch_ms_fanout(stream, d_ft, p->ms_ft.f64(), B, S, (int)ft_w));
-  if (pt_w && pbat) { HIP_OK(launch_ms_fanout(stream, d_pt, p->ms_pt.f64(), B, S, (int)pt_w)); d_pt = p->ms_pt.f64(); }
-  if (ct_w && cbat) { HIP_OK(launch_ms_fanout(stream, d_ct, p->ms_ct.f64(), B, S, (int)ct_w)); d_ct = p->ms_ct.f64(); }
+  auto fanout = [&](WsRole role, const double* src, size_t w) -> const double* {
+    double* const dst = st.f64(role, Nz * w);
+    ST_LAUNCH(st, launch_ms_fanout(stream, src, dst, B, S, (int)w));
+    return dst;
+  };
+  const double* const c_ft = fanout(WS_C_FT, d_ft, ft_w);
+  if (pt_w && pbat) d_pt = fanout(WS_C_PT, d_pt, pt_w);
+  if (ct_w && cbat) d_ct = fanout(WS_C_CT, d_ct, ct_w);
+  if (!st.ok()) return st.finish();
   // ---- the loop: mkh_solve_until's own path and dispatch on the B·S instances
   const int32_t loop_flags = (flags & ~MKH_FLAG_WARM_START) | MKH_FLAG_DEVICE_PTRS;
-  if (const int32_t rc = run(p, (int32_t)N, d_seeds, p->ms_ft.f64(), d_pt, d_ct, dt, damping, p->ms_v.f64(), d_status, nullptr,
-                             loop_flags, hip_stream, max_iters, d_q_all, nullptr, pos_threshold, ori_threshold, d_iters, d_conv))
-    return rc;
+  if (const int32_t rc = run(p, (int32_t)N, d_seeds, c_ft, d_pt, d_ct, dt, damping, c_v, d_status, nullptr, loop_flags, hip_stream,
+                             max_iters, d_q_all, nullptr, pos_threshold, ori_threshold, d_iters, d_conv))
+    return st.finish(rc);
   // ---- selection
   double *o_q = io->q_best, *o_v = io->v_best;
   int32_t *o_it = io->iters, *o_st = io->status, *o_cv = io->converged, *o_si = io->seed_index, *o_nc = io->n_converged;
   if (!devp) {
-    HIP_OK(p->ms_out_q.need(Bz * nq * f8));
-    HIP_OK(p->ms_out_v.need(Bz * nv * f8));
-    HIP_OK(p->ms_out_i32.need(5 * Bz * i4));
-    o_q = p->ms_out_q.f64(); o_v = p->ms_out_v.f64();
-    o_it = p->ms_out_i32.i32(); o_st = o_it + Bz; o_cv = o_it + 2 * Bz; o_si = o_it + 3 * Bz; o_nc = o_it + 4 * Bz;
+    o_q = st.f64(WS_OUT_Q, Bz * nq); o_v = st.f64(WS_OUT_V, Bz * nv);
+    o_it = st.i32(WS_OUT_I32, 3 * Bz); o_st = o_it + Bz; o_cv = o_it + 2 * Bz;
+    o_si = st.i32(WS_OUT_PICK, 2 * Bz); o_nc = o_si + Bz;
   }
-  HIP_OK(launch_ms_select(stream, B, S, (int)nq, (int)nv, p->model->njnt, p->ms_jnt.i32(), d_q_all, p->ms_v.f64(), d_status, d_iters,
-                          d_conv, d_ref ? d_ref : d_q, d_w, o_q, o_v, o_it, o_st, o_cv, o_si, o_nc));
-  if (devp) return MKH_OK;
-  auto down = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
-    return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream) : hipSuccess;
-  };
-  hipError_t e = down(io->q_best, o_q, Bz * nq * f8);
-  if (e == hipSuccess) e = down(io->v_best, o_v, Bz * nv * f8);
-  if (e == hipSuccess) e = down(io->iters, o_it, Bz * i4);
-  if (e == hipSuccess) e = down(io->status, o_st, Bz * i4);
-  if (e == hipSuccess) e = down(io->converged, o_cv, Bz * i4);
-  if (e == hipSuccess) e = down(io->seed_index, o_si, Bz * i4);
-  if (e == hipSuccess) e = down(io->n_converged, o_nc, Bz * i4);
-  if (e == hipSuccess) e = down(io->q_all, d_q_all, Nz * nq * f8);
-  if (e == hipSuccess) e = down(io->status_all, d_status, Nz * i4);
-  if (e == hipSuccess) e = down(io->iters_all, d_iters, Nz * i4);
-  if (e == hipSuccess) e = down(io->converged_all, d_conv, Nz * i4);
-  if (e == hipSuccess && io->seeds_out) e = down(io->seeds_out, p->ms_seeds.p, Nz * nq * f8);
-  const hipError_t e2 = hipStreamSynchronize(stream);       // (a failed call still drains what it started)
-  if (e == hipSuccess) e = e2;
-  if (e != hipSuccess) return fail(MKH_E_HIP, "multistart: %s", hipGetErrorString(e));
-  return MKH_OK;
+  ST_LAUNCH(st, launch_ms_select(stream, B, S, (int)nq, (int)nv, p->model->njnt, ws[WS_JNT].i32(), d_q_all, c_v, d_status, d_iters,
+                                 d_conv, d_ref ? d_ref : d_q, d_w, o_q, o_v, o_it, o_st, o_cv, o_si, o_nc));
+  if (devp) return st.finish();
+  st.down(io->q_best, o_q, Bz * nq * f8);
+  st.down(io->v_best, o_v, Bz * nv * f8);
+  st.down(io->iters, o_it, Bz * i4);
+  st.down(io->status, o_st, Bz * i4);
+  st.down(io->converged, o_cv, Bz * i4);
+  st.down(io->seed_index, o_si, Bz * i4);
+  st.down(io->n_converged, o_nc, Bz * i4);
+  st.down(io->q_all, d_q_all, Nz * nq * f8);
+  st.down(io->status_all, d_status, Nz * i4);
+  st.down(io->iters_all, d_iters, Nz * i4);
+  st.down(io->converged_all, d_conv, Nz * i4);
+  st.down(io->seeds_out, kept_seeds, Nz * nq * f8);
+  return st.finish();
 }
 
 }  // extern "C"
@@ -2464,21 +2474,14 @@ static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double
   }
   if (!p) return fail(MKH_E_INVALID, "null problem");
   const DeviceProblem& P = p->dev;
-  if (!q) return fail(MKH_E_INVALID, "q is null");
-  if (until && P.n_frame < 1)
-    return fail(MKH_E_INVALID, "%s needs at least one frame task to test the thresholds on", who);
-  if (P.n_frame > 0 && !frame_targets) return fail(MKH_E_INVALID, "frame_targets is null (TargetNotSet)");
-  if (P.n_posture > 0 && !posture_target) return fail(MKH_E_INVALID, "posture_target is null (TargetNotSet)");
-  if (P.n_com > 0 && !com_target) return fail(MKH_E_INVALID, "com_target is null (TargetNotSet)");
-  if (P.n_dense_rows || P.n_dense_limit_rows || P.dense_box)
-    return fail(MKH_E_INVALID, "dense (plugin) rows are evaluated by the caller at q: no fused loop, no trajectory");
+  if (const int32_t rc = refuse_inputs(P, q, frame_targets, posture_target, com_target, until ? who : nullptr, "trajectory"))
+    return rc;
   if (B > p->max_batch) return fail(MKH_E_INVALID, "B=%d exceeds max_batch=%d of this problem", B, p->max_batch);
   if (cs && (long long)B * cs->S > p->max_batch)
     return fail(MKH_E_INVALID, "B * n_seeds = %lld exceeds max_batch=%d of this problem", (long long)B * cs->S, p->max_batch);
   HIP_OK(hipSetDevice(p->model->device));
   if (cs || io->qvel || (kf && io->posture_per_waypoint && P.n_posture > 0))
     if (const int32_t rc = ms_build_tables(p)) return rc;
-  hipStream_t stream = (hipStream_t)hip_stream;
   const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0, tm = io->time_major != 0;
   const bool pbat = (flags & MKH_FLAG_POSTURE_BATCHED) != 0, cbat = (flags & MKH_FLAG_COM_BATCHED) != 0;
   const bool ptime = io->posture_per_waypoint != 0 && P.n_posture > 0, ctime = io->com_per_waypoint != 0 && P.n_com > 0;
@@ -2488,26 +2491,22 @@ static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double
   const int S = cs ? cs->S : 1;
   const size_t Rz = Bz * (size_t)S, NR = Tz * Rz;            // rows of a loop launch (the candidates, or the instances), of all T
   const size_t pt_n = pt_w * (pbat ? Bz : 1) * (ptime ? Kz : 1), ct_n = ct_w * (cbat ? Bz : 1) * (ctime ? Kz : 1);
+  Stager st{p, (hipStream_t)hip_stream, devp, who};
+  if (cs) st.cand_bytes = NR * ((nq + nv) * f8 + 3 * i4);
+  hipStream_t stream = st.stream;
+  GrowBuf* const ws = p->ws;
 
   // ---- inputs and the caller-layout outputs on the device
-  const double *d_q = q, *d_ft = frame_targets, *d_pt = posture_target, *d_ct = com_target;
+  const double* const d_q = st.up(WS_IN_Q, q, Bz * nq);
+  const double* d_ft = ft_w ? st.up(WS_IN_FT, frame_targets, Bz * Kz * ft_w) : frame_targets;
+  const double* d_pt = pt_w ? st.up(WS_IN_PT, posture_target, pt_n) : posture_target;
+  const double* d_ct = ct_w ? st.up(WS_IN_CT, com_target, ct_n) : com_target;
   double *o_q = io->q_traj, *o_v = io->v_traj, *o_qvel = io->qvel;
   int32_t *o_st = io->status, *o_it = io->iters, *o_cv = io->converged;
   if (!devp) {
-    auto up = [&](GrowBuf& g, const double* src, size_t n) -> hipError_t {
-      if (hipError_t e = g.need(n * f8)) return e;
-      return hipMemcpyAsync(g.p, src, n * f8, hipMemcpyHostToDevice, stream);
-    };
-    HIP_OK(p->tj_out_q.need(N * nq * f8));
-    HIP_OK(p->tj_out_v.need(N * nv * f8));
-    HIP_OK(p->tj_out_i32.need(3 * N * i4));
-    if (io->qvel) HIP_OK(p->tj_out_qvel.need(N * nv * f8));
-    HIP_OK(up(p->tj_in_q, q, Bz * nq)); d_q = p->tj_in_q.f64();
-    if (ft_w) { HIP_OK(up(p->tj_in_ft, frame_targets, Bz * Kz * ft_w)); d_ft = p->tj_in_ft.f64(); }
-    if (pt_w) { HIP_OK(up(p->tj_in_pt, posture_target, pt_n)); d_pt = p->tj_in_pt.f64(); }
-    if (ct_w) { HIP_OK(up(p->tj_in_ct, com_target, ct_n)); d_ct = p->tj_in_ct.f64(); }
-    o_q = p->tj_out_q.f64(); o_v = p->tj_out_v.f64(); o_qvel = io->qvel ? p->tj_out_qvel.f64() : nullptr;
-    o_st = p->tj_out_i32.i32();
+    o_q = st.f64(WS_OUT_Q, N * nq); o_v = st.f64(WS_OUT_V, N * nv);
+    o_qvel = io->qvel ? st.f64(WS_OUT_QVEL, N * nv) : nullptr;
+    o_st = st.i32(WS_OUT_I32, 3 * N);
     o_it = io->iters ? o_st + N : nullptr;
     o_cv = io->converged ? o_st + 2 * N : nullptr;
   }
@@ -2515,44 +2514,26 @@ static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double
   const double *d_user = nullptr, *d_w = nullptr;
   int32_t *o_si = nullptr, *o_nt = nullptr, *o_nc = nullptr;
   double* o_len = nullptr;
-  // a buffer of the candidates: a failed allocation drains what the call has enqueued and reports the size
-  auto tms_alloc = [&](GrowBuf& g, size_t bytes) -> bool {
-    if (g.need(bytes) == hipSuccess) return true;
-    (void)hipStreamSynchronize(stream);
-    (void)fail(MKH_E_HIP, "%s: no device memory for a buffer of %zu bytes (the candidates' results take T*B*S*((nq+nv)*8+12) = %zu bytes)",
-               who, bytes, NR * ((nq + nv) * f8 + 3 * i4));
-    return false;
-  };
   if (cs) {
-    d_user = cs->seeds; d_w = cs->weights;
+    d_user = st.up(WS_IN_SEEDS, cs->seeds, Rz * nq); d_w = st.up(WS_IN_W, cs->weights, nv);
     o_si = cs->seed_index; o_nt = cs->n_tracked; o_nc = cs->n_complete; o_len = cs->path_length;
     if (!devp) {
-      if (cs->seeds) {
-        if (!tms_alloc(p->tms_in_seeds, Rz * nq * f8)) return MKH_E_HIP;
-        HIP_OK(hipMemcpyAsync(p->tms_in_seeds.p, cs->seeds, Rz * nq * f8, hipMemcpyHostToDevice, stream));
-        d_user = p->tms_in_seeds.f64();
-      }
-      if (cs->weights) {
-        if (!tms_alloc(p->tms_in_w, nv * f8)) return MKH_E_HIP;
-        HIP_OK(hipMemcpyAsync(p->tms_in_w.p, cs->weights, nv * f8, hipMemcpyHostToDevice, stream));
-        d_w = p->tms_in_w.f64();
-      }
-      if (!tms_alloc(p->tms_out_i32, 3 * Bz * i4) || !tms_alloc(p->tms_out_len, Bz * f8)) return MKH_E_HIP;
-      o_si = p->tms_out_i32.i32(); o_nt = o_si + Bz; o_nc = o_si + 2 * Bz; o_len = p->tms_out_len.f64();
+      o_si = st.i32(WS_OUT_PICK, 3 * Bz); o_nt = o_si + Bz; o_nc = o_si + 2 * Bz;
+      o_len = st.f64(WS_OUT_LEN, Bz);
     }
   }
   // ---- keyframes: one slab per target group for all waypoints; the interpolated targets, where asked for, in the caller's layout
-  double *k_ft_out = nullptr, *k_pt_out = nullptr, *k_ct_out = nullptr;
+  double *k_ft = nullptr, *k_pt = nullptr, *k_ct = nullptr, *k_ft_out = nullptr, *k_pt_out = nullptr, *k_ct_out = nullptr;
   const size_t pt_rows = pbat ? Bz : 1, ct_rows = cbat ? Bz : 1;
   if (kf) {
     k_ft_out = ft_w ? kf->ft_out : nullptr; k_pt_out = ptime ? kf->pt_out : nullptr; k_ct_out = ctime ? kf->ct_out : nullptr;
-    if (ft_w) HIP_OK(p->kf_ft.need(Bz * ft_w * f8));
-    if (ptime) HIP_OK(p->kf_pt.need(pt_rows * pt_w * f8));
-    if (ctime) HIP_OK(p->kf_ct.need(ct_rows * ct_w * f8));
+    if (ft_w) k_ft = st.f64(WS_KF_FT, Bz * ft_w);
+    if (ptime) k_pt = st.f64(WS_KF_PT, pt_rows * pt_w);
+    if (ctime) k_ct = st.f64(WS_KF_CT, ct_rows * ct_w);
     if (!devp) {
-      if (k_ft_out) { HIP_OK(p->kf_out_ft.need(N * ft_w * f8)); k_ft_out = p->kf_out_ft.f64(); }
-      if (k_pt_out) { HIP_OK(p->kf_out_pt.need(Tz * pt_rows * pt_w * f8)); k_pt_out = p->kf_out_pt.f64(); }
-      if (k_ct_out) { HIP_OK(p->kf_out_ct.need(Tz * ct_rows * ct_w * f8)); k_ct_out = p->kf_out_ct.f64(); }
+      if (k_ft_out) k_ft_out = st.f64(WS_OUT_FT, N * ft_w);
+      if (k_pt_out) k_pt_out = st.f64(WS_OUT_PT, Tz * pt_rows * pt_w);
+      if (k_ct_out) k_ct_out = st.f64(WS_OUT_CT, Tz * ct_rows * ct_w);
     }
   }
   // ---- what the loops read and write: time-major slabs.  A time-major call: the caller's own arrays; a batch-major call:
@@ -2561,48 +2542,34 @@ static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double
   //      buffers, else the handle's workspace —, the starts sit beside them
   double *l_q = o_q, *l_v = o_v;
   int32_t *l_st = o_st, *l_it = o_it, *l_cv = o_cv;
-  double* d_seeds = nullptr;
+  double *d_seeds = nullptr, *c_ft = nullptr, *c_pt = nullptr, *c_ct = nullptr;
   if (cs) {
-    auto ws = [&](GrowBuf& g, size_t bytes, void* given) -> void* {
-      if (devp && given) return given;
-      return tms_alloc(g, bytes) ? g.p : nullptr;
-    };
-    if (!(l_q = (double*)ws(p->tms_q, NR * nq * f8, cs->q_all))) return MKH_E_HIP;
-    if (!(l_v = (double*)ws(p->tms_v, NR * nv * f8, cs->v_all))) return MKH_E_HIP;
-    if (!(l_st = (int32_t*)ws(p->tms_st, NR * i4, cs->status_all))) return MKH_E_HIP;
-    if (!(l_it = (int32_t*)ws(p->tms_it, NR * i4, cs->iters_all))) return MKH_E_HIP;
-    if (!(l_cv = (int32_t*)ws(p->tms_cv, NR * i4, cs->converged_all))) return MKH_E_HIP;
-    if (!(d_seeds = (double*)ws(p->tms_seeds, Rz * nq * f8, cs->seeds_out))) return MKH_E_HIP;
+    l_q = (double*)st.given_or(WS_C_Q, cs->q_all, NR * nq * f8);
+    l_v = (double*)st.given_or(WS_C_V, cs->v_all, NR * nv * f8);
+    l_st = (int32_t*)st.given_or(WS_C_ST, cs->status_all, NR * i4);
+    l_it = (int32_t*)st.given_or(WS_C_IT, cs->iters_all, NR * i4);
+    l_cv = (int32_t*)st.given_or(WS_C_CV, cs->converged_all, NR * i4);
+    d_seeds = (double*)st.given_or(WS_C_STARTS, cs->seeds_out, Rz * nq * f8);
     if (S > 1) {
-      if (ft_w && !tms_alloc(p->tms_ft, Rz * ft_w * f8)) return MKH_E_HIP;
-      if (pt_w && pbat && !tms_alloc(p->tms_pt, Rz * pt_w * f8)) return MKH_E_HIP;
-      if (ct_w && cbat && !tms_alloc(p->tms_ct, Rz * ct_w * f8)) return MKH_E_HIP;
+      if (ft_w) c_ft = st.f64(WS_C_FT, Rz * ft_w);
+      if (pt_w && pbat) c_pt = st.f64(WS_C_PT, Rz * pt_w);
+      if (ct_w && cbat) c_ct = st.f64(WS_C_CT, Rz * ct_w);
     }
   } else if (!tm) {
-    HIP_OK(p->tj_q.need(N * nq * f8));
-    HIP_OK(p->tj_v.need(N * nv * f8));
-    HIP_OK(p->tj_i32.need(3 * N * i4));
-    l_q = p->tj_q.f64(); l_v = p->tj_v.f64();
-    l_st = p->tj_i32.i32();
+    l_q = st.f64(WS_TM_Q, N * nq); l_v = st.f64(WS_TM_V, N * nv);
+    l_st = st.i32(WS_TM_I32, 3 * N);
     l_it = o_it ? l_st + N : nullptr;
     l_cv = o_cv ? l_st + 2 * N : nullptr;
   }
-  if (!tm) {
-    if (ft_w && !kf) {                // (keyframes are read in place through strides: no transposed copy)
-      HIP_OK(p->tj_ft.need(N * ft_w * f8));
-      HIP_OK(launch_tj_gather(stream, d_ft, p->tj_ft.f64(), B, T, (int)ft_w));
-      d_ft = p->tj_ft.f64();
-    }
-    if (ptime && pbat && !kf) {      // (a target without a B axis has its T axis in front already)
-      HIP_OK(p->tj_pt.need(N * pt_w * f8));
-      HIP_OK(launch_tj_gather(stream, d_pt, p->tj_pt.f64(), B, T, (int)pt_w));
-      d_pt = p->tj_pt.f64();
-    }
-    if (ctime && cbat && !kf) {
-      HIP_OK(p->tj_ct.need(N * ct_w * f8));
-      HIP_OK(launch_tj_gather(stream, d_ct, p->tj_ct.f64(), B, T, (int)ct_w));
-      d_ct = p->tj_ct.f64();
-    }
+  if (!tm && !kf) {                  // (keyframes are read in place through strides: no transposed copy)
+    auto time_major = [&](WsRole role, const double* src, size_t w) -> const double* {
+      double* const dst = st.f64(role, N * w);
+      ST_LAUNCH(st, launch_tj_gather(stream, src, dst, B, T, (int)w));
+      return dst;
+    };
+    if (ft_w) d_ft = time_major(WS_TM_FT, d_ft, ft_w);
+    if (ptime && pbat) d_pt = time_major(WS_TM_PT, d_pt, pt_w);      // (a target without a B axis has its T axis in front already)
+    if (ctime && cbat) d_ct = time_major(WS_TM_CT, d_ct, ct_w);
   }
   // ---- the waypoints: one loop launch each on the caller's stream, slab t - 1 → slab t, nothing in between
   const int32_t loop_flags = flags | MKH_FLAG_DEVICE_PTRS;
@@ -2616,19 +2583,12 @@ static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double
   auto out_st = [&](size_t rows, size_t w) { return tm ? rows * w : w; };
   if (cs) {
     // the starts (candidate 0: q[b] itself), and a batched target that is held: fanned out once, in front of waypoint 0
-    hipError_t ce = launch_ms_seed(stream, p->ms_seed_i.i32(), p->ms_seed_f.f64(), B, S, (int)nq, d_q, d_user,
-                                   (unsigned long long)cs->rng_seed, (long long)cs->target_index0, d_seeds);
-    if (ce == hipSuccess && S > 1 && pt_w && pbat && !ptime) {
-      ce = launch_ms_fanout(stream, d_pt, p->tms_pt.f64(), B, S, (int)pt_w);
-      d_pt = p->tms_pt.f64();
-    }
-    if (ce == hipSuccess && S > 1 && ct_w && cbat && !ctime) {
-      ce = launch_ms_fanout(stream, d_ct, p->tms_ct.f64(), B, S, (int)ct_w);
-      d_ct = p->tms_ct.f64();
-    }
-    if (ce != hipSuccess) { (void)hipStreamSynchronize(stream); return fail(MKH_E_HIP, "%s: %s", who, hipGetErrorString(ce)); }
+    ST_LAUNCH(st, launch_ms_seed(stream, ws[WS_SEED_I].i32(), ws[WS_SEED_F].f64(), B, S, (int)nq, d_q, d_user,
+                                 (unsigned long long)cs->rng_seed, (long long)cs->target_index0, d_seeds));
+    if (S > 1 && pt_w && pbat && !ptime) { ST_LAUNCH(st, launch_ms_fanout(stream, d_pt, c_pt, B, S, (int)pt_w)); d_pt = c_pt; }
+    if (S > 1 && ct_w && cbat && !ctime) { ST_LAUNCH(st, launch_ms_fanout(stream, d_ct, c_ct, B, S, (int)ct_w)); d_ct = c_ct; }
   }
-  for (size_t t = 0; t < Tz && rc == MKH_OK; ++t) {
+  for (size_t t = 0; t < Tz && rc == MKH_OK && st.ok(); ++t) {
     const double* const q_in = t ? l_q + (t - 1) * Rz * nq : (cs ? d_seeds : d_q);
     const double *t_ft = nullptr, *t_pt = d_pt, *t_ct = d_ct;       // (held targets: the same array for every waypoint)
     if (!kf) {
@@ -2638,111 +2598,87 @@ static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double
     } else {
       const int k = kf->seg_k[t];
       const double u = kf->seg_u[t];
-      hipError_t ke = hipSuccess;
       if (ft_w) {
-        ke = launch_kf_frames(stream, d_ft, key_sb(Bz, ft_w), key_sk(Bz, ft_w), k, u, B, P.n_frame, p->kf_ft.f64(),
-                              k_ft_out ? k_ft_out + t * out_st(Bz, ft_w) : nullptr, out_sb(Bz, ft_w));
-        t_ft = p->kf_ft.f64();
+        ST_LAUNCH(st, launch_kf_frames(stream, d_ft, key_sb(Bz, ft_w), key_sk(Bz, ft_w), k, u, B, P.n_frame, k_ft,
+                                       k_ft_out ? k_ft_out + t * out_st(Bz, ft_w) : nullptr, out_sb(Bz, ft_w)));
+        t_ft = k_ft;
       }
       if (ptime) {
-        if (ke == hipSuccess)
-          ke = launch_kf_posture(stream, p->ms_jnt.i32(), p->model->njnt, d_pt, key_sb(pt_rows, pt_w), key_sk(pt_rows, pt_w), k, u,
-                                 (int)pt_rows, P.n_posture, (int)nq, p->kf_pt.f64(),
-                                 k_pt_out ? k_pt_out + t * out_st(pt_rows, pt_w) : nullptr, out_sb(pt_rows, pt_w));
-        t_pt = p->kf_pt.f64();
+        ST_LAUNCH(st, launch_kf_posture(stream, ws[WS_JNT].i32(), p->model->njnt, d_pt, key_sb(pt_rows, pt_w), key_sk(pt_rows, pt_w),
+                                        k, u, (int)pt_rows, P.n_posture, (int)nq, k_pt,
+                                        k_pt_out ? k_pt_out + t * out_st(pt_rows, pt_w) : nullptr, out_sb(pt_rows, pt_w)));
+        t_pt = k_pt;
       }
       if (ctime) {
-        if (ke == hipSuccess)
-          ke = launch_kf_com(stream, d_ct, key_sb(ct_rows, ct_w), key_sk(ct_rows, ct_w), k, u, (int)ct_rows, (int)ct_w,
-                             p->kf_ct.f64(), k_ct_out ? k_ct_out + t * out_st(ct_rows, ct_w) : nullptr, out_sb(ct_rows, ct_w));
-        t_ct = p->kf_ct.f64();
+        ST_LAUNCH(st, launch_kf_com(stream, d_ct, key_sb(ct_rows, ct_w), key_sk(ct_rows, ct_w), k, u, (int)ct_rows, (int)ct_w, k_ct,
+                                    k_ct_out ? k_ct_out + t * out_st(ct_rows, ct_w) : nullptr, out_sb(ct_rows, ct_w)));
+        t_ct = k_ct;
       }
-      if (ke != hipSuccess) { rc = fail(MKH_E_HIP, "%s: %s", who, hipGetErrorString(ke)); break; }
     }
     if (cs && S > 1) {
       // waypoint t's (B, .) slabs repeated for the S candidates of every instance, into the ONE (B·S, .) slab of each group
-      hipError_t fe = hipSuccess;
-      if (ft_w) { fe = launch_ms_fanout(stream, t_ft, p->tms_ft.f64(), B, S, (int)ft_w); t_ft = p->tms_ft.f64(); }
-      if (ptime && pbat) {
-        if (fe == hipSuccess) fe = launch_ms_fanout(stream, t_pt, p->tms_pt.f64(), B, S, (int)pt_w);
-        t_pt = p->tms_pt.f64();
-      }
-      if (ctime && cbat) {
-        if (fe == hipSuccess) fe = launch_ms_fanout(stream, t_ct, p->tms_ct.f64(), B, S, (int)ct_w);
-        t_ct = p->tms_ct.f64();
-      }
-      if (fe != hipSuccess) { rc = fail(MKH_E_HIP, "%s: %s", who, hipGetErrorString(fe)); break; }
+      if (ft_w) { ST_LAUNCH(st, launch_ms_fanout(stream, t_ft, c_ft, B, S, (int)ft_w)); t_ft = c_ft; }
+      if (ptime && pbat) { ST_LAUNCH(st, launch_ms_fanout(stream, t_pt, c_pt, B, S, (int)pt_w)); t_pt = c_pt; }
+      if (ctime && cbat) { ST_LAUNCH(st, launch_ms_fanout(stream, t_ct, c_ct, B, S, (int)ct_w)); t_ct = c_ct; }
     }
+    if (!st.ok()) break;
     rc = run(p, (int32_t)Rz, q_in, t_ft, t_pt, t_ct, dt, damping, l_v + t * Rz * nv, l_st + t * Rz, nullptr, loop_flags, hip_stream,
              n_steps, l_q + t * Rz * nq, nullptr, until ? pos_threshold : -1.0, until ? ori_threshold : -1.0,
              l_it ? l_it + t * Rz : nullptr, l_cv ? l_cv + t * Rz : nullptr);
   }
-  if (rc != MKH_OK) {
-    (void)hipStreamSynchronize(stream);                       // (a failed call still drains what it started)
-    return rc;
-  }
-  hipError_t e = hipSuccess;
+  if (rc != MKH_OK || !st.ok()) return st.finish(rc);
+  // (instance, waypoint) strides in elements of an array of width w in the caller's layout
+  auto sb = [&](size_t w) { return (long long)(tm ? w : Tz * w); };
+  auto sw = [&](size_t w) { return (long long)(tm ? Bz * w : w); };
   if (cs) {
-    // the score over every candidate's path and the choice, then the chosen rows into the caller's layout: (instance,
-    // waypoint) strides in elements of an output of width w
-    auto sb = [&](size_t w) { return (long long)(tm ? w : Tz * w); };
-    auto st = [&](size_t w) { return (long long)(tm ? Bz * w : w); };
-    e = launch_tms_score(stream, B, S, T, (int)nq, p->model->njnt, p->ms_jnt.i32(), d_q, l_q, l_st, l_cv, d_w, o_si, o_nt, o_nc, o_len);
-    if (e == hipSuccess) e = launch_tms_gather(stream, l_q, o_q, o_si, B, S, T, (int)nq, sb(nq), st(nq));
-    if (e == hipSuccess) e = launch_tms_gather(stream, l_v, o_v, o_si, B, S, T, (int)nv, sb(nv), st(nv));
-    if (e == hipSuccess) e = launch_tms_gather_i32(stream, l_st, o_st, o_si, B, S, T, sb(1), st(1));
-    if (e == hipSuccess) e = launch_tms_gather_i32(stream, l_it, o_it, o_si, B, S, T, sb(1), st(1));
-    if (e == hipSuccess) e = launch_tms_gather_i32(stream, l_cv, o_cv, o_si, B, S, T, sb(1), st(1));
-    if (e == hipSuccess && o_qvel)
-      e = launch_tj_qvel(stream, p->ms_jnt.i32(), p->model->njnt, B, T, (int)nq, d_q, o_q, sb(nq), st(nq), io->waypoint_dt, o_qvel,
-                         sb(nv), st(nv), tm ? 1 : 0);
-  } else if (!tm) {
-    e = launch_tj_scatter(stream, l_q, o_q, B, T, (int)nq);
-    if (e == hipSuccess) e = launch_tj_scatter(stream, l_v, o_v, B, T, (int)nv);
-    if (e == hipSuccess) e = launch_tj_scatter_i32(stream, l_st, o_st, B, T);
-    if (e == hipSuccess && o_it) e = launch_tj_scatter_i32(stream, l_it, o_it, B, T);
-    if (e == hipSuccess && o_cv) e = launch_tj_scatter_i32(stream, l_cv, o_cv, B, T);
+    // the score over every candidate's path and the choice, then the chosen rows into the caller's layout
+    ST_LAUNCH(st, launch_tms_score(stream, B, S, T, (int)nq, p->model->njnt, ws[WS_JNT].i32(), d_q, l_q, l_st, l_cv, d_w, o_si, o_nt,
+                                   o_nc, o_len));
+    ST_LAUNCH(st, launch_tms_gather(stream, l_q, o_q, o_si, B, S, T, (int)nq, sb(nq), sw(nq)));
+    ST_LAUNCH(st, launch_tms_gather(stream, l_v, o_v, o_si, B, S, T, (int)nv, sb(nv), sw(nv)));
+    ST_LAUNCH(st, launch_tms_gather_i32(stream, l_st, o_st, o_si, B, S, T, sb(1), sw(1)));
+    ST_LAUNCH(st, launch_tms_gather_i32(stream, l_it, o_it, o_si, B, S, T, sb(1), sw(1)));
+    ST_LAUNCH(st, launch_tms_gather_i32(stream, l_cv, o_cv, o_si, B, S, T, sb(1), sw(1)));
+    if (o_qvel)
+      ST_LAUNCH(st, launch_tj_qvel(stream, ws[WS_JNT].i32(), p->model->njnt, B, T, (int)nq, d_q, o_q, sb(nq), sw(nq), io->waypoint_dt,
+                                   o_qvel, sb(nv), sw(nv), tm ? 1 : 0));
+  } else {
+    if (!tm) {
+      ST_LAUNCH(st, launch_tj_scatter(stream, l_q, o_q, B, T, (int)nq));
+      ST_LAUNCH(st, launch_tj_scatter(stream, l_v, o_v, B, T, (int)nv));
+      ST_LAUNCH(st, launch_tj_scatter_i32(stream, l_st, o_st, B, T));
+      if (o_it) ST_LAUNCH(st, launch_tj_scatter_i32(stream, l_it, o_it, B, T));
+      if (o_cv) ST_LAUNCH(st, launch_tj_scatter_i32(stream, l_cv, o_cv, B, T));
+    }
+    if (o_qvel)                      // (from the loops' time-major q, into the caller's layout)
+      ST_LAUNCH(st, launch_tj_qvel(stream, ws[WS_JNT].i32(), p->model->njnt, B, T, (int)nq, d_q, l_q, (long long)nq,
+                                   (long long)(Bz * nq), io->waypoint_dt, o_qvel, sb(nv), sw(nv), tm ? 1 : 0));
   }
-  if (e == hipSuccess && o_qvel && !cs) {
-    // (instance, waypoint) strides in elements: the loops' time-major q, the caller's layout for qvel
-    const long long v_sb = tm ? (long long)nv : (long long)(Tz * nv), v_st = tm ? (long long)(Bz * nv) : (long long)nv;
-    e = launch_tj_qvel(stream, p->ms_jnt.i32(), p->model->njnt, B, T, (int)nq, d_q, l_q, (long long)nq, (long long)(Bz * nq),
-                       io->waypoint_dt, o_qvel, v_sb, v_st, tm ? 1 : 0);
-  }
-  if (devp) {
-    if (e != hipSuccess) { (void)hipStreamSynchronize(stream); return fail(MKH_E_HIP, "%s: %s", who, hipGetErrorString(e)); }
-    return MKH_OK;
-  }
-  auto down = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
-    return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream) : hipSuccess;
-  };
-  if (e == hipSuccess) e = down(io->q_traj, o_q, N * nq * f8);
-  if (e == hipSuccess) e = down(io->v_traj, o_v, N * nv * f8);
-  if (e == hipSuccess) e = down(io->status, o_st, N * i4);
-  if (e == hipSuccess) e = down(io->iters, o_it, N * i4);
-  if (e == hipSuccess) e = down(io->converged, o_cv, N * i4);
-  if (e == hipSuccess) e = down(io->qvel, o_qvel, N * nv * f8);
+  if (devp) return st.finish();
+  st.down(io->q_traj, o_q, N * nq * f8);
+  st.down(io->v_traj, o_v, N * nv * f8);
+  st.down(io->status, o_st, N * i4);
+  st.down(io->iters, o_it, N * i4);
+  st.down(io->converged, o_cv, N * i4);
+  st.down(io->qvel, o_qvel, N * nv * f8);
   if (kf) {
-    if (e == hipSuccess) e = down(kf->ft_out, k_ft_out, N * ft_w * f8);
-    if (e == hipSuccess) e = down(kf->pt_out, k_pt_out, Tz * pt_rows * pt_w * f8);
-    if (e == hipSuccess) e = down(kf->ct_out, k_ct_out, Tz * ct_rows * ct_w * f8);
+    st.down(kf->ft_out, k_ft_out, N * ft_w * f8);
+    st.down(kf->pt_out, k_pt_out, Tz * pt_rows * pt_w * f8);
+    st.down(kf->ct_out, k_ct_out, Tz * ct_rows * ct_w * f8);
   }
   if (cs) {
-    if (e == hipSuccess) e = down(cs->seed_index, o_si, Bz * i4);
-    if (e == hipSuccess) e = down(cs->n_tracked, o_nt, Bz * i4);
-    if (e == hipSuccess) e = down(cs->n_complete, o_nc, Bz * i4);
-    if (e == hipSuccess) e = down(cs->path_length, o_len, Bz * f8);
-    if (e == hipSuccess) e = down(cs->seeds_out, d_seeds, Rz * nq * f8);
-    if (e == hipSuccess) e = down(cs->q_all, l_q, NR * nq * f8);
-    if (e == hipSuccess) e = down(cs->v_all, l_v, NR * nv * f8);
-    if (e == hipSuccess) e = down(cs->status_all, l_st, NR * i4);
-    if (e == hipSuccess) e = down(cs->iters_all, l_it, NR * i4);
-    if (e == hipSuccess) e = down(cs->converged_all, l_cv, NR * i4);
+    st.down(cs->seed_index, o_si, Bz * i4);
+    st.down(cs->n_tracked, o_nt, Bz * i4);
+    st.down(cs->n_complete, o_nc, Bz * i4);
+    st.down(cs->path_length, o_len, Bz * f8);
+    st.down(cs->seeds_out, d_seeds, Rz * nq * f8);
+    st.down(cs->q_all, l_q, NR * nq * f8);
+    st.down(cs->v_all, l_v, NR * nv * f8);
+    st.down(cs->status_all, l_st, NR * i4);
+    st.down(cs->iters_all, l_it, NR * i4);
+    st.down(cs->converged_all, l_cv, NR * i4);
   }
-  const hipError_t e2 = hipStreamSynchronize(stream);         // (a failed call still drains what it started)
-  if (e == hipSuccess) e = e2;
-  if (e != hipSuccess) return fail(MKH_E_HIP, "%s: %s", who, hipGetErrorString(e));
-  return MKH_OK;
+  return st.finish();
 }
 
 extern "C" {

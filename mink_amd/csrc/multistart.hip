@@ -1,11 +1,12 @@
 // Multi-start IK (mkh_solve_multistart, include/minkhip.h): the three small kernels around the fused loop — seeding,
-// target fan-out, selection — and their launchers (declared in minkhip.hip next to the other launchers).  The loop
+// target fan-out, selection — and their launchers (declared in outer_launch.h).  The loop
 // between them is mkh_solve_until's own launch: nothing here touches a solve kernel or its argument structs.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
 #include "lie_dev.h"
 #include "ms_distance.h"
+#include "outer_launch.h"
 #include "wave_ops.h"
 
 namespace mkh {
@@ -125,11 +126,9 @@ __global__ __launch_bounds__(64) void multistart_select_kernel(
 
 hipError_t launch_ms_seed(hipStream_t stream, const int32_t* seed_i, const double* seed_f, int B, int S, int nq, const double* q,
                           const double* user_seeds, unsigned long long rng_seed, long long target_index0, double* q_seeds) {
-  const long long total = (long long)B * S * nq;
-  const int block = 256;
-  const long long grid = (total + block - 1) / block;
-  if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(multistart_seed_kernel, dim3((unsigned)grid), dim3(block), 0, stream, seed_i, seed_f, B, S, nq, q, user_seeds,
+  unsigned grid;
+  if (!grid_1d((long long)B * S * nq, &grid)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(multistart_seed_kernel, dim3(grid), dim3(kOuterBlock), 0, stream, seed_i, seed_f, B, S, nq, q, user_seeds,
                      rng_seed, target_index0, q_seeds);
   return hipGetLastError();
 }
@@ -137,10 +136,9 @@ hipError_t launch_ms_seed(hipStream_t stream, const int32_t* seed_i, const doubl
 hipError_t launch_ms_fanout(hipStream_t stream, const double* src, double* dst, int B, int S, int width) {
   const long long total = (long long)B * S * width;
   if (total == 0) return hipSuccess;
-  const int block = 256;
-  const long long grid = (total + block - 1) / block;
-  if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(multistart_fanout_kernel, dim3((unsigned)grid), dim3(block), 0, stream, src, dst, total, S, width);
+  unsigned grid;
+  if (!grid_1d(total, &grid)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(multistart_fanout_kernel, dim3(grid), dim3(kOuterBlock), 0, stream, src, dst, total, S, width);
   return hipGetLastError();
 }
 

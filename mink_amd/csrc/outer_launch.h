@@ -1,0 +1,55 @@
+// Launchers of the small kernels around the loop launches of the outer-loop entry points (mkh_solve_multistart,
+// mkh_solve_trajectory, mkh_solve_keyframes, mkh_solve_trajectory_multistart): declared once, for the four files that define
+// them and for minkhip.hip, which calls them — a signature that drifts fails to compile in the file that drifted.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+namespace mkh {
+
+constexpr int kOuterBlock = 256;        // threads per block of every one-thread-per-element kernel of these files
+
+// Blocks of kOuterBlock threads that cover `total` elements; false when the grid would not fit (the launcher then reports
+// hipErrorInvalidValue).
+static inline bool grid_1d(long long total, unsigned* grid) {
+  const long long g = (total + kOuterBlock - 1) / kOuterBlock;
+  if (g > 0x7fffffffLL) return false;
+  *grid = (unsigned)g;
+  return true;
+}
+
+// multi-start IK (multistart.hip): seeding, target fan-out, selection — the kernels around the loop of mkh_solve_multistart
+hipError_t launch_ms_seed(hipStream_t stream, const int32_t* seed_i, const double* seed_f, int B, int S, int nq, const double* q,
+                          const double* user_seeds, unsigned long long rng_seed, long long target_index0, double* q_seeds);
+hipError_t launch_ms_fanout(hipStream_t stream, const double* src, double* dst, int B, int S, int width);
+hipError_t launch_ms_select(hipStream_t stream, int B, int S, int nq, int nv, int njnt, const int32_t* jnt, const double* q_all,
+                            const double* v_all, const int32_t* status_all, const int32_t* iters_all, const int32_t* converged_all,
+                            const double* q_ref, const double* weights, double* q_best, double* v_best, int32_t* iters,
+                            int32_t* status, int32_t* converged, int32_t* seed_index, int32_t* n_converged);
+// trajectory IK (trajectory.hip): (B, T, W) ↔ (T, B, W) transposes and the joint velocity between waypoints — the kernels
+// around the T loop launches of mkh_solve_trajectory
+hipError_t launch_tj_gather(hipStream_t stream, const double* src, double* dst, int B, int T, int W);
+hipError_t launch_tj_scatter(hipStream_t stream, const double* src, double* dst, int B, int T, int W);
+hipError_t launch_tj_scatter_i32(hipStream_t stream, const int32_t* src, int32_t* dst, int B, int T);
+hipError_t launch_tj_qvel(hipStream_t stream, const int32_t* jnt, int njnt, int B, int T, int nq, const double* q0,
+                          const double* q_traj, long long q_sb, long long q_st, double dt, double* qvel, long long v_sb,
+                          long long v_st, int time_major);
+// keyframed trajectory IK (keyframes.hip): waypoint t's targets blended from keyframes k and k + 1 at parameter u, read in place
+// through (instance, keyframe) strides, written to the loop's slab and (optionally) to waypoint t of the caller's *_targets_out
+hipError_t launch_kf_frames(hipStream_t stream, const double* keys, long long s_b, long long s_k, int k, double u, int rows,
+                            int n_frame, double* slab, double* out, long long o_sb);
+hipError_t launch_kf_posture(hipStream_t stream, const int32_t* jnt, int njnt, const double* keys, long long s_b, long long s_k,
+                             int k, double u, int rows, int n_posture, int nq, double* slab, double* out, long long o_sb);
+hipError_t launch_kf_com(hipStream_t stream, const double* keys, long long s_b, long long s_k, int k, double u, int rows,
+                         int width, double* slab, double* out, long long o_sb);
+// multi-start trajectory IK (trajectory_multistart.hip): every candidate scored over its path and one chosen per instance, the
+// chosen candidate's rows of the time-major (T, B·S, .) results gathered through the (instance, waypoint) strides of `out`
+hipError_t launch_tms_score(hipStream_t stream, int B, int S, int T, int nq, int njnt, const int32_t* jnt, const double* q0,
+                            const double* q_all, const int32_t* status_all, const int32_t* converged_all, const double* weights,
+                            int32_t* seed_index, int32_t* n_tracked, int32_t* n_complete, double* path_length);
+hipError_t launch_tms_gather(hipStream_t stream, const double* all, double* out, const int32_t* seed_index, int B, int S, int T,
+                             int W, long long o_sb, long long o_st);
+hipError_t launch_tms_gather_i32(hipStream_t stream, const int32_t* all, int32_t* out, const int32_t* seed_index, int B, int S,
+                                 int T, long long o_sb, long long o_st);
+
+}  // namespace mkh

@@ -1,12 +1,13 @@
 // Trajectory IK (mkh_solve_trajectory, include/minkhip.h): the small kernels around the T fused-loop launches — the
 // batch-major → time-major transpose of the targets, the transpose of the results back, the finite-difference joint
-// velocity between waypoints — and their launchers (declared in minkhip.hip next to the other launchers).  The loops
+// velocity between waypoints — and their launchers (declared in outer_launch.h).  The loops
 // between them are mkh_solve_until's / mkh_solve_steps' own launches: nothing here touches a solve kernel or its argument
 // structs.  All of them are bandwidth kernels: one thread per output element, consecutive threads store consecutive addresses.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
 #include "lie_dev.h"
+#include "outer_launch.h"
 
 namespace mkh {
 
@@ -81,19 +82,12 @@ __global__ __launch_bounds__(256) void trajectory_qvel_kernel(const int32_t* __r
   out[va] = dw.x / dt; out[va + 1] = dw.y / dt; out[va + 2] = dw.z / dt;
 }
 
-static bool tj_grid(long long total, int block, unsigned* grid) {
-  const long long g = (total + block - 1) / block;
-  if (g > 0x7fffffffLL) return false;
-  *grid = (unsigned)g;
-  return true;
-}
-
 hipError_t launch_tj_gather(hipStream_t stream, const double* src, double* dst, int B, int T, int W) {
   const long long total = (long long)B * T * W;
   if (total == 0) return hipSuccess;
   unsigned grid;
-  if (!tj_grid(total, 256, &grid)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(trajectory_gather_kernel, dim3(grid), dim3(256), 0, stream, src, dst, total, B, T, W);
+  if (!grid_1d(total, &grid)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(trajectory_gather_kernel, dim3(grid), dim3(kOuterBlock), 0, stream, src, dst, total, B, T, W);
   return hipGetLastError();
 }
 
@@ -101,8 +95,8 @@ hipError_t launch_tj_scatter(hipStream_t stream, const double* src, double* dst,
   const long long total = (long long)B * T * W;
   if (total == 0) return hipSuccess;
   unsigned grid;
-  if (!tj_grid(total, 256, &grid)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(trajectory_scatter_kernel, dim3(grid), dim3(256), 0, stream, src, dst, total, B, T, W);
+  if (!grid_1d(total, &grid)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(trajectory_scatter_kernel, dim3(grid), dim3(kOuterBlock), 0, stream, src, dst, total, B, T, W);
   return hipGetLastError();
 }
 
@@ -110,8 +104,8 @@ hipError_t launch_tj_scatter_i32(hipStream_t stream, const int32_t* src, int32_t
   const long long total = (long long)B * T;
   if (total == 0) return hipSuccess;
   unsigned grid;
-  if (!tj_grid(total, 256, &grid)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(trajectory_scatter_i32_kernel, dim3(grid), dim3(256), 0, stream, src, dst, total, B, T);
+  if (!grid_1d(total, &grid)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(trajectory_scatter_i32_kernel, dim3(grid), dim3(kOuterBlock), 0, stream, src, dst, total, B, T);
   return hipGetLastError();
 }
 
@@ -121,8 +115,8 @@ hipError_t launch_tj_qvel(hipStream_t stream, const int32_t* jnt, int njnt, int 
   const long long total = (long long)B * T * njnt;
   if (total == 0) return hipSuccess;
   unsigned grid;
-  if (!tj_grid(total, 256, &grid)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(trajectory_qvel_kernel, dim3(grid), dim3(256), 0, stream, jnt, njnt, B, T, nq, q0, q_traj, q_sb, q_st, dt,
+  if (!grid_1d(total, &grid)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(trajectory_qvel_kernel, dim3(grid), dim3(kOuterBlock), 0, stream, jnt, njnt, B, T, nq, q0, q_traj, q_sb, q_st, dt,
                      qvel, v_sb, v_st, time_major);
   return hipGetLastError();
 }

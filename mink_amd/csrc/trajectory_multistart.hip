@@ -1,13 +1,13 @@
 // Multi-start trajectory IK (mkh_solve_trajectory_multistart, include/minkhip.h "THE RULE"): the two kernels behind the T loop
 // launches of the B·S candidate trajectories — scoring every candidate over its whole path and choosing one per instance, then
-// gathering the chosen candidate's rows into the caller's arrays — and their launchers (declared in minkhip.hip next to the
-// other launchers).  In front of the loops sit multistart.hip's seeding and fan-out kernels, behind the gather trajectory.hip's
-// waypoint velocity.  The candidates' results are time-major: row t·(B·S) + b·S + s.  Nothing here touches a solve kernel.
+// gathering the chosen candidate's rows into the caller's arrays — and their launchers (declared in outer_launch.h).  In front
+// of the loops sit multistart.hip's seeding and fan-out kernels, behind the gather trajectory.hip's waypoint velocity.  The candidates' results are time-major: row t·(B·S) + b·S + s.  Nothing here touches a solve kernel.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
 #include "lie_dev.h"
 #include "ms_distance.h"
+#include "outer_launch.h"
 #include "wave_ops.h"
 
 namespace mkh {
@@ -102,20 +102,13 @@ hipError_t launch_tms_score(hipStream_t stream, int B, int S, int T, int nq, int
   return hipGetLastError();
 }
 
-static bool tms_grid(long long total, int block, unsigned* grid) {
-  const long long g = (total + block - 1) / block;
-  if (g > 0x7fffffffLL) return false;
-  *grid = (unsigned)g;
-  return true;
-}
-
 hipError_t launch_tms_gather(hipStream_t stream, const double* all, double* out, const int32_t* seed_index, int B, int S, int T,
                              int W, long long o_sb, long long o_st) {
   const long long total = (long long)B * T * W;
   if (total == 0) return hipSuccess;
   unsigned grid;
-  if (!tms_grid(total, 256, &grid)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(tms_gather_kernel, dim3(grid), dim3(256), 0, stream, all, out, seed_index, total, B, S, W, o_sb, o_st);
+  if (!grid_1d(total, &grid)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(tms_gather_kernel, dim3(grid), dim3(kOuterBlock), 0, stream, all, out, seed_index, total, B, S, W, o_sb, o_st);
   return hipGetLastError();
 }
 
@@ -124,8 +117,8 @@ hipError_t launch_tms_gather_i32(hipStream_t stream, const int32_t* all, int32_t
   const long long total = (long long)B * T;
   if (total == 0) return hipSuccess;
   unsigned grid;
-  if (!tms_grid(total, 256, &grid)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(tms_gather_i32_kernel, dim3(grid), dim3(256), 0, stream, all, out, seed_index, total, B, S, o_sb, o_st);
+  if (!grid_1d(total, &grid)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(tms_gather_i32_kernel, dim3(grid), dim3(kOuterBlock), 0, stream, all, out, seed_index, total, B, S, o_sb, o_st);
   return hipGetLastError();
 }
 

@@ -106,7 +106,9 @@ def _dense_inputs(configuration: Configuration, layout, dt: float):
 
 
 def _compile(configuration: Configuration, tasks: Sequence, limits: Optional[Sequence], batch: int,
-             dense_dt: float = 1.0):
+             dense_dt: float = 1.0, devices: Optional[Sequence[int]] = None):
+    """The cached handle of a call site for `batch` instances, and its layout.  `devices`: the devices to compile for (default:
+    the configuration's list) — more than one gives a ShardedProblem, `batch` split among them."""
     from .limits import ConfigurationLimit
     from .tasks import Task
 
@@ -117,7 +119,10 @@ def _compile(configuration: Configuration, tasks: Sequence, limits: Optional[Seq
     # Memo for control loops: the same task / limit objects with the same costs → the same handle and layout, without
     # rebuilding and hashing every descriptor (78 µs of a 185 µs G1 iteration; tools/bench_control_loop.py).
     fps = [x._fingerprint() for x in tasks] + [x._fingerprint() for x in limits]
-    memo_key = None if any(f is None for f in fps) else (tuple(fps), len(tasks), batch)
+    # (a device list of its own — an outer loop that uses fewer devices than the configuration lists — is a handle of its own)
+    devices = list(configuration.devices if devices is None else devices)
+    on = () if devices == configuration.devices else (tuple(devices),)
+    memo_key = None if any(f is None for f in fps) else (tuple(fps), len(tasks), batch) + on
     if memo_key is not None:
         hit = configuration._compile_memo.get(memo_key)
         if hit is not None and hit[0] in configuration._problems:
@@ -161,7 +166,7 @@ def _compile(configuration: Configuration, tasks: Sequence, limits: Optional[Seq
                 f"caller-defined limits ({names}) contribute {layout['dense_limit_rows']} general rows G·Δq ≤ h (rows with a "
                 f"single nonzero entry are folded into the per-dof box and do not count); at most {cap} half-space rows per "
                 f"instance, shared with collision contacts")
-    key = (_key(groups), batch, layout["dense_limit_rows"], layout.get("dense_box") is not None)
+    key = (_key(groups), batch, layout["dense_limit_rows"], layout.get("dense_box") is not None) + on
     cache = configuration._problems
     prob = cache.pop(key, None)
     if prob is None:
@@ -169,9 +174,9 @@ def _compile(configuration: Configuration, tasks: Sequence, limits: Optional[Seq
                       com_tasks=groups["com"], configuration_limits=groups["cfg"], velocity_limits=groups["vel"],
                       collision_limits=groups["col"], max_batch=batch, dense_tasks=groups["dense"],
                       dense_limit_rows=layout["dense_limit_rows"], dense_limit_box=layout.get("dense_box") is not None)
-        if len(configuration.devices) > 1 and batch >= len(configuration.devices):
+        if len(devices) > 1 and batch >= len(devices):
             from .distributed import ShardedProblem                  # one handle per listed device, rows split among them
-            prob = ShardedProblem(configuration.model, configuration.devices, **kwargs)
+            prob = ShardedProblem(configuration.model, devices, **kwargs)
         else:
             prob = nat.NativeProblem(configuration.native, **kwargs)
     cache[key] = prob                                               # (re)insert as most recently used
@@ -183,9 +188,6 @@ def _compile(configuration: Configuration, tasks: Sequence, limits: Optional[Seq
     for old in [k for k in cache if k not in pinned][:max(0, len(cache) - PROBLEM_CACHE_SIZE)]:
         cache.pop(old).close()
     layout["cache_key"] = key
-    layout["native_kwargs"] = dict(frame_tasks=groups["frame"], posture_tasks=groups["posture"], com_tasks=groups["com"],
-                                   configuration_limits=groups["cfg"], velocity_limits=groups["vel"],
-                                   collision_limits=groups["col"])      # (further handles of this call site: multi-start shards)
     if memo_key is not None:
         if len(configuration._compile_memo) >= 4 * PROBLEM_CACHE_SIZE:
             configuration._compile_memo.clear()
@@ -313,15 +315,9 @@ def solve_ik_steps(configuration: Configuration, tasks: Sequence, dt: float, n_s
     Robots of 17 … 32 dofs or links loop on the row kernel's two-row build, floating base included, where that measured faster
     than the wavefront kernel's loop (a ComTask or RelativeFrameTask, or no floating base), and where every free
     joint is on a task chain."""
-    until = None
-    if pos_threshold is not None or ori_threshold is not None:
-        until = (float(pos_threshold if pos_threshold is not None else np.inf),
-                 float(ori_threshold if ori_threshold is not None else np.inf))
+    until = _thresholds(pos_threshold, ori_threshold)
     prob, layout = _compile(configuration, tasks, limits, configuration.batch_size, dt)
-    if layout["dense"] or layout["dense_limits"]:
-        raise exceptions.TaskDefinitionError(
-            "solve_ik_steps fuses the outer loop on the device; caller-defined Task / Limit subclasses are evaluated on "
-            "the host at every step: call solve_ik + integrate_inplace in a loop instead")
+    _refuse_plugin_rows(layout, "solve_ik_steps")
     ft, pt, ct = _gather_targets(configuration, layout)
     res = prob.solve(configuration.q_batch, ft, pt, ct, dt, damping, n_steps=int(n_steps), until=until)
     q, v, status = res[:3]
@@ -346,6 +342,21 @@ def solve_ik_steps(configuration: Configuration, tasks: Sequence, dt: float, n_s
         return (configuration._unbatch(q), configuration._unbatch(v), configuration._unbatch(res[3]),
                 configuration._unbatch(res[4].astype(bool)))
     return configuration._unbatch(q), configuration._unbatch(v)
+
+
+def _thresholds(pos_threshold, ori_threshold):
+    """The (pos, ori) pair of a threshold-terminated loop, None when neither is given (one alone: the other never decides)."""
+    if pos_threshold is None and ori_threshold is None:
+        return None
+    return (float(pos_threshold if pos_threshold is not None else np.inf),
+            float(ori_threshold if ori_threshold is not None else np.inf))
+
+
+def _refuse_plugin_rows(layout, who: str) -> None:
+    if layout["dense"] or layout["dense_limits"]:
+        raise exceptions.TaskDefinitionError(
+            f"{who} fuses the outer loop on the device; caller-defined Task / Limit subclasses are evaluated on "
+            "the host at every step: call solve_ik + integrate_inplace in a loop instead")
 
 
 class MultistartResult(NamedTuple):
@@ -380,6 +391,61 @@ def _host_array(x, name: str):
         raise ValueError(f"{name} must be an array of numbers") from e
 
 
+def _optional_array(x, name: str, row: tuple, B: Optional[int] = None):
+    """An optional argument (seeds, reference, weights) on the host with its shape checked: `row`, or — given `B` — one row for
+    the whole batch or one per instance, returned as (B,) + row."""
+    x = _host_array(x, name)
+    if x is None:
+        return None
+    if B is None:
+        if x.shape != row:
+            raise ValueError(f"{name} must have shape {row}, got {x.shape}")
+    elif x.shape == row:
+        x = np.ascontiguousarray(np.broadcast_to(x, (B,) + row))
+    elif x.shape != (B,) + row:
+        raise ValueError(f"{name} must have shape {row} or {(B,) + row}, got {x.shape}")
+    return x
+
+
+def _compile_outer(configuration: Configuration, tasks, limits, dt: float, who: str, S: int, max_instances: int):
+    """The handle(s) of an outer-loop call with S loop rows per instance, and its plan: (handles, layout, chunk, n_dev).  The
+    instances are walked in chunks of `chunk` — as many as fit `max_instances` loop rows — and the configuration's first
+    `n_dev` devices share a chunk by instance: one NativeProblem, or the shards of a ShardedProblem, each sized for its share."""
+    B, devices = configuration.batch_size, configuration.devices
+    chunk = min(B, max(1, int(max_instances) // S))
+    n_dev = len(devices) if (len(devices) > 1 and chunk >= len(devices)) else 1
+    shard = -(-chunk // n_dev)
+    prob, layout = _compile(configuration, tasks, limits, n_dev * shard * S, dt, devices=devices[:n_dev])
+    _refuse_plugin_rows(layout, who)
+    return ([prob] if n_dev == 1 else prob.shards), layout, chunk, n_dev
+
+
+def _rows(x, held_ndim: int, lo: int, hi: int):
+    """Rows [lo, hi) of an optional per-instance array; one that is held for the batch (`held_ndim` axes) as it is."""
+    return None if x is None else (x if x.ndim == held_ndim else np.ascontiguousarray(x[lo:hi]))
+
+
+def _join(cls, parts):
+    """The jobs' results, concatenated by instance into one `cls` (a NamedTuple whose absent fields are None in every part)."""
+    return cls(*[None if parts[0][k] is None else np.concatenate([p[k] for p in parts], axis=0) for k in range(len(cls._fields))])
+
+
+def _status_epilogue(status: np.ndarray, who: str, outside: str, failed: str) -> None:
+    """What an outer-loop call reports from its (B,) or (B, T) status bits, as solve_ik_steps does: ONE warning for instances
+    that were outside their configuration limits at some step (`outside` names them), SolverError for a QP failure (`failed`:
+    the message, with {n} failures of {of}, the {first} index and its {status})."""
+    out = (status & nat.ST_OUTSIDE_LIMITS) != 0
+    if status.ndim == 2:
+        out = out.any(axis=1)
+    if out.any():
+        logging.warning(who + ": %d " + outside + " were outside their configuration limits at some fused step", int(out.sum()))
+    bad = np.argwhere((status & ~nat.ST_OUTSIDE_LIMITS) != 0)
+    if len(bad):
+        first = tuple(int(x) for x in bad[0])
+        raise exceptions.SolverError(failed.format(n=len(bad), of=status.size, first=first[0] if status.ndim == 1 else first,
+                                                   status=int(status[first])))
+
+
 def solve_ik_multistart(configuration: Configuration, tasks: Sequence, dt: float, n_seeds: int, max_iters: int,
                         pos_threshold: float, ori_threshold: float, solver: str = "mi355x", damping: float = 1e-12,
                         limits: Optional[Sequence] = None, rng_seed: int = 0, seeds=None, reference=None, weights=None,
@@ -409,57 +475,24 @@ def solve_ik_multistart(configuration: Configuration, tasks: Sequence, dt: float
     if int(max_instances) < 1:
         raise ValueError("max_instances must be >= 1")
     B, nq, nv = configuration.batch_size, configuration.nq, configuration.nv
-    seeds = _host_array(seeds, "seeds")
-    if seeds is not None:
-        if seeds.shape == (S, nq):
-            seeds = np.ascontiguousarray(np.broadcast_to(seeds, (B, S, nq)))
-        elif seeds.shape != (B, S, nq):
-            raise ValueError(f"seeds must have shape ({S}, {nq}) or ({B}, {S}, {nq}), got {seeds.shape}")
-    reference = _host_array(reference, "reference")
-    if reference is not None:
-        if reference.shape == (nq,):
-            reference = np.ascontiguousarray(np.broadcast_to(reference, (B, nq)))
-        elif reference.shape != (B, nq):
-            raise ValueError(f"reference must have shape ({nq},) or ({B}, {nq}), got {reference.shape}")
-    weights = _host_array(weights, "weights")
-    if weights is not None and weights.shape != (nv,):
-        raise ValueError(f"weights must have shape ({nv},), got {weights.shape}")
-    # targets per chunk: as many as fit max_instances; devices share a chunk by target
-    devices = configuration.devices
-    per_chunk = max(1, int(max_instances) // S)
-    n_dev = len(devices) if (len(devices) > 1 and min(B, per_chunk) >= len(devices)) else 1
-    chunk = min(B, per_chunk)
-    shard = -(-chunk // n_dev)
-    # one handle per shard, sized for its instances (the single-device handle lives in the configuration's cache)
-    prob, layout = _compile_single(configuration, tasks, limits, shard * S, dt)
-    if layout["dense"] or layout["dense_limits"]:
-        raise exceptions.TaskDefinitionError(
-            "solve_ik_multistart fuses the outer loop on the device; caller-defined Task / Limit subclasses are evaluated on "
-            "the host at every step: call solve_ik + integrate_inplace in a loop instead")
+    seeds = _optional_array(seeds, "seeds", (S, nq), B)
+    reference = _optional_array(reference, "reference", (nq,), B)
+    weights = _optional_array(weights, "weights", (nv,))
+    handles, layout, chunk, n_dev = _compile_outer(configuration, tasks, limits, dt, "solve_ik_multistart", S, max_instances)
     ft, pt, ct = _gather_targets(configuration, layout)
     q = configuration.q_batch
     kw = dict(n_seeds=S, max_iters=max_iters, pos_threshold=float(pos_threshold), ori_threshold=float(ori_threshold),
               rng_seed=int(rng_seed), return_all=bool(return_all))
 
-    def rows(x, per, lo, hi):
-        return None if x is None else (np.ascontiguousarray(x[lo:hi]) if x.ndim == per + 1 else x)
-
     def job(handle, lo, hi):
-        return handle.solve_multistart(q[lo:hi], rows(ft, 2, lo, hi), rows(pt, 2, lo, hi), rows(ct, 2, lo, hi), dt, damping,
-                                       target_index0=lo, seeds=rows(seeds, 2, lo, hi), reference=rows(reference, 1, lo, hi),
+        return handle.solve_multistart(q[lo:hi], _rows(ft, 2, lo, hi), _rows(pt, 2, lo, hi), _rows(ct, 2, lo, hi), dt, damping,
+                                       target_index0=lo, seeds=_rows(seeds, 2, lo, hi), reference=_rows(reference, 1, lo, hi),
                                        weights=weights, **kw)
 
-    parts = _chunks_and_shards(configuration, layout, prob, B, chunk, n_dev, shard * S, job)
-    res = MultistartResult(*[None if parts[0][k] is None else np.concatenate([p[k] for p in parts], axis=0)
-                             for k in range(len(MultistartResult._fields))])
-    status = res.status
-    if (status & nat.ST_OUTSIDE_LIMITS).any():
-        logging.warning("solve_ik_multistart: %d chosen instance(s) were outside their configuration limits at some fused step",
-                        int(((status & nat.ST_OUTSIDE_LIMITS) != 0).sum()))
-    bad = np.nonzero(status & ~nat.ST_OUTSIDE_LIMITS)[0]
-    if len(bad):
-        raise exceptions.SolverError(f"QP failed for the chosen seed of {len(bad)} of {len(status)} targets "
-                                     f"(first: index {int(bad[0])}, status {int(status[bad[0]])}); none of their seeds converged")
+    res = _join(MultistartResult, _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job))
+    _status_epilogue(res.status, "solve_ik_multistart", "chosen instance(s)",
+                     "QP failed for the chosen seed of {n} of {of} targets (first: index {first}, status {status}); "
+                     "none of their seeds converged")
     if update:
         configuration.update(res.q if configuration.batched else res.q[0])
     un = configuration._unbatch
@@ -585,53 +618,30 @@ def solve_ik_trajectory(configuration: Configuration, tasks: Sequence, dt: float
         seqs, L = _trajectory_targets(configuration, tasks, targets, axis="keyframes K")
         if L != len(kt):
             raise ValueError(f"targets have {L} keyframes, keyframe_times has {len(kt)}")
-    until = None
-    if pos_threshold is not None or ori_threshold is not None:
-        until = (float(pos_threshold if pos_threshold is not None else np.inf),
-                 float(ori_threshold if ori_threshold is not None else np.inf))
-        if until[0] < 0.0 or until[1] < 0.0:
-            raise ValueError("thresholds must be >= 0")
+    until = _thresholds(pos_threshold, ori_threshold)
+    if until is not None and (until[0] < 0.0 or until[1] < 0.0):
+        raise ValueError("thresholds must be >= 0")
     B = configuration.batch_size
-    devices = configuration.devices
-    chunk = min(B, int(max_instances))
-    n_dev = len(devices) if (len(devices) > 1 and chunk >= len(devices)) else 1
-    shard = -(-chunk // n_dev)
-    prob, layout = _compile_single(configuration, tasks, limits, shard, dt)
-    if layout["dense"] or layout["dense_limits"]:
-        raise exceptions.TaskDefinitionError(
-            "solve_ik_trajectory fuses the outer loop on the device; caller-defined Task / Limit subclasses are evaluated on "
-            "the host at every step: call solve_ik + integrate_inplace in a loop instead")
+    handles, layout, chunk, n_dev = _compile_outer(configuration, tasks, limits, dt, "solve_ik_trajectory", 1, max_instances)
     ft, pt, ct = _stacked_targets(configuration, layout, seqs, L)
     q = configuration.q_batch
 
-    def rows(x, held_ndim, lo, hi):
-        return None if x is None else (x if x.ndim == held_ndim else np.ascontiguousarray(x[lo:hi]))
-
     def job(handle, lo, hi):
+        args = (_rows(ft, 0, lo, hi), _rows(pt, 2, lo, hi), _rows(ct, 2, lo, hi), dt, damping)
         kw = dict(n_steps=n_steps, until=until, qvel_dt=waypoint_dt, warm_start=bool(warm_start))
         if kt is None:
-            return handle.solve_trajectory(q[lo:hi], rows(ft, 0, lo, hi), rows(pt, 2, lo, hi), rows(ct, 2, lo, hi), dt, damping, **kw)
-        return handle.solve_keyframes(q[lo:hi], kt, wt, rows(ft, 0, lo, hi), rows(pt, 2, lo, hi), rows(ct, 2, lo, hi), dt, damping,
-                                      return_targets=bool(return_targets), **kw)
+            return handle.solve_trajectory(q[lo:hi], *args, **kw)
+        return handle.solve_keyframes(q[lo:hi], kt, wt, *args, return_targets=bool(return_targets), **kw)
 
-    parts = _chunks_and_shards(configuration, layout, prob, B, chunk, n_dev, shard, job)
+    parts = _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job)
     paths = None
     if kt is not None:                                         # (parts: KeyframesOut — the trajectory and the interpolated targets)
         if return_targets:
             paths = [None if parts[0][k] is None else np.concatenate([p[k] for p in parts], axis=0) for k in (1, 2, 3)]
         parts = [p.trajectory for p in parts]
-    res = TrajectoryResult(*[None if parts[0][k] is None else np.concatenate([p[k] for p in parts], axis=0)
-                             for k in range(len(TrajectoryResult._fields))])
-    status = res.status
-    outside = ((status & nat.ST_OUTSIDE_LIMITS) != 0).any(axis=1)
-    if outside.any():
-        logging.warning("solve_ik_trajectory: %d instance(s) were outside their configuration limits at some fused step",
-                        int(outside.sum()))
-    bad = np.argwhere((status & ~nat.ST_OUTSIDE_LIMITS) != 0)
-    if len(bad):
-        b0, t0 = (int(x) for x in bad[0])
-        raise exceptions.SolverError(f"QP failed at {len(bad)} of {status.size} waypoints "
-                                     f"(first: (instance, waypoint) = ({b0}, {t0}), status {int(status[b0, t0])})")
+    res = _join(TrajectoryResult, parts)
+    _status_epilogue(res.status, "solve_ik_trajectory", "instance(s)",
+                     "QP failed at {n} of {of} waypoints (first: (instance, waypoint) = {first}, status {status})")
     if update:
         configuration.update(res.q[:, -1] if configuration.batched else res.q[0, -1])
     un = configuration._unbatch
@@ -707,39 +717,20 @@ def solve_ik_trajectory_multistart(configuration: Configuration, tasks: Sequence
         raise ValueError("thresholds must be >= 0: multi-start trajectories run in threshold mode only")
     B, nq, nv = configuration.batch_size, configuration.nq, configuration.nv
     seqs, T = _trajectory_targets(configuration, tasks, targets)
-    seeds = _host_array(seeds, "seeds")
-    if seeds is not None:
-        if seeds.shape == (S, nq):
-            seeds = np.ascontiguousarray(np.broadcast_to(seeds, (B, S, nq)))
-        elif seeds.shape != (B, S, nq):
-            raise ValueError(f"seeds must have shape ({S}, {nq}) or ({B}, {S}, {nq}), got {seeds.shape}")
-    weights = _host_array(weights, "weights")
-    if weights is not None and weights.shape != (nv,):
-        raise ValueError(f"weights must have shape ({nv},), got {weights.shape}")
+    seeds = _optional_array(seeds, "seeds", (S, nq), B)
+    weights = _optional_array(weights, "weights", (nv,))
     if weights is not None and not (weights >= 0.0).all():
         raise ValueError("weights must be >= 0 (no NaN): the path length is a sum of non-negative terms")
-    # instances per chunk: as many as fit max_instances with their S candidates; devices share a chunk by instance
-    devices = configuration.devices
-    per_chunk = max(1, int(max_instances) // S)
-    n_dev = len(devices) if (len(devices) > 1 and min(B, per_chunk) >= len(devices)) else 1
-    chunk = min(B, per_chunk)
-    shard = -(-chunk // n_dev)
-    prob, layout = _compile_single(configuration, tasks, limits, shard * S, dt)
-    if layout["dense"] or layout["dense_limits"]:
-        raise exceptions.TaskDefinitionError(
-            "solve_ik_trajectory_multistart fuses the outer loop on the device; caller-defined Task / Limit subclasses are "
-            "evaluated on the host at every step: call solve_ik + integrate_inplace in a loop instead")
+    handles, layout, chunk, n_dev = _compile_outer(configuration, tasks, limits, dt, "solve_ik_trajectory_multistart", S,
+                                                   max_instances)
     ft, pt, ct = _stacked_targets(configuration, layout, seqs, T)
     q = configuration.q_batch
     kw = dict(n_seeds=S, n_steps=n_steps, pos_threshold=float(pos_threshold), ori_threshold=float(ori_threshold),
               rng_seed=int(rng_seed), weights=weights, qvel_dt=waypoint_dt, warm_start=bool(warm_start), return_all=bool(return_all))
 
-    def rows(x, held_ndim, lo, hi):
-        return None if x is None else (x if x.ndim == held_ndim else np.ascontiguousarray(x[lo:hi]))
-
     def job(handle, lo, hi):
-        out = handle.solve_trajectory_multistart(q[lo:hi], rows(ft, 0, lo, hi), rows(pt, 2, lo, hi), rows(ct, 2, lo, hi), dt, damping,
-                                                 target_index0=lo, seeds=rows(seeds, 0, lo, hi), **kw)
+        out = handle.solve_trajectory_multistart(q[lo:hi], _rows(ft, 0, lo, hi), _rows(pt, 2, lo, hi), _rows(ct, 2, lo, hi), dt,
+                                                 damping, target_index0=lo, seeds=_rows(seeds, 0, lo, hi), **kw)
         if not return_all:
             return out
         # every candidate's results, time-major (T, n·S, ·) → (n, S, T, ·), so that chunks and shards concatenate by instance
@@ -749,19 +740,10 @@ def solve_ik_trajectory_multistart(configuration: Configuration, tasks: Sequence
                             iters_all=by_inst(out.iters_all), converged_all=by_inst(out.converged_all),
                             seeds=out.seeds.reshape(n, S, nq))
 
-    parts = _chunks_and_shards(configuration, layout, prob, B, chunk, n_dev, shard * S, job)
-    res = TrajectoryMultistartResult(*[None if parts[0][k] is None else np.concatenate([p[k] for p in parts], axis=0)
-                                       for k in range(len(TrajectoryMultistartResult._fields))])
-    status = res.status
-    outside = ((status & nat.ST_OUTSIDE_LIMITS) != 0).any(axis=1)
-    if outside.any():
-        logging.warning("solve_ik_trajectory_multistart: %d chosen trajectorie(s) were outside their configuration limits at some "
-                        "fused step", int(outside.sum()))
-    bad = np.argwhere((status & ~nat.ST_OUTSIDE_LIMITS) != 0)
-    if len(bad):
-        b0, t0 = (int(x) for x in bad[0])
-        raise exceptions.SolverError(f"QP failed at {len(bad)} of {status.size} waypoints of the chosen candidates "
-                                     f"(first: (instance, waypoint) = ({b0}, {t0}), status {int(status[b0, t0])})")
+    res = _join(TrajectoryMultistartResult, _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job))
+    _status_epilogue(res.status, "solve_ik_trajectory_multistart", "chosen trajectorie(s)",
+                     "QP failed at {n} of {of} waypoints of the chosen candidates (first: (instance, waypoint) = {first}, "
+                     "status {status})")
     if update:
         configuration.update(res.q[:, -1] if configuration.batched else res.q[0, -1])
     un = configuration._unbatch
@@ -772,17 +754,13 @@ def solve_ik_trajectory_multistart(configuration: Configuration, tasks: Sequence
                                       opt(res.converged_all, True), opt(res.seeds))
 
 
-def _chunks_and_shards(configuration: Configuration, layout, prob, B: int, chunk: int, n_dev: int, max_batch: int, job):
-    """[job(handle, lo, hi), ...] over the rows [0, B): chunks of `chunk` rows, each split among `n_dev` handles (one per listed
-    device, `max_batch` instances each) that run side by side.  The one driver of solve_ik_multistart, solve_ik_trajectory and
-    solve_ik_trajectory_multistart: a job is told its global row offset `lo`, so results do not depend on chunks or shards.
-    (A ShardedProblem cached by solve_ik_steps for the same tasks and batch size cannot serve: it splits rows without telling a
-    shard its global offset — every handle but the cached single-device one is built here.)"""
-    devices = configuration.devices
+def _chunks_and_shards(configuration: Configuration, layout, handles, B: int, chunk: int, n_dev: int, job):
+    """[job(handle, lo, hi), ...] over the rows [0, B): chunks of `chunk` rows, each split among the `n_dev` handles of
+    _compile_outer, which run side by side.  The one driver of solve_ik_multistart, solve_ik_trajectory and
+    solve_ik_trajectory_multistart: a job is told its global row offset `lo`, so results do not depend on chunks or shards
+    (ShardedProblem.solve splits rows without telling a shard its offset: its shards are driven from here instead)."""
     parts = []
     with _pin(configuration, layout):
-        first = [prob] if isinstance(prob, nat.NativeProblem) else []
-        handles = first if (n_dev == 1 and first) else _multistart_shards(configuration, layout, first, devices[:n_dev], max_batch)
         for c0 in range(0, B, chunk):
             c1 = min(B, c0 + chunk)
             bounds = [(c0 + lo, c0 + hi) for lo, hi in (shard_bounds(c1 - c0, n_dev, r) for r in range(n_dev))]
@@ -794,32 +772,3 @@ def _chunks_and_shards(configuration: Configuration, layout, prob, B: int, chunk
                 with ThreadPoolExecutor(max_workers=len(bounds)) as pool:      # (a libminkhip call releases the GIL)
                     parts += [f.result() for f in [pool.submit(job, h, lo, hi) for h, (lo, hi) in zip(handles, bounds)]]
     return parts
-
-
-def _compile_single(configuration: Configuration, tasks, limits, batch: int, dt: float):
-    """_compile for ONE device whatever the configuration's device list says (multi-start shards by target itself: every shard
-    has to know its global target offset, which ShardedProblem's row split does not pass on)."""
-    devices = configuration.devices
-    configuration.devices = devices[:1]
-    try:
-        return _compile(configuration, tasks, limits, batch, dt)
-    finally:
-        configuration.devices = devices
-
-
-def _multistart_shards(configuration: Configuration, layout, first, devices, max_batch: int):
-    """One handle per listed device for a multi-start call (a device may be listed more than once: problem handles of one
-    model are independent).  `first` holds the cached single-device handle (or nothing); the others are built from the same
-    descriptors and kept on the configuration until the call site or the shard size changes."""
-    from .configuration import native_model
-
-    key = (layout["cache_key"], tuple(devices), max_batch, len(first))
-    held = configuration._multistart_shards
-    if held.get("key") != key:
-        for h in held.get("handles", []):
-            h.close()
-        held.clear()
-        held["key"] = key
-        held["handles"] = [nat.NativeProblem(native_model(configuration.model, d), max_batch=max_batch, **layout["native_kwargs"])
-                           for d in devices[len(first):]]
-    return list(first) + held["handles"]

@@ -256,7 +256,7 @@ def test_result_does_not_depend_on_chunks_shards_or_array_kind(nat):
     same(chunked, "max_instances=1024")
     _, cfg_s, tasks_s, lims_s, _ = _far_ur5e(B, device=[0, 0])
     sharded = mink.solve_ik_multistart(cfg_s, tasks_s, 1.0, S, 40, 1e-4, 1e-4, limits=lims_s, **_KW)
-    shards = [list(cfg_s._problems.values())[-1]] + cfg_s._multistart_shards["handles"]
+    shards = list(cfg_s._problems.values())[-1].shards            # (the cached ShardedProblem's handles, one per listed device)
     assert len(shards) == 2 and all(p.max_batch == 2048 and p.last_kernel() == k for p in shards)
     same(sharded, "device=[0, 0]")
     # numpy against torch inputs, one level down (a Configuration holds its q on the host)

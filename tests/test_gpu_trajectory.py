@@ -319,7 +319,7 @@ def test_result_does_not_depend_on_chunks_or_shards(nat):
     assert prob_c.max_batch == 64 and prob_c.last_kernel() == k
     _same(chunked, whole, "max_instances=64")
     cfg_s, sharded = run(device=[0, 0])
-    shards = [list(cfg_s._problems.values())[-1]] + cfg_s._multistart_shards["handles"]
+    shards = list(cfg_s._problems.values())[-1].shards            # (the cached ShardedProblem's handles, one per listed device)
     assert len(shards) == 2 and all(p.max_batch == 128 and p.last_kernel() == k for p in shards)
     _same(sharded, whole, "device=[0, 0]")
 

@@ -382,7 +382,7 @@ def test_result_does_not_depend_on_chunks_or_shards(nat):
     assert prob_c.max_batch == 4 * _S5 and prob_c.last_kernel() == k
     same(chunked, "max_instances")
     cfg_s, sharded = run(device=[0, 0])
-    shards = [list(cfg_s._problems.values())[-1]] + cfg_s._multistart_shards["handles"]
+    shards = list(cfg_s._problems.values())[-1].shards            # (the cached ShardedProblem's handles, one per listed device)
     assert len(shards) == 2 and all(p.max_batch == 8 * _S5 and p.last_kernel() == k for p in shards)
     same(sharded, "device=[0, 0]")
 
@@ -461,3 +461,83 @@ def test_public_api(nat):
     rc = L.mkh_solve_trajectory_multistart(prob.handle, B, T, S + 1, buf.ctypes.data, buf.ctypes.data, None, None, 1.0, 1e-3, 5, 1e-4, 1e-4,
                                            0, 0, ctypes.byref(io), 0, None)
     assert rc == -1 and b"B * n_seeds" in L.mkh_last_error() and b"exceeds max_batch" in L.mkh_last_error()
+
+
+# ------------------------------------------------------------------ 8. one handle, every outer loop
+def _flat(out, prefix=""):
+    """{field: numpy array} of a result, the trajectory inside a KeyframesOut included; fields that are None left out."""
+    fields = {}
+    for f, x in zip(out._fields, out):
+        if hasattr(x, "_fields"):
+            fields.update(_flat(x, prefix + f + "."))
+        elif x is not None:
+            fields[prefix + f] = _np(x)
+    return fields
+
+
+@pytest.mark.parametrize("name", ["ur5e_c2", "h1_full"])
+def test_one_handle_serves_every_outer_loop_in_any_order(nat, name):
+    """The four outer-loop entry points share one workspace per handle, by role.  ONE handle runs them interleaved, at changing
+    sizes and with host and device arrays; every field of every call equals — bit for bit — the same call on a fresh handle of
+    its own.  h1_full has per-instance, per-waypoint CoM targets: the CoM slabs are in use."""
+    import torch
+    w = _workload(nat, name)
+    B, T, S, m = w.B, w.T, w.S, w.m
+    rng = np.random.default_rng(21)
+    seeds = rng.uniform(-1.0, 1.0, size=(B, S, m.nq))
+    if m.nq != m.nv:                                                        # (a floating base: keep the caller's, as the seeder does)
+        seeds[:, :, :7] = w.q[:, None, :7]
+    reference = w.q + 0.05 * rng.standard_normal(w.q.shape)
+    weights = rng.uniform(0.5, 2.0, size=m.nv)
+    first = lambda x: None if x is None else np.ascontiguousarray(x[:, 0])  # waypoint 0's targets: a multi-start call's
+    keys = lambda x: None if x is None else np.ascontiguousarray(x[:, :3])  # waypoints 0..2 as K = 3 keyframes
+    kt, wt = np.array([0.0, 1.0, 2.0]), np.linspace(0.0, 2.0, T + 1)
+    thr = dict(pos_threshold=w.until[0], ori_threshold=w.until[1])
+    ms = dict(max_iters=w.iters, return_all=True, **thr)
+    dev = torch.device("cuda:0")
+    on = lambda x: x if not isinstance(x, np.ndarray) else torch.as_tensor(np.ascontiguousarray(x), device=dev)
+
+    # (method, positional arrays, keywords) of calls 1 … 6; 5 is two calls, 6 is 1 again
+    tms = ("solve_trajectory_multistart", (w.q, w.tg, w.pt, w.ct), dict(return_all=True, qvel_dt=0.05, rng_seed=4, **_kw(w)))
+    calls = [tms,
+             ("solve_multistart", (w.q, first(w.tg), w.pt, first(w.ct)),
+              dict(n_seeds=S, seeds=seeds, reference=reference, weights=weights, **ms)),
+             ("solve_keyframes", (w.q, kt, wt, keys(w.tg), w.pt, keys(w.ct)), dict(n_steps=w.iters, until=w.until, return_targets=True)),
+             ("solve_trajectory", (w.q, w.tg, w.pt, w.ct), dict(n_steps=w.iters, until=w.until, qvel_dt=0.02)),
+             ("solve_multistart", (w.q, first(w.tg), w.pt, first(w.ct)), dict(n_seeds=2, rng_seed=11, **ms)),
+             ("solve_multistart", (w.q, first(w.tg), w.pt, first(w.ct)), dict(n_seeds=S, rng_seed=11, **ms)),
+             tms]
+    number = (1, 2, 3, 4, 5, 5, 6)
+
+    def call(prob, method, args, kw, device):
+        if device:
+            args, kw = tuple(on(x) for x in args), {k: on(v) for k, v in kw.items()}
+        return _flat(getattr(prob, method)(*args, w.dt, w.damping, **kw))
+
+    def fresh(method, args, kw, device):
+        prob, _, _ = workloads.bench_config(name, m, w.nm, B * S)
+        try:
+            return call(prob, method, args, kw, device)
+        finally:
+            prob.close()
+
+    want = {}                                                               # (index of the call, device arrays) → its fields
+    for torch_evens in (False, True):
+        prob, _, _ = workloads.bench_config(name, m, w.nm, B * S)
+        assert prob.max_batch == B * S
+        try:
+            got = []
+            for i, (method, args, kw) in enumerate(calls):
+                device = torch_evens and number[i] % 2 == 0
+                if (i, device) not in want:
+                    want[i, device] = fresh(method, args, kw, device)
+                got.append(call(prob, method, args, kw, device))
+                what = f"{name}, call {number[i]} ({method}{', torch' if device else ''})"
+                assert set(got[-1]) == set(want[i, device]), what
+                for f, x in got[-1].items():
+                    np.testing.assert_array_equal(x, want[i, device][f], err_msg=f"{what}: {f}")
+            assert set(got[6]) == set(got[0])
+            for f, x in got[6].items():
+                np.testing.assert_array_equal(x, got[0][f], err_msg=f"{name}: call 6 against call 1: {f}")
+        finally:
+            prob.close()
