@@ -10,6 +10,12 @@ UR5e, one FrameTask on `attachment_site` (costs 1 / 1, lm_damping 1), Configurat
 (clipped to ±π), every loop starts at `home`.  Printed: how many targets converge from the single start (`solve_ik_steps`)
 and from `--seeds` starts (seed 0 is the single start, so multi-start never converges fewer), and how far the chosen
 solutions are from `home` next to the first converged seed's.
+
+    python examples/batched_global_ik_ur5e.py --targets 256 --seeds 4 --seed-table 4096
+
+`--seed-table N` also builds a `SeedTable` of N postures drawn around `home`, keyed on the site pose each one reaches, and
+solves once more with seeds 1 … S − 1 taken from the table's entries nearest to each target: converged counts for random and
+for table seeds at the same S.
 """
 import argparse
 import os
@@ -28,6 +34,7 @@ def main():
     ap.add_argument("--seeds", type=int, default=16)
     ap.add_argument("--max-iters", type=int, default=40)
     ap.add_argument("--rng-seed", type=int, default=0)
+    ap.add_argument("--seed-table", type=int, default=0, metavar="N", help="also solve with seeds from a table of N stored postures")
     args = ap.parse_args()
     B, S = args.targets, args.seeds
     rng = np.random.default_rng(20261016)
@@ -54,6 +61,16 @@ def main():
     print(f"  single start : {int(single.sum()):6d} of {B} converged")
     print(f"  {S:3d} starts   : {int(res.converged.sum()):6d} of {B} converged   ({1e3 * (t1 - t0):.2f} ms, numpy in and out)")
     assert res.converged[single].all()
+    if args.seed_table:
+        table = mink.SeedTable(mink.Configuration(model, home), tasks, args.seed_table, limits=limits, rng_seed=11)
+        near = mink.solve_ik_multistart(configuration, tasks, dt, S, args.max_iters, pos_thr, ori_thr, damping=damping,
+                                        limits=limits, update=False, seed_table=table)
+        index, distance, _ = table.query(end_effector.transform_target_to_world.wxyz_xyz, max(1, S - 1))
+        print(f"  {S:3d} starts, seeds 1 … {S - 1} the nearest of {args.seed_table} stored postures: {int(near.converged.sum()):6d} of {B} "
+              f"converged (random seeds: {int(res.converged.sum())}); median distance of the nearest entry "
+              f"{np.median(distance[:, 0]):.3f} (m² + rad²)")
+        assert near.converged[single].all()
+        table.close()
     # the selection: closest to `home` among the converged seeds, against taking the first one that converged
     ok = res.converged_all & ((res.status_all & ~1) == 0)
     many = np.flatnonzero(ok.sum(axis=1) > 1)

@@ -117,6 +117,7 @@ extern "C" {
 
 typedef struct MkhModel MkhModel;
 typedef struct MkhProblem MkhProblem;
+typedef struct MkhSeedTable MkhSeedTable;   /* "Seed tables" below */
 
 /*
  * One-time flattened copy of the mjModel kinematic tree: the mjModel fields the
@@ -642,6 +643,61 @@ int32_t mkh_solve_trajectory_multistart(MkhProblem *problem, int32_t B, int32_t 
                                         double dt, double damping, int32_t n_steps, double pos_threshold, double ori_threshold,
                                         uint64_t rng_seed, int64_t target_index0, const MkhTrajectoryMultistartIO *io,
                                         int32_t flags, void *hip_stream);
+
+/*
+ * Seed tables: multi-start seeded from the nearest stored postures.  The drawn starts of mkh_solve_multistart and
+ * mkh_solve_trajectory_multistart are blind to the target; a seed table holds N postures keyed on the world poses their
+ * frame-task frames reach, and a query returns, per target, the K stored postures whose poses are nearest — the way planners
+ * start IK from a database.  A table is device memory of its own: it outlives the problem that made it and may be attached to
+ * any problem of the same model, device and number of frame tasks, by several handles and threads at once (it is read-only
+ * after mkh_seed_table_create).  No counterpart in the reference.
+ *
+ * Entries.  q_tab (N, nq).  Drawn (entries == NULL): entry j is row s = 1 of multi-start's seeding rule above at
+ * (rng_seed, t = j, s = 1) around the one configuration q0 (nq,) — the same kernel, the same generator.  Free joints and
+ * unlimited slides keep q0's value: the table of a floating-base robot belongs to q0's base pose.  Caller's entries: the
+ * (N, nq) array as given (solutions of earlier calls, a teach-in set); q0 may then be NULL.
+ *
+ * Keys.  The world poses (wxyz, xyz) of the problem's n_frame frame-task frames at every entry: the frame_pose tap of mkh_eval
+ * on the entries, evaluated in chunks of the problem's max_batch — a key is bitwise what mkh_eval says about that entry.
+ * mkh_seed_table_read returns them as (N, n_frame, 7).
+ *
+ * Metric between a target T (n_frame, 7) and entry e, every product and sum rounded on its own (no fused multiply-add), in
+ * this order:
+ *   d = sum over f ascending, from 0, of ( wp_f * ((dx*dx + dy*dy) + dz*dz)  +  wo_f * max(0, 4 * (1 - c*c)) )
+ *   (dx, dy, dz) = position of e's frame f - position of T's,  c = (((w w' + x x') + y y') + z z') / sqrt(n_T * n_e),
+ *   n = ((w w + x x) + y y) + z z of either quaternion.
+ * The orientation term is 4 sin^2(theta / 2) of the angle between the two rotations — theta^2 for small angles — and does not
+ * change with the sign or the scale of either quaternion.  A d that is not finite (a NaN in the target: the max() keeps it)
+ * counts as DBL_MAX, as in multi-start's selection.  Default weights (position in m^2, orientation in rad^2): wp_f = 1 when
+ * any position cost of frame task f is > 0, else 0; wo_f likewise from its orientation costs; a RelativeFrameTask gets 0 / 0
+ * (its target is no world pose).  pos_weight / ori_weight (n_frame,) replace them; each must be finite and >= 0, and all of
+ * them 0 is refused, as is a problem whose default weights are all 0 (no plain FrameTask with a non-zero cost).
+ *
+ * Query.  Per target the K entries with the smallest (d, j) in lexicographic order — ties go to the lower entry index —
+ * in ascending order: index_out (B, K), dist_out (B, K), and the entries' q as rows 1 .. K of seeds_out (B, K + 1, nq), whose
+ * row 0 is left alone (it is the slab mkh_solve_multistart's io->seeds takes, where row 0 is replaced by q anyway).  The scan
+ * is exact.  1 <= K <= 255 (else MKH_E_LIMIT above, MKH_E_INVALID below) and K <= N (MKH_E_INVALID); every output is optional
+ * but one must be given.  Pointers are host pointers (synchronous), or device pointers with MKH_FLAG_DEVICE_PTRS
+ * (asynchronous on the stream).  mkh_seed_table_create and mkh_seed_table_read take host pointers and are synchronous.
+ *
+ * Attached (mkh_problem_set_seed_table; NULL detaches): every mkh_solve_multistart and mkh_solve_trajectory_multistart call
+ * on that handle WHOSE io->seeds IS NULL takes rows s >= 1 of every instance from the table — the n_seeds - 1 entries nearest
+ * to the instance's frame targets (the trajectory call: waypoint 0's) — instead of drawing them: the query runs on the call's
+ * stream directly in front of the seed kernel and writes the slab that kernel reads a caller's seeds from.  Seed 0 stays the
+ * caller's q; io->seeds given: the caller's seeds win; rng_seed and target_index0 then do not enter the starts, so the result
+ * depends on the targets alone.  n_seeds = 1 and no table attached: the call as it is without this section, bit for bit.
+ * Refused with MKH_E_INVALID (MKH_E_LIMIT beyond 255 rows), the figure in the message: a table of another device, of another
+ * model (nq, njnt) or of another n_frame; a problem without a plain FrameTask of non-zero cost; n_seeds - 1 > N.  The table
+ * must stay alive while it is attached.
+ */
+int32_t mkh_seed_table_create(MkhProblem *problem, int32_t n_entries, const double *q0, const double *entries,
+                              uint64_t rng_seed, const double *pos_weight, const double *ori_weight, MkhSeedTable **out);
+void mkh_seed_table_destroy(MkhSeedTable *table);
+int32_t mkh_seed_table_read(const MkhSeedTable *table, double *q_out /* (N, nq) or NULL */,
+                            double *keys_out /* (N, n_frame, 7) or NULL */);
+int32_t mkh_seed_table_query(const MkhSeedTable *table, int32_t B, const double *frame_targets, int32_t K,
+                             int32_t *index_out, double *dist_out, double *seeds_out, int32_t flags, void *hip_stream);
+int32_t mkh_problem_set_seed_table(MkhProblem *problem, const MkhSeedTable *table);
 
 /* Same inputs; additionally writes the requested intermediates (build_ik / compute_error /
  * compute_jacobian / get_transform_frame_to_world parity taps).  v_out/status_out may be NULL

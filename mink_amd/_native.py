@@ -321,6 +321,16 @@ def lib() -> C.CDLL:
     L.mkh_geom_distance_eval.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
     L.mkh_geom_distance_eval.restype = C.c_int32
     L.mkh_problem_launch_info.argtypes = [C.c_void_p, C.c_int32] + [C.POINTER(C.c_int32)] * 4
+    L.mkh_seed_table_create.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                        C.POINTER(C.c_void_p)]
+    L.mkh_seed_table_destroy.argtypes = [C.c_void_p]
+    L.mkh_seed_table_destroy.restype = None
+    L.mkh_seed_table_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mkh_seed_table_query.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_int32, C.c_void_p]
+    L.mkh_problem_set_seed_table.argtypes = [C.c_void_p, C.c_void_p]
+    for f in ("mkh_seed_table_create", "mkh_seed_table_read", "mkh_seed_table_query", "mkh_problem_set_seed_table"):
+        getattr(L, f).restype = C.c_int32
     for f in ("mkh_model_create", "mkh_problem_create", "mkh_problem_num_task_rows",
               "mkh_problem_num_collision_pairs", "mkh_solve", "mkh_eval", "mkh_integrate",
               "mkh_problem_launch_info", "mkh_solve_steps"):
@@ -336,6 +346,8 @@ EXPORTED_SYMBOLS = (
     "mkh_solve_steps", "mkh_problem_last_kernel", "mkh_lie_eval", "mkh_solve_dense", "mkh_solve_until",
     "mkh_geom_distance_eval", "mkh_problem_create_diag", "mkh_solve_multistart",
     "mkh_solve_trajectory", "mkh_solve_keyframes", "mkh_solve_trajectory_multistart",
+    "mkh_seed_table_create", "mkh_seed_table_destroy", "mkh_seed_table_read", "mkh_seed_table_query",
+    "mkh_problem_set_seed_table",
 )
 
 LIE_OPS = {"se3_log": (0, 7, 0, (6,)), "se3_jlog": (1, 7, 0, (6, 6)), "se3_ljacinv": (2, 6, 0, (6, 6)),
@@ -484,6 +496,102 @@ class NativeModel:
         _check(lib().mkh_integrate(self.handle, q.shape[0], q.ctypes.data, v.ctypes.data, float(dt),
                                    out.ctypes.data, 0, None))
         return out
+
+
+class NativeSeedTable:
+    """A seed table on one device (mkh_seed_table_create): `n_entries` postures drawn around `q0` by multi-start's seeding rule
+    at (rng_seed, t = j, s = 1) — or the caller's `entries` (N, nq) —, keyed on the world poses of `problem`'s frame-task
+    frames.  The table owns its device memory: `problem` may be closed afterwards."""
+
+    def __init__(self, problem: "NativeProblem", n_entries: int, q0=None, *, entries=None, rng_seed: int = 0,
+                 position_weight=None, orientation_weight=None):
+        m = problem.nmodel.model
+        self.device = problem.nmodel.device
+        self.nq, self.n_frame = int(m.nq), int(problem.n_frame)
+        if entries is not None:
+            entries = _f64(entries)
+            if entries.ndim != 2 or entries.shape[1] != m.nq or len(entries) < 1:
+                raise ValueError(f"entries must have shape (N, {m.nq}) with N >= 1, got {entries.shape}")
+            n_entries = len(entries)
+        if q0 is not None:
+            q0 = _f64(q0)
+            if q0.shape != (m.nq,):
+                raise ValueError(f"q0 must have shape ({m.nq},), got {q0.shape}")
+        elif entries is None:
+            raise ValueError("q0 is required when the entries are drawn")
+        n_entries = int(n_entries)
+        if n_entries < 1:
+            raise ValueError("n_entries must be >= 1")
+        w = []
+        for x, name in ((position_weight, "position_weight"), (orientation_weight, "orientation_weight")):
+            if x is not None:
+                x = _f64(x)
+                if x.shape != (self.n_frame,):
+                    raise ValueError(f"{name} must have shape ({self.n_frame},), got {x.shape}")
+            w.append(x)
+        ptr = lambda x: None if x is None else x.ctypes.data
+        h = C.c_void_p()
+        with problem._lock:
+            _check(lib().mkh_seed_table_create(problem.handle, n_entries, ptr(q0), ptr(entries), int(rng_seed) & (2 ** 64 - 1),
+                                               ptr(w[0]), ptr(w[1]), C.byref(h)))
+        self.handle = h
+        self.n_entries = n_entries
+
+    def close(self):
+        if getattr(self, "handle", None):
+            lib().mkh_seed_table_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _native_for(self, problem: "NativeProblem") -> "NativeSeedTable":
+        return self
+
+    def read(self):
+        """(q (N, nq), poses (N, n_frame, 7)) on the host (mkh_seed_table_read)."""
+        q, poses = np.empty((self.n_entries, self.nq)), np.empty((self.n_entries, self.n_frame, 7))
+        _check(lib().mkh_seed_table_read(self.handle, q.ctypes.data, poses.ctypes.data))
+        return q, poses
+
+    def query(self, frame_targets, k: int):
+        """(index (B, k) int32, distance (B, k), q (B, k, nq)) of the k entries nearest to each row of frame_targets
+        (B, n_frame, 7), ascending (mkh_seed_table_query).  numpy in → numpy out (synchronous); torch tensors on the table's
+        device in → torch tensors out, asynchronous on the current stream."""
+        k = int(k)
+        prep, empty, ptr, stream, devp = _call_kit(frame_targets)
+        ft = prep(frame_targets)
+        if ft.ndim != 3 or tuple(ft.shape[1:]) != (self.n_frame, 7) or ft.shape[0] < 1:
+            raise ValueError(f"frame_targets must have shape (B, {self.n_frame}, 7) with B >= 1, got {tuple(ft.shape)}")
+        if devp and (ft.device.index if ft.device.index is not None else 0) != self.device:
+            raise ValueError(f"frame_targets live on {ft.device}, the seed table on device {self.device}")
+        B = int(ft.shape[0])
+        rows = max(k, 0)
+        idx, dist = empty((B, rows), np.int32), empty((B, rows), np.float64)
+        slab = empty((B, rows + 1, self.nq), np.float64)
+        _check(lib().mkh_seed_table_query(self.handle, B, ptr(ft), k, ptr(idx), ptr(dist), ptr(slab), devp, stream))
+        return idx, dist, slab[:, 1:]
+
+
+class _attached:
+    """A seed table attached to a handle for one call (mkh_problem_set_seed_table), detached on the way out."""
+
+    def __init__(self, problem: "NativeProblem", table):
+        self.problem = problem
+        self.table = None if table is None else table._native_for(problem)
+
+    def __enter__(self):
+        if self.table is not None:
+            if not self.table.handle:
+                raise ValueError("the seed table is closed")
+            _check(lib().mkh_problem_set_seed_table(self.problem.handle, self.table.handle))
+
+    def __exit__(self, *exc):
+        if self.table is not None:
+            lib().mkh_problem_set_seed_table(self.problem.handle, None)
 
 
 class NativeProblem:
@@ -757,12 +865,16 @@ class NativeProblem:
                          damping: float = 1e-12, *, n_seeds: int, max_iters: int, pos_threshold: float, ori_threshold: float,
                          rng_seed: int = 0, target_index0: int = 0, seeds=None, reference=None, weights=None,
                          return_all: bool = False, wave_kernel: bool = False, lane_kernel: bool = False,
-                         quad_kernel: bool = False) -> MultistartOut:
+                         quad_kernel: bool = False, seed_table=None) -> MultistartOut:
         """mkh_solve_multistart: the threshold-terminated loop from `n_seeds` starts per row of q (seed 0 = the row itself, the
         others drawn on the device or taken from `seeds` (B, S, nq)), the converged result closest to `reference` (default q)
         picked on the device.  numpy in → numpy out (synchronous); torch CUDA tensors in → torch tensors out, asynchronous on
-        the current stream, no host copy.  The handle needs max_batch >= B·n_seeds."""
-        with self._lock:
+        the current stream, no host copy.  The handle needs max_batch >= B·n_seeds.  `seed_table` (a SeedTable or
+        NativeSeedTable, not together with `seeds`): seeds 1 … n_seeds − 1 are the table's entries nearest to each target,
+        looked up on the device in front of the seed kernel; the table is attached for this call only."""
+        if seeds is not None and seed_table is not None:
+            raise ValueError("seeds and seed_table are two sources of the same starts: pass one of them")
+        with self._lock, _attached(self, seed_table):
             return self._solve_multistart(q, frame_targets, posture_target, com_target, dt, damping, int(n_seeds), int(max_iters),
                                           float(pos_threshold), float(ori_threshold), int(rng_seed), int(target_index0), seeds,
                                           reference, weights, return_all, wave_kernel, lane_kernel, quad_kernel)
@@ -858,14 +970,17 @@ class NativeProblem:
                                     ori_threshold: float, rng_seed: int = 0, target_index0: int = 0, seeds=None, weights=None,
                                     qvel_dt: Optional[float] = None, time_major: bool = False, warm_start: bool = False,
                                     return_all: bool = False, wave_kernel: bool = False, lane_kernel: bool = False,
-                                    quad_kernel: bool = False) -> TrajectoryMultistartOut:
+                                    quad_kernel: bool = False, seed_table=None) -> TrajectoryMultistartOut:
         """mkh_solve_trajectory_multistart: solve_trajectory's threshold-terminated loops from `n_seeds` candidate starts per row
         of q (candidate 0 = the row itself, the others drawn on the device as in solve_multistart or taken from `seeds`
         (B, S, nq)); per row the candidate that tracked the most waypoints, then the one with the shortest path from q
         (Σ_t Σ_k weights_k·(q_t ⊖ q_{t−1})_k²), is picked and gathered on the device (the rule: include/minkhip.h).  Targets
         and time_major as in solve_trajectory.  numpy in → numpy out (synchronous); torch CUDA tensors in → torch tensors out,
-        asynchronous on the current stream, no host copy.  The handle needs max_batch >= B·n_seeds."""
-        with self._lock:
+        asynchronous on the current stream, no host copy.  The handle needs max_batch >= B·n_seeds.  `seed_table` (not
+        together with `seeds`): candidates 1 … n_seeds − 1 start at the table's entries nearest to waypoint 0's targets."""
+        if seeds is not None and seed_table is not None:
+            raise ValueError("seeds and seed_table are two sources of the same starts: pass one of them")
+        with self._lock, _attached(self, seed_table):
             return self._solve_trajectory(q, frame_targets, posture_target, com_target, dt, damping, int(n_steps),
                                           (float(pos_threshold), float(ori_threshold)), qvel_dt, bool(time_major), warm_start,
                                           wave_kernel, lane_kernel, quad_kernel,

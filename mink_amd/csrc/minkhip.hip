@@ -233,6 +233,19 @@ struct MkhProblem {
   // the outer-loop entry points' workspace, by role (WsRole)
   bool ws_tables = false;
   GrowBuf ws[WS_COUNT];
+  // seed tables: the default weights of a table made from this problem — [f]: 1 when plain FrameTask f has a position cost > 0,
+  // [n_frame + f]: an orientation cost > 0; a RelativeFrameTask: 0 / 0 — and the table attached by mkh_problem_set_seed_table
+  std::vector<double> frame_w;
+  const MkhSeedTable* seed_table = nullptr;
+};
+
+// A seed table (include/minkhip.h "Seed tables"): device memory of its own — nothing of the problem that made it is kept.
+struct MkhSeedTable {
+  int device = 0;
+  int N = 0, nq = 0, njnt = 0, n_frame = 0;
+  double* d_q = nullptr;             // (N, nq)
+  double* d_keys = nullptr;          // (n_frame·7, N): seed_table.hip
+  double* d_w = nullptr;             // (2·n_frame): position weights, orientation weights
 };
 
 // The wavefront kernel's variants live in their own translation units (mink_amd/csrc/build.py generates one variant_<name>.hip
@@ -1000,6 +1013,12 @@ int32_t mkh_problem_create_diag(MkhModel* m, const MkhProblemDesc* d, int32_t ma
     for (int k = 0; k < 6; ++k) if (s.cost[k] != 0.0) f.rowmask |= 1 << k;
     f.jrow0 = jrows;
     jrows += __builtin_popcount(f.rowmask);
+  }
+  p->frame_w.assign(2 * (size_t)d->n_frame_tasks, 0.0);
+  for (int t = 0; t < d->n_frame_tasks; ++t) {
+    if (ft[t].relative) continue;
+    p->frame_w[t] = (ft[t].rowmask & 7) ? 1.0 : 0.0;
+    p->frame_w[d->n_frame_tasks + t] = ft[t].any_ori ? 1.0 : 0.0;
   }
   std::vector<double> pcost((size_t)(d->n_posture_tasks ? d->n_posture_tasks : 1) * 64, 0.0);
   for (int t = 0; t < d->n_posture_tasks; ++t) {
@@ -2288,7 +2307,206 @@ struct Stager {
 // a launcher's hipError_t into the latch; not launched at all behind an earlier error
 #define ST_LAUNCH(st, call) do { if ((st).ok()) (st).latch(call); } while (0)
 
+// ---- seed tables
+// device buffers of one call, freed on every way out
+struct DevTmp {
+  std::vector<void*> all;
+  ~DevTmp() { for (void* x : all) (void)hipFree(x); }
+  hipError_t get(void** out, size_t bytes) {
+    *out = nullptr;
+    const hipError_t e = hipMalloc(out, bytes ? bytes : 8);
+    if (e == hipSuccess) all.push_back(*out);
+    return e;
+  }
+};
+
+// Whether `tab` can seed a call on `p` that wants `k` rows per instance (k < 0: attaching — the row count is the call's).
+static int32_t st_refuse(const MkhProblem* p, const MkhSeedTable* tab, int k, const char* who) {
+  const MkhModel* m = p->model;
+  if (tab->device != m->device)
+    return fail(MKH_E_INVALID, "%s: the seed table lives on device %d, the problem on device %d", who, tab->device, m->device);
+  if (tab->nq != m->nq || tab->njnt != m->njnt)
+    return fail(MKH_E_INVALID, "%s: the seed table belongs to another model (nq = %d, njnt = %d; this problem: nq = %d, njnt = %d)",
+                who, tab->nq, tab->njnt, m->nq, m->njnt);
+  if (tab->n_frame != p->dev.n_frame)
+    return fail(MKH_E_INVALID, "%s: the seed table is keyed on %d frame-task frames, this problem has %d", who, tab->n_frame,
+                p->dev.n_frame);
+  bool any = false;
+  for (double w : p->frame_w) any = any || w > 0.0;
+  if (!any)
+    return fail(MKH_E_INVALID, "%s: the problem has no plain FrameTask with a non-zero cost (%d frame tasks): nothing to look a "
+                               "world pose up by", who, p->dev.n_frame);
+  if (k > tab->N)
+    return fail(MKH_E_INVALID, "%s: n_seeds - 1 = %d exceeds the seed table's %d entries", who, k, tab->N);
+  if (k > 255) return fail(MKH_E_LIMIT, "%s: n_seeds - 1 = %d rows from a seed table, at most 255", who, k);
+  return MKH_OK;
+}
+
 extern "C" {
+
+void mkh_seed_table_destroy(MkhSeedTable* t) {
+  if (!t) return;
+  (void)hipSetDevice(t->device);
+  (void)hipFree(t->d_q); (void)hipFree(t->d_keys); (void)hipFree(t->d_w);
+  delete t;
+}
+
+int32_t mkh_seed_table_create(MkhProblem* p, int32_t n_entries, const double* q0, const double* entries, uint64_t rng_seed,
+                              const double* pos_weight, const double* ori_weight, MkhSeedTable** out) {
+  if (!p || !out) return fail(MKH_E_INVALID, "null argument");
+  *out = nullptr;
+  if (n_entries < 1) return fail(MKH_E_INVALID, "n_entries = %d must be >= 1", n_entries);
+  if (!q0 && !entries) return fail(MKH_E_INVALID, "q0 is null (the configuration the entries are drawn around) and so is entries");
+  const DeviceProblem& P = p->dev;
+  const MkhModel* m = p->model;
+  const int nf = P.n_frame, nq = P.nq;
+  if (P.n_dense_rows || P.n_dense_limit_rows || P.dense_box)
+    return fail(MKH_E_INVALID, "dense (plugin) rows are evaluated by the caller at q: no seed table");
+  std::vector<double> w(p->frame_w);
+  bool any_default = false;
+  for (double x : w) any_default = any_default || x > 0.0;
+  if (!any_default)
+    return fail(MKH_E_INVALID, "mkh_seed_table_create: the problem has no plain FrameTask with a non-zero cost (%d frame tasks): "
+                               "nothing to key the entries on", nf);
+  for (int f = 0; f < nf; ++f) {
+    if (pos_weight) w[f] = pos_weight[f];
+    if (ori_weight) w[nf + f] = ori_weight[f];
+  }
+  bool any = false;
+  for (int f = 0; f < 2 * nf; ++f) {
+    if (!(w[f] >= 0.0) || !std::isfinite(w[f]))
+      return fail(MKH_E_INVALID, "%s weight of frame %d is %g: weights must be finite and >= 0", f < nf ? "position" : "orientation",
+                  f % nf, w[f]);
+    any = any || w[f] > 0.0;
+  }
+  if (!any) return fail(MKH_E_INVALID, "all %d position and orientation weights are 0: every entry would be at distance 0", 2 * nf);
+  HIP_OK(hipSetDevice(m->device));
+  if (!entries)
+    if (const int32_t rc = ms_build_tables(p)) return rc;
+  const size_t Nz = (size_t)n_entries, f8 = sizeof(double);
+  MkhSeedTable* t = new MkhSeedTable();
+  t->device = m->device; t->N = n_entries; t->nq = nq; t->njnt = m->njnt; t->n_frame = nf;
+  auto bail = [&](int32_t code) { mkh_seed_table_destroy(t); return code; };
+  auto hip_bail = [&](hipError_t e, const char* what) {
+    (void)hipDeviceSynchronize();
+    return bail(fail(MKH_E_HIP, "mkh_seed_table_create: %s: %s", what, hipGetErrorString(e)));
+  };
+  hipError_t e;
+  if ((e = hipMalloc((void**)&t->d_q, Nz * nq * f8)) || (e = hipMalloc((void**)&t->d_keys, Nz * nf * 7 * f8)) ||
+      (e = hipMalloc((void**)&t->d_w, 2 * (size_t)nf * f8)))
+    return hip_bail(e, "no device memory for the table");
+  if ((e = hipMemcpy(t->d_w, w.data(), 2 * (size_t)nf * f8, hipMemcpyHostToDevice))) return hip_bail(e, "weights");
+  DevTmp tmp;
+  hipStream_t stream = nullptr;
+  // ---- the entries
+  if (entries) {
+    if ((e = hipMemcpy(t->d_q, entries, Nz * nq * f8, hipMemcpyHostToDevice))) return hip_bail(e, "entries");
+  } else {
+    // entry j = row s = 1 of "target" j of multi-start's seed kernel around q0: (N, 2, nq) starts from N copies of q0
+    std::vector<double> tiled(Nz * nq);
+    for (size_t j = 0; j < Nz; ++j) memcpy(&tiled[j * nq], q0, (size_t)nq * f8);
+    double *d_q0 = nullptr, *d_draw = nullptr;
+    if ((e = tmp.get((void**)&d_q0, Nz * nq * f8)) || (e = tmp.get((void**)&d_draw, 2 * Nz * nq * f8)))
+      return hip_bail(e, "no device memory to draw the entries in");
+    if ((e = hipMemcpy(d_q0, tiled.data(), Nz * nq * f8, hipMemcpyHostToDevice))) return hip_bail(e, "q0");
+    if ((e = launch_ms_seed(stream, p->ws[WS_SEED_I].i32(), p->ws[WS_SEED_F].f64(), n_entries, 2, nq, d_q0, nullptr,
+                            (unsigned long long)rng_seed, 0, d_draw)))
+      return hip_bail(e, "seed kernel");
+    if ((e = hipMemcpy2DAsync(t->d_q, (size_t)nq * f8, d_draw + nq, 2 * (size_t)nq * f8, (size_t)nq * f8, Nz, hipMemcpyDeviceToDevice,
+                              stream)))
+      return hip_bail(e, "entries");
+  }
+  // ---- the keys: the frame_pose tap of mkh_eval on the entries, in chunks of max_batch.  The evaluation's targets do not
+  //      enter a frame's pose: identity poses, the first entry as every posture target, a zero CoM target.
+  const size_t chunk = (size_t)p->max_batch < Nz ? (size_t)p->max_batch : Nz;
+  double *d_pose = nullptr, *d_ft = nullptr, *d_pt = nullptr, *d_ct = nullptr;
+  std::vector<double> ident(chunk * nf * 7, 0.0);
+  for (size_t i = 0; i < chunk * nf; ++i) ident[7 * i] = 1.0;
+  if ((e = tmp.get((void**)&d_pose, chunk * nf * 7 * f8)) || (e = tmp.get((void**)&d_ft, chunk * nf * 7 * f8)) ||
+      (e = tmp.get((void**)&d_pt, (size_t)P.n_posture * nq * f8)) || (e = tmp.get((void**)&d_ct, (size_t)P.n_com * 3 * f8)))
+    return hip_bail(e, "no device memory to evaluate the keys in");
+  if ((e = hipMemcpy(d_ft, ident.data(), ident.size() * f8, hipMemcpyHostToDevice))) return hip_bail(e, "targets");
+  for (int k = 0; k < P.n_posture; ++k)
+    if ((e = hipMemcpyAsync(d_pt + (size_t)k * nq, t->d_q, (size_t)nq * f8, hipMemcpyDeviceToDevice, stream))) return hip_bail(e, "targets");
+  if (P.n_com && (e = hipMemsetAsync(d_ct, 0, (size_t)P.n_com * 3 * f8, stream))) return hip_bail(e, "targets");
+  MkhTaps taps;
+  memset(&taps, 0, sizeof taps);
+  taps.frame_pose = d_pose;
+  for (size_t j0 = 0; j0 < Nz; j0 += chunk) {
+    const size_t n = Nz - j0 < chunk ? Nz - j0 : chunk;
+    if (const int32_t rc = mkh_eval(p, (int32_t)n, t->d_q + j0 * nq, d_ft, P.n_posture ? d_pt : nullptr, P.n_com ? d_ct : nullptr, 1.0,
+                                    1e-12, nullptr, nullptr, &taps, MKH_FLAG_DEVICE_PTRS, stream)) {
+      (void)hipDeviceSynchronize();
+      return bail(rc);
+    }
+    if ((e = launch_st_keys(stream, d_pose, (int)n, nf, (long long)Nz, (long long)j0, t->d_keys))) return hip_bail(e, "key kernel");
+  }
+  if ((e = hipStreamSynchronize(stream))) return hip_bail(e, "evaluating the keys");
+  *out = t;
+  return MKH_OK;
+}
+
+int32_t mkh_seed_table_read(const MkhSeedTable* t, double* q_out, double* keys_out) {
+  if (!t) return fail(MKH_E_INVALID, "null seed table");
+  HIP_OK(hipSetDevice(t->device));
+  const size_t Nz = (size_t)t->N, f8 = sizeof(double);
+  if (q_out) HIP_OK(hipMemcpy(q_out, t->d_q, Nz * t->nq * f8, hipMemcpyDeviceToHost));
+  if (keys_out) {
+    // (N, n_frame, 7) for the caller from the table's (n_frame·7, N)
+    const size_t rows = (size_t)t->n_frame * 7;
+    std::vector<double> k(rows * Nz);
+    HIP_OK(hipMemcpy(k.data(), t->d_keys, rows * Nz * f8, hipMemcpyDeviceToHost));
+    for (size_t j = 0; j < Nz; ++j)
+      for (size_t r = 0; r < rows; ++r) keys_out[j * rows + r] = k[r * Nz + j];
+  }
+  return MKH_OK;
+}
+
+int32_t mkh_seed_table_query(const MkhSeedTable* t, int32_t B, const double* frame_targets, int32_t K, int32_t* index_out,
+                             double* dist_out, double* seeds_out, int32_t flags, void* hip_stream) {
+  if (!t) return fail(MKH_E_INVALID, "null seed table");
+  if (B < 1) return fail(MKH_E_INVALID, "B = %d must be >= 1", B);
+  if (K < 1) return fail(MKH_E_INVALID, "K = %d must be >= 1", K);
+  if (K > 255) return fail(MKH_E_LIMIT, "K = %d: a query returns at most 255 entries per target", K);
+  if (K > t->N) return fail(MKH_E_INVALID, "K = %d exceeds the seed table's %d entries", K, t->N);
+  if (!frame_targets) return fail(MKH_E_INVALID, "frame_targets is null");
+  if (!index_out && !dist_out && !seeds_out) return fail(MKH_E_INVALID, "index_out, dist_out and seeds_out are all null");
+  HIP_OK(hipSetDevice(t->device));
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const int nf = t->n_frame, nq = t->nq;
+  if (flags & MKH_FLAG_DEVICE_PTRS) {
+    HIP_OK(launch_st_query(stream, t->d_keys, t->d_q, t->d_w, t->N, nf, nq, B, frame_targets, K, index_out, dist_out, seeds_out));
+    return MKH_OK;
+  }
+  // host pointers: staged through buffers of this call (a table is shared by handles and threads: it owns no workspace)
+  DevTmp tmp;
+  const size_t Bz = B, Kz = K, f8 = sizeof(double);
+  double *d_ft = nullptr, *d_dist = nullptr, *d_seeds = nullptr;
+  int32_t* d_idx = nullptr;
+  HIP_OK(tmp.get((void**)&d_ft, Bz * nf * 7 * f8));
+  if (index_out) HIP_OK(tmp.get((void**)&d_idx, Bz * Kz * sizeof(int32_t)));
+  if (dist_out) HIP_OK(tmp.get((void**)&d_dist, Bz * Kz * f8));
+  if (seeds_out) HIP_OK(tmp.get((void**)&d_seeds, Bz * (Kz + 1) * nq * f8));
+  hipError_t e = hipMemcpyAsync(d_ft, frame_targets, Bz * nf * 7 * f8, hipMemcpyHostToDevice, stream);
+  // (row 0 of the caller's slab is left alone: it goes down and comes back as it was)
+  if (e == hipSuccess && seeds_out) e = hipMemcpyAsync(d_seeds, seeds_out, Bz * (Kz + 1) * nq * f8, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = launch_st_query(stream, t->d_keys, t->d_q, t->d_w, t->N, nf, nq, B, d_ft, K, d_idx, d_dist, d_seeds);
+  if (e == hipSuccess && index_out) e = hipMemcpyAsync(index_out, d_idx, Bz * Kz * sizeof(int32_t), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess && dist_out) e = hipMemcpyAsync(dist_out, d_dist, Bz * Kz * f8, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess && seeds_out) e = hipMemcpyAsync(seeds_out, d_seeds, Bz * (Kz + 1) * nq * f8, hipMemcpyDeviceToHost, stream);
+  const hipError_t es = hipStreamSynchronize(stream);      // (whatever happened: copies from or to the caller's arrays may be in flight)
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return fail(MKH_E_HIP, "mkh_seed_table_query: %s", hipGetErrorString(e));
+  return MKH_OK;
+}
+
+int32_t mkh_problem_set_seed_table(MkhProblem* p, const MkhSeedTable* table) {
+  if (!p) return fail(MKH_E_INVALID, "null problem");
+  if (table)
+    if (const int32_t rc = st_refuse(p, table, -1, "mkh_problem_set_seed_table")) return rc;
+  p->seed_table = table;
+  return MKH_OK;
+}
 
 int32_t mkh_solve_multistart(MkhProblem* p, int32_t B, const double* q, const double* frame_targets,
                              const double* posture_target, const double* com_target, double dt, double damping,
@@ -2309,6 +2527,10 @@ int32_t mkh_solve_multistart(MkhProblem* p, int32_t B, const double* q, const do
   const long long N = (long long)B * n_seeds;
   if (N > p->max_batch)
     return fail(MKH_E_INVALID, "B * n_seeds = %lld exceeds max_batch=%d of this problem", N, p->max_batch);
+  // an attached seed table gives rows s >= 1 unless the caller brought seeds of their own
+  const MkhSeedTable* const tab = (!io->seeds && n_seeds > 1) ? p->seed_table : nullptr;
+  if (tab)
+    if (const int32_t rc = st_refuse(p, tab, n_seeds - 1, "mkh_solve_multistart")) return rc;
   HIP_OK(hipSetDevice(p->model->device));
   if (const int32_t rc = ms_build_tables(p)) return rc;
   const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
@@ -2327,7 +2549,7 @@ int32_t mkh_solve_multistart(MkhProblem* p, int32_t B, const double* q, const do
   const double* d_ct = ct_w ? st.up(WS_IN_CT, com_target, ct_w * (cbat ? Bz : 1)) : com_target;
   const double* const d_ref = st.up(WS_IN_REF, io->q_ref, Bz * nq);
   const double* const d_w = st.up(WS_IN_W, io->weights, nv);
-  const double* const d_user = st.up(WS_IN_SEEDS, io->seeds, Nz * nq);       // (the seed kernel reads them once)
+  const double* d_user = st.up(WS_IN_SEEDS, io->seeds, Nz * nq);             // (the seed kernel reads them once)
   // ---- workspace of the B·S instances: the caller's *_all arrays where they are device buffers
   double* const c_q = st.f64(WS_C_Q, Nz * nq);
   double* const c_v = st.f64(WS_C_V, Nz * nv);
@@ -2338,6 +2560,12 @@ int32_t mkh_solve_multistart(MkhProblem* p, int32_t B, const double* q, const do
   // where the loop runs in place
   double* const d_seeds = (devp && io->seeds_out) ? io->seeds_out : c_q;
   double* const d_q_all = (devp && io->q_all) ? io->q_all : c_q;
+  if (tab) {                          // the S − 1 entries nearest to each target, into the slab a caller's seeds would be in
+    double* const slab = st.f64(WS_IN_SEEDS, Nz * nq);
+    ST_LAUNCH(st, launch_st_query(stream, tab->d_keys, tab->d_q, tab->d_w, tab->N, P.n_frame, (int)nq, B, d_ft, S - 1, nullptr,
+                                  nullptr, slab));
+    d_user = slab;
+  }
   ST_LAUNCH(st, launch_ms_seed(stream, ws[WS_SEED_I].i32(), ws[WS_SEED_F].f64(), B, S, (int)nq, d_q, d_user,
                                (unsigned long long)rng_seed, (long long)target_index0, d_seeds));
   double* kept_seeds = nullptr;       // (host caller: the seeds are set aside before the loop overwrites them in place)
@@ -2479,6 +2707,10 @@ static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double
   if (B > p->max_batch) return fail(MKH_E_INVALID, "B=%d exceeds max_batch=%d of this problem", B, p->max_batch);
   if (cs && (long long)B * cs->S > p->max_batch)
     return fail(MKH_E_INVALID, "B * n_seeds = %lld exceeds max_batch=%d of this problem", (long long)B * cs->S, p->max_batch);
+  // an attached seed table gives the candidates' starts unless the caller brought seeds of their own
+  const MkhSeedTable* const tab = (cs && !cs->seeds && cs->S > 1) ? p->seed_table : nullptr;
+  if (tab)
+    if (const int32_t rc = st_refuse(p, tab, cs->S - 1, who)) return rc;
   HIP_OK(hipSetDevice(p->model->device));
   if (cs || io->qvel || (kf && io->posture_per_waypoint && P.n_posture > 0))
     if (const int32_t rc = ms_build_tables(p)) return rc;
@@ -2583,6 +2815,12 @@ static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double
   auto out_st = [&](size_t rows, size_t w) { return tm ? rows * w : w; };
   if (cs) {
     // the starts (candidate 0: q[b] itself), and a batched target that is held: fanned out once, in front of waypoint 0
+    if (tab) {                        // the S − 1 entries nearest to waypoint 0's targets (d_ft is time-major here: its first slab)
+      double* const slab = st.f64(WS_IN_SEEDS, Rz * nq);
+      ST_LAUNCH(st, launch_st_query(stream, tab->d_keys, tab->d_q, tab->d_w, tab->N, P.n_frame, (int)nq, B, d_ft, S - 1, nullptr,
+                                    nullptr, slab));
+      d_user = slab;
+    }
     ST_LAUNCH(st, launch_ms_seed(stream, ws[WS_SEED_I].i32(), ws[WS_SEED_F].f64(), B, S, (int)nq, d_q, d_user,
                                  (unsigned long long)cs->rng_seed, (long long)cs->target_index0, d_seeds));
     if (S > 1 && pt_w && pbat && !ptime) { ST_LAUNCH(st, launch_ms_fanout(stream, d_pt, c_pt, B, S, (int)pt_w)); d_pt = c_pt; }

@@ -1,6 +1,7 @@
 // Launchers of the small kernels around the loop launches of the outer-loop entry points (mkh_solve_multistart,
-// mkh_solve_trajectory, mkh_solve_keyframes, mkh_solve_trajectory_multistart): declared once, for the four files that define
-// them and for minkhip.hip, which calls them — a signature that drifts fails to compile in the file that drifted.
+// mkh_solve_trajectory, mkh_solve_keyframes, mkh_solve_trajectory_multistart) and of the seed tables in front of them: declared
+// once, for the five files that define them and for minkhip.hip, which calls them — a signature that drifts fails to compile in
+// the file that drifted.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -51,5 +52,11 @@ hipError_t launch_tms_gather(hipStream_t stream, const double* all, double* out,
                              int W, long long o_sb, long long o_st);
 hipError_t launch_tms_gather_i32(hipStream_t stream, const int32_t* all, int32_t* out, const int32_t* seed_index, int B, int S,
                                  int T, long long o_sb, long long o_st);
+// seed tables (seed_table.hip): a chunk's (n, n_frame, 7) poses into the table's (n_frame·7, N) keys at entries j0 …, and the
+// K entries nearest to each of B targets — indices (B, K), distances (B, K), the entries' q into rows 1 … K of a
+// (B, K + 1, nq) slab; each output optional
+hipError_t launch_st_keys(hipStream_t stream, const double* poses, int n, int n_frame, long long N, long long j0, double* keys);
+hipError_t launch_st_query(hipStream_t stream, const double* keys, const double* q_tab, const double* weights, int N, int n_frame,
+                           int nq, int B, const double* targets, int K, int32_t* index_out, double* dist_out, double* seeds_out);
 
 }  // namespace mkh

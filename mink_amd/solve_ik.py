@@ -446,10 +446,163 @@ def _status_epilogue(status: np.ndarray, who: str, outside: str, failed: str) ->
                                                    status=int(status[first])))
 
 
+SEED_TABLE_MAX_K = 255         # entries per target of one query (include/minkhip.h "Seed tables")
+SEED_TABLE_BUILD_BATCH = 4096  # instances per evaluation of the keys
+
+
+class SeedTable:
+    """Stored postures keyed on the end-effector poses they reach, for multi-start seeded from the nearest ones
+    (include/minkhip.h "Seed tables"): pass it as `seed_table=` to solve_ik_multistart / solve_ik_trajectory_multistart and
+    seeds 1 … n_seeds − 1 of every target are the table's entries nearest to that target instead of blind draws.
+
+    `configuration` holds the single q the `n_entries` entries are drawn around, by multi-start's seeding rule at
+    (rng_seed, t = j, s = 1) — free joints and unlimited slides keep its value, so the table of a floating-base robot belongs
+    to that base pose.  `entries` (N, nq) are the table as given instead (earlier solutions, a teach-in set).  The keys are
+    the world poses of the frames of the FrameTasks in `tasks`, in task order; the metric is
+    Σ_f position_weight_f·|Δp|² + orientation_weight_f·4 sin²(θ/2), weights 1 where the task has a cost of that kind
+    (RelativeFrameTasks: 0), or the (n_frame,) arrays given.  One device table per device is built on first use — its content
+    is a function of (model, q, rng_seed) or of `entries` alone, so the shards of a multi-device call agree — through the
+    configuration's compile cache; the table does not need that handle afterwards."""
+
+    def __init__(self, configuration: Configuration, tasks: Sequence, n_entries: int = 16384, *, limits: Optional[Sequence] = None,
+                 rng_seed: int = 0, entries=None, position_weight=None, orientation_weight=None):
+        import threading
+
+        if configuration.batch_size != 1:
+            raise ValueError(f"configuration must hold a single q (the one the entries are drawn around), got a batch of "
+                             f"{configuration.batch_size}")
+        self.model, self.nq = configuration.model, configuration.nq
+        self.q0 = np.array(configuration.q_batch[0], dtype=np.float64)
+        entries = _host_array(entries, "entries")
+        if entries is not None:
+            if entries.ndim != 2 or entries.shape[1] != self.nq or len(entries) < 1:
+                raise ValueError(f"entries must have shape (N, {self.nq}) with N >= 1, got {entries.shape}")
+            n_entries = len(entries)
+        self.n_entries = int(n_entries)
+        if self.n_entries < 1:
+            raise ValueError("n_entries must be >= 1")
+        self.entries, self.rng_seed = entries, int(rng_seed)
+        descs = [t._native_desc(configuration) for t in tasks if not t._is_dense()]
+        frames = [d for kind, d in descs if kind == "frame"]
+        self.n_frame = len(frames)
+        plain = lambda d, part: d.get("root_type") is None and any(float(c) > 0.0 for c in d["cost"][part])
+        default = [np.array([1.0 if plain(d, part) else 0.0 for d in frames]) for part in (slice(0, 3), slice(3, 6))]
+        if not (default[0].any() or default[1].any()):
+            raise ValueError(f"the tasks hold no plain FrameTask with a non-zero cost ({self.n_frame} frame tasks): nothing to key "
+                             "the entries on")
+        w = []
+        for x, name, dflt in ((position_weight, "position_weight", default[0]), (orientation_weight, "orientation_weight", default[1])):
+            x = _optional_array(x, name, (self.n_frame,))
+            if x is not None and not (np.isfinite(x).all() and (x >= 0.0).all()):
+                raise ValueError(f"{name} must be finite and >= 0")
+            w.append(dflt if x is None else x)
+        if not (w[0].any() or w[1].any()):
+            raise ValueError("position_weight and orientation_weight are all 0: every entry would be at distance 0")
+        self.position_weight, self.orientation_weight = w
+        self._configuration, self._tasks = configuration, list(tasks)
+        self._limits = None if limits is None else list(limits)
+        self._tables, self._cfgs, self._host = {}, {configuration.device: configuration}, None
+        self._lock = threading.Lock()
+        self._closed = False
+
+    # -- device tables
+    def _table(self, device: int) -> "nat.NativeSeedTable":
+        with self._lock:
+            if self._closed:
+                raise ValueError("the seed table is closed")
+            tab = self._tables.get(device)
+            if tab is None:
+                cfg = self._cfgs.get(device)
+                if cfg is None:
+                    cfg = self._cfgs[device] = Configuration(self.model, self.q0, device=device)
+                prob, layout = _compile(cfg, self._tasks, self._limits, min(self.n_entries, SEED_TABLE_BUILD_BATCH), devices=[device])
+                _refuse_plugin_rows(layout, "SeedTable")
+                with _pin(cfg, layout):
+                    tab = nat.NativeSeedTable(prob, self.n_entries, self.q0, entries=self.entries, rng_seed=self.rng_seed,
+                                              position_weight=self.position_weight, orientation_weight=self.orientation_weight)
+                self._tables[device] = tab
+            return tab
+
+    def _native_for(self, problem) -> "nat.NativeSeedTable":
+        return self._table(problem.nmodel.device)
+
+    def _read(self):
+        if self._host is None:
+            self._host = self._table(self._configuration.device).read()
+        return self._host
+
+    @property
+    def q(self) -> np.ndarray:
+        """(N, nq): the entries."""
+        return self._read()[0]
+
+    @property
+    def poses(self) -> np.ndarray:
+        """(N, n_frame, 7): the world pose (wxyz, xyz) of every frame-task frame at every entry."""
+        return self._read()[1]
+
+    def _check_k(self, k: int, what: str = "k") -> int:
+        k = int(k)
+        if k < 1:
+            raise ValueError(f"{what} = {k} must be >= 1")
+        if k > SEED_TABLE_MAX_K:
+            raise ValueError(f"{what} = {k}: a seed table returns at most {SEED_TABLE_MAX_K} entries per target")
+        if k > self.n_entries:
+            raise ValueError(f"{what} = {k} exceeds the seed table's {self.n_entries} entries")
+        return k
+
+    def query(self, targets, k: int):
+        """The k entries nearest to each target: (index (B, k), distance (B, k), q (B, k, nq)), ascending, ties to the lower
+        index.  `targets` (B, n_frame, 7) — or (B, 7) / (7,) with one frame task — as numpy (→ numpy) or as a torch tensor on
+        a device (→ torch tensors there, on the current stream)."""
+        k = self._check_k(k)
+        is_torch = nat._is_torch(targets)
+        t = targets if is_torch else _host_array(targets, "targets")
+        if t.ndim == 1:
+            t = t.reshape(1, -1)
+        if t.ndim == 2 and self.n_frame == 1:
+            t = t.reshape(t.shape[0], 1, t.shape[1])
+        if t.ndim != 3 or tuple(t.shape[1:]) != (self.n_frame, 7) or t.shape[0] < 1:
+            raise ValueError(f"targets must have shape (B, {self.n_frame}, 7), got {tuple(targets.shape)}")
+        if is_torch:
+            device = t.device.index if t.device.index is not None else 0
+        else:
+            device = self._configuration.device
+        return self._table(device).query(t, k)
+
+    def close(self) -> None:
+        with self._lock:
+            self._closed = True
+            for tab in self._tables.values():
+                tab.close()
+            self._tables = {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _check_seed_table(seed_table, seeds, configuration: Configuration, S: int):
+    """The `seed_table=` keyword of the two multi-start calls, judged on the host."""
+    if seed_table is None:
+        return
+    if seeds is not None:
+        raise ValueError("seeds and seed_table are two sources of the same starts: pass one of them")
+    if not isinstance(seed_table, SeedTable):
+        raise ValueError(f"seed_table must be a SeedTable, got {type(seed_table).__name__}")
+    if seed_table.nq != configuration.nq or seed_table.model.njnt != configuration.model.njnt:
+        raise ValueError(f"seed_table belongs to another model (nq = {seed_table.nq}, this configuration: nq = {configuration.nq})")
+    if S > 1:
+        seed_table._check_k(S - 1, "n_seeds - 1")
+
+
 def solve_ik_multistart(configuration: Configuration, tasks: Sequence, dt: float, n_seeds: int, max_iters: int,
                         pos_threshold: float, ori_threshold: float, solver: str = "mi355x", damping: float = 1e-12,
                         limits: Optional[Sequence] = None, rng_seed: int = 0, seeds=None, reference=None, weights=None,
-                        update: bool = True, return_all: bool = False, max_instances: int = 1 << 20) -> MultistartResult:
+                        update: bool = True, return_all: bool = False, max_instances: int = 1 << 20,
+                        seed_table: Optional["SeedTable"] = None) -> MultistartResult:
     """Global IK by multi-start: the threshold-terminated loop of solve_ik_steps from `n_seeds` starts per target, the best
     solution picked on the device — seeding, target fan-out and selection happen there, in one call.
 
@@ -465,6 +618,10 @@ def solve_ik_multistart(configuration: Configuration, tasks: Sequence, dt: float
     the CHOSEN seeds only, like solve_ik_steps reports them: a warning for configuration limits, SolverError for a QP failure
     (which can only be seed 0's, of a target where nothing converged); a failed random seed is just discarded.
 
+    `seed_table` (a SeedTable; not together with `seeds`): seeds 1 … n_seeds − 1 of every target are the table's entries
+    nearest to the target's frame poses, looked up on the device in front of the seed kernel — they depend on the target
+    alone, not on rng_seed, chunks or shards.  The table is attached to the handle for this call only.
+
     When B·n_seeds exceeds `max_instances` the targets are walked in chunks; a multi-device configuration shards by target."""
     del solver
     S, max_iters = int(n_seeds), int(max_iters)
@@ -478,6 +635,7 @@ def solve_ik_multistart(configuration: Configuration, tasks: Sequence, dt: float
     seeds = _optional_array(seeds, "seeds", (S, nq), B)
     reference = _optional_array(reference, "reference", (nq,), B)
     weights = _optional_array(weights, "weights", (nv,))
+    _check_seed_table(seed_table, seeds, configuration, S)
     handles, layout, chunk, n_dev = _compile_outer(configuration, tasks, limits, dt, "solve_ik_multistart", S, max_instances)
     ft, pt, ct = _gather_targets(configuration, layout)
     q = configuration.q_batch
@@ -487,7 +645,7 @@ def solve_ik_multistart(configuration: Configuration, tasks: Sequence, dt: float
     def job(handle, lo, hi):
         return handle.solve_multistart(q[lo:hi], _rows(ft, 2, lo, hi), _rows(pt, 2, lo, hi), _rows(ct, 2, lo, hi), dt, damping,
                                        target_index0=lo, seeds=_rows(seeds, 2, lo, hi), reference=_rows(reference, 1, lo, hi),
-                                       weights=weights, **kw)
+                                       weights=weights, seed_table=seed_table, **kw)
 
     res = _join(MultistartResult, _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job))
     _status_epilogue(res.status, "solve_ik_multistart", "chosen instance(s)",
@@ -687,7 +845,8 @@ def solve_ik_trajectory_multistart(configuration: Configuration, tasks: Sequence
                                    pos_threshold: float, ori_threshold: float, solver: str = "mi355x", damping: float = 1e-12,
                                    limits: Optional[Sequence] = None, rng_seed: int = 0, seeds=None, weights=None,
                                    waypoint_dt: Optional[float] = None, warm_start: bool = False, update: bool = True,
-                                   return_all: bool = False, max_instances: int = 1 << 20) -> TrajectoryMultistartResult:
+                                   return_all: bool = False, max_instances: int = 1 << 20,
+                                   seed_table: Optional["SeedTable"] = None) -> TrajectoryMultistartResult:
     """Track a time sequence of targets globally: `n_seeds` candidate trajectories per instance, seeded like
     solve_ik_multistart and each tracked like solve_ik_trajectory (waypoint t from the same candidate's waypoint t − 1, so a
     candidate is continuous by construction), scored over the whole path, one chosen and gathered on the device — in one call.
@@ -702,7 +861,10 @@ def solve_ik_trajectory_multistart(configuration: Configuration, tasks: Sequence
     candidate (the jump to a far seed counts); ties go to the lowest index; when nobody tracked anything, candidate 0.  Limits
     warnings and SolverError follow solve_ik_trajectory's rules on the CHOSEN candidate only.  With `update` the configuration
     is left at the chosen q[:, -1].  When B·n_seeds exceeds `max_instances` the instances are walked in chunks; a multi-device
-    configuration shards by instance; the result depends on neither."""
+    configuration shards by instance; the result depends on neither.
+
+    `seed_table` (a SeedTable; not together with `seeds`): candidates 1 … n_seeds − 1 start at the table's entries nearest to
+    waypoint 0's frame targets, as in solve_ik_multistart."""
     del solver
     S, n_steps = int(n_seeds), int(n_steps)
     if S < 1:
@@ -721,6 +883,7 @@ def solve_ik_trajectory_multistart(configuration: Configuration, tasks: Sequence
     weights = _optional_array(weights, "weights", (nv,))
     if weights is not None and not (weights >= 0.0).all():
         raise ValueError("weights must be >= 0 (no NaN): the path length is a sum of non-negative terms")
+    _check_seed_table(seed_table, seeds, configuration, S)
     handles, layout, chunk, n_dev = _compile_outer(configuration, tasks, limits, dt, "solve_ik_trajectory_multistart", S,
                                                    max_instances)
     ft, pt, ct = _stacked_targets(configuration, layout, seqs, T)
@@ -730,7 +893,8 @@ def solve_ik_trajectory_multistart(configuration: Configuration, tasks: Sequence
 
     def job(handle, lo, hi):
         out = handle.solve_trajectory_multistart(q[lo:hi], _rows(ft, 0, lo, hi), _rows(pt, 2, lo, hi), _rows(ct, 2, lo, hi), dt,
-                                                 damping, target_index0=lo, seeds=_rows(seeds, 0, lo, hi), **kw)
+                                                 damping, target_index0=lo, seeds=_rows(seeds, 0, lo, hi), seed_table=seed_table,
+                                                 **kw)
         if not return_all:
             return out
         # every candidate's results, time-major (T, n·S, ·) → (n, S, T, ·), so that chunks and shards concatenate by instance
