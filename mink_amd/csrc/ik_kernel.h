@@ -459,7 +459,7 @@ struct PreView {
   const MKH_GLOBAL double *body_f, *jnt_f, *dof_f;
   const MKH_GLOBAL int32_t *body_i, *jnt_i, *dof_i;
   const MKH_GLOBAL FrameTaskDev* frame;
-  int nbody, nv, nq, njnt, n_frame, n_posture, n_com, max_rows, n_jrows, prefetch, prefetch_w3, prefetch_w3w, wood_compact, prefetch_wc, n_rows_tap, nrounds, robot_root, n_hsel;
+  int nbody, nv, nq, njnt, n_frame, n_posture, n_com, max_rows, n_jrows, prefetch, prefetch_w3, prefetch_w3w, wood_compact, prefetch_wc, n_rows_tap, nrounds, robot_root, n_hsel, jnt_pos_zero;
   __device__ __forceinline__ explicit PreView(const DeviceProblem* Pq) {
     const MKH_CONSTANT DeviceProblem* c = (const MKH_CONSTANT DeviceProblem*)Pq;
     body_f = (const MKH_GLOBAL double*)c->body_f; jnt_f = (const MKH_GLOBAL double*)c->jnt_f; dof_f = (const MKH_GLOBAL double*)c->dof_f;
@@ -469,6 +469,7 @@ struct PreView {
     max_rows = c->max_rows; n_jrows = c->n_jrows; prefetch = c->prefetch; prefetch_w3 = c->prefetch_w3; prefetch_w3w = c->prefetch_w3w;
     wood_compact = c->wood_compact; prefetch_wc = c->prefetch_wc;
     n_rows_tap = c->n_rows_tap; nrounds = c->nrounds; robot_root = c->robot_root; n_hsel = c->n_hsel;
+    jnt_pos_zero = c->jnt_pos_zero;
   }
 };
 // second LDS buffers for the next problem's inputs: decided on the host per LDS layout (only where they cost no resident wave)
@@ -536,6 +537,10 @@ __device__ MKH_PRE_ATTR PreOut pre_phases(const DeviceProblem* Pq, const TapArgs
     V3 xp{0, 0, 0};
     Q4 xq{1, 0, 0, 0};
     int b_jadr = 0, b_jnum = 0, anc_lo = 0, anc_hi = 0;
+    // joints at their bodies' origins (the whole model: a flag of the descriptor, wave-uniform): anchor = xpos — rotating the
+    // zero offset gives +0 and xp ± 0 is xp
+    // (low-rank builds only: the branch costs the direct-start builds spilled registers)
+    const bool jp_zero = kWood && P.jnt_pos_zero != 0;
     if (is_body) {
       anc_lo = P.body_i[BI_ANCPACK0 * 64 + ol];
       anc_hi = P.body_i[BI_ANCPACK1 * 64 + ol];
@@ -566,9 +571,11 @@ __device__ MKH_PRE_ATTR PreOut pre_phases(const DeviceProblem* Pq, const TapArgs
           } else {
             qloc = qnormalize(Q4{sq[qa], sq[qa + 1], sq[qa + 2], sq[qa + 3]});
           }
-          V3 anchor = xp + qrot(xq, jp);
+          V3 anchor = xp;
+          if (!jp_zero) anchor = xp + qrot(xq, jp);
           xq = qmul(xq, qloc);
-          xp = anchor - qrot(xq, jp);
+          xp = anchor;
+          if (!jp_zero) xp = anchor - qrot(xq, jp);
         }
       }
     }
@@ -614,7 +621,8 @@ __device__ MKH_PRE_ATTR PreOut pre_phases(const DeviceProblem* Pq, const TapArgs
         const int j = b_jadr;
         const auto* jf = P.jnt_f + j * JF_COUNT;
         V3 ax = qrot(xq, V3{jf[JF_AXIS], jf[JF_AXIS + 1], jf[JF_AXIS + 2]});
-        V3 an = xp + qrot(xq, V3{jf[JF_POS], jf[JF_POS + 1], jf[JF_POS + 2]});
+        V3 an = xp;
+        if (!jp_zero) an = xp + qrot(xq, V3{jf[JF_POS], jf[JF_POS + 1], jf[JF_POS + 2]});
         double* o = sJnt + j * 6;
         o[0] = ax.x; o[1] = ax.y; o[2] = ax.z; o[3] = an.x; o[4] = an.y; o[5] = an.z;
       } else {
@@ -768,11 +776,14 @@ __device__ MKH_PRE_ATTR PreOut pre_phases(const DeviceProblem* Pq, const TapArgs
       V3 ev, ew;
       double Jm[9], Qm[9];
       bool ident;
+      // (low-rank builds: one square root of |ew|² for log and jlog; in the others handing it over costs spilled registers)
+      double eth = 0.0;
+      const double* const eth_p = kWood ? &eth : nullptr;
       if (!(kRel && ft.relative)) {
         // e = target.minus(frame) = log(T_frame⁻¹ · T_target)          (frame_task.py:119-122)
-        se3_log(se3_mul(se3_inv(F), Tt), ev, ew);
+        se3_log(se3_mul(se3_inv(F), Tt), ev, ew, eth);
         // jlog(T_tb) = ljacinv(−log(T_tb)) = ljacinv(e)   since T_tb = T_bt⁻¹   (frame_task.py:144-146)
-        se3_ljacinv(ev, ew, Jm, Qm, ident);
+        se3_ljacinv(ev, ew, eth_p, Jm, Qm, ident);
       } else {
         // RelativeFrameTask (relative_frame_task.py:106-142): T_fr = T_root⁻¹·T_frame,
         // e = T_fr.rminus(target) = log(target⁻¹·T_fr),  J = jlog(T_tf)·(ᶠJ − Ad(T_fr⁻¹)·ʳJ)
@@ -782,8 +793,8 @@ __device__ MKH_PRE_ATTR PreOut pre_phases(const DeviceProblem* Pq, const TapArgs
         Rt.p = V3{xr[0], xr[XS], xr[2 * XS]} + qrot(rq0, V3{ft.root_lpos[0], ft.root_lpos[1], ft.root_lpos[2]});
         Rt.q = qmul(rq0, Q4{ft.root_lquat[0], ft.root_lquat[1], ft.root_lquat[2], ft.root_lquat[3]});
         const SE3 Tfr = se3_mul(se3_inv(Rt), F);
-        se3_log(se3_mul(se3_inv(Tt), Tfr), ev, ew);
-        se3_ljacinv(-1.0 * ev, -1.0 * ew, Jm, Qm, ident);       // jlog(T) = ljacinv(−log T)
+        se3_log(se3_mul(se3_inv(Tt), Tfr), ev, ew, eth);
+        se3_ljacinv(-1.0 * ev, -1.0 * ew, eth_p, Jm, Qm, ident);  // jlog(T) = ljacinv(−log T)
         const SE3 Trf = se3_inv(Tfr);
         const M3 Rr = qmat(Rt.q), Rrf = qmat(Trf.q);
 #pragma unroll
@@ -1155,6 +1166,21 @@ __device__ __attribute__((noinline)) void wood_s_dense_call(int n_mu, int nv, in
 }
 #endif
 
+// Zero n doubles of LDS at p (n wave-uniform): the whole 128-double blocks under a scalar loop with nothing but a paired store
+// — lane l writes doubles l and 64 + l of the block, each half conflict-free — and the address step in it, two guarded stores
+// for the rest.  (One double per lane under a per-lane bound was five VALU instructions per store: with machine LICM off the
+// zero was materialised inside the loop.)
+__device__ __forceinline__ void lds_zero_fill(double* p, int n, int lane) {
+  double z0 = 0.0, z1 = 0.0;
+  asm volatile("" : "+v"(z0), "+v"(z1));                               // (two registers, set once: the operands of a paired store)
+  double* o = p + lane;
+  const int blocks = n >> 7;
+  for (int b = 0; b < blocks; ++b, o += 2 * kWave) { o[0] = z0; o[kWave] = z1; }
+  const int rest = n - (blocks << 7);
+  if (lane < rest) o[0] = z0;
+  if (lane + kWave < rest) o[kWave] = z1;
+}
+
 // A real call in the 3-waves variants (see pre_phases) and in the F_COM builds, whose 24-row / two-pass instantiations do not
 // fit next to the kernel's own live values (86 spilled VGPRs when inlined).
 #if defined(MKH_CALLS) || (MKH_FEAT & 4)
@@ -1226,11 +1252,14 @@ __device__ MKH_WOOD_ATTR WoodOut wood_start(const DeviceProblem* Pq, int oz, int
   constexpr bool kPre = NR >= 44;
   int pre_src = 0, pre_t = 0, pre_k = 0, pre_wc = 0, pre_wr0 = 0;
   uint64_t pre_chain = 0;
+  uint32_t pre_list[4] = {0, 0, 0, 0};
   if constexpr (kPre) {
     pre_src = P.mu_src[is_s ? my_c : 0];
     pre_t = P.jpair_task[lane]; pre_k = P.jpair_dof[lane];
     pre_wc = P.wood_col[ol]; pre_wr0 = P.wood_row0[ol];
     pre_chain = P.wood_mask[ol];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) pre_list[i] = P.wood_list[ol][i];
   }
   double we_mu = 0.0;
   if (is_s) {
@@ -1284,7 +1313,7 @@ __device__ MKH_WOOD_ATTR WoodOut wood_start(const DeviceProblem* Pq, int oz, int
     }
     if (base == 0) {
       wave_sync();                                               // every pair of a one-pass problem has read its inputs
-      for (int i = lane; i < n_mu * NR; i += kWave) sJ[i] = 0.0;   // dofs off a task's chain
+      lds_zero_fill(sJ, n_mu * NR, lane);                        // dofs off a task's chain
       // x after the closed-form dof sweeps: z_k = −c_k/Dg_k (posture part of c only), staged as z_k·√Dg_k in row n_μ of
       // the array so that the right-hand side Jw·z is one more row of the product below
       // (a predicted dof contributes its bound: z̃_k = β_k)
@@ -1388,7 +1417,7 @@ __device__ MKH_WOOD_ATTR WoodOut wood_start(const DeviceProblem* Pq, int oz, int
   // axes / anchors / CoMs of the Jacobian columns are dead by now) when it fits, so that the low-rank start costs no LDS.
   double* const sS = (!kRowsW && wood_s_aliases_dof(nv, n_mu, SP, P.n_com > 0 ? P.nbody : 0)) ? sDof : smem + L.S;
   double* const sW = sS + n_mu * SP;
-  for (int i = lane; i < n_mu * SP; i += kWave) sS[i] = 0.0;
+  lds_zero_fill(sS, n_mu * SP, lane);
   wave_sync();
   if constexpr (kCom) {
     // Dense product (F_COM builds: ComTask rows reach every dof, and with 24 rows the chain walk below — a dependent
@@ -1427,6 +1456,19 @@ __device__ MKH_WOOD_ATTR WoodOut wood_start(const DeviceProblem* Pq, int oz, int
       const double* a = sJ + wc * NR;
       const uint64_t chain = kPre ? pre_chain : P.wood_mask[ol];
       const int rpc = P.wood_rpc;
+      // (not in the fused-loop builds of at most 24 rows on the two-waves map: the list's registers cost `24_48_r24`, which
+      //  inlines this function under a 168-register cap, two spilled VGPRs — a fused loop is cold for two of its steps only)
+#if defined(MKH_W3)
+      constexpr bool kLists = true;
+#else
+      constexpr bool kLists = !((MKH_FEAT & F_STEPS) && MKH_NT <= 24);
+#endif
+      const int trip = kLists ? P.wood_trip : 0;
+      uint32_t lst[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) lst[i] = !kLists ? 0u : kPre ? pre_list[i] : P.wood_list[ol][i];
+      int three = 3;
+      asm volatile("" : "+v"(three));                                  // (log2 of a double's size, in a register set once)
       // eight rows per pass (one pass for G1's 7 rows per lane): the lane's own column entry is read once per pass, and
       // the walk over the chain bits — a dependent ffs → address → LDS read → FMA chain per bit — runs once
       for (int i0 = 0; i0 < rpc; i0 += 8) {
@@ -1439,35 +1481,57 @@ __device__ MKH_WOOD_ATTR WoodOut wood_start(const DeviceProblem* Pq, int oz, int
         double acc[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc[j] = 0.0;
-        for (uint64_t mk = chain & ~a_mask; mk; mk &= mk - 1) {        // S: the free dofs of the chain
-          const int k = __ffsll((unsigned long long)mk) - 1;
+        if (a_mask == 0 && trip > 0) {
+          // cold solve: the chain as the host's list of the lane (DeviceProblem::wood_list) — a byte per dof in the order of
+          // the mask's bits, every lane wood_trip entries under scalar loop control; a padding entry adds +0·Jh[row][k]
+          uint32_t w0 = lst[0], w1 = lst[1], w2 = lst[2], w3 = lst[3];
+#pragma unroll 1
+          for (int e0 = 0; e0 < trip; e0 += 4) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              if (e0 + e < trip) {
+                const int k8 = (int)((w0 >> (8 * e)) & 0xffu) << three;
+                const double av = *(const double*)((const char*)a + k8);
+                const double* const bk = (const double*)((const char*)b0 + k8);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc[j] = fma(av, bk[j * NR], acc[j]);
+              }
+            }
+            w0 = w1; w1 = w2; w2 = w3;
+          }
+        } else
+        for (uint64_t mk = chain & ~a_mask; mk; mk &= mk - 1) {        // S: the free dofs of the chain (a predicted active set,
+          const int k = __ffsll((unsigned long long)mk) - 1;           // or no lists: the bits of the mask)
           const double av = a[k];
           const double* const bk = b0 + k;
 #pragma unroll
           for (int j = 0; j < 8; ++j) acc[j] = fma(av, bk[j * NR], acc[j]);
         }
+        double extra = 0.0;                                            // (+0 on a cold solve: the sum as it is)
         if (chain & a_mask) {                                          // Jw·z̃ also takes the predicted dofs (z̃ = β)
-          const int jr = n_mu - row0;                                  // the right-hand-side row of this pass, if any
-          double extra = 0.0;
           for (uint64_t mk = chain & a_mask; mk; mk &= mk - 1) {
             const int k = __ffsll((unsigned long long)mk) - 1;
             extra = fma(a[k], sJ[n_mu * NR + k], extra);
           }
-#pragma unroll
-          for (int j = 0; j < 8; ++j) acc[j] += (j == jr) ? extra : 0.0;
         }
+        // the lane's stores: S rows [row0, row0 + n_st) — the diagonal's 1 is added by the column's own lane below, which
+        // reads w anyway — and, on the lanes of the last chunk, the right-hand side: entry wood_jrhs of that chunk (host)
+        const int n_st = min(rpc - i0, n_mu - row0), j_rhs = P.wood_jrhs - i0;   // (j_rhs: wave-uniform)
+        const bool has_rhs = row0 + j_rhs == n_mu;
+        double* const so = sS + wc * SP + row0;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          const int row = row0 + j;
-          if (i0 + j < rpc && row <= n_mu) {
-            if (row < n_mu) sS[wc * SP + row] = acc[j] + (row == wc ? 1.0 : 0.0); else sW[wc] = acc[j];
-          }
+          if (j < n_st) so[j] = acc[j];
+          if (j == j_rhs && has_rhs) sW[wc] = acc[j] + extra;
         }
       }
     }
   }
   wave_sync();
-  if (is_s) sW[my_c] -= we_mu;                                         // w = Jw·z − r
+  if (is_s) {
+    sW[my_c] -= we_mu;                                                 // w = Jw·z − r
+    if constexpr (!kCom) sS[my_c * SP + my_c] += 1.0;                  // S = I + Jh·Jhᵀ
+  }
   wave_sync();
   if (prof) prof[1] = __builtin_readcyclecounter();                    // S and w ready
 #if defined(MKH_WOOD_CALL) && defined(MKH_CLOCKS)

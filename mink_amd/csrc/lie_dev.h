@@ -162,15 +162,17 @@ struct SE3 { Q4 q; V3 p; };
 __device__ __forceinline__ SE3 se3_mul(SE3 a, SE3 b) { return {qmul(a.q, b.q), qrot(a.q, b.p) + a.p}; }
 __device__ __forceinline__ SE3 se3_inv(SE3 a) { Q4 qi = qconj(a.q); return {qi, -1.0 * qrot(qi, a.p)}; }
 
-// SE3.log (mink/lie/se3.py:159-185): tangent (v, ω).
-__device__ __forceinline__ void se3_log(SE3 T, V3& v, V3& omega) {
+// SE3.log (mink/lie/se3.py:159-185): tangent (v, ω).  th: θ = |ω| where θ² ≥ 1e-10 (0 below: the Taylor branch takes no
+// root) — for se3_ljacinv of the same tangent, which would take the same root of the same θ² again.
+__device__ __forceinline__ void se3_log(SE3 T, V3& v, V3& omega, double& th) {
   omega = so3_log(T.q);
   const double th2 = dot(omega, omega);
   double k;  // coefficient of [ω]²
+  th = 0.0;
   if (th2 < 1e-10) {
     k = 1.0 / 12.0;
   } else {
-    const double th = sqrt(th2);
+    th = sqrt(th2);
     double s, c;
     sincos_cw(0.5 * th, &s, &c);
     k = (1.0 - th * c * fast_rcp(2.0 * s)) * fast_rcp(th2);
@@ -179,6 +181,7 @@ __device__ __forceinline__ void se3_log(SE3 T, V3& v, V3& omega) {
   V3 wt = cross(omega, T.p);
   v = T.p - 0.5 * wt + k * cross(omega, wt);
 }
+__device__ __forceinline__ void se3_log(SE3 T, V3& v, V3& omega) { double th; se3_log(T, v, omega, th); }
 
 // SE3.ljacinv(ξ) (mink/lie/se3.py:210-218) = [[J, −J·Q·J],[0, J]] with J = SO3.ljacinv(ω)
 // (so3.py:214-226) and Q = _getQ(ξ) (se3.py:222-249).  Returns J and Q (row-major 3x3);
@@ -188,7 +191,8 @@ __device__ __forceinline__ void se3_log(SE3 T, V3& v, V3& omega) {
 //   [w][v][w] = −(w·v)[w],  [v][w] + [w][v] = v wᵀ + w vᵀ − 2(w·v)I,
 //   [v][w]² − ([v][w]²)ᵀ = [w×(v×w)] − 2θ²[v],   [w]² = w wᵀ − θ²I,
 // i.e. the same matrix with O(10) instead of O(100) live registers.
-__device__ __forceinline__ void se3_ljacinv(V3 v, V3 w, double* J, double* Q, bool& ident) {
+// th_in: nullptr, or θ = √(w·w) from se3_log of this tangent or of its negative (read only where w·w ≥ 1e-10).
+__device__ __forceinline__ void se3_ljacinv(V3 v, V3 w, const double* th_in, double* J, double* Q, bool& ident) {
   const double th2 = dot(w, w);
   ident = th2 < 1e-10;
   if (ident) {
@@ -196,7 +200,7 @@ __device__ __forceinline__ void se3_ljacinv(V3 v, V3 w, double* J, double* Q, bo
     for (int i = 0; i < 9; ++i) { J[i] = (i % 4 == 0) ? 1.0 : 0.0; Q[i] = 0.0; }
     return;
   }
-  const double th = sqrt(th2);
+  const double th = th_in ? *th_in : sqrt(th2);
   double s, c;
   sincos_cw(th, &s, &c);
   // SO3.ljacinv: I − ½[ω] + A[ω]²   (θ ≥ 1e-5 here, never the θ < 1e-10 Taylor branch)
@@ -232,6 +236,9 @@ __device__ __forceinline__ void se3_ljacinv(V3 v, V3 w, double* J, double* Q, bo
       J[3 * i + j] = ((i == j) ? 1.0 : 0.0) - 0.5 * skw + A * w2;
       Q[3 * i + j] = sym + skq;
     }
+}
+__device__ __forceinline__ void se3_ljacinv(V3 v, V3 w, double* J, double* Q, bool& ident) {
+  se3_ljacinv(v, w, nullptr, J, Q, ident);
 }
 
 }  // namespace mkh

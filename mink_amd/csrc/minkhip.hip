@@ -934,6 +934,9 @@ static void fill_base(const MkhModel* m, DeviceProblem& P) {
   P.robot_root = 1;
   P.body_f = m->d_body_f; P.body_i = m->d_body_i; P.jnt_f = m->d_jnt_f; P.jnt_i = m->d_jnt_i;
   P.dof_i = m->d_dof_i; P.dof_f = m->d_dof_f;
+  // (joint anchors at the body origins — the G1, most menagerie robots: the kinematics skip rotating the zero offset)
+  P.jnt_pos_zero = 1;
+  for (double x : m->jnt_pos) if (x != 0.0) P.jnt_pos_zero = 0;
 }
 
 int32_t mkh_problem_create(MkhModel* m, const MkhProblemDesc* d, int32_t max_batch, MkhProblem** out) {
@@ -1288,6 +1291,34 @@ int32_t mkh_problem_create_diag(MkhModel* m, const MkhProblemDesc* d, int32_t ma
         if (P.wood_col[l] >= P.com_jrow0[t] && P.wood_col[l] < P.com_jrow0[t] + c)
           P.wood_mask[l] = m->nv >= 64 ? ~0ull : ((1ull << m->nv) - 1ull);
     }
+    // What a product lane used to work out of these tables in every solve.  Its dofs as a list: ascending, as the walk over
+    // the bits of wood_mask takes them (the order of the sums, hence every bit of S, stays), one byte each; every lane walks
+    // wood_trip entries, the longest list, a shorter one padded with a dof off its chain — that entry of its Jh row is the
+    // filled zero, and +0·b leaves a sum that started at +0 as it is.  No lists (wood_trip = 0, the lanes walk the mask)
+    // when a chain has more than kWoodList dofs or a shorter lane has no dof to pad with.
+    // Its stores: rows [wood_row0, +wood_rpc) below n_jrows go to S, row n_jrows — entry wood_jrhs of the one chunk that
+    // holds it — to w.
+    P.wood_trip = 0;
+    P.wood_jrhs = P.n_jrows % P.wood_rpc;
+    bool lists = true;
+    for (int l = 0; l < kWave; ++l) {
+      for (int i = 0; i < 4; ++i) P.wood_list[l][i] = 0;
+      if (P.wood_col[l] < 0) continue;
+      const int len = __builtin_popcountll(P.wood_mask[l]);
+      if (len > kWoodList) lists = false;
+      P.wood_trip = len > P.wood_trip ? len : P.wood_trip;
+    }
+    for (int l = 0; l < kWave && lists; ++l) {
+      if (P.wood_col[l] < 0) continue;
+      int n = 0, pad = -1;
+      for (int k = 0; k < 64; ++k) {
+        if ((P.wood_mask[l] >> k) & 1) { P.wood_list[l][n >> 2] |= (uint32_t)k << (8 * (n & 3)); ++n; }
+        else if (pad < 0 && k < m->nv) pad = k;
+      }
+      if (n < P.wood_trip && pad < 0) lists = false;
+      for (; n < P.wood_trip && lists; ++n) P.wood_list[l][n >> 2] |= (uint32_t)pad << (8 * (n & 3));
+    }
+    if (!lists) P.wood_trip = 0;
     return true;
   };
   // what the low-rank start's stability criterion compares (plan_launch(): damping + the smallest posture diagonal against the largest

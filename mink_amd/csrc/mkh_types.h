@@ -144,7 +144,17 @@ struct DeviceProblem {
   int32_t n_cv, n_cv_pad;
   const double* cv_contacts;       // [max_batch][n_cv][7], owned by the problem handle
   const PairCull* cull;  // one record per pair when n_pairs > 64, else nullptr (ik_kernel.h collision_phase)
+  // low-rank start: what the product lanes used to derive from wood_mask / wood_row0 in every solve (minkhip.hip wood_tables)
+  // wood_list[l]: the dofs of wood_mask[l] in ascending order, one byte each (entry i = byte i & 3 of word i >> 2), padded up
+  // to wood_trip entries with a dof OFF the lane's chain (its entry of the lane's Jh row is the filled zero);
+  // wood_trip: the longest list — every product lane walks that many entries —, or 0 when the lists do not apply (a chain of
+  // more than kWoodList dofs, or a shorter lane with no dof to pad with): then the lanes walk the bits of wood_mask
+  // wood_jrhs: the right-hand side (row n_jrows) is entry wood_jrhs of the chunk that holds it — one chunk, so one index
+  int32_t wood_trip, wood_jrhs;
+  int32_t jnt_pos_zero;  // every joint sits at its body's origin (jnt_pos == 0): anchor = xpos, no rotation of the offset
+  alignas(16) uint32_t wood_list[64][4];
 };
+constexpr int kWoodList = 16;      // entries of a lane's packed dof list (DeviceProblem::wood_list)
 
 struct SolveArgs {
   int32_t B;

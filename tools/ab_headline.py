@@ -6,7 +6,7 @@ import subprocess
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-args = [a for a in sys.argv[1:] if not a.startswith("--")]
+args = [a for i, a in enumerate(sys.argv[1:], 1) if not a.startswith("--") and sys.argv[i - 1] not in ("--config", "--rounds")]   # (library tags: not the options' values)
 cfg = sys.argv[sys.argv.index("--config") + 1] if "--config" in sys.argv else "g1_c3"
 rounds = int(sys.argv[sys.argv.index("--rounds") + 1]) if "--rounds" in sys.argv else 3
 code = ("import sys, json; sys.path.insert(0, %r); import bench, torch; "

@@ -38,7 +38,11 @@ def provenance(kernels: list) -> dict:
     linked at (mink_amd/build_info.json, written by build.py — the GPU box has no .git) and, per kernel of the timed solve,
     the sha256 of the kernel's code object (kernel_resources.json).  bench.py compares these with what IT loaded and ran."""
     out = {"kernels": [short_kernel_name(k) for k in kernels]}
-    lib = os.path.join(REPO, "mink_amd", "libminkhip.so")
+    # (MKH_LIB_TAG: the profiled run loaded an experiment build, mink_amd/_native.py — stamp that one: an A/B's parent profile
+    #  once carried the product library's hashes)
+    tag = os.environ.get("MKH_LIB_TAG", "")
+    sfx = f"_{tag}" if tag else ""
+    lib = os.path.join(REPO, "mink_amd", f"libminkhip{sfx}.so")
     try:
         h = hashlib.sha256()
         with open(lib, "rb") as fh:
@@ -48,14 +52,14 @@ def provenance(kernels: list) -> dict:
     except OSError:
         out["library_sha256"] = None
     try:
-        with open(os.path.join(REPO, "mink_amd", "build_info.json")) as fh:
+        with open(os.path.join(REPO, "mink_amd", f"build_info{sfx}.json")) as fh:
             info = json.load(fh)
         out["git_head"], out["git_dirty_sources"] = info.get("git_head"), info.get("git_dirty_sources")
         out["library_sha256_at_build"] = info.get("library_sha256")
     except (OSError, ValueError):
         out["git_head"] = None
     try:
-        with open(os.path.join(REPO, "mink_amd", "kernel_resources.json")) as fh:
+        with open(os.path.join(REPO, "mink_amd", f"kernel_resources{sfx}.json")) as fh:
             table = json.load(fh)
         out["kernel_code_sha256"] = {k: (table.get(k) or {}).get("code_sha256") for k in out["kernels"]}
     except (OSError, ValueError):
