@@ -12,6 +12,8 @@ with literal register numbers:
     load_*(lds_addr)          T[i] = lds[i]         whole column / leading rows / residual rows
     get_dyn(k) / set_dyn(k,x) single element, wave-uniform runtime index (VGPR index mode)
     get<I>() / set<I>(x)      single element, compile-time index (tableau build, taps)
+    load_gz / row_on_demand / hist_push   product form (maps of ≥ 36 rows): the range holds 18 rows of the low-rank factor and a
+                              history of pivots instead of a tableau; a row is formed when it is asked for
 
 Register maps (every primitive takes a `Regs&` first — an empty struct, kept so that call sites do not depend on the map):
 
@@ -184,6 +186,53 @@ def gen(nt: int, total: int = 0, name: str = "Tab") -> str:
         out.append(f"  __device__ static __forceinline__ void rank1_stream_{nr}(Regs& t, unsigned next, double g) {{")
         out.append(stmt(J(lines), ins='[g] "v"(g), [an] "v"(next)', clob=clob_tmp + ', "memory"'))
         out.append("  }")
+    # product form of the low-rank builds without half-space rows (ik_kernel.h kProduct): no tableau at all.  The range holds
+    #   rows [0, KMU)                 gz[r] = Z[r][lane]/d_r — the lane's column of the factor, scaled as the tableau's build loop scaled it
+    #   rows [KMU + 2q, KMU + 2q + 2) history slot q < P: (−g_q[lane], own_q[lane]) of past pivot q
+    # and row `col` of the dof block is formed when it is asked for: Σ_r Z[r][col]·gz[r] in ascending r, then one FMA per past pivot in
+    # pivot order — the FMA sequence the tableau register `col` went through (terms with a zero operand, skipped there, add +0 here).
+    if nt >= 2 * PF_KMU:      # (the 1/d_r of load_gz pass through rows [KMU, 2·KMU))
+        P = (nt - PF_KMU) // 2
+        h0 = t0 + 2 * PF_KMU
+        out.append(f"  static constexpr int kHist = {P};   // history slots of the product form")
+        lines = [f"ds_read_b64 {treg(r)}, %[a] offset:{8 * nt * r}" for r in range(PF_KMU)]
+        lines += [f"ds_read_b64 {treg(PF_KMU + r)}, %[d] offset:{8 * r}" for r in range(PF_KMU)]      # (1/d_r through the history rows: free until the first pivot)
+        lines.append("s_waitcnt lgkmcnt(0)")
+        lines += [f"v_mul_f64 {treg(r)}, {treg(r)}, {treg(PF_KMU + r)}" for r in range(PF_KMU)]
+        for r in reversed(range(PF_KMU)):                                                          # rows ≥ n_μ: zero
+            lines += [f"s_cmp_gt_i32 %[n], {r}", "s_cbranch_scc1 .Lgz_%=", f"v_mov_b64 {treg(r)}, 0"]
+        lines.append(".Lgz_%=:")
+        out.append(f"  // gz[r] = lds[a + {nt}·r]·lds[d + r] for r < n (n ≤ {PF_KMU}), 0 above: the lane's column of Z (row stride {nt}) times 1/d_r")
+        out.append("  __device__ static __forceinline__ void load_gz(Regs& t, unsigned lane_addr, unsigned dinv_addr, int n) {")
+        out.append("    n = __builtin_amdgcn_readfirstlane(n);")
+        out.append(stmt(J(lines), ins='[a] "v"(lane_addr), [d] "v"(dinv_addr), [n] "s"(n)', clob='"scc", "memory"'))
+        out.append("  }")
+        lines = ["s_nop 4"]
+        lines += [f"v_fmac_f64_dpp %[acc], %[p{r // 16}], {treg(r)} row_newbcast:{r % 16} row_mask:0xf bank_mask:0xf" for r in range(PF_KMU)]
+        for q in range(P):
+            o = h0 + 4 * q
+            lines += [f"s_cmp_le_i32 %[np], {q}", "s_cbranch_scc1 .Lrow_%=",
+                      f"v_readlane_b32 vcc_lo, v{o + 2}, %[c]", f"v_readlane_b32 vcc_hi, v{o + 3}, %[c]",
+                      f"v_fmac_f64 %[acc], vcc, v[{o}:{o + 1}]"]
+        lines.append(".Lrow_%=:")
+        out.append("  // row `col` of the dof block for this lane: p0 / p1 = Z[r][col] in 16-lane planes (lane l holds r = l % 16 and 16 + l % 16),")
+        out.append("  // then −own_q[col]·g_q for the npiv past pivots (own_q[col] is wave-uniform: read from lane `col`)")
+        out.append("  __device__ static __forceinline__ double row_on_demand(Regs& t, double p0, double p1, int col, int npiv) {")
+        out.append("    double acc = 0.0;")
+        out.append("    col = __builtin_amdgcn_readfirstlane(col); npiv = __builtin_amdgcn_readfirstlane(npiv);   // (an \"s\" operand is not made uniform for us)")
+        out.append(stmt(J(lines), outs='[acc] "+v"(acc)', ins='[p0] "v"(p0), [p1] "v"(p1), [c] "s"(col), [np] "s"(npiv)', clob='"vcc", "scc"'))
+        out.append("    return acc;")
+        out.append("  }")
+        out.append("  // history slot npiv (wave-uniform, < kHist) = (ng, own)")
+        out.append("  __device__ static __forceinline__ void hist_push(Regs& t, int npiv, double ng, double own) {")
+        out.append("    const int idx = __builtin_amdgcn_readfirstlane(4 * npiv);")
+        body = J(["s_set_gpr_idx_on %[i], gpr_idx(DST)", f"v_mov_b32 v{h0}, %[gl]", f"v_mov_b32 v{h0 + 1}, %[gh]",
+                  f"v_mov_b32 v{h0 + 2}, %[ol]", f"v_mov_b32 v{h0 + 3}, %[oh]", "s_set_gpr_idx_off", "s_nop 1"])
+        out.append(stmt(body, ins='[gl] "v"(__double2loint(ng)), [gh] "v"(__double2hiint(ng)), [ol] "v"(__double2loint(own)), [oh] "v"(__double2hiint(own)), [i] "s"(idx)',
+                        clob='"m0"'))
+        out.append("  }")
+    else:
+        out.append("  static constexpr int kHist = 0;    // (no product form on this map)")
     # get / set with compile-time index
     out.append("  template <int I> __device__ static __forceinline__ double get(Regs& t) {")
     out.append("    int lo, hi;")
@@ -205,6 +254,7 @@ def gen(nt: int, total: int = 0, name: str = "Tab") -> str:
     return "\n".join(out)
 
 
+PF_KMU = 18        # product form (gen): rows of the factor kept per lane = ik_kernel.h kMu
 KMUS = (18, 24)   # row capacities of the low-rank start's elimination (ik_kernel.h kMu*): task residuals of one problem
 
 

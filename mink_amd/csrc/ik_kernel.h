@@ -27,7 +27,9 @@
 //                             per lane — and the dof block −H⁻¹ is built by rank-1 updates that do not
 //                             depend on each other (wood_start); a cold G1-size solve first
 //                             re-eliminates for the bounds its unconstrained minimiser violates, so that the
-//                             tableau starts with those dofs on their bounds (wood_eliminate).
+//                             tableau starts with those dofs on their bounds (wood_eliminate).  The humanoid-size builds
+//                             without half-space rows do not build the dof block at all: a row is formed from the factors
+//                             when a pivot asks for it, past pivots are a history in the pinned range (publish_row).
 // Per-problem J rows, task blocks, poses and half-space rows are staged in LDS.
 // Kernel builds with one more resident wave per SIMD (_w3: 168 / 128 registers) run the phases that need many
 // registers — kinematics, Lie algebra, Jacobian rows, the elimination — as real function calls (pre_phases,
@@ -332,6 +334,63 @@ __device__ __forceinline__ void pivot(typename MKH_TAB<NT>::Regs& ts, QpLane& s,
     s.sg = (reverse ? -sk : sk) * inv;           // row/column k scaled by ±1/d
   } else {
     s.D = fma(-ck * inv, ck, s.D);               // T[j][j] −= T[j][k]²/d
+  }
+}
+
+// Product form of the low-rank builds without half-space rows (kProduct in the kernel): the dof block of the
+// tableau is never built.  R₀[i][j] = Σ_r Z[r][i]·Z[r][j]/d_r stays in its factors — Z in LDS as wood_start left it, the lane's
+// own column gz[r] = Z[r][j]/d_r in the first kMu pinned rows — and every pivot q leaves (−g_q[j], own_q[j]) in a history slot
+// instead of a rank-1 update of 44 rows.  Row `col` is formed when the active set asks for it: kMu broadcast FMAs in ascending
+// r, then one FMA per past pivot in pivot order — exactly the FMAs the tableau register `col` of this lane went through (the
+// tableau's build and updates skipped terms with a zero operand; here they add +0), so the solve is bit for bit the tableau's
+// until the history is full.  Then the solve is started again from its current active set (the kernel: `refac`).
+// Same contract as publish_column: the pivot lane's scalars through one LDS round trip, issued ahead of the FMAs.
+template <int NT, bool FULL = false>
+__device__ __forceinline__ double publish_row(typename MKH_TAB<NT>::Regs& ts, const QpLane& s, int col, int lane, double* sPiv, const double* sJ,
+                                              int n_mu, int npiv, PivotScalars& ps, int nact, double rown = 1.0) {
+  wave_sync();                                   // earlier readers of the scalar slots are done
+  if (lane == col) {
+    double2* o = reinterpret_cast<double2*>(sPiv + kWave);
+    o[0] = double2{s.D, s.sg};
+    o[1] = double2{s.x, rown};
+    if (FULL) o[2] = double2{s.lo, s.hi};
+  }
+  // Z[r][col] in two 16-lane planes (rows ≥ n_μ of the array are the parked right-hand side and whatever follows: +0)
+  const int r0 = lane & 15;
+  const double* zc = sJ + col;
+  const double p0 = (r0 < n_mu) ? zc[r0 * NT] : 0.0, p1 = (r0 + 16 < n_mu) ? zc[(r0 + 16) * NT] : 0.0;
+  wave_sync();
+  const double2* o = reinterpret_cast<const double2*>(sPiv + kWave);
+  const double2 a = o[0], b = o[1];
+  ps.d = a.x; ps.sg = a.y; ps.x = b.x; ps.rn = b.y;
+  if (FULL) {
+    const double2 c = o[2];
+    ps.lo = c.x; ps.hi = c.y;
+  }
+  double rowv = 0.0;
+  if constexpr (MKH_TAB<NT>::kHist > 0) rowv = MKH_TAB<NT>::row_on_demand(ts, p0, p1, col, npiv);
+  return (lane == col || lane >= nact) ? 0.0 : rowv;   // (publish_column's rule)
+}
+// gz[r] = Z[r][lane]/d_r, r < n_μ, into the first kMu pinned rows (Z with row stride NT at sJ, 1/d_r at sDinv)
+template <int NT>
+__device__ __forceinline__ void load_factor_column(typename MKH_TAB<NT>::Regs& ts, const double* sJ, const double* sDinv, int lane, int n_mu) {
+  // (lanes ≥ NT own nothing and publish 0: any finite column)
+  if constexpr (MKH_TAB<NT>::kHist > 0) MKH_TAB<NT>::load_gz(ts, lds_addr(sJ + (lane < NT ? lane : 0)), lds_addr(sDinv), n_mu);
+}
+// pivot() without a tableau: the multiplier and the published entry go to history slot npiv
+template <int NT>
+__device__ __forceinline__ void pivot_product(typename MKH_TAB<NT>::Regs& ts, QpLane& s, int k, bool reverse, int lane, double own,
+                                              const PivotScalars& ps, double inv, int& npiv) {
+  const double sk = ps.sg;
+  const double ck = s.sg * sk * own;             // true T[lane][k]
+  const double g = (sk * sk) * own * inv;        // R-units multiplier of this lane's column
+  if constexpr (MKH_TAB<NT>::kHist > 0) MKH_TAB<NT>::hist_push(ts, npiv, -g, own);     // a later row c takes fma(own[c], −g, ·): the update R[c][lane] −= R[c][k]·g
+  ++npiv;
+  if (lane == k) {
+    s.D = -inv;
+    s.sg = (reverse ? -sk : sk) * inv;
+  } else {
+    s.D = fma(-ck * inv, ck, s.D);
   }
 }
 
@@ -1982,6 +2041,10 @@ void MKH_KERNEL_NAME(const DeviceProblem* __restrict__ Pg, const SolveArgs A_k, 
   static_assert(!kWood || !kRel, "low-rank start: frame / posture / CoM tasks, box limits and (round 6) half-space rows");
   constexpr bool kWoodRows = kWood && kRows;       // low-rank start with half-space rows (wood_start "half-space rows")
   static_assert(!kWoodRows || NR == NT, "the rows' columns of the elimination live in the tableau-wide rows of Jh");
+  // Product form (publish_row above): the humanoid-size low-rank builds without half-space rows, ComTask rows or a fused loop keep
+  // no tableau — kMu rows of the factor and kHist history slots of two rows each in the pinned range.
+  constexpr int kHist = MKH_TAB<NT>::kHist;
+  constexpr bool kProduct = kWood && !kWoodRows && !kCom && !kSteps && NT == 44 && NR == NT && kHist > 0 && NT - kMu >= 2 * kHist;
 #ifdef MKH_W3
   constexpr bool kCompact = true;            // LDS ranges aliased by phase (lds_layout): 12 waves per CU need ≤ 13.3 KB each
   static_assert(!kColl, "compact LDS layout: the collision phase reads the body poses after the Jacobian rows");
@@ -2194,6 +2257,11 @@ void MKH_KERNEL_NAME(const DeviceProblem* __restrict__ Pg, const SolveArgs A_k, 
     // (variants with half-space rows run Goldfarb–Idnani only: no block step to seed)
     const bool warm_in = !kRows && A.warm != nullptr && A.warm_age >= 2;
     if (!kRows && warm_in && lane < nv) prev_bound = A.warm[(size_t)pb * nv + lane];
+    // product form, history full: the step is started again from the active set it has reached (prev_bound), as a warm start is —
+    // the factors are rebuilt for that set (wood_start), nothing is materialised.  Iterations keep counting.
+    // The block steps go on where they were (the state is the same state): started afresh after every refactorisation they
+    // flip-flop for good on ill-conditioned, heavily saturated problems (two of the 24 golden instances: 350 pivots, status 8).
+    int refac = 0, iters_carry = 0, best_carry = 4 * kWave, outer_carry = 0;
 #if !(MKH_FEAT & 16)
     // (no fused loop in this build: ONE step, and no loop for the compiler to carry values around — as a single-trip `for` it still was
     //  one to the compiler: a dozen to twenty spilled SGPRs less in every build; plugin workload 1.643 → 1.603 ms, G1 full example 1.231
@@ -2204,6 +2272,8 @@ void MKH_KERNEL_NAME(const DeviceProblem* __restrict__ Pg, const SolveArgs A_k, 
     for (int step = 0; step < n_steps + (until ? 1 : 0); ++step) {
 #endif
     int status = 0;
+    const bool refac_in = kProduct && refac != 0;
+    refac = 0;
     tci = 1;                                                 // phase stamps 1..7 belong to the current step
 
     // FK, joint axes / dof lanes, subtree CoM, frame-task lanes (pre_phases above)
@@ -2408,7 +2478,7 @@ void MKH_KERNEL_NAME(const DeviceProblem* __restrict__ Pg, const SolveArgs A_k, 
     int pred = 0;
     double pred_beta = 0.0;
     if constexpr (kWood) {
-      if ((kSteps && step >= 2) || (warm_in && step == 0)) pred = prev_bound;
+      if ((kSteps && step >= 2) || (warm_in && step == 0) || refac_in) pred = prev_bound;
       if ((pred == 2 && !(hi < kInf)) || (pred == 1 && !(lo > -kInf)) || !is_dof) pred = 0;
       pred_beta = (pred == 2) ? hi : ((pred == 1) ? lo : 0.0);
     }
@@ -2435,34 +2505,39 @@ void MKH_KERNEL_NAME(const DeviceProblem* __restrict__ Pg, const SolveArgs A_k, 
       pred = wo.clamp;                         // (cold start: the bounds the unconstrained minimiser violates)
       hdiag = wo.hdiag;
       if (MKH_CLK) ta[3] -= __builtin_readcyclecounter();
-      MKH_TAB<NT>::zero(ts);
-      if constexpr (kWoodRows) {
-        // the rows' block before the rank-1 updates: column nv + s (lane nv + s) = (Ah[s][·] | −Ah·Ah[s]ᵀ), rows nv + s of the dof
-        // columns = Ah[s][lane] (wood_start scaled the staged rows in place and left the Gram entries in the contact table)
-        if (nrows > 0) {
-          const bool row_lane = lane >= nv && lane < nv + nrows;
-          if (row_lane) load_leading_rows<NT>(ts, lds_addr(sA + (lane - nv) * AS), AS);   // (entries ≥ nv of a staged row are zero)
-          for (int sr = 0; sr < nrows; ++sr)
-            MKH_TAB<NT>::set_dyn(ts, nv + sr, is_dof ? sA[sr * AS + lane] : (row_lane ? -sCol[(lane - nv) * 16 + sr] : 0.0));
+      if constexpr (kProduct) {
+        // no dof block: the lane's column of Z, scaled by 1/d_r as the build loop below scales it, into the first kMu pinned rows
+        load_factor_column<NT>(ts, sJ, sPiv + kWoodRow, lane, P.n_jrows);
+      } else {                                  // every other build: the dof block of the tableau
+        MKH_TAB<NT>::zero(ts);
+        if constexpr (kWoodRows) {
+          // the rows' block before the rank-1 updates: column nv + s (lane nv + s) = (Ah[s][·] | −Ah·Ah[s]ᵀ), rows nv + s of the dof
+          // columns = Ah[s][lane] (wood_start scaled the staged rows in place and left the Gram entries in the contact table)
+          if (nrows > 0) {
+            const bool row_lane = lane >= nv && lane < nv + nrows;
+            if (row_lane) load_leading_rows<NT>(ts, lds_addr(sA + (lane - nv) * AS), AS);   // (entries ≥ nv of a staged row are zero)
+            for (int sr = 0; sr < nrows; ++sr)
+              MKH_TAB<NT>::set_dyn(ts, nv + sr, is_dof ? sA[sr * AS + lane] : (row_lane ? -sCol[(lane - nv) * 16 + sr] : 0.0));
+          }
         }
-      }
-      const int n_mu = P.n_jrows;
-      const double* const sDinv = sPiv + kWoodRow;
-      // (streamed: the statement of row r requests the planes of row r + 1 behind its own FMAs, Z[r + 1][lane] is read one
-      //  trip ahead — 18 updates × (LDS round trip + 44 FMAs) back to back were 14 % of a G1 solve)
-      const unsigned lane_off = (unsigned)(lane & 15) << 3;
-      double zr = (lane < NT && n_mu > 0) ? sJ[lane] : 0.0;
-      MKH_TAB<NT>::rank1_prefetch(ts, lds_addr(sJ));
+        const int n_mu = P.n_jrows;
+        const double* const sDinv = sPiv + kWoodRow;
+        // (streamed: the statement of row r requests the planes of row r + 1 behind its own FMAs, Z[r + 1][lane] is read one
+        //  trip ahead — 18 updates × (LDS round trip + 44 FMAs) back to back were 14 % of a G1 solve)
+        const unsigned lane_off = (unsigned)(lane & 15) << 3;
+        double zr = (lane < NT && n_mu > 0) ? sJ[lane] : 0.0;
+        MKH_TAB<NT>::rank1_prefetch(ts, lds_addr(sJ));
 #pragma nounroll
-      for (int r = 0; r < n_mu; ++r) {
-        const double g = zr * sDinv[r];
-        // dof rows the row reaches: [0, hb) (zero outside the kinematic chains eliminated so far)
-        const unsigned long long nzd = __ballot(zr != 0.0);
-        const int hb = nzd ? 64 - __builtin_clzll(nzd) : 0;
-        zr = (lane < NT) ? sJ[(r + 1) * NT + lane] : 0.0;          // (row n_μ exists: the parked Σ Jh²)
-        rank1_stream_rows<NT>(ts, lds_addr(sJ + (r + 1) * NT) + lane_off, g, hb);
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");           // the planes requested by the last statement are not used
+        for (int r = 0; r < n_mu; ++r) {
+          const double g = zr * sDinv[r];
+          // dof rows the row reaches: [0, hb) (zero outside the kinematic chains eliminated so far)
+          const unsigned long long nzd = __ballot(zr != 0.0);
+          const int hb = nzd ? 64 - __builtin_clzll(nzd) : 0;
+          zr = (lane < NT) ? sJ[(r + 1) * NT + lane] : 0.0;          // (row n_μ exists: the parked Σ Jh²)
+          rank1_stream_rows<NT>(ts, lds_addr(sJ + (r + 1) * NT) + lane_off, g, hb);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");           // the planes requested by the last statement are not used
+      }  // !kProduct
       if (MKH_CLK) { asm volatile("s_waitcnt lgkmcnt(0)"); ta[3] += __builtin_readcyclecounter(); }   // (− start below)
     }
     auto frame_column = [&](int t, int k, uint64_t mask, uint64_t rmask, bool rel, double (&Jt)[6]) {
@@ -2714,7 +2789,7 @@ void MKH_KERNEL_NAME(const DeviceProblem* __restrict__ Pg, const SolveArgs A_k, 
     const double hmax = wave_max(is_dof ? hdiag : 0.0);
     const double thr_dof = 1e-13 * fast_rcp(hmax * (double)nv);
 
-    int iters = 0;
+    int iters = kProduct ? iters_carry : 0;
     const int max_iters = 8 * (ntab + 8);
     // ---- phase 0: bring every dof into the basis, x0 = −H⁻¹c (Gauss–Jordan, no ratio tests).
     // Tight loop: publish row k → (LDS loads of the rank-1 update already in flight) → 1/d,
@@ -2781,6 +2856,12 @@ void MKH_KERNEL_NAME(const DeviceProblem* __restrict__ Pg, const SolveArgs A_k, 
     MKH_STOP(9);
     const int nact = (kWood && !kRows) ? nv : kWave;         // lanes that still own a live index
     int n_loop = 0, n_piv = 0;   // profiling (qp_iters tap): loop iterations / rank-1 pivots after x0
+    int npiv = 0;                // product form: history slots in use
+    // (wave-uniform, but carried through loops that end on the per-lane status word: tested as scalars, or every test is a
+    //  divergent branch and the loops' values are copied around it)
+    auto hist_full = [&]() -> bool { return kProduct && uni(npiv) == kHist; };
+    auto refac_set = [&]() -> bool { return kProduct && uni(refac) != 0; };
+    const int n_mu_q = kProduct ? P.n_jrows : 0;
     // ---- phase 1a (box limits only): block principal pivoting.  lo ≤ x ≤ hi with H ≻ 0 is a bound-constrained
     // LCP with a P-matrix; Júdice & Pires (1994): flip ALL infeasible indices at once — free dofs outside their
     // bounds onto the violated bound, bound dofs whose multiplier has the wrong sign back into the basis.  On
@@ -2807,8 +2888,12 @@ void MKH_KERNEL_NAME(const DeviceProblem* __restrict__ Pg, const SolveArgs A_k, 
       auto flip = [&](int k, bool kb, bool up) {
         PivotScalars ps;
                 MKH_LAP0();
-        const double own = publish_column<NT, true>(ts, s, k, lane, sPiv, ps, nact, 1.0);
-        MKH_TAB<NT>::rank1_prefetch(ts, lds_addr(sPiv));
+        double own;
+        if constexpr (kProduct) own = publish_row<NT, true>(ts, s, k, lane, sPiv, sJ, n_mu_q, npiv, ps, nact, 1.0);
+        else {
+          own = publish_column<NT, true>(ts, s, k, lane, sPiv, ps, nact, 1.0);
+          MKH_TAB<NT>::rank1_prefetch(ts, lds_addr(sPiv));
+        }
         MKH_LAP(3);
         if (__ballot(!((kb ? -ps.d : ps.d) > 0.0))) { status |= 4; asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); return; }
         const double inv = fast_rcp(ps.d);
@@ -2822,11 +2907,13 @@ void MKH_KERNEL_NAME(const DeviceProblem* __restrict__ Pg, const SolveArgs A_k, 
         }
         ++n_piv;
         MKH_LAP(4);
-        pivot<NT, NR>(ts, s, k, kb, lane, sPiv, own, ps, inv);
+        if constexpr (kProduct) pivot_product<NT>(ts, s, k, kb, lane, own, ps, inv, npiv);
+        else pivot<NT, NR>(ts, s, k, kb, lane, sPiv, own, ps, inv);
         MKH_LAP(5);
       };
-      int best = 4 * kWave;
-      for (int outer = 0;; ++outer) {
+      int best = kProduct ? best_carry : 4 * kWave;
+      int outer = kProduct ? outer_carry : 0;
+      for (;; ++outer) {
         ++n_loop;
         const bool is_b = s.sel == 1;                                     // basic dof
         const unsigned long long m_over = __ballot(is_b && (s.x - s.hi > 1e-12));
@@ -2852,16 +2939,21 @@ void MKH_KERNEL_NAME(const DeviceProblem* __restrict__ Pg, const SolveArgs A_k, 
           if (w_any) { m_basic = w_any; m_up = __ballot(is_b && prev_bound == 2); todo = w_any; }
         }
         while (todo && !(status & 14)) {
+          if (hist_full()) { refac = 1; break; }                           // history full, between flips: refactorise
           const int k = (int)__builtin_ctzll(todo);
           todo &= todo - 1;
           flip(k, ((m_basic >> k) & 1) != 0, ((m_up >> k) & 1) != 0);
         }
         if (status & 14) break;
+        if (refac_set()) { ++outer; break; }                              // (the interrupted block step counts)
       }
+      if constexpr (kProduct) { best_carry = best; outer_carry = outer; }
       // hand-over: release wrong-signed multipliers until the state is dual feasible (what Goldfarb–Idnani needs)
       while (need_gi && !(status & 14)) {
+        if (refac_set()) break;
         const unsigned long long m_wrong = __ballot(s.elig != 0 && xor_sign(s.x, s.ysign) < -tolw);
         if (!m_wrong) break;
+        if (hist_full()) { refac = 1; break; }
         if (++iters > max_iters) { status |= 8; break; }
         flip((int)__builtin_ctzll(m_wrong), false, false);
       }
@@ -2876,6 +2968,7 @@ void MKH_KERNEL_NAME(const DeviceProblem* __restrict__ Pg, const SolveArgs A_k, 
     bool pend_rev = false;
     const double inv_rown = (kRows && rown > 0.0) ? fast_rcp(rown) : 0.0;
     while (need_gi && !(status & 14)) {
+      if (refac_set()) break;
       MKH_MARK("gi_iter_begin");
             ++n_loop;
       MKH_LAP0();
@@ -2905,8 +2998,12 @@ void MKH_KERNEL_NAME(const DeviceProblem* __restrict__ Pg, const SolveArgs A_k, 
       MKH_MARK("gi_publish");
       PivotScalars ps;
       MKH_LAP(2);
-      const double own = publish_column<NT, true>(ts, s, col, lane, sPiv, ps, nact, rown);
-      MKH_TAB<NT>::rank1_prefetch(ts, lds_addr(sPiv));
+      double own;
+      if constexpr (kProduct) own = publish_row<NT, true>(ts, s, col, lane, sPiv, sJ, n_mu_q, npiv, ps, nact, rown);
+      else {
+        own = publish_column<NT, true>(ts, s, col, lane, sPiv, ps, nact, rown);
+        MKH_TAB<NT>::rank1_prefetch(ts, lds_addr(sPiv));
+      }
       MKH_LAP(3);
       const double inv = fast_rcp(ps.d);                         // 1 / T[col][col]
       bool rev = false;
@@ -2977,8 +3074,19 @@ void MKH_KERNEL_NAME(const DeviceProblem* __restrict__ Pg, const SolveArgs A_k, 
       MKH_MARK("gi_pivot");
       ++n_piv;
       MKH_LAP(4);
-      pivot<NT, NR>(ts, s, col, rev, lane, sPiv, own, ps, inv);
+      // (product form, history full — between two drives, or in one: the drive is abandoned.  The flags already say where
+      //  every index sits, the pivot that would have followed is part of the rebuilt factors.)
+      if (hist_full()) { refac = 1; break; }
+      if constexpr (kProduct) pivot_product<NT>(ts, s, col, rev, lane, own, ps, inv, npiv);
+      else pivot<NT, NR>(ts, s, col, rev, lane, sPiv, own, ps, inv);
       MKH_LAP(5);
+    }
+    if (refac_set()) {
+      // start the step again with the active set as the prediction; a refactorisation counts as the kHist pivots it closes, so
+      // that a cycle still ends in MKH_ST 8
+      iters_carry = iters + kHist;
+      if (iters_carry > max_iters) { status |= 8; refac = 0; }
+      else { prev_bound = (is_dof && !s.usign) ? (s.ysign ? 2 : 1) : 0; continue; }
     }
     // Δq of this dof: the free value when basic, else the bound it sits on
     const double zfin = s.usign ? s.x : (s.ysign ? s.hi : s.lo);
@@ -3057,7 +3165,7 @@ void MKH_KERNEL_NAME(const DeviceProblem* __restrict__ Pg, const SolveArgs A_k, 
       wave_sync();
     }
 #if !(MKH_FEAT & 16)
-    } while (0);
+    } while (kProduct && uni(refac) != 0);
 #else
     }  // step loop
 #endif
