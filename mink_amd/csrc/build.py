@@ -46,7 +46,10 @@ W3_WOOD = ((44, 44, 32), (44, 44, 48), (32, 32, 32), (32, 32, 48),    # (NT, NR,
 # loop's machinery (ticket draws, double-buffered inputs, loop-carried scalars) — launched when the grid is the batch (minkhip.hip plan_launch()).
 # Measured: `44_32_r44_w3o` 0.713 -> 0.703 ms on the headline; the F_COM twin `44_36_r44_w3o` (12 spilled VGPRs) 0.350 -> 0.352 ms at
 # 16 384 instances of the G1 full example — not built.
-W3_WOOD_ONE_SHOT = ((44, 44, 32),)
+# ... and its twin on FOUR waves per SIMD, `44_32_r44_w4o` (a fourth entry "w4"; ik_kernel.h MKH_W4P, tab_asm.inc TabW4<44>: the product form
+# alone below 128 VGPRs, history slots of one double, everything in LDS that is dead after the pair lanes in one union) — the headline's
+# build from the batch size at which it measures faster (minkhip.hip plan_launch()).
+W3_WOOD_ONE_SHOT = ((44, 44, 32), (44, 44, 32, "w4"))
 WOOD_FEATS = (32, 48, 33, 36, 52)      # F_WOOD, | F_STEPS, | F_TAPS (cycle-counter profiling only), | F_COM, | F_COM | F_STEPS
 # low-rank start WITH half-space rows (round 6; ik_kernel.h wood_start "half-space rows"): (NT, NR, FEAT) on the 2-waves map,
 # NR = NT (the rows' columns of the elimination sit behind the dofs in the tableau-wide rows of Jh).
@@ -62,16 +65,19 @@ class Variant(NamedTuple):
     nr: int = 0
     w3: bool = False
     one_shot: bool = False
+    w4 = False                 # (class attribute, not a field: VariantW4 below)
 
     @property
     def name(self) -> str:
-        return f"{self.nt}_{self.feat}" + (f"_r{self.nr}" if self.nr else "") + ("_w3" if self.w3 else "") + ("o" if self.one_shot else "")
+        return f"{self.nt}_{self.feat}" + (f"_r{self.nr}" if self.nr else "") + (("_w4" if self.w4 else "_w3") if self.w3 else "") + ("o" if self.one_shot else "")
 
     def translation_unit(self) -> str:
         defs = [f"MKH_NT {self.nt}"] + ([f"MKH_NR {self.nr}"] if self.nr else []) + [f"MKH_FEAT {self.feat}"]
         if self.w3:
             defs.append("MKH_W3 1")
-            if self.nr and self.nt <= 24 and not self.one_shot:
+            if self.w4:
+                defs.append("MKH_W4P 1")           # (the four-waves product-form map of the humanoid-size twin)
+            elif self.nr and self.nt <= 24 and not self.one_shot:
                 defs.append("MKH_W4 1")            # (the 4-waves map of the small low-rank builds, W3_WOOD)
         if self.one_shot:
             defs.append("MKH_ONE_SHOT 1")
@@ -87,6 +93,13 @@ void launch_{self.name}(int grid, int lds_bytes, hipStream_t stream, const Devic
 """
 
 
+class VariantW4(Variant):
+    """The twin of a one-more-wave build on the four-waves product-form map: the same five fields — the host's table tells the two
+    apart by the kernel's name, `_w4` for `_w3`."""
+    __slots__ = ()
+    w4 = True
+
+
 # every compiled build, once: the translation units, the host's table (_build/dispatch.hip → variants.h) and
 # kernel_resources.json all follow from this list
 VARIANTS = tuple([Variant(nt, ft) for nt in NTS for ft in FEATS]
@@ -94,7 +107,7 @@ VARIANTS = tuple([Variant(nt, ft) for nt in NTS for ft in FEATS]
                  + [Variant(nt, ft, nr) for nt, nr, ft in WOOD_ROWS]
                  + [Variant(nt, ft, w3=True) for nt, ft in W3]
                  + [Variant(nt, ft, nr, w3=True) for nt, nr, ft in W3_WOOD]
-                 + [Variant(nt, ft, nr, w3=True, one_shot=True) for nt, nr, ft in W3_WOOD_ONE_SHOT])
+                 + [(VariantW4 if e[3:] == ("w4",) else Variant)(e[0], e[2], e[1], w3=True, one_shot=True) for e in W3_WOOD_ONE_SHOT])
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-null-conversion"]
 # experiments: extra compiler flags for every translation unit (e.g. MKH_EXTRA_FLAGS="-DMKH_FORCE_COLL_CALL"); part of the
 # per-object command tag, so changing it recompiles

@@ -45,6 +45,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 NTS = (8, 16, 24, 32, 44, 48, 64)
 W3_NTS = (32, 44)   # tableaus that also get the 3-waves-per-SIMD map (TabW3<NT>: TOP = 168)
 W4_NTS = (16, 24)       # ... and the 4-waves-per-SIMD map (TabW4<NT>: TOP = 128; Tab<16> / Tab<24> are 3-waves maps)
+W4_PRODUCT_NT, W4_PRODUCT_HIST = 44, 13   # TabW4<44>: the product form alone (gen_w4_product) — 18 factor rows + 13 one-double slots (as many as the three-waves maps hold in two doubles: the builds refactorise at the same pivots, bit for bit)
 def total_for(nt):
     # VGPRs per lane = 512 / resident waves per SIMD: small tableaus leave room for 4 (NT ≤ 8) or 3 (NT ≤ 24)
     # waves per SIMD instead of 2 — more waves hide more of the serial pivot chain (UR5e-class arms)
@@ -254,6 +255,96 @@ def gen(nt: int, total: int = 0, name: str = "Tab") -> str:
     return "\n".join(out)
 
 
+def gen_w4_product(nt: int, P: int) -> str:
+    """TabW4<44>: the product form ALONE below 128 VGPRs — 4 resident waves per SIMD for the 44-lane builds (ik_kernel.h MKH_W4P).
+    No tableau, so no tableau primitives and no staging registers: the pinned range is PF_KMU factor rows gz[r] and P history
+    slots of ONE double, own_q[lane].  The multiplier of a slot is formed again whenever a row is asked for, from the pivot's two
+    wave-uniform scalars σ_k² and 1/d (LDS: slot q = doubles 2q, 2q + 1 of the scalar array), with the pivot's own multiplications
+    in the pivot's order — ((σ_k²)·own_q[j])·(1/d) — and taken as fma(own_q[col], −g, acc): the operands, hence the bits, of the
+    two-double slot's stored −g_q.  The primitives the tableau builds call by name are declared and NOT defined: a use that survives
+    to code generation fails the device link."""
+    TOTAL = 128
+    K = PF_KMU
+    t0 = TOTAL - 2 * (K + P)
+    h0 = t0 + 2 * K
+    treg = lambda i: f"v[{t0 + 2 * i}:{t0 + 2 * i + 1}]"
+    hreg = lambda q: f"v[{h0 + 2 * q}:{h0 + 2 * q + 1}]"
+    clob_t = ",".join(f'"v{r}"' for r in range(t0, TOTAL))
+    J = "\\n\\t".join
+    assert 2 * P >= K and t0 % 2 == 0
+    out = [f"template <> struct TabW4<{nt}> {{",
+           f"  static constexpr int kRows = {nt};",
+           f"  static constexpr int kCompilerVgprs = {t0};",
+           f"  static constexpr int kHist = {P};   // history slots of the product form, one double each",
+           "  static constexpr bool kOneDouble = true;",
+           "  struct Regs {};",
+           "  // (tableau primitives: declared for the builds that name them in discarded branches, never defined)",
+           "  __device__ static void zero(Regs&);",
+           "  __device__ static void rank1_prefetch(Regs&, unsigned);",
+           "  __device__ static void rank1_body_pub(Regs&, unsigned, double, unsigned, double);",
+           "  __device__ static double get_dyn(Regs&, int);",
+           "  __device__ static void set_dyn(Regs&, int, double);",
+           "  template <int I> __device__ static double get(Regs&);",
+           "  template <int I> __device__ static void set(Regs&, double);"]
+    out.append("  __device__ static void rank1_body(Regs&, unsigned, double);")
+    out.append("  __device__ static void load_all(Regs&, unsigned);")
+    for n in [r for r in NRS if r <= nt]:
+        out.append(f"  __device__ static void rank1_body_{n}(Regs&, unsigned, double);")
+        out.append(f"  __device__ static void rank1_stream_{n}(Regs&, unsigned, double);")
+        if n < nt:
+            out.append(f"  __device__ static void load_lo_{n}(Regs&, unsigned);")
+    half = K // 2
+    lines = []
+    for h in range(2):
+        rows = range(h * half, K if h else half)
+        lines += [f"ds_read_b64 {treg(r)}, %[a] offset:{8 * nt * r}" for r in rows]
+        lines += [f"ds_read_b64 {hreg(r - h * half)}, %[d] offset:{8 * r}" for r in rows]       # (1/d_r through the history slots: free until the first pivot)
+        lines.append("s_waitcnt lgkmcnt(0)")
+        lines += [f"v_mul_f64 {treg(r)}, {treg(r)}, {hreg(r - h * half)}" for r in rows]
+    for r in reversed(range(K)):
+        lines += [f"s_cmp_gt_i32 %[n], {r}", "s_cbranch_scc1 .Lgz_%=", f"v_mov_b64 {treg(r)}, 0"]
+    lines.append(".Lgz_%=:")
+    out.append(f"  // gz[r] = lds[a + {nt}·r]·lds[d + r] for r < n (n ≤ {K}), 0 above, in two halves (the 1/d_r pass through the {P} history slots)")
+    out.append("  __device__ static __forceinline__ void load_gz(Regs& t, unsigned lane_addr, unsigned dinv_addr, int n) {")
+    out.append("    n = __builtin_amdgcn_readfirstlane(n);")
+    out.append(f'    asm volatile("{J(lines)}" :: [a] "v"(lane_addr), [d] "v"(dinv_addr), [n] "s"(n) : {clob_t}, "scc", "memory");')
+    out.append("  }")
+    # (the lane's address of its scalar entry is formed inside the statement, from the lane id, in the destination of the read: as a
+    #  C++ value it is loop-invariant and lives through the whole QP; the multiplier is formed in p0's registers, dead after the planes' FMAs)
+    lines = ["v_mbcnt_lo_u32_b32 %[sl], -1, 0", "v_mbcnt_hi_u32_b32 %[sl], -1, %[sl]", f"v_min_u32 %[sl], {2 * P - 1}, %[sl]",
+             "v_lshl_add_u32 %[sl], %[sl], 3, %[sa]", "ds_read_b32 %[sh], %[sl] offset:4", "ds_read_b32 %[sl], %[sl]", "s_nop 4"]
+    lines += [f"v_fmac_f64_dpp %[acc], %[p{r // 16}], {treg(r)} row_newbcast:{r % 16} row_mask:0xf bank_mask:0xf" for r in range(K)]
+    lines.append("s_waitcnt lgkmcnt(0)")
+    for q in range(P):
+        o = h0 + 2 * q
+        lines += [f"s_cmp_le_i32 %[np], {q}", "s_cbranch_scc1 .Lrow_%=",
+                  f"v_readlane_b32 vcc_lo, %[sl], {2 * q}", f"v_readlane_b32 vcc_hi, %[sh], {2 * q}",
+                  f"v_mul_f64 %[p0], vcc, v[{o}:{o + 1}]",
+                  f"v_readlane_b32 vcc_lo, %[sl], {2 * q + 1}", f"v_readlane_b32 vcc_hi, %[sh], {2 * q + 1}",
+                  "v_mul_f64 %[p0], %[p0], vcc",
+                  f"v_readlane_b32 vcc_lo, v{o}, %[c]", f"v_readlane_b32 vcc_hi, v{o + 1}, %[c]",
+                  "v_fma_f64 %[acc], vcc, -%[p0], %[acc]"]
+    lines.append(".Lrow_%=:")
+    out.append("  // row `col` of the dof block for this lane: p0 / p1 = Z[r][col] in 16-lane planes, then fma(own_q[col], −g_q, ·) for the npiv past")
+    out.append(f"  // pivots with g_q = ((σ²)·own_q)·(1/d) formed here; scal_addr: the scalar array (wave-uniform)")
+    out.append("  __device__ static __forceinline__ double row_on_demand_1(Regs& t, double p0, double p1, int col, int npiv, unsigned scal_addr) {")
+    out.append("    double acc = 0.0;")
+    out.append("    int sl, sh;")
+    out.append("    col = __builtin_amdgcn_readfirstlane(col); npiv = __builtin_amdgcn_readfirstlane(npiv); scal_addr = __builtin_amdgcn_readfirstlane(scal_addr);")
+    out.append(f'    asm volatile("{J(lines)}" : [acc] "+v"(acc), [p0] "+v"(p0), [sl] "=&v"(sl), [sh] "=&v"(sh) '
+               f': [p1] "v"(p1), [c] "s"(col), [np] "s"(npiv), [sa] "s"(scal_addr) : {clob_t}, "vcc", "scc", "memory");')
+    out.append("    return acc;")
+    out.append("  }")
+    out.append("  // history slot npiv (wave-uniform, < kHist) = own")
+    out.append("  __device__ static __forceinline__ void hist_push_1(Regs& t, int npiv, double own) {")
+    out.append("    const int idx = __builtin_amdgcn_readfirstlane(2 * npiv);")
+    body = J(["s_set_gpr_idx_on %[i], gpr_idx(DST)", f"v_mov_b32 v{h0}, %[ol]", f"v_mov_b32 v{h0 + 1}, %[oh]", "s_set_gpr_idx_off", "s_nop 1"])
+    out.append(f'    asm volatile("{body}" :: [ol] "v"(__double2loint(own)), [oh] "v"(__double2hiint(own)), [i] "s"(idx) : {clob_t}, "m0");')
+    out.append("  }")
+    out.append("};")
+    return "\n".join(out)
+
+
 PF_KMU = 18        # product form (gen): rows of the factor kept per lane = ik_kernel.h kMu
 KMUS = (18, 24)   # row capacities of the low-rank start's elimination (ik_kernel.h kMu*): task residuals of one problem
 
@@ -295,6 +386,7 @@ def main():
     parts += [gen(nt) for nt in NTS]
     parts += [gen(nt, 168, "TabW3") for nt in W3_NTS]
     parts += [gen(nt, 128, "TabW4") for nt in W4_NTS]
+    parts.append(gen_w4_product(W4_PRODUCT_NT, W4_PRODUCT_HIST))
     parts.append(gen_wood_elim())
     parts.append("}  // namespace mkh")
     path, text = os.path.join(HERE, "tab_asm.inc"), "\n".join(parts) + "\n"

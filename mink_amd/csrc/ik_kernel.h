@@ -44,6 +44,11 @@
 
 // Register map of the tableau: Tab<NT> (2 resident waves per SIMD for NT > 24) or, in the variant TUs that define
 // MKH_W3, TabW3<NT> — the same primitives pinned below 168 VGPRs, i.e. 3 resident waves per SIMD.
+// MKH_W4P (with MKH_W3; `44_32_r44_w4o`): the humanoid-size build on FOUR waves per SIMD — product form only, history slots of one
+// double (TabW4<44>), its own LDS layout (build_lds_layout_w4p)
+#if defined(MKH_W4P) && !defined(MKH_W4)
+#define MKH_W4 1
+#endif
 #if defined(MKH_W4)     // (a W4 translation unit also defines MKH_W3: the same call structure and compact LDS layout)
 #define MKH_TAB TabW4
 #elif defined(MKH_W3)
@@ -87,6 +92,11 @@ __host__ __device__ inline int j_stride_direct(int nv, int nt) { const int a = a
 
 constexpr int kPivBuf = kWave + 8;   // doubles per pivot broadcast buffer
 constexpr int kMu = 18, kMuBig = 24; // low-rank start: compiled capacities of task-residual rows of one problem (WoodElim in tab_asm.inc)
+#ifdef MKH_W4P
+constexpr int kMuOm = kMu;           // offset of ω_r behind 1/d_r in the pivot range: the four-waves build's range is sized for kMu rows
+#else
+constexpr int kMuOm = kMuBig;
+#endif
 constexpr int kWoodRow = 64;         // low-rank start: doubles of the published-row buffer — (S[r][c], w_c) pairs — in the pivot buffers, followed by 1/d_r
 struct LdsLayout {
   int q, X, jnt, tgt, task, J, dof, com, col, A, piv, S, q2, tgt2, hsel, total;  // offsets in doubles
@@ -165,6 +175,34 @@ __host__ __device__ inline LdsLayout lds_layout(int nq, int nv, int nbody, int n
   // more collision pairs than tableau rows: h of EVERY pair, for the selection of the tightest rows and the check of the
   // dropped ones at the solution (collision_phase) — the ALOHA pair set of the reference is 1 104 pairs for 48 rows
   L.hsel = o; o += lds_even(n_hsel);
+  L.total = o;
+  return L;
+}
+
+// The layout of the four-waves product-form build (MKH_W4P: `44_32_r44_w4o`, one problem per workgroup, frame + posture tasks, one
+// pass of pair lanes): 16 wavefronts per CU need ≤ 8 LDS granules of 1 280 B each, so EVERYTHING that is dead once the pair lanes
+// hold their entries in registers — body poses, task blocks (in the joint axes' range: the dof lanes have read those before the
+// task lanes write), dof stash, q and the targets — is one union with what lives after: the rows of Jh and, behind them, S.  (q
+// and the targets are fetched again when a solve refactorises.)  One pivot range: the elimination's published row, 1/d_r and ω_r
+// sized for kMu rows; the QP's scalar slots (sPiv + kWave) and the history's scalars (sPiv + kPivBuf, 2 per slot) reuse it.
+template <class PT>
+__host__ __device__ __forceinline__ LdsLayout build_lds_layout_w4p(const PT& P0, int nr) {
+  LdsLayout L;
+  const int n_mu = P0.n_jrows, sp = lds_even(n_mu);
+  const int x_sz = 7 * lds_even(P0.nbody), jnt_sz = lds_even(P0.njnt * 6), task_sz = P0.n_frame * 64;
+  int o = 0;
+  L.X = o;    o += x_sz;
+  L.jnt = o;  L.task = o;  o += jnt_sz > task_sz ? jnt_sz : task_sz;
+  L.dof = o;  o += lds_even(P0.nv * 10);
+  L.q = o;    o += lds_even(P0.nq);
+  L.tgt = o;  o += lds_even(P0.n_frame * 7 + P0.n_com * 3);
+  L.J = 0;
+  L.S = lds_even((n_mu + 1) * nr);
+  const int after = L.S + lds_even(n_mu * (sp + 1));
+  if (o < after) o = after;
+  L.com = o; L.col = o; L.A = o;
+  L.piv = o;  o += kWoodRow + 2 * kMu;
+  L.q2 = L.q; L.tgt2 = L.tgt; L.hsel = o;
   L.total = o;
   return L;
 }
@@ -368,7 +406,11 @@ __device__ __forceinline__ double publish_row(typename MKH_TAB<NT>::Regs& ts, co
     ps.lo = c.x; ps.hi = c.y;
   }
   double rowv = 0.0;
+#ifdef MKH_W4P
+  rowv = MKH_TAB<NT>::row_on_demand_1(ts, p0, p1, col, npiv, lds_addr(sPiv + kPivBuf));
+#else
   if constexpr (MKH_TAB<NT>::kHist > 0) rowv = MKH_TAB<NT>::row_on_demand(ts, p0, p1, col, npiv);
+#endif
   return (lane == col || lane >= nact) ? 0.0 : rowv;   // (publish_column's rule)
 }
 // gz[r] = Z[r][lane]/d_r, r < n_μ, into the first kMu pinned rows (Z with row stride NT at sJ, 1/d_r at sDinv)
@@ -378,13 +420,27 @@ __device__ __forceinline__ void load_factor_column(typename MKH_TAB<NT>::Regs& t
   if constexpr (MKH_TAB<NT>::kHist > 0) MKH_TAB<NT>::load_gz(ts, lds_addr(sJ + (lane < NT ? lane : 0)), lds_addr(sDinv), n_mu);
 }
 // pivot() without a tableau: the multiplier and the published entry go to history slot npiv
+// (MKH_W4P, slots of one double: own_q to the slot, the pivot's σ_k² and 1/d — wave-uniform — to entry npiv of the scalar array behind
+//  the pivot buffer; row_on_demand_1 forms g again from them, with these multiplications in this order)
+#ifdef MKH_W4P
+#define MKH_HS_PARAM , double* sHs
+#define MKH_HS_ARG , sPiv + kPivBuf
+#else
+#define MKH_HS_PARAM
+#define MKH_HS_ARG
+#endif
 template <int NT>
 __device__ __forceinline__ void pivot_product(typename MKH_TAB<NT>::Regs& ts, QpLane& s, int k, bool reverse, int lane, double own,
-                                              const PivotScalars& ps, double inv, int& npiv) {
+                                              const PivotScalars& ps, double inv, int& npiv MKH_HS_PARAM) {
   const double sk = ps.sg;
   const double ck = s.sg * sk * own;             // true T[lane][k]
+#ifdef MKH_W4P
+  MKH_TAB<NT>::hist_push_1(ts, npiv, own);
+  if (lane == k) reinterpret_cast<double2*>(sHs)[npiv] = double2{sk * sk, inv};
+#else
   const double g = (sk * sk) * own * inv;        // R-units multiplier of this lane's column
   if constexpr (MKH_TAB<NT>::kHist > 0) MKH_TAB<NT>::hist_push(ts, npiv, -g, own);     // a later row c takes fma(own[c], −g, ·): the update R[c][lane] −= R[c][k]·g
+#endif
   ++npiv;
   if (lane == k) {
     s.D = -inv;
@@ -536,7 +592,10 @@ template <class PT>
 __device__ __forceinline__ bool kernel_prefetch(const PT& P0) {
   constexpr bool kWood = (MKH_FEAT & F_WOOD) != 0;
   constexpr bool kWoodRows = kWood && (MKH_FEAT & (F_COLL | F_DENSE)) != 0;    // low-rank start with half-space rows: its own layout
-#ifdef MKH_W3
+#if defined(MKH_W4P)
+  (void)kWood; (void)kWoodRows; (void)P0;
+  return false;
+#elif defined(MKH_W3)
   return (kWood ? P0.prefetch_w3w : P0.prefetch_w3) != 0;
 #else
   return ((kWoodRows || (kWood && P0.wood_compact != 0)) ? P0.prefetch_wc : P0.prefetch) != 0;
@@ -553,9 +612,23 @@ __device__ __forceinline__ bool kernel_prefetch(const PT& P0) {
 #else
 #define MKH_LAYOUT_W3 false
 #endif
+#ifdef MKH_W4P
+#define kernel_lds_layout(P0) build_lds_layout_w4p(P0, MKH_LAYOUT_NR)
+#else
 #define kernel_lds_layout(P0) build_lds_layout(P0, MKH_NT, MKH_LAYOUT_NR, MKH_FEAT, MKH_LAYOUT_W3)
+#endif
+// (MKH_W4P: q and the targets lie in the union that the rows of Jh and S overwrite — build_lds_layout_w4p — so a solve that
+//  refactorises has them fetched again, here, where the call's arguments cost the kernel body no scalar registers through the QP)
+#ifdef MKH_W4P
+//  (the call arguments' address is handed over: the kernarg-segment builtin is null inside a callee)
+#define MKH_PRE_RF_PARAM , int refetch, const SolveArgs* args_p
+#define MKH_PRE_RF_ARG , (refac_in ? 1 : 0), (const SolveArgs*)A_p
+#else
+#define MKH_PRE_RF_PARAM
+#define MKH_PRE_RF_ARG
+#endif
 __device__ MKH_PRE_ATTR PreOut pre_phases(const DeviceProblem* Pq, const TapArgs* tp, int pb, int oz, int off_q, int off_tgt,
-                                          bool until, double pos_thr, double ori_thr MKH_PRE_TC_PARAMS) {
+                                          bool until, double pos_thr, double ori_thr MKH_PRE_RF_PARAM MKH_PRE_TC_PARAMS) {
   constexpr int FEAT = MKH_FEAT;
   constexpr bool kTaps = (FEAT & F_TAPS) != 0, kRel = (FEAT & F_REL) != 0, kCom = (FEAT & F_COM) != 0;
   constexpr bool kSteps = (FEAT & F_STEPS) != 0, kWood = (FEAT & F_WOOD) != 0;
@@ -590,6 +663,25 @@ __device__ MKH_PRE_ATTR PreOut pre_phases(const DeviceProblem* Pq, const TapArgs
   const bool is_body = lane < nbody;
   const bool is_dof = lane < nv;
   int status = 0;
+#ifdef MKH_W4P
+  if (uni(refetch) != 0) {
+    typedef const __attribute__((address_space(1))) void* gptr_t;
+    typedef __attribute__((address_space(3))) void* lptr_t;
+    const MKH_CONSTANT SolveArgs& A = *(const MKH_CONSTANT SolveArgs*)uni((unsigned long long)reinterpret_cast<size_t>(args_p));
+    wave_sync();                                             // the QP's readers of the rows are done
+    const int ndq = 2 * P.nq, ndt = 2 * P.n_frame * 7;       // dwords per row
+    const char* gq = reinterpret_cast<const char*>(A.q + (size_t)pb * P.nq);
+    for (int b0 = 0; b0 < ndq; b0 += kWave)
+      if (b0 + lane < ndq)
+        __builtin_amdgcn_global_load_lds((gptr_t)(gq + 4 * (b0 + lane)), (lptr_t)(reinterpret_cast<char*>(sq) + 4 * b0), 4, 0, 0);
+    const char* gt = reinterpret_cast<const char*>(A.frame_targets + (size_t)pb * (ndt / 2));
+    for (int b0 = 0; b0 < ndt; b0 += kWave)
+      if (b0 + lane < ndt)
+        __builtin_amdgcn_global_load_lds((gptr_t)(gt + 4 * (b0 + lane)), (lptr_t)(reinterpret_cast<char*>(sTgt) + 4 * b0), 4, 0, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wave_sync();
+  }
+#endif
     // ------------------------------------------------- FK: local transforms
     // X = pose of body `lane` relative to its parent, joints applied
     // (mj_kinematics).
@@ -614,7 +706,11 @@ __device__ MKH_PRE_ATTR PreOut pre_phases(const DeviceProblem* Pq, const TapArgs
         const int qa = P.jnt_i[j * JI_COUNT + JI_QADR];
         // (the joint's constants with its type, not behind it: inside the branches they were a third dependent L2 round trip)
         const auto* jfp = P.jnt_f + j * JF_COUNT;
+#ifdef MKH_W4P
+        const auto* const jf = jfp;      // (four-waves build: read where they are used — seven doubles less at the phase's register peak)
+#else
         const double jf[JF_COUNT] = {jfp[0], jfp[1], jfp[2], jfp[3], jfp[4], jfp[5], jfp[6]};
+#endif
         if (jt == JNT_FREE) {
           xp = {sq[qa], sq[qa + 1], sq[qa + 2]};
           xq = qnormalize(Q4{sq[qa + 3], sq[qa + 4], sq[qa + 5], sq[qa + 6]});
@@ -838,6 +934,16 @@ __device__ MKH_PRE_ATTR PreOut pre_phases(const DeviceProblem* Pq, const TapArgs
       // (low-rank builds: one square root of |ew|² for log and jlog; in the others handing it over costs spilled registers)
       double eth = 0.0;
       const double* const eth_p = kWood ? &eth : nullptr;
+#ifdef MKH_W4P
+      // (four-waves build: the frame's rotation and position go to the task block BEFORE log / jlog — the same values, stored where the
+      //  pose's fourteen registers would otherwise live through this phase's register peak, beyond the 80 caller-saved ones)
+      {
+        const M3 Rf0 = qmat(F.q);
+#pragma unroll
+        for (int i = 0; i < 9; ++i) o[18 + i] = Rf0.m[i];
+        o[27] = F.p.x; o[28] = F.p.y; o[29] = F.p.z;
+      }
+#endif
       if (!(kRel && ft.relative)) {
         // e = target.minus(frame) = log(T_frame⁻¹ · T_target)          (frame_task.py:119-122)
         se3_log(se3_mul(se3_inv(F), Tt), ev, ew, eth);
@@ -865,10 +971,15 @@ __device__ MKH_PRE_ATTR PreOut pre_phases(const DeviceProblem* Pq, const TapArgs
           t[0] = Tfr.q.w; t[1] = Tfr.q.x; t[2] = Tfr.q.y; t[3] = Tfr.q.z; t[4] = Tfr.p.x; t[5] = Tfr.p.y; t[6] = Tfr.p.z;
         }
       }
+#ifdef MKH_W4P
+#pragma unroll
+      for (int i = 0; i < 9; ++i) { o[i] = Jm[i]; o[9 + i] = Qm[i]; }
+#else
       M3 Rf = qmat(F.q);
 #pragma unroll
       for (int i = 0; i < 9; ++i) { o[i] = Jm[i]; o[9 + i] = Qm[i]; o[18 + i] = Rf.m[i]; }
       o[27] = F.p.x; o[28] = F.p.y; o[29] = F.p.z;
+#endif
       const double e6[6] = {ev.x, ev.y, ev.z, ew.x, ew.y, ew.z};
       double ss = 0.0;
 #pragma unroll
@@ -1031,7 +1142,7 @@ __device__ __forceinline__ void wood_eliminate(int n_mu, int NR, int lane, doubl
       for (int r = 0; r < K; ++r) q = fma(z[r], z[r], q);                // Σ Jh² of a dof lane (before the elimination):
       if (lane < NR) sJ[n_mu * NR + lane] = q;                           // parked in LDS (the right-hand-side row of the product
     }                                                                    // is dead), not in two registers through the loop
-    double* const sOm = sDinv + kMuBig;
+    double* const sOm = sDinv + kMuOm;
     // (the steps' guards test a scalar copy of n_μ the compiler can neither merge with the lane conditions of the loads above nor
     //  evaluate ahead of the passes: evaluated ahead, every `r < n_μ` lived through both passes as a 64-bit lane mask — 36 scalar
     //  registers, which pushed wood_start into the callee-saved range, 33 scalars moved through lanes on entry and again on
@@ -1054,7 +1165,7 @@ __device__ __forceinline__ void wood_eliminate(int n_mu, int NR, int lane, doubl
           const double p1 = (K > 16) ? bperm_f64(z[r], (NR + 16 + (int)plane_off) & 63) : 0.0;   // rows ≥ n_μ: never used
           if (lane < NR) sJ[r * NR + lane] = z[r];                       // row r of Z, final (read after the loop)
           const double inv = fast_rcp(d);
-          wood_store_pivot<(MKH_NT + r) % kWave, r, kMuBig + r>(dinv_addr, inv, ws);   // sDinv[r] = 1/d_r, sOm[r] = ω_r  (NR = MKH_NT)
+          wood_store_pivot<(MKH_NT + r) % kWave, r, kMuOm + r>(dinv_addr, inv, ws);   // sDinv[r] = 1/d_r, sOm[r] = ω_r  (NR = MKH_NT)
           const double zi = z[r] * inv;
           quad = fma(z[r], zi, quad);
           zw = fma(om, zi, zw);
@@ -1073,7 +1184,19 @@ __device__ __forceinline__ void wood_eliminate(int n_mu, int NR, int lane, doubl
       // so a second elimination of the n_μ × n_μ matrix M = D − Z_A·Z_Aᵀ = L_M·D_M·L_Mᵀ — columns on the S lanes again, summed
       // over the |A| violated dofs only — carries Z to L_M⁻¹·Z and ω to L_M⁻¹·(ω + Σ_A Z[·][k]·(β_k − z_k)·√Dg_k): the state of
       // the predicted-set start (wood_start), from what the first pass left in registers and LDS.
+#ifdef MKH_W4P
+      // (four-waves build: the three products of rf formed here, from operands laundered inside the loop — as values of the caller
+      //  they lived through the first pass next to the 36 registers of the column)
+      double rc = rf.zsq, rd = rf.dsq, rh = rf.sqdg;          // −c_lane, 1/√Dg, Dg as handed over by wood_start
+      asm volatile("" : "+v"(rc), "+v"(rd), "+v"(rh));
+      // (... and the products opaque again: in the other builds each has a second use in wood_start, so none is contracted into
+      //  the FMAs below — here they would be, with other roundings)
+      double rf_zfree = rc * (rd * rd), rf_sqdg = rh * rd, rf_zsq = rc * rd;
+      asm volatile("" : "+v"(rf_zfree), "+v"(rf_sqdg), "+v"(rf_zsq));
+      const double x0 = rf_zfree - rd * zw;
+#else
       const double x0 = rf.zfree - rf.dsq * zw;
+#endif
       const int viol = (lane < rf.nv) ? ((x0 > rf.hi) ? 2 : ((x0 < rf.lo) ? 1 : 0)) : 0;
       const unsigned long long am = __ballot(viol != 0);
       if (!am) break;
@@ -1084,7 +1207,11 @@ __device__ __forceinline__ void wood_eliminate(int n_mu, int NR, int lane, doubl
       for (int r = 0; r < K; ++r) dself = (r == my_c) ? z[r] : dself;    // d_c: entry c of an S column is final after step c
       double om_c = is_s ? sOm[my_c] : 0.0;
       wave_sync();                                                       // the last row's readers are done
+#ifdef MKH_W4P
+      if (viol) sRow[lane] = beta * rf_sqdg - rf_zsq;
+#else
       if (viol) sRow[lane] = beta * rf.sqdg - rf.zsq;                    // (β_k − z_k)·√Dg_k
+#endif
       if (is_s) {
 #pragma unroll
         for (int r = 0; r < K; ++r) z[r] = (r == my_c) ? dself : 0.0;
@@ -1111,7 +1238,7 @@ __device__ __forceinline__ void wood_eliminate(int n_mu, int NR, int lane, doubl
     // stay in LDS (S is loaded into registers first, its storage takes the rows) — then the Jh columns on the dof lanes, which
     // only read multipliers: no publish / read-back chain at all.
     const bool is_s = lane < n_mu;
-    double* const sOm = sDinv + kMuBig;
+    double* const sOm = sDinv + kMuOm;
     {
       double z[K];
 #pragma unroll
@@ -1308,7 +1435,11 @@ __device__ MKH_WOOD_ATTR WoodOut wood_start(const DeviceProblem* Pq, int oz, int
   // (per-lane entries of the descriptor's tables, requested together here — each used to be fetched where it is needed, one L2
   //  round trip after the other: the residual's source, the first pass of (task, dof) pairs, the lane's column of S)
   // (humanoid-size builds only: in the 16- / 24- / 32-row builds the six values cost this function spilled registers)
+#ifdef MKH_W4P
+  constexpr bool kPre = false;         // (four-waves build: the function has the 80 caller-saved registers below 128, the six values do not fit)
+#else
   constexpr bool kPre = NR >= 44;
+#endif
   int pre_src = 0, pre_t = 0, pre_k = 0, pre_wc = 0, pre_wr0 = 0;
   uint64_t pre_chain = 0;
   uint32_t pre_list[4] = {0, 0, 0, 0};
@@ -1474,7 +1605,11 @@ __device__ MKH_WOOD_ATTR WoodOut wood_start(const DeviceProblem* Pq, int oz, int
   // 43 dofs on G1): the dot products walk the set bits of the column's chain mask instead of all NR dofs.
   // [column c][SP]: S[·][c], then [c]: (Jw·z)[c] − weighted error.  Lives in the dof stash (+ the subtree CoMs behind it:
   // axes / anchors / CoMs of the Jacobian columns are dead by now) when it fits, so that the low-rank start costs no LDS.
+#ifdef MKH_W4P
+  double* const sS = smem + L.S;                                       // (behind the rows of Jh: the dof stash is part of the union they overwrite)
+#else
   double* const sS = (!kRowsW && wood_s_aliases_dof(nv, n_mu, SP, P.n_com > 0 ? P.nbody : 0)) ? sDof : smem + L.S;
+#endif
   double* const sW = sS + n_mu * SP;
   lds_zero_fill(sS, n_mu * SP, lane);
   wave_sync();
@@ -1604,7 +1739,11 @@ __device__ MKH_WOOD_ATTR WoodOut wood_start(const DeviceProblem* Pq, int oz, int
   // (compiled into the lean 44- / 48-row builds only: its code costs the others — register pressure of this function, scalar
   //  spills — more than the pivots it saves: G1 +1.5 %, but H1 / hands / quadrupeds −10 % and the G1 full example −4.5 %)
   constexpr bool kRefine = !kCom && NR >= 44 && !(MKH_FEAT & F_STEPS) && !kRowsW;
+#ifdef MKH_W4P
+  const WoodRefine rf{kRefine && a_mask == 0 && !dual && P.wood_refine != 0, nv, lo, hi, 0.0, dsq, hdiag_base, -c_lane};   // (raw operands: wood_eliminate)
+#else
   const WoodRefine rf{kRefine && a_mask == 0 && !dual && P.wood_refine != 0, nv, lo, hi, -c_lane * (dsq * dsq), dsq, hdiag_base * dsq, -c_lane * dsq};
+#endif
   if constexpr (kCom) {
 #ifdef MKH_WOOD_SPLIT
     {
@@ -1636,7 +1775,16 @@ __device__ MKH_WOOD_ATTR WoodOut wood_start(const DeviceProblem* Pq, int oz, int
   const bool on_bound = is_dof && clamp != 0;                          // (predicted by the caller, or by the refinement pass)
   wo.clamp = on_bound ? clamp : 0;
   wo.D = on_bound ? hdiag_base * (1.0 + quad) : (dsq * dsq) * (quad - 1.0);
+#ifdef MKH_W4P
+  {
+    // (the two products that the refinement's operands shared with this line in the other builds, opaque as they are there)
+    double zfree = -c_lane * (dsq * dsq), sqdg = hdiag_base * dsq;
+    asm volatile("" : "+v"(zfree), "+v"(sqdg));
+    wo.x = on_bound ? fma(hdiag_base, beta, c_lane) + sqdg * zw : zfree - dsq * zw;
+  }
+#else
   wo.x = on_bound ? fma(hdiag_base, beta, c_lane) + hdiag_base * dsq * zw : -c_lane * (dsq * dsq) - dsq * zw;
+#endif
   wo.rown = 1.0;
   if constexpr (kRowsW) {
     if (is_row) { wo.D = quad - row_gs; wo.x = (row_a0 + zw) - row_h; wo.rown = row_n; }   // T_rr[s][s], the slack A·x0 − h, ‖A[s]‖
@@ -1974,7 +2122,9 @@ __device__ MKH_COLL_ATTR int collision_phase(const DeviceProblem* Pq, const TapA
 __device__ __forceinline__ int collision_phase(const DeviceProblem*, const TapArgs*, int, double, int, const LdsLayout&) { return 0; }
 #endif
 
-#ifdef MKH_W3
+#if defined(MKH_W4P)
+#define MKH_STAGE 0                            // product form only: no rank-1 update, no planes
+#elif defined(MKH_W3)
 #define MKH_STAGE (2 * ((MKH_NT + 15) / 16))   // 3-waves maps: only the planes the column has (gen_tab_asm.py)
 #else
 #define MKH_STAGE 8   // staging VGPRs of the rank-1 update: four 16-lane planes of the pivot column (gen_tab_asm.py ntmp_for)
@@ -1989,7 +2139,11 @@ __device__ __forceinline__ int collision_phase(const DeviceProblem*, const TapAr
 #define MKH_WAVES (MKH_NT <= 8 ? 4 : (MKH_NT <= 24 ? 3 : 2))   // resident waves per SIMD the register map is built for
 #define MKH_TOP (MKH_NT <= 8 ? 128 : (MKH_NT <= 24 ? 168 : 256))  // VGPRs per lane at that occupancy (gen_tab_asm.py total_for)
 #endif
+#if defined(MKH_W4P)
+#define MKH_CAP (MKH_TOP - 2 * (18 + 13))      // kMu factor rows + 13 history slots of one double (gen_tab_asm.py gen_w4_product)
+#else
 #define MKH_CAP (MKH_TOP - 2 * MKH_NT - MKH_STAGE)
+#endif
 #ifdef MKH_CAP_PROBE     // (pressure probing only: the code is wrong when the cap reaches into the pinned range)
 #undef MKH_CAP
 #define MKH_CAP MKH_CAP_PROBE
@@ -2277,7 +2431,7 @@ void MKH_KERNEL_NAME(const DeviceProblem* __restrict__ Pg, const SolveArgs A_k, 
     tci = 1;                                                 // phase stamps 1..7 belong to the current step
 
     // FK, joint axes / dof lanes, subtree CoM, frame-task lanes (pre_phases above)
-    const PreOut po = pre_phases(Pq, tp, pb, oz, (int)(sq - smem), (int)(sTgt - smem), until, A.pos_threshold, A.ori_threshold MKH_PRE_TC_ARGS);
+    const PreOut po = pre_phases(Pq, tp, pb, oz, (int)(sq - smem), (int)(sTgt - smem), until, A.pos_threshold, A.ori_threshold MKH_PRE_RF_ARG MKH_PRE_TC_ARGS);
 #ifdef MKH_CALLS
     tci = 3;                                                  // (a callee has no stamps: phases 1 and 2 read as 0)
 #endif
@@ -2907,7 +3061,7 @@ void MKH_KERNEL_NAME(const DeviceProblem* __restrict__ Pg, const SolveArgs A_k, 
         }
         ++n_piv;
         MKH_LAP(4);
-        if constexpr (kProduct) pivot_product<NT>(ts, s, k, kb, lane, own, ps, inv, npiv);
+        if constexpr (kProduct) pivot_product<NT>(ts, s, k, kb, lane, own, ps, inv, npiv MKH_HS_ARG);
         else pivot<NT, NR>(ts, s, k, kb, lane, sPiv, own, ps, inv);
         MKH_LAP(5);
       };
@@ -3077,7 +3231,7 @@ void MKH_KERNEL_NAME(const DeviceProblem* __restrict__ Pg, const SolveArgs A_k, 
       // (product form, history full — between two drives, or in one: the drive is abandoned.  The flags already say where
       //  every index sits, the pivot that would have followed is part of the rebuilt factors.)
       if (hist_full()) { refac = 1; break; }
-      if constexpr (kProduct) pivot_product<NT>(ts, s, col, rev, lane, own, ps, inv, npiv);
+      if constexpr (kProduct) pivot_product<NT>(ts, s, col, rev, lane, own, ps, inv, npiv MKH_HS_ARG);
       else pivot<NT, NR>(ts, s, col, rev, lane, sPiv, own, ps, inv);
       MKH_LAP(5);
     }

@@ -187,6 +187,7 @@ struct MkhProblem {
   // problem does not qualify; lower bound of the diagonal part of H without the damping argument, and
   // the largest squared task cost (conditioning gate, evaluated per call because damping is a call argument)
   int wood_nt = 0, wood_nr = 0, wood_lds_bytes = 0, wood_lds_bytes_w3 = 0;
+  int wood_lds_bytes_w4 = 0;         // LDS bytes of the four-waves product-form build (`44_32_r44_w4o`) when 16 wavefronts per CU fit, else 0
   // low-rank start WITH half-space rows (round 6; `48_40_r48`): the lane tables are in the descriptor(s), LDS bytes of that layout
   // for the tight-rows descriptor and for the main one (0: not available there)
   bool woodr_tables = false;
@@ -1386,6 +1387,14 @@ int32_t mkh_problem_create_diag(MkhModel* m, const MkhProblemDesc* d, int32_t ma
           p->wood_lds_bytes_w3 = lds_wood_w3(F_WOOD, P.prefetch_w3w != 0);
         }
       }
+      // ... and four (the product-form build on TabW4<44>, one problem per workgroup: everything that is dead after the pair lanes
+      // in one union, ik_kernel.h build_lds_layout_w4p).  Sixteen wavefronts per CU by registers (128 VGPRs), so the layout has to
+      // fit 8 of the CU's 128 LDS granules; 9 would be 14 wavefronts, uneven SIMDs — the problem then stays on the three-waves build.
+      p->wood_lds_bytes_w4 = 0;
+      if (p->wood_lds_bytes_w3 && p->wood_nt == 44 && P.n_com == 0 && !p->wood_big && find_variant(44, 44, F_WOOD, true, true, true)) {
+        const int bytes = build_lds_layout_w4p(P, p->wood_nr).total * (int)sizeof(double);
+        if (128 / ((bytes + 1279) / 1280) >= 16) p->wood_lds_bytes_w4 = bytes;
+      }
       // ... and the F_COM builds of a humanoid-size robot (ComTask rows and / or up to 24 task rows: `44_36_r44_w3`, round 5).
       // Their 25 rows of Jh take 8.8 KB of the compact layout — 15.4 KB for the G1 full example, 10 wavefronts per CU instead
       // of 8 — so the bar is "more resident wavefronts than the two-waves map", not all twelve.
@@ -1564,6 +1573,11 @@ static int grid_for(const MkhProblem* p, int B) {
 // 0.282 / 0.270, 24 576 = 8 rounds 0.321 / 0.335, 32 768 0.409 / 0.422, 65 536 0.754 / 0.827): over a few rounds the work of
 // the wavefronts has not drifted apart yet, and a ticket tail only adds its own ragged last round.  Round 1's threshold was 4.
 constexpr int kMinRoundsForTickets = 8;
+// Smallest batch that takes the four-waves product-form build of the humanoid-size low-rank start where its layout fits (plan_launch).
+// Kernel ms on G1 config 3, three-waves twin / four-waves build (docs/HISTORY.md, profiles/r17_batch_ab.txt; medians of three alternating
+// rounds): 14 336 instances 0.1566 / 0.1577 (a tie), 16 384 0.1656 / 0.1643 (−0.8 %: inside the parent's own spread), 32 768 0.3057 / 0.2739
+// (−10 %), 65 536 0.5707 / 0.5080 (−11 %), 131 072 1.1277 / 0.9882 (−12 %): the switch is where the gain is clear of run-to-run noise.
+constexpr long long kW4MinBatch = 32768;
 static int static_rounds_for(int per_wave, bool uneven, bool loops = false) {
   static const bool static78 = dbg_env("MKH_DEBUG_STATIC_78") != nullptr;
   static const int dbg_16ths = dbg_env("MKH_DEBUG_STATIC_16THS") ? atoi(dbg_env("MKH_DEBUG_STATIC_16THS")) : -1;
@@ -1631,7 +1645,7 @@ static hipError_t clk_end(MkhProblem* p, int B, hipStream_t stream) {
 enum class Family { WideOnly, Row, Lane, Wave };
 struct WaveLaunch {                // one launch of an ik_solve_kernel build
   int nt = 0, nr = 0, feat = 0;
-  bool w3 = false, one_shot = false;
+  bool w3 = false, one_shot = false, w4 = false;
   int grid = 0, lds = 0, static_rounds = INT32_MAX;
   const VariantRow* v = nullptr;   // its row of the table (variants.h); null: not compiled — launch() reports it
 };
@@ -1830,6 +1844,13 @@ static int32_t plan_launch(const MkhProblem& P_, const SolveArgs& a, const TapAr
   // ... and, round 6, on a build WITHOUT the persistent loop's machinery where one exists (`44_32_r44_w3o`: build.py W3_WOOD_ONE_SHOT,
   // ik_kernel.h MKH_ONE_SHOT — 78 → 32 spilled SGPRs in the kernel body, headline 0.713 → 0.703 ms; the F_COM twin measured no gain)
   const bool one_shot = grid == a.B && has_twin;
+  // ... and, round 17, on FOUR waves per SIMD where the handle's layout fits (`44_32_r44_w4o`, mkh_problem_create: wood_lds_bytes_w4):
+  // from 3.5 rounds of ITS resident wavefronts (16 per CU: 4 096 on 256 CUs, so 14 336 instances) and from the batch size at which
+  // it measured clearly faster (kW4MinBatch; MKH_DEBUG_W4_MIN_BATCH=n moves the switch for A/B sweeps, a huge n turns the build off).
+  static const long long w4_min = dbg_env("MKH_DEBUG_W4_MIN_BATCH") ? atoll(dbg_env("MKH_DEBUG_W4_MIN_BATCH")) : kW4MinBatch;
+  const bool w4 = one_shot && nt == 44 && nr == 44 && feat == F_WOOD && p->wood_lds_bytes_w4 != 0 && a.B >= w4_min &&
+                  2 * (long long)a.B >= 7LL * 16 * num_cus && find_variant(nt, nr, feat, true, true, true);
+  if (w4) lds = p->wood_lds_bytes_w4;
   // Distribution (ik_kernel.h): most of each wave's share is static — one contiguous row range per XCD — and the tail
   // of the batch goes through the ticket counter (how much: static_rounds_for above).  Round 1, on G1 (kernel ms by static
   // sixteenths): 16 → 1.283, 15 → 1.233, 14 → 1.183, 12 → 1.185, 8 → 1.193, 4 → 1.195, 0 → 1.264: every wave opening with an
@@ -1838,9 +1859,9 @@ static int32_t plan_launch(const MkhProblem& P_, const SolveArgs& a, const TapAr
   // (fused loops: problems of very different length — the ticket tail from four rounds on, as before)
   const bool dynamic = nt > 8 && per_wave >= (a.n_steps > 1 ? 4 : kMinRoundsForTickets) && !tight;   // (a redo launch walks its static share, ik_kernel.h)
   WaveLaunch& w = L.main;
-  w.nt = nt; w.nr = nr; w.feat = feat; w.w3 = w3; w.one_shot = one_shot; w.grid = grid; w.lds = lds;
+  w.nt = nt; w.nr = nr; w.feat = feat; w.w3 = w3; w.one_shot = one_shot; w.w4 = w4; w.grid = grid; w.lds = lds;
   if (dynamic) w.static_rounds = static_rounds_for(per_wave, grid % num_cus == 0 && ((grid / num_cus) & 3) != 0, a.n_steps > 1);
-  w.v = find_variant(nt, nr, feat, w3, one_shot);
+  w.v = find_variant(nt, nr, feat, w3, one_shot, w4);
   // what the call reports: the launch that does the work — the tight one where there is one; "convex_pre+": the pre-pass launch
   // in front, "+redo_<rows>" / "+wide": the launches behind
   const WaveLaunch& rep = tight ? L.tight : L.main;

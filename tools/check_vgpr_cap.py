@@ -50,6 +50,8 @@ def check(src: str):
     w3 = os.path.basename(src).endswith(("_w3.hip", "_w3o.hip"))     # (_w3o: the one-problem-per-workgroup twin, same map)
     top = (128 if nt <= 24 else 168) if w3 else gen.total_for(nt)
     cap = top - 2 * nt - (2 * ((nt + 15) // 16) if w3 else gen.ntmp_for(nt))
+    if os.path.basename(src).endswith("_w4o.hip"):                   # (the product form alone below 128 registers: gen_w4_product)
+        cap = 128 - 2 * (gen.PF_KMU + gen.W4_PRODUCT_HIST)
     out = subprocess.run([hipbuild._hipcc()] + hipbuild.FLAGS + hipbuild.KERNEL_FLAGS +
                          ["-S", "--cuda-device-only", "-o", "-", src], check=True, capture_output=True, text=True).stdout
     mx = max_compiler_vgpr(out)

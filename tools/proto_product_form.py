@@ -7,14 +7,18 @@ kernel's product-form builds (ik_kernel.h kProduct) — the block stays in its f
 
     row col for index j   =   Σ_r Z[r][col]·gz[r][j]   −   Σ_{q < npiv} own_q[col]·g_q[j]        gz[r][j] = Z[r][j]/d_r
 
-with one history slot (g_q, own_q) per past pivot, P slots.  When the history is full the solve starts again from the active
+with one history slot (g_q, own_q) per past pivot, P slots.  A slot of ONE double (`one_double`) keeps own_q per lane and the
+pivot's two wave-uniform scalars (σ_k², 1/d) apart, and re-forms g_q[j] = ((σ_k²)·own_q[j])·(1/d) — the multiplications of the
+pivot, in the pivot's order — whenever a row is asked for: the same bits as the stored multiplier (counted in
+stats["reformed_unequal"], which must stay 0), at half the registers per slot.  When the history is full the solve starts again from the active
 set it has reached — the predicted-active-set start of a warm start — which rebuilds Z and d for that set; nothing is ever
 materialised.  Iterations keep counting across such refactorisations (one counts as the P pivots it closes).
 
 The rules are the kernel's: cold-start refinement (the bounds x⁰ violates become the first active set), block steps while each
 at least halves the infeasibilities (≤ 3), hand-over releases, Goldfarb–Idnani.
 
-    python tools/proto_product_form.py [n=512] [seed=0]      histogram of pivots per solve, share of solves that refactorise
+    python tools/proto_product_form.py [n=512] [seed=0] [P=13]   histogram of pivots per solve, share of solves that refactorise
+                                                                 at P (two-double slots, then one-double slots)
 """
 import os
 import sys
@@ -29,7 +33,7 @@ for p in (REPO, os.path.join(REPO, "tests"), os.path.join(REPO, "tools")):
 P_DEFAULT = 13            # history slots of the 44-row builds: (44 − 18) / 2
 
 
-def solve(Dg, c_d, Jw, r, lo, hi, P=P_DEFAULT, cold_refine=True, stats=None):
+def solve(Dg, c_d, Jw, r, lo, hi, P=P_DEFAULT, cold_refine=True, stats=None, one_double=False):
     """min ½xᵀ(Dg + JwᵀJw)x + (c_d − Jwᵀr)ᵀx, lo ≤ x ≤ hi.  Returns (x, status): 0 solved, 2 infeasible, 4 bad pivot, 8 iteration cap."""
     nv = len(Dg)
     # (the start takes the posture part c_d and the residuals apart: Jw·z̃ − r)
@@ -66,7 +70,7 @@ def solve(Dg, c_d, Jw, r, lo, hi, P=P_DEFAULT, cold_refine=True, stats=None):
         return np.full(nv, np.nan), 2
     bound = np.zeros(nv, int)
     iters = 0
-    n_piv = n_refac = 0
+    n_piv = n_refac = n_unequal = 0
     best, outer = 4 * 64, 0                            # block steps: carried across refactorisations (the state is the same state)
     while True:                                        # one pass = one factorisation
         Z, d, sg, D, x = start(bound)
@@ -79,12 +83,17 @@ def solve(Dg, c_d, Jw, r, lo, hi, P=P_DEFAULT, cold_refine=True, stats=None):
         gz = Z / d[:, None]
         basic = bound == 0
         at_hi = bound == 2
-        hist = []                                       # (g_q, own_q)
+        hist = []                                       # (g_q, own_q, σ_k², 1/d): a one-double slot keeps own_q, the scalars are the pivot's
         refac = False
 
         def row(col):
+            nonlocal n_unequal
             acc = Z[:, col] @ gz                        # Σ_r Z[r][col]·gz[r][j]
-            for g, own in hist:
+            for g, own, sk2, inv in hist:
+                if one_double:
+                    g2 = (sk2 * own) * inv              # the pivot's own multiplications, in its order
+                    n_unequal += int((g2 != g).sum())
+                    g = g2
                 acc = acc - own[col] * g
             acc[col] = 0.0
             return acc
@@ -94,8 +103,9 @@ def solve(Dg, c_d, Jw, r, lo, hi, P=P_DEFAULT, cold_refine=True, stats=None):
             dk, sk = D[k], sg[k]
             inv = 1.0 / dk
             ck = sg * sk * own
-            g = sk * sk * own * inv
-            hist.append((g, own))
+            sk2 = sk * sk
+            g = sk2 * own * inv
+            hist.append((g, own, sk2, inv))
             Dn = D - ck * inv * ck
             Dn[k] = -inv
             D = Dn
@@ -235,6 +245,7 @@ def solve(Dg, c_d, Jw, r, lo, hi, P=P_DEFAULT, cold_refine=True, stats=None):
     if stats is not None:
         stats["pivots"] = n_piv
         stats["refactorisations"] = n_refac
+        stats["reformed_unequal"] = n_unequal
     if status:
         return np.full(nv, np.nan), status
     return np.where(basic, x, np.where(at_hi, hi, lo)), 0
@@ -303,8 +314,9 @@ def g1_problems(q, tg, stand):
     return [g1_problem(q[i], tg[i], stand) for i in range(len(q))]
 
 
-def replay(problems, P=P_DEFAULT, cold_refine=True):
-    """v, status, pivots, refactorisations per instance."""
+def replay(problems, P=P_DEFAULT, cold_refine=True, one_double=False, unequal=None):
+    """v, status, pivots, refactorisations per instance.  unequal: a list that receives, per instance, the count of re-formed
+    multiplier entries that differ from the stored ones (one_double)."""
     n = len(problems)
     v = np.empty((n, len(problems[0][0])))
     st = np.zeros(n, int)
@@ -312,7 +324,9 @@ def replay(problems, P=P_DEFAULT, cold_refine=True):
     ref = np.zeros(n, int)
     for i, (Dg, c_d, Jw, r, lo, hi, dt) in enumerate(problems):
         s = {}
-        x, st[i] = solve(Dg, c_d, Jw, r, lo, hi, P=P, cold_refine=cold_refine, stats=s)
+        x, st[i] = solve(Dg, c_d, Jw, r, lo, hi, P=P, cold_refine=cold_refine, stats=s, one_double=one_double)
+        if unequal is not None:
+            unequal.append(s["reformed_unequal"])
         v[i] = x / dt
         piv[i], ref[i] = s["pivots"], s["refactorisations"]
     return v, st, piv, ref
@@ -321,13 +335,18 @@ def replay(problems, P=P_DEFAULT, cold_refine=True):
 def main():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 512
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+    P = int(sys.argv[3]) if len(sys.argv) > 3 else P_DEFAULT
     problems = g1_problems(*g1_batch(n, seed))
     for cold in (True, False):
-        v, st, piv, ref = replay(problems, cold_refine=cold)
+        v, st, piv, ref = replay(problems, P=P, cold_refine=cold)
         print("cold-start refinement %s: %d instances, status != 0: %d, pivots per solve mean %.2f max %d" % (
             "on" if cold else "off", n, int((st != 0).sum()), piv.mean(), piv.max()))
         print("  histogram of pivots per solve:", np.bincount(piv).tolist())
-        print("  solves that refactorise at P = %d: %d (%.2f %%)" % (P_DEFAULT, int((ref > 0).sum()), 100.0 * (ref > 0).mean()))
+        print("  solves that refactorise at P = %d: %d (%.2f %%)" % (P, int((ref > 0).sum()), 100.0 * (ref > 0).mean()))
+        uneq = []
+        v1, st1, piv1, ref1 = replay(problems, P=P, cold_refine=cold, one_double=True, unequal=uneq)
+        print("  one-double slots: re-formed multiplier entries unequal to the stored ones: %d; v bitwise equal: %s; statuses equal: %s" % (
+            sum(uneq), np.array_equal(v1, v), np.array_equal(st1, st)))
 
 
 if __name__ == "__main__":
