@@ -266,17 +266,14 @@ def _write_if_changed(path: str, text: str) -> None:
         fh.write(text)
 
 
-def _generate() -> list:
-    os.makedirs(BUILD, exist_ok=True)
-    subprocess.run([sys.executable, os.path.join(HERE, "gen_tab_asm.py")], check=True)
-    srcs = []
-    for v in VARIANTS:
-        _write_if_changed(os.path.join(BUILD, f"variant_{v.name}.hip"), v.translation_unit())
-        srcs.append(f"variant_{v.name}")
-    decls = "\n".join(f"void launch_{v.name}(int, int, hipStream_t, const DeviceProblem*, const SolveArgs&, const TapArgs*);" for v in VARIANTS)
-    rows = "\n".join(f'    {{{v.nt}, {v.nr}, {v.feat}, {str(v.w3).lower()}, {str(v.one_shot).lower()}, "ik_solve_kernel_{v.name}", &launch_{v.name}}},'
-                     for v in VARIANTS)
-    _write_if_changed(os.path.join(BUILD, "dispatch.hip"), f"""// generated by build.py: the table of compiled kernel variants (variants.h)
+def variant_table_source(launchers: bool = True) -> str:
+    """The translation unit that defines the table of variants.h, one row per entry of VARIANTS.  `launchers` = False: null launch
+    pointers — the table of a host-only program that plans problems and never launches (tests/test_problem_plan_cpu.py)."""
+    decls = "\n".join(f"void launch_{v.name}(int, int, hipStream_t, const DeviceProblem*, const SolveArgs&, const TapArgs*);"
+                      for v in VARIANTS) if launchers else ""
+    rows = "\n".join(f'    {{{v.nt}, {v.nr}, {v.feat}, {str(v.w3).lower()}, {str(v.one_shot).lower()}, "ik_solve_kernel_{v.name}", '
+                     + (f"&launch_{v.name}" if launchers else "nullptr") + "}," for v in VARIANTS)
+    return f"""// generated by build.py: the table of compiled kernel variants (variants.h)
 #include <hip/hip_runtime.h>
 #include "../variants.h"
 namespace mkh {{
@@ -289,7 +286,17 @@ const VariantRow* variant_table() {{
 }}
 const int kNumVariants = {len(VARIANTS)};
 }}  // namespace mkh
-""")
+"""
+
+
+def _generate() -> list:
+    os.makedirs(BUILD, exist_ok=True)
+    subprocess.run([sys.executable, os.path.join(HERE, "gen_tab_asm.py")], check=True)
+    srcs = []
+    for v in VARIANTS:
+        _write_if_changed(os.path.join(BUILD, f"variant_{v.name}.hip"), v.translation_unit())
+        srcs.append(f"variant_{v.name}")
+    _write_if_changed(os.path.join(BUILD, "dispatch.hip"), variant_table_source())
     srcs.append("dispatch")
     # translation units of variants that are no longer built (tools/check_vgpr_cap.py walks the directory)
     for f in os.listdir(BUILD):
@@ -305,6 +312,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     srcs = _generate()
     jobs = [(os.path.join(BUILD, s + ".hip"), os.path.join(BUILD, s + ".o")) for s in srcs]
     jobs.append((os.path.join(HERE, "minkhip.hip"), os.path.join(BUILD, "minkhip.o")))
+    jobs.append((os.path.join(HERE, "problem_plan.hip"), os.path.join(BUILD, "problem_plan.o")))   # host-only planning of models and problems (no HIP runtime call)
     jobs.append((os.path.join(HERE, "lane_variants.hip"), os.path.join(BUILD, "lane_variants.o")))
     jobs.append((os.path.join(HERE, "wide_variants.hip"), os.path.join(BUILD, "wide_variants.o")))
     jobs.append((os.path.join(HERE, "convex_pre.hip"), os.path.join(BUILD, "convex_pre.o")))

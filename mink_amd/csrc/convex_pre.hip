@@ -14,9 +14,16 @@
 #include "mkh_types.h"
 #include "wave_ops.h"
 #include "collide_dev.h"
+#include "problem_plan.h"
 #include "wide_types.h"
 
 namespace mkh {
+
+// what the host's planning states on its own because it includes no kernel header (problem_plan.h)
+static_assert(PLAN_GEOM_PLANE == GEOM_PLANE && PLAN_GEOM_SPHERE == GEOM_SPHERE && PLAN_GEOM_CAPSULE == GEOM_CAPSULE &&
+              PLAN_GEOM_ELLIPSOID == GEOM_ELLIPSOID && PLAN_GEOM_CYLINDER == GEOM_CYLINDER && PLAN_GEOM_BOX == GEOM_BOX &&
+              PLAN_GEOM_MESH == GEOM_MESH, "problem_plan.h: geom codes");
+static_assert(kConvexWsDoubles == (kEpaWsDoubles > kGjkWsDoubles ? kEpaWsDoubles : kGjkWsDoubles), "problem_plan.h: convex workspace");
 
 struct CvPre {
   int32_t n_cv;

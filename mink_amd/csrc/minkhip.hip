@@ -1,7 +1,7 @@
 // libminkhip.so — host side of the C ABI declared in include/minkhip.h.
 //
-// mkh_model_create / mkh_problem_create flatten the mjModel fields and the Task/Limit
-// plugin objects of one mink.solve_ik call site into lane tables on the device
+// mkh_model_create / mkh_problem_create upload what problem_plan.hip plans on the host — the mjModel
+// fields and the Task/Limit plugin objects of one mink.solve_ik call site, flattened into lane tables
 // (mkh_types.h); mkh_solve launches the one-wavefront-per-problem kernel (ik_kernel.h).
 #include "../../include/minkhip.h"
 
@@ -18,14 +18,44 @@
 #include <type_traits>
 #include <vector>
 
-#include "ik_kernel.h"
-#include "lane_kernel.h"
+#include "collide_dev.h"
+#include "lie_dev.h"
 #include "outer_launch.h"
-#include "variants.h"
-#include "wide_types.h"
+#include "problem_plan.h"
 
 namespace mkh {
 struct CvPre { int32_t n_cv; const int32_t* pair; const int32_t* chain_adr; const int32_t* chain; };     // (convex_pre.hip)
+
+// q_out = q ⊕ v·dt (mj_integratePos; Configuration.integrate, mink/configuration.py:214-226).
+// One thread per (problem, joint).
+__global__ __launch_bounds__(256) void integrate_kernel(const DeviceProblem P, int B, const double* __restrict__ q,
+                                                        const double* __restrict__ v, double dt,
+                                                        double* __restrict__ q_out) {
+  const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long total = (long long)B * P.njnt;
+  if (tid >= total) return;
+  const int b = (int)(tid / P.njnt), j = (int)(tid % P.njnt);
+  const int jt = P.jnt_i[j * JI_COUNT + JI_TYPE];
+  int qa = P.jnt_i[j * JI_COUNT + JI_QADR];
+  int va = P.jnt_i[j * JI_COUNT + JI_DADR];
+  const double* qi = q + (size_t)b * P.nq;
+  const double* vi = v + (size_t)b * P.nv;
+  double* qo = q_out + (size_t)b * P.nq;
+  if (jt == JNT_HINGE || jt == JNT_SLIDE) { qo[qa] = qi[qa] + dt * vi[va]; return; }
+  if (jt == JNT_FREE) {
+    for (int i = 0; i < 3; ++i) qo[qa + i] = qi[qa + i] + dt * vi[va + i];
+    qa += 3; va += 3;
+  }
+  // mju_quatIntegrate: q ← normalize(q) ⊗ axisangle(v̂, dt·|v|)
+  V3 w{vi[va], vi[va + 1], vi[va + 2]};
+  const double n = sqrt(dot(w, w));
+  V3 ax = (n < 1e-15) ? V3{1.0, 0.0, 0.0} : (1.0 / n) * w;
+  const double ang = dt * n;
+  Q4 qr = (ang == 0.0) ? Q4{1, 0, 0, 0} : axis_angle(ax, ang);
+  Q4 q0 = qnormalize(Q4{qi[qa], qi[qa + 1], qi[qa + 2], qi[qa + 3]});
+  Q4 r = qmul(q0, qr);
+  qo[qa] = r.w; qo[qa + 1] = r.x; qo[qa + 2] = r.y; qo[qa + 3] = r.z;
+}
 }
 using namespace mkh;
 
@@ -125,23 +155,12 @@ enum WsRole {
   WS_COUNT
 };
 
-struct MkhModel {
+struct MkhModel : HostModel {     // (the host arrays problems are planned from: problem_plan.h)
   int device = 0;
   PinnedScratch small;             // mkh_integrate, host pointers
   std::mutex small_mutex;          // one model serves many callers (every Configuration of a FlatModel shares it): the small
                                    // host-pointer path of mkh_integrate is serialised, so the entry point stays re-entrant
-  int nq = 0, nv = 0, nbody = 0, njnt = 0, ngeom = 0, nsite = 0, nrounds = 0;
-  // host copies needed when problems are created
-  std::vector<int32_t> body_parentid, body_rootid, body_jntnum, body_jntadr, body_dofnum, body_dofadr;
-  std::vector<int32_t> jnt_type, jnt_qposadr, jnt_dofadr, jnt_bodyid, jnt_limited;
-  std::vector<int32_t> dof_bodyid, dof_jntid, dof_parentid, site_bodyid, geom_bodyid, geom_type;
-  std::vector<double> body_pos, body_quat, site_pos, site_quat, geom_size, geom_pos, geom_quat, jnt_range;
-  std::vector<double> jnt_pos, jnt_axis, jnt_qpos0;   // (per joint; qpos0 at the joint's first qpos address)
-  std::vector<double> body_ipos, body_mass, body_subtreemass;
-  bool big = false;                // more than 64 bodies or dofs: no lane tables — every problem runs on the workgroup-per-problem kernel
-  std::vector<int32_t> geom_dataid, mesh_vertadr, mesh_vertnum;   // mesh geoms: hull vertices (geom frame) in d_mesh_vert
-  double* d_mesh_vert = nullptr;
-  std::vector<double> h_mesh_vert;   // (host copy: bounding radii of mesh geoms, mkh_problem_create)
+  double* d_mesh_vert = nullptr;   // hull vertices of the mesh geoms (HostModel::h_mesh_vert)
   // device tables
   double* d_body_f = nullptr;
   int32_t* d_body_i = nullptr;
@@ -152,64 +171,22 @@ struct MkhModel {
   int num_cus = 0;
 };
 
-struct MkhProblem {
+struct MkhProblem : ProblemSelect {     // (what creation decided and plan_launch reads: problem_plan.h)
   PinnedScratch small;             // run(), host pointers
   MkhModel* model = nullptr;
   int device = 0;                  // (copied: the destructor must not depend on the model still being alive)
   DeviceProblem dev{};
-  int nt = 8;  // tableau rows per lane (compiled variants: multiples of 8)
   int max_batch = 0;
-  int lds_bytes = 0;
-  int blocks_per_cu = 1;
-  // feature-rich variants (taps / ComTask / collisions / RelativeFrameTask) need the compiler's full VGPR
-  // budget: they never use the high-occupancy register maps of NT ≤ 24 (ik_kernel.h MKH_WAVES)
-  int nt_full = 8, lds_bytes_full = 0;
-  // tight rows (capsule-only collision sets on a small tableau): the same problem with fewer half-space rows than pairs — the
-  // tightest contacts get them, dropped ones are checked at the solution — launched first; the full-row variant then re-solves
-  // what it flagged (SolveArgs::redo_mask)
-  DeviceProblem* d_dev_tight = nullptr;
+  DeviceProblem* d_dev_tight = nullptr;   // the tight-rows twin of `dev` (ProblemSelect::nt_tight)
   int32_t* d_status_tight = nullptr;   // status of a call with a redo launch whose caller passed no status_out (the redo launch reads it)
-  // the workgroup-per-problem kernel (wide_kernel.h): every call of a model beyond one wavefront (wide_only), or the redo
-  // launch of the instances a wavefront kernel flagged MKH_ST_ROW_OVERFLOW
   WideProblem wide{};
   WideProblem* d_wide = nullptr;
-  bool wide_only = false;
-  int wide_grid = 0, wide_lds = 0;
-  std::vector<void*> wide_allocs;
-  int nt_tight = 0, lds_tight = 0;
-  // 3-waves-per-SIMD register map + compact LDS layout (ik_kernel.h MKH_W3; variants without collision rows):
-  // LDS bytes per wavefront, 0 when no such variant is compiled for this tableau size or it would not reach 12 waves per CU
-  int lds_bytes_w3 = 0;
-  bool has_relative = false;
-  bool simple_pairs = false;       // every collision pair is plane / sphere / capsule (F_SIMPLE_COLL variants)
-  bool convex_pairs = false;       // some pair has no analytic routine: general convex distance (F_CONVEX_COLL variants)
-  // low-rank ("Woodbury") start of the QP (ik_kernel.h F_WOOD): compiled (NT, NR) pair or 0 when the
-  // problem does not qualify; lower bound of the diagonal part of H without the damping argument, and
-  // the largest squared task cost (conditioning gate, evaluated per call because damping is a call argument)
-  int wood_nt = 0, wood_nr = 0, wood_lds_bytes = 0, wood_lds_bytes_w3 = 0;
-  int wood_lds_bytes_w4 = 0;         // LDS bytes of the four-waves product-form build (`44_32_r44_w4o`) when 16 wavefronts per CU fit, else 0
-  // low-rank start WITH half-space rows (round 6; `48_40_r48`): the lane tables are in the descriptor(s), LDS bytes of that layout
-  // for the tight-rows descriptor and for the main one (0: not available there)
-  bool woodr_tables = false;
-  int woodr_lds_tight = 0, woodr_lds = 0;
-  bool wood_big = false;           // more than kMu task rows, or S columns in a second register set: the F_COM builds carry those
-  double wood_min_diag = 0.0, wood_max_cost2 = 0.0;
-  // lane-per-problem kernel for small arms (lane_kernel.h): template size (0 = the problem does not qualify)
-  int lane_nv = 0, lane_lds = 0;   // lane kernel's template size (0: not eligible)
-  int quad_nt = 0;                 // row kernel's column registers, 8 or 16 (0: not eligible)
-  bool quad_loop_ok = true;        // two-row build: its fused loop can integrate every coordinate (a free joint is a link)
+  // device memory the handle keeps only to free it: what the descriptors point to (frame tasks, cost and limit tables, pairs,
+  // the wide kernel's arrays, workspace and redo queue, the convex split's lists)
+  std::vector<void*> owned;
   LaneProblem* d_lane = nullptr;
-  LaneDims lane_dims{};
   char last_kernel[64] = "";
-  // device descriptor storage
-  FrameTaskDev* d_frame = nullptr;
-  double* d_posture_cost = nullptr;
-  double *d_cfg_lower = nullptr, *d_cfg_upper = nullptr, *d_vel = nullptr;
-  CollisionPairDev* d_pairs = nullptr;
-  PairCull* d_cull = nullptr;          // bounding-sphere records of the pairs (problems with more than 64 of them)
-  bool use_cull = false;
   int32_t diag = 0;                // MKH_DIAG_* of mkh_problem_create_diag (parity / measurement switches of this handle)
-  double *d_dense_cost = nullptr, *d_dense_wgain = nullptr;
   DeviceProblem* d_dev = nullptr;   // device copy of `dev` (the kernel reads the descriptor from memory)
   TapArgs* d_taps = nullptr;
   int last_grid = 0, last_lds = 0, last_nt = 0, last_block = kWave;   // geometry of the most recent launch (mkh_problem_launch_info)
@@ -217,7 +194,6 @@ struct MkhProblem {
   // general convex pairs of plain solves: evaluated by convex_contacts_kernel in front of the analytic collision build
   mkh::CvPre cv{};
   double* d_cv = nullptr;          // [max_batch][n_cv][7]
-  int32_t *d_cv_pair = nullptr, *d_cv_adr = nullptr, *d_cv_chain = nullptr;
   double* d_qkeep = nullptr;       // fused loops with a redo launch behind them: the call's q as it came (q_out may alias it)
   int8_t* d_warm = nullptr;        // MKH_FLAG_WARM_START: active set of every instance after the previous solve (max_batch × nv)
   int warm_age = 0, warm_B = 0;    // solves since the state was reset / the batch size it belongs to
@@ -234,10 +210,7 @@ struct MkhProblem {
   // the outer-loop entry points' workspace, by role (WsRole)
   bool ws_tables = false;
   GrowBuf ws[WS_COUNT];
-  // seed tables: the default weights of a table made from this problem — [f]: 1 when plain FrameTask f has a position cost > 0,
-  // [n_frame + f]: an orientation cost > 0; a RelativeFrameTask: 0 / 0 — and the table attached by mkh_problem_set_seed_table
-  std::vector<double> frame_w;
-  const MkhSeedTable* seed_table = nullptr;
+  const MkhSeedTable* seed_table = nullptr;    // attached by mkh_problem_set_seed_table
 };
 
 // A seed table (include/minkhip.h "Seed tables"): device memory of its own — nothing of the problem that made it is kept.
@@ -260,233 +233,6 @@ int launch_convex_pre(hipStream_t stream, const WideProblem* P, const CvPre& C, 
 constexpr int kLaneMinBatchLoop = 28672;  // fused loops of a small arm: row kernel below, lane kernel from here (M targets/s at 16 384: 39.7 vs 24.1, at 32 768: 42.4 vs 48.2)
 constexpr int kLaneMinBatch = 73728;  // plain solves of a small arm: row kernel below, lane kernel from here (plan_launch())
 }
-
-// Descriptor of the row- and lane-per-problem kernels (quad_kernel.h, lane_kernel.h) of a problem that qualifies: nv ≤ 16
-// (row kernel; the lane kernel: nv ≤ 8), at most 16 links on the frames' chains, hinge / slide joints only, plain
-// FrameTasks (≤ 8) + PostureTasks + box limits.  Returns the size class (4 / 6 / 7 / 8: both kernels, 16: the row
-// kernel only), 0 when the problem stays on the wavefront kernel.
-static int build_lane_problem(const MkhModel* m, const MkhProblemDesc* d, const DeviceProblem& P,
-                              const std::vector<FrameTaskDev>& ft, const std::vector<double>& pcost,
-                              const std::vector<double>& clo, const std::vector<double>& chi,
-                              const std::vector<double>& vlim, bool has_relative, LaneProblem2& L) {
-  const double inf = std::numeric_limits<double>::infinity();
-  if (m->nv > kLaneDescDofs2) return 0;
-  if (P.n_frame < 1 || P.n_frame > kLaneMaxFrames || P.n_com > 1 || P.n_pairs || P.n_dense_rows ||
-      P.n_dense_limit_rows || P.dense_box)       // (dense_box: per-instance box rows of a plugin limit, wavefront kernels only)
-    return 0;
-  const bool com = P.n_com == 1;                 // ComTask: the two-row build of the row kernel, every body of the robot a link
-  if (com && (m->big || m->body_mass.empty())) return 0;
-  // hinge / slide joints; the two-row build of the row kernel (17 … 32 dofs or links) also takes free joints — a floating base
-  bool has_free = false;
-  for (int j = 0; j < m->njnt; ++j) {
-    if (m->jnt_type[j] == JNT_FREE && m->body_jntnum[m->jnt_bodyid[j]] == 1) { has_free = true; continue; }
-    if (m->jnt_type[j] != JNT_HINGE && m->jnt_type[j] != JNT_SLIDE) return 0;
-  }
-  if (m->nq != m->nv + (has_free ? 1 : 0)) return 0;      // (one free joint at most: its quaternion is the extra coordinate)
-  memset(&L, 0, sizeof L);
-  L.nq = m->nq; L.nv = m->nv; L.n_frame = P.n_frame; L.n_posture = P.n_posture; L.n_cfg = P.n_cfg; L.n_vel = P.n_vel;
-  // links = the bodies on the chains world → frame bodies, in body-id order (parents first)
-  std::vector<int> need(m->nbody, 0), link_of(m->nbody, -1);
-  for (int t = 0; t < P.n_frame; ++t) {
-    for (int b = ft[t].body; b > 0; b = m->body_parentid[b]) need[b] = 1;
-    if (ft[t].relative)                              // RelativeFrameTask: the root frame's chain as well (two-row build)
-      for (int b = ft[t].root_body; b > 0; b = m->body_parentid[b]) need[b] = 1;
-  }
-  std::vector<char> in_robot(m->nbody, 0);           // subtree of body 1 (mj_jacSubtreeCom(m, d, jac, 1): com_task.py:71-97)
-  if (com)
-    for (int b = 1; b < m->nbody; ++b) {
-      in_robot[b] = b == 1 || in_robot[m->body_parentid[b]];
-      if (in_robot[b]) need[b] = 1;
-    }
-  int nl = 0;
-  int free_link[4] = {-1, -1, -1, -1};
-  std::vector<int> link_of_jnt(m->njnt, -1);
-  // Pose of a jointless body relative to its nearest ancestor that is a link (or the world): folded into the local
-  // transforms of its children and of the frames attached to it, so that it costs neither a link nor LDS.
-  struct Xf { double p[3], q[4]; };
-  auto compose = [](const Xf& a, const double* p, const double* q) {     // a ∘ (p, q)
-    Xf r;
-    const double w = a.q[0], x = a.q[1], y = a.q[2], z = a.q[3];
-    const double tx = 2 * (y * p[2] - z * p[1]), ty = 2 * (z * p[0] - x * p[2]), tz = 2 * (x * p[1] - y * p[0]);
-    r.p[0] = a.p[0] + p[0] + w * tx + (y * tz - z * ty);
-    r.p[1] = a.p[1] + p[1] + w * ty + (z * tx - x * tz);
-    r.p[2] = a.p[2] + p[2] + w * tz + (x * ty - y * tx);
-    r.q[0] = w * q[0] - x * q[1] - y * q[2] - z * q[3];
-    r.q[1] = w * q[1] + x * q[0] + y * q[3] - z * q[2];
-    r.q[2] = w * q[2] - x * q[3] + y * q[0] + z * q[1];
-    r.q[3] = w * q[3] + x * q[2] - y * q[1] + z * q[0];
-    return r;
-  };
-  const Xf ident{{0, 0, 0}, {1, 0, 0, 0}};
-  std::vector<Xf> fold(m->nbody, ident);
-  std::vector<char> folded(m->nbody, 0);
-  folded[0] = 1;                                      // the world: identity, link −1
-  for (int b = 1; b < m->nbody; ++b) {
-    if (!need[b]) continue;
-    const int pb = m->body_parentid[b];
-    const Xf local = folded[pb] ? compose(fold[pb], &m->body_pos[3 * b], &m->body_quat[4 * b])
-                                : compose(ident, &m->body_pos[3 * b], &m->body_quat[4 * b]);
-    if (m->body_jntnum[b] == 0) {                     // jointless: fold
-      fold[b] = local; folded[b] = 1; link_of[b] = link_of[pb];
-      continue;
-    }
-    // A body with k > 1 joints becomes a chain of k links with identity offsets: mj_kinematics applies a body's
-    // joints one after the other in the moving body frame, which is exactly a serial chain of coincident frames.
-    if (m->jnt_type[m->body_jntadr[b]] == JNT_FREE) {
-      // mj_kinematics: a free body's pose IS its qpos (body_pos / body_quat are not used): three slide links along the world
-      // axes from the origin, then the rotation
-      const int jj = m->body_jntadr[b];
-      if (nl + 4 > kLaneMaxLinks2) return 0;
-      for (int i = 0; i < 4; ++i) {
-        LaneLink& k = L.link[nl];
-        k.parent = i == 0 ? -1 : nl - 1;
-        k.quat[0] = 1.0;
-        k.jtype = i < 3 ? JNT_SLIDE : JNT_BALL;
-        k.dof = m->jnt_dofadr[jj] + (i < 3 ? i : 3);
-        k.qadr = m->jnt_qposadr[jj] + 3;
-        if (i < 3) k.axis[i] = 1.0;
-        free_link[i] = nl++;
-      }
-      link_of_jnt[jj] = nl - 1;
-      link_of[b] = nl - 1;
-      continue;
-    }
-    for (int i = 0; i < m->body_jntnum[b]; ++i) {
-      if (nl >= kLaneMaxLinks2) return 0;
-      LaneLink& k = L.link[nl];
-      k.parent = i == 0 ? link_of[pb] : nl - 1;
-      k.quat[0] = 1.0;
-      if (i == 0) {
-        for (int c = 0; c < 3; ++c) k.pos[c] = local.p[c];
-        for (int c = 0; c < 4; ++c) k.quat[c] = local.q[c];
-      }
-      const int jj = m->body_jntadr[b] + i;
-      k.jtype = m->jnt_type[jj]; k.dof = m->jnt_dofadr[jj]; k.qpos0 = m->jnt_qpos0[jj];
-      for (int c = 0; c < 3; ++c) { k.axis[c] = m->jnt_axis[3 * jj + c]; k.jpos[c] = m->jnt_pos[3 * jj + c]; }
-      link_of_jnt[jj] = nl;
-      link_of[b] = nl++;
-    }
-  }
-  L.nlink = nl;
-  for (int dd = 0; dd < kLaneDescDofs2; ++dd) { L.dof_link[dd] = -1; L.dof_qadr[dd] = 0; L.range_lo[dd] = -inf; L.range_hi[dd] = inf; }
-  for (int dd = 0; dd < m->nv; ++dd) {
-    const int j = m->dof_jntid[dd];
-    if (m->jnt_type[j] == JNT_FREE) {
-      // dofs 0-2: translations along the world axes (the slide links); 3-5: rotations about the body's own axes through its origin
-      const int k = dd - m->jnt_dofadr[j];
-      L.dof_link[dd] = link_of_jnt[j] < 0 ? -1 : (k < 3 ? free_link[k] : free_link[3]);
-      L.dof_qadr[dd] = m->jnt_qposadr[j] + (k < 3 ? k : k + 1);      // (rotations: any finite entry — their posture cost is zero, mink/tasks/posture_task.py:95-99)
-      L.dof_axis[dd][k % 3] = 1.0;
-      L.dof_slide[dd] = k < 3;
-      continue;
-    }
-    L.dof_link[dd] = link_of_jnt[j];
-    L.dof_qadr[dd] = m->jnt_qposadr[j];
-    for (int c = 0; c < 3; ++c) { L.dof_axis[dd][c] = m->jnt_axis[3 * j + c]; L.dof_jpos[dd][c] = m->jnt_pos[3 * j + c]; }
-    L.dof_slide[dd] = m->jnt_type[j] == JNT_SLIDE;
-    if (m->jnt_limited[j]) { L.range_lo[dd] = m->jnt_range[2 * j]; L.range_hi[dd] = m->jnt_range[2 * j + 1]; }
-  }
-  if (com) {
-    L.n_com = 1;
-    L.com_rowmask = P.com_rowmask[0];
-    for (int k = 0; k < 3; ++k) L.com_cost[k] = P.com_cost[0][k];
-    L.com_gain = P.com_gain[0]; L.com_lm = P.com_lm[0];
-    double mtot = 0.0;
-    std::vector<double> wsum(3 * (nl > 0 ? nl : 1), 0.0);        // Σ m·(centre of mass in the link frame) per link
-    for (int b = 1; b < m->nbody; ++b) {
-      if (!in_robot[b]) continue;
-      const double mb = m->body_mass[b];
-      mtot += mb;
-      // the body's centre of mass in the frame of its link (its own frame, or through the folded jointless chain) — or in the world
-      Xf at = ident;
-      if (m->body_jntnum[b] == 0) at = fold[b];
-      const Xf cw = compose(at, &m->body_ipos[3 * b], ident.q);
-      const int a = link_of[b];
-      if (a < 0) { for (int k = 0; k < 3; ++k) L.com_static[k] += mb * cw.p[k]; continue; }
-      L.link_mass[a] += mb;
-      for (int k = 0; k < 3; ++k) wsum[3 * a + k] += mb * cw.p[k];
-    }
-    if (!(mtot > 0.0)) return 0;
-    L.com_minv = 1.0 / mtot;
-    for (int a = 0; a < nl; ++a) {
-      for (int k = 0; k < 3; ++k) L.link_ipos[a][k] = L.link_mass[a] > 0.0 ? wsum[3 * a + k] / L.link_mass[a] : 0.0;
-      // links are in body order (depth first): the subtree of a link is the range up to the next link that is not below it
-      int last = a;
-      for (int c = a + 1; c < nl; ++c) {
-        int up = L.link[c].parent;
-        while (up > a) up = L.link[up].parent;
-        if (up != a) break;
-        last = c;
-      }
-      L.link_last[a] = last;
-      for (int c = a; c <= last; ++c) L.link_stmass[a] += L.link_mass[c];
-    }
-    for (int dd = 0; dd < m->nv; ++dd) if (L.dof_link[dd] < 0) return 0;     // (every dof of the robot moves mass: all need their link)
-  }
-  for (int t = 0; t < P.n_frame; ++t) {
-    LaneFrame& f = L.frame[t];
-    f.link = link_of[ft[t].body];
-    f.chain = (uint32_t)ft[t].dof_mask;
-    f.rowmask = ft[t].rowmask;
-    const Xf fl = folded[ft[t].body] ? compose(fold[ft[t].body], ft[t].lpos, ft[t].lquat) : compose(ident, ft[t].lpos, ft[t].lquat);
-    for (int i = 0; i < 3; ++i) f.lpos[i] = fl.p[i];
-    for (int i = 0; i < 4; ++i) f.lquat[i] = fl.q[i];
-    for (int i = 0; i < 6; ++i) f.cost[i] = ft[t].cost[i];
-    f.gain = ft[t].gain; f.lm_damping = ft[t].lm_damping;
-    if (ft[t].relative) {
-      auto& r = L.rel[t];
-      r.relative = 1;
-      r.root_link = link_of[ft[t].root_body];
-      r.rchain = (uint32_t)ft[t].root_mask;
-      const Xf rl = folded[ft[t].root_body] ? compose(fold[ft[t].root_body], ft[t].root_lpos, ft[t].root_lquat)
-                                             : compose(ident, ft[t].root_lpos, ft[t].root_lquat);
-      for (int i = 0; i < 3; ++i) r.rlpos[i] = rl.p[i];
-      for (int i = 0; i < 4; ++i) r.rlquat[i] = rl.q[i];
-    }
-  }
-  for (int t = 0; t < P.n_posture; ++t) {
-    for (int dd = 0; dd < m->nv; ++dd)      // (free-joint dofs: error and Jacobian column are zero, posture_task.py:115-116,139-141)
-      L.posture_cost[t][dd] = m->jnt_type[m->dof_jntid[dd]] == JNT_FREE ? 0.0 : pcost[t * 64 + dd];
-    L.posture_gain[t] = P.posture_gain[t]; L.posture_lm[t] = P.posture_lm[t];
-  }
-  for (int t = 0; t < kMaxBoxTerms; ++t)
-    for (int dd = 0; dd < kLaneDescDofs2; ++dd) { L.cfg_lower[t][dd] = -inf; L.cfg_upper[t][dd] = inf; L.vel_limit[t][dd] = inf; }
-  for (int t = 0; t < P.n_cfg; ++t) {
-    L.cfg_gain[t] = P.cfg_gain[t];
-    for (int dd = 0; dd < m->nv; ++dd) { L.cfg_lower[t][dd] = clo[t * 64 + dd]; L.cfg_upper[t][dd] = chi[t * 64 + dd]; }
-  }
-  for (int t = 0; t < P.n_vel; ++t)
-    for (int dd = 0; dd < m->nv; ++dd) L.vel_limit[t][dd] = vlim[t * 64 + dd];
-  (void)d;
-  if (has_free || com || has_relative || m->nv > 16 || nl > 16) return 32;                                     // (32: the row kernel on two DPP rows per problem)
-  return m->nv <= 4 ? 4 : (m->nv <= 6 ? 6 : (m->nv == 7 ? 7 : (m->nv == 8 ? 8 : 16)));   // (16: the row kernel only)
-}
-
-// Resident wavefronts per CU of a kernel variant: bounded by LDS (160 KiB/CU) and by the register map the
-// variant was built for (4 waves/SIMD for NT ≤ 8, 3 for NT ≤ 24, else 2 — ik_kernel.h MKH_WAVES).
-static int waves_per_cu(int nt, int lds_bytes, bool w3 = false) {
-  int by_lds = (160 * 1024) / (lds_bytes > 0 ? lds_bytes : 1);
-  // gfx950 hands LDS out in granules of 320 dwords: 128 of them per CU.  A persistent kernel must not be launched with more
-  // workgroups than are resident at once — the ones that wait for a slot start when the first ones EXIT, i.e. after the whole
-  // batch, and then walk their static share alone (round 5: `44_36_r44_w3` asked for 16 064 B, 10 per CU by division, 9 by
-  // granules: 2.12 ms instead of 1.44 with a third of the CUs idle; SQ_WAVE_CYCLES / SQ_BUSY_CYCLES gave it away).  Applied
-  // where a layout lands between the two figures: the F_COM builds on the one-more-wave map.
-  if (w3 && nt == 44 && lds_bytes > (160 * 1024) / 12) by_lds = 128 / ((lds_bytes + 1279) / 1280);
-  // (w3: the high-occupancy build of the variant — one more resident wave per SIMD than its plain register map)
-  const int by_regs = 4 * (nt <= 8 ? 4 : (nt <= 24 ? (w3 ? 4 : 3) : (w3 ? 3 : 2)));
-  const int w = by_lds < by_regs ? by_lds : by_regs;
-  return w < 1 ? 1 : w;
-}
-
-// LDS bytes per wavefront of one build (nt, nr, feat, one-more-wave map) on descriptor D: the `total` of the layout that build's
-// kernel indexes (ik_kernel.h build_lds_layout — kernel_lds_layout calls the same function with its compile-time constants).
-// (prefetch, compact: 0 / 1 while mkh_problem_create tries them; kFromDescriptor once they are fixed in D)
-static int lds_bytes_of(const DeviceProblem& D, int nt, int nr, int feat, bool w3, int prefetch = kFromDescriptor, int compact = kFromDescriptor) {
-  return build_lds_layout(D, nt, nr, feat, w3, prefetch, compact).total * (int)sizeof(double);
-}
-// The two-waves direct-start builds share one reservation per tableau size, whatever their features: the one with collision
-// rows, whose layout ends with the pair-selection block (DeviceProblem::n_hsel — 0 in a problem without pairs).
-constexpr int kDirectFeat = F_COLL;
 
 template <class T>
 static hipError_t ensure(T** buf, size_t n) {
@@ -516,211 +262,6 @@ static void assign_taps(const MkhTaps* taps, const DeviceProblem& P, size_t Bz, 
 }
 
 
-// The descriptor of the workgroup-per-problem kernel (wide_kernel.h): plain arrays over bodies / joints / dofs (no 64-wide
-// lane tables), the kinematic tree by levels, the dof chain of every body as a bit set, LDS offsets, and the per-workgroup
-// slice of device memory (weighted Jacobian rows, contact records, the tableau when it does not fit in LDS).
-static int32_t build_wide_problem(MkhProblem* p, const MkhModel* m, const MkhProblemDesc* d, const std::vector<FrameTaskDev>& ft,
-                                  const std::vector<CollisionPairDev>& pairs, const std::vector<PairCull>& culls, const std::vector<double>& dcost,
-                                  const std::vector<double>& dwgain) {
-  const double inf = std::numeric_limits<double>::infinity();
-  WideProblem& W = p->wide;
-  memset(&W, 0, sizeof W);
-  const int nv = m->nv, nb = m->nbody, nj = m->njnt;
-  W.nq = m->nq; W.nv = nv; W.nbody = nb; W.njnt = nj; W.robot_root = 1;
-  W.n_frame = d->n_frame_tasks; W.n_posture = d->n_posture_tasks; W.n_com = d->n_com_tasks;
-  W.n_cfg = d->n_configuration_limits; W.n_vel = d->n_velocity_limits; W.n_pairs = (int)pairs.size();
-  W.n_dense_tasks = d->n_dense_tasks; W.n_dense_rows = (int)dcost.size(); W.n_dense_limit_rows = d->n_dense_limit_rows;
-  W.dense_box = d->dense_limit_box ? 1 : 0;
-  auto up = [&](const auto& v, auto** out) -> hipError_t {
-    const hipError_t e = upload(v, out);
-    if (e == hipSuccess) p->wide_allocs.push_back((void*)*out);
-    return e;
-  };
-  // ---- the tree by levels, subtree ranges, dof chains
-  std::vector<int32_t> depth(nb, 0), level_start, level_body, last(nb), inrobot(nb), jadr(nb);
-  int maxd = 0;
-  for (int b = 1; b < nb; ++b) { depth[b] = depth[m->body_parentid[b]] + 1; if (depth[b] > maxd) maxd = depth[b]; }
-  for (int lv = 0; lv <= maxd; ++lv) {
-    level_start.push_back((int32_t)level_body.size());
-    for (int b = 0; b < nb; ++b) if (depth[b] == lv) level_body.push_back(b);
-  }
-  level_start.push_back((int32_t)level_body.size());
-  W.nlevels = maxd + 1;
-  for (int b = nb - 1; b >= 0; --b) {
-    last[b] = b;
-    for (int c = b + 1; c < nb; ++c) if (m->body_parentid[c] == b && last[c] > last[b]) last[b] = last[c];
-  }
-  for (int b = 0; b < nb; ++b) { inrobot[b] = (b >= 1 && m->body_rootid[b] == 1) ? 1 : 0; jadr[b] = m->body_jntadr[b] < 0 ? 0 : m->body_jntadr[b]; }
-  W.chain_words = (nv + 63) / 64;
-  std::vector<uint64_t> chain((size_t)nb * W.chain_words, 0ull);
-  for (int b = 1; b < nb; ++b) {
-    int x = b;
-    while (x > 0 && m->body_dofnum[x] == 0) x = m->body_parentid[x];
-    if (x == 0) continue;
-    for (int i = m->body_dofadr[x] + m->body_dofnum[x] - 1; i >= 0; i = m->dof_parentid[i])
-      chain[(size_t)b * W.chain_words + (i >> 6)] |= 1ull << (i & 63);
-  }
-  // ---- dofs
-  std::vector<int32_t> dkind(nv), dk(nv, 0), dqadr(nv, -1);
-  std::vector<double> dlo(nv, -inf), dhi(nv, inf);
-  for (int dd = 0; dd < nv; ++dd) {
-    const int j = m->dof_jntid[dd], jt = m->jnt_type[j], k = dd - m->jnt_dofadr[j];
-    if (jt == JNT_HINGE) { dkind[dd] = DOF_HINGE; dqadr[dd] = m->jnt_qposadr[j]; }
-    else if (jt == JNT_SLIDE) { dkind[dd] = DOF_SLIDE; dqadr[dd] = m->jnt_qposadr[j]; }
-    else if (jt == JNT_BALL) { dkind[dd] = DOF_BALL; dk[dd] = k; dqadr[dd] = m->jnt_qposadr[j]; }
-    else if (k < 3) { dkind[dd] = DOF_FREE_LIN; dk[dd] = k; }
-    else { dkind[dd] = DOF_FREE_ANG; dk[dd] = k - 3; }
-    if (((jt == JNT_HINGE || jt == JNT_SLIDE) || (jt == JNT_BALL && k == 0)) && m->jnt_limited[j]) {
-      dlo[dd] = m->jnt_range[2 * j]; dhi[dd] = m->jnt_range[2 * j + 1];
-    }
-  }
-  // ---- tasks and limits, one value per dof
-  std::vector<double> pcost((size_t)(W.n_posture ? W.n_posture : 1) * nv, 0.0);
-  for (int t = 0; t < W.n_posture; ++t) {
-    for (int i = 0; i < nv; ++i) pcost[(size_t)t * nv + i] = d->posture_tasks[t].cost[i];
-    W.posture_gain[t] = d->posture_tasks[t].gain; W.posture_lm[t] = d->posture_tasks[t].lm_damping;
-  }
-  int jrows = 0;
-  for (const auto& f : ft) jrows += __builtin_popcount(f.rowmask);      // (FrameTaskDev::jrow0 counts the same way)
-  for (int t = 0; t < W.n_com; ++t) {
-    W.com_rowmask[t] = 0;
-    for (int k = 0; k < 3; ++k) { W.com_cost[t][k] = d->com_tasks[t].cost[k]; if (d->com_tasks[t].cost[k] != 0.0) W.com_rowmask[t] |= 1 << k; }
-    W.com_gain[t] = d->com_tasks[t].gain; W.com_lm[t] = d->com_tasks[t].lm_damping;
-    W.com_jrow0[t] = jrows; jrows += __builtin_popcount(W.com_rowmask[t]);
-  }
-  W.n_jrows = jrows;
-  // rows of the (e, J) tap layout — the same order mkh_problem_create counts for the wavefront kernels (DeviceProblem::n_rows_tap)
-  {
-    int row = 6 * W.n_frame;
-    for (int t = 0; t < W.n_posture; ++t) { W.posture_row0[t] = row; row += nv; }
-    for (int t = 0; t < W.n_com; ++t) { W.com_row0[t] = row; row += 3; }
-    W.dense_tap_row0 = row;
-    for (int t = 0; t < W.n_dense_tasks; ++t) row += d->dense_tasks[t].k;
-    W.n_rows_tap = row;
-  }
-  for (int t = 0, r0 = 0; t < W.n_dense_tasks; ++t) {
-    W.dense_row0[t] = r0; W.dense_k[t] = d->dense_tasks[t].k; W.dense_lm[t] = d->dense_tasks[t].lm_damping; r0 += d->dense_tasks[t].k;
-  }
-  std::vector<double> clo((size_t)(W.n_cfg ? W.n_cfg : 1) * nv, -inf), chi((size_t)(W.n_cfg ? W.n_cfg : 1) * nv, inf);
-  for (int t = 0; t < W.n_cfg; ++t) {
-    const MkhConfigurationLimitDesc& c = d->configuration_limits[t];
-    W.cfg_gain[t] = c.gain;
-    for (int k = 0; k < c.n_indices; ++k) {
-      const int dof = c.indices[k], qa = m->jnt_qposadr[m->dof_jntid[dof]];     // (validated by the caller)
-      clo[(size_t)t * nv + dof] = c.lower[qa]; chi[(size_t)t * nv + dof] = c.upper[qa];
-    }
-  }
-  std::vector<double> vlim((size_t)(W.n_vel ? W.n_vel : 1) * nv, inf);
-  for (int t = 0; t < W.n_vel; ++t) {
-    const MkhVelocityLimitDesc& v = d->velocity_limits[t];
-    for (int k = 0; k < v.n_indices; ++k) vlim[(size_t)t * nv + v.indices[k]] = std::fmin(vlim[(size_t)t * nv + v.indices[k]], v.limit[k]);
-  }
-  hipError_t e = hipSuccess;
-#define MKH_UP(vec, field) if (e == hipSuccess) { std::remove_const_t<std::remove_pointer_t<decltype(W.field)>>* dp = nullptr; e = up(vec, &dp); W.field = dp; }
-  MKH_UP(level_start, level_start) MKH_UP(level_body, level_body) MKH_UP(m->body_parentid, body_parent) MKH_UP(jadr, body_jntadr)
-  MKH_UP(m->body_jntnum, body_jntnum) MKH_UP(last, body_last) MKH_UP(inrobot, body_inrobot)
-  MKH_UP(m->body_pos, body_pos) MKH_UP(m->body_quat, body_quat) MKH_UP(m->body_ipos, body_ipos) MKH_UP(m->body_mass, body_mass)
-  MKH_UP(m->body_subtreemass, body_stmass) MKH_UP(m->jnt_type, jnt_type) MKH_UP(m->jnt_qposadr, jnt_qadr) MKH_UP(m->jnt_dofadr, jnt_dadr) MKH_UP(m->jnt_axis, jnt_axis)
-  MKH_UP(m->jnt_pos, jnt_pos) MKH_UP(m->jnt_qpos0, jnt_qpos0) MKH_UP(m->dof_jntid, dof_jnt) MKH_UP(dkind, dof_kind) MKH_UP(dk, dof_k)
-  MKH_UP(m->dof_bodyid, dof_body) MKH_UP(dqadr, dof_qadr) MKH_UP(dlo, dof_lo) MKH_UP(dhi, dof_hi) MKH_UP(chain, chain)
-  MKH_UP(ft, frame) MKH_UP(pcost, posture_cost) MKH_UP(dcost, dense_cost) MKH_UP(dwgain, dense_wgain) MKH_UP(clo, cfg_lower)
-  MKH_UP(chi, cfg_upper) MKH_UP(vlim, vel_limit) MKH_UP(pairs, pairs)
-  // ---- LDS layout and the per-workgroup slice of device memory
-  const int rows_max = W.n_pairs + W.n_dense_limit_rows;
-  W.max_rows = rows_max < kWideMaxRows ? rows_max : kWideMaxRows;
-  const int Ncap = nv + W.max_rows, R_all = W.n_jrows + W.n_dense_rows;
-  auto ev = [](int x) { return (x + 1) & ~1; };
-  // more than a wavefront of pairs: bounding-sphere cull in front of the distance routines (wide_contacts; the candidate list —
-  // 16-bit pair indices — lives in the three QP vectors behind o_rown, which are dead until the tableau is built)
-  W.cull = nullptr;
-  if (W.n_pairs > kWave && W.n_pairs < 65536 && W.n_pairs <= 12 * ev(Ncap) && culls.size() == pairs.size() && !(p->diag & MKH_DIAG_NO_PAIR_CULL)) { MKH_UP(culls, cull) }
-#undef MKH_UP
-  if (e != hipSuccess) return fail(MKH_E_HIP, "wide problem upload: %s", hipGetErrorString(e));
-  int o = 0;
-  W.o_q = o; o += ev(W.nq);
-  W.o_X = o; o += ev(7 * nb);
-  W.o_jnt = o; o += ev(6 * (nj > 0 ? nj : 1));
-  W.o_dof = o; o += 10 * nv;
-  W.o_task = o; o += 64 * (W.n_frame > 0 ? W.n_frame : 1);
-  W.o_com = o; o += W.n_com > 0 ? 4 * nb : 0;
-  W.o_we = o; o += ev(R_all > 0 ? R_all : 1);
-  W.o_c = o; o += ev(nv);
-  W.o_hd = o; o += ev(nv);
-  W.o_z = o; o += ev(Ncap); W.o_w = o; o += ev(Ncap); W.o_lo = o; o += ev(nv); W.o_hi = o; o += ev(nv);
-  W.o_rown = o; o += ev(Ncap); W.o_ref = o; o += ev(Ncap); W.o_col = o; o += ev(Ncap);
-  W.o_red = o; o += kWideThreads + kWideThreads / 2;
-  W.o_state = o; o += ev((Ncap + 1) / 2);
-  W.o_cws = o; o += p->convex_pairs ? 4 * (kEpaWsDoubles > kGjkWsDoubles ? kEpaWsDoubles : kGjkWsDoubles) : 0;
-  const int lds_cap = (160 * 1024 - 2048) / 8;                              // doubles of LDS one workgroup may take
-  // staging vectors of the block pivots (wide_kernel.h wide_rank4): over the poses / joint axes when they fit, else appended — unless
-  // that would push the tableau out of LDS or cost the second resident workgroup
-  W.blk_stride = ev(Ncap);
-  W.o_blk = -1;
-  if (8 * W.blk_stride <= W.o_dof - W.o_X) W.o_blk = W.o_X;
-  else {
-    const long long with = (long long)o + 8 * W.blk_stride, t = (long long)Ncap * Ncap;
-    const bool keeps_t = (with + t <= lds_cap) == ((long long)o + t <= lds_cap);
-    const long long tot0 = (long long)o + ((long long)o + t <= lds_cap ? t : 0), tot1 = with + (with + t <= lds_cap ? t : 0);
-    const bool keeps_two = (tot1 * 8 <= 80 * 1024) == (tot0 * 8 <= 80 * 1024);
-    if (with <= lds_cap && keeps_t && keeps_two) { W.o_blk = o; o += 8 * W.blk_stride; }
-  }
-  W.tableau_in_lds = (long long)o + (long long)Ncap * Ncap <= lds_cap ? 1 : 0;
-  // the dense Goldfarb–Idnani fallback's factors (2·nv² + 2·nv + 8 doubles) in LDS when that costs neither the tableau's place nor
-  // the second resident workgroup
-  const long long gi_sz = rows_max > 0 ? 2ll * nv * (nv | 1) + 4ll * (nv + 2) : 0;
-  const int two_wg = 80 * 1024 / 8;
-  W.o_gi = o; W.gi_in_lds = 0;
-  if (gi_sz > 0 && (long long)o + gi_sz + (long long)(nv + 8) * (nv + 8) <= two_wg) { W.gi_in_lds = 1; o += (int)gi_sz; }
-  W.o_T = o;
-  if (W.tableau_in_lds) { W.t_lds_doubles = Ncap * Ncap; o += Ncap * Ncap; }
-  else {
-    // the largest instance does not fit: reserve what keeps two workgroups resident (or, failing that, what is left) for the
-    // instances that do — most have far fewer rows in range than the limit lists pairs
-    long long room = (long long)two_wg - o;
-    if (room < (long long)(nv + 8) * (nv + 8)) room = (long long)lds_cap - o;
-    W.t_lds_doubles = room > 0 ? (int)room : 0;
-    o += W.t_lds_doubles;
-  }
-  W.lds_doubles = o;
-  if (o > lds_cap)
-    return fail(MKH_E_LIMIT, "model too large for the workgroup-per-problem kernel: %d KB of LDS per problem, 158 KB available (per problem "
-                "≈ 8·(nq + 7·nbody + 6·njnt + 14·nv + 5.5·(nv + rows) + 64·frame tasks) bytes: a serial chain fits up to ≈ 550 dofs)", o / 128);
-  long long w = 0;
-  W.ws_jw = w; w += (long long)(R_all > 0 ? R_all : 1) * nv;
-  W.ws_rec = w; w += (long long)(W.n_pairs > 0 ? W.n_pairs : 1) * 10;
-  W.ws_rowpair = w; w += ev((W.max_rows + 2) / 2);
-  W.ws_rank = w; w += ev((W.n_pairs + 2) / 2);
-  W.ws_T = w; w += W.tableau_in_lds ? 0 : (long long)Ncap * Ncap;
-  W.ws_gi = w; w += rows_max > 0 ? 2ll * nv * (nv | 1) + 4ll * (nv + 2) : 0;
-  W.ws_stride = (w + 15) & ~15ll;
-  const int per_cu = (160 * 1024) / (o * 8) < 2 ? ((160 * 1024) / (o * 8) < 1 ? 1 : (160 * 1024) / (o * 8)) : 2;
-  int grid = m->num_cus * per_cu;
-  if (grid > p->max_batch) grid = p->max_batch;
-  while (grid > 1 && (long long)grid * W.ws_stride * 8 > (1ll << 30)) grid /= 2;      // (≤ 1 GB of slices)
-  double* ws = nullptr;
-  if (hipMalloc((void**)&ws, (size_t)grid * W.ws_stride * 8) != hipSuccess) return fail(MKH_E_HIP, "wide workspace (%lld MB)", (long long)grid * W.ws_stride * 8 >> 20);
-  p->wide_allocs.push_back(ws);
-  W.ws = ws;
-  p->wide_grid = grid; p->wide_lds = o * 8;
-
-  {
-    uint32_t cap = 256;
-    while (cap < (uint32_t)p->max_batch) cap *= 2;
-    int32_t* rq = nullptr;
-    if (hipMalloc((void**)&rq, ((size_t)cap + 4) * sizeof(int32_t)) != hipSuccess) return fail(MKH_E_HIP, "redo queue");
-    p->wide_allocs.push_back(rq);
-    if (hipMemset(rq, 0xff, (size_t)cap * sizeof(int32_t)) != hipSuccess || hipMemset(rq + cap, 0, 4 * sizeof(int32_t)) != hipSuccess)
-      return fail(MKH_E_HIP, "redo queue");
-    W.redo_queue = rq; W.redo_ctr = reinterpret_cast<uint32_t*>(rq + cap); W.redo_cap = cap; W.redo_pad = 0;
-  }
-  if (hipMalloc((void**)&p->d_wide, sizeof(WideProblem)) != hipSuccess ||
-      hipMemcpy(p->d_wide, &W, sizeof(WideProblem), hipMemcpyHostToDevice) != hipSuccess)
-    return fail(MKH_E_HIP, "wide descriptor upload failed");
-  if (!p->d_status_tight && hipMalloc((void**)&p->d_status_tight, (size_t)p->max_batch * sizeof(int32_t)) != hipSuccess)
-    return fail(MKH_E_HIP, "status buffer");
-  return MKH_OK;
-}
-
 // one launch of the workgroup-per-problem kernel: every instance (redo_mask = 0) or the ones a wavefront kernel flagged
 static int32_t launch_wide_kernel(MkhProblem* p, const SolveArgs& a, hipStream_t stream, int32_t redo_mask, const TapArgs* dtaps = nullptr) {
   SolveArgs aw = a;
@@ -745,176 +286,25 @@ int32_t mkh_device_count(void) {
   return n;
 }
 
-static uint64_t dof_chain_mask(const MkhModel* m, int body) {
-  uint64_t mask = 0;
-  while (body > 0 && m->body_dofnum[body] == 0) body = m->body_parentid[body];
-  if (body == 0) return 0;
-  int i = m->body_dofadr[body] + m->body_dofnum[body] - 1;
-  while (i >= 0) {
-    mask |= 1ull << i;
-    i = m->dof_parentid[i];
-  }
-  return mask;
-}
-
 int32_t mkh_model_create(const MkhFlatModel* h, int32_t device, MkhModel** out) {
   if (!h || !out) return fail(MKH_E_INVALID, "null argument");
   *out = nullptr;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MKH_E_NOGPU, "no HIP device visible");
   if (device < 0 || device >= ndev) return fail(MKH_E_INVALID, "device %d out of range (%d visible)", device, ndev);
-  // (more than 64 bodies or dofs: beyond the wavefront kernels — the workgroup-per-problem kernel takes every call, wide_kernel.h)
-  const bool big = h->nbody > kWave || h->nv > kWave;
-  if (h->nbody > 4096 || h->nv > 1024) return fail(MKH_E_LIMIT, "nbody=%d / nv=%d: at most 4096 bodies and 1024 dofs", h->nbody, h->nv);
-  if (h->nv < 1 || h->nbody < 2) return fail(MKH_E_INVALID, "model has no degrees of freedom");
   HIP_OK(hipSetDevice(device));
   MkhModel* m = new MkhModel();
   m->device = device;
-  m->big = big;
-  m->nq = h->nq; m->nv = h->nv; m->nbody = h->nbody; m->njnt = h->njnt; m->ngeom = h->ngeom; m->nsite = h->nsite;
-  m->body_ipos.assign(h->body_ipos, h->body_ipos + 3 * h->nbody);
-  m->body_mass.assign(h->body_mass, h->body_mass + h->nbody);
-  m->body_subtreemass.assign(h->body_subtreemass, h->body_subtreemass + h->nbody);
-  auto cpi = [](const int32_t* p, int n) { return std::vector<int32_t>(p, p + n); };
-  auto cpd = [](const double* p, int n) { return std::vector<double>(p, p + n); };
-  m->body_parentid = cpi(h->body_parentid, h->nbody); m->body_rootid = cpi(h->body_rootid, h->nbody);
-  m->body_jntnum = cpi(h->body_jntnum, h->nbody); m->body_jntadr = cpi(h->body_jntadr, h->nbody);
-  m->body_dofnum = cpi(h->body_dofnum, h->nbody); m->body_dofadr = cpi(h->body_dofadr, h->nbody);
-  m->jnt_type = cpi(h->jnt_type, h->njnt); m->jnt_qposadr = cpi(h->jnt_qposadr, h->njnt);
-  m->jnt_dofadr = cpi(h->jnt_dofadr, h->njnt); m->jnt_bodyid = cpi(h->jnt_bodyid, h->njnt);
-  m->jnt_limited = cpi(h->jnt_limited, h->njnt); m->jnt_range = cpd(h->jnt_range, h->njnt * 2);
-  m->jnt_pos = cpd(h->jnt_pos, h->njnt * 3); m->jnt_axis = cpd(h->jnt_axis, h->njnt * 3);
-  for (int j = 0; j < h->njnt; ++j) m->jnt_qpos0.push_back(h->qpos0[h->jnt_qposadr[j]]);
-  m->dof_bodyid = cpi(h->dof_bodyid, h->nv); m->dof_jntid = cpi(h->dof_jntid, h->nv);
-  m->dof_parentid = cpi(h->dof_parentid, h->nv);
-  m->site_bodyid = cpi(h->site_bodyid, h->nsite); m->geom_bodyid = cpi(h->geom_bodyid, h->ngeom);
-  m->geom_type = cpi(h->geom_type, h->ngeom);
-  m->body_pos = cpd(h->body_pos, h->nbody * 3); m->body_quat = cpd(h->body_quat, h->nbody * 4);
-  m->site_pos = cpd(h->site_pos, h->nsite * 3); m->site_quat = cpd(h->site_quat, h->nsite * 4);
-  m->geom_size = cpd(h->geom_size, h->ngeom * 3); m->geom_pos = cpd(h->geom_pos, h->ngeom * 3);
-  m->geom_quat = cpd(h->geom_quat, h->ngeom * 4);
-  m->geom_dataid.assign(h->ngeom, -1);
-  if (h->nmesh > 0) {
-    if (!h->geom_dataid || !h->mesh_vertadr || !h->mesh_vertnum || !h->mesh_vert || h->nmeshvert < 1) {
-      delete m; return fail(MKH_E_INVALID, "nmesh = %d but a mesh array is null", h->nmesh);
-    }
-    m->geom_dataid = cpi(h->geom_dataid, h->ngeom);
-    m->mesh_vertadr = cpi(h->mesh_vertadr, h->nmesh); m->mesh_vertnum = cpi(h->mesh_vertnum, h->nmesh);
-    for (int k = 0; k < h->nmesh; ++k)
-      if (m->mesh_vertadr[k] < 0 || m->mesh_vertnum[k] < 1 || m->mesh_vertadr[k] + m->mesh_vertnum[k] > h->nmeshvert) {
-        delete m; return fail(MKH_E_INVALID, "mesh %d: vertex range out of bounds", k);
-      }
-    for (int g = 0; g < h->ngeom; ++g)
-      if (m->geom_dataid[g] >= h->nmesh) { delete m; return fail(MKH_E_INVALID, "geom %d: mesh id out of range", g); }
-  }
-
-  const double inf = std::numeric_limits<double>::infinity();
-  // ---- body tables
-  std::vector<int> depth(h->nbody, 0);
-  int maxdepth = 0;
-  for (int b = 1; b < h->nbody; ++b) {
-    if (h->body_parentid[b] >= b) { delete m; return fail(MKH_E_INVALID, "body %d has parent id >= its own id", b); }
-    depth[b] = depth[h->body_parentid[b]] + 1;
-    if (depth[b] > maxdepth) maxdepth = depth[b];
-  }
-  int nrounds = 0;
-  while ((1 << nrounds) < maxdepth) ++nrounds;
-  if (!big && nrounds > kMaxRounds) { delete m; return fail(MKH_E_LIMIT, "kinematic tree too deep"); }
-  m->nrounds = nrounds;
-  std::vector<double> body_f(BF_COUNT * 64, 0.0);
-  std::vector<int32_t> body_i(BI_COUNT * 64, 0);
-  if (!big) {                                      // (the lane tables of the wavefront kernels: ≤ 64 bodies / dofs)
-  std::vector<int> subtree_last(h->nbody);
-  for (int b = h->nbody - 1; b >= 0; --b) {
-    subtree_last[b] = b;
-    for (int c = b + 1; c < h->nbody; ++c)
-      if (h->body_parentid[c] == b && subtree_last[c] > subtree_last[b]) subtree_last[b] = subtree_last[c];
-  }
-  for (int b = 0; b < h->nbody; ++b) {
-    for (int k = 0; k < 3; ++k) body_f[(BF_POS + k) * 64 + b] = h->body_pos[3 * b + k];
-    for (int k = 0; k < 4; ++k) body_f[(BF_QUAT + k) * 64 + b] = h->body_quat[4 * b + k];
-    for (int k = 0; k < 3; ++k) body_f[(BF_IPOS + k) * 64 + b] = h->body_ipos[3 * b + k];
-    body_f[BF_MASS * 64 + b] = h->body_mass[b];
-    body_f[BF_SUBTREEMASS * 64 + b] = h->body_subtreemass[b];
-    body_i[BI_PARENT * 64 + b] = h->body_parentid[b];
-    body_i[BI_JNTADR * 64 + b] = h->body_jntadr[b] < 0 ? 0 : h->body_jntadr[b];
-    body_i[BI_JNTNUM * 64 + b] = h->body_jntnum[b];
-    body_i[BI_SUBTREE_LAST * 64 + b] = subtree_last[b];
-    body_i[BI_IN_ROBOT * 64 + b] = (b >= 1 && h->body_rootid[b] == 1) ? 1 : 0;  // subtree of body 1 (ComTask)
-    // pointer-jumping ancestors: anc_0 = parent, anc_{r+1} = anc_r(anc_r)
-    int a = h->body_parentid[b];
-    for (int r = 0; r < kMaxRounds; ++r) {
-      body_i[(BI_ANC0 + r) * 64 + b] = a;
-      // advance 2^r more steps
-      int steps = 1 << r, x = a;
-      for (int k = 0; k < steps && x > 0; ++k) x = h->body_parentid[x];
-      a = x;
-    }
-  }
-  for (int b = 0; b < h->nbody; ++b) {
-    int lo = 0;
-    for (int r = 0; r < 5 && r < kMaxRounds; ++r) lo |= (body_i[(BI_ANC0 + r) * 64 + b] & 63) << (6 * r);
-    body_i[BI_ANCPACK0 * 64 + b] = lo;
-    body_i[BI_ANCPACK1 * 64 + b] = kMaxRounds > 5 ? (body_i[(BI_ANC0 + 5) * 64 + b] & 63) : 0;
-  }
-  // the anc recurrence above must satisfy anc_{r+1}(b) = anc_r(anc_r(b)); verify
-  for (int b = 0; b < h->nbody; ++b)
-    for (int r = 0; r + 1 < kMaxRounds; ++r) {
-      int a = body_i[(BI_ANC0 + r) * 64 + b];
-      int aa = body_i[(BI_ANC0 + r) * 64 + a];
-      if (body_i[(BI_ANC0 + r + 1) * 64 + b] != aa) { delete m; return fail(MKH_E_INVALID, "internal: ancestor table"); }
-    }
-  }
-  // ---- joint arrays
-  std::vector<double> jnt_f(h->njnt * JF_COUNT, 0.0);
-  std::vector<int32_t> jnt_i(h->njnt * JI_COUNT, 0);
-  for (int j = 0; j < h->njnt; ++j) {
-    for (int k = 0; k < 3; ++k) jnt_f[j * JF_COUNT + JF_AXIS + k] = h->jnt_axis[3 * j + k];
-    for (int k = 0; k < 3; ++k) jnt_f[j * JF_COUNT + JF_POS + k] = h->jnt_pos[3 * j + k];
-    jnt_f[j * JF_COUNT + JF_QPOS0] = h->qpos0[h->jnt_qposadr[j]];
-    jnt_i[j * JI_COUNT + JI_TYPE] = h->jnt_type[j];
-    jnt_i[j * JI_COUNT + JI_QADR] = h->jnt_qposadr[j];
-    jnt_i[j * JI_COUNT + JI_DADR] = h->jnt_dofadr[j];
-    if (h->jnt_type[j] == JNT_FREE && (h->body_jntnum[h->jnt_bodyid[j]] != 1)) {
-      delete m; return fail(MKH_E_INVALID, "free joint must be the only joint of its body");
-    }
-  }
-  // ---- dof tables
-  std::vector<int32_t> dof_i(DI_COUNT * 64, 0);
-  std::vector<double> dof_f(DF_COUNT * 64, 0.0);
-  for (int d = 0; d < 64; ++d) { dof_f[DF_RANGE_LO * 64 + d] = -inf; dof_f[DF_RANGE_HI * 64 + d] = inf; dof_i[DI_QADR * 64 + d] = -1; }
-  for (int d = 0; d < (big ? 0 : h->nv); ++d) {
-    const int j = h->dof_jntid[d];
-    const int jt = h->jnt_type[j];
-    const int k = d - h->jnt_dofadr[j];
-    int kind, kk = 0, qadr = -1;
-    if (jt == JNT_HINGE) { kind = DOF_HINGE; qadr = h->jnt_qposadr[j]; }
-    else if (jt == JNT_SLIDE) { kind = DOF_SLIDE; qadr = h->jnt_qposadr[j]; }
-    else if (jt == JNT_BALL) { kind = DOF_BALL; kk = k; qadr = h->jnt_qposadr[j]; }
-    else { if (k < 3) { kind = DOF_FREE_LIN; kk = k; } else { kind = DOF_FREE_ANG; kk = k - 3; } }
-    dof_i[DI_JNT * 64 + d] = j;
-    dof_i[DI_KIND * 64 + d] = kind;
-    dof_i[DI_K * 64 + d] = kk;
-    dof_i[DI_BODY * 64 + d] = h->dof_bodyid[d];
-    dof_i[DI_QADR * 64 + d] = qadr;
-    dof_i[DI_JIDX * 64 + d] = j - h->body_jntadr[h->jnt_bodyid[j]];
-    // (a limited ball joint: the reference's check_limits compares the quaternion's w with the range — first dof lane)
-    if (((jt == JNT_HINGE || jt == JNT_SLIDE) || (jt == JNT_BALL && k == 0)) && h->jnt_limited[j]) {
-      dof_f[DF_RANGE_LO * 64 + d] = h->jnt_range[2 * j];
-      dof_f[DF_RANGE_HI * 64 + d] = h->jnt_range[2 * j + 1];
-    }
-  }
-  hipError_t e = hipSuccess;
-  if (e == hipSuccess) e = upload(body_f, &m->d_body_f);
-  if (e == hipSuccess) e = upload(body_i, &m->d_body_i);
-  if (e == hipSuccess) e = upload(jnt_f, &m->d_jnt_f);
-  if (e == hipSuccess) e = upload(jnt_i, &m->d_jnt_i);
-  if (e == hipSuccess) e = upload(dof_i, &m->d_dof_i);
-  if (e == hipSuccess) e = upload(dof_f, &m->d_dof_f);
+  if (const int32_t rc = plan_model(h, *m, g_err)) { delete m; return rc; }
+  hipError_t e = upload(m->body_f, &m->d_body_f);
+  if (e == hipSuccess) e = upload(m->body_i, &m->d_body_i);
+  if (e == hipSuccess) e = upload(m->jnt_f, &m->d_jnt_f);
+  if (e == hipSuccess) e = upload(m->jnt_i, &m->d_jnt_i);
+  if (e == hipSuccess) e = upload(m->dof_i, &m->d_dof_i);
+  if (e == hipSuccess) e = upload(m->dof_f, &m->d_dof_f);
   hipDeviceProp_t prop;
   if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
-  if (h->nmesh > 0) m->h_mesh_vert.assign(h->mesh_vert, h->mesh_vert + (size_t)h->nmeshvert * 3);
-  if (e == hipSuccess && h->nmesh > 0) e = upload(m->h_mesh_vert, &m->d_mesh_vert);
+  if (e == hipSuccess && !m->h_mesh_vert.empty()) e = upload(m->h_mesh_vert, &m->d_mesh_vert);
   if (e != hipSuccess) { mkh_model_destroy(m); return fail(MKH_E_HIP, "model upload: %s", hipGetErrorString(e)); }
   m->num_cus = prop.multiProcessorCount;
   *out = m;
@@ -930,599 +320,128 @@ void mkh_model_destroy(MkhModel* m) {
   delete m;
 }
 
-static void fill_base(const MkhModel* m, DeviceProblem& P) {
-  P.nq = m->nq; P.nv = m->nv; P.nbody = m->nbody; P.njnt = m->njnt; P.nrounds = m->nrounds;
-  P.robot_root = 1;
-  P.body_f = m->d_body_f; P.body_i = m->d_body_i; P.jnt_f = m->d_jnt_f; P.jnt_i = m->d_jnt_i;
-  P.dof_i = m->d_dof_i; P.dof_f = m->d_dof_f;
-  // (joint anchors at the body origins — the G1, most menagerie robots: the kinematics skip rotating the zero offset)
-  P.jnt_pos_zero = 1;
-  for (double x : m->jnt_pos) if (x != 0.0) P.jnt_pos_zero = 0;
-}
-
 int32_t mkh_problem_create(MkhModel* m, const MkhProblemDesc* d, int32_t max_batch, MkhProblem** out) {
   return mkh_problem_create_diag(m, d, max_batch, 0, out);
+}
+
+// The experiment switches of problem creation (problem_plan.h PlanSwitches; tools/README.md): read at every create, in experiment
+// builds only — dbg_env is a constant nullptr in the product library.
+static PlanSwitches plan_switches() {
+  PlanSwitches s;
+  if (const char* cap = dbg_env("MKH_DEBUG_MAX_ROWS")) s.max_rows = atoi(cap);
+  s.wood_always = dbg_env("MKH_DEBUG_WOOD_ALWAYS") != nullptr;
+  s.no_com_w3 = dbg_env("MKH_DEBUG_NO_COM_W3") != nullptr;
+  s.no_tight_rows = dbg_env("MKH_DEBUG_NO_TIGHT_ROWS") != nullptr;
+  s.no_tight_generic = dbg_env("MKH_DEBUG_NO_TIGHT_GENERIC") != nullptr;
+  s.no_pair_rows = dbg_env("MKH_DEBUG_NO_PAIR_ROWS") != nullptr;
+  s.no_convex_split = dbg_env("MKH_DEBUG_NO_CONVEX_SPLIT") != nullptr;
+  return s;
+}
+
+// A planned problem on the device: the only place that allocates and fills descriptor memory.  Every array a descriptor points to
+// goes into p->owned; the descriptors are copied once, after their pointer fields are patched.  One error path: the caller
+// destroys the handle, which frees whatever was allocated.
+static int32_t upload_problem(MkhProblem* p, const ProblemPlan& plan) {
+  const MkhModel* m = p->model;
+  hipError_t e = hipSuccess;
+  auto up = [&](const auto& v) {                       // a host vector, owned by the handle
+    typename std::decay_t<decltype(v)>::value_type* dp = nullptr;
+    if (e == hipSuccess) e = upload(v, &dp);
+    if (dp) p->owned.push_back(dp);
+    return dp;
+  };
+  auto alloc = [&](auto** out, size_t bytes) { if (e == hipSuccess) e = hipMalloc((void**)out, bytes); };
+  auto put = [&](auto** out, const void* src, size_t bytes) {
+    alloc(out, bytes);
+    if (e == hipSuccess) e = hipMemcpy(*out, src, bytes, hipMemcpyHostToDevice);
+  };
+  // mesh geoms: the hull's vertices in the model's device array
+  std::vector<CollisionPairDev> pairs = plan.pairs;
+  for (size_t k = 0; k < pairs.size(); ++k) {
+    if (plan.pair_vert[2 * k] >= 0) pairs[k].vert1 = m->d_mesh_vert + plan.pair_vert[2 * k];
+    if (plan.pair_vert[2 * k + 1] >= 0) pairs[k].vert2 = m->d_mesh_vert + plan.pair_vert[2 * k + 1];
+  }
+  DeviceProblem& P = p->dev;
+  P = plan.dev;
+  if (!plan.sel.wide_only) {
+    P.body_f = m->d_body_f; P.body_i = m->d_body_i; P.jnt_f = m->d_jnt_f; P.jnt_i = m->d_jnt_i;
+    P.dof_i = m->d_dof_i; P.dof_f = m->d_dof_f;
+    P.frame = up(plan.ft); P.posture_cost = up(plan.pcost); P.cfg_lower = up(plan.clo); P.cfg_upper = up(plan.chi);
+    P.vel_limit = up(plan.vlim); P.pairs = up(pairs); P.cull = plan.sel.use_cull ? up(plan.culls) : nullptr;
+    P.dense_cost = up(plan.dcost); P.dense_wgain = up(plan.dwgain);
+    if (plan.lane_class) {
+      // (the lane kernel and the one-row builds of the row kernel read the small descriptor, the two-row build the large one)
+      LaneProblem lp1;
+      if (plan.lane_class != 32) lane_problem_narrow(plan.lane, lp1);
+      if (plan.lane_class == 32) put(&p->d_lane, &plan.lane, sizeof(LaneProblem2));
+      else put(&p->d_lane, &lp1, sizeof(LaneProblem));
+    }
+    if (plan.tight) {
+      DeviceProblem T = plan.dev_tight;                // (planned before the convex split: no pre-evaluated contacts)
+      T.body_f = P.body_f; T.body_i = P.body_i; T.jnt_f = P.jnt_f; T.jnt_i = P.jnt_i; T.dof_i = P.dof_i; T.dof_f = P.dof_f;
+      T.frame = P.frame; T.posture_cost = P.posture_cost; T.cfg_lower = P.cfg_lower; T.cfg_upper = P.cfg_upper;
+      T.vel_limit = P.vel_limit; T.pairs = P.pairs; T.cull = P.cull; T.dense_cost = P.dense_cost; T.dense_wgain = P.dense_wgain;
+      put(&p->d_dev_tight, &T, sizeof(DeviceProblem));
+      alloc(&p->d_status_tight, (size_t)p->max_batch * sizeof(int32_t));
+    }
+  }
+  if (plan.wide.built) {
+    const WidePlan& wp = plan.wide;
+    WideProblem& W = p->wide;
+    W = wp.W;
+    W.level_start = up(m->level_start); W.level_body = up(m->level_body); W.body_parent = up(m->body_parentid);
+    W.body_jntadr = up(m->jntadr0); W.body_jntnum = up(m->body_jntnum); W.body_last = up(m->subtree_last);
+    W.body_inrobot = up(m->in_robot); W.body_pos = up(m->body_pos); W.body_quat = up(m->body_quat); W.body_ipos = up(m->body_ipos);
+    W.body_mass = up(m->body_mass); W.body_stmass = up(m->body_subtreemass); W.jnt_type = up(m->jnt_type);
+    W.jnt_qadr = up(m->jnt_qposadr); W.jnt_dadr = up(m->jnt_dofadr); W.jnt_axis = up(m->jnt_axis); W.jnt_pos = up(m->jnt_pos);
+    W.jnt_qpos0 = up(m->jnt_qpos0); W.dof_jnt = up(m->dof_jntid); W.dof_kind = up(m->dof_kind); W.dof_k = up(m->dof_k);
+    W.dof_body = up(m->dof_bodyid); W.dof_qadr = up(m->dof_qadr); W.dof_lo = up(m->dof_lo); W.dof_hi = up(m->dof_hi);
+    W.chain = up(m->chain);
+    W.frame = up(plan.ft); W.posture_cost = up(wp.pcost); W.dense_cost = up(plan.dcost); W.dense_wgain = up(plan.dwgain);
+    W.cfg_lower = up(wp.clo); W.cfg_upper = up(wp.chi); W.vel_limit = up(wp.vlim); W.pairs = up(pairs);
+    W.cull = wp.use_cull ? up(plan.culls) : nullptr;
+    alloc(&W.ws, (size_t)wp.ws_doubles * 8);
+    if (W.ws) p->owned.push_back(W.ws);
+    // the redo queue: every entry empty (−1), head and tail behind it
+    alloc(&W.redo_queue, ((size_t)wp.redo_cap + 4) * sizeof(int32_t));
+    if (W.redo_queue) p->owned.push_back(W.redo_queue);
+    if (e == hipSuccess) e = hipMemset(W.redo_queue, 0xff, (size_t)wp.redo_cap * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemset(W.redo_queue + wp.redo_cap, 0, 4 * sizeof(int32_t));
+    W.redo_ctr = reinterpret_cast<uint32_t*>(W.redo_queue + wp.redo_cap);
+    put(&p->d_wide, &W, sizeof(WideProblem));
+    if (!p->d_status_tight) alloc(&p->d_status_tight, (size_t)p->max_batch * sizeof(int32_t));
+  }
+  if (plan.n_cv > 0) {
+    // general convex pairs of plain solves: the chains convex_contacts_kernel walks and the contacts it leaves for the solve
+    p->cv = mkh::CvPre{plan.n_cv, up(plan.cv_pair), up(plan.cv_adr), up(plan.cv_chain)};
+    alloc(&p->d_cv, (size_t)p->max_batch * plan.n_cv * 7 * sizeof(double));
+    P.cv_contacts = p->d_cv;
+  }
+  if (!plan.sel.wide_only) put(&p->d_dev, &P, sizeof(DeviceProblem));
+  alloc(&p->d_taps, sizeof(TapArgs));
+  alloc(&p->d_work, 128);
+  if (e == hipSuccess) e = hipMemset(p->d_work, 0, 128);
+  if (e == hipSuccess) e = hipDeviceSynchronize();   // (hipMemset may return before the fill has run; launches may come on any stream)
+  if (e != hipSuccess) return fail(MKH_E_HIP, "problem upload: %s", hipGetErrorString(e));
+  return MKH_OK;
 }
 
 int32_t mkh_problem_create_diag(MkhModel* m, const MkhProblemDesc* d, int32_t max_batch, int32_t diag, MkhProblem** out) {
   if (!m || !d || !out) return fail(MKH_E_INVALID, "null argument");
   *out = nullptr;
-  if (diag & ~(MKH_DIAG_NO_WIDE_REDO | MKH_DIAG_NO_TIGHT_REDO | MKH_DIAG_NO_COLD_REFINE | MKH_DIAG_NO_PAIR_CULL))
-    return fail(MKH_E_INVALID, "unknown MKH_DIAG_* bits 0x%x", diag);
-  if (max_batch < 1) return fail(MKH_E_INVALID, "max_batch must be >= 1");
-  if (d->n_frame_tasks > kMaxFrameTasks) return fail(MKH_E_LIMIT, "at most %d frame tasks", kMaxFrameTasks);
-  if (d->n_posture_tasks > kMaxPostureTasks) return fail(MKH_E_LIMIT, "at most %d posture tasks", kMaxPostureTasks);
-  if (d->n_com_tasks > kMaxComTasks) return fail(MKH_E_LIMIT, "at most %d CoM tasks", kMaxComTasks);
-  if (d->n_dense_tasks < 0 || d->n_dense_tasks > kMaxDenseTasks) return fail(MKH_E_LIMIT, "at most %d dense (plugin) tasks", kMaxDenseTasks);
-  if (d->n_dense_limit_rows < 0) return fail(MKH_E_INVALID, "n_dense_limit_rows must be >= 0");
-  if (d->n_configuration_limits > kMaxBoxTerms || d->n_velocity_limits > kMaxBoxTerms)
-    return fail(MKH_E_LIMIT, "at most %d configuration and %d velocity limits", kMaxBoxTerms, kMaxBoxTerms);
+  ProblemPlan plan;
+  if (const int32_t rc = plan_problem(*m, *d, diag, max_batch, m->num_cus, plan_switches(), plan, g_err)) return rc;
   HIP_OK(hipSetDevice(m->device));
-  const double inf = std::numeric_limits<double>::infinity();
   MkhProblem* p = new MkhProblem();
+  static_cast<ProblemSelect&>(*p) = plan.sel;
   p->model = m;
   p->device = m->device;
   p->max_batch = max_batch;
   p->diag = diag;
-  DeviceProblem& P = p->dev;
-  fill_base(m, P);
-  P.n_frame = d->n_frame_tasks; P.n_posture = d->n_posture_tasks; P.n_com = d->n_com_tasks;
-  P.n_cfg = d->n_configuration_limits; P.n_vel = d->n_velocity_limits;
-  auto bail = [&](int32_t code) { mkh_problem_destroy(p); return code; };
-
-  // ---- frame tasks: resolve the frame to (body, local pose); rows of the tap layout
-  int row = 0, jrows = 0;
-  std::vector<FrameTaskDev> ft(d->n_frame_tasks);
-  for (int t = 0; t < d->n_frame_tasks; ++t) {
-    const MkhFrameTaskDesc& s = d->frame_tasks[t];
-    FrameTaskDev& f = ft[t];
-    memset(&f, 0, sizeof f);
-    static const double zero3[3] = {0, 0, 0}, ident4[4] = {1, 0, 0, 0};
-    auto resolve = [&](int ftype, int fid, int32_t& body, const double*& lp, const double*& lq) -> int32_t {
-      if (ftype == MKH_FRAME_BODY) {
-        if (fid < 0 || fid >= m->nbody) return fail(MKH_E_INVALID, "frame task %d: body id %d out of range", t, fid);
-        body = fid; lp = zero3; lq = ident4;
-      } else if (ftype == MKH_FRAME_SITE) {
-        if (fid < 0 || fid >= m->nsite) return fail(MKH_E_INVALID, "frame task %d: site id %d out of range", t, fid);
-        body = m->site_bodyid[fid]; lp = &m->site_pos[3 * fid]; lq = &m->site_quat[4 * fid];
-      } else if (ftype == MKH_FRAME_GEOM) {
-        if (fid < 0 || fid >= m->ngeom) return fail(MKH_E_INVALID, "frame task %d: geom id %d out of range", t, fid);
-        body = m->geom_bodyid[fid]; lp = &m->geom_pos[3 * fid]; lq = &m->geom_quat[4 * fid];
-      } else {
-        return fail(MKH_E_INVALID, "frame task %d: unsupported frame type %d", t, ftype);
-      }
-      return MKH_OK;
-    };
-    const double *lp = nullptr, *lq = nullptr;
-    if (resolve(s.frame_type, s.frame_id, f.body, lp, lq) != MKH_OK) return bail(MKH_E_INVALID);
-    for (int k = 0; k < 3; ++k) f.lpos[k] = lp[k];
-    for (int k = 0; k < 4; ++k) f.lquat[k] = lq[k];
-    if (s.root_type >= 0) {
-      f.relative = 1;
-      p->has_relative = true;
-      if (resolve(s.root_type, s.root_id, f.root_body, lp, lq) != MKH_OK) return bail(MKH_E_INVALID);
-      for (int k = 0; k < 3; ++k) f.root_lpos[k] = lp[k];
-      for (int k = 0; k < 4; ++k) f.root_lquat[k] = lq[k];
-      f.root_mask = m->big ? 0ull : dof_chain_mask(m, f.root_body);
-    }
-    for (int k = 0; k < 6; ++k) {
-      if (!(s.cost[k] >= 0.0)) return bail(fail(MKH_E_INVALID, "frame task %d: cost must be >= 0", t));
-      f.cost[k] = s.cost[k];
-    }
-    f.gain = s.gain; f.lm_damping = s.lm_damping;
-    f.dof_mask = m->big ? 0ull : dof_chain_mask(m, f.body);
-    f.row0 = row; row += 6;
-    f.any_ori = (s.cost[3] != 0.0 || s.cost[4] != 0.0 || s.cost[5] != 0.0) ? 1 : 0;
-    f.rowmask = 0;
-    for (int k = 0; k < 6; ++k) if (s.cost[k] != 0.0) f.rowmask |= 1 << k;
-    f.jrow0 = jrows;
-    jrows += __builtin_popcount(f.rowmask);
-  }
-  p->frame_w.assign(2 * (size_t)d->n_frame_tasks, 0.0);
-  for (int t = 0; t < d->n_frame_tasks; ++t) {
-    if (ft[t].relative) continue;
-    p->frame_w[t] = (ft[t].rowmask & 7) ? 1.0 : 0.0;
-    p->frame_w[d->n_frame_tasks + t] = ft[t].any_ori ? 1.0 : 0.0;
-  }
-  std::vector<double> pcost((size_t)(d->n_posture_tasks ? d->n_posture_tasks : 1) * 64, 0.0);
-  for (int t = 0; t < d->n_posture_tasks; ++t) {
-    for (int i = 0; i < (m->big ? 0 : m->nv); ++i) pcost[t * 64 + i] = d->posture_tasks[t].cost[i];
-    P.posture_gain[t] = d->posture_tasks[t].gain; P.posture_lm[t] = d->posture_tasks[t].lm_damping;
-    P.posture_row0[t] = row; row += m->nv;
-  }
-  for (int t = 0; t < d->n_com_tasks; ++t) {
-    for (int k = 0; k < 3; ++k) P.com_cost[t][k] = d->com_tasks[t].cost[k];
-    P.com_gain[t] = d->com_tasks[t].gain; P.com_lm[t] = d->com_tasks[t].lm_damping;
-    P.com_row0[t] = row; row += 3;
-    P.com_rowmask[t] = 0;
-    for (int k = 0; k < 3; ++k) if (d->com_tasks[t].cost[k] != 0.0) P.com_rowmask[t] |= 1 << k;
-    P.com_jrow0[t] = jrows;
-    jrows += __builtin_popcount(P.com_rowmask[t]);
-  }
-  // ---- plugin route: caller-defined tasks as dense rows (tap rows follow the built-in ones)
-  std::vector<double> dcost, dwgain;
-  P.n_dense_tasks = d->n_dense_tasks;
-  P.dense_tap_row0 = row;
-  for (int t = 0; t < d->n_dense_tasks; ++t) {
-    const MkhDenseTaskDesc& s = d->dense_tasks[t];
-    if (s.k < 1 || !s.cost) return bail(fail(MKH_E_INVALID, "dense task %d: k must be >= 1 and cost non-null", t));
-    if (!(s.gain >= 0.0 && s.gain <= 1.0) || !(s.lm_damping >= 0.0))
-      return bail(fail(MKH_E_INVALID, "dense task %d: gain must be in [0, 1] and lm_damping >= 0", t));
-    P.dense_row0[t] = (int)dcost.size(); P.dense_k[t] = s.k; P.dense_lm[t] = s.lm_damping;
-    for (int r = 0; r < s.k; ++r) {
-      if (!(s.cost[r] >= 0.0)) return bail(fail(MKH_E_INVALID, "dense task %d: cost must be >= 0", t));
-      dcost.push_back(s.cost[r]);
-      dwgain.push_back(s.cost[r] * -s.gain);
-    }
-    row += s.k;
-  }
-  P.n_dense_rows = (int)dcost.size();
-  P.n_dense_limit_rows = d->n_dense_limit_rows;
-  P.dense_box = d->dense_limit_box ? 1 : 0;
-  P.n_rows_tap = row;
-  P.n_jrows = jrows;
-
-  // ---- box limits: per-dof lower/upper in joint coordinates (±inf = absent)
-  std::vector<double> clo((size_t)(P.n_cfg ? P.n_cfg : 1) * 64, -inf), chi((size_t)(P.n_cfg ? P.n_cfg : 1) * 64, inf);
-  for (int t = 0; t < P.n_cfg; ++t) {
-    const MkhConfigurationLimitDesc& c = d->configuration_limits[t];
-    if (!(c.gain > 0.0 && c.gain <= 1.0)) return bail(fail(MKH_E_INVALID, "configuration limit gain must be in (0, 1]"));
-    P.cfg_gain[t] = c.gain;
-    for (int k = 0; k < c.n_indices; ++k) {
-      const int dof = c.indices[k];
-      if (dof < 0 || dof >= m->nv) return bail(fail(MKH_E_INVALID, "configuration limit: dof %d out of range", dof));
-      const int jt = m->jnt_type[m->dof_jntid[dof]];
-      if (jt == JNT_FREE) return bail(fail(MKH_E_INVALID, "configuration limit on free-joint dof %d (the reference skips free joints)", dof));
-      const int qa = m->jnt_qposadr[m->dof_jntid[dof]];
-      if (m->big) continue;                                  // (beyond 64 dofs: build_wide_problem keeps its own arrays)
-      clo[t * 64 + dof] = c.lower[qa];
-      chi[t * 64 + dof] = c.upper[qa];
-    }
-  }
-  std::vector<double> vlim((size_t)(P.n_vel ? P.n_vel : 1) * 64, inf);
-  for (int t = 0; t < P.n_vel; ++t) {
-    const MkhVelocityLimitDesc& v = d->velocity_limits[t];
-    for (int k = 0; k < v.n_indices; ++k) {
-      const int dof = v.indices[k];
-      if (dof < 0 || dof >= m->nv) return bail(fail(MKH_E_INVALID, "velocity limit: dof %d out of range", dof));
-      if (!m->big) vlim[t * 64 + dof] = std::fmin(vlim[t * 64 + dof], v.limit[k]);
-    }
-  }
-  // ---- collision pairs
-  std::vector<CollisionPairDev> pairs;
-  std::vector<PairCull> culls;
-  int n_cv = 0;
-  for (int t = 0; t < d->n_collision_limits; ++t) {
-    const MkhCollisionLimitDesc& c = d->collision_limits[t];
-    for (int k = 0; k < c.n_pairs; ++k) {
-      const int g1 = c.geom_id_pairs[2 * k], g2 = c.geom_id_pairs[2 * k + 1];
-      if (g1 < 0 || g2 < 0 || g1 >= m->ngeom || g2 >= m->ngeom) return bail(fail(MKH_E_INVALID, "collision pair (%d,%d): geom id out of range", g1, g2));
-      CollisionPairDev cp;
-      memset(&cp, 0, sizeof cp);
-      int t1 = m->geom_type[g1], t2 = m->geom_type[g2];
-      // pairs with an analytic routine (collide_dev.h) ...
-      auto analytic = [](int a, int b) {
-        if (a > b) { int x = a; a = b; b = x; }
-        return (a == GEOM_CAPSULE && b == GEOM_CAPSULE) || (a == GEOM_SPHERE && b == GEOM_SPHERE) ||
-               (a == GEOM_SPHERE && b == GEOM_CAPSULE) || (a == GEOM_PLANE && (b == GEOM_SPHERE || b == GEOM_CAPSULE)) ||
-               (b == GEOM_BOX && (a == GEOM_PLANE || a == GEOM_SPHERE || a == GEOM_CAPSULE || a == GEOM_BOX)) ||
-               (b == GEOM_CYLINDER && (a == GEOM_PLANE || a == GEOM_SPHERE || a == GEOM_CAPSULE));
-      };
-      // ... and the ones that go through the general convex routine (convex_dev.h): cylinder–box, cylinder–cylinder,
-      // ellipsoid against any primitive
-      // ellipsoid against any primitive, and every pair with a mesh geom (its hull: plane–mesh analytically)
-      auto convex = [](int a, int b) {
-        if (a > b) { int x = a; a = b; b = x; }
-        const bool cb = b == GEOM_SPHERE || b == GEOM_CAPSULE || b == GEOM_ELLIPSOID || b == GEOM_CYLINDER || b == GEOM_BOX || b == GEOM_MESH;
-        return cb && (a == GEOM_PLANE ? (b == GEOM_ELLIPSOID || b == GEOM_MESH) : (a >= GEOM_SPHERE && a <= GEOM_MESH));
-      };
-      auto supported = [&](int a, int b) { return analytic(a, b) || convex(a, b); };
-      cp.cv_slot = -1;
-      if (!analytic(t1, t2) && convex(t1, t2)) { p->convex_pairs = true; cp.cv_slot = n_cv++; }
-      if (!supported(t1, t2)) return bail(fail(MKH_E_INVALID, "collision pair (%d,%d): geom types (%d,%d) are not supported (height fields)", g1, g2, t1, t2));
-      for (int side = 0; side < 2; ++side) {
-        const int g = side ? g2 : g1;
-        if (m->geom_type[g] != GEOM_MESH) continue;
-        const int k = m->geom_dataid[g];
-        if (k < 0 || !m->d_mesh_vert)
-          return bail(fail(MKH_E_INVALID, "collision pair (%d,%d): mesh geom %d has no hull in the model (geom_dataid / mesh_vert)", g1, g2, g));
-        (side ? cp.vert2 : cp.vert1) = m->d_mesh_vert + 3 * (size_t)m->mesh_vertadr[k];
-        (side ? cp.nvert2 : cp.nvert1) = m->mesh_vertnum[k];
-      }
-      cp.type1 = t1; cp.type2 = t2; cp.body1 = m->geom_bodyid[g1]; cp.body2 = m->geom_bodyid[g2];
-      for (int i = 0; i < 3; ++i) { cp.size1[i] = m->geom_size[3 * g1 + i]; cp.size2[i] = m->geom_size[3 * g2 + i];
-                                    cp.lpos1[i] = m->geom_pos[3 * g1 + i]; cp.lpos2[i] = m->geom_pos[3 * g2 + i]; }
-      for (int i = 0; i < 4; ++i) { cp.lquat1[i] = m->geom_quat[4 * g1 + i]; cp.lquat2[i] = m->geom_quat[4 * g2 + i]; }
-      if (!m->big) { cp.mask1 = dof_chain_mask(m, cp.body1); cp.mask2 = dof_chain_mask(m, cp.body2); }
-      cp.gain = c.gain; cp.dmin = c.minimum_distance_from_collisions; cp.ddetect = c.collision_detection_distance;
-      cp.relax = c.bound_relaxation;
-      pairs.push_back(cp);
-      // bounding spheres for the cull pass of problems with more than one wavefront of pairs (mkh_types.h PairCull)
-      auto rbound = [&](int g) -> double {
-        const double* sz = &m->geom_size[3 * g];
-        switch (m->geom_type[g]) {
-          case GEOM_SPHERE: return sz[0];
-          case GEOM_CAPSULE: return sz[0] + sz[1];
-          case GEOM_ELLIPSOID: return std::fmax(sz[0], std::fmax(sz[1], sz[2]));
-          case GEOM_CYLINDER: return std::hypot(sz[0], sz[1]);
-          case GEOM_BOX: return std::sqrt(sz[0] * sz[0] + sz[1] * sz[1] + sz[2] * sz[2]);
-          case GEOM_MESH: {
-            const int k = m->geom_dataid[g];
-            double r2 = 0.0;
-            if (k < 0 || m->h_mesh_vert.empty()) return inf;
-            for (int v = 0; v < m->mesh_vertnum[k]; ++v) {
-              const double* x = &m->h_mesh_vert[3 * ((size_t)m->mesh_vertadr[k] + v)];
-              r2 = std::fmax(r2, x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
-            }
-            return std::sqrt(r2);
-          }
-          default: return inf;                                 // planes (and anything unbounded): never culled
-        }
-      };
-      PairCull pc;
-      memset(&pc, 0, sizeof pc);
-      pc.body1 = cp.body1; pc.body2 = cp.body2;
-      for (int i = 0; i < 3; ++i) { pc.lpos1[i] = cp.lpos1[i]; pc.lpos2[i] = cp.lpos2[i]; }
-      const double reach = (rbound(g1) + rbound(g2) + std::fmax(cp.ddetect, 0.0)) * (1.0 + 1e-9) + 1e-12;
-      pc.reach2 = reach * reach;
-      culls.push_back(pc);
-    }
-  }
-  P.n_pairs = (int)pairs.size();
-  p->simple_pairs = !pairs.empty();
-  for (const auto& cp : pairs)
-    for (int ty : {cp.type1, cp.type2})
-      if (ty != GEOM_PLANE && ty != GEOM_SPHERE && ty != GEOM_CAPSULE) p->simple_pairs = false;
-  if (m->big) {
-    // beyond one wavefront: the workgroup-per-problem kernel takes every call of this problem (wide_kernel.h)
-    const int32_t rc = build_wide_problem(p, m, d, ft, pairs, culls, dcost, dwgain);
-    if (rc != MKH_OK) return bail(rc);
-    p->wide_only = true;
-    if (hipMalloc((void**)&p->d_taps, sizeof(TapArgs)) != hipSuccess || hipMalloc((void**)&p->d_work, 128) != hipSuccess ||
-        hipMemset(p->d_work, 0, 128) != hipSuccess)
-      return bail(fail(MKH_E_HIP, "descriptor upload failed"));
+  if (const int32_t rc = upload_problem(p, plan)) { mkh_problem_destroy(p); return rc; }
+  if (p->wide_only) {
     snprintf(p->last_kernel, sizeof(p->last_kernel), "ik_wide_kernel");
-    p->dev.n_rows_tap = p->wide.n_rows_tap;        // (what mkh_problem_num_task_rows reports; the wavefront descriptor is not built)
     p->last_grid = p->wide_grid; p->last_lds = p->wide_lds; p->last_nt = p->wide.nv + p->wide.max_rows; p->last_block = kWideThreads;
-    *out = p;
-    return MKH_OK;
-  }
-  {
-    const int want = P.n_pairs + P.n_dense_limit_rows;          // half-space rows that can be active at once
-    P.max_rows = want < (kWave - m->nv) ? want : (kWave - m->nv);
-    if (const char* cap = dbg_env("MKH_DEBUG_MAX_ROWS")) { const int c = atoi(cap); if (c > 0 && c < P.max_rows) P.max_rows = c; }   // (experiments)
-    // LDS behind the per-problem ranges: h of every pair when pairs outnumber rows (row selection), then the expanding polytope's
-    // workspace when some pair goes through the general convex routine (collision_phase: the same two terms)
-    P.n_hsel = (P.n_pairs > P.max_rows ? lds_even(P.n_pairs) : 0) + (p->convex_pairs ? (kEpaWsDoubles > kGjkWsDoubles ? kEpaWsDoubles : kGjkWsDoubles) : 0);
-    // the cull pass's candidate list (16-bit pair indices) when the pairs do not fit one trip of the wavefront
-    p->use_cull = P.n_pairs > kWave && P.n_pairs < 65536 && !p->simple_pairs && !(p->diag & MKH_DIAG_NO_PAIR_CULL);
-    if (p->use_cull) P.n_hsel += lds_even((P.n_pairs + 3) / 4);
-  }
-  const int ntab = m->nv + P.max_rows;
-  p->nt = size_class(ntab, 0);       // (ntab ≤ kWave by the cap on max_rows above: the largest build holds it)
-  if (!p->nt) return bail(fail(MKH_E_LIMIT, "no kernel variant with %d tableau rows", ntab));
-
-  hipError_t e = hipSuccess;
-  if (e == hipSuccess) e = upload(ft, &p->d_frame);
-  if (e == hipSuccess) e = upload(pcost, &p->d_posture_cost);
-  if (e == hipSuccess) e = upload(clo, &p->d_cfg_lower);
-  if (e == hipSuccess) e = upload(chi, &p->d_cfg_upper);
-  if (e == hipSuccess) e = upload(vlim, &p->d_vel);
-  if (e == hipSuccess) e = upload(pairs, &p->d_pairs);
-  if (e == hipSuccess && p->use_cull) e = upload(culls, &p->d_cull);
-  if (e == hipSuccess) e = upload(dcost, &p->d_dense_cost);
-  if (e == hipSuccess) e = upload(dwgain, &p->d_dense_wgain);
-  if (e != hipSuccess) return bail(fail(MKH_E_HIP, "problem upload: %s", hipGetErrorString(e)));
-  P.frame = p->d_frame; P.posture_cost = p->d_posture_cost; P.cfg_lower = p->d_cfg_lower; P.cfg_upper = p->d_cfg_upper;
-  P.vel_limit = p->d_vel; P.pairs = p->d_pairs; P.cull = p->use_cull ? p->d_cull : nullptr;
-  P.dense_cost = p->d_dense_cost; P.dense_wgain = p->d_dense_wgain;
-
-  P.nt = p->nt;
-  p->nt_full = p->nt < 32 ? 32 : p->nt;
-  // Second LDS buffers for the next problem's inputs (ik_kernel.h "load inputs") only where they do not cost a
-  // resident wave in the lean or the all-feature variant of this problem (the low-rank variant is checked below).
-  auto lds_of = [&](int nt, bool pre) { return lds_bytes_of(P, nt, 0, kDirectFeat, false, pre); };
-  P.prefetch = (waves_per_cu(p->nt, lds_of(p->nt, true)) == waves_per_cu(p->nt, lds_of(p->nt, false)) &&
-                waves_per_cu(p->nt_full, lds_of(p->nt_full, true)) == waves_per_cu(p->nt_full, lds_of(p->nt_full, false))) ? 1 : 0;
-  p->lds_bytes = lds_of(p->nt, P.prefetch != 0);
-  if (p->lds_bytes > 64 * 1024) return bail(fail(MKH_E_LIMIT, "problem needs %d bytes of LDS per wavefront (> 64 KiB)", p->lds_bytes));
-  p->blocks_per_cu = waves_per_cu(p->nt, p->lds_bytes);
-  p->lds_bytes_full = lds_of(p->nt_full, P.prefetch != 0);
-  if (p->blocks_per_cu < 1) p->blocks_per_cu = 1;
-  // 3 waves per SIMD: tableau sizes with a lean build on the TabW3 map, no half-space rows (the compact layout lets the
-  // Jacobian rows reuse the body poses, which the collision phase still reads), and 12 wavefronts' LDS must fit the CU
-  P.prefetch_w3 = 0;
-  if (find_variant(p->nt, 0, 0, true) && P.max_rows == 0 && P.n_dense_rows == 0) {
-    auto lds_w3 = [&](bool pre) { return lds_bytes_of(P, p->nt, 0, 0, true, pre); };
-    if (waves_per_cu(p->nt, lds_w3(false), true) == 12) {
-      P.prefetch_w3 = waves_per_cu(p->nt, lds_w3(true), true) == 12 ? 1 : 0;
-      p->lds_bytes_w3 = lds_w3(P.prefetch_w3 != 0);
-    }
-  }
-  // ---- direct start: Jacobian columns by (task, dof) pair lanes when they fit one wavefront
-  P.n_dpairs = 0;
-  {
-    int n = 0;
-    bool fits = true;
-    for (size_t t = 0; t < ft.size() && fits; ++t) {
-      const uint64_t cm = ft[t].dof_mask | (ft[t].relative ? ft[t].root_mask : 0ull);
-      for (int k = 0; k < m->nv && fits; ++k)
-        if ((cm >> k) & 1) {
-          if (n >= kWave) { fits = false; break; }
-          P.dpair_task[n] = (int16_t)t; P.dpair_dof[n] = (int16_t)k; ++n;
-        }
-    }
-    if (fits) P.n_dpairs = n;
-  }
-  // The low-rank start's lane tables (ik_kernel.h wood_start): which column / row chunk of Jh·Jhᵀ a lane computes and over which
-  // dofs, the (task, dof) pair lanes of the Jacobian rows, the source of each residual's weighted error.  They depend on the
-  // tasks only — shared by the builds without rows and, round 6, the ones with half-space rows.  false: more than 256 pairs.
-  auto wood_tables = [&]() -> bool {
-    // (column, row-chunk) lanes of the Jh·Jhᵀ product: rows 0..n_jrows (the last one is the rhs)
-    const int groups = kWave / P.n_jrows;
-    P.wood_rpc = (P.n_jrows + 1 + groups - 1) / groups;
-    for (int l = 0; l < kWave; ++l) {
-      const int ch = l / P.n_jrows;
-      P.wood_col[l] = ch < groups ? l % P.n_jrows : -1;
-      P.wood_row0[l] = ch < groups ? ch * P.wood_rpc : 0;
-      P.wood_mask[l] = 0;
-      if (ch < groups)
-        for (size_t t = 0; t < ft.size(); ++t)
-          if (l % P.n_jrows >= ft[t].jrow0 && l % P.n_jrows < ft[t].jrow0 + __builtin_popcount(ft[t].rowmask & 63))
-            P.wood_mask[l] = ft[t].dof_mask;
-    }
-    // Jacobian columns by (task, dof) pair lanes; source of each residual's weighted error
-    P.n_jpairs = 0;
-    for (size_t t = 0; t < ft.size(); ++t) {
-      for (int k = 0; k < m->nv; ++k)
-        if ((ft[t].dof_mask >> k) & 1) {
-          if (P.n_jpairs >= 256) return false;
-          P.jpair_task[P.n_jpairs] = (int16_t)t; P.jpair_dof[P.n_jpairs] = (int16_t)k; ++P.n_jpairs;
-        }
-      int c = 0;
-      for (int r = 0; r < 6; ++r)
-        if ((ft[t].rowmask >> r) & 1) { P.mu_src[ft[t].jrow0 + c] = (int16_t)(t * 64 + 30 + r); ++c; }
-    }
-    // ComTask rows: dense over the robot's dofs; their weighted error is computed on the device (mu_src < 0)
-    for (int t = 0; t < P.n_com; ++t) {
-      int c = 0;
-      for (int r = 0; r < 3; ++r)
-        if ((P.com_rowmask[t] >> r) & 1) { P.mu_src[P.com_jrow0[t] + c] = (int16_t)(-1 - 3 * t - r); ++c; }
-      for (int l = 0; l < kWave; ++l)
-        if (P.wood_col[l] >= P.com_jrow0[t] && P.wood_col[l] < P.com_jrow0[t] + c)
-          P.wood_mask[l] = m->nv >= 64 ? ~0ull : ((1ull << m->nv) - 1ull);
-    }
-    // What a product lane used to work out of these tables in every solve.  Its dofs as a list: ascending, as the walk over
-    // the bits of wood_mask takes them (the order of the sums, hence every bit of S, stays), one byte each; every lane walks
-    // wood_trip entries, the longest list, a shorter one padded with a dof off its chain — that entry of its Jh row is the
-    // filled zero, and +0·b leaves a sum that started at +0 as it is.  No lists (wood_trip = 0, the lanes walk the mask)
-    // when a chain has more than kWoodList dofs or a shorter lane has no dof to pad with.
-    // Its stores: rows [wood_row0, +wood_rpc) below n_jrows go to S, row n_jrows — entry wood_jrhs of the one chunk that
-    // holds it — to w.
-    P.wood_trip = 0;
-    P.wood_jrhs = P.n_jrows % P.wood_rpc;
-    bool lists = true;
-    for (int l = 0; l < kWave; ++l) {
-      for (int i = 0; i < 4; ++i) P.wood_list[l][i] = 0;
-      if (P.wood_col[l] < 0) continue;
-      const int len = __builtin_popcountll(P.wood_mask[l]);
-      if (len > kWoodList) lists = false;
-      P.wood_trip = len > P.wood_trip ? len : P.wood_trip;
-    }
-    for (int l = 0; l < kWave && lists; ++l) {
-      if (P.wood_col[l] < 0) continue;
-      int n = 0, pad = -1;
-      for (int k = 0; k < 64; ++k) {
-        if ((P.wood_mask[l] >> k) & 1) { P.wood_list[l][n >> 2] |= (uint32_t)k << (8 * (n & 3)); ++n; }
-        else if (pad < 0 && k < m->nv) pad = k;
-      }
-      if (n < P.wood_trip && pad < 0) lists = false;
-      for (; n < P.wood_trip && lists; ++n) P.wood_list[l][n >> 2] |= (uint32_t)pad << (8 * (n & 3));
-    }
-    if (!lists) P.wood_trip = 0;
-    return true;
-  };
-  // what the low-rank start's stability criterion compares (plan_launch(): damping + the smallest posture diagonal against the largest
-  // task cost²)
-  auto wood_scales = [&]() {
-    double mn = __builtin_huge_val();
-    for (int i = 0; i < m->nv; ++i) {
-      double dsum = 0.0;
-      for (int t = 0; t < d->n_posture_tasks; ++t) {
-        // free-joint dofs carry no posture term (posture_task.py:115-116,139-141)
-        const int jt = m->jnt_type[m->dof_jntid[i]];
-        if (jt != 0) dsum += pcost[t * 64 + i] * pcost[t * 64 + i];
-      }
-      mn = dsum < mn ? dsum : mn;
-    }
-    p->wood_min_diag = mn;
-    p->wood_max_cost2 = 0.0;
-    for (const auto& f : ft) for (int k = 0; k < 6; ++k) p->wood_max_cost2 = fmax(p->wood_max_cost2, f.cost[k] * f.cost[k]);
-    for (int t = 0; t < P.n_com; ++t) for (int k = 0; k < 3; ++k) p->wood_max_cost2 = fmax(p->wood_max_cost2, P.com_cost[t][k] * P.com_cost[t][k]);
-  };
-  if (P.n_jrows > 0 && P.n_pairs == 0 && !p->has_relative && P.n_dense_rows == 0 &&
-      P.n_dense_limit_rows == 0 && P.n_jrows <= kMuBig) {
-    // (NT = NR: the task residuals are eliminated outside the tableau, one column of [S | Jh] per lane — wood_start; the
-    //  S columns sit on lanes [NR, NR + n_μ) or, when those do not exist, on lanes [0, n_μ) in a second register set)
-    int cand = 0;
-    for (int v = size_class(m->nv, F_WOOD, true); v && !cand; v = size_class(v + 1, F_WOOD, true))
-      if (v + P.n_jrows <= kWave || P.n_jrows <= v) cand = v;
-    const bool big = P.n_jrows > kMu || cand + P.n_jrows > kWave;
-    // When it pays.  Fewer task rows than dofs by a margin — half, three quarters for humanoid-size tableaus — measured in
-    // rounds 1-2 on arms, hands and the G1; round 4 (tools/bench_wood_criterion.py, H1 / Go1 / Spot / Allegro / Shadow with
-    // 12-18 rows on 18-25 dofs): whenever the small elimination applies (≤ kMu rows, S columns on lanes of their own) the
-    // low-rank start wins by 1.15-1.38 x up to rows = dofs; the large one (> kMu rows) loses beyond three quarters
-    // (Shadow 21 / 24: 0.57 x, H1 24 / 25: 0.93 x) and keeps the old margin.
-    const bool pays = 2 * P.n_jrows <= m->nv || (m->nv >= 32 && 4 * P.n_jrows <= 3 * m->nv) ||
-                      (!big && m->nv >= 16 && P.n_jrows <= m->nv) || dbg_env("MKH_DEBUG_WOOD_ALWAYS");
-    if (cand && pays) { p->wood_nt = cand; p->wood_nr = cand; }
-    if (p->wood_nt) {
-      p->wood_big = P.n_jrows > kMu || p->wood_nr + P.n_jrows > kWave;
-      // (two-waves map: plain or compact layout; one-more-wave map: always compact, one pivot buffer on the F_COM builds)
-      auto lds_wood = [&](bool pre, bool compact) { return lds_bytes_of(P, p->wood_nt, p->wood_nr, F_WOOD, false, pre, compact); };
-      auto lds_wood_w3 = [&](int feat, bool pre) { return lds_bytes_of(P, p->wood_nt, p->wood_nr, feat, true, pre); };
-      // 2-waves map: the plain layout, or — when that would cost a resident wave and the pair lanes need one pass only (the
-      // compact layout lets the Jacobian rows overwrite the task blocks) — the compact one
-      P.wood_compact = 0; P.prefetch_wc = 0;
-      P.wood_refine = (p->diag & MKH_DIAG_NO_COLD_REFINE) ? 0 : 1;
-      {
-        if (waves_per_cu(p->wood_nt, lds_wood(false, false)) < waves_per_cu(p->wood_nt, 1) && P.n_jrows > 0) {
-          int n_jp = 0;
-          for (size_t t = 0; t < ft.size(); ++t) n_jp += __builtin_popcountll(ft[t].dof_mask);
-          if (n_jp <= kWave && waves_per_cu(p->wood_nt, lds_wood(false, true)) > waves_per_cu(p->wood_nt, lds_wood(false, false))) {
-            P.wood_compact = 1;
-            P.prefetch_wc = waves_per_cu(p->wood_nt, lds_wood(true, true)) == waves_per_cu(p->wood_nt, lds_wood(false, true)) ? 1 : 0;
-          }
-        }
-      }
-      p->wood_lds_bytes = P.wood_compact ? lds_wood(P.prefetch_wc != 0, true) : lds_wood(P.prefetch != 0, false);
-      if (!wood_tables()) p->wood_nt = 0;
-      if (p->wood_lds_bytes * 8 > 160 * 1024) p->wood_nt = 0;      // would cost residency
-      // 3 waves per SIMD (compact layout: the Jacobian rows overwrite the task blocks, so the pair lanes need one pass)
-      P.prefetch_w3w = 0;
-      if (find_variant(p->wood_nt, p->wood_nr, F_WOOD, true) && P.n_jpairs <= kWave && P.n_com == 0 && !p->wood_big) {
-        const int full = waves_per_cu(p->wood_nt, 1, true);     // 16 waves per CU for NT ≤ 24, else 12
-        if (waves_per_cu(p->wood_nt, lds_wood_w3(F_WOOD, false), true) == full) {
-          P.prefetch_w3w = waves_per_cu(p->wood_nt, lds_wood_w3(F_WOOD, true), true) == full ? 1 : 0;
-          p->wood_lds_bytes_w3 = lds_wood_w3(F_WOOD, P.prefetch_w3w != 0);
-        }
-      }
-      // ... and four (the product-form build on TabW4<44>, one problem per workgroup: everything that is dead after the pair lanes
-      // in one union, ik_kernel.h build_lds_layout_w4p).  Sixteen wavefronts per CU by registers (128 VGPRs), so the layout has to
-      // fit 8 of the CU's 128 LDS granules; 9 would be 14 wavefronts, uneven SIMDs — the problem then stays on the three-waves build.
-      p->wood_lds_bytes_w4 = 0;
-      if (p->wood_lds_bytes_w3 && p->wood_nt == 44 && P.n_com == 0 && !p->wood_big && find_variant(44, 44, F_WOOD, true, true, true)) {
-        const int bytes = build_lds_layout_w4p(P, p->wood_nr).total * (int)sizeof(double);
-        if (128 / ((bytes + 1279) / 1280) >= 16) p->wood_lds_bytes_w4 = bytes;
-      }
-      // ... and the F_COM builds of a humanoid-size robot (ComTask rows and / or up to 24 task rows: `44_36_r44_w3`, round 5).
-      // Their 25 rows of Jh take 8.8 KB of the compact layout — 15.4 KB for the G1 full example, 10 wavefronts per CU instead
-      // of 8 — so the bar is "more resident wavefronts than the two-waves map", not all twelve.
-      static const bool no_com_w3 = dbg_env("MKH_DEBUG_NO_COM_W3") != nullptr;       // (A/B switch)
-      if (!no_com_w3 && find_variant(p->wood_nt, p->wood_nr, F_WOOD | F_COM, true) && P.n_jpairs <= kWave && (P.n_com > 0 || p->wood_big)) {
-        const int two = waves_per_cu(p->wood_nt, 1, false);     // 8
-        const int w = waves_per_cu(p->wood_nt, lds_wood_w3(F_WOOD | F_COM, false), true);
-        if (w >= two + 2) {                                   // (nine per CU — 3 + 2 + 2 + 2 — measured SLOWER than eight: 1.51 vs 1.44 ms)
-          P.prefetch_w3w = waves_per_cu(p->wood_nt, lds_wood_w3(F_WOOD | F_COM, true), true) == w ? 1 : 0;
-          p->wood_lds_bytes_w3 = lds_wood_w3(F_WOOD | F_COM, P.prefetch_w3w != 0);
-        }
-      }
-      wood_scales();
-    }
-  }
-  // ---- low-rank start WITH half-space rows (round 6; ik_kernel.h wood_start "half-space rows"): a collision problem whose
-  // tasks qualify for the low-rank start keeps it — every contact row is one more column of the n_μ-step elimination instead of
-  // the reason for nv single pivots on the whole tableau (47 % of `g1_coll`).  Analytic pair sets (FEAT 8 → 40), frame + posture
-  // tasks, at most kMu task rows, one pass of (task, dof) pair lanes (the Jacobian rows overwrite the task blocks in LDS) and at most
-  // 8 half-space rows per instance (the rows' Gram entries wait in the contact table); a 48-row tableau (mkh_problem_create below).
-  if (P.n_jrows > 0 && P.n_jrows <= kMu && P.n_pairs > 0 && !p->has_relative && P.n_com == 0 && P.n_dense_rows == 0 &&
-      P.n_dense_limit_rows == 0 && !P.dense_box && !p->simple_pairs && !p->convex_pairs) {
-    if (wood_tables() && P.n_jpairs <= kWave) { p->woodr_tables = true; wood_scales(); }
-  }
-  auto woodr_bytes = [&](const DeviceProblem& D, bool pre) { return lds_bytes_of(D, 48, 48, F_WOOD | F_COLL, false, pre); };
-  if (p->woodr_tables && p->nt == 48 && P.max_rows <= 8) {
-    P.prefetch_wc = waves_per_cu(48, woodr_bytes(P, true)) == waves_per_cu(48, woodr_bytes(P, false)) ? 1 : 0;
-    p->woodr_lds = woodr_bytes(P, P.prefetch_wc != 0);
-  }
-  {
-    LaneProblem2 lp;
-    const int small_cls = build_lane_problem(m, d, P, ft, pcost, clo, chi, vlim, p->has_relative, lp);
-    p->lane_nv = small_cls <= 8 ? small_cls : 0;
-    p->quad_nt = small_cls ? (small_cls <= 8 ? 8 : (small_cls == 32 ? 32 : 16)) : 0;
-    if (dbg_env("MKH_DEBUG_NO_PAIR_ROWS") && p->quad_nt == 32) p->quad_nt = 0;   // (A/B switch: 17 … 32-dof robots back on the wavefront kernel)
-    // (the two-row loop carries a free joint's quaternion on the link of its rotation; a free body on no task chain — the loose
-    //  object of a hand scene — has no link, and its loops stay on the wavefront kernel, which integrates every joint)
-    if (small_cls == 32 && lp.nq != lp.nv) {
-      bool linked = false;
-      for (int k = 0; k < lp.nlink; ++k) linked = linked || lp.link[k].jtype == JNT_BALL;
-      p->quad_loop_ok = linked;
-    }
-    if (small_cls) {
-      p->lane_lds = lane_lds_bytes(lp.nlink);
-      bool ident = true;
-      for (int dd = 0; dd < lp.nv; ++dd) ident = ident && lp.dof_qadr[dd] == dd;
-      p->lane_dims = LaneDims{lp.nq, lp.nv, lp.nlink, lp.n_frame, lp.n_posture, lp.n_cfg, lp.n_vel, ident ? 1 : 0};
-      // (the lane kernel and the one-row builds of the row kernel read the small descriptor, the two-row build the large one)
-      LaneProblem lp1;
-      if (small_cls != 32) lane_problem_narrow(lp, lp1);
-      const void* src = small_cls == 32 ? (const void*)&lp : (const void*)&lp1;
-      const size_t bytes = small_cls == 32 ? sizeof(LaneProblem2) : sizeof(LaneProblem);
-      if (hipMalloc((void**)&p->d_lane, bytes) != hipSuccess || hipMemcpy(p->d_lane, src, bytes, hipMemcpyHostToDevice) != hipSuccess)
-        return bail(fail(MKH_E_HIP, "lane descriptor upload failed"));
-    }
-  }
-  // Tight rows: a hand with 40 capsule pairs has ≈17 contacts inside the detection distance at a time, but 40 rows put it
-  // on the 64-row tableau (128 pinned VGPRs, 23 KB of LDS: 7 wavefronts per CU).  With 48 − nv rows it runs on the 48-row
-  // build — Shadow config 4: 0.398 → 0.343 ms — and the rare instance with a violated dropped contact is solved again on
-  // the full-row build (launch()).
-  {
-    const DeviceProblem& P0 = p->dev;
-    const int cap = 48 - m->nv;
-    static const bool no_tight = dbg_env("MKH_DEBUG_NO_TIGHT_ROWS") != nullptr;      // (A/B of this path)
-    // Round 5: the same for pair sets with boxes, cylinders, ... (the analytic collision build) — a humanoid-size robot reserves
-    // 64 − nv rows, which costs the 64-row build a resident wavefront or two in LDS: G1 with 46 pairs (21 rows, 24.6 KB: 6
-    // wavefronts per CU) 0.757 → ≈ 0.60 ms with 5 rows on the 48-row build.  Few contacts are in range at a time when
-    // collision avoidance works; when many are, the cost is the two launches (MKH_FLAG_FULL_ROWS pins the full-row build).
-    //  Humanoid-size robots only (32 dofs and up): ALOHA (16 dofs, 48 rows reserved, 1 104 pairs) measures 2.26 → 2.53 ms this
-    //  way — its full build is not short of wavefronts, and the instances that overflow 32 rows walk the pair list twice.
-    const bool generic = !p->simple_pairs && !p->convex_pairs && P0.n_pairs > 0 && m->nv >= 32 && cap >= 4 && !dbg_env("MKH_DEBUG_NO_TIGHT_GENERIC");
-    if (!no_tight && (p->simple_pairs ? cap >= 16 : generic) && P0.n_dense_limit_rows == 0 && P0.n_dense_rows == 0 && !P0.dense_box && p->nt == 64 &&
-        P0.n_pairs > cap) {
-      DeviceProblem T = P0;
-      T.max_rows = cap;
-      T.n_hsel = lds_even(T.n_pairs) + (p->use_cull ? lds_even((T.n_pairs + 3) / 4) : 0);
-      T.nt = 48;
-      auto lds_t = [&](bool pre) { return lds_bytes_of(T, 48, 0, kDirectFeat, false, pre); };
-      T.prefetch = waves_per_cu(48, lds_t(true)) == waves_per_cu(48, lds_t(false)) ? 1 : 0;
-      p->nt_tight = 48;
-      p->lds_tight = lds_t(T.prefetch != 0);
-      if (p->woodr_tables && T.max_rows <= 8) {               // the tight launch with the low-rank start (round 6)
-        T.prefetch_wc = waves_per_cu(48, woodr_bytes(T, true)) == waves_per_cu(48, woodr_bytes(T, false)) ? 1 : 0;
-        p->woodr_lds_tight = woodr_bytes(T, T.prefetch_wc != 0);
-      }
-      if (hipMalloc((void**)&p->d_dev_tight, sizeof(DeviceProblem)) != hipSuccess ||
-          hipMemcpy(p->d_dev_tight, &T, sizeof(DeviceProblem), hipMemcpyHostToDevice) != hipSuccess ||
-          hipMalloc((void**)&p->d_status_tight, (size_t)p->max_batch * sizeof(int32_t)) != hipSuccess)
-        return bail(fail(MKH_E_HIP, "descriptor upload failed"));
-    }
-  }
-  if (hipMalloc((void**)&p->d_dev, sizeof(DeviceProblem)) != hipSuccess ||
-      hipMemcpy(p->d_dev, &p->dev, sizeof(DeviceProblem), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMalloc((void**)&p->d_taps, sizeof(TapArgs)) != hipSuccess ||
-      hipMalloc((void**)&p->d_work, 128) != hipSuccess || hipMemset(p->d_work, 0, 128) != hipSuccess ||
-      hipDeviceSynchronize() != hipSuccess)   // (hipMemset may return before the fill has run; launches may come on any stream)
-    return bail(fail(MKH_E_HIP, "descriptor upload failed"));
-  // More rows can be active at once than the 64 − nv the wavefront kernels hold (the reference stacks them all:
-  // mink/solve_ik.py:25-40): the instances a launch flags MKH_ST_ROW_OVERFLOW are solved again by the workgroup-per-problem
-  // kernel with every row (launch(): the redo launch behind plain solves)
-  const bool no_wide = (p->diag & MKH_DIAG_NO_WIDE_REDO) != 0;                  // (tests: what the wavefront kernel alone leaves flagged)
-  // (round 5: EVERY problem with half-space rows gets this twin — its dense Goldfarb–Idnani iteration also re-solves the instances
-  //  whose active rows are almost dependent, wherever they occur)
-  if (!no_wide && P.n_pairs + P.n_dense_limit_rows > 0) {
-    const int32_t rc = build_wide_problem(p, m, d, ft, pairs, culls, dcost, dwgain);
-    if (rc != MKH_OK) return bail(rc);
-  }
-  // The two-kernel split of general convex pairs (convex_pre.hip): per convex pair the chains root → body of its two geoms, and
-  // the buffer of pre-evaluated contacts the analytic build reads.  It uses the plain model arrays of the twin above.
-  static const bool no_split = dbg_env("MKH_DEBUG_NO_CONVEX_SPLIT") != nullptr;      // (A/B: the in-kernel routine, round 4's path)
-  if (p->d_wide && n_cv > 0 && !no_split) {
-    std::vector<int32_t> cv_pair, adr{0}, chain;
-    for (size_t k = 0; k < pairs.size(); ++k) {
-      if (pairs[k].cv_slot < 0) continue;
-      cv_pair.push_back((int32_t)k);
-      for (int body : {pairs[k].body1, pairs[k].body2}) {
-        std::vector<int32_t> up;
-        for (int b = body; b > 0; b = m->body_parentid[b]) up.push_back(b);
-        chain.insert(chain.end(), up.rbegin(), up.rend());
-        adr.push_back((int32_t)chain.size());
-      }
-    }
-    if (upload(cv_pair, &p->d_cv_pair) != hipSuccess || upload(adr, &p->d_cv_adr) != hipSuccess || upload(chain, &p->d_cv_chain) != hipSuccess ||
-        hipMalloc((void**)&p->d_cv, (size_t)p->max_batch * n_cv * 7 * sizeof(double)) != hipSuccess)
-      return bail(fail(MKH_E_HIP, "convex pre-pass buffers"));
-    p->cv = mkh::CvPre{n_cv, p->d_cv_pair, p->d_cv_adr, p->d_cv_chain};
-    p->dev.n_cv = n_cv; p->dev.cv_contacts = p->d_cv;
-    if (hipMemcpy(p->d_dev, &p->dev, sizeof(DeviceProblem), hipMemcpyHostToDevice) != hipSuccess) return bail(fail(MKH_E_HIP, "descriptor upload failed"));
   }
   *out = p;
   return MKH_OK;
@@ -1531,13 +450,12 @@ int32_t mkh_problem_create_diag(MkhModel* m, const MkhProblemDesc* d, int32_t ma
 void mkh_problem_destroy(MkhProblem* p) {
   if (!p) return;
   (void)hipSetDevice(p->device);
-  (void)hipFree(p->d_frame); (void)hipFree(p->d_posture_cost); (void)hipFree(p->d_cfg_lower); (void)hipFree(p->d_cfg_upper);
-  (void)hipFree(p->d_vel); (void)hipFree(p->d_pairs); (void)hipFree(p->d_cull); (void)hipFree(p->d_dev); (void)hipFree(p->d_taps); (void)hipFree(p->d_work);
+  for (void* w : p->owned) (void)hipFree(w);
+  (void)hipFree(p->d_dev); (void)hipFree(p->d_taps); (void)hipFree(p->d_work);
   (void)hipFree(p->d_lane); (void)hipFree(p->d_warm); (void)hipFree(p->d_qkeep);
-  (void)hipFree(p->d_cv); (void)hipFree(p->d_cv_pair); (void)hipFree(p->d_cv_adr); (void)hipFree(p->d_cv_chain); (void)hipFree(p->d_dev_tight); (void)hipFree(p->d_status_tight);
-  (void)hipFree(p->d_dense_cost); (void)hipFree(p->d_dense_wgain); (void)hipFree(p->s_iters);
+  (void)hipFree(p->d_cv); (void)hipFree(p->d_dev_tight); (void)hipFree(p->d_status_tight);
+  (void)hipFree(p->s_iters);
   (void)hipFree(p->s_de); (void)hipFree(p->s_dJ); (void)hipFree(p->s_dG); (void)hipFree(p->s_dh); (void)hipFree(p->s_dbox); (void)hipFree(p->d_clk);
-  for (void* w : p->wide_allocs) (void)hipFree(w);
   (void)hipFree(p->d_wide);
   (void)hipFree(p->s_q); (void)hipFree(p->s_ft); (void)hipFree(p->s_pt); (void)hipFree(p->s_ct); (void)hipFree(p->s_v); (void)hipFree(p->s_status);
   for (GrowBuf& g : p->ws) g.release();
@@ -3030,7 +1948,7 @@ int32_t mkh_integrate(MkhModel* m, int32_t B, const double* q, const double* v, 
   hipStream_t stream = (hipStream_t)hip_stream;
   DeviceProblem P;
   memset(&P, 0, sizeof P);
-  fill_base(m, P);
+  P.nq = m->nq; P.nv = m->nv; P.njnt = m->njnt; P.jnt_i = m->d_jnt_i;       // (all the kernel reads)
   const long long total = (long long)B * m->njnt;
   const int block = 256;
   const int grid = (int)((total + block - 1) / block);

@@ -1,6 +1,6 @@
 // Device-side problem descriptor: the flattened model + task/limit snapshot laid
 // out as lane tables (structure-of-arrays with stride 64 so that lane l reads
-// table[field*64 + l] coalesced).  Built once on the host in minkhip.hip.
+// table[field*64 + l] coalesced).  Built once on the host in problem_plan.hip.
 #pragma once
 #include <stdint.h>
 
@@ -144,7 +144,7 @@ struct DeviceProblem {
   int32_t n_cv, n_cv_pad;
   const double* cv_contacts;       // [max_batch][n_cv][7], owned by the problem handle
   const PairCull* cull;  // one record per pair when n_pairs > 64, else nullptr (ik_kernel.h collision_phase)
-  // low-rank start: what the product lanes used to derive from wood_mask / wood_row0 in every solve (minkhip.hip wood_tables)
+  // low-rank start: what the product lanes used to derive from wood_mask / wood_row0 in every solve (problem_plan.hip wood_tables)
   // wood_list[l]: the dofs of wood_mask[l] in ascending order, one byte each (entry i = byte i & 3 of word i >> 2), padded up
   // to wood_trip entries with a dof OFF the lane's chain (its entry of the lane's Jh row is the filled zero);
   // wood_trip: the longest list — every product lane walks that many entries —, or 0 when the lists do not apply (a chain of

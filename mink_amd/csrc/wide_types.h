@@ -1,4 +1,4 @@
-// Descriptor of the workgroup-per-problem kernel (wide_kernel.h), shared with the host side (minkhip.hip build_wide_problem).
+// Descriptor of the workgroup-per-problem kernel (wide_kernel.h), shared with the host side (problem_plan.hip plan_wide).
 #pragma once
 #include <stdint.h>
 

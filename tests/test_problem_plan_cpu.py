@@ -1,0 +1,248 @@
+"""The host tables of problem creation, checked without a device.
+
+mink_amd/csrc/problem_plan.hip plans a problem as plain data (problem_plan.h); tests/host/plan_cases.cpp drives it over synthetic
+models and descriptors that put every fixed-size array of the device descriptor at its edge, built with the host's address and
+undefined-behaviour sanitizers and run as a child process.  The tables it prints are recomputed here from the models' parent
+arrays and the descriptors' costs, not from the plan.
+"""
+
+import json
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(REPO, "mink_amd", "csrc")
+KMU, KMU_BIG, KWOOD_LIST = 18, 24, 16          # lds_layout.h kMu / kMuBig, mkh_types.h kWoodList
+
+
+@pytest.fixture(scope="module")
+def plans(tmp_path_factory):
+    from mink_amd.csrc import build as hipbuild
+
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    d = tmp_path_factory.mktemp("plan_cases")
+    # the table of variants.h from the same list as the library's, with null launch pointers
+    table = d / "variant_table.hip"
+    table.write_text(hipbuild.variant_table_source(launchers=False).replace('"../variants.h"', '"variants.h"'))
+    flags = ["-x", "hip", "--offload-host-only", "-std=c++17", "-O1", "-g", "-Xarch_host", "-fsanitize=address,undefined",
+             "-Xarch_host", "-fno-sanitize-recover=all", "-I", CSRC]
+    srcs = [os.path.join(REPO, "tests", "host", "plan_cases.cpp"), os.path.join(CSRC, "problem_plan.hip"), str(table)]
+    objs = [str(d / (os.path.basename(s) + ".o")) for s in srcs]
+    procs = [subprocess.Popen([hipcc] + flags + ["-c", s, "-o", o], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+             for s, o in zip(srcs, objs)]
+    for p in procs:
+        out = p.communicate()[0]
+        assert p.returncode == 0, out
+    exe = str(d / "plan_cases")
+    subprocess.run([hipcc, "--offload-host-only", "-Xarch_host", "-fsanitize=address,undefined"] + objs + ["-o", exe], check=True)   # (host code only: the sanitizers never see the device)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+    assert r.stderr == "", r.stderr[-4000:]             # the sanitized run: nothing reported
+    rows = [json.loads(line) for line in r.stdout.splitlines()]
+    return {(c["model"], c["case"]): c for c in rows}
+
+
+def chain_of(c, body):
+    """Dofs on the chain world -> body, from the parent array alone."""
+    dofs = []
+    while body > 0:
+        if c["body_dofnum"][body] > 0:
+            dofs += range(c["body_dofadr"][body], c["body_dofadr"][body] + c["body_dofnum"][body])
+        body = c["body_parentid"][body]
+    return sorted(dofs)
+
+
+def task_rows(c):
+    """Per frame task: its active rows (cost != 0) — then the ComTask's."""
+    return [[r for r in range(6) if t["cost"][r] != 0] for t in c["tasks"]]
+
+
+def ok_cases(plans, wavefront=True):
+    return [c for c in plans.values() if c["rc"] == 0 and (not wavefront or not c["big"])]
+
+
+def tables_in_effect(c):
+    return c["sel"]["wood_nt"] != 0 or c["sel"]["woodr_tables"] != 0
+
+
+def test_every_case_planned(plans):
+    assert len(plans) > 200
+    models = {m for m, _ in plans}
+    assert models == {"chain6", "chain16", "chain17", "chain44", "chain63", "chain64", "tree44", "tree62", "ball11", "chain68"}
+    assert {plans[(m, "t1_r6")]["nv"] for m in models} == {6, 16, 17, 44, 63, 64, 62, 11, 68}
+    # enough of them take the low-rank start for the table checks below to mean something
+    assert sum(1 for c in ok_cases(plans) if tables_in_effect(c)) >= 40
+    assert sum(1 for c in ok_cases(plans) if c["sel"]["woodr_tables"]) >= 8
+    assert sum(1 for c in ok_cases(plans) if c["dev"]["wood_trip"] > 0) >= 15
+
+
+def test_task_rows_and_tap_layout(plans):
+    for c in ok_cases(plans, wavefront=False):
+        rows = task_rows(c)
+        n_jrows = sum(len(r) for r in rows) + c["com_rows"]
+        d = c["dev"] if not c["big"] else c["wide"]
+        assert d["n_jrows"] == n_jrows, (c["model"], c["case"])
+        assert d["n_rows_tap"] == 6 * len(rows) + c["nv"] + 3 * c["n_com"] + (3 if c["dense"] else 0)
+        assert c["dev"]["n_rows_tap"] == d["n_rows_tap"]
+
+
+def test_direct_pair_lanes(plans):
+    """dpair_*: the (task, dof) bits in task-major, dof-ascending order — the frame's chain and, for a RelativeFrameTask, its root's
+    — and none at all beyond 64."""
+    for c in ok_cases(plans):
+        want = []
+        for t, task in enumerate(c["tasks"]):
+            dofs = set(chain_of(c, task["body"])) | (set(chain_of(c, task["root"])) if task["root"] >= 0 else set())
+            want += [(t, k) for k in sorted(dofs)]
+        d = c["dev"]
+        if len(want) <= 64:
+            assert d["n_dpairs"] == len(want)
+            assert list(zip(d["dpair_task"], d["dpair_dof"]))[:len(want)] == want, (c["model"], c["case"])
+        else:
+            assert d["n_dpairs"] == 0
+    assert plans[("chain16", "dpairs64")]["dev"]["n_dpairs"] == 64
+    assert plans[("chain17", "dpairs65")]["dev"]["n_dpairs"] == 0
+
+
+def test_low_rank_tables(plans):
+    for c in ok_cases(plans):
+        if not tables_in_effect(c):
+            continue
+        key = (c["model"], c["case"])
+        d, nv = c["dev"], c["nv"]
+        rows = task_rows(c)
+        n = d["n_jrows"]
+        # which task owns compact row r; the ComTask's rows are dense over the robot's dofs
+        owner = [t for t, r in enumerate(rows) for _ in r] + [-1] * c["com_rows"]
+        assert len(owner) == n
+        groups = 64 // n
+        rpc = -(-(n + 1) // groups)
+        assert d["wood_rpc"] == rpc and d["wood_jrhs"] == n % rpc, key
+        # rows [wood_row0, +wood_rpc) over the chunks of one column cover 0 … n_jrows once
+        for col in range(n):
+            covered = np.zeros(groups * rpc, dtype=int)
+            for lane in range(64):
+                if d["wood_col"][lane] == col:
+                    covered[d["wood_row0"][lane]:d["wood_row0"][lane] + rpc] += 1
+            assert (covered[:n + 1] == 1).all(), key
+        lens = []
+        for lane in range(64):
+            if lane >= groups * n:
+                assert d["wood_col"][lane] == -1
+                continue
+            col = lane % n
+            assert d["wood_col"][lane] == col and d["wood_row0"][lane] == (lane // n) * rpc, key
+            dofs = chain_of(c, c["tasks"][owner[col]]["body"]) if owner[col] >= 0 else list(range(nv))
+            assert int(d["wood_mask"][lane]) == sum(1 << k for k in dofs), key
+            lens.append(len(dofs))
+        # the packed lists: the mask's bits ascending, one byte each, padded to the longest with a dof off the chain
+        off_chain = lambda dofs: [k for k in range(nv) if k not in dofs]
+        lanes = [lane for lane in range(groups * n)]
+        chains = {lane: (chain_of(c, c["tasks"][owner[lane % n]]["body"]) if owner[lane % n] >= 0 else list(range(nv))) for lane in lanes}
+        trip = max(lens)
+        applies = trip <= KWOOD_LIST and all(len(chains[l]) == trip or off_chain(chains[l]) for l in lanes)
+        assert d["wood_trip"] == (trip if applies else 0), key
+        if applies:
+            lists = np.array(d["wood_list"], dtype=np.uint32).reshape(64, 4)
+            for lane in lanes:
+                got = [int(lists[lane][i >> 2] >> (8 * (i & 3))) & 255 for i in range(trip)]
+                m = len(chains[lane])
+                assert got[:m] == chains[lane], key
+                assert all(g not in chains[lane] and 0 <= g < nv for g in got[m:]), key
+                assert len(set(got[m:])) <= 1
+        # (task, dof) pair lanes of the Jacobian rows and the source of each row's weighted error
+        want = [(t, k) for t, task in enumerate(c["tasks"]) for k in chain_of(c, task["body"])]
+        assert d["n_jpairs"] == len(want) <= 256, key
+        assert list(zip(d["jpair_task"], d["jpair_dof"]))[:len(want)] == want, key
+        mu = [t * 64 + 30 + r for t, rr in enumerate(rows) for r in rr]
+        assert d["mu_src"][:len(mu)] == mu, key
+        assert all(x < 0 for x in d["mu_src"][len(mu):n])           # ComTask rows: computed on the device
+    # 256 pair lanes are the capacity: one more and the plan drops the low-rank start
+    assert plans[("chain44", "jpairs256")]["sel"]["wood_nt"] == 44 and plans[("chain44", "jpairs256")]["dev"]["n_jpairs"] == 256
+    assert plans[("chain44", "jpairs257")]["sel"]["wood_nt"] == 0
+    # kMu / kMuBig and one past each
+    assert plans[("tree44", "t4_rows18")]["sel"]["wood_big"] == 0 and plans[("tree44", "t4_rows19")]["sel"]["wood_big"] == 1
+    assert plans[("tree44", "t4_rows24")]["sel"]["wood_nt"] == 44 and plans[("tree44", "t5_rows25")]["sel"]["wood_nt"] == 0
+    # chains of 6 + 12 / 13 dofs are beyond the packed lists; 6 + 9 / 10 fill them exactly
+    assert plans[("tree44", "t4_rows18")]["dev"]["wood_trip"] == KWOOD_LIST
+    assert plans[("chain17", "t1_r6")]["sel"]["wood_nt"] and plans[("chain17", "t1_r6")]["dev"]["wood_trip"] == 0
+
+
+def test_reserved_lds_is_the_layout_statement(plans):
+    """Every *_lds_bytes* figure a launch reserves is 8 x total of build_lds_layout for that build on that descriptor (the program
+    prints both: this checks the plumbing between plan and layout), and the four-waves figure only where 16 wavefronts fit."""
+    for c in ok_cases(plans):
+        s, lay = c["sel"], c["layout"]
+        names = ["lds_bytes", "lds_bytes_full", "lds_bytes_w3", "wood_lds_bytes_w3", "wood_lds_bytes_w4", "woodr_lds", "lds_tight",
+                 "woodr_lds_tight"] + (["wood_lds_bytes"] if s["wood_nt"] else [])
+        for name in names:
+            if s[name]:
+                assert s[name] == lay[name], (c["model"], c["case"], name)
+        assert s["lds_bytes"] > 0 and s["lds_bytes_full"] > 0
+        assert s["wood_lds_bytes_w4"] <= 10240
+        if s["wood_lds_bytes_w4"]:
+            assert s["wood_nt"] == 44 and s["wood_lds_bytes_w3"] > 0
+        assert (s["nt_tight"] == 48) == bool(c["tight"]) == (s["lds_tight"] > 0)
+    assert sum(1 for c in ok_cases(plans) if c["sel"]["wood_lds_bytes_w4"]) >= 5
+    assert sum(1 for c in ok_cases(plans) if c["sel"]["lds_tight"]) >= 4
+    assert plans[("tree44", "t2_rows9_boxpairs4")]["sel"]["woodr_lds"] > 0
+    assert plans[("tree44", "t2_rows9_boxpairs21")]["sel"]["woodr_lds_tight"] > 0
+
+
+def test_humanoid_shape_selects_the_headline_builds(plans):
+    """The project's own record (docs/HISTORY.md): a 44-dof floating-base tree with feet (6 rows) and palms (3 rows) — 18 task
+    rows — plus a posture task runs the low-rank start on the 44-row builds with one more wave."""
+    s = plans[("tree44", "t4_rows18")]["sel"]
+    assert s["wood_nt"] == 44 and s["wood_nr"] == 44 and s["wood_lds_bytes_w3"] > 0
+    print("wood_lds_bytes_w4 =", s["wood_lds_bytes_w4"])
+    assert plans[("tree44", "t3_rows18")]["dev"]["wood_refine"] == 1
+    assert plans[("tree44", "t3_rows18_norefine")]["dev"]["wood_refine"] == 0
+
+
+def test_kernel_families(plans):
+    for c in ok_cases(plans, wavefront=False):
+        s, key = c["sel"], (c["model"], c["case"])
+        rows = c["n_pairs_in"]
+        if c["big"]:
+            assert s["wide_only"] == 1 and c["wide"]["built"] == 1 and c["wide"]["chain_words"] == 2 and c["lane"]["cls"] == 0, key
+            continue
+        assert s["wide_only"] == 0 and c["wide"]["built"] == (1 if rows else 0), key
+        assert c["dev"]["n_pairs"] == rows and c["dev"]["max_rows"] == min(rows, 64 - c["nv"]), key
+        assert c["dev"]["nt"] == s["nt"] >= c["nv"] + c["dev"]["max_rows"], key
+        assert c["n_cv"] == (1 if c["cylbox"] else 0) and s["convex_pairs"] == c["cylbox"], key
+        if c["cylbox"]:
+            # the chains root -> body of the pair's two geoms: the last body, then body 1
+            last = c["nbody"] - 1
+            up = []
+            b = last
+            while b > 0:
+                up.append(b)
+                b = c["body_parentid"][b]
+            assert c["cv_pair"] == [rows - 1] and c["cv_chain"] == up[::-1] + [1] and c["cv_adr"] == [0, len(up), len(up) + 1], key
+        if c["lane"]["cls"]:
+            assert c["lane"]["nv"] == c["nv"] and c["lane"]["nq"] == c["nq"] and c["nv"] <= 32 and not rows and not c["dense"], key
+    assert plans[("chain6", "t1_r6")]["sel"]["lane_nv"] == 6 and plans[("chain16", "t1_r6")]["sel"]["quad_nt"] == 16
+    assert plans[("chain17", "t1_r6")]["sel"]["quad_nt"] == 32 and plans[("chain44", "t1_r6")]["sel"]["quad_nt"] == 0
+    assert plans[("ball11", "t1_r6")]["lane"]["cls"] == 0                      # (a ball joint: wavefront kernel)
+    assert plans[("chain16", "t1_r6_relative")]["sel"]["has_relative"] == 1
+
+
+def test_refused_descriptors(plans):
+    """Code and text of mkh_last_error, as before the split."""
+    for (m, case), c in plans.items():
+        nv, nb = c["nv"], c["nbody"]
+        if case == "bad_dof_range":
+            assert (c["rc"], c["err"]) == (-1, "configuration limit: dof %d out of range" % nv)
+        elif case == "bad_cost":
+            assert (c["rc"], c["err"]) == (-1, "frame task 0: cost must be >= 0")
+        elif case == "bad_frame_id":
+            assert (c["rc"], c["err"]) == (-1, "frame task 0: body id %d out of range" % nb)
+        elif case == "bad_free_limit":
+            assert (c["rc"], c["err"]) == (-1, "configuration limit on free-joint dof 0 (the reference skips free joints)")
+        else:
+            assert c["rc"] == 0, (m, case, c["err"])
+    assert ("tree44", "bad_free_limit") in plans and ("tree62", "bad_free_limit") in plans
