@@ -699,6 +699,108 @@ int32_t mkh_seed_table_query(const MkhSeedTable *table, int32_t B, const double 
                              int32_t *index_out, double *dist_out, double *seeds_out, int32_t flags, void *hip_stream);
 int32_t mkh_problem_set_seed_table(MkhProblem *problem, const MkhSeedTable *table);
 
+/*
+ * Ladder-graph trajectory IK: S IK solutions per waypoint (a "rung"), computed independently of each other, and a dynamic
+ * program over the T rungs that picks the path — complete first, free of joint-space jumps second, shortest third.  It is the
+ * per-waypoint search ACROSS candidates that mkh_solve_trajectory_multistart leaves out: that call keeps one whole candidate,
+ * this one may change branch at every waypoint.  No counterpart in the reference.
+ *
+ * THE RULE (mkh_ladder_select; mkh_solve_trajectory_ladder runs it on the rungs it solves).
+ * Nodes.  Instance b, waypoint t, node s: configurations q_nodes (B, T, S, nq) and flags tracked (B, T, S), a node counting as
+ * tracked when its flag is != 0.  1 <= S <= 256 (back-pointers are bytes) and 1 <= T <= 65 535 (the two counts of a key are 16
+ * bits each); beyond either: MKH_E_LIMIT.
+ *
+ * Edge cost.  For t >= 1, from node s of rung t - 1 to node s' of rung t:
+ *   d = sum_k w_k ((q_{t,s'} (-) q_{t-1,s})_k)^2   multi-start's distance, the same device function: (-) = mj_differentiatePos at
+ *                                                   dt = 1, w = weights (nv,), each >= 0, or ones when NULL
+ *   c = d when 0 <= d <= DBL_MAX, else +inf         (a NaN or an overflow in either node: an edge nobody prefers)
+ * The START EDGE of node (0, s) is c(q_{0,s}, q[b]), from the caller's current posture q (B, nq) — the convention of
+ * mkh_solve_trajectory_multistart's length.  An edge with t >= 1 is a BREAK when c > max_step_sq; max_step_sq >= 0, +inf: nothing is
+ * ever a break; NaN or negative: MKH_E_INVALID.  The start edge is never a break.
+ *
+ * Key of a path (one node per rung), compared lexicographically:
+ *   lost    = its nodes with tracked == 0
+ *   breaks  = its break edges
+ *   length  = the sum of its c, start edge included, accumulated in ascending t by one rounded addition each — never fused
+ *             into the products inside d.  inf + x = inf: no NaN can arise.
+ *
+ * Recurrence.
+ *   K[0][s']  = (lost(0, s'), 0, c_start(s'))
+ *   K[t][s']  = min over s of  K[t-1][s] + (lost(t, s'), break(s -> s'), c(s -> s')),   pred[t][s'] = the LOWEST s attaining it
+ *   end node  = the lowest s with minimal K[T-1][s];  the path is the back-trace through pred.
+ * Rounded addition is monotone, so the recurrence is well defined; THE RESULT IS DEFINED BY THE RECURRENCE, not by "the optimum
+ * over the real numbers": a restatement that performs the same additions in the same order reproduces it.
+ *
+ * Outputs, per instance: node_index (B, T) the chosen s per waypoint; n_tracked (B,) = T - lost; n_breaks (B,); path_length
+ * (B,); edge_break (B, T): 1 where the edge INTO waypoint t is a break, entry 0 always 0.  Optional gather through the path:
+ * q_path[b, t] = q_nodes[b, t, node_index[b, t]].  Everything runs on the device, one wavefront per instance, without atomics;
+ * the back-pointers and break bits live in a workspace of the handle of B·T·(S + 8·ceil(S / 64)) bytes.
+ *
+ * Pointers are host pointers (staged, synchronous) or device pointers with MKH_FLAG_DEVICE_PTRS (asynchronous on the stream).
+ * A model for which one tile of 64 destination nodes, the keys, the joint table, the weights and one source node exceed 64 KB of
+ * LDS (nq beyond about 115): MKH_E_LIMIT.
+ */
+typedef struct MkhLadderIO {
+  int32_t *node_index;      /* (B, T)      the chosen node per waypoint                                           required  */
+  int32_t *n_tracked;       /* (B,)        tracked nodes on the path                                              required  */
+  int32_t *n_breaks;        /* (B,)        break edges on the path                                                required  */
+  double *path_length;      /* (B,)        its length                                                             required  */
+  int32_t *edge_break;      /* (B, T)      1 where the edge into waypoint t is a break                            required  */
+  double *q_path;           /* (B, T, nq)  optional: q_nodes gathered through the path                                      */
+} MkhLadderIO;
+int32_t mkh_ladder_select(MkhProblem *problem, int32_t B, int32_t T, int32_t S, const double *q, const double *q_nodes,
+                          const int32_t *tracked, const double *weights, double max_step_sq, const MkhLadderIO *io,
+                          int32_t flags, void *hip_stream);
+
+/*
+ * mkh_solve_trajectory_ladder: the rungs solved by multi-start, then THE RULE above.
+ *
+ * Rungs.  Rung t of instance b is what mkh_solve_multistart returns in q_all / converged_all / status_all / iters_all for
+ * target row (target_index0 + b)·T + t of the flattened (B·T) targets, BITWISE: the same seeding rule and generator
+ * u(rng_seed, (target_index0 + b)·T + t, s, k); seed 0 of every rung is the caller's q[b]; io->seeds (B, T, S, nq) as the
+ * alternative (row 0 of every rung is still replaced by q[b]); an attached seed table is queried with every waypoint's OWN
+ * frame targets, S - 1 nearest.  The B·T·S loops do not depend on each other: they run as one multi-start launch, or in chunks
+ * of whole rungs when B·T·S > max_batch (S <= max_batch is needed).  Node (b, t, s) is TRACKED when its loop converged and its
+ * status carries no bit but MKH_ST_OUTSIDE_LIMITS.
+ *
+ * Targets.  frame_targets (B, T, n_frame, 7).  posture_target is shared by the whole call — (n_posture, nq) — or, with
+ * MKH_FLAG_POSTURE_BATCHED, (B, T, n_posture, nq); the same for com_target with MKH_FLAG_COM_BATCHED.  Threshold mode only
+ * (both thresholds >= 0), at least one frame task, no dense rows.  MKH_FLAG_WARM_START does not enter, as in multi-start.
+ *
+ * Outputs.  The search's, and the chosen nodes' rows q_traj, v_traj, status, iters, converged in (B, T, .).  Optional: qvel by
+ * mkh_solve_trajectory's rule on the chosen path with q_{-1} = q; q_all (B, T, S, nq), v_all, status_all, iters_all,
+ * converged_all (B, T, S): every node; seeds_out (B, T, S, nq): the starts.  Pointers follow the call's convention; every
+ * argument error is reported before any device work.
+ */
+typedef struct MkhTrajectoryLadderIO {
+  const double *seeds;      /* (B, T, S, nq) caller-defined starts, or NULL: drawn, or from the attached seed table          */
+  const double *weights;    /* (nv,) weights of the edge cost, each >= 0, or NULL: ones                                      */
+  double max_step_sq;       /* the break gate on the edge cost, >= 0; +inf: no gate                                          */
+  double *q_traj;           /* (B, T, nq)  the chosen nodes' configurations                                        required  */
+  double *v_traj;           /* (B, T, nv)  their last velocities                                                   required  */
+  int32_t *status;          /* (B, T)      their MKH_ST_* bits                                                     required  */
+  int32_t *iters;           /* (B, T)      their iteration counts                                                  required  */
+  int32_t *converged;       /* (B, T)      their loops' converged flags                                            required  */
+  int32_t *node_index;      /* (B, T)      as MkhLadderIO                                                          required  */
+  int32_t *n_tracked;       /* (B,)                                                                                required  */
+  int32_t *n_breaks;        /* (B,)                                                                                required  */
+  double *path_length;      /* (B,)                                                                                required  */
+  int32_t *edge_break;      /* (B, T)                                                                              required  */
+  double *qvel;             /* (B, T, nv)  optional: (q_t (-) q_{t-1}) / waypoint_dt along the path, q_{-1} = q              */
+  double *seeds_out;        /* (B, T, S, nq) optional: the starts the loops ran from                                         */
+  double *q_all;            /* (B, T, S, nq) optional: every node's configuration                                            */
+  double *v_all;            /* (B, T, S, nv) optional                                                                        */
+  int32_t *status_all;      /* (B, T, S)   optional                                                                          */
+  int32_t *iters_all;       /* (B, T, S)   optional                                                                          */
+  int32_t *converged_all;   /* (B, T, S)   optional                                                                          */
+  double waypoint_dt;       /* > 0 when qvel is given                                                                        */
+} MkhTrajectoryLadderIO;
+int32_t mkh_solve_trajectory_ladder(MkhProblem *problem, int32_t B, int32_t T, int32_t n_seeds, const double *q,
+                                    const double *frame_targets, const double *posture_target, const double *com_target,
+                                    double dt, double damping, int32_t max_iters, double pos_threshold, double ori_threshold,
+                                    uint64_t rng_seed, int64_t target_index0, const MkhTrajectoryLadderIO *io, int32_t flags,
+                                    void *hip_stream);
+
 /* Same inputs; additionally writes the requested intermediates (build_ik / compute_error /
  * compute_jacobian / get_transform_frame_to_world parity taps).  v_out/status_out may be NULL
  * to skip the QP. */

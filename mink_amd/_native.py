@@ -222,6 +222,73 @@ class TrajectoryMultistartOut(NamedTuple):
     seeds: object = None
 
 
+LADDER_MAX_S = 256         # nodes per rung (back-pointers are bytes) and waypoints per path (include/minkhip.h "THE RULE")
+LADDER_MAX_T = 65535
+LADDER_IO_FIELDS = ("node_index", "n_tracked", "n_breaks", "path_length", "edge_break", "q_path")
+
+
+class MkhLadderIO(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in LADDER_IO_FIELDS]
+
+
+class LadderPathOut(NamedTuple):
+    """What NativeProblem.ladder_select returns (arrays of the caller's kind): the chosen `node_index` (B, T), per instance
+    `n_tracked`, `n_breaks` and `path_length` (B,), `edge_break` (B, T) and the nodes gathered through the path, `q` (B, T, nq)."""
+    node_index: object
+    n_tracked: object
+    n_breaks: object
+    path_length: object
+    edge_break: object
+    q: object
+
+
+TRAJECTORY_LADDER_IO_FIELDS = ("seeds", "weights", "max_step_sq", "q_traj", "v_traj", "status", "iters", "converged", "node_index",
+                               "n_tracked", "n_breaks", "path_length", "edge_break", "qvel", "seeds_out", "q_all", "v_all",
+                               "status_all", "iters_all", "converged_all", "waypoint_dt")
+
+
+class MkhTrajectoryLadderIO(C.Structure):
+    _fields_ = [(n, C.c_double if n in ("max_step_sq", "waypoint_dt") else C.c_void_p) for n in TRAJECTORY_LADDER_IO_FIELDS]
+
+
+class TrajectoryLadderOut(NamedTuple):
+    """What NativeProblem.solve_trajectory_ladder returns (arrays of the caller's kind).  The chosen nodes' rows `q`, `v`, `status`,
+    `iters`, `converged` (B, T, ·); the search's `node_index`, `edge_break` (B, T), `n_tracked`, `n_breaks`, `path_length` (B,);
+    `qvel` unless qvel_dt was not given.  With return_all every node's `q_all` (B, T, S, nq), `v_all` (B, T, S, nv),
+    `status_all`, `iters_all`, `converged_all` (B, T, S) and the `seeds` (B, T, S, nq); None otherwise."""
+    q: object
+    v: object
+    status: object
+    iters: object
+    converged: object
+    node_index: object
+    n_tracked: object
+    n_breaks: object
+    path_length: object
+    edge_break: object
+    qvel: object = None
+    q_all: object = None
+    v_all: object = None
+    status_all: object = None
+    iters_all: object = None
+    converged_all: object = None
+    seeds: object = None
+
+
+def check_ladder_shape(S: int, T: int, max_step_sq: float) -> None:
+    """The limits of include/minkhip.h "THE RULE" on a ladder's shape and gate, with no device in sight."""
+    if S < 1:
+        raise ValueError("a rung needs at least one node: S (n_seeds) must be >= 1")
+    if T < 1:
+        raise ValueError("a ladder needs at least one waypoint: T must be >= 1")
+    if S > LADDER_MAX_S:
+        raise ValueError(f"S = {S} nodes per rung: at most {LADDER_MAX_S} (back-pointers are bytes)")
+    if T > LADDER_MAX_T:
+        raise ValueError(f"T = {T} waypoints: at most {LADDER_MAX_T}")
+    if not max_step_sq >= 0.0:
+        raise ValueError(f"max_step must be >= 0 (None: no gate), got a squared gate of {max_step_sq}")
+
+
 def check_keyframe_times(key_times, waypoint_times):
     """The checks of include/minkhip.h "THE RULE" on the two time arrays, with no device in sight: float64 (K,) and (T,) arrays, or
     ValueError — key times strictly increasing, waypoint times non-decreasing and inside the keyframes' range, no NaN."""
@@ -310,6 +377,12 @@ def lib() -> C.CDLL:
     L.mkh_solve_trajectory_multistart.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + common[2:8] + \
         [C.c_int32, C.c_double, C.c_double, C.c_uint64, C.c_int64, C.POINTER(MkhTrajectoryMultistartIO), C.c_int32, C.c_void_p]
     L.mkh_solve_trajectory_multistart.restype = C.c_int32
+    L.mkh_ladder_select.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_double, C.POINTER(MkhLadderIO), C.c_int32, C.c_void_p]
+    L.mkh_ladder_select.restype = C.c_int32
+    L.mkh_solve_trajectory_ladder.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + common[2:8] + \
+        [C.c_int32, C.c_double, C.c_double, C.c_uint64, C.c_int64, C.POINTER(MkhTrajectoryLadderIO), C.c_int32, C.c_void_p]
+    L.mkh_solve_trajectory_ladder.restype = C.c_int32
     L.mkh_solve_dense.argtypes = common[:6] + [C.POINTER(MkhDenseRows), C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                                C.POINTER(MkhTaps), C.c_int32, C.c_void_p]
     L.mkh_solve_dense.restype = C.c_int32
@@ -347,7 +420,7 @@ EXPORTED_SYMBOLS = (
     "mkh_geom_distance_eval", "mkh_problem_create_diag", "mkh_solve_multistart",
     "mkh_solve_trajectory", "mkh_solve_keyframes", "mkh_solve_trajectory_multistart",
     "mkh_seed_table_create", "mkh_seed_table_destroy", "mkh_seed_table_read", "mkh_seed_table_query",
-    "mkh_problem_set_seed_table",
+    "mkh_problem_set_seed_table", "mkh_ladder_select", "mkh_solve_trajectory_ladder",
 )
 
 LIE_OPS = {"se3_log": (0, 7, 0, (6,)), "se3_jlog": (1, 7, 0, (6, 6)), "se3_ljacinv": (2, 6, 0, (6, 6)),
@@ -985,6 +1058,130 @@ class NativeProblem:
                                           (float(pos_threshold), float(ori_threshold)), qvel_dt, bool(time_major), warm_start,
                                           wave_kernel, lane_kernel, quad_kernel,
                                           cands=(int(n_seeds), int(rng_seed), int(target_index0), seeds, weights, bool(return_all)))
+
+    # ----------------------------------------------------------------- ladder
+    def ladder_select(self, q, q_nodes, tracked=None, max_step_sq: float = float("inf"), weights=None) -> LadderPathOut:
+        """mkh_ladder_select: the dynamic program of include/minkhip.h "THE RULE" over the caller's rungs — q (B, nq) the current
+        postures, q_nodes (B, T, S, nq), tracked (B, T, S) (None: every node), the squared break gate, weights (nv,) >= 0.
+        numpy in → numpy out (synchronous); torch CUDA tensors in → torch tensors out on the current stream, no host copy."""
+        m = self.nmodel.model
+        B = int(q.shape[0])
+        if len(q_nodes.shape) != 4:
+            raise ValueError(f"q_nodes must have shape (B, T, S, {m.nq}), got {tuple(q_nodes.shape)}")
+        T, S = int(q_nodes.shape[1]), int(q_nodes.shape[2])
+        check_ladder_shape(S, T, float(max_step_sq))
+        prep, empty, ptr, stream, devp = _call_kit(q)
+        q, q_nodes, weights = prep(q), prep(q_nodes), prep(weights)
+        if tuple(q.shape) != (B, m.nq):
+            raise ValueError(f"q must have shape (B, {m.nq}), got {tuple(q.shape)}")
+        if tuple(q_nodes.shape) != (B, T, S, m.nq):
+            raise ValueError(f"q_nodes must have shape ({B}, T, S, {m.nq}), got {tuple(q_nodes.shape)}")
+        if weights is not None and tuple(weights.shape) != (m.nv,):
+            raise ValueError(f"weights must have shape ({m.nv},), got {tuple(weights.shape)}")
+        if tracked is None:
+            tracked = empty((B, T, S), np.int32)
+            tracked[...] = 1
+        elif tuple(tracked.shape) != (B, T, S):
+            raise ValueError(f"tracked must have shape ({B}, {T}, {S}), got {tuple(tracked.shape)}")
+        elif devp:
+            import torch
+            tracked = (tracked != 0).to(device=q.device, dtype=torch.int32).contiguous()
+        else:
+            tracked = _i32(np.asarray(tracked) != 0)
+        f8, i4 = np.float64, np.int32
+        out = {"node_index": empty((B, T), i4), "n_tracked": empty((B,), i4), "n_breaks": empty((B,), i4),
+               "path_length": empty((B,), f8), "edge_break": empty((B, T), i4), "q_path": empty((B, T, m.nq), f8)}
+        io = MkhLadderIO()
+        for n, x in out.items():
+            setattr(io, n, ptr(x))
+        with self._lock:
+            _check(lib().mkh_ladder_select(self.handle, B, T, S, ptr(q), ptr(q_nodes), ptr(tracked), ptr(weights), float(max_step_sq),
+                                           C.byref(io), devp, stream))
+        return LadderPathOut(*[out[n] for n in LADDER_IO_FIELDS])
+
+    def solve_trajectory_ladder(self, q, frame_targets=None, posture_target=None, com_target=None, dt: float = 1e-2,
+                                damping: float = 1e-12, *, n_seeds: int, max_iters: int, pos_threshold: float,
+                                ori_threshold: float, max_step_sq: float = float("inf"), rng_seed: int = 0, target_index0: int = 0,
+                                seeds=None, weights=None, qvel_dt: Optional[float] = None, return_all: bool = False,
+                                wave_kernel: bool = False, lane_kernel: bool = False, quad_kernel: bool = False,
+                                seed_table=None) -> TrajectoryLadderOut:
+        """mkh_solve_trajectory_ladder: `n_seeds` IK solutions per waypoint — multi-start's loops on the (B·T) flattened targets,
+        seed 0 of every rung the row of q itself, the others drawn, taken from `seeds` (B, T, S, nq) or from `seed_table`
+        (queried with every waypoint's own targets) — then ladder_select's search and the gather of the chosen nodes, in one
+        call.  frame_targets (B, T, n_frame, 7); posture / CoM targets held for the whole call, (n, w), or (B, T, n, w).  The
+        handle needs max_batch >= n_seeds; B·T·n_seeds loops beyond max_batch run in chunks of whole rungs.  numpy in → numpy
+        out (synchronous); torch CUDA tensors in → torch tensors out on the current stream, no host copy."""
+        if seeds is not None and seed_table is not None:
+            raise ValueError("seeds and seed_table are two sources of the same starts: pass one of them")
+        m = self.nmodel.model
+        B, S, max_iters = int(q.shape[0]), int(n_seeds), int(max_iters)
+        if max_iters < 1:
+            raise ValueError("max_iters must be >= 1")
+        if qvel_dt is not None and not float(qvel_dt) > 0.0:
+            raise ValueError("qvel_dt must be > 0")
+        if not (float(pos_threshold) >= 0.0 and float(ori_threshold) >= 0.0):
+            raise ValueError("thresholds must be >= 0: a ladder's rungs run in threshold mode only")
+        if self.n_dense_rows or self.n_dense_limit_rows or self.dense_limit_box:
+            raise ValueError("dense (plugin) rows are evaluated by the caller at q: no fused loop, no ladder")
+        if not self.n_frame:
+            raise ValueError("a ladder needs at least one frame task to test the thresholds on")
+        if frame_targets is None or len(frame_targets.shape) != 4:
+            raise ValueError(f"frame_targets must have shape (B, T, {self.n_frame}, 7)")
+        T = int(frame_targets.shape[1])
+        check_ladder_shape(S, T, float(max_step_sq))
+        if S > self.max_batch:
+            raise MinkHipError(f"n_seeds={S} exceeds max_batch={self.max_batch} of this problem")
+        flags = (FLAG_WAVE_KERNEL if wave_kernel else 0) | (FLAG_LANE_KERNEL if lane_kernel else 0) | \
+            (FLAG_QUAD_KERNEL if quad_kernel else 0)
+        prep, empty, ptr, stream, devp = _call_kit(q)
+        flags |= devp
+        q, frame_targets, posture_target, com_target = prep(q), prep(frame_targets), prep(posture_target), prep(com_target)
+        seeds, weights = prep(seeds), prep(weights)
+        if tuple(q.shape) != (B, m.nq):
+            raise ValueError(f"q must have shape (B, {m.nq}), got {tuple(q.shape)}")
+        if tuple(frame_targets.shape) != (B, T, self.n_frame, 7):
+            raise ValueError(f"frame_targets must have shape ({B}, T, {self.n_frame}, 7), got {tuple(frame_targets.shape)}")
+
+        def held_or_rows(x, n, w, name, flag):
+            if x is None:
+                raise ValueError(f"{name} is required")
+            if tuple(x.shape) == (n, w):
+                return 0
+            if tuple(x.shape) == (B, T, n, w):
+                return flag
+            raise ValueError(f"{name} must have shape ({n}, {w}) or ({B}, {T}, {n}, {w}), got {tuple(x.shape)}")
+
+        if self.n_posture:
+            flags |= held_or_rows(posture_target, self.n_posture, m.nq, "posture_target", FLAG_POSTURE_BATCHED)
+        if self.n_com:
+            flags |= held_or_rows(com_target, self.n_com, 3, "com_target", FLAG_COM_BATCHED)
+        if seeds is not None and tuple(seeds.shape) != (B, T, S, m.nq):
+            raise ValueError(f"seeds must have shape ({B}, {T}, {S}, {m.nq}), got {tuple(seeds.shape)}")
+        if weights is not None and tuple(weights.shape) != (m.nv,):
+            raise ValueError(f"weights must have shape ({m.nv},), got {tuple(weights.shape)}")
+        f8, i4 = np.float64, np.int32
+        out = {"q_traj": empty((B, T, m.nq), f8), "v_traj": empty((B, T, m.nv), f8), "status": empty((B, T), i4),
+               "iters": empty((B, T), i4), "converged": empty((B, T), i4), "node_index": empty((B, T), i4),
+               "n_tracked": empty((B,), i4), "n_breaks": empty((B,), i4), "path_length": empty((B,), f8),
+               "edge_break": empty((B, T), i4), "qvel": empty((B, T, m.nv), f8) if qvel_dt is not None else None}
+        every = dict.fromkeys(("q_all", "v_all", "status_all", "iters_all", "converged_all", "seeds_out"))
+        if return_all:
+            every = {"q_all": empty((B, T, S, m.nq), f8), "v_all": empty((B, T, S, m.nv), f8), "status_all": empty((B, T, S), i4),
+                     "iters_all": empty((B, T, S), i4), "converged_all": empty((B, T, S), i4),
+                     "seeds_out": empty((B, T, S, m.nq), f8)}
+        io = MkhTrajectoryLadderIO()
+        io.seeds, io.weights, io.max_step_sq = ptr(seeds), ptr(weights), float(max_step_sq)
+        io.waypoint_dt = float(qvel_dt) if qvel_dt is not None else 0.0
+        for n, x in {**out, **every}.items():
+            setattr(io, n, ptr(x))
+        with self._lock, _attached(self, seed_table):
+            _check(lib().mkh_solve_trajectory_ladder(self.handle, B, T, S, ptr(q), ptr(frame_targets), ptr(posture_target),
+                                                     ptr(com_target), float(dt), float(damping), max_iters, float(pos_threshold),
+                                                     float(ori_threshold), int(rng_seed) & (2 ** 64 - 1), int(target_index0),
+                                                     C.byref(io), flags, stream))
+        return TrajectoryLadderOut(*[out[n] for n in ("q_traj", "v_traj", "status", "iters", "converged", "node_index", "n_tracked",
+                                                       "n_breaks", "path_length", "edge_break", "qvel")],
+                                   *[every[n] for n in ("q_all", "v_all", "status_all", "iters_all", "converged_all", "seeds_out")])
 
     def _solve_trajectory(self, q, frame_targets, posture_target, com_target, dt, damping, n_steps, until, qvel_dt, tm,
                           warm_start, wave_kernel, lane_kernel, quad_kernel, keys=None, cands=None):

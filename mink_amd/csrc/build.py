@@ -321,6 +321,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     jobs.append((os.path.join(HERE, "trajectory.hip"), os.path.join(BUILD, "trajectory.o")))   # layout transposes / waypoint velocity of mkh_solve_trajectory
     jobs.append((os.path.join(HERE, "keyframes.hip"), os.path.join(BUILD, "keyframes.o")))     # target blends between keyframes of mkh_solve_keyframes
     jobs.append((os.path.join(HERE, "trajectory_multistart.hip"), os.path.join(BUILD, "trajectory_multistart.o")))   # path scoring / selection / gather of mkh_solve_trajectory_multistart
+    jobs.append((os.path.join(HERE, "ladder.hip"), os.path.join(BUILD, "ladder.o")))   # dynamic program / back-trace / gather of mkh_ladder_select and mkh_solve_trajectory_ladder
 
     def compile_one(job):
         src, obj = job

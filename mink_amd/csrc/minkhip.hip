@@ -152,6 +152,10 @@ enum WsRole {
   // per row; OUT_PICK: the per-instance integers of a selection; OUT_LEN: path lengths; OUT_FT / PT / CT: the interpolated
   // targets a keyframed call was asked for — the only buffers of a call's targets that grow with T)
   WS_OUT_Q, WS_OUT_V, WS_OUT_I32, WS_OUT_QVEL, WS_OUT_PICK, WS_OUT_LEN, WS_OUT_FT, WS_OUT_PT, WS_OUT_CT,
+  // a ladder: the (B, T, S, .) node rows (one buffer per array, so that a caller's *_all array replaces its own), the tracked
+  // flags, the starts a host caller asked for, q fanned out to the (B·T) targets of the multi-start launch, and the search's
+  // break masks | back-pointers
+  WS_L_Q, WS_L_V, WS_L_ST, WS_L_IT, WS_L_CV, WS_L_TRK, WS_L_STARTS, WS_L_Q0, WS_L_PRED,
   WS_COUNT
 };
 
@@ -1478,18 +1482,20 @@ int32_t mkh_problem_set_seed_table(MkhProblem* p, const MkhSeedTable* table) {
   return MKH_OK;
 }
 
-int32_t mkh_solve_multistart(MkhProblem* p, int32_t B, const double* q, const double* frame_targets,
-                             const double* posture_target, const double* com_target, double dt, double damping,
-                             int32_t max_iters, double pos_threshold, double ori_threshold, int32_t n_seeds,
-                             uint64_t rng_seed, int64_t target_index0, const MkhMultistartIO* io, int32_t flags,
-                             void* hip_stream) {
+// mkh_solve_multistart, and the rungs of mkh_solve_trajectory_ladder: with `rungs_v` (device, (B·S, nv)) the loops' velocities go
+// there and the call ends behind the loop — no selection, io's per-target outputs are not read.
+static int32_t multistart_core(MkhProblem* p, int32_t B, const double* q, const double* frame_targets,
+                               const double* posture_target, const double* com_target, double dt, double damping,
+                               int32_t max_iters, double pos_threshold, double ori_threshold, int32_t n_seeds,
+                               uint64_t rng_seed, int64_t target_index0, const MkhMultistartIO* io, int32_t flags,
+                               void* hip_stream, double* rungs_v) {
   if (!p) return fail(MKH_E_INVALID, "null problem");
   if (B < 1) return fail(MKH_E_INVALID, "B must be >= 1");
   if (n_seeds < 1) return fail(MKH_E_INVALID, "n_seeds must be >= 1");
   if (max_iters < 1) return fail(MKH_E_INVALID, "max_iters must be >= 1");
   if (target_index0 < 0) return fail(MKH_E_INVALID, "target_index0 must be >= 0");
   if (!(pos_threshold >= 0.0) || !(ori_threshold >= 0.0)) return fail(MKH_E_INVALID, "thresholds must be >= 0");
-  if (!io || !io->q_best || !io->v_best || !io->iters || !io->status || !io->converged || !io->seed_index || !io->n_converged)
+  if (!io || (!rungs_v && (!io->q_best || !io->v_best || !io->iters || !io->status || !io->converged || !io->seed_index || !io->n_converged)))
     return fail(MKH_E_INVALID, "io and its per-target outputs (q_best, v_best, iters, status, converged, seed_index, n_converged) are required");
   const DeviceProblem& P = p->dev;
   if (const int32_t rc = refuse_inputs(P, q, frame_targets, posture_target, com_target, "mkh_solve_multistart", "multi-start"))
@@ -1522,7 +1528,7 @@ int32_t mkh_solve_multistart(MkhProblem* p, int32_t B, const double* q, const do
   const double* d_user = st.up(WS_IN_SEEDS, io->seeds, Nz * nq);             // (the seed kernel reads them once)
   // ---- workspace of the B·S instances: the caller's *_all arrays where they are device buffers
   double* const c_q = st.f64(WS_C_Q, Nz * nq);
-  double* const c_v = st.f64(WS_C_V, Nz * nv);
+  double* const c_v = rungs_v ? rungs_v : st.f64(WS_C_V, Nz * nv);
   int32_t* const d_status = (int32_t*)st.given_or(WS_C_ST, io->status_all, Nz * i4);
   int32_t* const d_iters = (int32_t*)st.given_or(WS_C_IT, io->iters_all, Nz * i4);
   int32_t* const d_conv = (int32_t*)st.given_or(WS_C_CV, io->converged_all, Nz * i4);
@@ -1556,6 +1562,7 @@ int32_t mkh_solve_multistart(MkhProblem* p, int32_t B, const double* q, const do
   if (const int32_t rc = run(p, (int32_t)N, d_seeds, c_ft, d_pt, d_ct, dt, damping, c_v, d_status, nullptr, loop_flags, hip_stream,
                              max_iters, d_q_all, nullptr, pos_threshold, ori_threshold, d_iters, d_conv))
     return st.finish(rc);
+  if (rungs_v) return st.finish();
   // ---- selection
   double *o_q = io->q_best, *o_v = io->v_best;
   int32_t *o_it = io->iters, *o_st = io->status, *o_cv = io->converged, *o_si = io->seed_index, *o_nc = io->n_converged;
@@ -1580,6 +1587,15 @@ int32_t mkh_solve_multistart(MkhProblem* p, int32_t B, const double* q, const do
   st.down(io->converged_all, d_conv, Nz * i4);
   st.down(io->seeds_out, kept_seeds, Nz * nq * f8);
   return st.finish();
+}
+
+int32_t mkh_solve_multistart(MkhProblem* p, int32_t B, const double* q, const double* frame_targets,
+                             const double* posture_target, const double* com_target, double dt, double damping,
+                             int32_t max_iters, double pos_threshold, double ori_threshold, int32_t n_seeds,
+                             uint64_t rng_seed, int64_t target_index0, const MkhMultistartIO* io, int32_t flags,
+                             void* hip_stream) {
+  return multistart_core(p, B, q, frame_targets, posture_target, com_target, dt, damping, max_iters, pos_threshold, ori_threshold,
+                         n_seeds, rng_seed, target_index0, io, flags, hip_stream, nullptr);
 }
 
 }  // extern "C"
@@ -1938,6 +1954,196 @@ int32_t mkh_solve_trajectory_multistart(MkhProblem* p, int32_t B, int32_t T, int
   }
   return trajectory_core(p, B, T, q, frame_targets, posture_target, com_target, dt, damping, n_steps, pos_threshold, ori_threshold,
                          io ? &tio : nullptr, flags, hip_stream, nullptr, &cs, "mkh_solve_trajectory_multistart");
+}
+
+// ---- ladder-graph trajectory IK (include/minkhip.h "THE RULE"; kernels: ladder.hip)
+// What both ladder entry points refuse about the graph's shape and gate.
+static int32_t ladder_refuse(const MkhProblem* p, int32_t B, int32_t T, int32_t S, double max_step_sq, const char* who) {
+  if (B < 1) return fail(MKH_E_INVALID, "%s: B = %d must be >= 1", who, B);
+  if (T < 1) return fail(MKH_E_INVALID, "%s: T = %d must be >= 1", who, T);
+  if (S < 1) return fail(MKH_E_INVALID, "%s: S = %d must be >= 1", who, S);
+  if (S > 256) return fail(MKH_E_LIMIT, "%s: S = %d nodes per rung, at most 256 (back-pointers are bytes)", who, S);
+  if (T > 65535) return fail(MKH_E_LIMIT, "%s: T = %d waypoints, at most 65535", who, T);
+  if (!(max_step_sq >= 0.0)) return fail(MKH_E_INVALID, "%s: max_step_sq = %g must be >= 0 (+inf: no gate)", who, max_step_sq);
+  if (ladder_source_tile(S, p->dev.nq, p->dev.nv, p->model->njnt, nullptr) < 1)
+    return fail(MKH_E_LIMIT, "%s: nq = %d: one destination tile and one source node do not fit 64 KB of LDS", who, p->dev.nq);
+  if ((long long)B * T > 0x7fffffffLL) return fail(MKH_E_LIMIT, "%s: B * T = %lld rows", who, (long long)B * T);
+  return MKH_OK;
+}
+
+// The search on device arrays, into device outputs, on the call's stream.
+static void ladder_search(Stager& st, int B, int T, int S, const double* d_q, const double* d_nodes, const int32_t* d_tracked,
+                          const double* d_w, double max_step_sq, int32_t* o_node, int32_t* o_nt, int32_t* o_nb, double* o_len,
+                          int32_t* o_eb) {
+  const MkhProblem* const p = st.p;
+  const size_t R = (size_t)B * T, nch = ((size_t)S + 63) / 64;
+  unsigned long long* const brk = (unsigned long long*)st.need(WS_L_PRED, R * nch * 8 + R * S);
+  uint8_t* const pred = (uint8_t*)(brk + R * nch);
+  ST_LAUNCH(st, launch_ladder_search(st.stream, B, T, S, p->dev.nq, p->dev.nv, p->model->njnt, p->ws[WS_JNT].i32(), d_q, d_nodes, d_tracked, d_w,
+                                     max_step_sq, pred, brk, o_node, o_nt, o_nb, o_len, o_eb));
+}
+
+static int32_t ladder_weights_refuse(const double* w, int nv, const char* who) {
+  for (int k = 0; w && k < nv; ++k)
+    if (!(w[k] >= 0.0)) return fail(MKH_E_INVALID, "%s: weights[%d] = %g: the weights of the edge cost must be >= 0", who, k, w[k]);
+  return MKH_OK;
+}
+
+int32_t mkh_ladder_select(MkhProblem* p, int32_t B, int32_t T, int32_t S, const double* q, const double* q_nodes,
+                          const int32_t* tracked, const double* weights, double max_step_sq, const MkhLadderIO* io, int32_t flags,
+                          void* hip_stream) {
+  const char* const who = "mkh_ladder_select";
+  if (!p) return fail(MKH_E_INVALID, "null problem");
+  if (const int32_t rc = ladder_refuse(p, B, T, S, max_step_sq, who)) return rc;
+  if (!q || !q_nodes || !tracked) return fail(MKH_E_INVALID, "%s: q, q_nodes and tracked are required", who);
+  if (!io || !io->node_index || !io->n_tracked || !io->n_breaks || !io->path_length || !io->edge_break)
+    return fail(MKH_E_INVALID, "%s: io and its outputs node_index, n_tracked, n_breaks, path_length, edge_break are required", who);
+  const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
+  if (!devp)
+    if (const int32_t rc = ladder_weights_refuse(weights, p->dev.nv, who)) return rc;
+  HIP_OK(hipSetDevice(p->model->device));
+  if (const int32_t rc = ms_build_tables(p)) return rc;
+  Stager st{p, (hipStream_t)hip_stream, devp, "ladder_select"};
+  const size_t Bz = B, R = Bz * T, N = R * S, nq = p->dev.nq, f8 = sizeof(double), i4 = sizeof(int32_t);
+  const double* const d_q = st.up(WS_IN_Q, q, Bz * nq);
+  const double* const d_nodes = st.up(WS_L_Q, q_nodes, N * nq);
+  const double* const d_w = st.up(WS_IN_W, weights, p->dev.nv);
+  const int32_t* d_trk = tracked;
+  if (!devp) {
+    int32_t* const t = st.i32(WS_L_TRK, N);
+    if (t) st.latch(hipMemcpyAsync(t, tracked, N * i4, hipMemcpyHostToDevice, st.stream));
+    d_trk = t;
+  }
+  int32_t *o_node = io->node_index, *o_eb = io->edge_break, *o_nt = io->n_tracked, *o_nb = io->n_breaks;
+  double *o_len = io->path_length, *o_q = io->q_path;
+  if (!devp) {
+    o_node = st.i32(WS_OUT_PICK, 2 * R + 2 * Bz); o_eb = o_node + R; o_nt = o_node + 2 * R; o_nb = o_nt + Bz;
+    o_len = st.f64(WS_OUT_LEN, Bz);
+    o_q = io->q_path ? st.f64(WS_OUT_Q, R * nq) : nullptr;
+  }
+  if (!st.ok()) return st.finish();
+  ladder_search(st, B, T, S, d_q, d_nodes, d_trk, d_w, max_step_sq, o_node, o_nt, o_nb, o_len, o_eb);
+  if (o_q) ST_LAUNCH(st, launch_ladder_gather(st.stream, d_nodes, o_q, o_node, (long long)R, S, (int)nq));
+  if (devp) return st.finish();
+  st.down(io->node_index, o_node, R * i4);
+  st.down(io->edge_break, o_eb, R * i4);
+  st.down(io->n_tracked, o_nt, Bz * i4);
+  st.down(io->n_breaks, o_nb, Bz * i4);
+  st.down(io->path_length, o_len, Bz * f8);
+  st.down(io->q_path, o_q, R * nq * f8);
+  return st.finish();
+}
+
+int32_t mkh_solve_trajectory_ladder(MkhProblem* p, int32_t B, int32_t T, int32_t n_seeds, const double* q,
+                                    const double* frame_targets, const double* posture_target, const double* com_target, double dt,
+                                    double damping, int32_t max_iters, double pos_threshold, double ori_threshold, uint64_t rng_seed,
+                                    int64_t target_index0, const MkhTrajectoryLadderIO* io, int32_t flags, void* hip_stream) {
+  const char* const who = "mkh_solve_trajectory_ladder";
+  if (!p) return fail(MKH_E_INVALID, "null problem");
+  if (!io) return fail(MKH_E_INVALID, "%s: io is required", who);
+  const int S = n_seeds;
+  if (const int32_t rc = ladder_refuse(p, B, T, S, io->max_step_sq, who)) return rc;
+  if (max_iters < 1) return fail(MKH_E_INVALID, "max_iters must be >= 1");
+  if (target_index0 < 0) return fail(MKH_E_INVALID, "target_index0 must be >= 0");
+  if (!(dt > 0.0)) return fail(MKH_E_INVALID, "dt must be > 0");
+  if (!(pos_threshold >= 0.0) || !(ori_threshold >= 0.0))
+    return fail(MKH_E_INVALID, "%s: thresholds must be >= 0 (a fixed count leaves no tracked flag to search on)", who);
+  if (!io->q_traj || !io->v_traj || !io->status || !io->iters || !io->converged || !io->node_index || !io->n_tracked ||
+      !io->n_breaks || !io->path_length || !io->edge_break)
+    return fail(MKH_E_INVALID, "%s: io's outputs q_traj, v_traj, status, iters, converged, node_index, n_tracked, n_breaks, path_length, "
+                               "edge_break are required", who);
+  if (io->qvel && !(io->waypoint_dt > 0.0)) return fail(MKH_E_INVALID, "qvel needs waypoint_dt > 0");
+  const DeviceProblem& P = p->dev;
+  if (const int32_t rc = refuse_inputs(P, q, frame_targets, posture_target, com_target, who, "ladder")) return rc;
+  if (S > p->max_batch) return fail(MKH_E_INVALID, "%s: n_seeds = %d exceeds max_batch=%d of this problem (a rung is one chunk)", who, S, p->max_batch);
+  const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
+  if (!devp)
+    if (const int32_t rc = ladder_weights_refuse(io->weights, P.nv, who)) return rc;
+  const MkhSeedTable* const tab = (!io->seeds && S > 1) ? p->seed_table : nullptr;
+  if (tab)
+    if (const int32_t rc = st_refuse(p, tab, S - 1, who)) return rc;
+  HIP_OK(hipSetDevice(p->model->device));
+  if (const int32_t rc = ms_build_tables(p)) return rc;
+  const bool pbat = (flags & MKH_FLAG_POSTURE_BATCHED) != 0, cbat = (flags & MKH_FLAG_COM_BATCHED) != 0;
+  Stager st{p, (hipStream_t)hip_stream, devp, "trajectory_ladder"};
+  hipStream_t stream = st.stream;
+  const size_t Bz = B, R = Bz * T, N = R * S, nq = P.nq, nv = P.nv, f8 = sizeof(double), i4 = sizeof(int32_t);
+  const size_t ft_w = (size_t)P.n_frame * 7, pt_w = (size_t)P.n_posture * nq, ct_w = (size_t)P.n_com * 3;
+  // ---- inputs on the device; q once per (instance, waypoint): the flattened targets' "current posture"
+  const double* const d_q = st.up(WS_IN_Q, q, Bz * nq);
+  const double* const d_ft = st.up(WS_IN_FT, frame_targets, R * ft_w);
+  const double* const d_pt = pt_w ? st.up(WS_IN_PT, posture_target, pt_w * (pbat ? R : 1)) : posture_target;
+  const double* const d_ct = ct_w ? st.up(WS_IN_CT, com_target, ct_w * (cbat ? R : 1)) : com_target;
+  const double* const d_w = st.up(WS_IN_W, io->weights, nv);
+  const double* const d_user = st.up(WS_IN_SEEDS, io->seeds, N * nq);
+  double* const d_q0 = st.f64(WS_L_Q0, R * nq);
+  ST_LAUNCH(st, launch_ms_fanout(stream, d_q, d_q0, B, T, (int)nq));
+  // ---- the nodes: the caller's *_all arrays where they are device buffers
+  double* const l_q = (double*)st.given_or(WS_L_Q, io->q_all, N * nq * f8);
+  double* const l_v = (double*)st.given_or(WS_L_V, io->v_all, N * nv * f8);
+  int32_t* const l_st = (int32_t*)st.given_or(WS_L_ST, io->status_all, N * i4);
+  int32_t* const l_it = (int32_t*)st.given_or(WS_L_IT, io->iters_all, N * i4);
+  int32_t* const l_cv = (int32_t*)st.given_or(WS_L_CV, io->converged_all, N * i4);
+  int32_t* const l_trk = st.i32(WS_L_TRK, N);
+  double* const l_starts = io->seeds_out ? (double*)st.given_or(WS_L_STARTS, io->seeds_out, N * nq * f8) : nullptr;
+  // ---- outputs
+  double *o_q = io->q_traj, *o_v = io->v_traj, *o_qvel = io->qvel, *o_len = io->path_length;
+  int32_t *o_st = io->status, *o_it = io->iters, *o_cv = io->converged;
+  int32_t *o_node = io->node_index, *o_eb = io->edge_break, *o_nt = io->n_tracked, *o_nb = io->n_breaks;
+  if (!devp) {
+    o_q = st.f64(WS_OUT_Q, R * nq); o_v = st.f64(WS_OUT_V, R * nv);
+    o_qvel = io->qvel ? st.f64(WS_OUT_QVEL, R * nv) : nullptr;
+    o_st = st.i32(WS_OUT_I32, 3 * R); o_it = o_st + R; o_cv = o_st + 2 * R;
+    o_node = st.i32(WS_OUT_PICK, 2 * R + 2 * Bz); o_eb = o_node + R; o_nt = o_node + 2 * R; o_nb = o_nt + Bz;
+    o_len = st.f64(WS_OUT_LEN, Bz);
+  }
+  if (!st.ok()) return st.finish();
+  // ---- the rungs: multi-start on the (B·T) flattened targets, whole rungs per chunk of at most max_batch loops
+  const size_t per = (size_t)p->max_batch / S;
+  const int32_t ms_flags = flags | MKH_FLAG_DEVICE_PTRS;
+  for (size_t r0 = 0; r0 < R; r0 += per) {
+    const size_t n = R - r0 < per ? R - r0 : per, i0 = r0 * S;
+    MkhMultistartIO mio;
+    memset(&mio, 0, sizeof mio);
+    mio.seeds = d_user ? d_user + i0 * nq : nullptr;
+    mio.q_all = l_q + i0 * nq; mio.status_all = l_st + i0; mio.iters_all = l_it + i0; mio.converged_all = l_cv + i0;
+    mio.seeds_out = l_starts ? l_starts + i0 * nq : nullptr;
+    if (const int32_t rc = multistart_core(p, (int32_t)n, d_q0 + r0 * nq, d_ft + r0 * ft_w, (pt_w && pbat) ? d_pt + r0 * pt_w : d_pt,
+                                           (ct_w && cbat) ? d_ct + r0 * ct_w : d_ct, dt, damping, max_iters, pos_threshold,
+                                           ori_threshold, S, rng_seed, target_index0 * T + (int64_t)r0, &mio, ms_flags, hip_stream,
+                                           l_v + i0 * nv))
+      return st.finish(rc);
+  }
+  // ---- the search, and the chosen nodes' rows
+  ST_LAUNCH(st, launch_ladder_tracked(stream, l_cv, l_st, (long long)N, l_trk));
+  ladder_search(st, B, T, S, d_q, l_q, l_trk, d_w, io->max_step_sq, o_node, o_nt, o_nb, o_len, o_eb);
+  ST_LAUNCH(st, launch_ladder_gather(stream, l_q, o_q, o_node, (long long)R, S, (int)nq));
+  ST_LAUNCH(st, launch_ladder_gather(stream, l_v, o_v, o_node, (long long)R, S, (int)nv));
+  ST_LAUNCH(st, launch_ladder_gather_i32(stream, l_st, o_st, o_node, (long long)R, S));
+  ST_LAUNCH(st, launch_ladder_gather_i32(stream, l_it, o_it, o_node, (long long)R, S));
+  ST_LAUNCH(st, launch_ladder_gather_i32(stream, l_cv, o_cv, o_node, (long long)R, S));
+  if (o_qvel)
+    ST_LAUNCH(st, launch_tj_qvel(stream, p->ws[WS_JNT].i32(), p->model->njnt, B, T, (int)nq, d_q, o_q, (long long)(T * nq), (long long)nq,
+                                 io->waypoint_dt, o_qvel, (long long)(T * nv), (long long)nv, 0));
+  if (devp) return st.finish();
+  st.down(io->q_traj, o_q, R * nq * f8);
+  st.down(io->v_traj, o_v, R * nv * f8);
+  st.down(io->status, o_st, R * i4);
+  st.down(io->iters, o_it, R * i4);
+  st.down(io->converged, o_cv, R * i4);
+  st.down(io->node_index, o_node, R * i4);
+  st.down(io->edge_break, o_eb, R * i4);
+  st.down(io->n_tracked, o_nt, Bz * i4);
+  st.down(io->n_breaks, o_nb, Bz * i4);
+  st.down(io->path_length, o_len, Bz * f8);
+  st.down(io->qvel, o_qvel, R * nv * f8);
+  st.down(io->q_all, l_q, N * nq * f8);
+  st.down(io->v_all, l_v, N * nv * f8);
+  st.down(io->status_all, l_st, N * i4);
+  st.down(io->iters_all, l_it, N * i4);
+  st.down(io->converged_all, l_cv, N * i4);
+  st.down(io->seeds_out, l_starts, N * nq * f8);
+  return st.finish();
 }
 
 int32_t mkh_integrate(MkhModel* m, int32_t B, const double* q, const double* v, double dt, double* q_out,

@@ -1,9 +1,10 @@
 // Launchers of the small kernels around the loop launches of the outer-loop entry points (mkh_solve_multistart,
-// mkh_solve_trajectory, mkh_solve_keyframes, mkh_solve_trajectory_multistart) and of the seed tables in front of them: declared
-// once, for the five files that define them and for minkhip.hip, which calls them — a signature that drifts fails to compile in
-// the file that drifted.
+// mkh_solve_trajectory, mkh_solve_keyframes, mkh_solve_trajectory_multistart, the two ladder calls) and of the seed tables in
+// front of them: declared once, for the six files that define them and for minkhip.hip, which calls them — a signature that
+// drifts fails to compile in the file that drifted.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstddef>
 #include <cstdint>
 
 namespace mkh {
@@ -58,5 +59,20 @@ hipError_t launch_tms_gather_i32(hipStream_t stream, const int32_t* all, int32_t
 hipError_t launch_st_keys(hipStream_t stream, const double* poses, int n, int n_frame, long long N, long long j0, double* keys);
 hipError_t launch_st_query(hipStream_t stream, const double* keys, const double* q_tab, const double* weights, int N, int n_frame,
                            int nq, int B, const double* targets, int K, int32_t* index_out, double* dist_out, double* seeds_out);
+// ladder-graph trajectory IK (ladder.hip): nodes tracked or not from the loops' flags, the dynamic program over the (B, T, S, nq)
+// nodes with its back-trace (pred: B·T·S bytes; brk: B·T·ceil(S / 64) break masks), and the chosen nodes' rows of a (rows, S, W)
+// array gathered through node_index (rows = B·T).  ladder_source_tile: the source nodes per LDS tile of a search launch (0: the
+// model does not fit) and the launch's LDS bytes.
+int ladder_source_tile(int S, int nq, int nv, int njnt, size_t* lds_bytes);
+hipError_t launch_ladder_tracked(hipStream_t stream, const int32_t* converged, const int32_t* status, long long total,
+                                 int32_t* tracked);
+hipError_t launch_ladder_search(hipStream_t stream, int B, int T, int S, int nq, int nv, int njnt, const int32_t* jnt,
+                                const double* q0, const double* q_nodes, const int32_t* tracked, const double* weights, double max_step_sq,
+                                uint8_t* pred, unsigned long long* brk, int32_t* node_index, int32_t* n_tracked, int32_t* n_breaks,
+                                double* path_length, int32_t* edge_break);
+hipError_t launch_ladder_gather(hipStream_t stream, const double* all, double* out, const int32_t* node_index, long long rows, int S,
+                                int W);
+hipError_t launch_ladder_gather_i32(hipStream_t stream, const int32_t* all, int32_t* out, const int32_t* node_index, long long rows,
+                                    int S);
 
 }  // namespace mkh

@@ -918,6 +918,170 @@ def solve_ik_trajectory_multistart(configuration: Configuration, tasks: Sequence
                                       opt(res.converged_all, True), opt(res.seeds))
 
 
+class LadderResult(NamedTuple):
+    """Result of solve_ik_trajectory_ladder.  The chosen path, (B, T, ·) — (T, ·) for an unbatched configuration —: `q`, `v`,
+    `status`, `iters`, `converged` of the chosen node of every waypoint; `node_index` (B, T) its index in the rung and
+    `edge_break` (B, T) whether the step into the waypoint exceeds max_step (entry 0: never); per instance `n_tracked` (waypoints
+    whose chosen node converged without a QP failure), `n_breaks` and `path_length`; `qvel` when waypoint_dt was given.  With
+    return_all every node's `q_all` (B, T, S, nq), `v_all` (B, T, S, nv), `status_all`, `iters_all`, `converged_all` (B, T, S)
+    and the `seeds` (B, T, S, nq) the loops started from; None otherwise."""
+    q: np.ndarray
+    v: np.ndarray
+    status: np.ndarray
+    iters: np.ndarray
+    converged: np.ndarray
+    node_index: np.ndarray
+    n_tracked: np.ndarray
+    n_breaks: np.ndarray
+    path_length: np.ndarray
+    edge_break: np.ndarray
+    qvel: Optional[np.ndarray] = None
+    q_all: Optional[np.ndarray] = None
+    v_all: Optional[np.ndarray] = None
+    status_all: Optional[np.ndarray] = None
+    iters_all: Optional[np.ndarray] = None
+    converged_all: Optional[np.ndarray] = None
+    seeds: Optional[np.ndarray] = None
+
+
+class LadderPath(NamedTuple):
+    """Result of ladder_path: the chosen `node_index` (B, T), the nodes along it `q` (B, T, nq), `edge_break` (B, T), and per
+    instance `n_tracked`, `n_breaks`, `path_length` — without the leading axis for an unbatched configuration."""
+    node_index: np.ndarray
+    q: np.ndarray
+    n_tracked: np.ndarray
+    n_breaks: np.ndarray
+    path_length: np.ndarray
+    edge_break: np.ndarray
+
+
+def _max_step_sq(max_step) -> float:
+    """The squared gate of the ladder's break rule from the caller's joint-space step (None: no gate)."""
+    if max_step is None:
+        return float("inf")
+    max_step = float(max_step)
+    if not max_step >= 0.0:
+        raise ValueError(f"max_step must be >= 0 (None: no gate), got {max_step}")
+    return max_step * max_step
+
+
+def _ladder_weights(weights, nv: int):
+    weights = _optional_array(weights, "weights", (nv,))
+    if weights is not None and not (weights >= 0.0).all():
+        raise ValueError("weights must be >= 0 (no NaN): an edge cost is a sum of non-negative terms")
+    return weights
+
+
+def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt: float, targets, n_seeds: int, max_iters: int,
+                               pos_threshold: float, ori_threshold: float, max_step: Optional[float] = None, weights=None,
+                               seeds=None, seed_table: Optional["SeedTable"] = None, rng_seed: int = 0,
+                               qvel_dt: Optional[float] = None, return_all: bool = False, update: bool = True,
+                               max_instances: int = 1 << 20, damping: float = 1e-12, limits: Optional[Sequence] = None,
+                               safety_break: bool = False, solver: str = "mi355x") -> LadderResult:
+    """Track a time sequence of targets through a ladder graph: `n_seeds` IK solutions per waypoint, solved independently of
+    each other, and a dynamic program on the device that picks one per waypoint — the path that is complete first, free of
+    joint-space jumps second and shortest third (the rule in full: include/minkhip.h).  Where solve_ik_trajectory_multistart
+    keeps one whole candidate, the ladder may change IK branch at every waypoint.
+
+    `targets` as in solve_ik_trajectory (no keyframes).  Rung t of instance b is solve_ik_multistart's set of solutions for
+    waypoint t's targets from the configuration's own q[b]: seed 0 is q[b], the others are drawn by the stateless generator at
+    target index b·T + t, taken from `seeds` — (S, nq), (T, S, nq) or (B, T, S, nq) — or from `seed_table`, queried with every
+    waypoint's own frame targets.  A node is tracked when its loop converged without a QP failure.
+
+    An edge costs Σ_k weights_k·(q_t ⊖ q_{t−1})_k² (the first one from the configuration's q); it is a break when that exceeds
+    max_step² (`max_step` None: never).  A path's key is (untracked nodes, breaks, length), compared in that order; ties go to
+    the lowest node index.  Limits warnings and SolverError follow solve_ik_trajectory's rules on the CHOSEN nodes only
+    (`safety_break`, as in mink: False keeps going — the warning — where True raises NotWithinConfigurationLimits).  With
+    `update` the configuration is left at the chosen q[:, -1].  The instances are walked in chunks of as many as keep
+    chunk·T·n_seeds within `max_instances`; a multi-device configuration shards by instance; the result depends on neither."""
+    del solver
+    S, max_iters = int(n_seeds), int(max_iters)
+    if max_iters < 1:
+        raise ValueError("max_iters must be >= 1")
+    if int(max_instances) < 1:
+        raise ValueError("max_instances must be >= 1")
+    if qvel_dt is not None and not float(qvel_dt) > 0.0:
+        raise ValueError("qvel_dt must be > 0")
+    if pos_threshold is None or ori_threshold is None or not (float(pos_threshold) >= 0.0 and float(ori_threshold) >= 0.0):
+        raise ValueError("thresholds must be >= 0: a ladder's rungs run in threshold mode only")
+    step_sq = _max_step_sq(max_step)
+    # (judged on the objects themselves: the handle's layout says the same, but only once a handle exists)
+    _refuse_plugin_rows({"dense": [t for t in tasks if t._is_dense()], "dense_limits": [x for x in (limits or ()) if x._is_dense()]},
+                        "solve_ik_trajectory_ladder")
+    B, nq, nv = configuration.batch_size, configuration.nq, configuration.nv
+    seqs, T = _trajectory_targets(configuration, tasks, targets)
+    nat.check_ladder_shape(S, T, step_sq)
+    if S * T > int(max_instances):
+        raise ValueError(f"one instance's ladder has T*n_seeds = {T * S} loops, beyond max_instances = {int(max_instances)}")
+    seeds = _host_array(seeds, "seeds")
+    if seeds is not None:
+        if seeds.shape not in ((S, nq), (T, S, nq), (B, T, S, nq)):
+            raise ValueError(f"seeds must have shape {(S, nq)}, {(T, S, nq)} or {(B, T, S, nq)}, got {seeds.shape}")
+        seeds = np.ascontiguousarray(np.broadcast_to(seeds, (B, T, S, nq)))
+    weights = _ladder_weights(weights, nv)
+    _check_seed_table(seed_table, seeds, configuration, S)
+    handles, layout, chunk, n_dev = _compile_outer(configuration, tasks, limits, dt, "solve_ik_trajectory_ladder", S * T,
+                                                   max_instances)
+    ft, pt, ct = _stacked_targets(configuration, layout, seqs, T)
+    # a batched target that is held over the path gets its T axis: the call takes (n, w) or (B, T, n, w)
+    pt, ct = [x if x is None or x.ndim != 3 else np.ascontiguousarray(np.broadcast_to(x[:, None], (B, T) + x.shape[1:]))
+              for x in (pt, ct)]
+    q = configuration.q_batch
+    kw = dict(n_seeds=S, max_iters=max_iters, pos_threshold=float(pos_threshold), ori_threshold=float(ori_threshold),
+              max_step_sq=step_sq, rng_seed=int(rng_seed), weights=weights, qvel_dt=qvel_dt, return_all=bool(return_all))
+
+    def job(handle, lo, hi):
+        return handle.solve_trajectory_ladder(q[lo:hi], _rows(ft, 0, lo, hi), _rows(pt, 2, lo, hi), _rows(ct, 2, lo, hi), dt,
+                                              damping, target_index0=lo, seeds=_rows(seeds, 0, lo, hi), seed_table=seed_table, **kw)
+
+    res = _join(LadderResult, _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job))
+    if safety_break and ((res.status & nat.ST_OUTSIDE_LIMITS) != 0).any():
+        b, t = (int(x) for x in np.argwhere((res.status & nat.ST_OUTSIDE_LIMITS) != 0)[0])
+        raise exceptions.NotWithinConfigurationLimits(
+            f"solve_ik_trajectory_ladder: the chosen node of (instance, waypoint) = ({b}, {t}) left its configuration limits at "
+            "some fused step")
+    _status_epilogue(res.status, "solve_ik_trajectory_ladder", "chosen path(s)",
+                     "QP failed at {n} of {of} chosen nodes (first: (instance, waypoint) = {first}, status {status})")
+    if update:
+        configuration.update(res.q[:, -1] if configuration.batched else res.q[0, -1])
+    un = configuration._unbatch
+    opt = lambda x, as_bool=False: None if x is None else un(x.astype(bool) if as_bool else x)
+    return LadderResult(un(res.q), un(res.v), un(res.status), un(res.iters), un(res.converged.astype(bool)), un(res.node_index),
+                        un(res.n_tracked), un(res.n_breaks), un(res.path_length), un(res.edge_break.astype(bool)),
+                        opt(res.qvel), opt(res.q_all), opt(res.v_all), opt(res.status_all), opt(res.iters_all),
+                        opt(res.converged_all, True), opt(res.seeds))
+
+
+def ladder_path(configuration: Configuration, q_nodes, tracked=None, max_step: Optional[float] = None, weights=None) -> LadderPath:
+    """The ladder's search alone, over the caller's own rungs (closed-form IK branches, solutions of earlier calls): q_nodes
+    (T, S, nq) or (B, T, S, nq), `tracked` (same leading shape, default: every node counts as tracked), the start edge from the
+    configuration's q.  The rule — key (untracked, breaks, length), ties to the lowest index — is solve_ik_trajectory_ladder's;
+    the configuration is not changed."""
+    from .tasks import PostureTask
+
+    step_sq = _max_step_sq(max_step)
+    B, nq, nv = configuration.batch_size, configuration.nq, configuration.nv
+    q_nodes = _host_array(q_nodes, "q_nodes")
+    if q_nodes is None or q_nodes.ndim not in (3, 4) or q_nodes.shape[-1] != nq or (q_nodes.ndim == 4 and q_nodes.shape[0] != B):
+        raise ValueError(f"q_nodes must have shape (T, S, {nq}) or ({B}, T, S, {nq}), got {None if q_nodes is None else q_nodes.shape}")
+    T, S = q_nodes.shape[-3], q_nodes.shape[-2]
+    nat.check_ladder_shape(S, T, step_sq)
+    q_nodes = np.ascontiguousarray(np.broadcast_to(q_nodes, (B, T, S, nq)))
+    if tracked is not None:
+        tracked = np.asarray(tracked.detach().cpu().numpy() if nat._is_torch(tracked) else tracked)
+        if tracked.shape not in ((T, S), (B, T, S)):
+            raise ValueError(f"tracked must have shape {(T, S)} or {(B, T, S)}, got {tracked.shape}")
+        tracked = np.ascontiguousarray(np.broadcast_to(tracked != 0, (B, T, S)))
+    weights = _ladder_weights(weights, nv)
+    # (the search reads the model's joint table through a problem handle: the smallest one, a posture task, serves)
+    prob, layout = _compile(configuration, [PostureTask(configuration.model, cost=1.0)], None, 1, devices=configuration.devices[:1])
+    with _pin(configuration, layout):
+        out = prob.ladder_select(configuration.q_batch, q_nodes, tracked, step_sq, weights)
+    un = configuration._unbatch
+    return LadderPath(un(out.node_index), un(out.q), un(out.n_tracked), un(out.n_breaks), un(out.path_length),
+                      un(out.edge_break.astype(bool)))
+
+
 def _chunks_and_shards(configuration: Configuration, layout, handles, B: int, chunk: int, n_dev: int, job):
     """[job(handle, lo, hi), ...] over the rows [0, B): chunks of `chunk` rows, each split among the `n_dev` handles of
     _compile_outer, which run side by side.  The one driver of solve_ik_multistart, solve_ik_trajectory and
