@@ -175,7 +175,11 @@ typedef struct MkhComTaskDesc {
 
 /* mink.ConfigurationLimit(model, gain, min_distance_from_limits) —
  * mink/limits/configuration_limit.py:18-67.  lower/upper are the constructor's
- * per-qpos arrays (±mjMAXVAL where unlimited); indices are its dof `indices`. */
+ * per-qpos arrays (±mjMAXVAL where unlimited); indices are its dof `indices`.
+ * A ball joint named by `indices` holds ONE value over its four qpos slots in lower and
+ * in upper, as the constructor writes its range (the kernels rebuild the quaternion
+ * (u, u, u, u) from it): slots that differ fail mkh_problem_create with MKH_E_INVALID.
+ * Up to 4 configuration and 4 velocity limits per problem (MKH_E_LIMIT beyond). */
 typedef struct MkhConfigurationLimitDesc {
   double gain;
   const double *lower /*nq*/, *upper /*nq*/;

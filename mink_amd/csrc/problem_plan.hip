@@ -507,6 +507,15 @@ int32_t validate(const Ctx& c) {
       if (dof < 0 || dof >= m.nv) return fail(MKH_E_INVALID, "configuration limit: dof %d out of range", dof);
       if (m.jnt_type[m.dof_jntid[dof]] == JNT_FREE)
         return fail(MKH_E_INVALID, "configuration limit on free-joint dof %d (the reference skips free joints)", dof);
+      if (m.jnt_type[m.dof_jntid[dof]] == JNT_BALL) {
+        // the kernels rebuild a ball joint's bound as the quaternion (u, u, u, u) from the ONE value its dofs' table entries hold
+        // (the range end, as the reference's constructor fills the joint's four qpos slots): anything else is not evaluated
+        const int qa = m.jnt_qposadr[m.dof_jntid[dof]];
+        for (int s = 1; s < 4; ++s)
+          if (cl.lower[qa + s] != cl.lower[qa] || cl.upper[qa + s] != cl.upper[qa])
+            return fail(MKH_E_INVALID, "configuration limit %d: lower / upper differ over the four qpos slots of the ball joint of dof %d "
+                                       "(one value per ball joint, as the reference's constructor writes its range)", t, dof);
+      }
     }
   }
   for (int t = 0; t < d.n_velocity_limits; ++t) {

@@ -19,6 +19,7 @@ from .flatmodel import JNT_FREE
 
 DEVICE_SOLVERS = ("mi355x", "hip", "quadprog")
 PROBLEM_CACHE_SIZE = 16       # compiled descriptors kept per Configuration (least recently used are destroyed)
+MAX_BOX_TERMS = 4             # ConfigurationLimits / VelocityLimits of one device descriptor (mkh_types.h kMaxBoxTerms)
 
 
 class Problem(NamedTuple):
@@ -84,6 +85,21 @@ def _fold_box_rows(G: np.ndarray, h: np.ndarray):
     return lo, hi, G[:, keep], h[:, keep], bool(single.any())
 
 
+def _fold_velocity_terms(terms):
+    """At most MAX_BOX_TERMS VelocityLimit descriptors: the reference stacks any number (mink/solve_ik.py:25-40); the surplus is
+    folded into the last term as elementwise minima.  Exact, not approximately so: the rows are ±Δq_k ≤ dt·v with dt > 0, and
+    min over terms of dt·v equals dt·(min over terms of v) bitwise (rounding is monotone)."""
+    if len(terms) <= MAX_BOX_TERMS:
+        return terms
+    vmin = {}
+    for t in terms[MAX_BOX_TERMS - 1:]:
+        for k, v in zip(np.asarray(t["indices"]).tolist(), np.asarray(t["limit"], dtype=np.float64).tolist()):
+            vmin[k] = min(vmin.get(k, np.inf), v)
+    idx = sorted(vmin)
+    folded = {"indices": np.array(idx, dtype=np.int64), "limit": np.array([vmin[k] for k in idx], dtype=np.float64)}
+    return list(terms[:MAX_BOX_TERMS - 1]) + [folded]
+
+
 def _dense_inputs(configuration: Configuration, layout, dt: float):
     """Per-call arrays of the plugin route (mkh_solve_dense), None when the call site has no caller-defined rows."""
     if not layout["dense"] and not layout["dense_limits"]:
@@ -146,6 +162,12 @@ def _compile(configuration: Configuration, tasks: Sequence, limits: Optional[Seq
         if kind in ("cfg", "vel") and len(desc["indices"]) == 0:
             continue                                                # inactive Constraint() (solve_ik.py:34)
         groups[kind].append(desc)
+    if len(groups["cfg"]) > MAX_BOX_TERMS:
+        # (no exact fold: the gains differ, and a ball joint's distance to its limit is not monotone in the bound)
+        raise exceptions.LimitDefinitionError(
+            f"{len(groups['cfg'])} ConfigurationLimits in one call; the device evaluates at most {MAX_BOX_TERMS} "
+            f"(merge limits that share a gain into one, with the tighter lower / upper per joint)")
+    groups["vel"] = _fold_velocity_terms(groups["vel"])
     if layout["dense_limits"]:
         # the row count of a plugin limit is only known from what it returns: evaluate once here (dt does not change
         # the shape), keep the rows for this call

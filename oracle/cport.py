@@ -173,6 +173,8 @@ class CProblem:
                 if (a, b) not in _C_PAIR_TYPES:
                     raise TypeError("the C restatement covers plane / sphere / capsule pairs and box / cylinder against "
                                     f"plane / sphere / capsule, not geom types ({a}, {b})")
+        if any(l.lower is not None or l.upper is not None or l.indices is not None for l in cfg):
+            raise TypeError("the C restatement takes a ConfigurationLimit's bounds and indices from the model")
         if cfg and vel and limits.index(cfg[0]) > limits.index(vel[0]):
             raise TypeError("row order: ConfigurationLimit first")
         pr.has_cfg_limit = 1 if cfg else 0

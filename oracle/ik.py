@@ -77,8 +77,14 @@ class ComTaskSpec:
 
 @dataclass
 class ConfigurationLimitSpec:
+    """`lower` / `upper` (nq,) and `indices` (dof ids): the attributes of the same names a caller may overwrite after
+    mink/limits/configuration_limit.py:41-67 has built them (the reference's own tests do: test_configuration_limit.py:142-156);
+    None keeps what the constructor derives from the model."""
     gain: float = 0.95
     min_distance_from_limits: float = 0.0
+    lower: Optional[np.ndarray] = None
+    upper: Optional[np.ndarray] = None
+    indices: Optional[np.ndarray] = None
 
 
 @dataclass
@@ -260,6 +266,12 @@ def configuration_limit_arrays(m, spec: ConfigurationLimitSpec):
         upper[padr:padr + _QW[jt]] = m.jnt_range[jnt, 1] - spec.min_distance_from_limits
         va = int(m.jnt_dofadr[jnt])
         index_list.extend(range(va, va + _DW[jt]))
+    if spec.lower is not None:
+        lower = np.asarray(spec.lower, dtype=np.float64)
+    if spec.upper is not None:
+        upper = np.asarray(spec.upper, dtype=np.float64)
+    if spec.indices is not None:
+        return np.asarray(spec.indices, dtype=np.int64), lower, upper
     return np.array(index_list, dtype=np.int64), lower, upper
 
 

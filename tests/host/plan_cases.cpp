@@ -1,6 +1,8 @@
 // Host-only driver of mink_amd/csrc/problem_plan.hip for tests/test_problem_plan_cpu.py: synthetic models and descriptors that
 // put every fixed-size table of the device descriptor at its edge, planned without a device and printed as one JSON object per
-// line.  Built with the host sanitizers by the test and run as a child process.
+// line — among them lists of 2 to 4 limits of each kind (and 5: refused) whose terms have their own gain, bounds and index subset,
+// printed with every copy of the per-dof tables the plan makes of them.  Built with the host sanitizers by the test and run as a
+// child process.
 #include <cstdio>
 #include <string>
 #include <vector>
@@ -109,13 +111,24 @@ std::vector<BodySpec> tree(const std::vector<int>& limbs) {
 
 // One descriptor: the frame tasks as (body, root body or −1, active rows: the first `rows` costs are 1), then the counts of everything else.
 struct TaskSpec { int body, root, rows; };
-enum Bad { BAD_NONE = 0, BAD_DOF_RANGE, BAD_COST, BAD_FRAME_ID, BAD_FREE_LIMIT };
+enum Bad { BAD_NONE = 0, BAD_DOF_RANGE, BAD_COST, BAD_FRAME_ID, BAD_FREE_LIMIT, BAD_BALL_SLOTS };
 struct Case {
   std::string name;
   std::vector<TaskSpec> tasks;
   int n_com = 0, n_pairs = 0, n_boxpairs = 0;
   bool cylbox = false, dense = false;
   int diag = 0, bad = BAD_NONE;
+  // lists of limits (n_cfg >= 0): that many ConfigurationLimits / VelocityLimits, each with its own gain, bounds and index subset,
+  // two PostureTasks, and the capsule pairs split over n_col CollisionAvoidanceLimits with their own parameters
+  int n_cfg = -1, n_vel = 1, n_col = 1;
+  Case& lists(int c, int v, int col = 1) { n_cfg = c; n_vel = v; n_col = col; return *this; }
+};
+
+// One term of a list of limits: the arrays a descriptor points to.
+struct BoxTerm {
+  double gain = 0.0;
+  std::vector<int32_t> idx;
+  std::vector<double> lower, upper, limit;
 };
 
 void put(const char* key, long long v, bool comma = true) { printf("\"%s\":%lld%s", key, v, comma ? "," : ""); }
@@ -129,6 +142,26 @@ void put_u64(const char* key, const uint64_t* a, size_t n) {       // (as string
   printf("\"%s\":[", key);
   for (size_t i = 0; i < n; ++i) printf("%s\"%llu\"", i ? "," : "", (unsigned long long)a[i]);
   printf("],");
+}
+// doubles as %.17g (read back exactly); the infinities as the tokens Python's json module reads
+void put_dbl(const char* key, const double* a, size_t n, bool comma = true) {
+  printf("\"%s\":[", key);
+  for (size_t i = 0; i < n; ++i) {
+    if (a[i] == a[i] && (a[i] - a[i]) != 0.0) printf("%s%sInfinity", i ? "," : "", a[i] < 0 ? "-" : "");
+    else printf("%s%.17g", i ? "," : "", a[i]);
+  }
+  printf("]%s", comma ? "," : "");
+}
+// the box and posture tables of a lane descriptor, [term][MD] flattened
+template <int ML, int MD>
+void put_lane(const char* key, const LaneProblemT<ML, MD>& L) {
+  printf("\"%s\":{", key);
+  put("md", MD); put("n_posture", L.n_posture); put("n_cfg", L.n_cfg); put("n_vel", L.n_vel);
+  put_dbl("cfg_gain", L.cfg_gain, kMaxBoxTerms); put_dbl("cfg_lower", &L.cfg_lower[0][0], (size_t)kMaxBoxTerms * MD);
+  put_dbl("cfg_upper", &L.cfg_upper[0][0], (size_t)kMaxBoxTerms * MD); put_dbl("vel_limit", &L.vel_limit[0][0], (size_t)kMaxBoxTerms * MD);
+  put_dbl("posture_cost", &L.posture_cost[0][0], (size_t)kMaxPostureTasks * MD);
+  put_dbl("posture_gain", L.posture_gain, kMaxPostureTasks); put_dbl("posture_lm", L.posture_lm, kMaxPostureTasks, false);
+  printf("},");
 }
 void put_str(const char* key, const std::string& s) {
   printf("\"%s\":\"", key);
@@ -166,7 +199,10 @@ void run_case(const Model& M, const HostModel& hm, const Case& cs) {
   if (cs.bad == BAD_COST) ft.at(0).cost[1] = -1.0;
   if (cs.bad == BAD_FRAME_ID) ft.at(0).frame_id = nb;
   std::vector<double> pcost(nv, 0.1), lower(nq, -1.0), upper(nq, 1.0), vmax(nv, 3.0);
-  MkhPostureTaskDesc pt{pcost.data(), 1.0, 0.0};
+  const bool lists = cs.n_cfg >= 0;
+  std::vector<double> pcost1(nv);
+  for (int dd = 0; dd < nv; ++dd) pcost1[dd] = 0.25 + 0.015625 * dd;
+  MkhPostureTaskDesc pts[2] = {{pcost.data(), 1.0, 0.0}, {pcost1.data(), 0.5, 0.125}};
   MkhComTaskDesc ct{{1.0, 1.0, 0.0}, 1.0, 0.0};
   std::vector<int32_t> lim_dofs, all_dofs;
   for (int dd = 0; dd < nv; ++dd) {
@@ -175,23 +211,65 @@ void run_case(const Model& M, const HostModel& hm, const Case& cs) {
   }
   if (cs.bad == BAD_DOF_RANGE) lim_dofs.push_back(nv);
   if (cs.bad == BAD_FREE_LIMIT) lim_dofs.push_back(0);
-  MkhConfigurationLimitDesc cl{0.5, lower.data(), upper.data(), (int32_t)lim_dofs.size(), lim_dofs.data()};
-  MkhVelocityLimitDesc vl{(int32_t)all_dofs.size(), all_dofs.data(), vmax.data()};
+  if (cs.bad == BAD_BALL_SLOTS)                   // a ball joint's four qpos slots of `upper` holding a quaternion of their own
+    for (int dd = 0; dd < nv; ++dd)
+      if (hm.jnt_type[hm.dof_jntid[dd]] == JNT_BALL) upper[hm.jnt_qposadr[hm.dof_jntid[dd]] + 2] = 0.5;
+  // the terms of a list.  Index subsets over the limited dofs L: configuration term 0 the even positions of L, term 1 the odd ones
+  // (disjoint: a dof of term 1 is in no term before it), term 2 all of L backwards, term 3 and 4 every third; velocity term 0 the
+  // first half, term 1 the second half and its last dof named three more times (four in all: a smaller limit between two larger ones), term 2 all,
+  // term 3 and 4 the first dof of L alone.  Bounds are indexed by qpos address, limits by position in the term.
+  std::vector<BoxTerm> cterm(lists ? cs.n_cfg : 0), vterm(lists ? cs.n_vel : 0);
+  const int nl = (int)lim_dofs.size();
+  for (int t = 0; t < (int)cterm.size(); ++t) {
+    BoxTerm& b = cterm[t];
+    const double gains[5] = {0.95, 0.5, 1.0, 0.25, 0.75};
+    b.gain = gains[t];
+    for (int k = 0; k < nl; ++k)
+      if (t == 0 ? k % 2 == 0 : (t == 1 ? k % 2 == 1 : (t == 2 ? true : k % 3 == 0))) b.idx.push_back(lim_dofs[t == 2 ? nl - 1 - k : k]);
+    b.lower.resize(nq); b.upper.resize(nq);
+    for (int a = 0; a < nq; ++a) { b.lower[a] = -1.0 - 0.125 * t - 0.0078125 * a; b.upper[a] = 0.5 + 0.25 * t + 0.00390625 * a; }
+    for (int dd = 0; dd < nv; ++dd)                 // (a ball joint: one value over its four slots, or the descriptor is refused)
+      if (hm.jnt_type[hm.dof_jntid[dd]] == JNT_BALL) {
+        const int qa = hm.jnt_qposadr[hm.dof_jntid[dd]];
+        for (int k = 1; k < 4; ++k) { b.lower[qa + k] = b.lower[qa]; b.upper[qa + k] = b.upper[qa]; }
+      }
+  }
+  for (int t = 0; t < (int)vterm.size(); ++t) {
+    BoxTerm& b = vterm[t];
+    for (int k = 0; k < nl; ++k)
+      if (t == 0 ? k < nl / 2 : (t == 1 ? k >= nl / 2 : (t == 2 ? true : k == 0))) b.idx.push_back(lim_dofs[k]);
+    for (size_t k = 0; k < b.idx.size(); ++k) b.limit.push_back(2.0 + 0.5 * t + 0.03125 * (double)k);
+    if (t == 1) for (double x : {1.75, 0.375, 1.5}) { b.idx.push_back(lim_dofs[nl - 1]); b.limit.push_back(x); }
+  }
+  std::vector<MkhConfigurationLimitDesc> cls;
+  std::vector<MkhVelocityLimitDesc> vls;
+  for (BoxTerm& b : cterm) cls.push_back({b.gain, b.lower.data(), b.upper.data(), (int32_t)b.idx.size(), b.idx.data()});
+  for (BoxTerm& b : vterm) vls.push_back({(int32_t)b.idx.size(), b.idx.data(), b.limit.data()});
+  if (!lists) {
+    cls.push_back({0.5, lower.data(), upper.data(), (int32_t)lim_dofs.size(), lim_dofs.data()});
+    vls.push_back({(int32_t)all_dofs.size(), all_dofs.data(), vmax.data()});
+  }
   // capsule pairs: the capsule of the last body against those of the first ones (cycling), then the cylinder against the box
   std::vector<int32_t> gp;
   for (int k = 0; k < cs.n_pairs; ++k) { gp.push_back(nb - 2); gp.push_back(k % (nb - 2)); }
   for (int k = 0; k < cs.n_boxpairs; ++k) { gp.push_back(nb - 2 - k % (nb - 2)); gp.push_back(M.box_geom); }   // capsules against the box
   if (cs.cylbox) { gp.push_back(M.cyl_geom); gp.push_back(M.box_geom); }
-  MkhCollisionLimitDesc col{(int32_t)gp.size() / 2, gp.data(), 0.85, 0.005, 0.01, 0.0};
+  // two CollisionAvoidanceLimits: the second takes the pairs from the last one of the first onwards (one geom pair is in both)
+  // and has its own four parameters
+  std::vector<int32_t> gp1;
+  if (cs.n_col == 2 && gp.size() >= 4) gp1.assign(gp.begin() + ((gp.size() / 4) * 2 - 2), gp.end()), gp.resize((gp.size() / 4) * 2);
+  std::vector<MkhCollisionLimitDesc> cols;
+  if (!gp.empty()) cols.push_back({(int32_t)gp.size() / 2, gp.data(), 0.85, 0.005, 0.01, 0.0});
+  if (!gp1.empty()) cols.push_back({(int32_t)gp1.size() / 2, gp1.data(), 0.5, 0.02, 0.05, 1e-3});
   const double dense_cost[3] = {1.0, 0.5, 0.25};
   MkhDenseTaskDesc dt{3, dense_cost, 1.0, 0.0};
   MkhProblemDesc d{};
   d.n_frame_tasks = (int32_t)ft.size(); d.frame_tasks = ft.data();
-  d.n_posture_tasks = 1; d.posture_tasks = &pt;
+  d.n_posture_tasks = lists ? 2 : 1; d.posture_tasks = pts;
   d.n_com_tasks = cs.n_com; d.com_tasks = &ct;
-  d.n_configuration_limits = 1; d.configuration_limits = &cl;
-  d.n_velocity_limits = 1; d.velocity_limits = &vl;
-  d.n_collision_limits = gp.empty() ? 0 : 1; d.collision_limits = &col;
+  d.n_configuration_limits = (int32_t)cls.size(); d.configuration_limits = cls.data();
+  d.n_velocity_limits = (int32_t)vls.size(); d.velocity_limits = vls.data();
+  d.n_collision_limits = (int32_t)cols.size(); d.collision_limits = cols.data();
   d.n_dense_tasks = cs.dense ? 1 : 0; d.dense_tasks = &dt;
 
   ProblemPlan plan;
@@ -212,7 +290,42 @@ void run_case(const Model& M, const HostModel& hm, const Case& cs) {
     printf("]}");
   }
   printf("],");
-  put("n_com", cs.n_com); put("com_rows", cs.n_com ? 2 : 0); put("n_pairs_in", (long long)gp.size() / 2); put("cylbox", cs.cylbox);
+  put("n_com", cs.n_com); put("com_rows", cs.n_com ? 2 : 0); put("n_pairs_in", (long long)(gp.size() + gp1.size()) / 2); put("cylbox", cs.cylbox);
+  put("n_posture", d.n_posture_tasks); put("lists", lists);
+  if (lists) {
+    // the descriptor as handed over, and per dof what indexes it: the joint's qpos address and whether the joint is a free one
+    std::vector<int32_t> qa(nv), fr(nv);
+    for (int dd = 0; dd < nv; ++dd) { qa[dd] = hm.jnt_qposadr[hm.dof_jntid[dd]]; fr[dd] = hm.jnt_type[hm.dof_jntid[dd]] == JNT_FREE; }
+    put_arr("dof_qposadr", qa.data(), nv); put_arr("dof_free", fr.data(), nv);
+    printf("\"desc\":{\"cfg\":[");
+    for (size_t t = 0; t < cterm.size(); ++t) {
+      printf("%s{", t ? "," : "");
+      put_dbl("gain", &cterm[t].gain, 1); put_arr("indices", cterm[t].idx.data(), cterm[t].idx.size());
+      put_dbl("lower", cterm[t].lower.data(), nq); put_dbl("upper", cterm[t].upper.data(), nq, false);
+      printf("}");
+    }
+    printf("],\"vel\":[");
+    for (size_t t = 0; t < vterm.size(); ++t) {
+      printf("%s{", t ? "," : "");
+      put_arr("indices", vterm[t].idx.data(), vterm[t].idx.size()); put_dbl("limit", vterm[t].limit.data(), vterm[t].limit.size(), false);
+      printf("}");
+    }
+    printf("],\"col\":[");
+    for (size_t t = 0; t < cols.size(); ++t) {
+      const double par[4] = {cols[t].gain, cols[t].minimum_distance_from_collisions, cols[t].collision_detection_distance, cols[t].bound_relaxation};
+      printf("%s{", t ? "," : "");
+      put_arr("pairs", cols[t].geom_id_pairs, 2 * (size_t)cols[t].n_pairs); put_dbl("par", par, 4, false);
+      printf("}");
+    }
+    printf("],\"post\":[");
+    for (int t = 0; t < d.n_posture_tasks; ++t) {
+      const double gl[2] = {pts[t].gain, pts[t].lm_damping};
+      printf("%s{", t ? "," : "");
+      put_dbl("cost", pts[t].cost, nv); put_dbl("gain_lm", gl, 2, false);
+      printf("}");
+    }
+    printf("]},");
+  }
   put("dense", cs.dense); put("diag", cs.diag); put("rc", rc); put_str("err", err);
   if (rc == MKH_OK) {
     const ProblemSelect& S = plan.sel;
@@ -257,6 +370,32 @@ void run_case(const Model& M, const HostModel& hm, const Case& cs) {
     printf("},");
     put("n_cv", plan.n_cv); put_arr("cv_pair", plan.cv_pair.data(), plan.cv_pair.size());
     put_arr("cv_adr", plan.cv_adr.data(), plan.cv_adr.size()); put_arr("cv_chain", plan.cv_chain.data(), plan.cv_chain.size());
+    if (lists) {
+      // the planned tables: lane tables of the wavefront kernels (stride 64), both lane descriptors, the plain arrays of the
+      // workgroup-per-problem kernel (stride nv) and the parameters of every pair
+      printf("\"tables\":{");
+      put_dbl("cfg_gain", P.cfg_gain, kMaxBoxTerms); put("n_cfg", P.n_cfg); put("n_vel", P.n_vel);
+      put_dbl("pcost", plan.pcost.data(), plan.pcost.size()); put_dbl("clo", plan.clo.data(), plan.clo.size());
+      put_dbl("chi", plan.chi.data(), plan.chi.size()); put_dbl("vlim", plan.vlim.data(), plan.vlim.size());
+      if (plan.lane_class) put_lane("lane2", plan.lane);
+      if (plan.lane_class && plan.lane_class != 32) {
+        LaneProblem lp1;
+        lane_problem_narrow(plan.lane, lp1);
+        put_lane("lane1", lp1);
+      }
+      if (plan.wide.built) {
+        const WideProblem& W = plan.wide.W;
+        printf("\"wide\":{");
+        put("n_cfg", W.n_cfg); put("n_vel", W.n_vel); put("n_posture", W.n_posture); put_dbl("cfg_gain", W.cfg_gain, kMaxBoxTerms);
+        put_dbl("pcost", plan.wide.pcost.data(), plan.wide.pcost.size()); put_dbl("clo", plan.wide.clo.data(), plan.wide.clo.size());
+        put_dbl("chi", plan.wide.chi.data(), plan.wide.chi.size()); put_dbl("vlim", plan.wide.vlim.data(), plan.wide.vlim.size(), false);
+        printf("},");
+      }
+      std::vector<double> pp;
+      for (const CollisionPairDev& cp : plan.pairs) for (double x : {cp.gain, cp.dmin, cp.ddetect, cp.relax}) pp.push_back(x);
+      put_dbl("pair_par", pp.data(), pp.size(), false);
+      printf("},");
+    }
   }
   put("end", 1, false);
   printf("}\n");
@@ -323,11 +462,22 @@ int main() {
       add("jpairs256", {{43, -1, 1}, {43, -1, 1}, {43, -1, 1}, {43, -1, 1}, {42, -1, 1}, {42, -1, 1}});
       add("jpairs257", {{43, -1, 1}, {43, -1, 1}, {43, -1, 1}, {43, -1, 1}, {43, -1, 1}, {42, -1, 1}});
     }
+    // lists of limits: 2 and 4 terms of each box kind (and one kind alone), two posture tasks; with capsule pairs (the wide
+    // arrays of a model within one wavefront are only built behind half-space rows) split over two collision limits
+    add("lim_c2_v2", on_leaves(M, {6})).lists(2, 2);
+    add("lim_c4_v4", on_leaves(M, {6, 3})).lists(4, 4);
+    add("lim_c3_v0", on_leaves(M, {6})).lists(3, 0);
+    add("lim_c0_v3", on_leaves(M, {6})).lists(0, 3);
+    add("lim_c2_v2_col2", on_leaves(M, {6})).lists(2, 2, 2).n_pairs = 5;
+    add("lim_c4_v4_col2", on_leaves(M, {6})).lists(4, 4, 2).n_pairs = 4;
     // refused descriptors
+    add("bad_cfg5", on_leaves(M, {6})).lists(5, 1);
+    add("bad_vel5", on_leaves(M, {6})).lists(1, 5);
     add("bad_dof_range", on_leaves(M, {6})).bad = BAD_DOF_RANGE;
     add("bad_cost", on_leaves(M, {6})).bad = BAD_COST;
     add("bad_frame_id", on_leaves(M, {6})).bad = BAD_FRAME_ID;
     if (hm.jnt_type[hm.dof_jntid[0]] == JNT_FREE) add("bad_free_limit", on_leaves(M, {6})).bad = BAD_FREE_LIMIT;
+    if (std::string(e.name) == "ball11") add("bad_ball_slots", on_leaves(M, {6})).bad = BAD_BALL_SLOTS;
     for (const Case& c : cases) run_case(M, hm, c);
   }
   return 0;

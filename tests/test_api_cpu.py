@@ -292,6 +292,32 @@ def test_fold_box_rows_of_caller_defined_limits():
     assert _fold_box_rows(np.ones((2, 1, nv)), np.ones((2, 1)))[4] is False
 
 
+def test_more_limits_than_the_device_holds():
+    """The reference stacks any number of limits (mink/solve_ik.py:25-40); a device descriptor holds four of each box kind.
+    Velocity limits beyond the fourth fold into it as per-dof minima; a fifth ConfigurationLimit is refused by name and count
+    before anything reaches the device."""
+    from mink_amd.solve_ik import MAX_BOX_TERMS, _fold_velocity_terms
+    term = lambda idx, lim: {"indices": np.array(idx, dtype=np.int64), "limit": np.array(lim, dtype=np.float64)}
+    four = [term([0, 1], [1.0, 2.0]), term([2], [3.0]), term([0], [0.5]), term([5, 1], [4.0, 1.5])]
+    assert _fold_velocity_terms(four) is four and MAX_BOX_TERMS == 4
+    six = four + [term([1, 3], [0.25, 7.0]), term([5, 3], [6.0, 0.0])]
+    out = _fold_velocity_terms(six)
+    assert len(out) == 4 and all(a is b for a, b in zip(out[:3], six[:3]))
+    assert out[3]["indices"].tolist() == [1, 3, 5] and out[3]["limit"].tolist() == [0.25, 0.0, 4.0]
+    # elementwise minimum over ALL terms per dof is unchanged by the fold
+    def merged(terms):
+        v = np.full(6, np.inf)
+        for t in terms:
+            np.minimum.at(v, t["indices"], t["limit"])
+        return v
+    np.testing.assert_array_equal(merged(out), merged(six))
+    arm = mink.load_robot("ur5e")
+    cfg = mink.Configuration(arm)
+    lims = [mink.ConfigurationLimit(arm, gain=g) for g in (0.95, 0.9, 0.8, 0.7, 0.6)]
+    with pytest.raises(mink.LimitDefinitionError, match=r"5 ConfigurationLimits.*at most 4"):
+        mink.solve_ik(cfg, [], 1e-2, limits=lims)
+
+
 def test_partial_override_detection():
     import mink_amd as mink
 

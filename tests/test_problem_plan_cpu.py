@@ -4,6 +4,12 @@ mink_amd/csrc/problem_plan.hip plans a problem as plain data (problem_plan.h); t
 models and descriptors that put every fixed-size array of the device descriptor at its edge, built with the host's address and
 undefined-behaviour sanitizers and run as a child process.  The tables it prints are recomputed here from the models' parent
 arrays and the descriptors' costs, not from the plan.
+
+Lists of limits (the `lim_*` cases): 2 to 4 ConfigurationLimits and VelocityLimits with their own gain, bounds and index subset
+(two of them disjoint, one velocity term naming a dof four times), two PostureTasks and two CollisionAvoidanceLimits that share
+a geom pair.  Every entry of every copy the plan makes — lane tables at stride 64, LaneProblem2 and its narrowed LaneProblem,
+the wide arrays at stride nv, the parameters per pair — is recomputed from the descriptor and compared exactly; five limits of a
+kind are refused with MKH_E_LIMIT and the cap in the text.
 """
 
 import json
@@ -86,7 +92,7 @@ def test_task_rows_and_tap_layout(plans):
         n_jrows = sum(len(r) for r in rows) + c["com_rows"]
         d = c["dev"] if not c["big"] else c["wide"]
         assert d["n_jrows"] == n_jrows, (c["model"], c["case"])
-        assert d["n_rows_tap"] == 6 * len(rows) + c["nv"] + 3 * c["n_com"] + (3 if c["dense"] else 0)
+        assert d["n_rows_tap"] == 6 * len(rows) + c["n_posture"] * c["nv"] + 3 * c["n_com"] + (3 if c["dense"] else 0)
         assert c["dev"]["n_rows_tap"] == d["n_rows_tap"]
 
 
@@ -231,6 +237,143 @@ def test_kernel_families(plans):
     assert plans[("chain16", "t1_r6_relative")]["sel"]["has_relative"] == 1
 
 
+KMAX_BOX, KMAX_POSTURE = 4, 4                  # mkh_types.h kMaxBoxTerms, kMaxPostureTasks
+INF = float("inf")
+LIST_MODELS = {"chain6": (6, 16), "chain16": (16, 16), "chain17": (32, None), "ball11": (0, None), "chain68": (0, None)}
+
+
+def box_tables(c, stride, filled=True):
+    """[term][stride] arrays of a list of limits from the descriptor alone: a configuration term bounds the dofs it names by
+    lower / upper at the joint's qpos address (a dof named twice: the same value), a velocity term by the smallest limit given
+    for the dof; every other entry is -inf / +inf / +inf — and a list without terms still has one such row."""
+    nv, desc = c["nv"], c["desc"]
+    nc, nl, npost = len(desc["cfg"]), len(desc["vel"]), len(desc["post"])
+    clo = np.full((max(nc, 1), stride), -INF); chi = np.full((max(nc, 1), stride), INF)
+    vlim = np.full((max(nl, 1), stride), INF); pcost = np.zeros((max(npost, 1), stride))
+    if filled:
+        for t, term in enumerate(desc["cfg"]):
+            for dof in term["indices"]:
+                clo[t, dof] = term["lower"][c["dof_qposadr"][dof]]
+                chi[t, dof] = term["upper"][c["dof_qposadr"][dof]]
+        for t, term in enumerate(desc["vel"]):
+            for dof, lim in zip(term["indices"], term["limit"]):
+                vlim[t, dof] = min(vlim[t, dof], lim)
+        for t, term in enumerate(desc["post"]):
+            pcost[t, :nv] = term["cost"]
+    return pcost, clo, chi, vlim
+
+
+def list_cases(plans):
+    return [c for c in plans.values() if c.get("lists") and c["rc"] == 0]
+
+
+def same(got, want, key, what):
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64).ravel()
+    assert got.shape == want.shape, (key, what, got.shape, want.shape)
+    bad = np.flatnonzero(got != want)            # (exact: the plan copies, it does not compute; no NaN anywhere)
+    assert len(bad) == 0, (key, what, bad[:8], got[bad[:8]], want[bad[:8]])
+
+
+def test_limit_lists_cover_every_table(plans):
+    """The list cases reach every copy of the box tables: lane tables, both lane descriptors with and without the narrowed one,
+    the wide arrays of small and large models, and two collision limits."""
+    cases = list_cases(plans)
+    assert len(cases) == 60
+    for m, (cls, narrowed) in LIST_MODELS.items():
+        c = plans[(m, "lim_c4_v4")]
+        assert c["lane"]["cls"] == cls and ("lane2" in c["tables"]) == bool(cls) and ("lane1" in c["tables"]) == bool(narrowed), m
+        assert "wide" in plans[(m, "lim_c4_v4_col2")]["tables"], m
+    assert "wide" in plans[("chain68", "lim_c4_v4")]["tables"] and plans[("chain68", "lim_c4_v4")]["big"]
+    for c in cases:
+        desc = c["desc"]
+        want = {"lim_c2_v2": (2, 2, 0), "lim_c4_v4": (4, 4, 0), "lim_c3_v0": (3, 0, 0), "lim_c0_v3": (0, 3, 0),
+                "lim_c2_v2_col2": (2, 2, 2), "lim_c4_v4_col2": (4, 4, 2)}[c["case"]]
+        assert (len(desc["cfg"]), len(desc["vel"]), len(desc["col"])) == want and len(desc["post"]) == 2
+        # what the terms were made to be: own gains, disjoint subsets (a dof of term 1 is in no term before it), one dof named
+        # four times in velocity term 1 (once in its half, three more behind it) with the smallest limit between two larger ones
+        if len(desc["cfg"]) >= 2:
+            i0, i1 = set(desc["cfg"][0]["indices"]), set(desc["cfg"][1]["indices"])
+            assert i0 and i1 and not (i0 & i1)
+            assert len({t["gain"][0] for t in desc["cfg"]}) == len(desc["cfg"])
+            assert desc["cfg"][0]["lower"] != desc["cfg"][1]["lower"] and desc["cfg"][0]["upper"] != desc["cfg"][1]["upper"]
+        if len(desc["vel"]) >= 2:
+            idx, lim = desc["vel"][1]["indices"], desc["vel"][1]["limit"]
+            twice = [k for k in range(len(idx)) if idx[k] == idx[-1]]
+            assert len(twice) == 4 and min(lim[k] for k in twice) == lim[twice[2]] < lim[twice[3]]
+            assert not (set(desc["vel"][0]["indices"]) & set(idx))
+        if len(desc["col"]) == 2:
+            p0 = {tuple(desc["col"][0]["pairs"][i:i + 2]) for i in range(0, len(desc["col"][0]["pairs"]), 2)}
+            p1 = {tuple(desc["col"][1]["pairs"][i:i + 2]) for i in range(0, len(desc["col"][1]["pairs"]), 2)}
+            assert len(p0 & p1) == 1 and p0 - p1 and p1 - p0
+            assert all(a != b for a, b in zip(desc["col"][0]["par"], desc["col"][1]["par"])) and desc["col"][1]["par"][3] == 1e-3
+
+
+def test_limit_list_tables(plans):
+    """Every entry of every planned copy, recomputed from the descriptor: the lane tables of the wavefront kernels (stride 64; a
+    model beyond one wavefront keeps the defaults), LaneProblem2 and its narrowed LaneProblem ([term][MD], every term and dof
+    beyond the problem's at -inf / +inf / +inf, posture costs 0), the wide arrays (stride nv) and the four parameters of
+    every pair in list order."""
+    for c in list_cases(plans):
+        key, nv, T, desc = (c["model"], c["case"]), c["nv"], c["tables"], c["desc"]
+        nc, nl, npost = len(desc["cfg"]), len(desc["vel"]), len(desc["post"])
+        gains = [t["gain"][0] for t in desc["cfg"]]
+        assert (T["n_cfg"], T["n_vel"]) == (nc, nl), key
+        same(T["cfg_gain"][:nc], gains, key, "cfg_gain")
+        pcost, clo, chi, vlim = box_tables(c, 64, filled=not c["big"])
+        for name, want in (("pcost", pcost), ("clo", clo), ("chi", chi), ("vlim", vlim)):
+            same(T[name], want, key, name)
+        for lane in ("lane2", "lane1"):
+            if lane not in T:
+                continue
+            L = T[lane]
+            md = L["md"]
+            assert md == (32 if lane == "lane2" else 16) and nv <= md
+            assert (L["n_posture"], L["n_cfg"], L["n_vel"]) == (npost, nc, nl), key
+            pc, lo, hi, vl = box_tables(c, md)
+            wlo, whi, wvl = np.full((KMAX_BOX, md), -INF), np.full((KMAX_BOX, md), INF), np.full((KMAX_BOX, md), INF)
+            wpc = np.zeros((KMAX_POSTURE, md))
+            wlo[:nc], whi[:nc], wvl[:nl], wpc[:npost] = lo[:nc], hi[:nc], vl[:nl], pc[:npost]
+            wpc[:, :nv] *= 1 - np.asarray(c["dof_free"])             # (free-joint dofs: no posture error)
+            same(L["cfg_lower"], wlo, key, lane + ".cfg_lower")
+            same(L["cfg_upper"], whi, key, lane + ".cfg_upper")
+            same(L["vel_limit"], wvl, key, lane + ".vel_limit")
+            same(L["posture_cost"], wpc, key, lane + ".posture_cost")
+            same(L["cfg_gain"], gains + [0.0] * (KMAX_BOX - nc), key, lane + ".cfg_gain")
+            same(L["posture_gain"][:npost], [t["gain_lm"][0] for t in desc["post"]], key, lane + ".posture_gain")
+            same(L["posture_lm"][:npost], [t["gain_lm"][1] for t in desc["post"]], key, lane + ".posture_lm")
+        if "wide" in T:
+            W = T["wide"]
+            assert (W["n_posture"], W["n_cfg"], W["n_vel"]) == (npost, nc, nl), key
+            same(W["cfg_gain"][:nc], gains, key, "wide.cfg_gain")
+            pc, lo, hi, vl = box_tables(c, nv)
+            for name, want in (("pcost", pc), ("clo", lo), ("chi", hi), ("vlim", vl)):
+                same(W[name], want, key, "wide." + name)
+        want = [x for t in desc["col"] for _ in range(len(t["pairs"]) // 2) for x in t["par"]]
+        same(T["pair_par"], want, key, "pair_par")
+        assert len(T["pair_par"]) == 4 * c["n_pairs_in"]
+
+
+def test_dof_outside_a_term_is_unbounded(plans):
+    """Read off the printed tables themselves, on the case whose terms 0 and 1 are disjoint: a dof of term 1 reads
+    -inf / +inf in term 0 and finite bounds in term 1, on every copy."""
+    for m in LIST_MODELS:
+        c = plans[(m, "lim_c4_v4_col2" if m != "chain68" else "lim_c4_v4")]
+        nv, T, desc = c["nv"], c["tables"], c["desc"]
+        only1 = sorted(set(desc["cfg"][1]["indices"]) - set(desc["cfg"][0]["indices"]))
+        v_only1 = sorted(set(desc["vel"][1]["indices"]) - set(desc["vel"][0]["indices"]))
+        assert len(only1) >= 2 and len(v_only1) >= 2
+        copies = [(T["wide"], nv)] + ([(T, 64)] if not c["big"] else [])
+        c2 = plans[(m, "lim_c4_v4")]["tables"]
+        copies += [(c2[k], c2[k]["md"]) for k in ("lane2", "lane1") if k in c2]
+        for tab, stride in copies:
+            lo, hi = tab.get("clo", tab.get("cfg_lower")), tab.get("chi", tab.get("cfg_upper"))
+            vl = tab.get("vlim", tab.get("vel_limit"))
+            for dof in only1:
+                assert lo[dof] == -INF and hi[dof] == INF and np.isfinite([lo[stride + dof], hi[stride + dof]]).all(), (m, dof)
+            for dof in v_only1:
+                assert vl[dof] == INF and np.isfinite(vl[stride + dof]), (m, dof)
+
+
 def test_refused_descriptors(plans):
     """Code and text of mkh_last_error, as before the split."""
     for (m, case), c in plans.items():
@@ -241,8 +384,15 @@ def test_refused_descriptors(plans):
             assert (c["rc"], c["err"]) == (-1, "frame task 0: cost must be >= 0")
         elif case == "bad_frame_id":
             assert (c["rc"], c["err"]) == (-1, "frame task 0: body id %d out of range" % nb)
+        elif case in ("bad_cfg5", "bad_vel5"):
+            # MKH_E_LIMIT, and the text names the cap (kMaxBoxTerms)
+            assert (c["rc"], c["err"]) == (-4, "at most 4 configuration and 4 velocity limits")
+        elif case == "bad_ball_slots":
+            # (the kernels rebuild a ball joint's bound from one value per dof: a quaternion of its own in the four slots is refused)
+            assert (c["rc"], c["err"]) == (-1, "configuration limit 0: lower / upper differ over the four qpos slots of the ball joint of dof 5 "
+                                               "(one value per ball joint, as the reference's constructor writes its range)")
         elif case == "bad_free_limit":
             assert (c["rc"], c["err"]) == (-1, "configuration limit on free-joint dof 0 (the reference skips free joints)")
         else:
             assert c["rc"] == 0, (m, case, c["err"])
-    assert ("tree44", "bad_free_limit") in plans and ("tree62", "bad_free_limit") in plans
+    assert ("tree44", "bad_free_limit") in plans and ("tree62", "bad_free_limit") in plans and ("ball11", "bad_ball_slots") in plans
