@@ -2,9 +2,11 @@
 """Ladder-graph trajectory IK: the far Cartesian lines of batched_global_trajectory_ur5e.py, tracked four ways — from one start
 (`solve_ik_trajectory`), from several whole candidates (`solve_ik_trajectory_multistart`), and through a ladder graph
 (`solve_ik_trajectory_ladder`: several IK solutions per waypoint, the path picked by a dynamic program on the device) with
-drawn seeds and, with `--seed-table`, with seeds looked up in a table of stored postures by every waypoint's own pose.
+drawn seeds and, with `--seed-table`, with seeds looked up in a table of stored postures by every waypoint's own pose.  With
+`--refine` every ladder runs a second time with the refinement pass behind its search (`refine=True`): the chosen path is
+re-tracked across its breaks and lost waypoints, and kept only where that makes it better.
 
-    python examples/batched_ladder_ur5e.py --paths 256 --seeds 8 --seed-table
+    python examples/batched_ladder_ur5e.py --paths 256 --seeds 8 --seed-table --refine
 
 UR5e, one FrameTask on `attachment_site` (costs 1 / 1, lm_damping 1), ConfigurationLimit, dt = 1, damping = 1e-3, thresholds
 1e-4 / 1e-4, 40 iterations per waypoint, every path started at `home`.  A path counts as COMPLETE when every waypoint is tracked
@@ -42,6 +44,7 @@ def main():
     ap.add_argument("--rng-seed", type=int, default=5)
     ap.add_argument("--seed-table", action="store_true", help="also run the ladder seeded from a table of stored postures")
     ap.add_argument("--table-entries", type=int, default=16384)
+    ap.add_argument("--refine", action="store_true", help="also run every ladder with the refinement pass behind its search")
     args = ap.parse_args()
     B, S, T = args.paths, args.seeds, args.waypoints
     rng = np.random.default_rng(20261018)
@@ -77,25 +80,40 @@ def main():
     drawn, ms = timed(ladder)
     rows.append((f"ladder ({S} nodes per waypoint, drawn)", drawn.q, drawn.converged & ((drawn.status & ~1) == 0), ms))
     results = [drawn]
+    if args.refine:
+        fine, ms = timed(lambda: ladder(refine=True))
+        rows.append((f"ladder ({S} nodes per waypoint, drawn) + refinement", fine.q, fine.converged & ((fine.status & ~1) == 0), ms))
+        results.append(fine)
     if args.seed_table:
         table = mink.SeedTable(mink.Configuration(model, home), tasks, args.table_entries, limits=limits)
         looked_up, ms = timed(lambda: ladder(seed_table=table))
         rows.append((f"ladder ({S} nodes per waypoint, seed table of {args.table_entries})", looked_up.q,
                      looked_up.converged & ((looked_up.status & ~1) == 0), ms))
         results.append(looked_up)
+        if args.refine:
+            fine, ms = timed(lambda: ladder(seed_table=table, refine=True))
+            rows.append((f"ladder ({S} nodes per waypoint, seed table of {args.table_entries}) + refinement", fine.q,
+                         fine.converged & ((fine.status & ~1) == 0), ms))
+            results.append(fine)
         table.close()
 
     print(f"UR5e, {B} Cartesian lines of {T} waypoints whose first pose is far from `home`, at most {args.max_iters} iterations per "
           f"waypoint; a break is a joint step beyond {args.max_step} rad:")
     for name, q, tracked, ms in rows:
         complete, clean = complete_and_break_free(q, tracked, args.max_step)
-        print(f"  {name:58s}: {int(complete.sum()):5d} complete, {int(clean.sum()):5d} complete and break-free of {B}; "
+        print(f"  {name:71s}: {int(complete.sum()):5d} complete, {int(clean.sum()):5d} complete and break-free of {B}; "
               f"{int(tracked.sum()):6d} of {B * T} waypoints   ({ms:.2f} ms)")
     for res in results:                                                      # what the search reports is what the path shows
         steps_sq = (np.diff(res.q, axis=1) ** 2).sum(axis=2)
         clear = np.abs(steps_sq - args.max_step ** 2) > 1e-9
         assert (res.edge_break[:, 1:] == (steps_sq > args.max_step ** 2))[clear].all()
         assert (res.n_tracked == (res.converged & ((res.status & ~1) == 0)).sum(axis=1)).all()
+    for plain, fine in zip(results[0::2], results[1::2]) if args.refine else ():     # the pass never returns a worse path
+        worse = [(T - f_t, f_b, f_l) > (T - p_t, p_b, p_l) for f_t, f_b, f_l, p_t, p_b, p_l in
+                 zip(fine.n_tracked, fine.n_breaks, fine.path_length, plain.n_tracked, plain.n_breaks, plain.path_length)]
+        assert not any(worse)
+        print(f"  refinement: {int(fine.refined.sum())} of {B} paths returned re-tracked, {int((fine.repaired != 0).sum())} waypoints repaired "
+              f"({int((fine.repaired == 1).sum())} forward, {int((fine.repaired == 2).sum())} backward)")
 
 
 if __name__ == "__main__":

@@ -805,6 +805,89 @@ int32_t mkh_solve_trajectory_ladder(MkhProblem *problem, int32_t B, int32_t T, i
                                     uint64_t rng_seed, int64_t target_index0, const MkhTrajectoryLadderIO *io, int32_t flags,
                                     void *hip_stream);
 
+/*
+ * Ladder refinement: a pass AFTER the search that re-tracks the chosen path across its breaks and lost nodes.  The rungs of a
+ * ladder are solved independently of each other, so consecutive chosen nodes may sit on different IK branches and the search
+ * can only choose among what the rungs hold; the pass re-solves the offending waypoints from their neighbours on the path.  It
+ * works on the B chosen paths only and costs 2T - 1 loop launches on B instances: about two plain trajectory calls.
+ *
+ * THE RULE OF THE REFINEMENT (mkh_ladder_refine; mkh_solve_trajectory_ladder_refined runs it on the path it searched).  The
+ * terms are those of THE RULE above: the edge cost c(a -> b) = sum_k w_k ((b (-) a)_k)^2 with its +inf for a NaN or an overflow,
+ * the same device function; the gate max_step_sq (>= 0, +inf legal: then only lost nodes are repaired); the start edge from
+ * q[b], which is never a break; the key (lost, breaks, length), length accumulated in ascending t by one rounded addition each.
+ *
+ * Input, per instance b: a path p_0 ... p_{T-1}, q_path (B, T, nq); flags tracked_path (B, T), != 0: tracked; the waypoint
+ * targets of mkh_solve_trajectory_ladder, in its shapes; the loop parameters dt, damping, max_iters, pos_threshold >= 0,
+ * ori_threshold >= 0.  A loop result TRACKS when its loop converged and its status carries no bit but MKH_ST_OUTSIDE_LIMITS —
+ * the ladder's own definition.
+ *
+ * Working path r, initialised to p.  Two sweeps; every waypoint of a sweep is ONE launch of mkh_solve_until's loop on all B
+ * instances with waypoint t's targets, stream-ordered, no host synchronisation in between.
+ *  1. Forward, t = 0 ... T-1, with r_{-1} = q[b].  Waypoint t of instance b is BAD when r_t is not tracked, or when t >= 1 and
+ *     c(r_{t-1} -> r_t) > max_step_sq.  The launch starts bad instances at r_{t-1}, all others at r_t (their result is discarded;
+ *     a converged posture ends its loop after one step).  A bad instance's result x is ACCEPTED when it tracks and, for t >= 1,
+ *     c(r_{t-1} -> x) <= max_step_sq.  Accepted: r_t = x, r_t counts as tracked, repaired[b, t] = 1, and v, status, iters,
+ *     converged of (b, t) become the loop's.  Otherwise nothing of (b, t) changes.
+ *  2. Backward, t = T-2 ... 0.  Waypoint t is bad when r_t is not tracked or c(r_t -> r_{t+1}) > max_step_sq; bad instances
+ *     start at r_{t+1}; x is accepted when it tracks and c(x -> r_{t+1}) <= max_step_sq; then repaired[b, t] = 2.  An accepted
+ *     repair may turn the edge INTO t into a break: that edge is judged at t - 1, the next step of the sweep; the start edge
+ *     stays exempt.  T = 1: the sweep is empty.
+ *  3. Guard.  The key of r and the key of p are computed by one device function, which also yields edge_break, n_tracked,
+ *     n_breaks and path_length of whichever path is returned.  r is returned only if its key is STRICTLY smaller,
+ *     lexicographically; then refined[b] = 1.  Otherwise every output of instance b is the input path's, bit for bit,
+ *     repaired[b, :] = 0 and refined[b] = 0.  THE RESULT IS NEVER WORSE THAN THE PATH THAT CAME IN — than the search's, in the
+ *     composed call.
+ *
+ * Threshold mode only, at least one frame task, no dense rows; MKH_FLAG_WARM_START does not enter, as in multi-start.  B <=
+ * max_batch.  The working path, the loops' rows of the repaired nodes, the start array and the flags live in the handle's
+ * workspace: about B·T·((2 nq + nv)·8 + 24) bytes.
+ *
+ * mkh_ladder_refine: the pass alone.  Outputs: q_path_out (B, T, nq) the returned path; tracked_out (B, T) its 0 / 1 flags;
+ * repaired (B, T): 0 kept, 1 / 2 replaced by the forward / backward sweep; refined (B,); edge_break, n_tracked, n_breaks,
+ * path_length of the returned path.  Optional v, status, iters, converged (B, T, .): the loops' rows of the REPAIRED nodes of a
+ * returned r; rows of kept nodes are left unwritten, so a caller pre-fills them with what it knows of its path.  q_path_out may
+ * be q_path itself, tracked_out may be tracked_path.  Pointers are host pointers (staged, synchronous; v ... converged are
+ * then copied in, updated and copied back) or device pointers with MKH_FLAG_DEVICE_PTRS (asynchronous on the stream).  Every
+ * argument error is reported before any device work.
+ */
+typedef struct MkhLadderRefineIO {
+  const double *weights;    /* (nv,) weights of the edge cost, each >= 0, or NULL: ones                                      */
+  double max_step_sq;       /* the break gate on the edge cost, >= 0; +inf: no gate                                          */
+  double *q_path_out;       /* (B, T, nq)  the returned path                                                       required  */
+  int32_t *tracked_out;     /* (B, T)      its tracked flags                                                       required  */
+  int32_t *repaired;        /* (B, T)      0 kept, 1 forward sweep, 2 backward sweep                               required  */
+  int32_t *refined;         /* (B,)        1 where the working path was returned                                   required  */
+  int32_t *edge_break;      /* (B, T)      1 where the edge into waypoint t of the returned path is a break        required  */
+  int32_t *n_tracked;       /* (B,)                                                                                required  */
+  int32_t *n_breaks;        /* (B,)                                                                                required  */
+  double *path_length;      /* (B,)                                                                                required  */
+  double *v;                /* (B, T, nv)  optional: rows of repaired nodes only                                             */
+  int32_t *status;          /* (B, T)      optional: the same                                                                */
+  int32_t *iters;           /* (B, T)      optional: the same                                                                */
+  int32_t *converged;       /* (B, T)      optional: the same                                                                */
+} MkhLadderRefineIO;
+int32_t mkh_ladder_refine(MkhProblem *problem, int32_t B, int32_t T, const double *q, const double *q_path,
+                          const int32_t *tracked_path, const double *frame_targets, const double *posture_target,
+                          const double *com_target, double dt, double damping, int32_t max_iters, double pos_threshold,
+                          double ori_threshold, const MkhLadderRefineIO *io, int32_t flags, void *hip_stream);
+
+/*
+ * mkh_solve_trajectory_ladder_refined: mkh_solve_trajectory_ladder and, with `refine` != NULL, the pass above on the path it
+ * searched — the rungs, the search, the gathers and the pass on the device, nothing over the bus in between.  The result is
+ * BITWISE mkh_solve_trajectory_ladder followed by mkh_ladder_refine on its outputs (q_traj and the chosen nodes' tracked flags
+ * as the path, v_traj ... converged pre-filled).  The returned path goes where the ladder's goes — io's q_traj, v_traj, status,
+ * iters, converged, n_tracked, n_breaks, path_length, edge_break —, the gate and the weights are io's, and of `refine` only
+ * tracked_out, repaired and refined are used (required); its other fields are ignored.  qvel, when asked for, follows the
+ * returned path.  node_index keeps the search's choice: at a repaired waypoint it names the node that was replaced.  With
+ * refine == NULL the call IS mkh_solve_trajectory_ladder, which is a wrapper around it.
+ */
+int32_t mkh_solve_trajectory_ladder_refined(MkhProblem *problem, int32_t B, int32_t T, int32_t n_seeds, const double *q,
+                                            const double *frame_targets, const double *posture_target,
+                                            const double *com_target, double dt, double damping, int32_t max_iters,
+                                            double pos_threshold, double ori_threshold, uint64_t rng_seed,
+                                            int64_t target_index0, const MkhTrajectoryLadderIO *io,
+                                            const MkhLadderRefineIO *refine, int32_t flags, void *hip_stream);
+
 /* Same inputs; additionally writes the requested intermediates (build_ik / compute_error /
  * compute_jacobian / get_transform_frame_to_world parity taps).  v_out/status_out may be NULL
  * to skip the QP. */

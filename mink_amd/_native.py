@@ -255,7 +255,8 @@ class TrajectoryLadderOut(NamedTuple):
     """What NativeProblem.solve_trajectory_ladder returns (arrays of the caller's kind).  The chosen nodes' rows `q`, `v`, `status`,
     `iters`, `converged` (B, T, ·); the search's `node_index`, `edge_break` (B, T), `n_tracked`, `n_breaks`, `path_length` (B,);
     `qvel` unless qvel_dt was not given.  With return_all every node's `q_all` (B, T, S, nq), `v_all` (B, T, S, nv),
-    `status_all`, `iters_all`, `converged_all` (B, T, S) and the `seeds` (B, T, S, nq); None otherwise."""
+    `status_all`, `iters_all`, `converged_all` (B, T, S) and the `seeds` (B, T, S, nq); None otherwise.  With refine the path is
+    the refinement's (LadderRefineOut) and `tracked`, `repaired` (B, T), `refined` (B,) are its; None otherwise."""
     q: object
     v: object
     status: object
@@ -273,6 +274,36 @@ class TrajectoryLadderOut(NamedTuple):
     iters_all: object = None
     converged_all: object = None
     seeds: object = None
+    tracked: object = None
+    repaired: object = None
+    refined: object = None
+
+
+LADDER_REFINE_IO_FIELDS = ("weights", "max_step_sq", "q_path_out", "tracked_out", "repaired", "refined", "edge_break", "n_tracked",
+                           "n_breaks", "path_length", "v", "status", "iters", "converged")
+
+
+class MkhLadderRefineIO(C.Structure):
+    _fields_ = [(n, C.c_double if n == "max_step_sq" else C.c_void_p) for n in LADDER_REFINE_IO_FIELDS]
+
+
+class LadderRefineOut(NamedTuple):
+    """What NativeProblem.ladder_refine returns (arrays of the caller's kind): the returned path `q` (B, T, nq) with its
+    `tracked` flags (B, T); `repaired` (B, T): 0 kept, 1 / 2 replaced by the forward / backward sweep; `refined` (B,): 1 where
+    the re-tracked path was returned; `edge_break` (B, T), `n_tracked`, `n_breaks`, `path_length` (B,) of the returned path; the
+    caller's `v`, `status`, `iters`, `converged` with the rows of repaired nodes replaced by their loops' (None where not passed)."""
+    q: object
+    tracked: object
+    repaired: object
+    refined: object
+    edge_break: object
+    n_tracked: object
+    n_breaks: object
+    path_length: object
+    v: object = None
+    status: object = None
+    iters: object = None
+    converged: object = None
 
 
 def check_ladder_shape(S: int, T: int, max_step_sq: float) -> None:
@@ -383,6 +414,13 @@ def lib() -> C.CDLL:
     L.mkh_solve_trajectory_ladder.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + common[2:8] + \
         [C.c_int32, C.c_double, C.c_double, C.c_uint64, C.c_int64, C.POINTER(MkhTrajectoryLadderIO), C.c_int32, C.c_void_p]
     L.mkh_solve_trajectory_ladder.restype = C.c_int32
+    L.mkh_solve_trajectory_ladder_refined.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + common[2:8] + \
+        [C.c_int32, C.c_double, C.c_double, C.c_uint64, C.c_int64, C.POINTER(MkhTrajectoryLadderIO), C.POINTER(MkhLadderRefineIO),
+         C.c_int32, C.c_void_p]
+    L.mkh_solve_trajectory_ladder_refined.restype = C.c_int32
+    L.mkh_ladder_refine.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p] + common[3:8] + \
+        [C.c_int32, C.c_double, C.c_double, C.POINTER(MkhLadderRefineIO), C.c_int32, C.c_void_p]
+    L.mkh_ladder_refine.restype = C.c_int32
     L.mkh_solve_dense.argtypes = common[:6] + [C.POINTER(MkhDenseRows), C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                                C.POINTER(MkhTaps), C.c_int32, C.c_void_p]
     L.mkh_solve_dense.restype = C.c_int32
@@ -421,6 +459,7 @@ EXPORTED_SYMBOLS = (
     "mkh_solve_trajectory", "mkh_solve_keyframes", "mkh_solve_trajectory_multistart",
     "mkh_seed_table_create", "mkh_seed_table_destroy", "mkh_seed_table_read", "mkh_seed_table_query",
     "mkh_problem_set_seed_table", "mkh_ladder_select", "mkh_solve_trajectory_ladder",
+    "mkh_ladder_refine", "mkh_solve_trajectory_ladder_refined",
 )
 
 LIE_OPS = {"se3_log": (0, 7, 0, (6,)), "se3_jlog": (1, 7, 0, (6, 6)), "se3_ljacinv": (2, 6, 0, (6, 6)),
@@ -1104,13 +1143,15 @@ class NativeProblem:
                                 ori_threshold: float, max_step_sq: float = float("inf"), rng_seed: int = 0, target_index0: int = 0,
                                 seeds=None, weights=None, qvel_dt: Optional[float] = None, return_all: bool = False,
                                 wave_kernel: bool = False, lane_kernel: bool = False, quad_kernel: bool = False,
-                                seed_table=None) -> TrajectoryLadderOut:
+                                seed_table=None, refine: bool = False) -> TrajectoryLadderOut:
         """mkh_solve_trajectory_ladder: `n_seeds` IK solutions per waypoint — multi-start's loops on the (B·T) flattened targets,
         seed 0 of every rung the row of q itself, the others drawn, taken from `seeds` (B, T, S, nq) or from `seed_table`
         (queried with every waypoint's own targets) — then ladder_select's search and the gather of the chosen nodes, in one
         call.  frame_targets (B, T, n_frame, 7); posture / CoM targets held for the whole call, (n, w), or (B, T, n, w).  The
         handle needs max_batch >= n_seeds; B·T·n_seeds loops beyond max_batch run in chunks of whole rungs.  numpy in → numpy
-        out (synchronous); torch CUDA tensors in → torch tensors out on the current stream, no host copy."""
+        out (synchronous); torch CUDA tensors in → torch tensors out on the current stream, no host copy.  With `refine` the
+        path is re-tracked across its breaks and lost nodes behind the search (mkh_solve_trajectory_ladder_refined; the handle
+        then needs max_batch >= B as well) and `tracked`, `repaired`, `refined` are returned with it."""
         if seeds is not None and seed_table is not None:
             raise ValueError("seeds and seed_table are two sources of the same starts: pass one of them")
         m = self.nmodel.model
@@ -1131,6 +1172,8 @@ class NativeProblem:
         check_ladder_shape(S, T, float(max_step_sq))
         if S > self.max_batch:
             raise MinkHipError(f"n_seeds={S} exceeds max_batch={self.max_batch} of this problem")
+        if refine and B > self.max_batch:
+            raise MinkHipError(f"B={B} exceeds max_batch={self.max_batch} of this problem (a sweep of the refinement is one launch)")
         flags = (FLAG_WAVE_KERNEL if wave_kernel else 0) | (FLAG_LANE_KERNEL if lane_kernel else 0) | \
             (FLAG_QUAD_KERNEL if quad_kernel else 0)
         prep, empty, ptr, stream, devp = _call_kit(q)
@@ -1174,14 +1217,112 @@ class NativeProblem:
         io.waypoint_dt = float(qvel_dt) if qvel_dt is not None else 0.0
         for n, x in {**out, **every}.items():
             setattr(io, n, ptr(x))
+        rio, extra = None, (None, None, None)
+        if refine:
+            extra = (empty((B, T), i4), empty((B, T), i4), empty((B,), i4))
+            rio = MkhLadderRefineIO()
+            rio.tracked_out, rio.repaired, rio.refined = (ptr(x) for x in extra)
         with self._lock, _attached(self, seed_table):
-            _check(lib().mkh_solve_trajectory_ladder(self.handle, B, T, S, ptr(q), ptr(frame_targets), ptr(posture_target),
-                                                     ptr(com_target), float(dt), float(damping), max_iters, float(pos_threshold),
-                                                     float(ori_threshold), int(rng_seed) & (2 ** 64 - 1), int(target_index0),
-                                                     C.byref(io), flags, stream))
+            _check(lib().mkh_solve_trajectory_ladder_refined(
+                self.handle, B, T, S, ptr(q), ptr(frame_targets), ptr(posture_target), ptr(com_target), float(dt), float(damping),
+                max_iters, float(pos_threshold), float(ori_threshold), int(rng_seed) & (2 ** 64 - 1), int(target_index0),
+                C.byref(io), C.byref(rio) if rio is not None else None, flags, stream))
         return TrajectoryLadderOut(*[out[n] for n in ("q_traj", "v_traj", "status", "iters", "converged", "node_index", "n_tracked",
                                                        "n_breaks", "path_length", "edge_break", "qvel")],
-                                   *[every[n] for n in ("q_all", "v_all", "status_all", "iters_all", "converged_all", "seeds_out")])
+                                   *[every[n] for n in ("q_all", "v_all", "status_all", "iters_all", "converged_all", "seeds_out")],
+                                   *extra)
+
+    def ladder_refine(self, q, q_path, tracked=None, frame_targets=None, posture_target=None, com_target=None, dt: float = 1e-2,
+                      damping: float = 1e-12, *, max_iters: int, pos_threshold: float, ori_threshold: float,
+                      max_step_sq: float = float("inf"), weights=None, v=None, status=None, iters=None, converged=None,
+                      wave_kernel: bool = False, lane_kernel: bool = False, quad_kernel: bool = False) -> LadderRefineOut:
+        """mkh_ladder_refine: the refinement pass of include/minkhip.h "THE RULE OF THE REFINEMENT" over the caller's path —
+        q (B, nq) the current postures, q_path (B, T, nq), tracked (B, T) (None: every node), the targets in
+        solve_trajectory_ladder's shapes, the loop parameters of the re-tracking sweeps, the squared break gate, weights (nv,)
+        >= 0.  `v` (B, T, nv), `status`, `iters`, `converged` (B, T): what the caller knows of its path's nodes; copies come
+        back with the rows of repaired nodes replaced.  numpy in → numpy out (synchronous); torch CUDA tensors in → torch
+        tensors out on the current stream, no host copy."""
+        m = self.nmodel.model
+        B, max_iters = int(q.shape[0]), int(max_iters)
+        if max_iters < 1:
+            raise ValueError("max_iters must be >= 1")
+        if not (float(pos_threshold) >= 0.0 and float(ori_threshold) >= 0.0):
+            raise ValueError("thresholds must be >= 0: the refinement's loops run in threshold mode only")
+        if self.n_dense_rows or self.n_dense_limit_rows or self.dense_limit_box:
+            raise ValueError("dense (plugin) rows are evaluated by the caller at q: no fused loop, no ladder refinement")
+        if not self.n_frame:
+            raise ValueError("a ladder refinement needs at least one frame task to test the thresholds on")
+        if q_path is None or len(q_path.shape) != 3 or tuple(q_path.shape) != (B, int(q_path.shape[1]), m.nq):
+            raise ValueError(f"q_path must have shape ({B}, T, {m.nq}), got {None if q_path is None else tuple(q_path.shape)}")
+        T = int(q_path.shape[1])
+        check_ladder_shape(1, T, float(max_step_sq))
+        if B > self.max_batch:
+            raise MinkHipError(f"B={B} exceeds max_batch={self.max_batch} of this problem")
+        flags = (FLAG_WAVE_KERNEL if wave_kernel else 0) | (FLAG_LANE_KERNEL if lane_kernel else 0) | \
+            (FLAG_QUAD_KERNEL if quad_kernel else 0)
+        prep, empty, ptr, stream, devp = _call_kit(q)
+        flags |= devp
+        q, q_path, frame_targets = prep(q), prep(q_path), prep(frame_targets)
+        posture_target, com_target, weights = prep(posture_target), prep(com_target), prep(weights)
+        if tuple(q.shape) != (B, m.nq):
+            raise ValueError(f"q must have shape (B, {m.nq}), got {tuple(q.shape)}")
+        if frame_targets is None or tuple(frame_targets.shape) != (B, T, self.n_frame, 7):
+            raise ValueError(f"frame_targets must have shape ({B}, {T}, {self.n_frame}, 7), got "
+                             f"{None if frame_targets is None else tuple(frame_targets.shape)}")
+
+        def held_or_rows(x, n, w, name, flag):
+            if x is None:
+                raise ValueError(f"{name} is required")
+            if tuple(x.shape) == (n, w):
+                return 0
+            if tuple(x.shape) == (B, T, n, w):
+                return flag
+            raise ValueError(f"{name} must have shape ({n}, {w}) or ({B}, {T}, {n}, {w}), got {tuple(x.shape)}")
+
+        if self.n_posture:
+            flags |= held_or_rows(posture_target, self.n_posture, m.nq, "posture_target", FLAG_POSTURE_BATCHED)
+        if self.n_com:
+            flags |= held_or_rows(com_target, self.n_com, 3, "com_target", FLAG_COM_BATCHED)
+        if weights is not None and tuple(weights.shape) != (m.nv,):
+            raise ValueError(f"weights must have shape ({m.nv},), got {tuple(weights.shape)}")
+
+        def i32_copy(x, name, flag_like=False):
+            """A caller's (B, T) integers as a fresh int32 array of the call's kind (flags: 0 / 1)."""
+            if tuple(x.shape) != (B, T):
+                raise ValueError(f"{name} must have shape ({B}, {T}), got {tuple(x.shape)}")
+            if devp:
+                import torch
+                x = torch.as_tensor(x).to(device=q.device)
+                return ((x != 0) if flag_like else x).to(dtype=torch.int32).contiguous().clone()
+            x = np.asarray(x)
+            return np.array((x != 0) if flag_like else x, dtype=np.int32, order="C")
+
+        if tracked is None:
+            tracked = empty((B, T), np.int32)
+            tracked[...] = 1
+        else:
+            tracked = i32_copy(tracked, "tracked", True)
+        f8, i4 = np.float64, np.int32
+        if v is not None:
+            if tuple(v.shape) != (B, T, m.nv):
+                raise ValueError(f"v must have shape ({B}, {T}, {m.nv}), got {tuple(v.shape)}")
+            v = prep(v).clone() if devp else np.array(v, dtype=f8, order="C")
+        status = None if status is None else i32_copy(status, "status")
+        iters = None if iters is None else i32_copy(iters, "iters")
+        converged = None if converged is None else i32_copy(converged, "converged")
+        out = {"q_path_out": empty((B, T, m.nq), f8), "tracked_out": empty((B, T), i4), "repaired": empty((B, T), i4),
+               "refined": empty((B,), i4), "edge_break": empty((B, T), i4), "n_tracked": empty((B,), i4),
+               "n_breaks": empty((B,), i4), "path_length": empty((B,), f8), "v": v, "status": status, "iters": iters,
+               "converged": converged}
+        io = MkhLadderRefineIO()
+        io.weights, io.max_step_sq = ptr(weights), float(max_step_sq)
+        for n, x in out.items():
+            setattr(io, n, ptr(x))
+        with self._lock:
+            _check(lib().mkh_ladder_refine(self.handle, B, T, ptr(q), ptr(q_path), ptr(tracked), ptr(frame_targets),
+                                           ptr(posture_target), ptr(com_target), float(dt), float(damping), max_iters,
+                                           float(pos_threshold), float(ori_threshold), C.byref(io), flags, stream))
+        return LadderRefineOut(*[out[n] for n in LADDER_REFINE_IO_FIELDS[2:]])
 
     def _solve_trajectory(self, q, frame_targets, posture_target, com_target, dt, damping, n_steps, until, qvel_dt, tm,
                           warm_start, wave_kernel, lane_kernel, quad_kernel, keys=None, cands=None):

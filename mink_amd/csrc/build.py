@@ -322,6 +322,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     jobs.append((os.path.join(HERE, "keyframes.hip"), os.path.join(BUILD, "keyframes.o")))     # target blends between keyframes of mkh_solve_keyframes
     jobs.append((os.path.join(HERE, "trajectory_multistart.hip"), os.path.join(BUILD, "trajectory_multistart.o")))   # path scoring / selection / gather of mkh_solve_trajectory_multistart
     jobs.append((os.path.join(HERE, "ladder.hip"), os.path.join(BUILD, "ladder.o")))   # dynamic program / back-trace / gather of mkh_ladder_select and mkh_solve_trajectory_ladder
+    jobs.append((os.path.join(HERE, "ladder_refine.hip"), os.path.join(BUILD, "ladder_refine.o")))   # step / guard kernels of mkh_ladder_refine
 
     def compile_one(job):
         src, obj = job

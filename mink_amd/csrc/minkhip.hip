@@ -156,6 +156,11 @@ enum WsRole {
   // flags, the starts a host caller asked for, q fanned out to the (B·T) targets of the multi-start launch, and the search's
   // break masks | back-pointers
   WS_L_Q, WS_L_V, WS_L_ST, WS_L_IT, WS_L_CV, WS_L_TRK, WS_L_STARTS, WS_L_Q0, WS_L_PRED,
+  // a ladder refinement: the working path r and the loops' velocities of its repaired nodes, (B, T, .); R_I32: tracked |
+  // repaired | status | iters | converged | break bits of r, (B, T) each; what one loop launch reads and writes — R_X: start | x
+  // | v, R_XI: status | iters | converged | bad flags, (B, .) each; a host caller's path and flags as they came (IN_PATH,
+  // IN_TRK); OUT_REF: tracked_out | repaired (B, T) | refined (B,) of a host-pointer call
+  WS_R_Q, WS_R_V, WS_R_I32, WS_R_X, WS_R_XI, WS_IN_PATH, WS_IN_TRK, WS_OUT_REF,
   WS_COUNT
 };
 
@@ -2034,11 +2039,166 @@ int32_t mkh_ladder_select(MkhProblem* p, int32_t B, int32_t T, int32_t S, const 
   return st.finish();
 }
 
+// The refinement pass (include/minkhip.h "THE RULE OF THE REFINEMENT") on device arrays, into device outputs, on the call's stream:
+// the targets' time-major slabs as mkh_solve_trajectory builds them, the working path, then per waypoint of the two sweeps one
+// step kernel and one loop launch through run(), and the guard.  Returns the first refusal of a loop launch; HIP errors are
+// latched in `st`.
+static int32_t refine_pass(Stager& st, int B, int T, const double* d_q, const double* d_path, const int32_t* d_trk, const double* d_ft,
+                           const double* d_pt, const double* d_ct, double dt, double damping, int32_t max_iters, double pos_threshold,
+                           double ori_threshold, const double* d_w, double max_step_sq, const mkh::LrOut& out, int32_t flags,
+                           void* hip_stream) {
+  MkhProblem* const p = st.p;
+  const DeviceProblem& P = p->dev;
+  hipStream_t stream = st.stream;
+  const bool pbat = (flags & MKH_FLAG_POSTURE_BATCHED) != 0, cbat = (flags & MKH_FLAG_COM_BATCHED) != 0;
+  const size_t Bz = B, Tz = T, R = Bz * Tz, nq = P.nq, nv = P.nv, f8 = sizeof(double), i4 = sizeof(int32_t);
+  const size_t ft_w = (size_t)P.n_frame * 7, pt_w = (size_t)P.n_posture * nq, ct_w = (size_t)P.n_com * 3;
+  auto time_major = [&](WsRole role, const double* src, size_t w) -> const double* {
+    double* const dst = st.f64(role, R * w);
+    ST_LAUNCH(st, launch_tj_gather(stream, src, dst, B, T, (int)w));
+    return dst;
+  };
+  if (ft_w) d_ft = time_major(WS_TM_FT, d_ft, ft_w);
+  if (pt_w && pbat) d_pt = time_major(WS_TM_PT, d_pt, pt_w);
+  if (ct_w && cbat) d_ct = time_major(WS_TM_CT, d_ct, ct_w);
+  const size_t pt_step = (pt_w && pbat) ? Bz * pt_w : 0, ct_step = (ct_w && cbat) ? Bz * ct_w : 0;
+  mkh::LrWork w;
+  w.r = st.f64(WS_R_Q, R * nq); w.r_v = st.f64(WS_R_V, R * nv);
+  w.r_trk = st.i32(WS_R_I32, 6 * R);
+  w.r_rep = w.r_trk + R; w.r_st = w.r_trk + 2 * R; w.r_it = w.r_trk + 3 * R; w.r_cv = w.r_trk + 4 * R; w.r_eb = w.r_trk + 5 * R;
+  w.start = st.f64(WS_R_X, Bz * (2 * nq + nv)); w.x = w.start + Bz * nq; w.xv = w.x + Bz * nq;
+  w.xst = st.i32(WS_R_XI, 4 * Bz); w.xit = w.xst + Bz; w.xcv = w.xst + 2 * Bz; w.bad = w.xst + 3 * Bz;
+  if (!st.ok()) return MKH_OK;
+  st.latch(hipMemcpyAsync(w.r, d_path, R * nq * f8, hipMemcpyDeviceToDevice, stream));
+  st.latch(hipMemcpyAsync(w.r_trk, d_trk, R * i4, hipMemcpyDeviceToDevice, stream));
+  st.latch(hipMemsetAsync(w.r_rep, 0, R * i4, stream));
+  const int32_t loop_flags = (flags & ~MKH_FLAG_WARM_START) | MKH_FLAG_DEVICE_PTRS;
+  const int njnt = p->model->njnt;
+  const int32_t* const jnt = p->ws[WS_JNT].i32();
+  auto step = [&](int ct, int cdir, int nt, int ndir) {
+    ST_LAUNCH(st, launch_lr_step(stream, B, T, (int)nq, (int)nv, njnt, jnt, d_q, d_w, max_step_sq, ct, cdir, nt, ndir, w));
+  };
+  auto loop = [&](size_t t) -> int32_t {
+    if (!st.ok()) return MKH_OK;
+    return run(p, B, w.start, d_ft ? d_ft + t * Bz * ft_w : nullptr, d_pt ? d_pt + t * pt_step : nullptr,
+               d_ct ? d_ct + t * ct_step : nullptr, dt, damping, w.xv, w.xst, nullptr, loop_flags, hip_stream, max_iters, w.x, nullptr,
+               pos_threshold, ori_threshold, w.xit, w.xcv);
+  };
+  step(-1, 1, 0, 1);
+  for (int t = 0; t < T; ++t) {                              // forward; its last commit decides the first backward waypoint
+    if (const int32_t rc = loop(t)) return rc;
+    if (t + 1 < T) step(t, 1, t + 1, 1); else step(t, 1, T - 2, -1);       // (T = 1: T - 2 < 0, nothing follows)
+  }
+  for (int t = T - 2; t >= 0; --t) {                         // backward
+    if (const int32_t rc = loop(t)) return rc;
+    step(t, -1, t - 1, -1);
+  }
+  ST_LAUNCH(st, launch_lr_guard(stream, B, T, (int)nq, (int)nv, njnt, jnt, d_q, d_w, max_step_sq, d_path, d_trk, w, out));
+  return MKH_OK;
+}
+
+// What both refining entry points refuse about the loops of the pass.
+static int32_t refine_refuse(const MkhProblem* p, int32_t B, int32_t T, double max_step_sq, int32_t max_iters, double dt,
+                             double pos_threshold, double ori_threshold, const char* who) {
+  if (B < 1) return fail(MKH_E_INVALID, "%s: B = %d must be >= 1", who, B);
+  if (T < 1) return fail(MKH_E_INVALID, "%s: T = %d must be >= 1", who, T);
+  if (T > 65535) return fail(MKH_E_LIMIT, "%s: T = %d waypoints, at most 65535", who, T);
+  if (!(max_step_sq >= 0.0)) return fail(MKH_E_INVALID, "%s: max_step_sq = %g must be >= 0 (+inf: no gate)", who, max_step_sq);
+  if ((long long)B * T > 0x7fffffffLL) return fail(MKH_E_LIMIT, "%s: B * T = %lld rows", who, (long long)B * T);
+  if (max_iters < 1) return fail(MKH_E_INVALID, "max_iters must be >= 1");
+  if (!(dt > 0.0)) return fail(MKH_E_INVALID, "dt must be > 0");
+  if (!(pos_threshold >= 0.0) || !(ori_threshold >= 0.0))
+    return fail(MKH_E_INVALID, "%s: thresholds must be >= 0 (a fixed count leaves no tracked flag to judge a repair by)", who);
+  if (B > p->max_batch) return fail(MKH_E_INVALID, "%s: B=%d exceeds max_batch=%d of this problem (a sweep's loop launch is one chunk)", who, B, p->max_batch);
+  return MKH_OK;
+}
+
+int32_t mkh_ladder_refine(MkhProblem* p, int32_t B, int32_t T, const double* q, const double* q_path, const int32_t* tracked_path,
+                          const double* frame_targets, const double* posture_target, const double* com_target, double dt,
+                          double damping, int32_t max_iters, double pos_threshold, double ori_threshold, const MkhLadderRefineIO* io,
+                          int32_t flags, void* hip_stream) {
+  const char* const who = "mkh_ladder_refine";
+  if (!p) return fail(MKH_E_INVALID, "null problem");
+  if (!io) return fail(MKH_E_INVALID, "%s: io is required", who);
+  if (const int32_t rc = refine_refuse(p, B, T, io->max_step_sq, max_iters, dt, pos_threshold, ori_threshold, who)) return rc;
+  if (!q_path || !tracked_path) return fail(MKH_E_INVALID, "%s: q_path and tracked_path are required", who);
+  if (!io->q_path_out || !io->tracked_out || !io->repaired || !io->refined || !io->edge_break || !io->n_tracked || !io->n_breaks ||
+      !io->path_length)
+    return fail(MKH_E_INVALID, "%s: io's outputs q_path_out, tracked_out, repaired, refined, edge_break, n_tracked, n_breaks, "
+                               "path_length are required", who);
+  const DeviceProblem& P = p->dev;
+  if (const int32_t rc = refuse_inputs(P, q, frame_targets, posture_target, com_target, who, "ladder refinement")) return rc;
+  const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
+  if (!devp)
+    if (const int32_t rc = ladder_weights_refuse(io->weights, P.nv, who)) return rc;
+  HIP_OK(hipSetDevice(p->model->device));
+  if (const int32_t rc = ms_build_tables(p)) return rc;
+  const bool pbat = (flags & MKH_FLAG_POSTURE_BATCHED) != 0, cbat = (flags & MKH_FLAG_COM_BATCHED) != 0;
+  Stager st{p, (hipStream_t)hip_stream, devp, "ladder_refine"};
+  const size_t Bz = B, R = Bz * T, nq = P.nq, nv = P.nv, f8 = sizeof(double), i4 = sizeof(int32_t);
+  const size_t ft_w = (size_t)P.n_frame * 7, pt_w = (size_t)P.n_posture * nq, ct_w = (size_t)P.n_com * 3;
+  const double* const d_q = st.up(WS_IN_Q, q, Bz * nq);
+  const double* const d_path = st.up(WS_IN_PATH, q_path, R * nq);
+  const double* const d_ft = st.up(WS_IN_FT, frame_targets, R * ft_w);
+  const double* const d_pt = pt_w ? st.up(WS_IN_PT, posture_target, pt_w * (pbat ? R : 1)) : posture_target;
+  const double* const d_ct = ct_w ? st.up(WS_IN_CT, com_target, ct_w * (cbat ? R : 1)) : com_target;
+  const double* const d_w = st.up(WS_IN_W, io->weights, nv);
+  const int32_t* d_trk = tracked_path;
+  mkh::LrOut o{io->q_path_out, io->v, io->path_length, io->tracked_out, io->repaired, io->refined, io->edge_break, io->n_tracked,
+               io->n_breaks, io->status, io->iters, io->converged};
+  if (!devp) {
+    int32_t* const t = st.i32(WS_IN_TRK, R);
+    if (t) st.latch(hipMemcpyAsync(t, tracked_path, R * i4, hipMemcpyHostToDevice, st.stream));
+    d_trk = t;
+    o.q = st.f64(WS_OUT_Q, R * nq);
+    o.path_length = st.f64(WS_OUT_LEN, Bz);
+    o.tracked = st.i32(WS_OUT_REF, 2 * R + Bz); o.repaired = o.tracked + R; o.refined = o.tracked + 2 * R;
+    o.edge_break = st.i32(WS_OUT_PICK, R + 2 * Bz); o.n_tracked = o.edge_break + R; o.n_breaks = o.n_tracked + Bz;
+    // the optional rows: the caller's values go in, the repaired rows are replaced, everything comes back
+    o.v = io->v ? st.f64(WS_OUT_V, R * nv) : nullptr;
+    int32_t* const oi = st.i32(WS_OUT_I32, 3 * R);
+    o.status = io->status ? oi : nullptr; o.iters = io->iters ? oi + R : nullptr; o.converged = io->converged ? oi + 2 * R : nullptr;
+    if (st.ok()) {
+      if (o.v) st.latch(hipMemcpyAsync(o.v, io->v, R * nv * f8, hipMemcpyHostToDevice, st.stream));
+      if (o.status) st.latch(hipMemcpyAsync(o.status, io->status, R * i4, hipMemcpyHostToDevice, st.stream));
+      if (o.iters) st.latch(hipMemcpyAsync(o.iters, io->iters, R * i4, hipMemcpyHostToDevice, st.stream));
+      if (o.converged) st.latch(hipMemcpyAsync(o.converged, io->converged, R * i4, hipMemcpyHostToDevice, st.stream));
+    }
+  }
+  if (!st.ok()) return st.finish();
+  if (const int32_t rc = refine_pass(st, B, T, d_q, d_path, d_trk, d_ft, d_pt, d_ct, dt, damping, max_iters, pos_threshold,
+                                     ori_threshold, d_w, io->max_step_sq, o, flags, hip_stream))
+    return st.finish(rc);
+  if (devp) return st.finish();
+  st.down(io->q_path_out, o.q, R * nq * f8);
+  st.down(io->tracked_out, o.tracked, R * i4);
+  st.down(io->repaired, o.repaired, R * i4);
+  st.down(io->refined, o.refined, Bz * i4);
+  st.down(io->edge_break, o.edge_break, R * i4);
+  st.down(io->n_tracked, o.n_tracked, Bz * i4);
+  st.down(io->n_breaks, o.n_breaks, Bz * i4);
+  st.down(io->path_length, o.path_length, Bz * f8);
+  st.down(io->v, o.v, R * nv * f8);
+  st.down(io->status, o.status, R * i4);
+  st.down(io->iters, o.iters, R * i4);
+  st.down(io->converged, o.converged, R * i4);
+  return st.finish();
+}
+
 int32_t mkh_solve_trajectory_ladder(MkhProblem* p, int32_t B, int32_t T, int32_t n_seeds, const double* q,
                                     const double* frame_targets, const double* posture_target, const double* com_target, double dt,
                                     double damping, int32_t max_iters, double pos_threshold, double ori_threshold, uint64_t rng_seed,
                                     int64_t target_index0, const MkhTrajectoryLadderIO* io, int32_t flags, void* hip_stream) {
-  const char* const who = "mkh_solve_trajectory_ladder";
+  return mkh_solve_trajectory_ladder_refined(p, B, T, n_seeds, q, frame_targets, posture_target, com_target, dt, damping, max_iters,
+                                             pos_threshold, ori_threshold, rng_seed, target_index0, io, nullptr, flags, hip_stream);
+}
+
+int32_t mkh_solve_trajectory_ladder_refined(MkhProblem* p, int32_t B, int32_t T, int32_t n_seeds, const double* q,
+                                            const double* frame_targets, const double* posture_target, const double* com_target,
+                                            double dt, double damping, int32_t max_iters, double pos_threshold, double ori_threshold,
+                                            uint64_t rng_seed, int64_t target_index0, const MkhTrajectoryLadderIO* io,
+                                            const MkhLadderRefineIO* refine, int32_t flags, void* hip_stream) {
+  const char* const who = refine ? "mkh_solve_trajectory_ladder_refined" : "mkh_solve_trajectory_ladder";
   if (!p) return fail(MKH_E_INVALID, "null problem");
   if (!io) return fail(MKH_E_INVALID, "%s: io is required", who);
   const int S = n_seeds;
@@ -2053,6 +2213,11 @@ int32_t mkh_solve_trajectory_ladder(MkhProblem* p, int32_t B, int32_t T, int32_t
     return fail(MKH_E_INVALID, "%s: io's outputs q_traj, v_traj, status, iters, converged, node_index, n_tracked, n_breaks, path_length, "
                                "edge_break are required", who);
   if (io->qvel && !(io->waypoint_dt > 0.0)) return fail(MKH_E_INVALID, "qvel needs waypoint_dt > 0");
+  if (refine) {
+    if (const int32_t rc = refine_refuse(p, B, T, io->max_step_sq, max_iters, dt, pos_threshold, ori_threshold, who)) return rc;
+    if (!refine->tracked_out || !refine->repaired || !refine->refined)
+      return fail(MKH_E_INVALID, "%s: refine's outputs tracked_out, repaired, refined are required", who);
+  }
   const DeviceProblem& P = p->dev;
   if (const int32_t rc = refuse_inputs(P, q, frame_targets, posture_target, com_target, who, "ladder")) return rc;
   if (S > p->max_batch) return fail(MKH_E_INVALID, "%s: n_seeds = %d exceeds max_batch=%d of this problem (a rung is one chunk)", who, S, p->max_batch);
@@ -2097,6 +2262,12 @@ int32_t mkh_solve_trajectory_ladder(MkhProblem* p, int32_t B, int32_t T, int32_t
     o_node = st.i32(WS_OUT_PICK, 2 * R + 2 * Bz); o_eb = o_node + R; o_nt = o_node + 2 * R; o_nb = o_nt + Bz;
     o_len = st.f64(WS_OUT_LEN, Bz);
   }
+  // ---- the pass's own outputs (the returned path goes where the search's goes)
+  int32_t *o_trk = nullptr, *o_rep = nullptr, *o_ref = nullptr;
+  if (refine) {
+    o_trk = refine->tracked_out; o_rep = refine->repaired; o_ref = refine->refined;
+    if (!devp) { o_trk = st.i32(WS_OUT_REF, 2 * R + Bz); o_rep = o_trk + R; o_ref = o_trk + 2 * R; }
+  }
   if (!st.ok()) return st.finish();
   // ---- the rungs: multi-start on the (B·T) flattened targets, whole rungs per chunk of at most max_batch loops
   const size_t per = (size_t)p->max_batch / S;
@@ -2122,6 +2293,14 @@ int32_t mkh_solve_trajectory_ladder(MkhProblem* p, int32_t B, int32_t T, int32_t
   ST_LAUNCH(st, launch_ladder_gather_i32(stream, l_st, o_st, o_node, (long long)R, S));
   ST_LAUNCH(st, launch_ladder_gather_i32(stream, l_it, o_it, o_node, (long long)R, S));
   ST_LAUNCH(st, launch_ladder_gather_i32(stream, l_cv, o_cv, o_node, (long long)R, S));
+  if (refine) {
+    // the chosen nodes' flags are the path's; the pass reads path and flags in place and writes the returned ones over them
+    ST_LAUNCH(st, launch_ladder_gather_i32(stream, l_trk, o_trk, o_node, (long long)R, S));
+    const mkh::LrOut o{o_q, o_v, o_len, o_trk, o_rep, o_ref, o_eb, o_nt, o_nb, o_st, o_it, o_cv};
+    if (const int32_t rc = refine_pass(st, B, T, d_q, o_q, o_trk, d_ft, d_pt, d_ct, dt, damping, max_iters, pos_threshold,
+                                       ori_threshold, d_w, io->max_step_sq, o, flags, hip_stream))
+      return st.finish(rc);
+  }
   if (o_qvel)
     ST_LAUNCH(st, launch_tj_qvel(stream, p->ws[WS_JNT].i32(), p->model->njnt, B, T, (int)nq, d_q, o_q, (long long)(T * nq), (long long)nq,
                                  io->waypoint_dt, o_qvel, (long long)(T * nv), (long long)nv, 0));
@@ -2143,6 +2322,11 @@ int32_t mkh_solve_trajectory_ladder(MkhProblem* p, int32_t B, int32_t T, int32_t
   st.down(io->iters_all, l_it, N * i4);
   st.down(io->converged_all, l_cv, N * i4);
   st.down(io->seeds_out, l_starts, N * nq * f8);
+  if (refine) {
+    st.down(refine->tracked_out, o_trk, R * i4);
+    st.down(refine->repaired, o_rep, R * i4);
+    st.down(refine->refined, o_ref, Bz * i4);
+  }
   return st.finish();
 }
 

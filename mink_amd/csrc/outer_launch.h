@@ -1,6 +1,6 @@
 // Launchers of the small kernels around the loop launches of the outer-loop entry points (mkh_solve_multistart,
-// mkh_solve_trajectory, mkh_solve_keyframes, mkh_solve_trajectory_multistart, the two ladder calls) and of the seed tables in
-// front of them: declared once, for the six files that define them and for minkhip.hip, which calls them — a signature that
+// mkh_solve_trajectory, mkh_solve_keyframes, mkh_solve_trajectory_multistart, the ladder calls) and of the seed tables in
+// front of them: declared once, for the seven files that define them and for minkhip.hip, which calls them — a signature that
 // drifts fails to compile in the file that drifted.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -74,5 +74,26 @@ hipError_t launch_ladder_gather(hipStream_t stream, const double* all, double* o
                                 int W);
 hipError_t launch_ladder_gather_i32(hipStream_t stream, const int32_t* all, int32_t* out, const int32_t* node_index, long long rows,
                                     int S);
+// ladder refinement (ladder_refine.hip): the pass's private arrays — the working path r (B, T, nq) with its flags, the loops'
+// rows of the repaired nodes, the break bits of r, and what one loop launch reads (start) and writes (x …) with the bad flags
+// beside it, (B, .) each — and the device outputs of the guard (v … converged: optional).  launch_lr_step commits waypoint
+// commit_t of the sweep in direction commit_dir (+1 / −1; commit_t < 0: nothing) and decides waypoint next_t of the sweep in
+// direction next_dir (next_t < 0: nothing); launch_lr_guard prices r and the input path p, and returns the better one.
+struct LrWork {
+  double *r, *r_v;
+  int32_t *r_trk, *r_rep, *r_st, *r_it, *r_cv, *r_eb;
+  double *start, *x, *xv;
+  int32_t *xst, *xit, *xcv, *bad;
+};
+struct LrOut {
+  double *q, *v, *path_length;
+  int32_t *tracked, *repaired, *refined, *edge_break, *n_tracked, *n_breaks, *status, *iters, *converged;
+};
+hipError_t launch_lr_step(hipStream_t stream, int B, int T, int nq, int nv, int njnt, const int32_t* jnt, const double* q0,
+                          const double* weights, double max_step_sq, int commit_t, int commit_dir, int next_t, int next_dir,
+                          const LrWork& w);
+hipError_t launch_lr_guard(hipStream_t stream, int B, int T, int nq, int nv, int njnt, const int32_t* jnt, const double* q0,
+                           const double* weights, double max_step_sq, const double* p, const int32_t* p_trk, const LrWork& w,
+                           const LrOut& o);
 
 }  // namespace mkh

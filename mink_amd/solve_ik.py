@@ -966,6 +966,31 @@ class LadderResult(NamedTuple):
     seeds: Optional[np.ndarray] = None
 
 
+class RefinedLadderResult(NamedTuple):
+    """Result of solve_ik_trajectory_ladder(refine=True): LadderResult's fields, in its order, for the path the refinement pass
+    returned, and behind them `repaired` (B, T) — 0 kept, 1 / 2 replaced by the forward / backward sweep — and `refined` (B,):
+    where the path differs from the search's.  `node_index` names the replaced node at a repaired waypoint."""
+    q: np.ndarray
+    v: np.ndarray
+    status: np.ndarray
+    iters: np.ndarray
+    converged: np.ndarray
+    node_index: np.ndarray
+    n_tracked: np.ndarray
+    n_breaks: np.ndarray
+    path_length: np.ndarray
+    edge_break: np.ndarray
+    qvel: Optional[np.ndarray] = None
+    q_all: Optional[np.ndarray] = None
+    v_all: Optional[np.ndarray] = None
+    status_all: Optional[np.ndarray] = None
+    iters_all: Optional[np.ndarray] = None
+    converged_all: Optional[np.ndarray] = None
+    seeds: Optional[np.ndarray] = None
+    repaired: Optional[np.ndarray] = None
+    refined: Optional[np.ndarray] = None
+
+
 class LadderPath(NamedTuple):
     """Result of ladder_path: the chosen `node_index` (B, T), the nodes along it `q` (B, T, nq), `edge_break` (B, T), and per
     instance `n_tracked`, `n_breaks`, `path_length` — without the leading axis for an unbatched configuration."""
@@ -987,6 +1012,22 @@ def _max_step_sq(max_step) -> float:
     return max_step * max_step
 
 
+def _outside_limits(message: str) -> exceptions.NotWithinConfigurationLimits:
+    """NotWithinConfigurationLimits for a status bit of a fused loop: the bit names no joint and no value (the exception's own
+    constructor formats both), so the message is the caller's."""
+    e = exceptions.NotWithinConfigurationLimits.__new__(exceptions.NotWithinConfigurationLimits)
+    exceptions.MinkError.__init__(e, message)
+    return e
+
+
+def _need_frame_task(tasks, what: str) -> None:
+    """The threshold-terminated loops test their thresholds on frame tasks: judged on the objects, before a handle exists."""
+    from .tasks import FrameTask
+
+    if not any(isinstance(t, FrameTask) for t in tasks):
+        raise ValueError(f"{what} needs at least one frame task to test the thresholds on")
+
+
 def _ladder_weights(weights, nv: int):
     weights = _optional_array(weights, "weights", (nv,))
     if weights is not None and not (weights >= 0.0).all():
@@ -999,7 +1040,7 @@ def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt
                                seeds=None, seed_table: Optional["SeedTable"] = None, rng_seed: int = 0,
                                qvel_dt: Optional[float] = None, return_all: bool = False, update: bool = True,
                                max_instances: int = 1 << 20, damping: float = 1e-12, limits: Optional[Sequence] = None,
-                               safety_break: bool = False, solver: str = "mi355x") -> LadderResult:
+                               safety_break: bool = False, solver: str = "mi355x", refine: bool = False):
     """Track a time sequence of targets through a ladder graph: `n_seeds` IK solutions per waypoint, solved independently of
     each other, and a dynamic program on the device that picks one per waypoint — the path that is complete first, free of
     joint-space jumps second and shortest third (the rule in full: include/minkhip.h).  Where solve_ik_trajectory_multistart
@@ -1015,7 +1056,12 @@ def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt
     the lowest node index.  Limits warnings and SolverError follow solve_ik_trajectory's rules on the CHOSEN nodes only
     (`safety_break`, as in mink: False keeps going — the warning — where True raises NotWithinConfigurationLimits).  With
     `update` the configuration is left at the chosen q[:, -1].  The instances are walked in chunks of as many as keep
-    chunk·T·n_seeds within `max_instances`; a multi-device configuration shards by instance; the result depends on neither."""
+    chunk·T·n_seeds within `max_instances`; a multi-device configuration shards by instance; the result depends on neither.
+
+    `refine=True` runs refine_path's pass behind the search, in the same call on the device: the chosen path is re-tracked
+    across its breaks and lost nodes with the same loop parameters, gate and weights, and comes back only where that makes its
+    key strictly smaller — the result is never worse than the search's.  Everything above then speaks of the returned path,
+    and the result is a RefinedLadderResult: LadderResult's fields and, behind them, `repaired` and `refined`."""
     del solver
     S, max_iters = int(n_seeds), int(max_iters)
     if max_iters < 1:
@@ -1033,6 +1079,7 @@ def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt
     B, nq, nv = configuration.batch_size, configuration.nq, configuration.nv
     seqs, T = _trajectory_targets(configuration, tasks, targets)
     nat.check_ladder_shape(S, T, step_sq)
+    _need_frame_task(tasks, "a ladder")
     if S * T > int(max_instances):
         raise ValueError(f"one instance's ladder has T*n_seeds = {T * S} loops, beyond max_instances = {int(max_instances)}")
     seeds = _host_array(seeds, "seeds")
@@ -1050,16 +1097,18 @@ def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt
               for x in (pt, ct)]
     q = configuration.q_batch
     kw = dict(n_seeds=S, max_iters=max_iters, pos_threshold=float(pos_threshold), ori_threshold=float(ori_threshold),
-              max_step_sq=step_sq, rng_seed=int(rng_seed), weights=weights, qvel_dt=qvel_dt, return_all=bool(return_all))
+              max_step_sq=step_sq, rng_seed=int(rng_seed), weights=weights, qvel_dt=qvel_dt, return_all=bool(return_all),
+              refine=bool(refine))
 
     def job(handle, lo, hi):
-        return handle.solve_trajectory_ladder(q[lo:hi], _rows(ft, 0, lo, hi), _rows(pt, 2, lo, hi), _rows(ct, 2, lo, hi), dt,
-                                              damping, target_index0=lo, seeds=_rows(seeds, 0, lo, hi), seed_table=seed_table, **kw)
+        r = handle.solve_trajectory_ladder(q[lo:hi], _rows(ft, 0, lo, hi), _rows(pt, 2, lo, hi), _rows(ct, 2, lo, hi), dt,
+                                           damping, target_index0=lo, seeds=_rows(seeds, 0, lo, hi), seed_table=seed_table, **kw)
+        return RefinedLadderResult(*r[:17], r.repaired, r.refined)
 
-    res = _join(LadderResult, _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job))
+    res = _join(RefinedLadderResult, _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job))
     if safety_break and ((res.status & nat.ST_OUTSIDE_LIMITS) != 0).any():
         b, t = (int(x) for x in np.argwhere((res.status & nat.ST_OUTSIDE_LIMITS) != 0)[0])
-        raise exceptions.NotWithinConfigurationLimits(
+        raise _outside_limits(
             f"solve_ik_trajectory_ladder: the chosen node of (instance, waypoint) = ({b}, {t}) left its configuration limits at "
             "some fused step")
     _status_epilogue(res.status, "solve_ik_trajectory_ladder", "chosen path(s)",
@@ -1068,10 +1117,105 @@ def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt
         configuration.update(res.q[:, -1] if configuration.batched else res.q[0, -1])
     un = configuration._unbatch
     opt = lambda x, as_bool=False: None if x is None else un(x.astype(bool) if as_bool else x)
-    return LadderResult(un(res.q), un(res.v), un(res.status), un(res.iters), un(res.converged.astype(bool)), un(res.node_index),
-                        un(res.n_tracked), un(res.n_breaks), un(res.path_length), un(res.edge_break.astype(bool)),
-                        opt(res.qvel), opt(res.q_all), opt(res.v_all), opt(res.status_all), opt(res.iters_all),
-                        opt(res.converged_all, True), opt(res.seeds))
+    out = LadderResult(un(res.q), un(res.v), un(res.status), un(res.iters), un(res.converged.astype(bool)), un(res.node_index),
+                       un(res.n_tracked), un(res.n_breaks), un(res.path_length), un(res.edge_break.astype(bool)),
+                       opt(res.qvel), opt(res.q_all), opt(res.v_all), opt(res.status_all), opt(res.iters_all),
+                       opt(res.converged_all, True), opt(res.seeds))
+    return RefinedLadderResult(*out, un(res.repaired), un(res.refined.astype(bool))) if refine else out
+
+
+class RefinedPath(NamedTuple):
+    """Result of refine_path, (B, T, ·) / (B,) — without the leading axis for an unbatched configuration: the returned path `q`
+    with its `tracked` flags; `repaired`: 0 kept, 1 / 2 replaced by the forward / backward sweep; `refined`: whether the
+    re-tracked path was returned (else everything is the input path's); `edge_break`, `n_tracked`, `n_breaks`, `path_length` of
+    the returned path; `v`, `status`, `iters`, `converged` of the loops of the repaired nodes (zeros at kept nodes)."""
+    q: np.ndarray
+    tracked: np.ndarray
+    repaired: np.ndarray
+    refined: np.ndarray
+    edge_break: np.ndarray
+    n_tracked: np.ndarray
+    n_breaks: np.ndarray
+    path_length: np.ndarray
+    v: np.ndarray
+    status: np.ndarray
+    iters: np.ndarray
+    converged: np.ndarray
+
+
+def refine_path(configuration: Configuration, tasks: Sequence, dt: float, targets, q_path, tracked=None, max_iters: int = 32,
+                pos_threshold: float = 1e-4, ori_threshold: float = 1e-4, max_step: Optional[float] = None, weights=None,
+                update: bool = True, max_instances: int = 1 << 20, damping: float = 1e-12, limits: Optional[Sequence] = None,
+                safety_break: bool = False, solver: str = "mi355x") -> RefinedPath:
+    """The ladder's refinement pass alone, over the caller's own path: q_path (T, nq) or (B, T, nq) — a ladder's chosen path,
+    a planner's, an earlier call's — with `tracked` (same leading shape, default: every node counts as tracked) and the
+    `targets` of solve_ik_trajectory (no keyframes) the path is meant to follow.
+
+    A working copy of the path is swept forward, then backward.  A waypoint is bad when its node is not tracked or the step
+    from the neighbour the sweep comes from costs more than max_step² (the ladder's edge cost, with `weights`; `max_step` None:
+    only lost nodes are bad; the step from the configuration's q into waypoint 0 is never a break).  A bad waypoint is
+    re-solved by the threshold-terminated loop from that neighbour and the result is taken when it converged without a QP
+    failure and stays within max_step of the neighbour.  The working copy is returned only where its key (untracked nodes,
+    breaks, length) is strictly smaller than the input path's: the result is never worse than what came in (the rule in
+    full: include/minkhip.h).  Each sweep costs T loop launches on the B instances.
+
+    Limits warnings and SolverError follow solve_ik_trajectory's rules on the RETURNED repaired nodes only (`safety_break` as
+    in solve_ik_trajectory_ladder).  With `update` the configuration is left at the returned q[:, -1].  When B exceeds
+    `max_instances` the paths are walked in chunks of instances; a multi-device configuration shards by instance; the result
+    depends on neither."""
+    del solver
+    max_iters = int(max_iters)
+    if max_iters < 1:
+        raise ValueError("max_iters must be >= 1")
+    if int(max_instances) < 1:
+        raise ValueError("max_instances must be >= 1")
+    if pos_threshold is None or ori_threshold is None or not (float(pos_threshold) >= 0.0 and float(ori_threshold) >= 0.0):
+        raise ValueError("thresholds must be >= 0: the refinement's loops run in threshold mode only")
+    step_sq = _max_step_sq(max_step)
+    _refuse_plugin_rows({"dense": [t for t in tasks if t._is_dense()], "dense_limits": [x for x in (limits or ()) if x._is_dense()]},
+                        "refine_path")
+    B, nq, nv = configuration.batch_size, configuration.nq, configuration.nv
+    seqs, T = _trajectory_targets(configuration, tasks, targets)
+    nat.check_ladder_shape(1, T, step_sq)
+    q_path = _host_array(q_path, "q_path")
+    if q_path is None or q_path.shape not in ((T, nq), (B, T, nq)):
+        raise ValueError(f"q_path must have shape {(T, nq)} or {(B, T, nq)}, got {None if q_path is None else q_path.shape}")
+    q_path = np.ascontiguousarray(np.broadcast_to(q_path, (B, T, nq)))
+    if tracked is not None:
+        tracked = np.asarray(tracked.detach().cpu().numpy() if nat._is_torch(tracked) else tracked)
+        if tracked.shape not in ((T,), (B, T)):
+            raise ValueError(f"tracked must have shape {(T,)} or {(B, T)}, got {tracked.shape}")
+        tracked = np.ascontiguousarray(np.broadcast_to(tracked != 0, (B, T)))
+    weights = _ladder_weights(weights, nv)
+    _need_frame_task(tasks, "a ladder refinement")
+    handles, layout, chunk, n_dev = _compile_outer(configuration, tasks, limits, dt, "refine_path", 1, max_instances)
+    ft, pt, ct = _stacked_targets(configuration, layout, seqs, T)
+    pt, ct = [x if x is None or x.ndim != 3 else np.ascontiguousarray(np.broadcast_to(x[:, None], (B, T) + x.shape[1:]))
+              for x in (pt, ct)]
+    q = configuration.q_batch
+
+    def job(handle, lo, hi):
+        n = hi - lo
+        r = handle.ladder_refine(q[lo:hi], q_path[lo:hi], None if tracked is None else tracked[lo:hi], _rows(ft, 0, lo, hi),
+                                 _rows(pt, 2, lo, hi), _rows(ct, 2, lo, hi), dt, damping, max_iters=max_iters,
+                                 pos_threshold=float(pos_threshold), ori_threshold=float(ori_threshold), max_step_sq=step_sq,
+                                 weights=weights, v=np.zeros((n, T, nv)), status=np.zeros((n, T), np.int32),
+                                 iters=np.zeros((n, T), np.int32), converged=np.zeros((n, T), np.int32))
+        return RefinedPath(*r)
+
+    res = _join(RefinedPath, _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job))
+    if safety_break and ((res.status & nat.ST_OUTSIDE_LIMITS) != 0).any():
+        b, t = (int(x) for x in np.argwhere((res.status & nat.ST_OUTSIDE_LIMITS) != 0)[0])
+        raise _outside_limits(
+            f"refine_path: the repaired node of (instance, waypoint) = ({b}, {t}) left its configuration limits at some fused step")
+    _status_epilogue(res.status, "refine_path", "returned path(s)",
+                     "QP failed at {n} of {of} returned nodes (first: (instance, waypoint) = {first}, status {status})")
+    if update:
+        configuration.update(res.q[:, -1] if configuration.batched else res.q[0, -1])
+    un = configuration._unbatch
+    return RefinedPath(un(res.q), un(res.tracked.astype(bool)), un(res.repaired), un(res.refined.astype(bool)),
+                       un(res.edge_break.astype(bool)), un(res.n_tracked), un(res.n_breaks), un(res.path_length), un(res.v),
+                       un(res.status), un(res.iters), un(res.converged.astype(bool)))
 
 
 def ladder_path(configuration: Configuration, q_nodes, tracked=None, max_step: Optional[float] = None, weights=None) -> LadderPath:

@@ -2,7 +2,7 @@
 """Ladder-graph trajectory IK (mkh_solve_trajectory_ladder): what the search costs next to the loops whose rungs it reads, and
 the whole call next to the two things a caller would do instead.
 
-    python tools/bench_ladder.py [workloads=ur5e_c2:256:8,...] [rounds=5] [T=64] > profiles/r15_ladder.txt
+    python tools/bench_ladder.py [workloads=ur5e_c2:256:8,...] [rounds=5] [T=64] [nohost] > profiles/r15_ladder.txt
 
 Per workload (bench config : B instances : S nodes per waypoint; T waypoints along a joint-space line from the bench batch's
 start; the threshold-terminated loop, up to 20 steps per node), device tensors in and out unless said otherwise:
@@ -14,10 +14,14 @@ start; the threshold-terminated loop, up to 20 steps per node), device tensors i
       numpy over (s', s), instance by instance (tests/ladder_ref.py: costs + search_fast)
   (m) solve_trajectory_multistart at the same B, T, S: S whole candidates tracked through T stream-ordered loop launches of
       B·S rows (its kernels are the parent commit's: adding the ladder moved no code_sha256 of kernel_resources.json)
+  (r) the refined call: (a) with the refinement pass behind its search (mkh_solve_trajectory_ladder_refined) — 2T − 1 loop
+      launches on the B chosen paths, one small kernel between two of them, the guard; (r) − (a) is what the pass costs
+  (t) what those loop launches should cost: solve_trajectory on the B instances, TWICE (2T loop launches of B rows between
+      time-major slabs, no kernel in between); ((r) − (a)) − (t) is the gap the pass leaves to it
 Wall clock around the leg with a device synchronisation at its end, ms per call.  The legs ALTERNATE, `rounds` times after a
 warm-up round ((h): one round beyond 256 instances — it runs for seconds); reported: the median and the (max - min) of each
-leg's rounds.  Complete paths (every waypoint tracked) of (a) and (m) are printed with them: the two calls answer different
-questions on the same targets.
+leg's rounds.  Complete paths (every waypoint tracked) of (a), (r) and (m) are printed with them: the calls answer different
+questions on the same targets.  `nohost` leaves leg (h) out (it runs for tens of seconds at 4 096 instances).
 """
 import os
 import sys
@@ -66,6 +70,7 @@ def main():
     specs = (sys.argv[1] if len(sys.argv) > 1 else DEFAULT).split(",")
     rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 5
     T = int(sys.argv[3]) if len(sys.argv) > 3 else 64
+    host = not (len(sys.argv) > 4 and sys.argv[4] == "nohost")
     if nat.lib().mkh_device_count() < 1:
         raise SystemExit("bench_ladder needs a GPU")
     dev = torch.device("cuda:0")
@@ -109,6 +114,14 @@ def main():
         def leg_m():
             return cand.solve_trajectory_multistart(dq, d_tg, dpt, None, dt, damping, n_steps=MAX_ITERS, **kw)
 
+        def leg_r():
+            return prob.solve_trajectory_ladder(dq, d_tg, dpt, None, dt, damping, max_iters=MAX_ITERS, refine=True, **kw)
+
+        def leg_t():
+            for _ in range(2):
+                out = cand.solve_trajectory(dq, d_tg, dpt, None, dt, damping, n_steps=MAX_ITERS, until=until)
+            return out
+
         def wall(fn):
             torch.cuda.synchronize()
             t0 = time.perf_counter(); out = fn(); torch.cuda.synchronize()
@@ -116,25 +129,36 @@ def main():
 
         ra, rs = leg_a(), leg_s()
         assert torch.equal(ra.node_index, rs.node_index) and torch.equal(ra.q, rs.q), "the call's path is not the search's on its rungs"
-        for fn in (leg_a, leg_s, leg_m):                         # warm-up round
+        for fn in (leg_a, leg_s, leg_m, leg_r, leg_t):           # warm-up round
             wall(fn)
-        ts = {k: [] for k in "ashm"}
+        ts = {k: [] for k in "ashmrt"}
         rh = None
         for r in range(rounds):
             ts["a"].append(wall(leg_a)[0]); ts["s"].append(wall(leg_s)[0]); ts["m"].append(wall(leg_m)[0])
-            if r == 0 or B <= 256:
+            ts["r"].append(wall(leg_r)[0]); ts["t"].append(wall(leg_t)[0])
+            if host and (r == 0 or B <= 256):
                 t, rh = wall(leg_h)
                 ts["h"].append(t)
-        rm = leg_m()
-        assert np.array_equal(rh[1], ra.n_tracked.cpu().numpy()), "the host composition tracks other waypoints than the call"
+        if not host:
+            ts["h"].append(float("nan"))
+        rm, rr = leg_m(), leg_r()
+        assert rh is None or np.array_equal(rh[1], ra.n_tracked.cpu().numpy()), "the host composition tracks other waypoints than the call"
+        worse = ((T - rr.n_tracked > T - ra.n_tracked) | ((rr.n_tracked == ra.n_tracked) & (rr.n_breaks > ra.n_breaks))).any().item()
+        assert not worse, "the refined call returned a path worse than the search's"
         med = {k: float(np.median(v)) for k, v in ts.items()}
         spread = {k: float(np.max(v) - np.min(v)) for k, v in ts.items()}
         cell = lambda k: f"{med[k]:10.3f} [{spread[k]:8.3f}]"
         print(f"{name:8s} B={B:5d} S={S:3d} ({N} loops in {-(-N // prob.max_batch)} launch(es) of kernel {k_loop}): (a) ladder call {cell('a')}  "
               f"(s) search alone {cell('s')} = {100.0 * med['s'] / med['a']:5.2f} % of (a)  (h) host composition {cell('h')} = "
               f"{med['h'] / med['a']:6.2f} x (a)  (m) candidate tracking {cell('m')} = {med['m'] / med['a']:6.2f} x (a)  |  complete paths of {B}: "
-              f"ladder {int((ra.n_tracked == T).sum().item())}, candidate tracking {int((rm.n_tracked == T).sum().item())}; "
+              f"ladder {int((ra.n_tracked == T).sum().item())}, refined {int((rr.n_tracked == T).sum().item())}, candidate tracking "
+              f"{int((rm.n_tracked == T).sum().item())}; "
               f"[{n_bad} nodes with a failure bit]", flush=True)
+        pass_ms = med["r"] - med["a"]
+        print(f"{'':8s} refinement: (r) refined call {cell('r')} = {med['r'] / med['a']:6.3f} x (a); the pass (r) - (a) = {pass_ms:10.3f} ms; "
+              f"(t) two trajectory calls on B {cell('t')}; the pass is {pass_ms / med['t']:6.3f} x (t), gap {pass_ms - med['t']:10.3f} ms; "
+              f"{int(rr.refined.sum().item())} of {B} paths returned re-tracked, {int((rr.repaired != 0).sum().item())} waypoints repaired",
+              flush=True)
         prob.close(); cand.close(); nm.close()
 
 
