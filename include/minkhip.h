@@ -453,6 +453,80 @@ int32_t mkh_solve_multistart(MkhProblem *problem, int32_t B, const double *q, co
                              void *hip_stream);
 
 /*
+ * Distinct solution sets: up to K = n_solutions DIFFERENT solutions per target out of the S that multi-start's loops found,
+ * instead of the one closest to the reference posture — the IK branches of a target, for robots without a closed form, picked
+ * and deduplicated on the device: no B·S rows over the bus.  No counterpart in the reference.
+ *
+ * THE RULE OF THE SET (mkh_select_distinct; mkh_solve_multistart_set runs it on the results of its loops).
+ * One target, S candidates q_0 .. q_{S-1}, K = n_solutions, r = min_distance, a reference posture q_ref and weights w.
+ *   Eligible   multi-start's: the loop converged (converged != 0) and status & ~MKH_ST_OUTSIDE_LIMITS == 0.  For
+ *              mkh_select_distinct: valid[s] != 0, every candidate when valid is NULL.
+ *   Distance   multi-start's, the same device function: d(a, b) = sum_k w_k ((a (-) b)_k)^2, (-) = mj_differentiatePos at
+ *              dt = 1, w = weights (nv,) or ones when NULL.  d_ref(s) = d(q_s, q_ref), a NaN or infinite value replaced by
+ *              DBL_MAX (last among the eligible), as in multi-start's selection.
+ *   For slot j = 0 .. K-1, while an eligible candidate is left uncovered:
+ *     the REPRESENTATIVE of slot j is the uncovered eligible candidate with the smallest d_ref, ties to the lowest index;
+ *     slot j then COVERS every not-yet-covered eligible candidate s with d(q_s, q_rep) <= r·r; a comparison with NaN is false,
+ *     so such a candidate stays uncovered.  The representative itself is always covered, and so is every candidate whose row
+ *     is a bitwise copy of the representative's, whatever the arithmetic of d gives for them (the quaternion product
+ *     conj(q) q of a ball or free joint need not round to the identity);
+ *     multiplicity[j] = the number of candidates covered in that step.
+ *   The walk stops when no uncovered eligible candidate is left, or after K slots.
+ * This is the greedy walk through the eligible candidates in ascending (d_ref, index) that keeps a candidate iff it is farther
+ * than r from every candidate kept before it; the cover formulation is the one that runs in parallel.
+ * Two solutions that differ by a full turn of an unlimited (or multi-turn) hinge are 2 pi apart in (-) and therefore DIFFERENT
+ * solutions: for a planner they are — reaching one from the other is a full turn of that joint.  r = 0 merges exact
+ * duplicates only.
+ *
+ * Outputs.  Per target: n_distinct (B,) the slots filled, at most K; n_converged (B,) the eligible candidates, as in
+ * multi-start; n_uncovered (B,) the eligible candidates no slot covers — 0: the set is complete for these candidates.  Per slot:
+ * q_set (B, K, nq), v_set (B, K, nv), iters / status / seed_index / multiplicity (B, K), distance (B, K) = the
+ * representative's d_ref.  AN EMPTY SLOT (j >= n_distinct) holds candidate 0's row in q_set / v_set / iters / status — every
+ * row is a valid configuration — with seed_index = -1, multiplicity = 0, distance = +inf.
+ * INVARIANT: where n_converged > 0, slot 0 is bitwise what mkh_solve_multistart returns for the same arguments (q_best, v_best,
+ * iters, status, seed_index); where n_converged == 0 every slot is empty and repeats what that call returns: seed 0's result.
+ *
+ * 1 <= n_solutions <= 64; min_distance >= 0 and finite; else MKH_E_INVALID.  At most 4 096 candidates per target (n_seeds, S:
+ * their state during the selection, 12 bytes each, lives in the LDS of the target's wavefront): beyond, MKH_E_LIMIT.
+ *
+ * mkh_solve_multistart_set: seeding, an attached seed table, target fan-out, the loops, the flags and the pointer conventions
+ * are mkh_solve_multistart's — the optional q_all / converged_all / iters_all / status_all / seeds_out are that call's, bitwise
+ * — and THE RULE OF THE SET replaces its selection.  Every output but those five is required.
+ * mkh_select_distinct: the rule alone over a caller's own candidates q_candidates (B, S, nq) — closed-form branches, the q_all of
+ * an earlier call filtered again with another r, the rungs of mkh_solve_trajectory_ladder.  Of MkhSolutionSetIO it reads the
+ * outputs q_set, seed_index, multiplicity, distance, n_distinct, n_uncovered (required) and n_converged (optional: the number of
+ * valid candidates); the other fields are ignored.  q_ref (B, nq) is required.
+ */
+typedef struct MkhSolutionSetIO {
+  const double *seeds;      /* (B, S, nq) caller-defined starts, or NULL: drawn by multi-start's rule                 */
+  const double *q_ref;      /* (B, nq) reference posture of d_ref, or NULL: q                                         */
+  const double *weights;    /* (nv,) weights of the distance, or NULL: ones                                           */
+  double *q_set;            /* (B, K, nq) final configuration of every slot's representative                          */
+  double *v_set;            /* (B, K, nv) its last velocity                                                           */
+  int32_t *iters;           /* (B, K)   its iteration count                                                           */
+  int32_t *status;          /* (B, K)   its MKH_ST_* bits                                                             */
+  int32_t *seed_index;      /* (B, K)   its s; -1 in an empty slot                                                    */
+  int32_t *multiplicity;    /* (B, K)   candidates the slot covers; 0 in an empty slot                                */
+  double *distance;         /* (B, K)   its d_ref; +inf in an empty slot                                              */
+  int32_t *n_distinct;      /* (B,)     slots filled                                                                  */
+  int32_t *n_converged;     /* (B,)     eligible candidates                                                           */
+  int32_t *n_uncovered;     /* (B,)     eligible candidates left uncovered after the last slot                        */
+  double *q_all;            /* (B*S, nq) optional, as in MkhMultistartIO                                              */
+  int32_t *converged_all;   /* (B*S,)    optional                                                                     */
+  int32_t *iters_all;       /* (B*S,)    optional                                                                     */
+  int32_t *status_all;      /* (B*S,)    optional                                                                     */
+  double *seeds_out;        /* (B*S, nq) optional: the starts the loop ran from                                       */
+} MkhSolutionSetIO;
+int32_t mkh_solve_multistart_set(MkhProblem *problem, int32_t B, const double *q, const double *frame_targets,
+                                 const double *posture_target, const double *com_target, double dt, double damping,
+                                 int32_t max_iters, double pos_threshold, double ori_threshold, int32_t n_seeds,
+                                 int32_t n_solutions, double min_distance, uint64_t rng_seed, int64_t target_index0,
+                                 const MkhSolutionSetIO *io, int32_t flags, void *hip_stream);
+int32_t mkh_select_distinct(MkhProblem *problem, int32_t B, int32_t S, const double *q_candidates, const int32_t *valid,
+                            const double *q_ref, const double *weights, int32_t n_solutions, double min_distance,
+                            const MkhSolutionSetIO *io, int32_t flags, void *hip_stream);
+
+/*
  * Trajectory IK: every instance follows its own time sequence of T waypoints, each solved from where the previous one ended —
  * what a caller writes as a loop of mkh_solve_until (motion retargeting, Cartesian path tracing, a horizon of goals), in one
  * call with nothing coming back to the host between waypoints.  No counterpart in the reference.

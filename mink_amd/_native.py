@@ -150,6 +150,60 @@ class MultistartOut(NamedTuple):
     seeds: object = None
 
 
+SOLUTION_SET_MAX_K = 64          # slots per target and candidates per target of a distinct set (include/minkhip.h
+SOLUTION_SET_MAX_S = 4096        # "THE RULE OF THE SET")
+SOLUTION_SET_IO_FIELDS = ("seeds", "q_ref", "weights", "q_set", "v_set", "iters", "status", "seed_index", "multiplicity",
+                          "distance", "n_distinct", "n_converged", "n_uncovered", "q_all", "converged_all", "iters_all",
+                          "status_all", "seeds_out")
+
+
+class MkhSolutionSetIO(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in SOLUTION_SET_IO_FIELDS]
+
+
+class SolutionSetOut(NamedTuple):
+    """What NativeProblem.solve_multistart_set returns (arrays of the caller's kind): per slot `q` (B, K, nq), `v` (B, K, nv),
+    `seed_index` (−1: empty slot), `distance`, `multiplicity`, `iters`, `status` (B, K); per target `n_distinct`, `n_converged`,
+    `n_uncovered` (B,).  The *_all fields and `seeds` are None unless asked for with return_all."""
+    q: object
+    v: object
+    seed_index: object
+    distance: object
+    multiplicity: object
+    iters: object
+    status: object
+    n_distinct: object
+    n_converged: object
+    n_uncovered: object
+    q_all: object = None
+    converged_all: object = None
+    iters_all: object = None
+    status_all: object = None
+    seeds: object = None
+
+
+class DistinctOut(NamedTuple):
+    """What NativeProblem.select_distinct returns: `q` (B, K, nq), `seed_index`, `distance`, `multiplicity` (B, K), `n_distinct`,
+    `n_valid`, `n_uncovered` (B,)."""
+    q: object
+    seed_index: object
+    distance: object
+    multiplicity: object
+    n_distinct: object
+    n_valid: object
+    n_uncovered: object
+
+
+def check_solution_set(K: int, min_distance: float, S: Optional[int] = None) -> None:
+    """What mkh_solve_multistart_set / mkh_select_distinct refuse about K, r and S, judged on the host."""
+    if not 1 <= K <= SOLUTION_SET_MAX_K:
+        raise ValueError(f"n_solutions = {K} must be in 1 ... {SOLUTION_SET_MAX_K}")
+    if not (min_distance >= 0.0 and min_distance < float("inf")):
+        raise ValueError(f"min_distance = {min_distance} must be >= 0 and finite (0: exact duplicates only)")
+    if S is not None and S > SOLUTION_SET_MAX_S:
+        raise ValueError(f"{S} candidates per target: a distinct set is selected among at most {SOLUTION_SET_MAX_S}")
+
+
 TRAJECTORY_IO_FIELDS = ("q_traj", "v_traj", "status", "iters", "converged", "qvel", "waypoint_dt", "posture_per_waypoint",
                         "com_per_waypoint", "time_major")
 
@@ -399,6 +453,12 @@ def lib() -> C.CDLL:
     L.mkh_solve_multistart.argtypes = common[:8] + [C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_uint64, C.c_int64,
                                                     C.POINTER(MkhMultistartIO), C.c_int32, C.c_void_p]
     L.mkh_solve_multistart.restype = C.c_int32
+    L.mkh_solve_multistart_set.argtypes = common[:8] + [C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_double,
+                                                        C.c_uint64, C.c_int64, C.POINTER(MkhSolutionSetIO), C.c_int32, C.c_void_p]
+    L.mkh_solve_multistart_set.restype = C.c_int32
+    L.mkh_select_distinct.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                      C.c_double, C.POINTER(MkhSolutionSetIO), C.c_int32, C.c_void_p]
+    L.mkh_select_distinct.restype = C.c_int32
     L.mkh_solve_trajectory.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + common[2:8] + \
         [C.c_int32, C.c_double, C.c_double, C.POINTER(MkhTrajectoryIO), C.c_int32, C.c_void_p]
     L.mkh_solve_trajectory.restype = C.c_int32
@@ -459,7 +519,7 @@ EXPORTED_SYMBOLS = (
     "mkh_solve_trajectory", "mkh_solve_keyframes", "mkh_solve_trajectory_multistart",
     "mkh_seed_table_create", "mkh_seed_table_destroy", "mkh_seed_table_read", "mkh_seed_table_query",
     "mkh_problem_set_seed_table", "mkh_ladder_select", "mkh_solve_trajectory_ladder",
-    "mkh_ladder_refine", "mkh_solve_trajectory_ladder_refined",
+    "mkh_ladder_refine", "mkh_solve_trajectory_ladder_refined", "mkh_solve_multistart_set", "mkh_select_distinct",
 )
 
 LIE_OPS = {"se3_log": (0, 7, 0, (6,)), "se3_jlog": (1, 7, 0, (6, 6)), "se3_ljacinv": (2, 6, 0, (6, 6)),
@@ -991,8 +1051,69 @@ class NativeProblem:
                                           float(pos_threshold), float(ori_threshold), int(rng_seed), int(target_index0), seeds,
                                           reference, weights, return_all, wave_kernel, lane_kernel, quad_kernel)
 
+    def solve_multistart_set(self, q, frame_targets=None, posture_target=None, com_target=None, dt: float = 1e-2,
+                             damping: float = 1e-12, *, n_seeds: int, n_solutions: int, max_iters: int, pos_threshold: float,
+                             ori_threshold: float, min_distance: float = 0.1, rng_seed: int = 0, target_index0: int = 0,
+                             seeds=None, reference=None, weights=None, return_all: bool = False, wave_kernel: bool = False,
+                             lane_kernel: bool = False, quad_kernel: bool = False, seed_table=None) -> SolutionSetOut:
+        """mkh_solve_multistart_set: solve_multistart's seeds and loops, then up to `n_solutions` converged results per row of q
+        no two of which lie within `min_distance` of each other (Σ_k weights_k·(a ⊖ b)_k² <= min_distance²), in ascending
+        distance from `reference` (default q) — slot 0 is solve_multistart's choice (the rule: include/minkhip.h "THE RULE OF THE
+        SET").  numpy in → numpy out (synchronous); torch CUDA tensors in → torch tensors out, asynchronous on the current
+        stream, no host copy.  Everything else as in solve_multistart."""
+        if seeds is not None and seed_table is not None:
+            raise ValueError("seeds and seed_table are two sources of the same starts: pass one of them")
+        check_solution_set(int(n_solutions), float(min_distance), int(n_seeds))
+        with self._lock, _attached(self, seed_table):
+            return self._solve_multistart(q, frame_targets, posture_target, com_target, dt, damping, int(n_seeds), int(max_iters),
+                                          float(pos_threshold), float(ori_threshold), int(rng_seed), int(target_index0), seeds,
+                                          reference, weights, return_all, wave_kernel, lane_kernel, quad_kernel,
+                                          solution_set=(int(n_solutions), float(min_distance)))
+
+    def select_distinct(self, q_candidates, valid=None, reference=None, weights=None, *, n_solutions: int,
+                        min_distance: float = 0.1) -> DistinctOut:
+        """mkh_select_distinct: the rule of solve_multistart_set alone over the caller's own candidates — q_candidates
+        (B, S, nq), valid (B, S) (None: every candidate), reference (B, nq) (required), weights (nv,).  numpy in → numpy out
+        (synchronous); torch CUDA tensors in → torch tensors out on the current stream, no host copy."""
+        m = self.nmodel.model
+        K = int(n_solutions)
+        if len(q_candidates.shape) != 3:
+            raise ValueError(f"q_candidates must have shape (B, S, {m.nq}), got {tuple(q_candidates.shape)}")
+        B, S = int(q_candidates.shape[0]), int(q_candidates.shape[1])
+        check_solution_set(K, float(min_distance), S)
+        if B < 1 or S < 1:
+            raise ValueError(f"q_candidates must hold at least one target and one candidate, got {tuple(q_candidates.shape)}")
+        prep, empty, ptr, stream, devp = _call_kit(q_candidates)
+        q_candidates, reference, weights = prep(q_candidates), prep(reference), prep(weights)
+        if tuple(q_candidates.shape) != (B, S, m.nq):
+            raise ValueError(f"q_candidates must have shape (B, S, {m.nq}), got {tuple(q_candidates.shape)}")
+        if reference is None or tuple(reference.shape) != (B, m.nq):
+            raise ValueError(f"reference must have shape ({B}, {m.nq})")
+        if weights is not None and tuple(weights.shape) != (m.nv,):
+            raise ValueError(f"weights must have shape ({m.nv},), got {tuple(weights.shape)}")
+        if valid is not None:
+            if tuple(valid.shape) != (B, S):
+                raise ValueError(f"valid must have shape ({B}, {S}), got {tuple(valid.shape)}")
+            if devp:
+                import torch
+                valid = (valid != 0).to(device=q_candidates.device, dtype=torch.int32).contiguous()
+            else:
+                valid = _i32(np.asarray(valid) != 0)
+        f8, i4 = np.float64, np.int32
+        out = {"q_set": empty((B, K, m.nq), f8), "seed_index": empty((B, K), i4), "distance": empty((B, K), f8),
+               "multiplicity": empty((B, K), i4), "n_distinct": empty((B,), i4), "n_converged": empty((B,), i4),
+               "n_uncovered": empty((B,), i4)}
+        io = MkhSolutionSetIO()
+        for n, x in out.items():
+            setattr(io, n, ptr(x))
+        with self._lock:
+            _check(lib().mkh_select_distinct(self.handle, B, S, ptr(q_candidates), ptr(valid), ptr(reference), ptr(weights), K,
+                                             float(min_distance), C.byref(io), devp, stream))
+        return DistinctOut(*out.values())
+
     def _solve_multistart(self, q, frame_targets, posture_target, com_target, dt, damping, S, max_iters, pos_thr, ori_thr,
-                          rng_seed, target_index0, seeds, reference, weights, return_all, wave_kernel, lane_kernel, quad_kernel):
+                          rng_seed, target_index0, seeds, reference, weights, return_all, wave_kernel, lane_kernel, quad_kernel,
+                          solution_set=None):
         m = self.nmodel.model
         B = int(q.shape[0])
         if S < 1:
@@ -1026,22 +1147,37 @@ class NativeProblem:
         if weights is not None and tuple(weights.shape) != (m.nv,):
             raise ValueError(f"weights must have shape ({m.nv},), got {tuple(weights.shape)}")
         f, i = np.float64, np.int32
-        out = {"q_best": empty((B, m.nq), f), "v_best": empty((B, m.nv), f), "iters": empty((B,), i), "status": empty((B,), i),
-               "converged": empty((B,), i), "seed_index": empty((B,), i), "n_converged": empty((B,), i)}
+        if solution_set is None:
+            out = {"q_best": empty((B, m.nq), f), "v_best": empty((B, m.nv), f), "iters": empty((B,), i), "status": empty((B,), i),
+                   "converged": empty((B,), i), "seed_index": empty((B,), i), "n_converged": empty((B,), i)}
+            io = MkhMultistartIO()
+        else:
+            K = solution_set[0]
+            out = {"q_set": empty((B, K, m.nq), f), "v_set": empty((B, K, m.nv), f), "seed_index": empty((B, K), i),
+                   "distance": empty((B, K), f), "multiplicity": empty((B, K), i), "iters": empty((B, K), i),
+                   "status": empty((B, K), i), "n_distinct": empty((B,), i), "n_converged": empty((B,), i),
+                   "n_uncovered": empty((B,), i)}
+            io = MkhSolutionSetIO()
+        n_own = len(out)
         if return_all:
             out.update({"q_all": empty((B * S, m.nq), f), "converged_all": empty((B * S,), i), "iters_all": empty((B * S,), i),
                         "status_all": empty((B * S,), i), "seeds_out": empty((B * S, m.nq), f)})
-        io = MkhMultistartIO()
         io.seeds, io.q_ref, io.weights = ptr(seeds), ptr(reference), ptr(weights)
         for n, x in out.items():
             setattr(io, n, ptr(x))
-        _check(lib().mkh_solve_multistart(self.handle, B, ptr(q), ptr(frame_targets), ptr(posture_target), ptr(com_target),
-                                          float(dt), float(damping), max_iters, pos_thr, ori_thr, S, rng_seed & (2 ** 64 - 1),
-                                          target_index0, C.byref(io), flags, stream))
+        head = (self.handle, B, ptr(q), ptr(frame_targets), ptr(posture_target), ptr(com_target), float(dt), float(damping),
+                max_iters, pos_thr, ori_thr, S)
+        tail = (rng_seed & (2 ** 64 - 1), target_index0, C.byref(io), flags, stream)
+        if solution_set is None:
+            _check(lib().mkh_solve_multistart(*head, *tail))
+        else:
+            _check(lib().mkh_solve_multistart_set(*head, solution_set[0], solution_set[1], *tail))
         extra = ()
         if return_all:
             extra = (out["q_all"].reshape(B, S, m.nq), out["converged_all"].reshape(B, S), out["iters_all"].reshape(B, S),
                      out["status_all"].reshape(B, S), out["seeds_out"].reshape(B, S, m.nq))
+        if solution_set is not None:
+            return SolutionSetOut(*list(out.values())[:n_own], *extra)
         return MultistartOut(out["q_best"], out["v_best"], out["converged"], out["seed_index"], out["n_converged"],
                              out["iters"], out["status"], *extra)
 

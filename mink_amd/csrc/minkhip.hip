@@ -1488,22 +1488,36 @@ int32_t mkh_problem_set_seed_table(MkhProblem* p, const MkhSeedTable* table) {
 }
 
 // mkh_solve_multistart, and the rungs of mkh_solve_trajectory_ladder: with `rungs_v` (device, (B·S, nv)) the loops' velocities go
-// there and the call ends behind the loop — no selection, io's per-target outputs are not read.
+// there and the call ends behind the loop — no selection, io's per-target outputs are not read.  With `set`
+// (mkh_solve_multistart_set) the selection behind the loop is the distinct set's (solution_set.hip) into set->io's outputs, and
+// io's per-target outputs are not read either: the two calls share everything in front of it.
+struct SetSpec {
+  int32_t K;                       // n_solutions
+  double r2;                       // min_distance²
+  const MkhSolutionSetIO* io;      // the outputs (checked by the entry point)
+};
+static void set_select(Stager& st, int B, int S, const SetSpec& set, const double* d_q_all, const double* d_v_all,
+                       const int32_t* d_status, const int32_t* d_iters, const int32_t* d_conv, const double* d_ref, const double* d_w);
+
 static int32_t multistart_core(MkhProblem* p, int32_t B, const double* q, const double* frame_targets,
                                const double* posture_target, const double* com_target, double dt, double damping,
                                int32_t max_iters, double pos_threshold, double ori_threshold, int32_t n_seeds,
                                uint64_t rng_seed, int64_t target_index0, const MkhMultistartIO* io, int32_t flags,
-                               void* hip_stream, double* rungs_v) {
+                               void* hip_stream, double* rungs_v, const SetSpec* set = nullptr) {
+  const char* const who = set ? "mkh_solve_multistart_set" : "mkh_solve_multistart";
   if (!p) return fail(MKH_E_INVALID, "null problem");
   if (B < 1) return fail(MKH_E_INVALID, "B must be >= 1");
   if (n_seeds < 1) return fail(MKH_E_INVALID, "n_seeds must be >= 1");
   if (max_iters < 1) return fail(MKH_E_INVALID, "max_iters must be >= 1");
   if (target_index0 < 0) return fail(MKH_E_INVALID, "target_index0 must be >= 0");
   if (!(pos_threshold >= 0.0) || !(ori_threshold >= 0.0)) return fail(MKH_E_INVALID, "thresholds must be >= 0");
-  if (!io || (!rungs_v && (!io->q_best || !io->v_best || !io->iters || !io->status || !io->converged || !io->seed_index || !io->n_converged)))
+  if (!io || (!rungs_v && !set && (!io->q_best || !io->v_best || !io->iters || !io->status || !io->converged || !io->seed_index || !io->n_converged)))
     return fail(MKH_E_INVALID, "io and its per-target outputs (q_best, v_best, iters, status, converged, seed_index, n_converged) are required");
+  if (set && n_seeds > mkh::kSsMaxCandidates)
+    return fail(MKH_E_LIMIT, "%s: n_seeds = %d candidates per target, at most %d (their selection state lives in LDS)", who, n_seeds,
+                mkh::kSsMaxCandidates);
   const DeviceProblem& P = p->dev;
-  if (const int32_t rc = refuse_inputs(P, q, frame_targets, posture_target, com_target, "mkh_solve_multistart", "multi-start"))
+  if (const int32_t rc = refuse_inputs(P, q, frame_targets, posture_target, com_target, who, "multi-start"))
     return rc;
   const long long N = (long long)B * n_seeds;
   if (N > p->max_batch)
@@ -1511,12 +1525,12 @@ static int32_t multistart_core(MkhProblem* p, int32_t B, const double* q, const 
   // an attached seed table gives rows s >= 1 unless the caller brought seeds of their own
   const MkhSeedTable* const tab = (!io->seeds && n_seeds > 1) ? p->seed_table : nullptr;
   if (tab)
-    if (const int32_t rc = st_refuse(p, tab, n_seeds - 1, "mkh_solve_multistart")) return rc;
+    if (const int32_t rc = st_refuse(p, tab, n_seeds - 1, who)) return rc;
   HIP_OK(hipSetDevice(p->model->device));
   if (const int32_t rc = ms_build_tables(p)) return rc;
   const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
   const bool pbat = (flags & MKH_FLAG_POSTURE_BATCHED) != 0, cbat = (flags & MKH_FLAG_COM_BATCHED) != 0;
-  Stager st{p, (hipStream_t)hip_stream, devp, "multistart"};
+  Stager st{p, (hipStream_t)hip_stream, devp, set ? "multistart_set" : "multistart"};
   hipStream_t stream = st.stream;
   GrowBuf* const ws = p->ws;
   const int S = n_seeds;
@@ -1569,23 +1583,29 @@ static int32_t multistart_core(MkhProblem* p, int32_t B, const double* q, const 
     return st.finish(rc);
   if (rungs_v) return st.finish();
   // ---- selection
-  double *o_q = io->q_best, *o_v = io->v_best;
-  int32_t *o_it = io->iters, *o_st = io->status, *o_cv = io->converged, *o_si = io->seed_index, *o_nc = io->n_converged;
-  if (!devp) {
-    o_q = st.f64(WS_OUT_Q, Bz * nq); o_v = st.f64(WS_OUT_V, Bz * nv);
-    o_it = st.i32(WS_OUT_I32, 3 * Bz); o_st = o_it + Bz; o_cv = o_it + 2 * Bz;
-    o_si = st.i32(WS_OUT_PICK, 2 * Bz); o_nc = o_si + Bz;
+  if (set) {
+    set_select(st, B, S, *set, d_q_all, c_v, d_status, d_iters, d_conv, d_ref ? d_ref : d_q, d_w);
+  } else {
+    double *o_q = io->q_best, *o_v = io->v_best;
+    int32_t *o_it = io->iters, *o_st = io->status, *o_cv = io->converged, *o_si = io->seed_index, *o_nc = io->n_converged;
+    if (!devp) {
+      o_q = st.f64(WS_OUT_Q, Bz * nq); o_v = st.f64(WS_OUT_V, Bz * nv);
+      o_it = st.i32(WS_OUT_I32, 3 * Bz); o_st = o_it + Bz; o_cv = o_it + 2 * Bz;
+      o_si = st.i32(WS_OUT_PICK, 2 * Bz); o_nc = o_si + Bz;
+    }
+    ST_LAUNCH(st, launch_ms_select(stream, B, S, (int)nq, (int)nv, p->model->njnt, ws[WS_JNT].i32(), d_q_all, c_v, d_status, d_iters,
+                                   d_conv, d_ref ? d_ref : d_q, d_w, o_q, o_v, o_it, o_st, o_cv, o_si, o_nc));
+    if (!devp) {
+      st.down(io->q_best, o_q, Bz * nq * f8);
+      st.down(io->v_best, o_v, Bz * nv * f8);
+      st.down(io->iters, o_it, Bz * i4);
+      st.down(io->status, o_st, Bz * i4);
+      st.down(io->converged, o_cv, Bz * i4);
+      st.down(io->seed_index, o_si, Bz * i4);
+      st.down(io->n_converged, o_nc, Bz * i4);
+    }
   }
-  ST_LAUNCH(st, launch_ms_select(stream, B, S, (int)nq, (int)nv, p->model->njnt, ws[WS_JNT].i32(), d_q_all, c_v, d_status, d_iters,
-                                 d_conv, d_ref ? d_ref : d_q, d_w, o_q, o_v, o_it, o_st, o_cv, o_si, o_nc));
   if (devp) return st.finish();
-  st.down(io->q_best, o_q, Bz * nq * f8);
-  st.down(io->v_best, o_v, Bz * nv * f8);
-  st.down(io->iters, o_it, Bz * i4);
-  st.down(io->status, o_st, Bz * i4);
-  st.down(io->converged, o_cv, Bz * i4);
-  st.down(io->seed_index, o_si, Bz * i4);
-  st.down(io->n_converged, o_nc, Bz * i4);
   st.down(io->q_all, d_q_all, Nz * nq * f8);
   st.down(io->status_all, d_status, Nz * i4);
   st.down(io->iters_all, d_iters, Nz * i4);
@@ -1601,6 +1621,110 @@ int32_t mkh_solve_multistart(MkhProblem* p, int32_t B, const double* q, const do
                              void* hip_stream) {
   return multistart_core(p, B, q, frame_targets, posture_target, com_target, dt, damping, max_iters, pos_threshold, ori_threshold,
                          n_seeds, rng_seed, target_index0, io, flags, hip_stream, nullptr);
+}
+
+// ---- distinct solution sets (include/minkhip.h "THE RULE OF THE SET"; kernel: solution_set.hip)
+// The selection on device arrays into set.io's outputs: in place for a device-pointer call, else through the workspace and
+// down.  v / status / iters / conv may be absent (a selection over a caller's own candidates: conv is then its `valid`).
+static void set_select(Stager& st, int B, int S, const SetSpec& set, const double* d_q_all, const double* d_v_all,
+                       const int32_t* d_status, const int32_t* d_iters, const int32_t* d_conv, const double* d_ref, const double* d_w) {
+  const MkhProblem* const p = st.p;
+  const MkhSolutionSetIO& io = *set.io;
+  const size_t R = (size_t)B * set.K, Bz = B, nq = p->dev.nq, nv = p->dev.nv, f8 = sizeof(double), i4 = sizeof(int32_t);
+  mkh::SsOut o{io.q_set, d_v_all ? io.v_set : nullptr, d_iters ? io.iters : nullptr, d_status ? io.status : nullptr, io.seed_index,
+               io.multiplicity, io.distance, io.n_distinct, io.n_converged, io.n_uncovered};
+  if (!st.devp) {
+    o.q_set = st.f64(WS_OUT_Q, R * nq);
+    if (o.v_set) o.v_set = st.f64(WS_OUT_V, R * nv);
+    int32_t* const rows = st.i32(WS_OUT_I32, 2 * R);
+    if (o.iters) o.iters = rows;
+    if (o.status) o.status = rows ? rows + R : nullptr;
+    int32_t* const pick = st.i32(WS_OUT_PICK, 2 * R + 3 * Bz);
+    o.seed_index = pick; o.multiplicity = pick ? pick + R : nullptr;
+    o.n_distinct = pick ? pick + 2 * R : nullptr;
+    if (o.n_converged) o.n_converged = pick ? pick + 2 * R + Bz : nullptr;
+    o.n_uncovered = pick ? pick + 2 * R + 2 * Bz : nullptr;
+    o.distance = st.f64(WS_OUT_LEN, R);
+  }
+  ST_LAUNCH(st, launch_ss_select(st.stream, B, S, set.K, (int)nq, (int)nv, p->model->njnt, p->ws[WS_JNT].i32(), d_q_all, d_v_all,
+                                 d_status, d_iters, d_conv, d_ref, d_w, set.r2, o));
+  if (st.devp) return;
+  st.down(io.q_set, o.q_set, R * nq * f8);
+  if (o.v_set) st.down(io.v_set, o.v_set, R * nv * f8);
+  if (o.iters) st.down(io.iters, o.iters, R * i4);
+  if (o.status) st.down(io.status, o.status, R * i4);
+  st.down(io.seed_index, o.seed_index, R * i4);
+  st.down(io.multiplicity, o.multiplicity, R * i4);
+  st.down(io.distance, o.distance, R * f8);
+  st.down(io.n_distinct, o.n_distinct, Bz * i4);
+  if (o.n_converged) st.down(io.n_converged, o.n_converged, Bz * i4);
+  st.down(io.n_uncovered, o.n_uncovered, Bz * i4);
+}
+
+// What both entry points refuse about K and r.
+static int32_t set_refuse(int32_t n_solutions, double min_distance, const char* who) {
+  if (n_solutions < 1 || n_solutions > mkh::kSsMaxSolutions)
+    return fail(MKH_E_INVALID, "%s: n_solutions = %d must be in 1 ... %d", who, n_solutions, mkh::kSsMaxSolutions);
+  if (!(min_distance >= 0.0) || min_distance > 1.7976931348623157e308)
+    return fail(MKH_E_INVALID, "%s: min_distance = %g must be >= 0 and finite (0: exact duplicates only)", who, min_distance);
+  return MKH_OK;
+}
+
+int32_t mkh_solve_multistart_set(MkhProblem* p, int32_t B, const double* q, const double* frame_targets,
+                                 const double* posture_target, const double* com_target, double dt, double damping,
+                                 int32_t max_iters, double pos_threshold, double ori_threshold, int32_t n_seeds,
+                                 int32_t n_solutions, double min_distance, uint64_t rng_seed, int64_t target_index0,
+                                 const MkhSolutionSetIO* io, int32_t flags, void* hip_stream) {
+  const char* const who = "mkh_solve_multistart_set";
+  if (!p) return fail(MKH_E_INVALID, "null problem");
+  if (const int32_t rc = set_refuse(n_solutions, min_distance, who)) return rc;
+  if (!io || !io->q_set || !io->v_set || !io->iters || !io->status || !io->seed_index || !io->multiplicity || !io->distance ||
+      !io->n_distinct || !io->n_converged || !io->n_uncovered)
+    return fail(MKH_E_INVALID, "%s: io and its outputs q_set, v_set, iters, status, seed_index, multiplicity, distance, n_distinct, "
+                               "n_converged, n_uncovered are required", who);
+  MkhMultistartIO mio{};           // what the shared path reads: the inputs and the optional per-instance arrays
+  mio.seeds = io->seeds; mio.q_ref = io->q_ref; mio.weights = io->weights;
+  mio.q_all = io->q_all; mio.converged_all = io->converged_all; mio.iters_all = io->iters_all; mio.status_all = io->status_all;
+  mio.seeds_out = io->seeds_out;
+  const SetSpec set{n_solutions, min_distance * min_distance, io};
+  return multistart_core(p, B, q, frame_targets, posture_target, com_target, dt, damping, max_iters, pos_threshold, ori_threshold,
+                         n_seeds, rng_seed, target_index0, &mio, flags, hip_stream, nullptr, &set);
+}
+
+int32_t mkh_select_distinct(MkhProblem* p, int32_t B, int32_t S, const double* q_candidates, const int32_t* valid,
+                            const double* q_ref, const double* weights, int32_t n_solutions, double min_distance,
+                            const MkhSolutionSetIO* io, int32_t flags, void* hip_stream) {
+  const char* const who = "mkh_select_distinct";
+  if (!p) return fail(MKH_E_INVALID, "null problem");
+  if (B < 1) return fail(MKH_E_INVALID, "%s: B = %d must be >= 1", who, B);
+  if (S < 1) return fail(MKH_E_INVALID, "%s: S = %d must be >= 1", who, S);
+  if (S > mkh::kSsMaxCandidates)
+    return fail(MKH_E_LIMIT, "%s: S = %d candidates per target, at most %d (their selection state lives in LDS)", who, S,
+                mkh::kSsMaxCandidates);
+  if ((long long)B * S > 0x7fffffffLL) return fail(MKH_E_LIMIT, "%s: B * S = %lld rows", who, (long long)B * S);
+  if (const int32_t rc = set_refuse(n_solutions, min_distance, who)) return rc;
+  if (!q_candidates || !q_ref) return fail(MKH_E_INVALID, "%s: q_candidates and q_ref are required", who);
+  if (!io || !io->q_set || !io->seed_index || !io->multiplicity || !io->distance || !io->n_distinct || !io->n_uncovered)
+    return fail(MKH_E_INVALID, "%s: io and its outputs q_set, seed_index, multiplicity, distance, n_distinct, n_uncovered are required", who);
+  const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
+  HIP_OK(hipSetDevice(p->model->device));
+  if (const int32_t rc = ms_build_tables(p)) return rc;
+  Stager st{p, (hipStream_t)hip_stream, devp, "select_distinct"};
+  const size_t Bz = B, N = Bz * S, nq = p->dev.nq;
+  const double* const d_cand = st.up(WS_C_Q, q_candidates, N * nq);
+  const double* const d_ref = st.up(WS_IN_REF, q_ref, Bz * nq);
+  const double* const d_w = st.up(WS_IN_W, weights, p->dev.nv);
+  const int32_t* d_valid = valid;
+  if (!devp && valid) {
+    int32_t* const t = st.i32(WS_C_CV, N);
+    if (t) st.latch(hipMemcpyAsync(t, valid, N * sizeof(int32_t), hipMemcpyHostToDevice, st.stream));
+    d_valid = t;
+  }
+  if (!st.ok()) return st.finish();
+  MkhSolutionSetIO sio = *io;      // (the selection alone has no loop rows: n_converged is the count of `valid`, when asked for)
+  const SetSpec set{n_solutions, min_distance * min_distance, &sio};
+  set_select(st, B, S, set, d_cand, nullptr, nullptr, nullptr, d_valid, d_ref, d_w);
+  return st.finish();
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // Launchers of the small kernels around the loop launches of the outer-loop entry points (mkh_solve_multistart,
-// mkh_solve_trajectory, mkh_solve_keyframes, mkh_solve_trajectory_multistart, the ladder calls) and of the seed tables in
-// front of them: declared once, for the seven files that define them and for minkhip.hip, which calls them — a signature that
+// mkh_solve_multistart_set, mkh_solve_trajectory, mkh_solve_keyframes, mkh_solve_trajectory_multistart, the ladder calls) and of
+// the seed tables in front of them: declared once, for the eight files that define them and for minkhip.hip, which calls them — a signature that
 // drifts fails to compile in the file that drifted.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -28,6 +28,21 @@ hipError_t launch_ms_select(hipStream_t stream, int B, int S, int nq, int nv, in
                             const double* v_all, const int32_t* status_all, const int32_t* iters_all, const int32_t* converged_all,
                             const double* q_ref, const double* weights, double* q_best, double* v_best, int32_t* iters,
                             int32_t* status, int32_t* converged, int32_t* seed_index, int32_t* n_converged);
+// distinct solution sets (solution_set.hip): up to K representatives per target among its S candidates, no two within r2 (a
+// squared distance) of each other — (B, K, .) outputs.  v_all / iters_all / status_all with their outputs, converged_all
+// (absent: every candidate is eligible) and n_converged are optional.  S beyond kSsMaxCandidates: hipErrorInvalidValue (the
+// per-candidate state of one target, 12 bytes each, lives in LDS).
+constexpr int kSsMaxCandidates = 4096;
+constexpr int kSsMaxSolutions = 64;
+struct SsOut {
+  double *q_set, *v_set;
+  int32_t *iters, *status, *seed_index, *multiplicity;
+  double* distance;
+  int32_t *n_distinct, *n_converged, *n_uncovered;
+};
+hipError_t launch_ss_select(hipStream_t stream, int B, int S, int K, int nq, int nv, int njnt, const int32_t* jnt,
+                            const double* q_all, const double* v_all, const int32_t* status_all, const int32_t* iters_all,
+                            const int32_t* converged_all, const double* q_ref, const double* weights, double r2, const SsOut& o);
 // trajectory IK (trajectory.hip): (B, T, W) ↔ (T, B, W) transposes and the joint velocity between waypoints — the kernels
 // around the T loop launches of mkh_solve_trajectory
 hipError_t launch_tj_gather(hipStream_t stream, const double* src, double* dst, int B, int T, int W);

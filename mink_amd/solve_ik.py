@@ -682,6 +682,145 @@ def solve_ik_multistart(configuration: Configuration, tasks: Sequence, dt: float
                               for k, x in enumerate((res.q_all, res.converged_all, res.iters_all, res.status_all, res.seeds))])
 
 
+class SolutionSet(NamedTuple):
+    """Result of solve_ik_solutions: per target up to K distinct solutions in ascending distance from the reference — `q`
+    (B, K, nq), `v` (B, K, nv), `valid` (B, K) (False: an empty slot, which repeats seed 0's result), `seed_index` (−1 in an
+    empty slot), `distance` (+inf), `multiplicity` (the converged seeds the slot stands for; 0), `iters`, `status` (B, K) — and
+    `n_distinct`, `n_converged`, `n_uncovered` (B,): slots filled, seeds that converged, converged seeds that no slot covers
+    (0: the set is complete for these seeds).  With return_all also `q_all`, `converged_all`, `iters_all`, `status_all`, `seeds`
+    as in MultistartResult.  Without the leading axis for an unbatched configuration."""
+    q: np.ndarray
+    v: np.ndarray
+    valid: np.ndarray
+    seed_index: np.ndarray
+    distance: np.ndarray
+    multiplicity: np.ndarray
+    iters: np.ndarray
+    status: np.ndarray
+    n_distinct: np.ndarray
+    n_converged: np.ndarray
+    n_uncovered: np.ndarray
+    q_all: Optional[np.ndarray] = None
+    converged_all: Optional[np.ndarray] = None
+    iters_all: Optional[np.ndarray] = None
+    status_all: Optional[np.ndarray] = None
+    seeds: Optional[np.ndarray] = None
+
+
+class DistinctSet(NamedTuple):
+    """Result of distinct_solutions: `q` (B, K, nq), `valid`, `seed_index` (the candidate's index; −1 in an empty slot),
+    `distance`, `multiplicity` (B, K), and `n_distinct`, `n_valid`, `n_uncovered` (B,) — without the leading axis for an
+    unbatched configuration."""
+    q: np.ndarray
+    valid: np.ndarray
+    seed_index: np.ndarray
+    distance: np.ndarray
+    multiplicity: np.ndarray
+    n_distinct: np.ndarray
+    n_valid: np.ndarray
+    n_uncovered: np.ndarray
+
+
+def _set_args(n_solutions, min_distance, S=None):
+    """(K, r) of a distinct set, judged on the host."""
+    try:
+        K, r = int(n_solutions), float(min_distance)
+    except (TypeError, ValueError) as e:
+        raise ValueError("n_solutions must be an integer and min_distance a number") from e
+    nat.check_solution_set(K, r, S)
+    return K, r
+
+
+def solve_ik_solutions(configuration: Configuration, tasks: Sequence, dt: float, n_seeds: int, n_solutions: int, max_iters: int,
+                       pos_threshold: float, ori_threshold: float, min_distance: float = 0.1, solver: str = "mi355x",
+                       damping: float = 1e-12, limits: Optional[Sequence] = None, rng_seed: int = 0, seeds=None, reference=None,
+                       weights=None, return_all: bool = False, max_instances: int = 1 << 20,
+                       seed_table: Optional["SeedTable"] = None) -> SolutionSet:
+    """The distinct IK solutions of every target that multi-start finds: solve_ik_multistart's seeds and loops — `n_seeds`
+    starts per target, the same generator, `seeds`, `seed_table`, chunks and shards — and, instead of its one result, up to
+    `n_solutions` converged results per target no two of which lie within `min_distance` of each other, picked and
+    deduplicated on the device.
+
+    Distances are multi-start's: d(a, b) = Σ_k weights_k·(a ⊖ b)_k² in the tangent space; two results are the same solution
+    when d <= min_distance² (0: exact duplicates only).  The slots are filled in ascending distance from `reference`
+    (default: q): slot 0 is what solve_ik_multistart returns, slot j the closest converged result that none of the slots
+    before it covers; `multiplicity` counts the seeds a slot stands for.  Slots beyond `n_distinct` are empty — valid = False,
+    seed 0's result in q.  `n_uncovered` > 0 says that more distinct solutions were found than `n_solutions` holds.  Two
+    solutions a full turn of an unlimited hinge apart count as different.
+
+    The configuration is not changed: a set does not update it.  Failures are reported for slot 0 only, as
+    solve_ik_multistart reports them for its choice."""
+    del solver
+    S, max_iters = int(n_seeds), int(max_iters)
+    if S < 1:
+        raise ValueError("n_seeds must be >= 1")
+    K, r = _set_args(n_solutions, min_distance, S)
+    if max_iters < 1:
+        raise ValueError("max_iters must be >= 1")
+    if int(max_instances) < 1:
+        raise ValueError("max_instances must be >= 1")
+    B, nq, nv = configuration.batch_size, configuration.nq, configuration.nv
+    seeds = _optional_array(seeds, "seeds", (S, nq), B)
+    reference = _optional_array(reference, "reference", (nq,), B)
+    weights = _optional_array(weights, "weights", (nv,))
+    _check_seed_table(seed_table, seeds, configuration, S)
+    handles, layout, chunk, n_dev = _compile_outer(configuration, tasks, limits, dt, "solve_ik_solutions", S, max_instances)
+    ft, pt, ct = _gather_targets(configuration, layout)
+    q = configuration.q_batch
+    kw = dict(n_seeds=S, n_solutions=K, min_distance=r, max_iters=max_iters, pos_threshold=float(pos_threshold),
+              ori_threshold=float(ori_threshold), rng_seed=int(rng_seed), return_all=bool(return_all))
+
+    def job(handle, lo, hi):
+        return handle.solve_multistart_set(q[lo:hi], _rows(ft, 2, lo, hi), _rows(pt, 2, lo, hi), _rows(ct, 2, lo, hi), dt, damping,
+                                           target_index0=lo, seeds=_rows(seeds, 2, lo, hi), reference=_rows(reference, 1, lo, hi),
+                                           weights=weights, seed_table=seed_table, **kw)
+
+    res = _join(nat.SolutionSetOut, _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job))
+    _status_epilogue(res.status[:, 0], "solve_ik_solutions", "chosen instance(s)",
+                     "QP failed for the chosen seed of {n} of {of} targets (first: index {first}, status {status}); "
+                     "none of their seeds converged")
+    un = configuration._unbatch
+    return SolutionSet(un(res.q), un(res.v), un(res.seed_index >= 0), un(res.seed_index), un(res.distance), un(res.multiplicity),
+                       un(res.iters), un(res.status), un(res.n_distinct), un(res.n_converged), un(res.n_uncovered),
+                       *[None if x is None else un(x.astype(bool) if k == 1 else x)
+                         for k, x in enumerate((res.q_all, res.converged_all, res.iters_all, res.status_all, res.seeds))])
+
+
+def distinct_solutions(configuration: Configuration, q_candidates, valid=None, n_solutions: int = 8, min_distance: float = 0.1,
+                       reference=None, weights=None) -> DistinctSet:
+    """The selection of solve_ik_solutions alone, over the caller's own candidates (closed-form IK branches, the q_all of an
+    earlier call filtered again with another min_distance, the rungs of a ladder): q_candidates (S, nq) or (B, S, nq), `valid`
+    (same leading shape; default: every candidate), `reference` (nq,) or (B, nq) (default: the configuration's q).  Up to
+    `n_solutions` valid candidates no two of which lie within `min_distance` of each other, in ascending distance from the
+    reference, ties to the lowest index — the rule of solve_ik_solutions.  The configuration is not changed."""
+    from .tasks import PostureTask
+
+    B, nq, nv = configuration.batch_size, configuration.nq, configuration.nv
+    q_candidates = _host_array(q_candidates, "q_candidates")
+    if q_candidates is None or q_candidates.ndim not in (2, 3) or q_candidates.shape[-1] != nq or q_candidates.shape[-2] < 1 \
+            or (q_candidates.ndim == 3 and q_candidates.shape[0] != B):
+        raise ValueError(f"q_candidates must have shape (S, {nq}) or ({B}, S, {nq}), got "
+                         f"{None if q_candidates is None else q_candidates.shape}")
+    S = q_candidates.shape[-2]
+    K, r = _set_args(n_solutions, min_distance, S)
+    q_candidates = np.ascontiguousarray(np.broadcast_to(q_candidates, (B, S, nq)))
+    if valid is not None:
+        valid = np.asarray(valid.detach().cpu().numpy() if nat._is_torch(valid) else valid)
+        if valid.shape not in ((S,), (B, S)):
+            raise ValueError(f"valid must have shape {(S,)} or {(B, S)}, got {valid.shape}")
+        valid = np.ascontiguousarray(np.broadcast_to(valid != 0, (B, S)))
+    reference = _optional_array(reference, "reference", (nq,), B)
+    weights = _optional_array(weights, "weights", (nv,))
+    # (the selection reads the model's joint table through a problem handle: the smallest one, a posture task, serves)
+    prob, layout = _compile(configuration, [PostureTask(configuration.model, cost=1.0)], None, 1, devices=configuration.devices[:1])
+    with _pin(configuration, layout):
+        out = prob.select_distinct(q_candidates, valid, configuration.q_batch if reference is None else reference, weights,
+                                   n_solutions=K, min_distance=r)
+    un = configuration._unbatch
+    return DistinctSet(un(out.q), un(out.seed_index >= 0), un(out.seed_index), un(out.distance), un(out.multiplicity),
+                       un(out.n_distinct), un(out.n_valid), un(out.n_uncovered))
+
+
 class TrajectoryResult(NamedTuple):
     """Result of solve_ik_trajectory, (B, T, ·) — (T, ·) for an unbatched configuration: the configuration `q` at the end of
     every waypoint's loop, the loop's last velocity `v`, its `status` bits, and in threshold mode its `iters` and `converged`
