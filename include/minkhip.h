@@ -527,6 +527,90 @@ int32_t mkh_select_distinct(MkhProblem *problem, int32_t B, int32_t S, const dou
                             const MkhSolutionSetIO *io, int32_t flags, void *hip_stream);
 
 /*
+ * Goal sets: multi-start IK to the BEST of G = n_goals candidate poses per target — the grasp poses of an object, the poses a
+ * placement accepts, the yaws of a tool that is symmetric about its axis — instead of to one pose: which of the goals the robot
+ * reaches, and the configuration of the one closest to the reference posture, picked on the device: no B·G·S rows over the bus.
+ * No counterpart in the reference.
+ *
+ * THE RULE OF THE GOAL SET (mkh_select_goalset; mkh_solve_goalset runs it on the results of its loops), in multi-start's terms.
+ * Shapes.  Target b has G goals and S = n_seeds starts per goal; instance i = (b·G + g)·S + s.  frame_targets (B, G, n_frame, 7);
+ *   posture_target / com_target (n, w), or (B, G, n, w) with MKH_FLAG_POSTURE_BATCHED / MKH_FLAG_COM_BATCHED, as in the ladder.
+ * Loops.  mkh_solve_multistart's on the B·G flattened (target, goal) pairs: q[b] is repeated G times, so seed 0 of EVERY goal
+ *   is the caller's q[b], bit for bit; drawn seeds use the global target index (target_index0 + b)·G + g; a caller's seeds are
+ *   (B, G, S, nq); an attached seed table is queried with every goal's own frame targets.  The loops run in chunks of whole
+ *   goals, at most max_batch loops each, like the ladder's rungs: the call needs only max_batch >= S.
+ * Level 1, per goal.  Multi-start's selection, unchanged: among the eligible seeds (converged != 0 and
+ *   status & ~MKH_ST_OUTSIDE_LIMITS == 0; for mkh_select_goalset: valid[b, g, s] != 0, every candidate when valid is NULL) the one
+ *   with the smallest d_ref(s) = d(q_s, q_ref[b]) wins — the same device function, d(a, b) = sum_k w_k ((a (-) b)_k)^2, a NaN or
+ *   infinite value replaced by DBL_MAX — ties to the lowest s.  A goal is VALID when goal_valid[b, g] != 0, always when
+ *   goal_valid is NULL; it is REACHED when it is valid and has an eligible seed; d_ref(g) is its winner's d_ref.
+ * Level 2, per target.  Among the reached goals the one with the smallest score = goal_cost[b, g] + d_ref(g) wins — one rounded
+ *   addition, never fused; goal_cost NULL: zeros — ties to the lowest g.  A given goal_cost must be finite and >= 0: host
+ *   pointers are checked (MKH_E_INVALID); behind MKH_FLAG_DEVICE_PTRS a NaN cost makes the goal lose every comparison (it still
+ *   counts in n_reached; a target whose reached goals all have NaN costs returns as if nothing were reached).
+ * Nothing reached.  The target's row is seed 0 of the lowest valid goal, of goal 0 when none is valid: converged = 0,
+ *   seed_index = 0, score = +inf, goal_index = that goal, or -1 when no goal is valid.
+ * Invalid goals still run their loops — the launch shape does not depend on data — so their target rows must be valid poses:
+ *   pad a ragged set by repeating one of its valid goals with goal_valid = 0.
+ *
+ * Outputs.  Per target: q_best (B, nq), v_best (B, nv), iters / status / converged / goal_index / seed_index / n_reached (B,),
+ * score (B,).  Per goal: q_goal (B, G, nq), v_goal (B, G, nv), iters_goal / status_goal / seed_index_goal / reached /
+ * n_converged_goal (B, G) (n_converged_goal: the eligible seeds, whatever goal_valid says), distance_goal (B, G) = d_ref(g),
+ * +inf when the goal is not reached.  AN UNREACHED GOAL holds its seed 0's row, with seed_index_goal = 0 and reached = 0.  The
+ * optional q_all / converged_all / iters_all / status_all / seeds_out are (B·G·S, .), as in MkhMultistartIO.
+ * INVARIANTS.  (1) With G = 1 and goal_cost, goal_valid NULL the per-target outputs are bitwise mkh_solve_multistart's (its
+ * n_converged is n_converged_goal).  (2) For any G, the per-goal outputs of valid goals are bitwise what mkh_solve_multistart
+ * returns for the B·G flattened pairs — q repeated G times, q_ref likewise — at target_index0·G (reached is its converged).
+ * (3) With goal_cost and goal_valid NULL, (goal_index, seed_index) is multi-start's selection over the G·S candidates of a
+ * target taken as one flat list, index g·S + s.
+ *
+ * n_goals >= 1, n_seeds >= 1, every output above but the five optional ones: else MKH_E_INVALID, before a device is touched.  The
+ * selection keeps no per-candidate state: the only cap is B·G·S <= 2^31 - 1 rows (MKH_E_LIMIT).
+ *
+ * mkh_solve_goalset: refusals, flags and pointer conventions are mkh_solve_multistart's.
+ * mkh_select_goalset: the two levels alone over a caller's own candidates q_candidates (B, G, S, nq) — the closed-form branches
+ * of every grasp — with valid (B, G, S) or NULL and q_ref (B, nq), required.  Of MkhGoalSetIO it reads goal_cost, goal_valid and
+ * the outputs q_best, converged, goal_index, seed_index, n_reached, score, q_goal, seed_index_goal, reached, n_converged_goal,
+ * distance_goal (required; n_converged_goal: the number of valid candidates); the velocity, iteration and status outputs and
+ * every other field are ignored.
+ */
+typedef struct MkhGoalSetIO {
+  const double *seeds;        /* (B, G, S, nq) caller-defined starts, or NULL: drawn by multi-start's rule              */
+  const double *q_ref;        /* (B, nq) reference posture of d_ref, or NULL: q                                         */
+  const double *weights;      /* (nv,) weights of the distance, or NULL: ones                                           */
+  const double *goal_cost;    /* (B, G) finite, >= 0, or NULL: zeros                                                    */
+  const int32_t *goal_valid;  /* (B, G) or NULL: every goal is valid                                                    */
+  double *q_best;             /* (B, nq) final configuration of the chosen (goal, seed)                                 */
+  double *v_best;             /* (B, nv) its last velocity                                                              */
+  int32_t *iters;             /* (B,)    its iteration count                                                            */
+  int32_t *status;            /* (B,)    its MKH_ST_* bits                                                              */
+  int32_t *converged;         /* (B,)    1: a goal was reached and chosen                                               */
+  int32_t *goal_index;        /* (B,)    the chosen g; nothing reached: the lowest valid goal, -1 when none is valid    */
+  int32_t *seed_index;        /* (B,)    the chosen s; 0 when nothing is reached                                        */
+  int32_t *n_reached;         /* (B,)    reached goals                                                                  */
+  double *score;              /* (B,)    goal_cost + d_ref of the chosen goal; +inf when nothing is reached             */
+  double *q_goal;             /* (B, G, nq) final configuration of every goal's winner (unreached: seed 0's)            */
+  double *v_goal;             /* (B, G, nv) its last velocity                                                           */
+  int32_t *iters_goal;        /* (B, G)  its iteration count                                                            */
+  int32_t *status_goal;       /* (B, G)  its MKH_ST_* bits                                                              */
+  int32_t *seed_index_goal;   /* (B, G)  its s; 0 when the goal is not reached                                          */
+  int32_t *reached;           /* (B, G)  1: valid and an eligible seed                                                  */
+  int32_t *n_converged_goal;  /* (B, G)  eligible seeds                                                                 */
+  double *distance_goal;      /* (B, G)  d_ref of the winner; +inf when the goal is not reached                         */
+  double *q_all;              /* (B*G*S, nq) optional, as in MkhMultistartIO                                            */
+  int32_t *converged_all;     /* (B*G*S,)    optional                                                                   */
+  int32_t *iters_all;         /* (B*G*S,)    optional                                                                   */
+  int32_t *status_all;        /* (B*G*S,)    optional                                                                   */
+  double *seeds_out;          /* (B*G*S, nq) optional: the starts the loops ran from                                    */
+} MkhGoalSetIO;
+int32_t mkh_solve_goalset(MkhProblem *problem, int32_t B, int32_t n_goals, const double *q, const double *frame_targets,
+                          const double *posture_target, const double *com_target, double dt, double damping, int32_t max_iters,
+                          double pos_threshold, double ori_threshold, int32_t n_seeds, uint64_t rng_seed, int64_t target_index0,
+                          const MkhGoalSetIO *io, int32_t flags, void *hip_stream);
+int32_t mkh_select_goalset(MkhProblem *problem, int32_t B, int32_t G, int32_t S, const double *q_candidates, const int32_t *valid,
+                           const double *q_ref, const double *weights, const MkhGoalSetIO *io, int32_t flags, void *hip_stream);
+
+/*
  * Trajectory IK: every instance follows its own time sequence of T waypoints, each solved from where the previous one ended —
  * what a caller writes as a loop of mkh_solve_until (motion retargeting, Cartesian path tracing, a horizon of goals), in one
  * call with nothing coming back to the host between waypoints.  No counterpart in the reference.

@@ -204,6 +204,97 @@ def check_solution_set(K: int, min_distance: float, S: Optional[int] = None) -> 
         raise ValueError(f"{S} candidates per target: a distinct set is selected among at most {SOLUTION_SET_MAX_S}")
 
 
+GOAL_SET_MAX_ROWS = 2 ** 31 - 1  # B·G·S of one native call (include/minkhip.h "THE RULE OF THE GOAL SET")
+GOAL_SET_IO_FIELDS = ("seeds", "q_ref", "weights", "goal_cost", "goal_valid", "q_best", "v_best", "iters", "status", "converged",
+                      "goal_index", "seed_index", "n_reached", "score", "q_goal", "v_goal", "iters_goal", "status_goal",
+                      "seed_index_goal", "reached", "n_converged_goal", "distance_goal", "q_all", "converged_all", "iters_all",
+                      "status_all", "seeds_out")
+
+
+class MkhGoalSetIO(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in GOAL_SET_IO_FIELDS]
+
+
+class GoalSetOut(NamedTuple):
+    """What NativeProblem.solve_goalset returns (arrays of the caller's kind): per target `q` (B, nq), `v` (B, nv), `converged`,
+    `goal_index` (−1: no valid goal), `seed_index`, `n_reached`, `score` (+inf: nothing reached), `iters`, `status` (B,); per
+    goal `q_goal` (B, G, nq), `v_goal` (B, G, nv), `reached`, `seed_index_goal`, `n_converged_goal`, `distance_goal` (+inf: not
+    reached), `iters_goal`, `status_goal` (B, G).  The *_all fields, (B, G, S, ·), and `seeds` are None unless asked for with
+    return_all."""
+    q: object
+    v: object
+    converged: object
+    goal_index: object
+    seed_index: object
+    n_reached: object
+    score: object
+    iters: object
+    status: object
+    q_goal: object
+    v_goal: object
+    reached: object
+    seed_index_goal: object
+    n_converged_goal: object
+    distance_goal: object
+    iters_goal: object
+    status_goal: object
+    q_all: object = None
+    converged_all: object = None
+    iters_all: object = None
+    status_all: object = None
+    seeds: object = None
+
+
+class GoalSelectOut(NamedTuple):
+    """What NativeProblem.select_goalset returns: `q` (B, nq), `converged`, `goal_index`, `seed_index`, `n_reached`, `score`
+    (B,), `q_goal` (B, G, nq), `reached`, `seed_index_goal`, `n_valid_goal` (the valid candidates of a goal), `distance_goal`
+    (B, G)."""
+    q: object
+    converged: object
+    goal_index: object
+    seed_index: object
+    n_reached: object
+    score: object
+    q_goal: object
+    reached: object
+    seed_index_goal: object
+    n_valid_goal: object
+    distance_goal: object
+
+
+def check_goalset_shape(B: int, G: int, S: int) -> None:
+    """What mkh_solve_goalset / mkh_select_goalset refuse about the shape of a goal set, judged on the host: the selection keeps
+    no per-candidate state, so the only cap is the row count of one call."""
+    if G < 1:
+        raise ValueError(f"a goal set needs at least one goal: G (n_goals) = {G} must be >= 1")
+    if S < 1:
+        raise ValueError(f"a goal needs at least one start: S (n_seeds) = {S} must be >= 1")
+    if B < 1:
+        raise ValueError(f"B = {B} must be >= 1")
+    if B * G * S > GOAL_SET_MAX_ROWS:
+        raise ValueError(f"B*G*S = {B * G * S} rows in one call: at most {GOAL_SET_MAX_ROWS}")
+
+
+def _goal_inputs(goal_cost, goal_valid, B: int, G: int, prep, q):
+    """goal_cost (B, G) float64 and goal_valid (B, G) int32 of a native goal-set call in q's kind, shapes checked; a host
+    array's costs are judged here (finite, >= 0), a device tensor's by the rule's NaN clause."""
+    if goal_cost is not None:
+        if tuple(goal_cost.shape) != (B, G):
+            raise ValueError(f"goal_cost must have shape ({B}, {G}), got {tuple(goal_cost.shape)}")
+        goal_cost = prep(goal_cost)
+        if not _is_torch(goal_cost) and not (np.isfinite(goal_cost) & (goal_cost >= 0.0)).all():
+            raise ValueError("goal_cost must be finite and >= 0")
+    if goal_valid is not None:
+        if tuple(goal_valid.shape) != (B, G):
+            raise ValueError(f"goal_valid must have shape ({B}, {G}), got {tuple(goal_valid.shape)}")
+        if _is_torch(q):
+            import torch
+            goal_valid = (torch.as_tensor(goal_valid) != 0).to(device=q.device, dtype=torch.int32).contiguous()
+        else:
+            goal_valid = _i32(np.asarray(goal_valid) != 0)
+    return goal_cost, goal_valid
+
+
 TRAJECTORY_IO_FIELDS = ("q_traj", "v_traj", "status", "iters", "converged", "qvel", "waypoint_dt", "posture_per_waypoint",
                         "com_per_waypoint", "time_major")
 
@@ -459,6 +550,12 @@ def lib() -> C.CDLL:
     L.mkh_select_distinct.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                       C.c_double, C.POINTER(MkhSolutionSetIO), C.c_int32, C.c_void_p]
     L.mkh_select_distinct.restype = C.c_int32
+    L.mkh_solve_goalset.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + common[2:8] + \
+        [C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_uint64, C.c_int64, C.POINTER(MkhGoalSetIO), C.c_int32, C.c_void_p]
+    L.mkh_solve_goalset.restype = C.c_int32
+    L.mkh_select_goalset.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.POINTER(MkhGoalSetIO), C.c_int32, C.c_void_p]
+    L.mkh_select_goalset.restype = C.c_int32
     L.mkh_solve_trajectory.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + common[2:8] + \
         [C.c_int32, C.c_double, C.c_double, C.POINTER(MkhTrajectoryIO), C.c_int32, C.c_void_p]
     L.mkh_solve_trajectory.restype = C.c_int32
@@ -520,6 +617,7 @@ EXPORTED_SYMBOLS = (
     "mkh_seed_table_create", "mkh_seed_table_destroy", "mkh_seed_table_read", "mkh_seed_table_query",
     "mkh_problem_set_seed_table", "mkh_ladder_select", "mkh_solve_trajectory_ladder",
     "mkh_ladder_refine", "mkh_solve_trajectory_ladder_refined", "mkh_solve_multistart_set", "mkh_select_distinct",
+    "mkh_solve_goalset", "mkh_select_goalset",
 )
 
 LIE_OPS = {"se3_log": (0, 7, 0, (6,)), "se3_jlog": (1, 7, 0, (6, 6)), "se3_ljacinv": (2, 6, 0, (6, 6)),
@@ -1110,6 +1208,130 @@ class NativeProblem:
             _check(lib().mkh_select_distinct(self.handle, B, S, ptr(q_candidates), ptr(valid), ptr(reference), ptr(weights), K,
                                              float(min_distance), C.byref(io), devp, stream))
         return DistinctOut(*out.values())
+
+    def solve_goalset(self, q, frame_targets=None, posture_target=None, com_target=None, dt: float = 1e-2,
+                      damping: float = 1e-12, *, n_seeds: int, max_iters: int, pos_threshold: float, ori_threshold: float,
+                      goal_cost=None, goal_valid=None, rng_seed: int = 0, target_index0: int = 0, seeds=None, reference=None,
+                      weights=None, return_all: bool = False, wave_kernel: bool = False, lane_kernel: bool = False,
+                      quad_kernel: bool = False, seed_table=None) -> GoalSetOut:
+        """mkh_solve_goalset: multi-start to the best of G goals per row of q — solve_multistart's seeds and loops on the (B·G)
+        flattened (target, goal) pairs (seed 0 of every goal the row of q itself, the others drawn at target index
+        (target_index0 + b)·G + g, taken from `seeds` (B, G, S, nq) or from `seed_table`, queried with every goal's own
+        targets), per goal the converged seed closest to `reference` (default q), per target the reached goal with the smallest
+        goal_cost + distance (the rule: include/minkhip.h "THE RULE OF THE GOAL SET").  frame_targets (B, G, n_frame, 7);
+        posture / CoM targets held for the whole call, (n, w), or (B, G, n, w); goal_cost, goal_valid (B, G).  The handle needs
+        max_batch >= n_seeds; B·G·n_seeds loops beyond max_batch run in chunks of whole goals.  numpy in → numpy out
+        (synchronous); torch CUDA tensors in → torch tensors out on the current stream, no host copy."""
+        if seeds is not None and seed_table is not None:
+            raise ValueError("seeds and seed_table are two sources of the same starts: pass one of them")
+        m = self.nmodel.model
+        B, S, max_iters = int(q.shape[0]), int(n_seeds), int(max_iters)
+        if max_iters < 1:
+            raise ValueError("max_iters must be >= 1")
+        if self.n_dense_rows or self.n_dense_limit_rows or self.dense_limit_box:
+            raise ValueError("dense (plugin) rows are evaluated by the caller at q: no fused loop, no goal set")
+        if not self.n_frame:
+            raise ValueError("a goal set needs at least one frame task to test the thresholds on")
+        if frame_targets is None or len(frame_targets.shape) != 4:
+            raise ValueError(f"frame_targets must have shape (B, G, {self.n_frame}, 7)")
+        G = int(frame_targets.shape[1])
+        check_goalset_shape(B, G, S)
+        if S > self.max_batch:
+            raise MinkHipError(f"n_seeds={S} exceeds max_batch={self.max_batch} of this problem")
+        flags = (FLAG_WAVE_KERNEL if wave_kernel else 0) | (FLAG_LANE_KERNEL if lane_kernel else 0) | \
+            (FLAG_QUAD_KERNEL if quad_kernel else 0)
+        prep, empty, ptr, stream, devp = _call_kit(q)
+        flags |= devp
+        q, frame_targets, posture_target, com_target = prep(q), prep(frame_targets), prep(posture_target), prep(com_target)
+        seeds, reference, weights = prep(seeds), prep(reference), prep(weights)
+        if tuple(q.shape) != (B, m.nq):
+            raise ValueError(f"q must have shape (B, {m.nq}), got {tuple(q.shape)}")
+        if tuple(frame_targets.shape) != (B, G, self.n_frame, 7):
+            raise ValueError(f"frame_targets must have shape ({B}, G, {self.n_frame}, 7), got {tuple(frame_targets.shape)}")
+
+        def held_or_rows(x, n, w, name, flag):
+            if x is None:
+                raise ValueError(f"{name} is required")
+            if tuple(x.shape) == (n, w):
+                return 0
+            if tuple(x.shape) == (B, G, n, w):
+                return flag
+            raise ValueError(f"{name} must have shape ({n}, {w}) or ({B}, {G}, {n}, {w}), got {tuple(x.shape)}")
+
+        if self.n_posture:
+            flags |= held_or_rows(posture_target, self.n_posture, m.nq, "posture_target", FLAG_POSTURE_BATCHED)
+        if self.n_com:
+            flags |= held_or_rows(com_target, self.n_com, 3, "com_target", FLAG_COM_BATCHED)
+        if seeds is not None and tuple(seeds.shape) != (B, G, S, m.nq):
+            raise ValueError(f"seeds must have shape ({B}, {G}, {S}, {m.nq}), got {tuple(seeds.shape)}")
+        if reference is not None and tuple(reference.shape) != (B, m.nq):
+            raise ValueError(f"reference must have shape ({B}, {m.nq}), got {tuple(reference.shape)}")
+        if weights is not None and tuple(weights.shape) != (m.nv,):
+            raise ValueError(f"weights must have shape ({m.nv},), got {tuple(weights.shape)}")
+        goal_cost, goal_valid = _goal_inputs(goal_cost, goal_valid, B, G, prep, q)
+        f8, i4 = np.float64, np.int32
+        out = {"q_best": empty((B, m.nq), f8), "v_best": empty((B, m.nv), f8), "converged": empty((B,), i4),
+               "goal_index": empty((B,), i4), "seed_index": empty((B,), i4), "n_reached": empty((B,), i4),
+               "score": empty((B,), f8), "iters": empty((B,), i4), "status": empty((B,), i4),
+               "q_goal": empty((B, G, m.nq), f8), "v_goal": empty((B, G, m.nv), f8), "reached": empty((B, G), i4),
+               "seed_index_goal": empty((B, G), i4), "n_converged_goal": empty((B, G), i4), "distance_goal": empty((B, G), f8),
+               "iters_goal": empty((B, G), i4), "status_goal": empty((B, G), i4)}
+        every = dict.fromkeys(("q_all", "converged_all", "iters_all", "status_all", "seeds_out"))
+        if return_all:
+            every = {"q_all": empty((B, G, S, m.nq), f8), "converged_all": empty((B, G, S), i4), "iters_all": empty((B, G, S), i4),
+                     "status_all": empty((B, G, S), i4), "seeds_out": empty((B, G, S, m.nq), f8)}
+        io = MkhGoalSetIO()
+        io.seeds, io.q_ref, io.weights, io.goal_cost, io.goal_valid = ptr(seeds), ptr(reference), ptr(weights), ptr(goal_cost), \
+            ptr(goal_valid)
+        for n, x in {**out, **every}.items():
+            setattr(io, n, ptr(x))
+        with self._lock, _attached(self, seed_table):
+            _check(lib().mkh_solve_goalset(self.handle, B, G, ptr(q), ptr(frame_targets), ptr(posture_target), ptr(com_target),
+                                           float(dt), float(damping), max_iters, float(pos_threshold), float(ori_threshold), S,
+                                           int(rng_seed) & (2 ** 64 - 1), int(target_index0), C.byref(io), flags, stream))
+        return GoalSetOut(*out.values(), *every.values())
+
+    def select_goalset(self, q_candidates, valid=None, reference=None, weights=None, *, goal_cost=None,
+                       goal_valid=None) -> GoalSelectOut:
+        """mkh_select_goalset: the two levels of solve_goalset alone over the caller's own candidates — q_candidates
+        (B, G, S, nq), valid (B, G, S) (None: every candidate), reference (B, nq) (required), weights (nv,), goal_cost and
+        goal_valid (B, G).  numpy in → numpy out (synchronous); torch CUDA tensors in → torch tensors out on the current
+        stream, no host copy."""
+        m = self.nmodel.model
+        if len(q_candidates.shape) != 4:
+            raise ValueError(f"q_candidates must have shape (B, G, S, {m.nq}), got {tuple(q_candidates.shape)}")
+        B, G, S = (int(x) for x in q_candidates.shape[:3])
+        check_goalset_shape(B, G, S)
+        prep, empty, ptr, stream, devp = _call_kit(q_candidates)
+        q_candidates, reference, weights = prep(q_candidates), prep(reference), prep(weights)
+        if tuple(q_candidates.shape) != (B, G, S, m.nq):
+            raise ValueError(f"q_candidates must have shape (B, G, S, {m.nq}), got {tuple(q_candidates.shape)}")
+        if reference is None or tuple(reference.shape) != (B, m.nq):
+            raise ValueError(f"reference must have shape ({B}, {m.nq})")
+        if weights is not None and tuple(weights.shape) != (m.nv,):
+            raise ValueError(f"weights must have shape ({m.nv},), got {tuple(weights.shape)}")
+        if valid is not None:
+            if tuple(valid.shape) != (B, G, S):
+                raise ValueError(f"valid must have shape ({B}, {G}, {S}), got {tuple(valid.shape)}")
+            if devp:
+                import torch
+                valid = (torch.as_tensor(valid) != 0).to(device=q_candidates.device, dtype=torch.int32).contiguous()
+            else:
+                valid = _i32(np.asarray(valid) != 0)
+        goal_cost, goal_valid = _goal_inputs(goal_cost, goal_valid, B, G, prep, q_candidates)
+        f8, i4 = np.float64, np.int32
+        out = {"q_best": empty((B, m.nq), f8), "converged": empty((B,), i4), "goal_index": empty((B,), i4),
+               "seed_index": empty((B,), i4), "n_reached": empty((B,), i4), "score": empty((B,), f8),
+               "q_goal": empty((B, G, m.nq), f8), "reached": empty((B, G), i4), "seed_index_goal": empty((B, G), i4),
+               "n_converged_goal": empty((B, G), i4), "distance_goal": empty((B, G), f8)}
+        io = MkhGoalSetIO()
+        io.goal_cost, io.goal_valid = ptr(goal_cost), ptr(goal_valid)
+        for n, x in out.items():
+            setattr(io, n, ptr(x))
+        with self._lock:
+            _check(lib().mkh_select_goalset(self.handle, B, G, S, ptr(q_candidates), ptr(valid), ptr(reference), ptr(weights),
+                                            C.byref(io), devp, stream))
+        return GoalSelectOut(*out.values())
 
     def _solve_multistart(self, q, frame_targets, posture_target, com_target, dt, damping, S, max_iters, pos_thr, ori_thr,
                           rng_seed, target_index0, seeds, reference, weights, return_all, wave_kernel, lane_kernel, quad_kernel,

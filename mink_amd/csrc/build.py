@@ -318,6 +318,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     jobs.append((os.path.join(HERE, "convex_pre.hip"), os.path.join(BUILD, "convex_pre.o")))
     jobs.append((os.path.join(HERE, "multistart.hip"), os.path.join(BUILD, "multistart.o")))   # seeding / fan-out / selection of mkh_solve_multistart
     jobs.append((os.path.join(HERE, "solution_set.hip"), os.path.join(BUILD, "solution_set.o")))   # distinct-set selection of mkh_solve_multistart_set / mkh_select_distinct (same flags as multistart.hip: d_ref is bitwise multi-start's)
+    jobs.append((os.path.join(HERE, "goalset.hip"), os.path.join(BUILD, "goalset.o")))   # two-level selection of mkh_solve_goalset / mkh_select_goalset (same flags as multistart.hip: d_ref is bitwise multi-start's)
     jobs.append((os.path.join(HERE, "seed_table.hip"),os.path.join(BUILD, "seed_table.o")))   # key layout / K-nearest query of mkh_seed_table_*
     jobs.append((os.path.join(HERE, "trajectory.hip"), os.path.join(BUILD, "trajectory.o")))   # layout transposes / waypoint velocity of mkh_solve_trajectory
     jobs.append((os.path.join(HERE, "keyframes.hip"), os.path.join(BUILD, "keyframes.o")))     # target blends between keyframes of mkh_solve_keyframes

@@ -161,6 +161,12 @@ enum WsRole {
   // | v, R_XI: status | iters | converged | bad flags, (B, .) each; a host caller's path and flags as they came (IN_PATH,
   // IN_TRK); OUT_REF: tracked_out | repaired (B, T) | refined (B,) of a host-pointer call
   WS_R_Q, WS_R_V, WS_R_I32, WS_R_X, WS_R_XI, WS_IN_PATH, WS_IN_TRK, WS_OUT_REF,
+  // a goal set: a host caller's goal_cost and goal_valid, (B, G) each, as they came.  Its (B, G, S, .) candidate rows, its
+  // starts and q fanned out to the (B·G) pairs are a ladder's node rows with G for T and live in WS_L_Q … WS_L_Q0; its outputs
+  // go through WS_OUT_Q / V (q_best | q_goal), OUT_I32 (iters | status, per target then per goal), OUT_PICK (converged |
+  // goal_index | seed_index | n_reached (B,), then seed_index_goal | reached | n_converged_goal (B, G)) and OUT_LEN (score |
+  // distance_goal)
+  WS_IN_GCOST, WS_IN_GVALID,
   WS_COUNT
 };
 
@@ -2451,6 +2457,181 @@ int32_t mkh_solve_trajectory_ladder_refined(MkhProblem* p, int32_t B, int32_t T,
     st.down(refine->repaired, o_rep, R * i4);
     st.down(refine->refined, o_ref, Bz * i4);
   }
+  return st.finish();
+}
+
+// ---- goal sets (include/minkhip.h "THE RULE OF THE GOAL SET"; kernel: goalset.hip)
+// What both entry points refuse about the shape, the outputs and a host caller's costs.
+static int32_t goalset_refuse(int32_t B, int32_t G, int32_t S, const MkhGoalSetIO* io, bool loops, bool devp, const char* who) {
+  if (B < 1) return fail(MKH_E_INVALID, "%s: B = %d must be >= 1", who, B);
+  if (G < 1) return fail(MKH_E_INVALID, "%s: n_goals = %d must be >= 1", who, G);
+  if (S < 1) return fail(MKH_E_INVALID, "%s: n_seeds = %d must be >= 1", who, S);
+  if (!io || !io->q_best || !io->converged || !io->goal_index || !io->seed_index || !io->n_reached || !io->score || !io->q_goal ||
+      !io->seed_index_goal || !io->reached || !io->n_converged_goal || !io->distance_goal)
+    return fail(MKH_E_INVALID, "%s: io and its outputs q_best, converged, goal_index, seed_index, n_reached, score, q_goal, "
+                               "seed_index_goal, reached, n_converged_goal, distance_goal are required", who);
+  if (loops && (!io->v_best || !io->iters || !io->status || !io->v_goal || !io->iters_goal || !io->status_goal))
+    return fail(MKH_E_INVALID, "%s: io's outputs v_best, iters, status, v_goal, iters_goal, status_goal are required", who);
+  if ((long long)B * G * S > 0x7fffffffLL) return fail(MKH_E_LIMIT, "%s: B * n_goals * n_seeds = %lld rows", who, (long long)B * G * S);
+  if (!devp && io->goal_cost)
+    for (size_t r = 0, R = (size_t)B * G; r < R; ++r)
+      if (!(io->goal_cost[r] >= 0.0) || io->goal_cost[r] > 1.7976931348623157e308)
+        return fail(MKH_E_INVALID, "%s: goal_cost[%zu] = %g must be finite and >= 0", who, r, io->goal_cost[r]);
+  return MKH_OK;
+}
+
+// The two levels on device arrays into io's outputs: in place for a device-pointer call, else through the workspace and down.
+// v / status / iters may be absent (a selection over a caller's own candidates: conv is then its `valid`, or absent too).
+static void goalset_select(Stager& st, int B, int G, int S, const MkhGoalSetIO& io, const double* d_q_all, const double* d_v_all,
+                           const int32_t* d_status, const int32_t* d_iters, const int32_t* d_conv, const double* d_ref,
+                           const double* d_w) {
+  const MkhProblem* const p = st.p;
+  const size_t Bz = B, R = Bz * G, nq = p->dev.nq, nv = p->dev.nv, f8 = sizeof(double), i4 = sizeof(int32_t);
+  const bool loops = d_v_all != nullptr;
+  const double* const d_cost = st.up(WS_IN_GCOST, io.goal_cost, R);
+  const int32_t* d_gvalid = io.goal_valid;
+  if (!st.devp && io.goal_valid) {
+    int32_t* const t = st.i32(WS_IN_GVALID, R);
+    if (t) st.latch(hipMemcpyAsync(t, io.goal_valid, R * i4, hipMemcpyHostToDevice, st.stream));
+    d_gvalid = t;
+  }
+  mkh::GsOut o{io.q_best, loops ? io.v_best : nullptr, loops ? io.iters : nullptr, loops ? io.status : nullptr, io.converged,
+               io.goal_index, io.seed_index, io.n_reached, io.score, io.q_goal, loops ? io.v_goal : nullptr,
+               loops ? io.iters_goal : nullptr, loops ? io.status_goal : nullptr, io.seed_index_goal, io.reached,
+               io.n_converged_goal, io.distance_goal};
+  if (!st.devp) {
+    double* const oq = st.f64(WS_OUT_Q, (Bz + R) * nq);
+    double* const ov = loops ? st.f64(WS_OUT_V, (Bz + R) * nv) : nullptr;
+    int32_t* const rows = loops ? st.i32(WS_OUT_I32, 2 * (Bz + R)) : nullptr;
+    int32_t* const pick = st.i32(WS_OUT_PICK, 4 * Bz + 3 * R);
+    double* const len = st.f64(WS_OUT_LEN, Bz + R);
+    if (!st.ok()) return;
+    o.q_best = oq; o.q_goal = oq + Bz * nq;
+    if (loops) {
+      o.v_best = ov; o.v_goal = ov + Bz * nv;
+      o.iters = rows; o.status = rows + Bz; o.iters_goal = rows + 2 * Bz; o.status_goal = rows + 2 * Bz + R;
+    }
+    o.converged = pick; o.goal_index = pick + Bz; o.seed_index = pick + 2 * Bz; o.n_reached = pick + 3 * Bz;
+    o.seed_index_goal = pick + 4 * Bz; o.reached = pick + 4 * Bz + R; o.n_converged_goal = pick + 4 * Bz + 2 * R;
+    o.score = len; o.distance_goal = len + Bz;
+  }
+  const mkh::GsIn in{d_q_all, d_v_all, d_status, d_iters, d_conv, d_ref, d_w, d_cost, d_gvalid};
+  ST_LAUNCH(st, launch_gs_select(st.stream, B, G, S, (int)nq, (int)nv, p->model->njnt, p->ws[WS_JNT].i32(), in, o));
+  if (st.devp) return;
+  st.down(io.q_best, o.q_best, Bz * nq * f8);
+  st.down(io.q_goal, o.q_goal, R * nq * f8);
+  if (loops) {
+    st.down(io.v_best, o.v_best, Bz * nv * f8);
+    st.down(io.v_goal, o.v_goal, R * nv * f8);
+    st.down(io.iters, o.iters, Bz * i4);
+    st.down(io.status, o.status, Bz * i4);
+    st.down(io.iters_goal, o.iters_goal, R * i4);
+    st.down(io.status_goal, o.status_goal, R * i4);
+  }
+  st.down(io.converged, o.converged, Bz * i4);
+  st.down(io.goal_index, o.goal_index, Bz * i4);
+  st.down(io.seed_index, o.seed_index, Bz * i4);
+  st.down(io.n_reached, o.n_reached, Bz * i4);
+  st.down(io.seed_index_goal, o.seed_index_goal, R * i4);
+  st.down(io.reached, o.reached, R * i4);
+  st.down(io.n_converged_goal, o.n_converged_goal, R * i4);
+  st.down(io.score, o.score, Bz * f8);
+  st.down(io.distance_goal, o.distance_goal, R * f8);
+}
+
+int32_t mkh_solve_goalset(MkhProblem* p, int32_t B, int32_t n_goals, const double* q, const double* frame_targets,
+                          const double* posture_target, const double* com_target, double dt, double damping, int32_t max_iters,
+                          double pos_threshold, double ori_threshold, int32_t n_seeds, uint64_t rng_seed, int64_t target_index0,
+                          const MkhGoalSetIO* io, int32_t flags, void* hip_stream) {
+  const char* const who = "mkh_solve_goalset";
+  if (!p) return fail(MKH_E_INVALID, "null problem");
+  const int G = n_goals, S = n_seeds;
+  const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
+  if (const int32_t rc = goalset_refuse(B, G, S, io, true, devp, who)) return rc;
+  if (max_iters < 1) return fail(MKH_E_INVALID, "max_iters must be >= 1");
+  if (target_index0 < 0) return fail(MKH_E_INVALID, "target_index0 must be >= 0");
+  if (!(pos_threshold >= 0.0) || !(ori_threshold >= 0.0)) return fail(MKH_E_INVALID, "thresholds must be >= 0");
+  const DeviceProblem& P = p->dev;
+  if (const int32_t rc = refuse_inputs(P, q, frame_targets, posture_target, com_target, who, "goal set")) return rc;
+  if (S > p->max_batch)
+    return fail(MKH_E_INVALID, "%s: n_seeds = %d exceeds max_batch=%d of this problem (a goal is one chunk)", who, S, p->max_batch);
+  const MkhSeedTable* const tab = (!io->seeds && S > 1) ? p->seed_table : nullptr;
+  if (tab)
+    if (const int32_t rc = st_refuse(p, tab, S - 1, who)) return rc;
+  HIP_OK(hipSetDevice(p->model->device));
+  if (const int32_t rc = ms_build_tables(p)) return rc;
+  const bool pbat = (flags & MKH_FLAG_POSTURE_BATCHED) != 0, cbat = (flags & MKH_FLAG_COM_BATCHED) != 0;
+  Stager st{p, (hipStream_t)hip_stream, devp, "goalset"};
+  hipStream_t stream = st.stream;
+  const size_t Bz = B, R = Bz * G, N = R * S, nq = P.nq, nv = P.nv, f8 = sizeof(double), i4 = sizeof(int32_t);
+  const size_t ft_w = (size_t)P.n_frame * 7, pt_w = (size_t)P.n_posture * nq, ct_w = (size_t)P.n_com * 3;
+  // ---- inputs on the device; q once per (target, goal): the flattened pairs' "current posture"
+  const double* const d_q = st.up(WS_IN_Q, q, Bz * nq);
+  const double* const d_ft = st.up(WS_IN_FT, frame_targets, R * ft_w);
+  const double* const d_pt = pt_w ? st.up(WS_IN_PT, posture_target, pt_w * (pbat ? R : 1)) : posture_target;
+  const double* const d_ct = ct_w ? st.up(WS_IN_CT, com_target, ct_w * (cbat ? R : 1)) : com_target;
+  const double* const d_ref = st.up(WS_IN_REF, io->q_ref, Bz * nq);
+  const double* const d_w = st.up(WS_IN_W, io->weights, nv);
+  const double* const d_user = st.up(WS_IN_SEEDS, io->seeds, N * nq);
+  double* const d_q0 = st.f64(WS_L_Q0, R * nq);
+  ST_LAUNCH(st, launch_ms_fanout(stream, d_q, d_q0, B, G, (int)nq));
+  // ---- the candidates' rows, in the ladder's node slots: the caller's *_all arrays where they are device buffers
+  double* const l_q = (double*)st.given_or(WS_L_Q, io->q_all, N * nq * f8);
+  double* const l_v = st.f64(WS_L_V, N * nv);
+  int32_t* const l_st = (int32_t*)st.given_or(WS_L_ST, io->status_all, N * i4);
+  int32_t* const l_it = (int32_t*)st.given_or(WS_L_IT, io->iters_all, N * i4);
+  int32_t* const l_cv = (int32_t*)st.given_or(WS_L_CV, io->converged_all, N * i4);
+  double* const l_starts = io->seeds_out ? (double*)st.given_or(WS_L_STARTS, io->seeds_out, N * nq * f8) : nullptr;
+  if (!st.ok()) return st.finish();
+  // ---- the loops: multi-start on the (B·G) flattened pairs, whole goals per chunk of at most max_batch loops
+  const size_t per = (size_t)p->max_batch / S;
+  const int32_t ms_flags = flags | MKH_FLAG_DEVICE_PTRS;
+  for (size_t r0 = 0; r0 < R; r0 += per) {
+    const size_t n = R - r0 < per ? R - r0 : per, i0 = r0 * S;
+    MkhMultistartIO mio;
+    memset(&mio, 0, sizeof mio);
+    mio.seeds = d_user ? d_user + i0 * nq : nullptr;
+    mio.q_all = l_q + i0 * nq; mio.status_all = l_st + i0; mio.iters_all = l_it + i0; mio.converged_all = l_cv + i0;
+    mio.seeds_out = l_starts ? l_starts + i0 * nq : nullptr;
+    if (const int32_t rc = multistart_core(p, (int32_t)n, d_q0 + r0 * nq, d_ft + r0 * ft_w, (pt_w && pbat) ? d_pt + r0 * pt_w : d_pt,
+                                           (ct_w && cbat) ? d_ct + r0 * ct_w : d_ct, dt, damping, max_iters, pos_threshold,
+                                           ori_threshold, S, rng_seed, target_index0 * G + (int64_t)r0, &mio, ms_flags, hip_stream,
+                                           l_v + i0 * nv))
+      return st.finish(rc);
+  }
+  // ---- the two levels
+  goalset_select(st, B, G, S, *io, l_q, l_v, l_st, l_it, l_cv, d_ref ? d_ref : d_q, d_w);
+  if (devp) return st.finish();
+  st.down(io->q_all, l_q, N * nq * f8);
+  st.down(io->status_all, l_st, N * i4);
+  st.down(io->iters_all, l_it, N * i4);
+  st.down(io->converged_all, l_cv, N * i4);
+  st.down(io->seeds_out, l_starts, N * nq * f8);
+  return st.finish();
+}
+
+int32_t mkh_select_goalset(MkhProblem* p, int32_t B, int32_t G, int32_t S, const double* q_candidates, const int32_t* valid,
+                           const double* q_ref, const double* weights, const MkhGoalSetIO* io, int32_t flags, void* hip_stream) {
+  const char* const who = "mkh_select_goalset";
+  if (!p) return fail(MKH_E_INVALID, "null problem");
+  const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
+  if (const int32_t rc = goalset_refuse(B, G, S, io, false, devp, who)) return rc;
+  if (!q_candidates || !q_ref) return fail(MKH_E_INVALID, "%s: q_candidates and q_ref are required", who);
+  HIP_OK(hipSetDevice(p->model->device));
+  if (const int32_t rc = ms_build_tables(p)) return rc;
+  Stager st{p, (hipStream_t)hip_stream, devp, "select_goalset"};
+  const size_t Bz = B, N = Bz * G * S, nq = p->dev.nq;
+  const double* const d_cand = st.up(WS_L_Q, q_candidates, N * nq);
+  const double* const d_ref = st.up(WS_IN_REF, q_ref, Bz * nq);
+  const double* const d_w = st.up(WS_IN_W, weights, p->dev.nv);
+  const int32_t* d_valid = valid;
+  if (!devp && valid) {
+    int32_t* const t = st.i32(WS_L_CV, N);
+    if (t) st.latch(hipMemcpyAsync(t, valid, N * sizeof(int32_t), hipMemcpyHostToDevice, st.stream));
+    d_valid = t;
+  }
+  if (!st.ok()) return st.finish();
+  goalset_select(st, B, G, S, *io, d_cand, nullptr, nullptr, nullptr, d_valid, d_ref, d_w);
   return st.finish();
 }
 

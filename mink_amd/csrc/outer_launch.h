@@ -1,6 +1,6 @@
 // Launchers of the small kernels around the loop launches of the outer-loop entry points (mkh_solve_multistart,
-// mkh_solve_multistart_set, mkh_solve_trajectory, mkh_solve_keyframes, mkh_solve_trajectory_multistart, the ladder calls) and of
-// the seed tables in front of them: declared once, for the eight files that define them and for minkhip.hip, which calls them — a signature that
+// mkh_solve_multistart_set, mkh_solve_goalset, mkh_solve_trajectory, mkh_solve_keyframes, mkh_solve_trajectory_multistart, the ladder calls) and of
+// the seed tables in front of them: declared once, for the nine files that define them and for minkhip.hip, which calls them — a signature that
 // drifts fails to compile in the file that drifted.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -43,6 +43,33 @@ struct SsOut {
 hipError_t launch_ss_select(hipStream_t stream, int B, int S, int K, int nq, int nv, int njnt, const int32_t* jnt,
                             const double* q_all, const double* v_all, const int32_t* status_all, const int32_t* iters_all,
                             const int32_t* converged_all, const double* q_ref, const double* weights, double r2, const SsOut& o);
+// goal sets (goalset.hip): per goal the closest eligible of its S candidates, per target the reached goal with the smallest
+// goal_cost + distance, over (B, G, S, .) rows — (B, G, .) and (B, .) outputs.  converged_all (absent: every candidate is
+// eligible), status_all / iters_all / v_all with their outputs, goal_cost (zeros) and goal_valid (every goal) are optional.
+// B·G·S beyond int32: hipErrorInvalidValue.
+struct GsIn {
+  const double* __restrict__ q_all;
+  const double* __restrict__ v_all;
+  const int32_t* __restrict__ status_all;
+  const int32_t* __restrict__ iters_all;
+  const int32_t* __restrict__ converged_all;
+  const double* __restrict__ q_ref;
+  const double* __restrict__ weights;
+  const double* __restrict__ goal_cost;
+  const int32_t* __restrict__ goal_valid;
+};
+struct GsOut {
+  double* __restrict__ q_best;
+  double* __restrict__ v_best;
+  int32_t *iters, *status, *converged, *goal_index, *seed_index, *n_reached;
+  double* score;
+  double* __restrict__ q_goal;
+  double* __restrict__ v_goal;
+  int32_t *iters_goal, *status_goal, *seed_index_goal, *reached, *n_converged_goal;
+  double* distance_goal;
+};
+hipError_t launch_gs_select(hipStream_t stream, int B, int G, int S, int nq, int nv, int njnt, const int32_t* jnt, const GsIn& in,
+                            const GsOut& o);
 // trajectory IK (trajectory.hip): (B, T, W) ↔ (T, B, W) transposes and the joint velocity between waypoints — the kernels
 // around the T loop launches of mkh_solve_trajectory
 hipError_t launch_tj_gather(hipStream_t stream, const double* src, double* dst, int B, int T, int W);

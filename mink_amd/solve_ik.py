@@ -821,6 +821,196 @@ def distinct_solutions(configuration: Configuration, q_candidates, valid=None, n
                        un(out.n_distinct), un(out.n_valid), un(out.n_uncovered))
 
 
+class GoalSetResult(NamedTuple):
+    """Result of solve_ik_goalset.  Per target: the chosen (goal, seed)'s final configuration `q`, its last velocity `v`,
+    whether any goal was reached (`converged`), the chosen `goal_index` (nothing reached: the lowest valid goal, −1 when no goal
+    is valid) and `seed_index` (0), `n_reached` goals, the chosen goal's `score` = goal_cost + distance (+inf), and the chosen
+    loop's `iters` and `status`.  Per goal, (B, G, ·): `q_goal`, `v_goal` of the goal's closest converged seed (seed 0's when
+    the goal is not reached), `reached`, `seed_index_goal`, `n_converged_goal` of its S seeds, `distance_goal` (+inf),
+    `iters_goal`, `status_goal`.  With return_all also every loop's `q_all` (B, G, S, nq), `converged_all`, `iters_all`,
+    `status_all` (B, G, S) and the `seeds` (B, G, S, nq) the loops started from; None otherwise.  Without the leading axis for an
+    unbatched configuration."""
+    q: np.ndarray
+    v: np.ndarray
+    converged: np.ndarray
+    goal_index: np.ndarray
+    seed_index: np.ndarray
+    n_reached: np.ndarray
+    score: np.ndarray
+    iters: np.ndarray
+    status: np.ndarray
+    q_goal: np.ndarray
+    v_goal: np.ndarray
+    reached: np.ndarray
+    seed_index_goal: np.ndarray
+    n_converged_goal: np.ndarray
+    distance_goal: np.ndarray
+    iters_goal: np.ndarray
+    status_goal: np.ndarray
+    q_all: Optional[np.ndarray] = None
+    converged_all: Optional[np.ndarray] = None
+    iters_all: Optional[np.ndarray] = None
+    status_all: Optional[np.ndarray] = None
+    seeds: Optional[np.ndarray] = None
+
+
+class GoalChoice(NamedTuple):
+    """Result of best_goal: `q` (B, nq), `converged`, `goal_index`, `seed_index`, `n_reached`, `score` (B,), and per goal `q_goal`
+    (B, G, nq), `reached`, `seed_index_goal`, `n_valid_goal`, `distance_goal` (B, G) — without the leading axis for an unbatched
+    configuration."""
+    q: np.ndarray
+    converged: np.ndarray
+    goal_index: np.ndarray
+    seed_index: np.ndarray
+    n_reached: np.ndarray
+    score: np.ndarray
+    q_goal: np.ndarray
+    reached: np.ndarray
+    seed_index_goal: np.ndarray
+    n_valid_goal: np.ndarray
+    distance_goal: np.ndarray
+
+
+def _goal_arrays(goal_cost, goal_valid, B: int, G: int):
+    """goal_cost as float64 (B, G) and goal_valid as bool (B, G) on the host — each given as (G,) or (B, G) — or None."""
+    goal_cost = _host_array(goal_cost, "goal_cost")
+    if goal_cost is not None:
+        if goal_cost.shape not in ((G,), (B, G)):
+            raise ValueError(f"goal_cost must have shape {(G,)} or {(B, G)}, got {goal_cost.shape}")
+        if not (np.isfinite(goal_cost) & (goal_cost >= 0.0)).all():
+            raise ValueError("goal_cost must be finite and >= 0")
+        goal_cost = np.ascontiguousarray(np.broadcast_to(goal_cost, (B, G)))
+    if goal_valid is not None:
+        goal_valid = np.asarray(goal_valid.detach().cpu().numpy() if nat._is_torch(goal_valid) else goal_valid)
+        if goal_valid.shape not in ((G,), (B, G)):
+            raise ValueError(f"goal_valid must have shape {(G,)} or {(B, G)}, got {goal_valid.shape}")
+        goal_valid = np.ascontiguousarray(np.broadcast_to(goal_valid != 0, (B, G)))
+    return goal_cost, goal_valid
+
+
+def solve_ik_goalset(configuration: Configuration, tasks: Sequence, dt: float, goals, n_seeds: int, max_iters: int,
+                     pos_threshold: float, ori_threshold: float, goal_cost=None, goal_valid=None, reference=None, weights=None,
+                     seeds=None, seed_table: Optional["SeedTable"] = None, rng_seed: int = 0, return_all: bool = False,
+                     update: bool = True, max_instances: int = 1 << 20, damping: float = 1e-12,
+                     limits: Optional[Sequence] = None, safety_break: bool = False, solver: str = "mi355x") -> GoalSetResult:
+    """Global IK to the best of G candidate poses per target — the grasp poses of an object, the poses a placement accepts,
+    the yaws of a symmetric tool: which of them the robot reaches, and the configuration of the one closest to the current
+    posture, in one call, picked on the device.
+
+    `goals` is the trajectory calls' mapping {task: (G, w) or (B, G, w)} with the goals where those have their waypoints; at
+    least one FrameTask is needed.  Every goal of instance b is solved by solve_ik_multistart's loops from the configuration's
+    own q[b]: `n_seeds` starts, seed 0 q[b] itself, the others drawn by the stateless generator at target index b·G + g, taken
+    from `seeds` — (S, nq), (G, S, nq) or (B, G, S, nq) — or from `seed_table`, queried with every goal's own frame targets.
+
+    Per goal, the converged seed closest to `reference` (default: q) wins, as in solve_ik_multistart (`weights`, ties to the
+    lowest seed); a goal with such a seed, and not masked out by `goal_valid` — (G,) or (B, G) — is reached.  Per target, the
+    reached goal with the smallest `goal_cost` + distance wins (`goal_cost` (G,) or (B, G), finite and >= 0; ties to the lowest
+    goal).  Where nothing is reached the row is seed 0's of the lowest valid goal — what solve_ik_steps returns from q towards
+    it — with converged = False.  Masked goals still run their loops: pad a ragged set by repeating a valid goal (the rule in
+    full: include/minkhip.h "THE RULE OF THE GOAL SET").
+
+    Limits warnings and SolverError follow solve_ik_trajectory_ladder's rules on the CHOSEN rows only (`safety_break` as there).
+    With `update` the configuration is left at the chosen q.  The instances are walked in chunks of as many as keep
+    chunk·G·n_seeds within `max_instances`; a multi-device configuration shards by instance; the result depends on neither."""
+    del solver
+    S, max_iters = int(n_seeds), int(max_iters)
+    if S < 1:
+        raise ValueError("n_seeds must be >= 1")
+    if max_iters < 1:
+        raise ValueError("max_iters must be >= 1")
+    if int(max_instances) < 1:
+        raise ValueError("max_instances must be >= 1")
+    if pos_threshold is None or ori_threshold is None or not (float(pos_threshold) >= 0.0 and float(ori_threshold) >= 0.0):
+        raise ValueError("thresholds must be >= 0: a goal set's loops run in threshold mode only")
+    _refuse_plugin_rows({"dense": [t for t in tasks if t._is_dense()], "dense_limits": [x for x in (limits or ()) if x._is_dense()]},
+                        "solve_ik_goalset")
+    B, nq, nv = configuration.batch_size, configuration.nq, configuration.nv
+    seqs, G = _trajectory_targets(configuration, tasks, goals, axis="goals G")
+    _need_frame_task(tasks, "a goal set")
+    nat.check_goalset_shape(1, G, S)
+    if G * S > int(max_instances):
+        raise ValueError(f"one instance's goal set has G*n_seeds = {G * S} loops, beyond max_instances = {int(max_instances)}")
+    goal_cost, goal_valid = _goal_arrays(goal_cost, goal_valid, B, G)
+    seeds = _host_array(seeds, "seeds")
+    if seeds is not None:
+        if seeds.shape not in ((S, nq), (G, S, nq), (B, G, S, nq)):
+            raise ValueError(f"seeds must have shape {(S, nq)}, {(G, S, nq)} or {(B, G, S, nq)}, got {seeds.shape}")
+        seeds = np.ascontiguousarray(np.broadcast_to(seeds, (B, G, S, nq)))
+    reference = _optional_array(reference, "reference", (nq,), B)
+    weights = _optional_array(weights, "weights", (nv,))
+    _check_seed_table(seed_table, seeds, configuration, S)
+    handles, layout, chunk, n_dev = _compile_outer(configuration, tasks, limits, dt, "solve_ik_goalset", G * S, max_instances)
+    ft, pt, ct = _stacked_targets(configuration, layout, seqs, G)
+    # a batched target that is held over the goals gets its G axis: the call takes (n, w) or (B, G, n, w)
+    pt, ct = [x if x is None or x.ndim != 3 else np.ascontiguousarray(np.broadcast_to(x[:, None], (B, G) + x.shape[1:]))
+              for x in (pt, ct)]
+    q = configuration.q_batch
+    kw = dict(n_seeds=S, max_iters=max_iters, pos_threshold=float(pos_threshold), ori_threshold=float(ori_threshold),
+              rng_seed=int(rng_seed), weights=weights, return_all=bool(return_all))
+
+    def job(handle, lo, hi):
+        return handle.solve_goalset(q[lo:hi], _rows(ft, 0, lo, hi), _rows(pt, 2, lo, hi), _rows(ct, 2, lo, hi), dt, damping,
+                                    target_index0=lo, seeds=_rows(seeds, 0, lo, hi), reference=_rows(reference, 0, lo, hi),
+                                    goal_cost=_rows(goal_cost, 0, lo, hi), goal_valid=_rows(goal_valid, 0, lo, hi),
+                                    seed_table=seed_table, **kw)
+
+    res = _join(nat.GoalSetOut, _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job))
+    if safety_break and ((res.status & nat.ST_OUTSIDE_LIMITS) != 0).any():
+        b = int(np.argwhere((res.status & nat.ST_OUTSIDE_LIMITS) != 0)[0, 0])
+        raise _outside_limits(
+            f"solve_ik_goalset: the chosen loop of instance {b} (goal {int(res.goal_index[b])}, seed {int(res.seed_index[b])}) left "
+            "its configuration limits at some fused step")
+    _status_epilogue(res.status, "solve_ik_goalset", "chosen instance(s)",
+                     "QP failed for the chosen loop of {n} of {of} targets (first: index {first}, status {status}); "
+                     "none of their goals was reached")
+    if update:
+        configuration.update(res.q if configuration.batched else res.q[0])
+    un = configuration._unbatch
+    opt = lambda x, as_bool=False: None if x is None else un(x.astype(bool) if as_bool else x)
+    return GoalSetResult(un(res.q), un(res.v), un(res.converged.astype(bool)), un(res.goal_index), un(res.seed_index),
+                         un(res.n_reached), un(res.score), un(res.iters), un(res.status), un(res.q_goal), un(res.v_goal),
+                         un(res.reached.astype(bool)), un(res.seed_index_goal), un(res.n_converged_goal), un(res.distance_goal),
+                         un(res.iters_goal), un(res.status_goal), opt(res.q_all), opt(res.converged_all, True),
+                         opt(res.iters_all), opt(res.status_all), opt(res.seeds))
+
+
+def best_goal(configuration: Configuration, q_candidates, valid=None, goal_cost=None, goal_valid=None, reference=None,
+              weights=None) -> GoalChoice:
+    """The selection of solve_ik_goalset alone, over the caller's own candidates — the closed-form IK branches of every grasp
+    pose: q_candidates (G, S, nq) or (B, G, S, nq), `valid` (same leading shape; default: every candidate), `goal_cost` and
+    `goal_valid` (G,) or (B, G), `reference` (nq,) or (B, nq) (default: the configuration's q).  Per goal the valid candidate
+    closest to the reference, per target the reached goal with the smallest goal_cost + distance, ties to the lowest index —
+    the rule of solve_ik_goalset.  The configuration is not changed."""
+    from .tasks import PostureTask
+
+    B, nq, nv = configuration.batch_size, configuration.nq, configuration.nv
+    q_candidates = _host_array(q_candidates, "q_candidates")
+    if q_candidates is None or q_candidates.ndim not in (3, 4) or q_candidates.shape[-1] != nq or q_candidates.shape[-2] < 1 \
+            or q_candidates.shape[-3] < 1 or (q_candidates.ndim == 4 and q_candidates.shape[0] != B):
+        raise ValueError(f"q_candidates must have shape (G, S, {nq}) or ({B}, G, S, {nq}), got "
+                         f"{None if q_candidates is None else q_candidates.shape}")
+    G, S = q_candidates.shape[-3], q_candidates.shape[-2]
+    nat.check_goalset_shape(B, G, S)
+    q_candidates = np.ascontiguousarray(np.broadcast_to(q_candidates, (B, G, S, nq)))
+    if valid is not None:
+        valid = np.asarray(valid.detach().cpu().numpy() if nat._is_torch(valid) else valid)
+        if valid.shape not in ((G, S), (B, G, S)):
+            raise ValueError(f"valid must have shape {(G, S)} or {(B, G, S)}, got {valid.shape}")
+        valid = np.ascontiguousarray(np.broadcast_to(valid != 0, (B, G, S)))
+    goal_cost, goal_valid = _goal_arrays(goal_cost, goal_valid, B, G)
+    reference = _optional_array(reference, "reference", (nq,), B)
+    weights = _optional_array(weights, "weights", (nv,))
+    # (the selection reads the model's joint table through a problem handle: the smallest one, a posture task, serves)
+    prob, layout = _compile(configuration, [PostureTask(configuration.model, cost=1.0)], None, 1, devices=configuration.devices[:1])
+    with _pin(configuration, layout):
+        out = prob.select_goalset(q_candidates, valid, configuration.q_batch if reference is None else reference, weights,
+                                  goal_cost=goal_cost, goal_valid=goal_valid)
+    un = configuration._unbatch
+    return GoalChoice(un(out.q), un(out.converged.astype(bool)), un(out.goal_index), un(out.seed_index), un(out.n_reached),
+                      un(out.score), un(out.q_goal), un(out.reached.astype(bool)), un(out.seed_index_goal), un(out.n_valid_goal),
+                      un(out.distance_goal))
+
+
 class TrajectoryResult(NamedTuple):
     """Result of solve_ik_trajectory, (B, T, ·) — (T, ·) for an unbatched configuration: the configuration `q` at the end of
     every waypoint's loop, the loop's last velocity `v`, its `status` bits, and in threshold mode its `iters` and `converged`
