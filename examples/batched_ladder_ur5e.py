@@ -4,9 +4,13 @@
 (`solve_ik_trajectory_ladder`: several IK solutions per waypoint, the path picked by a dynamic program on the device) with
 drawn seeds and, with `--seed-table`, with seeds looked up in a table of stored postures by every waypoint's own pose.  With
 `--refine` every ladder runs a second time with the refinement pass behind its search (`refine=True`): the chosen path is
-re-tracked across its breaks and lost waypoints, and kept only where that makes it better.
+re-tracked across its breaks and lost waypoints, and kept only where that makes it better.  With `--n-nodes K` the drawn
+ladder also runs on K distinct nodes per waypoint, deduplicated on the device out of `--node-seeds` solutions (`n_nodes=K`:
+the search and the device's node rows then do not grow with the seeds), and with `--unwind` those solutions are first moved to
+the full turn of every long-range joint that lies nearest `home` (`unwind_turns=True`).
 
     python examples/batched_ladder_ur5e.py --paths 256 --seeds 8 --seed-table --refine
+    python examples/batched_ladder_ur5e.py --paths 256 --n-nodes 8 --node-seeds 64 --unwind
 
 UR5e, one FrameTask on `attachment_site` (costs 1 / 1, lm_damping 1), ConfigurationLimit, dt = 1, damping = 1e-3, thresholds
 1e-4 / 1e-4, 40 iterations per waypoint, every path started at `home`.  A path counts as COMPLETE when every waypoint is tracked
@@ -45,6 +49,10 @@ def main():
     ap.add_argument("--seed-table", action="store_true", help="also run the ladder seeded from a table of stored postures")
     ap.add_argument("--table-entries", type=int, default=16384)
     ap.add_argument("--refine", action="store_true", help="also run every ladder with the refinement pass behind its search")
+    ap.add_argument("--n-nodes", type=int, default=0, help="also run the drawn ladder on this many distinct nodes per waypoint")
+    ap.add_argument("--node-seeds", type=int, default=64, help="solutions per waypoint the nodes of --n-nodes are picked from")
+    ap.add_argument("--min-distance", type=float, default=0.1, help="two solutions closer than this are one node (rad)")
+    ap.add_argument("--unwind", action="store_true", help="with --n-nodes: move the solutions to the turn nearest `home` first")
     args = ap.parse_args()
     B, S, T = args.paths, args.seeds, args.waypoints
     rng = np.random.default_rng(20261018)
@@ -79,11 +87,28 @@ def main():
                                                              max_step=args.max_step, rng_seed=args.rng_seed, **kw, **extra)
     drawn, ms = timed(ladder)
     rows.append((f"ladder ({S} nodes per waypoint, drawn)", drawn.q, drawn.converged & ((drawn.status & ~1) == 0), ms))
-    results = [drawn]
+    results, notes = [drawn], []
     if args.refine:
         fine, ms = timed(lambda: ladder(refine=True))
         rows.append((f"ladder ({S} nodes per waypoint, drawn) + refinement", fine.q, fine.converged & ((fine.status & ~1) == 0), ms))
         results.append(fine)
+    if args.unwind and not args.n_nodes:
+        ap.error("--unwind works in front of the selection of --n-nodes")
+    if args.n_nodes:
+        K, S2 = args.n_nodes, args.node_seeds
+        nodes_kw = dict(n_nodes=K, min_distance=args.min_distance, unwind_turns=args.unwind)
+        few = lambda **extra: mink.solve_ik_trajectory_ladder(configuration, tasks, 1.0, targets, S2, args.max_iters,
+                                                              max_step=args.max_step, rng_seed=args.rng_seed, **kw, **nodes_kw, **extra)
+        label = f"ladder ({K} distinct of {S2} solutions{', unwound' if args.unwind else ''})"
+        picked, ms = timed(few)
+        rows.append((label, picked.q, picked.converged & ((picked.status & ~1) == 0), ms))
+        results.append(picked)
+        if args.refine:
+            fine, ms = timed(lambda: few(refine=True))
+            rows.append((label + " + refinement", fine.q, fine.converged & ((fine.status & ~1) == 0), ms))
+            results.append(fine)
+        notes.append(f"  nodes: {float(picked.n_distinct.mean()):.2f} distinct solutions per waypoint on average, "
+                     f"{int((picked.n_uncovered > 0).sum())} of {B * T} waypoints hold more than {K}")
     if args.seed_table:
         table = mink.SeedTable(mink.Configuration(model, home), tasks, args.table_entries, limits=limits)
         looked_up, ms = timed(lambda: ladder(seed_table=table))
@@ -108,6 +133,7 @@ def main():
         clear = np.abs(steps_sq - args.max_step ** 2) > 1e-9
         assert (res.edge_break[:, 1:] == (steps_sq > args.max_step ** 2))[clear].all()
         assert (res.n_tracked == (res.converged & ((res.status & ~1) == 0)).sum(axis=1)).all()
+    print("\n".join(notes), end="\n" if notes else "")
     for plain, fine in zip(results[0::2], results[1::2]) if args.refine else ():     # the pass never returns a worse path
         worse = [(T - f_t, f_b, f_l) > (T - p_t, p_b, p_l) for f_t, f_b, f_l, p_t, p_b, p_l in
                  zip(fine.n_tracked, fine.n_breaks, fine.path_length, plain.n_tracked, plain.n_breaks, plain.path_length)]

@@ -11,7 +11,9 @@ same solution.  Printed: how many distinct solutions the targets have and how ma
 
 Then the composition with the ladder search, on the far Cartesian lines of batched_ladder_ur5e.py: the waypoints of all lines
 solved as B·T independent targets, their K deduplicated solutions reshaped to (B, T, K, nq) rungs for `ladder_path`, next to
-`solve_ik_trajectory_ladder`, which searches all S loop results of every waypoint.
+`solve_ik_trajectory_ladder`, which searches all S loop results of every waypoint.  The composition stays here as an
+illustration of the two calls; `solve_ik_trajectory_ladder(..., n_nodes=K)` does the same in one call on the device, without
+the B·T·S rows crossing the bus (examples/batched_ladder_ur5e.py --n-nodes).
 """
 import argparse
 import os

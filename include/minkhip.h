@@ -109,6 +109,10 @@ extern "C" {
                                      * qualifies, whatever the batch size (default: plain solves below 73728 instances, fused
                                      * loops below 28672; the fused loops of a floating base under frame / posture tasks alone on
                                      * its two-row build, which the default leaves on the wavefront kernel; parity/diagnostic switch) */
+#define MKH_FLAG_UNWIND_TURNS 1024  /* mkh_solve_multistart_set and mkh_solve_trajectory_ladder_nodes only: the loops' results are
+                                     * moved to the full turn nearest the reference posture ("THE RULE OF THE UNWINDING") before
+                                     * the distinct-set selection compares them.  Every other entry point refuses the bit with
+                                     * MKH_E_INVALID. */
 
 /* frame types (mink/constants.py:3 SUPPORTED_FRAMES) */
 #define MKH_FRAME_BODY 0
@@ -525,6 +529,46 @@ int32_t mkh_solve_multistart_set(MkhProblem *problem, int32_t B, const double *q
 int32_t mkh_select_distinct(MkhProblem *problem, int32_t B, int32_t S, const double *q_candidates, const int32_t *valid,
                             const double *q_ref, const double *weights, int32_t n_solutions, double min_distance,
                             const MkhSolutionSetIO *io, int32_t flags, void *hip_stream);
+
+/*
+ * Turn unwinding: an opt-in step IN FRONT of the rule of the set.  THE RULE OF THE SET above stays as it is — two solutions a
+ * full turn apart are different solutions — and nothing changes by default.  A caller for whom the turn does not matter (a
+ * joint that may be commanded to any turn within its range) asks for every candidate to be moved to the turn nearest a
+ * reference posture first; the set then spends its K slots on IK branches, not on turns of one branch.
+ *
+ * THE RULE OF THE UNWINDING (mkh_unwind_turns; MKH_FLAG_UNWIND_TURNS runs it on the results of the loops).
+ * TWO_PI = 6.283185307179586 (the double nearest 2 pi).  Every product and every sum below is rounded on its own, never fused —
+ * the convention of multi-start's seeding rule, so a restatement in numpy reproduces the device bit for bit.
+ *   A joint is ELIGIBLE when it is a hinge and either unlimited or range_hi - range_lo >= TWO_PI (the rounded difference).
+ *   For an eligible joint, x = the row's value and r = the reference's value at its qposadr:
+ *     quotient = (r - x) / TWO_PI;  k = rint(quotient), rounding half to even;
+ *     k = 0 when x, r or the quotient is not finite, or |quotient| > 1e6;
+ *     when the joint is limited:  while k > 0 and x + k·TWO_PI > range_hi: k -= 1;
+ *                                 while k < 0 and x + k·TWO_PI < range_lo: k += 1;
+ *     the result is x itself, bit for bit, when k == 0, else x + k·TWO_PI.
+ *   Every other entry of the row — slides, the quaternions and positions of ball and free joints, hinges that are not
+ *   eligible — is a bit copy.
+ * Consequences.  (1) The map is idempotent, bitwise: the quotient of a result is within 1/2 of 0 up to rounding, a second
+ * pass finds k = 0 — or a k that the limits cut back to 0 — and returns the value itself; an exact half (r - x = ±pi) rounds
+ * to the even k = 0 and stays (only a quotient within rounding of k + 1/2 for a k != 0 can land on either side of the half
+ * after its shift).  (2) A value inside its range stays inside: k is cut back until the shifted value is, and k = 0
+ * returns x.  A value outside its range is not pulled in.  (3) The pose of the robot moves only by the rounding of the
+ * shift: a hinge at x + 2 pi k is the hinge at x, and |k·TWO_PI - 2 pi k| <= 2.5e-16 |k|.  (4) The loop's flags are CARRIED OVER,
+ * not re-evaluated: a row that converged counts as converged after the unwinding, its status, iteration count and velocity
+ * are the loop's.
+ *
+ * mkh_unwind_turns: the rule alone.  q_rows (n_rows, nq); row i is unwound toward q_ref[i / rows_per_ref], q_ref
+ * (ceil(n_rows / rows_per_ref), nq); q_out (n_rows, nq) may be q_rows itself (in place).  n_rows >= 1, rows_per_ref >= 1.  Pointers
+ * are host pointers (staged, synchronous) or device pointers with MKH_FLAG_DEVICE_PTRS (asynchronous on the stream); no other
+ * flag bit is accepted.
+ *
+ * MKH_FLAG_UNWIND_TURNS on mkh_solve_multistart_set: the B·S loop results are unwound toward q_ref[b] (io->q_ref, or q when NULL)
+ * in the workspace between the loops and the selection.  q_all then returns the UNWOUND rows; seeds_out, converged_all,
+ * iters_all and status_all are unchanged.  The set's invariant "slot 0 is bitwise what mkh_solve_multistart returns" then holds
+ * MODULO THE UNWINDING of that row: slot 0 is the closest unwound candidate, which need not be the closest raw one.
+ */
+int32_t mkh_unwind_turns(MkhProblem *problem, int32_t n_rows, int32_t rows_per_ref, const double *q_rows, const double *q_ref,
+                         double *q_out, int32_t flags, void *hip_stream);
 
 /*
  * Goal sets: multi-start IK to the BEST of G = n_goals candidate poses per target — the grasp poses of an object, the poses a
@@ -1045,6 +1089,64 @@ int32_t mkh_solve_trajectory_ladder_refined(MkhProblem *problem, int32_t B, int3
                                             double pos_threshold, double ori_threshold, uint64_t rng_seed,
                                             int64_t target_index0, const MkhTrajectoryLadderIO *io,
                                             const MkhLadderRefineIO *refine, int32_t flags, void *hip_stream);
+
+/*
+ * mkh_solve_trajectory_ladder_nodes: the ladder on K = n_nodes DEDUPLICATED nodes per rung.  The S = n_seeds loop results of a
+ * rung are reduced to at most K distinct ones by THE RULE OF THE SET on the device, between the loops and the search; the
+ * search then runs on (B, T, K) nodes.  The search costs T·K² instead of T·S², the node workspace holds B·T·K rows instead of
+ * B·T·S, and S is no longer bounded by the search's 256 (back-pointers are bytes) but by the set's 4 096 candidates.
+ *
+ * THE RULE, for rung (b, t):
+ *   The candidates are the S loop results, BITWISE what mkh_solve_multistart gives in q_all / converged_all / status_all /
+ *   iters_all for target row (target_index0 + b)·T + t — seeding, io->seeds, an attached seed table exactly as in
+ *   mkh_solve_trajectory_ladder.
+ *   With MKH_FLAG_UNWIND_TURNS they are unwound toward q[b] (THE RULE OF THE UNWINDING); their flags are carried over.
+ *   THE RULE OF THE SET runs on them with K = n_nodes, r = min_distance, q_ref = q[b] and the ladder's weights (io->weights);
+ *   a candidate is eligible when it is TRACKED in the ladder's sense (converged, no status bit but MKH_ST_OUTSIDE_LIMITS) —
+ *   which is the set's own eligibility.
+ *   Node (b, t, j) is slot j of that set; it is tracked iff j < n_distinct.  An empty slot holds candidate 0's row, as the
+ *   set rule says, and is not tracked.
+ *   THE RULE of the ladder then runs on the (B, T, K) nodes, unchanged: node_index (B, T) is a SLOT index in 0 .. K-1.
+ *   The refinement, with `refine` != NULL, runs on the chosen path, unchanged (as in mkh_solve_trajectory_ladder_refined; of
+ *   `refine` only tracked_out, repaired and refined are used).
+ * The nodes of a rung are a subset of its S candidates (up to the unwinding), so the path's key is never smaller than the
+ * plain ladder's on the same loops, and n_tracked is EQUAL: a rung holds a tracked node iff it holds a tracked candidate.
+ * With n_nodes >= n_seeds, min_distance = 0 and the flag clear, the nodes of a rung are its tracked candidates in ascending
+ * d_ref (bitwise copies merged), and on every instance WHOSE RUNGS ALL HOLD A TRACKED CANDIDATE (n_tracked == T) the chosen
+ * path's q_traj, n_breaks and path_length are the plain ladder's, ties between equal keys aside.  On a rung nobody tracked the
+ * plain ladder chooses among S untracked rows, this call holds candidate 0's row only: there the key may be larger.
+ *
+ * Limits.  1 <= n_nodes <= 64 (the set's; the search's 256 lies above it); 1 <= n_seeds <= 4 096, n_seeds <= max_batch;
+ * min_distance >= 0 and finite; T, max_step_sq, the targets, the thresholds and the weights as in mkh_solve_trajectory_ladder.
+ * Every argument error is reported before any device work.
+ *
+ * Workspace.  The loops of a chunk (whole rungs, at most max_batch loops) write into multi-start's candidate buffers of ONE
+ * chunk; the selection writes the chunk's slots straight into the (B·T, K, .) node arrays.  Nothing the call allocates is
+ * sized B·T·S; only io->seeds and io->seeds_out, when the caller passes them, have that size (a host caller's are staged
+ * whole, like every input and output of a host-pointer call).
+ *
+ * Outputs.  `io` is mkh_solve_trajectory_ladder's struct: the chosen nodes' rows, the search's outputs, qvel — and its optional
+ * q_all (B, T, K, nq), v_all (B, T, K, nv), status_all, iters_all, converged_all (B, T, K) are the NODES' rows (converged_all
+ * of an empty slot is candidate 0's flag); seeds_out (B, T, S, nq) stays the starts.  `nodes` holds what is new, all required:
+ * node_seed_index, node_multiplicity, node_distance (B, T, K) — the slots' seed_index (-1: empty), multiplicity and d_ref of the
+ * set rule; n_distinct, n_converged, n_uncovered (B, T) — the set rule's per-target counts; seed_index (B, T) — the chosen
+ * node's candidate index s (-1 where the chosen slot is empty: a lost waypoint).
+ */
+typedef struct MkhLadderNodesIO {
+  int32_t *node_seed_index;    /* (B, T, K)  the candidate each node is; -1: empty slot                           required  */
+  int32_t *node_multiplicity;  /* (B, T, K)  candidates the node covers; 0: empty slot                            required  */
+  double *node_distance;       /* (B, T, K)  its d_ref to q[b]; +inf: empty slot                                  required  */
+  int32_t *n_distinct;         /* (B, T)     nodes filled                                                         required  */
+  int32_t *n_converged;        /* (B, T)     tracked candidates                                                   required  */
+  int32_t *n_uncovered;        /* (B, T)     tracked candidates no node covers                                    required  */
+  int32_t *seed_index;         /* (B, T)     the chosen node's candidate index                                    required  */
+} MkhLadderNodesIO;
+int32_t mkh_solve_trajectory_ladder_nodes(MkhProblem *problem, int32_t B, int32_t T, int32_t n_seeds, int32_t n_nodes,
+                                          double min_distance, const double *q, const double *frame_targets,
+                                          const double *posture_target, const double *com_target, double dt, double damping,
+                                          int32_t max_iters, double pos_threshold, double ori_threshold, uint64_t rng_seed,
+                                          int64_t target_index0, const MkhTrajectoryLadderIO *io, const MkhLadderNodesIO *nodes,
+                                          const MkhLadderRefineIO *refine, int32_t flags, void *hip_stream);
 
 /* Same inputs; additionally writes the requested intermediates (build_ik / compute_error /
  * compute_jacobian / get_transform_frame_to_world parity taps).  v_out/status_out may be NULL

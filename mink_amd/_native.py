@@ -29,6 +29,7 @@ FLAG_TWO_WAVES = 64
 FLAG_WARM_START = 128
 FLAG_QUAD_KERNEL = 256
 FLAG_FULL_ROWS = 512
+FLAG_UNWIND_TURNS = 1024         # solve_multistart_set / solve_trajectory_ladder_nodes only: include/minkhip.h "THE RULE OF THE UNWINDING"
 # per-handle diagnostic switches of mkh_problem_create_diag (include/minkhip.h MKH_DIAG_*): parity tests and measurements only
 DIAG_NO_WIDE_REDO, DIAG_NO_TIGHT_REDO, DIAG_NO_COLD_REFINE, DIAG_NO_PAIR_CULL = 1, 2, 4, 8
 _diag_default = threading.local()
@@ -465,6 +466,57 @@ def check_ladder_shape(S: int, T: int, max_step_sq: float) -> None:
         raise ValueError(f"max_step must be >= 0 (None: no gate), got a squared gate of {max_step_sq}")
 
 
+LADDER_NODES_IO_FIELDS = ("node_seed_index", "node_multiplicity", "node_distance", "n_distinct", "n_converged", "n_uncovered",
+                          "seed_index")
+
+
+class MkhLadderNodesIO(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in LADDER_NODES_IO_FIELDS]
+
+
+class TrajectoryLadderNodesOut(NamedTuple):
+    """What NativeProblem.solve_trajectory_ladder_nodes returns (arrays of the caller's kind): TrajectoryLadderOut's fields, in
+    its order — with return_all the *_all fields are the NODES' rows, (B, T, K, ·), and `seeds` the (B, T, S, nq) starts — and
+    behind them the set's: `node_seed_index`, `node_multiplicity`, `node_distance` (B, T, K), `n_distinct`, `n_converged`,
+    `n_uncovered` (B, T), and `seed_index` (B, T), the chosen node's candidate index."""
+    q: object
+    v: object
+    status: object
+    iters: object
+    converged: object
+    node_index: object
+    n_tracked: object
+    n_breaks: object
+    path_length: object
+    edge_break: object
+    qvel: object = None
+    q_all: object = None
+    v_all: object = None
+    status_all: object = None
+    iters_all: object = None
+    converged_all: object = None
+    seeds: object = None
+    tracked: object = None
+    repaired: object = None
+    refined: object = None
+    node_seed_index: object = None
+    node_multiplicity: object = None
+    node_distance: object = None
+    n_distinct: object = None
+    n_converged: object = None
+    n_uncovered: object = None
+    seed_index: object = None
+
+
+def check_ladder_nodes_shape(S: int, K: int, T: int, max_step_sq: float, min_distance: float) -> None:
+    """The limits of include/minkhip.h on mkh_solve_trajectory_ladder_nodes' shape, gate and radius, with no device in sight:
+    the search's on the K nodes and T, the set's on K, the radius and the S candidates of a rung."""
+    if S < 1:
+        raise ValueError("a rung needs at least one candidate: n_seeds must be >= 1")
+    check_solution_set(K, min_distance, S)
+    check_ladder_shape(K, T, max_step_sq)
+
+
 def check_keyframe_times(key_times, waypoint_times):
     """The checks of include/minkhip.h "THE RULE" on the two time arrays, with no device in sight: float64 (K,) and (T,) arrays, or
     ValueError — key times strictly increasing, waypoint times non-decreasing and inside the keyframes' range, no NaN."""
@@ -575,6 +627,12 @@ def lib() -> C.CDLL:
         [C.c_int32, C.c_double, C.c_double, C.c_uint64, C.c_int64, C.POINTER(MkhTrajectoryLadderIO), C.POINTER(MkhLadderRefineIO),
          C.c_int32, C.c_void_p]
     L.mkh_solve_trajectory_ladder_refined.restype = C.c_int32
+    L.mkh_solve_trajectory_ladder_nodes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double] + \
+        common[2:8] + [C.c_int32, C.c_double, C.c_double, C.c_uint64, C.c_int64, C.POINTER(MkhTrajectoryLadderIO),
+                       C.POINTER(MkhLadderNodesIO), C.POINTER(MkhLadderRefineIO), C.c_int32, C.c_void_p]
+    L.mkh_solve_trajectory_ladder_nodes.restype = C.c_int32
+    L.mkh_unwind_turns.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    L.mkh_unwind_turns.restype = C.c_int32
     L.mkh_ladder_refine.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p] + common[3:8] + \
         [C.c_int32, C.c_double, C.c_double, C.POINTER(MkhLadderRefineIO), C.c_int32, C.c_void_p]
     L.mkh_ladder_refine.restype = C.c_int32
@@ -617,7 +675,7 @@ EXPORTED_SYMBOLS = (
     "mkh_seed_table_create", "mkh_seed_table_destroy", "mkh_seed_table_read", "mkh_seed_table_query",
     "mkh_problem_set_seed_table", "mkh_ladder_select", "mkh_solve_trajectory_ladder",
     "mkh_ladder_refine", "mkh_solve_trajectory_ladder_refined", "mkh_solve_multistart_set", "mkh_select_distinct",
-    "mkh_solve_goalset", "mkh_select_goalset",
+    "mkh_solve_goalset", "mkh_select_goalset", "mkh_unwind_turns", "mkh_solve_trajectory_ladder_nodes",
 )
 
 LIE_OPS = {"se3_log": (0, 7, 0, (6,)), "se3_jlog": (1, 7, 0, (6, 6)), "se3_ljacinv": (2, 6, 0, (6, 6)),
@@ -1153,12 +1211,14 @@ class NativeProblem:
                              damping: float = 1e-12, *, n_seeds: int, n_solutions: int, max_iters: int, pos_threshold: float,
                              ori_threshold: float, min_distance: float = 0.1, rng_seed: int = 0, target_index0: int = 0,
                              seeds=None, reference=None, weights=None, return_all: bool = False, wave_kernel: bool = False,
-                             lane_kernel: bool = False, quad_kernel: bool = False, seed_table=None) -> SolutionSetOut:
+                             lane_kernel: bool = False, quad_kernel: bool = False, seed_table=None,
+                             unwind_turns: bool = False) -> SolutionSetOut:
         """mkh_solve_multistart_set: solve_multistart's seeds and loops, then up to `n_solutions` converged results per row of q
         no two of which lie within `min_distance` of each other (Σ_k weights_k·(a ⊖ b)_k² <= min_distance²), in ascending
         distance from `reference` (default q) — slot 0 is solve_multistart's choice (the rule: include/minkhip.h "THE RULE OF THE
         SET").  numpy in → numpy out (synchronous); torch CUDA tensors in → torch tensors out, asynchronous on the current
-        stream, no host copy.  Everything else as in solve_multistart."""
+        stream, no host copy.  Everything else as in solve_multistart.  `unwind_turns` (MKH_FLAG_UNWIND_TURNS): the loops'
+        results are moved to the turn nearest the reference before they are compared; q_all then holds the unwound rows."""
         if seeds is not None and seed_table is not None:
             raise ValueError("seeds and seed_table are two sources of the same starts: pass one of them")
         check_solution_set(int(n_solutions), float(min_distance), int(n_seeds))
@@ -1166,7 +1226,33 @@ class NativeProblem:
             return self._solve_multistart(q, frame_targets, posture_target, com_target, dt, damping, int(n_seeds), int(max_iters),
                                           float(pos_threshold), float(ori_threshold), int(rng_seed), int(target_index0), seeds,
                                           reference, weights, return_all, wave_kernel, lane_kernel, quad_kernel,
-                                          solution_set=(int(n_solutions), float(min_distance)))
+                                          solution_set=(int(n_solutions), float(min_distance)),
+                                          extra_flags=FLAG_UNWIND_TURNS if unwind_turns else 0)
+
+    def unwind_turns(self, q_rows, reference, out=None):
+        """mkh_unwind_turns: include/minkhip.h "THE RULE OF THE UNWINDING" alone — q_rows (n, nq) or (B, S, nq), every row moved
+        to the full turn of its eligible hinges nearest its reference: reference (B, nq), row i of the flattened rows using
+        reference[i // S] (a 2-D q_rows: S = n / B, which must divide).  `out` may be q_rows itself.  numpy in → numpy out
+        (synchronous); torch CUDA tensors in → torch tensors out on the current stream, no host copy."""
+        m = self.nmodel.model
+        shp = tuple(q_rows.shape)
+        if len(shp) not in (2, 3) or shp[-1] != m.nq or min(shp) < 1:
+            raise ValueError(f"q_rows must have shape (n, {m.nq}) or (B, S, {m.nq}), got {shp}")
+        prep, empty, ptr, stream, devp = _call_kit(q_rows)
+        q_rows, reference = prep(q_rows), prep(reference)
+        n = shp[0] if len(shp) == 2 else shp[0] * shp[1]
+        if reference is None or len(reference.shape) != 2 or int(reference.shape[1]) != m.nq or int(reference.shape[0]) < 1:
+            raise ValueError(f"reference must have shape (B, {m.nq})")
+        Bref = int(reference.shape[0])
+        if n % Bref or (len(shp) == 3 and shp[0] != Bref):
+            raise ValueError(f"{n} rows do not split evenly among {Bref} reference rows")
+        if out is None:
+            out = empty(shp, np.float64)
+        elif tuple(out.shape) != shp or prep(out) is not out:
+            raise ValueError(f"out must be a contiguous float64 array of shape {shp}, of q_rows' kind")
+        with self._lock:
+            _check(lib().mkh_unwind_turns(self.handle, n, n // Bref, ptr(q_rows), ptr(reference), ptr(out), devp, stream))
+        return out
 
     def select_distinct(self, q_candidates, valid=None, reference=None, weights=None, *, n_solutions: int,
                         min_distance: float = 0.1) -> DistinctOut:
@@ -1335,7 +1421,7 @@ class NativeProblem:
 
     def _solve_multistart(self, q, frame_targets, posture_target, com_target, dt, damping, S, max_iters, pos_thr, ori_thr,
                           rng_seed, target_index0, seeds, reference, weights, return_all, wave_kernel, lane_kernel, quad_kernel,
-                          solution_set=None):
+                          solution_set=None, extra_flags: int = 0):
         m = self.nmodel.model
         B = int(q.shape[0])
         if S < 1:
@@ -1347,7 +1433,7 @@ class NativeProblem:
         if self.n_dense_rows or self.n_dense_limit_rows or self.dense_limit_box:
             raise ValueError("dense (plugin) rows are evaluated by the caller at q: no fused loop, no multi-start")
         flags = (FLAG_WAVE_KERNEL if wave_kernel else 0) | (FLAG_LANE_KERNEL if lane_kernel else 0) | \
-            (FLAG_QUAD_KERNEL if quad_kernel else 0)
+            (FLAG_QUAD_KERNEL if quad_kernel else 0) | int(extra_flags)
         prep, empty, ptr, stream, devp = _call_kit(q)
         flags |= devp
         q, frame_targets, posture_target, com_target = prep(q), prep(frame_targets), prep(posture_target), prep(com_target)
@@ -1510,6 +1596,31 @@ class NativeProblem:
         out (synchronous); torch CUDA tensors in → torch tensors out on the current stream, no host copy.  With `refine` the
         path is re-tracked across its breaks and lost nodes behind the search (mkh_solve_trajectory_ladder_refined; the handle
         then needs max_batch >= B as well) and `tracked`, `repaired`, `refined` are returned with it."""
+        return self._solve_trajectory_ladder(q, frame_targets, posture_target, com_target, dt, damping, n_seeds, max_iters,
+                                             pos_threshold, ori_threshold, max_step_sq, rng_seed, target_index0, seeds, weights,
+                                             qvel_dt, return_all, wave_kernel, lane_kernel, quad_kernel, seed_table, refine, None)
+
+    def solve_trajectory_ladder_nodes(self, q, frame_targets=None, posture_target=None, com_target=None, dt: float = 1e-2,
+                                      damping: float = 1e-12, *, n_seeds: int, n_nodes: int, max_iters: int, pos_threshold: float,
+                                      ori_threshold: float, min_distance: float = 0.1, unwind_turns: bool = False,
+                                      max_step_sq: float = float("inf"), rng_seed: int = 0, target_index0: int = 0, seeds=None,
+                                      weights=None, qvel_dt: Optional[float] = None, return_all: bool = False,
+                                      wave_kernel: bool = False, lane_kernel: bool = False, quad_kernel: bool = False,
+                                      seed_table=None, refine: bool = False) -> TrajectoryLadderNodesOut:
+        """mkh_solve_trajectory_ladder_nodes: solve_trajectory_ladder with every rung's `n_seeds` loop results reduced on the
+        device to at most `n_nodes` distinct ones (select_distinct's rule with `min_distance`, the reference q, the ladder's
+        weights; with `unwind_turns` moved to the turn nearest q first) before the search — n_seeds up to 4 096, the search and
+        the node workspace on n_nodes <= 64 per rung.  Everything else as in solve_trajectory_ladder; with return_all the *_all
+        fields are the nodes' rows (B, T, K, ·)."""
+        return self._solve_trajectory_ladder(q, frame_targets, posture_target, com_target, dt, damping, n_seeds, max_iters,
+                                             pos_threshold, ori_threshold, max_step_sq, rng_seed, target_index0, seeds, weights,
+                                             qvel_dt, return_all, wave_kernel, lane_kernel, quad_kernel, seed_table, refine,
+                                             (int(n_nodes), float(min_distance), bool(unwind_turns)))
+
+    def _solve_trajectory_ladder(self, q, frame_targets, posture_target, com_target, dt, damping, n_seeds, max_iters,
+                                 pos_threshold, ori_threshold, max_step_sq, rng_seed, target_index0, seeds, weights, qvel_dt,
+                                 return_all, wave_kernel, lane_kernel, quad_kernel, seed_table, refine, nodes):
+        """The body of the two ladder calls; `nodes`: None, or (n_nodes, min_distance, unwind_turns)."""
         if seeds is not None and seed_table is not None:
             raise ValueError("seeds and seed_table are two sources of the same starts: pass one of them")
         m = self.nmodel.model
@@ -1527,7 +1638,11 @@ class NativeProblem:
         if frame_targets is None or len(frame_targets.shape) != 4:
             raise ValueError(f"frame_targets must have shape (B, T, {self.n_frame}, 7)")
         T = int(frame_targets.shape[1])
-        check_ladder_shape(S, T, float(max_step_sq))
+        if nodes is None:
+            check_ladder_shape(S, T, float(max_step_sq))
+        else:
+            check_ladder_nodes_shape(S, nodes[0], T, float(max_step_sq), nodes[1])
+        W = S if nodes is None else nodes[0]          # nodes per rung: what the *_all arrays hold
         if S > self.max_batch:
             raise MinkHipError(f"n_seeds={S} exceeds max_batch={self.max_batch} of this problem")
         if refine and B > self.max_batch:
@@ -1567,8 +1682,8 @@ class NativeProblem:
                "edge_break": empty((B, T), i4), "qvel": empty((B, T, m.nv), f8) if qvel_dt is not None else None}
         every = dict.fromkeys(("q_all", "v_all", "status_all", "iters_all", "converged_all", "seeds_out"))
         if return_all:
-            every = {"q_all": empty((B, T, S, m.nq), f8), "v_all": empty((B, T, S, m.nv), f8), "status_all": empty((B, T, S), i4),
-                     "iters_all": empty((B, T, S), i4), "converged_all": empty((B, T, S), i4),
+            every = {"q_all": empty((B, T, W, m.nq), f8), "v_all": empty((B, T, W, m.nv), f8), "status_all": empty((B, T, W), i4),
+                     "iters_all": empty((B, T, W), i4), "converged_all": empty((B, T, W), i4),
                      "seeds_out": empty((B, T, S, m.nq), f8)}
         io = MkhTrajectoryLadderIO()
         io.seeds, io.weights, io.max_step_sq = ptr(seeds), ptr(weights), float(max_step_sq)
@@ -1580,15 +1695,27 @@ class NativeProblem:
             extra = (empty((B, T), i4), empty((B, T), i4), empty((B,), i4))
             rio = MkhLadderRefineIO()
             rio.tracked_out, rio.repaired, rio.refined = (ptr(x) for x in extra)
+        head = (ptr(q), ptr(frame_targets), ptr(posture_target), ptr(com_target), float(dt), float(damping), max_iters,
+                float(pos_threshold), float(ori_threshold), int(rng_seed) & (2 ** 64 - 1), int(target_index0), C.byref(io))
+        tail = (C.byref(rio) if rio is not None else None,)
+        plain = [out[n] for n in ("q_traj", "v_traj", "status", "iters", "converged", "node_index", "n_tracked", "n_breaks",
+                                  "path_length", "edge_break", "qvel")] + \
+            [every[n] for n in ("q_all", "v_all", "status_all", "iters_all", "converged_all", "seeds_out")] + list(extra)
+        if nodes is None:
+            with self._lock, _attached(self, seed_table):
+                _check(lib().mkh_solve_trajectory_ladder_refined(self.handle, B, T, S, *head, *tail, flags, stream))
+            return TrajectoryLadderOut(*plain)
+        K, r, unwind = nodes
+        sets = {"node_seed_index": empty((B, T, K), i4), "node_multiplicity": empty((B, T, K), i4),
+                "node_distance": empty((B, T, K), f8), "n_distinct": empty((B, T), i4), "n_converged": empty((B, T), i4),
+                "n_uncovered": empty((B, T), i4), "seed_index": empty((B, T), i4)}
+        nio = MkhLadderNodesIO()
+        for n, x in sets.items():
+            setattr(nio, n, ptr(x))
         with self._lock, _attached(self, seed_table):
-            _check(lib().mkh_solve_trajectory_ladder_refined(
-                self.handle, B, T, S, ptr(q), ptr(frame_targets), ptr(posture_target), ptr(com_target), float(dt), float(damping),
-                max_iters, float(pos_threshold), float(ori_threshold), int(rng_seed) & (2 ** 64 - 1), int(target_index0),
-                C.byref(io), C.byref(rio) if rio is not None else None, flags, stream))
-        return TrajectoryLadderOut(*[out[n] for n in ("q_traj", "v_traj", "status", "iters", "converged", "node_index", "n_tracked",
-                                                       "n_breaks", "path_length", "edge_break", "qvel")],
-                                   *[every[n] for n in ("q_all", "v_all", "status_all", "iters_all", "converged_all", "seeds_out")],
-                                   *extra)
+            _check(lib().mkh_solve_trajectory_ladder_nodes(self.handle, B, T, S, K, r, *head, C.byref(nio), *tail,
+                                                           flags | (FLAG_UNWIND_TURNS if unwind else 0), stream))
+        return TrajectoryLadderNodesOut(*plain, *[sets[n] for n in LADDER_NODES_IO_FIELDS])
 
     def ladder_refine(self, q, q_path, tracked=None, frame_targets=None, posture_target=None, com_target=None, dt: float = 1e-2,
                       damping: float = 1e-12, *, max_iters: int, pos_threshold: float, ori_threshold: float,

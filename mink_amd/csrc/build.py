@@ -325,6 +325,8 @@ def build(force: bool = False, verbose: bool = True) -> str:
     jobs.append((os.path.join(HERE, "trajectory_multistart.hip"), os.path.join(BUILD, "trajectory_multistart.o")))   # path scoring / selection / gather of mkh_solve_trajectory_multistart
     jobs.append((os.path.join(HERE, "ladder.hip"), os.path.join(BUILD, "ladder.o")))   # dynamic program / back-trace / gather of mkh_ladder_select and mkh_solve_trajectory_ladder
     jobs.append((os.path.join(HERE, "ladder_refine.hip"), os.path.join(BUILD, "ladder_refine.o")))   # step / guard kernels of mkh_ladder_refine
+    jobs.append((os.path.join(HERE, "unwind.hip"), os.path.join(BUILD, "unwind.o")))   # turn unwinding of mkh_unwind_turns / MKH_FLAG_UNWIND_TURNS
+    jobs.append((os.path.join(HERE, "ladder_nodes.hip"), os.path.join(BUILD, "ladder_nodes.o")))   # node flags of mkh_solve_trajectory_ladder_nodes
 
     def compile_one(job):
         src, obj = job

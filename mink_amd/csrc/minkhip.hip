@@ -82,6 +82,13 @@ static int32_t fail(int32_t code, const char* fmt, ...) {
   g_err = buf;
   return code;
 }
+// MKH_FLAG_UNWIND_TURNS in front of an entry point that has no distinct-set selection to unwind for (include/minkhip.h).
+static int32_t refuse_unwind(int32_t flags, const char* who) {
+  if (flags & MKH_FLAG_UNWIND_TURNS)
+    return fail(MKH_E_INVALID, "%s: MKH_FLAG_UNWIND_TURNS is honoured by mkh_solve_multistart_set and "
+                               "mkh_solve_trajectory_ladder_nodes only", who);
+  return MKH_OK;
+}
 #define HIP_OK(expr)                                                                             \
   do {                                                                                           \
     hipError_t e_ = (expr);                                                                      \
@@ -167,6 +174,12 @@ enum WsRole {
   // goal_index | seed_index | n_reached (B,), then seed_index_goal | reached | n_converged_goal (B, G)) and OUT_LEN (score |
   // distance_goal)
   WS_IN_GCOST, WS_IN_GVALID,
+  // turn unwinding: the per-qpos-address table (mode, range_lo, range_hi), built with the seeding table
+  WS_UNW,
+  // a ladder on deduplicated nodes: its (B, T, K, .) node rows live in a plain ladder's WS_L_Q … WS_L_TRK with K for S, the
+  // candidates of ONE chunk of rungs in multi-start's WS_C_Q … WS_C_CV.  A host caller's set outputs — N_I32: node_seed_index |
+  // node_multiplicity (B, T, K), then n_distinct | n_converged | n_uncovered | seed_index (B, T); N_DIST: node_distance (B, T, K)
+  WS_N_I32, WS_N_DIST,
   WS_COUNT
 };
 
@@ -913,6 +926,7 @@ static int32_t run(MkhProblem* p, int32_t B, const double* q, const double* fram
                    int32_t* iters_out = nullptr, int32_t* converged_out = nullptr) {
   if (!p) return fail(MKH_E_INVALID, "null problem");
   if (B < 1) return fail(MKH_E_INVALID, "B must be >= 1");
+  if (const int32_t rc = refuse_unwind(flags, "a solve")) return rc;       // (the outer-loop callers clear the bit in front of their loops)
   const DeviceProblem& P = p->dev;
   if (const int32_t rc = refuse_inputs(P, q, frame_targets, posture_target, com_target, nullptr, nullptr)) return rc;
   if (!(dt > 0.0)) return fail(MKH_E_INVALID, "dt must be > 0");
@@ -1215,12 +1229,16 @@ static int32_t ms_build_tables(MkhProblem* p) {
   const MkhModel* m = p->model;
   const int nq = m->nq, njnt = m->njnt;
   std::vector<int32_t> si(3 * (size_t)nq, 0), jn(3 * (size_t)njnt, 0);
-  std::vector<double> sf(2 * (size_t)nq, 0.0);
+  std::vector<double> sf(2 * (size_t)nq, 0.0), uw(3 * (size_t)nq, 0.0);     // (uw: kUnwCopy everywhere but at eligible hinges)
   for (int j = 0; j < njnt; ++j) {
     const int jt = m->jnt_type[j], qa = m->jnt_qposadr[j];
     jn[3 * j] = jt; jn[3 * j + 1] = qa; jn[3 * j + 2] = m->jnt_dofadr[j];
     const bool limited = m->jnt_limited[j] != 0;
     const double lo = m->jnt_range[2 * j], hi = m->jnt_range[2 * j + 1];
+    if (jt == 3) {                                     // the unwinding's eligibility: "THE RULE OF THE UNWINDING"
+      if (!limited) uw[3 * qa] = mkh::kUnwFree;
+      else if (hi - lo >= 6.283185307179586) { uw[3 * qa] = mkh::kUnwRange; uw[3 * qa + 1] = lo; uw[3 * qa + 2] = hi; }
+    }
     if (jt == 2 || jt == 3) {                          // slide / hinge
       si[3 * qa + 2] = qa;
       if (limited) { si[3 * qa] = 1; sf[2 * qa] = lo; sf[2 * qa + 1] = hi - lo; }
@@ -1238,6 +1256,8 @@ static int32_t ms_build_tables(MkhProblem* p) {
   HIP_OK(hipMemcpy(p->ws[WS_SEED_I].p, si.data(), si.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   HIP_OK(hipMemcpy(p->ws[WS_SEED_F].p, sf.data(), sf.size() * sizeof(double), hipMemcpyHostToDevice));
   HIP_OK(hipMemcpy(p->ws[WS_JNT].p, jn.data(), jn.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_OK(p->ws[WS_UNW].need(uw.size() * sizeof(double)));
+  HIP_OK(hipMemcpy(p->ws[WS_UNW].p, uw.data(), uw.size() * sizeof(double), hipMemcpyHostToDevice));
   p->ws_tables = true;
   return MKH_OK;
 }
@@ -1454,6 +1474,7 @@ int32_t mkh_seed_table_query(const MkhSeedTable* t, int32_t B, const double* fra
   if (K < 1) return fail(MKH_E_INVALID, "K = %d must be >= 1", K);
   if (K > 255) return fail(MKH_E_LIMIT, "K = %d: a query returns at most 255 entries per target", K);
   if (K > t->N) return fail(MKH_E_INVALID, "K = %d exceeds the seed table's %d entries", K, t->N);
+  if (const int32_t rc = refuse_unwind(flags, "mkh_seed_table_query")) return rc;
   if (!frame_targets) return fail(MKH_E_INVALID, "frame_targets is null");
   if (!index_out && !dist_out && !seeds_out) return fail(MKH_E_INVALID, "index_out, dist_out and seeds_out are all null");
   HIP_OK(hipSetDevice(t->device));
@@ -1517,6 +1538,9 @@ static int32_t multistart_core(MkhProblem* p, int32_t B, const double* q, const 
   if (max_iters < 1) return fail(MKH_E_INVALID, "max_iters must be >= 1");
   if (target_index0 < 0) return fail(MKH_E_INVALID, "target_index0 must be >= 0");
   if (!(pos_threshold >= 0.0) || !(ori_threshold >= 0.0)) return fail(MKH_E_INVALID, "thresholds must be >= 0");
+  const bool unwind = (flags & MKH_FLAG_UNWIND_TURNS) != 0;        // (the set's alone: its results are unwound in front of the selection)
+  if (!set || rungs_v)
+    if (const int32_t rc = refuse_unwind(flags, who)) return rc;
   if (!io || (!rungs_v && !set && (!io->q_best || !io->v_best || !io->iters || !io->status || !io->converged || !io->seed_index || !io->n_converged)))
     return fail(MKH_E_INVALID, "io and its per-target outputs (q_best, v_best, iters, status, converged, seed_index, n_converged) are required");
   if (set && n_seeds > mkh::kSsMaxCandidates)
@@ -1583,12 +1607,14 @@ static int32_t multistart_core(MkhProblem* p, int32_t B, const double* q, const 
   if (ct_w && cbat) d_ct = fanout(WS_C_CT, d_ct, ct_w);
   if (!st.ok()) return st.finish();
   // ---- the loop: mkh_solve_until's own path and dispatch on the B·S instances
-  const int32_t loop_flags = (flags & ~MKH_FLAG_WARM_START) | MKH_FLAG_DEVICE_PTRS;
+  const int32_t loop_flags = (flags & ~(MKH_FLAG_WARM_START | MKH_FLAG_UNWIND_TURNS)) | MKH_FLAG_DEVICE_PTRS;
   if (const int32_t rc = run(p, (int32_t)N, d_seeds, c_ft, d_pt, d_ct, dt, damping, c_v, d_status, nullptr, loop_flags, hip_stream,
                              max_iters, d_q_all, nullptr, pos_threshold, ori_threshold, d_iters, d_conv))
     return st.finish(rc);
   if (rungs_v) return st.finish();
   // ---- selection
+  if (unwind)                           // in place, where q_all is read from: the loops' flags are carried over
+    ST_LAUNCH(st, launch_unwind_turns(stream, ws[WS_UNW].f64(), N, S, (int)nq, d_q_all, d_ref ? d_ref : d_q, d_q_all));
   if (set) {
     set_select(st, B, S, *set, d_q_all, c_v, d_status, d_iters, d_conv, d_ref ? d_ref : d_q, d_w);
   } else {
@@ -1709,6 +1735,7 @@ int32_t mkh_select_distinct(MkhProblem* p, int32_t B, int32_t S, const double* q
                 mkh::kSsMaxCandidates);
   if ((long long)B * S > 0x7fffffffLL) return fail(MKH_E_LIMIT, "%s: B * S = %lld rows", who, (long long)B * S);
   if (const int32_t rc = set_refuse(n_solutions, min_distance, who)) return rc;
+  if (const int32_t rc = refuse_unwind(flags, who)) return rc;       // (the caller's own candidates: mkh_unwind_turns in front)
   if (!q_candidates || !q_ref) return fail(MKH_E_INVALID, "%s: q_candidates and q_ref are required", who);
   if (!io || !io->q_set || !io->seed_index || !io->multiplicity || !io->distance || !io->n_distinct || !io->n_uncovered)
     return fail(MKH_E_INVALID, "%s: io and its outputs q_set, seed_index, multiplicity, distance, n_distinct, n_uncovered are required", who);
@@ -1730,6 +1757,29 @@ int32_t mkh_select_distinct(MkhProblem* p, int32_t B, int32_t S, const double* q
   MkhSolutionSetIO sio = *io;      // (the selection alone has no loop rows: n_converged is the count of `valid`, when asked for)
   const SetSpec set{n_solutions, min_distance * min_distance, &sio};
   set_select(st, B, S, set, d_cand, nullptr, nullptr, nullptr, d_valid, d_ref, d_w);
+  return st.finish();
+}
+
+// ---- turn unwinding (include/minkhip.h "THE RULE OF THE UNWINDING"; kernel: unwind.hip)
+int32_t mkh_unwind_turns(MkhProblem* p, int32_t n_rows, int32_t rows_per_ref, const double* q_rows, const double* q_ref,
+                         double* q_out, int32_t flags, void* hip_stream) {
+  const char* const who = "mkh_unwind_turns";
+  if (!p) return fail(MKH_E_INVALID, "null problem");
+  if (n_rows < 1) return fail(MKH_E_INVALID, "%s: n_rows = %d must be >= 1", who, n_rows);
+  if (rows_per_ref < 1) return fail(MKH_E_INVALID, "%s: rows_per_ref = %d must be >= 1", who, rows_per_ref);
+  if (flags & ~MKH_FLAG_DEVICE_PTRS) return fail(MKH_E_INVALID, "%s: flags = %d: only MKH_FLAG_DEVICE_PTRS is accepted", who, flags);
+  if (!q_rows || !q_ref || !q_out) return fail(MKH_E_INVALID, "%s: q_rows, q_ref and q_out are required", who);
+  const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
+  HIP_OK(hipSetDevice(p->model->device));
+  if (const int32_t rc = ms_build_tables(p)) return rc;
+  Stager st{p, (hipStream_t)hip_stream, devp, "unwind_turns"};
+  const size_t Nz = n_rows, nq = p->dev.nq, n_ref = (Nz + rows_per_ref - 1) / (size_t)rows_per_ref;
+  const double* const d_rows = st.up(WS_C_Q, q_rows, Nz * nq);
+  const double* const d_ref = st.up(WS_IN_REF, q_ref, n_ref * nq);
+  double* const d_out = devp ? q_out : (double*)d_rows;      // (a host caller's rows are unwound in place in their staged copy)
+  if (!st.ok()) return st.finish();
+  ST_LAUNCH(st, launch_unwind_turns(st.stream, p->ws[WS_UNW].f64(), n_rows, rows_per_ref, (int)nq, d_rows, d_ref, d_out));
+  if (!devp) st.down(q_out, d_out, Nz * nq * sizeof(double));
   return st.finish();
 }
 
@@ -1804,6 +1854,7 @@ static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double
   if (cs && cs->S < 1) return fail(MKH_E_INVALID, "n_seeds must be >= 1");
   if (cs && cs->target_index0 < 0) return fail(MKH_E_INVALID, "target_index0 must be >= 0");
   if (!(dt > 0.0)) return fail(MKH_E_INVALID, "dt must be > 0");
+  if (const int32_t rc = refuse_unwind(flags, who)) return rc;
   const bool until = pos_threshold >= 0.0 && ori_threshold >= 0.0;
   if (!until && !(pos_threshold < 0.0 && ori_threshold < 0.0))
     return fail(MKH_E_INVALID, "thresholds must both be >= 0 (threshold mode) or both be < 0 (fixed count)");
@@ -2130,6 +2181,7 @@ int32_t mkh_ladder_select(MkhProblem* p, int32_t B, int32_t T, int32_t S, const 
   const char* const who = "mkh_ladder_select";
   if (!p) return fail(MKH_E_INVALID, "null problem");
   if (const int32_t rc = ladder_refuse(p, B, T, S, max_step_sq, who)) return rc;
+  if (const int32_t rc = refuse_unwind(flags, who)) return rc;
   if (!q || !q_nodes || !tracked) return fail(MKH_E_INVALID, "%s: q, q_nodes and tracked are required", who);
   if (!io || !io->node_index || !io->n_tracked || !io->n_breaks || !io->path_length || !io->edge_break)
     return fail(MKH_E_INVALID, "%s: io and its outputs node_index, n_tracked, n_breaks, path_length, edge_break are required", who);
@@ -2251,6 +2303,7 @@ int32_t mkh_ladder_refine(MkhProblem* p, int32_t B, int32_t T, const double* q, 
   if (!p) return fail(MKH_E_INVALID, "null problem");
   if (!io) return fail(MKH_E_INVALID, "%s: io is required", who);
   if (const int32_t rc = refine_refuse(p, B, T, io->max_step_sq, max_iters, dt, pos_threshold, ori_threshold, who)) return rc;
+  if (const int32_t rc = refuse_unwind(flags, who)) return rc;
   if (!q_path || !tracked_path) return fail(MKH_E_INVALID, "%s: q_path and tracked_path are required", who);
   if (!io->q_path_out || !io->tracked_out || !io->repaired || !io->refined || !io->edge_break || !io->n_tracked || !io->n_breaks ||
       !io->path_length)
@@ -2333,6 +2386,7 @@ int32_t mkh_solve_trajectory_ladder_refined(MkhProblem* p, int32_t B, int32_t T,
   if (!io) return fail(MKH_E_INVALID, "%s: io is required", who);
   const int S = n_seeds;
   if (const int32_t rc = ladder_refuse(p, B, T, S, io->max_step_sq, who)) return rc;
+  if (const int32_t rc = refuse_unwind(flags, who)) return rc;
   if (max_iters < 1) return fail(MKH_E_INVALID, "max_iters must be >= 1");
   if (target_index0 < 0) return fail(MKH_E_INVALID, "target_index0 must be >= 0");
   if (!(dt > 0.0)) return fail(MKH_E_INVALID, "dt must be > 0");
@@ -2460,6 +2514,186 @@ int32_t mkh_solve_trajectory_ladder_refined(MkhProblem* p, int32_t B, int32_t T,
   return st.finish();
 }
 
+// ---- the ladder on deduplicated nodes (include/minkhip.h mkh_solve_trajectory_ladder_nodes; kernels: unwind.hip,
+// solution_set.hip, ladder_nodes.hip, ladder.hip).  mkh_solve_trajectory_ladder_refined with the distinct-set selection between
+// the loops of a chunk and the node arrays: the loops write multi-start's candidate buffers of ONE chunk, the selection writes
+// the chunk's K slots per rung into the (B·T, K, .) node arrays, and everything behind the rung loop is the plain ladder's with
+// K for S.
+int32_t mkh_solve_trajectory_ladder_nodes(MkhProblem* p, int32_t B, int32_t T, int32_t n_seeds, int32_t n_nodes, double min_distance,
+                                          const double* q, const double* frame_targets, const double* posture_target,
+                                          const double* com_target, double dt, double damping, int32_t max_iters, double pos_threshold,
+                                          double ori_threshold, uint64_t rng_seed, int64_t target_index0,
+                                          const MkhTrajectoryLadderIO* io, const MkhLadderNodesIO* nodes, const MkhLadderRefineIO* refine,
+                                          int32_t flags, void* hip_stream) {
+  const char* const who = "mkh_solve_trajectory_ladder_nodes";
+  if (!p) return fail(MKH_E_INVALID, "null problem");
+  if (!io || !nodes) return fail(MKH_E_INVALID, "%s: io and nodes are required", who);
+  const int S = n_seeds, K = n_nodes;
+  if (S < 1) return fail(MKH_E_INVALID, "%s: n_seeds = %d must be >= 1", who, S);
+  if (S > mkh::kSsMaxCandidates)
+    return fail(MKH_E_LIMIT, "%s: n_seeds = %d candidates per rung, at most %d (their selection state lives in LDS)", who, S,
+                mkh::kSsMaxCandidates);
+  if (const int32_t rc = set_refuse(K, min_distance, who)) return rc;
+  if (const int32_t rc = ladder_refuse(p, B, T, K, io->max_step_sq, who)) return rc;       // (the search runs on K nodes per rung)
+  if ((long long)B * T * K > 0x7fffffffLL) return fail(MKH_E_LIMIT, "%s: B * T * n_nodes = %lld nodes", who, (long long)B * T * K);
+  if (max_iters < 1) return fail(MKH_E_INVALID, "max_iters must be >= 1");
+  if (target_index0 < 0) return fail(MKH_E_INVALID, "target_index0 must be >= 0");
+  if (!(dt > 0.0)) return fail(MKH_E_INVALID, "dt must be > 0");
+  if (!(pos_threshold >= 0.0) || !(ori_threshold >= 0.0))
+    return fail(MKH_E_INVALID, "%s: thresholds must be >= 0 (a fixed count leaves no tracked flag to search on)", who);
+  if (!io->q_traj || !io->v_traj || !io->status || !io->iters || !io->converged || !io->node_index || !io->n_tracked ||
+      !io->n_breaks || !io->path_length || !io->edge_break)
+    return fail(MKH_E_INVALID, "%s: io's outputs q_traj, v_traj, status, iters, converged, node_index, n_tracked, n_breaks, path_length, "
+                               "edge_break are required", who);
+  if (!nodes->node_seed_index || !nodes->node_multiplicity || !nodes->node_distance || !nodes->n_distinct || !nodes->n_converged ||
+      !nodes->n_uncovered || !nodes->seed_index)
+    return fail(MKH_E_INVALID, "%s: nodes' outputs node_seed_index, node_multiplicity, node_distance, n_distinct, n_converged, "
+                               "n_uncovered, seed_index are required", who);
+  if (io->qvel && !(io->waypoint_dt > 0.0)) return fail(MKH_E_INVALID, "qvel needs waypoint_dt > 0");
+  if (refine) {
+    if (const int32_t rc = refine_refuse(p, B, T, io->max_step_sq, max_iters, dt, pos_threshold, ori_threshold, who)) return rc;
+    if (!refine->tracked_out || !refine->repaired || !refine->refined)
+      return fail(MKH_E_INVALID, "%s: refine's outputs tracked_out, repaired, refined are required", who);
+  }
+  const DeviceProblem& P = p->dev;
+  if (const int32_t rc = refuse_inputs(P, q, frame_targets, posture_target, com_target, who, "ladder")) return rc;
+  if (S > p->max_batch) return fail(MKH_E_INVALID, "%s: n_seeds = %d exceeds max_batch=%d of this problem (a rung is one chunk)", who, S, p->max_batch);
+  const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
+  if (!devp)
+    if (const int32_t rc = ladder_weights_refuse(io->weights, P.nv, who)) return rc;
+  const MkhSeedTable* const tab = (!io->seeds && S > 1) ? p->seed_table : nullptr;
+  if (tab)
+    if (const int32_t rc = st_refuse(p, tab, S - 1, who)) return rc;
+  HIP_OK(hipSetDevice(p->model->device));
+  if (const int32_t rc = ms_build_tables(p)) return rc;
+  const bool unwind = (flags & MKH_FLAG_UNWIND_TURNS) != 0;
+  flags &= ~MKH_FLAG_UNWIND_TURNS;                           // (the loops and the pass below know nothing of it)
+  const bool pbat = (flags & MKH_FLAG_POSTURE_BATCHED) != 0, cbat = (flags & MKH_FLAG_COM_BATCHED) != 0;
+  Stager st{p, (hipStream_t)hip_stream, devp, "trajectory_ladder_nodes"};
+  hipStream_t stream = st.stream;
+  const size_t Bz = B, R = Bz * T, N = R * S, M = R * K, nq = P.nq, nv = P.nv, f8 = sizeof(double), i4 = sizeof(int32_t);
+  const size_t ft_w = (size_t)P.n_frame * 7, pt_w = (size_t)P.n_posture * nq, ct_w = (size_t)P.n_com * 3;
+  const size_t per = (size_t)p->max_batch / S, chunk = (per < R ? per : R) * S;      // rungs, and loops, of one chunk
+  // ---- inputs on the device; q once per (instance, waypoint): the flattened targets' "current posture" and the set's q_ref
+  const double* const d_q = st.up(WS_IN_Q, q, Bz * nq);
+  const double* const d_ft = st.up(WS_IN_FT, frame_targets, R * ft_w);
+  const double* const d_pt = pt_w ? st.up(WS_IN_PT, posture_target, pt_w * (pbat ? R : 1)) : posture_target;
+  const double* const d_ct = ct_w ? st.up(WS_IN_CT, com_target, ct_w * (cbat ? R : 1)) : com_target;
+  const double* const d_w = st.up(WS_IN_W, io->weights, nv);
+  const double* const d_user = st.up(WS_IN_SEEDS, io->seeds, N * nq);       // (the caller's: the one input of this size)
+  double* const d_q0 = st.f64(WS_L_Q0, R * nq);
+  ST_LAUNCH(st, launch_ms_fanout(stream, d_q, d_q0, B, T, (int)nq));
+  // ---- the candidates of one chunk: the loops' velocities (the other rows are multi-start's own buffers of its launch)
+  double* const c_v = st.f64(WS_C_V, chunk * nv);
+  // ---- the nodes, (B·T, K, .): the caller's *_all arrays where they are device buffers
+  double* const l_q = (double*)st.given_or(WS_L_Q, io->q_all, M * nq * f8);
+  double* const l_v = (double*)st.given_or(WS_L_V, io->v_all, M * nv * f8);
+  int32_t* const l_st = (int32_t*)st.given_or(WS_L_ST, io->status_all, M * i4);
+  int32_t* const l_it = (int32_t*)st.given_or(WS_L_IT, io->iters_all, M * i4);
+  int32_t* const l_cv = (int32_t*)st.given_or(WS_L_CV, io->converged_all, M * i4);
+  int32_t* const l_trk = st.i32(WS_L_TRK, M);
+  double* const l_starts = io->seeds_out ? (double*)st.given_or(WS_L_STARTS, io->seeds_out, N * nq * f8) : nullptr;
+  // ---- outputs
+  double *o_q = io->q_traj, *o_v = io->v_traj, *o_qvel = io->qvel, *o_len = io->path_length;
+  int32_t *o_st = io->status, *o_it = io->iters, *o_cv = io->converged;
+  int32_t *o_node = io->node_index, *o_eb = io->edge_break, *o_nt = io->n_tracked, *o_nb = io->n_breaks;
+  int32_t *n_si = nodes->node_seed_index, *n_mu = nodes->node_multiplicity, *n_nd = nodes->n_distinct, *n_nc = nodes->n_converged,
+          *n_nu = nodes->n_uncovered, *n_pick = nodes->seed_index;
+  double* n_dist = nodes->node_distance;
+  if (!devp) {
+    o_q = st.f64(WS_OUT_Q, R * nq); o_v = st.f64(WS_OUT_V, R * nv);
+    o_qvel = io->qvel ? st.f64(WS_OUT_QVEL, R * nv) : nullptr;
+    o_st = st.i32(WS_OUT_I32, 3 * R); o_it = o_st + R; o_cv = o_st + 2 * R;
+    o_node = st.i32(WS_OUT_PICK, 2 * R + 2 * Bz); o_eb = o_node + R; o_nt = o_node + 2 * R; o_nb = o_nt + Bz;
+    o_len = st.f64(WS_OUT_LEN, Bz);
+    n_si = st.i32(WS_N_I32, 2 * M + 4 * R); n_mu = n_si + M; n_nd = n_si + 2 * M; n_nc = n_nd + R; n_nu = n_nd + 2 * R; n_pick = n_nd + 3 * R;
+    n_dist = st.f64(WS_N_DIST, M);
+  }
+  int32_t *o_trk = nullptr, *o_rep = nullptr, *o_ref = nullptr;
+  if (refine) {
+    o_trk = refine->tracked_out; o_rep = refine->repaired; o_ref = refine->refined;
+    if (!devp) { o_trk = st.i32(WS_OUT_REF, 2 * R + Bz); o_rep = o_trk + R; o_ref = o_trk + 2 * R; }
+  }
+  if (!st.ok()) return st.finish();
+  // ---- the rungs: multi-start on the (B·T) flattened targets, whole rungs per chunk of at most max_batch loops; behind every
+  // chunk's loops its unwinding, its selection into the chunk's slots of the node arrays, and the slots' flags
+  const int32_t ms_flags = flags | MKH_FLAG_DEVICE_PTRS;
+  const double r2 = min_distance * min_distance;
+  const int njnt = p->model->njnt;
+  for (size_t r0 = 0; r0 < R; r0 += per) {
+    const size_t n = R - r0 < per ? R - r0 : per, i0 = r0 * S, m0 = r0 * K;
+    MkhMultistartIO mio;
+    memset(&mio, 0, sizeof mio);
+    mio.seeds = d_user ? d_user + i0 * nq : nullptr;
+    mio.seeds_out = l_starts ? l_starts + i0 * nq : nullptr;
+    if (const int32_t rc = multistart_core(p, (int32_t)n, d_q0 + r0 * nq, d_ft + r0 * ft_w, (pt_w && pbat) ? d_pt + r0 * pt_w : d_pt,
+                                           (ct_w && cbat) ? d_ct + r0 * ct_w : d_ct, dt, damping, max_iters, pos_threshold,
+                                           ori_threshold, S, rng_seed, target_index0 * T + (int64_t)r0, &mio, ms_flags, hip_stream,
+                                           c_v))
+      return st.finish(rc);
+    // (what that launch wrote: with no *_all array given it uses the candidate slots, sized for its n·S <= chunk rows)
+    double* const c_q = p->ws[WS_C_Q].f64();
+    const int32_t *c_st = p->ws[WS_C_ST].i32(), *c_it = p->ws[WS_C_IT].i32(), *c_cv = p->ws[WS_C_CV].i32();
+    const double* const ref = d_q0 + r0 * nq;
+    if (unwind)
+      ST_LAUNCH(st, launch_unwind_turns(stream, p->ws[WS_UNW].f64(), (long long)(n * S), S, (int)nq, c_q, ref, c_q));
+    const mkh::SsOut so{l_q + m0 * nq, l_v + m0 * nv, l_it + m0, l_st + m0, n_si + m0, n_mu + m0, n_dist + m0,
+                        n_nd + r0, n_nc + r0, n_nu + r0};
+    ST_LAUNCH(st, launch_ss_select(stream, (int)n, S, K, (int)nq, (int)nv, njnt, p->ws[WS_JNT].i32(), c_q, c_v, c_st, c_it, c_cv, ref,
+                                   d_w, r2, so));
+    ST_LAUNCH(st, launch_ladder_nodes_flags(stream, (long long)n, S, K, c_cv, n_si + m0, l_trk + m0, l_cv + m0));
+  }
+  // ---- the search on the (B, T, K) nodes, and the chosen nodes' rows
+  ladder_search(st, B, T, K, d_q, l_q, l_trk, d_w, io->max_step_sq, o_node, o_nt, o_nb, o_len, o_eb);
+  ST_LAUNCH(st, launch_ladder_gather(stream, l_q, o_q, o_node, (long long)R, K, (int)nq));
+  ST_LAUNCH(st, launch_ladder_gather(stream, l_v, o_v, o_node, (long long)R, K, (int)nv));
+  ST_LAUNCH(st, launch_ladder_gather_i32(stream, l_st, o_st, o_node, (long long)R, K));
+  ST_LAUNCH(st, launch_ladder_gather_i32(stream, l_it, o_it, o_node, (long long)R, K));
+  ST_LAUNCH(st, launch_ladder_gather_i32(stream, l_cv, o_cv, o_node, (long long)R, K));
+  ST_LAUNCH(st, launch_ladder_gather_i32(stream, n_si, n_pick, o_node, (long long)R, K));
+  if (refine) {
+    ST_LAUNCH(st, launch_ladder_gather_i32(stream, l_trk, o_trk, o_node, (long long)R, K));
+    const mkh::LrOut o{o_q, o_v, o_len, o_trk, o_rep, o_ref, o_eb, o_nt, o_nb, o_st, o_it, o_cv};
+    if (const int32_t rc = refine_pass(st, B, T, d_q, o_q, o_trk, d_ft, d_pt, d_ct, dt, damping, max_iters, pos_threshold,
+                                       ori_threshold, d_w, io->max_step_sq, o, flags, hip_stream))
+      return st.finish(rc);
+  }
+  if (o_qvel)
+    ST_LAUNCH(st, launch_tj_qvel(stream, p->ws[WS_JNT].i32(), njnt, B, T, (int)nq, d_q, o_q, (long long)(T * nq), (long long)nq,
+                                 io->waypoint_dt, o_qvel, (long long)(T * nv), (long long)nv, 0));
+  if (devp) return st.finish();
+  st.down(io->q_traj, o_q, R * nq * f8);
+  st.down(io->v_traj, o_v, R * nv * f8);
+  st.down(io->status, o_st, R * i4);
+  st.down(io->iters, o_it, R * i4);
+  st.down(io->converged, o_cv, R * i4);
+  st.down(io->node_index, o_node, R * i4);
+  st.down(io->edge_break, o_eb, R * i4);
+  st.down(io->n_tracked, o_nt, Bz * i4);
+  st.down(io->n_breaks, o_nb, Bz * i4);
+  st.down(io->path_length, o_len, Bz * f8);
+  st.down(io->qvel, o_qvel, R * nv * f8);
+  st.down(io->q_all, l_q, M * nq * f8);
+  st.down(io->v_all, l_v, M * nv * f8);
+  st.down(io->status_all, l_st, M * i4);
+  st.down(io->iters_all, l_it, M * i4);
+  st.down(io->converged_all, l_cv, M * i4);
+  st.down(io->seeds_out, l_starts, N * nq * f8);
+  st.down(nodes->node_seed_index, n_si, M * i4);
+  st.down(nodes->node_multiplicity, n_mu, M * i4);
+  st.down(nodes->node_distance, n_dist, M * f8);
+  st.down(nodes->n_distinct, n_nd, R * i4);
+  st.down(nodes->n_converged, n_nc, R * i4);
+  st.down(nodes->n_uncovered, n_nu, R * i4);
+  st.down(nodes->seed_index, n_pick, R * i4);
+  if (refine) {
+    st.down(refine->tracked_out, o_trk, R * i4);
+    st.down(refine->repaired, o_rep, R * i4);
+    st.down(refine->refined, o_ref, Bz * i4);
+  }
+  return st.finish();
+}
+
 // ---- goal sets (include/minkhip.h "THE RULE OF THE GOAL SET"; kernel: goalset.hip)
 // What both entry points refuse about the shape, the outputs and a host caller's costs.
 static int32_t goalset_refuse(int32_t B, int32_t G, int32_t S, const MkhGoalSetIO* io, bool loops, bool devp, const char* who) {
@@ -2548,6 +2782,7 @@ int32_t mkh_solve_goalset(MkhProblem* p, int32_t B, int32_t n_goals, const doubl
   const int G = n_goals, S = n_seeds;
   const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
   if (const int32_t rc = goalset_refuse(B, G, S, io, true, devp, who)) return rc;
+  if (const int32_t rc = refuse_unwind(flags, who)) return rc;
   if (max_iters < 1) return fail(MKH_E_INVALID, "max_iters must be >= 1");
   if (target_index0 < 0) return fail(MKH_E_INVALID, "target_index0 must be >= 0");
   if (!(pos_threshold >= 0.0) || !(ori_threshold >= 0.0)) return fail(MKH_E_INVALID, "thresholds must be >= 0");
@@ -2616,6 +2851,7 @@ int32_t mkh_select_goalset(MkhProblem* p, int32_t B, int32_t G, int32_t S, const
   if (!p) return fail(MKH_E_INVALID, "null problem");
   const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
   if (const int32_t rc = goalset_refuse(B, G, S, io, false, devp, who)) return rc;
+  if (const int32_t rc = refuse_unwind(flags, who)) return rc;
   if (!q_candidates || !q_ref) return fail(MKH_E_INVALID, "%s: q_candidates and q_ref are required", who);
   HIP_OK(hipSetDevice(p->model->device));
   if (const int32_t rc = ms_build_tables(p)) return rc;
@@ -2639,6 +2875,7 @@ int32_t mkh_integrate(MkhModel* m, int32_t B, const double* q, const double* v, 
                       int32_t flags, void* hip_stream) {
   if (!m || !q || !v || !q_out) return fail(MKH_E_INVALID, "null argument");
   if (B < 1) return fail(MKH_E_INVALID, "B must be >= 1");
+  if (const int32_t rc = refuse_unwind(flags, "mkh_integrate")) return rc;
   HIP_OK(hipSetDevice(m->device));
   hipStream_t stream = (hipStream_t)hip_stream;
   DeviceProblem P;
@@ -2761,6 +2998,7 @@ extern "C" int32_t mkh_lie_eval(int32_t device, int32_t op, int32_t n, const dou
                    n_out[] = {6, 36, 36, 7, 7, 6, 3, 9, 3};
   if (op < 0 || op > MKH_LIE_SE3_APPLY) return fail(MKH_E_INVALID, "mkh_lie_eval: unknown op %d", op);
   if (n < 1 || !a || !out || (in_b[op] && !b)) return fail(MKH_E_INVALID, "mkh_lie_eval: null argument or n < 1");
+  if (const int32_t rc = refuse_unwind(flags, "mkh_lie_eval")) return rc;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MKH_E_NOGPU, "no HIP device visible");
   if (device < 0 || device >= ndev) return fail(MKH_E_INVALID, "device %d out of range (%d visible)", device, ndev);

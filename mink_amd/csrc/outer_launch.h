@@ -1,6 +1,6 @@
 // Launchers of the small kernels around the loop launches of the outer-loop entry points (mkh_solve_multistart,
 // mkh_solve_multistart_set, mkh_solve_goalset, mkh_solve_trajectory, mkh_solve_keyframes, mkh_solve_trajectory_multistart, the ladder calls) and of
-// the seed tables in front of them: declared once, for the nine files that define them and for minkhip.hip, which calls them — a signature that
+// the seed tables in front of them: declared once, for the eleven files that define them and for minkhip.hip, which calls them — a signature that
 // drifts fails to compile in the file that drifted.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -43,6 +43,15 @@ struct SsOut {
 hipError_t launch_ss_select(hipStream_t stream, int B, int S, int K, int nq, int nv, int njnt, const int32_t* jnt,
                             const double* q_all, const double* v_all, const int32_t* status_all, const int32_t* iters_all,
                             const int32_t* converged_all, const double* q_ref, const double* weights, double r2, const SsOut& o);
+// turn unwinding (unwind.hip): n_rows rows of nq entries moved to the full turn nearest q_ref[row / rows_per_ref] at every
+// address whose table entry says so — table (nq, 3): mode, range_lo, range_hi.  q_out may be q_rows.
+constexpr double kUnwCopy = 0.0, kUnwFree = 1.0, kUnwRange = 2.0;
+hipError_t launch_unwind_turns(hipStream_t stream, const double* table, long long n_rows, long long rows_per_ref, int nq,
+                               const double* q_rows, const double* q_ref, double* q_out);
+// the ladder on deduplicated nodes (ladder_nodes.hip): tracked and converged of the (rungs, K) slots a selection filled, from the
+// slots' seed_index (>= 0: filled) and the (rungs, S) converged flags of the candidates
+hipError_t launch_ladder_nodes_flags(hipStream_t stream, long long rungs, int S, int K, const int32_t* converged_all,
+                                     const int32_t* seed_index, int32_t* tracked, int32_t* converged);
 // goal sets (goalset.hip): per goal the closest eligible of its S candidates, per target the reached goal with the smallest
 // goal_cost + distance, over (B, G, S, .) rows — (B, G, .) and (B, .) outputs.  converged_all (absent: every candidate is
 // eligible), status_all / iters_all / v_all with their outputs, goal_cost (zeros) and goal_valid (every goal) are optional.

@@ -735,7 +735,7 @@ def solve_ik_solutions(configuration: Configuration, tasks: Sequence, dt: float,
                        pos_threshold: float, ori_threshold: float, min_distance: float = 0.1, solver: str = "mi355x",
                        damping: float = 1e-12, limits: Optional[Sequence] = None, rng_seed: int = 0, seeds=None, reference=None,
                        weights=None, return_all: bool = False, max_instances: int = 1 << 20,
-                       seed_table: Optional["SeedTable"] = None) -> SolutionSet:
+                       seed_table: Optional["SeedTable"] = None, unwind_turns: bool = False) -> SolutionSet:
     """The distinct IK solutions of every target that multi-start finds: solve_ik_multistart's seeds and loops — `n_seeds`
     starts per target, the same generator, `seeds`, `seed_table`, chunks and shards — and, instead of its one result, up to
     `n_solutions` converged results per target no two of which lie within `min_distance` of each other, picked and
@@ -746,7 +746,9 @@ def solve_ik_solutions(configuration: Configuration, tasks: Sequence, dt: float,
     (default: q): slot 0 is what solve_ik_multistart returns, slot j the closest converged result that none of the slots
     before it covers; `multiplicity` counts the seeds a slot stands for.  Slots beyond `n_distinct` are empty — valid = False,
     seed 0's result in q.  `n_uncovered` > 0 says that more distinct solutions were found than `n_solutions` holds.  Two
-    solutions a full turn of an unlimited hinge apart count as different.
+    solutions a full turn of an unlimited hinge apart count as different — unless `unwind_turns` is set: every loop result is
+    then moved to the turn nearest the reference first (the function unwind_turns; `q_all` returns the moved rows), so the
+    slots go to IK branches and not to turns of one branch.  Slot 0 is then the closest MOVED result.
 
     The configuration is not changed: a set does not update it.  Failures are reported for slot 0 only, as
     solve_ik_multistart reports them for its choice."""
@@ -768,7 +770,8 @@ def solve_ik_solutions(configuration: Configuration, tasks: Sequence, dt: float,
     ft, pt, ct = _gather_targets(configuration, layout)
     q = configuration.q_batch
     kw = dict(n_seeds=S, n_solutions=K, min_distance=r, max_iters=max_iters, pos_threshold=float(pos_threshold),
-              ori_threshold=float(ori_threshold), rng_seed=int(rng_seed), return_all=bool(return_all))
+              ori_threshold=float(ori_threshold), rng_seed=int(rng_seed), return_all=bool(return_all),
+              unwind_turns=bool(unwind_turns))
 
     def job(handle, lo, hi):
         return handle.solve_multistart_set(q[lo:hi], _rows(ft, 2, lo, hi), _rows(pt, 2, lo, hi), _rows(ct, 2, lo, hi), dt, damping,
@@ -786,13 +789,39 @@ def solve_ik_solutions(configuration: Configuration, tasks: Sequence, dt: float,
                          for k, x in enumerate((res.q_all, res.converged_all, res.iters_all, res.status_all, res.seeds))])
 
 
+def unwind_turns(configuration: Configuration, q_rows, reference=None) -> np.ndarray:
+    """Move configurations to the full turn nearest a reference posture: q_rows (S, nq) or (B, S, nq); `reference` (nq,) or
+    (B, nq) (default: the configuration's q).  Every hinge that is unlimited, or whose range spans at least 2π, is
+    shifted by the whole number of turns that brings it nearest its reference value without leaving its range; every other
+    entry — slides, short-range hinges, the quaternions of ball and free joints — is copied bit for bit.  The pose of the robot
+    does not change (a hinge at x + 2πk is the hinge at x).  The rule in full, which the device and numpy restate bit for bit:
+    include/minkhip.h "THE RULE OF THE UNWINDING".  Returns (B, S, nq) — (S, nq) for an unbatched configuration; the
+    configuration is not changed."""
+    from .tasks import PostureTask
+
+    B, nq = configuration.batch_size, configuration.nq
+    q_rows = _host_array(q_rows, "q_rows")
+    if q_rows is None or q_rows.ndim not in (2, 3) or q_rows.shape[-1] != nq or q_rows.shape[-2] < 1 \
+            or (q_rows.ndim == 3 and q_rows.shape[0] != B):
+        raise ValueError(f"q_rows must have shape (S, {nq}) or ({B}, S, {nq}), got {None if q_rows is None else q_rows.shape}")
+    rows = np.ascontiguousarray(np.broadcast_to(q_rows, (B, q_rows.shape[-2], nq)))
+    reference = _optional_array(reference, "reference", (nq,), B)
+    # (the kernel reads the model's joint table through a problem handle: the smallest one, a posture task, serves)
+    prob, layout = _compile(configuration, [PostureTask(configuration.model, cost=1.0)], None, 1, devices=configuration.devices[:1])
+    with _pin(configuration, layout):
+        out = prob.unwind_turns(rows, configuration.q_batch if reference is None else reference)
+    return configuration._unbatch(out)
+
+
 def distinct_solutions(configuration: Configuration, q_candidates, valid=None, n_solutions: int = 8, min_distance: float = 0.1,
-                       reference=None, weights=None) -> DistinctSet:
+                       reference=None, weights=None, unwind_turns: bool = False) -> DistinctSet:
     """The selection of solve_ik_solutions alone, over the caller's own candidates (closed-form IK branches, the q_all of an
     earlier call filtered again with another min_distance, the rungs of a ladder): q_candidates (S, nq) or (B, S, nq), `valid`
     (same leading shape; default: every candidate), `reference` (nq,) or (B, nq) (default: the configuration's q).  Up to
     `n_solutions` valid candidates no two of which lie within `min_distance` of each other, in ascending distance from the
-    reference, ties to the lowest index — the rule of solve_ik_solutions.  The configuration is not changed."""
+    reference, ties to the lowest index — the rule of solve_ik_solutions.  With `unwind_turns` the candidates are moved to the
+    turn nearest the reference first (the function unwind_turns) and `q` holds the moved rows.  The configuration is not
+    changed."""
     from .tasks import PostureTask
 
     B, nq, nv = configuration.batch_size, configuration.nq, configuration.nv
@@ -813,9 +842,11 @@ def distinct_solutions(configuration: Configuration, q_candidates, valid=None, n
     weights = _optional_array(weights, "weights", (nv,))
     # (the selection reads the model's joint table through a problem handle: the smallest one, a posture task, serves)
     prob, layout = _compile(configuration, [PostureTask(configuration.model, cost=1.0)], None, 1, devices=configuration.devices[:1])
+    ref = configuration.q_batch if reference is None else reference
     with _pin(configuration, layout):
-        out = prob.select_distinct(q_candidates, valid, configuration.q_batch if reference is None else reference, weights,
-                                   n_solutions=K, min_distance=r)
+        if unwind_turns:                 # (the two device calls composed: the candidates moved to the turn nearest `ref` first)
+            q_candidates = prob.unwind_turns(q_candidates, ref)
+        out = prob.select_distinct(q_candidates, valid, ref, weights, n_solutions=K, min_distance=r)
     un = configuration._unbatch
     return DistinctSet(un(out.q), un(out.seed_index >= 0), un(out.seed_index), un(out.distance), un(out.multiplicity),
                        un(out.n_distinct), un(out.n_valid), un(out.n_uncovered))
@@ -1320,6 +1351,71 @@ class RefinedLadderResult(NamedTuple):
     refined: Optional[np.ndarray] = None
 
 
+class LadderNodesResult(NamedTuple):
+    """Result of solve_ik_trajectory_ladder(n_nodes=K): LadderResult's fields, in its order, for the ladder searched on the K
+    deduplicated nodes of every rung — `node_index` is a slot in 0 … K − 1, and with return_all the *_all fields are the NODES'
+    rows, (B, T, K, ·), `seeds` the (B, T, S, nq) starts — and behind them what the selection says of every rung:
+    `node_seed_index` (B, T, K) the candidate each node is (−1: an empty slot, which repeats candidate 0 and is not tracked),
+    `node_multiplicity` the candidates it stands for, `node_distance` its distance from q; `n_distinct`, `n_converged`,
+    `n_uncovered` (B, T) nodes filled, candidates tracked, tracked candidates that no node covers; `seed_index` (B, T) the
+    chosen node's candidate index."""
+    q: np.ndarray
+    v: np.ndarray
+    status: np.ndarray
+    iters: np.ndarray
+    converged: np.ndarray
+    node_index: np.ndarray
+    n_tracked: np.ndarray
+    n_breaks: np.ndarray
+    path_length: np.ndarray
+    edge_break: np.ndarray
+    qvel: Optional[np.ndarray] = None
+    q_all: Optional[np.ndarray] = None
+    v_all: Optional[np.ndarray] = None
+    status_all: Optional[np.ndarray] = None
+    iters_all: Optional[np.ndarray] = None
+    converged_all: Optional[np.ndarray] = None
+    seeds: Optional[np.ndarray] = None
+    node_seed_index: Optional[np.ndarray] = None
+    node_multiplicity: Optional[np.ndarray] = None
+    node_distance: Optional[np.ndarray] = None
+    n_distinct: Optional[np.ndarray] = None
+    n_converged: Optional[np.ndarray] = None
+    n_uncovered: Optional[np.ndarray] = None
+    seed_index: Optional[np.ndarray] = None
+
+
+class RefinedLadderNodesResult(NamedTuple):
+    """Result of solve_ik_trajectory_ladder(n_nodes=K, refine=True): RefinedLadderResult's fields, in its order, and behind them
+    LadderNodesResult's own."""
+    q: np.ndarray
+    v: np.ndarray
+    status: np.ndarray
+    iters: np.ndarray
+    converged: np.ndarray
+    node_index: np.ndarray
+    n_tracked: np.ndarray
+    n_breaks: np.ndarray
+    path_length: np.ndarray
+    edge_break: np.ndarray
+    qvel: Optional[np.ndarray] = None
+    q_all: Optional[np.ndarray] = None
+    v_all: Optional[np.ndarray] = None
+    status_all: Optional[np.ndarray] = None
+    iters_all: Optional[np.ndarray] = None
+    converged_all: Optional[np.ndarray] = None
+    seeds: Optional[np.ndarray] = None
+    repaired: Optional[np.ndarray] = None
+    refined: Optional[np.ndarray] = None
+    node_seed_index: Optional[np.ndarray] = None
+    node_multiplicity: Optional[np.ndarray] = None
+    node_distance: Optional[np.ndarray] = None
+    n_distinct: Optional[np.ndarray] = None
+    n_converged: Optional[np.ndarray] = None
+    n_uncovered: Optional[np.ndarray] = None
+    seed_index: Optional[np.ndarray] = None
+
+
 class LadderPath(NamedTuple):
     """Result of ladder_path: the chosen `node_index` (B, T), the nodes along it `q` (B, T, nq), `edge_break` (B, T), and per
     instance `n_tracked`, `n_breaks`, `path_length` — without the leading axis for an unbatched configuration."""
@@ -1369,7 +1465,8 @@ def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt
                                seeds=None, seed_table: Optional["SeedTable"] = None, rng_seed: int = 0,
                                qvel_dt: Optional[float] = None, return_all: bool = False, update: bool = True,
                                max_instances: int = 1 << 20, damping: float = 1e-12, limits: Optional[Sequence] = None,
-                               safety_break: bool = False, solver: str = "mi355x", refine: bool = False):
+                               safety_break: bool = False, solver: str = "mi355x", n_nodes: Optional[int] = None,
+                               min_distance: float = 0.1, unwind_turns: bool = False, refine: bool = False):
     """Track a time sequence of targets through a ladder graph: `n_seeds` IK solutions per waypoint, solved independently of
     each other, and a dynamic program on the device that picks one per waypoint — the path that is complete first, free of
     joint-space jumps second and shortest third (the rule in full: include/minkhip.h).  Where solve_ik_trajectory_multistart
@@ -1390,9 +1487,23 @@ def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt
     `refine=True` runs refine_path's pass behind the search, in the same call on the device: the chosen path is re-tracked
     across its breaks and lost nodes with the same loop parameters, gate and weights, and comes back only where that makes its
     key strictly smaller — the result is never worse than the search's.  Everything above then speaks of the returned path,
-    and the result is a RefinedLadderResult: LadderResult's fields and, behind them, `repaired` and `refined`."""
+    and the result is a RefinedLadderResult: LadderResult's fields and, behind them, `repaired` and `refined`.
+
+    `n_nodes=K` searches on at most K DISTINCT nodes per rung instead of on all n_seeds results: between the loops and the
+    search every rung is reduced on the device by distinct_solutions' rule — radius `min_distance`, reference the
+    configuration's q, the ladder's `weights` — so that the search costs T·K² and the device holds B·T·K node rows, whatever
+    n_seeds is: n_seeds may then reach 4 096 (1 <= K <= 64).  The nodes are a subset of the results, so the path's key is never
+    smaller than without n_nodes and the number of tracked waypoints is the same.  `unwind_turns` (with n_nodes only; alone
+    it raises) moves every result to the turn nearest q first, see the function unwind_turns.  The result is then a
+    LadderNodesResult — a RefinedLadderNodesResult with refine —: the fields above and, behind them, the selection's.  With
+    n_nodes None the call is the one described above, unchanged."""
     del solver
     S, max_iters = int(n_seeds), int(max_iters)
+    if n_nodes is None and unwind_turns:
+        raise ValueError("unwind_turns works in front of the selection of n_nodes distinct nodes per rung: pass n_nodes")
+    K = r = None
+    if n_nodes is not None:
+        K, r = _set_args(n_nodes, min_distance, S)
     if max_iters < 1:
         raise ValueError("max_iters must be >= 1")
     if int(max_instances) < 1:
@@ -1407,7 +1518,10 @@ def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt
                         "solve_ik_trajectory_ladder")
     B, nq, nv = configuration.batch_size, configuration.nq, configuration.nv
     seqs, T = _trajectory_targets(configuration, tasks, targets)
-    nat.check_ladder_shape(S, T, step_sq)
+    if K is None:
+        nat.check_ladder_shape(S, T, step_sq)
+    else:
+        nat.check_ladder_nodes_shape(S, K, T, step_sq, r)
     _need_frame_task(tasks, "a ladder")
     if S * T > int(max_instances):
         raise ValueError(f"one instance's ladder has T*n_seeds = {T * S} loops, beyond max_instances = {int(max_instances)}")
@@ -1430,11 +1544,15 @@ def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt
               refine=bool(refine))
 
     def job(handle, lo, hi):
-        r = handle.solve_trajectory_ladder(q[lo:hi], _rows(ft, 0, lo, hi), _rows(pt, 2, lo, hi), _rows(ct, 2, lo, hi), dt,
-                                           damping, target_index0=lo, seeds=_rows(seeds, 0, lo, hi), seed_table=seed_table, **kw)
-        return RefinedLadderResult(*r[:17], r.repaired, r.refined)
+        args = (q[lo:hi], _rows(ft, 0, lo, hi), _rows(pt, 2, lo, hi), _rows(ct, 2, lo, hi), dt, damping)
+        if K is None:
+            o = handle.solve_trajectory_ladder(*args, target_index0=lo, seeds=_rows(seeds, 0, lo, hi), seed_table=seed_table, **kw)
+            return RefinedLadderNodesResult(*o[:17], o.repaired, o.refined)
+        o = handle.solve_trajectory_ladder_nodes(*args, target_index0=lo, seeds=_rows(seeds, 0, lo, hi), seed_table=seed_table,
+                                                 n_nodes=K, min_distance=r, unwind_turns=bool(unwind_turns), **kw)
+        return RefinedLadderNodesResult(*o[:17], o.repaired, o.refined, *o[20:])
 
-    res = _join(RefinedLadderResult, _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job))
+    res = _join(RefinedLadderNodesResult, _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job))
     if safety_break and ((res.status & nat.ST_OUTSIDE_LIMITS) != 0).any():
         b, t = (int(x) for x in np.argwhere((res.status & nat.ST_OUTSIDE_LIMITS) != 0)[0])
         raise _outside_limits(
@@ -1450,7 +1568,12 @@ def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt
                        un(res.n_tracked), un(res.n_breaks), un(res.path_length), un(res.edge_break.astype(bool)),
                        opt(res.qvel), opt(res.q_all), opt(res.v_all), opt(res.status_all), opt(res.iters_all),
                        opt(res.converged_all, True), opt(res.seeds))
-    return RefinedLadderResult(*out, un(res.repaired), un(res.refined.astype(bool))) if refine else out
+    fixed = (un(res.repaired), un(res.refined.astype(bool))) if refine else ()
+    if K is None:
+        return RefinedLadderResult(*out, *fixed) if refine else out
+    sets = [un(x) for x in (res.node_seed_index, res.node_multiplicity, res.node_distance, res.n_distinct, res.n_converged,
+                            res.n_uncovered, res.seed_index)]
+    return (RefinedLadderNodesResult if refine else LadderNodesResult)(*out, *fixed, *sets)
 
 
 class RefinedPath(NamedTuple):
