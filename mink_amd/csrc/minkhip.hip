@@ -12,6 +12,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <mutex>
 #include <string>
@@ -148,7 +149,10 @@ enum WsRole {
   // inputs of a host-pointer call, staged as they came
   WS_IN_Q, WS_IN_FT, WS_IN_PT, WS_IN_CT, WS_IN_SEEDS, WS_IN_REF, WS_IN_W,
   // the B·S candidate rows: what the loops read and write (time-major (T, B·S, .) for a trajectory; one buffer per array, so
-  // that a caller's *_all array replaces its own), the starts, and ONE fanned-out (B·S, .) slab per target group
+  // that a caller's *_all array replaces its own), the starts, and ONE fanned-out (B·S, .) slab per target group.  Who asks:
+  // the entry point asks for the rows it hands to ms_loops (the multi-start calls all of C_Q … C_STARTS; a ladder or a goal set
+  // C_Q alone, for one chunk's starts, when the caller wants no seeds_out; the ladder on nodes C_Q … C_CV for one chunk);
+  // ms_loops itself asks for C_FT / C_PT / C_CT and, with a seed table, for the IN_SEEDS slab — per chunk, the largest first
   WS_C_Q, WS_C_V, WS_C_ST, WS_C_IT, WS_C_CV, WS_C_STARTS, WS_C_FT, WS_C_PT, WS_C_CT,
   // a batch-major trajectory call: time-major copies of its targets, the loops' time-major results (TM_I32: status | iters |
   // converged)
@@ -177,7 +181,7 @@ enum WsRole {
   // turn unwinding: the per-qpos-address table (mode, range_lo, range_hi), built with the seeding table
   WS_UNW,
   // a ladder on deduplicated nodes: its (B, T, K, .) node rows live in a plain ladder's WS_L_Q … WS_L_TRK with K for S, the
-  // candidates of ONE chunk of rungs in multi-start's WS_C_Q … WS_C_CV.  A host caller's set outputs — N_I32: node_seed_index |
+  // candidates of ONE chunk of rungs in multi-start's WS_C_Q … WS_C_CV, asked for by the call itself.  A host caller's set outputs — N_I32: node_seed_index |
   // node_multiplicity (B, T, K), then n_distinct | n_converged | n_uncovered | seed_index (B, T); N_DIST: node_distance (B, T, K)
   WS_N_I32, WS_N_DIST,
   WS_COUNT
@@ -1292,6 +1296,12 @@ struct Stager {
     if (d) latch(hipMemcpyAsync(d, src, n * sizeof(double), hipMemcpyHostToDevice, stream));
     return d;
   }
+  const int32_t* up_i32(WsRole role, const int32_t* src, size_t n) {       // (the same for `n` int32)
+    if (devp || !src) return src;
+    int32_t* const d = i32(role, n);
+    if (d) latch(hipMemcpyAsync(d, src, n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    return d;
+  }
   // rows the loops write: the caller's own array where it is a device buffer, else slot `role`
   void* given_or(WsRole role, void* given, size_t bytes) { return (devp && given) ? given : need(role, bytes); }
   // a result back into a host caller's array (an output the caller did not ask for: dst == NULL)
@@ -1514,136 +1524,155 @@ int32_t mkh_problem_set_seed_table(MkhProblem* p, const MkhSeedTable* table) {
   return MKH_OK;
 }
 
-// mkh_solve_multistart, and the rungs of mkh_solve_trajectory_ladder: with `rungs_v` (device, (B·S, nv)) the loops' velocities go
-// there and the call ends behind the loop — no selection, io's per-target outputs are not read.  With `set`
-// (mkh_solve_multistart_set) the selection behind the loop is the distinct set's (solution_set.hip) into set->io's outputs, and
-// io's per-target outputs are not read either: the two calls share everything in front of it.
-struct SetSpec {
-  int32_t K;                       // n_solutions
-  double r2;                       // min_distance²
-  const MkhSolutionSetIO* io;      // the outputs (checked by the entry point)
+// ---- the loop stage of every call that fans a target out to S starts (kernels: multistart.hip, seed_table.hip): the two
+// multi-start calls below, the rungs of the ladder calls and the goals of mkh_solve_goalset.  It works on device arrays and on
+// the caller's Stager; which arrays, the caller says.
+struct LoopSpec {                  // what a threshold loop is run with
+  double dt, damping;
+  int32_t max_iters;
+  double pos_threshold, ori_threshold;
 };
-static void set_select(Stager& st, int B, int S, const SetSpec& set, const double* d_q_all, const double* d_v_all,
-                       const int32_t* d_status, const int32_t* d_iters, const int32_t* d_conv, const double* d_ref, const double* d_w);
 
-static int32_t multistart_core(MkhProblem* p, int32_t B, const double* q, const double* frame_targets,
-                               const double* posture_target, const double* com_target, double dt, double damping,
-                               int32_t max_iters, double pos_threshold, double ori_threshold, int32_t n_seeds,
-                               uint64_t rng_seed, int64_t target_index0, const MkhMultistartIO* io, int32_t flags,
-                               void* hip_stream, double* rungs_v, const SetSpec* set = nullptr) {
-  const char* const who = set ? "mkh_solve_multistart_set" : "mkh_solve_multistart";
-  if (!p) return fail(MKH_E_INVALID, "null problem");
-  if (B < 1) return fail(MKH_E_INVALID, "B must be >= 1");
-  if (n_seeds < 1) return fail(MKH_E_INVALID, "n_seeds must be >= 1");
-  if (max_iters < 1) return fail(MKH_E_INVALID, "max_iters must be >= 1");
+// What these calls refuse about the loop's scalars, in this order (`why`: the entry point's own words on the thresholds).
+static int32_t loops_refuse(const LoopSpec& ls, int64_t target_index0, bool with_dt, const char* who = nullptr,
+                            const char* why = nullptr) {
+  if (ls.max_iters < 1) return fail(MKH_E_INVALID, "max_iters must be >= 1");
   if (target_index0 < 0) return fail(MKH_E_INVALID, "target_index0 must be >= 0");
-  if (!(pos_threshold >= 0.0) || !(ori_threshold >= 0.0)) return fail(MKH_E_INVALID, "thresholds must be >= 0");
-  const bool unwind = (flags & MKH_FLAG_UNWIND_TURNS) != 0;        // (the set's alone: its results are unwound in front of the selection)
-  if (!set || rungs_v)
-    if (const int32_t rc = refuse_unwind(flags, who)) return rc;
-  if (!io || (!rungs_v && !set && (!io->q_best || !io->v_best || !io->iters || !io->status || !io->converged || !io->seed_index || !io->n_converged)))
-    return fail(MKH_E_INVALID, "io and its per-target outputs (q_best, v_best, iters, status, converged, seed_index, n_converged) are required");
-  if (set && n_seeds > mkh::kSsMaxCandidates)
-    return fail(MKH_E_LIMIT, "%s: n_seeds = %d candidates per target, at most %d (their selection state lives in LDS)", who, n_seeds,
-                mkh::kSsMaxCandidates);
-  const DeviceProblem& P = p->dev;
-  if (const int32_t rc = refuse_inputs(P, q, frame_targets, posture_target, com_target, who, "multi-start"))
-    return rc;
-  const long long N = (long long)B * n_seeds;
-  if (N > p->max_batch)
-    return fail(MKH_E_INVALID, "B * n_seeds = %lld exceeds max_batch=%d of this problem", N, p->max_batch);
-  // an attached seed table gives rows s >= 1 unless the caller brought seeds of their own
-  const MkhSeedTable* const tab = (!io->seeds && n_seeds > 1) ? p->seed_table : nullptr;
-  if (tab)
-    if (const int32_t rc = st_refuse(p, tab, n_seeds - 1, who)) return rc;
-  HIP_OK(hipSetDevice(p->model->device));
-  if (const int32_t rc = ms_build_tables(p)) return rc;
-  const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
-  const bool pbat = (flags & MKH_FLAG_POSTURE_BATCHED) != 0, cbat = (flags & MKH_FLAG_COM_BATCHED) != 0;
-  Stager st{p, (hipStream_t)hip_stream, devp, set ? "multistart_set" : "multistart"};
-  hipStream_t stream = st.stream;
-  GrowBuf* const ws = p->ws;
-  const int S = n_seeds;
-  const size_t Bz = B, Nz = (size_t)N, nq = P.nq, nv = P.nv, f8 = sizeof(double), i4 = sizeof(int32_t);
-  const size_t ft_w = (size_t)P.n_frame * 7, pt_w = (size_t)P.n_posture * nq, ct_w = (size_t)P.n_com * 3;
+  if (with_dt && !(ls.dt > 0.0)) return fail(MKH_E_INVALID, "dt must be > 0");
+  if (!(ls.pos_threshold >= 0.0) || !(ls.ori_threshold >= 0.0))
+    return why ? fail(MKH_E_INVALID, "%s: thresholds must be >= 0 (%s)", who, why) : fail(MKH_E_INVALID, "thresholds must be >= 0");
+  return MKH_OK;
+}
 
-  // ---- inputs on the device
-  const double* const d_q = st.up(WS_IN_Q, q, Bz * nq);
-  const double* const d_ft = st.up(WS_IN_FT, frame_targets, Bz * ft_w);
-  const double* d_pt = pt_w ? st.up(WS_IN_PT, posture_target, pt_w * (pbat ? Bz : 1)) : posture_target;
-  const double* d_ct = ct_w ? st.up(WS_IN_CT, com_target, ct_w * (cbat ? Bz : 1)) : com_target;
-  const double* const d_ref = st.up(WS_IN_REF, io->q_ref, Bz * nq);
-  const double* const d_w = st.up(WS_IN_W, io->weights, nv);
-  const double* d_user = st.up(WS_IN_SEEDS, io->seeds, Nz * nq);             // (the seed kernel reads them once)
-  // ---- workspace of the B·S instances: the caller's *_all arrays where they are device buffers
-  double* const c_q = st.f64(WS_C_Q, Nz * nq);
-  double* const c_v = rungs_v ? rungs_v : st.f64(WS_C_V, Nz * nv);
-  int32_t* const d_status = (int32_t*)st.given_or(WS_C_ST, io->status_all, Nz * i4);
-  int32_t* const d_iters = (int32_t*)st.given_or(WS_C_IT, io->iters_all, Nz * i4);
-  int32_t* const d_conv = (int32_t*)st.given_or(WS_C_CV, io->converged_all, Nz * i4);
-  // seeds: into the caller's seeds_out when it is a device buffer (the loop then reads them there), else into the workspace,
-  // where the loop runs in place
-  double* const d_seeds = (devp && io->seeds_out) ? io->seeds_out : c_q;
-  double* const d_q_all = (devp && io->q_all) ? io->q_all : c_q;
-  if (tab) {                          // the S − 1 entries nearest to each target, into the slab a caller's seeds would be in
+// An attached seed table gives rows s >= 1 unless the caller brought seeds of their own: the table of this call, or none.
+static int32_t seed_table_for(const MkhProblem* p, const double* seeds, int S, const char* who, const MkhSeedTable** tab) {
+  *tab = (!seeds && S > 1) ? p->seed_table : nullptr;
+  return *tab ? st_refuse(p, *tab, S - 1, who) : MKH_OK;
+}
+
+struct MsIn {                      // what the stage reads, one row per target (pt / ct: one row in all where not batched)
+  const double *q, *ft, *pt, *ct;
+  const double* user;              // the caller's (B, S, nq) seeds, or NULL
+  const MkhSeedTable* tab;         // seed_table_for()
+};
+struct MsRows {                    // the (B·S, .) candidate rows it writes
+  double* starts;                  // the seed kernel writes them, the loop reads them; q_all itself: the loop runs in place
+  double *q_all, *v_all;
+  int32_t *status, *iters, *converged;
+  double* kept;                    // a copy of the starts set aside in front of an in-place loop, or NULL
+};
+
+// Seeds (rows s >= 1 from the seed table's nearest entries, the caller's seeds, or drawn), the three target groups fanned out,
+// and the loops: mkh_solve_until's own path and dispatch on the B·S instances.  Candidate 0 of a target is its row of in.q.
+// Returns the refusal of the loop launch; HIP errors are latched in `st`, and nothing is launched behind one.
+static int32_t ms_loops(Stager& st, int B, int S, const MsIn& in, const LoopSpec& ls, uint64_t rng_seed, int64_t target_index0,
+                        const MsRows& c, int32_t flags) {
+  MkhProblem* const p = st.p;
+  const DeviceProblem& P = p->dev;
+  hipStream_t stream = st.stream;
+  const bool pbat = (flags & MKH_FLAG_POSTURE_BATCHED) != 0, cbat = (flags & MKH_FLAG_COM_BATCHED) != 0;
+  const size_t Nz = (size_t)B * S, nq = P.nq;
+  const size_t ft_w = (size_t)P.n_frame * 7, pt_w = (size_t)P.n_posture * nq, ct_w = (size_t)P.n_com * 3;
+  const double* d_user = in.user;
+  if (in.tab) {                       // the S − 1 entries nearest to each target, into the slab a caller's seeds would be in
     double* const slab = st.f64(WS_IN_SEEDS, Nz * nq);
-    ST_LAUNCH(st, launch_st_query(stream, tab->d_keys, tab->d_q, tab->d_w, tab->N, P.n_frame, (int)nq, B, d_ft, S - 1, nullptr,
-                                  nullptr, slab));
+    ST_LAUNCH(st, launch_st_query(stream, in.tab->d_keys, in.tab->d_q, in.tab->d_w, in.tab->N, P.n_frame, (int)nq, B, in.ft, S - 1,
+                                  nullptr, nullptr, slab));
     d_user = slab;
   }
-  ST_LAUNCH(st, launch_ms_seed(stream, ws[WS_SEED_I].i32(), ws[WS_SEED_F].f64(), B, S, (int)nq, d_q, d_user,
-                               (unsigned long long)rng_seed, (long long)target_index0, d_seeds));
-  double* kept_seeds = nullptr;       // (host caller: the seeds are set aside before the loop overwrites them in place)
-  if (!devp && io->seeds_out && (kept_seeds = st.f64(WS_C_STARTS, Nz * nq)))
-    st.latch(hipMemcpyAsync(kept_seeds, d_seeds, Nz * nq * f8, hipMemcpyDeviceToDevice, stream));
-  // ---- target fan-out: every per-instance target S times (the solve kernels index targets by instance)
+  ST_LAUNCH(st, launch_ms_seed(stream, p->ws[WS_SEED_I].i32(), p->ws[WS_SEED_F].f64(), B, S, (int)nq, in.q, d_user,
+                               (unsigned long long)rng_seed, (long long)target_index0, c.starts));
+  if (c.kept) st.latch(hipMemcpyAsync(c.kept, c.starts, Nz * nq * sizeof(double), hipMemcpyDeviceToDevice, stream));
+  // target fan-out: every per-instance target S times (the solve kernels index targets by instance)
   auto fanout = [&](WsRole role, const double* src, size_t w) -> const double* {
     double* const dst = st.f64(role, Nz * w);
     ST_LAUNCH(st, launch_ms_fanout(stream, src, dst, B, S, (int)w));
     return dst;
   };
-  const double* const c_ft = fanout(WS_C_FT, d_ft, ft_w);
-  if (pt_w && pbat) d_pt = fanout(WS_C_PT, d_pt, pt_w);
-  if (ct_w && cbat) d_ct = fanout(WS_C_CT, d_ct, ct_w);
-  if (!st.ok()) return st.finish();
-  // ---- the loop: mkh_solve_until's own path and dispatch on the B·S instances
+  const double* const c_ft = fanout(WS_C_FT, in.ft, ft_w);
+  const double* const c_pt = (pt_w && pbat) ? fanout(WS_C_PT, in.pt, pt_w) : in.pt;
+  const double* const c_ct = (ct_w && cbat) ? fanout(WS_C_CT, in.ct, ct_w) : in.ct;
+  if (!st.ok()) return MKH_OK;
   const int32_t loop_flags = (flags & ~(MKH_FLAG_WARM_START | MKH_FLAG_UNWIND_TURNS)) | MKH_FLAG_DEVICE_PTRS;
-  if (const int32_t rc = run(p, (int32_t)N, d_seeds, c_ft, d_pt, d_ct, dt, damping, c_v, d_status, nullptr, loop_flags, hip_stream,
-                             max_iters, d_q_all, nullptr, pos_threshold, ori_threshold, d_iters, d_conv))
-    return st.finish(rc);
-  if (rungs_v) return st.finish();
-  // ---- selection
-  if (unwind)                           // in place, where q_all is read from: the loops' flags are carried over
-    ST_LAUNCH(st, launch_unwind_turns(stream, ws[WS_UNW].f64(), N, S, (int)nq, d_q_all, d_ref ? d_ref : d_q, d_q_all));
-  if (set) {
-    set_select(st, B, S, *set, d_q_all, c_v, d_status, d_iters, d_conv, d_ref ? d_ref : d_q, d_w);
-  } else {
-    double *o_q = io->q_best, *o_v = io->v_best;
-    int32_t *o_it = io->iters, *o_st = io->status, *o_cv = io->converged, *o_si = io->seed_index, *o_nc = io->n_converged;
-    if (!devp) {
-      o_q = st.f64(WS_OUT_Q, Bz * nq); o_v = st.f64(WS_OUT_V, Bz * nv);
-      o_it = st.i32(WS_OUT_I32, 3 * Bz); o_st = o_it + Bz; o_cv = o_it + 2 * Bz;
-      o_si = st.i32(WS_OUT_PICK, 2 * Bz); o_nc = o_si + Bz;
-    }
-    ST_LAUNCH(st, launch_ms_select(stream, B, S, (int)nq, (int)nv, p->model->njnt, ws[WS_JNT].i32(), d_q_all, c_v, d_status, d_iters,
-                                   d_conv, d_ref ? d_ref : d_q, d_w, o_q, o_v, o_it, o_st, o_cv, o_si, o_nc));
-    if (!devp) {
-      st.down(io->q_best, o_q, Bz * nq * f8);
-      st.down(io->v_best, o_v, Bz * nv * f8);
-      st.down(io->iters, o_it, Bz * i4);
-      st.down(io->status, o_st, Bz * i4);
-      st.down(io->converged, o_cv, Bz * i4);
-      st.down(io->seed_index, o_si, Bz * i4);
-      st.down(io->n_converged, o_nc, Bz * i4);
-    }
+  return run(p, (int32_t)Nz, c.starts, c_ft, c_pt, c_ct, ls.dt, ls.damping, c.v_all, c.status, nullptr, loop_flags, (void*)stream,
+             ls.max_iters, c.q_all, nullptr, ls.pos_threshold, ls.ori_threshold, c.iters, c.converged);
+}
+
+// R flattened rows of targets (a ladder's rungs, a goal set's goals) through ms_loops, whole rows per chunk of at most
+// max_batch / S of them: chunk r0 … reads rows r0 … of `in` and draws with target index index0 + r0; rows_at(r0) names the
+// candidate rows it writes, then(r0, n) is what the caller enqueues behind its n rows' loops.  The first chunk is the largest:
+// a slot sized for it is not grown while an earlier chunk's work is queued.  Returns as ms_loops does.
+static int32_t ms_rungs(Stager& st, size_t R, int S, const MsIn& in, const LoopSpec& ls, uint64_t rng_seed, int64_t index0,
+                        int32_t flags, const std::function<MsRows(size_t)>& rows_at,
+                        const std::function<void(size_t, size_t)>& then = nullptr) {
+  const DeviceProblem& P = st.p->dev;
+  const bool pbat = (flags & MKH_FLAG_POSTURE_BATCHED) != 0, cbat = (flags & MKH_FLAG_COM_BATCHED) != 0;
+  const size_t nq = P.nq, ft_w = (size_t)P.n_frame * 7, pt_w = (size_t)P.n_posture * nq, ct_w = (size_t)P.n_com * 3;
+  const size_t per = (size_t)st.p->max_batch / S;
+  for (size_t r0 = 0; r0 < R; r0 += per) {
+    const size_t n = R - r0 < per ? R - r0 : per;
+    const MsIn chunk{in.q + r0 * nq, in.ft + r0 * ft_w, (pt_w && pbat) ? in.pt + r0 * pt_w : in.pt,
+                     (ct_w && cbat) ? in.ct + r0 * ct_w : in.ct, in.user ? in.user + r0 * S * nq : nullptr, in.tab};
+    const int32_t rc = ms_loops(st, (int)n, S, chunk, ls, rng_seed, index0 + (int64_t)r0, rows_at(r0), flags);
+    if (rc || !st.ok()) return rc;
+    if (then) then(r0, n);
   }
-  if (devp) return st.finish();
-  st.down(io->q_all, d_q_all, Nz * nq * f8);
-  st.down(io->status_all, d_status, Nz * i4);
-  st.down(io->iters_all, d_iters, Nz * i4);
-  st.down(io->converged_all, d_conv, Nz * i4);
-  st.down(io->seeds_out, kept_seeds, Nz * nq * f8);
-  return st.finish();
+  return MKH_OK;
+}
+
+// ---- mkh_solve_multistart and mkh_solve_multistart_set: everything in front of their selections
+static int32_t ms_refuse(const MkhProblem* p, int32_t B, int32_t n_seeds, const double* q, const double* frame_targets,
+                         const double* posture_target, const double* com_target, const double* seeds, const char* who,
+                         const MkhSeedTable** tab) {
+  if (const int32_t rc = refuse_inputs(p->dev, q, frame_targets, posture_target, com_target, who, "multi-start")) return rc;
+  const long long N = (long long)B * n_seeds;
+  if (N > p->max_batch)
+    return fail(MKH_E_INVALID, "B * n_seeds = %lld exceeds max_batch=%d of this problem", N, p->max_batch);
+  return seed_table_for(p, seeds, n_seeds, who, tab);
+}
+
+struct MsCall {                    // what the two calls stage: the loops' inputs and rows, and the selections' reference and weights
+  MsIn in;
+  MsRows c;
+  const double *ref, *w;
+};
+// The inputs on the device, and the B·S candidate rows: the caller's *_all arrays where they are device buffers.  Seeds go into
+// the caller's seeds_out when it is a device buffer (the loop then reads them there), else into the workspace, where the loop
+// runs in place (a host caller's seeds_out: set aside before the loop overwrites them).
+static MsCall ms_stage(Stager& st, int B, int S, const double* q, const double* frame_targets, const double* posture_target,
+                       const double* com_target, const MkhSeedTable* tab, const MkhMultistartIO& io, int32_t flags) {
+  const DeviceProblem& P = st.p->dev;
+  const bool pbat = (flags & MKH_FLAG_POSTURE_BATCHED) != 0, cbat = (flags & MKH_FLAG_COM_BATCHED) != 0;
+  const size_t Bz = B, Nz = Bz * S, nq = P.nq, nv = P.nv, i4 = sizeof(int32_t);
+  const size_t ft_w = (size_t)P.n_frame * 7, pt_w = (size_t)P.n_posture * nq, ct_w = (size_t)P.n_com * 3;
+  MsCall m;
+  m.in.q = st.up(WS_IN_Q, q, Bz * nq);
+  m.in.ft = st.up(WS_IN_FT, frame_targets, Bz * ft_w);
+  m.in.pt = pt_w ? st.up(WS_IN_PT, posture_target, pt_w * (pbat ? Bz : 1)) : posture_target;
+  m.in.ct = ct_w ? st.up(WS_IN_CT, com_target, ct_w * (cbat ? Bz : 1)) : com_target;
+  const double* const d_ref = st.up(WS_IN_REF, io.q_ref, Bz * nq);
+  m.ref = d_ref ? d_ref : m.in.q;
+  m.w = st.up(WS_IN_W, io.weights, nv);
+  m.in.user = st.up(WS_IN_SEEDS, io.seeds, Nz * nq);             // (the seed kernel reads them once)
+  m.in.tab = tab;
+  double* const c_q = st.f64(WS_C_Q, Nz * nq);
+  m.c.starts = (st.devp && io.seeds_out) ? io.seeds_out : c_q;
+  m.c.q_all = (st.devp && io.q_all) ? io.q_all : c_q;
+  m.c.v_all = st.f64(WS_C_V, Nz * nv);
+  m.c.status = (int32_t*)st.given_or(WS_C_ST, io.status_all, Nz * i4);
+  m.c.iters = (int32_t*)st.given_or(WS_C_IT, io.iters_all, Nz * i4);
+  m.c.converged = (int32_t*)st.given_or(WS_C_CV, io.converged_all, Nz * i4);
+  m.c.kept = (!st.devp && io.seeds_out) ? st.f64(WS_C_STARTS, Nz * nq) : nullptr;
+  return m;
+}
+// a host caller's optional per-instance arrays
+static void ms_down(Stager& st, size_t Nz, const MkhMultistartIO& io, const MsRows& c) {
+  const size_t nq = st.p->dev.nq, f8 = sizeof(double), i4 = sizeof(int32_t);
+  st.down(io.q_all, c.q_all, Nz * nq * f8);
+  st.down(io.status_all, c.status, Nz * i4);
+  st.down(io.iters_all, c.iters, Nz * i4);
+  st.down(io.converged_all, c.converged, Nz * i4);
+  st.down(io.seeds_out, c.kept, Nz * nq * f8);
 }
 
 int32_t mkh_solve_multistart(MkhProblem* p, int32_t B, const double* q, const double* frame_targets,
@@ -1651,11 +1680,53 @@ int32_t mkh_solve_multistart(MkhProblem* p, int32_t B, const double* q, const do
                              int32_t max_iters, double pos_threshold, double ori_threshold, int32_t n_seeds,
                              uint64_t rng_seed, int64_t target_index0, const MkhMultistartIO* io, int32_t flags,
                              void* hip_stream) {
-  return multistart_core(p, B, q, frame_targets, posture_target, com_target, dt, damping, max_iters, pos_threshold, ori_threshold,
-                         n_seeds, rng_seed, target_index0, io, flags, hip_stream, nullptr);
+  const char* const who = "mkh_solve_multistart";
+  const LoopSpec ls{dt, damping, max_iters, pos_threshold, ori_threshold};
+  const int S = n_seeds;
+  if (!p) return fail(MKH_E_INVALID, "null problem");
+  if (B < 1) return fail(MKH_E_INVALID, "B must be >= 1");
+  if (S < 1) return fail(MKH_E_INVALID, "n_seeds must be >= 1");
+  if (const int32_t rc = loops_refuse(ls, target_index0, false)) return rc;
+  if (const int32_t rc = refuse_unwind(flags, who)) return rc;
+  if (!io || !io->q_best || !io->v_best || !io->iters || !io->status || !io->converged || !io->seed_index || !io->n_converged)
+    return fail(MKH_E_INVALID, "io and its per-target outputs (q_best, v_best, iters, status, converged, seed_index, n_converged) are required");
+  const MkhSeedTable* tab;
+  if (const int32_t rc = ms_refuse(p, B, S, q, frame_targets, posture_target, com_target, io->seeds, who, &tab)) return rc;
+  HIP_OK(hipSetDevice(p->model->device));
+  if (const int32_t rc = ms_build_tables(p)) return rc;
+  const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
+  Stager st{p, (hipStream_t)hip_stream, devp, "multistart"};
+  const size_t Bz = B, nq = p->dev.nq, nv = p->dev.nv, f8 = sizeof(double), i4 = sizeof(int32_t);
+  const MsCall m = ms_stage(st, B, S, q, frame_targets, posture_target, com_target, tab, *io, flags);
+  if (const int32_t rc = ms_loops(st, B, S, m.in, ls, rng_seed, target_index0, m.c, flags); rc || !st.ok()) return st.finish(rc);
+  // ---- selection
+  double *o_q = io->q_best, *o_v = io->v_best;
+  int32_t *o_it = io->iters, *o_st = io->status, *o_cv = io->converged, *o_si = io->seed_index, *o_nc = io->n_converged;
+  if (!devp) {
+    o_q = st.f64(WS_OUT_Q, Bz * nq); o_v = st.f64(WS_OUT_V, Bz * nv);
+    o_it = st.i32(WS_OUT_I32, 3 * Bz); o_st = o_it + Bz; o_cv = o_it + 2 * Bz;
+    o_si = st.i32(WS_OUT_PICK, 2 * Bz); o_nc = o_si + Bz;
+  }
+  ST_LAUNCH(st, launch_ms_select(st.stream, B, S, (int)nq, (int)nv, p->model->njnt, p->ws[WS_JNT].i32(), m.c.q_all, m.c.v_all,
+                                 m.c.status, m.c.iters, m.c.converged, m.ref, m.w, o_q, o_v, o_it, o_st, o_cv, o_si, o_nc));
+  if (devp) return st.finish();
+  st.down(io->q_best, o_q, Bz * nq * f8);
+  st.down(io->v_best, o_v, Bz * nv * f8);
+  st.down(io->iters, o_it, Bz * i4);
+  st.down(io->status, o_st, Bz * i4);
+  st.down(io->converged, o_cv, Bz * i4);
+  st.down(io->seed_index, o_si, Bz * i4);
+  st.down(io->n_converged, o_nc, Bz * i4);
+  ms_down(st, Bz * S, *io, m.c);
+  return st.finish();
 }
 
 // ---- distinct solution sets (include/minkhip.h "THE RULE OF THE SET"; kernel: solution_set.hip)
+struct SetSpec {
+  int32_t K;                       // n_solutions
+  double r2;                       // min_distance²
+  const MkhSolutionSetIO* io;      // the outputs (checked by the entry point)
+};
 // The selection on device arrays into set.io's outputs: in place for a device-pointer call, else through the workspace and
 // down.  v / status / iters / conv may be absent (a selection over a caller's own candidates: conv is then its `valid`).
 static void set_select(Stager& st, int B, int S, const SetSpec& set, const double* d_q_all, const double* d_v_all,
@@ -1702,25 +1773,44 @@ static int32_t set_refuse(int32_t n_solutions, double min_distance, const char* 
   return MKH_OK;
 }
 
+// mkh_solve_multistart with the distinct set's selection behind the loops, the results unwound in front of it when asked.
 int32_t mkh_solve_multistart_set(MkhProblem* p, int32_t B, const double* q, const double* frame_targets,
                                  const double* posture_target, const double* com_target, double dt, double damping,
                                  int32_t max_iters, double pos_threshold, double ori_threshold, int32_t n_seeds,
                                  int32_t n_solutions, double min_distance, uint64_t rng_seed, int64_t target_index0,
                                  const MkhSolutionSetIO* io, int32_t flags, void* hip_stream) {
   const char* const who = "mkh_solve_multistart_set";
+  const LoopSpec ls{dt, damping, max_iters, pos_threshold, ori_threshold};
+  const int S = n_seeds;
   if (!p) return fail(MKH_E_INVALID, "null problem");
   if (const int32_t rc = set_refuse(n_solutions, min_distance, who)) return rc;
   if (!io || !io->q_set || !io->v_set || !io->iters || !io->status || !io->seed_index || !io->multiplicity || !io->distance ||
       !io->n_distinct || !io->n_converged || !io->n_uncovered)
     return fail(MKH_E_INVALID, "%s: io and its outputs q_set, v_set, iters, status, seed_index, multiplicity, distance, n_distinct, "
                                "n_converged, n_uncovered are required", who);
-  MkhMultistartIO mio{};           // what the shared path reads: the inputs and the optional per-instance arrays
+  if (B < 1) return fail(MKH_E_INVALID, "B must be >= 1");
+  if (S < 1) return fail(MKH_E_INVALID, "n_seeds must be >= 1");
+  if (const int32_t rc = loops_refuse(ls, target_index0, false)) return rc;
+  if (S > mkh::kSsMaxCandidates)
+    return fail(MKH_E_LIMIT, "%s: n_seeds = %d candidates per target, at most %d (their selection state lives in LDS)", who, S,
+                mkh::kSsMaxCandidates);
+  const MkhSeedTable* tab;
+  if (const int32_t rc = ms_refuse(p, B, S, q, frame_targets, posture_target, com_target, io->seeds, who, &tab)) return rc;
+  HIP_OK(hipSetDevice(p->model->device));
+  if (const int32_t rc = ms_build_tables(p)) return rc;
+  Stager st{p, (hipStream_t)hip_stream, (flags & MKH_FLAG_DEVICE_PTRS) != 0, "multistart_set"};
+  MkhMultistartIO mio{};           // what the staging reads: the inputs and the optional per-instance arrays
   mio.seeds = io->seeds; mio.q_ref = io->q_ref; mio.weights = io->weights;
   mio.q_all = io->q_all; mio.converged_all = io->converged_all; mio.iters_all = io->iters_all; mio.status_all = io->status_all;
   mio.seeds_out = io->seeds_out;
+  const MsCall m = ms_stage(st, B, S, q, frame_targets, posture_target, com_target, tab, mio, flags);
+  if (const int32_t rc = ms_loops(st, B, S, m.in, ls, rng_seed, target_index0, m.c, flags); rc || !st.ok()) return st.finish(rc);
+  if (flags & MKH_FLAG_UNWIND_TURNS)     // in place, where q_all is read from: the loops' flags are carried over
+    ST_LAUNCH(st, launch_unwind_turns(st.stream, p->ws[WS_UNW].f64(), (long long)B * S, S, (int)p->dev.nq, m.c.q_all, m.ref, m.c.q_all));
   const SetSpec set{n_solutions, min_distance * min_distance, io};
-  return multistart_core(p, B, q, frame_targets, posture_target, com_target, dt, damping, max_iters, pos_threshold, ori_threshold,
-                         n_seeds, rng_seed, target_index0, &mio, flags, hip_stream, nullptr, &set);
+  set_select(st, B, S, set, m.c.q_all, m.c.v_all, m.c.status, m.c.iters, m.c.converged, m.ref, m.w);
+  if (!st.devp) ms_down(st, (size_t)B * S, mio, m.c);
+  return st.finish();
 }
 
 int32_t mkh_select_distinct(MkhProblem* p, int32_t B, int32_t S, const double* q_candidates, const int32_t* valid,
@@ -1747,12 +1837,7 @@ int32_t mkh_select_distinct(MkhProblem* p, int32_t B, int32_t S, const double* q
   const double* const d_cand = st.up(WS_C_Q, q_candidates, N * nq);
   const double* const d_ref = st.up(WS_IN_REF, q_ref, Bz * nq);
   const double* const d_w = st.up(WS_IN_W, weights, p->dev.nv);
-  const int32_t* d_valid = valid;
-  if (!devp && valid) {
-    int32_t* const t = st.i32(WS_C_CV, N);
-    if (t) st.latch(hipMemcpyAsync(t, valid, N * sizeof(int32_t), hipMemcpyHostToDevice, st.stream));
-    d_valid = t;
-  }
+  const int32_t* const d_valid = st.up_i32(WS_C_CV, valid, N);
   if (!st.ok()) return st.finish();
   MkhSolutionSetIO sio = *io;      // (the selection alone has no loop rows: n_converged is the count of `valid`, when asked for)
   const SetSpec set{n_solutions, min_distance * min_distance, &sio};
@@ -2195,12 +2280,7 @@ int32_t mkh_ladder_select(MkhProblem* p, int32_t B, int32_t T, int32_t S, const 
   const double* const d_q = st.up(WS_IN_Q, q, Bz * nq);
   const double* const d_nodes = st.up(WS_L_Q, q_nodes, N * nq);
   const double* const d_w = st.up(WS_IN_W, weights, p->dev.nv);
-  const int32_t* d_trk = tracked;
-  if (!devp) {
-    int32_t* const t = st.i32(WS_L_TRK, N);
-    if (t) st.latch(hipMemcpyAsync(t, tracked, N * i4, hipMemcpyHostToDevice, st.stream));
-    d_trk = t;
-  }
+  const int32_t* const d_trk = st.up_i32(WS_L_TRK, tracked, N);
   int32_t *o_node = io->node_index, *o_eb = io->edge_break, *o_nt = io->n_tracked, *o_nb = io->n_breaks;
   double *o_len = io->path_length, *o_q = io->q_path;
   if (!devp) {
@@ -2226,9 +2306,8 @@ int32_t mkh_ladder_select(MkhProblem* p, int32_t B, int32_t T, int32_t S, const 
 // step kernel and one loop launch through run(), and the guard.  Returns the first refusal of a loop launch; HIP errors are
 // latched in `st`.
 static int32_t refine_pass(Stager& st, int B, int T, const double* d_q, const double* d_path, const int32_t* d_trk, const double* d_ft,
-                           const double* d_pt, const double* d_ct, double dt, double damping, int32_t max_iters, double pos_threshold,
-                           double ori_threshold, const double* d_w, double max_step_sq, const mkh::LrOut& out, int32_t flags,
-                           void* hip_stream) {
+                           const double* d_pt, const double* d_ct, const LoopSpec& ls, const double* d_w, double max_step_sq,
+                           const mkh::LrOut& out, int32_t flags) {
   MkhProblem* const p = st.p;
   const DeviceProblem& P = p->dev;
   hipStream_t stream = st.stream;
@@ -2263,8 +2342,8 @@ static int32_t refine_pass(Stager& st, int B, int T, const double* d_q, const do
   auto loop = [&](size_t t) -> int32_t {
     if (!st.ok()) return MKH_OK;
     return run(p, B, w.start, d_ft ? d_ft + t * Bz * ft_w : nullptr, d_pt ? d_pt + t * pt_step : nullptr,
-               d_ct ? d_ct + t * ct_step : nullptr, dt, damping, w.xv, w.xst, nullptr, loop_flags, hip_stream, max_iters, w.x, nullptr,
-               pos_threshold, ori_threshold, w.xit, w.xcv);
+               d_ct ? d_ct + t * ct_step : nullptr, ls.dt, ls.damping, w.xv, w.xst, nullptr, loop_flags, (void*)stream, ls.max_iters, w.x,
+               nullptr, ls.pos_threshold, ls.ori_threshold, w.xit, w.xcv);
   };
   step(-1, 1, 0, 1);
   for (int t = 0; t < T; ++t) {                              // forward; its last commit decides the first backward waypoint
@@ -2280,17 +2359,13 @@ static int32_t refine_pass(Stager& st, int B, int T, const double* d_q, const do
 }
 
 // What both refining entry points refuse about the loops of the pass.
-static int32_t refine_refuse(const MkhProblem* p, int32_t B, int32_t T, double max_step_sq, int32_t max_iters, double dt,
-                             double pos_threshold, double ori_threshold, const char* who) {
+static int32_t refine_refuse(const MkhProblem* p, int32_t B, int32_t T, double max_step_sq, const LoopSpec& ls, const char* who) {
   if (B < 1) return fail(MKH_E_INVALID, "%s: B = %d must be >= 1", who, B);
   if (T < 1) return fail(MKH_E_INVALID, "%s: T = %d must be >= 1", who, T);
   if (T > 65535) return fail(MKH_E_LIMIT, "%s: T = %d waypoints, at most 65535", who, T);
   if (!(max_step_sq >= 0.0)) return fail(MKH_E_INVALID, "%s: max_step_sq = %g must be >= 0 (+inf: no gate)", who, max_step_sq);
   if ((long long)B * T > 0x7fffffffLL) return fail(MKH_E_LIMIT, "%s: B * T = %lld rows", who, (long long)B * T);
-  if (max_iters < 1) return fail(MKH_E_INVALID, "max_iters must be >= 1");
-  if (!(dt > 0.0)) return fail(MKH_E_INVALID, "dt must be > 0");
-  if (!(pos_threshold >= 0.0) || !(ori_threshold >= 0.0))
-    return fail(MKH_E_INVALID, "%s: thresholds must be >= 0 (a fixed count leaves no tracked flag to judge a repair by)", who);
+  if (const int32_t rc = loops_refuse(ls, 0, true, who, "a fixed count leaves no tracked flag to judge a repair by")) return rc;
   if (B > p->max_batch) return fail(MKH_E_INVALID, "%s: B=%d exceeds max_batch=%d of this problem (a sweep's loop launch is one chunk)", who, B, p->max_batch);
   return MKH_OK;
 }
@@ -2300,9 +2375,10 @@ int32_t mkh_ladder_refine(MkhProblem* p, int32_t B, int32_t T, const double* q, 
                           double damping, int32_t max_iters, double pos_threshold, double ori_threshold, const MkhLadderRefineIO* io,
                           int32_t flags, void* hip_stream) {
   const char* const who = "mkh_ladder_refine";
+  const LoopSpec ls{dt, damping, max_iters, pos_threshold, ori_threshold};
   if (!p) return fail(MKH_E_INVALID, "null problem");
   if (!io) return fail(MKH_E_INVALID, "%s: io is required", who);
-  if (const int32_t rc = refine_refuse(p, B, T, io->max_step_sq, max_iters, dt, pos_threshold, ori_threshold, who)) return rc;
+  if (const int32_t rc = refine_refuse(p, B, T, io->max_step_sq, ls, who)) return rc;
   if (const int32_t rc = refuse_unwind(flags, who)) return rc;
   if (!q_path || !tracked_path) return fail(MKH_E_INVALID, "%s: q_path and tracked_path are required", who);
   if (!io->q_path_out || !io->tracked_out || !io->repaired || !io->refined || !io->edge_break || !io->n_tracked || !io->n_breaks ||
@@ -2326,13 +2402,10 @@ int32_t mkh_ladder_refine(MkhProblem* p, int32_t B, int32_t T, const double* q, 
   const double* const d_pt = pt_w ? st.up(WS_IN_PT, posture_target, pt_w * (pbat ? R : 1)) : posture_target;
   const double* const d_ct = ct_w ? st.up(WS_IN_CT, com_target, ct_w * (cbat ? R : 1)) : com_target;
   const double* const d_w = st.up(WS_IN_W, io->weights, nv);
-  const int32_t* d_trk = tracked_path;
+  const int32_t* const d_trk = st.up_i32(WS_IN_TRK, tracked_path, R);
   mkh::LrOut o{io->q_path_out, io->v, io->path_length, io->tracked_out, io->repaired, io->refined, io->edge_break, io->n_tracked,
                io->n_breaks, io->status, io->iters, io->converged};
   if (!devp) {
-    int32_t* const t = st.i32(WS_IN_TRK, R);
-    if (t) st.latch(hipMemcpyAsync(t, tracked_path, R * i4, hipMemcpyHostToDevice, st.stream));
-    d_trk = t;
     o.q = st.f64(WS_OUT_Q, R * nq);
     o.path_length = st.f64(WS_OUT_LEN, Bz);
     o.tracked = st.i32(WS_OUT_REF, 2 * R + Bz); o.repaired = o.tracked + R; o.refined = o.tracked + 2 * R;
@@ -2349,8 +2422,7 @@ int32_t mkh_ladder_refine(MkhProblem* p, int32_t B, int32_t T, const double* q, 
     }
   }
   if (!st.ok()) return st.finish();
-  if (const int32_t rc = refine_pass(st, B, T, d_q, d_path, d_trk, d_ft, d_pt, d_ct, dt, damping, max_iters, pos_threshold,
-                                     ori_threshold, d_w, io->max_step_sq, o, flags, hip_stream))
+  if (const int32_t rc = refine_pass(st, B, T, d_q, d_path, d_trk, d_ft, d_pt, d_ct, ls, d_w, io->max_step_sq, o, flags))
     return st.finish(rc);
   if (devp) return st.finish();
   st.down(io->q_path_out, o.q, R * nq * f8);
@@ -2368,6 +2440,149 @@ int32_t mkh_ladder_refine(MkhProblem* p, int32_t B, int32_t T, const double* q, 
   return st.finish();
 }
 
+// ---- the fused ladder calls: mkh_solve_trajectory_ladder(_refined) on the loops' S nodes per rung, and
+// mkh_solve_trajectory_ladder_nodes on K deduplicated ones.  They share everything but the width W of the (B·T, W, .) node
+// arrays and what fills them: refuse → stage → rungs → pick → refine, qvel → copy back.
+struct LadderCall {
+  MsIn in;                         // the (B·T) flattened targets; in.q: q once per (instance, waypoint), their "current posture"
+  const double *q, *w;             // q (B, nq); the edge cost's weights
+  // the nodes, (B·T, W, .): the caller's *_all arrays where they are device buffers; the starts, (B·T, S, nq), when asked for
+  double *l_q, *l_v;
+  int32_t *l_st, *l_it, *l_cv, *l_trk;
+  double* l_starts;
+  // the device-side outputs, (B, T, .) and (B,): the caller's arrays for a device-pointer call, else carved from WS_OUT_*.  The
+  // path's rows, the search's integers, and the refinement's three arrays (NULL without a pass)
+  double *o_q, *o_v, *o_qvel, *o_len;
+  int32_t *o_st, *o_it, *o_cv, *o_node, *o_eb, *o_nt, *o_nb, *o_trk, *o_rep, *o_ref;
+};
+
+// What both calls refuse behind their own checks of the graph's shape, in this order (`nodes`: the call on distinct nodes).
+static int32_t ladder_call_refuse(const MkhProblem* p, int32_t B, int32_t T, int S, const LoopSpec& ls, int64_t target_index0,
+                                  const double* q, const double* frame_targets, const double* posture_target,
+                                  const double* com_target, const MkhTrajectoryLadderIO* io, const MkhLadderNodesIO* nodes,
+                                  const MkhLadderRefineIO* refine, bool devp, const char* who, const MkhSeedTable** tab) {
+  if (const int32_t rc = loops_refuse(ls, target_index0, true, who, "a fixed count leaves no tracked flag to search on")) return rc;
+  if (!io->q_traj || !io->v_traj || !io->status || !io->iters || !io->converged || !io->node_index || !io->n_tracked ||
+      !io->n_breaks || !io->path_length || !io->edge_break)
+    return fail(MKH_E_INVALID, "%s: io's outputs q_traj, v_traj, status, iters, converged, node_index, n_tracked, n_breaks, path_length, "
+                               "edge_break are required", who);
+  if (nodes && (!nodes->node_seed_index || !nodes->node_multiplicity || !nodes->node_distance || !nodes->n_distinct ||
+                !nodes->n_converged || !nodes->n_uncovered || !nodes->seed_index))
+    return fail(MKH_E_INVALID, "%s: nodes' outputs node_seed_index, node_multiplicity, node_distance, n_distinct, n_converged, "
+                               "n_uncovered, seed_index are required", who);
+  if (io->qvel && !(io->waypoint_dt > 0.0)) return fail(MKH_E_INVALID, "qvel needs waypoint_dt > 0");
+  if (refine) {
+    if (const int32_t rc = refine_refuse(p, B, T, io->max_step_sq, ls, who)) return rc;
+    if (!refine->tracked_out || !refine->repaired || !refine->refined)
+      return fail(MKH_E_INVALID, "%s: refine's outputs tracked_out, repaired, refined are required", who);
+  }
+  if (const int32_t rc = refuse_inputs(p->dev, q, frame_targets, posture_target, com_target, who, "ladder")) return rc;
+  if (S > p->max_batch) return fail(MKH_E_INVALID, "%s: n_seeds = %d exceeds max_batch=%d of this problem (a rung is one chunk)", who, S, p->max_batch);
+  if (!devp)
+    if (const int32_t rc = ladder_weights_refuse(io->weights, p->dev.nv, who)) return rc;
+  return seed_table_for(p, io->seeds, S, who, tab);
+}
+
+// The inputs on the device with q fanned out to the rungs, the node arrays, and the outputs.
+static LadderCall ladder_stage(Stager& st, int B, int T, int S, int W, const double* q, const double* frame_targets,
+                               const double* posture_target, const double* com_target, const MkhSeedTable* tab,
+                               const MkhTrajectoryLadderIO* io, const MkhLadderRefineIO* refine, int32_t flags) {
+  const DeviceProblem& P = st.p->dev;
+  const bool pbat = (flags & MKH_FLAG_POSTURE_BATCHED) != 0, cbat = (flags & MKH_FLAG_COM_BATCHED) != 0;
+  const size_t Bz = B, R = Bz * T, N = R * S, M = R * W, nq = P.nq, nv = P.nv, f8 = sizeof(double), i4 = sizeof(int32_t);
+  const size_t ft_w = (size_t)P.n_frame * 7, pt_w = (size_t)P.n_posture * nq, ct_w = (size_t)P.n_com * 3;
+  LadderCall c;
+  c.q = st.up(WS_IN_Q, q, Bz * nq);
+  c.in.ft = st.up(WS_IN_FT, frame_targets, R * ft_w);
+  c.in.pt = pt_w ? st.up(WS_IN_PT, posture_target, pt_w * (pbat ? R : 1)) : posture_target;
+  c.in.ct = ct_w ? st.up(WS_IN_CT, com_target, ct_w * (cbat ? R : 1)) : com_target;
+  c.w = st.up(WS_IN_W, io->weights, nv);
+  c.in.user = st.up(WS_IN_SEEDS, io->seeds, N * nq);
+  c.in.tab = tab;
+  double* const d_q0 = st.f64(WS_L_Q0, R * nq);
+  ST_LAUNCH(st, launch_ms_fanout(st.stream, c.q, d_q0, B, T, (int)nq));
+  c.in.q = d_q0;
+  c.l_q = (double*)st.given_or(WS_L_Q, io->q_all, M * nq * f8);
+  c.l_v = (double*)st.given_or(WS_L_V, io->v_all, M * nv * f8);
+  c.l_st = (int32_t*)st.given_or(WS_L_ST, io->status_all, M * i4);
+  c.l_it = (int32_t*)st.given_or(WS_L_IT, io->iters_all, M * i4);
+  c.l_cv = (int32_t*)st.given_or(WS_L_CV, io->converged_all, M * i4);
+  c.l_trk = st.i32(WS_L_TRK, M);
+  c.l_starts = io->seeds_out ? (double*)st.given_or(WS_L_STARTS, io->seeds_out, N * nq * f8) : nullptr;
+  c.o_q = io->q_traj; c.o_v = io->v_traj; c.o_qvel = io->qvel; c.o_len = io->path_length;
+  c.o_st = io->status; c.o_it = io->iters; c.o_cv = io->converged;
+  c.o_node = io->node_index; c.o_eb = io->edge_break; c.o_nt = io->n_tracked; c.o_nb = io->n_breaks;
+  c.o_trk = refine ? refine->tracked_out : nullptr; c.o_rep = refine ? refine->repaired : nullptr; c.o_ref = refine ? refine->refined : nullptr;
+  if (!st.devp) {
+    c.o_q = st.f64(WS_OUT_Q, R * nq); c.o_v = st.f64(WS_OUT_V, R * nv);
+    c.o_qvel = io->qvel ? st.f64(WS_OUT_QVEL, R * nv) : nullptr;
+    c.o_st = st.i32(WS_OUT_I32, 3 * R); c.o_it = c.o_st + R; c.o_cv = c.o_st + 2 * R;
+    c.o_node = st.i32(WS_OUT_PICK, 2 * R + 2 * Bz); c.o_eb = c.o_node + R; c.o_nt = c.o_node + 2 * R; c.o_nb = c.o_nt + Bz;
+    c.o_len = st.f64(WS_OUT_LEN, Bz);
+    if (refine) { c.o_trk = st.i32(WS_OUT_REF, 2 * R + Bz); c.o_rep = c.o_trk + R; c.o_ref = c.o_trk + 2 * R; }
+  }
+  return c;
+}
+
+// The search on the (B, T, W) nodes, and the chosen nodes' rows.
+static void ladder_pick(Stager& st, int B, int T, int W, const LadderCall& c, double max_step_sq) {
+  const long long R = (long long)B * T;
+  const int nq = st.p->dev.nq, nv = st.p->dev.nv;
+  ladder_search(st, B, T, W, c.q, c.l_q, c.l_trk, c.w, max_step_sq, c.o_node, c.o_nt, c.o_nb, c.o_len, c.o_eb);
+  ST_LAUNCH(st, launch_ladder_gather(st.stream, c.l_q, c.o_q, c.o_node, R, W, nq));
+  ST_LAUNCH(st, launch_ladder_gather(st.stream, c.l_v, c.o_v, c.o_node, R, W, nv));
+  ST_LAUNCH(st, launch_ladder_gather_i32(st.stream, c.l_st, c.o_st, c.o_node, R, W));
+  ST_LAUNCH(st, launch_ladder_gather_i32(st.stream, c.l_it, c.o_it, c.o_node, R, W));
+  ST_LAUNCH(st, launch_ladder_gather_i32(st.stream, c.l_cv, c.o_cv, c.o_node, R, W));
+}
+
+// The optional pass over the chosen path, and the waypoint velocities.  The chosen nodes' flags are the path's; the pass reads
+// path and flags in place and writes the returned ones over them.  Returns as refine_pass does.
+static int32_t ladder_refine_qvel(Stager& st, int B, int T, int W, const LadderCall& c, const LoopSpec& ls,
+                                  const MkhTrajectoryLadderIO* io, bool refine, int32_t flags) {
+  const MkhProblem* const p = st.p;
+  const int nq = p->dev.nq, nv = p->dev.nv;
+  if (refine) {
+    ST_LAUNCH(st, launch_ladder_gather_i32(st.stream, c.l_trk, c.o_trk, c.o_node, (long long)B * T, W));
+    const mkh::LrOut o{c.o_q, c.o_v, c.o_len, c.o_trk, c.o_rep, c.o_ref, c.o_eb, c.o_nt, c.o_nb, c.o_st, c.o_it, c.o_cv};
+    if (const int32_t rc = refine_pass(st, B, T, c.q, c.o_q, c.o_trk, c.in.ft, c.in.pt, c.in.ct, ls, c.w, io->max_step_sq, o, flags))
+      return rc;
+  }
+  if (c.o_qvel)
+    ST_LAUNCH(st, launch_tj_qvel(st.stream, p->ws[WS_JNT].i32(), p->model->njnt, B, T, nq, c.q, c.o_q, (long long)T * nq, (long long)nq,
+                                 io->waypoint_dt, c.o_qvel, (long long)T * nv, (long long)nv, 0));
+  return MKH_OK;
+}
+
+// A host caller's results: io's, then (through `between`) what the entry point adds, then the pass's.
+static void ladder_down(Stager& st, int B, int T, int S, int W, const LadderCall& c, const MkhTrajectoryLadderIO* io,
+                        const MkhLadderRefineIO* refine, const std::function<void()>& between = nullptr) {
+  const size_t Bz = B, R = Bz * T, N = R * S, M = R * W, nq = st.p->dev.nq, nv = st.p->dev.nv, f8 = sizeof(double), i4 = sizeof(int32_t);
+  st.down(io->q_traj, c.o_q, R * nq * f8);
+  st.down(io->v_traj, c.o_v, R * nv * f8);
+  st.down(io->status, c.o_st, R * i4);
+  st.down(io->iters, c.o_it, R * i4);
+  st.down(io->converged, c.o_cv, R * i4);
+  st.down(io->node_index, c.o_node, R * i4);
+  st.down(io->edge_break, c.o_eb, R * i4);
+  st.down(io->n_tracked, c.o_nt, Bz * i4);
+  st.down(io->n_breaks, c.o_nb, Bz * i4);
+  st.down(io->path_length, c.o_len, Bz * f8);
+  st.down(io->qvel, c.o_qvel, R * nv * f8);
+  st.down(io->q_all, c.l_q, M * nq * f8);
+  st.down(io->v_all, c.l_v, M * nv * f8);
+  st.down(io->status_all, c.l_st, M * i4);
+  st.down(io->iters_all, c.l_it, M * i4);
+  st.down(io->converged_all, c.l_cv, M * i4);
+  st.down(io->seeds_out, c.l_starts, N * nq * f8);
+  if (between) between();
+  if (refine) {
+    st.down(refine->tracked_out, c.o_trk, R * i4);
+    st.down(refine->repaired, c.o_rep, R * i4);
+    st.down(refine->refined, c.o_ref, Bz * i4);
+  }
+}
+
 int32_t mkh_solve_trajectory_ladder(MkhProblem* p, int32_t B, int32_t T, int32_t n_seeds, const double* q,
                                     const double* frame_targets, const double* posture_target, const double* com_target, double dt,
                                     double damping, int32_t max_iters, double pos_threshold, double ori_threshold, uint64_t rng_seed,
@@ -2382,143 +2597,43 @@ int32_t mkh_solve_trajectory_ladder_refined(MkhProblem* p, int32_t B, int32_t T,
                                             uint64_t rng_seed, int64_t target_index0, const MkhTrajectoryLadderIO* io,
                                             const MkhLadderRefineIO* refine, int32_t flags, void* hip_stream) {
   const char* const who = refine ? "mkh_solve_trajectory_ladder_refined" : "mkh_solve_trajectory_ladder";
+  const LoopSpec ls{dt, damping, max_iters, pos_threshold, ori_threshold};
+  const int S = n_seeds;
+  const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
   if (!p) return fail(MKH_E_INVALID, "null problem");
   if (!io) return fail(MKH_E_INVALID, "%s: io is required", who);
-  const int S = n_seeds;
   if (const int32_t rc = ladder_refuse(p, B, T, S, io->max_step_sq, who)) return rc;
   if (const int32_t rc = refuse_unwind(flags, who)) return rc;
-  if (max_iters < 1) return fail(MKH_E_INVALID, "max_iters must be >= 1");
-  if (target_index0 < 0) return fail(MKH_E_INVALID, "target_index0 must be >= 0");
-  if (!(dt > 0.0)) return fail(MKH_E_INVALID, "dt must be > 0");
-  if (!(pos_threshold >= 0.0) || !(ori_threshold >= 0.0))
-    return fail(MKH_E_INVALID, "%s: thresholds must be >= 0 (a fixed count leaves no tracked flag to search on)", who);
-  if (!io->q_traj || !io->v_traj || !io->status || !io->iters || !io->converged || !io->node_index || !io->n_tracked ||
-      !io->n_breaks || !io->path_length || !io->edge_break)
-    return fail(MKH_E_INVALID, "%s: io's outputs q_traj, v_traj, status, iters, converged, node_index, n_tracked, n_breaks, path_length, "
-                               "edge_break are required", who);
-  if (io->qvel && !(io->waypoint_dt > 0.0)) return fail(MKH_E_INVALID, "qvel needs waypoint_dt > 0");
-  if (refine) {
-    if (const int32_t rc = refine_refuse(p, B, T, io->max_step_sq, max_iters, dt, pos_threshold, ori_threshold, who)) return rc;
-    if (!refine->tracked_out || !refine->repaired || !refine->refined)
-      return fail(MKH_E_INVALID, "%s: refine's outputs tracked_out, repaired, refined are required", who);
-  }
-  const DeviceProblem& P = p->dev;
-  if (const int32_t rc = refuse_inputs(P, q, frame_targets, posture_target, com_target, who, "ladder")) return rc;
-  if (S > p->max_batch) return fail(MKH_E_INVALID, "%s: n_seeds = %d exceeds max_batch=%d of this problem (a rung is one chunk)", who, S, p->max_batch);
-  const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
-  if (!devp)
-    if (const int32_t rc = ladder_weights_refuse(io->weights, P.nv, who)) return rc;
-  const MkhSeedTable* const tab = (!io->seeds && S > 1) ? p->seed_table : nullptr;
-  if (tab)
-    if (const int32_t rc = st_refuse(p, tab, S - 1, who)) return rc;
+  const MkhSeedTable* tab;
+  if (const int32_t rc = ladder_call_refuse(p, B, T, S, ls, target_index0, q, frame_targets, posture_target, com_target, io, nullptr,
+                                            refine, devp, who, &tab))
+    return rc;
   HIP_OK(hipSetDevice(p->model->device));
   if (const int32_t rc = ms_build_tables(p)) return rc;
-  const bool pbat = (flags & MKH_FLAG_POSTURE_BATCHED) != 0, cbat = (flags & MKH_FLAG_COM_BATCHED) != 0;
   Stager st{p, (hipStream_t)hip_stream, devp, "trajectory_ladder"};
-  hipStream_t stream = st.stream;
-  const size_t Bz = B, R = Bz * T, N = R * S, nq = P.nq, nv = P.nv, f8 = sizeof(double), i4 = sizeof(int32_t);
-  const size_t ft_w = (size_t)P.n_frame * 7, pt_w = (size_t)P.n_posture * nq, ct_w = (size_t)P.n_com * 3;
-  // ---- inputs on the device; q once per (instance, waypoint): the flattened targets' "current posture"
-  const double* const d_q = st.up(WS_IN_Q, q, Bz * nq);
-  const double* const d_ft = st.up(WS_IN_FT, frame_targets, R * ft_w);
-  const double* const d_pt = pt_w ? st.up(WS_IN_PT, posture_target, pt_w * (pbat ? R : 1)) : posture_target;
-  const double* const d_ct = ct_w ? st.up(WS_IN_CT, com_target, ct_w * (cbat ? R : 1)) : com_target;
-  const double* const d_w = st.up(WS_IN_W, io->weights, nv);
-  const double* const d_user = st.up(WS_IN_SEEDS, io->seeds, N * nq);
-  double* const d_q0 = st.f64(WS_L_Q0, R * nq);
-  ST_LAUNCH(st, launch_ms_fanout(stream, d_q, d_q0, B, T, (int)nq));
-  // ---- the nodes: the caller's *_all arrays where they are device buffers
-  double* const l_q = (double*)st.given_or(WS_L_Q, io->q_all, N * nq * f8);
-  double* const l_v = (double*)st.given_or(WS_L_V, io->v_all, N * nv * f8);
-  int32_t* const l_st = (int32_t*)st.given_or(WS_L_ST, io->status_all, N * i4);
-  int32_t* const l_it = (int32_t*)st.given_or(WS_L_IT, io->iters_all, N * i4);
-  int32_t* const l_cv = (int32_t*)st.given_or(WS_L_CV, io->converged_all, N * i4);
-  int32_t* const l_trk = st.i32(WS_L_TRK, N);
-  double* const l_starts = io->seeds_out ? (double*)st.given_or(WS_L_STARTS, io->seeds_out, N * nq * f8) : nullptr;
-  // ---- outputs
-  double *o_q = io->q_traj, *o_v = io->v_traj, *o_qvel = io->qvel, *o_len = io->path_length;
-  int32_t *o_st = io->status, *o_it = io->iters, *o_cv = io->converged;
-  int32_t *o_node = io->node_index, *o_eb = io->edge_break, *o_nt = io->n_tracked, *o_nb = io->n_breaks;
-  if (!devp) {
-    o_q = st.f64(WS_OUT_Q, R * nq); o_v = st.f64(WS_OUT_V, R * nv);
-    o_qvel = io->qvel ? st.f64(WS_OUT_QVEL, R * nv) : nullptr;
-    o_st = st.i32(WS_OUT_I32, 3 * R); o_it = o_st + R; o_cv = o_st + 2 * R;
-    o_node = st.i32(WS_OUT_PICK, 2 * R + 2 * Bz); o_eb = o_node + R; o_nt = o_node + 2 * R; o_nb = o_nt + Bz;
-    o_len = st.f64(WS_OUT_LEN, Bz);
-  }
-  // ---- the pass's own outputs (the returned path goes where the search's goes)
-  int32_t *o_trk = nullptr, *o_rep = nullptr, *o_ref = nullptr;
-  if (refine) {
-    o_trk = refine->tracked_out; o_rep = refine->repaired; o_ref = refine->refined;
-    if (!devp) { o_trk = st.i32(WS_OUT_REF, 2 * R + Bz); o_rep = o_trk + R; o_ref = o_trk + 2 * R; }
-  }
+  const size_t R = (size_t)B * T, per = (size_t)p->max_batch / S, nq = p->dev.nq, nv = p->dev.nv;
+  const LadderCall c = ladder_stage(st, B, T, S, S, q, frame_targets, posture_target, com_target, tab, io, refine, flags);
+  // (without the caller's seeds_out the starts of one chunk go through multi-start's candidate slot; the loops write the nodes)
+  double* const c_q = c.l_starts ? nullptr : st.f64(WS_C_Q, (per < R ? per : R) * S * nq);
   if (!st.ok()) return st.finish();
-  // ---- the rungs: multi-start on the (B·T) flattened targets, whole rungs per chunk of at most max_batch loops
-  const size_t per = (size_t)p->max_batch / S;
-  const int32_t ms_flags = flags | MKH_FLAG_DEVICE_PTRS;
-  for (size_t r0 = 0; r0 < R; r0 += per) {
-    const size_t n = R - r0 < per ? R - r0 : per, i0 = r0 * S;
-    MkhMultistartIO mio;
-    memset(&mio, 0, sizeof mio);
-    mio.seeds = d_user ? d_user + i0 * nq : nullptr;
-    mio.q_all = l_q + i0 * nq; mio.status_all = l_st + i0; mio.iters_all = l_it + i0; mio.converged_all = l_cv + i0;
-    mio.seeds_out = l_starts ? l_starts + i0 * nq : nullptr;
-    if (const int32_t rc = multistart_core(p, (int32_t)n, d_q0 + r0 * nq, d_ft + r0 * ft_w, (pt_w && pbat) ? d_pt + r0 * pt_w : d_pt,
-                                           (ct_w && cbat) ? d_ct + r0 * ct_w : d_ct, dt, damping, max_iters, pos_threshold,
-                                           ori_threshold, S, rng_seed, target_index0 * T + (int64_t)r0, &mio, ms_flags, hip_stream,
-                                           l_v + i0 * nv))
-      return st.finish(rc);
-  }
-  // ---- the search, and the chosen nodes' rows
-  ST_LAUNCH(st, launch_ladder_tracked(stream, l_cv, l_st, (long long)N, l_trk));
-  ladder_search(st, B, T, S, d_q, l_q, l_trk, d_w, io->max_step_sq, o_node, o_nt, o_nb, o_len, o_eb);
-  ST_LAUNCH(st, launch_ladder_gather(stream, l_q, o_q, o_node, (long long)R, S, (int)nq));
-  ST_LAUNCH(st, launch_ladder_gather(stream, l_v, o_v, o_node, (long long)R, S, (int)nv));
-  ST_LAUNCH(st, launch_ladder_gather_i32(stream, l_st, o_st, o_node, (long long)R, S));
-  ST_LAUNCH(st, launch_ladder_gather_i32(stream, l_it, o_it, o_node, (long long)R, S));
-  ST_LAUNCH(st, launch_ladder_gather_i32(stream, l_cv, o_cv, o_node, (long long)R, S));
-  if (refine) {
-    // the chosen nodes' flags are the path's; the pass reads path and flags in place and writes the returned ones over them
-    ST_LAUNCH(st, launch_ladder_gather_i32(stream, l_trk, o_trk, o_node, (long long)R, S));
-    const mkh::LrOut o{o_q, o_v, o_len, o_trk, o_rep, o_ref, o_eb, o_nt, o_nb, o_st, o_it, o_cv};
-    if (const int32_t rc = refine_pass(st, B, T, d_q, o_q, o_trk, d_ft, d_pt, d_ct, dt, damping, max_iters, pos_threshold,
-                                       ori_threshold, d_w, io->max_step_sq, o, flags, hip_stream))
-      return st.finish(rc);
-  }
-  if (o_qvel)
-    ST_LAUNCH(st, launch_tj_qvel(stream, p->ws[WS_JNT].i32(), p->model->njnt, B, T, (int)nq, d_q, o_q, (long long)(T * nq), (long long)nq,
-                                 io->waypoint_dt, o_qvel, (long long)(T * nv), (long long)nv, 0));
-  if (devp) return st.finish();
-  st.down(io->q_traj, o_q, R * nq * f8);
-  st.down(io->v_traj, o_v, R * nv * f8);
-  st.down(io->status, o_st, R * i4);
-  st.down(io->iters, o_it, R * i4);
-  st.down(io->converged, o_cv, R * i4);
-  st.down(io->node_index, o_node, R * i4);
-  st.down(io->edge_break, o_eb, R * i4);
-  st.down(io->n_tracked, o_nt, Bz * i4);
-  st.down(io->n_breaks, o_nb, Bz * i4);
-  st.down(io->path_length, o_len, Bz * f8);
-  st.down(io->qvel, o_qvel, R * nv * f8);
-  st.down(io->q_all, l_q, N * nq * f8);
-  st.down(io->v_all, l_v, N * nv * f8);
-  st.down(io->status_all, l_st, N * i4);
-  st.down(io->iters_all, l_it, N * i4);
-  st.down(io->converged_all, l_cv, N * i4);
-  st.down(io->seeds_out, l_starts, N * nq * f8);
-  if (refine) {
-    st.down(refine->tracked_out, o_trk, R * i4);
-    st.down(refine->repaired, o_rep, R * i4);
-    st.down(refine->refined, o_ref, Bz * i4);
-  }
+  // ---- the rungs: multi-start on the (B·T) flattened targets, straight into the node arrays
+  auto rows_at = [&](size_t r0) {
+    const size_t i0 = r0 * S;
+    return MsRows{c.l_starts ? c.l_starts + i0 * nq : c_q, c.l_q + i0 * nq, c.l_v + i0 * nv, c.l_st + i0, c.l_it + i0, c.l_cv + i0,
+                  nullptr};
+  };
+  if (const int32_t rc = ms_rungs(st, R, S, c.in, ls, rng_seed, target_index0 * T, flags, rows_at)) return st.finish(rc);
+  ST_LAUNCH(st, launch_ladder_tracked(st.stream, c.l_cv, c.l_st, (long long)(R * S), c.l_trk));
+  ladder_pick(st, B, T, S, c, io->max_step_sq);
+  if (const int32_t rc = ladder_refine_qvel(st, B, T, S, c, ls, io, refine != nullptr, flags)) return st.finish(rc);
+  if (!devp) ladder_down(st, B, T, S, S, c, io, refine);
   return st.finish();
 }
 
-// ---- the ladder on deduplicated nodes (include/minkhip.h mkh_solve_trajectory_ladder_nodes; kernels: unwind.hip,
-// solution_set.hip, ladder_nodes.hip, ladder.hip).  mkh_solve_trajectory_ladder_refined with the distinct-set selection between
-// the loops of a chunk and the node arrays: the loops write multi-start's candidate buffers of ONE chunk, the selection writes
-// the chunk's K slots per rung into the (B·T, K, .) node arrays, and everything behind the rung loop is the plain ladder's with
-// K for S.
+// The ladder on deduplicated nodes (include/minkhip.h mkh_solve_trajectory_ladder_nodes; kernels: unwind.hip, solution_set.hip,
+// ladder_nodes.hip, ladder.hip): the loops write the candidate buffers of ONE chunk of rungs, which this call requests itself;
+// behind every chunk's loops its unwinding, the distinct-set selection into the chunk's K slots per rung of the node arrays, and
+// the slots' flags.  Everything behind the rungs is the plain ladder's with K for S.
 int32_t mkh_solve_trajectory_ladder_nodes(MkhProblem* p, int32_t B, int32_t T, int32_t n_seeds, int32_t n_nodes, double min_distance,
                                           const double* q, const double* frame_targets, const double* posture_target,
                                           const double* com_target, double dt, double damping, int32_t max_iters, double pos_threshold,
@@ -2526,9 +2641,11 @@ int32_t mkh_solve_trajectory_ladder_nodes(MkhProblem* p, int32_t B, int32_t T, i
                                           const MkhTrajectoryLadderIO* io, const MkhLadderNodesIO* nodes, const MkhLadderRefineIO* refine,
                                           int32_t flags, void* hip_stream) {
   const char* const who = "mkh_solve_trajectory_ladder_nodes";
+  const LoopSpec ls{dt, damping, max_iters, pos_threshold, ori_threshold};
+  const int S = n_seeds, K = n_nodes;
+  const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
   if (!p) return fail(MKH_E_INVALID, "null problem");
   if (!io || !nodes) return fail(MKH_E_INVALID, "%s: io and nodes are required", who);
-  const int S = n_seeds, K = n_nodes;
   if (S < 1) return fail(MKH_E_INVALID, "%s: n_seeds = %d must be >= 1", who, S);
   if (S > mkh::kSsMaxCandidates)
     return fail(MKH_E_LIMIT, "%s: n_seeds = %d candidates per rung, at most %d (their selection state lives in LDS)", who, S,
@@ -2536,161 +2653,59 @@ int32_t mkh_solve_trajectory_ladder_nodes(MkhProblem* p, int32_t B, int32_t T, i
   if (const int32_t rc = set_refuse(K, min_distance, who)) return rc;
   if (const int32_t rc = ladder_refuse(p, B, T, K, io->max_step_sq, who)) return rc;       // (the search runs on K nodes per rung)
   if ((long long)B * T * K > 0x7fffffffLL) return fail(MKH_E_LIMIT, "%s: B * T * n_nodes = %lld nodes", who, (long long)B * T * K);
-  if (max_iters < 1) return fail(MKH_E_INVALID, "max_iters must be >= 1");
-  if (target_index0 < 0) return fail(MKH_E_INVALID, "target_index0 must be >= 0");
-  if (!(dt > 0.0)) return fail(MKH_E_INVALID, "dt must be > 0");
-  if (!(pos_threshold >= 0.0) || !(ori_threshold >= 0.0))
-    return fail(MKH_E_INVALID, "%s: thresholds must be >= 0 (a fixed count leaves no tracked flag to search on)", who);
-  if (!io->q_traj || !io->v_traj || !io->status || !io->iters || !io->converged || !io->node_index || !io->n_tracked ||
-      !io->n_breaks || !io->path_length || !io->edge_break)
-    return fail(MKH_E_INVALID, "%s: io's outputs q_traj, v_traj, status, iters, converged, node_index, n_tracked, n_breaks, path_length, "
-                               "edge_break are required", who);
-  if (!nodes->node_seed_index || !nodes->node_multiplicity || !nodes->node_distance || !nodes->n_distinct || !nodes->n_converged ||
-      !nodes->n_uncovered || !nodes->seed_index)
-    return fail(MKH_E_INVALID, "%s: nodes' outputs node_seed_index, node_multiplicity, node_distance, n_distinct, n_converged, "
-                               "n_uncovered, seed_index are required", who);
-  if (io->qvel && !(io->waypoint_dt > 0.0)) return fail(MKH_E_INVALID, "qvel needs waypoint_dt > 0");
-  if (refine) {
-    if (const int32_t rc = refine_refuse(p, B, T, io->max_step_sq, max_iters, dt, pos_threshold, ori_threshold, who)) return rc;
-    if (!refine->tracked_out || !refine->repaired || !refine->refined)
-      return fail(MKH_E_INVALID, "%s: refine's outputs tracked_out, repaired, refined are required", who);
-  }
-  const DeviceProblem& P = p->dev;
-  if (const int32_t rc = refuse_inputs(P, q, frame_targets, posture_target, com_target, who, "ladder")) return rc;
-  if (S > p->max_batch) return fail(MKH_E_INVALID, "%s: n_seeds = %d exceeds max_batch=%d of this problem (a rung is one chunk)", who, S, p->max_batch);
-  const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
-  if (!devp)
-    if (const int32_t rc = ladder_weights_refuse(io->weights, P.nv, who)) return rc;
-  const MkhSeedTable* const tab = (!io->seeds && S > 1) ? p->seed_table : nullptr;
-  if (tab)
-    if (const int32_t rc = st_refuse(p, tab, S - 1, who)) return rc;
+  const MkhSeedTable* tab;
+  if (const int32_t rc = ladder_call_refuse(p, B, T, S, ls, target_index0, q, frame_targets, posture_target, com_target, io, nodes,
+                                            refine, devp, who, &tab))
+    return rc;
   HIP_OK(hipSetDevice(p->model->device));
   if (const int32_t rc = ms_build_tables(p)) return rc;
   const bool unwind = (flags & MKH_FLAG_UNWIND_TURNS) != 0;
   flags &= ~MKH_FLAG_UNWIND_TURNS;                           // (the loops and the pass below know nothing of it)
-  const bool pbat = (flags & MKH_FLAG_POSTURE_BATCHED) != 0, cbat = (flags & MKH_FLAG_COM_BATCHED) != 0;
   Stager st{p, (hipStream_t)hip_stream, devp, "trajectory_ladder_nodes"};
-  hipStream_t stream = st.stream;
-  const size_t Bz = B, R = Bz * T, N = R * S, M = R * K, nq = P.nq, nv = P.nv, f8 = sizeof(double), i4 = sizeof(int32_t);
-  const size_t ft_w = (size_t)P.n_frame * 7, pt_w = (size_t)P.n_posture * nq, ct_w = (size_t)P.n_com * 3;
+  const size_t R = (size_t)B * T, M = R * K, nq = p->dev.nq, nv = p->dev.nv, f8 = sizeof(double), i4 = sizeof(int32_t);
   const size_t per = (size_t)p->max_batch / S, chunk = (per < R ? per : R) * S;      // rungs, and loops, of one chunk
-  // ---- inputs on the device; q once per (instance, waypoint): the flattened targets' "current posture" and the set's q_ref
-  const double* const d_q = st.up(WS_IN_Q, q, Bz * nq);
-  const double* const d_ft = st.up(WS_IN_FT, frame_targets, R * ft_w);
-  const double* const d_pt = pt_w ? st.up(WS_IN_PT, posture_target, pt_w * (pbat ? R : 1)) : posture_target;
-  const double* const d_ct = ct_w ? st.up(WS_IN_CT, com_target, ct_w * (cbat ? R : 1)) : com_target;
-  const double* const d_w = st.up(WS_IN_W, io->weights, nv);
-  const double* const d_user = st.up(WS_IN_SEEDS, io->seeds, N * nq);       // (the caller's: the one input of this size)
-  double* const d_q0 = st.f64(WS_L_Q0, R * nq);
-  ST_LAUNCH(st, launch_ms_fanout(stream, d_q, d_q0, B, T, (int)nq));
-  // ---- the candidates of one chunk: the loops' velocities (the other rows are multi-start's own buffers of its launch)
-  double* const c_v = st.f64(WS_C_V, chunk * nv);
-  // ---- the nodes, (B·T, K, .): the caller's *_all arrays where they are device buffers
-  double* const l_q = (double*)st.given_or(WS_L_Q, io->q_all, M * nq * f8);
-  double* const l_v = (double*)st.given_or(WS_L_V, io->v_all, M * nv * f8);
-  int32_t* const l_st = (int32_t*)st.given_or(WS_L_ST, io->status_all, M * i4);
-  int32_t* const l_it = (int32_t*)st.given_or(WS_L_IT, io->iters_all, M * i4);
-  int32_t* const l_cv = (int32_t*)st.given_or(WS_L_CV, io->converged_all, M * i4);
-  int32_t* const l_trk = st.i32(WS_L_TRK, M);
-  double* const l_starts = io->seeds_out ? (double*)st.given_or(WS_L_STARTS, io->seeds_out, N * nq * f8) : nullptr;
-  // ---- outputs
-  double *o_q = io->q_traj, *o_v = io->v_traj, *o_qvel = io->qvel, *o_len = io->path_length;
-  int32_t *o_st = io->status, *o_it = io->iters, *o_cv = io->converged;
-  int32_t *o_node = io->node_index, *o_eb = io->edge_break, *o_nt = io->n_tracked, *o_nb = io->n_breaks;
+  const LadderCall c = ladder_stage(st, B, T, S, K, q, frame_targets, posture_target, com_target, tab, io, refine, flags);
+  // ---- the candidates of one chunk, in multi-start's slots: the loops run in place in c_q
+  double *const c_q = st.f64(WS_C_Q, chunk * nq), *const c_v = st.f64(WS_C_V, chunk * nv);
+  int32_t *const c_st = st.i32(WS_C_ST, chunk), *const c_it = st.i32(WS_C_IT, chunk), *const c_cv = st.i32(WS_C_CV, chunk);
+  // ---- the set's outputs per slot and per rung
   int32_t *n_si = nodes->node_seed_index, *n_mu = nodes->node_multiplicity, *n_nd = nodes->n_distinct, *n_nc = nodes->n_converged,
           *n_nu = nodes->n_uncovered, *n_pick = nodes->seed_index;
   double* n_dist = nodes->node_distance;
   if (!devp) {
-    o_q = st.f64(WS_OUT_Q, R * nq); o_v = st.f64(WS_OUT_V, R * nv);
-    o_qvel = io->qvel ? st.f64(WS_OUT_QVEL, R * nv) : nullptr;
-    o_st = st.i32(WS_OUT_I32, 3 * R); o_it = o_st + R; o_cv = o_st + 2 * R;
-    o_node = st.i32(WS_OUT_PICK, 2 * R + 2 * Bz); o_eb = o_node + R; o_nt = o_node + 2 * R; o_nb = o_nt + Bz;
-    o_len = st.f64(WS_OUT_LEN, Bz);
     n_si = st.i32(WS_N_I32, 2 * M + 4 * R); n_mu = n_si + M; n_nd = n_si + 2 * M; n_nc = n_nd + R; n_nu = n_nd + 2 * R; n_pick = n_nd + 3 * R;
     n_dist = st.f64(WS_N_DIST, M);
   }
-  int32_t *o_trk = nullptr, *o_rep = nullptr, *o_ref = nullptr;
-  if (refine) {
-    o_trk = refine->tracked_out; o_rep = refine->repaired; o_ref = refine->refined;
-    if (!devp) { o_trk = st.i32(WS_OUT_REF, 2 * R + Bz); o_rep = o_trk + R; o_ref = o_trk + 2 * R; }
-  }
   if (!st.ok()) return st.finish();
-  // ---- the rungs: multi-start on the (B·T) flattened targets, whole rungs per chunk of at most max_batch loops; behind every
-  // chunk's loops its unwinding, its selection into the chunk's slots of the node arrays, and the slots' flags
-  const int32_t ms_flags = flags | MKH_FLAG_DEVICE_PTRS;
-  const double r2 = min_distance * min_distance;
-  const int njnt = p->model->njnt;
-  for (size_t r0 = 0; r0 < R; r0 += per) {
-    const size_t n = R - r0 < per ? R - r0 : per, i0 = r0 * S, m0 = r0 * K;
-    MkhMultistartIO mio;
-    memset(&mio, 0, sizeof mio);
-    mio.seeds = d_user ? d_user + i0 * nq : nullptr;
-    mio.seeds_out = l_starts ? l_starts + i0 * nq : nullptr;
-    if (const int32_t rc = multistart_core(p, (int32_t)n, d_q0 + r0 * nq, d_ft + r0 * ft_w, (pt_w && pbat) ? d_pt + r0 * pt_w : d_pt,
-                                           (ct_w && cbat) ? d_ct + r0 * ct_w : d_ct, dt, damping, max_iters, pos_threshold,
-                                           ori_threshold, S, rng_seed, target_index0 * T + (int64_t)r0, &mio, ms_flags, hip_stream,
-                                           c_v))
-      return st.finish(rc);
-    // (what that launch wrote: with no *_all array given it uses the candidate slots, sized for its n·S <= chunk rows)
-    double* const c_q = p->ws[WS_C_Q].f64();
-    const int32_t *c_st = p->ws[WS_C_ST].i32(), *c_it = p->ws[WS_C_IT].i32(), *c_cv = p->ws[WS_C_CV].i32();
-    const double* const ref = d_q0 + r0 * nq;
+  // ---- the rungs: multi-start on the (B·T) flattened targets, then the chunk's nodes
+  auto rows_at = [&](size_t r0) {
+    return MsRows{c.l_starts ? c.l_starts + r0 * S * nq : c_q, c_q, c_v, c_st, c_it, c_cv, nullptr};
+  };
+  auto select = [&](size_t r0, size_t n) {
+    const size_t m0 = r0 * K;
+    const double* const ref = c.in.q + r0 * nq;
     if (unwind)
-      ST_LAUNCH(st, launch_unwind_turns(stream, p->ws[WS_UNW].f64(), (long long)(n * S), S, (int)nq, c_q, ref, c_q));
-    const mkh::SsOut so{l_q + m0 * nq, l_v + m0 * nv, l_it + m0, l_st + m0, n_si + m0, n_mu + m0, n_dist + m0,
+      ST_LAUNCH(st, launch_unwind_turns(st.stream, p->ws[WS_UNW].f64(), (long long)(n * S), S, (int)nq, c_q, ref, c_q));
+    const mkh::SsOut so{c.l_q + m0 * nq, c.l_v + m0 * nv, c.l_it + m0, c.l_st + m0, n_si + m0, n_mu + m0, n_dist + m0,
                         n_nd + r0, n_nc + r0, n_nu + r0};
-    ST_LAUNCH(st, launch_ss_select(stream, (int)n, S, K, (int)nq, (int)nv, njnt, p->ws[WS_JNT].i32(), c_q, c_v, c_st, c_it, c_cv, ref,
-                                   d_w, r2, so));
-    ST_LAUNCH(st, launch_ladder_nodes_flags(stream, (long long)n, S, K, c_cv, n_si + m0, l_trk + m0, l_cv + m0));
-  }
-  // ---- the search on the (B, T, K) nodes, and the chosen nodes' rows
-  ladder_search(st, B, T, K, d_q, l_q, l_trk, d_w, io->max_step_sq, o_node, o_nt, o_nb, o_len, o_eb);
-  ST_LAUNCH(st, launch_ladder_gather(stream, l_q, o_q, o_node, (long long)R, K, (int)nq));
-  ST_LAUNCH(st, launch_ladder_gather(stream, l_v, o_v, o_node, (long long)R, K, (int)nv));
-  ST_LAUNCH(st, launch_ladder_gather_i32(stream, l_st, o_st, o_node, (long long)R, K));
-  ST_LAUNCH(st, launch_ladder_gather_i32(stream, l_it, o_it, o_node, (long long)R, K));
-  ST_LAUNCH(st, launch_ladder_gather_i32(stream, l_cv, o_cv, o_node, (long long)R, K));
-  ST_LAUNCH(st, launch_ladder_gather_i32(stream, n_si, n_pick, o_node, (long long)R, K));
-  if (refine) {
-    ST_LAUNCH(st, launch_ladder_gather_i32(stream, l_trk, o_trk, o_node, (long long)R, K));
-    const mkh::LrOut o{o_q, o_v, o_len, o_trk, o_rep, o_ref, o_eb, o_nt, o_nb, o_st, o_it, o_cv};
-    if (const int32_t rc = refine_pass(st, B, T, d_q, o_q, o_trk, d_ft, d_pt, d_ct, dt, damping, max_iters, pos_threshold,
-                                       ori_threshold, d_w, io->max_step_sq, o, flags, hip_stream))
-      return st.finish(rc);
-  }
-  if (o_qvel)
-    ST_LAUNCH(st, launch_tj_qvel(stream, p->ws[WS_JNT].i32(), njnt, B, T, (int)nq, d_q, o_q, (long long)(T * nq), (long long)nq,
-                                 io->waypoint_dt, o_qvel, (long long)(T * nv), (long long)nv, 0));
-  if (devp) return st.finish();
-  st.down(io->q_traj, o_q, R * nq * f8);
-  st.down(io->v_traj, o_v, R * nv * f8);
-  st.down(io->status, o_st, R * i4);
-  st.down(io->iters, o_it, R * i4);
-  st.down(io->converged, o_cv, R * i4);
-  st.down(io->node_index, o_node, R * i4);
-  st.down(io->edge_break, o_eb, R * i4);
-  st.down(io->n_tracked, o_nt, Bz * i4);
-  st.down(io->n_breaks, o_nb, Bz * i4);
-  st.down(io->path_length, o_len, Bz * f8);
-  st.down(io->qvel, o_qvel, R * nv * f8);
-  st.down(io->q_all, l_q, M * nq * f8);
-  st.down(io->v_all, l_v, M * nv * f8);
-  st.down(io->status_all, l_st, M * i4);
-  st.down(io->iters_all, l_it, M * i4);
-  st.down(io->converged_all, l_cv, M * i4);
-  st.down(io->seeds_out, l_starts, N * nq * f8);
-  st.down(nodes->node_seed_index, n_si, M * i4);
-  st.down(nodes->node_multiplicity, n_mu, M * i4);
-  st.down(nodes->node_distance, n_dist, M * f8);
-  st.down(nodes->n_distinct, n_nd, R * i4);
-  st.down(nodes->n_converged, n_nc, R * i4);
-  st.down(nodes->n_uncovered, n_nu, R * i4);
-  st.down(nodes->seed_index, n_pick, R * i4);
-  if (refine) {
-    st.down(refine->tracked_out, o_trk, R * i4);
-    st.down(refine->repaired, o_rep, R * i4);
-    st.down(refine->refined, o_ref, Bz * i4);
-  }
+    ST_LAUNCH(st, launch_ss_select(st.stream, (int)n, S, K, (int)nq, (int)nv, p->model->njnt, p->ws[WS_JNT].i32(), c_q, c_v, c_st, c_it,
+                                   c_cv, ref, c.w, min_distance * min_distance, so));
+    ST_LAUNCH(st, launch_ladder_nodes_flags(st.stream, (long long)n, S, K, c_cv, n_si + m0, c.l_trk + m0, c.l_cv + m0));
+  };
+  if (const int32_t rc = ms_rungs(st, R, S, c.in, ls, rng_seed, target_index0 * T, flags, rows_at, select)) return st.finish(rc);
+  ladder_pick(st, B, T, K, c, io->max_step_sq);
+  ST_LAUNCH(st, launch_ladder_gather_i32(st.stream, n_si, n_pick, c.o_node, (long long)R, K));
+  if (const int32_t rc = ladder_refine_qvel(st, B, T, K, c, ls, io, refine != nullptr, flags)) return st.finish(rc);
+  if (!devp)
+    ladder_down(st, B, T, S, K, c, io, refine, [&] {
+      st.down(nodes->node_seed_index, n_si, M * i4);
+      st.down(nodes->node_multiplicity, n_mu, M * i4);
+      st.down(nodes->node_distance, n_dist, M * f8);
+      st.down(nodes->n_distinct, n_nd, R * i4);
+      st.down(nodes->n_converged, n_nc, R * i4);
+      st.down(nodes->n_uncovered, n_nu, R * i4);
+      st.down(nodes->seed_index, n_pick, R * i4);
+    });
   return st.finish();
 }
 
@@ -2723,12 +2738,7 @@ static void goalset_select(Stager& st, int B, int G, int S, const MkhGoalSetIO& 
   const size_t Bz = B, R = Bz * G, nq = p->dev.nq, nv = p->dev.nv, f8 = sizeof(double), i4 = sizeof(int32_t);
   const bool loops = d_v_all != nullptr;
   const double* const d_cost = st.up(WS_IN_GCOST, io.goal_cost, R);
-  const int32_t* d_gvalid = io.goal_valid;
-  if (!st.devp && io.goal_valid) {
-    int32_t* const t = st.i32(WS_IN_GVALID, R);
-    if (t) st.latch(hipMemcpyAsync(t, io.goal_valid, R * i4, hipMemcpyHostToDevice, st.stream));
-    d_gvalid = t;
-  }
+  const int32_t* const d_gvalid = st.up_i32(WS_IN_GVALID, io.goal_valid, R);
   mkh::GsOut o{io.q_best, loops ? io.v_best : nullptr, loops ? io.iters : nullptr, loops ? io.status : nullptr, io.converged,
                io.goal_index, io.seed_index, io.n_reached, io.score, io.q_goal, loops ? io.v_goal : nullptr,
                loops ? io.iters_goal : nullptr, loops ? io.status_goal : nullptr, io.seed_index_goal, io.reached,
@@ -2778,62 +2788,55 @@ int32_t mkh_solve_goalset(MkhProblem* p, int32_t B, int32_t n_goals, const doubl
                           double pos_threshold, double ori_threshold, int32_t n_seeds, uint64_t rng_seed, int64_t target_index0,
                           const MkhGoalSetIO* io, int32_t flags, void* hip_stream) {
   const char* const who = "mkh_solve_goalset";
+  const LoopSpec ls{dt, damping, max_iters, pos_threshold, ori_threshold};
   if (!p) return fail(MKH_E_INVALID, "null problem");
   const int G = n_goals, S = n_seeds;
   const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
   if (const int32_t rc = goalset_refuse(B, G, S, io, true, devp, who)) return rc;
   if (const int32_t rc = refuse_unwind(flags, who)) return rc;
-  if (max_iters < 1) return fail(MKH_E_INVALID, "max_iters must be >= 1");
-  if (target_index0 < 0) return fail(MKH_E_INVALID, "target_index0 must be >= 0");
-  if (!(pos_threshold >= 0.0) || !(ori_threshold >= 0.0)) return fail(MKH_E_INVALID, "thresholds must be >= 0");
+  if (const int32_t rc = loops_refuse(ls, target_index0, false)) return rc;
   const DeviceProblem& P = p->dev;
   if (const int32_t rc = refuse_inputs(P, q, frame_targets, posture_target, com_target, who, "goal set")) return rc;
   if (S > p->max_batch)
     return fail(MKH_E_INVALID, "%s: n_seeds = %d exceeds max_batch=%d of this problem (a goal is one chunk)", who, S, p->max_batch);
-  const MkhSeedTable* const tab = (!io->seeds && S > 1) ? p->seed_table : nullptr;
-  if (tab)
-    if (const int32_t rc = st_refuse(p, tab, S - 1, who)) return rc;
+  const MkhSeedTable* tab;
+  if (const int32_t rc = seed_table_for(p, io->seeds, S, who, &tab)) return rc;
   HIP_OK(hipSetDevice(p->model->device));
   if (const int32_t rc = ms_build_tables(p)) return rc;
   const bool pbat = (flags & MKH_FLAG_POSTURE_BATCHED) != 0, cbat = (flags & MKH_FLAG_COM_BATCHED) != 0;
   Stager st{p, (hipStream_t)hip_stream, devp, "goalset"};
-  hipStream_t stream = st.stream;
   const size_t Bz = B, R = Bz * G, N = R * S, nq = P.nq, nv = P.nv, f8 = sizeof(double), i4 = sizeof(int32_t);
   const size_t ft_w = (size_t)P.n_frame * 7, pt_w = (size_t)P.n_posture * nq, ct_w = (size_t)P.n_com * 3;
+  const size_t per = (size_t)p->max_batch / S;
   // ---- inputs on the device; q once per (target, goal): the flattened pairs' "current posture"
+  MsIn in;
   const double* const d_q = st.up(WS_IN_Q, q, Bz * nq);
-  const double* const d_ft = st.up(WS_IN_FT, frame_targets, R * ft_w);
-  const double* const d_pt = pt_w ? st.up(WS_IN_PT, posture_target, pt_w * (pbat ? R : 1)) : posture_target;
-  const double* const d_ct = ct_w ? st.up(WS_IN_CT, com_target, ct_w * (cbat ? R : 1)) : com_target;
+  in.ft = st.up(WS_IN_FT, frame_targets, R * ft_w);
+  in.pt = pt_w ? st.up(WS_IN_PT, posture_target, pt_w * (pbat ? R : 1)) : posture_target;
+  in.ct = ct_w ? st.up(WS_IN_CT, com_target, ct_w * (cbat ? R : 1)) : com_target;
   const double* const d_ref = st.up(WS_IN_REF, io->q_ref, Bz * nq);
   const double* const d_w = st.up(WS_IN_W, io->weights, nv);
-  const double* const d_user = st.up(WS_IN_SEEDS, io->seeds, N * nq);
+  in.user = st.up(WS_IN_SEEDS, io->seeds, N * nq);
+  in.tab = tab;
   double* const d_q0 = st.f64(WS_L_Q0, R * nq);
-  ST_LAUNCH(st, launch_ms_fanout(stream, d_q, d_q0, B, G, (int)nq));
-  // ---- the candidates' rows, in the ladder's node slots: the caller's *_all arrays where they are device buffers
+  ST_LAUNCH(st, launch_ms_fanout(st.stream, d_q, d_q0, B, G, (int)nq));
+  in.q = d_q0;
+  // ---- the candidates' rows, in the ladder's node slots: the caller's *_all arrays where they are device buffers (without the
+  // caller's seeds_out the starts of one chunk go through multi-start's candidate slot)
   double* const l_q = (double*)st.given_or(WS_L_Q, io->q_all, N * nq * f8);
   double* const l_v = st.f64(WS_L_V, N * nv);
   int32_t* const l_st = (int32_t*)st.given_or(WS_L_ST, io->status_all, N * i4);
   int32_t* const l_it = (int32_t*)st.given_or(WS_L_IT, io->iters_all, N * i4);
   int32_t* const l_cv = (int32_t*)st.given_or(WS_L_CV, io->converged_all, N * i4);
   double* const l_starts = io->seeds_out ? (double*)st.given_or(WS_L_STARTS, io->seeds_out, N * nq * f8) : nullptr;
+  double* const c_q = l_starts ? nullptr : st.f64(WS_C_Q, (per < R ? per : R) * S * nq);
   if (!st.ok()) return st.finish();
-  // ---- the loops: multi-start on the (B·G) flattened pairs, whole goals per chunk of at most max_batch loops
-  const size_t per = (size_t)p->max_batch / S;
-  const int32_t ms_flags = flags | MKH_FLAG_DEVICE_PTRS;
-  for (size_t r0 = 0; r0 < R; r0 += per) {
-    const size_t n = R - r0 < per ? R - r0 : per, i0 = r0 * S;
-    MkhMultistartIO mio;
-    memset(&mio, 0, sizeof mio);
-    mio.seeds = d_user ? d_user + i0 * nq : nullptr;
-    mio.q_all = l_q + i0 * nq; mio.status_all = l_st + i0; mio.iters_all = l_it + i0; mio.converged_all = l_cv + i0;
-    mio.seeds_out = l_starts ? l_starts + i0 * nq : nullptr;
-    if (const int32_t rc = multistart_core(p, (int32_t)n, d_q0 + r0 * nq, d_ft + r0 * ft_w, (pt_w && pbat) ? d_pt + r0 * pt_w : d_pt,
-                                           (ct_w && cbat) ? d_ct + r0 * ct_w : d_ct, dt, damping, max_iters, pos_threshold,
-                                           ori_threshold, S, rng_seed, target_index0 * G + (int64_t)r0, &mio, ms_flags, hip_stream,
-                                           l_v + i0 * nv))
-      return st.finish(rc);
-  }
+  // ---- the loops: multi-start on the (B·G) flattened pairs
+  auto rows_at = [&](size_t r0) {
+    const size_t i0 = r0 * S;
+    return MsRows{l_starts ? l_starts + i0 * nq : c_q, l_q + i0 * nq, l_v + i0 * nv, l_st + i0, l_it + i0, l_cv + i0, nullptr};
+  };
+  if (const int32_t rc = ms_rungs(st, R, S, in, ls, rng_seed, target_index0 * G, flags, rows_at)) return st.finish(rc);
   // ---- the two levels
   goalset_select(st, B, G, S, *io, l_q, l_v, l_st, l_it, l_cv, d_ref ? d_ref : d_q, d_w);
   if (devp) return st.finish();
@@ -2860,12 +2863,7 @@ int32_t mkh_select_goalset(MkhProblem* p, int32_t B, int32_t G, int32_t S, const
   const double* const d_cand = st.up(WS_L_Q, q_candidates, N * nq);
   const double* const d_ref = st.up(WS_IN_REF, q_ref, Bz * nq);
   const double* const d_w = st.up(WS_IN_W, weights, p->dev.nv);
-  const int32_t* d_valid = valid;
-  if (!devp && valid) {
-    int32_t* const t = st.i32(WS_L_CV, N);
-    if (t) st.latch(hipMemcpyAsync(t, valid, N * sizeof(int32_t), hipMemcpyHostToDevice, st.stream));
-    d_valid = t;
-  }
+  const int32_t* const d_valid = st.up_i32(WS_L_CV, valid, N);
   if (!st.ok()) return st.finish();
   goalset_select(st, B, G, S, *io, d_cand, nullptr, nullptr, nullptr, d_valid, d_ref, d_w);
   return st.finish();

@@ -1,7 +1,10 @@
 // Launchers of the small kernels around the loop launches of the outer-loop entry points (mkh_solve_multistart,
 // mkh_solve_multistart_set, mkh_solve_goalset, mkh_solve_trajectory, mkh_solve_keyframes, mkh_solve_trajectory_multistart, the ladder calls) and of
 // the seed tables in front of them: declared once, for the eleven files that define them and for minkhip.hip, which calls them — a signature that
-// drifts fails to compile in the file that drifted.
+// drifts fails to compile in the file that drifted.  In minkhip.hip the multi-start calls, the ladder calls and the goal set
+// launch the seeding, the seed-table query and the target fan-out from one place, the loop stage ms_loops(), which also asks for
+// their workspace slots (WS_C_FT / PT / CT, the WS_IN_SEEDS slab); mkh_solve_trajectory_multistart has its own (time-major) ones.
+// Every other launcher below is called by the entry point that asked for the slots it reads and writes.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
