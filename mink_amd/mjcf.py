@@ -434,11 +434,10 @@ def load_mjcf(path: str) -> FlatModel:
             B["mass"][body_id] = mt
             if mt > mjMINVAL:
                 B["ipos"][body_id] = sum(m * p for m, p in parts) / mt
-        for ch in el:
-            if ch.tag == "body":
-                visit_body(ch, body_id, childclass)
+        return [(ch, body_id, childclass) for ch in el if ch.tag == "body"]
 
     def visit_body(el, parent_id, childclass):
+        """One body; returns its child bodies as (element, parent id, childclass), in document order."""
         childclass = el.get("childclass", childclass)
         body_id = len(B["parent"])
         B["parent"].append(parent_id)
@@ -449,7 +448,14 @@ def load_mjcf(path: str) -> FlatModel:
         B["name"].append(el.get("name", ""))
         B["jntnum"].append(0); B["jntadr"].append(-1)
         B["geomnum"].append(0); B["geomadr"].append(-1)
-        visit_body_children(el, body_id, childclass)
+        return visit_body_children(el, body_id, childclass)
+
+    def visit_subtree(el, parent_id, childclass):
+        # depth first in document order on an explicit stack: a serial chain nests one level per link, and the models of the
+        # workgroup-per-problem kernel (hundreds of links) are deeper than the interpreter's recursion limit
+        stack = [(el, parent_id, childclass)]
+        while stack:
+            stack.extend(reversed(visit_body(*stack.pop())))
 
     # multiple <worldbody> sections concatenate in document order.  World-level
     # geoms/sites belong to body 0; MuJoCo numbers a body's geoms contiguously, so
@@ -470,7 +476,7 @@ def load_mjcf(path: str) -> FlatModel:
     for wb in worldbodies:
         for ch in wb:
             if ch.tag == "body":
-                visit_body(ch, 0, wb.get("childclass"))
+                visit_subtree(ch, 0, wb.get("childclass"))
 
     nbody, njnt = len(B["parent"]), len(J["type"])
     from .flatmodel import dof_width, qpos_width

@@ -3,7 +3,15 @@
 // line — among them lists of 2 to 4 limits of each kind (and 5: refused) whose terms have their own gain, bounds and index subset,
 // printed with every copy of the per-dof tables the plan makes of them.  Built with the host sanitizers by the test and run as a
 // child process.
+//
+// With a file name as its argument the program also plans the models that file describes — the large models of tests/wide_cases.py,
+// taken from the same MJCF text the device tests load: one line each,
+//   name  spheres(0/1)  n  (parent kind)·n  n_tasks  body·n_tasks  n_com  n_pairs  (geom geom)·n_pairs
+// planned once (case `wide`: six-row frame tasks on the given bodies, a posture task, ConfigurationLimit, VelocityLimit, the pairs
+// in one CollisionAvoidanceLimit) and printed with the chain bit table of every body.
 #include <cstdio>
+#include <fstream>
+#include <sstream>
 #include <string>
 #include <vector>
 
@@ -13,7 +21,7 @@ using namespace mkh;
 
 namespace {
 
-enum Kind { FIXED = 0, HINGE = 1, HINGE2 = 2, BALL = 3, FREE = 4 };
+enum Kind { FIXED = 0, HINGE = 1, HINGE2 = 2, BALL = 3, FREE = 4, SLIDE = 5 };
 struct BodySpec { int parent; int kind; };
 
 // A flat model and the arrays it points to.
@@ -30,7 +38,7 @@ struct Model {
   MkhFlatModel flat{};
 };
 
-void make_model(Model& M, const std::string& name, const std::vector<BodySpec>& spec) {
+void make_model(Model& M, const std::string& name, const std::vector<BodySpec>& spec, bool spheres = false) {
   M.name = name;
   const int nb = (int)spec.size() + 1;
   M.body_parentid.assign(nb, 0); M.body_rootid.assign(nb, 0); M.body_jntnum.assign(nb, 0); M.body_jntadr.assign(nb, -1);
@@ -52,11 +60,11 @@ void make_model(Model& M, const std::string& name, const std::vector<BodySpec>& 
     if (nj) { M.body_jntadr[b] = (int)M.jnt_type.size(); M.body_dofadr[b] = nv; }
     M.body_jntnum[b] = nj;
     for (int i = 0; i < nj; ++i) {
-      const int jt = s.kind == FREE ? JNT_FREE : (s.kind == BALL ? JNT_BALL : JNT_HINGE);
+      const int jt = s.kind == FREE ? JNT_FREE : (s.kind == BALL ? JNT_BALL : (s.kind == SLIDE ? JNT_SLIDE : JNT_HINGE));
       const int ndof = jt == JNT_FREE ? 6 : (jt == JNT_BALL ? 3 : 1), nqj = jt == JNT_FREE ? 7 : (jt == JNT_BALL ? 4 : 1);
       const int j = (int)M.jnt_type.size();
       M.jnt_type.push_back(jt); M.jnt_qposadr.push_back(nq); M.jnt_dofadr.push_back(nv); M.jnt_bodyid.push_back(b);
-      M.jnt_limited.push_back(jt == JNT_HINGE ? 1 : 0);
+      M.jnt_limited.push_back(jt == JNT_HINGE || jt == JNT_SLIDE ? 1 : 0);
       for (int k = 0; k < 3; ++k) { M.jnt_pos.push_back(0.0); M.jnt_axis.push_back(k == (j % 3) ? 1.0 : 0.0); }
       M.jnt_range.push_back(-2.0); M.jnt_range.push_back(2.0);
       for (int k = 0; k < nqj; ++k) M.qpos0.push_back((jt == JNT_FREE && k == 3) || (jt == JNT_BALL && k == 0) ? 1.0 : 0.0);
@@ -74,7 +82,7 @@ void make_model(Model& M, const std::string& name, const std::vector<BodySpec>& 
     if (!has_child[b]) M.leaves.insert(M.leaves.begin(), b);
   }
   // one capsule per moving body, then a cylinder on the last body and a box on the first; one site on the last body
-  for (int b = 1; b < nb; ++b) { M.geom_bodyid.push_back(b); M.geom_type.push_back(PLAN_GEOM_CAPSULE); }
+  for (int b = 1; b < nb; ++b) { M.geom_bodyid.push_back(b); M.geom_type.push_back(spheres ? PLAN_GEOM_SPHERE : PLAN_GEOM_CAPSULE); }
   M.cyl_geom = (int)M.geom_type.size(); M.geom_bodyid.push_back(nb - 1); M.geom_type.push_back(PLAN_GEOM_CYLINDER);
   M.box_geom = (int)M.geom_type.size(); M.geom_bodyid.push_back(1); M.geom_type.push_back(PLAN_GEOM_BOX);
   const int ng = (int)M.geom_type.size();
@@ -118,6 +126,8 @@ struct Case {
   int n_com = 0, n_pairs = 0, n_boxpairs = 0;
   bool cylbox = false, dense = false;
   int diag = 0, bad = BAD_NONE;
+  std::vector<int32_t> pair_list;                 // explicit geom pairs (a, b, a, b, …) in front of the counted ones
+  bool print_chain = false;
   // lists of limits (n_cfg >= 0): that many ConfigurationLimits / VelocityLimits, each with its own gain, bounds and index subset,
   // two PostureTasks, and the capsule pairs split over n_col CollisionAvoidanceLimits with their own parameters
   int n_cfg = -1, n_vel = 1, n_col = 1;
@@ -250,7 +260,7 @@ void run_case(const Model& M, const HostModel& hm, const Case& cs) {
     vls.push_back({(int32_t)all_dofs.size(), all_dofs.data(), vmax.data()});
   }
   // capsule pairs: the capsule of the last body against those of the first ones (cycling), then the cylinder against the box
-  std::vector<int32_t> gp;
+  std::vector<int32_t> gp = cs.pair_list;
   for (int k = 0; k < cs.n_pairs; ++k) { gp.push_back(nb - 2); gp.push_back(k % (nb - 2)); }
   for (int k = 0; k < cs.n_boxpairs; ++k) { gp.push_back(nb - 2 - k % (nb - 2)); gp.push_back(M.box_geom); }   // capsules against the box
   if (cs.cylbox) { gp.push_back(M.cyl_geom); gp.push_back(M.box_geom); }
@@ -278,7 +288,8 @@ void run_case(const Model& M, const HostModel& hm, const Case& cs) {
 
   printf("{");
   put_str("model", M.name); put_str("case", cs.name);
-  put("nv", nv); put("nq", nq); put("nbody", nb); put("big", hm.big);
+  put("nv", nv); put("nq", nq); put("nbody", nb); put("njnt", hm.njnt); put("big", hm.big);
+  if (cs.print_chain) { put("model_chain_words", hm.chain_words); put_u64("chain", hm.chain.data(), hm.chain.size()); }
   put_arr("body_parentid", hm.body_parentid.data(), nb); put_arr("body_dofadr", hm.body_dofadr.data(), nb);
   put_arr("body_dofnum", hm.body_dofnum.data(), nb);
   printf("\"tasks\":[");
@@ -366,7 +377,12 @@ void run_case(const Model& M, const HostModel& hm, const Case& cs) {
     put("built", plan.wide.built); put("nv", W.nv); put("chain_words", W.chain_words); put("nlevels", W.nlevels);
     put("max_rows", W.max_rows); put("n_jrows", W.n_jrows); put("n_rows_tap", W.n_rows_tap); put("lds_doubles", W.lds_doubles);
     put("tableau_in_lds", W.tableau_in_lds); put("ws_stride", W.ws_stride); put("ws_doubles", plan.wide.ws_doubles);
-    put("redo_cap", plan.wide.redo_cap); put("use_cull", plan.wide.use_cull, false);
+    put("redo_cap", plan.wide.redo_cap); put("use_cull", plan.wide.use_cull);
+    // the staging vectors of the block pivots: over the poses (overlay), behind the QP vectors (appended), or none (absent)
+    put("o_X", W.o_X); put("o_blk", W.o_blk); put("blk_stride", W.blk_stride); put("t_lds_doubles", W.t_lds_doubles);
+    put("n_frame", W.n_frame); put("n_pairs", W.n_pairs); put("gi_in_lds", W.gi_in_lds);
+    put_str("blk", !plan.wide.built ? "" : (W.o_blk < 0 ? "absent" : (W.o_blk == W.o_X ? "overlay" : "appended")));
+    put("o_T", W.o_T, false);
     printf("},");
     put("n_cv", plan.n_cv); put_arr("cv_pair", plan.cv_pair.data(), plan.cv_pair.size());
     put_arr("cv_adr", plan.cv_adr.data(), plan.cv_adr.size()); put_arr("cv_chain", plan.cv_chain.data(), plan.cv_chain.size());
@@ -409,7 +425,43 @@ std::vector<TaskSpec> on_leaves(const Model& M, const std::vector<int>& rows) {
 
 }  // namespace
 
-int main() {
+// the models of a description file (see the head of this file), each planned once
+int run_file(const char* path) {
+  std::ifstream in(path);
+  if (!in) { fprintf(stderr, "cannot read %s\n", path); return 1; }
+  std::string line;
+  while (std::getline(in, line)) {
+    if (line.empty()) continue;
+    std::istringstream ss(line);
+    std::string name;
+    int spheres = 0, n = 0, nt = 0, np = 0;
+    ss >> name >> spheres >> n;
+    std::vector<BodySpec> spec(n);
+    for (BodySpec& b : spec) ss >> b.parent >> b.kind;
+    Case c;
+    c.name = "wide"; c.print_chain = true;
+    ss >> nt;
+    for (int t = 0; t < nt; ++t) { int body = 0; ss >> body; c.tasks.push_back({body, -1, 6}); }
+    ss >> c.n_com >> np;
+    c.pair_list.resize(2 * (size_t)np);
+    for (int32_t& g : c.pair_list) ss >> g;
+    if (!ss) { fprintf(stderr, "%s: malformed line for %s\n", path, name.c_str()); return 1; }
+    for (int b = 0; b < n; ++b)
+      if (spec[b].parent < 0 || spec[b].parent > b || spec[b].kind < FIXED || spec[b].kind > SLIDE) { fprintf(stderr, "%s: bad body %d\n", name.c_str(), b + 1); return 1; }
+    for (const TaskSpec& t : c.tasks) if (t.body < 1 || t.body > n) { fprintf(stderr, "%s: bad task body\n", name.c_str()); return 1; }
+    for (int32_t g : c.pair_list) if (g < 0 || g >= n) { fprintf(stderr, "%s: bad geom\n", name.c_str()); return 1; }
+    Model M;
+    make_model(M, name, spec, spheres != 0);
+    HostModel hm;
+    std::string err;
+    if (plan_model(&M.flat, hm, err) != MKH_OK) { fprintf(stderr, "%s: %s\n", name.c_str(), err.c_str()); return 1; }
+    run_case(M, hm, c);
+  }
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1) return run_file(argv[1]);
   struct Entry { const char* name; std::vector<BodySpec> spec; };
   const std::vector<Entry> models = {
       {"chain6", chain(6)}, {"chain16", chain(16)}, {"chain17", chain(17)}, {"chain44", chain(44)}, {"chain63", chain(63)},

@@ -153,6 +153,41 @@ def ball_chain_mjcf(n_ball=18, n_hinge=8, seed=0, limited_every=4, n_sites=3):
     return "\n".join(lines), sites
 
 
+def ball_chain_kinds(n_ball=18, n_hinge=8, seed=0):
+    """The joint kind of every link of ball_chain_mjcf, root to tip (the generator's first draw: the shuffle)."""
+    rng = np.random.default_rng(seed)
+    kinds = ["ball"] * n_ball + ["hinge"] * n_hinge
+    rng.shuffle(kinds)
+    return kinds
+
+
+def fixed_chain_mjcf(n_links, n_fixed=2, seed=0):
+    """A serial chain of `n_links` hinges in which every link carries `n_fixed` jointless bodies in front of the next link
+    (leaves, in the model's depth-first body order between a link and its child): 1 + n_links·(1 + n_fixed) bodies with the
+    world on n_links dofs.  Sites `mid` and `tip` sit on the LAST jointless body of links n_links // 2 and n_links − 1
+    (on the link itself with n_fixed = 0, at the same place: the jointless bodies are not rotated), so the kinematics of the
+    sites does not depend on n_fixed.  Offsets are multiples of 0.01 whose sums are exact."""
+    rng = np.random.default_rng(seed)
+    xml = ['<mujoco><compiler angle="radian"/><worldbody>']
+    for i in range(n_links):
+        ax = rng.normal(size=3)
+        ax /= np.linalg.norm(ax)
+        xml.append(f'<body name="b{i}" pos="{0.03 + 0.02 * rng.uniform():.4f} {0.01 * rng.normal():.4f} {0.01 * rng.normal():.4f}">'
+                   f'<inertial pos="0 0 0" mass="0.1" diaginertia="1 1 1"/>'
+                   f'<joint name="j{i}" type="hinge" axis="{ax[0]:.5f} {ax[1]:.5f} {ax[2]:.5f}" range="-1.5 1.5"/>')
+        name = "mid" if i == n_links // 2 else ("tip" if i == n_links - 1 else None)
+        for k in range(n_fixed):
+            xml.append(f'<body name="f{i}_{k}" pos="0.01 0.02 0"><inertial pos="0 0 0" mass="0.05" diaginertia="1 1 1"/>')
+            if name and k == n_fixed - 1:
+                xml.append(f'<site name="{name}" pos="0.01 0 0.03"/>')
+            xml.append('</body>')
+        if name and n_fixed == 0:
+            xml.append(f'<site name="{name}" pos="0.02 0.02 0.03"/>')
+    xml.append("</body>" * n_links)
+    xml.append("</worldbody></mujoco>")
+    return "".join(xml), ["mid", "tip"]
+
+
 def hinge_chain_mjcf(n_links, seed=0):
     """A serial chain of `n_links` hinges about random axes (range ±1.5) with a site `tip` on the last link: nv = n_links,
     n_links + 1 bodies with the world — the sizes around the one-wavefront limit of 64."""

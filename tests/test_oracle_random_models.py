@@ -8,6 +8,7 @@ from mink_amd.mjcf import loads_mjcf
 from oracle import cport
 from oracle import ik as oik
 from random_models import rand_q, random_mjcf
+import wide_cases as wc
 
 
 @pytest.mark.parametrize("seed", range(8))
@@ -40,3 +41,41 @@ def test_c_vs_numpy_on_random_tree(seed):
         np.testing.assert_allclose(H_c, P, rtol=0, atol=1e-12 * max(1.0, np.abs(P).max()))
         np.testing.assert_allclose(c_c, c, rtol=0, atol=1e-12 * max(1.0, np.abs(c).max()))
         np.testing.assert_allclose(v_c, v_np, rtol=0, atol=1e-9 * max(1.0, np.abs(v_np).max()))
+
+
+@pytest.mark.parametrize("seed", wc.TREE_SEEDS)
+def test_c_vs_numpy_on_trees_past_one_wavefront(seed):
+    """The six trees of tests/test_gpu_wide_sizes.py::test_random_tree_past_one_wavefront (66 … 120 bodies, every joint kind,
+    the draw of test_random_tree): the reference is pinned before the device is held to it.  Every instance solves on the C
+    oracle, two agree with the numpy oracle in H, c and v, and v does not move under one-ulp changes of H and c — all within
+    1 % of the device's tolerance 1e-8·max(1, ‖v‖∞)."""
+    from test_wide_cases_cpu import ONE_PERCENT, one_ulp_sensitivity
+    T = wc.random_tree(seed)
+    m = T["m"]
+    assert m.nbody - 1 == T["nbody"] > 64 and len(T["q"]) == 16
+    v_c, st_c = wc.tree_c_oracle(T)
+    assert (st_c == 0).all(), np.unique(st_c, return_counts=True)
+    agree = moved = 0.0
+    for i in (0, 15):
+        ts, ls = wc.tree_specs(T, i)
+        v_np, (P, c, G, h) = oik.solve_ik(m, T["q"][i], ts, T["dt"], T["damping"], ls, return_problem=True)
+        _, (H_c, c_c) = cport.CProblem(m, ts, ls).solve(T["q"][i], T["dt"], T["damping"], return_problem=True)
+        np.testing.assert_allclose(H_c, P, rtol=0, atol=1e-12 * max(1.0, np.abs(P).max()))
+        np.testing.assert_allclose(c_c, c, rtol=0, atol=1e-12 * max(1.0, np.abs(c).max()))
+        sc = max(1.0, np.abs(v_np).max())
+        agree = max(agree, np.abs(v_c[i] - v_np).max() / sc)
+        moved = max(moved, one_ulp_sensitivity(P, c, G, h, T["dt"], sc))
+    print("tree %d: nbody %d nv %d, %d frame tasks, ComTask %s: oracles agree %.1e, one-ulp sensitivity %.1e"
+          % (seed, m.nbody, m.nv, len(T["frames"]), T["com"] is not None, agree, moved))
+    assert agree <= ONE_PERCENT and moved <= ONE_PERCENT
+
+
+def test_the_six_trees_cover_what_they_were_picked_for():
+    props = {seed: wc.tree_properties(wc.random_tree(seed)["m"]) for seed in wc.TREE_SEEDS}
+    for key in ("ball_below_branch", "two_joints", "jointless", "nv_gt_128", "slide_next_to_ball"):
+        assert any(p[key] for p in props.values()), key
+    trees = [wc.random_tree(seed) for seed in wc.TREE_SEEDS]
+    assert len(trees) == 6 and all(T["m"].nbody > 64 or T["m"].nv > 64 for T in trees)
+    assert sum(T["com"] is not None for T in trees) >= 2 and any(T["com"] is None for T in trees)
+    assert {typ for T in trees for _, typ, _, _, _ in T["frames"]} == {"site", "body"}
+    assert any((cost == 0).any() for T in trees for _, _, cost, _, _ in T["frames"])

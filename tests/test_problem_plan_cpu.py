@@ -10,6 +10,11 @@ Lists of limits (the `lim_*` cases): 2 to 4 ConfigurationLimits and VelocityLimi
 a geom pair.  Every entry of every copy the plan makes — lane tables at stride 64, LaneProblem2 and its narrowed LaneProblem,
 the wide arrays at stride nv, the parameters per pair — is recomputed from the descriptor and compared exactly; five limits of a
 kind are refused with MKH_E_LIMIT and the cap in the text.
+
+The large models of tests/wide_cases.py (the `wide` cases; the program reads them from a file this test writes from the same MJCF
+text the device tests load): the layout of the workgroup-per-problem kernel is recomputed here from the model's counts
+(`wide_layout`, which shares no code with plan_wide), the chain bit table from the parent arrays, and each model is held to the
+branch it was chosen for — the device tests of tests/test_gpu_wide_sizes.py run exactly these models.
 """
 
 import json
@@ -19,6 +24,8 @@ import subprocess
 
 import numpy as np
 import pytest
+
+import wide_cases as wc
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, "mink_amd", "csrc")
@@ -49,6 +56,13 @@ def plans(tmp_path_factory):
     assert r.returncode == 0, r.stderr[-4000:]
     assert r.stderr == "", r.stderr[-4000:]             # the sanitized run: nothing reported
     rows = [json.loads(line) for line in r.stdout.splitlines()]
+    # the large models of tests/wide_cases.py, from a description file
+    spec = d / "wide_models.txt"
+    spec.write_text("".join(wc.spec_line(name) + "\n" for name in wc.HOST_MODELS))
+    r = subprocess.run([exe, str(spec)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+    assert r.stderr == "", r.stderr[-4000:]
+    rows += [json.loads(line) for line in r.stdout.splitlines()]
     return {(c["model"], c["case"]): c for c in rows}
 
 
@@ -77,8 +91,13 @@ def tables_in_effect(c):
 
 def test_every_case_planned(plans):
     assert len(plans) > 200
-    models = {m for m, _ in plans}
+    wide = {m for m, case in plans if case == "wide"}
+    assert wide == set(wc.HOST_MODELS) and len(wide) == 11
+    models = {m for m, _ in plans} - wide
     assert models == {"chain6", "chain16", "chain17", "chain44", "chain63", "chain64", "tree44", "tree62", "ball11", "chain68"}
+    assert {m: plans[(m, "wide")]["nv"] for m in wide} == {
+        "chain123": 123, "chain124": 124, "chain130": 130, "chain300": 300, "chain_last": wc.CHAIN_LAST, "chain_last+1": wc.CHAIN_LAST + 1,
+        "ball80": 80, "ball86": 86, "ball92": 92, "fixed30": 30, "hinge80": 80}
     assert {plans[(m, "t1_r6")]["nv"] for m in models} == {6, 16, 17, 44, 63, 64, 62, 11, 68}
     # enough of them take the low-rank start for the table checks below to mean something
     assert sum(1 for c in ok_cases(plans) if tables_in_effect(c)) >= 40
@@ -214,7 +233,8 @@ def test_kernel_families(plans):
         s, key = c["sel"], (c["model"], c["case"])
         rows = c["n_pairs_in"]
         if c["big"]:
-            assert s["wide_only"] == 1 and c["wide"]["built"] == 1 and c["wide"]["chain_words"] == 2 and c["lane"]["cls"] == 0, key
+            assert s["wide_only"] == 1 and c["wide"]["built"] == 1 and c["wide"]["chain_words"] == (c["nv"] + 63) // 64 and c["lane"]["cls"] == 0, key
+            assert c["wide"]["chain_words"] == 2 or c["case"] == "wide", key
             continue
         assert s["wide_only"] == 0 and c["wide"]["built"] == (1 if rows else 0), key
         assert c["dev"]["n_pairs"] == rows and c["dev"]["max_rows"] == min(rows, 64 - c["nv"]), key
@@ -393,6 +413,126 @@ def test_refused_descriptors(plans):
                                                "(one value per ball joint, as the reference's constructor writes its range)")
         elif case == "bad_free_limit":
             assert (c["rc"], c["err"]) == (-1, "configuration limit on free-joint dof 0 (the reference skips free joints)")
+        elif m == "chain_last+1":
+            # MKH_E_LIMIT, and the text carries the LDS figure (test_wide_models_plan_their_branch)
+            assert c["rc"] == -4 and c["err"].startswith("model too large for the workgroup-per-problem kernel: "), c["err"]
         else:
             assert c["rc"] == 0, (m, case, c["err"])
     assert ("tree44", "bad_free_limit") in plans and ("tree62", "bad_free_limit") in plans and ("ball11", "bad_ball_slots") in plans
+
+
+# ---- the large models of tests/wide_cases.py on the workgroup-per-problem kernel
+
+KWIDE_THREADS, KWIDE_MAX_ROWS = 256, 448           # wide_types.h kWideThreads, kWideMaxRows
+LDS_CAP, TWO_WG = (160 * 1024 - 2048) // 8, 80 * 1024 // 8     # doubles one workgroup may take / that leave room for a second one
+
+
+def wide_layout(nq, nbody, njnt, nv, n_frame, n_com, n_jrows, n_pairs):
+    """LDS of one problem in doubles, as DESIGN.md §8 describes it (no general convex pairs, no caller-defined rows): the
+    per-problem state, the staging vectors of the block pivots, the dense fallback's factors, the tableau.
+    → dict(blk, tableau_in_lds, t_lds_doubles, lds_doubles); lds_doubles > LDS_CAP: refused."""
+    ev = lambda x: x + (x & 1)
+    ncap = nv + min(n_pairs, KWIDE_MAX_ROWS)
+    poses = ev(7 * nbody) + ev(6 * max(njnt, 1))               # body poses + joint axes / anchors: free again once the dofs have theirs
+    state = ev(nq) + poses + 10 * nv + 64 * max(n_frame, 1) + (4 * nbody if n_com else 0) + ev(max(n_jrows, 1))
+    state += 4 * ev(nv) + 5 * ev(ncap)                         # c, posture diagonal, lo, hi | z, w, row norms, reference, column
+    state += KWIDE_THREADS + KWIDE_THREADS // 2 + ev((ncap + 1) // 2)
+    t = ncap * ncap
+    stage = 8 * ev(ncap)
+    total = lambda o: o + (t if o + t <= LDS_CAP else 0)
+    if stage <= poses:
+        blk = "overlay"
+    elif (state + stage <= LDS_CAP and (state + stage + t <= LDS_CAP) == (state + t <= LDS_CAP)
+          and (total(state + stage) <= TWO_WG) == (total(state) <= TWO_WG)):
+        blk = "appended"
+        state += stage
+    else:
+        blk = "absent"
+    in_lds = state + t <= LDS_CAP
+    if n_pairs:
+        gi = 2 * nv * (nv | 1) + 4 * (nv + 2)
+        if state + gi + (nv + 8) ** 2 <= TWO_WG:
+            state += gi
+    if in_lds:
+        t_lds = t
+    else:
+        room = TWO_WG - state
+        if room < (nv + 8) ** 2:
+            room = LDS_CAP - state
+        t_lds = max(room, 0)
+    return {"blk": blk, "tableau_in_lds": int(in_lds), "t_lds_doubles": t_lds, "lds_doubles": state + t_lds}
+
+
+def _wide_counts(c):
+    return dict(nq=c["nq"], nbody=c["nbody"], njnt=c["njnt"], nv=c["nv"], n_frame=len(c["tasks"]), n_com=c["n_com"],
+                n_jrows=sum(len(r) for r in task_rows(c)) + c["com_rows"], n_pairs=c["n_pairs_in"])
+
+
+def test_wide_layout_recomputed(plans):
+    """chain_words, the LDS total and the three layout decisions of EVERY planned model beyond one wavefront (the fixed set's
+    chain68 among them), recomputed from the model's counts."""
+    seen = 0
+    for c in ok_cases(plans, wavefront=False):
+        if not c["big"] or c["dense"] or c["cylbox"]:
+            continue
+        w, want = c["wide"], wide_layout(**_wide_counts(c))
+        key = (c["model"], c["case"])
+        assert w["chain_words"] == -(-c["nv"] // 64), key
+        assert {k: w[k] for k in want} == want, (key, want, {k: w[k] for k in want})
+        assert want["lds_doubles"] <= LDS_CAP and c["sel"]["wide_lds"] == 8 * want["lds_doubles"], key
+        seen += 1
+    assert seen >= 20 + len(wc.HOST_MODELS) - 1             # (chain68: every case without plugin rows or convex pairs)
+
+
+def test_wide_chain_bit_table(plans):
+    """The chain bit table of the large models — word k >> 6, bit k & 63 of body b: dof k moves b — from the parent arrays."""
+    for name in wc.HOST_MODELS:
+        c = plans[(name, "wide")]
+        nw = c["model_chain_words"]
+        assert nw == -(-c["nv"] // 64) and len(c["chain"]) == c["nbody"] * nw, name
+        for b in range(c["nbody"]):
+            mask = sum(1 << k for k in chain_of(c, b))
+            assert [int(x) for x in c["chain"][b * nw:(b + 1) * nw]] == [(mask >> (64 * i)) & (2 ** 64 - 1) for i in range(nw)], (name, b)
+    # the models are the device tests': parent arrays and dof counts of the MJCF text itself
+    for name in wc.HOST_MODELS:
+        m, c = wc.model(name), plans[(name, "wide")]
+        assert (m.nq, m.nv, m.nbody, m.njnt) == (c["nq"], c["nv"], c["nbody"], c["njnt"]), name
+        assert [int(x) for x in m.body_parentid] == c["body_parentid"] and [int(x) for x in m.body_dofnum] == c["body_dofnum"], name
+        assert len(c["tasks"]) == len(wc.mjcf_text(name)[1]) <= 16, name
+
+
+def test_wide_models_plan_their_branch(plans):
+    """Each model of tests/wide_cases.py plans the branch it was chosen for (the sizes were found by sweeping this program)."""
+    W = {name: plans[(name, "wide")] for name in wc.HOST_MODELS}
+    for name, c in W.items():
+        if name != "chain_last+1":
+            w = c["wide"]
+            print("%-10s nv %3d nbody %3d: tableau_in_lds %d, chain_words %d, staging %-8s, %6d doubles of LDS (tableau %5d), "
+                  "ws_stride %d, use_cull %d" % (name, c["nv"], c["nbody"], w["tableau_in_lds"], w["chain_words"], w["blk"], w["lds_doubles"],
+                                                 w["t_lds_doubles"], w["ws_stride"], w["use_cull"]))
+            assert c["rc"] == 0 and c["big"] and c["sel"]["wide_only"] == 1, name
+    wide = lambda name: W[name]["wide"]
+    # the tableau's place: 123 dofs is the last chain with it in LDS
+    assert wide("chain123")["tableau_in_lds"] == 1 and wide("chain123")["t_lds_doubles"] == 123 * 123
+    for name in ("chain124", "chain130", "chain300", "chain_last"):
+        assert wide(name)["tableau_in_lds"] == 0 and wide(name)["t_lds_doubles"] < W[name]["nv"] ** 2, name
+        assert wide(name)["ws_stride"] >= W[name]["nv"] ** 2, name           # (the slice of device memory holds it)
+    assert (wide("chain124")["chain_words"], wide("chain130")["chain_words"], wide("chain300")["chain_words"]) == (2, 3, 5)
+    assert wide("chain_last")["chain_words"] == 9 and W["chain300"]["nv"] > KWIDE_THREADS and W["chain_last"]["nv"] > 2 * KWIDE_THREADS
+    # the largest chain and the first that is refused: code, and the LDS figure in the text
+    assert W["chain_last"]["nv"] + 1 == W["chain_last+1"]["nv"] and wide("chain_last")["lds_doubles"] == LDS_CAP
+    bad = W["chain_last+1"]
+    need = wide_layout(**_wide_counts(bad))["lds_doubles"]
+    assert need > LDS_CAP and bad["rc"] == -4
+    assert bad["err"].startswith("model too large for the workgroup-per-problem kernel: %d KB of LDS per problem, 158 KB available" % (need // 128))
+    # staging of the block pivots: over the poses on serial hinge chains, appended / absent / appended on the ball chains
+    assert {wide(n)["blk"] for n in ("chain123", "chain124", "chain130", "chain300", "chain_last", "fixed30")} == {"overlay"}
+    assert (wide("ball80")["blk"], wide("ball86")["blk"], wide("ball92")["blk"]) == ("appended", "absent", "appended")
+    assert wide("ball86")["o_blk"] < 0 and wide("ball80")["o_blk"] > wide("ball80")["o_X"]
+    assert all(wide(n)["tableau_in_lds"] == 1 for n in ("ball80", "ball86", "ball92", "fixed30"))
+    # the wide route by body count alone
+    assert (W["fixed30"]["nv"], W["fixed30"]["nbody"]) == (30, 91)
+    # collision pairs on a wide-only model: more than a wavefront of them, culled by bounding spheres
+    assert 70 <= W["hinge80"]["n_pairs_in"] <= 100 and wide("hinge80")["n_pairs"] == len(wc.HINGE80_PAIRS) > 64
+    assert wide("hinge80")["use_cull"] == 1 and wide("hinge80")["max_rows"] == len(wc.HINGE80_PAIRS)
+    assert all(wide(n)["use_cull"] == 0 for n in W if n not in ("hinge80", "chain_last+1"))
