@@ -84,6 +84,9 @@ extern "C" {
                                     re-solves such instances with orthogonal factors (quadprog's own algorithm) and clears the bit.
                                     A caller sees it only where that launch does not run: handles created with
                                     MKH_DIAG_NO_WIDE_REDO and calls that tap the cycle counters. */
+#define MKH_ST_IN_COLLISION 64   /* set by the fan-out calls on a candidate whose final q is in collision, while a collision checker
+                                    is attached (mkh_problem_set_collision_check, "THE RULE OF CLEARANCE" below).  No solve kernel
+                                    sets it; like every bit but MKH_ST_OUTSIDE_LIMITS it makes a candidate ineligible. */
 
 /* flags */
 #define MKH_FLAG_DEVICE_PTRS 1   /* data pointers are device pointers; async on stream */
@@ -904,6 +907,61 @@ int32_t mkh_seed_table_read(const MkhSeedTable *table, double *q_out /* (N, nq) 
 int32_t mkh_seed_table_query(const MkhSeedTable *table, int32_t B, const double *frame_targets, int32_t K,
                              int32_t *index_out, double *dist_out, double *seeds_out, int32_t flags, void *hip_stream);
 int32_t mkh_problem_set_seed_table(MkhProblem *problem, const MkhSeedTable *table);
+
+/*
+ * Clearance: how far a batch of configurations is from collision, on the device — and, attached to a problem, the stage behind
+ * the loops of the fan-out calls that takes colliding candidates out of their selections.  No counterpart in the reference: it is
+ * the check a caller runs on the results of a global IK before using one (mj_geomDistance over a pair list at every candidate).
+ *
+ * A CHECKER is an ordinary MkhProblem whose descriptor has collision limits; its tasks and its other limits do not enter (a
+ * descriptor with no tasks at all is accepted).
+ *
+ * THE RULE OF CLEARANCE (mkh_clearance; the fan-out calls run it on the final q of every candidate).
+ *   Pair list  the checker's collision limits in descriptor order, each limit's geom_id_pairs in its own order: pair k carries
+ *              dmin_k = minimum_distance_from_collisions and ddetect_k = collision_detection_distance of its limit; gain and
+ *              bound_relaxation do not enter.
+ *   For one row q (nq,):
+ *   d_k        mj_geomDistance(geom1_k, geom2_k, distmax = ddetect_k) at the forward kinematics of q (quaternions normalised as
+ *              mj_kinematics does), by the device routines of the collision phase: d_k <= ddetect_k, and a pair the
+ *              bounding-sphere cull skips has d_k = ddetect_k — what mj_geomDistance says about it.
+ *   margin     min_k (d_k - dmin_k)
+ *   pair       the lowest k that attains the minimum
+ *   n_violated #{k : !(d_k >= dmin_k)}
+ *   The row is IN COLLISION iff !(margin >= 0).  A NaN decides: a row with a NaN term has margin = NaN and pair = the lowest k
+ *   with a NaN term (numpy's min / argmin), and is in collision, never free.  A row of q with a NaN or an infinite entry has
+ *   EVERY d_k = NaN, stated outright and not left to what the distance routines make of such poses (their clamps and range
+ *   tests swallow a NaN): margin = NaN, pair = 0, n_violated = the number of pairs.
+ *
+ * mkh_clearance evaluates N rows in chunks of the checker's max_batch.  Pointers are host pointers (synchronous) or device
+ * pointers with MKH_FLAG_DEVICE_PTRS (asynchronous on the stream); no other flag is accepted.  Refused with MKH_E_INVALID: a
+ * checker without collision pairs; a checker created with MKH_DIAG_NO_WIDE_REDO (it has no per-body arrays to compute poses
+ * from); general convex pairs (cylinder-box, ellipsoid-*, mesh hulls) on a checker whose model has more than 64 bodies or dofs
+ * (they are not pre-evaluated there).  MKH_E_LIMIT beyond 1170 bodies (the poses of a row live in 64 KB of LDS).
+ *
+ * Attached (mkh_problem_set_collision_check; NULL detaches; the checker may be the problem itself: "the limit I solved with"):
+ * mkh_solve_multistart, mkh_solve_multistart_set and mkh_solve_goalset run the clearance of every candidate's final q directly
+ * behind their loops, on the call's stream, and OR MKH_ST_IN_COLLISION into the status row of every candidate that is in
+ * collision.  Their selections then run on those rows unchanged — any status bit but MKH_ST_OUTSIDE_LIMITS makes a candidate
+ * ineligible — so n_converged / n_reached count the candidates that converged AND are free.  q_all, iters_all and
+ * converged_all are the loops' own; status_all carries the bit.  If nothing is eligible the result is seed 0's with
+ * converged = 0, as without a checker; its status says so when seed 0 itself collides.  With a checker attached the call is
+ * therefore NOT "never worse than mkh_solve_until from q": a converged seed 0 that collides is not returned as converged.
+ * Every other entry point that runs loops over candidates or waypoints — mkh_solve_trajectory, mkh_solve_keyframes,
+ * mkh_solve_trajectory_multistart, the three ladder calls and mkh_ladder_refine — returns MKH_E_INVALID while a checker is
+ * attached (it would not be honoured).  The checker must live on the problem's device and belong to the same MkhModel
+ * (MKH_E_INVALID otherwise), and must stay alive while it is attached.  The stage runs on the CHECKER handle's buffers (its
+ * pre-evaluated convex pairs): "one call in flight per handle" holds for the checker too — two problems that share a checker,
+ * or a problem and mkh_clearance on it, must not run at the same time on different streams.
+ */
+typedef struct MkhClearanceIO {
+  double  *margin;      /* (N,)  required */
+  int32_t *pair;        /* (N,)  required */
+  int32_t *n_violated;  /* (N,)  required */
+  double  *distance;    /* (N, n_pairs) optional: every d_k */
+} MkhClearanceIO;
+int32_t mkh_clearance(MkhProblem *checker, int32_t N, const double *q_rows /* (N, nq) */, const MkhClearanceIO *io,
+                      int32_t flags, void *hip_stream);
+int32_t mkh_problem_set_collision_check(MkhProblem *problem, MkhProblem *checker /* or NULL */);
 
 /*
  * Ladder-graph trajectory IK: S IK solutions per waypoint (a "rung"), computed independently of each other, and a dynamic

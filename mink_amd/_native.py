@@ -52,6 +52,7 @@ class diag_options:
         _diag_default.bits = self.prev
         return False
 ST_OUTSIDE_LIMITS, ST_INFEASIBLE, ST_NOT_PD, ST_ITER_LIMIT, ST_ROW_OVERFLOW = 1, 2, 4, 8, 16
+ST_IN_COLLISION = 64             # set on a candidate of a fan-out call with a collision checker: include/minkhip.h "THE RULE OF CLEARANCE"
 FRAME_TYPE_ID = {"body": 0, "geom": 1, "site": 2}
 
 _pd = C.POINTER(C.c_double)
@@ -544,6 +545,19 @@ TAP_NAMES = ("xpos", "xquat", "frame_pose", "subtree_com", "task_e", "task_J", "
              "box_hi", "coll_G", "coll_h", "qp_iters", "cycles")
 
 
+class MkhClearanceIO(C.Structure):
+    _fields_ = [("margin", C.c_void_p), ("pair", C.c_void_p), ("n_violated", C.c_void_p), ("distance", C.c_void_p)]
+
+
+class ClearanceOut(NamedTuple):
+    """mkh_clearance of N rows (include/minkhip.h "THE RULE OF CLEARANCE"): margin (N,), pair (N,) int32, n_violated (N,) int32,
+    distance (N, n_pairs) or None."""
+    margin: object
+    pair: object
+    n_violated: object
+    distance: object = None
+
+
 class MkhTaps(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in TAP_NAMES]
 
@@ -655,6 +669,10 @@ def lib() -> C.CDLL:
     L.mkh_seed_table_query.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_int32, C.c_void_p]
     L.mkh_problem_set_seed_table.argtypes = [C.c_void_p, C.c_void_p]
+    L.mkh_clearance.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(MkhClearanceIO), C.c_int32, C.c_void_p]
+    L.mkh_clearance.restype = C.c_int32
+    L.mkh_problem_set_collision_check.argtypes = [C.c_void_p, C.c_void_p]
+    L.mkh_problem_set_collision_check.restype = C.c_int32
     for f in ("mkh_seed_table_create", "mkh_seed_table_read", "mkh_seed_table_query", "mkh_problem_set_seed_table"):
         getattr(L, f).restype = C.c_int32
     for f in ("mkh_model_create", "mkh_problem_create", "mkh_problem_num_task_rows",
@@ -676,6 +694,7 @@ EXPORTED_SYMBOLS = (
     "mkh_problem_set_seed_table", "mkh_ladder_select", "mkh_solve_trajectory_ladder",
     "mkh_ladder_refine", "mkh_solve_trajectory_ladder_refined", "mkh_solve_multistart_set", "mkh_select_distinct",
     "mkh_solve_goalset", "mkh_select_goalset", "mkh_unwind_turns", "mkh_solve_trajectory_ladder_nodes",
+    "mkh_clearance", "mkh_problem_set_collision_check",
 )
 
 LIE_OPS = {"se3_log": (0, 7, 0, (6,)), "se3_jlog": (1, 7, 0, (6, 6)), "se3_ljacinv": (2, 6, 0, (6, 6)),
@@ -922,6 +941,40 @@ class _attached:
             lib().mkh_problem_set_seed_table(self.problem.handle, None)
 
 
+class _checked:
+    """A collision checker attached to a handle for one call (mkh_problem_set_collision_check), detached on the way out.
+    `checker`: None, a NativeProblem with collision pairs on the handle's device and model, or an object with
+    `_native_for(problem)` that returns one (mink_amd.CollisionChecker).  The checker handle's lock is held for the call: host-pointer
+    calls that share a checker from several threads are serialised on it; device-pointer calls are asynchronous, and those that
+    share a checker must be ordered by the caller (one stream, or events), as for any handle."""
+
+    def __init__(self, problem: "NativeProblem", checker):
+        self.problem = problem
+        self.checker = None if checker is None else checker._native_for(problem)
+
+    def __enter__(self):
+        if self.checker is not None:
+            # the call runs on the checker handle's buffers (its pre-evaluated convex pairs): one call per handle holds for it too.
+            # Always the problem's lock first, the checker's second; a problem that checks itself holds its one lock already.
+            self.locked = self.checker is not self.problem
+            if self.locked:
+                self.checker._lock.acquire()
+            try:
+                if not self.checker.handle:
+                    raise ValueError("the collision checker is closed")
+                _check(lib().mkh_problem_set_collision_check(self.problem.handle, self.checker.handle))
+            except BaseException:
+                if self.locked:
+                    self.checker._lock.release()
+                raise
+
+    def __exit__(self, *exc):
+        if self.checker is not None:
+            lib().mkh_problem_set_collision_check(self.problem.handle, None)
+            if self.locked:
+                self.checker._lock.release()
+
+
 class NativeProblem:
     """Device descriptor of one solve_ik call site (mkh_problem_create)."""
 
@@ -1022,6 +1075,29 @@ class NativeProblem:
             self.close()
         except Exception:
             pass
+
+    def _native_for(self, problem: "NativeProblem") -> "NativeProblem":
+        return self
+
+    def clearance(self, q_rows, return_distances: bool = False) -> ClearanceOut:
+        """mkh_clearance with this handle as the checker: q_rows (N, nq) → margin (N,), pair (N,), n_violated (N,) and, asked
+        for, distance (N, n_pairs) — include/minkhip.h "THE RULE OF CLEARANCE".  Any N: the rows are walked in chunks of
+        max_batch.  numpy in → numpy out (synchronous); a torch CUDA tensor in → torch tensors out, asynchronous on the
+        current stream, no host copy."""
+        m = self.nmodel.model
+        prep, empty, ptr, stream, devp = _call_kit(q_rows)
+        q_rows = prep(q_rows)
+        if len(q_rows.shape) != 2 or int(q_rows.shape[1]) != m.nq or int(q_rows.shape[0]) < 1:
+            raise ValueError(f"q_rows must have shape (N, {m.nq}) with N >= 1, got {tuple(q_rows.shape)}")
+        if devp and (q_rows.device.index if q_rows.device.index is not None else 0) != self.nmodel.device:
+            raise ValueError(f"q_rows live on {q_rows.device}, the checker on device {self.nmodel.device}")
+        N = int(q_rows.shape[0])
+        out = ClearanceOut(empty((N,), np.float64), empty((N,), np.int32), empty((N,), np.int32),
+                           empty((N, self.n_pairs), np.float64) if return_distances else None)
+        io = MkhClearanceIO(ptr(out.margin), ptr(out.pair), ptr(out.n_violated), ptr(out.distance))
+        with self._lock:
+            _check(lib().mkh_clearance(self.handle, N, ptr(q_rows), C.byref(io), devp, stream))
+        return out
 
     def last_kernel(self) -> str:
         """Kernel variant launched by the last solve on this handle (diagnostic)."""
@@ -1193,16 +1269,19 @@ class NativeProblem:
                          damping: float = 1e-12, *, n_seeds: int, max_iters: int, pos_threshold: float, ori_threshold: float,
                          rng_seed: int = 0, target_index0: int = 0, seeds=None, reference=None, weights=None,
                          return_all: bool = False, wave_kernel: bool = False, lane_kernel: bool = False,
-                         quad_kernel: bool = False, seed_table=None) -> MultistartOut:
+                         quad_kernel: bool = False, seed_table=None, collision_check=None) -> MultistartOut:
         """mkh_solve_multistart: the threshold-terminated loop from `n_seeds` starts per row of q (seed 0 = the row itself, the
         others drawn on the device or taken from `seeds` (B, S, nq)), the converged result closest to `reference` (default q)
         picked on the device.  numpy in → numpy out (synchronous); torch CUDA tensors in → torch tensors out, asynchronous on
         the current stream, no host copy.  The handle needs max_batch >= B·n_seeds.  `seed_table` (a SeedTable or
         NativeSeedTable, not together with `seeds`): seeds 1 … n_seeds − 1 are the table's entries nearest to each target,
-        looked up on the device in front of the seed kernel; the table is attached for this call only."""
+        looked up on the device in front of the seed kernel; the table is attached for this call only.  `collision_check` (a
+        CollisionChecker, or a NativeProblem with collision pairs on this handle's model — this handle itself included): every
+        candidate whose final q is in collision gets ST_IN_COLLISION in its status row directly behind the loops and is not
+        eligible (include/minkhip.h "THE RULE OF CLEARANCE"); attached for this call only."""
         if seeds is not None and seed_table is not None:
             raise ValueError("seeds and seed_table are two sources of the same starts: pass one of them")
-        with self._lock, _attached(self, seed_table):
+        with self._lock, _attached(self, seed_table), _checked(self, collision_check):
             return self._solve_multistart(q, frame_targets, posture_target, com_target, dt, damping, int(n_seeds), int(max_iters),
                                           float(pos_threshold), float(ori_threshold), int(rng_seed), int(target_index0), seeds,
                                           reference, weights, return_all, wave_kernel, lane_kernel, quad_kernel)
@@ -1212,17 +1291,18 @@ class NativeProblem:
                              ori_threshold: float, min_distance: float = 0.1, rng_seed: int = 0, target_index0: int = 0,
                              seeds=None, reference=None, weights=None, return_all: bool = False, wave_kernel: bool = False,
                              lane_kernel: bool = False, quad_kernel: bool = False, seed_table=None,
-                             unwind_turns: bool = False) -> SolutionSetOut:
+                             unwind_turns: bool = False, collision_check=None) -> SolutionSetOut:
         """mkh_solve_multistart_set: solve_multistart's seeds and loops, then up to `n_solutions` converged results per row of q
         no two of which lie within `min_distance` of each other (Σ_k weights_k·(a ⊖ b)_k² <= min_distance²), in ascending
         distance from `reference` (default q) — slot 0 is solve_multistart's choice (the rule: include/minkhip.h "THE RULE OF THE
         SET").  numpy in → numpy out (synchronous); torch CUDA tensors in → torch tensors out, asynchronous on the current
         stream, no host copy.  Everything else as in solve_multistart.  `unwind_turns` (MKH_FLAG_UNWIND_TURNS): the loops'
-        results are moved to the turn nearest the reference before they are compared; q_all then holds the unwound rows."""
+        results are moved to the turn nearest the reference before they are compared; q_all then holds the unwound rows.
+        `collision_check`: as in solve_multistart (the check runs in front of the unwinding)."""
         if seeds is not None and seed_table is not None:
             raise ValueError("seeds and seed_table are two sources of the same starts: pass one of them")
         check_solution_set(int(n_solutions), float(min_distance), int(n_seeds))
-        with self._lock, _attached(self, seed_table):
+        with self._lock, _attached(self, seed_table), _checked(self, collision_check):
             return self._solve_multistart(q, frame_targets, posture_target, com_target, dt, damping, int(n_seeds), int(max_iters),
                                           float(pos_threshold), float(ori_threshold), int(rng_seed), int(target_index0), seeds,
                                           reference, weights, return_all, wave_kernel, lane_kernel, quad_kernel,
@@ -1299,7 +1379,7 @@ class NativeProblem:
                       damping: float = 1e-12, *, n_seeds: int, max_iters: int, pos_threshold: float, ori_threshold: float,
                       goal_cost=None, goal_valid=None, rng_seed: int = 0, target_index0: int = 0, seeds=None, reference=None,
                       weights=None, return_all: bool = False, wave_kernel: bool = False, lane_kernel: bool = False,
-                      quad_kernel: bool = False, seed_table=None) -> GoalSetOut:
+                      quad_kernel: bool = False, seed_table=None, collision_check=None) -> GoalSetOut:
         """mkh_solve_goalset: multi-start to the best of G goals per row of q — solve_multistart's seeds and loops on the (B·G)
         flattened (target, goal) pairs (seed 0 of every goal the row of q itself, the others drawn at target index
         (target_index0 + b)·G + g, taken from `seeds` (B, G, S, nq) or from `seed_table`, queried with every goal's own
@@ -1307,7 +1387,8 @@ class NativeProblem:
         goal_cost + distance (the rule: include/minkhip.h "THE RULE OF THE GOAL SET").  frame_targets (B, G, n_frame, 7);
         posture / CoM targets held for the whole call, (n, w), or (B, G, n, w); goal_cost, goal_valid (B, G).  The handle needs
         max_batch >= n_seeds; B·G·n_seeds loops beyond max_batch run in chunks of whole goals.  numpy in → numpy out
-        (synchronous); torch CUDA tensors in → torch tensors out on the current stream, no host copy."""
+        (synchronous); torch CUDA tensors in → torch tensors out on the current stream, no host copy.  `collision_check`: as in
+        solve_multistart — a goal whose candidates all collide is not reached."""
         if seeds is not None and seed_table is not None:
             raise ValueError("seeds and seed_table are two sources of the same starts: pass one of them")
         m = self.nmodel.model
@@ -1371,7 +1452,7 @@ class NativeProblem:
             ptr(goal_valid)
         for n, x in {**out, **every}.items():
             setattr(io, n, ptr(x))
-        with self._lock, _attached(self, seed_table):
+        with self._lock, _attached(self, seed_table), _checked(self, collision_check):
             _check(lib().mkh_solve_goalset(self.handle, B, G, ptr(q), ptr(frame_targets), ptr(posture_target), ptr(com_target),
                                            float(dt), float(damping), max_iters, float(pos_threshold), float(ori_threshold), S,
                                            int(rng_seed) & (2 ** 64 - 1), int(target_index0), C.byref(io), flags, stream))

@@ -243,6 +243,7 @@ struct MkhProblem : ProblemSelect {     // (what creation decided and plan_launc
   bool ws_tables = false;
   GrowBuf ws[WS_COUNT];
   const MkhSeedTable* seed_table = nullptr;    // attached by mkh_problem_set_seed_table
+  MkhProblem* checker = nullptr;               // attached by mkh_problem_set_collision_check
 };
 
 // A seed table (include/minkhip.h "Seed tables"): device memory of its own — nothing of the problem that made it is kept.
@@ -1524,6 +1525,90 @@ int32_t mkh_problem_set_seed_table(MkhProblem* p, const MkhSeedTable* table) {
   return MKH_OK;
 }
 
+// ---- clearance (include/minkhip.h "THE RULE OF CLEARANCE"; kernel: clearance.hip, in front of it convex_pre.hip's for the pairs
+// without an analytic routine)
+static_assert(mkh::kStInCollision == MKH_ST_IN_COLLISION, "outer_launch.h: the bit clearance.hip sets");
+
+// Whether `ck` can be a checker.
+static int32_t clearance_refuse(const MkhProblem* ck, const char* who) {
+  if (ck->dev.n_pairs < 1) return fail(MKH_E_INVALID, "%s: the checker has no collision pairs (a problem with CollisionAvoidanceLimits is one)", who);
+  if (!ck->d_wide)
+    return fail(MKH_E_INVALID, "%s: the checker was created with MKH_DIAG_NO_WIDE_REDO: it has no per-body arrays to compute poses from", who);
+  if (ck->convex_pairs && ck->cv.n_cv == 0)
+    return fail(MKH_E_INVALID, "%s: the checker has general convex pairs (cylinder-box, ellipsoid-*, mesh hulls) that are not pre-evaluated "
+                               "on this handle (a model beyond 64 bodies or dofs): no clearance", who);
+  if ((size_t)ck->model->nbody * 7 * sizeof(double) > 64 * 1024)
+    return fail(MKH_E_LIMIT, "%s: %d bodies: the poses of one row do not fit 64 KB of LDS (at most 1170 bodies)", who, ck->model->nbody);
+  return MKH_OK;
+}
+
+// The clearance of N device rows on st's stream, in chunks of the checker's max_batch (its buffer of pre-evaluated convex pairs
+// holds that many rows; the stream orders its reuse).  Every output is optional; status: MKH_ST_IN_COLLISION OR-ed in.
+static void clearance_rows(Stager& st, MkhProblem* ck, size_t N, const double* d_q, double* margin, int32_t* pair, int32_t* n_violated,
+                           double* distance, int32_t* status) {
+  const size_t per = (size_t)ck->max_batch, nq = ck->model->nq, np = ck->dev.n_pairs;
+  for (size_t r0 = 0; r0 < N && st.ok(); r0 += per) {
+    const int n = (int)(N - r0 < per ? N - r0 : per);
+    const double* const q = d_q + r0 * nq;
+    if (ck->cv.n_cv > 0) st.latch((hipError_t)mkh::launch_convex_pre(st.stream, ck->d_wide, ck->cv, n, q, ck->d_cv));
+    ST_LAUNCH(st, launch_clearance(st.stream, ck->d_wide, ck->model->nbody, (int)np, ck->cv.n_cv, ck->d_cv, n, q, margin ? margin + r0 : nullptr,
+                                   pair ? pair + r0 : nullptr, n_violated ? n_violated + r0 : nullptr,
+                                   distance ? distance + r0 * np : nullptr, status ? status + r0 : nullptr));
+  }
+}
+
+// An attached checker in front of an entry point that would not run it.
+static int32_t refuse_checker(const MkhProblem* p, const char* who) {
+  if (p->checker)
+    return fail(MKH_E_INVALID, "%s: a collision checker is attached to this problem (mkh_problem_set_collision_check) and this call would "
+                               "not run it: mkh_solve_multistart, mkh_solve_multistart_set and mkh_solve_goalset are the calls that "
+                               "do — detach it first", who);
+  return MKH_OK;
+}
+
+int32_t mkh_clearance(MkhProblem* ck, int32_t N, const double* q_rows, const MkhClearanceIO* io, int32_t flags, void* hip_stream) {
+  const char* const who = "mkh_clearance";
+  if (!ck) return fail(MKH_E_INVALID, "null problem");
+  if (N < 1) return fail(MKH_E_INVALID, "%s: N = %d must be >= 1", who, N);
+  if (flags & ~MKH_FLAG_DEVICE_PTRS) return fail(MKH_E_INVALID, "%s: flags = %d: only MKH_FLAG_DEVICE_PTRS is accepted", who, flags);
+  if (!q_rows || !io || !io->margin || !io->pair || !io->n_violated)
+    return fail(MKH_E_INVALID, "%s: q_rows, io and its outputs margin, pair, n_violated are required", who);
+  if (const int32_t rc = clearance_refuse(ck, who)) return rc;
+  const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
+  HIP_OK(hipSetDevice(ck->model->device));
+  Stager st{ck, (hipStream_t)hip_stream, devp, "clearance"};
+  const size_t Nz = N, nq = ck->model->nq, np = ck->dev.n_pairs, f8 = sizeof(double), i4 = sizeof(int32_t);
+  const double* const d_q = st.up(WS_C_Q, q_rows, Nz * nq);
+  double *o_m = io->margin, *o_d = io->distance;
+  int32_t *o_p = io->pair, *o_n = io->n_violated;
+  if (!devp) {
+    o_m = st.f64(WS_OUT_LEN, Nz);
+    o_p = st.i32(WS_OUT_PICK, 2 * Nz); o_n = o_p ? o_p + Nz : nullptr;
+    if (o_d) o_d = st.f64(WS_OUT_Q, Nz * np);
+  }
+  if (!st.ok()) return st.finish();
+  clearance_rows(st, ck, Nz, d_q, o_m, o_p, o_n, o_d, nullptr);
+  if (devp) return st.finish();
+  st.down(io->margin, o_m, Nz * f8);
+  st.down(io->pair, o_p, Nz * i4);
+  st.down(io->n_violated, o_n, Nz * i4);
+  st.down(io->distance, o_d, Nz * np * f8);
+  return st.finish();
+}
+
+int32_t mkh_problem_set_collision_check(MkhProblem* p, MkhProblem* checker) {
+  const char* const who = "mkh_problem_set_collision_check";
+  if (!p) return fail(MKH_E_INVALID, "null problem");
+  if (checker) {
+    if (checker->device != p->device)
+      return fail(MKH_E_INVALID, "%s: the checker lives on device %d, the problem on device %d", who, checker->device, p->device);
+    if (checker->model != p->model) return fail(MKH_E_INVALID, "%s: the checker belongs to another MkhModel than the problem", who);
+    if (const int32_t rc = clearance_refuse(checker, who)) return rc;
+  }
+  p->checker = checker;
+  return MKH_OK;
+}
+
 // ---- the loop stage of every call that fans a target out to S starts (kernels: multistart.hip, seed_table.hip): the two
 // multi-start calls below, the rungs of the ladder calls and the goals of mkh_solve_goalset.  It works on device arrays and on
 // the caller's Stager; which arrays, the caller says.
@@ -1699,6 +1784,7 @@ int32_t mkh_solve_multistart(MkhProblem* p, int32_t B, const double* q, const do
   const size_t Bz = B, nq = p->dev.nq, nv = p->dev.nv, f8 = sizeof(double), i4 = sizeof(int32_t);
   const MsCall m = ms_stage(st, B, S, q, frame_targets, posture_target, com_target, tab, *io, flags);
   if (const int32_t rc = ms_loops(st, B, S, m.in, ls, rng_seed, target_index0, m.c, flags); rc || !st.ok()) return st.finish(rc);
+  if (p->checker) clearance_rows(st, p->checker, Bz * S, m.c.q_all, nullptr, nullptr, nullptr, nullptr, m.c.status);
   // ---- selection
   double *o_q = io->q_best, *o_v = io->v_best;
   int32_t *o_it = io->iters, *o_st = io->status, *o_cv = io->converged, *o_si = io->seed_index, *o_nc = io->n_converged;
@@ -1805,6 +1891,8 @@ int32_t mkh_solve_multistart_set(MkhProblem* p, int32_t B, const double* q, cons
   mio.seeds_out = io->seeds_out;
   const MsCall m = ms_stage(st, B, S, q, frame_targets, posture_target, com_target, tab, mio, flags);
   if (const int32_t rc = ms_loops(st, B, S, m.in, ls, rng_seed, target_index0, m.c, flags); rc || !st.ok()) return st.finish(rc);
+  // (the checker in front of the unwinding: it judges the loops' own results, and whole turns move no body)
+  if (p->checker) clearance_rows(st, p->checker, (size_t)B * S, m.c.q_all, nullptr, nullptr, nullptr, nullptr, m.c.status);
   if (flags & MKH_FLAG_UNWIND_TURNS)     // in place, where q_all is read from: the loops' flags are carried over
     ST_LAUNCH(st, launch_unwind_turns(st.stream, p->ws[WS_UNW].f64(), (long long)B * S, S, (int)p->dev.nq, m.c.q_all, m.ref, m.c.q_all));
   const SetSpec set{n_solutions, min_distance * min_distance, io};
@@ -1958,6 +2046,7 @@ static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double
       return fail(MKH_E_INVALID, "posture_targets_out / com_targets_out must be NULL for a target that is held");
   }
   if (!p) return fail(MKH_E_INVALID, "null problem");
+  if (const int32_t rc = refuse_checker(p, who)) return rc;
   const DeviceProblem& P = p->dev;
   if (const int32_t rc = refuse_inputs(P, q, frame_targets, posture_target, com_target, until ? who : nullptr, "trajectory"))
     return rc;
@@ -2379,6 +2468,7 @@ int32_t mkh_ladder_refine(MkhProblem* p, int32_t B, int32_t T, const double* q, 
   if (!p) return fail(MKH_E_INVALID, "null problem");
   if (!io) return fail(MKH_E_INVALID, "%s: io is required", who);
   if (const int32_t rc = refine_refuse(p, B, T, io->max_step_sq, ls, who)) return rc;
+  if (const int32_t rc = refuse_checker(p, who)) return rc;
   if (const int32_t rc = refuse_unwind(flags, who)) return rc;
   if (!q_path || !tracked_path) return fail(MKH_E_INVALID, "%s: q_path and tracked_path are required", who);
   if (!io->q_path_out || !io->tracked_out || !io->repaired || !io->refined || !io->edge_break || !io->n_tracked || !io->n_breaks ||
@@ -2462,6 +2552,7 @@ static int32_t ladder_call_refuse(const MkhProblem* p, int32_t B, int32_t T, int
                                   const double* com_target, const MkhTrajectoryLadderIO* io, const MkhLadderNodesIO* nodes,
                                   const MkhLadderRefineIO* refine, bool devp, const char* who, const MkhSeedTable** tab) {
   if (const int32_t rc = loops_refuse(ls, target_index0, true, who, "a fixed count leaves no tracked flag to search on")) return rc;
+  if (const int32_t rc = refuse_checker(p, who)) return rc;
   if (!io->q_traj || !io->v_traj || !io->status || !io->iters || !io->converged || !io->node_index || !io->n_tracked ||
       !io->n_breaks || !io->path_length || !io->edge_break)
     return fail(MKH_E_INVALID, "%s: io's outputs q_traj, v_traj, status, iters, converged, node_index, n_tracked, n_breaks, path_length, "
@@ -2837,6 +2928,7 @@ int32_t mkh_solve_goalset(MkhProblem* p, int32_t B, int32_t n_goals, const doubl
     return MsRows{l_starts ? l_starts + i0 * nq : c_q, l_q + i0 * nq, l_v + i0 * nv, l_st + i0, l_it + i0, l_cv + i0, nullptr};
   };
   if (const int32_t rc = ms_rungs(st, R, S, in, ls, rng_seed, target_index0 * G, flags, rows_at)) return st.finish(rc);
+  if (p->checker) clearance_rows(st, p->checker, N, l_q, nullptr, nullptr, nullptr, nullptr, l_st);
   // ---- the two levels
   goalset_select(st, B, G, S, *io, l_q, l_v, l_st, l_it, l_cv, d_ref ? d_ref : d_q, d_w);
   if (devp) return st.finish();

@@ -1,6 +1,6 @@
 // Launchers of the small kernels around the loop launches of the outer-loop entry points (mkh_solve_multistart,
 // mkh_solve_multistart_set, mkh_solve_goalset, mkh_solve_trajectory, mkh_solve_keyframes, mkh_solve_trajectory_multistart, the ladder calls) and of
-// the seed tables in front of them: declared once, for the eleven files that define them and for minkhip.hip, which calls them — a signature that
+// the seed tables in front of them: declared once, for the twelve files that define them and for minkhip.hip, which calls them — a signature that
 // drifts fails to compile in the file that drifted.  In minkhip.hip the multi-start calls, the ladder calls and the goal set
 // launch the seeding, the seed-table query and the target fan-out from one place, the loop stage ms_loops(), which also asks for
 // their workspace slots (WS_C_FT / PT / CT, the WS_IN_SEEDS slab); mkh_solve_trajectory_multistart has its own (time-major) ones.
@@ -149,5 +149,13 @@ hipError_t launch_lr_step(hipStream_t stream, int B, int T, int nq, int nv, int 
 hipError_t launch_lr_guard(hipStream_t stream, int B, int T, int nq, int nv, int njnt, const int32_t* jnt, const double* q0,
                            const double* weights, double max_step_sq, const double* p, const int32_t* p_trk, const LrWork& w,
                            const LrOut& o);
+// clearance (clearance.hip; include/minkhip.h "THE RULE OF CLEARANCE"): margin / pair / n_violated (N,) and distance (N, n_pairs) of
+// N rows of q against the n_pairs >= 1 pairs of a checker's per-body descriptor (a device WideProblem), each output optional.
+// nbody and n_pairs choose between one and four rows per wavefront and size the launch's LDS: beyond 64 KB of poses
+// hipErrorInvalidValue.  cv: the (N, n_cv, 7) records launch_convex_pre left for the same rows, read for the pairs without an
+// analytic routine.  status given: kStInCollision is OR-ed into the rows that are in collision.
+constexpr int32_t kStInCollision = 64;   // MKH_ST_IN_COLLISION
+hipError_t launch_clearance(hipStream_t stream, const void* wide_problem, int nbody, int n_pairs, int n_cv, const double* cv, int N,
+                            const double* q, double* margin, int32_t* pair, int32_t* n_violated, double* distance, int32_t* status);
 
 }  // namespace mkh

@@ -461,7 +461,8 @@ def _status_epilogue(status: np.ndarray, who: str, outside: str, failed: str) ->
         out = out.any(axis=1)
     if out.any():
         logging.warning(who + ": %d " + outside + " were outside their configuration limits at some fused step", int(out.sum()))
-    bad = np.argwhere((status & ~nat.ST_OUTSIDE_LIMITS) != 0)
+    # (ST_IN_COLLISION is no QP failure: a collision checker's verdict on the chosen row, which its status and converged = False state)
+    bad = np.argwhere((status & ~(nat.ST_OUTSIDE_LIMITS | nat.ST_IN_COLLISION)) != 0)
     if len(bad):
         first = tuple(int(x) for x in bad[0])
         raise exceptions.SolverError(failed.format(n=len(bad), of=status.size, first=first[0] if status.ndim == 1 else first,
@@ -606,6 +607,119 @@ class SeedTable:
             pass
 
 
+class Clearance(NamedTuple):
+    """Result of CollisionChecker.clearance, each with the leading shape of the rows: `margin` = min_k (d_k − dmin_k), the `pair`
+    (index into the checker's pair list) that attains it — the lowest on a tie —, `n_violated` pairs closer than their minimum
+    distance, `in_collision` = not (margin >= 0) — a NaN row is in collision —, and, asked for, every `distance` d_k
+    (..., n_pairs), capped at the pair's detection distance."""
+    margin: object
+    pair: object
+    n_violated: object
+    in_collision: object
+    distance: object = None
+
+
+class CollisionChecker:
+    """Clearance of configurations on the device, and the `collision_check=` of solve_ik_multistart / solve_ik_solutions /
+    solve_ik_goalset (include/minkhip.h "THE RULE OF CLEARANCE").
+
+    `limits`: built-in CollisionAvoidanceLimit objects of `model`; their geom pairs, in order, are the pair list — pair k with
+    its limit's minimum_distance_from_collisions and collision_detection_distance (gain and bound_relaxation do not enter).
+    A row is in collision when some pair is closer than its minimum distance.  One native handle per device model is built on
+    first use, for `max_rows` rows per launch (more rows are walked in chunks)."""
+
+    def __init__(self, model, limits: Sequence, max_rows: int = 65536):
+        import threading
+        from .configuration import as_flat_model
+        from .limits import CollisionAvoidanceLimit
+
+        self.model = as_flat_model(model)
+        limits = list(limits)
+        for lim in limits:
+            if not isinstance(lim, CollisionAvoidanceLimit) or lim._is_dense():
+                raise exceptions.LimitDefinitionError(
+                    f"a CollisionChecker takes built-in CollisionAvoidanceLimit objects, got {type(lim).__name__}"
+                    + (" (a subclass that overrides compute_qp_inequalities has no pair list the device evaluates)"
+                       if isinstance(lim, CollisionAvoidanceLimit) else ""))
+        self._descs = [lim._native_desc()[1] for lim in limits]
+        pairs = [d["geom_id_pairs"].reshape(-1, 2) for d in self._descs]
+        self.geom_id_pairs = np.concatenate(pairs, axis=0).astype(np.int32) if pairs else np.zeros((0, 2), np.int32)
+        self.n_pairs = int(len(self.geom_id_pairs))
+        if self.n_pairs < 1:
+            raise exceptions.LimitDefinitionError("a CollisionChecker needs at least one geom pair")
+        self.minimum_distance = np.concatenate([np.full(len(p), float(d["minimum_distance_from_collisions"]))
+                                                for p, d in zip(pairs, self._descs)])
+        self.detection_distance = np.concatenate([np.full(len(p), float(d["collision_detection_distance"]))
+                                                  for p, d in zip(pairs, self._descs)])
+        self.max_rows = int(max_rows)
+        if self.max_rows < 1:
+            raise ValueError("max_rows must be >= 1")
+        self._handles = {}                 # id(NativeModel) → (NativeModel, NativeProblem)
+        self._lock = threading.Lock()
+        self._closed = False
+
+    def _handle(self, nmodel) -> "nat.NativeProblem":
+        with self._lock:
+            if self._closed:
+                raise ValueError("the collision checker is closed")
+            hit = self._handles.get(id(nmodel))
+            if hit is None:
+                hit = self._handles[id(nmodel)] = (nmodel, nat.NativeProblem(nmodel, collision_limits=self._descs,
+                                                                             max_batch=self.max_rows))
+            return hit[1]
+
+    def _native_for(self, problem) -> "nat.NativeProblem":
+        if problem.nmodel.model is not self.model:
+            raise ValueError("collision_check belongs to another model than the configuration")
+        return self._handle(problem.nmodel)
+
+    def clearance(self, q_rows, return_distances: bool = False) -> Clearance:
+        """The clearance of `q_rows` — (nq,), (N, nq) or (..., nq); the outputs take the leading shape.  numpy (or anything
+        array-like) in → numpy out; a torch tensor on a device in → torch tensors there, on the current stream."""
+        from .configuration import native_model
+
+        if self._closed:
+            raise ValueError("the collision checker is closed")
+        nq = self.model.nq
+        is_torch = nat._is_torch(q_rows)
+        q = q_rows if is_torch else _host_array(q_rows, "q_rows")
+        if q.ndim < 1 or int(q.shape[-1]) != nq:
+            raise ValueError(f"q_rows must have shape (..., {nq}), got {tuple(q.shape)}")
+        lead = tuple(int(x) for x in q.shape[:-1])
+        if 0 in lead:
+            raise ValueError(f"q_rows holds no row: shape {tuple(q.shape)}")
+        if is_torch and q.device.type != "cuda":
+            is_torch, q = False, _host_array(q, "q_rows")
+        device = (q.device.index if q.device.index is not None else 0) if is_torch else 0
+        o = self._handle(native_model(self.model, device)).clearance(q.reshape(-1, nq), bool(return_distances))
+        return Clearance(o.margin.reshape(lead), o.pair.reshape(lead), o.n_violated.reshape(lead),
+                         ~(o.margin >= 0.0).reshape(lead),
+                         None if o.distance is None else o.distance.reshape(lead + (self.n_pairs,)))
+
+    def close(self) -> None:
+        with self._lock:
+            self._closed = True
+            for _, prob in self._handles.values():
+                prob.close()
+            self._handles = {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _check_collision_check(collision_check, configuration: Configuration):
+    """The `collision_check=` keyword of the three fan-out calls, judged on the host."""
+    if collision_check is None:
+        return
+    if not isinstance(collision_check, CollisionChecker):
+        raise ValueError(f"collision_check must be a CollisionChecker, got {type(collision_check).__name__}")
+    if collision_check.model is not configuration.model:
+        raise ValueError("collision_check belongs to another model than the configuration")
+
+
 def _check_seed_table(seed_table, seeds, configuration: Configuration, S: int):
     """The `seed_table=` keyword of the two multi-start calls, judged on the host."""
     if seed_table is None:
@@ -624,7 +738,8 @@ def solve_ik_multistart(configuration: Configuration, tasks: Sequence, dt: float
                         pos_threshold: float, ori_threshold: float, solver: str = "mi355x", damping: float = 1e-12,
                         limits: Optional[Sequence] = None, rng_seed: int = 0, seeds=None, reference=None, weights=None,
                         update: bool = True, return_all: bool = False, max_instances: int = 1 << 20,
-                        seed_table: Optional["SeedTable"] = None) -> MultistartResult:
+                        seed_table: Optional["SeedTable"] = None,
+                        collision_check: Optional["CollisionChecker"] = None) -> MultistartResult:
     """Global IK by multi-start: the threshold-terminated loop of solve_ik_steps from `n_seeds` starts per target, the best
     solution picked on the device — seeding, target fan-out and selection happen there, in one call.
 
@@ -644,6 +759,12 @@ def solve_ik_multistart(configuration: Configuration, tasks: Sequence, dt: float
     nearest to the target's frame poses, looked up on the device in front of the seed kernel — they depend on the target
     alone, not on rng_seed, chunks or shards.  The table is attached to the handle for this call only.
 
+    `collision_check` (a CollisionChecker): directly behind the loops every seed's final q is checked on the device and a seed
+    that is in collision gets ST_IN_COLLISION in its status and is not eligible — `n_converged` counts the seeds that converged
+    AND are free, and `status_all` carries the bit.  With a checker the call is no longer "never worse than solve_ik_steps from
+    q": where nothing is eligible the result is still seed 0's with converged = False — also when seed 0 converged into a
+    collision, which its status then says (no SolverError for that bit).  Attached to the handle for this call only.
+
     When B·n_seeds exceeds `max_instances` the targets are walked in chunks; a multi-device configuration shards by target."""
     del solver
     S, max_iters = int(n_seeds), int(max_iters)
@@ -658,6 +779,7 @@ def solve_ik_multistart(configuration: Configuration, tasks: Sequence, dt: float
     reference = _optional_array(reference, "reference", (nq,), B)
     weights = _optional_array(weights, "weights", (nv,))
     _check_seed_table(seed_table, seeds, configuration, S)
+    _check_collision_check(collision_check, configuration)
     handles, layout, chunk, n_dev = _compile_outer(configuration, tasks, limits, dt, "solve_ik_multistart", S, max_instances)
     ft, pt, ct = _gather_targets(configuration, layout)
     q = configuration.q_batch
@@ -667,7 +789,7 @@ def solve_ik_multistart(configuration: Configuration, tasks: Sequence, dt: float
     def job(handle, lo, hi):
         return handle.solve_multistart(q[lo:hi], _rows(ft, 2, lo, hi), _rows(pt, 2, lo, hi), _rows(ct, 2, lo, hi), dt, damping,
                                        target_index0=lo, seeds=_rows(seeds, 2, lo, hi), reference=_rows(reference, 1, lo, hi),
-                                       weights=weights, seed_table=seed_table, **kw)
+                                       weights=weights, seed_table=seed_table, collision_check=collision_check, **kw)
 
     res = _join(MultistartResult, _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job))
     _status_epilogue(res.status, "solve_ik_multistart", "chosen instance(s)",
@@ -735,7 +857,8 @@ def solve_ik_solutions(configuration: Configuration, tasks: Sequence, dt: float,
                        pos_threshold: float, ori_threshold: float, min_distance: float = 0.1, solver: str = "mi355x",
                        damping: float = 1e-12, limits: Optional[Sequence] = None, rng_seed: int = 0, seeds=None, reference=None,
                        weights=None, return_all: bool = False, max_instances: int = 1 << 20,
-                       seed_table: Optional["SeedTable"] = None, unwind_turns: bool = False) -> SolutionSet:
+                       seed_table: Optional["SeedTable"] = None, unwind_turns: bool = False,
+                       collision_check: Optional["CollisionChecker"] = None) -> SolutionSet:
     """The distinct IK solutions of every target that multi-start finds: solve_ik_multistart's seeds and loops — `n_seeds`
     starts per target, the same generator, `seeds`, `seed_table`, chunks and shards — and, instead of its one result, up to
     `n_solutions` converged results per target no two of which lie within `min_distance` of each other, picked and
@@ -749,6 +872,11 @@ def solve_ik_solutions(configuration: Configuration, tasks: Sequence, dt: float,
     solutions a full turn of an unlimited hinge apart count as different — unless `unwind_turns` is set: every loop result is
     then moved to the turn nearest the reference first (the function unwind_turns; `q_all` returns the moved rows), so the
     slots go to IK branches and not to turns of one branch.  Slot 0 is then the closest MOVED result.
+
+    `collision_check` (a CollisionChecker): as in solve_ik_multistart — colliding results get ST_IN_COLLISION behind the loops
+    (in front of the unwinding) and fill no slot; `n_converged` counts the converged and free ones.  With a checker slot 0 is
+    no longer "never worse than solve_ik_steps from q": an empty set repeats seed 0's result, whose status says so when it
+    collides.
 
     The configuration is not changed: a set does not update it.  Failures are reported for slot 0 only, as
     solve_ik_multistart reports them for its choice."""
@@ -766,6 +894,7 @@ def solve_ik_solutions(configuration: Configuration, tasks: Sequence, dt: float,
     reference = _optional_array(reference, "reference", (nq,), B)
     weights = _optional_array(weights, "weights", (nv,))
     _check_seed_table(seed_table, seeds, configuration, S)
+    _check_collision_check(collision_check, configuration)
     handles, layout, chunk, n_dev = _compile_outer(configuration, tasks, limits, dt, "solve_ik_solutions", S, max_instances)
     ft, pt, ct = _gather_targets(configuration, layout)
     q = configuration.q_batch
@@ -776,7 +905,7 @@ def solve_ik_solutions(configuration: Configuration, tasks: Sequence, dt: float,
     def job(handle, lo, hi):
         return handle.solve_multistart_set(q[lo:hi], _rows(ft, 2, lo, hi), _rows(pt, 2, lo, hi), _rows(ct, 2, lo, hi), dt, damping,
                                            target_index0=lo, seeds=_rows(seeds, 2, lo, hi), reference=_rows(reference, 1, lo, hi),
-                                           weights=weights, seed_table=seed_table, **kw)
+                                           weights=weights, seed_table=seed_table, collision_check=collision_check, **kw)
 
     res = _join(nat.SolutionSetOut, _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job))
     _status_epilogue(res.status[:, 0], "solve_ik_solutions", "chosen instance(s)",
@@ -923,7 +1052,8 @@ def solve_ik_goalset(configuration: Configuration, tasks: Sequence, dt: float, g
                      pos_threshold: float, ori_threshold: float, goal_cost=None, goal_valid=None, reference=None, weights=None,
                      seeds=None, seed_table: Optional["SeedTable"] = None, rng_seed: int = 0, return_all: bool = False,
                      update: bool = True, max_instances: int = 1 << 20, damping: float = 1e-12,
-                     limits: Optional[Sequence] = None, safety_break: bool = False, solver: str = "mi355x") -> GoalSetResult:
+                     limits: Optional[Sequence] = None, safety_break: bool = False, solver: str = "mi355x",
+                     collision_check: Optional["CollisionChecker"] = None) -> GoalSetResult:
     """Global IK to the best of G candidate poses per target — the grasp poses of an object, the poses a placement accepts,
     the yaws of a symmetric tool: which of them the robot reaches, and the configuration of the one closest to the current
     posture, in one call, picked on the device.
@@ -939,6 +1069,10 @@ def solve_ik_goalset(configuration: Configuration, tasks: Sequence, dt: float, g
     goal).  Where nothing is reached the row is seed 0's of the lowest valid goal — what solve_ik_steps returns from q towards
     it — with converged = False.  Masked goals still run their loops: pad a ragged set by repeating a valid goal (the rule in
     full: include/minkhip.h "THE RULE OF THE GOAL SET").
+
+    `collision_check` (a CollisionChecker): as in solve_ik_multistart — a seed whose final q is in collision gets
+    ST_IN_COLLISION and is not eligible, so a goal whose seeds all collide is not reached; `n_converged_goal` and `n_reached`
+    count the free ones.  With a checker the call is no longer "never worse than solve_ik_steps from q" towards a goal.
 
     Limits warnings and SolverError follow solve_ik_trajectory_ladder's rules on the CHOSEN rows only (`safety_break` as there).
     With `update` the configuration is left at the chosen q.  The instances are walked in chunks of as many as keep
@@ -970,6 +1104,7 @@ def solve_ik_goalset(configuration: Configuration, tasks: Sequence, dt: float, g
     reference = _optional_array(reference, "reference", (nq,), B)
     weights = _optional_array(weights, "weights", (nv,))
     _check_seed_table(seed_table, seeds, configuration, S)
+    _check_collision_check(collision_check, configuration)
     handles, layout, chunk, n_dev = _compile_outer(configuration, tasks, limits, dt, "solve_ik_goalset", G * S, max_instances)
     ft, pt, ct = _stacked_targets(configuration, layout, seqs, G)
     # a batched target that is held over the goals gets its G axis: the call takes (n, w) or (B, G, n, w)
@@ -983,7 +1118,7 @@ def solve_ik_goalset(configuration: Configuration, tasks: Sequence, dt: float, g
         return handle.solve_goalset(q[lo:hi], _rows(ft, 0, lo, hi), _rows(pt, 2, lo, hi), _rows(ct, 2, lo, hi), dt, damping,
                                     target_index0=lo, seeds=_rows(seeds, 0, lo, hi), reference=_rows(reference, 0, lo, hi),
                                     goal_cost=_rows(goal_cost, 0, lo, hi), goal_valid=_rows(goal_valid, 0, lo, hi),
-                                    seed_table=seed_table, **kw)
+                                    seed_table=seed_table, collision_check=collision_check, **kw)
 
     res = _join(nat.GoalSetOut, _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job))
     if safety_break and ((res.status & nat.ST_OUTSIDE_LIMITS) != 0).any():
