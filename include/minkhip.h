@@ -964,6 +964,40 @@ int32_t mkh_clearance(MkhProblem *checker, int32_t N, const double *q_rows /* (N
 int32_t mkh_problem_set_collision_check(MkhProblem *problem, MkhProblem *checker /* or NULL */);
 
 /*
+ * Swept clearance: whether the MOTION between two configurations is free of collision, not only its two ends — the check a
+ * planner runs on every edge of a joint-space path.  The straight joint-space move is sampled at M interior points and every
+ * sample is judged by THE RULE OF CLEARANCE; the samples are built and evaluated on the device and never written to memory.
+ *
+ * THE RULE OF THE SWEEP (mkh_swept_clearance; the checked ladder calls run it on the edges of their graph).
+ * For an edge from row a to row b (nq each) and M = n_samples >= 1:
+ *   Samples        u_i = i / (M + 1) for i = 1 .. M (one division of doubles): interior points — the ends are nodes and are
+ *                  judged as nodes.  q(u) = a (+) u (b (-) a) per joint type, exactly the posture rule of mkh_solve_keyframes:
+ *                  scalars a + u (b - a) — a difference, a product, a sum, contraction off —, quaternions by
+ *                  mju_quatIntegrate(a, mju_subQuat(b, a), u): the shortest arc whatever the sign of either quaternion.
+ *   Sample margin  m_i = margin(q(u_i)) by THE RULE OF CLEARANCE, unchanged: the pair list, the ddetect cap, the cull, "a NaN
+ *                  decides".
+ *   Edge outputs   margin = min_i m_i; sample = the lowest i - 1 that attains it; pair = the pair of that sample's clearance —
+ *                  numpy's min / argmin, a NaN sample deciding as a NaN term does (the first one).
+ *   The edge COLLIDES iff !(margin >= 0).
+ *   A NaN or an infinity in a or b makes EVERY sample NaN: margin = NaN, sample = 0, pair = 0, the edge collides.
+ *
+ * mkh_swept_clearance evaluates N edges, q_from and q_to (N, nq); every output is (N,) and required.  Host pointers
+ * (synchronous; staged whole) or device pointers with MKH_FLAG_DEVICE_PTRS (asynchronous on the stream); one launch either way —
+ * a sweep has no per-row workspace, so N is not bound by the checker's max_batch; no other flag is accepted.  The checker is refused as mkh_clearance refuses it, and in addition:
+ * Not covered: general convex pairs.  A checker WITH general convex pairs (cylinder-box, ellipsoid-*, mesh hulls) is refused
+ * with MKH_E_INVALID by every sweep entry point: those pairs are pre-evaluated on rows in memory, and a sweep has none.
+ * MKH_E_LIMIT when the poses of a row and the three rows of q beside them (a, b (-) a, q(u)) exceed 64 KB of LDS:
+ * 7 nbody + 3 nq > 8192 doubles.  "One call in flight per checker handle" holds as for mkh_clearance.
+ */
+typedef struct MkhSweptClearanceIO {
+  double  *margin;      /* (N,)  required */
+  int32_t *sample;      /* (N,)  required */
+  int32_t *pair;        /* (N,)  required */
+} MkhSweptClearanceIO;
+int32_t mkh_swept_clearance(MkhProblem *checker, int32_t N, const double *q_from /* (N, nq) */, const double *q_to /* (N, nq) */,
+                            int32_t n_samples, const MkhSweptClearanceIO *io, int32_t flags, void *hip_stream);
+
+/*
  * Ladder-graph trajectory IK: S IK solutions per waypoint (a "rung"), computed independently of each other, and a dynamic
  * program over the T rungs that picks the path — complete first, free of joint-space jumps second, shortest third.  It is the
  * per-waypoint search ACROSS candidates that mkh_solve_trajectory_multistart leaves out: that call keeps one whole candidate,
@@ -1015,6 +1049,44 @@ typedef struct MkhLadderIO {
 int32_t mkh_ladder_select(MkhProblem *problem, int32_t B, int32_t T, int32_t S, const double *q, const double *q_nodes,
                           const int32_t *tracked, const double *weights, double max_step_sq, const MkhLadderIO *io,
                           int32_t flags, void *hip_stream);
+
+/*
+ * THE RULE, with a checker (mkh_ladder_select_free; mkh_solve_trajectory_ladder_free runs it on the rungs it solves): the path
+ * whose waypoints AND motions are free of collision.  The checker is an ARGUMENT of these calls; a checker attached with
+ * mkh_problem_set_collision_check is neither read nor needed here (mkh_ladder_select_free ignores one;
+ * mkh_solve_trajectory_ladder_free refuses one, as every ladder call that runs loops does).
+ *   Nodes.   node_margin(t, s) = the margin of q_{t,s} by THE RULE OF CLEARANCE.  The EFFECTIVE flag of a node is
+ *            tracked(t, s) != 0 && node_margin(t, s) >= 0: a node in collision counts as not tracked.
+ *   Edges.   For t >= 1, blocked(t, s', s) = the edge from node (t - 1, s) to node (t, s') COLLIDES by THE RULE OF THE SWEEP
+ *            with M = n_samples.  An edge whose DESTINATION node is not tracked by the effective flag is not swept — its
+ *            waypoint is lost on any path through it —: its swept margin is NaN and blocked = 0.  The start edge from q[b] is
+ *            never swept, just as it is never a break.
+ *   Key.     Only the first component changes.  Waypoint t of a path counts as LOST when its node is not tracked by the
+ *            effective flag, or — for t >= 1 — the edge into it collides.  In the recurrence the term lost(t, s') becomes
+ *            lost(t, s') | blocked(t, s', s); breaks, length, the tie order (lowest s, lowest end node), the 16-bit counts and
+ *            the back-trace are unchanged.  n_tracked = T - lost therefore counts the waypoints that are reached, tracked,
+ *            free of collision and entered by a free motion.
+ *   Outputs, beside MkhLadderIO's: edge_collision (B, T): 1 where the edge INTO waypoint t collides, entry 0 always 0;
+ *            n_edge_collisions (B,); edge_margin (B, T): the swept margin of the chosen edge, entry 0 = +inf, NaN where the edge
+ *            was not swept.  Optional: node_margin (B, T, S); edge_margin_all (B, T, S, S), entry [b, t, s', s], NaN for t = 0
+ *            and for edges not swept.
+ * The full mask is the defined result: every edge into an effectively tracked node is swept, B (T - 1) S^2 M row evaluations
+ * at the most, into one flag byte per edge in a workspace of the PROBLEM handle (B T S^2 bytes; B T S^2 doubles more only when
+ * edge_margin_all is asked for); the node clearances run on the checker handle.  The checker must pass mkh_swept_clearance's
+ * refusals and live on the problem's device and belong to its MkhModel (MKH_E_INVALID); n_samples >= 1; B T S^2 < 2^31.
+ * "One call in flight per checker handle" holds.
+ */
+typedef struct MkhLadderFreeIO {
+  int32_t *edge_collision;     /* (B, T)        1 where the edge into waypoint t collides                          required  */
+  int32_t *n_edge_collisions;  /* (B,)          colliding edges on the path                                        required  */
+  double *edge_margin;         /* (B, T)        the swept margin of the chosen edges                               required  */
+  double *node_margin;         /* (B, T, S)     optional: the clearance margin of every node                                 */
+  double *edge_margin_all;     /* (B, T, S, S)  optional: the swept margin of every edge                                     */
+} MkhLadderFreeIO;
+int32_t mkh_ladder_select_free(MkhProblem *problem, MkhProblem *checker, int32_t B, int32_t T, int32_t S, const double *q,
+                               const double *q_nodes, const int32_t *tracked, const double *weights, double max_step_sq,
+                               int32_t n_samples, const MkhLadderIO *io, const MkhLadderFreeIO *free_io, int32_t flags,
+                               void *hip_stream);
 
 /*
  * mkh_solve_trajectory_ladder: the rungs solved by multi-start, then THE RULE above.
@@ -1205,6 +1277,30 @@ int32_t mkh_solve_trajectory_ladder_nodes(MkhProblem *problem, int32_t B, int32_
                                           int32_t max_iters, double pos_threshold, double ori_threshold, uint64_t rng_seed,
                                           int64_t target_index0, const MkhTrajectoryLadderIO *io, const MkhLadderNodesIO *nodes,
                                           const MkhLadderRefineIO *refine, int32_t flags, void *hip_stream);
+
+/*
+ * mkh_solve_trajectory_ladder_free: the ladder calls above with THE RULE "with a checker" in place of THE RULE.  The arguments
+ * are those of the call on distinct nodes, with the checker, n_samples and the MkhLadderFreeIO: n_nodes = 0 with nodes = NULL is
+ * mkh_solve_trajectory_ladder on n_seeds nodes per rung, n_nodes = K >= 1 with nodes the ladder on K distinct nodes (anything
+ * else: MKH_E_INVALID).  `refine` must be NULL: the refinement pass knows nothing of collisions — Not covered.
+ *   Behind the loops of every chunk of rungs the clearance of the candidates' final q runs on the checker and
+ *   MKH_ST_IN_COLLISION is OR-ed into their status rows — status_all in the plain ladder; the chunk's candidate rows in the call
+ *   on nodes, behind the optional unwinding and in front of the selection, so that a colliding candidate takes no slot and a
+ *   FILLED slot's status never carries the bit (an empty slot holds candidate 0's rows, as in the plain call, and is not tracked).  A node's tracked flag follows from its status as before, so a colliding node is not
+ *   tracked: that IS the effective flag of the rule.  Then the sweep of every edge into a tracked node, the masked search, and
+ *   everything behind it as in the plain calls.
+ * The result is the composition of the plain call's nodes (return_all), the clearance of those rows, and mkh_ladder_select_free
+ * on them, bit for bit.  free_io->node_margin must be NULL here (the nodes' verdict is the status bit); edge_margin_all is
+ * (B, T, W, W) with W the nodes per rung.  The checker is an argument: a checker ATTACHED to the problem is refused as in the
+ * plain calls.  Checker refusals, n_samples and sizes as in mkh_ladder_select_free.
+ */
+int32_t mkh_solve_trajectory_ladder_free(MkhProblem *problem, MkhProblem *checker, int32_t B, int32_t T, int32_t n_seeds,
+                                         int32_t n_nodes, double min_distance, const double *q, const double *frame_targets,
+                                         const double *posture_target, const double *com_target, double dt, double damping,
+                                         int32_t max_iters, double pos_threshold, double ori_threshold, uint64_t rng_seed,
+                                         int64_t target_index0, int32_t n_samples, const MkhTrajectoryLadderIO *io,
+                                         const MkhLadderNodesIO *nodes, const MkhLadderRefineIO *refine,
+                                         const MkhLadderFreeIO *free_io, int32_t flags, void *hip_stream);
 
 /* Same inputs; additionally writes the requested intermediates (build_ik / compute_error /
  * compute_jacobian / get_transform_frame_to_world parity taps).  v_out/status_out may be NULL

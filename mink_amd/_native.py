@@ -558,6 +558,34 @@ class ClearanceOut(NamedTuple):
     distance: object = None
 
 
+class MkhSweptClearanceIO(C.Structure):
+    _fields_ = [("margin", C.c_void_p), ("sample", C.c_void_p), ("pair", C.c_void_p)]
+
+
+class SweptClearanceOut(NamedTuple):
+    """mkh_swept_clearance of N edges (include/minkhip.h "THE RULE OF THE SWEEP"): margin (N,), sample (N,) int32, pair (N,) int32."""
+    margin: object
+    sample: object
+    pair: object
+
+
+LADDER_FREE_IO_FIELDS = ("edge_collision", "n_edge_collisions", "edge_margin", "node_margin", "edge_margin_all")
+
+
+class MkhLadderFreeIO(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in LADDER_FREE_IO_FIELDS]
+
+
+class LadderFreeOut(NamedTuple):
+    """What the checked ladder calls add (include/minkhip.h THE RULE "with a checker"): edge_collision (B, T) int32,
+    n_edge_collisions (B,) int32, edge_margin (B, T), and, where asked for, node_margin (B, T, S) and edge_margin_all (B, T, S, S)."""
+    edge_collision: object
+    n_edge_collisions: object
+    edge_margin: object
+    node_margin: object = None
+    edge_margin_all: object = None
+
+
 class MkhTaps(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in TAP_NAMES]
 
@@ -673,6 +701,17 @@ def lib() -> C.CDLL:
     L.mkh_clearance.restype = C.c_int32
     L.mkh_problem_set_collision_check.argtypes = [C.c_void_p, C.c_void_p]
     L.mkh_problem_set_collision_check.restype = C.c_int32
+    L.mkh_swept_clearance.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(MkhSweptClearanceIO),
+                                      C.c_int32, C.c_void_p]
+    L.mkh_swept_clearance.restype = C.c_int32
+    L.mkh_ladder_select_free.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_double, C.c_int32, C.POINTER(MkhLadderIO), C.POINTER(MkhLadderFreeIO),
+                                         C.c_int32, C.c_void_p]
+    L.mkh_ladder_select_free.restype = C.c_int32
+    L.mkh_solve_trajectory_ladder_free.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double] + \
+        common[2:8] + [C.c_int32, C.c_double, C.c_double, C.c_uint64, C.c_int64, C.c_int32, C.POINTER(MkhTrajectoryLadderIO),
+                       C.POINTER(MkhLadderNodesIO), C.POINTER(MkhLadderRefineIO), C.POINTER(MkhLadderFreeIO), C.c_int32, C.c_void_p]
+    L.mkh_solve_trajectory_ladder_free.restype = C.c_int32
     for f in ("mkh_seed_table_create", "mkh_seed_table_read", "mkh_seed_table_query", "mkh_problem_set_seed_table"):
         getattr(L, f).restype = C.c_int32
     for f in ("mkh_model_create", "mkh_problem_create", "mkh_problem_num_task_rows",
@@ -695,6 +734,7 @@ EXPORTED_SYMBOLS = (
     "mkh_ladder_refine", "mkh_solve_trajectory_ladder_refined", "mkh_solve_multistart_set", "mkh_select_distinct",
     "mkh_solve_goalset", "mkh_select_goalset", "mkh_unwind_turns", "mkh_solve_trajectory_ladder_nodes",
     "mkh_clearance", "mkh_problem_set_collision_check",
+    "mkh_swept_clearance", "mkh_ladder_select_free", "mkh_solve_trajectory_ladder_free",
 )
 
 LIE_OPS = {"se3_log": (0, 7, 0, (6,)), "se3_jlog": (1, 7, 0, (6, 6)), "se3_ljacinv": (2, 6, 0, (6, 6)),
@@ -941,6 +981,36 @@ class _attached:
             lib().mkh_problem_set_seed_table(self.problem.handle, None)
 
 
+class _with_checker:
+    """The locks of a call that takes its checker as an argument (mkh_ladder_select_free, mkh_solve_trajectory_ladder_free): the
+    problem's first, the checker's second; a problem that checks itself has one."""
+
+    def __init__(self, problem: "NativeProblem", checker: "NativeProblem"):
+        self.locks = [problem._lock] + ([checker._lock] if checker is not problem else [])
+        self.checker = checker
+
+    def __enter__(self):
+        for k in self.locks:
+            k.acquire()
+        if not self.checker.handle:
+            self.__exit__()
+            raise ValueError("the collision checker is closed")
+
+    def __exit__(self, *exc):
+        for k in reversed(self.locks):
+            k.release()
+
+
+def _checker_handle(problem: "NativeProblem", checker, edge_samples) -> "NativeProblem":
+    """The native checker of a checked ladder call on `problem`, judged on the host."""
+    if int(edge_samples) < 1:
+        raise ValueError(f"edge_samples must be >= 1, got {edge_samples}")
+    checker = checker._native_for(problem)
+    if checker.nmodel is not problem.nmodel:
+        raise ValueError("the checker belongs to another NativeModel than the problem")
+    return checker
+
+
 class _checked:
     """A collision checker attached to a handle for one call (mkh_problem_set_collision_check), detached on the way out.
     `checker`: None, a NativeProblem with collision pairs on the handle's device and model, or an object with
@@ -1097,6 +1167,26 @@ class NativeProblem:
         io = MkhClearanceIO(ptr(out.margin), ptr(out.pair), ptr(out.n_violated), ptr(out.distance))
         with self._lock:
             _check(lib().mkh_clearance(self.handle, N, ptr(q_rows), C.byref(io), devp, stream))
+        return out
+
+    def swept_clearance(self, q_from, q_to, n_samples: int = 8) -> SweptClearanceOut:
+        """mkh_swept_clearance with this handle as the checker: the edges from q_from (N, nq) to q_to (N, nq), `n_samples`
+        interior samples each → margin (N,), sample (N,), pair (N,) — include/minkhip.h "THE RULE OF THE SWEEP".  numpy in →
+        numpy out (synchronous); torch CUDA tensors in → torch tensors out, asynchronous on the current stream."""
+        m = self.nmodel.model
+        if int(n_samples) < 1:
+            raise ValueError(f"n_samples must be >= 1, got {n_samples}")
+        prep, empty, ptr, stream, devp = _call_kit(q_from)
+        q_from, q_to = prep(q_from), prep(q_to)
+        if len(q_from.shape) != 2 or int(q_from.shape[1]) != m.nq or int(q_from.shape[0]) < 1:
+            raise ValueError(f"q_from must have shape (N, {m.nq}) with N >= 1, got {tuple(q_from.shape)}")
+        if tuple(q_to.shape) != tuple(q_from.shape):
+            raise ValueError(f"q_to must have q_from's shape {tuple(q_from.shape)}, got {tuple(q_to.shape)}")
+        N = int(q_from.shape[0])
+        out = SweptClearanceOut(empty((N,), np.float64), empty((N,), np.int32), empty((N,), np.int32))
+        io = MkhSweptClearanceIO(ptr(out.margin), ptr(out.sample), ptr(out.pair))
+        with self._lock:
+            _check(lib().mkh_swept_clearance(self.handle, N, ptr(q_from), ptr(q_to), int(n_samples), C.byref(io), devp, stream))
         return out
 
     def last_kernel(self) -> str:
@@ -1628,6 +1718,17 @@ class NativeProblem:
         """mkh_ladder_select: the dynamic program of include/minkhip.h "THE RULE" over the caller's rungs — q (B, nq) the current
         postures, q_nodes (B, T, S, nq), tracked (B, T, S) (None: every node), the squared break gate, weights (nv,) >= 0.
         numpy in → numpy out (synchronous); torch CUDA tensors in → torch tensors out on the current stream, no host copy."""
+        return self._ladder_select(q, q_nodes, tracked, max_step_sq, weights, None, 0, False)[0]
+
+    def ladder_select_free(self, q, q_nodes, checker: "NativeProblem", tracked=None, max_step_sq: float = float("inf"), weights=None,
+                           edge_samples: int = 8, return_margins: bool = False):
+        """mkh_ladder_select_free: ladder_select under THE RULE "with a checker" — `checker` a handle with collision limits on
+        the same NativeModel, `edge_samples` interior samples per edge.  Returns (LadderPathOut, LadderFreeOut); with
+        `return_margins` the latter carries node_margin (B, T, S) and edge_margin_all (B, T, S, S)."""
+        checker = _checker_handle(self, checker, edge_samples)
+        return self._ladder_select(q, q_nodes, tracked, max_step_sq, weights, checker, int(edge_samples), bool(return_margins))
+
+    def _ladder_select(self, q, q_nodes, tracked, max_step_sq, weights, checker, edge_samples, return_margins):
         m = self.nmodel.model
         B = int(q.shape[0])
         if len(q_nodes.shape) != 4:
@@ -1658,10 +1759,18 @@ class NativeProblem:
         io = MkhLadderIO()
         for n, x in out.items():
             setattr(io, n, ptr(x))
-        with self._lock:
-            _check(lib().mkh_ladder_select(self.handle, B, T, S, ptr(q), ptr(q_nodes), ptr(tracked), ptr(weights), float(max_step_sq),
-                                           C.byref(io), devp, stream))
-        return LadderPathOut(*[out[n] for n in LADDER_IO_FIELDS])
+        if checker is None:
+            with self._lock:
+                _check(lib().mkh_ladder_select(self.handle, B, T, S, ptr(q), ptr(q_nodes), ptr(tracked), ptr(weights),
+                                               float(max_step_sq), C.byref(io), devp, stream))
+            return LadderPathOut(*[out[n] for n in LADDER_IO_FIELDS]), None
+        more = LadderFreeOut(empty((B, T), i4), empty((B,), i4), empty((B, T), f8),
+                             empty((B, T, S), f8) if return_margins else None, empty((B, T, S, S), f8) if return_margins else None)
+        fio = MkhLadderFreeIO(*[ptr(x) for x in more])
+        with _with_checker(self, checker):
+            _check(lib().mkh_ladder_select_free(self.handle, checker.handle, B, T, S, ptr(q), ptr(q_nodes), ptr(tracked), ptr(weights),
+                                                float(max_step_sq), edge_samples, C.byref(io), C.byref(fio), devp, stream))
+        return LadderPathOut(*[out[n] for n in LADDER_IO_FIELDS]), more
 
     def solve_trajectory_ladder(self, q, frame_targets=None, posture_target=None, com_target=None, dt: float = 1e-2,
                                 damping: float = 1e-12, *, n_seeds: int, max_iters: int, pos_threshold: float,
@@ -1698,10 +1807,28 @@ class NativeProblem:
                                              qvel_dt, return_all, wave_kernel, lane_kernel, quad_kernel, seed_table, refine,
                                              (int(n_nodes), float(min_distance), bool(unwind_turns)))
 
+    def solve_trajectory_ladder_free(self, q, frame_targets=None, posture_target=None, com_target=None, dt: float = 1e-2,
+                                     damping: float = 1e-12, *, checker: "NativeProblem", edge_samples: int = 8, n_seeds: int,
+                                     max_iters: int, pos_threshold: float, ori_threshold: float, n_nodes: Optional[int] = None,
+                                     min_distance: float = 0.1, unwind_turns: bool = False, max_step_sq: float = float("inf"),
+                                     rng_seed: int = 0, target_index0: int = 0, seeds=None, weights=None,
+                                     qvel_dt: Optional[float] = None, return_all: bool = False, wave_kernel: bool = False,
+                                     lane_kernel: bool = False, quad_kernel: bool = False, seed_table=None):
+        """mkh_solve_trajectory_ladder_free: solve_trajectory_ladder (n_nodes None) or solve_trajectory_ladder_nodes under THE
+        RULE "with a checker": colliding candidates get ST_IN_COLLISION behind the loops, every edge into a tracked node is swept
+        with `edge_samples` interior samples, and the search runs on the mask.  Returns (the plain call's result, LadderFreeOut)."""
+        checker = _checker_handle(self, checker, edge_samples)
+        nodes = None if n_nodes is None else (int(n_nodes), float(min_distance), bool(unwind_turns))
+        return self._solve_trajectory_ladder(q, frame_targets, posture_target, com_target, dt, damping, n_seeds, max_iters,
+                                             pos_threshold, ori_threshold, max_step_sq, rng_seed, target_index0, seeds, weights,
+                                             qvel_dt, return_all, wave_kernel, lane_kernel, quad_kernel, seed_table, False, nodes,
+                                             (checker, int(edge_samples)))
+
     def _solve_trajectory_ladder(self, q, frame_targets, posture_target, com_target, dt, damping, n_seeds, max_iters,
                                  pos_threshold, ori_threshold, max_step_sq, rng_seed, target_index0, seeds, weights, qvel_dt,
-                                 return_all, wave_kernel, lane_kernel, quad_kernel, seed_table, refine, nodes):
-        """The body of the two ladder calls; `nodes`: None, or (n_nodes, min_distance, unwind_turns)."""
+                                 return_all, wave_kernel, lane_kernel, quad_kernel, seed_table, refine, nodes, free=None):
+        """The body of the ladder calls; `nodes`: None, or (n_nodes, min_distance, unwind_turns); `free`: None, or (checker,
+        edge_samples) — the result is then (the plain result, LadderFreeOut)."""
         if seeds is not None and seed_table is not None:
             raise ValueError("seeds and seed_table are two sources of the same starts: pass one of them")
         m = self.nmodel.model
@@ -1782,10 +1909,18 @@ class NativeProblem:
         plain = [out[n] for n in ("q_traj", "v_traj", "status", "iters", "converged", "node_index", "n_tracked", "n_breaks",
                                   "path_length", "edge_break", "qvel")] + \
             [every[n] for n in ("q_all", "v_all", "status_all", "iters_all", "converged_all", "seeds_out")] + list(extra)
-        if nodes is None:
+        if nodes is None and free is None:
             with self._lock, _attached(self, seed_table):
                 _check(lib().mkh_solve_trajectory_ladder_refined(self.handle, B, T, S, *head, *tail, flags, stream))
             return TrajectoryLadderOut(*plain)
+        if free is not None:
+            more = LadderFreeOut(empty((B, T), i4), empty((B,), i4), empty((B, T), f8))
+            fio = MkhLadderFreeIO(*[ptr(x) for x in more])
+        if nodes is None:
+            with _with_checker(self, free[0]), _attached(self, seed_table):
+                _check(lib().mkh_solve_trajectory_ladder_free(self.handle, free[0].handle, B, T, S, 0, 0.0, *head[:-1], free[1], head[-1],
+                                                              None, None, C.byref(fio), flags, stream))
+            return TrajectoryLadderOut(*plain), more
         K, r, unwind = nodes
         sets = {"node_seed_index": empty((B, T, K), i4), "node_multiplicity": empty((B, T, K), i4),
                 "node_distance": empty((B, T, K), f8), "n_distinct": empty((B, T), i4), "n_converged": empty((B, T), i4),
@@ -1793,6 +1928,12 @@ class NativeProblem:
         nio = MkhLadderNodesIO()
         for n, x in sets.items():
             setattr(nio, n, ptr(x))
+        if free is not None:
+            with _with_checker(self, free[0]), _attached(self, seed_table):
+                _check(lib().mkh_solve_trajectory_ladder_free(self.handle, free[0].handle, B, T, S, K, r, *head[:-1], free[1], head[-1],
+                                                              C.byref(nio), None, C.byref(fio), flags | (FLAG_UNWIND_TURNS if unwind else 0),
+                                                              stream))
+            return TrajectoryLadderNodesOut(*plain, *[sets[n] for n in LADDER_NODES_IO_FIELDS]), more
         with self._lock, _attached(self, seed_table):
             _check(lib().mkh_solve_trajectory_ladder_nodes(self.handle, B, T, S, K, r, *head, C.byref(nio), *tail,
                                                            flags | (FLAG_UNWIND_TURNS if unwind else 0), stream))

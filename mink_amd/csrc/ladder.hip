@@ -2,6 +2,8 @@
 // over the T rungs of S nodes of every instance, the back-trace, and the gather of the chosen nodes' rows — and their launchers
 // (declared in outer_launch.h).  The rungs themselves are multi-start's (multistart.hip and the solve kernels); behind the gather
 // sits trajectory.hip's waypoint velocity.  Nodes are batch-major: row (b·T + t)·S + s.  Nothing here touches a solve kernel.
+// The checked calls (mkh_ladder_select_free, mkh_solve_trajectory_ladder_free; THE RULE "with a checker") run the same dynamic
+// program on the mask of blocked edges that sweep.hip leaves: ladder_search_free_kernel, the MASK build of the one search body.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
@@ -26,13 +28,20 @@ constexpr int kLdIlp = 4;               // source nodes whose edge costs a lane 
 // node's best edge to `brk` as one ballot per pass; lane 0 finds the end node and walks back.
 //
 // dynamic LDS: dq (nq, 64) doubles | sq (nq, TS) doubles | lengths (2, S) doubles | weights (nv) doubles | counts (2, S) uint32 |
-// joint table (njnt, 3) int32
-__global__ __launch_bounds__(64) void ladder_search_kernel(
+// joint table (njnt, 3) int32 | MASK: flags (TS, 64) bytes
+//
+// MASK (THE RULE "with a checker"): `blocked` (B, T, S, S) bytes, 1 where the edge from node (t − 1, s) to node (t, s') collides
+// — byte ((b·T + t)·S + s')·S + s, so a destination's sources are consecutive.  The flags of a (destination pass, source tile)
+// are staged in LDS beside the source tile, source-major: the flag of source j at fl[j·64 + lane], consecutive lanes consecutive
+// bytes.  The destination's lost bit then depends on the source — lost(t, s') | blocked(t, s', s) — and enters the candidate's
+// count inside the loop over the sources; without MASK it is added once behind it, as before.
+template <bool MASK>
+__device__ __forceinline__ void ladder_search_body(
     int B, int T, int S, int nq, int nv, int njnt, int TS, const int32_t* __restrict__ jnt, const double* __restrict__ q0,
-    const double* __restrict__ q_nodes, const int32_t* __restrict__ tracked, const double* __restrict__ weights,
-    double max_step_sq, uint8_t* __restrict__ pred, unsigned long long* __restrict__ brk, int32_t* __restrict__ node_index,
-    int32_t* __restrict__ n_tracked, int32_t* __restrict__ n_breaks, double* __restrict__ path_length,
-    int32_t* __restrict__ edge_break) {
+    const double* __restrict__ q_nodes, const int32_t* __restrict__ tracked, const uint8_t* __restrict__ blocked,
+    const double* __restrict__ weights, double max_step_sq, uint8_t* __restrict__ pred, unsigned long long* __restrict__ brk,
+    int32_t* __restrict__ node_index, int32_t* __restrict__ n_tracked, int32_t* __restrict__ n_breaks, double* __restrict__ path_length,
+    int32_t* __restrict__ edge_break, int32_t* __restrict__ edge_collision, int32_t* __restrict__ n_edge_collisions) {
 #pragma clang fp contract(off)      // length: one rounded addition per edge, never fused into the distance
   extern __shared__ double ld_lds[];
   const int b = blockIdx.x;
@@ -44,6 +53,7 @@ __global__ __launch_bounds__(64) void ladder_search_kernel(
   double* const wl = klen + 2 * (size_t)S;
   uint32_t* const kcnt = (uint32_t*)(wl + nv);
   int32_t* const jl = (int32_t*)(kcnt + 2 * (size_t)S);
+  uint8_t* const fl = (uint8_t*)(jl + 3 * (size_t)njnt);                     // (MASK only)
   // the joint table and the weights (ones without) in LDS: every lane reads the same word — a broadcast, and a vector register
   // where a read from memory would hold scalar ones across the whole search
   for (int e = lane; e < 3 * njnt; e += 64) jl[e] = jnt[e];
@@ -66,6 +76,8 @@ __global__ __launch_bounds__(64) void ladder_search_kernel(
         const int j = e / nq, a = e - j * nq;
         dq[a * kLdDest + j] = q_nodes[(rung + (size_t)c * kLdDest) * nq + e];
       }
+      uint32_t lost_dst = 0u;           // (MASK: the destination's own lost bit, known in front of the sources)
+      if constexpr (MASK) lost_dst = (valid && tracked[rung + s1] == 0) ? 1u : 0u;
       uint32_t best_cnt = 0xffffffffu;  // (above every key: the first source always wins)
       double best_len = kInf;
       int best_s = 0;
@@ -77,6 +89,17 @@ __global__ __launch_bounds__(64) void ladder_search_kernel(
           const int j = e / nq, a = e - j * nq;
           sq[a * TS + j] = src_rung[(size_t)tile0 * nq + e];
         }
+        if constexpr (MASK) {
+          // (e runs along a destination's sources, so the global reads are contiguous — the whole n_dst x n_tile block when the
+          // tile is the rung — and the LDS byte stores of consecutive lanes lie 64 bytes apart: they share four banks.  The other
+          // order would store contiguously and read memory at a stride of S bytes.  One byte per edge against the nq-term cost of
+          // the same edge behind it: the staging was not measured apart from the call, profiles/r22_swept.txt has the call.)
+          if (t)
+            for (int e = lane; e < n_dst * n_tile; e += 64) {
+              const int d = e / n_tile, j = e - d * n_tile;
+              fl[j * kLdDest + d] = blocked[(rung + (size_t)c * kLdDest + d) * S + tile0 + j];
+            }
+        }
         __syncthreads();
         for (int j0 = 0; valid && j0 < n_tile; j0 += kLdIlp) {
           double d[kLdIlp];
@@ -87,7 +110,8 @@ __global__ __launch_bounds__(64) void ladder_search_kernel(
             const int s = tile0 + j0 + k;
             const double cost = (d[k] >= 0.0 && d[k] <= kMax) ? d[k] : kInf;
             const bool bk = t != 0 && cost > max_step_sq;                      // (the start edge is never a break)
-            const uint32_t cnt = (t ? kcnt[prv * S + s] : 0u) + (bk ? 1u : 0u);
+            uint32_t cnt = (t ? kcnt[prv * S + s] : 0u) + (bk ? 1u : 0u);
+            if constexpr (MASK) cnt += (lost_dst | (t ? (uint32_t)fl[(j0 + k) * kLdDest + lane] : 0u)) << 16;
             const double len = (t ? klen[prv * S + s] : 0.0) + cost;
             if (cnt < best_cnt || (cnt == best_cnt && len < best_len)) {
               best_cnt = cnt; best_len = len; best_s = s; best_brk = bk;
@@ -96,7 +120,8 @@ __global__ __launch_bounds__(64) void ladder_search_kernel(
         }
       }
       if (valid) {
-        const uint32_t lost = tracked[rung + s1] == 0 ? 1u : 0u;
+        uint32_t lost = 0u;
+        if constexpr (!MASK) lost = tracked[rung + s1] == 0 ? 1u : 0u;
         kcnt[cur * S + s1] = best_cnt + (lost << 16);
         klen[cur * S + s1] = best_len;
         pred[rung + s1] = (uint8_t)best_s;
@@ -119,12 +144,40 @@ __global__ __launch_bounds__(64) void ladder_search_kernel(
   n_tracked[b] = T - (int)(end_cnt >> 16);
   n_breaks[b] = (int)(end_cnt & 0xffffu);
   path_length[b] = end_len;
+  int n_col = 0;
   for (int t = T - 1; t >= 0; --t) {
     const size_t row = (size_t)b * T + t;
     node_index[row] = node;
     edge_break[row] = (int32_t)((brk[row * nch + (node >> 6)] >> (node & 63)) & 1ull);
-    node = pred[row * S + node];
+    const int from = pred[row * S + node];
+    if constexpr (MASK) {
+      const int col = t ? (int)blocked[(row * S + node) * S + from] : 0;
+      edge_collision[row] = col;
+      n_col += col;
+    }
+    node = from;
   }
+  if constexpr (MASK) n_edge_collisions[b] = n_col;
+}
+
+__global__ __launch_bounds__(64) void ladder_search_kernel(
+    int B, int T, int S, int nq, int nv, int njnt, int TS, const int32_t* __restrict__ jnt, const double* __restrict__ q0,
+    const double* __restrict__ q_nodes, const int32_t* __restrict__ tracked, const double* __restrict__ weights,
+    double max_step_sq, uint8_t* __restrict__ pred, unsigned long long* __restrict__ brk, int32_t* __restrict__ node_index,
+    int32_t* __restrict__ n_tracked, int32_t* __restrict__ n_breaks, double* __restrict__ path_length,
+    int32_t* __restrict__ edge_break) {
+  ladder_search_body<false>(B, T, S, nq, nv, njnt, TS, jnt, q0, q_nodes, tracked, nullptr, weights, max_step_sq, pred, brk, node_index,
+                            n_tracked, n_breaks, path_length, edge_break, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(64) void ladder_search_free_kernel(
+    int B, int T, int S, int nq, int nv, int njnt, int TS, const int32_t* __restrict__ jnt, const double* __restrict__ q0,
+    const double* __restrict__ q_nodes, const int32_t* __restrict__ tracked, const uint8_t* __restrict__ blocked,
+    const double* __restrict__ weights, double max_step_sq, uint8_t* __restrict__ pred, unsigned long long* __restrict__ brk,
+    int32_t* __restrict__ node_index, int32_t* __restrict__ n_tracked, int32_t* __restrict__ n_breaks, double* __restrict__ path_length,
+    int32_t* __restrict__ edge_break, int32_t* __restrict__ edge_collision, int32_t* __restrict__ n_edge_collisions) {
+  ladder_search_body<true>(B, T, S, nq, nv, njnt, TS, jnt, q0, q_nodes, tracked, blocked, weights, max_step_sq, pred, brk, node_index,
+                           n_tracked, n_breaks, path_length, edge_break, edge_collision, n_edge_collisions);
 }
 
 // out[b, t, k] = all[b, t, node_index[b, t], k]: one thread per output element, k fastest.
@@ -158,10 +211,10 @@ __global__ __launch_bounds__(256) void ladder_tracked_kernel(const int32_t* __re
 
 // The source tile of a search launch: the whole rung when it fits beside the destination tile and the keys in 64 KB of LDS, else
 // the largest tile that does; 0 when not even one source node fits.
-int ladder_source_tile(int S, int nq, int nv, int njnt, size_t* lds_bytes) {
+int ladder_source_tile(int S, int nq, int nv, int njnt, size_t* lds_bytes, bool mask) {
   const size_t fixed = (size_t)nq * kLdDest * sizeof(double) + 2 * (size_t)S * (sizeof(double) + sizeof(uint32_t)) +
                        (size_t)nv * sizeof(double) + 3 * (size_t)njnt * sizeof(int32_t);
-  const size_t cap = 64u << 10, node = (size_t)nq * sizeof(double);
+  const size_t cap = 64u << 10, node = (size_t)nq * sizeof(double) + (mask ? kLdDest : 0);
   if (fixed + node > cap) return 0;
   size_t ts = (cap - fixed) / node;
   if (ts > (size_t)S) ts = (size_t)S;
@@ -178,6 +231,20 @@ hipError_t launch_ladder_search(hipStream_t stream, int B, int T, int S, int nq,
   if (B < 1 || T < 1 || S < 1 || S > 256 || T > 65535 || TS < 1) return hipErrorInvalidValue;
   hipLaunchKernelGGL(ladder_search_kernel, dim3((unsigned)B), dim3(64), lds, stream, B, T, S, nq, nv, njnt, TS, jnt, q0, q_nodes, tracked,
                      weights, max_step_sq, pred, brk, node_index, n_tracked, n_breaks, path_length, edge_break);
+  return hipGetLastError();
+}
+
+hipError_t launch_ladder_search_free(hipStream_t stream, int B, int T, int S, int nq, int nv, int njnt, const int32_t* jnt,
+                                     const double* q0, const double* q_nodes, const int32_t* tracked, const uint8_t* blocked,
+                                     const double* weights, double max_step_sq, uint8_t* pred, unsigned long long* brk,
+                                     int32_t* node_index, int32_t* n_tracked, int32_t* n_breaks, double* path_length,
+                                     int32_t* edge_break, int32_t* edge_collision, int32_t* n_edge_collisions) {
+  size_t lds = 0;
+  const int TS = ladder_source_tile(S, nq, nv, njnt, &lds, true);
+  if (B < 1 || T < 1 || S < 1 || S > 256 || T > 65535 || TS < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ladder_search_free_kernel, dim3((unsigned)B), dim3(64), lds, stream, B, T, S, nq, nv, njnt, TS, jnt, q0, q_nodes,
+                     tracked, blocked, weights, max_step_sq, pred, brk, node_index, n_tracked, n_breaks, path_length, edge_break,
+                     edge_collision, n_edge_collisions);
   return hipGetLastError();
 }
 

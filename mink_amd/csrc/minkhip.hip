@@ -184,6 +184,11 @@ enum WsRole {
   // candidates of ONE chunk of rungs in multi-start's WS_C_Q … WS_C_CV, asked for by the call itself.  A host caller's set outputs — N_I32: node_seed_index |
   // node_multiplicity (B, T, K), then n_distinct | n_converged | n_uncovered | seed_index (B, T); N_DIST: node_distance (B, T, K)
   WS_N_I32, WS_N_DIST,
+  // swept clearance and the checked ladder calls: a host caller's q_to as it came (q_from goes through WS_C_Q); the nodes'
+  // clearance margins (B, T, S) and effective tracked flags; the blocked flag of every edge, (B, T, S, S) bytes; every edge's swept
+  // margin when the caller asked for it; a host caller's outputs — F_OUT_I: edge_collision (B, T) | n_edge_collisions (B,), F_OUT_F:
+  // edge_margin (B, T)
+  WS_SW_TO, WS_F_NMARGIN, WS_F_TRK, WS_F_BLOCK, WS_F_EMARGIN, WS_F_OUT_I, WS_F_OUT_F,
   WS_COUNT
 };
 
@@ -1609,6 +1614,60 @@ int32_t mkh_problem_set_collision_check(MkhProblem* p, MkhProblem* checker) {
   return MKH_OK;
 }
 
+// ---- swept clearance (include/minkhip.h "THE RULE OF THE SWEEP"; kernel: sweep.hip)
+// Whether `ck` can be the checker of a sweep: what a clearance refuses, general convex pairs, and the wider LDS slice.
+static int32_t sweep_refuse(const MkhProblem* ck, const char* who) {
+  if (const int32_t rc = clearance_refuse(ck, who)) return rc;
+  if (ck->cv.n_cv > 0)
+    return fail(MKH_E_INVALID, "%s: the checker has general convex pairs (cylinder-box, ellipsoid-*, mesh hulls): they are pre-evaluated on "
+                               "rows in memory, and the samples of a sweep are never written there", who);
+  if (mkh::sweep_lds_bytes(ck->model->nbody, ck->model->nq, ck->dev.n_pairs) > 64 * 1024)
+    return fail(MKH_E_LIMIT, "%s: %d bodies, nq = %d: the poses of a sample and the three rows of q beside them do not fit 64 KB of LDS "
+                             "(7 nbody + 3 nq <= 8192)", who, ck->model->nbody, ck->model->nq);
+  return MKH_OK;
+}
+
+// ... and of a checked call on problem `p`.
+static int32_t sweep_refuse_for(const MkhProblem* p, const MkhProblem* ck, const char* who) {
+  if (!ck) return fail(MKH_E_INVALID, "%s: null checker", who);
+  if (ck->device != p->device)
+    return fail(MKH_E_INVALID, "%s: the checker lives on device %d, the problem on device %d", who, ck->device, p->device);
+  if (ck->model != p->model) return fail(MKH_E_INVALID, "%s: the checker belongs to another MkhModel than the problem", who);
+  return sweep_refuse(ck, who);
+}
+
+int32_t mkh_swept_clearance(MkhProblem* ck, int32_t N, const double* q_from, const double* q_to, int32_t n_samples,
+                            const MkhSweptClearanceIO* io, int32_t flags, void* hip_stream) {
+  const char* const who = "mkh_swept_clearance";
+  if (!ck) return fail(MKH_E_INVALID, "null problem");
+  if (N < 1) return fail(MKH_E_INVALID, "%s: N = %d must be >= 1", who, N);
+  if (n_samples < 1) return fail(MKH_E_INVALID, "%s: n_samples = %d must be >= 1", who, n_samples);
+  if (flags & ~MKH_FLAG_DEVICE_PTRS) return fail(MKH_E_INVALID, "%s: flags = %d: only MKH_FLAG_DEVICE_PTRS is accepted", who, flags);
+  if (!q_from || !q_to || !io || !io->margin || !io->sample || !io->pair)
+    return fail(MKH_E_INVALID, "%s: q_from, q_to, io and its outputs margin, sample, pair are required", who);
+  if (const int32_t rc = sweep_refuse(ck, who)) return rc;
+  const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
+  HIP_OK(hipSetDevice(ck->model->device));
+  Stager st{ck, (hipStream_t)hip_stream, devp, "swept_clearance"};
+  const size_t Nz = N, nq = ck->model->nq;
+  mkh::SweepArgs a{};
+  a.mode = mkh::kSweepPairs; a.M = n_samples; a.N = N;
+  a.from = st.up(WS_C_Q, q_from, Nz * nq);
+  a.to = st.up(WS_SW_TO, q_to, Nz * nq);
+  a.margin = io->margin; a.sample = io->sample; a.pair = io->pair;
+  if (!devp) {
+    a.margin = st.f64(WS_OUT_LEN, Nz);
+    a.sample = st.i32(WS_OUT_PICK, 2 * Nz); a.pair = a.sample ? a.sample + Nz : nullptr;
+  }
+  if (!st.ok()) return st.finish();
+  ST_LAUNCH(st, launch_sweep(st.stream, ck->d_wide, ck->model->nbody, (int)nq, ck->dev.n_pairs, a));
+  if (devp) return st.finish();
+  st.down(io->margin, a.margin, Nz * sizeof(double));
+  st.down(io->sample, a.sample, Nz * sizeof(int32_t));
+  st.down(io->pair, a.pair, Nz * sizeof(int32_t));
+  return st.finish();
+}
+
 // ---- the loop stage of every call that fans a target out to S starts (kernels: multistart.hip, seed_table.hip): the two
 // multi-start calls below, the rungs of the ladder calls and the goals of mkh_solve_goalset.  It works on device arrays and on
 // the caller's Stager; which arrays, the caller says.
@@ -2390,6 +2449,112 @@ int32_t mkh_ladder_select(MkhProblem* p, int32_t B, int32_t T, int32_t S, const 
   return st.finish();
 }
 
+// ---- the checked ladder (include/minkhip.h THE RULE "with a checker"; kernels: sweep.hip, ladder.hip)
+struct LadderFreeOut {             // device arrays: the back-trace's (B, T) / (B,) outputs, and every edge's margin or NULL
+  int32_t *edge_collision, *n_edge_collisions;
+  double *edge_margin, *edge_margin_all;
+};
+
+// The sweep of every edge into a tracked node, the masked search, and the chosen edges' margins — on device arrays, on the call's
+// stream.  d_tracked: the EFFECTIVE flags.
+static void ladder_search_free(Stager& st, const MkhProblem* ck, int B, int T, int S, int M, const double* d_q, const double* d_nodes,
+                               const int32_t* d_tracked, const double* d_w, double max_step_sq, int32_t* o_node, int32_t* o_nt,
+                               int32_t* o_nb, double* o_len, int32_t* o_eb, const LadderFreeOut& f) {
+  const MkhProblem* const p = st.p;
+  const size_t R = (size_t)B * T, nch = ((size_t)S + 63) / 64, E = R * S * S;
+  const int nbody = ck->model->nbody, nq = ck->model->nq, np = ck->dev.n_pairs;
+  uint8_t* const blocked = (uint8_t*)st.need(WS_F_BLOCK, E);
+  unsigned long long* const brk = (unsigned long long*)st.need(WS_L_PRED, R * nch * 8 + R * S);
+  uint8_t* const pred = (uint8_t*)(brk + R * nch);
+  if (!st.ok()) return;
+  // (rung 0 has no edges: its flags are never read, and its margins are NaN — every byte 0xff is one)
+  if (f.edge_margin_all)
+    ST_LAUNCH(st, hipMemset2DAsync(f.edge_margin_all, (size_t)T * S * S * sizeof(double), 0xff, (size_t)S * S * sizeof(double), B, st.stream));
+  if (T > 1) {
+    mkh::SweepArgs a{};
+    a.mode = mkh::kSweepLadder; a.M = M; a.T = T; a.W = S; a.N = (long long)(E - (size_t)B * S * S);
+    a.nodes = d_nodes; a.tracked = d_tracked; a.margin = f.edge_margin_all; a.blocked = blocked;
+    ST_LAUNCH(st, launch_sweep(st.stream, ck->d_wide, nbody, nq, np, a));
+  }
+  ST_LAUNCH(st, launch_ladder_search_free(st.stream, B, T, S, p->dev.nq, p->dev.nv, p->model->njnt, p->ws[WS_JNT].i32(), d_q, d_nodes,
+                                          d_tracked, blocked, d_w, max_step_sq, pred, brk, o_node, o_nt, o_nb, o_len, o_eb,
+                                          f.edge_collision, f.n_edge_collisions));
+  mkh::SweepArgs c{};
+  c.mode = mkh::kSweepPath; c.M = M; c.T = T; c.W = S; c.N = (long long)R;
+  c.nodes = d_nodes; c.tracked = d_tracked; c.node_index = o_node; c.margin = f.edge_margin;
+  ST_LAUNCH(st, launch_sweep(st.stream, ck->d_wide, nbody, nq, np, c));
+}
+
+// What the checked calls refuse about the checker, the sample count and the graph's size.
+static int32_t ladder_free_refuse(const MkhProblem* p, const MkhProblem* ck, int32_t B, int32_t T, int32_t S, int32_t n_samples,
+                                  const MkhLadderFreeIO* f, const char* who) {
+  if (const int32_t rc = sweep_refuse_for(p, ck, who)) return rc;
+  if (n_samples < 1) return fail(MKH_E_INVALID, "%s: n_samples = %d must be >= 1", who, n_samples);
+  if (!f || !f->edge_collision || !f->n_edge_collisions || !f->edge_margin)
+    return fail(MKH_E_INVALID, "%s: free_io and its outputs edge_collision, n_edge_collisions, edge_margin are required", who);
+  if ((long long)B * T * S * S > 0x7fffffffLL)
+    return fail(MKH_E_LIMIT, "%s: B * T * S^2 = %lld edges, at most 2^31 - 1", who, (long long)B * T * S * S);
+  return MKH_OK;
+}
+
+int32_t mkh_ladder_select_free(MkhProblem* p, MkhProblem* ck, int32_t B, int32_t T, int32_t S, const double* q, const double* q_nodes,
+                               const int32_t* tracked, const double* weights, double max_step_sq, int32_t n_samples,
+                               const MkhLadderIO* io, const MkhLadderFreeIO* fio, int32_t flags, void* hip_stream) {
+  const char* const who = "mkh_ladder_select_free";
+  if (!p) return fail(MKH_E_INVALID, "null problem");
+  if (const int32_t rc = ladder_refuse(p, B, T, S, max_step_sq, who)) return rc;
+  if (const int32_t rc = refuse_unwind(flags, who)) return rc;
+  if (!q || !q_nodes || !tracked) return fail(MKH_E_INVALID, "%s: q, q_nodes and tracked are required", who);
+  if (!io || !io->node_index || !io->n_tracked || !io->n_breaks || !io->path_length || !io->edge_break)
+    return fail(MKH_E_INVALID, "%s: io and its outputs node_index, n_tracked, n_breaks, path_length, edge_break are required", who);
+  if (const int32_t rc = ladder_free_refuse(p, ck, B, T, S, n_samples, fio, who)) return rc;
+  if (mkh::ladder_source_tile(S, p->dev.nq, p->dev.nv, p->model->njnt, nullptr, true) < 1)
+    return fail(MKH_E_LIMIT, "%s: nq = %d: one destination tile and one source node with its flags do not fit 64 KB of LDS", who, p->dev.nq);
+  const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
+  if (!devp)
+    if (const int32_t rc = ladder_weights_refuse(weights, p->dev.nv, who)) return rc;
+  HIP_OK(hipSetDevice(p->model->device));
+  if (const int32_t rc = ms_build_tables(p)) return rc;
+  Stager st{p, (hipStream_t)hip_stream, devp, "ladder_select_free"};
+  const size_t Bz = B, R = Bz * T, N = R * S, nq = p->dev.nq, f8 = sizeof(double), i4 = sizeof(int32_t);
+  const double* const d_q = st.up(WS_IN_Q, q, Bz * nq);
+  const double* const d_nodes = st.up(WS_L_Q, q_nodes, N * nq);
+  const double* const d_w = st.up(WS_IN_W, weights, p->dev.nv);
+  const int32_t* const d_trk = st.up_i32(WS_L_TRK, tracked, N);
+  int32_t *o_node = io->node_index, *o_eb = io->edge_break, *o_nt = io->n_tracked, *o_nb = io->n_breaks;
+  double *o_len = io->path_length, *o_q = io->q_path;
+  LadderFreeOut f{fio->edge_collision, fio->n_edge_collisions, fio->edge_margin, fio->edge_margin_all};
+  if (!devp) {
+    o_node = st.i32(WS_OUT_PICK, 2 * R + 2 * Bz); o_eb = o_node + R; o_nt = o_node + 2 * R; o_nb = o_nt + Bz;
+    o_len = st.f64(WS_OUT_LEN, Bz);
+    o_q = io->q_path ? st.f64(WS_OUT_Q, R * nq) : nullptr;
+    f.edge_collision = st.i32(WS_F_OUT_I, R + Bz); f.n_edge_collisions = f.edge_collision ? f.edge_collision + R : nullptr;
+    f.edge_margin = st.f64(WS_F_OUT_F, R);
+    if (f.edge_margin_all) f.edge_margin_all = st.f64(WS_F_EMARGIN, N * S);
+  }
+  double* const d_nm = (double*)st.given_or(WS_F_NMARGIN, fio->node_margin, N * f8);
+  int32_t* const d_eff = st.i32(WS_F_TRK, N);
+  if (!st.ok()) return st.finish();
+  // ---- the nodes' clearance, their effective flags, the edges, the search
+  clearance_rows(st, ck, N, d_nodes, d_nm, nullptr, nullptr, nullptr, nullptr);
+  ST_LAUNCH(st, launch_ladder_free_tracked(st.stream, d_trk, d_nm, (long long)N, d_eff));
+  ladder_search_free(st, ck, B, T, S, n_samples, d_q, d_nodes, d_eff, d_w, max_step_sq, o_node, o_nt, o_nb, o_len, o_eb, f);
+  if (o_q) ST_LAUNCH(st, launch_ladder_gather(st.stream, d_nodes, o_q, o_node, (long long)R, S, (int)nq));
+  if (devp) return st.finish();
+  st.down(io->node_index, o_node, R * i4);
+  st.down(io->edge_break, o_eb, R * i4);
+  st.down(io->n_tracked, o_nt, Bz * i4);
+  st.down(io->n_breaks, o_nb, Bz * i4);
+  st.down(io->path_length, o_len, Bz * f8);
+  st.down(io->q_path, o_q, R * nq * f8);
+  st.down(fio->edge_collision, f.edge_collision, R * i4);
+  st.down(fio->n_edge_collisions, f.n_edge_collisions, Bz * i4);
+  st.down(fio->edge_margin, f.edge_margin, R * f8);
+  st.down(fio->node_margin, d_nm, N * f8);
+  st.down(fio->edge_margin_all, f.edge_margin_all, N * S * f8);
+  return st.finish();
+}
+
 // The refinement pass (include/minkhip.h "THE RULE OF THE REFINEMENT") on device arrays, into device outputs, on the call's stream:
 // the targets' time-major slabs as mkh_solve_trajectory builds them, the working path, then per waypoint of the two sweeps one
 // step kernel and one loop launch through run(), and the guard.  Returns the first refusal of a loop launch; HIP errors are
@@ -2615,11 +2780,42 @@ static LadderCall ladder_stage(Stager& st, int B, int T, int S, int W, const dou
   return c;
 }
 
-// The search on the (B, T, W) nodes, and the chosen nodes' rows.
-static void ladder_pick(Stager& st, int B, int T, int W, const LadderCall& c, double max_step_sq) {
+// A checked call's part of a ladder call (ck == NULL: a plain one): the checker, the samples per edge, and the outputs.
+struct LadderFree {
+  MkhProblem* ck = nullptr;
+  int M = 0;
+  const MkhLadderFreeIO* io = nullptr;
+  LadderFreeOut o{};               // device arrays (ladder_free_stage)
+};
+
+// The device side of a checked call's outputs: the caller's arrays for a device-pointer call, else workspace.
+static void ladder_free_stage(Stager& st, int B, int T, int W, LadderFree& lf) {
+  if (!lf.ck) return;
+  const size_t Bz = B, R = Bz * T;
+  lf.o = LadderFreeOut{lf.io->edge_collision, lf.io->n_edge_collisions, lf.io->edge_margin, lf.io->edge_margin_all};
+  if (st.devp) return;
+  lf.o.edge_collision = st.i32(WS_F_OUT_I, R + Bz); lf.o.n_edge_collisions = lf.o.edge_collision ? lf.o.edge_collision + R : nullptr;
+  lf.o.edge_margin = st.f64(WS_F_OUT_F, R);
+  if (lf.o.edge_margin_all) lf.o.edge_margin_all = st.f64(WS_F_EMARGIN, R * W * W);
+}
+
+static void ladder_free_down(Stager& st, int B, int T, int W, const LadderFree& lf) {
+  if (!lf.ck) return;
+  const size_t Bz = B, R = Bz * T;
+  st.down(lf.io->edge_collision, lf.o.edge_collision, R * sizeof(int32_t));
+  st.down(lf.io->n_edge_collisions, lf.o.n_edge_collisions, Bz * sizeof(int32_t));
+  st.down(lf.io->edge_margin, lf.o.edge_margin, R * sizeof(double));
+  st.down(lf.io->edge_margin_all, lf.o.edge_margin_all, R * W * W * sizeof(double));
+}
+
+// The search on the (B, T, W) nodes — behind the sweep of their edges in a checked call —, and the chosen nodes' rows.
+static void ladder_pick(Stager& st, int B, int T, int W, const LadderCall& c, double max_step_sq, const LadderFree& lf) {
   const long long R = (long long)B * T;
   const int nq = st.p->dev.nq, nv = st.p->dev.nv;
-  ladder_search(st, B, T, W, c.q, c.l_q, c.l_trk, c.w, max_step_sq, c.o_node, c.o_nt, c.o_nb, c.o_len, c.o_eb);
+  if (lf.ck)
+    ladder_search_free(st, lf.ck, B, T, W, lf.M, c.q, c.l_q, c.l_trk, c.w, max_step_sq, c.o_node, c.o_nt, c.o_nb, c.o_len, c.o_eb, lf.o);
+  else
+    ladder_search(st, B, T, W, c.q, c.l_q, c.l_trk, c.w, max_step_sq, c.o_node, c.o_nt, c.o_nb, c.o_len, c.o_eb);
   ST_LAUNCH(st, launch_ladder_gather(st.stream, c.l_q, c.o_q, c.o_node, R, W, nq));
   ST_LAUNCH(st, launch_ladder_gather(st.stream, c.l_v, c.o_v, c.o_node, R, W, nv));
   ST_LAUNCH(st, launch_ladder_gather_i32(st.stream, c.l_st, c.o_st, c.o_node, R, W));
@@ -2682,12 +2878,29 @@ int32_t mkh_solve_trajectory_ladder(MkhProblem* p, int32_t B, int32_t T, int32_t
                                              pos_threshold, ori_threshold, rng_seed, target_index0, io, nullptr, flags, hip_stream);
 }
 
+// The plain ladder call and its checked twin (lf.ck given: mkh_solve_trajectory_ladder_free without n_nodes, which has refused
+// the checker and a refinement already).
+static int32_t ladder_plain_call(MkhProblem* p, LadderFree lf, const char* who, int32_t B, int32_t T, int32_t n_seeds, const double* q,
+                                 const double* frame_targets, const double* posture_target, const double* com_target, double dt,
+                                 double damping, int32_t max_iters, double pos_threshold, double ori_threshold, uint64_t rng_seed,
+                                 int64_t target_index0, const MkhTrajectoryLadderIO* io, const MkhLadderRefineIO* refine, int32_t flags,
+                                 void* hip_stream);
+
 int32_t mkh_solve_trajectory_ladder_refined(MkhProblem* p, int32_t B, int32_t T, int32_t n_seeds, const double* q,
                                             const double* frame_targets, const double* posture_target, const double* com_target,
                                             double dt, double damping, int32_t max_iters, double pos_threshold, double ori_threshold,
                                             uint64_t rng_seed, int64_t target_index0, const MkhTrajectoryLadderIO* io,
                                             const MkhLadderRefineIO* refine, int32_t flags, void* hip_stream) {
-  const char* const who = refine ? "mkh_solve_trajectory_ladder_refined" : "mkh_solve_trajectory_ladder";
+  return ladder_plain_call(p, LadderFree{}, refine ? "mkh_solve_trajectory_ladder_refined" : "mkh_solve_trajectory_ladder", B, T, n_seeds,
+                           q, frame_targets, posture_target, com_target, dt, damping, max_iters, pos_threshold, ori_threshold, rng_seed,
+                           target_index0, io, refine, flags, hip_stream);
+}
+
+static int32_t ladder_plain_call(MkhProblem* p, LadderFree lf, const char* who, int32_t B, int32_t T, int32_t n_seeds, const double* q,
+                                 const double* frame_targets, const double* posture_target, const double* com_target, double dt,
+                                 double damping, int32_t max_iters, double pos_threshold, double ori_threshold, uint64_t rng_seed,
+                                 int64_t target_index0, const MkhTrajectoryLadderIO* io, const MkhLadderRefineIO* refine, int32_t flags,
+                                 void* hip_stream) {
   const LoopSpec ls{dt, damping, max_iters, pos_threshold, ori_threshold};
   const int S = n_seeds;
   const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
@@ -2704,6 +2917,7 @@ int32_t mkh_solve_trajectory_ladder_refined(MkhProblem* p, int32_t B, int32_t T,
   Stager st{p, (hipStream_t)hip_stream, devp, "trajectory_ladder"};
   const size_t R = (size_t)B * T, per = (size_t)p->max_batch / S, nq = p->dev.nq, nv = p->dev.nv;
   const LadderCall c = ladder_stage(st, B, T, S, S, q, frame_targets, posture_target, com_target, tab, io, refine, flags);
+  ladder_free_stage(st, B, T, S, lf);
   // (without the caller's seeds_out the starts of one chunk go through multi-start's candidate slot; the loops write the nodes)
   double* const c_q = c.l_starts ? nullptr : st.f64(WS_C_Q, (per < R ? per : R) * S * nq);
   if (!st.ok()) return st.finish();
@@ -2714,10 +2928,12 @@ int32_t mkh_solve_trajectory_ladder_refined(MkhProblem* p, int32_t B, int32_t T,
                   nullptr};
   };
   if (const int32_t rc = ms_rungs(st, R, S, c.in, ls, rng_seed, target_index0 * T, flags, rows_at)) return st.finish(rc);
+  // (a checked call: MKH_ST_IN_COLLISION into the nodes' status rows, so that a colliding node is not tracked)
+  if (lf.ck) clearance_rows(st, lf.ck, R * S, c.l_q, nullptr, nullptr, nullptr, nullptr, c.l_st);
   ST_LAUNCH(st, launch_ladder_tracked(st.stream, c.l_cv, c.l_st, (long long)(R * S), c.l_trk));
-  ladder_pick(st, B, T, S, c, io->max_step_sq);
+  ladder_pick(st, B, T, S, c, io->max_step_sq, lf);
   if (const int32_t rc = ladder_refine_qvel(st, B, T, S, c, ls, io, refine != nullptr, flags)) return st.finish(rc);
-  if (!devp) ladder_down(st, B, T, S, S, c, io, refine);
+  if (!devp) ladder_down(st, B, T, S, S, c, io, refine, [&] { ladder_free_down(st, B, T, S, lf); });
   return st.finish();
 }
 
@@ -2725,13 +2941,29 @@ int32_t mkh_solve_trajectory_ladder_refined(MkhProblem* p, int32_t B, int32_t T,
 // ladder_nodes.hip, ladder.hip): the loops write the candidate buffers of ONE chunk of rungs, which this call requests itself;
 // behind every chunk's loops its unwinding, the distinct-set selection into the chunk's K slots per rung of the node arrays, and
 // the slots' flags.  Everything behind the rungs is the plain ladder's with K for S.
+static int32_t ladder_nodes_call(MkhProblem* p, LadderFree lf, const char* who, int32_t B, int32_t T, int32_t n_seeds, int32_t n_nodes,
+                                 double min_distance, const double* q, const double* frame_targets, const double* posture_target,
+                                 const double* com_target, double dt, double damping, int32_t max_iters, double pos_threshold,
+                                 double ori_threshold, uint64_t rng_seed, int64_t target_index0, const MkhTrajectoryLadderIO* io,
+                                 const MkhLadderNodesIO* nodes, const MkhLadderRefineIO* refine, int32_t flags, void* hip_stream);
+
 int32_t mkh_solve_trajectory_ladder_nodes(MkhProblem* p, int32_t B, int32_t T, int32_t n_seeds, int32_t n_nodes, double min_distance,
                                           const double* q, const double* frame_targets, const double* posture_target,
                                           const double* com_target, double dt, double damping, int32_t max_iters, double pos_threshold,
                                           double ori_threshold, uint64_t rng_seed, int64_t target_index0,
                                           const MkhTrajectoryLadderIO* io, const MkhLadderNodesIO* nodes, const MkhLadderRefineIO* refine,
                                           int32_t flags, void* hip_stream) {
-  const char* const who = "mkh_solve_trajectory_ladder_nodes";
+  return ladder_nodes_call(p, LadderFree{}, "mkh_solve_trajectory_ladder_nodes", B, T, n_seeds, n_nodes, min_distance, q, frame_targets,
+                           posture_target, com_target, dt, damping, max_iters, pos_threshold, ori_threshold, rng_seed, target_index0, io,
+                           nodes, refine, flags, hip_stream);
+}
+
+// ... and its checked twin (lf.ck given: mkh_solve_trajectory_ladder_free with n_nodes).
+static int32_t ladder_nodes_call(MkhProblem* p, LadderFree lf, const char* who, int32_t B, int32_t T, int32_t n_seeds, int32_t n_nodes,
+                                 double min_distance, const double* q, const double* frame_targets, const double* posture_target,
+                                 const double* com_target, double dt, double damping, int32_t max_iters, double pos_threshold,
+                                 double ori_threshold, uint64_t rng_seed, int64_t target_index0, const MkhTrajectoryLadderIO* io,
+                                 const MkhLadderNodesIO* nodes, const MkhLadderRefineIO* refine, int32_t flags, void* hip_stream) {
   const LoopSpec ls{dt, damping, max_iters, pos_threshold, ori_threshold};
   const int S = n_seeds, K = n_nodes;
   const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
@@ -2756,6 +2988,7 @@ int32_t mkh_solve_trajectory_ladder_nodes(MkhProblem* p, int32_t B, int32_t T, i
   const size_t R = (size_t)B * T, M = R * K, nq = p->dev.nq, nv = p->dev.nv, f8 = sizeof(double), i4 = sizeof(int32_t);
   const size_t per = (size_t)p->max_batch / S, chunk = (per < R ? per : R) * S;      // rungs, and loops, of one chunk
   const LadderCall c = ladder_stage(st, B, T, S, K, q, frame_targets, posture_target, com_target, tab, io, refine, flags);
+  ladder_free_stage(st, B, T, K, lf);
   // ---- the candidates of one chunk, in multi-start's slots: the loops run in place in c_q
   double *const c_q = st.f64(WS_C_Q, chunk * nq), *const c_v = st.f64(WS_C_V, chunk * nv);
   int32_t *const c_st = st.i32(WS_C_ST, chunk), *const c_it = st.i32(WS_C_IT, chunk), *const c_cv = st.i32(WS_C_CV, chunk);
@@ -2777,6 +3010,8 @@ int32_t mkh_solve_trajectory_ladder_nodes(MkhProblem* p, int32_t B, int32_t T, i
     const double* const ref = c.in.q + r0 * nq;
     if (unwind)
       ST_LAUNCH(st, launch_unwind_turns(st.stream, p->ws[WS_UNW].f64(), (long long)(n * S), S, (int)nq, c_q, ref, c_q));
+    // (a checked call: MKH_ST_IN_COLLISION into the chunk's candidate rows, so that a colliding candidate takes no slot)
+    if (lf.ck) clearance_rows(st, lf.ck, n * S, c_q, nullptr, nullptr, nullptr, nullptr, c_st);
     const mkh::SsOut so{c.l_q + m0 * nq, c.l_v + m0 * nv, c.l_it + m0, c.l_st + m0, n_si + m0, n_mu + m0, n_dist + m0,
                         n_nd + r0, n_nc + r0, n_nu + r0};
     ST_LAUNCH(st, launch_ss_select(st.stream, (int)n, S, K, (int)nq, (int)nv, p->model->njnt, p->ws[WS_JNT].i32(), c_q, c_v, c_st, c_it,
@@ -2784,7 +3019,7 @@ int32_t mkh_solve_trajectory_ladder_nodes(MkhProblem* p, int32_t B, int32_t T, i
     ST_LAUNCH(st, launch_ladder_nodes_flags(st.stream, (long long)n, S, K, c_cv, n_si + m0, c.l_trk + m0, c.l_cv + m0));
   };
   if (const int32_t rc = ms_rungs(st, R, S, c.in, ls, rng_seed, target_index0 * T, flags, rows_at, select)) return st.finish(rc);
-  ladder_pick(st, B, T, K, c, io->max_step_sq);
+  ladder_pick(st, B, T, K, c, io->max_step_sq, lf);
   ST_LAUNCH(st, launch_ladder_gather_i32(st.stream, n_si, n_pick, c.o_node, (long long)R, K));
   if (const int32_t rc = ladder_refine_qvel(st, B, T, K, c, ls, io, refine != nullptr, flags)) return st.finish(rc);
   if (!devp)
@@ -2796,8 +3031,37 @@ int32_t mkh_solve_trajectory_ladder_nodes(MkhProblem* p, int32_t B, int32_t T, i
       st.down(nodes->n_converged, n_nc, R * i4);
       st.down(nodes->n_uncovered, n_nu, R * i4);
       st.down(nodes->seed_index, n_pick, R * i4);
+      ladder_free_down(st, B, T, K, lf);
     });
   return st.finish();
+}
+
+int32_t mkh_solve_trajectory_ladder_free(MkhProblem* p, MkhProblem* ck, int32_t B, int32_t T, int32_t n_seeds, int32_t n_nodes,
+                                         double min_distance, const double* q, const double* frame_targets, const double* posture_target,
+                                         const double* com_target, double dt, double damping, int32_t max_iters, double pos_threshold,
+                                         double ori_threshold, uint64_t rng_seed, int64_t target_index0, int32_t n_samples,
+                                         const MkhTrajectoryLadderIO* io, const MkhLadderNodesIO* nodes, const MkhLadderRefineIO* refine,
+                                         const MkhLadderFreeIO* fio, int32_t flags, void* hip_stream) {
+  const char* const who = "mkh_solve_trajectory_ladder_free";
+  if (!p) return fail(MKH_E_INVALID, "null problem");
+  if (refine) return fail(MKH_E_INVALID, "%s: the refinement pass knows nothing of collisions: refine must be NULL", who);
+  if (n_nodes < 0 || (n_nodes == 0) != (nodes == nullptr))
+    return fail(MKH_E_INVALID, "%s: n_nodes = %d with nodes %s: n_nodes = 0 and nodes = NULL is the plain ladder, n_nodes >= 1 with nodes "
+                               "the ladder on distinct nodes", who, n_nodes, nodes ? "given" : "NULL");
+  const int W = n_nodes ? n_nodes : n_seeds;
+  if (B < 1 || T < 1 || W < 1 || W > 256) return fail(MKH_E_INVALID, "%s: B = %d, T = %d and %d nodes per rung: B, T >= 1, 1 <= nodes <= 256", who, B, T, W);
+  if (const int32_t rc = ladder_free_refuse(p, ck, B, T, W, n_samples, fio, who)) return rc;
+  if (fio->node_margin)
+    return fail(MKH_E_INVALID, "%s: node_margin is mkh_ladder_select_free's output: here the nodes' verdict is MKH_ST_IN_COLLISION in status_all", who);
+  if (mkh::ladder_source_tile(W, p->dev.nq, p->dev.nv, p->model->njnt, nullptr, true) < 1)
+    return fail(MKH_E_LIMIT, "%s: nq = %d: one destination tile and one source node with its flags do not fit 64 KB of LDS", who, p->dev.nq);
+  LadderFree lf;
+  lf.ck = ck; lf.M = n_samples; lf.io = fio;
+  if (!n_nodes)
+    return ladder_plain_call(p, lf, who, B, T, n_seeds, q, frame_targets, posture_target, com_target, dt, damping, max_iters, pos_threshold,
+                             ori_threshold, rng_seed, target_index0, io, nullptr, flags, hip_stream);
+  return ladder_nodes_call(p, lf, who, B, T, n_seeds, n_nodes, min_distance, q, frame_targets, posture_target, com_target, dt, damping,
+                           max_iters, pos_threshold, ori_threshold, rng_seed, target_index0, io, nodes, nullptr, flags, hip_stream);
 }
 
 // ---- goal sets (include/minkhip.h "THE RULE OF THE GOAL SET"; kernel: goalset.hip)

@@ -117,7 +117,7 @@ hipError_t launch_st_query(hipStream_t stream, const double* keys, const double*
 // nodes with its back-trace (pred: B·T·S bytes; brk: B·T·ceil(S / 64) break masks), and the chosen nodes' rows of a (rows, S, W)
 // array gathered through node_index (rows = B·T).  ladder_source_tile: the source nodes per LDS tile of a search launch (0: the
 // model does not fit) and the launch's LDS bytes.
-int ladder_source_tile(int S, int nq, int nv, int njnt, size_t* lds_bytes);
+int ladder_source_tile(int S, int nq, int nv, int njnt, size_t* lds_bytes, bool mask = false);   // (mask: 64 flag bytes per source node more)
 hipError_t launch_ladder_tracked(hipStream_t stream, const int32_t* converged, const int32_t* status, long long total,
                                  int32_t* tracked);
 hipError_t launch_ladder_search(hipStream_t stream, int B, int T, int S, int nq, int nv, int njnt, const int32_t* jnt,
@@ -157,5 +157,37 @@ hipError_t launch_lr_guard(hipStream_t stream, int B, int T, int nq, int nv, int
 constexpr int32_t kStInCollision = 64;   // MKH_ST_IN_COLLISION
 hipError_t launch_clearance(hipStream_t stream, const void* wide_problem, int nbody, int n_pairs, int n_cv, const double* cv, int N,
                             const double* q, double* margin, int32_t* pair, int32_t* n_violated, double* distance, int32_t* status);
+// swept clearance (sweep.hip; include/minkhip.h "THE RULE OF THE SWEEP"): the M interior samples of N edges against the pairs of a
+// checker WITHOUT general convex pairs, one edge per wavefront or per DPP row by launch_clearance's criterion.  Which edges:
+//   kSweepPairs  edge e runs from row e of `from` to row e of `to`, (N, nq) each.
+//   kSweepLadder N = B·(T − 1)·W·W, T >= 2: the edges (b, t >= 1, s', s) from node (t − 1, s) to node (t, s') of `nodes`
+//                (B, T, W, nq), their outputs at ((b·T + t)·W + s')·W + s of (B, T, W, W) arrays whose t = 0 entries the launch
+//                leaves alone; a destination with tracked == 0: not swept — margin NaN, blocked 0.
+//   kSweepPath   N = B·T: the edge into waypoint t of the path `node_index` (B, T) through the same nodes; t = 0: margin +inf;
+//                a destination with tracked == 0: as above.
+// margin is optional; sample and pair (N,) are kSweepPairs' and required there; blocked, bytes, 1 where the edge collides, is the
+// ladder modes' and optional.
+enum : int32_t { kSweepPairs = 0, kSweepLadder = 1, kSweepPath = 2 };
+struct SweepArgs {
+  int32_t mode, M, T, W;
+  long long N;
+  const double *from, *to, *nodes;
+  const int32_t *tracked, *node_index;
+  double* margin;
+  int32_t *sample, *pair;
+  uint8_t* blocked;
+};
+size_t sweep_lds_bytes(int nbody, int nq, int n_pairs);
+hipError_t launch_sweep(hipStream_t stream, const void* wide_problem, int nbody, int nq, int n_pairs, const SweepArgs& a);
+// the nodes of a checked ladder: tracked_out[i] = tracked[i] != 0 && node_margin[i] >= 0
+hipError_t launch_ladder_free_tracked(hipStream_t stream, const int32_t* tracked, const double* node_margin, long long total,
+                                      int32_t* tracked_out);
+// launch_ladder_search with the mask of blocked edges (B, T, S, S) bytes of a kSweepLadder launch (include/minkhip.h THE RULE,
+// "with a checker"), and the back-trace's edge_collision (B, T) and n_edge_collisions (B,)
+hipError_t launch_ladder_search_free(hipStream_t stream, int B, int T, int S, int nq, int nv, int njnt, const int32_t* jnt,
+                                     const double* q0, const double* q_nodes, const int32_t* tracked, const uint8_t* blocked,
+                                     const double* weights, double max_step_sq, uint8_t* pred, unsigned long long* brk,
+                                     int32_t* node_index, int32_t* n_tracked, int32_t* n_breaks, double* path_length,
+                                     int32_t* edge_break, int32_t* edge_collision, int32_t* n_edge_collisions);
 
 }  // namespace mkh

@@ -619,6 +619,16 @@ class Clearance(NamedTuple):
     distance: object = None
 
 
+class SweptClearance(NamedTuple):
+    """Result of CollisionChecker.swept_clearance, each with the leading shape of the edges: `margin` = the smallest clearance
+    margin over the interior samples of the straight joint-space move, `sample` the (lowest) sample index that attains it,
+    `pair` the pair of that sample's clearance, `in_collision` = not (margin >= 0) — a NaN or infinite end collides."""
+    margin: object
+    sample: object
+    pair: object
+    in_collision: object
+
+
 class CollisionChecker:
     """Clearance of configurations on the device, and the `collision_check=` of solve_ik_multistart / solve_ik_solutions /
     solve_ik_goalset (include/minkhip.h "THE RULE OF CLEARANCE").
@@ -696,6 +706,30 @@ class CollisionChecker:
                          ~(o.margin >= 0.0).reshape(lead),
                          None if o.distance is None else o.distance.reshape(lead + (self.n_pairs,)))
 
+    def swept_clearance(self, q_from, q_to, n_samples: int = 8) -> SweptClearance:
+        """The swept clearance of the straight joint-space moves from `q_from` to `q_to` — (nq,), (N, nq) or (..., nq), the
+        same shape —: `n_samples` interior samples per edge at u = i / (n_samples + 1), each judged as `clearance` judges a row
+        (include/minkhip.h "THE RULE OF THE SWEEP"); the ends themselves are not sampled.  The samples are built and evaluated
+        on the device.  Not for checkers with general convex pairs (cylinder-box, ellipsoids, mesh hulls): MinkHipError.
+        numpy in → numpy out; torch tensors on a device in → torch tensors there, on the current stream."""
+        from .configuration import native_model
+
+        if self._closed:
+            raise ValueError("the collision checker is closed")
+        if int(n_samples) < 1:
+            raise ValueError(f"n_samples must be >= 1, got {n_samples}")
+        nq = self.model.nq
+        is_torch = nat._is_torch(q_from) and nat._is_torch(q_to) and q_from.device.type == "cuda" and q_to.device == q_from.device
+        a, b = (q_from, q_to) if is_torch else (_host_array(q_from, "q_from"), _host_array(q_to, "q_to"))
+        if a.ndim < 1 or int(a.shape[-1]) != nq or tuple(b.shape) != tuple(a.shape):
+            raise ValueError(f"q_from and q_to must have one shape (..., {nq}), got {tuple(a.shape)} and {tuple(b.shape)}")
+        lead = tuple(int(x) for x in a.shape[:-1])
+        if 0 in lead:
+            raise ValueError(f"q_from holds no row: shape {tuple(a.shape)}")
+        device = (a.device.index if a.device.index is not None else 0) if is_torch else 0
+        o = self._handle(native_model(self.model, device)).swept_clearance(a.reshape(-1, nq), b.reshape(-1, nq), int(n_samples))
+        return SweptClearance(o.margin.reshape(lead), o.sample.reshape(lead), o.pair.reshape(lead), ~(o.margin >= 0.0).reshape(lead))
+
     def close(self) -> None:
         with self._lock:
             self._closed = True
@@ -710,10 +744,14 @@ class CollisionChecker:
             pass
 
 
-def _check_collision_check(collision_check, configuration: Configuration):
-    """The `collision_check=` keyword of the three fan-out calls, judged on the host."""
+def _check_collision_check(collision_check, configuration: Configuration, edge_samples=None, refine: bool = False):
+    """The `collision_check=` keyword of the fan-out calls, judged on the host (`edge_samples`, `refine`: the ladder calls')."""
     if collision_check is None:
         return
+    if refine:
+        raise ValueError("refine=True together with collision_check: the refinement pass knows nothing of collisions")
+    if edge_samples is not None and int(edge_samples) < 1:
+        raise ValueError(f"edge_samples must be >= 1, got {edge_samples}")
     if not isinstance(collision_check, CollisionChecker):
         raise ValueError(f"collision_check must be a CollisionChecker, got {type(collision_check).__name__}")
     if collision_check.model is not configuration.model:
@@ -1562,6 +1600,82 @@ class LadderPath(NamedTuple):
     edge_break: np.ndarray
 
 
+class FreeLadderPath(NamedTuple):
+    """Result of ladder_path(collision_check=...): LadderPath's fields, in its order, then `edge_collision` (B, T) — the motion
+    into waypoint t passes through collision, entry 0 never —, `n_edge_collisions` (B,), `edge_margin` (B, T) — the swept margin
+    of the chosen edges, +inf at waypoint 0, NaN where the edge was not swept —, `node_margin` (B, T, S) and `edge_margin_all`
+    (B, T, S, S), entry [b, t, s', s].  `n_tracked` counts the waypoints that are tracked, free of collision and entered by a
+    free motion."""
+    node_index: np.ndarray
+    q: np.ndarray
+    n_tracked: np.ndarray
+    n_breaks: np.ndarray
+    path_length: np.ndarray
+    edge_break: np.ndarray
+    edge_collision: np.ndarray
+    n_edge_collisions: np.ndarray
+    edge_margin: np.ndarray
+    node_margin: np.ndarray
+    edge_margin_all: np.ndarray
+
+
+class FreeLadderResult(NamedTuple):
+    """Result of solve_ik_trajectory_ladder(collision_check=...): LadderResult's fields, in its order, and behind them
+    `edge_collision` (B, T), `n_edge_collisions` (B,) and `edge_margin` (B, T) of the chosen path, as in FreeLadderPath."""
+    q: np.ndarray
+    v: np.ndarray
+    status: np.ndarray
+    iters: np.ndarray
+    converged: np.ndarray
+    node_index: np.ndarray
+    n_tracked: np.ndarray
+    n_breaks: np.ndarray
+    path_length: np.ndarray
+    edge_break: np.ndarray
+    qvel: Optional[np.ndarray] = None
+    q_all: Optional[np.ndarray] = None
+    v_all: Optional[np.ndarray] = None
+    status_all: Optional[np.ndarray] = None
+    iters_all: Optional[np.ndarray] = None
+    converged_all: Optional[np.ndarray] = None
+    seeds: Optional[np.ndarray] = None
+    edge_collision: Optional[np.ndarray] = None
+    n_edge_collisions: Optional[np.ndarray] = None
+    edge_margin: Optional[np.ndarray] = None
+
+
+class FreeLadderNodesResult(NamedTuple):
+    """Result of solve_ik_trajectory_ladder(collision_check=..., n_nodes=K): LadderNodesResult's fields, in its order, and behind
+    them `edge_collision`, `n_edge_collisions`, `edge_margin`, as in FreeLadderPath."""
+    q: np.ndarray
+    v: np.ndarray
+    status: np.ndarray
+    iters: np.ndarray
+    converged: np.ndarray
+    node_index: np.ndarray
+    n_tracked: np.ndarray
+    n_breaks: np.ndarray
+    path_length: np.ndarray
+    edge_break: np.ndarray
+    qvel: Optional[np.ndarray] = None
+    q_all: Optional[np.ndarray] = None
+    v_all: Optional[np.ndarray] = None
+    status_all: Optional[np.ndarray] = None
+    iters_all: Optional[np.ndarray] = None
+    converged_all: Optional[np.ndarray] = None
+    seeds: Optional[np.ndarray] = None
+    node_seed_index: Optional[np.ndarray] = None
+    node_multiplicity: Optional[np.ndarray] = None
+    node_distance: Optional[np.ndarray] = None
+    n_distinct: Optional[np.ndarray] = None
+    n_converged: Optional[np.ndarray] = None
+    n_uncovered: Optional[np.ndarray] = None
+    seed_index: Optional[np.ndarray] = None
+    edge_collision: Optional[np.ndarray] = None
+    n_edge_collisions: Optional[np.ndarray] = None
+    edge_margin: Optional[np.ndarray] = None
+
+
 def _max_step_sq(max_step) -> float:
     """The squared gate of the ladder's break rule from the caller's joint-space step (None: no gate)."""
     if max_step is None:
@@ -1601,7 +1715,8 @@ def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt
                                qvel_dt: Optional[float] = None, return_all: bool = False, update: bool = True,
                                max_instances: int = 1 << 20, damping: float = 1e-12, limits: Optional[Sequence] = None,
                                safety_break: bool = False, solver: str = "mi355x", n_nodes: Optional[int] = None,
-                               min_distance: float = 0.1, unwind_turns: bool = False, refine: bool = False):
+                               min_distance: float = 0.1, unwind_turns: bool = False,
+                               collision_check: Optional["CollisionChecker"] = None, edge_samples: int = 8, refine: bool = False):
     """Track a time sequence of targets through a ladder graph: `n_seeds` IK solutions per waypoint, solved independently of
     each other, and a dynamic program on the device that picks one per waypoint — the path that is complete first, free of
     joint-space jumps second and shortest third (the rule in full: include/minkhip.h).  Where solve_ik_trajectory_multistart
@@ -1631,8 +1746,16 @@ def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt
     smaller than without n_nodes and the number of tracked waypoints is the same.  `unwind_turns` (with n_nodes only; alone
     it raises) moves every result to the turn nearest q first, see the function unwind_turns.  The result is then a
     LadderNodesResult — a RefinedLadderNodesResult with refine —: the fields above and, behind them, the selection's.  With
-    n_nodes None the call is the one described above, unchanged."""
+    n_nodes None the call is the one described above, unchanged.
+
+    `collision_check` (a CollisionChecker of the same model; not together with refine): a joint path whose waypoints and motions
+    are free of collision.  Behind the loops every result is checked on the device and a result in collision gets
+    ST_IN_COLLISION (in `status_all`; with n_nodes it takes no slot), so it is not tracked; every edge into a tracked node is
+    swept with `edge_samples` interior samples and the search counts a waypoint entered by a colliding motion as lost (ladder_path
+    states the rule).  The result is a FreeLadderResult / FreeLadderNodesResult: the fields above and `edge_collision`,
+    `n_edge_collisions`, `edge_margin`.  Without collision_check the call takes exactly the path described above."""
     del solver
+    _check_collision_check(collision_check, configuration, edge_samples, bool(refine))
     S, max_iters = int(n_seeds), int(max_iters)
     if n_nodes is None and unwind_turns:
         raise ValueError("unwind_turns works in front of the selection of n_nodes distinct nodes per rung: pass n_nodes")
@@ -1678,8 +1801,18 @@ def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt
               max_step_sq=step_sq, rng_seed=int(rng_seed), weights=weights, qvel_dt=qvel_dt, return_all=bool(return_all),
               refine=bool(refine))
 
+    free_parts = []
+
     def job(handle, lo, hi):
         args = (q[lo:hi], _rows(ft, 0, lo, hi), _rows(pt, 2, lo, hi), _rows(ct, 2, lo, hi), dt, damping)
+        if collision_check is not None:
+            fkw = {k: v for k, v in kw.items() if k != "refine"}
+            if K is not None:
+                fkw.update(n_nodes=K, min_distance=r, unwind_turns=bool(unwind_turns))
+            o, more = handle.solve_trajectory_ladder_free(*args, checker=collision_check, edge_samples=int(edge_samples), target_index0=lo,
+                                                          seeds=_rows(seeds, 0, lo, hi), seed_table=seed_table, **fkw)
+            free_parts.append((lo, more))
+            return RefinedLadderNodesResult(*o[:17], o.repaired, o.refined, *o[20:])
         if K is None:
             o = handle.solve_trajectory_ladder(*args, target_index0=lo, seeds=_rows(seeds, 0, lo, hi), seed_table=seed_table, **kw)
             return RefinedLadderNodesResult(*o[:17], o.repaired, o.refined)
@@ -1704,11 +1837,20 @@ def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt
                        opt(res.qvel), opt(res.q_all), opt(res.v_all), opt(res.status_all), opt(res.iters_all),
                        opt(res.converged_all, True), opt(res.seeds))
     fixed = (un(res.repaired), un(res.refined.astype(bool))) if refine else ()
-    if K is None:
+    if K is None and collision_check is None:
         return RefinedLadderResult(*out, *fixed) if refine else out
+    if K is None:
+        free_parts.sort(key=lambda x: x[0])
+        more = [un(np.concatenate([np.asarray(m[i]) for _, m in free_parts])) for i in range(3)]
+        return FreeLadderResult(*out, more[0].astype(bool), more[1], more[2])
     sets = [un(x) for x in (res.node_seed_index, res.node_multiplicity, res.node_distance, res.n_distinct, res.n_converged,
                             res.n_uncovered, res.seed_index)]
-    return (RefinedLadderNodesResult if refine else LadderNodesResult)(*out, *fixed, *sets)
+    if collision_check is None:
+        return (RefinedLadderNodesResult if refine else LadderNodesResult)(*out, *fixed, *sets)
+    free_parts.sort(key=lambda x: x[0])                     # (shards finish in any order; the rows are told apart by their offset)
+    more = [un(np.concatenate([np.asarray(m[i]) for _, m in free_parts])) for i in range(3)]
+    more[0] = more[0].astype(bool)
+    return FreeLadderNodesResult(*out, *sets, *more)
 
 
 class RefinedPath(NamedTuple):
@@ -1805,13 +1947,21 @@ def refine_path(configuration: Configuration, tasks: Sequence, dt: float, target
                        un(res.status), un(res.iters), un(res.converged.astype(bool)))
 
 
-def ladder_path(configuration: Configuration, q_nodes, tracked=None, max_step: Optional[float] = None, weights=None) -> LadderPath:
+def ladder_path(configuration: Configuration, q_nodes, tracked=None, max_step: Optional[float] = None, weights=None,
+                collision_check: Optional["CollisionChecker"] = None, edge_samples: int = 8) -> LadderPath:
     """The ladder's search alone, over the caller's own rungs (closed-form IK branches, solutions of earlier calls): q_nodes
     (T, S, nq) or (B, T, S, nq), `tracked` (same leading shape, default: every node counts as tracked), the start edge from the
     configuration's q.  The rule — key (untracked, breaks, length), ties to the lowest index — is solve_ik_trajectory_ladder's;
-    the configuration is not changed."""
+    the configuration is not changed.
+
+    `collision_check` (a CollisionChecker of the same model): the path whose waypoints and motions are free of collision.  Every
+    node is checked on the device and a node in collision counts as not tracked; every edge into a tracked node is swept with
+    `edge_samples` interior samples (CollisionChecker.swept_clearance's rule) and a waypoint entered by a colliding motion counts
+    as lost, so the key's first component counts the waypoints that are untracked, in collision or entered through collision.
+    The result is then a FreeLadderPath.  Without collision_check the call is the one above, unchanged."""
     from .tasks import PostureTask
 
+    _check_collision_check(collision_check, configuration, edge_samples)
     step_sq = _max_step_sq(max_step)
     B, nq, nv = configuration.batch_size, configuration.nq, configuration.nv
     q_nodes = _host_array(q_nodes, "q_nodes")
@@ -1829,10 +1979,18 @@ def ladder_path(configuration: Configuration, q_nodes, tracked=None, max_step: O
     # (the search reads the model's joint table through a problem handle: the smallest one, a posture task, serves)
     prob, layout = _compile(configuration, [PostureTask(configuration.model, cost=1.0)], None, 1, devices=configuration.devices[:1])
     with _pin(configuration, layout):
-        out = prob.ladder_select(configuration.q_batch, q_nodes, tracked, step_sq, weights)
+        if collision_check is None:
+            out = prob.ladder_select(configuration.q_batch, q_nodes, tracked, step_sq, weights)
+        else:
+            out, more = prob.ladder_select_free(configuration.q_batch, q_nodes, collision_check, tracked, step_sq, weights,
+                                                int(edge_samples), True)
     un = configuration._unbatch
-    return LadderPath(un(out.node_index), un(out.q), un(out.n_tracked), un(out.n_breaks), un(out.path_length),
+    path = LadderPath(un(out.node_index), un(out.q), un(out.n_tracked), un(out.n_breaks), un(out.path_length),
                       un(out.edge_break.astype(bool)))
+    if collision_check is None:
+        return path
+    return FreeLadderPath(*path, un(more.edge_collision.astype(bool)), un(more.n_edge_collisions), un(more.edge_margin),
+                          un(more.node_margin), un(more.edge_margin_all))
 
 
 def _chunks_and_shards(configuration: Configuration, layout, handles, B: int, chunk: int, n_dev: int, job):
