@@ -4,7 +4,11 @@ by the ladder on 8 distinct unwound nodes per waypoint — once as it is, once w
 checked on the device behind its loop, every joint-space motion between consecutive nodes is swept (`--edge-samples` interior
 samples), and the dynamic program picks the path whose waypoints AND motions are free.
 
-    python examples/batched_collision_free_ladder_ur5e.py --paths 256
+    python examples/batched_collision_free_ladder_ur5e.py --paths 256 [--refine]
+
+With `--refine` a third call adds `refine="free"`: behind the checked search the refinement pass re-solves lost waypoints, breaks
+and waypoints entered through collision from their neighbours on the path, every repair checked as a node and the motions on
+both sides of it swept, on the device.
 
 UR5e, one FrameTask on `attachment_site` (costs 1 / 1, lm_damping 1), ConfigurationLimit, dt = 1, damping = 1e-3, thresholds
 1e-4 / 1e-4, 40 iterations per waypoint, every path started at `home`.  The checker holds every link capsule of the arm against
@@ -35,6 +39,7 @@ def main():
     ap.add_argument("--max-step", type=float, default=1.0, help="joint-space step between waypoints that counts as a break (rad)")
     ap.add_argument("--min-distance", type=float, default=0.02, help="clearance every capsule keeps from floor and wall (m)")
     ap.add_argument("--rng-seed", type=int, default=5)
+    ap.add_argument("--refine", action="store_true", help='also run the checked call with refine="free"')
     args = ap.parse_args()
     B, T, S, K, M = args.paths, args.waypoints, args.seeds, args.n_nodes, args.edge_samples
     rng = np.random.default_rng(20261018)
@@ -67,6 +72,10 @@ def main():
 
     plain, ms_plain = timed(ladder)
     checked, ms_checked = timed(lambda: ladder(collision_check=checker, edge_samples=M))
+    rows = [("plain ladder", plain, ms_plain), ("with collision_check", checked, ms_checked)]
+    if args.refine:
+        refined, ms_refined = timed(lambda: ladder(collision_check=checker, edge_samples=M, refine="free"))
+        rows.append(('... and refine="free"', refined, ms_refined))
 
     def judge(res):
         """Per line: complete, + free of breaks, + free of node collisions, + free of swept collisions — by the checker alone."""
@@ -81,7 +90,7 @@ def main():
 
     print(f"UR5e, {B} Cartesian lines of {T} waypoints, floor and wall; the ladder on {K} distinct unwound nodes of {S} solutions per "
           f"waypoint, {M} samples per motion:")
-    for name, res, ms in (("plain ladder", plain, ms_plain), ("with collision_check", checked, ms_checked)):
+    for name, res, ms in rows:
         complete, clean, still, free, nodes_free, moves_free = judge(res)
         print(f"  {name:22s}: {int(complete.sum()):5d} complete, {int(clean.sum()):5d} + free of breaks, {int(still.sum()):5d} + free of "
               f"node collisions, {int(free.sum()):5d} + free of swept collisions of {B}; {int((~nodes_free).sum()):5d} colliding waypoints, "
@@ -93,6 +102,11 @@ def main():
     entered = tracked[:, 1:]                                                 # (a motion into a lost waypoint is not swept)
     assert (checked.edge_collision[:, 1:][entered] == ~moves_free[entered]).all()
     assert (checked.n_tracked == (tracked & ~checked.edge_collision).sum(axis=1)).all()
+    if args.refine:
+        # the guard: no line comes back with fewer free tracked waypoints than the checked search found
+        assert (refined.n_tracked >= checked.n_tracked).all()
+        print(f"  refined {int(refined.refined.sum())} of {B} lines, {int((refined.repaired != 0).sum())} waypoints repaired; free tracked "
+              f"waypoints {int(checked.n_tracked.sum())} -> {int(refined.n_tracked.sum())} of {B * T}")
     checker.close()
 
 

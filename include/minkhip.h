@@ -1204,6 +1204,57 @@ int32_t mkh_ladder_refine(MkhProblem *problem, int32_t B, int32_t T, const doubl
                           double ori_threshold, const MkhLadderRefineIO *io, int32_t flags, void *hip_stream);
 
 /*
+ * THE RULE OF THE REFINEMENT, with a checker (mkh_ladder_refine_free; mkh_solve_trajectory_ladder_free_refined runs it on the path
+ * it searched): the pass above whose repairs are checked as nodes and whose motions are swept.  The terms are those of THE RULE OF
+ * THE REFINEMENT, of THE RULE "with a checker" and of THE RULE OF THE SWEEP, unchanged; only what follows is amended.  The checker
+ * is an ARGUMENT, M = n_samples >= 1.
+ *   State of a path (the input path p and the working path r alike).  node_margin(t) by THE RULE OF CLEARANCE.  The EFFECTIVE
+ *     flag of waypoint t is tracked(t) != 0 && node_margin(t) >= 0.  For t >= 1, edge_margin(t) is the swept margin of the edge
+ *     INTO t with M samples; that edge is swept iff its DESTINATION is effectively tracked, whatever its source is — otherwise its
+ *     margin is NaN and it does not collide.  The start edge from q[b] is never swept: its margin is +inf.  An edge COLLIDES iff
+ *     it was swept and !(margin >= 0).
+ *   Initial state of r = that of p: one clearance of the B·T rows of p on the checker handle (in chunks of its max_batch, as
+ *     mkh_ladder_select_free's nodes) and one sweep of the path's edges — p seen as a ladder of width 1.
+ *   Forward, waypoint t.  BAD when r_t is not effectively tracked, or — t >= 1 — c(r_{t-1} -> r_t) > max_step_sq, or — t >= 1 —
+ *     the edge into t collides.  Bad instances start at r_{t-1} (q[b] for t = 0), as before.  The result x of a bad instance is
+ *     ACCEPTED when it tracks, margin(x) >= 0 and, for t >= 1, c(r_{t-1} -> x) <= max_step_sq and the swept edge r_{t-1} -> x does
+ *     not collide.  Accepted: r_t = x, effectively tracked, repaired = 1, the loop's rows are taken, as before; node_margin(t) =
+ *     margin(x); edge_margin(t) = that sweep's margin (t = 0: +inf stays); and for t + 1 < T edge_margin(t+1) is evaluated anew
+ *     for the edge x -> r_{t+1} — swept iff r_{t+1} is effectively tracked, else NaN.  Otherwise nothing of (b, t) changes.
+ *   Backward, t = T-2 ... 0.  BAD when r_t is not effectively tracked, or c(r_t -> r_{t+1}) > max_step_sq, or the edge into t + 1
+ *     collides.  Bad instances start at r_{t+1}.  x is accepted when it tracks, margin(x) >= 0, c(x -> r_{t+1}) <= max_step_sq
+ *     and the edge x -> r_{t+1} does not collide (it is swept iff r_{t+1} is effectively tracked).  Accepted: repaired = 2;
+ *     edge_margin(t+1) = that sweep's margin; for t >= 1 edge_margin(t) is evaluated anew for r_{t-1} -> x — its destination x is
+ *     tracked, so it is always swept.  That edge is judged at t - 1, the next step, exactly as a new break is.
+ *   Guard.  The key is the checked ladder's: waypoint t counts as LOST when it is not effectively tracked, or — t >= 1 — the edge
+ *     into it collides; breaks and length are unchanged.  r is returned only on a strictly smaller key; otherwise every output is
+ *     the input path's, bit for bit.  tracked_out holds the EFFECTIVE flags of the returned path: a kept node that collides comes
+ *     back with 0.  New outputs, of the returned path: node_margin (B, T); edge_margin (B, T), entry 0 = +inf, NaN where the edge
+ *     was not swept; edge_collision (B, T), entry 0 = 0; n_edge_collisions (B,).  n_tracked = T - lost counts the waypoints that
+ *     are tracked, free, and entered by a free motion.
+ *   NaN.  "A NaN decides", as in the two rules used: a candidate with a NaN row is in collision and is never accepted.
+ * The checks run on the device between the loop launch of a waypoint and the kernel that commits it: per bad instance whose x
+ * tracks at most 2M + 1 rows — margin(x); the edge the acceptance judges; the edge the commit would create — built in LDS, only
+ * three margins per instance (and per block its samples are dealt to) written; a colliding x skips its edges.  No host synchronisation between steps.
+ *
+ * mkh_ladder_refine_free: mkh_ladder_refine's arguments, refusals and pointer conventions, with the checker, n_samples and the
+ * new outputs.  The checker is refused as mkh_ladder_select_free refuses it (general convex pairs, another model, another device;
+ * n_samples < 1); a checker ATTACHED to the problem is refused as before.  "One call in flight per checker handle" holds.
+ */
+typedef struct MkhLadderRefineFreeIO {
+  int32_t *edge_collision;     /* (B, T)  1 where the edge into waypoint t of the returned path collides         required  */
+  int32_t *n_edge_collisions;  /* (B,)    colliding edges on the returned path                                  required  */
+  double *edge_margin;         /* (B, T)  the swept margins of its edges                                        required  */
+  double *node_margin;         /* (B, T)  optional: the clearance margins of its nodes                                    */
+} MkhLadderRefineFreeIO;
+int32_t mkh_ladder_refine_free(MkhProblem *problem, MkhProblem *checker, int32_t B, int32_t T, const double *q,
+                               const double *q_path, const int32_t *tracked_path, const double *frame_targets,
+                               const double *posture_target, const double *com_target, double dt, double damping,
+                               int32_t max_iters, double pos_threshold, double ori_threshold, int32_t n_samples,
+                               const MkhLadderRefineIO *io, const MkhLadderRefineFreeIO *free_io, int32_t flags,
+                               void *hip_stream);
+
+/*
  * mkh_solve_trajectory_ladder_refined: mkh_solve_trajectory_ladder and, with `refine` != NULL, the pass above on the path it
  * searched — the rungs, the search, the gathers and the pass on the device, nothing over the bus in between.  The result is
  * BITWISE mkh_solve_trajectory_ladder followed by mkh_ladder_refine on its outputs (q_traj and the chosen nodes' tracked flags
@@ -1282,7 +1333,7 @@ int32_t mkh_solve_trajectory_ladder_nodes(MkhProblem *problem, int32_t B, int32_
  * mkh_solve_trajectory_ladder_free: the ladder calls above with THE RULE "with a checker" in place of THE RULE.  The arguments
  * are those of the call on distinct nodes, with the checker, n_samples and the MkhLadderFreeIO: n_nodes = 0 with nodes = NULL is
  * mkh_solve_trajectory_ladder on n_seeds nodes per rung, n_nodes = K >= 1 with nodes the ladder on K distinct nodes (anything
- * else: MKH_E_INVALID).  `refine` must be NULL: the refinement pass knows nothing of collisions — Not covered.
+ * else: MKH_E_INVALID).  `refine` must be NULL here: the checked pass is mkh_solve_trajectory_ladder_free_refined's, below.
  *   Behind the loops of every chunk of rungs the clearance of the candidates' final q runs on the checker and
  *   MKH_ST_IN_COLLISION is OR-ed into their status rows — status_all in the plain ladder; the chunk's candidate rows in the call
  *   on nodes, behind the optional unwinding and in front of the selection, so that a colliding candidate takes no slot and a
@@ -1301,6 +1352,24 @@ int32_t mkh_solve_trajectory_ladder_free(MkhProblem *problem, MkhProblem *checke
                                          int64_t target_index0, int32_t n_samples, const MkhTrajectoryLadderIO *io,
                                          const MkhLadderNodesIO *nodes, const MkhLadderRefineIO *refine,
                                          const MkhLadderFreeIO *free_io, int32_t flags, void *hip_stream);
+
+/*
+ * mkh_solve_trajectory_ladder_free_refined: mkh_solve_trajectory_ladder_free's arguments with `refine` REQUIRED (of it only
+ * tracked_out, repaired and refined are used, as in the plain refined calls).  The result is BITWISE
+ * mkh_solve_trajectory_ladder_free followed by mkh_ladder_refine_free on its outputs: q_traj as the path, the chosen nodes'
+ * effective flags as its flags, v_traj ... converged pre-filled.  The returned path goes where the ladder's goes; free_io's
+ * edge_collision, n_edge_collisions and edge_margin follow the returned path (edge_margin_all stays the search's; node_margin
+ * must be NULL as above); qvel follows the returned path; node_index keeps the search's choice.  n_nodes = 0 and n_nodes = K
+ * as in mkh_solve_trajectory_ladder_free, which keeps refusing a `refine` of its own.
+ */
+int32_t mkh_solve_trajectory_ladder_free_refined(MkhProblem *problem, MkhProblem *checker, int32_t B, int32_t T, int32_t n_seeds,
+                                                 int32_t n_nodes, double min_distance, const double *q,
+                                                 const double *frame_targets, const double *posture_target,
+                                                 const double *com_target, double dt, double damping, int32_t max_iters,
+                                                 double pos_threshold, double ori_threshold, uint64_t rng_seed,
+                                                 int64_t target_index0, int32_t n_samples, const MkhTrajectoryLadderIO *io,
+                                                 const MkhLadderNodesIO *nodes, const MkhLadderRefineIO *refine,
+                                                 const MkhLadderFreeIO *free_io, int32_t flags, void *hip_stream);
 
 /* Same inputs; additionally writes the requested intermediates (build_ik / compute_error /
  * compute_jacobian / get_transform_frame_to_world parity taps).  v_out/status_out may be NULL

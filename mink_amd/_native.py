@@ -586,6 +586,36 @@ class LadderFreeOut(NamedTuple):
     edge_margin_all: object = None
 
 
+LADDER_REFINE_FREE_IO_FIELDS = ("edge_collision", "n_edge_collisions", "edge_margin", "node_margin")
+
+
+class MkhLadderRefineFreeIO(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in LADDER_REFINE_FREE_IO_FIELDS]
+
+
+class LadderRefineFreeOut(NamedTuple):
+    """What NativeProblem.ladder_refine_free returns (include/minkhip.h "THE RULE OF THE REFINEMENT, with a checker"):
+    LadderRefineOut's fields in its order — `tracked` the EFFECTIVE flags of the returned path —, then of the returned path
+    edge_collision (B, T) int32, n_edge_collisions (B,) int32, edge_margin (B, T) (entry 0 +inf, NaN where not swept) and
+    node_margin (B, T)."""
+    q: object
+    tracked: object
+    repaired: object
+    refined: object
+    edge_break: object
+    n_tracked: object
+    n_breaks: object
+    path_length: object
+    v: object = None
+    status: object = None
+    iters: object = None
+    converged: object = None
+    edge_collision: object = None
+    n_edge_collisions: object = None
+    edge_margin: object = None
+    node_margin: object = None
+
+
 class MkhTaps(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in TAP_NAMES]
 
@@ -712,6 +742,12 @@ def lib() -> C.CDLL:
         common[2:8] + [C.c_int32, C.c_double, C.c_double, C.c_uint64, C.c_int64, C.c_int32, C.POINTER(MkhTrajectoryLadderIO),
                        C.POINTER(MkhLadderNodesIO), C.POINTER(MkhLadderRefineIO), C.POINTER(MkhLadderFreeIO), C.c_int32, C.c_void_p]
     L.mkh_solve_trajectory_ladder_free.restype = C.c_int32
+    L.mkh_solve_trajectory_ladder_free_refined.argtypes = L.mkh_solve_trajectory_ladder_free.argtypes
+    L.mkh_solve_trajectory_ladder_free_refined.restype = C.c_int32
+    L.mkh_ladder_refine_free.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p] + \
+        common[3:8] + [C.c_int32, C.c_double, C.c_double, C.c_int32, C.POINTER(MkhLadderRefineIO),
+                       C.POINTER(MkhLadderRefineFreeIO), C.c_int32, C.c_void_p]
+    L.mkh_ladder_refine_free.restype = C.c_int32
     for f in ("mkh_seed_table_create", "mkh_seed_table_read", "mkh_seed_table_query", "mkh_problem_set_seed_table"):
         getattr(L, f).restype = C.c_int32
     for f in ("mkh_model_create", "mkh_problem_create", "mkh_problem_num_task_rows",
@@ -735,6 +771,7 @@ EXPORTED_SYMBOLS = (
     "mkh_solve_goalset", "mkh_select_goalset", "mkh_unwind_turns", "mkh_solve_trajectory_ladder_nodes",
     "mkh_clearance", "mkh_problem_set_collision_check",
     "mkh_swept_clearance", "mkh_ladder_select_free", "mkh_solve_trajectory_ladder_free",
+    "mkh_ladder_refine_free", "mkh_solve_trajectory_ladder_free_refined",
 )
 
 LIE_OPS = {"se3_log": (0, 7, 0, (6,)), "se3_jlog": (1, 7, 0, (6, 6)), "se3_ljacinv": (2, 6, 0, (6, 6)),
@@ -982,7 +1019,8 @@ class _attached:
 
 
 class _with_checker:
-    """The locks of a call that takes its checker as an argument (mkh_ladder_select_free, mkh_solve_trajectory_ladder_free): the
+    """The locks of a call that takes its checker as an argument (mkh_ladder_select_free, mkh_solve_trajectory_ladder_free,
+    mkh_ladder_refine_free, mkh_solve_trajectory_ladder_free_refined): the
     problem's first, the checker's second; a problem that checks itself has one."""
 
     def __init__(self, problem: "NativeProblem", checker: "NativeProblem"):
@@ -1813,16 +1851,20 @@ class NativeProblem:
                                      min_distance: float = 0.1, unwind_turns: bool = False, max_step_sq: float = float("inf"),
                                      rng_seed: int = 0, target_index0: int = 0, seeds=None, weights=None,
                                      qvel_dt: Optional[float] = None, return_all: bool = False, wave_kernel: bool = False,
-                                     lane_kernel: bool = False, quad_kernel: bool = False, seed_table=None):
+                                     lane_kernel: bool = False, quad_kernel: bool = False, seed_table=None,
+                                     refine: bool = False):
         """mkh_solve_trajectory_ladder_free: solve_trajectory_ladder (n_nodes None) or solve_trajectory_ladder_nodes under THE
         RULE "with a checker": colliding candidates get ST_IN_COLLISION behind the loops, every edge into a tracked node is swept
-        with `edge_samples` interior samples, and the search runs on the mask.  Returns (the plain call's result, LadderFreeOut)."""
+        with `edge_samples` interior samples, and the search runs on the mask.  Returns (the plain call's result, LadderFreeOut).
+        With `refine` the checked refinement pass runs on the chosen path behind the search
+        (mkh_solve_trajectory_ladder_free_refined; the handle then needs max_batch >= B as well): the plain result carries
+        `tracked`, `repaired`, `refined`, and LadderFreeOut follows the returned path."""
         checker = _checker_handle(self, checker, edge_samples)
         nodes = None if n_nodes is None else (int(n_nodes), float(min_distance), bool(unwind_turns))
         return self._solve_trajectory_ladder(q, frame_targets, posture_target, com_target, dt, damping, n_seeds, max_iters,
                                              pos_threshold, ori_threshold, max_step_sq, rng_seed, target_index0, seeds, weights,
-                                             qvel_dt, return_all, wave_kernel, lane_kernel, quad_kernel, seed_table, False, nodes,
-                                             (checker, int(edge_samples)))
+                                             qvel_dt, return_all, wave_kernel, lane_kernel, quad_kernel, seed_table, bool(refine),
+                                             nodes, (checker, int(edge_samples)))
 
     def _solve_trajectory_ladder(self, q, frame_targets, posture_target, com_target, dt, damping, n_seeds, max_iters,
                                  pos_threshold, ori_threshold, max_step_sq, rng_seed, target_index0, seeds, weights, qvel_dt,
@@ -1916,10 +1958,11 @@ class NativeProblem:
         if free is not None:
             more = LadderFreeOut(empty((B, T), i4), empty((B,), i4), empty((B, T), f8))
             fio = MkhLadderFreeIO(*[ptr(x) for x in more])
+            free_call = lib().mkh_solve_trajectory_ladder_free_refined if refine else lib().mkh_solve_trajectory_ladder_free
         if nodes is None:
             with _with_checker(self, free[0]), _attached(self, seed_table):
-                _check(lib().mkh_solve_trajectory_ladder_free(self.handle, free[0].handle, B, T, S, 0, 0.0, *head[:-1], free[1], head[-1],
-                                                              None, None, C.byref(fio), flags, stream))
+                _check(free_call(self.handle, free[0].handle, B, T, S, 0, 0.0, *head[:-1], free[1], head[-1],
+                                 None, *tail, C.byref(fio), flags, stream))
             return TrajectoryLadderOut(*plain), more
         K, r, unwind = nodes
         sets = {"node_seed_index": empty((B, T, K), i4), "node_multiplicity": empty((B, T, K), i4),
@@ -1930,9 +1973,8 @@ class NativeProblem:
             setattr(nio, n, ptr(x))
         if free is not None:
             with _with_checker(self, free[0]), _attached(self, seed_table):
-                _check(lib().mkh_solve_trajectory_ladder_free(self.handle, free[0].handle, B, T, S, K, r, *head[:-1], free[1], head[-1],
-                                                              C.byref(nio), None, C.byref(fio), flags | (FLAG_UNWIND_TURNS if unwind else 0),
-                                                              stream))
+                _check(free_call(self.handle, free[0].handle, B, T, S, K, r, *head[:-1], free[1], head[-1],
+                                 C.byref(nio), *tail, C.byref(fio), flags | (FLAG_UNWIND_TURNS if unwind else 0), stream))
             return TrajectoryLadderNodesOut(*plain, *[sets[n] for n in LADDER_NODES_IO_FIELDS]), more
         with self._lock, _attached(self, seed_table):
             _check(lib().mkh_solve_trajectory_ladder_nodes(self.handle, B, T, S, K, r, *head, C.byref(nio), *tail,
@@ -1943,7 +1985,28 @@ class NativeProblem:
                       damping: float = 1e-12, *, max_iters: int, pos_threshold: float, ori_threshold: float,
                       max_step_sq: float = float("inf"), weights=None, v=None, status=None, iters=None, converged=None,
                       wave_kernel: bool = False, lane_kernel: bool = False, quad_kernel: bool = False) -> LadderRefineOut:
-        """mkh_ladder_refine: the refinement pass of include/minkhip.h "THE RULE OF THE REFINEMENT" over the caller's path —
+        return self._ladder_refine(q, q_path, tracked, frame_targets, posture_target, com_target, dt, damping, max_iters,
+                                   pos_threshold, ori_threshold, max_step_sq, weights, v, status, iters, converged, wave_kernel,
+                                   lane_kernel, quad_kernel, None)
+
+    def ladder_refine_free(self, q, q_path, checker: "NativeProblem", tracked=None, frame_targets=None, posture_target=None,
+                           com_target=None, dt: float = 1e-2, damping: float = 1e-12, *, max_iters: int, pos_threshold: float,
+                           ori_threshold: float, edge_samples: int = 8, max_step_sq: float = float("inf"), weights=None, v=None,
+                           status=None, iters=None, converged=None, wave_kernel: bool = False, lane_kernel: bool = False,
+                           quad_kernel: bool = False) -> LadderRefineFreeOut:
+        """mkh_ladder_refine_free: ladder_refine under "THE RULE OF THE REFINEMENT, with a checker" — `checker` a handle with
+        collision limits on the same model and device; every repair candidate is checked as a node and the motions on both
+        sides of it are swept with `edge_samples` interior samples, on the device between the loops."""
+        checker = _checker_handle(self, checker, edge_samples)
+        return self._ladder_refine(q, q_path, tracked, frame_targets, posture_target, com_target, dt, damping, max_iters,
+                                   pos_threshold, ori_threshold, max_step_sq, weights, v, status, iters, converged, wave_kernel,
+                                   lane_kernel, quad_kernel, (checker, int(edge_samples)))
+
+    def _ladder_refine(self, q, q_path, tracked, frame_targets, posture_target, com_target, dt, damping, max_iters, pos_threshold,
+                       ori_threshold, max_step_sq, weights, v, status, iters, converged, wave_kernel, lane_kernel, quad_kernel,
+                       free):
+        """The body of ladder_refine and ladder_refine_free (`free`: None, or (checker, edge_samples)).
+        mkh_ladder_refine: the refinement pass of include/minkhip.h "THE RULE OF THE REFINEMENT" over the caller's path —
         q (B, nq) the current postures, q_path (B, T, nq), tracked (B, T) (None: every node), the targets in
         solve_trajectory_ladder's shapes, the loop parameters of the re-tracking sweeps, the squared break gate, weights (nv,)
         >= 0.  `v` (B, T, nv), `status`, `iters`, `converged` (B, T): what the caller knows of its path's nodes; copies come
@@ -2025,6 +2088,15 @@ class NativeProblem:
         io.weights, io.max_step_sq = ptr(weights), float(max_step_sq)
         for n, x in out.items():
             setattr(io, n, ptr(x))
+        if free is not None:
+            more = [empty((B, T), i4), empty((B,), i4), empty((B, T), f8), empty((B, T), f8)]
+            fio = MkhLadderRefineFreeIO(*[ptr(x) for x in more])
+            with _with_checker(self, free[0]):
+                _check(lib().mkh_ladder_refine_free(self.handle, free[0].handle, B, T, ptr(q), ptr(q_path), ptr(tracked),
+                                                    ptr(frame_targets), ptr(posture_target), ptr(com_target), float(dt),
+                                                    float(damping), max_iters, float(pos_threshold), float(ori_threshold), free[1],
+                                                    C.byref(io), C.byref(fio), flags, stream))
+            return LadderRefineFreeOut(*[out[n] for n in LADDER_REFINE_IO_FIELDS[2:]], *more)
         with self._lock:
             _check(lib().mkh_ladder_refine(self.handle, B, T, ptr(q), ptr(q_path), ptr(tracked), ptr(frame_targets),
                                            ptr(posture_target), ptr(com_target), float(dt), float(damping), max_iters,

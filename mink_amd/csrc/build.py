@@ -328,6 +328,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     jobs.append((os.path.join(HERE, "unwind.hip"), os.path.join(BUILD, "unwind.o")))   # turn unwinding of mkh_unwind_turns / MKH_FLAG_UNWIND_TURNS
     jobs.append((os.path.join(HERE, "ladder_nodes.hip"), os.path.join(BUILD, "ladder_nodes.o")))   # node flags of mkh_solve_trajectory_ladder_nodes
     jobs.append((os.path.join(HERE, "clearance.hip"), os.path.join(BUILD, "clearance.o")))   # clearance of a batch of rows: mkh_clearance, the collision check behind the multi-start loops
+    jobs.append((os.path.join(HERE, "ladder_refine_free.hip"), os.path.join(BUILD, "ladder_refine_free.o")))   # lr_check_kernel: the collision check between the loops of mkh_ladder_refine_free
     jobs.append((os.path.join(HERE, "sweep.hip"), os.path.join(BUILD, "sweep.o")))   # swept clearance of edges: mkh_swept_clearance, the edge mask of the checked ladder calls
 
     def compile_one(job):

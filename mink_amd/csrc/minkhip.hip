@@ -189,6 +189,11 @@ enum WsRole {
   // margin when the caller asked for it; a host caller's outputs — F_OUT_I: edge_collision (B, T) | n_edge_collisions (B,), F_OUT_F:
   // edge_margin (B, T)
   WS_SW_TO, WS_F_NMARGIN, WS_F_TRK, WS_F_BLOCK, WS_F_EMARGIN, WS_F_OUT_I, WS_F_OUT_F,
+  // a ladder refinement with a checker: RF_MARGIN: the node margins and the edge margins of the input path, then of the working
+  // path, (B, T) each; RF_TRIP: what lr_check_kernel leaves per step, (B, 3, slots); RF_IDX: the index array of the input path seen as a
+  // ladder of width 1 (zeros) | its effective flags, (B, T) each.  A host caller's outputs go through F_OUT_I, F_OUT_F and
+  // F_NMARGIN, as a checked ladder's do
+  WS_RF_MARGIN, WS_RF_TRIP, WS_RF_IDX,
   WS_COUNT
 };
 
@@ -2559,9 +2564,19 @@ int32_t mkh_ladder_select_free(MkhProblem* p, MkhProblem* ck, int32_t B, int32_t
 // the targets' time-major slabs as mkh_solve_trajectory builds them, the working path, then per waypoint of the two sweeps one
 // step kernel and one loop launch through run(), and the guard.  Returns the first refusal of a loop launch; HIP errors are
 // latched in `st`.
+// With a checker (rf != NULL: "THE RULE OF THE REFINEMENT, with a checker"; kernels: ladder_refine_free.hip and the _free builds of
+// ladder_refine.hip) the state of the input path comes first — one clearance of its rows on the checker handle, one kSweepPath
+// launch over it as a ladder of width 1 —, lr_check_kernel runs between every loop launch and its step kernel, and the guard
+// compares on the amended key.  Nothing of it touches the plain pass.
+struct RefineFree {
+  MkhProblem* ck;
+  int M;                           // samples per edge
+  double *node_margin, *edge_margin;             // device outputs of the returned path, (B, T); node_margin: optional
+  int32_t *edge_collision, *n_edge_collisions;   // (B, T), (B,)
+};
 static int32_t refine_pass(Stager& st, int B, int T, const double* d_q, const double* d_path, const int32_t* d_trk, const double* d_ft,
                            const double* d_pt, const double* d_ct, const LoopSpec& ls, const double* d_w, double max_step_sq,
-                           const mkh::LrOut& out, int32_t flags) {
+                           const mkh::LrOut& out, int32_t flags, const RefineFree* rf = nullptr) {
   MkhProblem* const p = st.p;
   const DeviceProblem& P = p->dev;
   hipStream_t stream = st.stream;
@@ -2583,15 +2598,40 @@ static int32_t refine_pass(Stager& st, int B, int T, const double* d_q, const do
   w.r_rep = w.r_trk + R; w.r_st = w.r_trk + 2 * R; w.r_it = w.r_trk + 3 * R; w.r_cv = w.r_trk + 4 * R; w.r_eb = w.r_trk + 5 * R;
   w.start = st.f64(WS_R_X, Bz * (2 * nq + nv)); w.x = w.start + Bz * nq; w.xv = w.x + Bz * nq;
   w.xst = st.i32(WS_R_XI, 4 * Bz); w.xit = w.xst + Bz; w.xcv = w.xst + 2 * Bz; w.bad = w.xst + 3 * Bz;
+  mkh::LrFreeWork fw{};
+  double *p_nm = nullptr, *p_em = nullptr;
+  int32_t *p_idx = nullptr, *p_eff = nullptr;
+  if (rf) {
+    p_nm = st.f64(WS_RF_MARGIN, 4 * R); p_em = p_nm + R; fw.r_nm = p_nm + 2 * R; fw.r_em = p_nm + 3 * R;
+    fw.slots = mkh::lr_check_slots(rf->M);
+    fw.trip = st.f64(WS_RF_TRIP, 3 * Bz * fw.slots);
+    p_idx = st.i32(WS_RF_IDX, 2 * R); p_eff = p_idx + R;
+  }
   if (!st.ok()) return MKH_OK;
+  const int ck_nbody = rf ? rf->ck->model->nbody : 0, ck_np = rf ? rf->ck->dev.n_pairs : 0;
+  if (rf) {                                                  // the state of p: its nodes' margins, effective flags, edges' margins
+    clearance_rows(st, rf->ck, R, d_path, p_nm, nullptr, nullptr, nullptr, nullptr);
+    ST_LAUNCH(st, launch_ladder_free_tracked(stream, d_trk, p_nm, (long long)R, p_eff));
+    st.latch(hipMemsetAsync(p_idx, 0, R * i4, stream));
+    mkh::SweepArgs a{};
+    a.mode = mkh::kSweepPath; a.M = rf->M; a.T = T; a.W = 1; a.N = (long long)R;
+    a.nodes = d_path; a.tracked = p_eff; a.node_index = p_idx; a.margin = p_em;
+    ST_LAUNCH(st, launch_sweep(stream, rf->ck->d_wide, ck_nbody, (int)nq, ck_np, a));
+    st.latch(hipMemcpyAsync(fw.r_nm, p_nm, 2 * R * f8, hipMemcpyDeviceToDevice, stream));     // (r's state = p's)
+  }
   st.latch(hipMemcpyAsync(w.r, d_path, R * nq * f8, hipMemcpyDeviceToDevice, stream));
-  st.latch(hipMemcpyAsync(w.r_trk, d_trk, R * i4, hipMemcpyDeviceToDevice, stream));
+  st.latch(hipMemcpyAsync(w.r_trk, rf ? p_eff : d_trk, R * i4, hipMemcpyDeviceToDevice, stream));
   st.latch(hipMemsetAsync(w.r_rep, 0, R * i4, stream));
   const int32_t loop_flags = (flags & ~MKH_FLAG_WARM_START) | MKH_FLAG_DEVICE_PTRS;
   const int njnt = p->model->njnt;
   const int32_t* const jnt = p->ws[WS_JNT].i32();
   auto step = [&](int ct, int cdir, int nt, int ndir) {
-    ST_LAUNCH(st, launch_lr_step(stream, B, T, (int)nq, (int)nv, njnt, jnt, d_q, d_w, max_step_sq, ct, cdir, nt, ndir, w));
+    if (!rf) {
+      ST_LAUNCH(st, launch_lr_step(stream, B, T, (int)nq, (int)nv, njnt, jnt, d_q, d_w, max_step_sq, ct, cdir, nt, ndir, w));
+      return;
+    }
+    if (ct >= 0) ST_LAUNCH(st, launch_lr_check(stream, rf->ck->d_wide, ck_nbody, (int)nq, ck_np, B, T, rf->M, ct, cdir, w, fw.trip));
+    ST_LAUNCH(st, launch_lr_step_free(stream, B, T, (int)nq, (int)nv, njnt, jnt, d_q, d_w, max_step_sq, ct, cdir, nt, ndir, w, fw));
   };
   auto loop = [&](size_t t) -> int32_t {
     if (!st.ok()) return MKH_OK;
@@ -2607,6 +2647,11 @@ static int32_t refine_pass(Stager& st, int B, int T, const double* d_q, const do
   for (int t = T - 2; t >= 0; --t) {                         // backward
     if (const int32_t rc = loop(t)) return rc;
     step(t, -1, t - 1, -1);
+  }
+  if (rf) {
+    const mkh::LrFreeGuard g{p_nm, p_em, fw.r_nm, fw.r_em, rf->node_margin, rf->edge_margin, rf->edge_collision, rf->n_edge_collisions};
+    ST_LAUNCH(st, launch_lr_guard_free(stream, B, T, (int)nq, (int)nv, njnt, jnt, d_q, d_w, max_step_sq, d_path, p_eff, w, out, g));
+    return MKH_OK;
   }
   ST_LAUNCH(st, launch_lr_guard(stream, B, T, (int)nq, (int)nv, njnt, jnt, d_q, d_w, max_step_sq, d_path, d_trk, w, out));
   return MKH_OK;
@@ -2624,17 +2669,24 @@ static int32_t refine_refuse(const MkhProblem* p, int32_t B, int32_t T, double m
   return MKH_OK;
 }
 
-int32_t mkh_ladder_refine(MkhProblem* p, int32_t B, int32_t T, const double* q, const double* q_path, const int32_t* tracked_path,
-                          const double* frame_targets, const double* posture_target, const double* com_target, double dt,
-                          double damping, int32_t max_iters, double pos_threshold, double ori_threshold, const MkhLadderRefineIO* io,
-                          int32_t flags, void* hip_stream) {
-  const char* const who = "mkh_ladder_refine";
+// mkh_ladder_refine (fio == NULL) and mkh_ladder_refine_free (the checker ck, n_samples and fio: the pass "with a checker").
+static int32_t ladder_refine_call(MkhProblem* p, MkhProblem* ck, int32_t n_samples, const MkhLadderRefineFreeIO* fio, const char* who,
+                                  int32_t B, int32_t T, const double* q, const double* q_path, const int32_t* tracked_path,
+                                  const double* frame_targets, const double* posture_target, const double* com_target, double dt,
+                                  double damping, int32_t max_iters, double pos_threshold, double ori_threshold,
+                                  const MkhLadderRefineIO* io, int32_t flags, void* hip_stream, bool free_call) {
   const LoopSpec ls{dt, damping, max_iters, pos_threshold, ori_threshold};
   if (!p) return fail(MKH_E_INVALID, "null problem");
   if (!io) return fail(MKH_E_INVALID, "%s: io is required", who);
   if (const int32_t rc = refine_refuse(p, B, T, io->max_step_sq, ls, who)) return rc;
   if (const int32_t rc = refuse_checker(p, who)) return rc;
   if (const int32_t rc = refuse_unwind(flags, who)) return rc;
+  if (free_call) {
+    if (const int32_t rc = sweep_refuse_for(p, ck, who)) return rc;
+    if (n_samples < 1) return fail(MKH_E_INVALID, "%s: n_samples = %d must be >= 1", who, n_samples);
+    if (!fio || !fio->edge_collision || !fio->n_edge_collisions || !fio->edge_margin)
+      return fail(MKH_E_INVALID, "%s: free_io and its outputs edge_collision, n_edge_collisions, edge_margin are required", who);
+  }
   if (!q_path || !tracked_path) return fail(MKH_E_INVALID, "%s: q_path and tracked_path are required", who);
   if (!io->q_path_out || !io->tracked_out || !io->repaired || !io->refined || !io->edge_break || !io->n_tracked || !io->n_breaks ||
       !io->path_length)
@@ -2648,7 +2700,7 @@ int32_t mkh_ladder_refine(MkhProblem* p, int32_t B, int32_t T, const double* q, 
   HIP_OK(hipSetDevice(p->model->device));
   if (const int32_t rc = ms_build_tables(p)) return rc;
   const bool pbat = (flags & MKH_FLAG_POSTURE_BATCHED) != 0, cbat = (flags & MKH_FLAG_COM_BATCHED) != 0;
-  Stager st{p, (hipStream_t)hip_stream, devp, "ladder_refine"};
+  Stager st{p, (hipStream_t)hip_stream, devp, free_call ? "ladder_refine_free" : "ladder_refine"};
   const size_t Bz = B, R = Bz * T, nq = P.nq, nv = P.nv, f8 = sizeof(double), i4 = sizeof(int32_t);
   const size_t ft_w = (size_t)P.n_frame * 7, pt_w = (size_t)P.n_posture * nq, ct_w = (size_t)P.n_com * 3;
   const double* const d_q = st.up(WS_IN_Q, q, Bz * nq);
@@ -2660,6 +2712,13 @@ int32_t mkh_ladder_refine(MkhProblem* p, int32_t B, int32_t T, const double* q, 
   const int32_t* const d_trk = st.up_i32(WS_IN_TRK, tracked_path, R);
   mkh::LrOut o{io->q_path_out, io->v, io->path_length, io->tracked_out, io->repaired, io->refined, io->edge_break, io->n_tracked,
                io->n_breaks, io->status, io->iters, io->converged};
+  RefineFree rf{};
+  if (free_call) rf = RefineFree{ck, n_samples, fio->node_margin, fio->edge_margin, fio->edge_collision, fio->n_edge_collisions};
+  if (free_call && !devp) {
+    rf.edge_collision = st.i32(WS_F_OUT_I, R + Bz); rf.n_edge_collisions = rf.edge_collision ? rf.edge_collision + R : nullptr;
+    rf.edge_margin = st.f64(WS_F_OUT_F, R);
+    if (rf.node_margin) rf.node_margin = st.f64(WS_F_NMARGIN, R);
+  }
   if (!devp) {
     o.q = st.f64(WS_OUT_Q, R * nq);
     o.path_length = st.f64(WS_OUT_LEN, Bz);
@@ -2677,9 +2736,16 @@ int32_t mkh_ladder_refine(MkhProblem* p, int32_t B, int32_t T, const double* q, 
     }
   }
   if (!st.ok()) return st.finish();
-  if (const int32_t rc = refine_pass(st, B, T, d_q, d_path, d_trk, d_ft, d_pt, d_ct, ls, d_w, io->max_step_sq, o, flags))
+  if (const int32_t rc = refine_pass(st, B, T, d_q, d_path, d_trk, d_ft, d_pt, d_ct, ls, d_w, io->max_step_sq, o, flags,
+                                     free_call ? &rf : nullptr))
     return st.finish(rc);
   if (devp) return st.finish();
+  if (free_call) {
+    st.down(fio->edge_collision, rf.edge_collision, R * i4);
+    st.down(fio->n_edge_collisions, rf.n_edge_collisions, Bz * i4);
+    st.down(fio->edge_margin, rf.edge_margin, R * f8);
+    st.down(fio->node_margin, rf.node_margin, R * f8);
+  }
   st.down(io->q_path_out, o.q, R * nq * f8);
   st.down(io->tracked_out, o.tracked, R * i4);
   st.down(io->repaired, o.repaired, R * i4);
@@ -2693,6 +2759,24 @@ int32_t mkh_ladder_refine(MkhProblem* p, int32_t B, int32_t T, const double* q, 
   st.down(io->iters, o.iters, R * i4);
   st.down(io->converged, o.converged, R * i4);
   return st.finish();
+}
+
+int32_t mkh_ladder_refine(MkhProblem* p, int32_t B, int32_t T, const double* q, const double* q_path, const int32_t* tracked_path,
+                          const double* frame_targets, const double* posture_target, const double* com_target, double dt,
+                          double damping, int32_t max_iters, double pos_threshold, double ori_threshold, const MkhLadderRefineIO* io,
+                          int32_t flags, void* hip_stream) {
+  return ladder_refine_call(p, nullptr, 0, nullptr, "mkh_ladder_refine", B, T, q, q_path, tracked_path, frame_targets, posture_target,
+                            com_target, dt, damping, max_iters, pos_threshold, ori_threshold, io, flags, hip_stream, false);
+}
+
+int32_t mkh_ladder_refine_free(MkhProblem* p, MkhProblem* ck, int32_t B, int32_t T, const double* q, const double* q_path,
+                               const int32_t* tracked_path, const double* frame_targets, const double* posture_target,
+                               const double* com_target, double dt, double damping, int32_t max_iters, double pos_threshold,
+                               double ori_threshold, int32_t n_samples, const MkhLadderRefineIO* io,
+                               const MkhLadderRefineFreeIO* fio, int32_t flags, void* hip_stream) {
+  return ladder_refine_call(p, ck, n_samples, fio, "mkh_ladder_refine_free", B, T, q, q_path, tracked_path, frame_targets,
+                            posture_target, com_target, dt, damping, max_iters, pos_threshold, ori_threshold, io, flags, hip_stream,
+                            true);
 }
 
 // ---- the fused ladder calls: mkh_solve_trajectory_ladder(_refined) on the loops' S nodes per rung, and
@@ -2826,13 +2910,16 @@ static void ladder_pick(Stager& st, int B, int T, int W, const LadderCall& c, do
 // The optional pass over the chosen path, and the waypoint velocities.  The chosen nodes' flags are the path's; the pass reads
 // path and flags in place and writes the returned ones over them.  Returns as refine_pass does.
 static int32_t ladder_refine_qvel(Stager& st, int B, int T, int W, const LadderCall& c, const LoopSpec& ls,
-                                  const MkhTrajectoryLadderIO* io, bool refine, int32_t flags) {
+                                  const MkhTrajectoryLadderIO* io, bool refine, int32_t flags, const LadderFree& lf) {
   const MkhProblem* const p = st.p;
   const int nq = p->dev.nq, nv = p->dev.nv;
   if (refine) {
     ST_LAUNCH(st, launch_ladder_gather_i32(st.stream, c.l_trk, c.o_trk, c.o_node, (long long)B * T, W));
     const mkh::LrOut o{c.o_q, c.o_v, c.o_len, c.o_trk, c.o_rep, c.o_ref, c.o_eb, c.o_nt, c.o_nb, c.o_st, c.o_it, c.o_cv};
-    if (const int32_t rc = refine_pass(st, B, T, c.q, c.o_q, c.o_trk, c.in.ft, c.in.pt, c.in.ct, ls, c.w, io->max_step_sq, o, flags))
+    // (a checked call: the pass "with a checker"; the returned path's edge outputs replace the search's)
+    const RefineFree rf{lf.ck, lf.M, nullptr, lf.o.edge_margin, lf.o.edge_collision, lf.o.n_edge_collisions};
+    if (const int32_t rc = refine_pass(st, B, T, c.q, c.o_q, c.o_trk, c.in.ft, c.in.pt, c.in.ct, ls, c.w, io->max_step_sq, o, flags,
+                                       lf.ck ? &rf : nullptr))
       return rc;
   }
   if (c.o_qvel)
@@ -2932,7 +3019,7 @@ static int32_t ladder_plain_call(MkhProblem* p, LadderFree lf, const char* who, 
   if (lf.ck) clearance_rows(st, lf.ck, R * S, c.l_q, nullptr, nullptr, nullptr, nullptr, c.l_st);
   ST_LAUNCH(st, launch_ladder_tracked(st.stream, c.l_cv, c.l_st, (long long)(R * S), c.l_trk));
   ladder_pick(st, B, T, S, c, io->max_step_sq, lf);
-  if (const int32_t rc = ladder_refine_qvel(st, B, T, S, c, ls, io, refine != nullptr, flags)) return st.finish(rc);
+  if (const int32_t rc = ladder_refine_qvel(st, B, T, S, c, ls, io, refine != nullptr, flags, lf)) return st.finish(rc);
   if (!devp) ladder_down(st, B, T, S, S, c, io, refine, [&] { ladder_free_down(st, B, T, S, lf); });
   return st.finish();
 }
@@ -3021,7 +3108,7 @@ static int32_t ladder_nodes_call(MkhProblem* p, LadderFree lf, const char* who, 
   if (const int32_t rc = ms_rungs(st, R, S, c.in, ls, rng_seed, target_index0 * T, flags, rows_at, select)) return st.finish(rc);
   ladder_pick(st, B, T, K, c, io->max_step_sq, lf);
   ST_LAUNCH(st, launch_ladder_gather_i32(st.stream, n_si, n_pick, c.o_node, (long long)R, K));
-  if (const int32_t rc = ladder_refine_qvel(st, B, T, K, c, ls, io, refine != nullptr, flags)) return st.finish(rc);
+  if (const int32_t rc = ladder_refine_qvel(st, B, T, K, c, ls, io, refine != nullptr, flags, lf)) return st.finish(rc);
   if (!devp)
     ladder_down(st, B, T, S, K, c, io, refine, [&] {
       st.down(nodes->node_seed_index, n_si, M * i4);
@@ -3036,15 +3123,18 @@ static int32_t ladder_nodes_call(MkhProblem* p, LadderFree lf, const char* who, 
   return st.finish();
 }
 
-int32_t mkh_solve_trajectory_ladder_free(MkhProblem* p, MkhProblem* ck, int32_t B, int32_t T, int32_t n_seeds, int32_t n_nodes,
-                                         double min_distance, const double* q, const double* frame_targets, const double* posture_target,
-                                         const double* com_target, double dt, double damping, int32_t max_iters, double pos_threshold,
-                                         double ori_threshold, uint64_t rng_seed, int64_t target_index0, int32_t n_samples,
-                                         const MkhTrajectoryLadderIO* io, const MkhLadderNodesIO* nodes, const MkhLadderRefineIO* refine,
-                                         const MkhLadderFreeIO* fio, int32_t flags, void* hip_stream) {
-  const char* const who = "mkh_solve_trajectory_ladder_free";
+// mkh_solve_trajectory_ladder_free (refine refused) and mkh_solve_trajectory_ladder_free_refined (refine required).
+static int32_t ladder_free_call(const char* who, bool refined, MkhProblem* p, MkhProblem* ck, int32_t B, int32_t T, int32_t n_seeds,
+                                int32_t n_nodes, double min_distance, const double* q, const double* frame_targets,
+                                const double* posture_target, const double* com_target, double dt, double damping, int32_t max_iters,
+                                double pos_threshold, double ori_threshold, uint64_t rng_seed, int64_t target_index0, int32_t n_samples,
+                                const MkhTrajectoryLadderIO* io, const MkhLadderNodesIO* nodes, const MkhLadderRefineIO* refine,
+                                const MkhLadderFreeIO* fio, int32_t flags, void* hip_stream) {
   if (!p) return fail(MKH_E_INVALID, "null problem");
-  if (refine) return fail(MKH_E_INVALID, "%s: the refinement pass knows nothing of collisions: refine must be NULL", who);
+  if (!refined && refine)
+    return fail(MKH_E_INVALID, "%s: the refinement pass knows nothing of collisions: refine must be NULL", who);
+  if (refined && !refine)
+    return fail(MKH_E_INVALID, "%s: refine is required (without it the call is mkh_solve_trajectory_ladder_free)", who);
   if (n_nodes < 0 || (n_nodes == 0) != (nodes == nullptr))
     return fail(MKH_E_INVALID, "%s: n_nodes = %d with nodes %s: n_nodes = 0 and nodes = NULL is the plain ladder, n_nodes >= 1 with nodes "
                                "the ladder on distinct nodes", who, n_nodes, nodes ? "given" : "NULL");
@@ -3059,9 +3149,32 @@ int32_t mkh_solve_trajectory_ladder_free(MkhProblem* p, MkhProblem* ck, int32_t 
   lf.ck = ck; lf.M = n_samples; lf.io = fio;
   if (!n_nodes)
     return ladder_plain_call(p, lf, who, B, T, n_seeds, q, frame_targets, posture_target, com_target, dt, damping, max_iters, pos_threshold,
-                             ori_threshold, rng_seed, target_index0, io, nullptr, flags, hip_stream);
+                             ori_threshold, rng_seed, target_index0, io, refine, flags, hip_stream);
   return ladder_nodes_call(p, lf, who, B, T, n_seeds, n_nodes, min_distance, q, frame_targets, posture_target, com_target, dt, damping,
-                           max_iters, pos_threshold, ori_threshold, rng_seed, target_index0, io, nodes, nullptr, flags, hip_stream);
+                           max_iters, pos_threshold, ori_threshold, rng_seed, target_index0, io, nodes, refine, flags, hip_stream);
+}
+
+int32_t mkh_solve_trajectory_ladder_free(MkhProblem* p, MkhProblem* ck, int32_t B, int32_t T, int32_t n_seeds, int32_t n_nodes,
+                                         double min_distance, const double* q, const double* frame_targets, const double* posture_target,
+                                         const double* com_target, double dt, double damping, int32_t max_iters, double pos_threshold,
+                                         double ori_threshold, uint64_t rng_seed, int64_t target_index0, int32_t n_samples,
+                                         const MkhTrajectoryLadderIO* io, const MkhLadderNodesIO* nodes, const MkhLadderRefineIO* refine,
+                                         const MkhLadderFreeIO* fio, int32_t flags, void* hip_stream) {
+  return ladder_free_call("mkh_solve_trajectory_ladder_free", false, p, ck, B, T, n_seeds, n_nodes, min_distance, q, frame_targets,
+                          posture_target, com_target, dt, damping, max_iters, pos_threshold, ori_threshold, rng_seed, target_index0,
+                          n_samples, io, nodes, refine, fio, flags, hip_stream);
+}
+
+int32_t mkh_solve_trajectory_ladder_free_refined(MkhProblem* p, MkhProblem* ck, int32_t B, int32_t T, int32_t n_seeds, int32_t n_nodes,
+                                                 double min_distance, const double* q, const double* frame_targets,
+                                                 const double* posture_target, const double* com_target, double dt, double damping,
+                                                 int32_t max_iters, double pos_threshold, double ori_threshold, uint64_t rng_seed,
+                                                 int64_t target_index0, int32_t n_samples, const MkhTrajectoryLadderIO* io,
+                                                 const MkhLadderNodesIO* nodes, const MkhLadderRefineIO* refine,
+                                                 const MkhLadderFreeIO* fio, int32_t flags, void* hip_stream) {
+  return ladder_free_call("mkh_solve_trajectory_ladder_free_refined", true, p, ck, B, T, n_seeds, n_nodes, min_distance, q,
+                          frame_targets, posture_target, com_target, dt, damping, max_iters, pos_threshold, ori_threshold, rng_seed,
+                          target_index0, n_samples, io, nodes, refine, fio, flags, hip_stream);
 }
 
 // ---- goal sets (include/minkhip.h "THE RULE OF THE GOAL SET"; kernel: goalset.hip)

@@ -149,6 +149,33 @@ hipError_t launch_lr_step(hipStream_t stream, int B, int T, int nq, int nv, int 
 hipError_t launch_lr_guard(hipStream_t stream, int B, int T, int nq, int nv, int njnt, const int32_t* jnt, const double* q0,
                            const double* weights, double max_step_sq, const double* p, const int32_t* p_trk, const LrWork& w,
                            const LrOut& o);
+// ladder refinement "with a checker" (ladder_refine.hip, ladder_refine_free.hip; include/minkhip.h "THE RULE OF THE REFINEMENT, with
+// a checker"): r_trk and the guard's p_trk are then EFFECTIVE flags.  LrFreeWork: the node and edge margins of the working path,
+// (B, T) each, and the three margins lr_check_kernel leaves per instance, step and SLOT, (B, 3, slots) — margin(x) | near edge |
+// far edge, NaN: not evaluated or not swept; the samples of an edge are dealt to slots = lr_check_slots(M) blocks, each writes
+// the minimum over its own, the step kernel the minimum over the slots.  LrFreeGuard: both paths' margins, and the returned path's (node_margin: optional).  launch_lr_check
+// runs between the loop launch of waypoint commit_t and the launch_lr_step_free that commits it, on the CHECKER's per-body
+// descriptor (a device WideProblem without general convex pairs; nbody and n_pairs choose the build as in launch_clearance, the
+// LDS is sweep_lds_bytes'); M >= 1 interior samples per edge.
+constexpr int kLrMaxSlots = 8;
+int lr_check_slots(int M);
+struct LrFreeWork {
+  double *r_nm, *r_em, *trip;
+  int slots;
+};
+struct LrFreeGuard {
+  const double *p_nm, *p_em, *r_nm, *r_em;
+  double *node_margin, *edge_margin;
+  int32_t *edge_collision, *n_edge_collisions;
+};
+hipError_t launch_lr_check(hipStream_t stream, const void* wide_problem, int nbody, int nq, int n_pairs, int B, int T, int M,
+                           int commit_t, int commit_dir, const LrWork& w, double* trip);
+hipError_t launch_lr_step_free(hipStream_t stream, int B, int T, int nq, int nv, int njnt, const int32_t* jnt, const double* q0,
+                               const double* weights, double max_step_sq, int commit_t, int commit_dir, int next_t, int next_dir,
+                               const LrWork& w, const LrFreeWork& f);
+hipError_t launch_lr_guard_free(hipStream_t stream, int B, int T, int nq, int nv, int njnt, const int32_t* jnt, const double* q0,
+                                const double* weights, double max_step_sq, const double* p, const int32_t* p_trk, const LrWork& w,
+                                const LrOut& o, const LrFreeGuard& f);
 // clearance (clearance.hip; include/minkhip.h "THE RULE OF CLEARANCE"): margin / pair / n_violated (N,) and distance (N, n_pairs) of
 // N rows of q against the n_pairs >= 1 pairs of a checker's per-body descriptor (a device WideProblem), each output optional.
 // nbody and n_pairs choose between one and four rows per wavefront and size the launch's LDS: beyond 64 KB of poses

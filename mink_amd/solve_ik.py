@@ -1676,6 +1676,68 @@ class FreeLadderNodesResult(NamedTuple):
     edge_margin: Optional[np.ndarray] = None
 
 
+class FreeRefinedLadderResult(NamedTuple):
+    """Result of solve_ik_trajectory_ladder(collision_check=..., refine="free"): FreeLadderResult's fields, in its order — all of
+    the RETURNED path, `edge_collision`, `n_edge_collisions` and `edge_margin` included —, and behind them `repaired` (B, T) and
+    `refined` (B,) of the checked refinement pass."""
+    q: np.ndarray
+    v: np.ndarray
+    status: np.ndarray
+    iters: np.ndarray
+    converged: np.ndarray
+    node_index: np.ndarray
+    n_tracked: np.ndarray
+    n_breaks: np.ndarray
+    path_length: np.ndarray
+    edge_break: np.ndarray
+    qvel: Optional[np.ndarray] = None
+    q_all: Optional[np.ndarray] = None
+    v_all: Optional[np.ndarray] = None
+    status_all: Optional[np.ndarray] = None
+    iters_all: Optional[np.ndarray] = None
+    converged_all: Optional[np.ndarray] = None
+    seeds: Optional[np.ndarray] = None
+    edge_collision: Optional[np.ndarray] = None
+    n_edge_collisions: Optional[np.ndarray] = None
+    edge_margin: Optional[np.ndarray] = None
+    repaired: Optional[np.ndarray] = None
+    refined: Optional[np.ndarray] = None
+
+
+class FreeRefinedLadderNodesResult(NamedTuple):
+    """Result of solve_ik_trajectory_ladder(collision_check=..., n_nodes=K, refine="free"): FreeLadderNodesResult's fields, in its
+    order, and behind them `repaired` and `refined`, as in FreeRefinedLadderResult."""
+    q: np.ndarray
+    v: np.ndarray
+    status: np.ndarray
+    iters: np.ndarray
+    converged: np.ndarray
+    node_index: np.ndarray
+    n_tracked: np.ndarray
+    n_breaks: np.ndarray
+    path_length: np.ndarray
+    edge_break: np.ndarray
+    qvel: Optional[np.ndarray] = None
+    q_all: Optional[np.ndarray] = None
+    v_all: Optional[np.ndarray] = None
+    status_all: Optional[np.ndarray] = None
+    iters_all: Optional[np.ndarray] = None
+    converged_all: Optional[np.ndarray] = None
+    seeds: Optional[np.ndarray] = None
+    node_seed_index: Optional[np.ndarray] = None
+    node_multiplicity: Optional[np.ndarray] = None
+    node_distance: Optional[np.ndarray] = None
+    n_distinct: Optional[np.ndarray] = None
+    n_converged: Optional[np.ndarray] = None
+    n_uncovered: Optional[np.ndarray] = None
+    seed_index: Optional[np.ndarray] = None
+    edge_collision: Optional[np.ndarray] = None
+    n_edge_collisions: Optional[np.ndarray] = None
+    edge_margin: Optional[np.ndarray] = None
+    repaired: Optional[np.ndarray] = None
+    refined: Optional[np.ndarray] = None
+
+
 def _max_step_sq(max_step) -> float:
     """The squared gate of the ladder's break rule from the caller's joint-space step (None: no gate)."""
     if max_step is None:
@@ -1748,14 +1810,27 @@ def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt
     LadderNodesResult — a RefinedLadderNodesResult with refine —: the fields above and, behind them, the selection's.  With
     n_nodes None the call is the one described above, unchanged.
 
-    `collision_check` (a CollisionChecker of the same model; not together with refine): a joint path whose waypoints and motions
+    `collision_check` (a CollisionChecker of the same model; not together with refine=True — the pass that knows of collisions is
+    refine="free", below): a joint path whose waypoints and motions
     are free of collision.  Behind the loops every result is checked on the device and a result in collision gets
     ST_IN_COLLISION (in `status_all`; with n_nodes it takes no slot), so it is not tracked; every edge into a tracked node is
     swept with `edge_samples` interior samples and the search counts a waypoint entered by a colliding motion as lost (ladder_path
     states the rule).  The result is a FreeLadderResult / FreeLadderNodesResult: the fields above and `edge_collision`,
-    `n_edge_collisions`, `edge_margin`.  Without collision_check the call takes exactly the path described above."""
+    `n_edge_collisions`, `edge_margin`.  Without collision_check the call takes exactly the path described above.
+
+    `refine="free"` (with collision_check only) runs refine_path(collision_check=...)'s pass behind the checked search, in the
+    same call on the device: lost waypoints, breaks and waypoints entered by a colliding motion are re-solved from their
+    neighbour on the path, a repair is taken only when it and the motion into it are free, and the path comes back only where
+    its key — the checked ladder's — is strictly smaller.  The result is a FreeRefinedLadderResult /
+    FreeRefinedLadderNodesResult: the checked call's fields, all of the returned path, then `repaired` and `refined`."""
     del solver
-    _check_collision_check(collision_check, configuration, edge_samples, bool(refine))
+    free_refine = isinstance(refine, str)
+    if free_refine:
+        if refine != "free":
+            raise ValueError(f'refine must be False, True or "free", got {refine!r}')
+        if collision_check is None:
+            raise ValueError('refine="free" is the refinement pass with a checker: pass collision_check')
+    _check_collision_check(collision_check, configuration, edge_samples, bool(refine) and not free_refine)
     S, max_iters = int(n_seeds), int(max_iters)
     if n_nodes is None and unwind_turns:
         raise ValueError("unwind_turns works in front of the selection of n_nodes distinct nodes per rung: pass n_nodes")
@@ -1810,7 +1885,8 @@ def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt
             if K is not None:
                 fkw.update(n_nodes=K, min_distance=r, unwind_turns=bool(unwind_turns))
             o, more = handle.solve_trajectory_ladder_free(*args, checker=collision_check, edge_samples=int(edge_samples), target_index0=lo,
-                                                          seeds=_rows(seeds, 0, lo, hi), seed_table=seed_table, **fkw)
+                                                          seeds=_rows(seeds, 0, lo, hi), seed_table=seed_table, refine=free_refine,
+                                                          **fkw)
             free_parts.append((lo, more))
             return RefinedLadderNodesResult(*o[:17], o.repaired, o.refined, *o[20:])
         if K is None:
@@ -1842,6 +1918,8 @@ def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt
     if K is None:
         free_parts.sort(key=lambda x: x[0])
         more = [un(np.concatenate([np.asarray(m[i]) for _, m in free_parts])) for i in range(3)]
+        if free_refine:
+            return FreeRefinedLadderResult(*out, more[0].astype(bool), more[1], more[2], *fixed)
         return FreeLadderResult(*out, more[0].astype(bool), more[1], more[2])
     sets = [un(x) for x in (res.node_seed_index, res.node_multiplicity, res.node_distance, res.n_distinct, res.n_converged,
                             res.n_uncovered, res.seed_index)]
@@ -1850,6 +1928,8 @@ def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt
     free_parts.sort(key=lambda x: x[0])                     # (shards finish in any order; the rows are told apart by their offset)
     more = [un(np.concatenate([np.asarray(m[i]) for _, m in free_parts])) for i in range(3)]
     more[0] = more[0].astype(bool)
+    if free_refine:
+        return FreeRefinedLadderNodesResult(*out, *sets, *more, *fixed)
     return FreeLadderNodesResult(*out, *sets, *more)
 
 
@@ -1872,10 +1952,35 @@ class RefinedPath(NamedTuple):
     converged: np.ndarray
 
 
+class FreeRefinedPath(NamedTuple):
+    """Result of refine_path(collision_check=...): RefinedPath's fields, in its order — `tracked` the EFFECTIVE flags of the
+    returned path: tracked and free of collision —, then of the returned path `edge_collision` (B, T) — the motion into waypoint t
+    passes through collision, entry 0 never —, `n_edge_collisions` (B,), `edge_margin` (B, T) — +inf at waypoint 0, NaN where the
+    edge was not swept — and `node_margin` (B, T).  `n_tracked` counts the waypoints that are tracked, free of collision and
+    entered by a free motion."""
+    q: np.ndarray
+    tracked: np.ndarray
+    repaired: np.ndarray
+    refined: np.ndarray
+    edge_break: np.ndarray
+    n_tracked: np.ndarray
+    n_breaks: np.ndarray
+    path_length: np.ndarray
+    v: np.ndarray
+    status: np.ndarray
+    iters: np.ndarray
+    converged: np.ndarray
+    edge_collision: np.ndarray
+    n_edge_collisions: np.ndarray
+    edge_margin: np.ndarray
+    node_margin: np.ndarray
+
+
 def refine_path(configuration: Configuration, tasks: Sequence, dt: float, targets, q_path, tracked=None, max_iters: int = 32,
                 pos_threshold: float = 1e-4, ori_threshold: float = 1e-4, max_step: Optional[float] = None, weights=None,
                 update: bool = True, max_instances: int = 1 << 20, damping: float = 1e-12, limits: Optional[Sequence] = None,
-                safety_break: bool = False, solver: str = "mi355x") -> RefinedPath:
+                safety_break: bool = False, solver: str = "mi355x", collision_check: Optional["CollisionChecker"] = None,
+                edge_samples: int = 8) -> RefinedPath:
     """The ladder's refinement pass alone, over the caller's own path: q_path (T, nq) or (B, T, nq) — a ladder's chosen path,
     a planner's, an earlier call's — with `tracked` (same leading shape, default: every node counts as tracked) and the
     `targets` of solve_ik_trajectory (no keyframes) the path is meant to follow.
@@ -1891,8 +1996,16 @@ def refine_path(configuration: Configuration, tasks: Sequence, dt: float, target
     Limits warnings and SolverError follow solve_ik_trajectory's rules on the RETURNED repaired nodes only (`safety_break` as
     in solve_ik_trajectory_ladder).  With `update` the configuration is left at the returned q[:, -1].  When B exceeds
     `max_instances` the paths are walked in chunks of instances; a multi-device configuration shards by instance; the result
-    depends on neither."""
+    depends on neither.
+
+    `collision_check` (a CollisionChecker of the same model): the pass whose repairs are free of collision.  A node in collision
+    counts as not tracked and a waypoint entered by a colliding motion as lost (ladder_path's rule, `edge_samples` interior
+    samples per motion) — both are bad and get re-solved; a result is taken only when it is itself free of collision and the
+    motion from the neighbour is; the motion on its other side is swept anew, and the key that decides which path comes back
+    counts all of it.  Everything is checked on the device between the loops.  The result is then a FreeRefinedPath.  Without
+    collision_check the call is the one above, unchanged."""
     del solver
+    _check_collision_check(collision_check, configuration, edge_samples)
     max_iters = int(max_iters)
     if max_iters < 1:
         raise ValueError("max_iters must be >= 1")
@@ -1925,14 +2038,18 @@ def refine_path(configuration: Configuration, tasks: Sequence, dt: float, target
 
     def job(handle, lo, hi):
         n = hi - lo
-        r = handle.ladder_refine(q[lo:hi], q_path[lo:hi], None if tracked is None else tracked[lo:hi], _rows(ft, 0, lo, hi),
-                                 _rows(pt, 2, lo, hi), _rows(ct, 2, lo, hi), dt, damping, max_iters=max_iters,
-                                 pos_threshold=float(pos_threshold), ori_threshold=float(ori_threshold), max_step_sq=step_sq,
-                                 weights=weights, v=np.zeros((n, T, nv)), status=np.zeros((n, T), np.int32),
-                                 iters=np.zeros((n, T), np.int32), converged=np.zeros((n, T), np.int32))
-        return RefinedPath(*r)
+        kw = dict(max_iters=max_iters, pos_threshold=float(pos_threshold), ori_threshold=float(ori_threshold), max_step_sq=step_sq,
+                  weights=weights, v=np.zeros((n, T, nv)), status=np.zeros((n, T), np.int32), iters=np.zeros((n, T), np.int32),
+                  converged=np.zeros((n, T), np.int32))
+        args = (None if tracked is None else tracked[lo:hi], _rows(ft, 0, lo, hi), _rows(pt, 2, lo, hi), _rows(ct, 2, lo, hi), dt,
+                damping)
+        if collision_check is not None:
+            return FreeRefinedPath(*handle.ladder_refine_free(q[lo:hi], q_path[lo:hi], collision_check, *args,
+                                                              edge_samples=int(edge_samples), **kw))
+        return RefinedPath(*handle.ladder_refine(q[lo:hi], q_path[lo:hi], *args, **kw))
 
-    res = _join(RefinedPath, _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job))
+    res = _join(RefinedPath if collision_check is None else FreeRefinedPath,
+                _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job))
     if safety_break and ((res.status & nat.ST_OUTSIDE_LIMITS) != 0).any():
         b, t = (int(x) for x in np.argwhere((res.status & nat.ST_OUTSIDE_LIMITS) != 0)[0])
         raise _outside_limits(
@@ -1942,9 +2059,13 @@ def refine_path(configuration: Configuration, tasks: Sequence, dt: float, target
     if update:
         configuration.update(res.q[:, -1] if configuration.batched else res.q[0, -1])
     un = configuration._unbatch
-    return RefinedPath(un(res.q), un(res.tracked.astype(bool)), un(res.repaired), un(res.refined.astype(bool)),
-                       un(res.edge_break.astype(bool)), un(res.n_tracked), un(res.n_breaks), un(res.path_length), un(res.v),
-                       un(res.status), un(res.iters), un(res.converged.astype(bool)))
+    out = RefinedPath(un(res.q), un(res.tracked.astype(bool)), un(res.repaired), un(res.refined.astype(bool)),
+                      un(res.edge_break.astype(bool)), un(res.n_tracked), un(res.n_breaks), un(res.path_length), un(res.v),
+                      un(res.status), un(res.iters), un(res.converged.astype(bool)))
+    if collision_check is None:
+        return out
+    return FreeRefinedPath(*out, un(res.edge_collision.astype(bool)), un(res.n_edge_collisions), un(res.edge_margin),
+                           un(res.node_margin))
 
 
 def ladder_path(configuration: Configuration, q_nodes, tracked=None, max_step: Optional[float] = None, weights=None,
