@@ -854,6 +854,77 @@ int32_t mkh_solve_trajectory_multistart(MkhProblem *problem, int32_t B, int32_t 
                                         int32_t flags, void *hip_stream);
 
 /*
+ * THE RULE, with a checker (mkh_select_trajectory_candidates; mkh_solve_trajectory_multistart_free runs it on the candidates it
+ * tracks): the candidate whose waypoints AND motions are free of collision.  The terms are those of THE RULE above, of THE RULE OF
+ * CLEARANCE and of THE RULE OF THE SWEEP (both further down), unchanged; the checker is an ARGUMENT of these calls, as for the
+ * ladder.
+ * Candidate i = b·S + s, waypoint t, rows q_all[t, i] (time-major, the layout the loops run on).
+ *   Nodes.   node_margin(t, i) = the margin of q_all[t, i] by THE RULE OF CLEARANCE, for every row whatever its loop's flags.  A
+ *            row in collision — !(margin >= 0), "a NaN decides" — gets MKH_ST_IN_COLLISION OR-ed into status_all[t, i], as the
+ *            checked multi-start calls do.
+ *            eligible(t, i) = converged_all[t, i] != 0 && (status_all[t, i] & ~MKH_ST_OUTSIDE_LIMITS) == 0, evaluated AFTER that OR.
+ *   Edges.   For t >= 1 the edge into (t, i) runs from the same candidate's own row q_all[t - 1, i].  It is swept by THE RULE OF
+ *            THE SWEEP with M = n_samples iff eligible(t, i); otherwise it is not swept and edge_margin(t, i) = NaN.  The start
+ *            edge from q[b] is never swept, the ladder's convention: edge_margin(0, i) = +inf — IN THE _all ARRAY TOO, so that
+ *            the chosen candidate's row is a plain gather.  This differs from the ladder's edge_margin_all, whose t = 0 entries
+ *            are NaN.
+ *   Score.   Waypoint t of a candidate counts as TRACKED iff eligible(t, i) && (t == 0 || edge_margin(t, i) >= 0).  Length,
+ *            selection (count, then length, then lowest s), "nobody tracked anything: candidate 0" and n_complete are THE RULE
+ *            above on these counts, unchanged.
+ *   Loops.   Unchanged.  A candidate continues from its own waypoint t - 1 whatever the checker says; q_all, v_all, iters_all
+ *            and converged_all are bitwise the unchecked call's, status_all differs by the one bit only.
+ *   Outputs (MkhTrajectoryFreeIO), of the chosen candidate and in the call's layout ((B, T), or (T, B) with time_major):
+ *            node_margin; edge_margin (entry 0 = +inf, NaN where the edge was not swept); edge_collision: 1 where t >= 1, the
+ *            edge was swept and !(edge_margin >= 0); n_edge_collisions (B,).  Optional, ALWAYS time-major: node_margin_all and
+ *            edge_margin_all (T, B·S).
+ * Everything runs on the device: one launch over all T·B·S rows behind the last loop (a sweep has no per-row workspace), the
+ * score, the gathers.  Both *_all margins live in a workspace of the PROBLEM handle of 2·T·B·S·8 bytes unless the caller's
+ * device arrays take them.
+ *
+ * mkh_select_trajectory_candidates: the selection alone, over the caller's own candidates — q (B, nq) the current postures,
+ * q_paths (T, B·S, nq) time-major, tracked (T, B·S) or NULL: every row.  checker NULL (free_io NULL iff checker NULL, else
+ * MKH_E_INVALID): THE RULE above with "tracked != 0" as a waypoint's flag.  With a checker: tracked plays converged_all,
+ * status_all is taken as 0, and the rule "with a checker" applies.  Outputs (B,): seed_index, n_tracked, n_complete,
+ * path_length; optional q_path (B, T, nq), the chosen candidate's rows; with a checker the MkhTrajectoryFreeIO, (B, T).  Host
+ * pointers (staged, synchronous) or device pointers with MKH_FLAG_DEVICE_PTRS (asynchronous on the stream); no other flag.  It
+ * runs no loops: an attached checker is neither read nor refused, and B·S is not bound by max_batch; B·S·T < 2^31.
+ *
+ * mkh_solve_trajectory_multistart_free: mkh_solve_trajectory_multistart's arguments, refusals and pointer conventions, with the
+ * checker, n_samples and the MkhTrajectoryFreeIO; it runs that call with the rule "with a checker" in place of the plain score.
+ * A checker attached with mkh_problem_set_collision_check is still refused.  The checker must pass mkh_swept_clearance's
+ * refusals (general convex pairs, the LDS slice), live on the problem's device and belong to its MkhModel (MKH_E_INVALID /
+ * MKH_E_LIMIT); n_samples >= 1.  Every argument error is reported before any device work.  n_seeds = 1 is mkh_solve_trajectory's
+ * rows, bitwise, plus the verdict.  "One call in flight per checker handle" holds.
+ */
+typedef struct MkhTrajectoryFreeIO {
+  double *node_margin;         /* (B, T)    the clearance margin of the chosen candidate's rows                    required  */
+  double *edge_margin;         /* (B, T)    the swept margin of the motion into each of them                       required  */
+  int32_t *edge_collision;     /* (B, T)    1 where the motion into waypoint t was swept and collides              required  */
+  int32_t *n_edge_collisions;  /* (B,)      colliding motions of the chosen candidate                              required  */
+  double *node_margin_all;     /* (T, B*S)  optional: every row's clearance margin, time-major                               */
+  double *edge_margin_all;     /* (T, B*S)  optional: every row's swept margin, time-major                                   */
+} MkhTrajectoryFreeIO;
+typedef struct MkhTrajectoryCandidatesIO {
+  int32_t *seed_index;      /* (B,)        the chosen s                                                            required  */
+  int32_t *n_tracked;       /* (B,)        tracked waypoints of the chosen candidate                               required  */
+  int32_t *n_complete;      /* (B,)        candidates that tracked all T waypoints                                 required  */
+  double *path_length;      /* (B,)        length of the chosen candidate's path                                   required  */
+  double *q_path;           /* (B, T, nq)  optional: the chosen candidate's rows                                             */
+} MkhTrajectoryCandidatesIO;
+int32_t mkh_select_trajectory_candidates(MkhProblem *problem, MkhProblem *checker /* or NULL */, int32_t B, int32_t T, int32_t S,
+                                         const double *q, const double *q_paths /* (T, B*S, nq) */,
+                                         const int32_t *tracked /* (T, B*S) or NULL: all */, const double *weights,
+                                         int32_t n_samples, const MkhTrajectoryCandidatesIO *io,
+                                         const MkhTrajectoryFreeIO *free_io /* NULL iff checker NULL */, int32_t flags,
+                                         void *hip_stream);
+int32_t mkh_solve_trajectory_multistart_free(MkhProblem *problem, MkhProblem *checker, int32_t B, int32_t T, int32_t n_seeds,
+                                             const double *q, const double *frame_targets, const double *posture_target,
+                                             const double *com_target, double dt, double damping, int32_t n_steps,
+                                             double pos_threshold, double ori_threshold, uint64_t rng_seed, int64_t target_index0,
+                                             int32_t n_samples, const MkhTrajectoryMultistartIO *io,
+                                             const MkhTrajectoryFreeIO *free_io, int32_t flags, void *hip_stream);
+
+/*
  * Seed tables: multi-start seeded from the nearest stored postures.  The drawn starts of mkh_solve_multistart and
  * mkh_solve_trajectory_multistart are blind to the target; a seed table holds N postures keyed on the world poses their
  * frame-task frames reach, and a query returns, per target, the K stored postures whose poses are nearest — the way planners

@@ -369,6 +369,41 @@ class TrajectoryMultistartOut(NamedTuple):
     seeds: object = None
 
 
+TRAJECTORY_FREE_IO_FIELDS = ("node_margin", "edge_margin", "edge_collision", "n_edge_collisions", "node_margin_all", "edge_margin_all")
+TRAJECTORY_CANDIDATES_IO_FIELDS = ("seed_index", "n_tracked", "n_complete", "path_length", "q_path")
+
+
+class MkhTrajectoryFreeIO(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in TRAJECTORY_FREE_IO_FIELDS]
+
+
+class MkhTrajectoryCandidatesIO(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in TRAJECTORY_CANDIDATES_IO_FIELDS]
+
+
+class TrajectoryFreeOut(NamedTuple):
+    """What the checked candidate-tracking calls add (include/minkhip.h "THE RULE, with a checker" of
+    mkh_solve_trajectory_multistart), of the chosen candidate: node_margin and edge_margin (B, T) — (T, B) with time_major; entry
+    0 of edge_margin +inf, NaN where the edge was not swept —, edge_collision (B, T) int32, n_edge_collisions (B,) int32, and,
+    where asked for, every row's node_margin_all and edge_margin_all (T, B·S), always time-major."""
+    node_margin: object
+    edge_margin: object
+    edge_collision: object
+    n_edge_collisions: object
+    node_margin_all: object = None
+    edge_margin_all: object = None
+
+
+class TrajectoryCandidatesOut(NamedTuple):
+    """What NativeProblem.select_trajectory_candidates returns: per instance (B,) the chosen `seed_index`, its `n_tracked`
+    waypoints, `n_complete` of the S candidates and its `path_length`; `q` (B, T, nq), the chosen candidate's rows."""
+    seed_index: object
+    n_tracked: object
+    n_complete: object
+    path_length: object
+    q: object
+
+
 LADDER_MAX_S = 256         # nodes per rung (back-pointers are bytes) and waypoints per path (include/minkhip.h "THE RULE")
 LADDER_MAX_T = 65535
 LADDER_IO_FIELDS = ("node_index", "n_tracked", "n_breaks", "path_length", "edge_break", "q_path")
@@ -689,6 +724,14 @@ def lib() -> C.CDLL:
     L.mkh_solve_trajectory_multistart.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + common[2:8] + \
         [C.c_int32, C.c_double, C.c_double, C.c_uint64, C.c_int64, C.POINTER(MkhTrajectoryMultistartIO), C.c_int32, C.c_void_p]
     L.mkh_solve_trajectory_multistart.restype = C.c_int32
+    L.mkh_solve_trajectory_multistart_free.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + common[2:8] + \
+        [C.c_int32, C.c_double, C.c_double, C.c_uint64, C.c_int64, C.c_int32, C.POINTER(MkhTrajectoryMultistartIO),
+         C.POINTER(MkhTrajectoryFreeIO), C.c_int32, C.c_void_p]
+    L.mkh_solve_trajectory_multistart_free.restype = C.c_int32
+    L.mkh_select_trajectory_candidates.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(MkhTrajectoryCandidatesIO),
+                                                   C.POINTER(MkhTrajectoryFreeIO), C.c_int32, C.c_void_p]
+    L.mkh_select_trajectory_candidates.restype = C.c_int32
     L.mkh_ladder_select.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_double, C.POINTER(MkhLadderIO), C.c_int32, C.c_void_p]
     L.mkh_ladder_select.restype = C.c_int32
@@ -772,6 +815,7 @@ EXPORTED_SYMBOLS = (
     "mkh_clearance", "mkh_problem_set_collision_check",
     "mkh_swept_clearance", "mkh_ladder_select_free", "mkh_solve_trajectory_ladder_free",
     "mkh_ladder_refine_free", "mkh_solve_trajectory_ladder_free_refined",
+    "mkh_select_trajectory_candidates", "mkh_solve_trajectory_multistart_free",
 )
 
 LIE_OPS = {"se3_log": (0, 7, 0, (6,)), "se3_jlog": (1, 7, 0, (6, 6)), "se3_ljacinv": (2, 6, 0, (6, 6)),
@@ -1020,7 +1064,8 @@ class _attached:
 
 class _with_checker:
     """The locks of a call that takes its checker as an argument (mkh_ladder_select_free, mkh_solve_trajectory_ladder_free,
-    mkh_ladder_refine_free, mkh_solve_trajectory_ladder_free_refined): the
+    mkh_ladder_refine_free, mkh_solve_trajectory_ladder_free_refined, mkh_select_trajectory_candidates,
+    mkh_solve_trajectory_multistart_free): the
     problem's first, the checker's second; a problem that checks itself has one."""
 
     def __init__(self, problem: "NativeProblem", checker: "NativeProblem"):
@@ -1751,6 +1796,76 @@ class NativeProblem:
                                           wave_kernel, lane_kernel, quad_kernel,
                                           cands=(int(n_seeds), int(rng_seed), int(target_index0), seeds, weights, bool(return_all)))
 
+    def solve_trajectory_multistart_free(self, q, frame_targets=None, posture_target=None, com_target=None, dt: float = 1e-2,
+                                         damping: float = 1e-12, *, checker: "NativeProblem", edge_samples: int = 8, n_seeds: int,
+                                         n_steps: int, pos_threshold: float, ori_threshold: float, rng_seed: int = 0,
+                                         target_index0: int = 0, seeds=None, weights=None, qvel_dt: Optional[float] = None,
+                                         time_major: bool = False, warm_start: bool = False, return_all: bool = False,
+                                         wave_kernel: bool = False, lane_kernel: bool = False, quad_kernel: bool = False,
+                                         seed_table=None):
+        """mkh_solve_trajectory_multistart_free: solve_trajectory_multistart under THE RULE "with a checker" (include/minkhip.h) —
+        `checker` a handle with collision limits on the same NativeModel, `edge_samples` interior samples per motion.  Every row of
+        every candidate is checked as a node, the motion into every eligible row is swept, and a waypoint counts only when it is
+        free and entered by a free motion.  Returns (TrajectoryMultistartOut, TrajectoryFreeOut); with `return_all` the latter
+        carries node_margin_all and edge_margin_all (T, B·S)."""
+        if seeds is not None and seed_table is not None:
+            raise ValueError("seeds and seed_table are two sources of the same starts: pass one of them")
+        checker = _checker_handle(self, checker, edge_samples)
+        with _with_checker(self, checker), _attached(self, seed_table):
+            return self._solve_trajectory(q, frame_targets, posture_target, com_target, dt, damping, int(n_steps),
+                                          (float(pos_threshold), float(ori_threshold)), qvel_dt, bool(time_major), warm_start,
+                                          wave_kernel, lane_kernel, quad_kernel,
+                                          cands=(int(n_seeds), int(rng_seed), int(target_index0), seeds, weights, bool(return_all)),
+                                          free=(checker, int(edge_samples)))
+
+    def select_trajectory_candidates(self, q, q_paths, tracked=None, weights=None, checker: Optional["NativeProblem"] = None,
+                                     edge_samples: int = 8, return_margins: bool = False):
+        """mkh_select_trajectory_candidates: the selection of solve_trajectory_multistart alone, over the caller's own candidates —
+        q (B, nq) the current postures, q_paths (T, B·S, nq) time-major, tracked (T, B·S) (None: every row), weights (nv,) >= 0.
+        Without `checker` THE RULE on the caller's flags: returns (TrajectoryCandidatesOut, None).  With one THE RULE "with a
+        checker", `tracked` playing converged_all: returns (TrajectoryCandidatesOut, TrajectoryFreeOut), the latter (B, T) and, with
+        `return_margins`, with node_margin_all and edge_margin_all (T, B·S).  numpy in → numpy out (synchronous); torch CUDA
+        tensors in → torch tensors out on the current stream, no host copy."""
+        m = self.nmodel.model
+        if checker is not None:
+            checker = _checker_handle(self, checker, edge_samples)
+        B = int(q.shape[0])
+        if len(q_paths.shape) != 3 or int(q_paths.shape[0]) < 1 or int(q_paths.shape[1]) < B or int(q_paths.shape[1]) % B:
+            raise ValueError(f"q_paths must have shape (T, B*S, {m.nq}) with B = {B}, got {tuple(q_paths.shape)}")
+        T, R = int(q_paths.shape[0]), int(q_paths.shape[1])
+        S = R // B
+        prep, empty, ptr, stream, devp = _call_kit(q)
+        q, q_paths, weights = prep(q), prep(q_paths), prep(weights)
+        if tuple(q.shape) != (B, m.nq):
+            raise ValueError(f"q must have shape (B, {m.nq}), got {tuple(q.shape)}")
+        if tuple(q_paths.shape) != (T, R, m.nq):
+            raise ValueError(f"q_paths must have shape ({T}, {R}, {m.nq}), got {tuple(q_paths.shape)}")
+        if weights is not None and tuple(weights.shape) != (m.nv,):
+            raise ValueError(f"weights must have shape ({m.nv},), got {tuple(weights.shape)}")
+        if tracked is not None:
+            if tuple(tracked.shape) != (T, R):
+                raise ValueError(f"tracked must have shape ({T}, {R}), got {tuple(tracked.shape)}")
+            if devp:
+                import torch
+                tracked = (tracked != 0).to(device=q.device, dtype=torch.int32).contiguous()
+            else:
+                tracked = _i32(np.asarray(tracked) != 0)
+        f8, i4 = np.float64, np.int32
+        out = TrajectoryCandidatesOut(empty((B,), i4), empty((B,), i4), empty((B,), i4), empty((B,), f8), empty((B, T, m.nq), f8))
+        io = MkhTrajectoryCandidatesIO(*[ptr(x) for x in out])
+        if checker is None:
+            with self._lock:
+                _check(lib().mkh_select_trajectory_candidates(self.handle, None, B, T, S, ptr(q), ptr(q_paths), ptr(tracked),
+                                                              ptr(weights), 0, C.byref(io), None, devp, stream))
+            return out, None
+        more = TrajectoryFreeOut(empty((B, T), f8), empty((B, T), f8), empty((B, T), i4), empty((B,), i4),
+                                 empty((T, R), f8) if return_margins else None, empty((T, R), f8) if return_margins else None)
+        fio = MkhTrajectoryFreeIO(*[ptr(x) for x in more])
+        with _with_checker(self, checker):
+            _check(lib().mkh_select_trajectory_candidates(self.handle, checker.handle, B, T, S, ptr(q), ptr(q_paths), ptr(tracked),
+                                                          ptr(weights), int(edge_samples), C.byref(io), C.byref(fio), devp, stream))
+        return out, more
+
     # ----------------------------------------------------------------- ladder
     def ladder_select(self, q, q_nodes, tracked=None, max_step_sq: float = float("inf"), weights=None) -> LadderPathOut:
         """mkh_ladder_select: the dynamic program of include/minkhip.h "THE RULE" over the caller's rungs — q (B, nq) the current
@@ -2104,7 +2219,7 @@ class NativeProblem:
         return LadderRefineOut(*[out[n] for n in LADDER_REFINE_IO_FIELDS[2:]])
 
     def _solve_trajectory(self, q, frame_targets, posture_target, com_target, dt, damping, n_steps, until, qvel_dt, tm,
-                          warm_start, wave_kernel, lane_kernel, quad_kernel, keys=None, cands=None):
+                          warm_start, wave_kernel, lane_kernel, quad_kernel, keys=None, cands=None, free=None):
         m = self.nmodel.model
         B = int(q.shape[0])
         if n_steps < 1:
@@ -2205,13 +2320,22 @@ class NativeProblem:
             cio.seeds, cio.weights = ptr(seeds), ptr(weights)
             for n, x in {**per, **every}.items():
                 setattr(cio, n, ptr(x))
-            _check(lib().mkh_solve_trajectory_multistart(self.handle, B, T, S, ptr(q), ptr(frame_targets), ptr(posture_target),
-                                                         ptr(com_target), float(dt), float(damping), n_steps, thr[0], thr[1],
-                                                         rng_seed & (2 ** 64 - 1), target_index0, C.byref(cio), flags, stream))
-            return TrajectoryMultistartOut(out_q, out_v, out_st, out_it, out_cv, per["seed_index"], per["n_tracked"],
-                                           per["n_complete"], per["path_length"], out_qvel,
-                                           *[every.get(n) for n in ("q_all", "v_all", "status_all", "iters_all", "converged_all",
-                                                                    "seeds_out")])
+            args = (B, T, S, ptr(q), ptr(frame_targets), ptr(posture_target), ptr(com_target), float(dt), float(damping), n_steps,
+                    thr[0], thr[1], rng_seed & (2 ** 64 - 1), target_index0)
+            more = None
+            if free is None:
+                _check(lib().mkh_solve_trajectory_multistart(self.handle, *args, C.byref(cio), flags, stream))
+            else:                                                      # (the caller holds both locks: _with_checker)
+                more = TrajectoryFreeOut(empty(lead, f8), empty(lead, f8), empty(lead, i4), empty((B,), i4),
+                                         empty((T, R), f8) if want_all else None, empty((T, R), f8) if want_all else None)
+                fio = MkhTrajectoryFreeIO(*[ptr(x) for x in more])
+                _check(lib().mkh_solve_trajectory_multistart_free(self.handle, free[0].handle, *args, free[1], C.byref(cio),
+                                                                  C.byref(fio), flags, stream))
+            res = TrajectoryMultistartOut(out_q, out_v, out_st, out_it, out_cv, per["seed_index"], per["n_tracked"],
+                                          per["n_complete"], per["path_length"], out_qvel,
+                                          *[every.get(n) for n in ("q_all", "v_all", "status_all", "iters_all", "converged_all",
+                                                                   "seeds_out")])
+            return res if free is None else (res, more)
         if keys is not None:
             kt, wt, want = keys
             out_ft = out_pt = out_ct = None

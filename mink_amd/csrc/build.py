@@ -331,6 +331,8 @@ def build(force: bool = False, verbose: bool = True) -> str:
     jobs.append((os.path.join(HERE, "ladder_refine_free.hip"), os.path.join(BUILD, "ladder_refine_free.o")))   # lr_check_kernel: the collision check between the loops of mkh_ladder_refine_free
     jobs.append((os.path.join(HERE, "sweep.hip"), os.path.join(BUILD, "sweep.o")))   # swept clearance of edges: mkh_swept_clearance, the edge mask of the checked ladder calls
 
+    jobs.append((os.path.join(HERE, "trajectory_free.hip"), os.path.join(BUILD, "trajectory_free.o")))   # tmf_check_kernel: nodes and edges of mkh_solve_trajectory_multistart_free / mkh_select_trajectory_candidates (sweep.hip's flags)
+
     def compile_one(job):
         src, obj = job
         extra = KERNEL_FLAGS if os.path.basename(src).startswith("variant_") else []

@@ -192,7 +192,10 @@ enum WsRole {
   // a ladder refinement with a checker: RF_MARGIN: the node margins and the edge margins of the input path, then of the working
   // path, (B, T) each; RF_TRIP: what lr_check_kernel leaves per step, (B, 3, slots); RF_IDX: the index array of the input path seen as a
   // ladder of width 1 (zeros) | its effective flags, (B, T) each.  A host caller's outputs go through F_OUT_I, F_OUT_F and
-  // F_NMARGIN, as a checked ladder's do
+  // F_NMARGIN, as a checked ladder's do.  Checked candidate tracking (trajectory_free.hip) has no slot of its own: every row's
+  // node and edge margins, (T, B·S) each, live in F_NMARGIN and F_EMARGIN; a host caller's outputs in F_OUT_F (node_margin |
+  // edge_margin, (B, T) each) and F_OUT_I (edge_collision (B, T) | n_edge_collisions (B,)); the selection alone keeps the
+  // caller's candidates and flags in C_Q and C_CV and its status of zeros in C_ST
   WS_RF_MARGIN, WS_RF_TRIP, WS_RF_IDX,
   WS_COUNT
 };
@@ -2075,7 +2078,68 @@ struct CandidateSpec {
   double* path_length;                                     // (B,) required
   double *seeds_out, *q_all, *v_all;                       // optional: (B·S, nq), (T, B·S, nq), (T, B·S, nv)
   int32_t *status_all, *iters_all, *converged_all;         // optional: (T, B·S)
+  // mkh_solve_trajectory_multistart_free ("THE RULE, with a checker"): the checker, the samples per edge and the free outputs
+  bool checked;
+  MkhProblem* ck;
+  int32_t M;
+  const MkhTrajectoryFreeIO* fio;
 };
+
+// ---- checked candidate tracking (include/minkhip.h "THE RULE, with a checker" of mkh_solve_trajectory_multistart; kernels:
+// trajectory_free.hip): what mkh_solve_trajectory_multistart_free and mkh_select_trajectory_candidates share
+struct TmfDev {                    // device arrays: every row's margins, (T, B·S), and the chosen candidate's outputs in the caller's layout
+  double *nm_all, *em_all;
+  double *node_margin, *edge_margin;
+  int32_t *edge_collision, *n_edge_collisions;
+};
+
+// What both calls refuse about the sample count and the free outputs: from the arguments alone.
+static int32_t tmf_refuse_args(int32_t n_samples, const MkhTrajectoryFreeIO* f, const char* who) {
+  if (n_samples < 1) return fail(MKH_E_INVALID, "%s: n_samples = %d must be >= 1", who, n_samples);
+  if (!f || !f->node_margin || !f->edge_margin || !f->edge_collision || !f->n_edge_collisions)
+    return fail(MKH_E_INVALID, "%s: free_io and its outputs node_margin, edge_margin, edge_collision, n_edge_collisions are required", who);
+  return MKH_OK;
+}
+
+// N = B·T rows of the chosen candidate, NR = T·B·S rows in all.  The *_all margins always exist on the device: the score reads
+// the edges', the gathers both.
+static TmfDev tmf_stage(Stager& st, const MkhTrajectoryFreeIO& f, size_t N, size_t Bz, size_t NR) {
+  TmfDev d{};
+  d.nm_all = (double*)st.given_or(WS_F_NMARGIN, f.node_margin_all, NR * sizeof(double));
+  d.em_all = (double*)st.given_or(WS_F_EMARGIN, f.edge_margin_all, NR * sizeof(double));
+  d.node_margin = f.node_margin; d.edge_margin = f.edge_margin;
+  d.edge_collision = f.edge_collision; d.n_edge_collisions = f.n_edge_collisions;
+  if (!st.devp) {
+    d.node_margin = st.f64(WS_F_OUT_F, 2 * N); d.edge_margin = d.node_margin ? d.node_margin + N : nullptr;
+    d.edge_collision = st.i32(WS_F_OUT_I, N + Bz); d.n_edge_collisions = d.edge_collision ? d.edge_collision + N : nullptr;
+  }
+  return d;
+}
+
+// The one launch over all T·B·S rows: node margins, the status bit, edge margins.
+static void tmf_check(Stager& st, const MkhProblem* ck, int B, int S, int T, int M, const double* q_all, const int32_t* cv_all,
+                      int32_t* st_all, const TmfDev& d) {
+  ST_LAUNCH(st, launch_tmf_check(st.stream, ck->d_wide, ck->model->nbody, ck->model->nq, ck->dev.n_pairs, B, S, T, M, q_all, cv_all, st_all,
+                                 d.nm_all, d.em_all));
+}
+
+// The chosen candidate's margins (plain gathers: edge_margin_all carries +inf at waypoint 0) and its edge flags, through the
+// (instance, waypoint) strides sb / sw of a (B, T) array in the caller's layout.
+static void tmf_chosen(Stager& st, int B, int S, int T, const int32_t* o_si, const int32_t* cv_all, const int32_t* st_all, const TmfDev& d,
+                       long long sb, long long sw) {
+  ST_LAUNCH(st, launch_tms_gather(st.stream, d.nm_all, d.node_margin, o_si, B, S, T, 1, sb, sw));
+  ST_LAUNCH(st, launch_tms_gather(st.stream, d.em_all, d.edge_margin, o_si, B, S, T, 1, sb, sw));
+  ST_LAUNCH(st, launch_tmf_edge_flags(st.stream, B, S, T, o_si, cv_all, st_all, d.em_all, d.edge_collision, sb, sw, d.n_edge_collisions));
+}
+
+static void tmf_down(Stager& st, const MkhTrajectoryFreeIO& f, const TmfDev& d, size_t N, size_t Bz, size_t NR) {
+  st.down(f.node_margin, d.node_margin, N * sizeof(double));
+  st.down(f.edge_margin, d.edge_margin, N * sizeof(double));
+  st.down(f.edge_collision, d.edge_collision, N * sizeof(int32_t));
+  st.down(f.n_edge_collisions, d.n_edge_collisions, Bz * sizeof(int32_t));
+  st.down(f.node_margin_all, d.nm_all, NR * sizeof(double));
+  st.down(f.edge_margin_all, d.em_all, NR * sizeof(double));
+}
 
 // mkh_solve_trajectory and, with `kf`, mkh_solve_keyframes, or, with `cs`, mkh_solve_trajectory_multistart: the T
 // stream-ordered loop launches between slabs of time-major buffers and everything around them.  `who` names the entry point
@@ -2101,6 +2165,10 @@ static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double
     return fail(MKH_E_INVALID, "io and its outputs q_traj, v_traj, status are required");
   if (cs && (!io->iters || !io->converged || !cs->seed_index || !cs->n_tracked || !cs->n_complete || !cs->path_length))
     return fail(MKH_E_INVALID, "io's outputs iters, converged, seed_index, n_tracked, n_complete, path_length are required");
+  if (cs && cs->checked) {
+    if (const int32_t rc = tmf_refuse_args(cs->M, cs->fio, who)) return rc;
+    if (!cs->ck) return fail(MKH_E_INVALID, "%s: null checker", who);
+  }
   if (!until && (io->iters || io->converged))
     return fail(MKH_E_INVALID, "iters / converged are outputs of threshold mode: they must be NULL with a fixed count");
   if (io->qvel && !(io->waypoint_dt > 0.0)) return fail(MKH_E_INVALID, "qvel needs waypoint_dt > 0");
@@ -2111,6 +2179,9 @@ static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double
   }
   if (!p) return fail(MKH_E_INVALID, "null problem");
   if (const int32_t rc = refuse_checker(p, who)) return rc;
+  const bool checked = cs && cs->checked;
+  if (checked)
+    if (const int32_t rc = sweep_refuse_for(p, cs->ck, who)) return rc;
   const DeviceProblem& P = p->dev;
   if (const int32_t rc = refuse_inputs(P, q, frame_targets, posture_target, com_target, until ? who : nullptr, "trajectory"))
     return rc;
@@ -2164,6 +2235,8 @@ static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double
       o_len = st.f64(WS_OUT_LEN, Bz);
     }
   }
+  TmfDev tf{};
+  if (checked) tf = tmf_stage(st, *cs->fio, N, Bz, NR);
   // ---- keyframes: one slab per target group for all waypoints; the interpolated targets, where asked for, in the caller's layout
   double *k_ft = nullptr, *k_pt = nullptr, *k_ct = nullptr, *k_ft_out = nullptr, *k_pt_out = nullptr, *k_ct_out = nullptr;
   const size_t pt_rows = pbat ? Bz : 1, ct_rows = cbat ? Bz : 1;
@@ -2280,13 +2353,16 @@ static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double
   auto sw = [&](size_t w) { return (long long)(tm ? Bz * w : w); };
   if (cs) {
     // the score over every candidate's path and the choice, then the chosen rows into the caller's layout
-    ST_LAUNCH(st, launch_tms_score(stream, B, S, T, (int)nq, p->model->njnt, ws[WS_JNT].i32(), d_q, l_q, l_st, l_cv, d_w, o_si, o_nt,
-                                   o_nc, o_len));
+    // (with a checker: one launch over all T·B·S rows behind the last loop — nodes, the status bit, edges — and the score on them)
+    if (checked) tmf_check(st, cs->ck, B, S, T, cs->M, l_q, l_cv, l_st, tf);
+    ST_LAUNCH(st, launch_tms_score(stream, B, S, T, (int)nq, p->model->njnt, ws[WS_JNT].i32(), d_q, l_q, l_st, l_cv, d_w,
+                                   checked ? tf.em_all : nullptr, o_si, o_nt, o_nc, o_len));
     ST_LAUNCH(st, launch_tms_gather(stream, l_q, o_q, o_si, B, S, T, (int)nq, sb(nq), sw(nq)));
     ST_LAUNCH(st, launch_tms_gather(stream, l_v, o_v, o_si, B, S, T, (int)nv, sb(nv), sw(nv)));
     ST_LAUNCH(st, launch_tms_gather_i32(stream, l_st, o_st, o_si, B, S, T, sb(1), sw(1)));
     ST_LAUNCH(st, launch_tms_gather_i32(stream, l_it, o_it, o_si, B, S, T, sb(1), sw(1)));
     ST_LAUNCH(st, launch_tms_gather_i32(stream, l_cv, o_cv, o_si, B, S, T, sb(1), sw(1)));
+    if (checked) tmf_chosen(st, B, S, T, o_si, l_cv, l_st, tf, sb(1), sw(1));
     if (o_qvel)
       ST_LAUNCH(st, launch_tj_qvel(stream, ws[WS_JNT].i32(), p->model->njnt, B, T, (int)nq, d_q, o_q, sb(nq), sw(nq), io->waypoint_dt,
                                    o_qvel, sb(nv), sw(nv), tm ? 1 : 0));
@@ -2325,6 +2401,7 @@ static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double
     st.down(cs->status_all, l_st, NR * i4);
     st.down(cs->iters_all, l_it, NR * i4);
     st.down(cs->converged_all, l_cv, NR * i4);
+    if (checked) tmf_down(st, *cs->fio, tf, N, Bz, NR);
   }
   return st.finish();
 }
@@ -2378,6 +2455,95 @@ int32_t mkh_solve_trajectory_multistart(MkhProblem* p, int32_t B, int32_t T, int
   }
   return trajectory_core(p, B, T, q, frame_targets, posture_target, com_target, dt, damping, n_steps, pos_threshold, ori_threshold,
                          io ? &tio : nullptr, flags, hip_stream, nullptr, &cs, "mkh_solve_trajectory_multistart");
+}
+
+int32_t mkh_solve_trajectory_multistart_free(MkhProblem* p, MkhProblem* ck, int32_t B, int32_t T, int32_t n_seeds, const double* q,
+                                             const double* frame_targets, const double* posture_target, const double* com_target,
+                                             double dt, double damping, int32_t n_steps, double pos_threshold, double ori_threshold,
+                                             uint64_t rng_seed, int64_t target_index0, int32_t n_samples,
+                                             const MkhTrajectoryMultistartIO* io, const MkhTrajectoryFreeIO* fio, int32_t flags,
+                                             void* hip_stream) {
+  // mkh_solve_trajectory_multistart's view of the call, with the checker beside it
+  MkhTrajectoryIO tio;
+  CandidateSpec cs{};
+  cs.S = n_seeds; cs.rng_seed = rng_seed; cs.target_index0 = target_index0;
+  cs.checked = true; cs.ck = ck; cs.M = n_samples; cs.fio = fio;
+  if (io) {
+    tio.q_traj = io->q_traj; tio.v_traj = io->v_traj; tio.status = io->status; tio.iters = io->iters;
+    tio.converged = io->converged; tio.qvel = io->qvel; tio.waypoint_dt = io->waypoint_dt;
+    tio.posture_per_waypoint = io->posture_per_waypoint; tio.com_per_waypoint = io->com_per_waypoint; tio.time_major = io->time_major;
+    cs.seeds = io->seeds; cs.weights = io->weights;
+    cs.seed_index = io->seed_index; cs.n_tracked = io->n_tracked; cs.n_complete = io->n_complete; cs.path_length = io->path_length;
+    cs.seeds_out = io->seeds_out; cs.q_all = io->q_all; cs.v_all = io->v_all;
+    cs.status_all = io->status_all; cs.iters_all = io->iters_all; cs.converged_all = io->converged_all;
+  }
+  return trajectory_core(p, B, T, q, frame_targets, posture_target, com_target, dt, damping, n_steps, pos_threshold, ori_threshold,
+                         io ? &tio : nullptr, flags, hip_stream, nullptr, &cs, "mkh_solve_trajectory_multistart_free");
+}
+
+// The selection alone, over the caller's own candidates: the score and the choice of "THE RULE" on the caller's flags, or — with
+// a checker — of "THE RULE, with a checker" with `tracked` for converged_all and a status of zeros.
+int32_t mkh_select_trajectory_candidates(MkhProblem* p, MkhProblem* ck, int32_t B, int32_t T, int32_t S, const double* q,
+                                         const double* q_paths, const int32_t* tracked, const double* weights, int32_t n_samples,
+                                         const MkhTrajectoryCandidatesIO* io, const MkhTrajectoryFreeIO* fio, int32_t flags,
+                                         void* hip_stream) {
+  const char* const who = "mkh_select_trajectory_candidates";
+  if (B < 1) return fail(MKH_E_INVALID, "%s: B = %d must be >= 1", who, B);
+  if (T < 1) return fail(MKH_E_INVALID, "%s: T = %d must be >= 1", who, T);
+  if (S < 1) return fail(MKH_E_INVALID, "%s: S = %d must be >= 1", who, S);
+  if (flags & ~MKH_FLAG_DEVICE_PTRS) return fail(MKH_E_INVALID, "%s: flags = %d: only MKH_FLAG_DEVICE_PTRS is accepted", who, flags);
+  if (!q || !q_paths) return fail(MKH_E_INVALID, "%s: q and q_paths are required", who);
+  if (!io || !io->seed_index || !io->n_tracked || !io->n_complete || !io->path_length)
+    return fail(MKH_E_INVALID, "%s: io and its outputs seed_index, n_tracked, n_complete, path_length are required", who);
+  if (!ck && fio) return fail(MKH_E_INVALID, "%s: free_io is given without a checker: free_io is NULL iff checker is NULL", who);
+  if (ck)
+    if (const int32_t rc = tmf_refuse_args(n_samples, fio, who)) return rc;
+  if (!p) return fail(MKH_E_INVALID, "null problem");
+  if (ck)
+    if (const int32_t rc = sweep_refuse_for(p, ck, who)) return rc;
+  if ((long long)B * S * T > 0x7fffffffLL)
+    return fail(MKH_E_LIMIT, "%s: B * S * T = %lld rows, at most 2^31 - 1", who, (long long)B * S * T);
+  const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
+  const size_t Bz = B, N = Bz * T, Rz = Bz * S, NR = Rz * T, nq = p->dev.nq, nv = p->dev.nv, f8 = sizeof(double), i4 = sizeof(int32_t);
+  for (size_t k = 0; !devp && weights && k < nv; ++k)
+    if (!(weights[k] >= 0.0)) return fail(MKH_E_INVALID, "%s: weights[%zu] = %g: the weights of the length must be >= 0", who, k, weights[k]);
+  HIP_OK(hipSetDevice(p->model->device));
+  if (const int32_t rc = ms_build_tables(p)) return rc;
+  Stager st{p, (hipStream_t)hip_stream, devp, "select_trajectory_candidates"};
+  const double* const d_q = st.up(WS_IN_Q, q, Bz * nq);
+  const double* const d_paths = st.up(WS_C_Q, q_paths, NR * nq);
+  const double* const d_w = st.up(WS_IN_W, weights, nv);
+  const int32_t* const d_trk = st.up_i32(WS_C_CV, tracked, NR);
+  int32_t *o_si = io->seed_index, *o_nt = io->n_tracked, *o_nc = io->n_complete;
+  double *o_len = io->path_length, *o_q = io->q_path;
+  if (!devp) {
+    o_si = st.i32(WS_OUT_PICK, 3 * Bz); o_nt = o_si ? o_si + Bz : nullptr; o_nc = o_si ? o_si + 2 * Bz : nullptr;
+    o_len = st.f64(WS_OUT_LEN, Bz);
+    o_q = io->q_path ? st.f64(WS_OUT_Q, N * nq) : nullptr;
+  }
+  TmfDev tf{};
+  int32_t* d_st = nullptr;           // with a checker: the status the rule takes as 0, and the kernel ORs its bit into
+  if (ck) {
+    tf = tmf_stage(st, *fio, N, Bz, NR);
+    d_st = st.i32(WS_C_ST, NR);
+  }
+  if (!st.ok()) return st.finish();
+  if (ck) {
+    st.latch(hipMemsetAsync(d_st, 0, NR * i4, st.stream));
+    tmf_check(st, ck, B, S, T, n_samples, d_paths, d_trk, d_st, tf);
+  }
+  ST_LAUNCH(st, launch_tms_score(st.stream, B, S, T, (int)nq, p->model->njnt, p->ws[WS_JNT].i32(), d_q, d_paths, d_st, d_trk, d_w,
+                                 ck ? tf.em_all : nullptr, o_si, o_nt, o_nc, o_len));
+  if (o_q) ST_LAUNCH(st, launch_tms_gather(st.stream, d_paths, o_q, o_si, B, S, T, (int)nq, (long long)(T * nq), (long long)nq));
+  if (ck) tmf_chosen(st, B, S, T, o_si, d_trk, d_st, tf, (long long)T, 1);
+  if (devp) return st.finish();
+  st.down(io->seed_index, o_si, Bz * i4);
+  st.down(io->n_tracked, o_nt, Bz * i4);
+  st.down(io->n_complete, o_nc, Bz * i4);
+  st.down(io->path_length, o_len, Bz * f8);
+  st.down(io->q_path, o_q, N * nq * f8);
+  if (ck) tmf_down(st, *fio, tf, N, Bz, NR);
+  return st.finish();
 }
 
 // ---- ladder-graph trajectory IK (include/minkhip.h "THE RULE"; kernels: ladder.hip)

@@ -1,6 +1,6 @@
 // Launchers of the small kernels around the loop launches of the outer-loop entry points (mkh_solve_multistart,
 // mkh_solve_multistart_set, mkh_solve_goalset, mkh_solve_trajectory, mkh_solve_keyframes, mkh_solve_trajectory_multistart, the ladder calls) and of
-// the seed tables in front of them: declared once, for the twelve files that define them and for minkhip.hip, which calls them — a signature that
+// the seed tables in front of them: declared once, for the thirteen files that define them and for minkhip.hip, which calls them — a signature that
 // drifts fails to compile in the file that drifted.  In minkhip.hip the multi-start calls, the ladder calls and the goal set
 // launch the seeding, the seed-table query and the target fan-out from one place, the loop stage ms_loops(), which also asks for
 // their workspace slots (WS_C_FT / PT / CT, the WS_IN_SEEDS slab); mkh_solve_trajectory_multistart has its own (time-major) ones.
@@ -99,14 +99,30 @@ hipError_t launch_kf_posture(hipStream_t stream, const int32_t* jnt, int njnt, c
 hipError_t launch_kf_com(hipStream_t stream, const double* keys, long long s_b, long long s_k, int k, double u, int rows,
                          int width, double* slab, double* out, long long o_sb);
 // multi-start trajectory IK (trajectory_multistart.hip): every candidate scored over its path and one chosen per instance, the
-// chosen candidate's rows of the time-major (T, B·S, .) results gathered through the (instance, waypoint) strides of `out`
+// chosen candidate's rows of the time-major (T, B·S, .) results gathered through the (instance, waypoint) strides of `out`.
+// status_all / converged_all absent: every row passes that test; edge_margin_all (T, B·S) given: the score of "THE RULE, with a
+// checker" — a waypoint t >= 1 counts only when edge_margin_all >= 0 (absent: the plain rule, bitwise)
 hipError_t launch_tms_score(hipStream_t stream, int B, int S, int T, int nq, int njnt, const int32_t* jnt, const double* q0,
                             const double* q_all, const int32_t* status_all, const int32_t* converged_all, const double* weights,
-                            int32_t* seed_index, int32_t* n_tracked, int32_t* n_complete, double* path_length);
+                            const double* edge_margin_all, int32_t* seed_index, int32_t* n_tracked, int32_t* n_complete,
+                            double* path_length);
 hipError_t launch_tms_gather(hipStream_t stream, const double* all, double* out, const int32_t* seed_index, int B, int S, int T,
                              int W, long long o_sb, long long o_st);
 hipError_t launch_tms_gather_i32(hipStream_t stream, const int32_t* all, int32_t* out, const int32_t* seed_index, int B, int S,
                                  int T, long long o_sb, long long o_st);
+// checked candidate tracking (trajectory_free.hip; include/minkhip.h "THE RULE, with a checker" of mkh_solve_trajectory_multistart):
+// launch_tmf_check judges the T·B·S rows of the time-major candidates q_all in one launch — node_margin_all, MKH_ST_IN_COLLISION
+// OR-ed into status_all, and edge_margin_all: +inf at waypoint 0, the swept margin of the M >= 1 interior samples of the edge from
+// the same candidate's row t − 1 where the row is eligible, NaN elsewhere — on the CHECKER's per-body descriptor (a device
+// WideProblem without general convex pairs; nbody and n_pairs choose the build as in launch_clearance, the LDS is
+// sweep_lds_bytes').  converged_all absent: every row counts as converged.  launch_tmf_edge_flags: the chosen candidate's
+// edge_collision through the (instance, waypoint) strides of the caller's layout, and n_edge_collisions (B,).
+hipError_t launch_tmf_check(hipStream_t stream, const void* wide_problem, int nbody, int nq, int n_pairs, int B, int S, int T, int M,
+                            const double* q_all, const int32_t* converged_all, int32_t* status_all, double* node_margin_all,
+                            double* edge_margin_all);
+hipError_t launch_tmf_edge_flags(hipStream_t stream, int B, int S, int T, const int32_t* seed_index, const int32_t* converged_all,
+                                 const int32_t* status_all, const double* edge_margin_all, int32_t* edge_collision, long long o_sb,
+                                 long long o_st, int32_t* n_edge_collisions);
 // seed tables (seed_table.hip): a chunk's (n, n_frame, 7) poses into the table's (n_frame·7, N) keys at entries j0 …, and the
 // K entries nearest to each of B targets — indices (B, K), distances (B, K), the entries' q into rows 1 … K of a
 // (B, K + 1, nq) slab; each output optional

@@ -17,8 +17,8 @@ namespace mkh {
 __global__ __launch_bounds__(64) void tms_score_select_kernel(
     int B, int S, int T, int nq, int njnt, const int32_t* __restrict__ jnt, const double* __restrict__ q0,
     const double* __restrict__ q_all, const int32_t* __restrict__ status_all, const int32_t* __restrict__ converged_all,
-    const double* __restrict__ weights, int32_t* __restrict__ seed_index, int32_t* __restrict__ n_tracked,
-    int32_t* __restrict__ n_complete, double* __restrict__ path_length) {
+    const double* __restrict__ weights, const double* __restrict__ edge_margin_all, int32_t* __restrict__ seed_index,
+    int32_t* __restrict__ n_tracked, int32_t* __restrict__ n_complete, double* __restrict__ path_length) {
 #pragma clang fp contract(off)      // length: a rounded sum of the waypoints' distances, in ascending t
   const int b = blockIdx.x;
   if (b >= B) return;
@@ -36,7 +36,12 @@ __global__ __launch_bounds__(64) void tms_score_select_kernel(
     const double* prev = start;                              // (q_{-1}: the caller's q[b], not the seed)
     for (int t = 0; t < T; ++t) {
       const size_t row = (size_t)t * R + i;
-      if (converged_all[row] != 0 && (status_all[row] & ~1) == 0) ++n;       // (~1: MKH_ST_OUTSIDE_LIMITS is no failure)
+      // (~1: MKH_ST_OUTSIDE_LIMITS is no failure.  The flags are optional for mkh_select_trajectory_candidates: absent, every
+      // row passes.  edge_margin_all — "THE RULE, with a checker" —: a waypoint entered by a motion that collides, or was not
+      // swept (NaN), does not count; waypoint 0's start edge is never asked)
+      if ((!converged_all || converged_all[row] != 0) && (!status_all || (status_all[row] & ~1) == 0) &&
+          (!edge_margin_all || t == 0 || edge_margin_all[row] >= 0.0))
+        ++n;
       const double* const cur = q_all + row * nq;
       len += ms_distance(jnt, njnt, cur, prev, weights);
       prev = cur;
@@ -96,9 +101,10 @@ __global__ __launch_bounds__(256) void tms_gather_i32_kernel(const int32_t* __re
 
 hipError_t launch_tms_score(hipStream_t stream, int B, int S, int T, int nq, int njnt, const int32_t* jnt, const double* q0,
                             const double* q_all, const int32_t* status_all, const int32_t* converged_all, const double* weights,
-                            int32_t* seed_index, int32_t* n_tracked, int32_t* n_complete, double* path_length) {
+                            const double* edge_margin_all, int32_t* seed_index, int32_t* n_tracked, int32_t* n_complete,
+                            double* path_length) {
   hipLaunchKernelGGL(tms_score_select_kernel, dim3((unsigned)B), dim3(64), 0, stream, B, S, T, nq, njnt, jnt, q0, q_all, status_all,
-                     converged_all, weights, seed_index, n_tracked, n_complete, path_length);
+                     converged_all, weights, edge_margin_all, seed_index, n_tracked, n_complete, path_length);
   return hipGetLastError();
 }
 

@@ -1396,12 +1396,55 @@ class TrajectoryMultistartResult(NamedTuple):
     seeds: Optional[np.ndarray] = None
 
 
+class FreeTrajectoryMultistartResult(NamedTuple):
+    """Result of solve_ik_trajectory_multistart(collision_check=...): TrajectoryMultistartResult's fields in its order — `n_tracked`
+    and `n_complete` count the waypoints that are tracked, free of collision and entered by a free motion; `status` and
+    `status_all` carry ST_IN_COLLISION where a row collides —, then of the chosen candidate `node_margin` and `edge_margin` (B, T)
+    (entry 0 of edge_margin +inf, NaN where the motion was not swept), `edge_collision` (B, T) bool, `n_edge_collisions` (B,)
+    and `tracked` (B, T) bool, the waypoints that counted: what refine_path(tracked=...) takes.  With return_all every
+    candidate's `node_margin_all` and `edge_margin_all` (B, S, T); None otherwise."""
+    q: np.ndarray
+    v: np.ndarray
+    status: np.ndarray
+    iters: np.ndarray
+    converged: np.ndarray
+    seed_index: np.ndarray
+    n_tracked: np.ndarray
+    n_complete: np.ndarray
+    path_length: np.ndarray
+    qvel: Optional[np.ndarray] = None
+    q_all: Optional[np.ndarray] = None
+    v_all: Optional[np.ndarray] = None
+    status_all: Optional[np.ndarray] = None
+    iters_all: Optional[np.ndarray] = None
+    converged_all: Optional[np.ndarray] = None
+    seeds: Optional[np.ndarray] = None
+    node_margin: Optional[np.ndarray] = None
+    edge_margin: Optional[np.ndarray] = None
+    edge_collision: Optional[np.ndarray] = None
+    n_edge_collisions: Optional[np.ndarray] = None
+    tracked: Optional[np.ndarray] = None
+    node_margin_all: Optional[np.ndarray] = None
+    edge_margin_all: Optional[np.ndarray] = None
+
+
+def _counted(eligible: np.ndarray, edge_margin: np.ndarray) -> np.ndarray:
+    """The waypoints of a chosen candidate that counted (include/minkhip.h "THE RULE, with a checker", Score), from its (B, T)
+    outputs: eligible, and — behind waypoint 0 — entered by a motion whose swept margin is >= 0."""
+    free_edge = np.zeros(edge_margin.shape, dtype=bool)
+    np.greater_equal(edge_margin, 0.0, out=free_edge, where=~np.isnan(edge_margin))
+    free_edge[:, 0] = True
+    return eligible & free_edge
+
+
 def solve_ik_trajectory_multistart(configuration: Configuration, tasks: Sequence, dt: float, targets, n_seeds: int, n_steps: int,
                                    pos_threshold: float, ori_threshold: float, solver: str = "mi355x", damping: float = 1e-12,
                                    limits: Optional[Sequence] = None, rng_seed: int = 0, seeds=None, weights=None,
                                    waypoint_dt: Optional[float] = None, warm_start: bool = False, update: bool = True,
                                    return_all: bool = False, max_instances: int = 1 << 20,
-                                   seed_table: Optional["SeedTable"] = None) -> TrajectoryMultistartResult:
+                                   seed_table: Optional["SeedTable"] = None,
+                                   collision_check: Optional["CollisionChecker"] = None,
+                                   edge_samples: int = 8) -> TrajectoryMultistartResult:
     """Track a time sequence of targets globally: `n_seeds` candidate trajectories per instance, seeded like
     solve_ik_multistart and each tracked like solve_ik_trajectory (waypoint t from the same candidate's waypoint t − 1, so a
     candidate is continuous by construction), scored over the whole path, one chosen and gathered on the device — in one call.
@@ -1419,8 +1462,17 @@ def solve_ik_trajectory_multistart(configuration: Configuration, tasks: Sequence
     configuration shards by instance; the result depends on neither.
 
     `seed_table` (a SeedTable; not together with `seeds`): candidates 1 … n_seeds − 1 start at the table's entries nearest to
-    waypoint 0's frame targets, as in solve_ik_multistart."""
+    waypoint 0's frame targets, as in solve_ik_multistart.
+
+    `collision_check` (a CollisionChecker of the same model): the candidate whose waypoints and motions are free of collision.
+    The loops are the same, bit for bit; behind them every row of every candidate is checked on the device (a row in collision
+    gets ST_IN_COLLISION and does not count), the motion into every row that still counts is swept from the same candidate's
+    previous row with `edge_samples` interior samples (CollisionChecker.swept_clearance's rule; the first motion, from the
+    configuration's q, is never swept), and a waypoint entered by a colliding motion does not count either.  Count, length and
+    ties then decide as above.  The result is a FreeTrajectoryMultistartResult.  Without collision_check the call is the one
+    above, unchanged."""
     del solver
+    _check_collision_check(collision_check, configuration, edge_samples)
     S, n_steps = int(n_seeds), int(n_steps)
     if S < 1:
         raise ValueError("n_seeds must be >= 1")
@@ -1447,19 +1499,30 @@ def solve_ik_trajectory_multistart(configuration: Configuration, tasks: Sequence
               rng_seed=int(rng_seed), weights=weights, qvel_dt=waypoint_dt, warm_start=bool(warm_start), return_all=bool(return_all))
 
     def job(handle, lo, hi):
-        out = handle.solve_trajectory_multistart(q[lo:hi], _rows(ft, 0, lo, hi), _rows(pt, 2, lo, hi), _rows(ct, 2, lo, hi), dt,
-                                                 damping, target_index0=lo, seeds=_rows(seeds, 0, lo, hi), seed_table=seed_table,
-                                                 **kw)
-        if not return_all:
-            return out
+        args = (q[lo:hi], _rows(ft, 0, lo, hi), _rows(pt, 2, lo, hi), _rows(ct, 2, lo, hi), dt, damping)
+        more = None
+        if collision_check is None:
+            out = handle.solve_trajectory_multistart(*args, target_index0=lo, seeds=_rows(seeds, 0, lo, hi), seed_table=seed_table,
+                                                     **kw)
+        else:
+            out, more = handle.solve_trajectory_multistart_free(*args, checker=collision_check, edge_samples=int(edge_samples),
+                                                                target_index0=lo, seeds=_rows(seeds, 0, lo, hi),
+                                                                seed_table=seed_table, **kw)
         # every candidate's results, time-major (T, n·S, ·) → (n, S, T, ·), so that chunks and shards concatenate by instance
         n = hi - lo
         by_inst = lambda x: np.ascontiguousarray(np.moveaxis(x.reshape((T, n, S) + x.shape[2:]), 0, 2))
-        return out._replace(q_all=by_inst(out.q_all), v_all=by_inst(out.v_all), status_all=by_inst(out.status_all),
-                            iters_all=by_inst(out.iters_all), converged_all=by_inst(out.converged_all),
-                            seeds=out.seeds.reshape(n, S, nq))
+        if return_all:
+            out = out._replace(q_all=by_inst(out.q_all), v_all=by_inst(out.v_all), status_all=by_inst(out.status_all),
+                               iters_all=by_inst(out.iters_all), converged_all=by_inst(out.converged_all),
+                               seeds=out.seeds.reshape(n, S, nq))
+        if more is None:
+            return out
+        every = (by_inst(more.node_margin_all), by_inst(more.edge_margin_all)) if return_all else (None, None)
+        return FreeTrajectoryMultistartResult(*out, more.node_margin, more.edge_margin, more.edge_collision, more.n_edge_collisions,
+                                              None, *every)
 
-    res = _join(TrajectoryMultistartResult, _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job))
+    res = _join(TrajectoryMultistartResult if collision_check is None else FreeTrajectoryMultistartResult,
+                _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job))
     _status_epilogue(res.status, "solve_ik_trajectory_multistart", "chosen trajectorie(s)",
                      "QP failed at {n} of {of} waypoints of the chosen candidates (first: (instance, waypoint) = {first}, "
                      "status {status})")
@@ -1467,10 +1530,93 @@ def solve_ik_trajectory_multistart(configuration: Configuration, tasks: Sequence
         configuration.update(res.q[:, -1] if configuration.batched else res.q[0, -1])
     un = configuration._unbatch
     opt = lambda x, as_bool=False: None if x is None else un(x.astype(bool) if as_bool else x)
-    return TrajectoryMultistartResult(un(res.q), un(res.v), un(res.status), un(res.iters), un(res.converged.astype(bool)),
-                                      un(res.seed_index), un(res.n_tracked), un(res.n_complete), un(res.path_length),
-                                      opt(res.qvel), opt(res.q_all), opt(res.v_all), opt(res.status_all), opt(res.iters_all),
-                                      opt(res.converged_all, True), opt(res.seeds))
+    out = TrajectoryMultistartResult(un(res.q), un(res.v), un(res.status), un(res.iters), un(res.converged.astype(bool)),
+                                     un(res.seed_index), un(res.n_tracked), un(res.n_complete), un(res.path_length),
+                                     opt(res.qvel), opt(res.q_all), opt(res.v_all), opt(res.status_all), opt(res.iters_all),
+                                     opt(res.converged_all, True), opt(res.seeds))
+    if collision_check is None:
+        return out
+    counted = _counted((res.converged != 0) & ((res.status & ~nat.ST_OUTSIDE_LIMITS) == 0), res.edge_margin)
+    return FreeTrajectoryMultistartResult(*out, un(res.node_margin), un(res.edge_margin), un(res.edge_collision.astype(bool)),
+                                          un(res.n_edge_collisions), un(counted), opt(res.node_margin_all),
+                                          opt(res.edge_margin_all))
+
+
+class CandidatePath(NamedTuple):
+    """Result of candidate_path: per instance the chosen `seed_index`, its path `q` (B, T, nq) — (T, nq) for an unbatched
+    configuration —, the `n_tracked` waypoints it tracked, `n_complete` of the S candidates and its `path_length`."""
+    seed_index: np.ndarray
+    q: np.ndarray
+    n_tracked: np.ndarray
+    n_complete: np.ndarray
+    path_length: np.ndarray
+
+
+class FreeCandidatePath(NamedTuple):
+    """Result of candidate_path(collision_check=...): CandidatePath's fields, then of the chosen candidate `node_margin` and
+    `edge_margin` (B, T), `edge_collision` (B, T) bool, `n_edge_collisions` (B,), `tracked` (B, T) bool — the waypoints that
+    counted — and every candidate's `node_margin_all` and `edge_margin_all` (B, S, T)."""
+    seed_index: np.ndarray
+    q: np.ndarray
+    n_tracked: np.ndarray
+    n_complete: np.ndarray
+    path_length: np.ndarray
+    node_margin: np.ndarray
+    edge_margin: np.ndarray
+    edge_collision: np.ndarray
+    n_edge_collisions: np.ndarray
+    tracked: np.ndarray
+    node_margin_all: np.ndarray
+    edge_margin_all: np.ndarray
+
+
+def candidate_path(configuration: Configuration, q_paths, tracked=None, weights=None,
+                   collision_check: Optional["CollisionChecker"] = None, edge_samples: int = 8) -> CandidatePath:
+    """The selection of solve_ik_trajectory_multistart alone, over the caller's own candidate paths: q_paths (S, T, nq) or
+    (B, S, T, nq), `tracked` (same leading shape, default: every waypoint counts as tracked), the first motion from the
+    configuration's q.  The rule — most tracked waypoints, then the shortest path Σ_t Σ_k weights_k·(q_t ⊖ q_{t−1})_k², then the
+    lowest index; nobody tracked anything: candidate 0 — is that call's; the configuration is not changed.
+
+    `collision_check` (a CollisionChecker of the same model): every row is checked on the device and a row in collision does
+    not count; the motion into every row that still counts is swept from the same candidate's previous row with `edge_samples`
+    interior samples, and a waypoint entered by a colliding motion does not count.  The result is then a FreeCandidatePath."""
+    from .tasks import PostureTask
+
+    _check_collision_check(collision_check, configuration, edge_samples)
+    B, nq, nv = configuration.batch_size, configuration.nq, configuration.nv
+    q_paths = _host_array(q_paths, "q_paths")
+    if q_paths is None or q_paths.ndim not in (3, 4) or q_paths.shape[-1] != nq or (q_paths.ndim == 4 and q_paths.shape[0] != B):
+        raise ValueError(f"q_paths must have shape (S, T, {nq}) or ({B}, S, T, {nq}), got {None if q_paths is None else q_paths.shape}")
+    S, T = q_paths.shape[-3], q_paths.shape[-2]
+    if S < 1 or T < 1:
+        raise ValueError(f"q_paths needs at least one candidate and one waypoint, got S = {S}, T = {T}")
+    # (B, S, T, ·) → the loops' time-major (T, B·S, ·)
+    q_tm = np.ascontiguousarray(np.moveaxis(np.broadcast_to(q_paths, (B, S, T, nq)), 2, 0)).reshape(T, B * S, nq)
+    trk_tm = None
+    if tracked is not None:
+        tracked = np.asarray(tracked.detach().cpu().numpy() if nat._is_torch(tracked) else tracked)
+        if tracked.shape not in ((S, T), (B, S, T)):
+            raise ValueError(f"tracked must have shape {(S, T)} or {(B, S, T)}, got {tracked.shape}")
+        trk_tm = np.ascontiguousarray(np.moveaxis(np.broadcast_to(tracked != 0, (B, S, T)), 2, 0)).reshape(T, B * S)
+    weights = _optional_array(weights, "weights", (nv,))
+    if weights is not None and not (weights >= 0.0).all():
+        raise ValueError("weights must be >= 0 (no NaN): the path length is a sum of non-negative terms")
+    # (the selection reads the model's joint table through a problem handle: the smallest one, a posture task, serves)
+    prob, layout = _compile(configuration, [PostureTask(configuration.model, cost=1.0)], None, 1, devices=configuration.devices[:1])
+    with _pin(configuration, layout):
+        out, more = prob.select_trajectory_candidates(configuration.q_batch, q_tm, trk_tm, weights, collision_check,
+                                                      int(edge_samples), collision_check is not None)
+    un = configuration._unbatch
+    path = CandidatePath(un(out.seed_index), un(out.q), un(out.n_tracked), un(out.n_complete), un(out.path_length))
+    if collision_check is None:
+        return path
+    by_inst = lambda x: np.ascontiguousarray(np.moveaxis(x.reshape(T, B, S), 0, 2))
+    given = np.ones((B, S, T), dtype=bool) if trk_tm is None else by_inst(trk_tm != 0)
+    chosen = given[np.arange(B), out.seed_index]                         # (B, T): the caller's flags of the chosen candidate
+    counted = _counted(chosen & (more.node_margin >= 0.0), more.edge_margin)
+    return FreeCandidatePath(*path, un(more.node_margin), un(more.edge_margin), un(more.edge_collision.astype(bool)),
+                             un(more.n_edge_collisions), un(counted), un(by_inst(more.node_margin_all)),
+                             un(by_inst(more.edge_margin_all)))
 
 
 class LadderResult(NamedTuple):
