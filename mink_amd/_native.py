@@ -9,6 +9,8 @@ every call raises.
 
 from __future__ import annotations
 
+import collections
+import itertools
 import ctypes as C
 import os
 import threading
@@ -57,6 +59,59 @@ FRAME_TYPE_ID = {"body": 0, "geom": 1, "site": 2}
 
 _pd = C.POINTER(C.c_double)
 _pi = C.POINTER(C.c_int32)
+_F8, _I4 = np.float64, np.int32
+_EVERY_NAMES = {"seeds_out": "seeds"}
+_LEADS = ("L", "P", "C")       # axes that stand for several: the (B, T) / (T, B) lead of a trajectory, a keyframed group's
+_NONE, _ALL, _MARGINS, _ALONE = frozenset(), frozenset({"all"}), frozenset({"margins"}), frozenset({"alone"})
+
+
+def _on(names: tuple, *flags) -> frozenset:
+    """The switches among `names` whose flag is set: the key of a table's generated function."""
+    return frozenset(itertools.compress(names, flags))
+
+
+class _out(dict):
+    """The outputs of one IO struct: field → (axes, dtype, condition), and `names` where the result calls a field otherwise
+    than the struct does.  An axis ("B T q") names an entry of the call's sizes, a number stands for itself; a field belongs to
+    a call when its condition is None or among the call's switches ("all": return_all, "qvel", "until", ...).
+
+    Allocation, the struct and the result all derive from the table BY NAME, once, when the module is imported: for every set
+    of its conditions `make[frozenset of switches]` is a generated straight-line function
+        make(empty, ptr, sizes, **struct fields) → (the struct, {result field: array})
+    that allocates the fields of that set, points a new struct at them — and at the inputs and numbers passed by keyword — and
+    names them as the result does.  A call costs what the same statements written out by hand cost."""
+
+    def __init__(self, struct, fields, names=None):
+        super().__init__(fields)
+        self.struct, self.names = struct, dict(names or {})
+        conditions = sorted({c for _, _, c in fields.values() if c is not None})
+        self.make = {}
+        for k in range(2 ** len(conditions)):
+            on = frozenset(c for i, c in enumerate(conditions) if k >> i & 1)
+            self.make[on] = self._generate(on)
+
+    def _generate(self, on):
+        def shape(axes):
+            lead, rest = (f"sizes[{axes[0]!r}] + ", axes[1:]) if axes[0] in _LEADS else ("", axes)
+            return lead + "(" + "".join((a if a.isdigit() else f"sizes[{a!r}]") + ", " for a in rest) + ")"
+
+        fields = [(n, axes.split(), "_F8" if dtype is _F8 else "_I4") for n, (axes, dtype, c) in self.items() if c is None or c in on]
+        source = ["def make(empty, ptr, sizes, **fields):"]
+        source += [f"    {n} = empty({shape(axes)}, {dtype})" for n, axes, dtype in fields]
+        source += ["    return struct(" + "".join(f"{n}=ptr({n}), " for n, _, _ in fields) + "**fields), {" +
+                   "".join(f"{self.names.get(n, n)!r}: {n}, " for n, _, _ in fields) + "}"]
+        scope = {"struct": self.struct, "_F8": _F8, "_I4": _I4}
+        exec("\n".join(source), scope)
+        return scope["make"]
+
+
+def _extended(name, base, own, doc, optional=True, module=__name__):
+    """The result type `name`: `base`'s fields in its order and with its defaults, behind them `own` — None by default, or,
+    not `optional`, required (`base` then has no defaults either)."""
+    defaults = [base._field_defaults[f] for f in base._fields if f in base._field_defaults] + [None] * len(own) if optional else None
+    cls = collections.namedtuple(name, base._fields + tuple(own), defaults=defaults, module=module)
+    cls.__doc__ = doc
+    return cls
 
 
 class MkhFlatModel(C.Structure):
@@ -152,6 +207,13 @@ class MultistartOut(NamedTuple):
     seeds: object = None
 
 
+_EVERY_SEED = {"q_all": ("B S q", _F8, "all"), "converged_all": ("B S", _I4, "all"), "iters_all": ("B S", _I4, "all"),
+               "status_all": ("B S", _I4, "all"), "seeds_out": ("B S q", _F8, "all")}
+MULTISTART_OUT = _out(MkhMultistartIO, {
+    "q_best": ("B q", _F8, None), "v_best": ("B v", _F8, None), "iters": ("B", _I4, None), "status": ("B", _I4, None),
+    "converged": ("B", _I4, None), "seed_index": ("B", _I4, None), "n_converged": ("B", _I4, None), **_EVERY_SEED},
+    {"q_best": "q", "v_best": "v", **_EVERY_NAMES})
+
 SOLUTION_SET_MAX_K = 64          # slots per target and candidates per target of a distinct set (include/minkhip.h
 SOLUTION_SET_MAX_S = 4096        # "THE RULE OF THE SET")
 SOLUTION_SET_IO_FIELDS = ("seeds", "q_ref", "weights", "q_set", "v_set", "iters", "status", "seed_index", "multiplicity",
@@ -194,6 +256,17 @@ class DistinctOut(NamedTuple):
     n_distinct: object
     n_valid: object
     n_uncovered: object
+
+
+# (mkh_select_distinct fills a part of these fields, and calls n_converged its n_valid: DISTINCT_OUT)
+SOLUTION_SET_OUT = _out(MkhSolutionSetIO, {
+    "q_set": ("B K q", _F8, None), "v_set": ("B K v", _F8, None), "seed_index": ("B K", _I4, None),
+    "distance": ("B K", _F8, None), "multiplicity": ("B K", _I4, None), "iters": ("B K", _I4, None),
+    "status": ("B K", _I4, None), "n_distinct": ("B", _I4, None), "n_converged": ("B", _I4, None),
+    "n_uncovered": ("B", _I4, None), **_EVERY_SEED}, {"q_set": "q", "v_set": "v", **_EVERY_NAMES})
+DISTINCT_OUT = _out(MkhSolutionSetIO, {n: SOLUTION_SET_OUT[n] for n in ("q_set", "seed_index", "distance", "multiplicity", "n_distinct",
+                                                                        "n_converged", "n_uncovered")},
+                    {"q_set": "q", "n_converged": "n_valid"})
 
 
 def check_solution_set(K: int, min_distance: float, S: Optional[int] = None) -> None:
@@ -264,6 +337,22 @@ class GoalSelectOut(NamedTuple):
     distance_goal: object
 
 
+# (mkh_select_goalset fills a part of these fields, and calls n_converged_goal its n_valid_goal: GOAL_SELECT_OUT)
+GOAL_SET_OUT = _out(MkhGoalSetIO, {
+    "q_best": ("B q", _F8, None), "v_best": ("B v", _F8, None), "converged": ("B", _I4, None),
+    "goal_index": ("B", _I4, None), "seed_index": ("B", _I4, None), "n_reached": ("B", _I4, None),
+    "score": ("B", _F8, None), "iters": ("B", _I4, None), "status": ("B", _I4, None),
+    "q_goal": ("B G q", _F8, None), "v_goal": ("B G v", _F8, None), "reached": ("B G", _I4, None),
+    "seed_index_goal": ("B G", _I4, None), "n_converged_goal": ("B G", _I4, None), "distance_goal": ("B G", _F8, None),
+    "iters_goal": ("B G", _I4, None), "status_goal": ("B G", _I4, None),
+    "q_all": ("B G S q", _F8, "all"), "converged_all": ("B G S", _I4, "all"), "iters_all": ("B G S", _I4, "all"),
+    "status_all": ("B G S", _I4, "all"), "seeds_out": ("B G S q", _F8, "all")}, {"q_best": "q", "v_best": "v", **_EVERY_NAMES})
+GOAL_SELECT_OUT = _out(MkhGoalSetIO, {n: GOAL_SET_OUT[n] for n in ("q_best", "converged", "goal_index", "seed_index", "n_reached", "score",
+                                                                   "q_goal", "reached", "seed_index_goal", "n_converged_goal",
+                                                                   "distance_goal")},
+                       {"q_best": "q", "n_converged_goal": "n_valid_goal"})
+
+
 def check_goalset_shape(B: int, G: int, S: int) -> None:
     """What mkh_solve_goalset / mkh_select_goalset refuse about the shape of a goal set, judged on the host: the selection keeps
     no per-candidate state, so the only cap is the row count of one call."""
@@ -277,24 +366,13 @@ def check_goalset_shape(B: int, G: int, S: int) -> None:
         raise ValueError(f"B*G*S = {B * G * S} rows in one call: at most {GOAL_SET_MAX_ROWS}")
 
 
-def _goal_inputs(goal_cost, goal_valid, B: int, G: int, prep, q):
-    """goal_cost (B, G) float64 and goal_valid (B, G) int32 of a native goal-set call in q's kind, shapes checked; a host
-    array's costs are judged here (finite, >= 0), a device tensor's by the rule's NaN clause."""
-    if goal_cost is not None:
-        if tuple(goal_cost.shape) != (B, G):
-            raise ValueError(f"goal_cost must have shape ({B}, {G}), got {tuple(goal_cost.shape)}")
-        goal_cost = prep(goal_cost)
-        if not _is_torch(goal_cost) and not (np.isfinite(goal_cost) & (goal_cost >= 0.0)).all():
-            raise ValueError("goal_cost must be finite and >= 0")
-    if goal_valid is not None:
-        if tuple(goal_valid.shape) != (B, G):
-            raise ValueError(f"goal_valid must have shape ({B}, {G}), got {tuple(goal_valid.shape)}")
-        if _is_torch(q):
-            import torch
-            goal_valid = (torch.as_tensor(goal_valid) != 0).to(device=q.device, dtype=torch.int32).contiguous()
-        else:
-            goal_valid = _i32(np.asarray(goal_valid) != 0)
-    return goal_cost, goal_valid
+def _goal_inputs(kit, goal_cost, goal_valid, B: int, G: int):
+    """goal_cost (B, G) float64 and goal_valid (B, G) int32 of a native goal-set call in the call's kind, shapes checked; a
+    host array's costs are judged here (finite, >= 0), a device tensor's by the rule's NaN clause."""
+    goal_cost = kit.prep(kit.want(goal_cost, (B, G), "goal_cost"))
+    if goal_cost is not None and not _is_torch(goal_cost) and not (np.isfinite(goal_cost) & (goal_cost >= 0.0)).all():
+        raise ValueError("goal_cost must be finite and >= 0")
+    return goal_cost, kit.flags01(goal_valid, (B, G), "goal_valid")
 
 
 TRAJECTORY_IO_FIELDS = ("q_traj", "v_traj", "status", "iters", "converged", "qvel", "waypoint_dt", "posture_per_waypoint",
@@ -317,6 +395,12 @@ class TrajectoryOut(NamedTuple):
     qvel: object = None
 
 
+# (L: the lead of the call, (B, T) or — time_major — (T, B); the three trajectory structs share these fields)
+TRAJECTORY_NAMES = {"q_traj": "q", "v_traj": "v", **_EVERY_NAMES}
+TRAJECTORY_OUT = _out(MkhTrajectoryIO, {
+    "q_traj": ("L q", _F8, None), "v_traj": ("L v", _F8, None), "status": ("L", _I4, None), "iters": ("L", _I4, "until"),
+    "converged": ("L", _I4, "until"), "qvel": ("L v", _F8, "qvel")}, TRAJECTORY_NAMES)
+
 KEYFRAME_IO_FIELDS = ("q_traj", "v_traj", "status", "iters", "converged", "qvel", "frame_targets_out", "posture_targets_out",
                       "com_targets_out", "waypoint_dt", "posture_keyframed", "com_keyframed", "time_major")
 
@@ -333,6 +417,15 @@ class KeyframesOut(NamedTuple):
     frame_targets: object = None
     posture_targets: object = None
     com_targets: object = None
+
+
+# MkhKeyframeIO: TRAJECTORY_OUT and, with return_targets, the interpolated targets of the groups that have keyframes (P, C: the
+# lead of a batched group, (T,) of one shared by the batch)
+KEYFRAME_OUT = _out(MkhKeyframeIO, {
+    **TRAJECTORY_OUT, "frame_targets_out": ("L nf 7", _F8, "frames"), "posture_targets_out": ("P np q", _F8, "postures"),
+    "com_targets_out": ("C nc 3", _F8, "coms")},
+    {**TRAJECTORY_NAMES, "frame_targets_out": "frame_targets", "posture_targets_out": "posture_targets",
+    "com_targets_out": "com_targets"})
 
 
 TRAJECTORY_MULTISTART_IO_FIELDS = ("seeds", "weights", "q_traj", "v_traj", "status", "iters", "converged", "seed_index", "n_tracked",
@@ -369,6 +462,13 @@ class TrajectoryMultistartOut(NamedTuple):
     seeds: object = None
 
 
+# (R = B·S candidate rows; every candidate's arrays are time-major whatever the lead is)
+TRAJECTORY_MULTISTART_OUT = _out(MkhTrajectoryMultistartIO, {
+    **TRAJECTORY_OUT, "seed_index": ("B", _I4, None), "n_tracked": ("B", _I4, None),
+    "n_complete": ("B", _I4, None), "path_length": ("B", _F8, None), "seeds_out": ("R q", _F8, "all"),
+    "q_all": ("T R q", _F8, "all"), "v_all": ("T R v", _F8, "all"), "status_all": ("T R", _I4, "all"),
+    "iters_all": ("T R", _I4, "all"), "converged_all": ("T R", _I4, "all")}, TRAJECTORY_NAMES)
+
 TRAJECTORY_FREE_IO_FIELDS = ("node_margin", "edge_margin", "edge_collision", "n_edge_collisions", "node_margin_all", "edge_margin_all")
 TRAJECTORY_CANDIDATES_IO_FIELDS = ("seed_index", "n_tracked", "n_complete", "path_length", "q_path")
 
@@ -404,6 +504,14 @@ class TrajectoryCandidatesOut(NamedTuple):
     q: object
 
 
+TRAJECTORY_FREE_OUT = _out(MkhTrajectoryFreeIO, {
+    "node_margin": ("L", _F8, None), "edge_margin": ("L", _F8, None), "edge_collision": ("L", _I4, None),
+    "n_edge_collisions": ("B", _I4, None), "node_margin_all": ("T R", _F8, "all"),
+    "edge_margin_all": ("T R", _F8, "all")})
+TRAJECTORY_CANDIDATES_OUT = _out(MkhTrajectoryCandidatesIO, {
+    "seed_index": ("B", _I4, None), "n_tracked": ("B", _I4, None), "n_complete": ("B", _I4, None),
+    "path_length": ("B", _F8, None), "q_path": ("B T q", _F8, None)}, {"q_path": "q"})
+
 LADDER_MAX_S = 256         # nodes per rung (back-pointers are bytes) and waypoints per path (include/minkhip.h "THE RULE")
 LADDER_MAX_T = 65535
 LADDER_IO_FIELDS = ("node_index", "n_tracked", "n_breaks", "path_length", "edge_break", "q_path")
@@ -422,6 +530,11 @@ class LadderPathOut(NamedTuple):
     path_length: object
     edge_break: object
     q: object
+
+
+LADDER_OUT = _out(MkhLadderIO, {
+    "node_index": ("B T", _I4, None), "n_tracked": ("B", _I4, None), "n_breaks": ("B", _I4, None),
+    "path_length": ("B", _F8, None), "edge_break": ("B T", _I4, None), "q_path": ("B T q", _F8, None)}, {"q_path": "q"})
 
 
 TRAJECTORY_LADDER_IO_FIELDS = ("seeds", "weights", "max_step_sq", "q_traj", "v_traj", "status", "iters", "converged", "node_index",
@@ -461,6 +574,15 @@ class TrajectoryLadderOut(NamedTuple):
     refined: object = None
 
 
+# (W: the nodes of a rung — S, or n_nodes of the ladder on distinct nodes)
+TRAJECTORY_LADDER_OUT = _out(MkhTrajectoryLadderIO, {
+    "q_traj": ("B T q", _F8, None), "v_traj": ("B T v", _F8, None), "status": ("B T", _I4, None),
+    "iters": ("B T", _I4, None), "converged": ("B T", _I4, None), "node_index": ("B T", _I4, None),
+    "n_tracked": ("B", _I4, None), "n_breaks": ("B", _I4, None), "path_length": ("B", _F8, None),
+    "edge_break": ("B T", _I4, None), "qvel": ("B T v", _F8, "qvel"), "q_all": ("B T W q", _F8, "all"),
+    "v_all": ("B T W v", _F8, "all"), "status_all": ("B T W", _I4, "all"), "iters_all": ("B T W", _I4, "all"),
+    "converged_all": ("B T W", _I4, "all"), "seeds_out": ("B T S q", _F8, "all")}, TRAJECTORY_NAMES)
+
 LADDER_REFINE_IO_FIELDS = ("weights", "max_step_sq", "q_path_out", "tracked_out", "repaired", "refined", "edge_break", "n_tracked",
                            "n_breaks", "path_length", "v", "status", "iters", "converged")
 
@@ -488,6 +610,14 @@ class LadderRefineOut(NamedTuple):
     converged: object = None
 
 
+# ("alone": what mkh_ladder_refine itself writes; behind a fused ladder the path's outputs are the ladder struct's.  v, status,
+# iters and converged are the caller's in-out arrays: copies of them are put into the struct, nothing is allocated)
+LADDER_REFINE_OUT = _out(MkhLadderRefineIO, {
+    "q_path_out": ("B T q", _F8, "alone"), "tracked_out": ("B T", _I4, None), "repaired": ("B T", _I4, None),
+    "refined": ("B", _I4, None), "edge_break": ("B T", _I4, "alone"), "n_tracked": ("B", _I4, "alone"),
+    "n_breaks": ("B", _I4, "alone"), "path_length": ("B", _F8, "alone")}, {"q_path_out": "q", "tracked_out": "tracked"})
+
+
 def check_ladder_shape(S: int, T: int, max_step_sq: float) -> None:
     """The limits of include/minkhip.h "THE RULE" on a ladder's shape and gate, with no device in sight."""
     if S < 1:
@@ -510,38 +640,16 @@ class MkhLadderNodesIO(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in LADDER_NODES_IO_FIELDS]
 
 
-class TrajectoryLadderNodesOut(NamedTuple):
+LADDER_NODES_OUT = _out(MkhLadderNodesIO, {
+    "node_seed_index": ("B T K", _I4, None), "node_multiplicity": ("B T K", _I4, None),
+    "node_distance": ("B T K", _F8, None), "n_distinct": ("B T", _I4, None), "n_converged": ("B T", _I4, None),
+    "n_uncovered": ("B T", _I4, None), "seed_index": ("B T", _I4, None)})
+TrajectoryLadderNodesOut = _extended(
+    "TrajectoryLadderNodesOut", TrajectoryLadderOut, LADDER_NODES_IO_FIELDS,
     """What NativeProblem.solve_trajectory_ladder_nodes returns (arrays of the caller's kind): TrajectoryLadderOut's fields, in
     its order — with return_all the *_all fields are the NODES' rows, (B, T, K, ·), and `seeds` the (B, T, S, nq) starts — and
     behind them the set's: `node_seed_index`, `node_multiplicity`, `node_distance` (B, T, K), `n_distinct`, `n_converged`,
-    `n_uncovered` (B, T), and `seed_index` (B, T), the chosen node's candidate index."""
-    q: object
-    v: object
-    status: object
-    iters: object
-    converged: object
-    node_index: object
-    n_tracked: object
-    n_breaks: object
-    path_length: object
-    edge_break: object
-    qvel: object = None
-    q_all: object = None
-    v_all: object = None
-    status_all: object = None
-    iters_all: object = None
-    converged_all: object = None
-    seeds: object = None
-    tracked: object = None
-    repaired: object = None
-    refined: object = None
-    node_seed_index: object = None
-    node_multiplicity: object = None
-    node_distance: object = None
-    n_distinct: object = None
-    n_converged: object = None
-    n_uncovered: object = None
-    seed_index: object = None
+    `n_uncovered` (B, T), and `seed_index` (B, T), the chosen node's candidate index.""")
 
 
 def check_ladder_nodes_shape(S: int, K: int, T: int, max_step_sq: float, min_distance: float) -> None:
@@ -621,6 +729,10 @@ class LadderFreeOut(NamedTuple):
     edge_margin_all: object = None
 
 
+LADDER_FREE_OUT = _out(MkhLadderFreeIO, {
+    "edge_collision": ("B T", _I4, None), "n_edge_collisions": ("B", _I4, None), "edge_margin": ("B T", _F8, None),
+    "node_margin": ("B T S", _F8, "margins"), "edge_margin_all": ("B T S S", _F8, "margins")})
+
 LADDER_REFINE_FREE_IO_FIELDS = ("edge_collision", "n_edge_collisions", "edge_margin", "node_margin")
 
 
@@ -628,27 +740,15 @@ class MkhLadderRefineFreeIO(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in LADDER_REFINE_FREE_IO_FIELDS]
 
 
-class LadderRefineFreeOut(NamedTuple):
+LADDER_REFINE_FREE_OUT = _out(MkhLadderRefineFreeIO, {
+    "edge_collision": ("B T", _I4, None), "n_edge_collisions": ("B", _I4, None),
+    "edge_margin": ("B T", _F8, None), "node_margin": ("B T", _F8, None)})
+LadderRefineFreeOut = _extended(
+    "LadderRefineFreeOut", LadderRefineOut, LADDER_REFINE_FREE_IO_FIELDS,
     """What NativeProblem.ladder_refine_free returns (include/minkhip.h "THE RULE OF THE REFINEMENT, with a checker"):
     LadderRefineOut's fields in its order — `tracked` the EFFECTIVE flags of the returned path —, then of the returned path
     edge_collision (B, T) int32, n_edge_collisions (B,) int32, edge_margin (B, T) (entry 0 +inf, NaN where not swept) and
-    node_margin (B, T)."""
-    q: object
-    tracked: object
-    repaired: object
-    refined: object
-    edge_break: object
-    n_tracked: object
-    n_breaks: object
-    path_length: object
-    v: object = None
-    status: object = None
-    iters: object = None
-    converged: object = None
-    edge_collision: object = None
-    n_edge_collisions: object = None
-    edge_margin: object = None
-    node_margin: object = None
+    node_margin (B, T).""")
 
 
 class MkhTaps(C.Structure):
@@ -868,39 +968,105 @@ def _is_torch(x) -> bool:
     return type(x).__module__.split(".")[0] == "torch"
 
 
-def _call_kit(q):
-    """(prep, empty, ptr, stream, flag) of an outer-loop call, from the kind of its q.  numpy: float64 host arrays, the default
-    stream, no flag; torch: float64 tensors on q's device, the current stream's handle, FLAG_DEVICE_PTRS.  prep(x) brings an
-    optional input into that form, empty(shape, np.float64 | np.int32) makes an output, ptr(x) is its address (None for None)."""
-    if not _is_torch(q):
-        return ((lambda x: None if x is None else _f64(x)), (lambda shape, dtype: np.empty(shape, dtype=dtype)),
-                (lambda x: None if x is None else x.ctypes.data), None, 0)
-    import torch
-    dev = q.device
+def _shape_text(shape) -> str:
+    """A shape as a tuple prints, symbolic axes ("B", "T") by their names."""
+    return "(" + ", ".join(str(a) for a in shape) + ("," if len(shape) == 1 else "") + ")"
 
-    def prep(x):
-        if x is None or (x.dtype is torch.float64 and x.device == dev and x.is_contiguous()):
+
+def _host_address(x):
+    return None if x is None else x.ctypes.data
+
+
+def _device_address(x):
+    return None if x is None else x.data_ptr()
+
+
+class _Kit:
+    """The argument kit of an outer-loop call, from the kind of its q.  numpy: float64 host arrays, the default stream, no flag;
+    torch: float64 tensors on q's device, the current stream's handle, FLAG_DEVICE_PTRS in `devp`.  It unpacks into (prep, empty,
+    ptr, stream, devp) for the calls that need no more."""
+
+    def __init__(self, q):
+        self.torch, self.dev, self.stream, self.devp = None, None, None, 0
+        # ptr(x): the address of an array of the call's kind, None for None; empty(shape, np.float64 | np.int32): an output array
+        self.ptr, self.empty = _host_address, np.empty
+        if _is_torch(q):
+            import torch
+            self.torch, self.dev, self.ptr, self.empty = torch, q.device, _device_address, self._device_empty
+            self.stream, self.devp = _raw_stream(torch, q.device), FLAG_DEVICE_PTRS
+
+    def __iter__(self):
+        return iter((self.prep, self.empty, self.ptr, self.stream, self.devp))
+
+    def prep(self, x):
+        """An optional input as a contiguous float64 array of the call's kind."""
+        if self.torch is None:
+            return None if x is None else _f64(x)
+        if x is None or (x.dtype is self.torch.float64 and x.device == self.dev and x.is_contiguous()):
             return x
-        return torch.as_tensor(x).to(device=dev, dtype=torch.float64).contiguous()
+        return self.torch.as_tensor(x).to(device=self.dev, dtype=self.torch.float64).contiguous()
 
-    def empty(shape, dtype):
-        return torch.empty(shape, dtype=torch.float64 if dtype is np.float64 else torch.int32, device=dev)
+    def _device_empty(self, shape, dtype):
+        return self.torch.empty(shape, dtype=self.torch.float64 if dtype is np.float64 else self.torch.int32, device=self.dev)
 
-    return prep, empty, (lambda x: None if x is None else x.data_ptr()), _raw_stream(torch, dev), FLAG_DEVICE_PTRS
+    def ones(self, shape):
+        """int32 flags that are all set: "None means every row"."""
+        x = self.empty(shape, np.int32)
+        x[...] = 1
+        return x
+
+    @staticmethod
+    def want(x, shape, name, required=False):
+        """x, its shape checked: an int axis must match, a named one ("T") takes any size.  None passes unless `required`."""
+        if x is None and not required:
+            return None
+        got = None if x is None else tuple(x.shape)
+        if got != shape and (x is None or len(got) != len(shape) or
+                             any(a != b for a, b in zip(shape, got) if not isinstance(a, str))):
+            raise ValueError(f"{name} must have shape {_shape_text(shape)}, got {got}")
+        return x
+
+    def flags01(self, x, shape, name):
+        """The caller's flags as a fresh contiguous int32 0 / 1 array of the call's kind (None stays None)."""
+        if self.want(x, shape, name) is None:
+            return None
+        if self.torch is None:
+            return _i32(np.asarray(x) != 0)
+        return (self.torch.as_tensor(x) != 0).to(device=self.dev, dtype=self.torch.int32).contiguous()
+
+    def i32_copy(self, x, shape, name):
+        """A caller's in-out integers as a fresh contiguous int32 array of the call's kind (None stays None)."""
+        if self.want(x, shape, name) is None:
+            return None
+        if self.torch is None:
+            return np.array(x, dtype=np.int32, order="C")
+        return self.torch.as_tensor(x).to(device=self.dev, dtype=self.torch.int32).contiguous().clone()
+
+    def f64_copy(self, x, shape, name):
+        """A caller's in-out reals as a fresh contiguous float64 array of the call's kind (None stays None)."""
+        if self.want(x, shape, name) is None:
+            return None
+        return np.array(x, dtype=np.float64, order="C") if self.torch is None else self.prep(x).clone()
 
 
-def _held_or_batched(x, B: int, n: int, w: int, name: str, flag: int, strict: bool = True):
-    """The flag bit of a posture / CoM target from its shape: 0 for one target held for the batch, (n, w); `flag` for one per
-    instance, (B, n, w).  Any other shape raises — or, not `strict`, returns None for the caller to read further."""
+def _call_kit(q) -> _Kit:
+    """The kit of a call whose arrays are of q's kind."""
+    return _Kit(q)
+
+
+def _held_or_rows(x, lead: tuple, n: int, w: int, name: str, flag: int, strict: bool = True):
+    """The flag bit of a posture / CoM target from its shape: 0 for one target held for the whole call, (n, w); `flag` for one per
+    row of the call's lead — (B,), (B, G) or (B, T) —, lead + (n, w).  Any other shape raises — or, not `strict`, returns None for
+    the caller to read further."""
     if x is None:
         raise ValueError(f"{name} is required")
     shp = tuple(x.shape)
     if shp == (n, w):
         return 0
-    if shp == (B, n, w):
+    if shp == lead + (n, w):
         return flag
     if strict:
-        raise ValueError(f"{name} must have shape ({n}, {w}) or (B, ...)")
+        raise ValueError(f"{name} must have shape {(n, w)} or {lead + (n, w)}, got {shp}")
     return None
 
 
@@ -1437,6 +1603,28 @@ class NativeProblem:
         _check(lib().mkh_solve(*args, flags, stream))
         return v, st
 
+    # ---------------------------------------------- what every fan-out call asks
+    @staticmethod
+    def _kernel_flags(wave: bool, lane: bool, quad: bool, extra: int = 0) -> int:
+        return (FLAG_WAVE_KERNEL if wave else 0) | (FLAG_LANE_KERNEL if lane else 0) | (FLAG_QUAD_KERNEL if quad else 0) | int(extra)
+
+    def _refuse_dense(self, what: str) -> None:
+        if self.n_dense_rows or self.n_dense_limit_rows or self.dense_limit_box:
+            raise ValueError(f"dense (plugin) rows are evaluated by the caller at q: no fused loop, no {what}")
+
+    def _need_frame(self, what: str) -> None:
+        if not self.n_frame:
+            raise ValueError(f"{what} needs at least one frame task to test the thresholds on")
+
+    def _held_flags(self, posture_target, com_target, lead: tuple) -> int:
+        """FLAG_POSTURE_BATCHED / FLAG_COM_BATCHED from the shapes of the two targets, each held or one per row of `lead`."""
+        m, flags = self.nmodel.model, 0
+        if self.n_posture:
+            flags |= _held_or_rows(posture_target, lead, self.n_posture, m.nq, "posture_target", FLAG_POSTURE_BATCHED)
+        if self.n_com:
+            flags |= _held_or_rows(com_target, lead, self.n_com, 3, "com_target", FLAG_COM_BATCHED)
+        return flags
+
     # ------------------------------------------------------------ multi-start
     def solve_multistart(self, q, frame_targets=None, posture_target=None, com_target=None, dt: float = 1e-2,
                          damping: float = 1e-12, *, n_seeds: int, max_iters: int, pos_threshold: float, ori_threshold: float,
@@ -1512,41 +1700,22 @@ class NativeProblem:
         """mkh_select_distinct: the rule of solve_multistart_set alone over the caller's own candidates — q_candidates
         (B, S, nq), valid (B, S) (None: every candidate), reference (B, nq) (required), weights (nv,).  numpy in → numpy out
         (synchronous); torch CUDA tensors in → torch tensors out on the current stream, no host copy."""
-        m = self.nmodel.model
+        m, kit = self.nmodel.model, _call_kit(q_candidates)
         K = int(n_solutions)
-        if len(q_candidates.shape) != 3:
-            raise ValueError(f"q_candidates must have shape (B, S, {m.nq}), got {tuple(q_candidates.shape)}")
+        kit.want(q_candidates, ("B", "S", m.nq), "q_candidates")
         B, S = int(q_candidates.shape[0]), int(q_candidates.shape[1])
         check_solution_set(K, float(min_distance), S)
         if B < 1 or S < 1:
             raise ValueError(f"q_candidates must hold at least one target and one candidate, got {tuple(q_candidates.shape)}")
-        prep, empty, ptr, stream, devp = _call_kit(q_candidates)
-        q_candidates, reference, weights = prep(q_candidates), prep(reference), prep(weights)
-        if tuple(q_candidates.shape) != (B, S, m.nq):
-            raise ValueError(f"q_candidates must have shape (B, S, {m.nq}), got {tuple(q_candidates.shape)}")
-        if reference is None or tuple(reference.shape) != (B, m.nq):
-            raise ValueError(f"reference must have shape ({B}, {m.nq})")
-        if weights is not None and tuple(weights.shape) != (m.nv,):
-            raise ValueError(f"weights must have shape ({m.nv},), got {tuple(weights.shape)}")
-        if valid is not None:
-            if tuple(valid.shape) != (B, S):
-                raise ValueError(f"valid must have shape ({B}, {S}), got {tuple(valid.shape)}")
-            if devp:
-                import torch
-                valid = (valid != 0).to(device=q_candidates.device, dtype=torch.int32).contiguous()
-            else:
-                valid = _i32(np.asarray(valid) != 0)
-        f8, i4 = np.float64, np.int32
-        out = {"q_set": empty((B, K, m.nq), f8), "seed_index": empty((B, K), i4), "distance": empty((B, K), f8),
-               "multiplicity": empty((B, K), i4), "n_distinct": empty((B,), i4), "n_converged": empty((B,), i4),
-               "n_uncovered": empty((B,), i4)}
-        io = MkhSolutionSetIO()
-        for n, x in out.items():
-            setattr(io, n, ptr(x))
+        q_candidates = kit.prep(q_candidates)
+        reference = kit.want(kit.prep(reference), (B, m.nq), "reference", required=True)
+        weights = kit.want(kit.prep(weights), (m.nv,), "weights")
+        valid = kit.flags01(valid, (B, S), "valid")
+        io, out = DISTINCT_OUT.make[_NONE](kit.empty, kit.ptr, dict(B=B, K=K, q=m.nq))
         with self._lock:
-            _check(lib().mkh_select_distinct(self.handle, B, S, ptr(q_candidates), ptr(valid), ptr(reference), ptr(weights), K,
-                                             float(min_distance), C.byref(io), devp, stream))
-        return DistinctOut(*out.values())
+            _check(lib().mkh_select_distinct(self.handle, B, S, kit.ptr(q_candidates), kit.ptr(valid), kit.ptr(reference),
+                                             kit.ptr(weights), K, float(min_distance), C.byref(io), kit.devp, kit.stream))
+        return DistinctOut(**out)
 
     def solve_goalset(self, q, frame_targets=None, posture_target=None, com_target=None, dt: float = 1e-2,
                       damping: float = 1e-12, *, n_seeds: int, max_iters: int, pos_threshold: float, ori_threshold: float,
@@ -1564,72 +1733,35 @@ class NativeProblem:
         solve_multistart — a goal whose candidates all collide is not reached."""
         if seeds is not None and seed_table is not None:
             raise ValueError("seeds and seed_table are two sources of the same starts: pass one of them")
-        m = self.nmodel.model
+        m, kit = self.nmodel.model, _call_kit(q)
         B, S, max_iters = int(q.shape[0]), int(n_seeds), int(max_iters)
         if max_iters < 1:
             raise ValueError("max_iters must be >= 1")
-        if self.n_dense_rows or self.n_dense_limit_rows or self.dense_limit_box:
-            raise ValueError("dense (plugin) rows are evaluated by the caller at q: no fused loop, no goal set")
-        if not self.n_frame:
-            raise ValueError("a goal set needs at least one frame task to test the thresholds on")
-        if frame_targets is None or len(frame_targets.shape) != 4:
-            raise ValueError(f"frame_targets must have shape (B, G, {self.n_frame}, 7)")
+        self._refuse_dense("goal set")
+        self._need_frame("a goal set")
+        kit.want(frame_targets, (B, "G", self.n_frame, 7), "frame_targets", required=True)
         G = int(frame_targets.shape[1])
         check_goalset_shape(B, G, S)
         if S > self.max_batch:
             raise MinkHipError(f"n_seeds={S} exceeds max_batch={self.max_batch} of this problem")
-        flags = (FLAG_WAVE_KERNEL if wave_kernel else 0) | (FLAG_LANE_KERNEL if lane_kernel else 0) | \
-            (FLAG_QUAD_KERNEL if quad_kernel else 0)
-        prep, empty, ptr, stream, devp = _call_kit(q)
-        flags |= devp
-        q, frame_targets, posture_target, com_target = prep(q), prep(frame_targets), prep(posture_target), prep(com_target)
-        seeds, reference, weights = prep(seeds), prep(reference), prep(weights)
-        if tuple(q.shape) != (B, m.nq):
-            raise ValueError(f"q must have shape (B, {m.nq}), got {tuple(q.shape)}")
-        if tuple(frame_targets.shape) != (B, G, self.n_frame, 7):
-            raise ValueError(f"frame_targets must have shape ({B}, G, {self.n_frame}, 7), got {tuple(frame_targets.shape)}")
-
-        def held_or_rows(x, n, w, name, flag):
-            if x is None:
-                raise ValueError(f"{name} is required")
-            if tuple(x.shape) == (n, w):
-                return 0
-            if tuple(x.shape) == (B, G, n, w):
-                return flag
-            raise ValueError(f"{name} must have shape ({n}, {w}) or ({B}, {G}, {n}, {w}), got {tuple(x.shape)}")
-
-        if self.n_posture:
-            flags |= held_or_rows(posture_target, self.n_posture, m.nq, "posture_target", FLAG_POSTURE_BATCHED)
-        if self.n_com:
-            flags |= held_or_rows(com_target, self.n_com, 3, "com_target", FLAG_COM_BATCHED)
-        if seeds is not None and tuple(seeds.shape) != (B, G, S, m.nq):
-            raise ValueError(f"seeds must have shape ({B}, {G}, {S}, {m.nq}), got {tuple(seeds.shape)}")
-        if reference is not None and tuple(reference.shape) != (B, m.nq):
-            raise ValueError(f"reference must have shape ({B}, {m.nq}), got {tuple(reference.shape)}")
-        if weights is not None and tuple(weights.shape) != (m.nv,):
-            raise ValueError(f"weights must have shape ({m.nv},), got {tuple(weights.shape)}")
-        goal_cost, goal_valid = _goal_inputs(goal_cost, goal_valid, B, G, prep, q)
-        f8, i4 = np.float64, np.int32
-        out = {"q_best": empty((B, m.nq), f8), "v_best": empty((B, m.nv), f8), "converged": empty((B,), i4),
-               "goal_index": empty((B,), i4), "seed_index": empty((B,), i4), "n_reached": empty((B,), i4),
-               "score": empty((B,), f8), "iters": empty((B,), i4), "status": empty((B,), i4),
-               "q_goal": empty((B, G, m.nq), f8), "v_goal": empty((B, G, m.nv), f8), "reached": empty((B, G), i4),
-               "seed_index_goal": empty((B, G), i4), "n_converged_goal": empty((B, G), i4), "distance_goal": empty((B, G), f8),
-               "iters_goal": empty((B, G), i4), "status_goal": empty((B, G), i4)}
-        every = dict.fromkeys(("q_all", "converged_all", "iters_all", "status_all", "seeds_out"))
-        if return_all:
-            every = {"q_all": empty((B, G, S, m.nq), f8), "converged_all": empty((B, G, S), i4), "iters_all": empty((B, G, S), i4),
-                     "status_all": empty((B, G, S), i4), "seeds_out": empty((B, G, S, m.nq), f8)}
-        io = MkhGoalSetIO()
-        io.seeds, io.q_ref, io.weights, io.goal_cost, io.goal_valid = ptr(seeds), ptr(reference), ptr(weights), ptr(goal_cost), \
-            ptr(goal_valid)
-        for n, x in {**out, **every}.items():
-            setattr(io, n, ptr(x))
+        q = kit.want(kit.prep(q), ("B", m.nq), "q")
+        frame_targets, posture_target, com_target = kit.prep(frame_targets), kit.prep(posture_target), kit.prep(com_target)
+        flags = self._kernel_flags(wave_kernel, lane_kernel, quad_kernel, kit.devp) | \
+            self._held_flags(posture_target, com_target, (B, G))
+        seeds = kit.want(kit.prep(seeds), (B, G, S, m.nq), "seeds")
+        reference = kit.want(kit.prep(reference), (B, m.nq), "reference")
+        weights = kit.want(kit.prep(weights), (m.nv,), "weights")
+        goal_cost, goal_valid = _goal_inputs(kit, goal_cost, goal_valid, B, G)
+        ptr = kit.ptr
+        io, out = GOAL_SET_OUT.make[_ALL if return_all else _NONE](
+            kit.empty, ptr, dict(B=B, G=G, S=S, q=m.nq, v=m.nv), seeds=ptr(seeds), q_ref=ptr(reference), weights=ptr(weights),
+            goal_cost=ptr(goal_cost), goal_valid=ptr(goal_valid))
         with self._lock, _attached(self, seed_table), _checked(self, collision_check):
-            _check(lib().mkh_solve_goalset(self.handle, B, G, ptr(q), ptr(frame_targets), ptr(posture_target), ptr(com_target),
-                                           float(dt), float(damping), max_iters, float(pos_threshold), float(ori_threshold), S,
-                                           int(rng_seed) & (2 ** 64 - 1), int(target_index0), C.byref(io), flags, stream))
-        return GoalSetOut(*out.values(), *every.values())
+            _check(lib().mkh_solve_goalset(self.handle, B, G, kit.ptr(q), kit.ptr(frame_targets), kit.ptr(posture_target),
+                                           kit.ptr(com_target), float(dt), float(damping), max_iters, float(pos_threshold),
+                                           float(ori_threshold), S, int(rng_seed) & (2 ** 64 - 1), int(target_index0), C.byref(io),
+                                           flags, kit.stream))
+        return GoalSetOut(**out)
 
     def select_goalset(self, q_candidates, valid=None, reference=None, weights=None, *, goal_cost=None,
                        goal_valid=None) -> GoalSelectOut:
@@ -1637,46 +1769,26 @@ class NativeProblem:
         (B, G, S, nq), valid (B, G, S) (None: every candidate), reference (B, nq) (required), weights (nv,), goal_cost and
         goal_valid (B, G).  numpy in → numpy out (synchronous); torch CUDA tensors in → torch tensors out on the current
         stream, no host copy."""
-        m = self.nmodel.model
-        if len(q_candidates.shape) != 4:
-            raise ValueError(f"q_candidates must have shape (B, G, S, {m.nq}), got {tuple(q_candidates.shape)}")
+        m, kit = self.nmodel.model, _call_kit(q_candidates)
+        kit.want(q_candidates, ("B", "G", "S", m.nq), "q_candidates")
         B, G, S = (int(x) for x in q_candidates.shape[:3])
         check_goalset_shape(B, G, S)
-        prep, empty, ptr, stream, devp = _call_kit(q_candidates)
-        q_candidates, reference, weights = prep(q_candidates), prep(reference), prep(weights)
-        if tuple(q_candidates.shape) != (B, G, S, m.nq):
-            raise ValueError(f"q_candidates must have shape (B, G, S, {m.nq}), got {tuple(q_candidates.shape)}")
-        if reference is None or tuple(reference.shape) != (B, m.nq):
-            raise ValueError(f"reference must have shape ({B}, {m.nq})")
-        if weights is not None and tuple(weights.shape) != (m.nv,):
-            raise ValueError(f"weights must have shape ({m.nv},), got {tuple(weights.shape)}")
-        if valid is not None:
-            if tuple(valid.shape) != (B, G, S):
-                raise ValueError(f"valid must have shape ({B}, {G}, {S}), got {tuple(valid.shape)}")
-            if devp:
-                import torch
-                valid = (torch.as_tensor(valid) != 0).to(device=q_candidates.device, dtype=torch.int32).contiguous()
-            else:
-                valid = _i32(np.asarray(valid) != 0)
-        goal_cost, goal_valid = _goal_inputs(goal_cost, goal_valid, B, G, prep, q_candidates)
-        f8, i4 = np.float64, np.int32
-        out = {"q_best": empty((B, m.nq), f8), "converged": empty((B,), i4), "goal_index": empty((B,), i4),
-               "seed_index": empty((B,), i4), "n_reached": empty((B,), i4), "score": empty((B,), f8),
-               "q_goal": empty((B, G, m.nq), f8), "reached": empty((B, G), i4), "seed_index_goal": empty((B, G), i4),
-               "n_converged_goal": empty((B, G), i4), "distance_goal": empty((B, G), f8)}
-        io = MkhGoalSetIO()
-        io.goal_cost, io.goal_valid = ptr(goal_cost), ptr(goal_valid)
-        for n, x in out.items():
-            setattr(io, n, ptr(x))
+        q_candidates = kit.prep(q_candidates)
+        reference = kit.want(kit.prep(reference), (B, m.nq), "reference", required=True)
+        weights = kit.want(kit.prep(weights), (m.nv,), "weights")
+        valid = kit.flags01(valid, (B, G, S), "valid")
+        goal_cost, goal_valid = _goal_inputs(kit, goal_cost, goal_valid, B, G)
+        io, out = GOAL_SELECT_OUT.make[_NONE](kit.empty, kit.ptr, dict(B=B, G=G, q=m.nq), goal_cost=kit.ptr(goal_cost),
+                                              goal_valid=kit.ptr(goal_valid))
         with self._lock:
-            _check(lib().mkh_select_goalset(self.handle, B, G, S, ptr(q_candidates), ptr(valid), ptr(reference), ptr(weights),
-                                            C.byref(io), devp, stream))
-        return GoalSelectOut(*out.values())
+            _check(lib().mkh_select_goalset(self.handle, B, G, S, kit.ptr(q_candidates), kit.ptr(valid), kit.ptr(reference),
+                                            kit.ptr(weights), C.byref(io), kit.devp, kit.stream))
+        return GoalSelectOut(**out)
 
     def _solve_multistart(self, q, frame_targets, posture_target, com_target, dt, damping, S, max_iters, pos_thr, ori_thr,
                           rng_seed, target_index0, seeds, reference, weights, return_all, wave_kernel, lane_kernel, quad_kernel,
                           solution_set=None, extra_flags: int = 0):
-        m = self.nmodel.model
+        m, kit = self.nmodel.model, _call_kit(q)
         B = int(q.shape[0])
         if S < 1:
             raise ValueError("n_seeds must be >= 1")
@@ -1684,64 +1796,28 @@ class NativeProblem:
             raise ValueError("max_iters must be >= 1")
         if B * S > self.max_batch:
             raise MinkHipError(f"B*n_seeds={B * S} exceeds max_batch={self.max_batch} of this problem")
-        if self.n_dense_rows or self.n_dense_limit_rows or self.dense_limit_box:
-            raise ValueError("dense (plugin) rows are evaluated by the caller at q: no fused loop, no multi-start")
-        flags = (FLAG_WAVE_KERNEL if wave_kernel else 0) | (FLAG_LANE_KERNEL if lane_kernel else 0) | \
-            (FLAG_QUAD_KERNEL if quad_kernel else 0) | int(extra_flags)
-        prep, empty, ptr, stream, devp = _call_kit(q)
-        flags |= devp
-        q, frame_targets, posture_target, com_target = prep(q), prep(frame_targets), prep(posture_target), prep(com_target)
-        seeds, reference, weights = prep(seeds), prep(reference), prep(weights)
-        if tuple(q.shape) != (B, m.nq):
-            raise ValueError(f"q must have shape (B, {m.nq}), got {tuple(q.shape)}")
-        if not self.n_frame:
-            raise ValueError("multi-start needs at least one frame task to test the thresholds on")
-        if frame_targets is None or tuple(frame_targets.shape) != (B, self.n_frame, 7):
-            raise ValueError(f"frame_targets must have shape ({B}, {self.n_frame}, 7)")
-        if self.n_posture:
-            flags |= _held_or_batched(posture_target, B, self.n_posture, m.nq, "posture_target", FLAG_POSTURE_BATCHED)
-        if self.n_com:
-            flags |= _held_or_batched(com_target, B, self.n_com, 3, "com_target", FLAG_COM_BATCHED)
-        if seeds is not None and tuple(seeds.shape) != (B, S, m.nq):
-            raise ValueError(f"seeds must have shape ({B}, {S}, {m.nq}), got {tuple(seeds.shape)}")
-        if reference is not None and tuple(reference.shape) != (B, m.nq):
-            raise ValueError(f"reference must have shape ({B}, {m.nq}), got {tuple(reference.shape)}")
-        if weights is not None and tuple(weights.shape) != (m.nv,):
-            raise ValueError(f"weights must have shape ({m.nv},), got {tuple(weights.shape)}")
-        f, i = np.float64, np.int32
+        self._refuse_dense("multi-start")
+        q = kit.want(kit.prep(q), ("B", m.nq), "q")
+        self._need_frame("multi-start")
+        frame_targets = kit.want(kit.prep(frame_targets), (B, self.n_frame, 7), "frame_targets", required=True)
+        posture_target, com_target = kit.prep(posture_target), kit.prep(com_target)
+        flags = self._kernel_flags(wave_kernel, lane_kernel, quad_kernel, int(extra_flags) | kit.devp) | \
+            self._held_flags(posture_target, com_target, (B,))
+        seeds = kit.want(kit.prep(seeds), (B, S, m.nq), "seeds")
+        reference = kit.want(kit.prep(reference), (B, m.nq), "reference")
+        weights = kit.want(kit.prep(weights), (m.nv,), "weights")
+        ptr = kit.ptr
         if solution_set is None:
-            out = {"q_best": empty((B, m.nq), f), "v_best": empty((B, m.nv), f), "iters": empty((B,), i), "status": empty((B,), i),
-                   "converged": empty((B,), i), "seed_index": empty((B,), i), "n_converged": empty((B,), i)}
-            io = MkhMultistartIO()
+            table, cls, call = MULTISTART_OUT, MultistartOut, lib().mkh_solve_multistart
         else:
-            K = solution_set[0]
-            out = {"q_set": empty((B, K, m.nq), f), "v_set": empty((B, K, m.nv), f), "seed_index": empty((B, K), i),
-                   "distance": empty((B, K), f), "multiplicity": empty((B, K), i), "iters": empty((B, K), i),
-                   "status": empty((B, K), i), "n_distinct": empty((B,), i), "n_converged": empty((B,), i),
-                   "n_uncovered": empty((B,), i)}
-            io = MkhSolutionSetIO()
-        n_own = len(out)
-        if return_all:
-            out.update({"q_all": empty((B * S, m.nq), f), "converged_all": empty((B * S,), i), "iters_all": empty((B * S,), i),
-                        "status_all": empty((B * S,), i), "seeds_out": empty((B * S, m.nq), f)})
-        io.seeds, io.q_ref, io.weights = ptr(seeds), ptr(reference), ptr(weights)
-        for n, x in out.items():
-            setattr(io, n, ptr(x))
-        head = (self.handle, B, ptr(q), ptr(frame_targets), ptr(posture_target), ptr(com_target), float(dt), float(damping),
-                max_iters, pos_thr, ori_thr, S)
-        tail = (rng_seed & (2 ** 64 - 1), target_index0, C.byref(io), flags, stream)
-        if solution_set is None:
-            _check(lib().mkh_solve_multistart(*head, *tail))
-        else:
-            _check(lib().mkh_solve_multistart_set(*head, solution_set[0], solution_set[1], *tail))
-        extra = ()
-        if return_all:
-            extra = (out["q_all"].reshape(B, S, m.nq), out["converged_all"].reshape(B, S), out["iters_all"].reshape(B, S),
-                     out["status_all"].reshape(B, S), out["seeds_out"].reshape(B, S, m.nq))
-        if solution_set is not None:
-            return SolutionSetOut(*list(out.values())[:n_own], *extra)
-        return MultistartOut(out["q_best"], out["v_best"], out["converged"], out["seed_index"], out["n_converged"],
-                             out["iters"], out["status"], *extra)
+            table, cls, call = SOLUTION_SET_OUT, SolutionSetOut, lib().mkh_solve_multistart_set
+        io, out = table.make[_ALL if return_all else _NONE](
+            kit.empty, ptr, dict(B=B, S=S, K=solution_set[0] if solution_set else 0, q=m.nq, v=m.nv), seeds=ptr(seeds),
+            q_ref=ptr(reference), weights=ptr(weights))
+        _check(call(self.handle, B, kit.ptr(q), kit.ptr(frame_targets), kit.ptr(posture_target), kit.ptr(com_target), float(dt),
+                    float(damping), max_iters, pos_thr, ori_thr, S, *(solution_set or ()), rng_seed & (2 ** 64 - 1), target_index0,
+                    C.byref(io), flags, kit.stream))
+        return cls(**out)
 
     # ------------------------------------------------------------- trajectory
     def solve_trajectory(self, q, frame_targets=None, posture_target=None, com_target=None, dt: float = 1e-2,
@@ -1826,45 +1902,29 @@ class NativeProblem:
         checker", `tracked` playing converged_all: returns (TrajectoryCandidatesOut, TrajectoryFreeOut), the latter (B, T) and, with
         `return_margins`, with node_margin_all and edge_margin_all (T, B·S).  numpy in → numpy out (synchronous); torch CUDA
         tensors in → torch tensors out on the current stream, no host copy."""
-        m = self.nmodel.model
+        m, kit = self.nmodel.model, _call_kit(q)
         if checker is not None:
             checker = _checker_handle(self, checker, edge_samples)
         B = int(q.shape[0])
         if len(q_paths.shape) != 3 or int(q_paths.shape[0]) < 1 or int(q_paths.shape[1]) < B or int(q_paths.shape[1]) % B:
             raise ValueError(f"q_paths must have shape (T, B*S, {m.nq}) with B = {B}, got {tuple(q_paths.shape)}")
         T, R = int(q_paths.shape[0]), int(q_paths.shape[1])
-        S = R // B
-        prep, empty, ptr, stream, devp = _call_kit(q)
-        q, q_paths, weights = prep(q), prep(q_paths), prep(weights)
-        if tuple(q.shape) != (B, m.nq):
-            raise ValueError(f"q must have shape (B, {m.nq}), got {tuple(q.shape)}")
-        if tuple(q_paths.shape) != (T, R, m.nq):
-            raise ValueError(f"q_paths must have shape ({T}, {R}, {m.nq}), got {tuple(q_paths.shape)}")
-        if weights is not None and tuple(weights.shape) != (m.nv,):
-            raise ValueError(f"weights must have shape ({m.nv},), got {tuple(weights.shape)}")
-        if tracked is not None:
-            if tuple(tracked.shape) != (T, R):
-                raise ValueError(f"tracked must have shape ({T}, {R}), got {tuple(tracked.shape)}")
-            if devp:
-                import torch
-                tracked = (tracked != 0).to(device=q.device, dtype=torch.int32).contiguous()
-            else:
-                tracked = _i32(np.asarray(tracked) != 0)
-        f8, i4 = np.float64, np.int32
-        out = TrajectoryCandidatesOut(empty((B,), i4), empty((B,), i4), empty((B,), i4), empty((B,), f8), empty((B, T, m.nq), f8))
-        io = MkhTrajectoryCandidatesIO(*[ptr(x) for x in out])
+        q = kit.want(kit.prep(q), ("B", m.nq), "q")
+        q_paths = kit.want(kit.prep(q_paths), (T, R, m.nq), "q_paths")
+        weights = kit.want(kit.prep(weights), (m.nv,), "weights")
+        tracked = kit.flags01(tracked, (T, R), "tracked")
+        sizes = dict(L=(B, T), B=B, T=T, R=R, q=m.nq)
+        io, out = TRAJECTORY_CANDIDATES_OUT.make[_NONE](kit.empty, kit.ptr, sizes)
+        rows = (B, T, R // B, kit.ptr(q), kit.ptr(q_paths), kit.ptr(tracked), kit.ptr(weights))
         if checker is None:
             with self._lock:
-                _check(lib().mkh_select_trajectory_candidates(self.handle, None, B, T, S, ptr(q), ptr(q_paths), ptr(tracked),
-                                                              ptr(weights), 0, C.byref(io), None, devp, stream))
-            return out, None
-        more = TrajectoryFreeOut(empty((B, T), f8), empty((B, T), f8), empty((B, T), i4), empty((B,), i4),
-                                 empty((T, R), f8) if return_margins else None, empty((T, R), f8) if return_margins else None)
-        fio = MkhTrajectoryFreeIO(*[ptr(x) for x in more])
+                _check(lib().mkh_select_trajectory_candidates(self.handle, None, *rows, 0, C.byref(io), None, kit.devp, kit.stream))
+            return TrajectoryCandidatesOut(**out), None
+        fio, more = TRAJECTORY_FREE_OUT.make[_ALL if return_margins else _NONE](kit.empty, kit.ptr, sizes)
         with _with_checker(self, checker):
-            _check(lib().mkh_select_trajectory_candidates(self.handle, checker.handle, B, T, S, ptr(q), ptr(q_paths), ptr(tracked),
-                                                          ptr(weights), int(edge_samples), C.byref(io), C.byref(fio), devp, stream))
-        return out, more
+            _check(lib().mkh_select_trajectory_candidates(self.handle, checker.handle, *rows, int(edge_samples), C.byref(io),
+                                                          C.byref(fio), kit.devp, kit.stream))
+        return TrajectoryCandidatesOut(**out), TrajectoryFreeOut(**more)
 
     # ----------------------------------------------------------------- ladder
     def ladder_select(self, q, q_nodes, tracked=None, max_step_sq: float = float("inf"), weights=None) -> LadderPathOut:
@@ -1882,48 +1942,26 @@ class NativeProblem:
         return self._ladder_select(q, q_nodes, tracked, max_step_sq, weights, checker, int(edge_samples), bool(return_margins))
 
     def _ladder_select(self, q, q_nodes, tracked, max_step_sq, weights, checker, edge_samples, return_margins):
-        m = self.nmodel.model
+        m, kit = self.nmodel.model, _call_kit(q)
         B = int(q.shape[0])
-        if len(q_nodes.shape) != 4:
-            raise ValueError(f"q_nodes must have shape (B, T, S, {m.nq}), got {tuple(q_nodes.shape)}")
+        kit.want(q_nodes, (B, "T", "S", m.nq), "q_nodes")
         T, S = int(q_nodes.shape[1]), int(q_nodes.shape[2])
         check_ladder_shape(S, T, float(max_step_sq))
-        prep, empty, ptr, stream, devp = _call_kit(q)
-        q, q_nodes, weights = prep(q), prep(q_nodes), prep(weights)
-        if tuple(q.shape) != (B, m.nq):
-            raise ValueError(f"q must have shape (B, {m.nq}), got {tuple(q.shape)}")
-        if tuple(q_nodes.shape) != (B, T, S, m.nq):
-            raise ValueError(f"q_nodes must have shape ({B}, T, S, {m.nq}), got {tuple(q_nodes.shape)}")
-        if weights is not None and tuple(weights.shape) != (m.nv,):
-            raise ValueError(f"weights must have shape ({m.nv},), got {tuple(weights.shape)}")
-        if tracked is None:
-            tracked = empty((B, T, S), np.int32)
-            tracked[...] = 1
-        elif tuple(tracked.shape) != (B, T, S):
-            raise ValueError(f"tracked must have shape ({B}, {T}, {S}), got {tuple(tracked.shape)}")
-        elif devp:
-            import torch
-            tracked = (tracked != 0).to(device=q.device, dtype=torch.int32).contiguous()
-        else:
-            tracked = _i32(np.asarray(tracked) != 0)
-        f8, i4 = np.float64, np.int32
-        out = {"node_index": empty((B, T), i4), "n_tracked": empty((B,), i4), "n_breaks": empty((B,), i4),
-               "path_length": empty((B,), f8), "edge_break": empty((B, T), i4), "q_path": empty((B, T, m.nq), f8)}
-        io = MkhLadderIO()
-        for n, x in out.items():
-            setattr(io, n, ptr(x))
+        q, q_nodes = kit.want(kit.prep(q), ("B", m.nq), "q"), kit.prep(q_nodes)
+        weights = kit.want(kit.prep(weights), (m.nv,), "weights")
+        tracked = kit.ones((B, T, S)) if tracked is None else kit.flags01(tracked, (B, T, S), "tracked")
+        sizes = dict(B=B, T=T, S=S, q=m.nq)
+        io, out = LADDER_OUT.make[_NONE](kit.empty, kit.ptr, sizes)
+        rungs = (B, T, S, kit.ptr(q), kit.ptr(q_nodes), kit.ptr(tracked), kit.ptr(weights), float(max_step_sq))
         if checker is None:
             with self._lock:
-                _check(lib().mkh_ladder_select(self.handle, B, T, S, ptr(q), ptr(q_nodes), ptr(tracked), ptr(weights),
-                                               float(max_step_sq), C.byref(io), devp, stream))
-            return LadderPathOut(*[out[n] for n in LADDER_IO_FIELDS]), None
-        more = LadderFreeOut(empty((B, T), i4), empty((B,), i4), empty((B, T), f8),
-                             empty((B, T, S), f8) if return_margins else None, empty((B, T, S, S), f8) if return_margins else None)
-        fio = MkhLadderFreeIO(*[ptr(x) for x in more])
+                _check(lib().mkh_ladder_select(self.handle, *rungs, C.byref(io), kit.devp, kit.stream))
+            return LadderPathOut(**out), None
+        fio, more = LADDER_FREE_OUT.make[_MARGINS if return_margins else _NONE](kit.empty, kit.ptr, sizes)
         with _with_checker(self, checker):
-            _check(lib().mkh_ladder_select_free(self.handle, checker.handle, B, T, S, ptr(q), ptr(q_nodes), ptr(tracked), ptr(weights),
-                                                float(max_step_sq), edge_samples, C.byref(io), C.byref(fio), devp, stream))
-        return LadderPathOut(*[out[n] for n in LADDER_IO_FIELDS]), more
+            _check(lib().mkh_ladder_select_free(self.handle, checker.handle, *rungs, edge_samples, C.byref(io), C.byref(fio),
+                                                kit.devp, kit.stream))
+        return LadderPathOut(**out), LadderFreeOut(**more)
 
     def solve_trajectory_ladder(self, q, frame_targets=None, posture_target=None, com_target=None, dt: float = 1e-2,
                                 damping: float = 1e-12, *, n_seeds: int, max_iters: int, pos_threshold: float,
@@ -1988,7 +2026,7 @@ class NativeProblem:
         edge_samples) — the result is then (the plain result, LadderFreeOut)."""
         if seeds is not None and seed_table is not None:
             raise ValueError("seeds and seed_table are two sources of the same starts: pass one of them")
-        m = self.nmodel.model
+        m, kit = self.nmodel.model, _call_kit(q)
         B, S, max_iters = int(q.shape[0]), int(n_seeds), int(max_iters)
         if max_iters < 1:
             raise ValueError("max_iters must be >= 1")
@@ -1996,105 +2034,57 @@ class NativeProblem:
             raise ValueError("qvel_dt must be > 0")
         if not (float(pos_threshold) >= 0.0 and float(ori_threshold) >= 0.0):
             raise ValueError("thresholds must be >= 0: a ladder's rungs run in threshold mode only")
-        if self.n_dense_rows or self.n_dense_limit_rows or self.dense_limit_box:
-            raise ValueError("dense (plugin) rows are evaluated by the caller at q: no fused loop, no ladder")
-        if not self.n_frame:
-            raise ValueError("a ladder needs at least one frame task to test the thresholds on")
-        if frame_targets is None or len(frame_targets.shape) != 4:
-            raise ValueError(f"frame_targets must have shape (B, T, {self.n_frame}, 7)")
+        self._refuse_dense("ladder")
+        self._need_frame("a ladder")
+        kit.want(frame_targets, (B, "T", self.n_frame, 7), "frame_targets", required=True)
         T = int(frame_targets.shape[1])
+        K, r, unwind = nodes or (0, 0.0, False)
         if nodes is None:
             check_ladder_shape(S, T, float(max_step_sq))
         else:
-            check_ladder_nodes_shape(S, nodes[0], T, float(max_step_sq), nodes[1])
-        W = S if nodes is None else nodes[0]          # nodes per rung: what the *_all arrays hold
+            check_ladder_nodes_shape(S, K, T, float(max_step_sq), r)
         if S > self.max_batch:
             raise MinkHipError(f"n_seeds={S} exceeds max_batch={self.max_batch} of this problem")
         if refine and B > self.max_batch:
             raise MinkHipError(f"B={B} exceeds max_batch={self.max_batch} of this problem (a sweep of the refinement is one launch)")
-        flags = (FLAG_WAVE_KERNEL if wave_kernel else 0) | (FLAG_LANE_KERNEL if lane_kernel else 0) | \
-            (FLAG_QUAD_KERNEL if quad_kernel else 0)
-        prep, empty, ptr, stream, devp = _call_kit(q)
-        flags |= devp
-        q, frame_targets, posture_target, com_target = prep(q), prep(frame_targets), prep(posture_target), prep(com_target)
-        seeds, weights = prep(seeds), prep(weights)
-        if tuple(q.shape) != (B, m.nq):
-            raise ValueError(f"q must have shape (B, {m.nq}), got {tuple(q.shape)}")
-        if tuple(frame_targets.shape) != (B, T, self.n_frame, 7):
-            raise ValueError(f"frame_targets must have shape ({B}, T, {self.n_frame}, 7), got {tuple(frame_targets.shape)}")
-
-        def held_or_rows(x, n, w, name, flag):
-            if x is None:
-                raise ValueError(f"{name} is required")
-            if tuple(x.shape) == (n, w):
-                return 0
-            if tuple(x.shape) == (B, T, n, w):
-                return flag
-            raise ValueError(f"{name} must have shape ({n}, {w}) or ({B}, {T}, {n}, {w}), got {tuple(x.shape)}")
-
-        if self.n_posture:
-            flags |= held_or_rows(posture_target, self.n_posture, m.nq, "posture_target", FLAG_POSTURE_BATCHED)
-        if self.n_com:
-            flags |= held_or_rows(com_target, self.n_com, 3, "com_target", FLAG_COM_BATCHED)
-        if seeds is not None and tuple(seeds.shape) != (B, T, S, m.nq):
-            raise ValueError(f"seeds must have shape ({B}, {T}, {S}, {m.nq}), got {tuple(seeds.shape)}")
-        if weights is not None and tuple(weights.shape) != (m.nv,):
-            raise ValueError(f"weights must have shape ({m.nv},), got {tuple(weights.shape)}")
-        f8, i4 = np.float64, np.int32
-        out = {"q_traj": empty((B, T, m.nq), f8), "v_traj": empty((B, T, m.nv), f8), "status": empty((B, T), i4),
-               "iters": empty((B, T), i4), "converged": empty((B, T), i4), "node_index": empty((B, T), i4),
-               "n_tracked": empty((B,), i4), "n_breaks": empty((B,), i4), "path_length": empty((B,), f8),
-               "edge_break": empty((B, T), i4), "qvel": empty((B, T, m.nv), f8) if qvel_dt is not None else None}
-        every = dict.fromkeys(("q_all", "v_all", "status_all", "iters_all", "converged_all", "seeds_out"))
-        if return_all:
-            every = {"q_all": empty((B, T, W, m.nq), f8), "v_all": empty((B, T, W, m.nv), f8), "status_all": empty((B, T, W), i4),
-                     "iters_all": empty((B, T, W), i4), "converged_all": empty((B, T, W), i4),
-                     "seeds_out": empty((B, T, S, m.nq), f8)}
-        io = MkhTrajectoryLadderIO()
-        io.seeds, io.weights, io.max_step_sq = ptr(seeds), ptr(weights), float(max_step_sq)
-        io.waypoint_dt = float(qvel_dt) if qvel_dt is not None else 0.0
-        for n, x in {**out, **every}.items():
-            setattr(io, n, ptr(x))
-        rio, extra = None, (None, None, None)
-        if refine:
-            extra = (empty((B, T), i4), empty((B, T), i4), empty((B,), i4))
-            rio = MkhLadderRefineIO()
-            rio.tracked_out, rio.repaired, rio.refined = (ptr(x) for x in extra)
-        head = (ptr(q), ptr(frame_targets), ptr(posture_target), ptr(com_target), float(dt), float(damping), max_iters,
-                float(pos_threshold), float(ori_threshold), int(rng_seed) & (2 ** 64 - 1), int(target_index0), C.byref(io))
-        tail = (C.byref(rio) if rio is not None else None,)
-        plain = [out[n] for n in ("q_traj", "v_traj", "status", "iters", "converged", "node_index", "n_tracked", "n_breaks",
-                                  "path_length", "edge_break", "qvel")] + \
-            [every[n] for n in ("q_all", "v_all", "status_all", "iters_all", "converged_all", "seeds_out")] + list(extra)
-        if nodes is None and free is None:
+        q = kit.want(kit.prep(q), ("B", m.nq), "q")
+        frame_targets, posture_target, com_target = kit.prep(frame_targets), kit.prep(posture_target), kit.prep(com_target)
+        flags = self._kernel_flags(wave_kernel, lane_kernel, quad_kernel, kit.devp | (FLAG_UNWIND_TURNS if unwind else 0)) | \
+            self._held_flags(posture_target, com_target, (B, T))
+        seeds = kit.want(kit.prep(seeds), (B, T, S, m.nq), "seeds")
+        weights = kit.want(kit.prep(weights), (m.nv,), "weights")
+        # (W, the nodes of a rung: what the *_all arrays hold)
+        sizes = dict(B=B, T=T, S=S, K=K, W=S if nodes is None else K, q=m.nq, v=m.nv)
+        empty, ptr = kit.empty, kit.ptr
+        io, out = TRAJECTORY_LADDER_OUT.make[_on(("qvel", "all"), qvel_dt is not None, return_all)](
+            empty, ptr, sizes, seeds=ptr(seeds), weights=ptr(weights), max_step_sq=float(max_step_sq),
+            waypoint_dt=float(qvel_dt) if qvel_dt is not None else 0.0)
+        rio = nio = None
+        if refine:                                  # (tracked, repaired, refined: the pass's own; the path's outputs are `out`'s)
+            rio, fixed = LADDER_REFINE_OUT.make[_NONE](empty, ptr, sizes)
+            out.update(fixed)
+            rio = C.byref(rio)
+        if nodes is not None:
+            nio, sets = LADDER_NODES_OUT.make[_NONE](empty, ptr, sizes)
+            out.update(sets)
+            nio = C.byref(nio)
+        loops = (ptr(q), ptr(frame_targets), ptr(posture_target), ptr(com_target), float(dt), float(damping),
+                 max_iters, float(pos_threshold), float(ori_threshold), int(rng_seed) & (2 ** 64 - 1), int(target_index0))
+        result = TrajectoryLadderOut if nodes is None else TrajectoryLadderNodesOut
+        if free is None:
             with self._lock, _attached(self, seed_table):
-                _check(lib().mkh_solve_trajectory_ladder_refined(self.handle, B, T, S, *head, *tail, flags, stream))
-            return TrajectoryLadderOut(*plain)
-        if free is not None:
-            more = LadderFreeOut(empty((B, T), i4), empty((B,), i4), empty((B, T), f8))
-            fio = MkhLadderFreeIO(*[ptr(x) for x in more])
-            free_call = lib().mkh_solve_trajectory_ladder_free_refined if refine else lib().mkh_solve_trajectory_ladder_free
-        if nodes is None:
-            with _with_checker(self, free[0]), _attached(self, seed_table):
-                _check(free_call(self.handle, free[0].handle, B, T, S, 0, 0.0, *head[:-1], free[1], head[-1],
-                                 None, *tail, C.byref(fio), flags, stream))
-            return TrajectoryLadderOut(*plain), more
-        K, r, unwind = nodes
-        sets = {"node_seed_index": empty((B, T, K), i4), "node_multiplicity": empty((B, T, K), i4),
-                "node_distance": empty((B, T, K), f8), "n_distinct": empty((B, T), i4), "n_converged": empty((B, T), i4),
-                "n_uncovered": empty((B, T), i4), "seed_index": empty((B, T), i4)}
-        nio = MkhLadderNodesIO()
-        for n, x in sets.items():
-            setattr(nio, n, ptr(x))
-        if free is not None:
-            with _with_checker(self, free[0]), _attached(self, seed_table):
-                _check(free_call(self.handle, free[0].handle, B, T, S, K, r, *head[:-1], free[1], head[-1],
-                                 C.byref(nio), *tail, C.byref(fio), flags | (FLAG_UNWIND_TURNS if unwind else 0), stream))
-            return TrajectoryLadderNodesOut(*plain, *[sets[n] for n in LADDER_NODES_IO_FIELDS]), more
-        with self._lock, _attached(self, seed_table):
-            _check(lib().mkh_solve_trajectory_ladder_nodes(self.handle, B, T, S, K, r, *head, C.byref(nio), *tail,
-                                                           flags | (FLAG_UNWIND_TURNS if unwind else 0), stream))
-        return TrajectoryLadderNodesOut(*plain, *[sets[n] for n in LADDER_NODES_IO_FIELDS])
+                if nodes is None:
+                    _check(lib().mkh_solve_trajectory_ladder_refined(self.handle, B, T, S, *loops, C.byref(io), rio, flags, kit.stream))
+                else:
+                    _check(lib().mkh_solve_trajectory_ladder_nodes(self.handle, B, T, S, K, r, *loops, C.byref(io), nio, rio, flags,
+                                                                   kit.stream))
+            return result(**out)
+        fio, more = LADDER_FREE_OUT.make[_NONE](empty, ptr, sizes)
+        call = lib().mkh_solve_trajectory_ladder_free_refined if refine else lib().mkh_solve_trajectory_ladder_free
+        with _with_checker(self, free[0]), _attached(self, seed_table):
+            _check(call(self.handle, free[0].handle, B, T, S, K, r, *loops, free[1], C.byref(io), nio, rio, C.byref(fio), flags,
+                        kit.stream))
+        return result(**out), LadderFreeOut(**more)
 
     def ladder_refine(self, q, q_path, tracked=None, frame_targets=None, posture_target=None, com_target=None, dt: float = 1e-2,
                       damping: float = 1e-12, *, max_iters: int, pos_threshold: float, ori_threshold: float,
@@ -2127,100 +2117,48 @@ class NativeProblem:
         >= 0.  `v` (B, T, nv), `status`, `iters`, `converged` (B, T): what the caller knows of its path's nodes; copies come
         back with the rows of repaired nodes replaced.  numpy in → numpy out (synchronous); torch CUDA tensors in → torch
         tensors out on the current stream, no host copy."""
-        m = self.nmodel.model
+        m, kit = self.nmodel.model, _call_kit(q)
         B, max_iters = int(q.shape[0]), int(max_iters)
         if max_iters < 1:
             raise ValueError("max_iters must be >= 1")
         if not (float(pos_threshold) >= 0.0 and float(ori_threshold) >= 0.0):
             raise ValueError("thresholds must be >= 0: the refinement's loops run in threshold mode only")
-        if self.n_dense_rows or self.n_dense_limit_rows or self.dense_limit_box:
-            raise ValueError("dense (plugin) rows are evaluated by the caller at q: no fused loop, no ladder refinement")
-        if not self.n_frame:
-            raise ValueError("a ladder refinement needs at least one frame task to test the thresholds on")
-        if q_path is None or len(q_path.shape) != 3 or tuple(q_path.shape) != (B, int(q_path.shape[1]), m.nq):
-            raise ValueError(f"q_path must have shape ({B}, T, {m.nq}), got {None if q_path is None else tuple(q_path.shape)}")
+        self._refuse_dense("ladder refinement")
+        self._need_frame("a ladder refinement")
+        kit.want(q_path, (B, "T", m.nq), "q_path", required=True)
         T = int(q_path.shape[1])
         check_ladder_shape(1, T, float(max_step_sq))
         if B > self.max_batch:
             raise MinkHipError(f"B={B} exceeds max_batch={self.max_batch} of this problem")
-        flags = (FLAG_WAVE_KERNEL if wave_kernel else 0) | (FLAG_LANE_KERNEL if lane_kernel else 0) | \
-            (FLAG_QUAD_KERNEL if quad_kernel else 0)
-        prep, empty, ptr, stream, devp = _call_kit(q)
-        flags |= devp
-        q, q_path, frame_targets = prep(q), prep(q_path), prep(frame_targets)
-        posture_target, com_target, weights = prep(posture_target), prep(com_target), prep(weights)
-        if tuple(q.shape) != (B, m.nq):
-            raise ValueError(f"q must have shape (B, {m.nq}), got {tuple(q.shape)}")
-        if frame_targets is None or tuple(frame_targets.shape) != (B, T, self.n_frame, 7):
-            raise ValueError(f"frame_targets must have shape ({B}, {T}, {self.n_frame}, 7), got "
-                             f"{None if frame_targets is None else tuple(frame_targets.shape)}")
-
-        def held_or_rows(x, n, w, name, flag):
-            if x is None:
-                raise ValueError(f"{name} is required")
-            if tuple(x.shape) == (n, w):
-                return 0
-            if tuple(x.shape) == (B, T, n, w):
-                return flag
-            raise ValueError(f"{name} must have shape ({n}, {w}) or ({B}, {T}, {n}, {w}), got {tuple(x.shape)}")
-
-        if self.n_posture:
-            flags |= held_or_rows(posture_target, self.n_posture, m.nq, "posture_target", FLAG_POSTURE_BATCHED)
-        if self.n_com:
-            flags |= held_or_rows(com_target, self.n_com, 3, "com_target", FLAG_COM_BATCHED)
-        if weights is not None and tuple(weights.shape) != (m.nv,):
-            raise ValueError(f"weights must have shape ({m.nv},), got {tuple(weights.shape)}")
-
-        def i32_copy(x, name, flag_like=False):
-            """A caller's (B, T) integers as a fresh int32 array of the call's kind (flags: 0 / 1)."""
-            if tuple(x.shape) != (B, T):
-                raise ValueError(f"{name} must have shape ({B}, {T}), got {tuple(x.shape)}")
-            if devp:
-                import torch
-                x = torch.as_tensor(x).to(device=q.device)
-                return ((x != 0) if flag_like else x).to(dtype=torch.int32).contiguous().clone()
-            x = np.asarray(x)
-            return np.array((x != 0) if flag_like else x, dtype=np.int32, order="C")
-
-        if tracked is None:
-            tracked = empty((B, T), np.int32)
-            tracked[...] = 1
-        else:
-            tracked = i32_copy(tracked, "tracked", True)
-        f8, i4 = np.float64, np.int32
-        if v is not None:
-            if tuple(v.shape) != (B, T, m.nv):
-                raise ValueError(f"v must have shape ({B}, {T}, {m.nv}), got {tuple(v.shape)}")
-            v = prep(v).clone() if devp else np.array(v, dtype=f8, order="C")
-        status = None if status is None else i32_copy(status, "status")
-        iters = None if iters is None else i32_copy(iters, "iters")
-        converged = None if converged is None else i32_copy(converged, "converged")
-        out = {"q_path_out": empty((B, T, m.nq), f8), "tracked_out": empty((B, T), i4), "repaired": empty((B, T), i4),
-               "refined": empty((B,), i4), "edge_break": empty((B, T), i4), "n_tracked": empty((B,), i4),
-               "n_breaks": empty((B,), i4), "path_length": empty((B,), f8), "v": v, "status": status, "iters": iters,
-               "converged": converged}
-        io = MkhLadderRefineIO()
-        io.weights, io.max_step_sq = ptr(weights), float(max_step_sq)
-        for n, x in out.items():
-            setattr(io, n, ptr(x))
-        if free is not None:
-            more = [empty((B, T), i4), empty((B,), i4), empty((B, T), f8), empty((B, T), f8)]
-            fio = MkhLadderRefineFreeIO(*[ptr(x) for x in more])
-            with _with_checker(self, free[0]):
-                _check(lib().mkh_ladder_refine_free(self.handle, free[0].handle, B, T, ptr(q), ptr(q_path), ptr(tracked),
-                                                    ptr(frame_targets), ptr(posture_target), ptr(com_target), float(dt),
-                                                    float(damping), max_iters, float(pos_threshold), float(ori_threshold), free[1],
-                                                    C.byref(io), C.byref(fio), flags, stream))
-            return LadderRefineFreeOut(*[out[n] for n in LADDER_REFINE_IO_FIELDS[2:]], *more)
-        with self._lock:
-            _check(lib().mkh_ladder_refine(self.handle, B, T, ptr(q), ptr(q_path), ptr(tracked), ptr(frame_targets),
-                                           ptr(posture_target), ptr(com_target), float(dt), float(damping), max_iters,
-                                           float(pos_threshold), float(ori_threshold), C.byref(io), flags, stream))
-        return LadderRefineOut(*[out[n] for n in LADDER_REFINE_IO_FIELDS[2:]])
+        q, q_path = kit.want(kit.prep(q), ("B", m.nq), "q"), kit.prep(q_path)
+        frame_targets = kit.want(kit.prep(frame_targets), (B, T, self.n_frame, 7), "frame_targets", required=True)
+        posture_target, com_target = kit.prep(posture_target), kit.prep(com_target)
+        flags = self._kernel_flags(wave_kernel, lane_kernel, quad_kernel, kit.devp) | \
+            self._held_flags(posture_target, com_target, (B, T))
+        weights = kit.want(kit.prep(weights), (m.nv,), "weights")
+        tracked = kit.ones((B, T)) if tracked is None else kit.flags01(tracked, (B, T), "tracked")
+        sizes = dict(B=B, T=T, q=m.nq)
+        known = dict(v=kit.f64_copy(v, (B, T, m.nv), "v"), status=kit.i32_copy(status, (B, T), "status"),
+                     iters=kit.i32_copy(iters, (B, T), "iters"), converged=kit.i32_copy(converged, (B, T), "converged"))
+        ptr = kit.ptr
+        io, out = LADDER_REFINE_OUT.make[_ALONE](kit.empty, ptr, sizes, weights=ptr(weights), max_step_sq=float(max_step_sq),
+                                                 **{n: ptr(x) for n, x in known.items()})
+        out.update(known)                           # (the caller's in-out arrays come back as they are: the copies made above)
+        loops = (B, T, kit.ptr(q), kit.ptr(q_path), kit.ptr(tracked), kit.ptr(frame_targets), kit.ptr(posture_target),
+                 kit.ptr(com_target), float(dt), float(damping), max_iters, float(pos_threshold), float(ori_threshold))
+        if free is None:
+            with self._lock:
+                _check(lib().mkh_ladder_refine(self.handle, *loops, C.byref(io), flags, kit.stream))
+            return LadderRefineOut(**out)
+        fio, more = LADDER_REFINE_FREE_OUT.make[_NONE](kit.empty, ptr, sizes)
+        with _with_checker(self, free[0]):
+            _check(lib().mkh_ladder_refine_free(self.handle, free[0].handle, *loops, free[1], C.byref(io), C.byref(fio), flags,
+                                                kit.stream))
+        return LadderRefineFreeOut(**out, **more)
 
     def _solve_trajectory(self, q, frame_targets, posture_target, com_target, dt, damping, n_steps, until, qvel_dt, tm,
                           warm_start, wave_kernel, lane_kernel, quad_kernel, keys=None, cands=None, free=None):
-        m = self.nmodel.model
+        m, kit = self.nmodel.model, _call_kit(q)
         B = int(q.shape[0])
         if n_steps < 1:
             raise ValueError("n_steps must be >= 1")
@@ -2235,30 +2173,24 @@ class NativeProblem:
                 raise MinkHipError(f"B*n_seeds={B * cands[0]} exceeds max_batch={self.max_batch} of this problem")
         if B > self.max_batch:
             raise MinkHipError(f"B={B} exceeds max_batch={self.max_batch} of this problem")
-        if self.n_dense_rows or self.n_dense_limit_rows or self.dense_limit_box:
-            raise ValueError("dense (plugin) rows are evaluated by the caller at q: no fused loop, no trajectory")
-        if until is not None and not self.n_frame:
-            raise ValueError("threshold mode needs at least one frame task to test the thresholds on")
-        flags = (FLAG_WAVE_KERNEL if wave_kernel else 0) | (FLAG_LANE_KERNEL if lane_kernel else 0) | \
-            (FLAG_QUAD_KERNEL if quad_kernel else 0) | (FLAG_WARM_START if warm_start else 0)
-        prep, empty, ptr, stream, devp = _call_kit(q)
-        flags |= devp
-        q, frame_targets, posture_target, com_target = prep(q), prep(frame_targets), prep(posture_target), prep(com_target)
-        if tuple(q.shape) != (B, m.nq):
-            raise ValueError(f"q must have shape (B, {m.nq}), got {tuple(q.shape)}")
+        self._refuse_dense("trajectory")
+        if until is not None:
+            self._need_frame("threshold mode")
+        flags = self._kernel_flags(wave_kernel, lane_kernel, quad_kernel, (FLAG_WARM_START if warm_start else 0) | kit.devp)
+        q = kit.want(kit.prep(q), ("B", m.nq), "q")
+        frame_targets, posture_target, com_target = kit.prep(frame_targets), kit.prep(posture_target), kit.prep(com_target)
         T = None
         if self.n_frame:
-            if frame_targets is None or frame_targets.ndim != 4:
-                raise ValueError(f"frame_targets must have shape (B, T, {self.n_frame}, 7)" + (" — (T, B, ...) time-major" if tm else ""))
+            shape = ("T", B, self.n_frame, 7) if tm else (B, "T", self.n_frame, 7)
+            kit.want(frame_targets, shape, "frame_targets", required=True)
             T = int(frame_targets.shape[0 if tm else 1])
-            want = (T, B, self.n_frame, 7) if tm else (B, T, self.n_frame, 7)
-            if T < 1 or tuple(frame_targets.shape) != want:
-                raise ValueError(f"frame_targets must have shape {want}, got {tuple(frame_targets.shape)}")
+            if T < 1:
+                raise ValueError(f"frame_targets must have shape {_shape_text(shape)} with T >= 1, got {tuple(frame_targets.shape)}")
 
         def held_or_timed(x, n, w, name, flag):
             """(per_waypoint, flags bit) of a posture / CoM target from its shape."""
             nonlocal T
-            held = _held_or_batched(x, B, n, w, name, flag, strict=False)      # (n, w) / (B, n, w) as in solve(): no T axis
+            held = _held_or_rows(x, (B,), n, w, name, flag, strict=False)      # (n, w) / (B, n, w) as in solve(): no T axis
             if held is not None:
                 return 0, held
             shp = tuple(x.shape)
@@ -2283,79 +2215,46 @@ class NativeProblem:
             flags |= f
         if T is None:
             raise ValueError("no target has a T axis: nothing says how many waypoints there are")
-        f8, i4 = np.float64, np.int32
         if keys is not None:                                   # (the axis read off the shapes is the keyframes'; T is the waypoints')
             K, T = T, len(keys[1])
             if K != len(keys[0]):
                 raise ValueError(f"the targets have {K} keyframes, keyframe_times has {len(keys[0])}")
         lead = (T, B) if tm else (B, T)
-        out_q, out_v, out_st = empty(lead + (m.nq,), f8), empty(lead + (m.nv,), f8), empty(lead, i4)
-        out_it = out_cv = out_qvel = None
-        if until is not None:
-            out_it, out_cv = empty(lead, i4), empty(lead, i4)
-        if qvel_dt is not None:
-            out_qvel = empty(lead + (m.nv,), f8)
-        io = MkhTrajectoryIO()
-        io.q_traj, io.v_traj, io.status, io.iters, io.converged, io.qvel = (ptr(x) for x in (out_q, out_v, out_st, out_it, out_cv, out_qvel))
-        io.waypoint_dt = float(qvel_dt) if qvel_dt is not None else 0.0
-        io.posture_per_waypoint, io.com_per_waypoint, io.time_major = p_time, c_time, int(tm)
-        thr = (float(until[0]), float(until[1])) if until is not None else (-1.0, -1.0)
+        sizes = dict(L=lead, B=B, T=T, q=m.nq, v=m.nv)
+        until_on, qvel_on = until is not None, qvel_dt is not None
+        empty, ptr = kit.empty, kit.ptr
+        numbers = dict(waypoint_dt=float(qvel_dt) if qvel_on else 0.0, time_major=int(tm))
+        thr = (float(until[0]), float(until[1])) if until_on else (-1.0, -1.0)
+        loops = (ptr(q), ptr(frame_targets), ptr(posture_target), ptr(com_target))
         if cands is not None:
             S, rng_seed, target_index0, seeds, weights, want_all = cands
-            seeds, weights = prep(seeds), prep(weights)
-            if seeds is not None and tuple(seeds.shape) != (B, S, m.nq):
-                raise ValueError(f"seeds must have shape ({B}, {S}, {m.nq}), got {tuple(seeds.shape)}")
-            if weights is not None and tuple(weights.shape) != (m.nv,):
-                raise ValueError(f"weights must have shape ({m.nv},), got {tuple(weights.shape)}")
-            R = B * S
-            per = {"seed_index": empty((B,), i4), "n_tracked": empty((B,), i4), "n_complete": empty((B,), i4),
-                   "path_length": empty((B,), f8)}
-            every = {}
-            if want_all:
-                every = {"q_all": empty((T, R, m.nq), f8), "v_all": empty((T, R, m.nv), f8), "status_all": empty((T, R), i4),
-                         "iters_all": empty((T, R), i4), "converged_all": empty((T, R), i4), "seeds_out": empty((R, m.nq), f8)}
-            cio = MkhTrajectoryMultistartIO()
-            for n in TRAJECTORY_IO_FIELDS:                             # the chosen outputs, waypoint_dt and the layout: as set above
-                setattr(cio, n, getattr(io, n))
-            cio.seeds, cio.weights = ptr(seeds), ptr(weights)
-            for n, x in {**per, **every}.items():
-                setattr(cio, n, ptr(x))
-            args = (B, T, S, ptr(q), ptr(frame_targets), ptr(posture_target), ptr(com_target), float(dt), float(damping), n_steps,
-                    thr[0], thr[1], rng_seed & (2 ** 64 - 1), target_index0)
-            more = None
+            seeds = kit.want(kit.prep(seeds), (B, S, m.nq), "seeds")
+            weights = kit.want(kit.prep(weights), (m.nv,), "weights")
+            sizes.update(R=B * S)
+            cio, out = TRAJECTORY_MULTISTART_OUT.make[_on(("until", "qvel", "all"), until_on, qvel_on, want_all)](
+                empty, ptr, sizes, seeds=ptr(seeds), weights=ptr(weights), posture_per_waypoint=p_time, com_per_waypoint=c_time, **numbers)
+            args = (B, T, S, *loops, float(dt), float(damping), n_steps, thr[0], thr[1], rng_seed & (2 ** 64 - 1), target_index0)
             if free is None:
-                _check(lib().mkh_solve_trajectory_multistart(self.handle, *args, C.byref(cio), flags, stream))
-            else:                                                      # (the caller holds both locks: _with_checker)
-                more = TrajectoryFreeOut(empty(lead, f8), empty(lead, f8), empty(lead, i4), empty((B,), i4),
-                                         empty((T, R), f8) if want_all else None, empty((T, R), f8) if want_all else None)
-                fio = MkhTrajectoryFreeIO(*[ptr(x) for x in more])
-                _check(lib().mkh_solve_trajectory_multistart_free(self.handle, free[0].handle, *args, free[1], C.byref(cio),
-                                                                  C.byref(fio), flags, stream))
-            res = TrajectoryMultistartOut(out_q, out_v, out_st, out_it, out_cv, per["seed_index"], per["n_tracked"],
-                                          per["n_complete"], per["path_length"], out_qvel,
-                                          *[every.get(n) for n in ("q_all", "v_all", "status_all", "iters_all", "converged_all",
-                                                                   "seeds_out")])
-            return res if free is None else (res, more)
+                _check(lib().mkh_solve_trajectory_multistart(self.handle, *args, C.byref(cio), flags, kit.stream))
+                return TrajectoryMultistartOut(**out)
+            fio, more = TRAJECTORY_FREE_OUT.make[_ALL if want_all else _NONE](empty, ptr, sizes)   # (the caller holds both locks)
+            _check(lib().mkh_solve_trajectory_multistart_free(self.handle, free[0].handle, *args, free[1], C.byref(cio),
+                                                              C.byref(fio), flags, kit.stream))
+            return TrajectoryMultistartOut(**out), TrajectoryFreeOut(**more)
         if keys is not None:
-            kt, wt, want = keys
-            out_ft = out_pt = out_ct = None
-            if want:
-                group = lambda batched: lead if batched else (T,)
-                if self.n_frame:
-                    out_ft = empty(lead + (self.n_frame, 7), f8)
-                if p_time:
-                    out_pt = empty(group(flags & FLAG_POSTURE_BATCHED) + (self.n_posture, m.nq), f8)
-                if c_time:
-                    out_ct = empty(group(flags & FLAG_COM_BATCHED) + (self.n_com, 3), f8)
-            kio = MkhKeyframeIO()
-            for n in TRAJECTORY_IO_FIELDS[:7] + ("time_major",):       # the outputs, waypoint_dt and the layout: as set above
-                setattr(kio, n, getattr(io, n))
-            kio.frame_targets_out, kio.posture_targets_out, kio.com_targets_out = ptr(out_ft), ptr(out_pt), ptr(out_ct)
-            kio.posture_keyframed, kio.com_keyframed = p_time, c_time
-            _check(lib().mkh_solve_keyframes(self.handle, B, K, T, ptr(q), ptr(frame_targets), ptr(posture_target), ptr(com_target),
-                                             kt.ctypes.data, wt.ctypes.data, float(dt), float(damping), n_steps, thr[0], thr[1],
-                                             C.byref(kio), flags, stream))
-            return KeyframesOut(TrajectoryOut(out_q, out_v, out_st, out_it, out_cv, out_qvel), out_ft, out_pt, out_ct)
-        _check(lib().mkh_solve_trajectory(self.handle, B, T, ptr(q), ptr(frame_targets), ptr(posture_target), ptr(com_target),
-                                          float(dt), float(damping), n_steps, thr[0], thr[1], C.byref(io), flags, stream))
-        return TrajectoryOut(out_q, out_v, out_st, out_it, out_cv, out_qvel)
+            kt, wt, want_targets = keys
+            group = lambda batched: lead if batched else (T,)
+            sizes.update(P=group(flags & FLAG_POSTURE_BATCHED), C=group(flags & FLAG_COM_BATCHED), nf=self.n_frame, np=self.n_posture,
+                         nc=self.n_com)
+            kio, out = KEYFRAME_OUT.make[_on(("until", "qvel", "frames", "postures", "coms"), until_on, qvel_on,
+                                             want_targets and self.n_frame, want_targets and p_time, want_targets and c_time)](
+                empty, ptr, sizes, posture_keyframed=p_time, com_keyframed=c_time, **numbers)
+            _check(lib().mkh_solve_keyframes(self.handle, B, K, T, *loops, kt.ctypes.data, wt.ctypes.data, float(dt), float(damping),
+                                             n_steps, thr[0], thr[1], C.byref(kio), flags, kit.stream))
+            paths = {n: out.pop(n) for n in KeyframesOut._fields[1:] if n in out}
+            return KeyframesOut(TrajectoryOut(**out), **paths)
+        io, out = TRAJECTORY_OUT.make[_on(("until", "qvel"), until_on, qvel_on)](empty, ptr, sizes, posture_per_waypoint=p_time,
+                                                                        com_per_waypoint=c_time, **numbers)
+        _check(lib().mkh_solve_trajectory(self.handle, B, T, *loops, float(dt), float(damping), n_steps, thr[0], thr[1], C.byref(io),
+                                          flags, kit.stream))
+        return TrajectoryOut(**out)

@@ -448,15 +448,90 @@ def _rows(x, held_ndim: int, lo: int, hi: int):
 
 
 def _join(cls, parts):
-    """The jobs' results, concatenated by instance into one `cls` (a NamedTuple whose absent fields are None in every part)."""
+    """The jobs' results, concatenated by instance into one `cls` (a NamedTuple whose absent fields are None in every part).
+    Where a job returns a pair (out, more), `cls` is the pair of their types and the pair of the joined results comes back."""
+    if type(parts[0]) is tuple:
+        return tuple(_join(c, [p[k] for p in parts]) for k, c in enumerate(cls))
     return cls(*[None if parts[0][k] is None else np.concatenate([p[k] for p in parts], axis=0) for k in range(len(cls._fields))])
 
 
-def _status_epilogue(status: np.ndarray, who: str, outside: str, failed: str) -> None:
+def _present(configuration: Configuration, cls, sources, flags=(), **computed):
+    """The caller's result `cls` from joined native results, BY FIELD NAME: every field of `cls` is `computed`'s where one is
+    passed, else that of the first of `sources` (one result, or a tuple of them) that has it; None stays None, the fields named
+    in `flags` become bool, and every array loses its leading axis for an unbatched configuration."""
+    sources = sources if type(sources) is tuple else (sources,)
+    un, fields, n_flags = configuration._unbatch, [], 0
+    for f in cls._fields:
+        n_flags += f in flags
+        if f in computed:
+            x = computed[f]
+        else:
+            x = None
+            for s in sources:
+                x = getattr(s, f, None)
+                if x is not None:
+                    break
+        if x is None:
+            if f not in cls._field_defaults:
+                raise TypeError(f"{cls.__name__}.{f} is required and no native result carries it")
+            fields.append(None)
+        else:
+            fields.append(un(x.astype(bool) if f in flags else x))
+    if n_flags != len(flags):
+        raise TypeError(f"{cls.__name__} has no field for one of the flags {flags}")
+    return cls._make(fields)
+
+
+def _loop_scalars(max_instances, n_seeds=None, loop: str = "max_iters", length=None, step_name: str = "waypoint_dt", step=None,
+                  thresholds=None, whose: str = ""):
+    """The scalar arguments of a fan-out call, judged on the host in one order: `n_seeds` (where the call has it), the loop
+    `length` — of the keyword `loop`, max_iters or n_steps —, `max_instances`, the uniform `step` of the keyword `step_name`
+    (None: not given) and, where `thresholds` = (pos, ori) is passed, both of them: `whose` loops run in threshold mode only.
+    Returns (S, length) as ints, S None without n_seeds."""
+    S = None if n_seeds is None else int(n_seeds)
+    if S is not None and S < 1:
+        raise ValueError("n_seeds must be >= 1")
+    length = int(length)
+    if length < 1:
+        raise ValueError(f"{loop} must be >= 1")
+    if int(max_instances) < 1:
+        raise ValueError("max_instances must be >= 1")
+    if step is not None and not float(step) > 0.0:
+        raise ValueError(f"{step_name} must be > 0")
+    if thresholds is not None:
+        pos, ori = thresholds
+        if pos is None or ori is None or not (float(pos) >= 0.0 and float(ori) >= 0.0):
+            raise ValueError(f"thresholds must be >= 0: {whose} run in threshold mode only")
+    return S, length
+
+
+def _host_flags(x, name: str, row: tuple, B: int):
+    """Optional flags (valid, tracked) on the host as a bool array (B,) + row: given as `row` for the whole batch, or one per
+    instance; a torch tensor, wherever it lives, is brought to the host."""
+    if x is None:
+        return None
+    x = np.asarray(x.detach().cpu().numpy() if nat._is_torch(x) else x)
+    if x.shape not in (row, (B,) + row):
+        raise ValueError(f"{name} must have shape {row} or {(B,) + row}, got {x.shape}")
+    return np.ascontiguousarray(np.broadcast_to(x != 0, (B,) + row))
+
+
+def _held_over(targets, B: int, L: int):
+    """Posture / CoM targets of a call whose rows are (instance, goal) or (instance, waypoint): a batched target that is held
+    over that second axis gets it — the native calls take (n, w) or (B, L, n, w)."""
+    return [x if x is None or x.ndim != 3 else np.ascontiguousarray(np.broadcast_to(x[:, None], (B, L) + x.shape[1:]))
+            for x in targets]
+
+
+def _status_epilogue(status: np.ndarray, who: str, outside: str, failed: str, safety_break=None) -> None:
     """What an outer-loop call reports from its (B,) or (B, T) status bits, as solve_ik_steps does: ONE warning for instances
     that were outside their configuration limits at some step (`outside` names them), SolverError for a QP failure (`failed`:
-    the message, with {n} failures of {of}, the {first} index and its {status})."""
+    the message, with {n} failures of {of}, the {first} index and its {status}).  `safety_break`: a function that names the
+    row at an index — the first row outside its limits then raises NotWithinConfigurationLimits instead of the warning."""
     out = (status & nat.ST_OUTSIDE_LIMITS) != 0
+    if safety_break is not None and out.any():
+        raise _outside_limits(f"{who}: {safety_break(*(int(x) for x in np.argwhere(out)[0]))} left its configuration limits at "
+                              "some fused step")
     if status.ndim == 2:
         out = out.any(axis=1)
     if out.any():
@@ -805,13 +880,7 @@ def solve_ik_multistart(configuration: Configuration, tasks: Sequence, dt: float
 
     When B·n_seeds exceeds `max_instances` the targets are walked in chunks; a multi-device configuration shards by target."""
     del solver
-    S, max_iters = int(n_seeds), int(max_iters)
-    if S < 1:
-        raise ValueError("n_seeds must be >= 1")
-    if max_iters < 1:
-        raise ValueError("max_iters must be >= 1")
-    if int(max_instances) < 1:
-        raise ValueError("max_instances must be >= 1")
+    S, max_iters = _loop_scalars(max_instances, n_seeds, length=max_iters)
     B, nq, nv = configuration.batch_size, configuration.nq, configuration.nv
     seeds = _optional_array(seeds, "seeds", (S, nq), B)
     reference = _optional_array(reference, "reference", (nq,), B)
@@ -829,17 +898,13 @@ def solve_ik_multistart(configuration: Configuration, tasks: Sequence, dt: float
                                        target_index0=lo, seeds=_rows(seeds, 2, lo, hi), reference=_rows(reference, 1, lo, hi),
                                        weights=weights, seed_table=seed_table, collision_check=collision_check, **kw)
 
-    res = _join(MultistartResult, _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job))
+    res = _join(nat.MultistartOut, _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job))
     _status_epilogue(res.status, "solve_ik_multistart", "chosen instance(s)",
                      "QP failed for the chosen seed of {n} of {of} targets (first: index {first}, status {status}); "
                      "none of their seeds converged")
     if update:
         configuration.update(res.q if configuration.batched else res.q[0])
-    un = configuration._unbatch
-    return MultistartResult(un(res.q), un(res.v), un(res.converged.astype(bool)), un(res.seed_index), un(res.n_converged),
-                            un(res.iters), un(res.status),
-                            *[None if x is None else un(x.astype(bool) if k == 1 else x)
-                              for k, x in enumerate((res.q_all, res.converged_all, res.iters_all, res.status_all, res.seeds))])
+    return _present(configuration, MultistartResult, res, flags=("converged", "converged_all"))
 
 
 class SolutionSet(NamedTuple):
@@ -919,14 +984,8 @@ def solve_ik_solutions(configuration: Configuration, tasks: Sequence, dt: float,
     The configuration is not changed: a set does not update it.  Failures are reported for slot 0 only, as
     solve_ik_multistart reports them for its choice."""
     del solver
-    S, max_iters = int(n_seeds), int(max_iters)
-    if S < 1:
-        raise ValueError("n_seeds must be >= 1")
+    S, max_iters = _loop_scalars(max_instances, n_seeds, length=max_iters)
     K, r = _set_args(n_solutions, min_distance, S)
-    if max_iters < 1:
-        raise ValueError("max_iters must be >= 1")
-    if int(max_instances) < 1:
-        raise ValueError("max_instances must be >= 1")
     B, nq, nv = configuration.batch_size, configuration.nq, configuration.nv
     seeds = _optional_array(seeds, "seeds", (S, nq), B)
     reference = _optional_array(reference, "reference", (nq,), B)
@@ -949,11 +1008,7 @@ def solve_ik_solutions(configuration: Configuration, tasks: Sequence, dt: float,
     _status_epilogue(res.status[:, 0], "solve_ik_solutions", "chosen instance(s)",
                      "QP failed for the chosen seed of {n} of {of} targets (first: index {first}, status {status}); "
                      "none of their seeds converged")
-    un = configuration._unbatch
-    return SolutionSet(un(res.q), un(res.v), un(res.seed_index >= 0), un(res.seed_index), un(res.distance), un(res.multiplicity),
-                       un(res.iters), un(res.status), un(res.n_distinct), un(res.n_converged), un(res.n_uncovered),
-                       *[None if x is None else un(x.astype(bool) if k == 1 else x)
-                         for k, x in enumerate((res.q_all, res.converged_all, res.iters_all, res.status_all, res.seeds))])
+    return _present(configuration, SolutionSet, res, flags=("converged_all",), valid=res.seed_index >= 0)
 
 
 def unwind_turns(configuration: Configuration, q_rows, reference=None) -> np.ndarray:
@@ -1000,11 +1055,7 @@ def distinct_solutions(configuration: Configuration, q_candidates, valid=None, n
     S = q_candidates.shape[-2]
     K, r = _set_args(n_solutions, min_distance, S)
     q_candidates = np.ascontiguousarray(np.broadcast_to(q_candidates, (B, S, nq)))
-    if valid is not None:
-        valid = np.asarray(valid.detach().cpu().numpy() if nat._is_torch(valid) else valid)
-        if valid.shape not in ((S,), (B, S)):
-            raise ValueError(f"valid must have shape {(S,)} or {(B, S)}, got {valid.shape}")
-        valid = np.ascontiguousarray(np.broadcast_to(valid != 0, (B, S)))
+    valid = _host_flags(valid, "valid", (S,), B)
     reference = _optional_array(reference, "reference", (nq,), B)
     weights = _optional_array(weights, "weights", (nv,))
     # (the selection reads the model's joint table through a problem handle: the smallest one, a posture task, serves)
@@ -1014,9 +1065,7 @@ def distinct_solutions(configuration: Configuration, q_candidates, valid=None, n
         if unwind_turns:                 # (the two device calls composed: the candidates moved to the turn nearest `ref` first)
             q_candidates = prob.unwind_turns(q_candidates, ref)
         out = prob.select_distinct(q_candidates, valid, ref, weights, n_solutions=K, min_distance=r)
-    un = configuration._unbatch
-    return DistinctSet(un(out.q), un(out.seed_index >= 0), un(out.seed_index), un(out.distance), un(out.multiplicity),
-                       un(out.n_distinct), un(out.n_valid), un(out.n_uncovered))
+    return _present(configuration, DistinctSet, out, valid=out.seed_index >= 0)
 
 
 class GoalSetResult(NamedTuple):
@@ -1078,12 +1127,7 @@ def _goal_arrays(goal_cost, goal_valid, B: int, G: int):
         if not (np.isfinite(goal_cost) & (goal_cost >= 0.0)).all():
             raise ValueError("goal_cost must be finite and >= 0")
         goal_cost = np.ascontiguousarray(np.broadcast_to(goal_cost, (B, G)))
-    if goal_valid is not None:
-        goal_valid = np.asarray(goal_valid.detach().cpu().numpy() if nat._is_torch(goal_valid) else goal_valid)
-        if goal_valid.shape not in ((G,), (B, G)):
-            raise ValueError(f"goal_valid must have shape {(G,)} or {(B, G)}, got {goal_valid.shape}")
-        goal_valid = np.ascontiguousarray(np.broadcast_to(goal_valid != 0, (B, G)))
-    return goal_cost, goal_valid
+    return goal_cost, _host_flags(goal_valid, "goal_valid", (G,), B)
 
 
 def solve_ik_goalset(configuration: Configuration, tasks: Sequence, dt: float, goals, n_seeds: int, max_iters: int,
@@ -1116,15 +1160,8 @@ def solve_ik_goalset(configuration: Configuration, tasks: Sequence, dt: float, g
     With `update` the configuration is left at the chosen q.  The instances are walked in chunks of as many as keep
     chunk·G·n_seeds within `max_instances`; a multi-device configuration shards by instance; the result depends on neither."""
     del solver
-    S, max_iters = int(n_seeds), int(max_iters)
-    if S < 1:
-        raise ValueError("n_seeds must be >= 1")
-    if max_iters < 1:
-        raise ValueError("max_iters must be >= 1")
-    if int(max_instances) < 1:
-        raise ValueError("max_instances must be >= 1")
-    if pos_threshold is None or ori_threshold is None or not (float(pos_threshold) >= 0.0 and float(ori_threshold) >= 0.0):
-        raise ValueError("thresholds must be >= 0: a goal set's loops run in threshold mode only")
+    S, max_iters = _loop_scalars(max_instances, n_seeds, length=max_iters, thresholds=(pos_threshold, ori_threshold),
+                                 whose="a goal set's loops")
     _refuse_plugin_rows({"dense": [t for t in tasks if t._is_dense()], "dense_limits": [x for x in (limits or ()) if x._is_dense()]},
                         "solve_ik_goalset")
     B, nq, nv = configuration.batch_size, configuration.nq, configuration.nv
@@ -1145,9 +1182,7 @@ def solve_ik_goalset(configuration: Configuration, tasks: Sequence, dt: float, g
     _check_collision_check(collision_check, configuration)
     handles, layout, chunk, n_dev = _compile_outer(configuration, tasks, limits, dt, "solve_ik_goalset", G * S, max_instances)
     ft, pt, ct = _stacked_targets(configuration, layout, seqs, G)
-    # a batched target that is held over the goals gets its G axis: the call takes (n, w) or (B, G, n, w)
-    pt, ct = [x if x is None or x.ndim != 3 else np.ascontiguousarray(np.broadcast_to(x[:, None], (B, G) + x.shape[1:]))
-              for x in (pt, ct)]
+    pt, ct = _held_over((pt, ct), B, G)
     q = configuration.q_batch
     kw = dict(n_seeds=S, max_iters=max_iters, pos_threshold=float(pos_threshold), ori_threshold=float(ori_threshold),
               rng_seed=int(rng_seed), weights=weights, return_all=bool(return_all))
@@ -1159,23 +1194,13 @@ def solve_ik_goalset(configuration: Configuration, tasks: Sequence, dt: float, g
                                     seed_table=seed_table, collision_check=collision_check, **kw)
 
     res = _join(nat.GoalSetOut, _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job))
-    if safety_break and ((res.status & nat.ST_OUTSIDE_LIMITS) != 0).any():
-        b = int(np.argwhere((res.status & nat.ST_OUTSIDE_LIMITS) != 0)[0, 0])
-        raise _outside_limits(
-            f"solve_ik_goalset: the chosen loop of instance {b} (goal {int(res.goal_index[b])}, seed {int(res.seed_index[b])}) left "
-            "its configuration limits at some fused step")
+    chosen = lambda b: f"the chosen loop of instance {b} (goal {int(res.goal_index[b])}, seed {int(res.seed_index[b])})"
     _status_epilogue(res.status, "solve_ik_goalset", "chosen instance(s)",
                      "QP failed for the chosen loop of {n} of {of} targets (first: index {first}, status {status}); "
-                     "none of their goals was reached")
+                     "none of their goals was reached", safety_break=chosen if safety_break else None)
     if update:
         configuration.update(res.q if configuration.batched else res.q[0])
-    un = configuration._unbatch
-    opt = lambda x, as_bool=False: None if x is None else un(x.astype(bool) if as_bool else x)
-    return GoalSetResult(un(res.q), un(res.v), un(res.converged.astype(bool)), un(res.goal_index), un(res.seed_index),
-                         un(res.n_reached), un(res.score), un(res.iters), un(res.status), un(res.q_goal), un(res.v_goal),
-                         un(res.reached.astype(bool)), un(res.seed_index_goal), un(res.n_converged_goal), un(res.distance_goal),
-                         un(res.iters_goal), un(res.status_goal), opt(res.q_all), opt(res.converged_all, True),
-                         opt(res.iters_all), opt(res.status_all), opt(res.seeds))
+    return _present(configuration, GoalSetResult, res, flags=("converged", "reached", "converged_all"))
 
 
 def best_goal(configuration: Configuration, q_candidates, valid=None, goal_cost=None, goal_valid=None, reference=None,
@@ -1196,11 +1221,7 @@ def best_goal(configuration: Configuration, q_candidates, valid=None, goal_cost=
     G, S = q_candidates.shape[-3], q_candidates.shape[-2]
     nat.check_goalset_shape(B, G, S)
     q_candidates = np.ascontiguousarray(np.broadcast_to(q_candidates, (B, G, S, nq)))
-    if valid is not None:
-        valid = np.asarray(valid.detach().cpu().numpy() if nat._is_torch(valid) else valid)
-        if valid.shape not in ((G, S), (B, G, S)):
-            raise ValueError(f"valid must have shape {(G, S)} or {(B, G, S)}, got {valid.shape}")
-        valid = np.ascontiguousarray(np.broadcast_to(valid != 0, (B, G, S)))
+    valid = _host_flags(valid, "valid", (G, S), B)
     goal_cost, goal_valid = _goal_arrays(goal_cost, goal_valid, B, G)
     reference = _optional_array(reference, "reference", (nq,), B)
     weights = _optional_array(weights, "weights", (nv,))
@@ -1209,10 +1230,7 @@ def best_goal(configuration: Configuration, q_candidates, valid=None, goal_cost=
     with _pin(configuration, layout):
         out = prob.select_goalset(q_candidates, valid, configuration.q_batch if reference is None else reference, weights,
                                   goal_cost=goal_cost, goal_valid=goal_valid)
-    un = configuration._unbatch
-    return GoalChoice(un(out.q), un(out.converged.astype(bool)), un(out.goal_index), un(out.seed_index), un(out.n_reached),
-                      un(out.score), un(out.q_goal), un(out.reached.astype(bool)), un(out.seed_index_goal), un(out.n_valid_goal),
-                      un(out.distance_goal))
+    return _present(configuration, GoalChoice, out, flags=("converged", "reached"))
 
 
 class TrajectoryResult(NamedTuple):
@@ -1312,13 +1330,7 @@ def solve_ik_trajectory(configuration: Configuration, tasks: Sequence, dt: float
     at q[:, -1].  When B exceeds `max_instances` the trajectories are walked in chunks of instances; a multi-device
     configuration shards by trajectory."""
     del solver
-    n_steps = int(n_steps)
-    if n_steps < 1:
-        raise ValueError("n_steps must be >= 1")
-    if int(max_instances) < 1:
-        raise ValueError("max_instances must be >= 1")
-    if waypoint_dt is not None and not float(waypoint_dt) > 0.0:
-        raise ValueError("waypoint_dt must be > 0")
+    _, n_steps = _loop_scalars(max_instances, loop="n_steps", length=n_steps, step=waypoint_dt)
     kt = wt = None
     if keyframe_times is None:
         if waypoint_times is not None or return_targets:
@@ -1358,9 +1370,7 @@ def solve_ik_trajectory(configuration: Configuration, tasks: Sequence, dt: float
     if update:
         configuration.update(res.q[:, -1] if configuration.batched else res.q[0, -1])
     un = configuration._unbatch
-    res = TrajectoryResult(un(res.q), un(res.v), un(res.status), None if res.iters is None else un(res.iters),
-                           None if res.converged is None else un(res.converged.astype(bool)),
-                           None if res.qvel is None else un(res.qvel))
+    res = _present(configuration, TrajectoryResult, res, flags=("converged",))
     if paths is None:
         return res
     # the interpolated path of every task of `targets`: its column of its group's (B, T, n, w) array
@@ -1396,36 +1406,16 @@ class TrajectoryMultistartResult(NamedTuple):
     seeds: Optional[np.ndarray] = None
 
 
-class FreeTrajectoryMultistartResult(NamedTuple):
+_FREE_PATH_FIELDS = ("node_margin", "edge_margin", "edge_collision", "n_edge_collisions", "tracked", "node_margin_all",
+                     "edge_margin_all")
+FreeTrajectoryMultistartResult = nat._extended(
+    "FreeTrajectoryMultistartResult", TrajectoryMultistartResult, _FREE_PATH_FIELDS,
     """Result of solve_ik_trajectory_multistart(collision_check=...): TrajectoryMultistartResult's fields in its order — `n_tracked`
     and `n_complete` count the waypoints that are tracked, free of collision and entered by a free motion; `status` and
     `status_all` carry ST_IN_COLLISION where a row collides —, then of the chosen candidate `node_margin` and `edge_margin` (B, T)
     (entry 0 of edge_margin +inf, NaN where the motion was not swept), `edge_collision` (B, T) bool, `n_edge_collisions` (B,)
     and `tracked` (B, T) bool, the waypoints that counted: what refine_path(tracked=...) takes.  With return_all every
-    candidate's `node_margin_all` and `edge_margin_all` (B, S, T); None otherwise."""
-    q: np.ndarray
-    v: np.ndarray
-    status: np.ndarray
-    iters: np.ndarray
-    converged: np.ndarray
-    seed_index: np.ndarray
-    n_tracked: np.ndarray
-    n_complete: np.ndarray
-    path_length: np.ndarray
-    qvel: Optional[np.ndarray] = None
-    q_all: Optional[np.ndarray] = None
-    v_all: Optional[np.ndarray] = None
-    status_all: Optional[np.ndarray] = None
-    iters_all: Optional[np.ndarray] = None
-    converged_all: Optional[np.ndarray] = None
-    seeds: Optional[np.ndarray] = None
-    node_margin: Optional[np.ndarray] = None
-    edge_margin: Optional[np.ndarray] = None
-    edge_collision: Optional[np.ndarray] = None
-    n_edge_collisions: Optional[np.ndarray] = None
-    tracked: Optional[np.ndarray] = None
-    node_margin_all: Optional[np.ndarray] = None
-    edge_margin_all: Optional[np.ndarray] = None
+    candidate's `node_margin_all` and `edge_margin_all` (B, S, T); None otherwise.""", module=__name__)
 
 
 def _counted(eligible: np.ndarray, edge_margin: np.ndarray) -> np.ndarray:
@@ -1473,17 +1463,8 @@ def solve_ik_trajectory_multistart(configuration: Configuration, tasks: Sequence
     above, unchanged."""
     del solver
     _check_collision_check(collision_check, configuration, edge_samples)
-    S, n_steps = int(n_seeds), int(n_steps)
-    if S < 1:
-        raise ValueError("n_seeds must be >= 1")
-    if n_steps < 1:
-        raise ValueError("n_steps must be >= 1")
-    if int(max_instances) < 1:
-        raise ValueError("max_instances must be >= 1")
-    if waypoint_dt is not None and not float(waypoint_dt) > 0.0:
-        raise ValueError("waypoint_dt must be > 0")
-    if pos_threshold is None or ori_threshold is None or not (float(pos_threshold) >= 0.0 and float(ori_threshold) >= 0.0):
-        raise ValueError("thresholds must be >= 0: multi-start trajectories run in threshold mode only")
+    S, n_steps = _loop_scalars(max_instances, n_seeds, loop="n_steps", length=n_steps, step=waypoint_dt,
+                               thresholds=(pos_threshold, ori_threshold), whose="multi-start trajectories")
     B, nq, nv = configuration.batch_size, configuration.nq, configuration.nv
     seqs, T = _trajectory_targets(configuration, tasks, targets)
     seeds = _optional_array(seeds, "seeds", (S, nq), B)
@@ -1517,29 +1498,25 @@ def solve_ik_trajectory_multistart(configuration: Configuration, tasks: Sequence
                                seeds=out.seeds.reshape(n, S, nq))
         if more is None:
             return out
-        every = (by_inst(more.node_margin_all), by_inst(more.edge_margin_all)) if return_all else (None, None)
-        return FreeTrajectoryMultistartResult(*out, more.node_margin, more.edge_margin, more.edge_collision, more.n_edge_collisions,
-                                              None, *every)
+        if return_all:
+            more = more._replace(node_margin_all=by_inst(more.node_margin_all), edge_margin_all=by_inst(more.edge_margin_all))
+        return out, more
 
-    res = _join(TrajectoryMultistartResult if collision_check is None else FreeTrajectoryMultistartResult,
-                _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job))
+    parts = _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job)
+    flags = ("converged", "converged_all")
+    if collision_check is None:
+        res = _join(nat.TrajectoryMultistartOut, parts)
+    else:
+        res, more = _join((nat.TrajectoryMultistartOut, nat.TrajectoryFreeOut), parts)
     _status_epilogue(res.status, "solve_ik_trajectory_multistart", "chosen trajectorie(s)",
                      "QP failed at {n} of {of} waypoints of the chosen candidates (first: (instance, waypoint) = {first}, "
                      "status {status})")
     if update:
         configuration.update(res.q[:, -1] if configuration.batched else res.q[0, -1])
-    un = configuration._unbatch
-    opt = lambda x, as_bool=False: None if x is None else un(x.astype(bool) if as_bool else x)
-    out = TrajectoryMultistartResult(un(res.q), un(res.v), un(res.status), un(res.iters), un(res.converged.astype(bool)),
-                                     un(res.seed_index), un(res.n_tracked), un(res.n_complete), un(res.path_length),
-                                     opt(res.qvel), opt(res.q_all), opt(res.v_all), opt(res.status_all), opt(res.iters_all),
-                                     opt(res.converged_all, True), opt(res.seeds))
     if collision_check is None:
-        return out
-    counted = _counted((res.converged != 0) & ((res.status & ~nat.ST_OUTSIDE_LIMITS) == 0), res.edge_margin)
-    return FreeTrajectoryMultistartResult(*out, un(res.node_margin), un(res.edge_margin), un(res.edge_collision.astype(bool)),
-                                          un(res.n_edge_collisions), un(counted), opt(res.node_margin_all),
-                                          opt(res.edge_margin_all))
+        return _present(configuration, TrajectoryMultistartResult, res, flags)
+    counted = _counted((res.converged != 0) & ((res.status & ~nat.ST_OUTSIDE_LIMITS) == 0), more.edge_margin)
+    return _present(configuration, FreeTrajectoryMultistartResult, (res, more), flags + ("edge_collision",), tracked=counted)
 
 
 class CandidatePath(NamedTuple):
@@ -1552,22 +1529,11 @@ class CandidatePath(NamedTuple):
     path_length: np.ndarray
 
 
-class FreeCandidatePath(NamedTuple):
+FreeCandidatePath = nat._extended(
+    "FreeCandidatePath", CandidatePath, _FREE_PATH_FIELDS,
     """Result of candidate_path(collision_check=...): CandidatePath's fields, then of the chosen candidate `node_margin` and
     `edge_margin` (B, T), `edge_collision` (B, T) bool, `n_edge_collisions` (B,), `tracked` (B, T) bool — the waypoints that
-    counted — and every candidate's `node_margin_all` and `edge_margin_all` (B, S, T)."""
-    seed_index: np.ndarray
-    q: np.ndarray
-    n_tracked: np.ndarray
-    n_complete: np.ndarray
-    path_length: np.ndarray
-    node_margin: np.ndarray
-    edge_margin: np.ndarray
-    edge_collision: np.ndarray
-    n_edge_collisions: np.ndarray
-    tracked: np.ndarray
-    node_margin_all: np.ndarray
-    edge_margin_all: np.ndarray
+    counted — and every candidate's `node_margin_all` and `edge_margin_all` (B, S, T).""", optional=False, module=__name__)
 
 
 def candidate_path(configuration: Configuration, q_paths, tracked=None, weights=None,
@@ -1592,12 +1558,8 @@ def candidate_path(configuration: Configuration, q_paths, tracked=None, weights=
         raise ValueError(f"q_paths needs at least one candidate and one waypoint, got S = {S}, T = {T}")
     # (B, S, T, ·) → the loops' time-major (T, B·S, ·)
     q_tm = np.ascontiguousarray(np.moveaxis(np.broadcast_to(q_paths, (B, S, T, nq)), 2, 0)).reshape(T, B * S, nq)
-    trk_tm = None
-    if tracked is not None:
-        tracked = np.asarray(tracked.detach().cpu().numpy() if nat._is_torch(tracked) else tracked)
-        if tracked.shape not in ((S, T), (B, S, T)):
-            raise ValueError(f"tracked must have shape {(S, T)} or {(B, S, T)}, got {tracked.shape}")
-        trk_tm = np.ascontiguousarray(np.moveaxis(np.broadcast_to(tracked != 0, (B, S, T)), 2, 0)).reshape(T, B * S)
+    tracked = _host_flags(tracked, "tracked", (S, T), B)
+    trk_tm = None if tracked is None else np.ascontiguousarray(np.moveaxis(tracked, 2, 0)).reshape(T, B * S)
     weights = _optional_array(weights, "weights", (nv,))
     if weights is not None and not (weights >= 0.0).all():
         raise ValueError("weights must be >= 0 (no NaN): the path length is a sum of non-negative terms")
@@ -1606,17 +1568,14 @@ def candidate_path(configuration: Configuration, q_paths, tracked=None, weights=
     with _pin(configuration, layout):
         out, more = prob.select_trajectory_candidates(configuration.q_batch, q_tm, trk_tm, weights, collision_check,
                                                       int(edge_samples), collision_check is not None)
-    un = configuration._unbatch
-    path = CandidatePath(un(out.seed_index), un(out.q), un(out.n_tracked), un(out.n_complete), un(out.path_length))
     if collision_check is None:
-        return path
+        return _present(configuration, CandidatePath, out)
     by_inst = lambda x: np.ascontiguousarray(np.moveaxis(x.reshape(T, B, S), 0, 2))
-    given = np.ones((B, S, T), dtype=bool) if trk_tm is None else by_inst(trk_tm != 0)
+    given = np.ones((B, S, T), dtype=bool) if tracked is None else tracked
     chosen = given[np.arange(B), out.seed_index]                         # (B, T): the caller's flags of the chosen candidate
     counted = _counted(chosen & (more.node_margin >= 0.0), more.edge_margin)
-    return FreeCandidatePath(*path, un(more.node_margin), un(more.edge_margin), un(more.edge_collision.astype(bool)),
-                             un(more.n_edge_collisions), un(counted), un(by_inst(more.node_margin_all)),
-                             un(by_inst(more.edge_margin_all)))
+    return _present(configuration, FreeCandidatePath, (out, more), flags=("edge_collision",), tracked=counted,
+                    node_margin_all=by_inst(more.node_margin_all), edge_margin_all=by_inst(more.edge_margin_all))
 
 
 class LadderResult(NamedTuple):
@@ -1645,94 +1604,26 @@ class LadderResult(NamedTuple):
     seeds: Optional[np.ndarray] = None
 
 
-class RefinedLadderResult(NamedTuple):
+_REFINED_FIELDS = ("repaired", "refined")
+_CHECKED_FIELDS = ("edge_collision", "n_edge_collisions", "edge_margin")
+RefinedLadderResult = nat._extended(
+    "RefinedLadderResult", LadderResult, _REFINED_FIELDS,
     """Result of solve_ik_trajectory_ladder(refine=True): LadderResult's fields, in its order, for the path the refinement pass
     returned, and behind them `repaired` (B, T) — 0 kept, 1 / 2 replaced by the forward / backward sweep — and `refined` (B,):
-    where the path differs from the search's.  `node_index` names the replaced node at a repaired waypoint."""
-    q: np.ndarray
-    v: np.ndarray
-    status: np.ndarray
-    iters: np.ndarray
-    converged: np.ndarray
-    node_index: np.ndarray
-    n_tracked: np.ndarray
-    n_breaks: np.ndarray
-    path_length: np.ndarray
-    edge_break: np.ndarray
-    qvel: Optional[np.ndarray] = None
-    q_all: Optional[np.ndarray] = None
-    v_all: Optional[np.ndarray] = None
-    status_all: Optional[np.ndarray] = None
-    iters_all: Optional[np.ndarray] = None
-    converged_all: Optional[np.ndarray] = None
-    seeds: Optional[np.ndarray] = None
-    repaired: Optional[np.ndarray] = None
-    refined: Optional[np.ndarray] = None
-
-
-class LadderNodesResult(NamedTuple):
+    where the path differs from the search's.  `node_index` names the replaced node at a repaired waypoint.""", module=__name__)
+LadderNodesResult = nat._extended(
+    "LadderNodesResult", LadderResult, nat.LADDER_NODES_IO_FIELDS,
     """Result of solve_ik_trajectory_ladder(n_nodes=K): LadderResult's fields, in its order, for the ladder searched on the K
     deduplicated nodes of every rung — `node_index` is a slot in 0 … K − 1, and with return_all the *_all fields are the NODES'
     rows, (B, T, K, ·), `seeds` the (B, T, S, nq) starts — and behind them what the selection says of every rung:
     `node_seed_index` (B, T, K) the candidate each node is (−1: an empty slot, which repeats candidate 0 and is not tracked),
     `node_multiplicity` the candidates it stands for, `node_distance` its distance from q; `n_distinct`, `n_converged`,
     `n_uncovered` (B, T) nodes filled, candidates tracked, tracked candidates that no node covers; `seed_index` (B, T) the
-    chosen node's candidate index."""
-    q: np.ndarray
-    v: np.ndarray
-    status: np.ndarray
-    iters: np.ndarray
-    converged: np.ndarray
-    node_index: np.ndarray
-    n_tracked: np.ndarray
-    n_breaks: np.ndarray
-    path_length: np.ndarray
-    edge_break: np.ndarray
-    qvel: Optional[np.ndarray] = None
-    q_all: Optional[np.ndarray] = None
-    v_all: Optional[np.ndarray] = None
-    status_all: Optional[np.ndarray] = None
-    iters_all: Optional[np.ndarray] = None
-    converged_all: Optional[np.ndarray] = None
-    seeds: Optional[np.ndarray] = None
-    node_seed_index: Optional[np.ndarray] = None
-    node_multiplicity: Optional[np.ndarray] = None
-    node_distance: Optional[np.ndarray] = None
-    n_distinct: Optional[np.ndarray] = None
-    n_converged: Optional[np.ndarray] = None
-    n_uncovered: Optional[np.ndarray] = None
-    seed_index: Optional[np.ndarray] = None
-
-
-class RefinedLadderNodesResult(NamedTuple):
+    chosen node's candidate index.""", module=__name__)
+RefinedLadderNodesResult = nat._extended(
+    "RefinedLadderNodesResult", RefinedLadderResult, nat.LADDER_NODES_IO_FIELDS,
     """Result of solve_ik_trajectory_ladder(n_nodes=K, refine=True): RefinedLadderResult's fields, in its order, and behind them
-    LadderNodesResult's own."""
-    q: np.ndarray
-    v: np.ndarray
-    status: np.ndarray
-    iters: np.ndarray
-    converged: np.ndarray
-    node_index: np.ndarray
-    n_tracked: np.ndarray
-    n_breaks: np.ndarray
-    path_length: np.ndarray
-    edge_break: np.ndarray
-    qvel: Optional[np.ndarray] = None
-    q_all: Optional[np.ndarray] = None
-    v_all: Optional[np.ndarray] = None
-    status_all: Optional[np.ndarray] = None
-    iters_all: Optional[np.ndarray] = None
-    converged_all: Optional[np.ndarray] = None
-    seeds: Optional[np.ndarray] = None
-    repaired: Optional[np.ndarray] = None
-    refined: Optional[np.ndarray] = None
-    node_seed_index: Optional[np.ndarray] = None
-    node_multiplicity: Optional[np.ndarray] = None
-    node_distance: Optional[np.ndarray] = None
-    n_distinct: Optional[np.ndarray] = None
-    n_converged: Optional[np.ndarray] = None
-    n_uncovered: Optional[np.ndarray] = None
-    seed_index: Optional[np.ndarray] = None
+    LadderNodesResult's own.""", module=__name__)
 
 
 class LadderPath(NamedTuple):
@@ -1746,142 +1637,31 @@ class LadderPath(NamedTuple):
     edge_break: np.ndarray
 
 
-class FreeLadderPath(NamedTuple):
+FreeLadderPath = nat._extended(
+    "FreeLadderPath", LadderPath, nat.LADDER_FREE_IO_FIELDS,
     """Result of ladder_path(collision_check=...): LadderPath's fields, in its order, then `edge_collision` (B, T) — the motion
     into waypoint t passes through collision, entry 0 never —, `n_edge_collisions` (B,), `edge_margin` (B, T) — the swept margin
     of the chosen edges, +inf at waypoint 0, NaN where the edge was not swept —, `node_margin` (B, T, S) and `edge_margin_all`
     (B, T, S, S), entry [b, t, s', s].  `n_tracked` counts the waypoints that are tracked, free of collision and entered by a
-    free motion."""
-    node_index: np.ndarray
-    q: np.ndarray
-    n_tracked: np.ndarray
-    n_breaks: np.ndarray
-    path_length: np.ndarray
-    edge_break: np.ndarray
-    edge_collision: np.ndarray
-    n_edge_collisions: np.ndarray
-    edge_margin: np.ndarray
-    node_margin: np.ndarray
-    edge_margin_all: np.ndarray
-
-
-class FreeLadderResult(NamedTuple):
+    free motion.""", optional=False, module=__name__)
+FreeLadderResult = nat._extended(
+    "FreeLadderResult", LadderResult, _CHECKED_FIELDS,
     """Result of solve_ik_trajectory_ladder(collision_check=...): LadderResult's fields, in its order, and behind them
-    `edge_collision` (B, T), `n_edge_collisions` (B,) and `edge_margin` (B, T) of the chosen path, as in FreeLadderPath."""
-    q: np.ndarray
-    v: np.ndarray
-    status: np.ndarray
-    iters: np.ndarray
-    converged: np.ndarray
-    node_index: np.ndarray
-    n_tracked: np.ndarray
-    n_breaks: np.ndarray
-    path_length: np.ndarray
-    edge_break: np.ndarray
-    qvel: Optional[np.ndarray] = None
-    q_all: Optional[np.ndarray] = None
-    v_all: Optional[np.ndarray] = None
-    status_all: Optional[np.ndarray] = None
-    iters_all: Optional[np.ndarray] = None
-    converged_all: Optional[np.ndarray] = None
-    seeds: Optional[np.ndarray] = None
-    edge_collision: Optional[np.ndarray] = None
-    n_edge_collisions: Optional[np.ndarray] = None
-    edge_margin: Optional[np.ndarray] = None
-
-
-class FreeLadderNodesResult(NamedTuple):
+    `edge_collision` (B, T), `n_edge_collisions` (B,) and `edge_margin` (B, T) of the chosen path, as in FreeLadderPath.""",
+    module=__name__)
+FreeLadderNodesResult = nat._extended(
+    "FreeLadderNodesResult", LadderNodesResult, _CHECKED_FIELDS,
     """Result of solve_ik_trajectory_ladder(collision_check=..., n_nodes=K): LadderNodesResult's fields, in its order, and behind
-    them `edge_collision`, `n_edge_collisions`, `edge_margin`, as in FreeLadderPath."""
-    q: np.ndarray
-    v: np.ndarray
-    status: np.ndarray
-    iters: np.ndarray
-    converged: np.ndarray
-    node_index: np.ndarray
-    n_tracked: np.ndarray
-    n_breaks: np.ndarray
-    path_length: np.ndarray
-    edge_break: np.ndarray
-    qvel: Optional[np.ndarray] = None
-    q_all: Optional[np.ndarray] = None
-    v_all: Optional[np.ndarray] = None
-    status_all: Optional[np.ndarray] = None
-    iters_all: Optional[np.ndarray] = None
-    converged_all: Optional[np.ndarray] = None
-    seeds: Optional[np.ndarray] = None
-    node_seed_index: Optional[np.ndarray] = None
-    node_multiplicity: Optional[np.ndarray] = None
-    node_distance: Optional[np.ndarray] = None
-    n_distinct: Optional[np.ndarray] = None
-    n_converged: Optional[np.ndarray] = None
-    n_uncovered: Optional[np.ndarray] = None
-    seed_index: Optional[np.ndarray] = None
-    edge_collision: Optional[np.ndarray] = None
-    n_edge_collisions: Optional[np.ndarray] = None
-    edge_margin: Optional[np.ndarray] = None
-
-
-class FreeRefinedLadderResult(NamedTuple):
+    them `edge_collision`, `n_edge_collisions`, `edge_margin`, as in FreeLadderPath.""", module=__name__)
+FreeRefinedLadderResult = nat._extended(
+    "FreeRefinedLadderResult", FreeLadderResult, _REFINED_FIELDS,
     """Result of solve_ik_trajectory_ladder(collision_check=..., refine="free"): FreeLadderResult's fields, in its order — all of
     the RETURNED path, `edge_collision`, `n_edge_collisions` and `edge_margin` included —, and behind them `repaired` (B, T) and
-    `refined` (B,) of the checked refinement pass."""
-    q: np.ndarray
-    v: np.ndarray
-    status: np.ndarray
-    iters: np.ndarray
-    converged: np.ndarray
-    node_index: np.ndarray
-    n_tracked: np.ndarray
-    n_breaks: np.ndarray
-    path_length: np.ndarray
-    edge_break: np.ndarray
-    qvel: Optional[np.ndarray] = None
-    q_all: Optional[np.ndarray] = None
-    v_all: Optional[np.ndarray] = None
-    status_all: Optional[np.ndarray] = None
-    iters_all: Optional[np.ndarray] = None
-    converged_all: Optional[np.ndarray] = None
-    seeds: Optional[np.ndarray] = None
-    edge_collision: Optional[np.ndarray] = None
-    n_edge_collisions: Optional[np.ndarray] = None
-    edge_margin: Optional[np.ndarray] = None
-    repaired: Optional[np.ndarray] = None
-    refined: Optional[np.ndarray] = None
-
-
-class FreeRefinedLadderNodesResult(NamedTuple):
+    `refined` (B,) of the checked refinement pass.""", module=__name__)
+FreeRefinedLadderNodesResult = nat._extended(
+    "FreeRefinedLadderNodesResult", FreeLadderNodesResult, _REFINED_FIELDS,
     """Result of solve_ik_trajectory_ladder(collision_check=..., n_nodes=K, refine="free"): FreeLadderNodesResult's fields, in its
-    order, and behind them `repaired` and `refined`, as in FreeRefinedLadderResult."""
-    q: np.ndarray
-    v: np.ndarray
-    status: np.ndarray
-    iters: np.ndarray
-    converged: np.ndarray
-    node_index: np.ndarray
-    n_tracked: np.ndarray
-    n_breaks: np.ndarray
-    path_length: np.ndarray
-    edge_break: np.ndarray
-    qvel: Optional[np.ndarray] = None
-    q_all: Optional[np.ndarray] = None
-    v_all: Optional[np.ndarray] = None
-    status_all: Optional[np.ndarray] = None
-    iters_all: Optional[np.ndarray] = None
-    converged_all: Optional[np.ndarray] = None
-    seeds: Optional[np.ndarray] = None
-    node_seed_index: Optional[np.ndarray] = None
-    node_multiplicity: Optional[np.ndarray] = None
-    node_distance: Optional[np.ndarray] = None
-    n_distinct: Optional[np.ndarray] = None
-    n_converged: Optional[np.ndarray] = None
-    n_uncovered: Optional[np.ndarray] = None
-    seed_index: Optional[np.ndarray] = None
-    edge_collision: Optional[np.ndarray] = None
-    n_edge_collisions: Optional[np.ndarray] = None
-    edge_margin: Optional[np.ndarray] = None
-    repaired: Optional[np.ndarray] = None
-    refined: Optional[np.ndarray] = None
+    order, and behind them `repaired` and `refined`, as in FreeRefinedLadderResult.""", module=__name__)
 
 
 def _max_step_sq(max_step) -> float:
@@ -1977,20 +1757,14 @@ def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt
         if collision_check is None:
             raise ValueError('refine="free" is the refinement pass with a checker: pass collision_check')
     _check_collision_check(collision_check, configuration, edge_samples, bool(refine) and not free_refine)
-    S, max_iters = int(n_seeds), int(max_iters)
+    S = int(n_seeds)                                    # (what S may be is the ladder's to say: nat.check_ladder_shape, below)
     if n_nodes is None and unwind_turns:
         raise ValueError("unwind_turns works in front of the selection of n_nodes distinct nodes per rung: pass n_nodes")
     K = r = None
     if n_nodes is not None:
         K, r = _set_args(n_nodes, min_distance, S)
-    if max_iters < 1:
-        raise ValueError("max_iters must be >= 1")
-    if int(max_instances) < 1:
-        raise ValueError("max_instances must be >= 1")
-    if qvel_dt is not None and not float(qvel_dt) > 0.0:
-        raise ValueError("qvel_dt must be > 0")
-    if pos_threshold is None or ori_threshold is None or not (float(pos_threshold) >= 0.0 and float(ori_threshold) >= 0.0):
-        raise ValueError("thresholds must be >= 0: a ladder's rungs run in threshold mode only")
+    _, max_iters = _loop_scalars(max_instances, length=max_iters, step_name="qvel_dt", step=qvel_dt,
+                                 thresholds=(pos_threshold, ori_threshold), whose="a ladder's rungs")
     step_sq = _max_step_sq(max_step)
     # (judged on the objects themselves: the handle's layout says the same, but only once a handle exists)
     _refuse_plugin_rows({"dense": [t for t in tasks if t._is_dense()], "dense_limits": [x for x in (limits or ()) if x._is_dense()]},
@@ -2014,69 +1788,38 @@ def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt
     handles, layout, chunk, n_dev = _compile_outer(configuration, tasks, limits, dt, "solve_ik_trajectory_ladder", S * T,
                                                    max_instances)
     ft, pt, ct = _stacked_targets(configuration, layout, seqs, T)
-    # a batched target that is held over the path gets its T axis: the call takes (n, w) or (B, T, n, w)
-    pt, ct = [x if x is None or x.ndim != 3 else np.ascontiguousarray(np.broadcast_to(x[:, None], (B, T) + x.shape[1:]))
-              for x in (pt, ct)]
+    pt, ct = _held_over((pt, ct), B, T)
     q = configuration.q_batch
     kw = dict(n_seeds=S, max_iters=max_iters, pos_threshold=float(pos_threshold), ori_threshold=float(ori_threshold),
-              max_step_sq=step_sq, rng_seed=int(rng_seed), weights=weights, qvel_dt=qvel_dt, return_all=bool(return_all),
-              refine=bool(refine))
-
-    free_parts = []
+              max_step_sq=step_sq, rng_seed=int(rng_seed), weights=weights, qvel_dt=qvel_dt, return_all=bool(return_all))
+    if K is not None:
+        kw.update(n_nodes=K, min_distance=r, unwind_turns=bool(unwind_turns))
 
     def job(handle, lo, hi):
         args = (q[lo:hi], _rows(ft, 0, lo, hi), _rows(pt, 2, lo, hi), _rows(ct, 2, lo, hi), dt, damping)
+        rows = dict(target_index0=lo, seeds=_rows(seeds, 0, lo, hi), seed_table=seed_table)
         if collision_check is not None:
-            fkw = {k: v for k, v in kw.items() if k != "refine"}
-            if K is not None:
-                fkw.update(n_nodes=K, min_distance=r, unwind_turns=bool(unwind_turns))
-            o, more = handle.solve_trajectory_ladder_free(*args, checker=collision_check, edge_samples=int(edge_samples), target_index0=lo,
-                                                          seeds=_rows(seeds, 0, lo, hi), seed_table=seed_table, refine=free_refine,
-                                                          **fkw)
-            free_parts.append((lo, more))
-            return RefinedLadderNodesResult(*o[:17], o.repaired, o.refined, *o[20:])
-        if K is None:
-            o = handle.solve_trajectory_ladder(*args, target_index0=lo, seeds=_rows(seeds, 0, lo, hi), seed_table=seed_table, **kw)
-            return RefinedLadderNodesResult(*o[:17], o.repaired, o.refined)
-        o = handle.solve_trajectory_ladder_nodes(*args, target_index0=lo, seeds=_rows(seeds, 0, lo, hi), seed_table=seed_table,
-                                                 n_nodes=K, min_distance=r, unwind_turns=bool(unwind_turns), **kw)
-        return RefinedLadderNodesResult(*o[:17], o.repaired, o.refined, *o[20:])
+            return handle.solve_trajectory_ladder_free(*args, checker=collision_check, edge_samples=int(edge_samples),
+                                                       refine=free_refine, **rows, **kw)
+        call = handle.solve_trajectory_ladder if K is None else handle.solve_trajectory_ladder_nodes
+        return call(*args, refine=bool(refine), **rows, **kw)
 
-    res = _join(RefinedLadderNodesResult, _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job))
-    if safety_break and ((res.status & nat.ST_OUTSIDE_LIMITS) != 0).any():
-        b, t = (int(x) for x in np.argwhere((res.status & nat.ST_OUTSIDE_LIMITS) != 0)[0])
-        raise _outside_limits(
-            f"solve_ik_trajectory_ladder: the chosen node of (instance, waypoint) = ({b}, {t}) left its configuration limits at "
-            "some fused step")
-    _status_epilogue(res.status, "solve_ik_trajectory_ladder", "chosen path(s)",
-                     "QP failed at {n} of {of} chosen nodes (first: (instance, waypoint) = {first}, status {status})")
+    # (the native result, and behind a checker the pair of it and the checker's outputs: the result types by (nodes, checker, refined))
+    native = nat.TrajectoryLadderOut if K is None else nat.TrajectoryLadderNodesOut
+    res = _join(native if collision_check is None else (native, nat.LadderFreeOut),
+                _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job))
+    path = res if collision_check is None else res[0]
+    _status_epilogue(path.status, "solve_ik_trajectory_ladder", "chosen path(s)",
+                     "QP failed at {n} of {of} chosen nodes (first: (instance, waypoint) = {first}, status {status})",
+                     safety_break=(lambda b, t: f"the chosen node of (instance, waypoint) = ({b}, {t})") if safety_break else None)
     if update:
-        configuration.update(res.q[:, -1] if configuration.batched else res.q[0, -1])
-    un = configuration._unbatch
-    opt = lambda x, as_bool=False: None if x is None else un(x.astype(bool) if as_bool else x)
-    out = LadderResult(un(res.q), un(res.v), un(res.status), un(res.iters), un(res.converged.astype(bool)), un(res.node_index),
-                       un(res.n_tracked), un(res.n_breaks), un(res.path_length), un(res.edge_break.astype(bool)),
-                       opt(res.qvel), opt(res.q_all), opt(res.v_all), opt(res.status_all), opt(res.iters_all),
-                       opt(res.converged_all, True), opt(res.seeds))
-    fixed = (un(res.repaired), un(res.refined.astype(bool))) if refine else ()
-    if K is None and collision_check is None:
-        return RefinedLadderResult(*out, *fixed) if refine else out
-    if K is None:
-        free_parts.sort(key=lambda x: x[0])
-        more = [un(np.concatenate([np.asarray(m[i]) for _, m in free_parts])) for i in range(3)]
-        if free_refine:
-            return FreeRefinedLadderResult(*out, more[0].astype(bool), more[1], more[2], *fixed)
-        return FreeLadderResult(*out, more[0].astype(bool), more[1], more[2])
-    sets = [un(x) for x in (res.node_seed_index, res.node_multiplicity, res.node_distance, res.n_distinct, res.n_converged,
-                            res.n_uncovered, res.seed_index)]
-    if collision_check is None:
-        return (RefinedLadderNodesResult if refine else LadderNodesResult)(*out, *fixed, *sets)
-    free_parts.sort(key=lambda x: x[0])                     # (shards finish in any order; the rows are told apart by their offset)
-    more = [un(np.concatenate([np.asarray(m[i]) for _, m in free_parts])) for i in range(3)]
-    more[0] = more[0].astype(bool)
-    if free_refine:
-        return FreeRefinedLadderNodesResult(*out, *sets, *more, *fixed)
-    return FreeLadderNodesResult(*out, *sets, *more)
+        configuration.update(path.q[:, -1] if configuration.batched else path.q[0, -1])
+    cls = {(False, False): (LadderResult, RefinedLadderResult), (True, False): (LadderNodesResult, RefinedLadderNodesResult),
+           (False, True): (FreeLadderResult, FreeRefinedLadderResult),
+           (True, True): (FreeLadderNodesResult, FreeRefinedLadderNodesResult)}[K is not None, collision_check is not None][bool(refine)]
+    flags = ("converged", "edge_break", "converged_all") + (("refined",) if refine else ()) + \
+        (("edge_collision",) if collision_check is not None else ())
+    return _present(configuration, cls, res, flags)
 
 
 class RefinedPath(NamedTuple):
@@ -2098,28 +1841,13 @@ class RefinedPath(NamedTuple):
     converged: np.ndarray
 
 
-class FreeRefinedPath(NamedTuple):
+FreeRefinedPath = nat._extended(
+    "FreeRefinedPath", RefinedPath, nat.LADDER_REFINE_FREE_IO_FIELDS,
     """Result of refine_path(collision_check=...): RefinedPath's fields, in its order — `tracked` the EFFECTIVE flags of the
     returned path: tracked and free of collision —, then of the returned path `edge_collision` (B, T) — the motion into waypoint t
     passes through collision, entry 0 never —, `n_edge_collisions` (B,), `edge_margin` (B, T) — +inf at waypoint 0, NaN where the
     edge was not swept — and `node_margin` (B, T).  `n_tracked` counts the waypoints that are tracked, free of collision and
-    entered by a free motion."""
-    q: np.ndarray
-    tracked: np.ndarray
-    repaired: np.ndarray
-    refined: np.ndarray
-    edge_break: np.ndarray
-    n_tracked: np.ndarray
-    n_breaks: np.ndarray
-    path_length: np.ndarray
-    v: np.ndarray
-    status: np.ndarray
-    iters: np.ndarray
-    converged: np.ndarray
-    edge_collision: np.ndarray
-    n_edge_collisions: np.ndarray
-    edge_margin: np.ndarray
-    node_margin: np.ndarray
+    entered by a free motion.""", optional=False, module=__name__)
 
 
 def refine_path(configuration: Configuration, tasks: Sequence, dt: float, targets, q_path, tracked=None, max_iters: int = 32,
@@ -2152,13 +1880,8 @@ def refine_path(configuration: Configuration, tasks: Sequence, dt: float, target
     collision_check the call is the one above, unchanged."""
     del solver
     _check_collision_check(collision_check, configuration, edge_samples)
-    max_iters = int(max_iters)
-    if max_iters < 1:
-        raise ValueError("max_iters must be >= 1")
-    if int(max_instances) < 1:
-        raise ValueError("max_instances must be >= 1")
-    if pos_threshold is None or ori_threshold is None or not (float(pos_threshold) >= 0.0 and float(ori_threshold) >= 0.0):
-        raise ValueError("thresholds must be >= 0: the refinement's loops run in threshold mode only")
+    _, max_iters = _loop_scalars(max_instances, length=max_iters, thresholds=(pos_threshold, ori_threshold),
+                                 whose="the refinement's loops")
     step_sq = _max_step_sq(max_step)
     _refuse_plugin_rows({"dense": [t for t in tasks if t._is_dense()], "dense_limits": [x for x in (limits or ()) if x._is_dense()]},
                         "refine_path")
@@ -2169,17 +1892,12 @@ def refine_path(configuration: Configuration, tasks: Sequence, dt: float, target
     if q_path is None or q_path.shape not in ((T, nq), (B, T, nq)):
         raise ValueError(f"q_path must have shape {(T, nq)} or {(B, T, nq)}, got {None if q_path is None else q_path.shape}")
     q_path = np.ascontiguousarray(np.broadcast_to(q_path, (B, T, nq)))
-    if tracked is not None:
-        tracked = np.asarray(tracked.detach().cpu().numpy() if nat._is_torch(tracked) else tracked)
-        if tracked.shape not in ((T,), (B, T)):
-            raise ValueError(f"tracked must have shape {(T,)} or {(B, T)}, got {tracked.shape}")
-        tracked = np.ascontiguousarray(np.broadcast_to(tracked != 0, (B, T)))
+    tracked = _host_flags(tracked, "tracked", (T,), B)
     weights = _ladder_weights(weights, nv)
     _need_frame_task(tasks, "a ladder refinement")
     handles, layout, chunk, n_dev = _compile_outer(configuration, tasks, limits, dt, "refine_path", 1, max_instances)
     ft, pt, ct = _stacked_targets(configuration, layout, seqs, T)
-    pt, ct = [x if x is None or x.ndim != 3 else np.ascontiguousarray(np.broadcast_to(x[:, None], (B, T) + x.shape[1:]))
-              for x in (pt, ct)]
+    pt, ct = _held_over((pt, ct), B, T)
     q = configuration.q_batch
 
     def job(handle, lo, hi):
@@ -2190,28 +1908,20 @@ def refine_path(configuration: Configuration, tasks: Sequence, dt: float, target
         args = (None if tracked is None else tracked[lo:hi], _rows(ft, 0, lo, hi), _rows(pt, 2, lo, hi), _rows(ct, 2, lo, hi), dt,
                 damping)
         if collision_check is not None:
-            return FreeRefinedPath(*handle.ladder_refine_free(q[lo:hi], q_path[lo:hi], collision_check, *args,
-                                                              edge_samples=int(edge_samples), **kw))
-        return RefinedPath(*handle.ladder_refine(q[lo:hi], q_path[lo:hi], *args, **kw))
+            return handle.ladder_refine_free(q[lo:hi], q_path[lo:hi], collision_check, *args, edge_samples=int(edge_samples), **kw)
+        return handle.ladder_refine(q[lo:hi], q_path[lo:hi], *args, **kw)
 
-    res = _join(RefinedPath if collision_check is None else FreeRefinedPath,
+    res = _join(nat.LadderRefineOut if collision_check is None else nat.LadderRefineFreeOut,
                 _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job))
-    if safety_break and ((res.status & nat.ST_OUTSIDE_LIMITS) != 0).any():
-        b, t = (int(x) for x in np.argwhere((res.status & nat.ST_OUTSIDE_LIMITS) != 0)[0])
-        raise _outside_limits(
-            f"refine_path: the repaired node of (instance, waypoint) = ({b}, {t}) left its configuration limits at some fused step")
     _status_epilogue(res.status, "refine_path", "returned path(s)",
-                     "QP failed at {n} of {of} returned nodes (first: (instance, waypoint) = {first}, status {status})")
+                     "QP failed at {n} of {of} returned nodes (first: (instance, waypoint) = {first}, status {status})",
+                     safety_break=(lambda b, t: f"the repaired node of (instance, waypoint) = ({b}, {t})") if safety_break else None)
     if update:
         configuration.update(res.q[:, -1] if configuration.batched else res.q[0, -1])
-    un = configuration._unbatch
-    out = RefinedPath(un(res.q), un(res.tracked.astype(bool)), un(res.repaired), un(res.refined.astype(bool)),
-                      un(res.edge_break.astype(bool)), un(res.n_tracked), un(res.n_breaks), un(res.path_length), un(res.v),
-                      un(res.status), un(res.iters), un(res.converged.astype(bool)))
+    flags = ("tracked", "refined", "edge_break", "converged")
     if collision_check is None:
-        return out
-    return FreeRefinedPath(*out, un(res.edge_collision.astype(bool)), un(res.n_edge_collisions), un(res.edge_margin),
-                           un(res.node_margin))
+        return _present(configuration, RefinedPath, res, flags)
+    return _present(configuration, FreeRefinedPath, res, flags + ("edge_collision",))
 
 
 def ladder_path(configuration: Configuration, q_nodes, tracked=None, max_step: Optional[float] = None, weights=None,
@@ -2237,27 +1947,17 @@ def ladder_path(configuration: Configuration, q_nodes, tracked=None, max_step: O
     T, S = q_nodes.shape[-3], q_nodes.shape[-2]
     nat.check_ladder_shape(S, T, step_sq)
     q_nodes = np.ascontiguousarray(np.broadcast_to(q_nodes, (B, T, S, nq)))
-    if tracked is not None:
-        tracked = np.asarray(tracked.detach().cpu().numpy() if nat._is_torch(tracked) else tracked)
-        if tracked.shape not in ((T, S), (B, T, S)):
-            raise ValueError(f"tracked must have shape {(T, S)} or {(B, T, S)}, got {tracked.shape}")
-        tracked = np.ascontiguousarray(np.broadcast_to(tracked != 0, (B, T, S)))
+    tracked = _host_flags(tracked, "tracked", (T, S), B)
     weights = _ladder_weights(weights, nv)
     # (the search reads the model's joint table through a problem handle: the smallest one, a posture task, serves)
     prob, layout = _compile(configuration, [PostureTask(configuration.model, cost=1.0)], None, 1, devices=configuration.devices[:1])
     with _pin(configuration, layout):
         if collision_check is None:
-            out = prob.ladder_select(configuration.q_batch, q_nodes, tracked, step_sq, weights)
-        else:
-            out, more = prob.ladder_select_free(configuration.q_batch, q_nodes, collision_check, tracked, step_sq, weights,
-                                                int(edge_samples), True)
-    un = configuration._unbatch
-    path = LadderPath(un(out.node_index), un(out.q), un(out.n_tracked), un(out.n_breaks), un(out.path_length),
-                      un(out.edge_break.astype(bool)))
-    if collision_check is None:
-        return path
-    return FreeLadderPath(*path, un(more.edge_collision.astype(bool)), un(more.n_edge_collisions), un(more.edge_margin),
-                          un(more.node_margin), un(more.edge_margin_all))
+            return _present(configuration, LadderPath, prob.ladder_select(configuration.q_batch, q_nodes, tracked, step_sq, weights),
+                            flags=("edge_break",))
+        out = prob.ladder_select_free(configuration.q_batch, q_nodes, collision_check, tracked, step_sq, weights, int(edge_samples),
+                                      True)
+    return _present(configuration, FreeLadderPath, out, flags=("edge_break", "edge_collision"))
 
 
 def _chunks_and_shards(configuration: Configuration, layout, handles, B: int, chunk: int, n_dev: int, job):
