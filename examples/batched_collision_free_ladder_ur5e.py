@@ -4,11 +4,17 @@ by the ladder on 8 distinct unwound nodes per waypoint — once as it is, once w
 checked on the device behind its loop, every joint-space motion between consecutive nodes is swept (`--edge-samples` interior
 samples), and the dynamic program picks the path whose waypoints AND motions are free.
 
-    python examples/batched_collision_free_ladder_ur5e.py --paths 256 [--refine]
+    python examples/batched_collision_free_ladder_ur5e.py --paths 256 [--refine | --convex]
 
 With `--refine` a third call adds `refine="free"`: behind the checked search the refinement pass re-solves lost waypoints, breaks
 and waypoints entered through collision from their neighbours on the path, every repair checked as a node and the motions on
 both sides of it swept, on the device.
+
+With `--convex` the arm is the `ur5e_convex` workload's: its wrist is a CYLINDER, and a cylinder against the box wall has no
+analytic distance routine — a general convex pair (GJK, the expanding polytope).  The checker then holds the wrist beside the
+link capsules and is built with `sweep_rows=`: room for those pairs' distances at that many swept samples, which is what lets
+the checked ladder sweep such a checker's motions (in chunks of sweep_rows // edge_samples edges).  Not together with
+`--refine`: the refinement pass still refuses general convex pairs.
 
 UR5e, one FrameTask on `attachment_site` (costs 1 / 1, lm_damping 1), ConfigurationLimit, dt = 1, damping = 1e-3, thresholds
 1e-4 / 1e-4, 40 iterations per waypoint, every path started at `home`.  The checker holds every link capsule of the arm against
@@ -40,11 +46,19 @@ def main():
     ap.add_argument("--min-distance", type=float, default=0.02, help="clearance every capsule keeps from floor and wall (m)")
     ap.add_argument("--rng-seed", type=int, default=5)
     ap.add_argument("--refine", action="store_true", help='also run the checked call with refine="free"')
+    ap.add_argument("--convex", action="store_true", help="the ur5e_convex arm: a cylinder wrist against the box wall (a general convex pair)")
+    ap.add_argument("--sweep-rows", type=int, default=1 << 16, help="with --convex: swept samples the checker holds distances for")
     args = ap.parse_args()
+    if args.convex and args.refine:
+        ap.error('--convex with --refine: refine="free" refuses a checker with general convex pairs')
     B, T, S, K, M = args.paths, args.waypoints, args.seeds, args.n_nodes, args.edge_samples
     rng = np.random.default_rng(20261018)
 
-    model = mink.load_robot("ur5e")
+    if args.convex:
+        from mink_amd import workloads
+        model = workloads.load_bench_robot("ur5e_convex")
+    else:
+        model = mink.load_robot("ur5e")
     home = mink.custom_configuration_vector(model, "home")
     lo, hi = np.maximum(model.jnt_range[:, 0], -np.pi), np.minimum(model.jnt_range[:, 1], np.pi)
     q_first = rng.uniform(lo, hi, size=(B, model.nq))
@@ -53,9 +67,12 @@ def main():
     lines = cartesian_lines(pose(q_first), pose(q_last), T)
 
     capsules = [g for g in range(model.ngeom) if int(model.geom_type[g]) == 3 and model.geom_valid[g]]
-    scene = mink.CollisionAvoidanceLimit(model, [(capsules, ["floor", "wall"])], minimum_distance_from_collisions=args.min_distance,
+    pairs = [(capsules, ["floor", "wall"])] if capsules else []
+    if args.convex:
+        pairs.append((["wrist_3_link"], ["floor", "wall"]))                  # (its cylinder: analytic against the floor, GJK against the wall)
+    scene = mink.CollisionAvoidanceLimit(model, pairs, minimum_distance_from_collisions=args.min_distance,
                                          collision_detection_distance=0.2)
-    checker = mink.CollisionChecker(model, [scene])
+    checker = mink.CollisionChecker(model, [scene], sweep_rows=args.sweep_rows if args.convex else 0)
 
     end_effector = mink.FrameTask("attachment_site", "site", position_cost=1.0, orientation_cost=1.0, lm_damping=1.0)
     configuration = mink.Configuration(model, np.tile(home, (B, 1)))
@@ -88,7 +105,7 @@ def main():
         still = clean & nodes_free.all(axis=1)
         return complete, clean, still, still & moves_free.all(axis=1), nodes_free, moves_free
 
-    print(f"UR5e, {B} Cartesian lines of {T} waypoints, floor and wall; the ladder on {K} distinct unwound nodes of {S} solutions per "
+    print(f"UR5e{' (cylinder wrist)' if args.convex else ''}, {B} Cartesian lines of {T} waypoints, floor and wall; the ladder on {K} distinct unwound nodes of {S} solutions per "
           f"waypoint, {M} samples per motion:")
     for name, res, ms in rows:
         complete, clean, still, free, nodes_free, moves_free = judge(res)
@@ -98,6 +115,8 @@ def main():
     # what the checked call reports is what the checker finds on the returned path
     _, _, _, _, nodes_free, moves_free = judge(checked)
     tracked = checked.converged & ((checked.status & ~1) == 0)
+    # (an empty slot of a rung with fewer than n_nodes distinct free solutions holds candidate 0's rows and is not a node)
+    tracked &= np.take_along_axis(checked.node_seed_index, checked.node_index[..., None], axis=2)[..., 0] >= 0
     assert nodes_free[tracked].all()
     entered = tracked[:, 1:]                                                 # (a motion into a lost waypoint is not swept)
     assert (checked.edge_collision[:, 1:][entered] == ~moves_free[entered]).all()

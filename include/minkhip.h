@@ -1055,8 +1055,20 @@ int32_t mkh_problem_set_collision_check(MkhProblem *problem, MkhProblem *checker
  * mkh_swept_clearance evaluates N edges, q_from and q_to (N, nq); every output is (N,) and required.  Host pointers
  * (synchronous; staged whole) or device pointers with MKH_FLAG_DEVICE_PTRS (asynchronous on the stream); one launch either way —
  * a sweep has no per-row workspace, so N is not bound by the checker's max_batch; no other flag is accepted.  The checker is refused as mkh_clearance refuses it, and in addition:
- * Not covered: general convex pairs.  A checker WITH general convex pairs (cylinder-box, ellipsoid-*, mesh hulls) is refused
- * with MKH_E_INVALID by every sweep entry point: those pairs are pre-evaluated on rows in memory, and a sweep has none.
+ * General convex pairs.  A checker WITH general convex pairs (cylinder-box, ellipsoid-*, mesh hulls) is refused with
+ * MKH_E_INVALID by every sweep entry point by default: those pairs are pre-evaluated on rows in memory, and a sweep has none.
+ * mkh_problem_set_sweep_rows(checker, rows) reserves what lifts the refusal for mkh_swept_clearance, mkh_ladder_select_free and
+ * mkh_solve_trajectory_ladder_free (with and without n_nodes): a device buffer of `rows` sample rows, one distance (8 bytes)
+ * per general convex pair and row.  Such a call then walks its edges in chunks of floor(rows / n_samples) edges; per chunk the
+ * general convex routine runs on every interior sample of the swept edges with finite ends — the sample's q(u) formed joint by
+ * joint with the arithmetic above, the same doubles the analytic pairs see — and the sweep reads the distances; the stream
+ * orders the reuse of the buffer.  THE RULE does not change: a sample is judged as mkh_clearance judges a row, and the outputs do
+ * not depend on `rows`.  rows < n_samples (less than one edge) on a checker with general convex pairs: MKH_E_LIMIT.  On a
+ * checker without such pairs `rows` changes nothing: one launch, as ever.  rows = 0 frees the buffer and restores the refusal.
+ * mkh_problem_set_sweep_rows itself refuses what mkh_clearance refuses about the checker, rows < 0 (MKH_E_INVALID) and a size
+ * that overflows (MKH_E_LIMIT); it synchronizes the device.  Still refused whatever `rows` is: mkh_ladder_refine_free,
+ * mkh_solve_trajectory_ladder_free_refined, mkh_select_trajectory_candidates with a checker and
+ * mkh_solve_trajectory_multistart_free — what they sweep is produced inside the same call.
  * MKH_E_LIMIT when the poses of a row and the three rows of q beside them (a, b (-) a, q(u)) exceed 64 KB of LDS:
  * 7 nbody + 3 nq > 8192 doubles.  "One call in flight per checker handle" holds as for mkh_clearance.
  */
@@ -1067,6 +1079,7 @@ typedef struct MkhSweptClearanceIO {
 } MkhSweptClearanceIO;
 int32_t mkh_swept_clearance(MkhProblem *checker, int32_t N, const double *q_from /* (N, nq) */, const double *q_to /* (N, nq) */,
                             int32_t n_samples, const MkhSweptClearanceIO *io, int32_t flags, void *hip_stream);
+int32_t mkh_problem_set_sweep_rows(MkhProblem *checker, int64_t rows /* 0: free the buffer */);
 
 /*
  * Ladder-graph trajectory IK: S IK solutions per waypoint (a "rung"), computed independently of each other, and a dynamic

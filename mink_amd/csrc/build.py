@@ -330,7 +330,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     jobs.append((os.path.join(HERE, "clearance.hip"), os.path.join(BUILD, "clearance.o")))   # clearance of a batch of rows: mkh_clearance, the collision check behind the multi-start loops
     jobs.append((os.path.join(HERE, "ladder_refine_free.hip"), os.path.join(BUILD, "ladder_refine_free.o")))   # lr_check_kernel: the collision check between the loops of mkh_ladder_refine_free
     jobs.append((os.path.join(HERE, "sweep.hip"), os.path.join(BUILD, "sweep.o")))   # swept clearance of edges: mkh_swept_clearance, the edge mask of the checked ladder calls
-
+    jobs.append((os.path.join(HERE, "convex_sweep.hip"), os.path.join(BUILD, "convex_sweep.o")))   # convex_sweep_kernel: the general convex pairs of a sweep's samples, in front of sweep_kernel (convex_pre.hip's flags)
     jobs.append((os.path.join(HERE, "trajectory_free.hip"), os.path.join(BUILD, "trajectory_free.o")))   # tmf_check_kernel: nodes and edges of mkh_solve_trajectory_multistart_free / mkh_select_trajectory_candidates (sweep.hip's flags)
 
     def compile_one(job):

@@ -121,8 +121,9 @@ struct ClrRow {                    // in every lane of the group
 // bad_q: the row has a NaN or an infinite entry (every d_k is NaN: the rule states it; the distance routines' clamps and range
 // tests would swallow a NaN, and a capsule–capsule pair would come out at its cap).  cv / cv_row: the (·, n_cv, 7) records of
 // convex_contacts_kernel and the row's index there (read only for pairs with a cv_slot).  distance_row: (n_pairs,) or null.
+// CVS: the doubles of one record there — the 7 of convex_contacts_kernel, or 1 where convex_sweep_kernel left the distance alone.
 // Every lane of the wavefront calls it (wave_sync inside): a group without a row of its own repeats another's.
-template <int LPR>
+template <int LPR, int CVS = 7>
 __device__ __forceinline__ ClrRow clr_row(const WideProblem& P, double* const sX, const double* const sq, bool bad_q, int sub, int grp,
                                           int n_cv, const double* __restrict__ cv, size_t cv_row, double* __restrict__ distance_row) {
   const int nbody = P.nbody, XS = nbody, n_pairs = P.n_pairs;
@@ -187,7 +188,7 @@ __device__ __forceinline__ ClrRow clr_row(const WideProblem& P, double* const sX
         dist = __builtin_nan("");
       } else if (near) {
         if (cp.cv_slot >= 0) {
-          dist = cv[(cv_row * n_cv + cp.cv_slot) * 7];
+          dist = cv[(cv_row * n_cv + cp.cv_slot) * CVS];
         } else {
           const V3 gp1 = bp1 + qrot(bq1, V3{cp.lpos1[0], cp.lpos1[1], cp.lpos1[2]});
           const V3 gp2 = bp2 + qrot(bq2, V3{cp.lpos2[0], cp.lpos2[1], cp.lpos2[2]});

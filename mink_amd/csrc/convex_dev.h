@@ -565,16 +565,35 @@ __device__ MKH_POLISH_ATTR CvxPolish cvx_polish(const int t1, const V3 s1, const
   // kink planes, slots 0-2: the axes of shape 1, 3-5: those of shape 2 (a box has three, a cylinder / capsule its z axis)
   // (select chains on named values: a runtime index into R21.m would send the matrix to scratch)
   const V3 c0{R21.m[0], R21.m[3], R21.m[6]}, c1{R21.m[1], R21.m[4], R21.m[7]}, c2{R21.m[2], R21.m[5], R21.m[8]};
+#ifdef MKH_POLISH_BY_VALUE
+  // (a kernel that must stay without scratch — convex_sweep.hip: the conditional operator on NAMED vectors selects between their
+  //  addresses, and the compiler keeps c0 .. c2 in scratch to have one; on copies it selects values.  Same values either way.)
+  auto sel = [](bool s, V3 a, V3 b) -> V3 { return V3{s ? a.x : b.x, s ? a.y : b.y, s ? a.z : b.z}; };
+  auto kink = [&](int i) -> V3 {
+    const V3 r = sel(i == 3, c0, sel(i == 4, c1, c2));
+    return i < 3 ? V3{i == 0 ? 1.0 : 0.0, i == 1 ? 1.0 : 0.0, i == 2 ? 1.0 : 0.0} : r;
+  };
+#else
   auto kink = [&](int i) -> V3 {
     const V3 r = i == 3 ? c0 : (i == 4 ? c1 : c2);
     return i < 3 ? V3{i == 0 ? 1.0 : 0.0, i == 1 ? 1.0 : 0.0, i == 2 ? 1.0 : 0.0} : r;
   };
+#endif
   const bool ax1 = t1 == kGeomBox, z1 = ax1 || t1 == kGeomCylinder || t1 == kGeomCapsule;
   const bool ax2 = t2 == kGeomBox, z2 = ax2 || t2 == kGeomCylinder || t2 == kGeomCapsule;
   int ka = -1, kb = -1;
   {
     const double d0 = fabs(n0.x), d1 = fabs(n0.y), d2 = fabs(n0.z), d3 = fabs(dot(n0, c0)), d4 = fabs(dot(n0, c1)), d5 = fabs(dot(n0, c2));
+#ifdef MKH_POLISH_BY_VALUE
+    // (... and two conditional stores become one store through a selected address: ka and kb in scratch)
+    auto take = [&](bool has, double d, int i) {
+      const bool hit = has && d < kKinkTol, first = hit && ka < 0, second = hit && !first && kb < 0;
+      ka = first ? i : ka;
+      kb = second ? i : kb;
+    };
+#else
     auto take = [&](bool has, double d, int i) { if (has && d < kKinkTol) { if (ka < 0) ka = i; else if (kb < 0) kb = i; } };
+#endif
     take(ax1, d0, 0); take(ax1, d1, 1); take(z1, d2, 2); take(ax2, d3, 3); take(ax2, d4, 4); take(z2, d5, 5);
   }
   const bool pole1 = t1 == kGeomCylinder && n0.x * n0.x + n0.y * n0.y < kKinkTol * kKinkTol;

@@ -14,6 +14,7 @@
 #include "mkh_types.h"
 #include "wave_ops.h"
 #include "collide_dev.h"
+#include "convex_chain.h"
 #include "problem_plan.h"
 #include "wide_types.h"
 
@@ -24,44 +25,6 @@ static_assert(PLAN_GEOM_PLANE == GEOM_PLANE && PLAN_GEOM_SPHERE == GEOM_SPHERE &
               PLAN_GEOM_ELLIPSOID == GEOM_ELLIPSOID && PLAN_GEOM_CYLINDER == GEOM_CYLINDER && PLAN_GEOM_BOX == GEOM_BOX &&
               PLAN_GEOM_MESH == GEOM_MESH, "problem_plan.h: geom codes");
 static_assert(kConvexWsDoubles == (kEpaWsDoubles > kGjkWsDoubles ? kEpaWsDoubles : kGjkWsDoubles), "problem_plan.h: convex workspace");
-
-struct CvPre {
-  int32_t n_cv;
-  const int32_t* pair;       // [n_cv] index into WideProblem::pairs
-  const int32_t* chain_adr;  // [2·n_cv + 1]: bodies root → body1 of convex pair k at [chain_adr[2k], chain_adr[2k+1]), → body2 behind
-  const int32_t* chain;      // body ids
-};
-
-// pose of the last body of a chain (root first) at qrow: mj_kinematics along one branch (the arithmetic of wide_kernel.h's FK)
-__device__ __forceinline__ void cv_chain_pose(const WideProblem& P, const double* qrow, const int32_t* ch, int len, V3& xp, Q4& xq) {
-  xp = V3{0, 0, 0};
-  xq = Q4{1, 0, 0, 0};
-  for (int c = 0; c < len; ++c) {
-    const int b = ch[c];
-    xp = xp + qrot(xq, V3{P.body_pos[3 * b], P.body_pos[3 * b + 1], P.body_pos[3 * b + 2]});
-    xq = qmul(xq, Q4{P.body_quat[4 * b], P.body_quat[4 * b + 1], P.body_quat[4 * b + 2], P.body_quat[4 * b + 3]});
-    const int jadr = P.body_jntadr[b], jnum = P.body_jntnum[b];
-    for (int jn = 0; jn < jnum; ++jn) {
-      const int j = jadr + jn, jt = P.jnt_type[j], qa = P.jnt_qadr[j];
-      const V3 axl{P.jnt_axis[3 * j], P.jnt_axis[3 * j + 1], P.jnt_axis[3 * j + 2]};
-      const V3 jp{P.jnt_pos[3 * j], P.jnt_pos[3 * j + 1], P.jnt_pos[3 * j + 2]};
-      if (jt == JNT_FREE) {
-        xp = {qrow[qa], qrow[qa + 1], qrow[qa + 2]};
-        xq = qnormalize(Q4{qrow[qa + 3], qrow[qa + 4], qrow[qa + 5], qrow[qa + 6]});
-      }
-      const V3 ax = qrot(xq, axl), an = xp + qrot(xq, jp);
-      if (jt == JNT_SLIDE) {
-        xp = xp + (qrow[qa] - P.jnt_qpos0[j]) * ax;
-      } else if (jt == JNT_HINGE || jt == JNT_BALL) {
-        const Q4 qloc = (jt == JNT_HINGE) ? axis_angle(axl, qrow[qa] - P.jnt_qpos0[j])
-                                          : qnormalize(Q4{qrow[qa], qrow[qa + 1], qrow[qa + 2], qrow[qa + 3]});
-        xq = qmul(xq, qloc);
-        xp = an - qrot(xq, jp);
-      }
-    }
-    xq = qnormalize(xq);
-  }
-}
 
 // `ipw` items per wavefront (lanes [0, ipw) work): the routine is one long dependent chain per lane and a wavefront lasts as long as its
 // slowest lane (and runs its overlapping pairs one after the other), so a small batch is spread over MANY thin wavefronts —
@@ -76,7 +39,7 @@ __global__ __launch_bounds__(64) void convex_contacts_kernel(const WideProblem* 
     const int b = (int)(item / C.n_cv), k = (int)(item - (long long)b * C.n_cv);
     const CollisionPairDev& cp = P.pairs[C.pair[k]];
     cpp = &cp;
-    const double* qrow = q + (size_t)b * P.nq;
+    const CvRowMem qrow{q + (size_t)b * P.nq};
     V3 xp1, xp2; Q4 xq1, xq2;
     cv_chain_pose(P, qrow, C.chain + C.chain_adr[2 * k], C.chain_adr[2 * k + 1] - C.chain_adr[2 * k], xp1, xq1);
     cv_chain_pose(P, qrow, C.chain + C.chain_adr[2 * k + 1], C.chain_adr[2 * k + 2] - C.chain_adr[2 * k + 1], xp2, xq2);

@@ -239,6 +239,8 @@ struct MkhProblem : ProblemSelect {     // (what creation decided and plan_launc
   // general convex pairs of plain solves: evaluated by convex_contacts_kernel in front of the analytic collision build
   mkh::CvPre cv{};
   double* d_cv = nullptr;          // [max_batch][n_cv][7]
+  double* d_cv_sweep = nullptr;    // [sweep_rows][n_cv]: the distances of a chunk of swept samples (mkh_problem_set_sweep_rows)
+  int64_t sweep_rows = 0;
   double* d_qkeep = nullptr;       // fused loops with a redo launch behind them: the call's q as it came (q_out may alias it)
   int8_t* d_warm = nullptr;        // MKH_FLAG_WARM_START: active set of every instance after the previous solve (max_batch × nv)
   int warm_age = 0, warm_B = 0;    // solves since the state was reset / the batch size it belongs to
@@ -499,7 +501,7 @@ void mkh_problem_destroy(MkhProblem* p) {
   for (void* w : p->owned) (void)hipFree(w);
   (void)hipFree(p->d_dev); (void)hipFree(p->d_taps); (void)hipFree(p->d_work);
   (void)hipFree(p->d_lane); (void)hipFree(p->d_warm); (void)hipFree(p->d_qkeep);
-  (void)hipFree(p->d_cv); (void)hipFree(p->d_dev_tight); (void)hipFree(p->d_status_tight);
+  (void)hipFree(p->d_cv); (void)hipFree(p->d_cv_sweep); (void)hipFree(p->d_dev_tight); (void)hipFree(p->d_status_tight);
   (void)hipFree(p->s_iters);
   (void)hipFree(p->s_de); (void)hipFree(p->s_dJ); (void)hipFree(p->s_dG); (void)hipFree(p->s_dh); (void)hipFree(p->s_dbox); (void)hipFree(p->d_clk);
   (void)hipFree(p->d_wide);
@@ -1623,12 +1625,19 @@ int32_t mkh_problem_set_collision_check(MkhProblem* p, MkhProblem* checker) {
 }
 
 // ---- swept clearance (include/minkhip.h "THE RULE OF THE SWEEP"; kernel: sweep.hip)
-// Whether `ck` can be the checker of a sweep: what a clearance refuses, general convex pairs, and the wider LDS slice.
-static int32_t sweep_refuse(const MkhProblem* ck, const char* who) {
+// Whether `ck` can be the checker of a sweep: what a clearance refuses, general convex pairs without room for the samples'
+// distances, and the wider LDS slice.  n_samples: of an entry point that takes general convex pairs in chunks of the handle's
+// sweep_rows (sweep_edges below); 0: of one that does not — what it evaluates depends on data produced inside the same call.
+static int32_t sweep_refuse(const MkhProblem* ck, const char* who, int32_t n_samples = 0) {
   if (const int32_t rc = clearance_refuse(ck, who)) return rc;
-  if (ck->cv.n_cv > 0)
+  if (ck->cv.n_cv > 0 && (n_samples < 1 || ck->sweep_rows == 0))
     return fail(MKH_E_INVALID, "%s: the checker has general convex pairs (cylinder-box, ellipsoid-*, mesh hulls): they are pre-evaluated on "
-                               "rows in memory, and the samples of a sweep are never written there", who);
+                               "rows in memory, and the samples of a sweep are never written there%s", who,
+                n_samples < 1 ? " (this call does not take them through sweep_rows either)"
+                              : " (mkh_problem_set_sweep_rows / CollisionChecker(sweep_rows=) reserves room for their distances)");
+  if (ck->cv.n_cv > 0 && ck->sweep_rows < n_samples)
+    return fail(MKH_E_LIMIT, "%s: sweep_rows = %lld holds less than one edge of n_samples = %d samples", who, (long long)ck->sweep_rows,
+                n_samples);
   if (mkh::sweep_lds_bytes(ck->model->nbody, ck->model->nq, ck->dev.n_pairs) > 64 * 1024)
     return fail(MKH_E_LIMIT, "%s: %d bodies, nq = %d: the poses of a sample and the three rows of q beside them do not fit 64 KB of LDS "
                              "(7 nbody + 3 nq <= 8192)", who, ck->model->nbody, ck->model->nq);
@@ -1636,12 +1645,54 @@ static int32_t sweep_refuse(const MkhProblem* ck, const char* who) {
 }
 
 // ... and of a checked call on problem `p`.
-static int32_t sweep_refuse_for(const MkhProblem* p, const MkhProblem* ck, const char* who) {
+static int32_t sweep_refuse_for(const MkhProblem* p, const MkhProblem* ck, const char* who, int32_t n_samples = 0) {
   if (!ck) return fail(MKH_E_INVALID, "%s: null checker", who);
   if (ck->device != p->device)
     return fail(MKH_E_INVALID, "%s: the checker lives on device %d, the problem on device %d", who, ck->device, p->device);
   if (ck->model != p->model) return fail(MKH_E_INVALID, "%s: the checker belongs to another MkhModel than the problem", who);
-  return sweep_refuse(ck, who);
+  return sweep_refuse(ck, who, n_samples);
+}
+
+int32_t mkh_problem_set_sweep_rows(MkhProblem* ck, int64_t rows) {
+  const char* const who = "mkh_problem_set_sweep_rows";
+  if (!ck) return fail(MKH_E_INVALID, "null problem");
+  if (rows < 0) return fail(MKH_E_INVALID, "%s: rows = %lld must be >= 0", who, (long long)rows);
+  if (const int32_t rc = clearance_refuse(ck, who)) return rc;
+  const uint64_t width = (uint64_t)ck->cv.n_cv * sizeof(double);
+  if (width > 0 && (uint64_t)rows > (uint64_t)0x7fffffffffffLL / width)
+    return fail(MKH_E_LIMIT, "%s: rows = %lld x %d general convex pairs x 8 bytes overflows", who, (long long)rows, ck->cv.n_cv);
+  HIP_OK(hipSetDevice(ck->model->device));
+  HIP_OK(hipDeviceSynchronize());                              // (a sweep in flight may still read the old buffer)
+  (void)hipFree(ck->d_cv_sweep);
+  ck->d_cv_sweep = nullptr;
+  ck->sweep_rows = 0;
+  if (rows > 0 && width > 0) {
+    // (zeroed: a sample the pre-pass skips is never judged by what stands here, and what is read of it is at least a number)
+    HIP_OK(hipMalloc((void**)&ck->d_cv_sweep, (size_t)rows * width));
+    HIP_OK(hipMemset(ck->d_cv_sweep, 0, (size_t)rows * width));
+    HIP_OK(hipDeviceSynchronize());
+  }
+  ck->sweep_rows = rows;
+  return MKH_OK;
+}
+
+// The sweep of a's edges on st's stream.  A checker with general convex pairs: in chunks of floor(sweep_rows / M) edges,
+// convex_sweep_kernel then sweep_kernel on each — the stream orders the reuse of the buffer.  Without: one launch, as ever.
+static void sweep_edges(Stager& st, const MkhProblem* ck, mkh::SweepArgs a) {
+  const int nbody = ck->model->nbody, nq = ck->model->nq, np = ck->dev.n_pairs;
+  if (ck->cv.n_cv == 0) {
+    ST_LAUNCH(st, launch_sweep(st.stream, ck->d_wide, nbody, nq, np, a));
+    return;
+  }
+  const long long per = ck->sweep_rows / a.M;                  // (>= 1: sweep_refuse)
+  a.cv = ck->d_cv_sweep; a.n_cv = ck->cv.n_cv;
+  const char* const ipw_env = dbg_env("MKH_DEBUG_CONVEX_SWEEP_IPW");       // (experiment builds: items per wavefront of the pre-pass)
+  const int ipw = ipw_env ? atoi(ipw_env) : 0;
+  for (a.first = 0; a.first < a.N && st.ok(); a.first += per) {
+    a.count = a.N - a.first < per ? a.N - a.first : per;
+    ST_LAUNCH(st, launch_convex_sweep(st.stream, ck->d_wide, ck->cv.pair, ck->cv.chain_adr, ck->cv.chain, a, ipw));
+    ST_LAUNCH(st, launch_sweep(st.stream, ck->d_wide, nbody, nq, np, a));
+  }
 }
 
 int32_t mkh_swept_clearance(MkhProblem* ck, int32_t N, const double* q_from, const double* q_to, int32_t n_samples,
@@ -1653,7 +1704,7 @@ int32_t mkh_swept_clearance(MkhProblem* ck, int32_t N, const double* q_from, con
   if (flags & ~MKH_FLAG_DEVICE_PTRS) return fail(MKH_E_INVALID, "%s: flags = %d: only MKH_FLAG_DEVICE_PTRS is accepted", who, flags);
   if (!q_from || !q_to || !io || !io->margin || !io->sample || !io->pair)
     return fail(MKH_E_INVALID, "%s: q_from, q_to, io and its outputs margin, sample, pair are required", who);
-  if (const int32_t rc = sweep_refuse(ck, who)) return rc;
+  if (const int32_t rc = sweep_refuse(ck, who, n_samples)) return rc;
   const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
   HIP_OK(hipSetDevice(ck->model->device));
   Stager st{ck, (hipStream_t)hip_stream, devp, "swept_clearance"};
@@ -1668,7 +1719,7 @@ int32_t mkh_swept_clearance(MkhProblem* ck, int32_t N, const double* q_from, con
     a.sample = st.i32(WS_OUT_PICK, 2 * Nz); a.pair = a.sample ? a.sample + Nz : nullptr;
   }
   if (!st.ok()) return st.finish();
-  ST_LAUNCH(st, launch_sweep(st.stream, ck->d_wide, ck->model->nbody, (int)nq, ck->dev.n_pairs, a));
+  sweep_edges(st, ck, a);
   if (devp) return st.finish();
   st.down(io->margin, a.margin, Nz * sizeof(double));
   st.down(io->sample, a.sample, Nz * sizeof(int32_t));
@@ -2633,7 +2684,6 @@ static void ladder_search_free(Stager& st, const MkhProblem* ck, int B, int T, i
                                int32_t* o_nb, double* o_len, int32_t* o_eb, const LadderFreeOut& f) {
   const MkhProblem* const p = st.p;
   const size_t R = (size_t)B * T, nch = ((size_t)S + 63) / 64, E = R * S * S;
-  const int nbody = ck->model->nbody, nq = ck->model->nq, np = ck->dev.n_pairs;
   uint8_t* const blocked = (uint8_t*)st.need(WS_F_BLOCK, E);
   unsigned long long* const brk = (unsigned long long*)st.need(WS_L_PRED, R * nch * 8 + R * S);
   uint8_t* const pred = (uint8_t*)(brk + R * nch);
@@ -2645,7 +2695,7 @@ static void ladder_search_free(Stager& st, const MkhProblem* ck, int B, int T, i
     mkh::SweepArgs a{};
     a.mode = mkh::kSweepLadder; a.M = M; a.T = T; a.W = S; a.N = (long long)(E - (size_t)B * S * S);
     a.nodes = d_nodes; a.tracked = d_tracked; a.margin = f.edge_margin_all; a.blocked = blocked;
-    ST_LAUNCH(st, launch_sweep(st.stream, ck->d_wide, nbody, nq, np, a));
+    sweep_edges(st, ck, a);
   }
   ST_LAUNCH(st, launch_ladder_search_free(st.stream, B, T, S, p->dev.nq, p->dev.nv, p->model->njnt, p->ws[WS_JNT].i32(), d_q, d_nodes,
                                           d_tracked, blocked, d_w, max_step_sq, pred, brk, o_node, o_nt, o_nb, o_len, o_eb,
@@ -2653,13 +2703,14 @@ static void ladder_search_free(Stager& st, const MkhProblem* ck, int B, int T, i
   mkh::SweepArgs c{};
   c.mode = mkh::kSweepPath; c.M = M; c.T = T; c.W = S; c.N = (long long)R;
   c.nodes = d_nodes; c.tracked = d_tracked; c.node_index = o_node; c.margin = f.edge_margin;
-  ST_LAUNCH(st, launch_sweep(st.stream, ck->d_wide, nbody, nq, np, c));
+  sweep_edges(st, ck, c);
 }
 
 // What the checked calls refuse about the checker, the sample count and the graph's size.
 static int32_t ladder_free_refuse(const MkhProblem* p, const MkhProblem* ck, int32_t B, int32_t T, int32_t S, int32_t n_samples,
-                                  const MkhLadderFreeIO* f, const char* who) {
-  if (const int32_t rc = sweep_refuse_for(p, ck, who)) return rc;
+                                  const MkhLadderFreeIO* f, const char* who, bool convex_ok) {
+  // (general convex pairs: through the checker's sweep_rows where the call sweeps and nothing else — not with refinement)
+  if (const int32_t rc = sweep_refuse_for(p, ck, who, convex_ok ? (n_samples < 1 ? 1 : n_samples) : 0)) return rc;
   if (n_samples < 1) return fail(MKH_E_INVALID, "%s: n_samples = %d must be >= 1", who, n_samples);
   if (!f || !f->edge_collision || !f->n_edge_collisions || !f->edge_margin)
     return fail(MKH_E_INVALID, "%s: free_io and its outputs edge_collision, n_edge_collisions, edge_margin are required", who);
@@ -2678,7 +2729,7 @@ int32_t mkh_ladder_select_free(MkhProblem* p, MkhProblem* ck, int32_t B, int32_t
   if (!q || !q_nodes || !tracked) return fail(MKH_E_INVALID, "%s: q, q_nodes and tracked are required", who);
   if (!io || !io->node_index || !io->n_tracked || !io->n_breaks || !io->path_length || !io->edge_break)
     return fail(MKH_E_INVALID, "%s: io and its outputs node_index, n_tracked, n_breaks, path_length, edge_break are required", who);
-  if (const int32_t rc = ladder_free_refuse(p, ck, B, T, S, n_samples, fio, who)) return rc;
+  if (const int32_t rc = ladder_free_refuse(p, ck, B, T, S, n_samples, fio, who, true)) return rc;
   if (mkh::ladder_source_tile(S, p->dev.nq, p->dev.nv, p->model->njnt, nullptr, true) < 1)
     return fail(MKH_E_LIMIT, "%s: nq = %d: one destination tile and one source node with its flags do not fit 64 KB of LDS", who, p->dev.nq);
   const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
@@ -3306,7 +3357,7 @@ static int32_t ladder_free_call(const char* who, bool refined, MkhProblem* p, Mk
                                "the ladder on distinct nodes", who, n_nodes, nodes ? "given" : "NULL");
   const int W = n_nodes ? n_nodes : n_seeds;
   if (B < 1 || T < 1 || W < 1 || W > 256) return fail(MKH_E_INVALID, "%s: B = %d, T = %d and %d nodes per rung: B, T >= 1, 1 <= nodes <= 256", who, B, T, W);
-  if (const int32_t rc = ladder_free_refuse(p, ck, B, T, W, n_samples, fio, who)) return rc;
+  if (const int32_t rc = ladder_free_refuse(p, ck, B, T, W, n_samples, fio, who, !refined)) return rc;
   if (fio->node_margin)
     return fail(MKH_E_INVALID, "%s: node_margin is mkh_ladder_select_free's output: here the nodes' verdict is MKH_ST_IN_COLLISION in status_all", who);
   if (mkh::ladder_source_tile(W, p->dev.nq, p->dev.nv, p->model->njnt, nullptr, true) < 1)

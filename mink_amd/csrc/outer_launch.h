@@ -201,7 +201,8 @@ constexpr int32_t kStInCollision = 64;   // MKH_ST_IN_COLLISION
 hipError_t launch_clearance(hipStream_t stream, const void* wide_problem, int nbody, int n_pairs, int n_cv, const double* cv, int N,
                             const double* q, double* margin, int32_t* pair, int32_t* n_violated, double* distance, int32_t* status);
 // swept clearance (sweep.hip; include/minkhip.h "THE RULE OF THE SWEEP"): the M interior samples of N edges against the pairs of a
-// checker WITHOUT general convex pairs, one edge per wavefront or per DPP row by launch_clearance's criterion.  Which edges:
+// checker, one edge per wavefront or per DPP row by launch_clearance's criterion (general convex pairs: in chunks behind
+// launch_convex_sweep, below).  Which edges:
 //   kSweepPairs  edge e runs from row e of `from` to row e of `to`, (N, nq) each.
 //   kSweepLadder N = B·(T − 1)·W·W, T >= 2: the edges (b, t >= 1, s', s) from node (t − 1, s) to node (t, s') of `nodes`
 //                (B, T, W, nq), their outputs at ((b·T + t)·W + s')·W + s of (B, T, W, W) arrays whose t = 0 entries the launch
@@ -210,6 +211,9 @@ hipError_t launch_clearance(hipStream_t stream, const void* wide_problem, int nb
 //                a destination with tracked == 0: as above.
 // margin is optional; sample and pair (N,) are kSweepPairs' and required there; blocked, bytes, 1 where the edge collides, is the
 // ladder modes' and optional.
+// A checker WITH general convex pairs: the call's edges go in chunks — count > 0: this launch takes the edges [first, first + count)
+// of the N, every index and output address still the whole call's — and cv (count·M, n_cv) holds the distances
+// launch_convex_sweep left for the chunk's samples, sample i of the chunk's edge c in row c·M + i.  count = 0: all N edges, no cv.
 enum : int32_t { kSweepPairs = 0, kSweepLadder = 1, kSweepPath = 2 };
 struct SweepArgs {
   int32_t mode, M, T, W;
@@ -219,9 +223,18 @@ struct SweepArgs {
   double* margin;
   int32_t *sample, *pair;
   uint8_t* blocked;
+  long long first, count;
+  double* cv;
+  int32_t n_cv;
 };
 size_t sweep_lds_bytes(int nbody, int nq, int n_pairs);
 hipError_t launch_sweep(hipStream_t stream, const void* wide_problem, int nbody, int nq, int n_pairs, const SweepArgs& a);
+// The pre-pass of a chunk (convex_sweep.hip): the general convex distance routine on every interior sample of the chunk's swept
+// edges with finite ends, one lane per (edge, sample, general convex pair), into a.cv — which the caller passes on to launch_sweep
+// with the same SweepArgs.  pair / chain_adr / chain: the checker's lists of those pairs (convex_pre.hip CvPre), n_cv = a.n_cv.
+// ipw: items per wavefront, 0 = chosen from the size of the chunk.
+hipError_t launch_convex_sweep(hipStream_t stream, const void* wide_problem, const int32_t* pair, const int32_t* chain_adr,
+                               const int32_t* chain, const SweepArgs& a, int ipw);
 // the nodes of a checked ladder: tracked_out[i] = tracked[i] != 0 && node_margin[i] >= 0
 hipError_t launch_ladder_free_tracked(hipStream_t stream, const int32_t* tracked, const double* node_margin, long long total,
                                       int32_t* tracked_out);

@@ -711,9 +711,16 @@ class CollisionChecker:
     `limits`: built-in CollisionAvoidanceLimit objects of `model`; their geom pairs, in order, are the pair list — pair k with
     its limit's minimum_distance_from_collisions and collision_detection_distance (gain and bound_relaxation do not enter).
     A row is in collision when some pair is closer than its minimum distance.  One native handle per device model is built on
-    first use, for `max_rows` rows per launch (more rows are walked in chunks)."""
+    first use, for `max_rows` rows per launch (more rows are walked in chunks).
 
-    def __init__(self, model, limits: Sequence, max_rows: int = 65536):
+    `sweep_rows`: what the calls that judge the MOTION between configurations — swept_clearance, ladder_path and
+    solve_ik_trajectory_ladder with `collision_check=` — need of a checker with general convex pairs (cylinder-box,
+    cylinder-cylinder, ellipsoids, mesh hulls): a device buffer for the distances of those pairs at `sweep_rows` swept samples,
+    8 bytes per such pair and sample.  Such a call walks its edges in chunks of sweep_rows // n_samples edges; the results do
+    not depend on the value, which must be at least the call's samples per edge.  0, the default: those calls refuse such a
+    checker.  A checker of analytic pairs alone never needs it."""
+
+    def __init__(self, model, limits: Sequence, max_rows: int = 65536, sweep_rows: int = 0):
         import threading
         from .configuration import as_flat_model
         from .limits import CollisionAvoidanceLimit
@@ -739,6 +746,9 @@ class CollisionChecker:
         self.max_rows = int(max_rows)
         if self.max_rows < 1:
             raise ValueError("max_rows must be >= 1")
+        if isinstance(sweep_rows, bool) or not isinstance(sweep_rows, (int, np.integer)) or int(sweep_rows) < 0:
+            raise ValueError(f"sweep_rows must be an int >= 0, got {sweep_rows!r}")
+        self.sweep_rows = int(sweep_rows)
         self._handles = {}                 # id(NativeModel) → (NativeModel, NativeProblem)
         self._lock = threading.Lock()
         self._closed = False
@@ -749,8 +759,14 @@ class CollisionChecker:
                 raise ValueError("the collision checker is closed")
             hit = self._handles.get(id(nmodel))
             if hit is None:
-                hit = self._handles[id(nmodel)] = (nmodel, nat.NativeProblem(nmodel, collision_limits=self._descs,
-                                                                             max_batch=self.max_rows))
+                prob = nat.NativeProblem(nmodel, collision_limits=self._descs, max_batch=self.max_rows)
+                if self.sweep_rows:
+                    try:
+                        prob.set_sweep_rows(self.sweep_rows)
+                    except Exception:
+                        prob.close()
+                        raise
+                hit = self._handles[id(nmodel)] = (nmodel, prob)
             return hit[1]
 
     def _native_for(self, problem) -> "nat.NativeProblem":
@@ -785,7 +801,8 @@ class CollisionChecker:
         """The swept clearance of the straight joint-space moves from `q_from` to `q_to` — (nq,), (N, nq) or (..., nq), the
         same shape —: `n_samples` interior samples per edge at u = i / (n_samples + 1), each judged as `clearance` judges a row
         (include/minkhip.h "THE RULE OF THE SWEEP"); the ends themselves are not sampled.  The samples are built and evaluated
-        on the device.  Not for checkers with general convex pairs (cylinder-box, ellipsoids, mesh hulls): MinkHipError.
+        on the device.  A checker with general convex pairs (cylinder-box, ellipsoids, mesh hulls) needs `sweep_rows` >=
+        n_samples (the constructor's keyword): MinkHipError without.
         numpy in → numpy out; torch tensors on a device in → torch tensors there, on the current stream."""
         from .configuration import native_model
 
@@ -1742,7 +1759,9 @@ def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt
     ST_IN_COLLISION (in `status_all`; with n_nodes it takes no slot), so it is not tracked; every edge into a tracked node is
     swept with `edge_samples` interior samples and the search counts a waypoint entered by a colliding motion as lost (ladder_path
     states the rule).  The result is a FreeLadderResult / FreeLadderNodesResult: the fields above and `edge_collision`,
-    `n_edge_collisions`, `edge_margin`.  Without collision_check the call takes exactly the path described above.
+    `n_edge_collisions`, `edge_margin`.  A checker with general convex pairs (cylinder-box, ellipsoids, mesh hulls) needs its
+    `sweep_rows` >= edge_samples, with and without n_nodes — and is still refused together with refine="free".  Without
+    collision_check the call takes exactly the path described above.
 
     `refine="free"` (with collision_check only) runs refine_path(collision_check=...)'s pass behind the checked search, in the
     same call on the device: lost waypoints, breaks and waypoints entered by a colliding motion are re-solved from their
@@ -1935,7 +1954,9 @@ def ladder_path(configuration: Configuration, q_nodes, tracked=None, max_step: O
     node is checked on the device and a node in collision counts as not tracked; every edge into a tracked node is swept with
     `edge_samples` interior samples (CollisionChecker.swept_clearance's rule) and a waypoint entered by a colliding motion counts
     as lost, so the key's first component counts the waypoints that are untracked, in collision or entered through collision.
-    The result is then a FreeLadderPath.  Without collision_check the call is the one above, unchanged."""
+    The result is then a FreeLadderPath.  A checker with general convex pairs (cylinder-box, ellipsoids, mesh hulls) needs its
+    `sweep_rows` >= edge_samples; the edges are then swept in chunks of sweep_rows // edge_samples, and the result does not
+    depend on the value.  Without collision_check the call is the one above, unchanged."""
     from .tasks import PostureTask
 
     _check_collision_check(collision_check, configuration, edge_samples)
