@@ -4,7 +4,7 @@ by the ladder on 8 distinct unwound nodes per waypoint — once as it is, once w
 checked on the device behind its loop, every joint-space motion between consecutive nodes is swept (`--edge-samples` interior
 samples), and the dynamic program picks the path whose waypoints AND motions are free.
 
-    python examples/batched_collision_free_ladder_ur5e.py --paths 256 [--refine | --convex]
+    python examples/batched_collision_free_ladder_ur5e.py --paths 256 [--refine] [--convex]
 
 With `--refine` a third call adds `refine="free"`: behind the checked search the refinement pass re-solves lost waypoints, breaks
 and waypoints entered through collision from their neighbours on the path, every repair checked as a node and the motions on
@@ -13,8 +13,9 @@ both sides of it swept, on the device.
 With `--convex` the arm is the `ur5e_convex` workload's: its wrist is a CYLINDER, and a cylinder against the box wall has no
 analytic distance routine — a general convex pair (GJK, the expanding polytope).  The checker then holds the wrist beside the
 link capsules and is built with `sweep_rows=`: room for those pairs' distances at that many swept samples, which is what lets
-the checked ladder sweep such a checker's motions (in chunks of sweep_rows // edge_samples edges).  Not together with
-`--refine`: the refinement pass still refuses general convex pairs.
+the checked ladder sweep such a checker's motions (in chunks of sweep_rows // edge_samples edges).  Together with `--refine`
+it is also built with `check_rows=`: room for those pairs' distances on the rows the refinement pass judges inside its own
+launches — a repaired node and the samples of the two motions beside it, 1 + 2 edge_samples rows per line and step.
 
 UR5e, one FrameTask on `attachment_site` (costs 1 / 1, lm_damping 1), ConfigurationLimit, dt = 1, damping = 1e-3, thresholds
 1e-4 / 1e-4, 40 iterations per waypoint, every path started at `home`.  The checker holds every link capsule of the arm against
@@ -48,9 +49,8 @@ def main():
     ap.add_argument("--refine", action="store_true", help='also run the checked call with refine="free"')
     ap.add_argument("--convex", action="store_true", help="the ur5e_convex arm: a cylinder wrist against the box wall (a general convex pair)")
     ap.add_argument("--sweep-rows", type=int, default=1 << 16, help="with --convex: swept samples the checker holds distances for")
+    ap.add_argument("--check-rows", type=int, default=1 << 14, help="with --convex --refine: judged rows the checker holds distances for")
     args = ap.parse_args()
-    if args.convex and args.refine:
-        ap.error('--convex with --refine: refine="free" refuses a checker with general convex pairs')
     B, T, S, K, M = args.paths, args.waypoints, args.seeds, args.n_nodes, args.edge_samples
     rng = np.random.default_rng(20261018)
 
@@ -72,7 +72,8 @@ def main():
         pairs.append((["wrist_3_link"], ["floor", "wall"]))                  # (its cylinder: analytic against the floor, GJK against the wall)
     scene = mink.CollisionAvoidanceLimit(model, pairs, minimum_distance_from_collisions=args.min_distance,
                                          collision_detection_distance=0.2)
-    checker = mink.CollisionChecker(model, [scene], sweep_rows=args.sweep_rows if args.convex else 0)
+    checker = mink.CollisionChecker(model, [scene], sweep_rows=args.sweep_rows if args.convex else 0,
+                                    check_rows=args.check_rows if args.convex and args.refine else 0)
 
     end_effector = mink.FrameTask("attachment_site", "site", position_cost=1.0, orientation_cost=1.0, lm_damping=1.0)
     configuration = mink.Configuration(model, np.tile(home, (B, 1)))

@@ -7,7 +7,12 @@ the most waypoints that are tracked, free and entered by a free motion wins.  A 
 `refine_path(..., tracked=res.tracked, collision_check=checker)`, which re-solves the waypoints that did not count from their
 neighbours on the path, every repair checked and swept.
 
-    python examples/batched_collision_free_trajectory_ur5e.py --paths 256
+    python examples/batched_collision_free_trajectory_ur5e.py --paths 256 [--convex]
+
+With `--convex` the arm is the `ur5e_convex` workload's, whose wrist is a CYLINDER — against the box wall a general convex pair
+(GJK, the expanding polytope), held beside the link capsules.  Both calls judge rows they produce themselves, so the checker is
+built with `check_rows=` (room for those pairs' distances on that many judged rows: a candidate's node and the samples of the
+motion into it) and, for refine_path's sweep of the incoming path, `sweep_rows=`.
 
 UR5e, one FrameTask on `attachment_site` (costs 1 / 1, lm_damping 1), ConfigurationLimit, dt = 1, damping = 1e-3, thresholds
 1e-4 / 1e-4, 40 iterations per waypoint, every path started at `home`.  The checker holds every link capsule of the arm against
@@ -36,11 +41,19 @@ def main():
     ap.add_argument("--max-iters", type=int, default=40)
     ap.add_argument("--min-distance", type=float, default=0.02, help="clearance every capsule keeps from floor and wall (m)")
     ap.add_argument("--rng-seed", type=int, default=5)
+    ap.add_argument("--convex", action="store_true", help="the ur5e_convex arm: a cylinder wrist against the box wall (a general convex pair)")
+    ap.add_argument("--check-rows", type=int, default=1 << 22, help="with --convex: judged rows the checker holds distances for (8 bytes per "
+                    "general convex pair and row; the candidates' rows go in chunks of check_rows // (1 + edge_samples), and chunks cost)")
+    ap.add_argument("--sweep-rows", type=int, default=1 << 14, help="with --convex: swept samples the checker holds distances for")
     args = ap.parse_args()
     B, T, S, M = args.paths, args.waypoints, args.seeds, args.edge_samples
     rng = np.random.default_rng(20261018)
 
-    model = mink.load_robot("ur5e")
+    if args.convex:
+        from mink_amd import workloads
+        model = workloads.load_bench_robot("ur5e_convex")
+    else:
+        model = mink.load_robot("ur5e")
     home = mink.custom_configuration_vector(model, "home")
     lo, hi = np.maximum(model.jnt_range[:, 0], -np.pi), np.minimum(model.jnt_range[:, 1], np.pi)
     q_first = rng.uniform(lo, hi, size=(B, model.nq))
@@ -49,9 +62,13 @@ def main():
     lines = cartesian_lines(pose(q_first), pose(q_last), T)
 
     capsules = [g for g in range(model.ngeom) if int(model.geom_type[g]) == 3 and model.geom_valid[g]]
-    scene = mink.CollisionAvoidanceLimit(model, [(capsules, ["floor", "wall"])], minimum_distance_from_collisions=args.min_distance,
+    pairs = [(capsules, ["floor", "wall"])] if capsules else []
+    if args.convex:
+        pairs.append((["wrist_3_link"], ["floor", "wall"]))                  # (its cylinder: analytic against the floor, GJK against the wall)
+    scene = mink.CollisionAvoidanceLimit(model, pairs, minimum_distance_from_collisions=args.min_distance,
                                          collision_detection_distance=0.2)
-    checker = mink.CollisionChecker(model, [scene])
+    checker = mink.CollisionChecker(model, [scene], check_rows=args.check_rows if args.convex else 0,
+                                    sweep_rows=args.sweep_rows if args.convex else 0)
 
     end_effector = mink.FrameTask("attachment_site", "site", position_cost=1.0, orientation_cost=1.0, lm_damping=1.0)
     limits = [mink.ConfigurationLimit(model)]
@@ -79,7 +96,7 @@ def main():
         complete = tracked.all(axis=1)
         return complete, complete & nodes_free.all(axis=1) & moves_free.all(axis=1), nodes_free, moves_free
 
-    print(f"UR5e, {B} Cartesian lines of {T} waypoints, floor and wall; {S} candidate paths per line, {M} samples per motion:")
+    print(f"UR5e{' (cylinder wrist)' if args.convex else ''}, {B} Cartesian lines of {T} waypoints, floor and wall; {S} candidate paths per line, {M} samples per motion:")
     rows = [("plain candidate tracking", plain.q, plain.converged & ((plain.status & ~1) == 0), ms_plain),
             ("with collision_check", checked.q, checked.converged & ((checked.status & ~1) == 0), ms_checked),
             ("... then refine_path", refined.q, refined.tracked, ms_refined)]
@@ -98,6 +115,17 @@ def main():
           f"{int((refined.n_tracked == T).sum())} of {B}; free tracked waypoints {int(checked.n_tracked.sum())} -> "
           f"{int(refined.n_tracked.sum())} of {B * T}; {int(refined.refined.sum())} lines refined, {int((refined.repaired != 0).sum())} "
           f"waypoints repaired")
+    if args.convex:
+        # what the speculative pre-pass of the general convex pairs evaluated and the check then never read: the samples of the
+        # motions into candidate rows that converged and whose node then turned out to collide
+        every = track(collision_check=checker, edge_samples=M, return_all=True)
+        held = every.converged_all & ((every.status_all & ~(1 | mink.ST_IN_COLLISION)) == 0)
+        held[:, :, 0] = False
+        read = held & ((every.status_all & mink.ST_IN_COLLISION) == 0)
+        n_rows = held.size
+        pre, used = n_rows + M * int(held.sum()), n_rows + M * int(read.sum())
+        print(f"  general convex pairs: the pre-pass evaluated {pre} rows ({n_rows} nodes, {int(held.sum())} motions of {M} samples), the check "
+              f"read {used}: {100.0 * (pre - used) / pre:.1f} % never read")
     checker.close()
 
 

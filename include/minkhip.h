@@ -1066,9 +1066,23 @@ int32_t mkh_problem_set_collision_check(MkhProblem *problem, MkhProblem *checker
  * not depend on `rows`.  rows < n_samples (less than one edge) on a checker with general convex pairs: MKH_E_LIMIT.  On a
  * checker without such pairs `rows` changes nothing: one launch, as ever.  rows = 0 frees the buffer and restores the refusal.
  * mkh_problem_set_sweep_rows itself refuses what mkh_clearance refuses about the checker, rows < 0 (MKH_E_INVALID) and a size
- * that overflows (MKH_E_LIMIT); it synchronizes the device.  Still refused whatever `rows` is: mkh_ladder_refine_free,
- * mkh_solve_trajectory_ladder_free_refined, mkh_select_trajectory_candidates with a checker and
- * mkh_solve_trajectory_multistart_free — what they sweep is produced inside the same call.
+ * that overflows (MKH_E_LIMIT); it synchronizes the device.  Still refused whatever `rows` is, on a checker that has
+ * sweep_rows alone: mkh_ladder_refine_free, mkh_solve_trajectory_ladder_free_refined, mkh_select_trajectory_candidates with a
+ * checker and mkh_solve_trajectory_multistart_free — what they sweep is produced inside the same call.  They take such a
+ * checker through a resource of its own:
+ * mkh_problem_set_check_rows(checker, rows) reserves a second device buffer, of `rows` JUDGED rows — a node or a sample judged
+ * inside a call, not an interior sample of an edge known in front of it —, one distance (8 bytes) per general convex pair and
+ * row, zeroed.  With M = n_samples, mkh_select_trajectory_candidates with a checker and mkh_solve_trajectory_multistart_free
+ * need rows >= 1 + M and judge their T * B * S candidate rows in chunks of floor(rows / (1 + M)); mkh_ladder_refine_free and
+ * mkh_solve_trajectory_ladder_free_refined need rows >= 1 + 2M AND sweep_rows >= M (the pass sweeps the incoming path, the fused
+ * call searches, with sweep_rows) and judge the B loop results of a waypoint step in chunks of floor(rows / (1 + 2M)).  Per
+ * chunk a SPECULATIVE pre-pass runs the general convex routine on every row the check could read — its conditions without the
+ * node's verdict, which only the check knows: the node itself where it is finite, and the samples of every edge that would be
+ * swept behind a free node — and the check reads a subset.  THE RULES do not change and the outputs do not depend on `rows`.
+ * check_rows = 0 on such a checker, or a missing sweep_rows where it is needed: MKH_E_INVALID, the message naming what is
+ * missing; a positive check_rows below one item: MKH_E_LIMIT.  On a checker without general convex pairs check_rows changes
+ * nothing: every call runs the launches it always ran.  rows = 0 frees the buffer.  mkh_problem_set_check_rows itself refuses
+ * and returns what mkh_problem_set_sweep_rows does; it synchronizes the device.
  * MKH_E_LIMIT when the poses of a row and the three rows of q beside them (a, b (-) a, q(u)) exceed 64 KB of LDS:
  * 7 nbody + 3 nq > 8192 doubles.  "One call in flight per checker handle" holds as for mkh_clearance.
  */
@@ -1080,6 +1094,7 @@ typedef struct MkhSweptClearanceIO {
 int32_t mkh_swept_clearance(MkhProblem *checker, int32_t N, const double *q_from /* (N, nq) */, const double *q_to /* (N, nq) */,
                             int32_t n_samples, const MkhSweptClearanceIO *io, int32_t flags, void *hip_stream);
 int32_t mkh_problem_set_sweep_rows(MkhProblem *checker, int64_t rows /* 0: free the buffer */);
+int32_t mkh_problem_set_check_rows(MkhProblem *checker, int64_t rows /* 0: free the buffer */);
 
 /*
  * Ladder-graph trajectory IK: S IK solutions per waypoint (a "rung"), computed independently of each other, and a dynamic

@@ -879,6 +879,8 @@ def lib() -> C.CDLL:
     L.mkh_swept_clearance.restype = C.c_int32
     L.mkh_problem_set_sweep_rows.argtypes = [C.c_void_p, C.c_int64]
     L.mkh_problem_set_sweep_rows.restype = C.c_int32
+    L.mkh_problem_set_check_rows.argtypes = [C.c_void_p, C.c_int64]
+    L.mkh_problem_set_check_rows.restype = C.c_int32
     L.mkh_ladder_select_free.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_double, C.c_int32, C.POINTER(MkhLadderIO), C.POINTER(MkhLadderFreeIO),
                                          C.c_int32, C.c_void_p]
@@ -915,7 +917,7 @@ EXPORTED_SYMBOLS = (
     "mkh_ladder_refine", "mkh_solve_trajectory_ladder_refined", "mkh_solve_multistart_set", "mkh_select_distinct",
     "mkh_solve_goalset", "mkh_select_goalset", "mkh_unwind_turns", "mkh_solve_trajectory_ladder_nodes",
     "mkh_clearance", "mkh_problem_set_collision_check",
-    "mkh_swept_clearance", "mkh_problem_set_sweep_rows", "mkh_ladder_select_free", "mkh_solve_trajectory_ladder_free",
+    "mkh_swept_clearance", "mkh_problem_set_sweep_rows", "mkh_problem_set_check_rows", "mkh_ladder_select_free", "mkh_solve_trajectory_ladder_free",
     "mkh_ladder_refine_free", "mkh_solve_trajectory_ladder_free_refined",
     "mkh_select_trajectory_candidates", "mkh_solve_trajectory_multistart_free",
 )
@@ -1449,6 +1451,16 @@ class NativeProblem:
             raise ValueError(f"rows must be an int >= 0, got {rows!r}")
         with self._lock:
             _check(lib().mkh_problem_set_sweep_rows(self.handle, int(rows)))
+
+    def set_check_rows(self, rows: int) -> None:
+        """mkh_problem_set_check_rows with this handle as the checker: room for the general convex pairs' distances of `rows`
+        rows judged inside a call (8 bytes per such pair and row) — what lets checked candidate tracking (>= 1 + n_samples) and,
+        together with set_sweep_rows, the checked refinement pass (>= 1 + 2 n_samples) take a checker with cylinder-box,
+        ellipsoid or mesh-hull pairs.  0 frees it.  Synchronizes the device."""
+        if isinstance(rows, bool) or not isinstance(rows, (int, np.integer)) or int(rows) < 0:
+            raise ValueError(f"rows must be an int >= 0, got {rows!r}")
+        with self._lock:
+            _check(lib().mkh_problem_set_check_rows(self.handle, int(rows)))
 
     def last_kernel(self) -> str:
         """Kernel variant launched by the last solve on this handle (diagnostic)."""

@@ -158,7 +158,8 @@ def _parse_resource_remarks(stderr: str) -> dict:
     -Rpass-analysis=kernel-resource-usage remarks of one translation unit (kernels and their real callees)."""
     out, cur = {}, None
     keys = {"VGPRs": "vgprs", "AGPRs": "agprs", "TotalSGPRs": "sgprs", "ScratchSize [bytes/lane]": "scratch_bytes_per_lane",
-            "Occupancy [waves/SIMD]": "occupancy_waves_per_simd", "SGPRs Spill": "sgpr_spills", "VGPRs Spill": "vgpr_spills"}
+            "Occupancy [waves/SIMD]": "occupancy_waves_per_simd", "SGPRs Spill": "sgpr_spills", "VGPRs Spill": "vgpr_spills",
+            "LDS Size [bytes/block]": "lds_bytes_per_block"}       # (static LDS: a launch's dynamic bytes are the launcher's)
     for m in re.finditer(r"remark:\s+([A-Za-z \[\]/]+): (\S+) \[-Rpass-analysis", stderr):
         k, v = m.group(1).strip(), m.group(2)
         if k == "Function Name":
@@ -331,6 +332,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     jobs.append((os.path.join(HERE, "ladder_refine_free.hip"), os.path.join(BUILD, "ladder_refine_free.o")))   # lr_check_kernel: the collision check between the loops of mkh_ladder_refine_free
     jobs.append((os.path.join(HERE, "sweep.hip"), os.path.join(BUILD, "sweep.o")))   # swept clearance of edges: mkh_swept_clearance, the edge mask of the checked ladder calls
     jobs.append((os.path.join(HERE, "convex_sweep.hip"), os.path.join(BUILD, "convex_sweep.o")))   # convex_sweep_kernel: the general convex pairs of a sweep's samples, in front of sweep_kernel (convex_pre.hip's flags)
+    jobs.append((os.path.join(HERE, "convex_check.hip"), os.path.join(BUILD, "convex_check.o")))   # convex_check_kernel: the general convex pairs of the rows tmf_check_cv_kernel / lr_check_cv_kernel judge inside their launch (convex_sweep.hip's flags)
     jobs.append((os.path.join(HERE, "trajectory_free.hip"), os.path.join(BUILD, "trajectory_free.o")))   # tmf_check_kernel: nodes and edges of mkh_solve_trajectory_multistart_free / mkh_select_trajectory_candidates (sweep.hip's flags)
 
     def compile_one(job):

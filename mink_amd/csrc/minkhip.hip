@@ -241,6 +241,8 @@ struct MkhProblem : ProblemSelect {     // (what creation decided and plan_launc
   double* d_cv = nullptr;          // [max_batch][n_cv][7]
   double* d_cv_sweep = nullptr;    // [sweep_rows][n_cv]: the distances of a chunk of swept samples (mkh_problem_set_sweep_rows)
   int64_t sweep_rows = 0;
+  double* d_cv_check = nullptr;    // [check_rows][n_cv]: the distances on the rows a check judges inside its launch (mkh_problem_set_check_rows)
+  int64_t check_rows = 0;
   double* d_qkeep = nullptr;       // fused loops with a redo launch behind them: the call's q as it came (q_out may alias it)
   int8_t* d_warm = nullptr;        // MKH_FLAG_WARM_START: active set of every instance after the previous solve (max_batch × nv)
   int warm_age = 0, warm_B = 0;    // solves since the state was reset / the batch size it belongs to
@@ -501,7 +503,7 @@ void mkh_problem_destroy(MkhProblem* p) {
   for (void* w : p->owned) (void)hipFree(w);
   (void)hipFree(p->d_dev); (void)hipFree(p->d_taps); (void)hipFree(p->d_work);
   (void)hipFree(p->d_lane); (void)hipFree(p->d_warm); (void)hipFree(p->d_qkeep);
-  (void)hipFree(p->d_cv); (void)hipFree(p->d_cv_sweep); (void)hipFree(p->d_dev_tight); (void)hipFree(p->d_status_tight);
+  (void)hipFree(p->d_cv); (void)hipFree(p->d_cv_sweep); (void)hipFree(p->d_cv_check); (void)hipFree(p->d_dev_tight); (void)hipFree(p->d_status_tight);
   (void)hipFree(p->s_iters);
   (void)hipFree(p->s_de); (void)hipFree(p->s_dJ); (void)hipFree(p->s_dG); (void)hipFree(p->s_dh); (void)hipFree(p->s_dbox); (void)hipFree(p->d_clk);
   (void)hipFree(p->d_wide);
@@ -1627,10 +1629,27 @@ int32_t mkh_problem_set_collision_check(MkhProblem* p, MkhProblem* checker) {
 // ---- swept clearance (include/minkhip.h "THE RULE OF THE SWEEP"; kernel: sweep.hip)
 // Whether `ck` can be the checker of a sweep: what a clearance refuses, general convex pairs without room for the samples'
 // distances, and the wider LDS slice.  n_samples: of an entry point that takes general convex pairs in chunks of the handle's
-// sweep_rows (sweep_edges below); 0: of one that does not — what it evaluates depends on data produced inside the same call.
-static int32_t sweep_refuse(const MkhProblem* ck, const char* who, int32_t n_samples = 0) {
+// sweep_rows (sweep_edges below); 0: of one that does not sweep edges known in front of a launch.  check_item: of an entry point
+// that judges rows INSIDE a launch (the candidate tracking check, the refinement's) the rows of one of its items, 1 + M or
+// 1 + 2M — it takes general convex pairs in chunks of the handle's check_rows (tmf_check, refine_pass below), and, where n_samples says so,
+// sweeps with sweep_rows as well; 0: of one that judges none.
+static int32_t sweep_refuse(const MkhProblem* ck, const char* who, int32_t n_samples = 0, int32_t check_item = 0) {
   if (const int32_t rc = clearance_refuse(ck, who)) return rc;
-  if (ck->cv.n_cv > 0 && (n_samples < 1 || ck->sweep_rows == 0))
+  if (ck->cv.n_cv > 0 && check_item > 0) {
+    if (ck->check_rows == 0)
+      return fail(MKH_E_INVALID, "%s: the checker has general convex pairs (cylinder-box, ellipsoid-*, mesh hulls): they are pre-evaluated on "
+                                 "rows in memory, and this call judges rows it produces inside a launch (mkh_problem_set_check_rows / "
+                                 "CollisionChecker(check_rows=) reserves room for their distances)", who);
+    if (n_samples >= 1 && ck->sweep_rows == 0)
+      return fail(MKH_E_INVALID, "%s: the checker has general convex pairs (cylinder-box, ellipsoid-*, mesh hulls) and check_rows, but this "
+                                 "call also sweeps edges of paths (mkh_problem_set_sweep_rows / CollisionChecker(sweep_rows=) reserves "
+                                 "room for their distances)", who);
+    if (ck->check_rows < check_item)
+      return fail(MKH_E_LIMIT, "%s: check_rows = %lld holds less than one item of %d rows", who, (long long)ck->check_rows, check_item);
+    if (n_samples >= 1 && ck->sweep_rows < n_samples)
+      return fail(MKH_E_LIMIT, "%s: sweep_rows = %lld holds less than one edge of n_samples = %d samples", who, (long long)ck->sweep_rows,
+                  n_samples);
+  } else if (ck->cv.n_cv > 0 && (n_samples < 1 || ck->sweep_rows == 0))
     return fail(MKH_E_INVALID, "%s: the checker has general convex pairs (cylinder-box, ellipsoid-*, mesh hulls): they are pre-evaluated on "
                                "rows in memory, and the samples of a sweep are never written there%s", who,
                 n_samples < 1 ? " (this call does not take them through sweep_rows either)"
@@ -1645,13 +1664,17 @@ static int32_t sweep_refuse(const MkhProblem* ck, const char* who, int32_t n_sam
 }
 
 // ... and of a checked call on problem `p`.
-static int32_t sweep_refuse_for(const MkhProblem* p, const MkhProblem* ck, const char* who, int32_t n_samples = 0) {
+static int32_t sweep_refuse_for(const MkhProblem* p, const MkhProblem* ck, const char* who, int32_t n_samples = 0, int32_t check_item = 0) {
   if (!ck) return fail(MKH_E_INVALID, "%s: null checker", who);
   if (ck->device != p->device)
     return fail(MKH_E_INVALID, "%s: the checker lives on device %d, the problem on device %d", who, ck->device, p->device);
   if (ck->model != p->model) return fail(MKH_E_INVALID, "%s: the checker belongs to another MkhModel than the problem", who);
-  return sweep_refuse(ck, who, n_samples);
+  return sweep_refuse(ck, who, n_samples, check_item);
 }
+
+// The rows of one item of the checks that judge rows inside a launch, from a sample count that may not have been judged yet.
+static int32_t tracking_item(int32_t n_samples) { return 1 + (n_samples < 1 ? 1 : n_samples); }
+static int32_t refinement_item(int32_t n_samples) { return 1 + 2 * (n_samples < 1 ? 1 : n_samples); }
 
 int32_t mkh_problem_set_sweep_rows(MkhProblem* ck, int64_t rows) {
   const char* const who = "mkh_problem_set_sweep_rows";
@@ -1673,6 +1696,29 @@ int32_t mkh_problem_set_sweep_rows(MkhProblem* ck, int64_t rows) {
     HIP_OK(hipDeviceSynchronize());
   }
   ck->sweep_rows = rows;
+  return MKH_OK;
+}
+
+int32_t mkh_problem_set_check_rows(MkhProblem* ck, int64_t rows) {
+  const char* const who = "mkh_problem_set_check_rows";
+  if (!ck) return fail(MKH_E_INVALID, "null problem");
+  if (rows < 0) return fail(MKH_E_INVALID, "%s: rows = %lld must be >= 0", who, (long long)rows);
+  if (const int32_t rc = clearance_refuse(ck, who)) return rc;
+  const uint64_t width = (uint64_t)ck->cv.n_cv * sizeof(double);
+  if (width > 0 && (uint64_t)rows > (uint64_t)0x7fffffffffffLL / width)
+    return fail(MKH_E_LIMIT, "%s: rows = %lld x %d general convex pairs x 8 bytes overflows", who, (long long)rows, ck->cv.n_cv);
+  HIP_OK(hipSetDevice(ck->model->device));
+  HIP_OK(hipDeviceSynchronize());                              // (a check in flight may still read the old buffer)
+  (void)hipFree(ck->d_cv_check);
+  ck->d_cv_check = nullptr;
+  ck->check_rows = 0;
+  if (rows > 0 && width > 0) {
+    // (zeroed: a row the pre-pass skips is never judged by what stands here, and what is read of it is at least a number)
+    HIP_OK(hipMalloc((void**)&ck->d_cv_check, (size_t)rows * width));
+    HIP_OK(hipMemset(ck->d_cv_check, 0, (size_t)rows * width));
+    HIP_OK(hipDeviceSynchronize());
+  }
+  ck->check_rows = rows;
   return MKH_OK;
 }
 
@@ -2167,11 +2213,27 @@ static TmfDev tmf_stage(Stager& st, const MkhTrajectoryFreeIO& f, size_t N, size
   return d;
 }
 
-// The one launch over all T·B·S rows: node margins, the status bit, edge margins.
+// The one launch over all T·B·S rows: node margins, the status bit, edge margins.  A checker with general convex pairs: in chunks
+// of rows, each behind its pre-pass.
 static void tmf_check(Stager& st, const MkhProblem* ck, int B, int S, int T, int M, const double* q_all, const int32_t* cv_all,
                       int32_t* st_all, const TmfDev& d) {
-  ST_LAUNCH(st, launch_tmf_check(st.stream, ck->d_wide, ck->model->nbody, ck->model->nq, ck->dev.n_pairs, B, S, T, M, q_all, cv_all, st_all,
-                                 d.nm_all, d.em_all));
+  if (ck->cv.n_cv == 0) {
+    ST_LAUNCH(st, launch_tmf_check(st.stream, ck->d_wide, ck->model->nbody, ck->model->nq, ck->dev.n_pairs, B, S, T, M, q_all, cv_all, st_all,
+                                   d.nm_all, d.em_all));
+    return;
+  }
+  // general convex pairs: chunks of floor(check_rows / (1 + M)) rows (>= 1: sweep_refuse), convex_check_kernel then the check on
+  // each — the pre-pass reads a chunk's status in front of the check that ORs into it; the stream orders the reuse of the buffer
+  const long long N = (long long)B * S * T, per = ck->check_rows / (1 + M);
+  mkh::CvCheckArgs a{};
+  a.mode = mkh::kCvCheckTrack; a.M = M; a.R = (long long)B * S; a.q_all = q_all; a.converged = cv_all; a.status = st_all;
+  for (a.first = 0; a.first < N && st.ok(); a.first += per) {
+    a.count = N - a.first < per ? N - a.first : per;
+    const mkh::CvChunk c{a.first, a.count, ck->d_cv_check, ck->cv.n_cv};
+    ST_LAUNCH(st, launch_convex_check(st.stream, ck->d_wide, ck->cv.pair, ck->cv.chain_adr, ck->cv.chain, ck->cv.n_cv, a, ck->d_cv_check));
+    ST_LAUNCH(st, launch_tmf_check(st.stream, ck->d_wide, ck->model->nbody, ck->model->nq, ck->dev.n_pairs, B, S, T, M, q_all, cv_all, st_all,
+                                   d.nm_all, d.em_all, c));
+  }
 }
 
 // The chosen candidate's margins (plain gathers: edge_margin_all carries +inf at waypoint 0) and its edge flags, through the
@@ -2232,7 +2294,7 @@ static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double
   if (const int32_t rc = refuse_checker(p, who)) return rc;
   const bool checked = cs && cs->checked;
   if (checked)
-    if (const int32_t rc = sweep_refuse_for(p, cs->ck, who)) return rc;
+    if (const int32_t rc = sweep_refuse_for(p, cs->ck, who, 0, tracking_item(cs->M))) return rc;
   const DeviceProblem& P = p->dev;
   if (const int32_t rc = refuse_inputs(P, q, frame_targets, posture_target, com_target, until ? who : nullptr, "trajectory"))
     return rc;
@@ -2551,7 +2613,7 @@ int32_t mkh_select_trajectory_candidates(MkhProblem* p, MkhProblem* ck, int32_t 
     if (const int32_t rc = tmf_refuse_args(n_samples, fio, who)) return rc;
   if (!p) return fail(MKH_E_INVALID, "null problem");
   if (ck)
-    if (const int32_t rc = sweep_refuse_for(p, ck, who)) return rc;
+    if (const int32_t rc = sweep_refuse_for(p, ck, who, 0, tracking_item(n_samples))) return rc;
   if ((long long)B * S * T > 0x7fffffffLL)
     return fail(MKH_E_LIMIT, "%s: B * S * T = %lld rows, at most 2^31 - 1", who, (long long)B * S * T);
   const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
@@ -2708,9 +2770,10 @@ static void ladder_search_free(Stager& st, const MkhProblem* ck, int B, int T, i
 
 // What the checked calls refuse about the checker, the sample count and the graph's size.
 static int32_t ladder_free_refuse(const MkhProblem* p, const MkhProblem* ck, int32_t B, int32_t T, int32_t S, int32_t n_samples,
-                                  const MkhLadderFreeIO* f, const char* who, bool convex_ok) {
-  // (general convex pairs: through the checker's sweep_rows where the call sweeps and nothing else — not with refinement)
-  if (const int32_t rc = sweep_refuse_for(p, ck, who, convex_ok ? (n_samples < 1 ? 1 : n_samples) : 0)) return rc;
+                                  const MkhLadderFreeIO* f, const char* who, bool refined) {
+  // (general convex pairs: through the checker's sweep_rows where the call sweeps and nothing else; with refinement through its
+  //  check_rows as well)
+  if (const int32_t rc = sweep_refuse_for(p, ck, who, n_samples < 1 ? 1 : n_samples, refined ? refinement_item(n_samples) : 0)) return rc;
   if (n_samples < 1) return fail(MKH_E_INVALID, "%s: n_samples = %d must be >= 1", who, n_samples);
   if (!f || !f->edge_collision || !f->n_edge_collisions || !f->edge_margin)
     return fail(MKH_E_INVALID, "%s: free_io and its outputs edge_collision, n_edge_collisions, edge_margin are required", who);
@@ -2729,7 +2792,7 @@ int32_t mkh_ladder_select_free(MkhProblem* p, MkhProblem* ck, int32_t B, int32_t
   if (!q || !q_nodes || !tracked) return fail(MKH_E_INVALID, "%s: q, q_nodes and tracked are required", who);
   if (!io || !io->node_index || !io->n_tracked || !io->n_breaks || !io->path_length || !io->edge_break)
     return fail(MKH_E_INVALID, "%s: io and its outputs node_index, n_tracked, n_breaks, path_length, edge_break are required", who);
-  if (const int32_t rc = ladder_free_refuse(p, ck, B, T, S, n_samples, fio, who, true)) return rc;
+  if (const int32_t rc = ladder_free_refuse(p, ck, B, T, S, n_samples, fio, who, false)) return rc;
   if (mkh::ladder_source_tile(S, p->dev.nq, p->dev.nv, p->model->njnt, nullptr, true) < 1)
     return fail(MKH_E_LIMIT, "%s: nq = %d: one destination tile and one source node with its flags do not fit 64 KB of LDS", who, p->dev.nq);
   const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
@@ -2833,7 +2896,7 @@ static int32_t refine_pass(Stager& st, int B, int T, const double* d_q, const do
     mkh::SweepArgs a{};
     a.mode = mkh::kSweepPath; a.M = rf->M; a.T = T; a.W = 1; a.N = (long long)R;
     a.nodes = d_path; a.tracked = p_eff; a.node_index = p_idx; a.margin = p_em;
-    ST_LAUNCH(st, launch_sweep(stream, rf->ck->d_wide, ck_nbody, (int)nq, ck_np, a));
+    sweep_edges(st, rf->ck, a);
     st.latch(hipMemcpyAsync(fw.r_nm, p_nm, 2 * R * f8, hipMemcpyDeviceToDevice, stream));     // (r's state = p's)
   }
   st.latch(hipMemcpyAsync(w.r, d_path, R * nq * f8, hipMemcpyDeviceToDevice, stream));
@@ -2847,7 +2910,22 @@ static int32_t refine_pass(Stager& st, int B, int T, const double* d_q, const do
       ST_LAUNCH(st, launch_lr_step(stream, B, T, (int)nq, (int)nv, njnt, jnt, d_q, d_w, max_step_sq, ct, cdir, nt, ndir, w));
       return;
     }
-    if (ct >= 0) ST_LAUNCH(st, launch_lr_check(stream, rf->ck->d_wide, ck_nbody, (int)nq, ck_np, B, T, rf->M, ct, cdir, w, fw.trip));
+    const MkhProblem* const ck = rf->ck;
+    if (ct >= 0 && ck->cv.n_cv == 0) ST_LAUNCH(st, launch_lr_check(stream, ck->d_wide, ck_nbody, (int)nq, ck_np, B, T, rf->M, ct, cdir, w, fw.trip));
+    if (ct >= 0 && ck->cv.n_cv > 0) {
+      // general convex pairs: chunks of floor(check_rows / (1 + 2M)) instances (>= 1: sweep_refuse), convex_check_kernel — once
+      // for all the slots of the check — then the check on each; the stream orders the reuse of the buffer
+      const long long per = ck->check_rows / (1 + 2 * rf->M);
+      mkh::CvCheckArgs a{};
+      a.mode = mkh::kCvCheckRefine; a.M = rf->M; a.T = T; a.ct = ct; a.cdir = cdir;
+      a.r = w.r; a.x = w.x; a.r_trk = w.r_trk; a.xst = w.xst; a.xcv = w.xcv; a.bad = w.bad;
+      for (a.first = 0; a.first < B && st.ok(); a.first += per) {
+        a.count = B - a.first < per ? B - a.first : per;
+        const mkh::CvChunk c{a.first, a.count, ck->d_cv_check, ck->cv.n_cv};
+        ST_LAUNCH(st, launch_convex_check(stream, ck->d_wide, ck->cv.pair, ck->cv.chain_adr, ck->cv.chain, ck->cv.n_cv, a, ck->d_cv_check));
+        ST_LAUNCH(st, launch_lr_check(stream, ck->d_wide, ck_nbody, (int)nq, ck_np, B, T, rf->M, ct, cdir, w, fw.trip, c));
+      }
+    }
     ST_LAUNCH(st, launch_lr_step_free(stream, B, T, (int)nq, (int)nv, njnt, jnt, d_q, d_w, max_step_sq, ct, cdir, nt, ndir, w, fw));
   };
   auto loop = [&](size_t t) -> int32_t {
@@ -2899,7 +2977,7 @@ static int32_t ladder_refine_call(MkhProblem* p, MkhProblem* ck, int32_t n_sampl
   if (const int32_t rc = refuse_checker(p, who)) return rc;
   if (const int32_t rc = refuse_unwind(flags, who)) return rc;
   if (free_call) {
-    if (const int32_t rc = sweep_refuse_for(p, ck, who)) return rc;
+    if (const int32_t rc = sweep_refuse_for(p, ck, who, n_samples < 1 ? 1 : n_samples, refinement_item(n_samples))) return rc;
     if (n_samples < 1) return fail(MKH_E_INVALID, "%s: n_samples = %d must be >= 1", who, n_samples);
     if (!fio || !fio->edge_collision || !fio->n_edge_collisions || !fio->edge_margin)
       return fail(MKH_E_INVALID, "%s: free_io and its outputs edge_collision, n_edge_collisions, edge_margin are required", who);
@@ -3357,7 +3435,7 @@ static int32_t ladder_free_call(const char* who, bool refined, MkhProblem* p, Mk
                                "the ladder on distinct nodes", who, n_nodes, nodes ? "given" : "NULL");
   const int W = n_nodes ? n_nodes : n_seeds;
   if (B < 1 || T < 1 || W < 1 || W > 256) return fail(MKH_E_INVALID, "%s: B = %d, T = %d and %d nodes per rung: B, T >= 1, 1 <= nodes <= 256", who, B, T, W);
-  if (const int32_t rc = ladder_free_refuse(p, ck, B, T, W, n_samples, fio, who, !refined)) return rc;
+  if (const int32_t rc = ladder_free_refuse(p, ck, B, T, W, n_samples, fio, who, refined)) return rc;
   if (fio->node_margin)
     return fail(MKH_E_INVALID, "%s: node_margin is mkh_ladder_select_free's output: here the nodes' verdict is MKH_ST_IN_COLLISION in status_all", who);
   if (mkh::ladder_source_tile(W, p->dev.nq, p->dev.nv, p->model->njnt, nullptr, true) < 1)

@@ -12,6 +12,15 @@
 
 namespace mkh {
 
+// What launch_tmf_check / launch_lr_check read of a chunk of their items on a checker WITH general convex pairs: its first item,
+// their count, and the distances launch_convex_check (below) left for the chunk.  cv null: all items in one launch — a checker
+// without such pairs, the kernels they always were.
+struct CvChunk {
+  long long first = 0, count = 0;
+  const double* cv = nullptr;
+  int32_t n_cv = 0;
+};
+
 constexpr int kOuterBlock = 256;        // threads per block of every one-thread-per-element kernel of these files
 
 // Blocks of kOuterBlock threads that cover `total` elements; false when the grid would not fit (the launcher then reports
@@ -114,12 +123,13 @@ hipError_t launch_tms_gather_i32(hipStream_t stream, const int32_t* all, int32_t
 // launch_tmf_check judges the T·B·S rows of the time-major candidates q_all in one launch — node_margin_all, MKH_ST_IN_COLLISION
 // OR-ed into status_all, and edge_margin_all: +inf at waypoint 0, the swept margin of the M >= 1 interior samples of the edge from
 // the same candidate's row t − 1 where the row is eligible, NaN elsewhere — on the CHECKER's per-body descriptor (a device
-// WideProblem without general convex pairs; nbody and n_pairs choose the build as in launch_clearance, the LDS is
+// WideProblem; with general convex pairs the rows go in chunks — `chunk`, above — behind launch_convex_check, without a chunk
+// it has none; nbody and n_pairs choose the build as in launch_clearance, the LDS is
 // sweep_lds_bytes').  converged_all absent: every row counts as converged.  launch_tmf_edge_flags: the chosen candidate's
 // edge_collision through the (instance, waypoint) strides of the caller's layout, and n_edge_collisions (B,).
 hipError_t launch_tmf_check(hipStream_t stream, const void* wide_problem, int nbody, int nq, int n_pairs, int B, int S, int T, int M,
                             const double* q_all, const int32_t* converged_all, int32_t* status_all, double* node_margin_all,
-                            double* edge_margin_all);
+                            double* edge_margin_all, const CvChunk& chunk = CvChunk{});
 hipError_t launch_tmf_edge_flags(hipStream_t stream, int B, int S, int T, const int32_t* seed_index, const int32_t* converged_all,
                                  const int32_t* status_all, const double* edge_margin_all, int32_t* edge_collision, long long o_sb,
                                  long long o_st, int32_t* n_edge_collisions);
@@ -171,7 +181,8 @@ hipError_t launch_lr_guard(hipStream_t stream, int B, int T, int nq, int nv, int
 // far edge, NaN: not evaluated or not swept; the samples of an edge are dealt to slots = lr_check_slots(M) blocks, each writes
 // the minimum over its own, the step kernel the minimum over the slots.  LrFreeGuard: both paths' margins, and the returned path's (node_margin: optional).  launch_lr_check
 // runs between the loop launch of waypoint commit_t and the launch_lr_step_free that commits it, on the CHECKER's per-body
-// descriptor (a device WideProblem without general convex pairs; nbody and n_pairs choose the build as in launch_clearance, the
+// descriptor (a device WideProblem; with general convex pairs the instances go in chunks — `chunk`, above — behind
+// launch_convex_check, without a chunk it has none; nbody and n_pairs choose the build as in launch_clearance, the
 // LDS is sweep_lds_bytes'); M >= 1 interior samples per edge.
 constexpr int kLrMaxSlots = 8;
 int lr_check_slots(int M);
@@ -185,7 +196,7 @@ struct LrFreeGuard {
   int32_t *edge_collision, *n_edge_collisions;
 };
 hipError_t launch_lr_check(hipStream_t stream, const void* wide_problem, int nbody, int nq, int n_pairs, int B, int T, int M,
-                           int commit_t, int commit_dir, const LrWork& w, double* trip);
+                           int commit_t, int commit_dir, const LrWork& w, double* trip, const CvChunk& chunk = CvChunk{});
 hipError_t launch_lr_step_free(hipStream_t stream, int B, int T, int nq, int nv, int njnt, const int32_t* jnt, const double* q0,
                                const double* weights, double max_step_sq, int commit_t, int commit_dir, int next_t, int next_dir,
                                const LrWork& w, const LrFreeWork& f);
@@ -235,6 +246,29 @@ hipError_t launch_sweep(hipStream_t stream, const void* wide_problem, int nbody,
 // ipw: items per wavefront, 0 = chosen from the size of the chunk.
 hipError_t launch_convex_sweep(hipStream_t stream, const void* wide_problem, const int32_t* pair, const int32_t* chain_adr,
                                const int32_t* chain, const SweepArgs& a, int ipw);
+// The pre-pass of the checks that judge rows INSIDE their launch (convex_check.hip), for a checker WITH general convex pairs: the
+// distances of those pairs on every row the check of the items [first, first + count) could read — its conditions without the
+// node's verdict —, one lane per (item, row, pair), into row (item − first)·rows_per_item + j of `out` (mkh_problem_set_check_rows).
+//   kCvCheckTrack   launch_tmf_check's rows: item g of the (T, R, nq) candidates, rows_per_item = 1 + M (the node, the M samples
+//                   of the edge from row g − R); status is read as it stands in front of the check.
+//   kCvCheckRefine  launch_lr_check's instances at waypoint ct of a sweep in direction cdir: rows_per_item = 1 + 2M (x, the near
+//                   edge, the far edge).
+// The check of the same chunk then runs with the same first / count and `out` for its cv.
+enum : int32_t { kCvCheckTrack = 0, kCvCheckRefine = 1 };
+struct CvCheckArgs {
+  int32_t mode, M;
+  long long first, count;
+  // kCvCheckTrack
+  long long R;
+  const double* q_all;
+  const int32_t *converged, *status;
+  // kCvCheckRefine
+  int32_t T, ct, cdir;
+  const double *r, *x;
+  const int32_t *r_trk, *xst, *xcv, *bad;
+};
+hipError_t launch_convex_check(hipStream_t stream, const void* wide_problem, const int32_t* pair, const int32_t* chain_adr,
+                               const int32_t* chain, int n_cv, const CvCheckArgs& a, double* out);
 // the nodes of a checked ladder: tracked_out[i] = tracked[i] != 0 && node_margin[i] >= 0
 hipError_t launch_ladder_free_tracked(hipStream_t stream, const int32_t* tracked, const double* node_margin, long long total,
                                       int32_t* tracked_out);

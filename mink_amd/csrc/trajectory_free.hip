@@ -12,6 +12,10 @@
 // behind row 0.  One lane of the group writes the two margins and, for a row in collision, the status word: plain vector
 // stores, no atomics, no scratch.
 //
+// A checker's general convex pairs: convex_check_kernel (convex_check.hip) runs in front on a chunk of rows and leaves their
+// distances on the node and on every sample this kernel could read; tmf_check_cv_kernel then takes the chunk (a first-row offset
+// into the call's rows) and clr_row reads them.
+//
 // dynamic LDS, per group: poses (7, nbody) | q(u) (nq) | a (nq) | b ⊖ a (nq) doubles
 #include <hip/hip_runtime.h>
 
@@ -24,7 +28,7 @@ namespace mkh {
 
 // What the kernel reads of a launch (kernel arguments live in scalar registers across the whole sample loop: as few as it takes).
 struct TmfKernelArgs {
-  long long N, R;                  // rows T·B·S, rows per waypoint B·S
+  long long N, R;                  // rows of this launch (T·B·S, or a chunk of them), rows per waypoint B·S
   int32_t M;
   const double* q_all;             // (T, R, nq)
   const int32_t* converged;        // (T, R), or null: every row counts as converged
@@ -39,8 +43,12 @@ __device__ __forceinline__ bool tmf_group_any(bool x, int grp) {
   return (LPR == 64 ? bb : (bb >> (grp * LPR)) & ((1ull << (LPR & 63)) - 1ull)) != 0ull;
 }
 
-template <int LPR>
-__global__ __launch_bounds__(64) void tmf_check_kernel(const WideProblem* __restrict__ Pg, const TmfKernelArgs a) {
+// CV: the build for a checker WITH general convex pairs (tmf_check_cv_kernel below) — a chunk of the call's rows (a.N of them
+// from row c.first) and the distances convex_check_kernel left for the chunk, row j of a chunk's item its walk's row j.  Without:
+// tmf_check_kernel, which reads neither and is the kernel it was.  (Pg without __restrict__ here: the kernels' parameter carries
+// it, and a second one on the inlined body's changes what the compiler may reorder — tmf_check_kernel<64> then spilled 8 SGPRs.)
+template <int LPR, bool CV>
+__device__ __forceinline__ void tmf_check_body(const WideProblem* Pg, const TmfKernelArgs& a, const CvChunk& c) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   constexpr int RPW = kWave / LPR;                             // rows per wavefront
   const WideProblem& P = *Pg;
@@ -48,7 +56,7 @@ __global__ __launch_bounds__(64) void tmf_check_kernel(const WideProblem* __rest
   const int nbody = P.nbody, nq = P.nq;
   const long long g_raw = (long long)blockIdx.x * RPW + grp;
   const bool live = g_raw < a.N;                               // (a row past the end repeats the last one and writes nothing)
-  const long long g = live ? g_raw : a.N - 1;
+  const long long g_in = live ? g_raw : a.N - 1, g = CV ? c.first + g_in : g_in;     // its place in this launch, and in the call
   const bool first = g < a.R;                                  // waypoint 0: the start edge is never swept
   const double* const pb = a.q_all + (size_t)g * nq;
   const double* const pa = first ? pb : pb - (size_t)a.R * nq;       // (a row of waypoint 0 walks its own node: every address is valid)
@@ -63,6 +71,14 @@ __global__ __launch_bounds__(64) void tmf_check_kernel(const WideProblem* __rest
   double* oe = writer ? a.edge_margin + g : nullptr;
   int32_t* os = writer ? a.status + g : nullptr;
   asm volatile("" : "+v"(on), "+v"(oe), "+v"(os), "+v"(st), "+v"(may_sweep));
+  // (general convex pairs: the same treatment — the buffer and its width stay out of the loop's scalar registers)
+  const double* cve = nullptr;
+  int n_cv = 0;
+  if constexpr (CV) {
+    cve = c.cv + (size_t)g_in * (a.M + 1) * c.n_cv;
+    n_cv = c.n_cv;
+    asm volatile("" : "+v"(cve), "+v"(n_cv));
+  }
   double* const sX = smem + (size_t)grp * (7 * nbody + 3 * nq);
   double *const sQ = sX + 7 * nbody, *const sA = sQ + nq, *const sD = sA + nq;
   // ---- a row with a NaN or an infinite entry: its node is NaN, and so is every sample of an edge that touches it
@@ -92,7 +108,7 @@ __global__ __launch_bounds__(64) void tmf_check_kernel(const WideProblem* __rest
   asm volatile("" : "+s"(row0));
 #pragma unroll 1
   for (int i = 0; i <= a.M; ++i) {
-    const ClrRow r = clr_row<LPR>(P, sX, sQ, (bad & (i == row0 ? 1 : 2)) != 0, sub, grp, 0, nullptr, 0, nullptr);
+    const ClrRow r = clr_row<LPR, CV ? 1 : 7>(P, sX, sQ, (bad & (i == row0 ? 1 : 2)) != 0, sub, grp, n_cv, cve, CV ? (size_t)i : 0, nullptr);
     wave_sync();                                               // (the next row's q(u) and poses overwrite what the pairs read)
     if (i == row0) {
       node = r.margin;
@@ -109,6 +125,16 @@ __global__ __launch_bounds__(64) void tmf_check_kernel(const WideProblem* __rest
   if (on) *on = node;
   if (oe) *oe = edge;
   if (os && !(node >= 0.0)) *os = st | kStInCollision;
+}
+
+template <int LPR>
+__global__ __launch_bounds__(64) void tmf_check_kernel(const WideProblem* __restrict__ Pg, const TmfKernelArgs a) {
+  tmf_check_body<LPR, false>(Pg, a, CvChunk{});
+}
+
+template <int LPR>
+__global__ __launch_bounds__(64) void tmf_check_cv_kernel(const WideProblem* __restrict__ Pg, const TmfKernelArgs a, const CvChunk c) {
+  tmf_check_body<LPR, true>(Pg, a, c);
 }
 
 // edge_collision[b, t] = t >= 1 && swept && !(edge_margin >= 0) of the chosen candidate, through the (instance, waypoint) strides
@@ -135,16 +161,25 @@ __global__ __launch_bounds__(256) void tmf_edge_flags_kernel(int B, int S, int T
 
 hipError_t launch_tmf_check(hipStream_t stream, const void* wide_problem, int nbody, int nq, int n_pairs, int B, int S, int T, int M,
                             const double* q_all, const int32_t* converged_all, int32_t* status_all, double* node_margin_all,
-                            double* edge_margin_all) {
+                            double* edge_margin_all, const CvChunk& chunk) {
   const bool quarter = nbody <= 32 && n_pairs <= 32;
   const size_t lds = sweep_lds_bytes(nbody, nq, n_pairs);
   const long long R = (long long)B * S, N = R * T;
-  const long long blocks = quarter ? (N + 3) / 4 : N;
+  // (a chunk and the general convex pairs' distances come together or not at all)
+  if ((chunk.cv != nullptr) != (chunk.n_cv > 0) || (chunk.cv != nullptr) != (chunk.count > 0) || chunk.first < 0 || chunk.count < 0 ||
+      chunk.first + chunk.count > N)
+    return hipErrorInvalidValue;
+  const long long n = chunk.cv ? chunk.count : N, blocks = quarter ? (n + 3) / 4 : n;
   if (B < 1 || S < 1 || T < 1 || M < 1 || n_pairs < 1 || lds > 64 * 1024 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
   if (!q_all || !status_all || !node_margin_all || !edge_margin_all) return hipErrorInvalidValue;
   const WideProblem* const P = (const WideProblem*)wide_problem;
-  const TmfKernelArgs k{N, R, M, q_all, converged_all, status_all, node_margin_all, edge_margin_all};
-  if (quarter)
+  const TmfKernelArgs k{n, R, M, q_all, converged_all, status_all, node_margin_all, edge_margin_all};
+  if (chunk.cv) {
+    if (quarter)
+      hipLaunchKernelGGL(tmf_check_cv_kernel<16>, dim3((unsigned)blocks), dim3(kWave), lds, stream, P, k, chunk);
+    else
+      hipLaunchKernelGGL(tmf_check_cv_kernel<64>, dim3((unsigned)blocks), dim3(kWave), lds, stream, P, k, chunk);
+  } else if (quarter)
     hipLaunchKernelGGL(tmf_check_kernel<16>, dim3((unsigned)blocks), dim3(kWave), lds, stream, P, k);
   else
     hipLaunchKernelGGL(tmf_check_kernel<64>, dim3((unsigned)blocks), dim3(kWave), lds, stream, P, k);

@@ -718,9 +718,18 @@ class CollisionChecker:
     cylinder-cylinder, ellipsoids, mesh hulls): a device buffer for the distances of those pairs at `sweep_rows` swept samples,
     8 bytes per such pair and sample.  Such a call walks its edges in chunks of sweep_rows // n_samples edges; the results do
     not depend on the value, which must be at least the call's samples per edge.  0, the default: those calls refuse such a
-    checker.  A checker of analytic pairs alone never needs it."""
+    checker.  A checker of analytic pairs alone never needs it.
 
-    def __init__(self, model, limits: Sequence, max_rows: int = 65536, sweep_rows: int = 0):
+    `check_rows`: what the calls that judge rows they produce themselves — candidate_path and
+    solve_ik_trajectory_multistart with `collision_check=`, refine_path with `collision_check=` and
+    solve_ik_trajectory_ladder(refine="free") — need of such a checker: a second device buffer, for the distances of those pairs
+    on `check_rows` judged rows (a node, or a sample of an edge into it), 8 bytes per such pair and row.  Candidate tracking needs
+    check_rows >= 1 + edge_samples and judges its candidate rows in chunks of check_rows // (1 + edge_samples); the two
+    refinement calls need check_rows >= 1 + 2 edge_samples AND sweep_rows >= edge_samples and judge the loop results of a
+    waypoint step in chunks of check_rows // (1 + 2 edge_samples).  The results do not depend on the value.  0, the default:
+    those calls refuse such a checker.  A checker of analytic pairs alone never needs it."""
+
+    def __init__(self, model, limits: Sequence, max_rows: int = 65536, sweep_rows: int = 0, check_rows: int = 0):
         import threading
         from .configuration import as_flat_model
         from .limits import CollisionAvoidanceLimit
@@ -749,6 +758,9 @@ class CollisionChecker:
         if isinstance(sweep_rows, bool) or not isinstance(sweep_rows, (int, np.integer)) or int(sweep_rows) < 0:
             raise ValueError(f"sweep_rows must be an int >= 0, got {sweep_rows!r}")
         self.sweep_rows = int(sweep_rows)
+        if isinstance(check_rows, bool) or not isinstance(check_rows, (int, np.integer)) or int(check_rows) < 0:
+            raise ValueError(f"check_rows must be an int >= 0, got {check_rows!r}")
+        self.check_rows = int(check_rows)
         self._handles = {}                 # id(NativeModel) → (NativeModel, NativeProblem)
         self._lock = threading.Lock()
         self._closed = False
@@ -760,12 +772,14 @@ class CollisionChecker:
             hit = self._handles.get(id(nmodel))
             if hit is None:
                 prob = nat.NativeProblem(nmodel, collision_limits=self._descs, max_batch=self.max_rows)
-                if self.sweep_rows:
-                    try:
+                try:
+                    if self.sweep_rows:
                         prob.set_sweep_rows(self.sweep_rows)
-                    except Exception:
-                        prob.close()
-                        raise
+                    if self.check_rows:
+                        prob.set_check_rows(self.check_rows)
+                except Exception:
+                    prob.close()
+                    raise
                 hit = self._handles[id(nmodel)] = (nmodel, prob)
             return hit[1]
 
@@ -1476,8 +1490,10 @@ def solve_ik_trajectory_multistart(configuration: Configuration, tasks: Sequence
     gets ST_IN_COLLISION and does not count), the motion into every row that still counts is swept from the same candidate's
     previous row with `edge_samples` interior samples (CollisionChecker.swept_clearance's rule; the first motion, from the
     configuration's q, is never swept), and a waypoint entered by a colliding motion does not count either.  Count, length and
-    ties then decide as above.  The result is a FreeTrajectoryMultistartResult.  Without collision_check the call is the one
-    above, unchanged."""
+    ties then decide as above.  The result is a FreeTrajectoryMultistartResult.  A checker with general convex pairs
+    (cylinder-box, ellipsoids, mesh hulls) needs its `check_rows` >= 1 + edge_samples: the rows are then judged in chunks of
+    check_rows // (1 + edge_samples), and the result does not depend on the value.  Without collision_check the call is the
+    one above, unchanged."""
     del solver
     _check_collision_check(collision_check, configuration, edge_samples)
     S, n_steps = _loop_scalars(max_instances, n_seeds, loop="n_steps", length=n_steps, step=waypoint_dt,
@@ -1562,7 +1578,9 @@ def candidate_path(configuration: Configuration, q_paths, tracked=None, weights=
 
     `collision_check` (a CollisionChecker of the same model): every row is checked on the device and a row in collision does
     not count; the motion into every row that still counts is swept from the same candidate's previous row with `edge_samples`
-    interior samples, and a waypoint entered by a colliding motion does not count.  The result is then a FreeCandidatePath."""
+    interior samples, and a waypoint entered by a colliding motion does not count.  The result is then a FreeCandidatePath.
+    A checker with general convex pairs (cylinder-box, ellipsoids, mesh hulls) needs its `check_rows` >= 1 + edge_samples; the
+    rows are then judged in chunks of check_rows // (1 + edge_samples), and the result does not depend on the value."""
     from .tasks import PostureTask
 
     _check_collision_check(collision_check, configuration, edge_samples)
@@ -1760,8 +1778,9 @@ def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt
     swept with `edge_samples` interior samples and the search counts a waypoint entered by a colliding motion as lost (ladder_path
     states the rule).  The result is a FreeLadderResult / FreeLadderNodesResult: the fields above and `edge_collision`,
     `n_edge_collisions`, `edge_margin`.  A checker with general convex pairs (cylinder-box, ellipsoids, mesh hulls) needs its
-    `sweep_rows` >= edge_samples, with and without n_nodes — and is still refused together with refine="free".  Without
-    collision_check the call takes exactly the path described above.
+    `sweep_rows` >= edge_samples, with and without n_nodes — and together with refine="free" its `check_rows` >=
+    1 + 2 edge_samples as well (refine_path's condition).  Without collision_check the call takes exactly the path described
+    above.
 
     `refine="free"` (with collision_check only) runs refine_path(collision_check=...)'s pass behind the checked search, in the
     same call on the device: lost waypoints, breaks and waypoints entered by a colliding motion are re-solved from their
@@ -1895,7 +1914,10 @@ def refine_path(configuration: Configuration, tasks: Sequence, dt: float, target
     counts as not tracked and a waypoint entered by a colliding motion as lost (ladder_path's rule, `edge_samples` interior
     samples per motion) — both are bad and get re-solved; a result is taken only when it is itself free of collision and the
     motion from the neighbour is; the motion on its other side is swept anew, and the key that decides which path comes back
-    counts all of it.  Everything is checked on the device between the loops.  The result is then a FreeRefinedPath.  Without
+    counts all of it.  Everything is checked on the device between the loops.  The result is then a FreeRefinedPath.  A
+    checker with general convex pairs (cylinder-box, ellipsoids, mesh hulls) needs its `check_rows` >= 1 + 2 edge_samples AND its
+    `sweep_rows` >= edge_samples (the pass sweeps the incoming path); the loop results of a waypoint step are then judged in
+    chunks of check_rows // (1 + 2 edge_samples) instances, and the result does not depend on either value.  Without
     collision_check the call is the one above, unchanged."""
     del solver
     _check_collision_check(collision_check, configuration, edge_samples)
