@@ -108,6 +108,32 @@ VARIANTS = tuple([Variant(nt, ft) for nt in NTS for ft in FEATS]
                  + [Variant(nt, ft, w3=True) for nt, ft in W3]
                  + [Variant(nt, ft, nr, w3=True) for nt, nr, ft in W3_WOOD]
                  + [(VariantW4 if e[3:] == ("w4",) else Variant)(e[0], e[2], e[1], w3=True, one_shot=True) for e in W3_WOOD_ONE_SHOT])
+# the hand-written translation units behind the generated ones, in link order: (name, what it holds)
+HAND_WRITTEN = (
+    ("minkhip", "host side of the C ABI: handles, the solve path, the outer-loop entry points"),
+    ("checker_host", "host side of the collision checker: its entry points and the stages of the checked calls (host code only)"),
+    ("problem_plan", "host-only planning of models and problems (no HIP runtime call)"),
+    ("lane_variants", "the lane-per-problem and row-per-problem kernels of small arms"),
+    ("wide_variants", "the workgroup-per-problem kernel"),
+    ("convex_pre", "convex_contacts_kernel: general convex pairs in front of a plain solve or a clearance"),
+    ("multistart", "seeding / fan-out / selection of mkh_solve_multistart"),
+    ("solution_set", "distinct-set selection of mkh_solve_multistart_set / mkh_select_distinct (same flags as multistart.hip: d_ref is bitwise multi-start's)"),
+    ("goalset", "two-level selection of mkh_solve_goalset / mkh_select_goalset (same flags as multistart.hip: d_ref is bitwise multi-start's)"),
+    ("seed_table", "key layout / K-nearest query of mkh_seed_table_*"),
+    ("trajectory", "layout transposes / waypoint velocity of mkh_solve_trajectory"),
+    ("keyframes", "target blends between keyframes of mkh_solve_keyframes"),
+    ("trajectory_multistart", "path scoring / selection / gather of mkh_solve_trajectory_multistart"),
+    ("ladder", "dynamic program / back-trace / gather of mkh_ladder_select and mkh_solve_trajectory_ladder"),
+    ("ladder_refine", "step / guard kernels of mkh_ladder_refine"),
+    ("unwind", "turn unwinding of mkh_unwind_turns / MKH_FLAG_UNWIND_TURNS"),
+    ("ladder_nodes", "node flags of mkh_solve_trajectory_ladder_nodes"),
+    ("clearance", "clearance of a batch of rows: mkh_clearance, the collision check behind the multi-start loops"),
+    ("ladder_refine_free", "lr_check_kernel: the collision check between the loops of mkh_ladder_refine_free"),
+    ("sweep", "swept clearance of edges: mkh_swept_clearance, the edge mask of the checked ladder calls"),
+    ("convex_sweep", "convex_sweep_kernel: the general convex pairs of a sweep's samples, in front of sweep_kernel (convex_pre.hip's flags)"),
+    ("convex_check", "convex_check_kernel: the general convex pairs of the rows tmf_check_cv_kernel / lr_check_cv_kernel judge inside their launch (convex_sweep.hip's flags)"),
+    ("trajectory_free", "tmf_check_kernel: nodes and edges of mkh_solve_trajectory_multistart_free / mkh_select_trajectory_candidates (sweep.hip's flags)"),
+)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-null-conversion"]
 # experiments: extra compiler flags for every translation unit (e.g. MKH_EXTRA_FLAGS="-DMKH_FORCE_COLL_CALL"); part of the
 # per-object command tag, so changing it recompiles
@@ -312,28 +338,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     hipcc = _hipcc()
     srcs = _generate()
     jobs = [(os.path.join(BUILD, s + ".hip"), os.path.join(BUILD, s + ".o")) for s in srcs]
-    jobs.append((os.path.join(HERE, "minkhip.hip"), os.path.join(BUILD, "minkhip.o")))
-    jobs.append((os.path.join(HERE, "problem_plan.hip"), os.path.join(BUILD, "problem_plan.o")))   # host-only planning of models and problems (no HIP runtime call)
-    jobs.append((os.path.join(HERE, "lane_variants.hip"), os.path.join(BUILD, "lane_variants.o")))
-    jobs.append((os.path.join(HERE, "wide_variants.hip"), os.path.join(BUILD, "wide_variants.o")))
-    jobs.append((os.path.join(HERE, "convex_pre.hip"), os.path.join(BUILD, "convex_pre.o")))
-    jobs.append((os.path.join(HERE, "multistart.hip"), os.path.join(BUILD, "multistart.o")))   # seeding / fan-out / selection of mkh_solve_multistart
-    jobs.append((os.path.join(HERE, "solution_set.hip"), os.path.join(BUILD, "solution_set.o")))   # distinct-set selection of mkh_solve_multistart_set / mkh_select_distinct (same flags as multistart.hip: d_ref is bitwise multi-start's)
-    jobs.append((os.path.join(HERE, "goalset.hip"), os.path.join(BUILD, "goalset.o")))   # two-level selection of mkh_solve_goalset / mkh_select_goalset (same flags as multistart.hip: d_ref is bitwise multi-start's)
-    jobs.append((os.path.join(HERE, "seed_table.hip"),os.path.join(BUILD, "seed_table.o")))   # key layout / K-nearest query of mkh_seed_table_*
-    jobs.append((os.path.join(HERE, "trajectory.hip"), os.path.join(BUILD, "trajectory.o")))   # layout transposes / waypoint velocity of mkh_solve_trajectory
-    jobs.append((os.path.join(HERE, "keyframes.hip"), os.path.join(BUILD, "keyframes.o")))     # target blends between keyframes of mkh_solve_keyframes
-    jobs.append((os.path.join(HERE, "trajectory_multistart.hip"), os.path.join(BUILD, "trajectory_multistart.o")))   # path scoring / selection / gather of mkh_solve_trajectory_multistart
-    jobs.append((os.path.join(HERE, "ladder.hip"), os.path.join(BUILD, "ladder.o")))   # dynamic program / back-trace / gather of mkh_ladder_select and mkh_solve_trajectory_ladder
-    jobs.append((os.path.join(HERE, "ladder_refine.hip"), os.path.join(BUILD, "ladder_refine.o")))   # step / guard kernels of mkh_ladder_refine
-    jobs.append((os.path.join(HERE, "unwind.hip"), os.path.join(BUILD, "unwind.o")))   # turn unwinding of mkh_unwind_turns / MKH_FLAG_UNWIND_TURNS
-    jobs.append((os.path.join(HERE, "ladder_nodes.hip"), os.path.join(BUILD, "ladder_nodes.o")))   # node flags of mkh_solve_trajectory_ladder_nodes
-    jobs.append((os.path.join(HERE, "clearance.hip"), os.path.join(BUILD, "clearance.o")))   # clearance of a batch of rows: mkh_clearance, the collision check behind the multi-start loops
-    jobs.append((os.path.join(HERE, "ladder_refine_free.hip"), os.path.join(BUILD, "ladder_refine_free.o")))   # lr_check_kernel: the collision check between the loops of mkh_ladder_refine_free
-    jobs.append((os.path.join(HERE, "sweep.hip"), os.path.join(BUILD, "sweep.o")))   # swept clearance of edges: mkh_swept_clearance, the edge mask of the checked ladder calls
-    jobs.append((os.path.join(HERE, "convex_sweep.hip"), os.path.join(BUILD, "convex_sweep.o")))   # convex_sweep_kernel: the general convex pairs of a sweep's samples, in front of sweep_kernel (convex_pre.hip's flags)
-    jobs.append((os.path.join(HERE, "convex_check.hip"), os.path.join(BUILD, "convex_check.o")))   # convex_check_kernel: the general convex pairs of the rows tmf_check_cv_kernel / lr_check_cv_kernel judge inside their launch (convex_sweep.hip's flags)
-    jobs.append((os.path.join(HERE, "trajectory_free.hip"), os.path.join(BUILD, "trajectory_free.o")))   # tmf_check_kernel: nodes and edges of mkh_solve_trajectory_multistart_free / mkh_select_trajectory_candidates (sweep.hip's flags)
+    jobs += [(os.path.join(HERE, name + ".hip"), os.path.join(BUILD, name + ".o")) for name, _ in HAND_WRITTEN]
 
     def compile_one(job):
         src, obj = job

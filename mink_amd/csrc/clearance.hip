@@ -13,6 +13,7 @@
 // The row body — FK, pair loop, key reduction — is clr_row of clearance_row.h, which sweep.hip runs on the samples of an edge.
 #include <hip/hip_runtime.h>
 
+#include "checker_plan.h"
 #include "clearance_row.h"
 #include "outer_launch.h"
 
@@ -56,9 +57,8 @@ __global__ __launch_bounds__(64) void clearance_kernel(const WideProblem* __rest
 // null).  `cv`: the (N, n_cv, 7) records of convex_contacts_kernel on the same rows.  At least one pair.
 hipError_t launch_clearance(hipStream_t stream, const void* wide_problem, int nbody, int n_pairs, int n_cv, const double* cv, int N,
                             const double* q, double* margin, int32_t* pair, int32_t* n_violated, double* distance, int32_t* status) {
-  // four rows per wavefront where a quarter of one holds a row's bodies and pairs in a trip or two
-  const bool quarter = nbody <= 32 && n_pairs <= 32;
-  const size_t lds = (size_t)(quarter ? 4 : 1) * 7 * (size_t)nbody * sizeof(double);
+  const bool quarter = checker_quarter(nbody, n_pairs);        // (four rows per wavefront or one, and their poses in LDS: checker_plan.h)
+  const size_t lds = clearance_lds_bytes(nbody, n_pairs);
   if (N < 1 || n_pairs < 1 || lds > 64 * 1024) return hipErrorInvalidValue;
   const WideProblem* const P = (const WideProblem*)wide_problem;
   if (quarter)

@@ -1,6 +1,8 @@
 // The kinematic chains of a checker's general convex pairs and the walk down one of them — shared by convex_contacts_kernel
 // (convex_pre.hip: rows of q in memory) and convex_sweep_kernel (convex_sweep.hip: rows of q blended between the two ends of an
-// edge, joint by joint, as the walk asks for them).
+// edge, joint by joint, as the walk asks for them).  CvPre, the lists themselves, is defined here once: the handle keeps one
+// (host_internal.h) and the three pre-pass launchers take it (launch_convex_pre below; launch_convex_sweep and
+// launch_convex_check in outer_launch.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,6 +18,9 @@ struct CvPre {
   const int32_t* chain_adr;  // [2·n_cv + 1]: bodies root → body1 of convex pair k at [chain_adr[2k], chain_adr[2k+1]), → body2 behind
   const int32_t* chain;      // body ids
 };
+
+// convex_pre.hip: (dist, from, to) of every (row, general convex pair) of B rows of q, (B, n_cv, 7) into `out`
+hipError_t launch_convex_pre(hipStream_t stream, const WideProblem* P, const CvPre& C, int B, const double* q, double* out);
 
 // A row of q in memory, as the walk reads it: a scalar joint's coordinate, a free joint's position, a quaternion.
 struct CvRowMem {

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #define MKH_POLISH_BY_VALUE 1      // (convex_dev.h cvx_polish: this kernel carries the routine without scratch)
+#include "checker_plan.h"
 #include "convex_lane.h"
 #include "outer_launch.h"
 #include "problem_plan.h"
@@ -114,8 +115,8 @@ __global__ __launch_bounds__(64) void convex_check_kernel(const WideProblem* __r
   if (want) out[item] = dist;
 }
 
-hipError_t launch_convex_check(hipStream_t stream, const void* wide_problem, const int32_t* pair, const int32_t* chain_adr,
-                               const int32_t* chain, int n_cv, const CvCheckArgs& a, double* out) {
+hipError_t launch_convex_check(hipStream_t stream, const void* wide_problem, const CvPre& C, const CvCheckArgs& a, double* out) {
+  const int n_cv = C.n_cv;
   if (a.count < 1 || a.first < 0 || a.M < 1 || n_cv < 1 || !out) return hipErrorInvalidValue;
   if (a.mode == kCvCheckTrack) {
     if (a.R < 1 || !a.q_all || !a.status) return hipErrorInvalidValue;
@@ -124,16 +125,12 @@ hipError_t launch_convex_check(hipStream_t stream, const void* wide_problem, con
   } else {
     return hipErrorInvalidValue;
   }
-  const CvPre C{n_cv, pair, chain_adr, chain};
   const long long rpi = a.mode == kCvCheckTrack ? 1 + (long long)a.M : 1 + 2 * (long long)a.M;
   const long long total = a.count * rpi * n_cv;
-  // ≈ 4 096 wavefronts when the chunk allows, at most 64 items each (launch_convex_pre's rule)
-  long long ipw = (total + 4095) / 4096;
-  if (ipw < 1) ipw = 1;
-  if (ipw > 64) ipw = 64;
+  const int ipw = cv_items_per_wave(total);
   const long long blocks = (total + ipw - 1) / ipw;
   if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(convex_check_kernel, dim3((unsigned)blocks), dim3(64), 0, stream, (const WideProblem*)wide_problem, C, a, (int)ipw, out);
+  hipLaunchKernelGGL(convex_check_kernel, dim3((unsigned)blocks), dim3(64), 0, stream, (const WideProblem*)wide_problem, C, a, ipw, out);
   return hipGetLastError();
 }
 

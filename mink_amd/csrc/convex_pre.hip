@@ -13,6 +13,7 @@
 
 #include "mkh_types.h"
 #include "wave_ops.h"
+#include "checker_plan.h"
 #include "collide_dev.h"
 #include "convex_chain.h"
 #include "problem_plan.h"
@@ -89,15 +90,11 @@ __global__ __launch_bounds__(64) void convex_contacts_kernel(const WideProblem* 
   }
 }
 
-// returns 0 or the HIP error of the launch
-int launch_convex_pre(hipStream_t stream, const WideProblem* P, const CvPre& C, int B, const double* q, double* out) {
+hipError_t launch_convex_pre(hipStream_t stream, const WideProblem* P, const CvPre& C, int B, const double* q, double* out) {
   const long long total = (long long)B * C.n_cv;
-  // ≈ 4 096 wavefronts when the batch allows (2 resident per SIMD x 1 024 SIMDs, twice over), at most 64 items each
-  long long ipw = (total + 4095) / 4096;
-  if (ipw < 1) ipw = 1;
-  if (ipw > 64) ipw = 64;
-  hipLaunchKernelGGL(convex_contacts_kernel, dim3((unsigned)((total + ipw - 1) / ipw)), dim3(64), 0, stream, P, C, B, (int)ipw, q, out);
-  return (int)hipGetLastError();
+  const int ipw = cv_items_per_wave(total);
+  hipLaunchKernelGGL(convex_contacts_kernel, dim3((unsigned)((total + ipw - 1) / ipw)), dim3(64), 0, stream, P, C, B, ipw, q, out);
+  return hipGetLastError();
 }
 
 }  // namespace mkh

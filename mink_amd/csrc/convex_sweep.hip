@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #define MKH_POLISH_BY_VALUE 1      // (convex_dev.h cvx_polish: this kernel carries the routine without scratch)
+#include "checker_plan.h"
 #include "convex_lane.h"
 #include "problem_plan.h"
 #include "sweep_edge.h"
@@ -52,18 +53,12 @@ __global__ __launch_bounds__(64) void convex_sweep_kernel(const WideProblem* __r
   if (want) out[item] = dist;
 }
 
-hipError_t launch_convex_sweep(hipStream_t stream, const void* wide_problem, const int32_t* pair, const int32_t* chain_adr,
-                               const int32_t* chain, const SweepArgs& a, int ipw) {
-  if (a.count < 1 || a.first < 0 || a.first + a.count > a.N || a.M < 1 || a.n_cv < 1 || !a.cv) return hipErrorInvalidValue;
+hipError_t launch_convex_sweep(hipStream_t stream, const void* wide_problem, const CvPre& C, const SweepArgs& a, int ipw) {
+  if (a.count < 1 || a.first < 0 || a.first + a.count > a.N || a.M < 1 || a.n_cv < 1 || C.n_cv != a.n_cv || !a.cv) return hipErrorInvalidValue;
   const SweepKernelArgs k = sweep_kernel_args(a);
-  const CvPre C{a.n_cv, pair, chain_adr, chain};
   const long long total = a.count * a.M * a.n_cv;
-  // ≈ 4 096 wavefronts when the chunk allows, at most 64 items each (launch_convex_pre's choice, measured again here:
-  // docs/HISTORY.md)
-  if (ipw < 1) {
-    const long long w = (total + 4095) / 4096;
-    ipw = (int)(w < 1 ? 1 : (w > 64 ? 64 : w));
-  }
+  // (launch_convex_pre's choice, measured again here: docs/HISTORY.md)
+  if (ipw < 1) ipw = cv_items_per_wave(total);
   if (ipw > 64) ipw = 64;
   const long long blocks = (total + ipw - 1) / ipw;
   if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;

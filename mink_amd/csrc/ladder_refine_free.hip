@@ -21,6 +21,7 @@
 // dynamic LDS, per group: poses (7, nbody) | q(u) (nq) | a (nq) | b ⊖ a (nq) doubles
 #include <hip/hip_runtime.h>
 
+#include "checker_plan.h"
 #include "clearance_row.h"
 #include "lie_dev.h"
 #include "outer_launch.h"
@@ -144,7 +145,7 @@ int lr_check_slots(int M) { return M < kLrMaxSlots ? (M < 1 ? 1 : M) : kLrMaxSlo
 
 hipError_t launch_lr_check(hipStream_t stream, const void* wide_problem, int nbody, int nq, int n_pairs, int B, int T, int M,
                            int commit_t, int commit_dir, const LrWork& w, double* trip, const CvChunk& chunk) {
-  const bool quarter = nbody <= 32 && n_pairs <= 32;
+  const bool quarter = checker_quarter(nbody, n_pairs);
   const size_t lds = sweep_lds_bytes(nbody, nq, n_pairs);
   if (B < 1 || T < 1 || M < 1 || n_pairs < 1 || lds > 64 * 1024 || commit_t < 0 || commit_t >= T) return hipErrorInvalidValue;
   if (commit_dir < 0 && commit_t > T - 2) return hipErrorInvalidValue;       // (a backward step reads t + 1)

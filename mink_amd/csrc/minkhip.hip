@@ -19,14 +19,14 @@
 #include <type_traits>
 #include <vector>
 
+#include "checker_host.h"
 #include "collide_dev.h"
+#include "host_internal.h"
 #include "lie_dev.h"
 #include "outer_launch.h"
 #include "problem_plan.h"
 
 namespace mkh {
-struct CvPre { int32_t n_cv; const int32_t* pair; const int32_t* chain_adr; const int32_t* chain; };     // (convex_pre.hip)
-
 // q_out = q ⊕ v·dt (mj_integratePos; Configuration.integrate, mink/configuration.py:214-226).
 // One thread per (problem, joint).
 __global__ __launch_bounds__(256) void integrate_kernel(const DeviceProblem P, int B, const double* __restrict__ q,
@@ -57,24 +57,10 @@ __global__ __launch_bounds__(256) void integrate_kernel(const DeviceProblem P, i
   Q4 r = qmul(q0, qr);
   qo[qa] = r.w; qo[qa + 1] = r.x; qo[qa + 2] = r.y; qo[qa + 3] = r.z;
 }
-}
-using namespace mkh;
 
-// Experiment switches (A/B runs, sweeps, phase censuses): environment variables MKH_DEBUG_* that change kernel selection, launch
-// shapes or caps.  They exist only in builds made with -DMKH_DEBUG_SWITCHES (MKH_EXTRA_FLAGS=-DMKH_DEBUG_SWITCHES python -m
-// mink_amd.csrc.build, normally under an MKH_BUILD_TAG): the product library never reads the environment, so a stray variable
-// cannot change a production handle's results or speed (round-5 review).  The four switches the parity tests and bench.py need
-// are per-handle diagnostic options of the ABI instead: mkh_problem_create_diag, MKH_DIAG_*.
-#if defined(MKH_CLOCKS) && !defined(MKH_DEBUG_SWITCHES)
-#define MKH_DEBUG_SWITCHES 1     // (a clock build is an experiment build: MKH_DEBUG_CLOCKS / MKH_DEBUG_PHASE_STOP drive its stamps)
-#endif
-#ifdef MKH_DEBUG_SWITCHES
-static inline const char* dbg_env(const char* name) { return getenv(name); }
-#else
-static inline const char* dbg_env(const char*) { return nullptr; }
-#endif
-static thread_local std::string g_err;
-static int32_t fail(int32_t code, const char* fmt, ...) {
+// mkh_last_error's text and its writer (host_internal.h)
+thread_local std::string g_err;
+int32_t fail(int32_t code, const char* fmt, ...) {
   char buf[512];
   va_list ap;
   va_start(ap, fmt);
@@ -83,6 +69,9 @@ static int32_t fail(int32_t code, const char* fmt, ...) {
   g_err = buf;
   return code;
 }
+}
+using namespace mkh;
+
 // MKH_FLAG_UNWIND_TURNS in front of an entry point that has no distinct-set selection to unwind for (include/minkhip.h).
 static int32_t refuse_unwind(int32_t flags, const char* who) {
   if (flags & MKH_FLAG_UNWIND_TURNS)
@@ -90,12 +79,6 @@ static int32_t refuse_unwind(int32_t flags, const char* who) {
                                "mkh_solve_trajectory_ladder_nodes only", who);
   return MKH_OK;
 }
-#define HIP_OK(expr)                                                                             \
-  do {                                                                                           \
-    hipError_t e_ = (expr);                                                                      \
-    if (e_ != hipSuccess) return fail(MKH_E_HIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                                      __FILE__, __LINE__);                                       \
-  } while (0)
 
 template <class T>
 static hipError_t upload(const std::vector<T>& h, T** d) {
@@ -106,162 +89,6 @@ static hipError_t upload(const std::vector<T>& h, T** d) {
   if (!h.empty()) e = hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
   return e;
 }
-
-// Small host-pointer calls (a control loop's single configuration: the reference's everyday use) go through ONE pinned,
-// device-visible host buffer: the kernel reads its inputs and writes its outputs across the bus itself — a launch and a
-// synchronize instead of five staged copies of ≈8 µs host time each, whatever their size.
-constexpr size_t kSmallCallBytes = 64 << 10;
-struct PinnedScratch {
-  char* host = nullptr;
-  char* dev = nullptr;
-  hipError_t ensure() {
-    if (host) return hipSuccess;
-    if (hipError_t e = hipHostMalloc((void**)&host, kSmallCallBytes, hipHostMallocDefault)) { host = nullptr; return e; }
-    if (hipError_t e = hipHostGetDevicePointer((void**)&dev, host, 0)) { (void)hipHostFree(host); host = nullptr; return e; }
-    return hipSuccess;
-  }
-  void release() { if (host) (void)hipHostFree(host); host = dev = nullptr; }
-};
-
-// A device buffer of the outer-loop entry points' workspace (MkhProblem::ws): grown to what a call needs (never beyond what
-// max_batch allows), kept for the next call, never shrunk.
-struct GrowBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  hipError_t need(size_t bytes) {
-    if (bytes <= cap && p) return hipSuccess;
-    (void)hipFree(p); p = nullptr; cap = 0;
-    const hipError_t e = hipMalloc(&p, bytes ? bytes : 8);
-    if (e == hipSuccess) cap = bytes; else p = nullptr;
-    return e;
-  }
-  void release() { (void)hipFree(p); p = nullptr; cap = 0; }
-  double* f64() const { return (double*)p; }
-  int32_t* i32() const { return (int32_t*)p; }
-};
-
-// The slots of that workspace, named by what a buffer HOLDS, not by the entry point that asked for it: one call is in flight
-// per handle (include/minkhip.h), so mkh_solve_multistart, mkh_solve_trajectory, mkh_solve_keyframes and
-// mkh_solve_trajectory_multistart share them.  Two roles that one call needs at the same time are two slots.
-enum WsRole {
-  // the per-qpos-address seeding table and the joint list (ms_build_tables, at the first call that needs them)
-  WS_SEED_I, WS_SEED_F, WS_JNT,
-  // inputs of a host-pointer call, staged as they came
-  WS_IN_Q, WS_IN_FT, WS_IN_PT, WS_IN_CT, WS_IN_SEEDS, WS_IN_REF, WS_IN_W,
-  // the B·S candidate rows: what the loops read and write (time-major (T, B·S, .) for a trajectory; one buffer per array, so
-  // that a caller's *_all array replaces its own), the starts, and ONE fanned-out (B·S, .) slab per target group.  Who asks:
-  // the entry point asks for the rows it hands to ms_loops (the multi-start calls all of C_Q … C_STARTS; a ladder or a goal set
-  // C_Q alone, for one chunk's starts, when the caller wants no seeds_out; the ladder on nodes C_Q … C_CV for one chunk);
-  // ms_loops itself asks for C_FT / C_PT / C_CT and, with a seed table, for the IN_SEEDS slab — per chunk, the largest first
-  WS_C_Q, WS_C_V, WS_C_ST, WS_C_IT, WS_C_CV, WS_C_STARTS, WS_C_FT, WS_C_PT, WS_C_CT,
-  // a batch-major trajectory call: time-major copies of its targets, the loops' time-major results (TM_I32: status | iters |
-  // converged)
-  WS_TM_FT, WS_TM_PT, WS_TM_CT, WS_TM_Q, WS_TM_V, WS_TM_I32,
-  // keyframes: ONE (B, .) slab per target group, rewritten in front of every waypoint's loop
-  WS_KF_FT, WS_KF_PT, WS_KF_CT,
-  // outputs of a host-pointer call in the caller's layout, until they are copied back (OUT_I32: status | iters | converged
-  // per row; OUT_PICK: the per-instance integers of a selection; OUT_LEN: path lengths; OUT_FT / PT / CT: the interpolated
-  // targets a keyframed call was asked for — the only buffers of a call's targets that grow with T)
-  WS_OUT_Q, WS_OUT_V, WS_OUT_I32, WS_OUT_QVEL, WS_OUT_PICK, WS_OUT_LEN, WS_OUT_FT, WS_OUT_PT, WS_OUT_CT,
-  // a ladder: the (B, T, S, .) node rows (one buffer per array, so that a caller's *_all array replaces its own), the tracked
-  // flags, the starts a host caller asked for, q fanned out to the (B·T) targets of the multi-start launch, and the search's
-  // break masks | back-pointers
-  WS_L_Q, WS_L_V, WS_L_ST, WS_L_IT, WS_L_CV, WS_L_TRK, WS_L_STARTS, WS_L_Q0, WS_L_PRED,
-  // a ladder refinement: the working path r and the loops' velocities of its repaired nodes, (B, T, .); R_I32: tracked |
-  // repaired | status | iters | converged | break bits of r, (B, T) each; what one loop launch reads and writes — R_X: start | x
-  // | v, R_XI: status | iters | converged | bad flags, (B, .) each; a host caller's path and flags as they came (IN_PATH,
-  // IN_TRK); OUT_REF: tracked_out | repaired (B, T) | refined (B,) of a host-pointer call
-  WS_R_Q, WS_R_V, WS_R_I32, WS_R_X, WS_R_XI, WS_IN_PATH, WS_IN_TRK, WS_OUT_REF,
-  // a goal set: a host caller's goal_cost and goal_valid, (B, G) each, as they came.  Its (B, G, S, .) candidate rows, its
-  // starts and q fanned out to the (B·G) pairs are a ladder's node rows with G for T and live in WS_L_Q … WS_L_Q0; its outputs
-  // go through WS_OUT_Q / V (q_best | q_goal), OUT_I32 (iters | status, per target then per goal), OUT_PICK (converged |
-  // goal_index | seed_index | n_reached (B,), then seed_index_goal | reached | n_converged_goal (B, G)) and OUT_LEN (score |
-  // distance_goal)
-  WS_IN_GCOST, WS_IN_GVALID,
-  // turn unwinding: the per-qpos-address table (mode, range_lo, range_hi), built with the seeding table
-  WS_UNW,
-  // a ladder on deduplicated nodes: its (B, T, K, .) node rows live in a plain ladder's WS_L_Q … WS_L_TRK with K for S, the
-  // candidates of ONE chunk of rungs in multi-start's WS_C_Q … WS_C_CV, asked for by the call itself.  A host caller's set outputs — N_I32: node_seed_index |
-  // node_multiplicity (B, T, K), then n_distinct | n_converged | n_uncovered | seed_index (B, T); N_DIST: node_distance (B, T, K)
-  WS_N_I32, WS_N_DIST,
-  // swept clearance and the checked ladder calls: a host caller's q_to as it came (q_from goes through WS_C_Q); the nodes'
-  // clearance margins (B, T, S) and effective tracked flags; the blocked flag of every edge, (B, T, S, S) bytes; every edge's swept
-  // margin when the caller asked for it; a host caller's outputs — F_OUT_I: edge_collision (B, T) | n_edge_collisions (B,), F_OUT_F:
-  // edge_margin (B, T)
-  WS_SW_TO, WS_F_NMARGIN, WS_F_TRK, WS_F_BLOCK, WS_F_EMARGIN, WS_F_OUT_I, WS_F_OUT_F,
-  // a ladder refinement with a checker: RF_MARGIN: the node margins and the edge margins of the input path, then of the working
-  // path, (B, T) each; RF_TRIP: what lr_check_kernel leaves per step, (B, 3, slots); RF_IDX: the index array of the input path seen as a
-  // ladder of width 1 (zeros) | its effective flags, (B, T) each.  A host caller's outputs go through F_OUT_I, F_OUT_F and
-  // F_NMARGIN, as a checked ladder's do.  Checked candidate tracking (trajectory_free.hip) has no slot of its own: every row's
-  // node and edge margins, (T, B·S) each, live in F_NMARGIN and F_EMARGIN; a host caller's outputs in F_OUT_F (node_margin |
-  // edge_margin, (B, T) each) and F_OUT_I (edge_collision (B, T) | n_edge_collisions (B,)); the selection alone keeps the
-  // caller's candidates and flags in C_Q and C_CV and its status of zeros in C_ST
-  WS_RF_MARGIN, WS_RF_TRIP, WS_RF_IDX,
-  WS_COUNT
-};
-
-struct MkhModel : HostModel {     // (the host arrays problems are planned from: problem_plan.h)
-  int device = 0;
-  PinnedScratch small;             // mkh_integrate, host pointers
-  std::mutex small_mutex;          // one model serves many callers (every Configuration of a FlatModel shares it): the small
-                                   // host-pointer path of mkh_integrate is serialised, so the entry point stays re-entrant
-  double* d_mesh_vert = nullptr;   // hull vertices of the mesh geoms (HostModel::h_mesh_vert)
-  // device tables
-  double* d_body_f = nullptr;
-  int32_t* d_body_i = nullptr;
-  double* d_jnt_f = nullptr;
-  int32_t* d_jnt_i = nullptr;
-  int32_t* d_dof_i = nullptr;
-  double* d_dof_f = nullptr;
-  int num_cus = 0;
-};
-
-struct MkhProblem : ProblemSelect {     // (what creation decided and plan_launch reads: problem_plan.h)
-  PinnedScratch small;             // run(), host pointers
-  MkhModel* model = nullptr;
-  int device = 0;                  // (copied: the destructor must not depend on the model still being alive)
-  DeviceProblem dev{};
-  int max_batch = 0;
-  DeviceProblem* d_dev_tight = nullptr;   // the tight-rows twin of `dev` (ProblemSelect::nt_tight)
-  int32_t* d_status_tight = nullptr;   // status of a call with a redo launch whose caller passed no status_out (the redo launch reads it)
-  WideProblem wide{};
-  WideProblem* d_wide = nullptr;
-  // device memory the handle keeps only to free it: what the descriptors point to (frame tasks, cost and limit tables, pairs,
-  // the wide kernel's arrays, workspace and redo queue, the convex split's lists)
-  std::vector<void*> owned;
-  LaneProblem* d_lane = nullptr;
-  char last_kernel[64] = "";
-  int32_t diag = 0;                // MKH_DIAG_* of mkh_problem_create_diag (parity / measurement switches of this handle)
-  DeviceProblem* d_dev = nullptr;   // device copy of `dev` (the kernel reads the descriptor from memory)
-  TapArgs* d_taps = nullptr;
-  int last_grid = 0, last_lds = 0, last_nt = 0, last_block = kWave;   // geometry of the most recent launch (mkh_problem_launch_info)
-  long long* d_clk = nullptr;      // MKH_DEBUG_CLOCKS (experiment builds): cycle stamps of the last launch
-  // general convex pairs of plain solves: evaluated by convex_contacts_kernel in front of the analytic collision build
-  mkh::CvPre cv{};
-  double* d_cv = nullptr;          // [max_batch][n_cv][7]
-  double* d_cv_sweep = nullptr;    // [sweep_rows][n_cv]: the distances of a chunk of swept samples (mkh_problem_set_sweep_rows)
-  int64_t sweep_rows = 0;
-  double* d_cv_check = nullptr;    // [check_rows][n_cv]: the distances on the rows a check judges inside its launch (mkh_problem_set_check_rows)
-  int64_t check_rows = 0;
-  double* d_qkeep = nullptr;       // fused loops with a redo launch behind them: the call's q as it came (q_out may alias it)
-  int8_t* d_warm = nullptr;        // MKH_FLAG_WARM_START: active set of every instance after the previous solve (max_batch × nv)
-  int warm_age = 0, warm_B = 0;    // solves since the state was reset / the batch size it belongs to
-  uint32_t* d_work = nullptr;      // ticket counter of the dynamic problem distribution (zeroed by the kernel's last draw)
-  // staging buffers for host-pointer calls
-  double *s_q = nullptr, *s_ft = nullptr, *s_pt = nullptr, *s_ct = nullptr, *s_v = nullptr;
-  // host-pointer calls on large batches: copies of chunk c + 1 / c − 1 run beside the kernel of chunk c
-  hipStream_t st_in = nullptr, st_out = nullptr;
-  hipEvent_t ev_start = nullptr, ev_in[4] = {nullptr, nullptr, nullptr, nullptr}, ev_k[4] = {nullptr, nullptr, nullptr, nullptr};
-  int32_t* s_status = nullptr;
-  int32_t* s_iters = nullptr;      // [2][max_batch]: iterations, converged (mkh_solve_until, host-pointer calls)
-  size_t s_pt_cap = 0, s_ct_cap = 0;
-  double *s_de = nullptr, *s_dJ = nullptr, *s_dG = nullptr, *s_dh = nullptr, *s_dbox = nullptr;   // dense (plugin) rows
-  // the outer-loop entry points' workspace, by role (WsRole)
-  bool ws_tables = false;
-  GrowBuf ws[WS_COUNT];
-  const MkhSeedTable* seed_table = nullptr;    // attached by mkh_problem_set_seed_table
-  MkhProblem* checker = nullptr;               // attached by mkh_problem_set_collision_check
-};
 
 // A seed table (include/minkhip.h "Seed tables"): device memory of its own — nothing of the problem that made it is kept.
 struct MkhSeedTable {
@@ -279,7 +106,6 @@ namespace mkh {
 int launch_lane(int nv_max, bool loop, int grid, int lds_bytes, hipStream_t stream, const LaneProblem* P, const SolveArgs& a);
 int launch_quad(int nt, bool loop, int grid, hipStream_t stream, const void* P, const LaneDims& dims, const SolveArgs& a);   // returns its LDS bytes per wavefront
 int launch_wide(int grid, int lds_bytes, hipStream_t stream, const WideProblem* P, const SolveArgs& a, const TapArgs* taps, bool convex);
-int launch_convex_pre(hipStream_t stream, const WideProblem* P, const CvPre& C, int B, const double* q, double* out);
 constexpr int kLaneMinBatchLoop = 28672;  // fused loops of a small arm: row kernel below, lane kernel from here (M targets/s at 16 384: 39.7 vs 24.1, at 32 768: 42.4 vs 48.2)
 constexpr int kLaneMinBatch = 73728;  // plain solves of a small arm: row kernel below, lane kernel from here (plan_launch())
 }
@@ -503,7 +329,7 @@ void mkh_problem_destroy(MkhProblem* p) {
   for (void* w : p->owned) (void)hipFree(w);
   (void)hipFree(p->d_dev); (void)hipFree(p->d_taps); (void)hipFree(p->d_work);
   (void)hipFree(p->d_lane); (void)hipFree(p->d_warm); (void)hipFree(p->d_qkeep);
-  (void)hipFree(p->d_cv); (void)hipFree(p->d_cv_sweep); (void)hipFree(p->d_cv_check); (void)hipFree(p->d_dev_tight); (void)hipFree(p->d_status_tight);
+  (void)hipFree(p->d_cv); (void)hipFree(p->cv_sweep.d); (void)hipFree(p->cv_check.d); (void)hipFree(p->d_dev_tight); (void)hipFree(p->d_status_tight);
   (void)hipFree(p->s_iters);
   (void)hipFree(p->s_de); (void)hipFree(p->s_dJ); (void)hipFree(p->s_dG); (void)hipFree(p->s_dh); (void)hipFree(p->s_dbox); (void)hipFree(p->d_clk);
   (void)hipFree(p->d_wide);
@@ -902,8 +728,8 @@ static int32_t launch(MkhProblem* p, const SolveArgs& a_in, const TapArgs* taps,
     al.redo_mask = MKH_ST_ROW_OVERFLOW;              // the full-row build: only what the tight launch flagged
   }
   if (L.cv_split) {
-    const int rc = mkh::launch_convex_pre(stream, p->d_wide, p->cv, a.B, a.q, p->d_cv);
-    if (rc != 0) return fail(MKH_E_HIP, "convex pre-pass: %s", hipGetErrorString((hipError_t)rc));
+    const hipError_t rc = mkh::launch_convex_pre(stream, p->d_wide, p->cv, a.B, a.q, p->d_cv);
+    if (rc != hipSuccess) return fail(MKH_E_HIP, "convex pre-pass: %s", hipGetErrorString(rc));
   }
   if (const int32_t rc = launch_wave(p, L.main, p->d_dev, al, stream, dtaps)) return rc;
   HIP_OK(clk_end(p, a.B, stream));
@@ -1284,62 +1110,6 @@ static int32_t ms_build_tables(MkhProblem* p) {
   return MKH_OK;
 }
 
-// One outer-loop call's traffic with the workspace and with the caller's arrays.  The first HIP error is latched and everything
-// after it is skipped; finish() is the only way out once something is enqueued: a host-pointer call may have copies from or to
-// the caller's arrays in flight, so it drains the stream before it returns, whatever happened.
-struct Stager {
-  MkhProblem* p;
-  hipStream_t stream;
-  bool devp;                         // MKH_FLAG_DEVICE_PTRS: the caller's arrays are used in place, nothing is staged
-  const char* who;                   // the entry point, in messages
-  hipError_t err = hipSuccess;
-  size_t oom_bytes = 0;              // the size of the allocation that failed, if one did
-  size_t cand_bytes = 0;             // a call with candidates: what their results take (the out-of-memory message states it)
-
-  bool ok() const { return err == hipSuccess; }
-  void latch(hipError_t e) { if (err == hipSuccess) err = e; }
-  // slot `role` grown to `bytes`; NULL when that failed (or an error is latched already)
-  void* need(WsRole role, size_t bytes) {
-    if (!ok()) return nullptr;
-    GrowBuf& g = p->ws[role];
-    if ((err = g.need(bytes)) != hipSuccess) { oom_bytes = bytes; return nullptr; }
-    return g.p;
-  }
-  double* f64(WsRole role, size_t n) { return (double*)need(role, n * sizeof(double)); }
-  int32_t* i32(WsRole role, size_t n) { return (int32_t*)need(role, n * sizeof(int32_t)); }
-  // `n` doubles of a caller's input on the device: `src` itself, or its staged copy in slot `role`
-  const double* up(WsRole role, const double* src, size_t n) {
-    if (devp || !src) return src;
-    double* const d = f64(role, n);
-    if (d) latch(hipMemcpyAsync(d, src, n * sizeof(double), hipMemcpyHostToDevice, stream));
-    return d;
-  }
-  const int32_t* up_i32(WsRole role, const int32_t* src, size_t n) {       // (the same for `n` int32)
-    if (devp || !src) return src;
-    int32_t* const d = i32(role, n);
-    if (d) latch(hipMemcpyAsync(d, src, n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-    return d;
-  }
-  // rows the loops write: the caller's own array where it is a device buffer, else slot `role`
-  void* given_or(WsRole role, void* given, size_t bytes) { return (devp && given) ? given : need(role, bytes); }
-  // a result back into a host caller's array (an output the caller did not ask for: dst == NULL)
-  void down(void* dst, const void* src, size_t bytes) {
-    if (dst && ok()) latch(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream));
-  }
-  // the way out: `rc` != MKH_OK is a refusal or failure of a loop launch, whose message stands
-  int32_t finish(int32_t rc = MKH_OK) {
-    if (devp && ok() && rc == MKH_OK) return MKH_OK;         // (asynchronous on the caller's stream)
-    latch(hipStreamSynchronize(stream));                     // (a failed call still drains what it started)
-    if (rc != MKH_OK || ok()) return rc;
-    if (oom_bytes && cand_bytes)
-      return fail(MKH_E_HIP, "%s: no device memory for a buffer of %zu bytes (the candidates' results take T*B*S*((nq+nv)*8+12) = %zu bytes)",
-                  who, oom_bytes, cand_bytes);
-    return fail(MKH_E_HIP, "%s: %s", who, hipGetErrorString(err));
-  }
-};
-// a launcher's hipError_t into the latch; not launched at all behind an earlier error
-#define ST_LAUNCH(st, call) do { if ((st).ok()) (st).latch(call); } while (0)
-
 // ---- seed tables
 // device buffers of one call, freed on every way out
 struct DevTmp {
@@ -1540,237 +1310,6 @@ int32_t mkh_problem_set_seed_table(MkhProblem* p, const MkhSeedTable* table) {
     if (const int32_t rc = st_refuse(p, table, -1, "mkh_problem_set_seed_table")) return rc;
   p->seed_table = table;
   return MKH_OK;
-}
-
-// ---- clearance (include/minkhip.h "THE RULE OF CLEARANCE"; kernel: clearance.hip, in front of it convex_pre.hip's for the pairs
-// without an analytic routine)
-static_assert(mkh::kStInCollision == MKH_ST_IN_COLLISION, "outer_launch.h: the bit clearance.hip sets");
-
-// Whether `ck` can be a checker.
-static int32_t clearance_refuse(const MkhProblem* ck, const char* who) {
-  if (ck->dev.n_pairs < 1) return fail(MKH_E_INVALID, "%s: the checker has no collision pairs (a problem with CollisionAvoidanceLimits is one)", who);
-  if (!ck->d_wide)
-    return fail(MKH_E_INVALID, "%s: the checker was created with MKH_DIAG_NO_WIDE_REDO: it has no per-body arrays to compute poses from", who);
-  if (ck->convex_pairs && ck->cv.n_cv == 0)
-    return fail(MKH_E_INVALID, "%s: the checker has general convex pairs (cylinder-box, ellipsoid-*, mesh hulls) that are not pre-evaluated "
-                               "on this handle (a model beyond 64 bodies or dofs): no clearance", who);
-  if ((size_t)ck->model->nbody * 7 * sizeof(double) > 64 * 1024)
-    return fail(MKH_E_LIMIT, "%s: %d bodies: the poses of one row do not fit 64 KB of LDS (at most 1170 bodies)", who, ck->model->nbody);
-  return MKH_OK;
-}
-
-// The clearance of N device rows on st's stream, in chunks of the checker's max_batch (its buffer of pre-evaluated convex pairs
-// holds that many rows; the stream orders its reuse).  Every output is optional; status: MKH_ST_IN_COLLISION OR-ed in.
-static void clearance_rows(Stager& st, MkhProblem* ck, size_t N, const double* d_q, double* margin, int32_t* pair, int32_t* n_violated,
-                           double* distance, int32_t* status) {
-  const size_t per = (size_t)ck->max_batch, nq = ck->model->nq, np = ck->dev.n_pairs;
-  for (size_t r0 = 0; r0 < N && st.ok(); r0 += per) {
-    const int n = (int)(N - r0 < per ? N - r0 : per);
-    const double* const q = d_q + r0 * nq;
-    if (ck->cv.n_cv > 0) st.latch((hipError_t)mkh::launch_convex_pre(st.stream, ck->d_wide, ck->cv, n, q, ck->d_cv));
-    ST_LAUNCH(st, launch_clearance(st.stream, ck->d_wide, ck->model->nbody, (int)np, ck->cv.n_cv, ck->d_cv, n, q, margin ? margin + r0 : nullptr,
-                                   pair ? pair + r0 : nullptr, n_violated ? n_violated + r0 : nullptr,
-                                   distance ? distance + r0 * np : nullptr, status ? status + r0 : nullptr));
-  }
-}
-
-// An attached checker in front of an entry point that would not run it.
-static int32_t refuse_checker(const MkhProblem* p, const char* who) {
-  if (p->checker)
-    return fail(MKH_E_INVALID, "%s: a collision checker is attached to this problem (mkh_problem_set_collision_check) and this call would "
-                               "not run it: mkh_solve_multistart, mkh_solve_multistart_set and mkh_solve_goalset are the calls that "
-                               "do — detach it first", who);
-  return MKH_OK;
-}
-
-int32_t mkh_clearance(MkhProblem* ck, int32_t N, const double* q_rows, const MkhClearanceIO* io, int32_t flags, void* hip_stream) {
-  const char* const who = "mkh_clearance";
-  if (!ck) return fail(MKH_E_INVALID, "null problem");
-  if (N < 1) return fail(MKH_E_INVALID, "%s: N = %d must be >= 1", who, N);
-  if (flags & ~MKH_FLAG_DEVICE_PTRS) return fail(MKH_E_INVALID, "%s: flags = %d: only MKH_FLAG_DEVICE_PTRS is accepted", who, flags);
-  if (!q_rows || !io || !io->margin || !io->pair || !io->n_violated)
-    return fail(MKH_E_INVALID, "%s: q_rows, io and its outputs margin, pair, n_violated are required", who);
-  if (const int32_t rc = clearance_refuse(ck, who)) return rc;
-  const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
-  HIP_OK(hipSetDevice(ck->model->device));
-  Stager st{ck, (hipStream_t)hip_stream, devp, "clearance"};
-  const size_t Nz = N, nq = ck->model->nq, np = ck->dev.n_pairs, f8 = sizeof(double), i4 = sizeof(int32_t);
-  const double* const d_q = st.up(WS_C_Q, q_rows, Nz * nq);
-  double *o_m = io->margin, *o_d = io->distance;
-  int32_t *o_p = io->pair, *o_n = io->n_violated;
-  if (!devp) {
-    o_m = st.f64(WS_OUT_LEN, Nz);
-    o_p = st.i32(WS_OUT_PICK, 2 * Nz); o_n = o_p ? o_p + Nz : nullptr;
-    if (o_d) o_d = st.f64(WS_OUT_Q, Nz * np);
-  }
-  if (!st.ok()) return st.finish();
-  clearance_rows(st, ck, Nz, d_q, o_m, o_p, o_n, o_d, nullptr);
-  if (devp) return st.finish();
-  st.down(io->margin, o_m, Nz * f8);
-  st.down(io->pair, o_p, Nz * i4);
-  st.down(io->n_violated, o_n, Nz * i4);
-  st.down(io->distance, o_d, Nz * np * f8);
-  return st.finish();
-}
-
-int32_t mkh_problem_set_collision_check(MkhProblem* p, MkhProblem* checker) {
-  const char* const who = "mkh_problem_set_collision_check";
-  if (!p) return fail(MKH_E_INVALID, "null problem");
-  if (checker) {
-    if (checker->device != p->device)
-      return fail(MKH_E_INVALID, "%s: the checker lives on device %d, the problem on device %d", who, checker->device, p->device);
-    if (checker->model != p->model) return fail(MKH_E_INVALID, "%s: the checker belongs to another MkhModel than the problem", who);
-    if (const int32_t rc = clearance_refuse(checker, who)) return rc;
-  }
-  p->checker = checker;
-  return MKH_OK;
-}
-
-// ---- swept clearance (include/minkhip.h "THE RULE OF THE SWEEP"; kernel: sweep.hip)
-// Whether `ck` can be the checker of a sweep: what a clearance refuses, general convex pairs without room for the samples'
-// distances, and the wider LDS slice.  n_samples: of an entry point that takes general convex pairs in chunks of the handle's
-// sweep_rows (sweep_edges below); 0: of one that does not sweep edges known in front of a launch.  check_item: of an entry point
-// that judges rows INSIDE a launch (the candidate tracking check, the refinement's) the rows of one of its items, 1 + M or
-// 1 + 2M — it takes general convex pairs in chunks of the handle's check_rows (tmf_check, refine_pass below), and, where n_samples says so,
-// sweeps with sweep_rows as well; 0: of one that judges none.
-static int32_t sweep_refuse(const MkhProblem* ck, const char* who, int32_t n_samples = 0, int32_t check_item = 0) {
-  if (const int32_t rc = clearance_refuse(ck, who)) return rc;
-  if (ck->cv.n_cv > 0 && check_item > 0) {
-    if (ck->check_rows == 0)
-      return fail(MKH_E_INVALID, "%s: the checker has general convex pairs (cylinder-box, ellipsoid-*, mesh hulls): they are pre-evaluated on "
-                                 "rows in memory, and this call judges rows it produces inside a launch (mkh_problem_set_check_rows / "
-                                 "CollisionChecker(check_rows=) reserves room for their distances)", who);
-    if (n_samples >= 1 && ck->sweep_rows == 0)
-      return fail(MKH_E_INVALID, "%s: the checker has general convex pairs (cylinder-box, ellipsoid-*, mesh hulls) and check_rows, but this "
-                                 "call also sweeps edges of paths (mkh_problem_set_sweep_rows / CollisionChecker(sweep_rows=) reserves "
-                                 "room for their distances)", who);
-    if (ck->check_rows < check_item)
-      return fail(MKH_E_LIMIT, "%s: check_rows = %lld holds less than one item of %d rows", who, (long long)ck->check_rows, check_item);
-    if (n_samples >= 1 && ck->sweep_rows < n_samples)
-      return fail(MKH_E_LIMIT, "%s: sweep_rows = %lld holds less than one edge of n_samples = %d samples", who, (long long)ck->sweep_rows,
-                  n_samples);
-  } else if (ck->cv.n_cv > 0 && (n_samples < 1 || ck->sweep_rows == 0))
-    return fail(MKH_E_INVALID, "%s: the checker has general convex pairs (cylinder-box, ellipsoid-*, mesh hulls): they are pre-evaluated on "
-                               "rows in memory, and the samples of a sweep are never written there%s", who,
-                n_samples < 1 ? " (this call does not take them through sweep_rows either)"
-                              : " (mkh_problem_set_sweep_rows / CollisionChecker(sweep_rows=) reserves room for their distances)");
-  if (ck->cv.n_cv > 0 && ck->sweep_rows < n_samples)
-    return fail(MKH_E_LIMIT, "%s: sweep_rows = %lld holds less than one edge of n_samples = %d samples", who, (long long)ck->sweep_rows,
-                n_samples);
-  if (mkh::sweep_lds_bytes(ck->model->nbody, ck->model->nq, ck->dev.n_pairs) > 64 * 1024)
-    return fail(MKH_E_LIMIT, "%s: %d bodies, nq = %d: the poses of a sample and the three rows of q beside them do not fit 64 KB of LDS "
-                             "(7 nbody + 3 nq <= 8192)", who, ck->model->nbody, ck->model->nq);
-  return MKH_OK;
-}
-
-// ... and of a checked call on problem `p`.
-static int32_t sweep_refuse_for(const MkhProblem* p, const MkhProblem* ck, const char* who, int32_t n_samples = 0, int32_t check_item = 0) {
-  if (!ck) return fail(MKH_E_INVALID, "%s: null checker", who);
-  if (ck->device != p->device)
-    return fail(MKH_E_INVALID, "%s: the checker lives on device %d, the problem on device %d", who, ck->device, p->device);
-  if (ck->model != p->model) return fail(MKH_E_INVALID, "%s: the checker belongs to another MkhModel than the problem", who);
-  return sweep_refuse(ck, who, n_samples, check_item);
-}
-
-// The rows of one item of the checks that judge rows inside a launch, from a sample count that may not have been judged yet.
-static int32_t tracking_item(int32_t n_samples) { return 1 + (n_samples < 1 ? 1 : n_samples); }
-static int32_t refinement_item(int32_t n_samples) { return 1 + 2 * (n_samples < 1 ? 1 : n_samples); }
-
-int32_t mkh_problem_set_sweep_rows(MkhProblem* ck, int64_t rows) {
-  const char* const who = "mkh_problem_set_sweep_rows";
-  if (!ck) return fail(MKH_E_INVALID, "null problem");
-  if (rows < 0) return fail(MKH_E_INVALID, "%s: rows = %lld must be >= 0", who, (long long)rows);
-  if (const int32_t rc = clearance_refuse(ck, who)) return rc;
-  const uint64_t width = (uint64_t)ck->cv.n_cv * sizeof(double);
-  if (width > 0 && (uint64_t)rows > (uint64_t)0x7fffffffffffLL / width)
-    return fail(MKH_E_LIMIT, "%s: rows = %lld x %d general convex pairs x 8 bytes overflows", who, (long long)rows, ck->cv.n_cv);
-  HIP_OK(hipSetDevice(ck->model->device));
-  HIP_OK(hipDeviceSynchronize());                              // (a sweep in flight may still read the old buffer)
-  (void)hipFree(ck->d_cv_sweep);
-  ck->d_cv_sweep = nullptr;
-  ck->sweep_rows = 0;
-  if (rows > 0 && width > 0) {
-    // (zeroed: a sample the pre-pass skips is never judged by what stands here, and what is read of it is at least a number)
-    HIP_OK(hipMalloc((void**)&ck->d_cv_sweep, (size_t)rows * width));
-    HIP_OK(hipMemset(ck->d_cv_sweep, 0, (size_t)rows * width));
-    HIP_OK(hipDeviceSynchronize());
-  }
-  ck->sweep_rows = rows;
-  return MKH_OK;
-}
-
-int32_t mkh_problem_set_check_rows(MkhProblem* ck, int64_t rows) {
-  const char* const who = "mkh_problem_set_check_rows";
-  if (!ck) return fail(MKH_E_INVALID, "null problem");
-  if (rows < 0) return fail(MKH_E_INVALID, "%s: rows = %lld must be >= 0", who, (long long)rows);
-  if (const int32_t rc = clearance_refuse(ck, who)) return rc;
-  const uint64_t width = (uint64_t)ck->cv.n_cv * sizeof(double);
-  if (width > 0 && (uint64_t)rows > (uint64_t)0x7fffffffffffLL / width)
-    return fail(MKH_E_LIMIT, "%s: rows = %lld x %d general convex pairs x 8 bytes overflows", who, (long long)rows, ck->cv.n_cv);
-  HIP_OK(hipSetDevice(ck->model->device));
-  HIP_OK(hipDeviceSynchronize());                              // (a check in flight may still read the old buffer)
-  (void)hipFree(ck->d_cv_check);
-  ck->d_cv_check = nullptr;
-  ck->check_rows = 0;
-  if (rows > 0 && width > 0) {
-    // (zeroed: a row the pre-pass skips is never judged by what stands here, and what is read of it is at least a number)
-    HIP_OK(hipMalloc((void**)&ck->d_cv_check, (size_t)rows * width));
-    HIP_OK(hipMemset(ck->d_cv_check, 0, (size_t)rows * width));
-    HIP_OK(hipDeviceSynchronize());
-  }
-  ck->check_rows = rows;
-  return MKH_OK;
-}
-
-// The sweep of a's edges on st's stream.  A checker with general convex pairs: in chunks of floor(sweep_rows / M) edges,
-// convex_sweep_kernel then sweep_kernel on each — the stream orders the reuse of the buffer.  Without: one launch, as ever.
-static void sweep_edges(Stager& st, const MkhProblem* ck, mkh::SweepArgs a) {
-  const int nbody = ck->model->nbody, nq = ck->model->nq, np = ck->dev.n_pairs;
-  if (ck->cv.n_cv == 0) {
-    ST_LAUNCH(st, launch_sweep(st.stream, ck->d_wide, nbody, nq, np, a));
-    return;
-  }
-  const long long per = ck->sweep_rows / a.M;                  // (>= 1: sweep_refuse)
-  a.cv = ck->d_cv_sweep; a.n_cv = ck->cv.n_cv;
-  const char* const ipw_env = dbg_env("MKH_DEBUG_CONVEX_SWEEP_IPW");       // (experiment builds: items per wavefront of the pre-pass)
-  const int ipw = ipw_env ? atoi(ipw_env) : 0;
-  for (a.first = 0; a.first < a.N && st.ok(); a.first += per) {
-    a.count = a.N - a.first < per ? a.N - a.first : per;
-    ST_LAUNCH(st, launch_convex_sweep(st.stream, ck->d_wide, ck->cv.pair, ck->cv.chain_adr, ck->cv.chain, a, ipw));
-    ST_LAUNCH(st, launch_sweep(st.stream, ck->d_wide, nbody, nq, np, a));
-  }
-}
-
-int32_t mkh_swept_clearance(MkhProblem* ck, int32_t N, const double* q_from, const double* q_to, int32_t n_samples,
-                            const MkhSweptClearanceIO* io, int32_t flags, void* hip_stream) {
-  const char* const who = "mkh_swept_clearance";
-  if (!ck) return fail(MKH_E_INVALID, "null problem");
-  if (N < 1) return fail(MKH_E_INVALID, "%s: N = %d must be >= 1", who, N);
-  if (n_samples < 1) return fail(MKH_E_INVALID, "%s: n_samples = %d must be >= 1", who, n_samples);
-  if (flags & ~MKH_FLAG_DEVICE_PTRS) return fail(MKH_E_INVALID, "%s: flags = %d: only MKH_FLAG_DEVICE_PTRS is accepted", who, flags);
-  if (!q_from || !q_to || !io || !io->margin || !io->sample || !io->pair)
-    return fail(MKH_E_INVALID, "%s: q_from, q_to, io and its outputs margin, sample, pair are required", who);
-  if (const int32_t rc = sweep_refuse(ck, who, n_samples)) return rc;
-  const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
-  HIP_OK(hipSetDevice(ck->model->device));
-  Stager st{ck, (hipStream_t)hip_stream, devp, "swept_clearance"};
-  const size_t Nz = N, nq = ck->model->nq;
-  mkh::SweepArgs a{};
-  a.mode = mkh::kSweepPairs; a.M = n_samples; a.N = N;
-  a.from = st.up(WS_C_Q, q_from, Nz * nq);
-  a.to = st.up(WS_SW_TO, q_to, Nz * nq);
-  a.margin = io->margin; a.sample = io->sample; a.pair = io->pair;
-  if (!devp) {
-    a.margin = st.f64(WS_OUT_LEN, Nz);
-    a.sample = st.i32(WS_OUT_PICK, 2 * Nz); a.pair = a.sample ? a.sample + Nz : nullptr;
-  }
-  if (!st.ok()) return st.finish();
-  sweep_edges(st, ck, a);
-  if (devp) return st.finish();
-  st.down(io->margin, a.margin, Nz * sizeof(double));
-  st.down(io->sample, a.sample, Nz * sizeof(int32_t));
-  st.down(io->pair, a.pair, Nz * sizeof(int32_t));
-  return st.finish();
 }
 
 // ---- the loop stage of every call that fans a target out to S starts (kernels: multistart.hip, seed_table.hip): the two
@@ -2213,29 +1752,6 @@ static TmfDev tmf_stage(Stager& st, const MkhTrajectoryFreeIO& f, size_t N, size
   return d;
 }
 
-// The one launch over all T·B·S rows: node margins, the status bit, edge margins.  A checker with general convex pairs: in chunks
-// of rows, each behind its pre-pass.
-static void tmf_check(Stager& st, const MkhProblem* ck, int B, int S, int T, int M, const double* q_all, const int32_t* cv_all,
-                      int32_t* st_all, const TmfDev& d) {
-  if (ck->cv.n_cv == 0) {
-    ST_LAUNCH(st, launch_tmf_check(st.stream, ck->d_wide, ck->model->nbody, ck->model->nq, ck->dev.n_pairs, B, S, T, M, q_all, cv_all, st_all,
-                                   d.nm_all, d.em_all));
-    return;
-  }
-  // general convex pairs: chunks of floor(check_rows / (1 + M)) rows (>= 1: sweep_refuse), convex_check_kernel then the check on
-  // each — the pre-pass reads a chunk's status in front of the check that ORs into it; the stream orders the reuse of the buffer
-  const long long N = (long long)B * S * T, per = ck->check_rows / (1 + M);
-  mkh::CvCheckArgs a{};
-  a.mode = mkh::kCvCheckTrack; a.M = M; a.R = (long long)B * S; a.q_all = q_all; a.converged = cv_all; a.status = st_all;
-  for (a.first = 0; a.first < N && st.ok(); a.first += per) {
-    a.count = N - a.first < per ? N - a.first : per;
-    const mkh::CvChunk c{a.first, a.count, ck->d_cv_check, ck->cv.n_cv};
-    ST_LAUNCH(st, launch_convex_check(st.stream, ck->d_wide, ck->cv.pair, ck->cv.chain_adr, ck->cv.chain, ck->cv.n_cv, a, ck->d_cv_check));
-    ST_LAUNCH(st, launch_tmf_check(st.stream, ck->d_wide, ck->model->nbody, ck->model->nq, ck->dev.n_pairs, B, S, T, M, q_all, cv_all, st_all,
-                                   d.nm_all, d.em_all, c));
-  }
-}
-
 // The chosen candidate's margins (plain gathers: edge_margin_all carries +inf at waypoint 0) and its edge flags, through the
 // (instance, waypoint) strides sb / sw of a (B, T) array in the caller's layout.
 static void tmf_chosen(Stager& st, int B, int S, int T, const int32_t* o_si, const int32_t* cv_all, const int32_t* st_all, const TmfDev& d,
@@ -2294,7 +1810,7 @@ static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double
   if (const int32_t rc = refuse_checker(p, who)) return rc;
   const bool checked = cs && cs->checked;
   if (checked)
-    if (const int32_t rc = sweep_refuse_for(p, cs->ck, who, 0, tracking_item(cs->M))) return rc;
+    if (const int32_t rc = sweep_refuse_for(p, cs->ck, who, CheckerUse::tracking(cs->M))) return rc;
   const DeviceProblem& P = p->dev;
   if (const int32_t rc = refuse_inputs(P, q, frame_targets, posture_target, com_target, until ? who : nullptr, "trajectory"))
     return rc;
@@ -2467,7 +1983,7 @@ static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double
   if (cs) {
     // the score over every candidate's path and the choice, then the chosen rows into the caller's layout
     // (with a checker: one launch over all T·B·S rows behind the last loop — nodes, the status bit, edges — and the score on them)
-    if (checked) tmf_check(st, cs->ck, B, S, T, cs->M, l_q, l_cv, l_st, tf);
+    if (checked) tmf_check(st, cs->ck, B, S, T, cs->M, l_q, l_cv, l_st, tf.nm_all, tf.em_all);
     ST_LAUNCH(st, launch_tms_score(stream, B, S, T, (int)nq, p->model->njnt, ws[WS_JNT].i32(), d_q, l_q, l_st, l_cv, d_w,
                                    checked ? tf.em_all : nullptr, o_si, o_nt, o_nc, o_len));
     ST_LAUNCH(st, launch_tms_gather(stream, l_q, o_q, o_si, B, S, T, (int)nq, sb(nq), sw(nq)));
@@ -2613,7 +2129,7 @@ int32_t mkh_select_trajectory_candidates(MkhProblem* p, MkhProblem* ck, int32_t 
     if (const int32_t rc = tmf_refuse_args(n_samples, fio, who)) return rc;
   if (!p) return fail(MKH_E_INVALID, "null problem");
   if (ck)
-    if (const int32_t rc = sweep_refuse_for(p, ck, who, 0, tracking_item(n_samples))) return rc;
+    if (const int32_t rc = sweep_refuse_for(p, ck, who, CheckerUse::tracking(n_samples))) return rc;
   if ((long long)B * S * T > 0x7fffffffLL)
     return fail(MKH_E_LIMIT, "%s: B * S * T = %lld rows, at most 2^31 - 1", who, (long long)B * S * T);
   const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
@@ -2643,7 +2159,7 @@ int32_t mkh_select_trajectory_candidates(MkhProblem* p, MkhProblem* ck, int32_t 
   if (!st.ok()) return st.finish();
   if (ck) {
     st.latch(hipMemsetAsync(d_st, 0, NR * i4, st.stream));
-    tmf_check(st, ck, B, S, T, n_samples, d_paths, d_trk, d_st, tf);
+    tmf_check(st, ck, B, S, T, n_samples, d_paths, d_trk, d_st, tf.nm_all, tf.em_all);
   }
   ST_LAUNCH(st, launch_tms_score(st.stream, B, S, T, (int)nq, p->model->njnt, p->ws[WS_JNT].i32(), d_q, d_paths, d_st, d_trk, d_w,
                                  ck ? tf.em_all : nullptr, o_si, o_nt, o_nc, o_len));
@@ -2773,7 +2289,7 @@ static int32_t ladder_free_refuse(const MkhProblem* p, const MkhProblem* ck, int
                                   const MkhLadderFreeIO* f, const char* who, bool refined) {
   // (general convex pairs: through the checker's sweep_rows where the call sweeps and nothing else; with refinement through its
   //  check_rows as well)
-  if (const int32_t rc = sweep_refuse_for(p, ck, who, n_samples < 1 ? 1 : n_samples, refined ? refinement_item(n_samples) : 0)) return rc;
+  if (const int32_t rc = sweep_refuse_for(p, ck, who, CheckerUse::ladder(n_samples, refined))) return rc;
   if (n_samples < 1) return fail(MKH_E_INVALID, "%s: n_samples = %d must be >= 1", who, n_samples);
   if (!f || !f->edge_collision || !f->n_edge_collisions || !f->edge_margin)
     return fail(MKH_E_INVALID, "%s: free_io and its outputs edge_collision, n_edge_collisions, edge_margin are required", who);
@@ -2888,7 +2404,6 @@ static int32_t refine_pass(Stager& st, int B, int T, const double* d_q, const do
     p_idx = st.i32(WS_RF_IDX, 2 * R); p_eff = p_idx + R;
   }
   if (!st.ok()) return MKH_OK;
-  const int ck_nbody = rf ? rf->ck->model->nbody : 0, ck_np = rf ? rf->ck->dev.n_pairs : 0;
   if (rf) {                                                  // the state of p: its nodes' margins, effective flags, edges' margins
     clearance_rows(st, rf->ck, R, d_path, p_nm, nullptr, nullptr, nullptr, nullptr);
     ST_LAUNCH(st, launch_ladder_free_tracked(stream, d_trk, p_nm, (long long)R, p_eff));
@@ -2910,22 +2425,7 @@ static int32_t refine_pass(Stager& st, int B, int T, const double* d_q, const do
       ST_LAUNCH(st, launch_lr_step(stream, B, T, (int)nq, (int)nv, njnt, jnt, d_q, d_w, max_step_sq, ct, cdir, nt, ndir, w));
       return;
     }
-    const MkhProblem* const ck = rf->ck;
-    if (ct >= 0 && ck->cv.n_cv == 0) ST_LAUNCH(st, launch_lr_check(stream, ck->d_wide, ck_nbody, (int)nq, ck_np, B, T, rf->M, ct, cdir, w, fw.trip));
-    if (ct >= 0 && ck->cv.n_cv > 0) {
-      // general convex pairs: chunks of floor(check_rows / (1 + 2M)) instances (>= 1: sweep_refuse), convex_check_kernel — once
-      // for all the slots of the check — then the check on each; the stream orders the reuse of the buffer
-      const long long per = ck->check_rows / (1 + 2 * rf->M);
-      mkh::CvCheckArgs a{};
-      a.mode = mkh::kCvCheckRefine; a.M = rf->M; a.T = T; a.ct = ct; a.cdir = cdir;
-      a.r = w.r; a.x = w.x; a.r_trk = w.r_trk; a.xst = w.xst; a.xcv = w.xcv; a.bad = w.bad;
-      for (a.first = 0; a.first < B && st.ok(); a.first += per) {
-        a.count = B - a.first < per ? B - a.first : per;
-        const mkh::CvChunk c{a.first, a.count, ck->d_cv_check, ck->cv.n_cv};
-        ST_LAUNCH(st, launch_convex_check(stream, ck->d_wide, ck->cv.pair, ck->cv.chain_adr, ck->cv.chain, ck->cv.n_cv, a, ck->d_cv_check));
-        ST_LAUNCH(st, launch_lr_check(stream, ck->d_wide, ck_nbody, (int)nq, ck_np, B, T, rf->M, ct, cdir, w, fw.trip, c));
-      }
-    }
+    if (ct >= 0) lr_check_step(st, rf->ck, B, T, rf->M, ct, cdir, w, fw.trip);
     ST_LAUNCH(st, launch_lr_step_free(stream, B, T, (int)nq, (int)nv, njnt, jnt, d_q, d_w, max_step_sq, ct, cdir, nt, ndir, w, fw));
   };
   auto loop = [&](size_t t) -> int32_t {
@@ -2977,7 +2477,7 @@ static int32_t ladder_refine_call(MkhProblem* p, MkhProblem* ck, int32_t n_sampl
   if (const int32_t rc = refuse_checker(p, who)) return rc;
   if (const int32_t rc = refuse_unwind(flags, who)) return rc;
   if (free_call) {
-    if (const int32_t rc = sweep_refuse_for(p, ck, who, n_samples < 1 ? 1 : n_samples, refinement_item(n_samples))) return rc;
+    if (const int32_t rc = sweep_refuse_for(p, ck, who, CheckerUse::refinement(n_samples))) return rc;
     if (n_samples < 1) return fail(MKH_E_INVALID, "%s: n_samples = %d must be >= 1", who, n_samples);
     if (!fio || !fio->edge_collision || !fio->n_edge_collisions || !fio->edge_margin)
       return fail(MKH_E_INVALID, "%s: free_io and its outputs edge_collision, n_edge_collisions, edge_margin are required", who);

@@ -1,6 +1,7 @@
 // Launchers of the small kernels around the loop launches of the outer-loop entry points (mkh_solve_multistart,
 // mkh_solve_multistart_set, mkh_solve_goalset, mkh_solve_trajectory, mkh_solve_keyframes, mkh_solve_trajectory_multistart, the ladder calls) and of
-// the seed tables in front of them: declared once, for the thirteen files that define them and for minkhip.hip, which calls them — a signature that
+// the seed tables in front of them: declared once, for the thirteen files that define them and for the two host files that call them
+// (minkhip.hip; checker_host.hip: the clearance, sweep and check launchers and their pre-passes) — a signature that
 // drifts fails to compile in the file that drifted.  In minkhip.hip the multi-start calls, the ladder calls and the goal set
 // launch the seeding, the seed-table query and the target fan-out from one place, the loop stage ms_loops(), which also asks for
 // their workspace slots (WS_C_FT / PT / CT, the WS_IN_SEEDS slab); mkh_solve_trajectory_multistart has its own (time-major) ones.
@@ -11,6 +12,8 @@
 #include <cstdint>
 
 namespace mkh {
+
+struct CvPre;                      // a checker's lists of general convex pairs (convex_chain.h)
 
 // What launch_tmf_check / launch_lr_check read of a chunk of their items on a checker WITH general convex pairs: its first item,
 // their count, and the distances launch_convex_check (below) left for the chunk.  cv null: all items in one launch — a checker
@@ -125,7 +128,7 @@ hipError_t launch_tms_gather_i32(hipStream_t stream, const int32_t* all, int32_t
 // the same candidate's row t − 1 where the row is eligible, NaN elsewhere — on the CHECKER's per-body descriptor (a device
 // WideProblem; with general convex pairs the rows go in chunks — `chunk`, above — behind launch_convex_check, without a chunk
 // it has none; nbody and n_pairs choose the build as in launch_clearance, the LDS is
-// sweep_lds_bytes').  converged_all absent: every row counts as converged.  launch_tmf_edge_flags: the chosen candidate's
+// checker_plan.h's sweep_lds_bytes).  converged_all absent: every row counts as converged.  launch_tmf_edge_flags: the chosen candidate's
 // edge_collision through the (instance, waypoint) strides of the caller's layout, and n_edge_collisions (B,).
 hipError_t launch_tmf_check(hipStream_t stream, const void* wide_problem, int nbody, int nq, int n_pairs, int B, int S, int T, int M,
                             const double* q_all, const int32_t* converged_all, int32_t* status_all, double* node_margin_all,
@@ -183,7 +186,7 @@ hipError_t launch_lr_guard(hipStream_t stream, int B, int T, int nq, int nv, int
 // runs between the loop launch of waypoint commit_t and the launch_lr_step_free that commits it, on the CHECKER's per-body
 // descriptor (a device WideProblem; with general convex pairs the instances go in chunks — `chunk`, above — behind
 // launch_convex_check, without a chunk it has none; nbody and n_pairs choose the build as in launch_clearance, the
-// LDS is sweep_lds_bytes'); M >= 1 interior samples per edge.
+// LDS is checker_plan.h's sweep_lds_bytes); M >= 1 interior samples per edge.
 constexpr int kLrMaxSlots = 8;
 int lr_check_slots(int M);
 struct LrFreeWork {
@@ -238,14 +241,12 @@ struct SweepArgs {
   double* cv;
   int32_t n_cv;
 };
-size_t sweep_lds_bytes(int nbody, int nq, int n_pairs);
 hipError_t launch_sweep(hipStream_t stream, const void* wide_problem, int nbody, int nq, int n_pairs, const SweepArgs& a);
 // The pre-pass of a chunk (convex_sweep.hip): the general convex distance routine on every interior sample of the chunk's swept
 // edges with finite ends, one lane per (edge, sample, general convex pair), into a.cv — which the caller passes on to launch_sweep
-// with the same SweepArgs.  pair / chain_adr / chain: the checker's lists of those pairs (convex_pre.hip CvPre), n_cv = a.n_cv.
-// ipw: items per wavefront, 0 = chosen from the size of the chunk.
-hipError_t launch_convex_sweep(hipStream_t stream, const void* wide_problem, const int32_t* pair, const int32_t* chain_adr,
-                               const int32_t* chain, const SweepArgs& a, int ipw);
+// with the same SweepArgs.  C: the checker's lists of those pairs, C.n_cv = a.n_cv.
+// ipw: items per wavefront, 0 = chosen from the size of the chunk (checker_plan.h cv_items_per_wave).
+hipError_t launch_convex_sweep(hipStream_t stream, const void* wide_problem, const CvPre& C, const SweepArgs& a, int ipw);
 // The pre-pass of the checks that judge rows INSIDE their launch (convex_check.hip), for a checker WITH general convex pairs: the
 // distances of those pairs on every row the check of the items [first, first + count) could read — its conditions without the
 // node's verdict —, one lane per (item, row, pair), into row (item − first)·rows_per_item + j of `out` (mkh_problem_set_check_rows).
@@ -267,8 +268,7 @@ struct CvCheckArgs {
   const double *r, *x;
   const int32_t *r_trk, *xst, *xcv, *bad;
 };
-hipError_t launch_convex_check(hipStream_t stream, const void* wide_problem, const int32_t* pair, const int32_t* chain_adr,
-                               const int32_t* chain, int n_cv, const CvCheckArgs& a, double* out);
+hipError_t launch_convex_check(hipStream_t stream, const void* wide_problem, const CvPre& C, const CvCheckArgs& a, double* out);
 // the nodes of a checked ladder: tracked_out[i] = tracked[i] != 0 && node_margin[i] >= 0
 hipError_t launch_ladder_free_tracked(hipStream_t stream, const int32_t* tracked, const double* node_margin, long long total,
                                       int32_t* tracked_out);

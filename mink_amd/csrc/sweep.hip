@@ -13,6 +13,7 @@
 // dynamic LDS, per group: poses (7, nbody) | q(u) (nq) | a (nq) | b ⊖ a (nq) doubles
 #include <hip/hip_runtime.h>
 
+#include "checker_plan.h"
 #include "clearance_row.h"
 #include "lie_dev.h"
 #include "outer_launch.h"
@@ -103,14 +104,9 @@ __global__ __launch_bounds__(256) void ladder_free_tracked_kernel(const int32_t*
   tracked_out[e] = (tracked[e] != 0 && node_margin[e] >= 0.0) ? 1 : 0;
 }
 
-// The launch's LDS bytes (beyond 64 KB the launch is refused): four slices where a quarter of a wavefront holds an edge.
-size_t sweep_lds_bytes(int nbody, int nq, int n_pairs) {
-  const bool quarter = nbody <= 32 && n_pairs <= 32;
-  return (size_t)(quarter ? 4 : 1) * (7 * (size_t)nbody + 3 * (size_t)nq) * sizeof(double);
-}
-
+// (the launch's LDS bytes — beyond 64 KB it is refused — and one or four edges per wavefront: checker_plan.h)
 hipError_t launch_sweep(hipStream_t stream, const void* wide_problem, int nbody, int nq, int n_pairs, const SweepArgs& a) {
-  const bool quarter = nbody <= 32 && n_pairs <= 32;
+  const bool quarter = checker_quarter(nbody, n_pairs);
   const size_t lds = sweep_lds_bytes(nbody, nq, n_pairs);
   const long long n = a.count > 0 ? a.count : a.N, blocks = quarter ? (n + 3) / 4 : n;
   if (a.N < 1 || a.M < 1 || n_pairs < 1 || lds > 64 * 1024 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;

@@ -19,6 +19,7 @@
 // dynamic LDS, per group: poses (7, nbody) | q(u) (nq) | a (nq) | b ⊖ a (nq) doubles
 #include <hip/hip_runtime.h>
 
+#include "checker_plan.h"
 #include "clearance_row.h"
 #include "lie_dev.h"
 #include "outer_launch.h"
@@ -162,7 +163,7 @@ __global__ __launch_bounds__(256) void tmf_edge_flags_kernel(int B, int S, int T
 hipError_t launch_tmf_check(hipStream_t stream, const void* wide_problem, int nbody, int nq, int n_pairs, int B, int S, int T, int M,
                             const double* q_all, const int32_t* converged_all, int32_t* status_all, double* node_margin_all,
                             double* edge_margin_all, const CvChunk& chunk) {
-  const bool quarter = nbody <= 32 && n_pairs <= 32;
+  const bool quarter = checker_quarter(nbody, n_pairs);
   const size_t lds = sweep_lds_bytes(nbody, nq, n_pairs);
   const long long R = (long long)B * S, N = R * T;
   // (a chunk and the general convex pairs' distances come together or not at all)

@@ -77,6 +77,19 @@ def test_chunking_and_leading_shapes(nat):
         assert np.abs(part.distance - ref.distance[:23]).max() <= TOL and np.abs(part.margin - ref.margin[:23]).max() <= TOL
 
 
+@pytest.mark.parametrize("max_rows", [5, 1])
+def test_pre_evaluated_pairs_do_not_depend_on_the_chunking(nat, max_rows):
+    """`shapes` (general convex pairs behind their pre-pass, analytic pairs beside them): 7 rows in chunks of 5 + 2 and of one row
+    each against one launch, bit for bit — the buffer of pre-evaluated pairs is reused by every chunk."""
+    _, _, q = cr.fixture("shapes")
+    whole, chunked = _checker("shapes", 256), _checker("shapes", max_rows)
+    a, b = whole.clearance(q[:7], return_distances=True), chunked.clearance(q[:7], return_distances=True)
+    whole.close(); chunked.close()
+    assert a.margin.shape == (7,)
+    for f in a._fields:
+        np.testing.assert_array_equal(getattr(a, f), getattr(b, f), err_msg=f)
+
+
 @pytest.mark.parametrize("name", ["shapes", "shapes_wide", "ur5e_convex", "g1"])
 def test_rows_with_nan_or_inf_are_in_collision(nat, name):
     """A row of q with a NaN or an infinite entry: every d_k NaN, margin NaN, pair 0, every pair violated, in collision — on
