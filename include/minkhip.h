@@ -1097,6 +1097,89 @@ int32_t mkh_problem_set_sweep_rows(MkhProblem *checker, int64_t rows /* 0: free 
 int32_t mkh_problem_set_check_rows(MkhProblem *checker, int64_t rows /* 0: free the buffer */);
 
 /*
+ * Certified sweep: a sweep whose sample count follows from how far the edge can move the checker's geoms, and which says whether
+ * the SPACE BETWEEN its samples is free as well — "this motion is free", not "these postures are".  A fixed n_samples is too many
+ * for a millimetre of wrist correction and far too few for a radian of a shoulder; here every edge gets the count its own motion
+ * asks for at a stated resolution, and a lower bound of the clearance over the whole edge.  It builds on THE RULE OF CLEARANCE
+ * and THE RULE OF THE SWEEP, whose terms stand unchanged.
+ *
+ * THE RULE OF THE CERTIFIED SWEEP (mkh_certified_sweep).
+ *   The reach table  (mkh_checker_motion_reach) is a model constant of a checker, (n_pairs, njnt, 2) doubles.  For pair k with
+ *                  geoms g1, g2 on bodies b1, b2 take the body chains from the world to b1 and to b2 and drop their common prefix:
+ *                  joints on common ancestors move both geoms rigidly together and do not change their distance.  For a joint j
+ *                  of body c on what remains of the chain of geom g, c = c_0 -> c_1 -> ... -> c_m = body(g):
+ *                    coef[k][j][0]  multiplies the joint's LINEAR weight: 1 for a slide or free joint, 0 otherwise.
+ *                    coef[k][j][1]  multiplies its ANGULAR weight: 0 for a slide; for a hinge, ball or free joint
+ *                                   rho = |jnt_pos_j| + D_after(c, j) + sum_{i=1..m} (|body_pos[c_i]| + D(c_i)) + |geom_pos_g| + r_g.
+ *                  D(c) bounds how far body c's own joints move its origin: over its slide joints max(|lo - qpos0|, |hi - qpos0|)
+ *                  (+inf for an unlimited slide), plus over its hinge and ball joints 2 |jnt_pos|; +inf for a free joint anywhere
+ *                  but as joint j itself.  D_after(c, j) is the same sum over the joints of c behind j.  r_g is the radius of the
+ *                  geom about its own centre: sphere r; capsule r + half; ellipsoid max(size); cylinder hypot(r, half); box
+ *                  |size|; mesh the largest hull-vertex norm; plane +inf (a plane on the world body has an empty chain: its
+ *                  radius is never used).  Joints on neither remaining chain have both coefficients 0.
+ *   Edge weights   from the sweep's own b (-) a: hinge rot = |dq|; slide lin = |dq|; ball rot = the angle of the shortest arc;
+ *                  free lin = |dp| and rot = the arc's angle.
+ *   Motion bound   L_k = sum_j (coef0 lin_j + coef1 rot_j), where a weight of 0 contributes 0 whatever its coefficient (inf * 0
+ *                  never occurs); motion = max_k L_k.  The edge is UNBOUNDED when motion is not finite, or when a limited slide
+ *                  joint lies outside its range at either end (D presumes the range).
+ *   Sample count   M = clamp(ceil(motion / resolution) - 1, 1, max_samples) — one division of doubles —, capped = 1 where the
+ *                  unclamped value exceeds max_samples (so an infinite motion is capped); an UNBOUNDED edge has M = max_samples.
+ *   Points         u_i = i / (M + 1) for i = 0 .. M + 1, BOTH ends included; q(u_i) by the sweep's blend, unchanged — the ends
+ *                  too, so q(u_{M+1}) is a (+) 1 (b (-) a) —; m_{k,i} = (d_k(q(u_i)) - dmin_k) + 0.0 by THE RULE OF CLEARANCE,
+ *                  unchanged: the pair list, the ddetect cap, the cull, "a NaN decides".
+ *   Outputs        margin = min_i min_k m_{k,i}; sample = the lowest i that attains it; pair = the pair of that point's clearance.
+ *                  lower_bound = min over the segments i = 0 .. M and the pairs k of
+ *                                1/2 ((m_{k,i} + m_{k,i+1}) - L_k / (M + 1));
+ *                  segment and bound_pair attain it, lowest segment first, then lowest pair.  An UNBOUNDED edge has
+ *                  lower_bound = -inf, segment = bound_pair = 0.  n_samples = M; motion; capped.
+ *                  verdict = 2 (COLLIDES) iff !(margin >= 0); 1 (CERTIFIED FREE) iff margin >= 0 and lower_bound >= 0;
+ *                  0 (UNDECIDED) otherwise.
+ *   A NaN or an infinity in a or b: margin = lower_bound = motion = NaN; sample = pair = segment = bound_pair = capped = 0;
+ *   n_samples = 1; verdict = 2.
+ *
+ * Why it is a proof.  A point of geom g is carried by joint j at most coef0 lin_j + coef1 rot_j far when the joint alone moves
+ * along the edge — a slide by its travel, a rotation about an anchor by the arc, whose lever is at most rho —, and the joints of
+ * an edge move in proportion to u; so each geom of pair k moves, relative to the other, at most L_k |du| over a piece du of the
+ * edge, and d_k — a distance between the two sets, clamped at ddetect_k or not, a minimum of 1-Lipschitz functions either way —
+ * is Lipschitz in u with constant L_k.  Between two neighbouring points, 1 / (M + 1) apart, d_k therefore cannot fall below the
+ * crossing point of the two cones that descend from them, which is the expression above.  The clamped distance and the
+ * distance ddetect_k of a culled pair are lower bounds of the true one.  So a CERTIFIED edge keeps every pair at or above its dmin
+ * for EVERY u in [0, 1], not only at the points.  Certification needs margins at the points of about resolution / 2; the margins
+ * of a checker never exceed ddetect - dmin, so a resolution at or above 2 (ddetect - dmin) certifies nothing — edges come out
+ * undecided; that is not an error.
+ *
+ * mkh_certified_sweep evaluates N edges, q_from and q_to (N, nq); all ten outputs are (N,) and required.  Host pointers
+ * (synchronous; staged whole) or device pointers with MKH_FLAG_DEVICE_PTRS (asynchronous on the stream); one launch either way,
+ * and N is not bound by the checker's max_batch.  The reach table is filled and uploaded at the handle's first such call.
+ * MKH_E_INVALID before any device work: resolution not finite or <= 0; max_samples outside [1, 4096]; N < 1; any other flag.  The
+ * checker is refused as mkh_clearance refuses it, and in addition: a checker WITH general convex pairs (cylinder-box,
+ * ellipsoid-*, mesh hulls) with MKH_E_INVALID, whatever sweep_rows it has — such pairs are not certified yet: sample counts
+ * that vary per edge do not fit the chunks of sweep_rows —; MKH_E_LIMIT when a group's slice of LDS — the sweep's, and three rows
+ * of n_pairs doubles beside it (L_k, the previous point's margins, this point's distances) — exceeds 64 KB.  "One call in
+ * flight per checker handle" holds as for mkh_clearance.
+ * mkh_checker_motion_reach writes the (n_pairs, njnt, 2) reach table to host memory; it needs no device work and serves any
+ * checker with collision pairs.
+ */
+typedef struct MkhCertifiedSweepIO {
+  double  *margin;       /* (N,)  every field required */
+  int32_t *sample;       /* (N,)  0 .. n_samples + 1 */
+  int32_t *pair;         /* (N,) */
+  double  *lower_bound;  /* (N,) */
+  int32_t *segment;      /* (N,)  0 .. n_samples */
+  int32_t *bound_pair;   /* (N,) */
+  int32_t *n_samples;    /* (N,) */
+  double  *motion;       /* (N,) */
+  int32_t *capped;       /* (N,) */
+  int32_t *verdict;      /* (N,)  MKH_SWEEP_* */
+} MkhCertifiedSweepIO;
+#define MKH_SWEEP_UNDECIDED 0
+#define MKH_SWEEP_CERTIFIED 1
+#define MKH_SWEEP_COLLIDES  2
+int32_t mkh_certified_sweep(MkhProblem *checker, int32_t N, const double *q_from /* (N, nq) */, const double *q_to /* (N, nq) */,
+                            double resolution, int32_t max_samples, const MkhCertifiedSweepIO *io, int32_t flags, void *hip_stream);
+int32_t mkh_checker_motion_reach(MkhProblem *checker, double *out /* (n_pairs, njnt, 2), host memory */);
+
+/*
  * Ladder-graph trajectory IK: S IK solutions per waypoint (a "rung"), computed independently of each other, and a dynamic
  * program over the T rungs that picks the path — complete first, free of joint-space jumps second, shortest third.  It is the
  * per-waypoint search ACROSS candidates that mkh_solve_trajectory_multistart leaves out: that call keeps one whole candidate,

@@ -712,6 +712,29 @@ class SweptClearanceOut(NamedTuple):
     pair: object
 
 
+CERTIFIED_SWEEP_FIELDS = ("margin", "sample", "pair", "lower_bound", "segment", "bound_pair", "n_samples", "motion", "capped", "verdict")
+SWEEP_UNDECIDED, SWEEP_CERTIFIED, SWEEP_COLLIDES = 0, 1, 2     # MKH_SWEEP_*
+
+
+class MkhCertifiedSweepIO(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in CERTIFIED_SWEEP_FIELDS]
+
+
+class CertifiedSweepOut(NamedTuple):
+    """mkh_certified_sweep of N edges (include/minkhip.h "THE RULE OF THE CERTIFIED SWEEP"), (N,) each: margin, lower_bound and
+    motion float64, the rest int32."""
+    margin: object
+    sample: object
+    pair: object
+    lower_bound: object
+    segment: object
+    bound_pair: object
+    n_samples: object
+    motion: object
+    capped: object
+    verdict: object
+
+
 LADDER_FREE_IO_FIELDS = ("edge_collision", "n_edge_collisions", "edge_margin", "node_margin", "edge_margin_all")
 
 
@@ -877,6 +900,11 @@ def lib() -> C.CDLL:
     L.mkh_swept_clearance.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(MkhSweptClearanceIO),
                                       C.c_int32, C.c_void_p]
     L.mkh_swept_clearance.restype = C.c_int32
+    L.mkh_certified_sweep.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_int32,
+                                      C.POINTER(MkhCertifiedSweepIO), C.c_int32, C.c_void_p]
+    L.mkh_certified_sweep.restype = C.c_int32
+    L.mkh_checker_motion_reach.argtypes = [C.c_void_p, C.c_void_p]
+    L.mkh_checker_motion_reach.restype = C.c_int32
     L.mkh_problem_set_sweep_rows.argtypes = [C.c_void_p, C.c_int64]
     L.mkh_problem_set_sweep_rows.restype = C.c_int32
     L.mkh_problem_set_check_rows.argtypes = [C.c_void_p, C.c_int64]
@@ -920,6 +948,7 @@ EXPORTED_SYMBOLS = (
     "mkh_swept_clearance", "mkh_problem_set_sweep_rows", "mkh_problem_set_check_rows", "mkh_ladder_select_free", "mkh_solve_trajectory_ladder_free",
     "mkh_ladder_refine_free", "mkh_solve_trajectory_ladder_free_refined",
     "mkh_select_trajectory_candidates", "mkh_solve_trajectory_multistart_free",
+    "mkh_certified_sweep", "mkh_checker_motion_reach",
 )
 
 LIE_OPS = {"se3_log": (0, 7, 0, (6,)), "se3_jlog": (1, 7, 0, (6, 6)), "se3_ljacinv": (2, 6, 0, (6, 6)),
@@ -1440,6 +1469,34 @@ class NativeProblem:
         io = MkhSweptClearanceIO(ptr(out.margin), ptr(out.sample), ptr(out.pair))
         with self._lock:
             _check(lib().mkh_swept_clearance(self.handle, N, ptr(q_from), ptr(q_to), int(n_samples), C.byref(io), devp, stream))
+        return out
+
+    def certified_sweep(self, q_from, q_to, resolution: float, max_samples: int = 64) -> CertifiedSweepOut:
+        """mkh_certified_sweep with this handle as the checker: the edges from q_from (N, nq) to q_to (N, nq), each at the sample
+        count its motion bound asks for at `resolution`, at most `max_samples` → the ten (N,) outputs of include/minkhip.h "THE
+        RULE OF THE CERTIFIED SWEEP".  numpy in → numpy out (synchronous); torch CUDA tensors in → torch tensors out, asynchronous
+        on the current stream."""
+        m = self.nmodel.model
+        prep, empty, ptr, stream, devp = _call_kit(q_from)
+        q_from, q_to = prep(q_from), prep(q_to)
+        if len(q_from.shape) != 2 or int(q_from.shape[1]) != m.nq or int(q_from.shape[0]) < 1:
+            raise ValueError(f"q_from must have shape (N, {m.nq}) with N >= 1, got {tuple(q_from.shape)}")
+        if tuple(q_to.shape) != tuple(q_from.shape):
+            raise ValueError(f"q_to must have q_from's shape {tuple(q_from.shape)}, got {tuple(q_to.shape)}")
+        N = int(q_from.shape[0])
+        out = CertifiedSweepOut(*[empty((N,), np.float64 if f in ("margin", "lower_bound", "motion") else np.int32)
+                                  for f in CERTIFIED_SWEEP_FIELDS])
+        io = MkhCertifiedSweepIO(*[ptr(x) for x in out])
+        with self._lock:
+            _check(lib().mkh_certified_sweep(self.handle, N, ptr(q_from), ptr(q_to), float(resolution), int(max_samples), C.byref(io),
+                                             devp, stream))
+        return out
+
+    def motion_reach(self) -> np.ndarray:
+        """mkh_checker_motion_reach: the (n_pairs, njnt, 2) reach table of this handle's pair list."""
+        out = np.empty((self.n_pairs, self.nmodel.model.njnt, 2))
+        with self._lock:
+            _check(lib().mkh_checker_motion_reach(self.handle, out.ctypes.data))
         return out
 
     def set_sweep_rows(self, rows: int) -> None:

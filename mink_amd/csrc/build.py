@@ -130,6 +130,7 @@ HAND_WRITTEN = (
     ("clearance", "clearance of a batch of rows: mkh_clearance, the collision check behind the multi-start loops"),
     ("ladder_refine_free", "lr_check_kernel: the collision check between the loops of mkh_ladder_refine_free"),
     ("sweep", "swept clearance of edges: mkh_swept_clearance, the edge mask of the checked ladder calls"),
+    ("certified_sweep", "certified sweep of edges: mkh_certified_sweep — motion-bounded sample counts and the bound between samples (sweep.hip's flags)"),
     ("convex_sweep", "convex_sweep_kernel: the general convex pairs of a sweep's samples, in front of sweep_kernel (convex_pre.hip's flags)"),
     ("convex_check", "convex_check_kernel: the general convex pairs of the rows tmf_check_cv_kernel / lr_check_cv_kernel judge inside their launch (convex_sweep.hip's flags)"),
     ("trajectory_free", "tmf_check_kernel: nodes and edges of mkh_solve_trajectory_multistart_free / mkh_select_trajectory_candidates (sweep.hip's flags)"),

@@ -9,6 +9,11 @@
 // always was.
 #include "checker_host.h"
 
+#include <algorithm>
+#include <cmath>
+
+#include "motion_bound.h"
+
 using namespace mkh;
 
 static_assert(kStInCollision == MKH_ST_IN_COLLISION, "outer_launch.h: the bit clearance.hip sets");
@@ -25,6 +30,33 @@ template <class F>
 static void run_chunks(Stager& st, long long total, long long per, F&& enqueue) {
   if (per < 1) { st.latch(hipErrorInvalidValue); return; }
   for (long long first = 0; first < total && st.ok(); first += per) enqueue(first, total - first < per ? total - first : per);
+}
+
+// The reach table of the checker's pair list on the host (motion_bound.h), filled once.
+static const std::vector<double>& reach_of(MkhProblem* ck) {
+  if (ck->h_reach.empty()) {
+    const HostModel& m = *ck->model;
+    auto ptr = [](const auto& v) { return v.empty() ? nullptr : v.data(); };
+    const MotionModel mm{m.nbody, m.njnt, ptr(m.body_parentid), ptr(m.body_jntnum), ptr(m.body_jntadr), ptr(m.body_pos), ptr(m.jnt_type),
+                         ptr(m.jnt_limited), ptr(m.jnt_pos), ptr(m.jnt_range), ptr(m.jnt_qpos0), ptr(m.geom_bodyid), ptr(m.geom_type),
+                         ptr(m.geom_size), ptr(m.geom_pos), ptr(m.geom_dataid), ptr(m.mesh_vertadr), ptr(m.mesh_vertnum),
+                         ptr(m.h_mesh_vert)};
+    const int np = ck->dev.n_pairs;
+    ck->h_reach.assign((size_t)np * m.njnt * 2 + 1, 0.0);      // (+ 1: a model without joints still has a table that is "filled")
+    motion_reach(mm, np, ck->pair_geom.data(), ck->h_reach.data());
+  }
+  return ck->h_reach;
+}
+
+// ... and on the device, uploaded once (synchronous: a constant of the handle from here on).
+static int32_t ensure_reach(MkhProblem* ck) {
+  if (ck->d_reach) return MKH_OK;
+  const std::vector<double>& h = reach_of(ck);
+  HIP_OK(hipMalloc((void**)&ck->d_reach, h.size() * sizeof(double)));
+  const hipError_t e = hipMemcpy(ck->d_reach, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
+  if (e != hipSuccess) { (void)hipFree(ck->d_reach); ck->d_reach = nullptr; }
+  HIP_OK(e);
+  return MKH_OK;
 }
 
 namespace mkh {
@@ -228,6 +260,61 @@ int32_t mkh_swept_clearance(MkhProblem* ck, int32_t N, const double* q_from, con
   st.down(io->margin, a.margin, Nz * sizeof(double));
   st.down(io->sample, a.sample, Nz * sizeof(int32_t));
   st.down(io->pair, a.pair, Nz * sizeof(int32_t));
+  return st.finish();
+}
+
+int32_t mkh_checker_motion_reach(MkhProblem* ck, double* out) {
+  const char* const who = "mkh_checker_motion_reach";
+  if (!ck) return fail(MKH_E_INVALID, "null problem");
+  if (!out) return fail(MKH_E_INVALID, "%s: out is required", who);
+  if (ck->dev.n_pairs < 1) return fail(MKH_E_INVALID, "%s: the checker has no collision pairs (a problem with CollisionAvoidanceLimits is one)", who);
+  const std::vector<double>& h = reach_of(ck);
+  std::copy(h.begin(), h.begin() + (size_t)ck->dev.n_pairs * ck->model->njnt * 2, out);
+  return MKH_OK;
+}
+
+// (include/minkhip.h "THE RULE OF THE CERTIFIED SWEEP"; kernel: certified_sweep.hip): one launch
+int32_t mkh_certified_sweep(MkhProblem* ck, int32_t N, const double* q_from, const double* q_to, double resolution, int32_t max_samples,
+                            const MkhCertifiedSweepIO* io, int32_t flags, void* hip_stream) {
+  const char* const who = "mkh_certified_sweep";
+  if (!ck) return fail(MKH_E_INVALID, "null problem");
+  if (N < 1) return fail(MKH_E_INVALID, "%s: N = %d must be >= 1", who, N);
+  if (!std::isfinite(resolution) || !(resolution > 0.0))
+    return fail(MKH_E_INVALID, "%s: resolution = %g must be finite and > 0", who, resolution);
+  if (max_samples < 1 || max_samples > 4096) return fail(MKH_E_INVALID, "%s: max_samples = %d must be in [1, 4096]", who, max_samples);
+  if (flags & ~MKH_FLAG_DEVICE_PTRS) return fail(MKH_E_INVALID, "%s: flags = %d: only MKH_FLAG_DEVICE_PTRS is accepted", who, flags);
+  if (!q_from || !q_to || !io || !io->margin || !io->sample || !io->pair || !io->lower_bound || !io->segment || !io->bound_pair ||
+      !io->n_samples || !io->motion || !io->capped || !io->verdict)
+    return fail(MKH_E_INVALID, "%s: q_from, q_to, io and its ten outputs are required", who);
+  if (const int32_t rc = refuse(ck, who, CheckerUse::certified())) return rc;
+  const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
+  HIP_OK(hipSetDevice(ck->model->device));
+  if (const int32_t rc = ensure_reach(ck)) return rc;
+  Stager st{ck, (hipStream_t)hip_stream, devp, "certified_sweep"};
+  const size_t Nz = N, nq = ck->model->nq, f8 = sizeof(double), i4 = sizeof(int32_t);
+  CertifiedArgs a{};
+  a.N = N; a.resolution = resolution; a.max_samples = max_samples; a.reach = ck->d_reach;
+  a.from = st.up(WS_C_Q, q_from, Nz * nq);
+  a.to = st.up(WS_SW_TO, q_to, Nz * nq);
+  a.margin = io->margin; a.lower_bound = io->lower_bound; a.motion = io->motion;
+  a.sample = io->sample; a.pair = io->pair; a.segment = io->segment; a.bound_pair = io->bound_pair;
+  a.n_samples = io->n_samples; a.capped = io->capped; a.verdict = io->verdict;
+  if (!devp) {                                                 // (OUT_LEN: margin | lower_bound | motion; OUT_PICK: the seven integers)
+    double* const f = st.f64(WS_OUT_LEN, 3 * Nz);
+    int32_t* const i = st.i32(WS_OUT_PICK, 7 * Nz);
+    if (f && i) {
+      a.margin = f; a.lower_bound = f + Nz; a.motion = f + 2 * Nz;
+      a.sample = i; a.pair = i + Nz; a.segment = i + 2 * Nz; a.bound_pair = i + 3 * Nz;
+      a.n_samples = i + 4 * Nz; a.capped = i + 5 * Nz; a.verdict = i + 6 * Nz;
+    }
+  }
+  if (!st.ok()) return st.finish();
+  ST_LAUNCH(st, launch_certified_sweep(st.stream, ck->d_wide, ck->model->nbody, (int)nq, ck->dev.n_pairs, a));
+  if (devp) return st.finish();
+  st.down(io->margin, a.margin, Nz * f8); st.down(io->lower_bound, a.lower_bound, Nz * f8); st.down(io->motion, a.motion, Nz * f8);
+  st.down(io->sample, a.sample, Nz * i4); st.down(io->pair, a.pair, Nz * i4); st.down(io->segment, a.segment, Nz * i4);
+  st.down(io->bound_pair, a.bound_pair, Nz * i4); st.down(io->n_samples, a.n_samples, Nz * i4); st.down(io->capped, a.capped, Nz * i4);
+  st.down(io->verdict, a.verdict, Nz * i4);
   return st.finish();
 }
 

@@ -25,6 +25,11 @@ constexpr size_t clearance_lds_bytes(int nbody, int n_pairs) {
 constexpr size_t sweep_lds_bytes(int nbody, int nq, int n_pairs) {
   return (size_t)(checker_quarter(nbody, n_pairs) ? 4 : 1) * (7 * (size_t)nbody + 3 * (size_t)nq) * sizeof(double);
 }
+// ... and of a certified sweep (certified_sweep.hip): the sweep's slice and three rows of n_pairs per group — the motion bounds
+// L_k of the edge, the previous point's margins, the current point's distances.
+constexpr size_t certified_lds_bytes(int nbody, int nq, int n_pairs) {
+  return (size_t)(checker_quarter(nbody, n_pairs) ? 4 : 1) * (7 * (size_t)nbody + 3 * (size_t)nq + 3 * (size_t)n_pairs) * sizeof(double);
+}
 constexpr size_t kCheckerLdsMax = 64 * 1024;
 // Items per wavefront of the general convex pre-passes (convex_pre.hip, and why): ≈ 4 096 wavefronts when the launch allows
 // (2 resident per SIMD x 1 024 SIMDs, twice over), at most 64 items each.
@@ -47,6 +52,7 @@ struct CheckerUse {
                                    // through sweep_rows; 0: it sweeps none
   int32_t item_rows;               // > 0: it judges rows INSIDE a launch, so many per item, general convex pairs through
                                    // check_rows; 0: it judges none
+  int32_t certifies = 0;           // 1: a certified sweep — per-edge sample counts, which the sweep_rows chunking does not hold
   // (a sample count may reach these before the entry point has judged it: below 1 it counts as 1)
   static constexpr int32_t samples(int32_t M) { return M < 1 ? 1 : M; }
   static constexpr int32_t tracking_item(int32_t M) { return 1 + samples(M); }          // the node, the edge into it
@@ -56,18 +62,24 @@ struct CheckerUse {
   static constexpr CheckerUse tracking(int32_t M) { return {0, tracking_item(M)}; }
   static constexpr CheckerUse refinement(int32_t M) { return {samples(M), refinement_item(M)}; }
   static constexpr CheckerUse ladder(int32_t M, bool refined) { return refined ? refinement(M) : sweep(M); }
+  static constexpr CheckerUse certified() { return {0, 0, 1}; }
 };
 
 // ---- the refusal: which test fails first, in the order the messages have always had
 enum CheckerRefusal {
   CK_OK, CK_NO_PAIRS, CK_NO_WIDE, CK_CONVEX_NOT_PRE, CK_POSES_LDS,       // what a clearance refuses
-  CK_NO_CHECK_ROWS, CK_NO_SWEEP_ROWS, CK_CHECK_ROWS_SHORT, CK_SWEEP_ROWS_SHORT, CK_SWEEP_LDS
+  CK_NO_CHECK_ROWS, CK_NO_SWEEP_ROWS, CK_CHECK_ROWS_SHORT, CK_SWEEP_ROWS_SHORT, CK_SWEEP_LDS,
+  CK_CERT_CONVEX, CK_CERT_LDS                                            // what a certified sweep refuses beyond a clearance
 };
 constexpr CheckerRefusal checker_refusal(const CheckerShape& s, const CheckerUse& u) {
   if (s.n_pairs < 1) return CK_NO_PAIRS;
   if (!s.has_wide) return CK_NO_WIDE;
   if (s.convex_pairs && s.n_cv == 0) return CK_CONVEX_NOT_PRE;
   if ((size_t)s.nbody * 7 * sizeof(double) > kCheckerLdsMax) return CK_POSES_LDS;
+  if (u.certifies) {
+    if (s.convex_pairs) return CK_CERT_CONVEX;
+    return certified_lds_bytes(s.nbody, s.nq, s.n_pairs) > kCheckerLdsMax ? CK_CERT_LDS : CK_OK;
+  }
   if (u.sweeps_edges < 1 && u.item_rows < 1) return CK_OK;
   if (s.n_cv > 0) {                                            // room for the distances of the general convex pairs
     if (u.item_rows > 0 && s.check_rows == 0) return CK_NO_CHECK_ROWS;
@@ -130,6 +142,16 @@ inline int32_t checker_refuse(const CheckerShape& s, const CheckerUse& u, const 
       snprintf(buf, sizeof buf, "%s: %d bodies, nq = %d: the poses of a sample and the three rows of q beside them do not fit 64 KB of LDS "
                                 "(7 nbody + 3 nq <= 8192)", who, s.nbody, s.nq);
       break;
+    case CK_CERT_CONVEX:
+      snprintf(buf, sizeof buf, "%s: the checker has general convex pairs (cylinder-box, ellipsoid-*, mesh hulls): they are not certified "
+                                "yet — the per-edge sample counts of a certified sweep do not fit the chunks of sweep_rows", who);
+      break;
+    case CK_CERT_LDS:
+      code = MKH_E_LIMIT;
+      snprintf(buf, sizeof buf, "%s: %d bodies, nq = %d, %d pairs: the sweep's slice and the three rows of pairs beside it do not fit "
+                                "64 KB of LDS (%s(7 nbody + 3 nq + 3 n_pairs) <= 8192)", who, s.nbody, s.nq, s.n_pairs,
+               checker_quarter(s.nbody, s.n_pairs) ? "4 " : "");
+      break;
   }
   err = buf;
   return code;
@@ -170,6 +192,10 @@ constexpr bool all_chunks_hold() {
   return true;
 }
 static_assert(all_chunks_hold(), "a use the refusal serves has a chunk of at least one item");
+static_assert(checker_refusal(CheckerShape{3, 2, true, true, 7, 6, 1, 64, 64}, CheckerUse::certified()) == CK_CERT_CONVEX &&
+              checker_refusal(CheckerShape{3, 0, false, true, 7, 6, 1, 0, 0}, CheckerUse::certified()) == CK_OK &&
+              checker_refusal(CheckerShape{2720, 0, false, true, 7, 6, 1, 0, 0}, CheckerUse::certified()) == CK_CERT_LDS,
+              "a certified sweep: no general convex pairs whatever the buffers hold, and its own LDS slice");
 static_assert(checker_refusal(CheckerShape{3, 2, true, true, 7, 6, 1, 1, 4}, CheckerUse::refinement(2)) == CK_CHECK_ROWS_SHORT &&
               checker_refusal(CheckerShape{3, 2, true, true, 7, 6, 1, 1, 5}, CheckerUse::refinement(2)) == CK_SWEEP_ROWS_SHORT,
               "check_rows is judged before sweep_rows");

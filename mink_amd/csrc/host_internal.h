@@ -182,6 +182,11 @@ struct MkhProblem : mkh::ProblemSelect {     // (what creation decided and plan_
   double* d_cv = nullptr;          // [max_batch][n_cv][7]
   CvRows cv_sweep;                 // a chunk of swept samples (mkh_problem_set_sweep_rows)
   CvRows cv_check;                 // the rows a check judges inside its launch (mkh_problem_set_check_rows)
+  // the certified sweep's reach table (motion_bound.h), [n_pairs][njnt][2]: filled from pair_geom and uploaded at the first call
+  // that needs it (checker_host.hip ensure_reach), then a constant of the handle
+  std::vector<int32_t> pair_geom;  // [n_pairs][2]: the geom ids of the pair list
+  std::vector<double> h_reach;
+  double* d_reach = nullptr;
   double* d_qkeep = nullptr;       // fused loops with a redo launch behind them: the call's q as it came (q_out may alias it)
   int8_t* d_warm = nullptr;        // MKH_FLAG_WARM_START: active set of every instance after the previous solve (max_batch × nv)
   int warm_age = 0, warm_B = 0;    // solves since the state was reset / the batch size it belongs to

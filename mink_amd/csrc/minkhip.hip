@@ -314,6 +314,7 @@ int32_t mkh_problem_create_diag(MkhModel* m, const MkhProblemDesc* d, int32_t ma
   p->device = m->device;
   p->max_batch = max_batch;
   p->diag = diag;
+  p->pair_geom = plan.pair_geom;
   if (const int32_t rc = upload_problem(p, plan)) { mkh_problem_destroy(p); return rc; }
   if (p->wide_only) {
     snprintf(p->last_kernel, sizeof(p->last_kernel), "ik_wide_kernel");
@@ -329,7 +330,7 @@ void mkh_problem_destroy(MkhProblem* p) {
   for (void* w : p->owned) (void)hipFree(w);
   (void)hipFree(p->d_dev); (void)hipFree(p->d_taps); (void)hipFree(p->d_work);
   (void)hipFree(p->d_lane); (void)hipFree(p->d_warm); (void)hipFree(p->d_qkeep);
-  (void)hipFree(p->d_cv); (void)hipFree(p->cv_sweep.d); (void)hipFree(p->cv_check.d); (void)hipFree(p->d_dev_tight); (void)hipFree(p->d_status_tight);
+  (void)hipFree(p->d_cv); (void)hipFree(p->cv_sweep.d); (void)hipFree(p->cv_check.d); (void)hipFree(p->d_reach); (void)hipFree(p->d_dev_tight); (void)hipFree(p->d_status_tight);
   (void)hipFree(p->s_iters);
   (void)hipFree(p->s_de); (void)hipFree(p->s_dJ); (void)hipFree(p->s_dG); (void)hipFree(p->s_dh); (void)hipFree(p->s_dbox); (void)hipFree(p->d_clk);
   (void)hipFree(p->d_wide);

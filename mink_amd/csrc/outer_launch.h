@@ -242,6 +242,18 @@ struct SweepArgs {
   int32_t n_cv;
 };
 hipError_t launch_sweep(hipStream_t stream, const void* wide_problem, int nbody, int nq, int n_pairs, const SweepArgs& a);
+// certified sweep (certified_sweep.hip; include/minkhip.h "THE RULE OF THE CERTIFIED SWEEP"): N edges from row e of `from` to row e
+// of `to`, each at the sample count its own motion bound asks for, on launch_sweep's geometry.  reach: the checker's
+// (n_pairs, njnt, 2) table on the device (motion_bound.h).  Every output (N,) and required.  A checker of analytic pairs only.
+struct CertifiedArgs {
+  long long N;
+  const double *from, *to, *reach;
+  double resolution;
+  int32_t max_samples;
+  double *margin, *lower_bound, *motion;
+  int32_t *sample, *pair, *segment, *bound_pair, *n_samples, *capped, *verdict;
+};
+hipError_t launch_certified_sweep(hipStream_t stream, const void* wide_problem, int nbody, int nq, int n_pairs, const CertifiedArgs& a);
 // The pre-pass of a chunk (convex_sweep.hip): the general convex distance routine on every interior sample of the chunk's swept
 // edges with finite ends, one lane per (edge, sample, general convex pair), into a.cv — which the caller passes on to launch_sweep
 // with the same SweepArgs.  C: the checker's lists of those pairs, C.n_cv = a.n_cv.

@@ -123,6 +123,7 @@ struct ProblemPlan {
   std::vector<CollisionPairDev> pairs;           // vert1 / vert2 null: pair_vert
   std::vector<long long> pair_vert;              // [pair][2]: offset of a mesh geom's first vertex in the model's mesh array, in doubles; −1: a primitive
   std::vector<PairCull> culls;
+  std::vector<int32_t> pair_geom;                // [pair][2]: the geom ids of the pair list (motion_bound.h reads the model through them)
   std::vector<double> dcost, dwgain;
   int lane_class = 0;              // build_lane_problem's size class (0: none, 32: the large descriptor, else the small one)
   LaneProblem2 lane;

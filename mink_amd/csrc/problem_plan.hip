@@ -682,6 +682,7 @@ void plan_pairs(Ctx& c) {
         (side ? cp.nvert2 : cp.nvert1) = m.mesh_vertnum[km];
       }
       c.pl.pair_vert.push_back(vert[0]); c.pl.pair_vert.push_back(vert[1]);
+      c.pl.pair_geom.push_back(g1); c.pl.pair_geom.push_back(g2);
       cp.type1 = t1; cp.type2 = t2; cp.body1 = m.geom_bodyid[g1]; cp.body2 = m.geom_bodyid[g2];
       for (int i = 0; i < 3; ++i) { cp.size1[i] = m.geom_size[3 * g1 + i]; cp.size2[i] = m.geom_size[3 * g2 + i];
                                     cp.lpos1[i] = m.geom_pos[3 * g1 + i]; cp.lpos2[i] = m.geom_pos[3 * g2 + i]; }

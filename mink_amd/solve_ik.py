@@ -704,6 +704,29 @@ class SweptClearance(NamedTuple):
     in_collision: object
 
 
+class CertifiedSweep(NamedTuple):
+    """Result of CollisionChecker.certified_sweep, each with the leading shape of the edges (include/minkhip.h "THE RULE OF THE
+    CERTIFIED SWEEP").  `n_samples` interior samples were chosen from `motion`, the bound on how far the edge moves any pair of
+    geoms against each other (`capped`: the resolution asked for more than max_samples).  `margin`, `sample`, `pair`: the
+    smallest clearance margin over the n_samples + 2 points, ends included, the (lowest) point 0 .. n_samples + 1 that attains
+    it and that point's pair.  `lower_bound`: what the margin of any pair can fall to BETWEEN the points at the worst, attained
+    on `segment` 0 .. n_samples by `bound_pair`; -inf where the motion has no bound.  `verdict`: 2 collides — not (margin >= 0) —,
+    1 certified free — margin >= 0 and lower_bound >= 0: every pair keeps its minimum distance along the whole edge —, 0
+    undecided.  `certified` = verdict == 1, `in_collision` = verdict == 2."""
+    margin: object
+    sample: object
+    pair: object
+    lower_bound: object
+    segment: object
+    bound_pair: object
+    n_samples: object
+    motion: object
+    capped: object
+    verdict: object
+    certified: object
+    in_collision: object
+
+
 class CollisionChecker:
     """Clearance of configurations on the device, and the `collision_check=` of solve_ik_multistart / solve_ik_solutions /
     solve_ik_goalset (include/minkhip.h "THE RULE OF CLEARANCE").
@@ -835,6 +858,42 @@ class CollisionChecker:
         device = (a.device.index if a.device.index is not None else 0) if is_torch else 0
         o = self._handle(native_model(self.model, device)).swept_clearance(a.reshape(-1, nq), b.reshape(-1, nq), int(n_samples))
         return SweptClearance(o.margin.reshape(lead), o.sample.reshape(lead), o.pair.reshape(lead), ~(o.margin >= 0.0).reshape(lead))
+
+    def certified_sweep(self, q_from, q_to, resolution: float, max_samples: int = 64) -> CertifiedSweep:
+        """The straight joint-space moves from `q_from` to `q_to` — (nq,), (N, nq) or (..., nq), the same shape — swept at a
+        sample count of their own and judged BETWEEN the samples as well (include/minkhip.h "THE RULE OF THE CERTIFIED SWEEP").
+        `resolution` (metres, > 0): how far a pair of geoms may move against each other between two neighbouring points; an
+        edge whose motion bound is `motion` gets ceil(motion / resolution) - 1 interior samples, at least 1 and at most
+        `max_samples` (1 .. 4096), and both ends are judged too.  Certifying an edge takes margins of about resolution / 2 at
+        the points, so a resolution at or above twice (detection distance - minimum distance) certifies nothing.  A checker
+        with general convex pairs (cylinder-box, ellipsoids, mesh hulls) is refused: MinkHipError.
+        numpy in → numpy out; torch tensors on a device in → torch tensors there, on the current stream."""
+        from .configuration import native_model
+
+        if self._closed:
+            raise ValueError("the collision checker is closed")
+        nq = self.model.nq
+        is_torch = nat._is_torch(q_from) and nat._is_torch(q_to) and q_from.device.type == "cuda" and q_to.device == q_from.device
+        a, b = (q_from, q_to) if is_torch else (_host_array(q_from, "q_from"), _host_array(q_to, "q_to"))
+        if a.ndim < 1 or int(a.shape[-1]) != nq or tuple(b.shape) != tuple(a.shape):
+            raise ValueError(f"q_from and q_to must have one shape (..., {nq}), got {tuple(a.shape)} and {tuple(b.shape)}")
+        lead = tuple(int(x) for x in a.shape[:-1])
+        if 0 in lead:
+            raise ValueError(f"q_from holds no row: shape {tuple(a.shape)}")
+        device = (a.device.index if a.device.index is not None else 0) if is_torch else 0
+        o = self._handle(native_model(self.model, device)).certified_sweep(a.reshape(-1, nq), b.reshape(-1, nq), float(resolution),
+                                                                           int(max_samples))
+        return CertifiedSweep(*[x.reshape(lead) for x in o], (o.verdict == nat.SWEEP_CERTIFIED).reshape(lead),
+                              (o.verdict == nat.SWEEP_COLLIDES).reshape(lead))
+
+    def motion_reach(self, device: int = 0) -> np.ndarray:
+        """The reach table of the pair list, (n_pairs, njnt, 2): per pair and joint, what multiplies the joint's linear and its
+        angular travel along an edge in the motion bound of that pair (include/minkhip.h "THE RULE OF THE CERTIFIED SWEEP")."""
+        from .configuration import native_model
+
+        if self._closed:
+            raise ValueError("the collision checker is closed")
+        return self._handle(native_model(self.model, int(device))).motion_reach()
 
     def close(self) -> None:
         with self._lock:
