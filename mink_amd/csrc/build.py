@@ -43,12 +43,12 @@ W3_WOOD = ((44, 44, 32), (44, 44, 48), (32, 32, 32), (32, 32, 48),    # (NT, NR,
            (24, 24, 32), (24, 24, 48), (16, 16, 32), (16, 16, 48),    # ... and, for NT ≤ 24, the 4-waves map (TabW4; same suffix _w3: "one more wave")
            (44, 44, 36), (44, 44, 52))                                # F_COM (ComTask rows / up to 24 task rows) and its fused loops: round 5, ik_kernel.h MKH_WOOD_SPLIT
 # one problem per workgroup (round 6; ik_kernel.h MKH_ONE_SHOT): a twin of the humanoid-size one-more-wave build WITHOUT the persistent
-# loop's machinery (ticket draws, double-buffered inputs, loop-carried scalars) — launched when the grid is the batch (minkhip.hip plan_launch()).
+# loop's machinery (ticket draws, double-buffered inputs, loop-carried scalars) — launched when the grid is the batch (solve_host.hip plan_launch()).
 # Measured: `44_32_r44_w3o` 0.713 -> 0.703 ms on the headline; the F_COM twin `44_36_r44_w3o` (12 spilled VGPRs) 0.350 -> 0.352 ms at
 # 16 384 instances of the G1 full example — not built.
 # ... and its twin on FOUR waves per SIMD, `44_32_r44_w4o` (a fourth entry "w4"; ik_kernel.h MKH_W4P, tab_asm.inc TabW4<44>: the product form
 # alone below 128 VGPRs, history slots of one double, everything in LDS that is dead after the pair lanes in one union) — the headline's
-# build from the batch size at which it measures faster (minkhip.hip plan_launch()).
+# build from the batch size at which it measures faster (solve_host.hip plan_launch()).
 W3_WOOD_ONE_SHOT = ((44, 44, 32), (44, 44, 32, "w4"))
 WOOD_FEATS = (32, 48, 33, 36, 52)      # F_WOOD, | F_STEPS, | F_TAPS (cycle-counter profiling only), | F_COM, | F_COM | F_STEPS
 # low-rank start WITH half-space rows (round 6; ik_kernel.h wood_start "half-space rows"): (NT, NR, FEAT) on the 2-waves map,
@@ -110,7 +110,8 @@ VARIANTS = tuple([Variant(nt, ft) for nt in NTS for ft in FEATS]
                  + [(VariantW4 if e[3:] == ("w4",) else Variant)(e[0], e[2], e[1], w3=True, one_shot=True) for e in W3_WOOD_ONE_SHOT])
 # the hand-written translation units behind the generated ones, in link order: (name, what it holds)
 HAND_WRITTEN = (
-    ("minkhip", "host side of the C ABI: handles, the solve path, the outer-loop entry points"),
+    ("minkhip", "host side of the C ABI: handles, problem upload, the outer-loop entry points"),
+    ("solve_host", "host side of the plain solve: launch planning, launching, the routes of a call's arrays, its five entry points (host code only)"),
     ("checker_host", "host side of the collision checker: its entry points and the stages of the checked calls (host code only)"),
     ("problem_plan", "host-only planning of models and problems (no HIP runtime call)"),
     ("lane_variants", "the lane-per-problem and row-per-problem kernels of small arms"),

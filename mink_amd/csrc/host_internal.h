@@ -1,6 +1,7 @@
-// What the host translation units of the C ABI share: minkhip.hip (the handles, the solve path, the outer-loop entry points) and
-// checker_host.hip (the collision checker's calls and stages).  The error string and its one writer, the handles, the workspace
-// and the Stager every outer-loop call stages through — and nothing else.
+// What the host translation units of the C ABI share: minkhip.hip (the handles, the outer-loop entry points), solve_host.hip (the
+// plain solve: launch planning, launching and the four ways a call's arrays travel) and checker_host.hip (the collision checker's
+// calls and stages).  The error string and its one writer, the handles, the workspace and the Stager every outer-loop call stages
+// through — and nothing else.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,6 +14,7 @@
 #include "../../include/minkhip.h"
 #include "convex_chain.h"
 #include "problem_plan.h"
+#include "solve_plan.h"
 
 // Experiment switches (A/B runs, sweeps, phase censuses): environment variables MKH_DEBUG_* that change kernel selection, launch
 // shapes or caps.  They exist only in builds made with -DMKH_DEBUG_SWITCHES (MKH_EXTRA_FLAGS=-DMKH_DEBUG_SWITCHES python -m
@@ -43,21 +45,20 @@ __attribute__((visibility("hidden"))) int32_t fail(int32_t code, const char* fmt
 
 // Small host-pointer calls (a control loop's single configuration: the reference's everyday use) go through ONE pinned,
 // device-visible host buffer: the kernel reads its inputs and writes its outputs across the bus itself — a launch and a
-// synchronize instead of five staged copies of ≈8 µs host time each, whatever their size.
-constexpr size_t kSmallCallBytes = 64 << 10;
+// synchronize instead of five staged copies of ≈8 µs host time each, whatever their size (mkh::kSmallCallBytes: solve_plan.h).
 struct PinnedScratch {
   char* host = nullptr;
   char* dev = nullptr;
   hipError_t ensure() {
     if (host) return hipSuccess;
-    if (hipError_t e = hipHostMalloc((void**)&host, kSmallCallBytes, hipHostMallocDefault)) { host = nullptr; return e; }
+    if (hipError_t e = hipHostMalloc((void**)&host, mkh::kSmallCallBytes, hipHostMallocDefault)) { host = nullptr; return e; }
     if (hipError_t e = hipHostGetDevicePointer((void**)&dev, host, 0)) { (void)hipHostFree(host); host = nullptr; return e; }
     return hipSuccess;
   }
   void release() { if (host) (void)hipHostFree(host); host = dev = nullptr; }
 };
 
-// A device buffer of the outer-loop entry points' workspace (MkhProblem::ws): grown to what a call needs (never beyond what
+// A device buffer of the outer-loop entry points' workspace (MkhProblem::ws) or of the plain solve's staging (MkhProblem::stage): grown to what a call needs (never beyond what
 // max_batch allows), kept for the next call, never shrunk.
 struct GrowBuf {
   void* p = nullptr;
@@ -158,7 +159,7 @@ struct CvRows {
 };
 
 struct MkhProblem : mkh::ProblemSelect {     // (what creation decided and plan_launch reads: problem_plan.h)
-  PinnedScratch small;             // run(), host pointers
+  PinnedScratch small;             // solve(), small host-pointer calls
   MkhModel* model = nullptr;
   int device = 0;                  // (copied: the destructor must not depend on the model still being alive)
   mkh::DeviceProblem dev{};
@@ -187,19 +188,16 @@ struct MkhProblem : mkh::ProblemSelect {     // (what creation decided and plan_
   std::vector<int32_t> pair_geom;  // [n_pairs][2]: the geom ids of the pair list
   std::vector<double> h_reach;
   double* d_reach = nullptr;
-  double* d_qkeep = nullptr;       // fused loops with a redo launch behind them: the call's q as it came (q_out may alias it)
   int8_t* d_warm = nullptr;        // MKH_FLAG_WARM_START: active set of every instance after the previous solve (max_batch × nv)
   int warm_age = 0, warm_B = 0;    // solves since the state was reset / the batch size it belongs to
   uint32_t* d_work = nullptr;      // ticket counter of the dynamic problem distribution (zeroed by the kernel's last draw)
-  // staging buffers for host-pointer calls
-  double *s_q = nullptr, *s_ft = nullptr, *s_pt = nullptr, *s_ct = nullptr, *s_v = nullptr;
+  // staging buffers of the plain solve's host-pointer calls, by table row (solve_plan.h SolveSlot; the per-instance ones sized
+  // for max_batch at their first use) — apart from ws[]: the outer-loop calls hold WS_IN_* while they run plain solves.  SS_QKEEP:
+  // fused loops with a redo launch behind them keep the call's q as it came (q_out may alias it)
+  GrowBuf stage[mkh::SS_COUNT];
   // host-pointer calls on large batches: copies of chunk c + 1 / c − 1 run beside the kernel of chunk c
   hipStream_t st_in = nullptr, st_out = nullptr;
   hipEvent_t ev_start = nullptr, ev_in[4] = {nullptr, nullptr, nullptr, nullptr}, ev_k[4] = {nullptr, nullptr, nullptr, nullptr};
-  int32_t* s_status = nullptr;
-  int32_t* s_iters = nullptr;      // [2][max_batch]: iterations, converged (mkh_solve_until, host-pointer calls)
-  size_t s_pt_cap = 0, s_ct_cap = 0;
-  double *s_de = nullptr, *s_dJ = nullptr, *s_dG = nullptr, *s_dh = nullptr, *s_dbox = nullptr;   // dense (plugin) rows
   // the outer-loop entry points' workspace, by role (WsRole)
   bool ws_tables = false;
   GrowBuf ws[WS_COUNT];

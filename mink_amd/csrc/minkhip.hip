@@ -2,7 +2,7 @@
 //
 // mkh_model_create / mkh_problem_create upload what problem_plan.hip plans on the host — the mjModel
 // fields and the Task/Limit plugin objects of one mink.solve_ik call site, flattened into lane tables
-// (mkh_types.h); mkh_solve launches the one-wavefront-per-problem kernel (ik_kernel.h).
+// (mkh_types.h); the outer-loop entry points run their loops through the plain solve of solve_host.hip.
 #include "../../include/minkhip.h"
 
 #include <hip/hip_runtime.h>
@@ -25,6 +25,7 @@
 #include "lie_dev.h"
 #include "outer_launch.h"
 #include "problem_plan.h"
+#include "solve_host.h"
 
 namespace mkh {
 // q_out = q ⊕ v·dt (mj_integratePos; Configuration.integrate, mink/configuration.py:214-226).
@@ -75,8 +76,7 @@ using namespace mkh;
 // MKH_FLAG_UNWIND_TURNS in front of an entry point that has no distinct-set selection to unwind for (include/minkhip.h).
 static int32_t refuse_unwind(int32_t flags, const char* who) {
   if (flags & MKH_FLAG_UNWIND_TURNS)
-    return fail(MKH_E_INVALID, "%s: MKH_FLAG_UNWIND_TURNS is honoured by mkh_solve_multistart_set and "
-                               "mkh_solve_trajectory_ladder_nodes only", who);
+    return fail(MKH_E_INVALID, kUnwindRefusalFmt, who);
   return MKH_OK;
 }
 
@@ -99,57 +99,8 @@ struct MkhSeedTable {
   double* d_w = nullptr;             // (2·n_frame): position weights, orientation weights
 };
 
-// The wavefront kernel's variants live in their own translation units (mink_amd/csrc/build.py generates one variant_<name>.hip
-// per compiled combination so that they build in parallel) and are reached through the generated table of variants.h; these are
-// the launchers of the other kernels (those of the outer-loop entry points' small kernels: outer_launch.h).
-namespace mkh {
-int launch_lane(int nv_max, bool loop, int grid, int lds_bytes, hipStream_t stream, const LaneProblem* P, const SolveArgs& a);
-int launch_quad(int nt, bool loop, int grid, hipStream_t stream, const void* P, const LaneDims& dims, const SolveArgs& a);   // returns its LDS bytes per wavefront
-int launch_wide(int grid, int lds_bytes, hipStream_t stream, const WideProblem* P, const SolveArgs& a, const TapArgs* taps, bool convex);
-constexpr int kLaneMinBatchLoop = 28672;  // fused loops of a small arm: row kernel below, lane kernel from here (M targets/s at 16 384: 39.7 vs 24.1, at 32 768: 42.4 vs 48.2)
-constexpr int kLaneMinBatch = 73728;  // plain solves of a small arm: row kernel below, lane kernel from here (plan_launch())
-}
-
-template <class T>
-static hipError_t ensure(T** buf, size_t n) {
-  if (*buf) return hipSuccess;
-  return hipMalloc((void**)buf, (n ? n : 1) * sizeof(T));
-}
-
-// The debug / plugin taps of a call: `alloc(host pointer, bytes, zero first)` returns the device-visible buffer the kernel
-// writes (nullptr for a tap the caller did not ask for).
-template <typename Alloc>
-static void assign_taps(const MkhTaps* taps, const DeviceProblem& P, size_t Bz, TapArgs& t, Alloc&& alloc) {
-  const size_t nv = P.nv;
-  t.t_xpos = (double*)alloc(taps->xpos, Bz * P.nbody * 3 * 8, false);
-  t.t_xquat = (double*)alloc(taps->xquat, Bz * P.nbody * 4 * 8, false);
-  t.t_frame_pose = (double*)alloc(taps->frame_pose, Bz * P.n_frame * 7 * 8, false);
-  t.t_subtree_com = (double*)alloc(taps->subtree_com, Bz * 3 * 8, true);
-  t.t_task_e = (double*)alloc(taps->task_e, Bz * P.n_rows_tap * 8, true);
-  t.t_task_J = (double*)alloc(taps->task_J, Bz * P.n_rows_tap * nv * 8, true);
-  t.t_H = (double*)alloc(taps->H, Bz * nv * nv * 8, false);
-  t.t_c = (double*)alloc(taps->c, Bz * nv * 8, false);
-  t.t_box_lo = (double*)alloc(taps->box_lo, Bz * nv * 8, false);
-  t.t_box_hi = (double*)alloc(taps->box_hi, Bz * nv * 8, false);
-  t.t_coll_G = (double*)alloc(taps->coll_G, Bz * P.n_pairs * nv * 8, true);
-  t.t_coll_h = (double*)alloc(taps->coll_h, Bz * P.n_pairs * 8, false);
-  t.t_qp_iters = (int32_t*)alloc(taps->qp_iters, Bz * 4, true);
-  t.t_cycles = (long long*)alloc(taps->cycles, Bz * 16 * 8, true);
-}
 
 
-// one launch of the workgroup-per-problem kernel: every instance (redo_mask = 0) or the ones a wavefront kernel flagged
-static int32_t launch_wide_kernel(MkhProblem* p, const SolveArgs& a, hipStream_t stream, int32_t redo_mask, const TapArgs* dtaps = nullptr) {
-  SolveArgs aw = a;
-  aw.redo_mask = redo_mask;
-  aw.work_counter = p->d_work;        // (redo_mask = 0: the kernel as THE path of a model draws its problems from it)
-  int grid = p->wide_grid < a.B ? p->wide_grid : a.B;
-  if (grid < 1) grid = 1;
-  const int rc = mkh::launch_wide(grid, p->wide_lds, stream, p->d_wide, aw, dtaps, p->convex_pairs);
-  if (rc != 0) return fail(MKH_E_HIP, "wide kernel: %s", hipGetErrorString((hipError_t)rc));
-  HIP_OK(hipGetLastError());
-  return MKH_OK;
-}
 
 extern "C" {
 
@@ -329,12 +280,11 @@ void mkh_problem_destroy(MkhProblem* p) {
   (void)hipSetDevice(p->device);
   for (void* w : p->owned) (void)hipFree(w);
   (void)hipFree(p->d_dev); (void)hipFree(p->d_taps); (void)hipFree(p->d_work);
-  (void)hipFree(p->d_lane); (void)hipFree(p->d_warm); (void)hipFree(p->d_qkeep);
+  (void)hipFree(p->d_lane); (void)hipFree(p->d_warm);
   (void)hipFree(p->d_cv); (void)hipFree(p->cv_sweep.d); (void)hipFree(p->cv_check.d); (void)hipFree(p->d_reach); (void)hipFree(p->d_dev_tight); (void)hipFree(p->d_status_tight);
-  (void)hipFree(p->s_iters);
-  (void)hipFree(p->s_de); (void)hipFree(p->s_dJ); (void)hipFree(p->s_dG); (void)hipFree(p->s_dh); (void)hipFree(p->s_dbox); (void)hipFree(p->d_clk);
+  (void)hipFree(p->d_clk);
   (void)hipFree(p->d_wide);
-  (void)hipFree(p->s_q); (void)hipFree(p->s_ft); (void)hipFree(p->s_pt); (void)hipFree(p->s_ct); (void)hipFree(p->s_v); (void)hipFree(p->s_status);
+  for (GrowBuf& g : p->stage) g.release();
   for (GrowBuf& g : p->ws) g.release();
   p->small.release();
   if (p->st_in) (void)hipStreamDestroy(p->st_in);
@@ -348,727 +298,22 @@ const char* mkh_problem_last_kernel(const MkhProblem* p) { return p ? p->last_ke
 int32_t mkh_problem_num_task_rows(const MkhProblem* p) { return p ? p->dev.n_rows_tap : 0; }
 int32_t mkh_problem_num_collision_pairs(const MkhProblem* p) { return p ? p->dev.n_pairs : 0; }
 
-static int grid_for(const MkhProblem* p, int B) {
-  int g = p->model->num_cus * p->blocks_per_cu;
-  return B < g ? B : g;
-}
-
-// Static rounds of a wavefront kernel's problem distribution (ik_kernel.h): each wavefront first walks `static` problems of its
-// XCD's contiguous row range, the rest of the batch goes through the ticket counter.  Static rows share cache lines inside one
-// L2 and cost no atomic; the ticket tail evens out what the static part left uneven — QP work varies by ±9 % per problem,
-// CUs differ by a few per cent — and that grows with the number of rounds.  Round 1 measured the 1.18-ms kernel of its day
-// flat between 4/16 and 14/16 static and took 7/8; on today's kernels (round 5, sweep by sixteenths at 65 536 / 32 768 / 16 384
-// G1 instances, the plugin workload and the G1 full example): 21 rounds per wavefront want 6 of them dynamic (0.779 -> 0.752 ms
-// on the headline), 10 want 2, 5 want 1, 32 of the two-waves plugin build 6 or more (1.681 -> 1.632 ms).
-// `uneven`: resident wavefronts per CU that do not divide by its four SIMDs (ten: 3 + 3 + 2 + 2) — a wavefront that shares its
-// SIMD with two others is slower than one that shares it with one, so nearly half of the batch goes through the counter there
-// (G1 full example 1.37 -> 1.24 ms).  MKH_DEBUG_STATIC_78=1: the old 7/8 rule; MKH_DEBUG_STATIC_16THS=n: n sixteenths (sweeps).
-// Below this many rounds per wavefront the batch is dealt statically as a whole (round 5, kernel ms on G1 config 3, ticket tail /
-// one strided share per wavefront: 12 288 instances = 4 rounds 0.186 / 0.177, 16 384 = 5.3 rounds 0.243 / 0.224, 20 480 = 6.7 rounds
-// 0.282 / 0.270, 24 576 = 8 rounds 0.321 / 0.335, 32 768 0.409 / 0.422, 65 536 0.754 / 0.827): over a few rounds the work of
-// the wavefronts has not drifted apart yet, and a ticket tail only adds its own ragged last round.  Round 1's threshold was 4.
-constexpr int kMinRoundsForTickets = 8;
-// Smallest batch that takes the four-waves product-form build of the humanoid-size low-rank start where its layout fits (plan_launch).
-// Kernel ms on G1 config 3, three-waves twin / four-waves build (docs/HISTORY.md, profiles/r17_batch_ab.txt; medians of three alternating
-// rounds): 14 336 instances 0.1566 / 0.1577 (a tie), 16 384 0.1656 / 0.1643 (−0.8 %: inside the parent's own spread), 32 768 0.3057 / 0.2739
-// (−10 %), 65 536 0.5707 / 0.5080 (−11 %), 131 072 1.1277 / 0.9882 (−12 %): the switch is where the gain is clear of run-to-run noise.
-constexpr long long kW4MinBatch = 32768;
-static int static_rounds_for(int per_wave, bool uneven, bool loops = false) {
-  static const bool static78 = dbg_env("MKH_DEBUG_STATIC_78") != nullptr;
-  static const int dbg_16ths = dbg_env("MKH_DEBUG_STATIC_16THS") ? atoi(dbg_env("MKH_DEBUG_STATIC_16THS")) : -1;
-  if (dbg_16ths >= 0 && dbg_16ths <= 16) return (per_wave * dbg_16ths) / 16;
-  if (dbg_16ths == 99) return INT32_MAX;                     // (no ticket counter at all: one strided share per wavefront)
-  if (static78) return (per_wave * 7) / 8;
-  if (uneven) return (per_wave * 9) / 16;
-  // (fused loops: a problem is 3 … 40 solves long and the threshold-terminated ones differ by that much — half of the batch
-  //  dynamic: converged targets of the headline's loop leg 5.45 -> 5.65 M/s; the fixed-count loops do not care)
-  if (loops) return per_wave / 2;
-  const int dyn = (3 * per_wave - 2) / 10;
-  return per_wave - (dyn < 1 ? 1 : dyn);
-}
-
-static int grid_for_variant(const MkhProblem* p, int B, int nt, int lds, bool w3 = false) {
-  int wpc = waves_per_cu(nt, lds, w3);
-  // diagnostic: cap the resident waves per CU (occupancy experiments, docs/HISTORY.md §7b); never raises it
-  static const int dbg = dbg_env("MKH_DEBUG_WAVES_PER_CU") ? atoi(dbg_env("MKH_DEBUG_WAVES_PER_CU")) : 0;
-  if (dbg > 0 && dbg < wpc) wpc = dbg;
-  int g = p->model->num_cus * wpc;
-  return B < g ? B : g;
-}
-
-int32_t mkh_problem_launch_info(const MkhProblem* p, int32_t B, int32_t* grid, int32_t* block, int32_t* lds_bytes,
-                                int32_t* tableau_rows) {
-  if (!p) return fail(MKH_E_INVALID, "null problem");
-  // what the most recent launch of this problem used (the variant depends on the call: taps, fused steps, the
-  // low-rank QP start); before any launch, the lean direct variant
-  if (grid) *grid = p->wide_only ? (p->wide_grid < B ? p->wide_grid : B) : (p->last_nt ? p->last_grid : grid_for(p, B));
-  if (block) *block = p->last_block;        // (64: one wavefront per workgroup; 256 on the workgroup-per-problem kernel)
-  if (lds_bytes) *lds_bytes = p->last_nt ? p->last_lds : p->lds_bytes;
-  if (tableau_rows) *tableau_rows = p->last_nt ? p->last_nt : p->nt;
-  return MKH_OK;
-}
-
-// Experiment builds with -DMKH_CLOCKS (tools/phase_clocks.py): MKH_DEBUG_CLOCKS=<file> makes every launch of this process
-// synchronous and writes its (B, 24) cycle stamps to <file> — phase profile of kernels that cannot be tapped
-static const char* clk_path() { static const char* const s = dbg_env("MKH_DEBUG_CLOCKS"); return s; }
-static hipError_t clk_begin(MkhProblem* p, SolveArgs& a, hipStream_t stream) {
-  if (!clk_path()) return hipSuccess;
-  if (!p->d_clk)
-    if (hipError_t e = hipMalloc((void**)&p->d_clk, (size_t)p->max_batch * 24 * sizeof(long long))) return e;
-  a.clk = p->d_clk;
-  if (hipError_t e = hipMemsetAsync(p->d_clk, 0, (size_t)a.B * 24 * sizeof(long long), stream)) return e;
-  // MKH_DEBUG_PHASE_STOP=k (tools/phase_census.sh): slot 15 of every row = the phase boundary after which the kernel abandons the solve
-  static const int stop = dbg_env("MKH_DEBUG_PHASE_STOP") ? atoi(dbg_env("MKH_DEBUG_PHASE_STOP")) : 0;
-  if (stop) {
-    std::vector<long long> h((size_t)a.B, (long long)stop);
-    if (hipError_t e = hipMemcpy2DAsync(p->d_clk + 15, 24 * sizeof(long long), h.data(), sizeof(long long), sizeof(long long), (size_t)a.B,
-                                        hipMemcpyHostToDevice, stream)) return e;
-    return hipStreamSynchronize(stream);
-  }
-  return hipSuccess;
-}
-static hipError_t clk_end(MkhProblem* p, int B, hipStream_t stream) {
-  if (!clk_path()) return hipSuccess;
-  std::vector<long long> h((size_t)B * 24);
-  if (hipError_t e = hipMemcpyAsync(h.data(), p->d_clk, h.size() * sizeof(long long), hipMemcpyDeviceToHost, stream)) return e;
-  if (hipError_t e = hipStreamSynchronize(stream)) return e;
-  if (FILE* f = fopen(clk_path(), "wb")) { fwrite(h.data(), sizeof(long long), h.size(), f); fclose(f); }
-  return hipSuccess;
-}
-
-// ---- launch planning: what a call runs (kernel family, build, grid, LDS bytes, ticket share), decided apart from running it
-enum class Family { WideOnly, Row, Lane, Wave };
-struct WaveLaunch {                // one launch of an ik_solve_kernel build
-  int nt = 0, nr = 0, feat = 0;
-  bool w3 = false, one_shot = false, w4 = false;
-  int grid = 0, lds = 0, static_rounds = INT32_MAX;
-  const VariantRow* v = nullptr;   // its row of the table (variants.h); null: not compiled — launch() reports it
-};
-struct LaunchPlan {
-  Family family = Family::Wave;
-  bool loop = false;               // row / lane kernels: the fused caller loop (steps / until) build
-  WaveLaunch main;                 // wavefront family: the launch on the handle's descriptor ...
-  WaveLaunch tight;                // ... and, when has_tight, the tight-rows launch in front of it (p->d_dev_tight)
-  bool has_tight = false, tight_redo = false;   // tight_redo: `main` follows as the redo launch of what `tight` flagged
-  bool cv_split = false;           // convex_contacts_kernel in front of the analytic collision build
-  bool wide_redo = false;          // the workgroup-per-problem kernel behind, on the flagged instances
-  bool keep_q = false;             // ... which then needs the call's q as it came (q_out aliases it)
-  char last_kernel[64] = "";       // what mkh_problem_last_kernel / mkh_problem_launch_info report after the call
-  int last_grid = 0, last_lds = 0, last_nt = 0, last_block = kWave;
-};
-
-static void plan_name(LaunchPlan& L, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(L.last_kernel, sizeof L.last_kernel, fmt, ap);
-  va_end(ap);
-}
-static const char* wave_name(const WaveLaunch& w) { return w.v ? w.v->kernel : "(not compiled)"; }
-
-// Fills the plan of one call.  Calls nothing of HIP and writes nothing to the handle: launch() below executes it.
-// (`taps`: the host copy of the call's tap pointers, or null)
-static int32_t plan_launch(const MkhProblem& P_, const SolveArgs& a, const TapArgs* taps, int32_t flags, LaunchPlan& L) {
-  const MkhProblem* p = &P_;
-  if (p->wide_only) {
-    if (taps && taps->t_cycles)
-      return fail(MKH_E_INVALID, "models beyond one wavefront (more than 64 bodies or dofs) run on the workgroup-per-problem kernel, "
-                                 "which has no cycle-counter tap");
-    L.family = Family::WideOnly;
-    plan_name(L, "ik_wide_kernel");
-    L.last_grid = p->wide_grid < a.B ? p->wide_grid : a.B; L.last_lds = p->wide_lds; L.last_nt = p->wide.nv + p->wide.max_rows;
-    L.last_block = kWideThreads;
-    return MKH_OK;
-  }
-  // Small arms (nv ≤ 8, hinge / slide joints, box limits) have two kernels of their own (plain solves without taps):
-  //   * a 16-lane ROW per problem (quad_kernel.h): four problems per wavefront, so 4 096 problems put one wavefront on
-  //     every SIMD and each problem still spreads its phases over its lanes.  Its fused loop below
-  //     kLaneMinBatchLoop instances (threshold-terminated UR5e loop at 4 096: 22.4 M targets/s against 8.4 on the
-  //     wavefront kernel and 6.0 on the lane kernel);
-  //   * one LANE per problem (lane_kernel.h): 64 problems per wavefront with every lane busy, one ≈48 µs dependent
-  //     instruction stream per problem whatever the batch — the best use of the machine once every SIMD has several
-  //     wavefronts to interleave.  Also the fused caller loop (steps / until) from kLaneMinBatchLoop instances.
-  // Measured on MI355X, UR5e config 2, M solves/s (tools/bench_small_arm.py; wavefront / row / lane kernel):
-  //   B = 256: 12 / 25 / 7.6    4 096: 119 / 219 / 90    8 192: 130 / 449 / 152    32 768: 150 / 839 / 528
-  //   65 536: 155 / 900 / 855    131 072: 158 / 1 169 / 1 609    1 048 576: 160 / 1 331 / 3 510
-  // — the row kernel up to kLaneMinBatch, the lane kernel beyond.
-  // MKH_FLAG_WAVE_KERNEL / _QUAD_KERNEL / _LANE_KERNEL force one of the three (parity switches).
-  const bool small_ok = !taps && a.do_qp && !(flags & MKH_FLAG_WAVE_KERNEL);
-  const bool small_arm = p->lane_nv && small_ok;                               // (nv ≤ 8: both kernels)
-  const bool loop = a.n_steps > 1 || a.q_out || a.pos_threshold >= 0.0;       // fused caller loop (steps / until)
-  L.loop = loop;
-  // (9 … 16 dofs — hands, mobile arms: the row kernel with sixteen column registers, whatever the batch; there is no lane
-  //  kernel of that size to hand over to)
-  // (MKH_FLAG_WARM_START: the row kernel keeps its partition in the handle's warm-start buffer like the wavefront kernels)
-  // (17 … 32 dofs or links, floating bases — H1, Go1, Spot, Allegro: the row kernel on TWO DPP rows per problem, two problems per
-  //  wavefront; its fused loop carries the floating base's quaternion from step to step.  Fused loops, kernel ms two-row against
-  //  wavefront kernel, 10 fixed steps / threshold loop, 4 096 … 65 536 instances (tools/bench_two_row_loop.py,
-  //  profiles/r07_two_row_loop.txt): H1 with its ComTask 3.2 … 3.7x faster, H1 with RelativeFrameTasks 2.4 … 3.0x (the
-  //  wavefront kernel needs its all-feature build for both), the Shadow hand without contacts 1.10 … 1.21x; a floating base under frame / posture tasks alone runs the
-  //  wavefront kernel's low-rank loop build faster — H1 0.87 … 0.95x, Go1 0.82 … 1.06x — and stays there.
-  //  MKH_FLAG_QUAD_KERNEL forces the two-row loop where it can run: not for a free joint that is no link, see quad_loop_ok.)
-  const bool two_row_loop_slower = p->quad_nt == 32 && loop && p->dev.nq != p->dev.nv && !p->has_relative && p->dev.n_com == 0 &&
-                                   !(flags & MKH_FLAG_QUAD_KERNEL);
-  const bool two_row_loop_bad = p->quad_nt == 32 && loop && !p->quad_loop_ok;
-  if (p->quad_nt && small_ok && !two_row_loop_slower && !two_row_loop_bad && !((flags & MKH_FLAG_LANE_KERNEL) && p->lane_nv) &&
-      (!p->lane_nv || a.B < (loop ? mkh::kLaneMinBatchLoop : mkh::kLaneMinBatch) || (flags & MKH_FLAG_QUAD_KERNEL))) {
-    L.family = Family::Row;
-    const int per_wave = p->quad_nt == 32 ? 2 : 4;
-    L.last_grid = (a.B + per_wave - 1) / per_wave; L.last_nt = p->quad_nt;   // (last_lds: what launch_quad returns)
-    plan_name(L, p->quad_nt == 8 ? (loop ? "ik_quad_kernel_loop" : "ik_quad_kernel")
-                                 : (p->quad_nt == 32 ? (loop ? "ik_quad_kernel_32_loop" : "ik_quad_kernel_32")
-                                                     : (loop ? "ik_quad_kernel_16_loop" : "ik_quad_kernel_16")));
-    return MKH_OK;
-  }
-  if (small_arm && (a.B >= (loop ? mkh::kLaneMinBatchLoop : mkh::kLaneMinBatch) || (flags & MKH_FLAG_LANE_KERNEL))) {
-    L.family = Family::Lane;
-    L.last_grid = (a.B + kWave - 1) / kWave; L.last_lds = p->lane_lds; L.last_nt = p->lane_nv;
-    plan_name(L, loop ? "ik_lane_kernel_%d_loop" : "ik_lane_kernel_%d", p->lane_nv);
-    return MKH_OK;
-  }
-  // A problem whose rows can outnumber the tableau's: the flagged instances once more, with every row — plain solves, calls
-  // with taps (the workgroup-per-problem kernel writes every tap but the cycle counters) and, round 5, the fused loops: an
-  // instance that overflows at some step runs its whole loop again from its ORIGINAL q, of which the handle keeps a copy for
-  // the duration of the call (q_out may alias q) — a device-to-device copy of B·nq doubles in front of the launch
-  L.wide_redo = p->d_wide && a.do_qp && a.status_out && !(taps && taps->t_cycles);
-  // (only when q_out really aliases q: otherwise the redo reads the caller's q, which the first launch did not touch — the copy
-  //  was a latency cost of every small-batch control loop with collision limits, round-5 advisor finding)
-  L.keep_q = L.wide_redo && a.q_out && a.q_out == a.q;
-  // lean production variant unless the call needs a feature it leaves out
-  int need = 0;
-  if (taps) need |= F_TAPS;
-  if (p->has_relative) need |= F_REL;
-  if (p->dev.n_com > 0) need |= F_COM;
-  if (p->dev.n_pairs > 0) need |= F_COLL;
-  if (loop) need |= F_STEPS;
-  const bool dense = p->dev.n_dense_rows > 0 || p->dev.n_dense_limit_rows > 0 || p->dev.dense_box;
-  if (dense) need |= 64;                                              // plugin rows: only the all-feature variants have them
-  // (general convex pairs of a plain solve: their contacts come from convex_contacts_kernel, launched in front of the
-  //  ANALYTIC build — round 5; without the pre-pass buffers, the build with the routine inside)
-  // Measured (ur5e_convex, one cylinder–box pair; in-kernel routine / split): 4 096 instances 0.165 / 0.207 ms, 16 384 0.463 / 0.505,
-  // 65 536 1.270 / 0.970: GJK is one long dependent chain per lane — in front of a small batch its latency adds to the solve's, on
-  // a large one 64 busy lanes per wavefront beat one busy lane per problem.  The split from 32 768 (instance, pair) items on.
-  const bool cv_split = need == F_COLL && p->convex_pairs && p->d_cv != nullptr && (long long)a.B * p->cv.n_cv >= 32768;
-  L.cv_split = cv_split;
-  int feat;
-  if (need == 0) feat = 0;
-  else if (need == 64) feat = F_DENSE;                                // plugin rows next to frame / posture tasks and box limits: lean build
-  else if (need == F_STEPS) feat = F_STEPS;
-  else if (need == F_COLL) feat = p->simple_pairs ? (F_COLL | F_SIMPLE_COLL) : ((p->convex_pairs && !cv_split) ? (F_COLL | F_CONVEX_COLL) : F_COLL);
-  // (fused loops over capsule-only collision sets — the Shadow hand's closed loop — have a build of their own: the
-  //  all-feature one spills 534 VGPRs at this tableau size)
-  else if (need == (F_COLL | F_STEPS) && p->simple_pairs) feat = F_COLL | F_SIMPLE_COLL | F_STEPS;
-  else if ((need & ~(F_REL | F_COM)) == 0) feat = F_REL | F_COM;      // box limits only: keeps the block-pivoting active set
-  else feat = (need & F_TAPS) ? F_ALL : (F_ALL & ~F_TAPS);
-  const bool rich = (feat & (F_ALL & ~F_STEPS)) != 0;
-  int nt = rich ? p->nt_full : p->nt, nr = 0, lds = rich ? p->lds_bytes_full : p->lds_bytes;
-  // Builds whose register-hungry phases are real calls (ik_kernel.h MKH_CALLS: FEAT 8 / 136 / 30) do not need the 256-register
-  // map of a 32-row tableau for the compiler's sake: a small arm keeps a small tableau (UR5e + 2 collision rows: phase 0 on
-  // 32 rows was a third of the solve) — at least `calls_nt_min` rows, so that the callees still find a usable register file
-  // Measured (UR5e + 2 collision rows, 4 096 instances): analytic pairs 0.060 ms on 32 rows, 0.049 on 16 and on 8; with a
-  // cylinder–box pair on the general convex routine (round 4: simplex in LDS, 143 VGPRs) 0.186 ms on 32 rows, 0.156 on 16
-  // and on 24 — round 3's register-resident GJK (196 VGPRs) wanted the 2-waves file and kept 32 rows.
-  static const int dbg_min = dbg_env("MKH_DEBUG_CALLS_NT") ? atoi(dbg_env("MKH_DEBUG_CALLS_NT")) : 0;
-  const int calls_nt_min = dbg_min ? dbg_min : 16;
-  const bool calls = feat == F_COLL || feat == (F_ALL & ~F_TAPS) || feat == (F_COLL | F_CONVEX_COLL);
-  if (calls && p->nt < 32) {
-    // (the smallest compiled size that holds the problem and the minimum, up to the 32 rows of nt_full)
-    const int v = size_class(p->nt > calls_nt_min ? p->nt : calls_nt_min, feat);
-    if (v && v <= nt) nt = v;
-    lds = nt == p->nt ? p->lds_bytes : lds_bytes_of(p->dev, nt, 0, kDirectFeat, false);
-  }
-  // Low-rank start when the problem qualifies and the diagonal part of H is not tiny against JwᵀJw
-  // (error amplification of the quasi-definite elimination ≈ eps·max cost²/min Dg ≤ 1e-9).
-  const double dg_min = a.damping + p->wood_min_diag;
-  // (taps: only the cycle counters / pivot counts exist in the low-rank variant — profiling)
-  const bool prof_only = taps && !taps->t_xpos && !taps->t_xquat && !taps->t_frame_pose && !taps->t_subtree_com &&
-                         !taps->t_task_e && !taps->t_task_J && !taps->t_H && !taps->t_c && !taps->t_box_lo &&
-                         !taps->t_box_hi && !taps->t_coll_G && !taps->t_coll_h;
-  if (p->wood_nt && ((need & ~(F_STEPS | F_COM)) == 0 || (need == F_TAPS && prof_only)) && a.do_qp &&
-      !(flags & MKH_FLAG_DIRECT_QP) && dg_min > 0.0 && dg_min >= 1e-7 * p->wood_max_cost2 &&
-      !((need & F_TAPS) && ((need & F_COM) || p->wood_big))) {   // (no profiling build of the F_COM low-rank start: direct variant)
-    nt = p->wood_nt; nr = p->wood_nr; lds = p->wood_lds_bytes;
-    feat = F_WOOD | (need & (F_STEPS | F_TAPS | F_COM)) | (p->wood_big ? F_COM : 0);
-  }
-  // ... and, round 6, with half-space rows (`48_40_r48`: analytic collision pairs; mkh_problem_create "low-rank start WITH half-space
-  // rows"): the launch that does the work of a plain collision solve — the tight-rows one where it exists, else the main one
-  const bool woodr_ok = a.do_qp && !taps && feat == F_COLL && !(flags & MKH_FLAG_DIRECT_QP) && dg_min > 0.0 && dg_min >= 1e-7 * p->wood_max_cost2;
-  if (woodr_ok && p->woodr_lds && !p->d_dev_tight && nt == 48) { nr = 48; lds = p->woodr_lds; feat = F_WOOD | F_COLL; }
-  // three resident waves per SIMD where a variant exists (FrameTask / PostureTask / RelativeFrameTask / ComTask, box limits) and
-  // the handle found its LDS layout worth it (mkh_problem_create: lds_bytes_w3 / wood_lds_bytes_w3)
-  const int w3_lds = nr ? p->wood_lds_bytes_w3 : p->lds_bytes_w3;
-  const bool w3 = w3_lds && !(flags & MKH_FLAG_TWO_WAVES) && find_variant(nt, nr, feat, true);
-  if (w3) lds = w3_lds;
-  // tight rows first (see mkh_problem_create): plain solves on the capsule-only collision build whose caller takes the status
-  const bool tight = p->d_dev_tight && (feat == (F_COLL | F_SIMPLE_COLL) || feat == F_COLL) && !nr && !w3 && a.do_qp && a.status_out && !taps &&
-                     !(flags & MKH_FLAG_FULL_ROWS);
-  const int num_cus = p->model->num_cus;
-  if (tight) {
-    // (the tight launch itself on the low-rank start: same descriptor, its own LDS layout)
-    const bool tight_wood = woodr_ok && p->woodr_lds_tight != 0;
-    WaveLaunch& t = L.tight;
-    L.has_tight = true;
-    L.tight_redo = !(p->diag & MKH_DIAG_NO_TIGHT_REDO);            // (tests: what the tight launch alone leaves flagged)
-    t.nt = p->nt_tight; t.nr = tight_wood ? 48 : 0; t.feat = tight_wood ? (feat | F_WOOD) : feat;
-    t.lds = tight_wood ? p->woodr_lds_tight : p->lds_tight;
-    t.grid = grid_for_variant(p, a.B, t.nt, t.lds, false);
-    const int pw = a.B / t.grid;
-    if (L.tight_redo && pw >= kMinRoundsForTickets)
-      t.static_rounds = static_rounds_for(pw, t.grid % num_cus == 0 && ((t.grid / num_cus) & 3) != 0);
-    t.v = find_variant(t.nt, t.nr, t.feat);
-  }
-  int grid = grid_for_variant(p, a.B, nt, lds, w3);
-  // One problem per workgroup instead of persistent wavefronts, for the humanoid-size builds of the one-more-wave map between
-  // 3.5 and 22 rounds (round 5): the hardware's workgroup dispatcher is a ticket counter that costs nothing, and a workgroup of
-  // these builds starts cheaply (the phases that need registers are callees).  Kernel ms on G1 config 3, persistent /
-  // one per workgroup: 12 288 instances 0.176 / 0.163, 16 384 0.224 / 0.209, 24 576 0.323 / 0.301, 32 768 0.411 / 0.390,
-  // 49 152 0.588 / 0.572, 65 536 0.751 / 0.743; outside the range it loses (8 192: 0.111 / 0.117, 131 072: 1.414 / 1.424), and so
-  // it does on every two-waves build (plugin workload 1.627 / 1.689, Shadow at 65 536 instances 1.186 / 1.226) and on the G1 full
-  // example's 25.6 rounds (1.244 / 1.265; at 16 384 instances 0.392 / 0.349).  Two, three, four problems per workgroup lie
-  // between the two shapes (65 536: 0.739 / 0.772 / 0.766).  The XCD still owns one contiguous row range
-  // (workgroup g: XCD g % 8, row g / 8 of its range).  MKH_DEBUG_PERSISTENT=1: persistent wavefronts everywhere (A/B).
-  static const bool persistent_only = dbg_env("MKH_DEBUG_PERSISTENT") != nullptr;
-  // (fused loops, measured: no difference — 13.55 / 13.58 ms for the headline's 20-step loop, converged targets 5.64 / 5.58 M/s — they stay persistent)
-  // Round 6: where the build has a twin compiled for this shape (`44_32_r44_w3o`, below) there is no upper end — kernel ms, persistent /
-  // one per workgroup on the twin: 12 288 instances 0.166 / 0.151, 65 536 0.737 / 0.701, 73 728 0.817 / 0.786, 131 072 1.400 / 1.379,
-  // 262 144 2.750 / 2.728 (below 3.5 rounds the persistent shape stays: 10 240 instances 0.145 on both).
-  static const int os_max = dbg_env("MKH_DEBUG_ONE_SHOT_MAX") ? atoi(dbg_env("MKH_DEBUG_ONE_SHOT_MAX")) : 22;    // (A/B switch: upper end of the range, in rounds)
-  const bool has_twin = w3 && !taps && find_variant(nt, nr, feat, true, true);
-  if (!persistent_only && !tight && w3 && nt == 44 && a.n_steps <= 1 && a.B > grid && 2 * (long long)a.B >= 7LL * grid &&
-      (has_twin || a.B <= (long long)os_max * grid))
-    grid = a.B;
-  // ... and, round 6, on a build WITHOUT the persistent loop's machinery where one exists (`44_32_r44_w3o`: build.py W3_WOOD_ONE_SHOT,
-  // ik_kernel.h MKH_ONE_SHOT — 78 → 32 spilled SGPRs in the kernel body, headline 0.713 → 0.703 ms; the F_COM twin measured no gain)
-  const bool one_shot = grid == a.B && has_twin;
-  // ... and, round 17, on FOUR waves per SIMD where the handle's layout fits (`44_32_r44_w4o`, mkh_problem_create: wood_lds_bytes_w4):
-  // from 3.5 rounds of ITS resident wavefronts (16 per CU: 4 096 on 256 CUs, so 14 336 instances) and from the batch size at which
-  // it measured clearly faster (kW4MinBatch; MKH_DEBUG_W4_MIN_BATCH=n moves the switch for A/B sweeps, a huge n turns the build off).
-  static const long long w4_min = dbg_env("MKH_DEBUG_W4_MIN_BATCH") ? atoll(dbg_env("MKH_DEBUG_W4_MIN_BATCH")) : kW4MinBatch;
-  const bool w4 = one_shot && nt == 44 && nr == 44 && feat == F_WOOD && p->wood_lds_bytes_w4 != 0 && a.B >= w4_min &&
-                  2 * (long long)a.B >= 7LL * 16 * num_cus && find_variant(nt, nr, feat, true, true, true);
-  if (w4) lds = p->wood_lds_bytes_w4;
-  // Distribution (ik_kernel.h): most of each wave's share is static — one contiguous row range per XCD — and the tail
-  // of the batch goes through the ticket counter (how much: static_rounds_for above).  Round 1, on G1 (kernel ms by static
-  // sixteenths): 16 → 1.283, 15 → 1.233, 14 → 1.183, 12 → 1.185, 8 → 1.193, 4 → 1.195, 0 → 1.264: every wave opening with an
-  // atomic costs more than the balance returns.  Short problems (the 8-row variants) and thin batches stay static.
-  const int per_wave = a.B / grid;
-  // (fused loops: problems of very different length — the ticket tail from four rounds on, as before)
-  const bool dynamic = nt > 8 && per_wave >= (a.n_steps > 1 ? 4 : kMinRoundsForTickets) && !tight;   // (a redo launch walks its static share, ik_kernel.h)
-  WaveLaunch& w = L.main;
-  w.nt = nt; w.nr = nr; w.feat = feat; w.w3 = w3; w.one_shot = one_shot; w.w4 = w4; w.grid = grid; w.lds = lds;
-  if (dynamic) w.static_rounds = static_rounds_for(per_wave, grid % num_cus == 0 && ((grid / num_cus) & 3) != 0, a.n_steps > 1);
-  w.v = find_variant(nt, nr, feat, w3, one_shot, w4);
-  // what the call reports: the launch that does the work — the tight one where there is one; "convex_pre+": the pre-pass launch
-  // in front, "+redo_<rows>" / "+wide": the launches behind
-  const WaveLaunch& rep = tight ? L.tight : L.main;
-  L.last_grid = rep.grid; L.last_lds = rep.lds; L.last_nt = rep.nt;
-  char redo[16] = "";
-  if (tight && L.tight_redo) snprintf(redo, sizeof redo, "+redo_%d", nt);
-  if (tight && !L.tight_redo) L.wide_redo = L.keep_q = false;      // (the tight launch alone: nothing behind it)
-  plan_name(L, "%s%s%s%s", L.cv_split ? "convex_pre+" : "", wave_name(rep), redo, L.wide_redo ? "+wide" : "");
-  return MKH_OK;
-}
-
-static int32_t launch_wave(MkhProblem* p, const WaveLaunch& w, const DeviceProblem* d_dev, SolveArgs a, hipStream_t stream, const TapArgs* dtaps) {
-  if (!w.v)
-    return fail(MKH_E_INVALID, "no kernel variant for %d tableau rows, %d dof rows, features %d%s%s", w.nt, w.nr, w.feat, w.w3 ? ", one more wave" : "",
-                w.one_shot ? ", one problem per workgroup" : "");
-  a.work_counter = p->d_work;
-  a.static_rounds = w.static_rounds;
-  w.v->launch(w.grid, w.lds, stream, d_dev, a, dtaps);
-  HIP_OK(hipGetLastError());
-  return MKH_OK;
-}
-
-static int32_t launch(MkhProblem* p, const SolveArgs& a_in, const TapArgs* taps, hipStream_t stream, int32_t flags) {
-  // (the kernel choice must not depend on whether the caller wants the status: a call without status_out on a handle with a
-  //  tight-rows build keeps it in a buffer of the handle — round-3 advisor finding)
-  SolveArgs a = a_in;
-  if (!a.status_out && p->d_status_tight && a.do_qp) a.status_out = p->d_status_tight;
-  LaunchPlan L;
-  if (const int32_t rc = plan_launch(*p, a, taps, flags, L)) return rc;
-  memcpy(p->last_kernel, L.last_kernel, sizeof p->last_kernel);
-  p->last_grid = L.last_grid; p->last_lds = L.last_lds; p->last_nt = L.last_nt; p->last_block = L.last_block;
-  (void)hipGetLastError();          // a stale error of an unrelated earlier runtime call must not be blamed on this launch
-  const TapArgs* dtaps = nullptr;
-  if (taps) {
-    HIP_OK(hipMemcpyAsync(p->d_taps, taps, sizeof(TapArgs), hipMemcpyHostToDevice, stream));
-    HIP_OK(hipStreamSynchronize(stream));   // taps are a debug path: keep the host struct's lifetime simple
-    dtaps = p->d_taps;
-  }
-  if (L.family == Family::WideOnly) {
-    HIP_OK(clk_begin(p, a, stream));                         // (MKH_DEBUG_CLOCKS=<file>: phase stamps of every problem, tools/wide_phase_clocks.py)
-    const int32_t rcw = launch_wide_kernel(p, a, stream, 0, dtaps);
-    if (rcw == MKH_OK) HIP_OK(clk_end(p, a.B, stream));
-    return rcw;
-  }
-  if (L.family == Family::Row) {
-    HIP_OK(clk_begin(p, a, stream));
-    p->last_lds = mkh::launch_quad(p->quad_nt, L.loop, L.last_grid, stream, p->d_lane, p->lane_dims, a);
-    HIP_OK(hipGetLastError());
-    HIP_OK(clk_end(p, a.B, stream));
-    return MKH_OK;
-  }
-  if (L.family == Family::Lane) {
-    if (mkh::launch_lane(p->lane_nv, L.loop, L.last_grid, p->lane_lds, stream, p->d_lane, a) != 0)
-      return fail(MKH_E_INVALID, "no kernel variant %s", p->last_kernel);
-    HIP_OK(hipGetLastError());
-    return MKH_OK;
-  }
-  const double* q_redo = a.q;
-  if (L.keep_q) {
-    HIP_OK(ensure(&p->d_qkeep, (size_t)p->max_batch * p->dev.nq));
-    HIP_OK(hipMemcpyAsync(p->d_qkeep, a.q, (size_t)a.B * p->dev.nq * sizeof(double), hipMemcpyDefault, stream));
-    q_redo = p->d_qkeep;
-  }
-  SolveArgs al = a;
-  HIP_OK(clk_begin(p, al, stream));                          // (clock builds: the stamps of the launch that does the work)
-  if (L.has_tight) {
-    if (const int32_t rc = launch_wave(p, L.tight, p->d_dev_tight, al, stream, nullptr)) return rc;
-    if (!L.tight_redo) return MKH_OK;
-    al = a;
-    al.redo_mask = MKH_ST_ROW_OVERFLOW;              // the full-row build: only what the tight launch flagged
-  }
-  if (L.cv_split) {
-    const hipError_t rc = mkh::launch_convex_pre(stream, p->d_wide, p->cv, a.B, a.q, p->d_cv);
-    if (rc != hipSuccess) return fail(MKH_E_HIP, "convex pre-pass: %s", hipGetErrorString(rc));
-  }
-  if (const int32_t rc = launch_wave(p, L.main, p->d_dev, al, stream, dtaps)) return rc;
-  HIP_OK(clk_end(p, a.B, stream));
-  if (L.wide_redo) {
-    SolveArgs ar = a;
-    ar.q = q_redo;
-    HIP_OK(clk_begin(p, ar, stream));                      // (MKH_DEBUG_CLOCKS: the stamps of the redo launch overwrite the main kernel's)
-    // (… and the instances whose active rows the sweep tableau found almost dependent, or on which it failed: MKH_ST_DEGENERATE is
-    //  internal — the dense Goldfarb–Idnani iteration of the workgroup-per-problem kernel answers for them)
-    const int32_t rcr = launch_wide_kernel(p, ar, stream, MKH_ST_ROW_OVERFLOW | MKH_ST_INFEASIBLE | MKH_ST_ITER_LIMIT | 32, dtaps);
-    if (rcr == MKH_OK) HIP_OK(clk_end(p, a.B, stream));
-    return rcr;
-  }
-  return MKH_OK;
-}
-
-struct TapBuf {
-  void* host; void* dev; size_t bytes;
-};
-
-// What every solve refuses about its inputs, in this order: a NULL q, a threshold loop without a frame task to test (`until_who`
+// What every outer-loop call refuses about its inputs (a plain solve: solve_plan.h solve_refusal), in this order: a NULL q, a threshold loop without a frame task to test (`until_who`
 // names the entry point; NULL: no thresholds), a NULL target of a task group the problem has, and — for the entry points that
 // cannot serve plugin rows at all — those (`no_plugin` ends the message: what besides the fused loop they rule out; NULL: the
 // caller has its own rules for them).
 static int32_t refuse_inputs(const DeviceProblem& P, const double* q, const double* frame_targets, const double* posture_target,
                              const double* com_target, const char* until_who, const char* no_plugin) {
-  if (!q) return fail(MKH_E_INVALID, "q is null");
-  if (until_who && P.n_frame < 1)
-    return fail(MKH_E_INVALID, "%s needs at least one frame task to test the thresholds on", until_who);
-  if (P.n_frame > 0 && !frame_targets) return fail(MKH_E_INVALID, "frame_targets is null (TargetNotSet)");
-  if (P.n_posture > 0 && !posture_target) return fail(MKH_E_INVALID, "posture_target is null (TargetNotSet)");
-  if (P.n_com > 0 && !com_target) return fail(MKH_E_INVALID, "com_target is null (TargetNotSet)");
+  if (!q) return fail(MKH_E_INVALID, "%s", kNullInputText[A_Q]);
+  if (until_who && P.n_frame < 1) return fail(MKH_E_INVALID, kUntilNoFrameFmt, until_who);
+  if (P.n_frame > 0 && !frame_targets) return fail(MKH_E_INVALID, "%s", kNullInputText[A_FT]);
+  if (P.n_posture > 0 && !posture_target) return fail(MKH_E_INVALID, "%s", kNullInputText[A_PT]);
+  if (P.n_com > 0 && !com_target) return fail(MKH_E_INVALID, "%s", kNullInputText[A_CT]);
   if (no_plugin && (P.n_dense_rows || P.n_dense_limit_rows || P.dense_box))
     return fail(MKH_E_INVALID, "dense (plugin) rows are evaluated by the caller at q: no fused loop, no %s", no_plugin);
   return MKH_OK;
 }
 
-static int32_t run(MkhProblem* p, int32_t B, const double* q, const double* frame_targets, const double* posture_target,
-                   const double* com_target, double dt, double damping, double* v_out, int32_t* status_out,
-                   const MkhTaps* taps, int32_t flags, void* hip_stream, int32_t n_steps, double* q_out,
-                   const MkhDenseRows* dense = nullptr, double pos_threshold = -1.0, double ori_threshold = -1.0,
-                   int32_t* iters_out = nullptr, int32_t* converged_out = nullptr) {
-  if (!p) return fail(MKH_E_INVALID, "null problem");
-  if (B < 1) return fail(MKH_E_INVALID, "B must be >= 1");
-  if (const int32_t rc = refuse_unwind(flags, "a solve")) return rc;       // (the outer-loop callers clear the bit in front of their loops)
-  const DeviceProblem& P = p->dev;
-  if (const int32_t rc = refuse_inputs(P, q, frame_targets, posture_target, com_target, nullptr, nullptr)) return rc;
-  if (!(dt > 0.0)) return fail(MKH_E_INVALID, "dt must be > 0");
-  if (n_steps < 1) return fail(MKH_E_INVALID, "n_steps must be >= 1");
-  const size_t Kd = P.n_dense_rows, Md = P.n_dense_limit_rows;
-  const bool Bd = P.dense_box != 0;
-  if (!Bd && dense && (dense->limit_lo || dense->limit_hi))
-    return fail(MKH_E_INVALID, "limit_lo / limit_hi need a problem created with dense_limit_box = 1");
-  if (Kd || Md || Bd) {
-    if (!dense) return fail(MKH_E_INVALID, "this problem has dense (plugin) rows: call mkh_solve_dense");
-    if (Kd && (!dense->task_e || !dense->task_J)) return fail(MKH_E_INVALID, "dense task_e / task_J is null");
-    if (Md && (!dense->limit_G || !dense->limit_h)) return fail(MKH_E_INVALID, "dense limit_G / limit_h is null");
-    if (n_steps > 1 || q_out) return fail(MKH_E_INVALID, "dense (plugin) rows are evaluated by the caller at q: no fused steps");
-  }
-  // max_batch bounds everything the handle owns per instance — staging buffers, the warm-start active sets — whichever
-  // kind of pointer the caller passes (a device-pointer warm start used to write past d_warm here)
-  if (B > p->max_batch) return fail(MKH_E_INVALID, "B=%d exceeds max_batch=%d of this problem", B, p->max_batch);
-  HIP_OK(hipSetDevice(p->model->device));
-  hipStream_t stream = (hipStream_t)hip_stream;
-  const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
-  const bool pbat = (flags & MKH_FLAG_POSTURE_BATCHED) != 0, cbat = (flags & MKH_FLAG_COM_BATCHED) != 0;
-  SolveArgs a;
-  memset(&a, 0, sizeof a);
-  TapArgs t;
-  memset(&t, 0, sizeof t);
-  bool any_tap = false;
-  a.B = B; a.posture_batched = pbat; a.com_batched = cbat; a.do_qp = (v_out != nullptr);
-  a.dt = dt; a.damping = damping; a.n_steps = n_steps;
-  a.pos_threshold = pos_threshold; a.ori_threshold = ori_threshold;
-  if (flags & MKH_FLAG_WARM_START) {
-    // closed-loop callers solve the same instances again and again: keep each instance's active set on the device
-    if (!p->d_warm) HIP_OK(hipMalloc((void**)&p->d_warm, (size_t)p->max_batch * P.nv));
-    if (p->warm_B != B) { HIP_OK(hipMemsetAsync(p->d_warm, 0, (size_t)p->max_batch * P.nv, stream)); p->warm_B = B; p->warm_age = 0; }
-    a.warm = p->d_warm; a.warm_age = p->warm_age;
-    if (v_out) ++p->warm_age;
-  }
-  const bool until = pos_threshold >= 0.0;
-  if (until && P.n_frame < 1) return fail(MKH_E_INVALID, "mkh_solve_until needs at least one frame task to test the thresholds on");
-  const size_t nq = P.nq, nv = P.nv;
-  const size_t n_pt = (size_t)P.n_posture * nq * (pbat ? B : 1), n_ct = (size_t)P.n_com * 3 * (cbat ? B : 1);
-  std::vector<TapBuf> tb;
-  if (devp) {
-    a.q = q; a.frame_targets = frame_targets; a.posture_target = posture_target; a.com_target = com_target;
-    a.v_out = v_out; a.status_out = status_out; a.q_out = q_out;
-    a.iters_out = iters_out; a.converged_out = converged_out;
-    if (Kd) { a.dense_e = dense->task_e; a.dense_J = dense->task_J; }
-    if (Md) { a.dense_G = dense->limit_G; a.dense_h = dense->limit_h; }
-    if (Bd) { a.dense_lo = dense->limit_lo; a.dense_hi = dense->limit_hi; }
-    if (taps) {
-      t.t_xpos = taps->xpos; t.t_xquat = taps->xquat; t.t_frame_pose = taps->frame_pose;
-      t.t_subtree_com = taps->subtree_com; t.t_task_e = taps->task_e; t.t_task_J = taps->task_J; t.t_H = taps->H;
-      t.t_c = taps->c; t.t_box_lo = taps->box_lo; t.t_box_hi = taps->box_hi; t.t_coll_G = taps->coll_G;
-      t.t_coll_h = taps->coll_h; t.t_qp_iters = taps->qp_iters; t.t_cycles = (long long*)taps->cycles;
-      if (t.t_coll_G) HIP_OK(hipMemsetAsync(t.t_coll_G, 0, (size_t)B * P.n_pairs * nv * sizeof(double), stream));
-    }
-    return launch(p, a, taps ? &t : nullptr, stream, flags);
-  }
-  // ---- host pointers, small call: everything through the pinned scratch (see PinnedScratch) — inputs, outputs and taps
-  {
-    const size_t Bz = B;
-    const size_t d_q = Bz * nq, d_ft = Bz * P.n_frame * 7, d_v = v_out ? Bz * nv : 0;
-    size_t bytes = (d_q + d_ft + n_pt + n_ct + d_v) * sizeof(double) + ((Bz * (until ? 3 : 1) * sizeof(int32_t) + 7) & ~(size_t)7);
-    if (taps) {
-      TapArgs sizes;
-      assign_taps(taps, P, Bz, sizes, [&](void* host, size_t n, bool) -> void* { if (host) bytes += (n + 7) & ~(size_t)7; return nullptr; });
-    }
-    if (!Kd && !Md && !Bd && bytes <= kSmallCallBytes) {
-      HIP_OK(p->small.ensure());
-      char* const h = p->small.host;
-      char* const d = p->small.dev;
-      size_t o = 0;                                    // (bytes; every block a multiple of 8)
-      auto put = [&](const double* src, size_t n) -> const double* {
-        if (!n) return nullptr;
-        memcpy(h + o, src, n * sizeof(double));
-        const double* r = (const double*)(d + o);
-        o += n * sizeof(double);
-        return r;
-      };
-      a.q = put(q, d_q);
-      a.frame_targets = put(frame_targets, d_ft);
-      a.posture_target = put(posture_target, n_pt);
-      a.com_target = put(com_target, n_ct);
-      const size_t o_v = o;
-      a.v_out = v_out ? (double*)(d + o_v) : nullptr;
-      o += d_v * sizeof(double);
-      const size_t o_i = o;
-      int32_t* const di32 = (int32_t*)(d + o_i);
-      a.status_out = di32;
-      a.q_out = q_out ? (double*)a.q : nullptr;        // in place, as in the staged path
-      if (until) { a.iters_out = di32 + Bz; a.converged_out = di32 + 2 * Bz; }
-      o += (Bz * (until ? 3 : 1) * sizeof(int32_t) + 7) & ~(size_t)7;
-      struct Back { void* host; size_t off, n; };
-      std::vector<Back> back;
-      if (taps)
-        assign_taps(taps, P, Bz, t, [&](void* host, size_t n, bool zero) -> void* {
-          if (!host) return nullptr;
-          if (zero) memset(h + o, 0, n);
-          back.push_back({host, o, n});
-          void* r = d + o;
-          o += (n + 7) & ~(size_t)7;
-          return r;
-        });
-      const int32_t rc = launch(p, a, taps ? &t : nullptr, stream, flags);
-      if (rc != MKH_OK) return rc;
-      HIP_OK(hipStreamSynchronize(stream));
-      const int32_t* const hi32 = (const int32_t*)(h + o_i);
-      if (v_out) memcpy(v_out, h + o_v, d_v * sizeof(double));
-      if (q_out) memcpy(q_out, h, d_q * sizeof(double));
-      if (status_out && v_out) memcpy(status_out, hi32, Bz * sizeof(int32_t));
-      if (until && iters_out) memcpy(iters_out, hi32 + Bz, Bz * sizeof(int32_t));
-      if (until && converged_out) memcpy(converged_out, hi32 + 2 * Bz, Bz * sizeof(int32_t));
-      for (const Back& b : back) memcpy(b.host, h + b.off, b.n);
-      return MKH_OK;
-    }
-  }
-  // ---- host pointers: stage through library-owned device buffers
-  const size_t mb = p->max_batch;
-  HIP_OK(ensure(&p->s_q, mb * nq));
-  HIP_OK(ensure(&p->s_ft, mb * P.n_frame * 7));
-  HIP_OK(ensure(&p->s_v, mb * nv));
-  HIP_OK(ensure(&p->s_status, mb));
-  if (n_pt > p->s_pt_cap) { (void)hipFree(p->s_pt); p->s_pt = nullptr; HIP_OK(hipMalloc((void**)&p->s_pt, n_pt * sizeof(double))); p->s_pt_cap = n_pt; }
-  if (n_ct > p->s_ct_cap) { (void)hipFree(p->s_ct); p->s_ct = nullptr; HIP_OK(hipMalloc((void**)&p->s_ct, n_ct * sizeof(double))); p->s_ct_cap = n_ct; }
-  // Large plain solves in chunks: the host → device copy of chunk c + 1 and the device → host copy of chunk c − 1 run on
-  // streams of their own beside the kernel of chunk c (the single-shot sequence copy in, solve, copy out left the GPU idle
-  // for more than half of a 65 536-instance G1 call).  Chunks of at least 8 192 instances; each is dispatched by its own
-  // size (a small arm's chunk may run the row kernel where the whole batch would have taken the lane kernel: same optimum).
-  // Only where the copies are worth overlapping (≥ 32 MB staged: tools/bench_host_path.py — G1 at 65 536 instances
-  // 2.02 → 1.72 ms per call, the G1 full example 2.79 → 2.19 ms; a 65 536-instance UR5e call moves 10 MB around a 0.08 ms
-  // kernel and LOSES 0.15 ms to the events and the three extra launches).
-  static const bool no_chunks = dbg_env("MKH_DEBUG_NO_CHUNKS") != nullptr;      // (A/B of this path)
-  const size_t staged_bytes = (size_t)B * sizeof(double) *
-      (nq + (size_t)P.n_frame * 7 + nv + (pbat ? (size_t)P.n_posture * nq : 0) + (cbat ? (size_t)P.n_com * 3 : 0) + (q_out ? nq : 0));
-  const int n_chunks = (!no_chunks && !taps && !Kd && !Md && !Bd && v_out && B >= 2 * 8192 && staged_bytes >= ((size_t)32 << 20))
-                           ? (B / 8192 < 4 ? B / 8192 : 4) : 1;
-  if (n_chunks > 1) {
-    if (!p->st_in) {
-      HIP_OK(hipStreamCreateWithFlags(&p->st_in, hipStreamNonBlocking));
-      HIP_OK(hipStreamCreateWithFlags(&p->st_out, hipStreamNonBlocking));
-      HIP_OK(hipEventCreateWithFlags(&p->ev_start, hipEventDisableTiming));
-      for (int i = 0; i < 4; ++i) {
-        HIP_OK(hipEventCreateWithFlags(&p->ev_in[i], hipEventDisableTiming));
-        HIP_OK(hipEventCreateWithFlags(&p->ev_k[i], hipEventDisableTiming));
-      }
-    }
-    if (until) HIP_OK(ensure(&p->s_iters, mb * 2));
-    // (shared targets on the caller's stream, ahead of the first kernel; the side streams start behind the caller's work)
-    if (n_pt && !pbat) HIP_OK(hipMemcpyAsync(p->s_pt, posture_target, n_pt * sizeof(double), hipMemcpyHostToDevice, stream));
-    if (n_ct && !cbat) HIP_OK(hipMemcpyAsync(p->s_ct, com_target, n_ct * sizeof(double), hipMemcpyHostToDevice, stream));
-    HIP_OK(hipEventRecord(p->ev_start, stream));
-    HIP_OK(hipStreamWaitEvent(p->st_in, p->ev_start, 0));
-    const size_t chunk = ((size_t)B / n_chunks) / 64 * 64;          // ≥ 8 192; the last chunk takes the remainder
-    const size_t ft_w = (size_t)P.n_frame * 7, pt_w = (size_t)P.n_posture * nq, ct_w = (size_t)P.n_com * 3;
-    int32_t rc = MKH_OK;
-    hipError_t e = hipSuccess;
-    // (an error inside the loop must not return: copies that read the caller's q / targets may be in flight on st_in)
-    auto ok = [&](hipError_t r) { if (e == hipSuccess) e = r; return e == hipSuccess; };
-    for (int c = 0; c < n_chunks && rc == MKH_OK && e == hipSuccess; ++c) {
-      const size_t off = c * chunk, Bc = (c + 1 < n_chunks) ? chunk : (size_t)B - off;
-      ok(hipMemcpyAsync(p->s_q + off * nq, q + off * nq, Bc * nq * sizeof(double), hipMemcpyHostToDevice, p->st_in));
-      if (ft_w) ok(hipMemcpyAsync(p->s_ft + off * ft_w, frame_targets + off * ft_w, Bc * ft_w * sizeof(double), hipMemcpyHostToDevice, p->st_in));
-      if (n_pt && pbat) ok(hipMemcpyAsync(p->s_pt + off * pt_w, posture_target + off * pt_w, Bc * pt_w * sizeof(double), hipMemcpyHostToDevice, p->st_in));
-      if (n_ct && cbat) ok(hipMemcpyAsync(p->s_ct + off * ct_w, com_target + off * ct_w, Bc * ct_w * sizeof(double), hipMemcpyHostToDevice, p->st_in));
-      ok(hipEventRecord(p->ev_in[c], p->st_in));
-      if (!ok(hipStreamWaitEvent(stream, p->ev_in[c], 0))) break;
-      SolveArgs ac = a;
-      ac.B = (int32_t)Bc;
-      ac.q = p->s_q + off * nq; ac.frame_targets = p->s_ft + off * ft_w;
-      ac.posture_target = p->s_pt + (pbat ? off * pt_w : 0); ac.com_target = p->s_ct + (cbat ? off * ct_w : 0);
-      ac.v_out = p->s_v + off * nv; ac.status_out = p->s_status + off;
-      ac.q_out = q_out ? p->s_q + off * nq : nullptr;
-      if (until) { ac.iters_out = p->s_iters + off; ac.converged_out = p->s_iters + mb + off; }
-      if (a.warm) ac.warm = a.warm + off * nv;
-      rc = launch(p, ac, nullptr, stream, flags);
-      if (rc == MKH_OK) ok(hipEventRecord(p->ev_k[c], stream));
-    }
-    for (int c = 0; c < n_chunks && rc == MKH_OK && e == hipSuccess; ++c) {
-      const size_t off = c * chunk, Bc = (c + 1 < n_chunks) ? chunk : (size_t)B - off;
-      e = hipStreamWaitEvent(p->st_out, p->ev_k[c], 0);
-      if (e == hipSuccess) e = hipMemcpyAsync(v_out + off * nv, p->s_v + off * nv, Bc * nv * sizeof(double), hipMemcpyDeviceToHost, p->st_out);
-      if (e == hipSuccess && q_out) e = hipMemcpyAsync(q_out + off * nq, p->s_q + off * nq, Bc * nq * sizeof(double), hipMemcpyDeviceToHost, p->st_out);
-      if (e == hipSuccess && status_out) e = hipMemcpyAsync(status_out + off, p->s_status + off, Bc * sizeof(int32_t), hipMemcpyDeviceToHost, p->st_out);
-      if (e == hipSuccess && until && iters_out) e = hipMemcpyAsync(iters_out + off, p->s_iters + off, Bc * sizeof(int32_t), hipMemcpyDeviceToHost, p->st_out);
-      if (e == hipSuccess && until && converged_out) e = hipMemcpyAsync(converged_out + off, p->s_iters + mb + off, Bc * sizeof(int32_t), hipMemcpyDeviceToHost, p->st_out);
-    }
-    // (a failed call still drains what it started: the staging buffers belong to the handle)
-    const hipError_t e1 = hipStreamSynchronize(p->st_in), e2 = hipStreamSynchronize(stream), e3 = hipStreamSynchronize(p->st_out);
-    if (e == hipSuccess) e = e1 != hipSuccess ? e1 : (e2 != hipSuccess ? e2 : e3);
-    if (rc == MKH_OK && e != hipSuccess) rc = fail(MKH_E_HIP, "solve: %s", hipGetErrorString(e));
-    return rc;
-  }
-  HIP_OK(hipMemcpyAsync(p->s_q, q, (size_t)B * nq * sizeof(double), hipMemcpyHostToDevice, stream));
-  if (P.n_frame) HIP_OK(hipMemcpyAsync(p->s_ft, frame_targets, (size_t)B * P.n_frame * 7 * sizeof(double), hipMemcpyHostToDevice, stream));
-  if (n_pt) HIP_OK(hipMemcpyAsync(p->s_pt, posture_target, n_pt * sizeof(double), hipMemcpyHostToDevice, stream));
-  if (n_ct) HIP_OK(hipMemcpyAsync(p->s_ct, com_target, n_ct * sizeof(double), hipMemcpyHostToDevice, stream));
-  if (Kd) {
-    HIP_OK(ensure(&p->s_de, mb * Kd));
-    HIP_OK(ensure(&p->s_dJ, mb * Kd * nv));
-    HIP_OK(hipMemcpyAsync(p->s_de, dense->task_e, (size_t)B * Kd * sizeof(double), hipMemcpyHostToDevice, stream));
-    HIP_OK(hipMemcpyAsync(p->s_dJ, dense->task_J, (size_t)B * Kd * nv * sizeof(double), hipMemcpyHostToDevice, stream));
-    a.dense_e = p->s_de; a.dense_J = p->s_dJ;
-  }
-  if (Md) {
-    HIP_OK(ensure(&p->s_dG, mb * Md * nv));
-    HIP_OK(ensure(&p->s_dh, mb * Md));
-    HIP_OK(hipMemcpyAsync(p->s_dG, dense->limit_G, (size_t)B * Md * nv * sizeof(double), hipMemcpyHostToDevice, stream));
-    HIP_OK(hipMemcpyAsync(p->s_dh, dense->limit_h, (size_t)B * Md * sizeof(double), hipMemcpyHostToDevice, stream));
-    a.dense_G = p->s_dG; a.dense_h = p->s_dh;
-  }
-  if (Bd && (dense->limit_lo || dense->limit_hi)) {
-    HIP_OK(ensure(&p->s_dbox, mb * nv * 2));
-    if (dense->limit_lo) { HIP_OK(hipMemcpyAsync(p->s_dbox, dense->limit_lo, (size_t)B * nv * sizeof(double), hipMemcpyHostToDevice, stream)); a.dense_lo = p->s_dbox; }
-    if (dense->limit_hi) { HIP_OK(hipMemcpyAsync(p->s_dbox + mb * nv, dense->limit_hi, (size_t)B * nv * sizeof(double), hipMemcpyHostToDevice, stream)); a.dense_hi = p->s_dbox + mb * nv; }
-  }
-  a.q = p->s_q; a.frame_targets = p->s_ft; a.posture_target = p->s_pt; a.com_target = p->s_ct;
-  a.v_out = v_out ? p->s_v : nullptr;
-  a.status_out = p->s_status;
-  a.q_out = q_out ? p->s_q : nullptr;               // in place in the staging buffer
-  if (until) {
-    HIP_OK(ensure(&p->s_iters, mb * 2));
-    a.iters_out = p->s_iters; a.converged_out = p->s_iters + mb;
-  }
-  int32_t rc = MKH_OK;
-  auto tap = [&](void* host, size_t bytes, bool zero) -> void* {
-    if (!host || rc != MKH_OK) return nullptr;
-    void* dptr = nullptr;
-    if (hipMalloc(&dptr, bytes ? bytes : 1) != hipSuccess) { rc = fail(MKH_E_HIP, "tap buffer allocation failed"); return nullptr; }
-    tb.push_back({host, dptr, bytes});               // (freed at the end of the call whatever happens next)
-    if (zero && hipMemsetAsync(dptr, 0, bytes, stream) != hipSuccess) { rc = fail(MKH_E_HIP, "tap buffer clear failed"); return nullptr; }
-    return dptr;
-  };
-  if (taps) assign_taps(taps, P, (size_t)B, t, tap);
-  if (rc == MKH_OK) rc = launch(p, a, taps ? &t : nullptr, stream, flags);
-  if (rc == MKH_OK) {
-    hipError_t e = hipSuccess;
-    if (v_out) e = hipMemcpyAsync(v_out, p->s_v, (size_t)B * nv * sizeof(double), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && q_out) e = hipMemcpyAsync(q_out, p->s_q, (size_t)B * nq * sizeof(double), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && status_out && v_out)
-      e = hipMemcpyAsync(status_out, p->s_status, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && until && iters_out)
-      e = hipMemcpyAsync(iters_out, p->s_iters, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && until && converged_out)
-      e = hipMemcpyAsync(converged_out, p->s_iters + mb, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, stream);
-    for (auto& t : tb)
-      if (e == hipSuccess) e = hipMemcpyAsync(t.host, t.dev, t.bytes, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) rc = fail(MKH_E_HIP, "solve: %s", hipGetErrorString(e));
-  }
-  for (auto& t : tb) (void)hipFree(t.dev);
-  return rc;
-}
-
-int32_t mkh_eval(MkhProblem* p, int32_t B, const double* q, const double* frame_targets, const double* posture_target,
-                 const double* com_target, double dt, double damping, double* v_out, int32_t* status_out,
-                 const MkhTaps* taps, int32_t flags, void* hip_stream) {
-  return run(p, B, q, frame_targets, posture_target, com_target, dt, damping, v_out, status_out, taps, flags, hip_stream,
-             1, nullptr);
-}
-
-int32_t mkh_solve(MkhProblem* p, int32_t B, const double* q, const double* frame_targets, const double* posture_target,
-                  const double* com_target, double dt, double damping, double* v_out, int32_t* status_out,
-                  int32_t flags, void* hip_stream) {
-  if (!v_out) return fail(MKH_E_INVALID, "v_out is null");
-  return run(p, B, q, frame_targets, posture_target, com_target, dt, damping, v_out, status_out, nullptr, flags,
-             hip_stream, 1, nullptr);
-}
-
-int32_t mkh_solve_dense(MkhProblem* p, int32_t B, const double* q, const double* frame_targets,
-                        const double* posture_target, const double* com_target, const MkhDenseRows* dense, double dt,
-                        double damping, double* v_out, int32_t* status_out, const MkhTaps* taps, int32_t flags,
-                        void* hip_stream) {
-  return run(p, B, q, frame_targets, posture_target, com_target, dt, damping, v_out, status_out, taps, flags, hip_stream,
-             1, nullptr, dense);
-}
-
-int32_t mkh_solve_steps(MkhProblem* p, int32_t B, const double* q, const double* frame_targets,
-                        const double* posture_target, const double* com_target, double dt, double damping,
-                        int32_t n_steps, double* q_out, double* v_out, int32_t* status_out, int32_t flags,
-                        void* hip_stream) {
-  if (!v_out || !q_out) return fail(MKH_E_INVALID, "v_out / q_out is null");
-  return run(p, B, q, frame_targets, posture_target, com_target, dt, damping, v_out, status_out, nullptr, flags,
-             hip_stream, n_steps, q_out);
-}
-
-int32_t mkh_solve_until(MkhProblem* p, int32_t B, const double* q, const double* frame_targets,
-                        const double* posture_target, const double* com_target, double dt, double damping,
-                        int32_t max_iters, double pos_threshold, double ori_threshold, double* q_out, double* v_out,
-                        int32_t* status_out, int32_t* iters_out, int32_t* converged_out, int32_t flags, void* hip_stream) {
-  if (!v_out || !q_out) return fail(MKH_E_INVALID, "v_out / q_out is null");
-  if (!(pos_threshold >= 0.0) || !(ori_threshold >= 0.0)) return fail(MKH_E_INVALID, "thresholds must be >= 0");
-  return run(p, B, q, frame_targets, posture_target, com_target, dt, damping, v_out, status_out, nullptr, flags,
-             hip_stream, max_iters, q_out, nullptr, pos_threshold, ori_threshold, iters_out, converged_out);
-}
 
 }  // extern "C"
 
@@ -1383,8 +628,12 @@ static int32_t ms_loops(Stager& st, int B, int S, const MsIn& in, const LoopSpec
   const double* const c_ct = (ct_w && cbat) ? fanout(WS_C_CT, in.ct, ct_w) : in.ct;
   if (!st.ok()) return MKH_OK;
   const int32_t loop_flags = (flags & ~(MKH_FLAG_WARM_START | MKH_FLAG_UNWIND_TURNS)) | MKH_FLAG_DEVICE_PTRS;
-  return run(p, (int32_t)Nz, c.starts, c_ft, c_pt, c_ct, ls.dt, ls.damping, c.v_all, c.status, nullptr, loop_flags, (void*)stream,
-             ls.max_iters, c.q_all, nullptr, ls.pos_threshold, ls.ori_threshold, c.iters, c.converged);
+  SolveCall sc;
+  sc.p = p; sc.B = (int32_t)Nz; sc.q = c.starts; sc.frame_targets = c_ft; sc.posture_target = c_pt; sc.com_target = c_ct;
+  sc.dt = ls.dt; sc.damping = ls.damping; sc.v_out = c.v_all; sc.status_out = c.status; sc.flags = loop_flags; sc.hip_stream = (void*)stream;
+  sc.n_steps = ls.max_iters; sc.q_out = c.q_all; sc.pos_threshold = ls.pos_threshold; sc.ori_threshold = ls.ori_threshold;
+  sc.iters_out = c.iters; sc.converged_out = c.converged;
+  return solve(sc);
 }
 
 // R flattened rows of targets (a ladder's rungs, a goal set's goals) through ms_loops, whole rows per chunk of at most
@@ -1973,9 +1222,13 @@ static int32_t trajectory_core(MkhProblem* p, int32_t B, int32_t T, const double
       if (ctime && cbat) { ST_LAUNCH(st, launch_ms_fanout(stream, t_ct, c_ct, B, S, (int)ct_w)); t_ct = c_ct; }
     }
     if (!st.ok()) break;
-    rc = run(p, (int32_t)Rz, q_in, t_ft, t_pt, t_ct, dt, damping, l_v + t * Rz * nv, l_st + t * Rz, nullptr, loop_flags, hip_stream,
-             n_steps, l_q + t * Rz * nq, nullptr, until ? pos_threshold : -1.0, until ? ori_threshold : -1.0,
-             l_it ? l_it + t * Rz : nullptr, l_cv ? l_cv + t * Rz : nullptr);
+    SolveCall sc;
+    sc.p = p; sc.B = (int32_t)Rz; sc.q = q_in; sc.frame_targets = t_ft; sc.posture_target = t_pt; sc.com_target = t_ct;
+    sc.dt = dt; sc.damping = damping; sc.v_out = l_v + t * Rz * nv; sc.status_out = l_st + t * Rz; sc.flags = loop_flags; sc.hip_stream = hip_stream;
+    sc.n_steps = n_steps; sc.q_out = l_q + t * Rz * nq;
+    if (until) { sc.pos_threshold = pos_threshold; sc.ori_threshold = ori_threshold; }
+    sc.iters_out = l_it ? l_it + t * Rz : nullptr; sc.converged_out = l_cv ? l_cv + t * Rz : nullptr;
+    rc = solve(sc);
   }
   if (rc != MKH_OK || !st.ok()) return st.finish(rc);
   // (instance, waypoint) strides in elements of an array of width w in the caller's layout
@@ -2359,7 +1612,7 @@ int32_t mkh_ladder_select_free(MkhProblem* p, MkhProblem* ck, int32_t B, int32_t
 
 // The refinement pass (include/minkhip.h "THE RULE OF THE REFINEMENT") on device arrays, into device outputs, on the call's stream:
 // the targets' time-major slabs as mkh_solve_trajectory builds them, the working path, then per waypoint of the two sweeps one
-// step kernel and one loop launch through run(), and the guard.  Returns the first refusal of a loop launch; HIP errors are
+// step kernel and one loop launch through solve(), and the guard.  Returns the first refusal of a loop launch; HIP errors are
 // latched in `st`.
 // With a checker (rf != NULL: "THE RULE OF THE REFINEMENT, with a checker"; kernels: ladder_refine_free.hip and the _free builds of
 // ladder_refine.hip) the state of the input path comes first — one clearance of its rows on the checker handle, one kSweepPath
@@ -2431,9 +1684,13 @@ static int32_t refine_pass(Stager& st, int B, int T, const double* d_q, const do
   };
   auto loop = [&](size_t t) -> int32_t {
     if (!st.ok()) return MKH_OK;
-    return run(p, B, w.start, d_ft ? d_ft + t * Bz * ft_w : nullptr, d_pt ? d_pt + t * pt_step : nullptr,
-               d_ct ? d_ct + t * ct_step : nullptr, ls.dt, ls.damping, w.xv, w.xst, nullptr, loop_flags, (void*)stream, ls.max_iters, w.x,
-               nullptr, ls.pos_threshold, ls.ori_threshold, w.xit, w.xcv);
+    SolveCall sc;
+    sc.p = p; sc.B = B; sc.q = w.start; sc.frame_targets = d_ft ? d_ft + t * Bz * ft_w : nullptr;
+    sc.posture_target = d_pt ? d_pt + t * pt_step : nullptr; sc.com_target = d_ct ? d_ct + t * ct_step : nullptr;
+    sc.dt = ls.dt; sc.damping = ls.damping; sc.v_out = w.xv; sc.status_out = w.xst; sc.flags = loop_flags; sc.hip_stream = (void*)stream;
+    sc.n_steps = ls.max_iters; sc.q_out = w.x; sc.pos_threshold = ls.pos_threshold; sc.ori_threshold = ls.ori_threshold;
+    sc.iters_out = w.xit; sc.converged_out = w.xcv;
+    return solve(sc);
   };
   step(-1, 1, 0, 1);
   for (int t = 0; t < T; ++t) {                              // forward; its last commit decides the first backward waypoint

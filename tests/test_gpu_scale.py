@@ -99,7 +99,7 @@ def test_device_pointer_path_matches_host_path(g1_setup):
     np.testing.assert_array_equal(v_d.cpu().numpy(), v_h)
     np.testing.assert_array_equal(st_d.cpu().numpy(), st_h)
     # a host-pointer call that stages 32 MB or more runs in up to four chunks whose copies overlap the kernels of their
-    # neighbours (minkhip.hip run()): same answers, ragged last chunk included, fused steps and their outputs too
+    # neighbours (solve_host.hip via_staged): same answers, ragged last chunk included, fused steps and their outputs too
     n = 40001
     to = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
     v_h, st_h = prob.solve(q[:n], tg[:n], stand[None, :], None, dt, damping)
@@ -121,6 +121,20 @@ def test_device_pointer_path_matches_host_path(g1_setup):
     torch.cuda.synchronize()
     for a_h, a_d in zip(out_h, out_d):
         np.testing.assert_array_equal(a_d.cpu().numpy(), a_h)
+    # ... and the warm-start state, of which every chunk reads and writes its own rows: consecutive warm-started calls through the
+    # chunks against the same calls on device tensors (a call of another batch size in between resets the handle's state; three
+    # calls, because the state is read from the third on)
+    n = 40001
+
+    def warm_calls(conv):
+        prob.solve(conv(q[:16]), conv(tg[:16]), conv(stand[None, :]), None, dt, damping, warm_start=True)
+        return [prob.solve(conv(q[:n]), conv(tg[:n]), conv(stand[None, :]), None, dt, damping, warm_start=True) for _ in range(3)]
+
+    warm_h, warm_d = warm_calls(lambda x: x), warm_calls(to)
+    torch.cuda.synchronize()
+    for (v_h, st_h), (v_d, st_d) in zip(warm_h, warm_d):
+        np.testing.assert_array_equal(v_d.cpu().numpy(), v_h)
+        np.testing.assert_array_equal(st_d.cpu().numpy(), st_h)
 
 
 @pytest.mark.parametrize("name,B", [("ur5e_c2", 4096), ("shadow_c4", 16384)])
