@@ -1271,6 +1271,55 @@ int32_t mkh_ladder_select_free(MkhProblem *problem, MkhProblem *checker, int32_t
                                void *hip_stream);
 
 /*
+ * THE RULE, with a certifying checker (mkh_ladder_select_certified; mkh_solve_trajectory_ladder_certified runs it on the rungs it
+ * solves): THE RULE "with a checker" above with ONE term replaced — how an edge is judged.  Nodes, the effective flag, the key,
+ * the ties, the breaks, the 16-bit counts and the back-trace are that rule's, unchanged; so is the gating: the destination must be
+ * effectively tracked, the start edge from q[b] is never swept, an edge that is not swept has NaN margins and is not blocked.
+ *   Edges.   For t >= 1 the edge from node (t - 1, s) to an effectively tracked node (t, s') is judged by THE RULE OF THE
+ *            CERTIFIED SWEEP, unchanged, on (q_{t-1,s}, q_{t,s'}) at the call's `resolution` and `max_samples`: BOTH ends are
+ *            points of the edge, as that rule has them, and the sample count follows from the edge's own motion bound.  margin,
+ *            lower_bound, n_samples and verdict of a swept edge are BITWISE what mkh_certified_sweep returns for that pair of rows.
+ *   blocked(t, s', s) follows `edge_policy`:
+ *            MKH_EDGE_REJECT_COLLIDING  (0)  blocked iff verdict == MKH_SWEEP_COLLIDES: the sampled rule's reading, at the
+ *                                            points the motion bound asks for.
+ *            MKH_EDGE_REQUIRE_CERTIFIED (1)  blocked iff verdict != MKH_SWEEP_CERTIFIED: an UNDECIDED edge is blocked as well, so
+ *                                            every waypoint n_tracked counts is entered by a motion PROVEN free for every u.
+ *            Any other value: MKH_E_INVALID.
+ *   What differs from the sampled rule, beside the count: the end points are judged.  The destination of a swept edge is free
+ *            by the gating, but its SOURCE may be a colliding node: the sampled rule looks at interior samples only and may call
+ *            such an edge free; here it COLLIDES, so the waypoint behind a colliding node is lost on that path as well.
+ *   Outputs. MkhLadderIO's and MkhLadderFreeIO's keep their meaning — edge_collision and n_edge_collisions are "what the search
+ *            counted as blocked on the chosen path": under MKH_EDGE_REQUIRE_CERTIFIED that INCLUDES the undecided edges —;
+ *            edge_margin (B, T) is the certified sweep's margin of the chosen edge, both ends included; edge_margin_all as there.
+ *            MkhLadderCertifiedIO adds, of the chosen path: edge_verdict (B, T) MKH_SWEEP_*, -1 where the edge was not swept
+ *            (t = 0 included); edge_lower_bound (B, T), +inf at t = 0, NaN where not swept; edge_n_samples (B, T), 0 where not
+ *            swept; n_certified (B,) = the t >= 1 on the path with verdict MKH_SWEEP_CERTIFIED.  Optional: edge_verdict_all
+ *            (B, T, S, S) int8, entry [b, t, s', s], -1 for t = 0 and for edges not swept.
+ * One launch judges every edge into an effectively tracked node, a second one the chosen edges; the mask lives where the
+ * sampled rule's does, B T S^2 bytes more only when edge_verdict_all is asked for, and B T doubles and 2 B T int32 for the path's
+ * new outputs of a host-pointer call.  Refused before any device work: everything mkh_ladder_select_free refuses; resolution not
+ * finite or <= 0, max_samples outside [1, 4096], an edge_policy other than the two (MKH_E_INVALID); the checker as
+ * mkh_certified_sweep refuses it — general convex pairs with MKH_E_INVALID whatever its sweep_rows, its LDS slice beyond 64 KB
+ * with MKH_E_LIMIT.  The reach table is filled and uploaded at the checker's first such call.  Refinement
+ * (mkh_ladder_refine_free) and candidate tracking (mkh_select_trajectory_candidates) still sample: they judge rows inside
+ * their own kernels.
+ */
+#define MKH_EDGE_REJECT_COLLIDING  0
+#define MKH_EDGE_REQUIRE_CERTIFIED 1
+typedef struct MkhLadderCertifiedIO {
+  int32_t *edge_verdict;       /* (B, T)        MKH_SWEEP_* of the chosen edges, -1: not swept                      required  */
+  double *edge_lower_bound;    /* (B, T)        the certified sweep's lower bound of the chosen edges              required  */
+  int32_t *edge_n_samples;     /* (B, T)        their sample counts, 0: not swept                                  required  */
+  int32_t *n_certified;        /* (B,)          chosen edges proven free                                           required  */
+  int8_t *edge_verdict_all;    /* (B, T, S, S)  optional: the verdict of every edge                                          */
+} MkhLadderCertifiedIO;
+int32_t mkh_ladder_select_certified(MkhProblem *problem, MkhProblem *checker, int32_t B, int32_t T, int32_t S, const double *q,
+                                    const double *q_nodes, const int32_t *tracked, const double *weights, double max_step_sq,
+                                    double resolution, int32_t max_samples, int32_t edge_policy, const MkhLadderIO *io,
+                                    const MkhLadderFreeIO *free_io, const MkhLadderCertifiedIO *certified_io, int32_t flags,
+                                    void *hip_stream);
+
+/*
  * mkh_solve_trajectory_ladder: the rungs solved by multi-start, then THE RULE above.
  *
  * Rungs.  Rung t of instance b is what mkh_solve_multistart returns in q_all / converged_all / status_all / iters_all for
@@ -1552,6 +1601,26 @@ int32_t mkh_solve_trajectory_ladder_free_refined(MkhProblem *problem, MkhProblem
                                                  int64_t target_index0, int32_t n_samples, const MkhTrajectoryLadderIO *io,
                                                  const MkhLadderNodesIO *nodes, const MkhLadderRefineIO *refine,
                                                  const MkhLadderFreeIO *free_io, int32_t flags, void *hip_stream);
+
+/*
+ * mkh_solve_trajectory_ladder_certified: mkh_solve_trajectory_ladder_free with THE RULE "with a certifying checker" in place of
+ * THE RULE "with a checker": its arguments with n_samples replaced by resolution, max_samples and edge_policy, and the
+ * MkhLadderCertifiedIO behind the MkhLadderFreeIO.  n_nodes = 0 with nodes = NULL is the plain ladder, n_nodes = K >= 1 with nodes
+ * the ladder on K distinct nodes, as there; everything in front of the edges — the loops, the clearance of the candidates, the
+ * status bit, the nodes' flags — is that call's.  The result is the composition of the plain call's nodes (return_all), the
+ * clearance of those rows, and mkh_ladder_select_certified on them, bit for bit.  `refine` must be NULL: the refinement pass
+ * still samples, and a path judged by two rules is nobody's result.  free_io->node_margin must be NULL as there;
+ * edge_margin_all and edge_verdict_all are (B, T, W, W) with W the nodes per rung.  Refusals as in
+ * mkh_solve_trajectory_ladder_free and mkh_ladder_select_certified.
+ */
+int32_t mkh_solve_trajectory_ladder_certified(MkhProblem *problem, MkhProblem *checker, int32_t B, int32_t T, int32_t n_seeds,
+                                              int32_t n_nodes, double min_distance, const double *q, const double *frame_targets,
+                                              const double *posture_target, const double *com_target, double dt, double damping,
+                                              int32_t max_iters, double pos_threshold, double ori_threshold, uint64_t rng_seed,
+                                              int64_t target_index0, double resolution, int32_t max_samples, int32_t edge_policy,
+                                              const MkhTrajectoryLadderIO *io, const MkhLadderNodesIO *nodes,
+                                              const MkhLadderRefineIO *refine, const MkhLadderFreeIO *free_io,
+                                              const MkhLadderCertifiedIO *certified_io, int32_t flags, void *hip_stream);
 
 /* Same inputs; additionally writes the requested intermediates (build_ik / compute_error /
  * compute_jacobian / get_transform_frame_to_world parity taps).  v_out/status_out may be NULL

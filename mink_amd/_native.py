@@ -756,6 +756,40 @@ LADDER_FREE_OUT = _out(MkhLadderFreeIO, {
     "edge_collision": ("B T", _I4, None), "n_edge_collisions": ("B", _I4, None), "edge_margin": ("B T", _F8, None),
     "node_margin": ("B T S", _F8, "margins"), "edge_margin_all": ("B T S S", _F8, "margins")})
 
+LADDER_CERTIFIED_IO_FIELDS = ("edge_verdict", "edge_lower_bound", "edge_n_samples", "n_certified", "edge_verdict_all")
+EDGE_REJECT_COLLIDING, EDGE_REQUIRE_CERTIFIED = 0, 1     # MKH_EDGE_*
+
+
+class MkhLadderCertifiedIO(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in LADDER_CERTIFIED_IO_FIELDS]
+
+
+LadderCertifiedOut = _extended(
+    "LadderCertifiedOut", LadderFreeOut, LADDER_CERTIFIED_IO_FIELDS,
+    """What the certifying ladder calls add (include/minkhip.h THE RULE "with a certifying checker"): LadderFreeOut's fields in its
+    order — edge_collision and n_edge_collisions count what the search blocked, undecided edges included under
+    EDGE_REQUIRE_CERTIFIED; edge_margin is the certified sweep's, both ends included —, then of the chosen path edge_verdict (B, T)
+    int32 (SWEEP_*, -1: not swept), edge_lower_bound (B, T), edge_n_samples (B, T) int32, n_certified (B,) int32, and, where asked
+    for, edge_verdict_all (B, T, S, S) int8.""")
+LADDER_CERTIFIED_OUT = _out(MkhLadderCertifiedIO, {
+    "edge_verdict": ("B T", _I4, None), "edge_lower_bound": ("B T", _F8, None), "edge_n_samples": ("B T", _I4, None),
+    "n_certified": ("B", _I4, None)})       # (edge_verdict_all, bytes, is no entry of a table of doubles and int32: _verdict_bytes)
+
+
+def _verdict_bytes(kit, cio, proof, B, T, S):
+    """edge_verdict_all (B, T, S, S) int8 of the call's kind, into the struct and the result."""
+    proof["edge_verdict_all"] = kit.empty((B, T, S, S), np.int8)
+    cio.edge_verdict_all = kit.ptr(proof["edge_verdict_all"])
+
+
+def check_edge_rule(resolution, max_samples) -> None:
+    """The certified rule's arguments, with no device in sight (mkh_certified_sweep's checks)."""
+    if not (np.isfinite(float(resolution)) and float(resolution) > 0.0):
+        raise ValueError(f"edge_resolution must be finite and > 0, got {resolution}")
+    if not 1 <= int(max_samples) <= 4096:
+        raise ValueError(f"max_edge_samples must be in [1, 4096], got {max_samples}")
+
+
 LADDER_REFINE_FREE_IO_FIELDS = ("edge_collision", "n_edge_collisions", "edge_margin", "node_margin")
 
 
@@ -918,6 +952,16 @@ def lib() -> C.CDLL:
                        C.POINTER(MkhLadderNodesIO), C.POINTER(MkhLadderRefineIO), C.POINTER(MkhLadderFreeIO), C.c_int32, C.c_void_p]
     L.mkh_solve_trajectory_ladder_free.restype = C.c_int32
     L.mkh_solve_trajectory_ladder_free_refined.argtypes = L.mkh_solve_trajectory_ladder_free.argtypes
+    L.mkh_ladder_select_certified.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_int32,
+                                              C.POINTER(MkhLadderIO), C.POINTER(MkhLadderFreeIO), C.POINTER(MkhLadderCertifiedIO),
+                                              C.c_int32, C.c_void_p]
+    L.mkh_ladder_select_certified.restype = C.c_int32
+    L.mkh_solve_trajectory_ladder_certified.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double] + \
+        common[2:8] + [C.c_int32, C.c_double, C.c_double, C.c_uint64, C.c_int64, C.c_double, C.c_int32, C.c_int32,
+                       C.POINTER(MkhTrajectoryLadderIO), C.POINTER(MkhLadderNodesIO), C.POINTER(MkhLadderRefineIO),
+                       C.POINTER(MkhLadderFreeIO), C.POINTER(MkhLadderCertifiedIO), C.c_int32, C.c_void_p]
+    L.mkh_solve_trajectory_ladder_certified.restype = C.c_int32
     L.mkh_solve_trajectory_ladder_free_refined.restype = C.c_int32
     L.mkh_ladder_refine_free.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p] + \
         common[3:8] + [C.c_int32, C.c_double, C.c_double, C.c_int32, C.POINTER(MkhLadderRefineIO),
@@ -949,6 +993,7 @@ EXPORTED_SYMBOLS = (
     "mkh_ladder_refine_free", "mkh_solve_trajectory_ladder_free_refined",
     "mkh_select_trajectory_candidates", "mkh_solve_trajectory_multistart_free",
     "mkh_certified_sweep", "mkh_checker_motion_reach",
+    "mkh_ladder_select_certified", "mkh_solve_trajectory_ladder_certified",
 )
 
 LIE_OPS = {"se3_log": (0, 7, 0, (6,)), "se3_jlog": (1, 7, 0, (6, 6)), "se3_ljacinv": (2, 6, 0, (6, 6)),
@@ -1040,7 +1085,8 @@ class _Kit:
         return self.torch.as_tensor(x).to(device=self.dev, dtype=self.torch.float64).contiguous()
 
     def _device_empty(self, shape, dtype):
-        return self.torch.empty(shape, dtype=self.torch.float64 if dtype is np.float64 else self.torch.int32, device=self.dev)
+        t = self.torch
+        return t.empty(shape, dtype=t.float64 if dtype is np.float64 else (t.int8 if dtype is np.int8 else t.int32), device=self.dev)
 
     def ones(self, shape):
         """int32 flags that are all set: "None means every row"."""
@@ -2022,7 +2068,19 @@ class NativeProblem:
         checker = _checker_handle(self, checker, edge_samples)
         return self._ladder_select(q, q_nodes, tracked, max_step_sq, weights, checker, int(edge_samples), bool(return_margins))
 
-    def _ladder_select(self, q, q_nodes, tracked, max_step_sq, weights, checker, edge_samples, return_margins):
+    def ladder_select_certified(self, q, q_nodes, checker: "NativeProblem", tracked=None, max_step_sq: float = float("inf"),
+                                weights=None, resolution: float = 0.02, max_samples: int = 64, require_certified: bool = False,
+                                return_margins: bool = False):
+        """mkh_ladder_select_certified: ladder_select under THE RULE "with a certifying checker" — every edge into an effectively
+        tracked node judged by certified_sweep's rule at `resolution` and `max_samples`, blocked where it collides or, with
+        `require_certified`, wherever it is not proven free.  Returns (LadderPathOut, LadderCertifiedOut); with `return_margins`
+        the latter carries node_margin (B, T, S), edge_margin_all (B, T, S, S) and edge_verdict_all (B, T, S, S) int8."""
+        check_edge_rule(resolution, max_samples)
+        checker = _checker_handle(self, checker, 1)
+        rule = (float(resolution), int(max_samples), EDGE_REQUIRE_CERTIFIED if require_certified else EDGE_REJECT_COLLIDING)
+        return self._ladder_select(q, q_nodes, tracked, max_step_sq, weights, checker, 0, bool(return_margins), rule)
+
+    def _ladder_select(self, q, q_nodes, tracked, max_step_sq, weights, checker, edge_samples, return_margins, certified=None):
         m, kit = self.nmodel.model, _call_kit(q)
         B = int(q.shape[0])
         kit.want(q_nodes, (B, "T", "S", m.nq), "q_nodes")
@@ -2039,6 +2097,14 @@ class NativeProblem:
                 _check(lib().mkh_ladder_select(self.handle, *rungs, C.byref(io), kit.devp, kit.stream))
             return LadderPathOut(**out), None
         fio, more = LADDER_FREE_OUT.make[_MARGINS if return_margins else _NONE](kit.empty, kit.ptr, sizes)
+        if certified is not None:
+            cio, proof = LADDER_CERTIFIED_OUT.make[_NONE](kit.empty, kit.ptr, sizes)
+            if return_margins:
+                _verdict_bytes(kit, cio, proof, B, T, S)
+            with _with_checker(self, checker):
+                _check(lib().mkh_ladder_select_certified(self.handle, checker.handle, *rungs, *certified, C.byref(io), C.byref(fio),
+                                                         C.byref(cio), kit.devp, kit.stream))
+            return LadderPathOut(**out), LadderCertifiedOut(**more, **proof)
         with _with_checker(self, checker):
             _check(lib().mkh_ladder_select_free(self.handle, checker.handle, *rungs, edge_samples, C.byref(io), C.byref(fio),
                                                 kit.devp, kit.stream))
@@ -2100,11 +2166,33 @@ class NativeProblem:
                                              qvel_dt, return_all, wave_kernel, lane_kernel, quad_kernel, seed_table, bool(refine),
                                              nodes, (checker, int(edge_samples)))
 
+    def solve_trajectory_ladder_certified(self, q, frame_targets=None, posture_target=None, com_target=None, dt: float = 1e-2,
+                                          damping: float = 1e-12, *, checker: "NativeProblem", resolution: float,
+                                          max_samples: int = 64, require_certified: bool = False, n_seeds: int, max_iters: int,
+                                          pos_threshold: float, ori_threshold: float, n_nodes: Optional[int] = None,
+                                          min_distance: float = 0.1, unwind_turns: bool = False,
+                                          max_step_sq: float = float("inf"), rng_seed: int = 0, target_index0: int = 0, seeds=None,
+                                          weights=None, qvel_dt: Optional[float] = None, return_all: bool = False,
+                                          wave_kernel: bool = False, lane_kernel: bool = False, quad_kernel: bool = False,
+                                          seed_table=None):
+        """mkh_solve_trajectory_ladder_certified: solve_trajectory_ladder_free with the edges judged by certified_sweep's rule at
+        `resolution` and `max_samples` instead of a fixed sample count (ladder_select_certified states the policy).  Returns (the
+        plain call's result, LadderCertifiedOut).  There is no refinement here: the pass still samples."""
+        check_edge_rule(resolution, max_samples)
+        checker = _checker_handle(self, checker, 1)
+        nodes = None if n_nodes is None else (int(n_nodes), float(min_distance), bool(unwind_turns))
+        rule = (float(resolution), int(max_samples), EDGE_REQUIRE_CERTIFIED if require_certified else EDGE_REJECT_COLLIDING)
+        return self._solve_trajectory_ladder(q, frame_targets, posture_target, com_target, dt, damping, n_seeds, max_iters,
+                                             pos_threshold, ori_threshold, max_step_sq, rng_seed, target_index0, seeds, weights,
+                                             qvel_dt, return_all, wave_kernel, lane_kernel, quad_kernel, seed_table, False,
+                                             nodes, (checker, 0, rule))
+
     def _solve_trajectory_ladder(self, q, frame_targets, posture_target, com_target, dt, damping, n_seeds, max_iters,
                                  pos_threshold, ori_threshold, max_step_sq, rng_seed, target_index0, seeds, weights, qvel_dt,
                                  return_all, wave_kernel, lane_kernel, quad_kernel, seed_table, refine, nodes, free=None):
         """The body of the ladder calls; `nodes`: None, or (n_nodes, min_distance, unwind_turns); `free`: None, or (checker,
-        edge_samples) — the result is then (the plain result, LadderFreeOut)."""
+        edge_samples) — the result is then (the plain result, LadderFreeOut) — or (checker, 0, (resolution, max_samples, policy)),
+        the certified rule — (the plain result, LadderCertifiedOut)."""
         if seeds is not None and seed_table is not None:
             raise ValueError("seeds and seed_table are two sources of the same starts: pass one of them")
         m, kit = self.nmodel.model, _call_kit(q)
@@ -2161,6 +2249,13 @@ class NativeProblem:
                                                                    kit.stream))
             return result(**out)
         fio, more = LADDER_FREE_OUT.make[_NONE](empty, ptr, sizes)
+        if len(free) == 3:
+            cio, proof = LADDER_CERTIFIED_OUT.make[_NONE](empty, ptr, sizes)
+            with _with_checker(self, free[0]), _attached(self, seed_table):
+                _check(lib().mkh_solve_trajectory_ladder_certified(self.handle, free[0].handle, B, T, S, K, r, *loops, *free[2],
+                                                                   C.byref(io), nio, rio, C.byref(fio), C.byref(cio), flags,
+                                                                   kit.stream))
+            return result(**out), LadderCertifiedOut(**more, **proof)
         call = lib().mkh_solve_trajectory_ladder_free_refined if refine else lib().mkh_solve_trajectory_ladder_free
         with _with_checker(self, free[0]), _attached(self, seed_table):
             _check(call(self.handle, free[0].handle, B, T, S, K, r, *loops, free[1], C.byref(io), nio, rio, C.byref(fio), flags,

@@ -1,5 +1,5 @@
 // The collision checker's host side (checker_host.hip), as the checked entry points of minkhip.hip see it: two refusals and the
-// four stages that run a checker handle on a call's Stager.  Which buffer a stage goes through, in chunks of how many items and
+// five stages that run a checker handle on a call's Stager.  Which buffer a stage goes through, in chunks of how many items and
 // behind which pre-pass is its own business (checker_plan.h decides, checker_host.hip launches).
 #pragma once
 #include "checker_plan.h"
@@ -18,6 +18,9 @@ void clearance_rows(Stager& st, MkhProblem* ck, size_t N, const double* d_q, dou
                     double* distance, int32_t* status);
 // The sweep of a's edges (a.first, a.count, a.cv and a.n_cv are the stage's to fill).
 void sweep_edges(Stager& st, const MkhProblem* ck, SweepArgs a);
+// The certified sweep of a's edges in a's mode, one launch (a.reach is the stage's to fill: the checker's reach table, filled and
+// uploaded at the handle's first use — a failure of that upload is latched like a failed launch).
+void certify_edges(Stager& st, MkhProblem* ck, CertifiedArgs a);
 // The check of candidate tracking over all T·B·S rows: node margins, the status bit, edge margins.
 void tmf_check(Stager& st, const MkhProblem* ck, int B, int S, int T, int M, const double* q_all, const int32_t* cv_all, int32_t* st_all,
                double* nm_all, double* em_all);

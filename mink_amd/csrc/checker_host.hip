@@ -1,5 +1,5 @@
 // The collision checker's host side: the entry points that run a checker handle on its own (mkh_clearance, mkh_swept_clearance),
-// the ones that attach one or size its buffers, and the four stages the checked calls of minkhip.hip run on their Stager
+// the ones that attach one or size its buffers, and the five stages the checked calls of minkhip.hip run on their Stager
 // (checker_host.h).  Every decision that needs only integers — refusals, chunk sizes, launch geometry — is checker_plan.h's; here
 // a handle is read into a CheckerShape, and launches are enqueued.
 //
@@ -49,13 +49,17 @@ static const std::vector<double>& reach_of(MkhProblem* ck) {
 }
 
 // ... and on the device, uploaded once (synchronous: a constant of the handle from here on).
-static int32_t ensure_reach(MkhProblem* ck) {
-  if (ck->d_reach) return MKH_OK;
+static hipError_t upload_reach(MkhProblem* ck) {
+  if (ck->d_reach) return hipSuccess;
   const std::vector<double>& h = reach_of(ck);
-  HIP_OK(hipMalloc((void**)&ck->d_reach, h.size() * sizeof(double)));
-  const hipError_t e = hipMemcpy(ck->d_reach, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
+  hipError_t e = hipMalloc((void**)&ck->d_reach, h.size() * sizeof(double));
+  if (e != hipSuccess) { ck->d_reach = nullptr; return e; }
+  e = hipMemcpy(ck->d_reach, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
   if (e != hipSuccess) { (void)hipFree(ck->d_reach); ck->d_reach = nullptr; }
-  HIP_OK(e);
+  return e;
+}
+static int32_t ensure_reach(MkhProblem* ck) {
+  HIP_OK(upload_reach(ck));
   return MKH_OK;
 }
 
@@ -109,6 +113,15 @@ void sweep_edges(Stager& st, const MkhProblem* ck, SweepArgs a) {
     ST_LAUNCH(st, launch_convex_sweep(st.stream, ck->d_wide, ck->cv, a, ipw));
     ST_LAUNCH(st, launch_sweep(st.stream, ck->d_wide, nbody, nq, np, a));
   });
+}
+
+// ---- certified sweep (include/minkhip.h "THE RULE OF THE CERTIFIED SWEEP"; kernel: certified_sweep.hip): one launch in every mode —
+// a checker with general convex pairs never gets here (CheckerUse::certified)
+void certify_edges(Stager& st, MkhProblem* ck, CertifiedArgs a) {
+  if (!st.ok()) return;
+  st.latch(upload_reach(ck));
+  a.reach = ck->d_reach;
+  ST_LAUNCH(st, launch_certified_sweep(st.stream, ck->d_wide, ck->model->nbody, ck->model->nq, ck->dev.n_pairs, a));
 }
 
 // ---- checked candidate tracking (kernels: trajectory_free.hip): general convex pairs in chunks of floor(check_rows / (1 + M))
@@ -293,7 +306,7 @@ int32_t mkh_certified_sweep(MkhProblem* ck, int32_t N, const double* q_from, con
   Stager st{ck, (hipStream_t)hip_stream, devp, "certified_sweep"};
   const size_t Nz = N, nq = ck->model->nq, f8 = sizeof(double), i4 = sizeof(int32_t);
   CertifiedArgs a{};
-  a.N = N; a.resolution = resolution; a.max_samples = max_samples; a.reach = ck->d_reach;
+  a.mode = kSweepPairs; a.N = N; a.resolution = resolution; a.max_samples = max_samples;
   a.from = st.up(WS_C_Q, q_from, Nz * nq);
   a.to = st.up(WS_SW_TO, q_to, Nz * nq);
   a.margin = io->margin; a.lower_bound = io->lower_bound; a.motion = io->motion;
@@ -309,7 +322,7 @@ int32_t mkh_certified_sweep(MkhProblem* ck, int32_t N, const double* q_from, con
     }
   }
   if (!st.ok()) return st.finish();
-  ST_LAUNCH(st, launch_certified_sweep(st.stream, ck->d_wide, ck->model->nbody, (int)nq, ck->dev.n_pairs, a));
+  certify_edges(st, ck, a);
   if (devp) return st.finish();
   st.down(io->margin, a.margin, Nz * f8); st.down(io->lower_bound, a.lower_bound, Nz * f8); st.down(io->motion, a.motion, Nz * f8);
   st.down(io->sample, a.sample, Nz * i4); st.down(io->pair, a.pair, Nz * i4); st.down(io->segment, a.segment, Nz * i4);

@@ -122,8 +122,10 @@ enum WsRole {
   // swept clearance and the checked ladder calls: a host caller's q_to as it came (q_from goes through WS_C_Q); the nodes'
   // clearance margins (B, T, S) and effective tracked flags; the blocked flag of every edge, (B, T, S, S) bytes; every edge's swept
   // margin when the caller asked for it; a host caller's outputs — F_OUT_I: edge_collision (B, T) | n_edge_collisions (B,), F_OUT_F:
-  // edge_margin (B, T)
-  WS_SW_TO, WS_F_NMARGIN, WS_F_TRK, WS_F_BLOCK, WS_F_EMARGIN, WS_F_OUT_I, WS_F_OUT_F,
+  // edge_margin (B, T).  The certifying ladder calls: F_OUT_I holds edge_verdict | edge_n_samples (B, T) | n_certified (B,) behind
+  // those, F_OUT_F edge_lower_bound (B, T) behind edge_margin; F_EVERDICT: every edge's verdict, (B, T, S, S) bytes, when a host
+  // caller asked for it
+  WS_SW_TO, WS_F_NMARGIN, WS_F_TRK, WS_F_BLOCK, WS_F_EMARGIN, WS_F_OUT_I, WS_F_OUT_F, WS_F_EVERDICT,
   // a ladder refinement with a checker: RF_MARGIN: the node margins and the edge margins of the input path, then of the working
   // path, (B, T) each; RF_TRIP: what lr_check_kernel leaves per step, (B, 3, slots); RF_IDX: the index array of the input path seen as a
   // ladder of width 1 (zeros) | its effective flags, (B, T) each.  A host caller's outputs go through F_OUT_I, F_OUT_F and

@@ -1504,65 +1504,152 @@ int32_t mkh_ladder_select(MkhProblem* p, int32_t B, int32_t T, int32_t S, const 
 }
 
 // ---- the checked ladder (include/minkhip.h THE RULE "with a checker"; kernels: sweep.hip, ladder.hip)
-struct LadderFreeOut {             // device arrays: the back-trace's (B, T) / (B,) outputs, and every edge's margin or NULL
-  int32_t *edge_collision, *n_edge_collisions;
-  double *edge_margin, *edge_margin_all;
+// How a checked ladder call judges an edge: M interior samples (THE RULE "with a checker"), or — certified — THE RULE OF THE
+// CERTIFIED SWEEP at a resolution, a cap and a policy (THE RULE "with a certifying checker").
+struct EdgeRule {
+  int M = 0;
+  bool certified = false;
+  double resolution = 0.0;
+  int32_t max_samples = 0, policy = 0;
+  CheckerUse use(bool refined) const { return certified ? CheckerUse::certified() : CheckerUse::ladder(M, refined); }
 };
 
+// device arrays: the back-trace's (B, T) / (B,) outputs and every edge's margin or NULL; behind them the certified rule's — the
+// chosen edges' verdict, lower bound and count, n_certified, every edge's verdict or NULL (all NULL under the sampled rule)
+struct LadderFreeOut {
+  int32_t *edge_collision, *n_edge_collisions;
+  double *edge_margin, *edge_margin_all;
+  int32_t* edge_verdict = nullptr;
+  double* edge_lower_bound = nullptr;
+  int32_t *edge_n_samples = nullptr, *n_certified = nullptr;
+  int8_t* edge_verdict_all = nullptr;
+};
+
+// The device side of a checked call's edge outputs: the caller's arrays for a device-pointer call, else workspace (F_OUT_I:
+// edge_collision | n_edge_collisions | edge_verdict | edge_n_samples | n_certified; F_OUT_F: edge_margin | edge_lower_bound).
+static LadderFreeOut ladder_free_out(Stager& st, int B, int T, int W, const EdgeRule& rule, const MkhLadderFreeIO* fio,
+                                     const MkhLadderCertifiedIO* cio) {
+  const size_t Bz = B, R = Bz * T;
+  const bool cert = rule.certified;
+  LadderFreeOut o{fio->edge_collision, fio->n_edge_collisions, fio->edge_margin, fio->edge_margin_all};
+  if (cert) {
+    o.edge_verdict = cio->edge_verdict; o.edge_lower_bound = cio->edge_lower_bound; o.edge_n_samples = cio->edge_n_samples;
+    o.n_certified = cio->n_certified; o.edge_verdict_all = cio->edge_verdict_all;
+  }
+  if (st.devp) return o;
+  o.edge_collision = st.i32(WS_F_OUT_I, cert ? 3 * R + 2 * Bz : R + Bz);
+  o.n_edge_collisions = o.edge_collision ? o.edge_collision + R : nullptr;
+  o.edge_margin = st.f64(WS_F_OUT_F, cert ? 2 * R : R);
+  if (o.edge_margin_all) o.edge_margin_all = st.f64(WS_F_EMARGIN, R * W * W);
+  if (cert && st.ok()) {
+    o.edge_verdict = o.n_edge_collisions + Bz; o.edge_n_samples = o.edge_verdict + R; o.n_certified = o.edge_n_samples + R;
+    o.edge_lower_bound = o.edge_margin + R;
+    if (o.edge_verdict_all) o.edge_verdict_all = (int8_t*)st.need(WS_F_EVERDICT, R * W * W);
+  }
+  return o;
+}
+
+static void ladder_free_out_down(Stager& st, int B, int T, int W, const LadderFreeOut& o, const MkhLadderFreeIO* fio,
+                                 const MkhLadderCertifiedIO* cio) {
+  const size_t Bz = B, R = Bz * T, f8 = sizeof(double), i4 = sizeof(int32_t);
+  st.down(fio->edge_collision, o.edge_collision, R * i4);
+  st.down(fio->n_edge_collisions, o.n_edge_collisions, Bz * i4);
+  st.down(fio->edge_margin, o.edge_margin, R * f8);
+  st.down(fio->edge_margin_all, o.edge_margin_all, R * W * W * f8);
+  if (!cio) return;
+  st.down(cio->edge_verdict, o.edge_verdict, R * i4);
+  st.down(cio->edge_lower_bound, o.edge_lower_bound, R * f8);
+  st.down(cio->edge_n_samples, o.edge_n_samples, R * i4);
+  st.down(cio->n_certified, o.n_certified, Bz * i4);
+  st.down(cio->edge_verdict_all, o.edge_verdict_all, R * W * W);
+}
+
 // The sweep of every edge into a tracked node, the masked search, and the chosen edges' margins — on device arrays, on the call's
-// stream.  d_tracked: the EFFECTIVE flags.
-static void ladder_search_free(Stager& st, const MkhProblem* ck, int B, int T, int S, int M, const double* d_q, const double* d_nodes,
-                               const int32_t* d_tracked, const double* d_w, double max_step_sq, int32_t* o_node, int32_t* o_nt,
-                               int32_t* o_nb, double* o_len, int32_t* o_eb, const LadderFreeOut& f) {
+// stream.  d_tracked: the EFFECTIVE flags.  The sampled rule: two launches of sweep_kernel around the search; the certified
+// rule: two of certified_sweep_kernel in their place, and the count of the chosen edges that are proven free.
+static void ladder_search_free(Stager& st, MkhProblem* ck, int B, int T, int S, const EdgeRule& rule, const double* d_q,
+                               const double* d_nodes, const int32_t* d_tracked, const double* d_w, double max_step_sq, int32_t* o_node,
+                               int32_t* o_nt, int32_t* o_nb, double* o_len, int32_t* o_eb, const LadderFreeOut& f) {
   const MkhProblem* const p = st.p;
   const size_t R = (size_t)B * T, nch = ((size_t)S + 63) / 64, E = R * S * S;
   uint8_t* const blocked = (uint8_t*)st.need(WS_F_BLOCK, E);
   unsigned long long* const brk = (unsigned long long*)st.need(WS_L_PRED, R * nch * 8 + R * S);
   uint8_t* const pred = (uint8_t*)(brk + R * nch);
   if (!st.ok()) return;
-  // (rung 0 has no edges: its flags are never read, and its margins are NaN — every byte 0xff is one)
+  // (rung 0 has no edges: its flags are never read, and its margins are NaN — every byte 0xff is one —, its verdicts −1 — too)
   if (f.edge_margin_all)
     ST_LAUNCH(st, hipMemset2DAsync(f.edge_margin_all, (size_t)T * S * S * sizeof(double), 0xff, (size_t)S * S * sizeof(double), B, st.stream));
+  if (f.edge_verdict_all)
+    ST_LAUNCH(st, hipMemset2DAsync(f.edge_verdict_all, (size_t)T * S * S, 0xff, (size_t)S * S, B, st.stream));
+  mkh::CertifiedArgs ca{};
+  ca.resolution = rule.resolution; ca.max_samples = rule.max_samples; ca.policy = rule.policy;
+  ca.T = T; ca.W = S; ca.nodes = d_nodes; ca.tracked = d_tracked;
   if (T > 1) {
-    mkh::SweepArgs a{};
-    a.mode = mkh::kSweepLadder; a.M = M; a.T = T; a.W = S; a.N = (long long)(E - (size_t)B * S * S);
-    a.nodes = d_nodes; a.tracked = d_tracked; a.margin = f.edge_margin_all; a.blocked = blocked;
-    sweep_edges(st, ck, a);
+    if (rule.certified) {
+      mkh::CertifiedArgs a = ca;
+      a.mode = mkh::kSweepLadder; a.N = (long long)(E - (size_t)B * S * S);
+      a.margin = f.edge_margin_all; a.blocked = blocked; a.verdict_all = f.edge_verdict_all;
+      certify_edges(st, ck, a);
+    } else {
+      mkh::SweepArgs a{};
+      a.mode = mkh::kSweepLadder; a.M = rule.M; a.T = T; a.W = S; a.N = (long long)(E - (size_t)B * S * S);
+      a.nodes = d_nodes; a.tracked = d_tracked; a.margin = f.edge_margin_all; a.blocked = blocked;
+      sweep_edges(st, ck, a);
+    }
   }
   ST_LAUNCH(st, launch_ladder_search_free(st.stream, B, T, S, p->dev.nq, p->dev.nv, p->model->njnt, p->ws[WS_JNT].i32(), d_q, d_nodes,
                                           d_tracked, blocked, d_w, max_step_sq, pred, brk, o_node, o_nt, o_nb, o_len, o_eb,
                                           f.edge_collision, f.n_edge_collisions));
+  if (rule.certified) {
+    mkh::CertifiedArgs c = ca;
+    c.mode = mkh::kSweepPath; c.N = (long long)R; c.node_index = o_node;
+    c.margin = f.edge_margin; c.lower_bound = f.edge_lower_bound; c.n_samples = f.edge_n_samples; c.verdict = f.edge_verdict;
+    certify_edges(st, ck, c);
+    ST_LAUNCH(st, mkh::launch_certified_count(st.stream, B, T, f.edge_verdict, f.n_certified));
+    return;
+  }
   mkh::SweepArgs c{};
-  c.mode = mkh::kSweepPath; c.M = M; c.T = T; c.W = S; c.N = (long long)R;
+  c.mode = mkh::kSweepPath; c.M = rule.M; c.T = T; c.W = S; c.N = (long long)R;
   c.nodes = d_nodes; c.tracked = d_tracked; c.node_index = o_node; c.margin = f.edge_margin;
   sweep_edges(st, ck, c);
 }
 
-// What the checked calls refuse about the checker, the sample count and the graph's size.
-static int32_t ladder_free_refuse(const MkhProblem* p, const MkhProblem* ck, int32_t B, int32_t T, int32_t S, int32_t n_samples,
-                                  const MkhLadderFreeIO* f, const char* who, bool refined) {
+// What the checked calls refuse about the checker, the edge rule and the graph's size (cio: the certified rule's outputs).
+static int32_t ladder_free_refuse(const MkhProblem* p, const MkhProblem* ck, int32_t B, int32_t T, int32_t S, const EdgeRule& rule,
+                                  const MkhLadderFreeIO* f, const MkhLadderCertifiedIO* cio, const char* who, bool refined) {
+  if (rule.certified) {                                        // (mkh_certified_sweep's argument checks, and the policy)
+    if (!std::isfinite(rule.resolution) || !(rule.resolution > 0.0))
+      return fail(MKH_E_INVALID, "%s: resolution = %g must be finite and > 0", who, rule.resolution);
+    if (rule.max_samples < 1 || rule.max_samples > 4096)
+      return fail(MKH_E_INVALID, "%s: max_samples = %d must be in [1, 4096]", who, rule.max_samples);
+    if (rule.policy != MKH_EDGE_REJECT_COLLIDING && rule.policy != MKH_EDGE_REQUIRE_CERTIFIED)
+      return fail(MKH_E_INVALID, "%s: edge_policy = %d: MKH_EDGE_REJECT_COLLIDING (0) or MKH_EDGE_REQUIRE_CERTIFIED (1)", who, rule.policy);
+  }
   // (general convex pairs: through the checker's sweep_rows where the call sweeps and nothing else; with refinement through its
-  //  check_rows as well)
-  if (const int32_t rc = sweep_refuse_for(p, ck, who, CheckerUse::ladder(n_samples, refined))) return rc;
-  if (n_samples < 1) return fail(MKH_E_INVALID, "%s: n_samples = %d must be >= 1", who, n_samples);
+  //  check_rows as well; the certified rule refuses them whatever the buffers hold)
+  if (const int32_t rc = sweep_refuse_for(p, ck, who, rule.use(refined))) return rc;
+  if (!rule.certified && rule.M < 1) return fail(MKH_E_INVALID, "%s: n_samples = %d must be >= 1", who, rule.M);
   if (!f || !f->edge_collision || !f->n_edge_collisions || !f->edge_margin)
     return fail(MKH_E_INVALID, "%s: free_io and its outputs edge_collision, n_edge_collisions, edge_margin are required", who);
+  if (rule.certified && (!cio || !cio->edge_verdict || !cio->edge_lower_bound || !cio->edge_n_samples || !cio->n_certified))
+    return fail(MKH_E_INVALID, "%s: certified_io and its outputs edge_verdict, edge_lower_bound, edge_n_samples, n_certified are required", who);
   if ((long long)B * T * S * S > 0x7fffffffLL)
     return fail(MKH_E_LIMIT, "%s: B * T * S^2 = %lld edges, at most 2^31 - 1", who, (long long)B * T * S * S);
   return MKH_OK;
 }
 
-int32_t mkh_ladder_select_free(MkhProblem* p, MkhProblem* ck, int32_t B, int32_t T, int32_t S, const double* q, const double* q_nodes,
-                               const int32_t* tracked, const double* weights, double max_step_sq, int32_t n_samples,
-                               const MkhLadderIO* io, const MkhLadderFreeIO* fio, int32_t flags, void* hip_stream) {
-  const char* const who = "mkh_ladder_select_free";
+// mkh_ladder_select_free (cio == NULL) and mkh_ladder_select_certified.
+static int32_t ladder_select_checked(const char* who, const char* tag, const EdgeRule& rule, MkhProblem* p, MkhProblem* ck, int32_t B,
+                                     int32_t T, int32_t S, const double* q, const double* q_nodes, const int32_t* tracked,
+                                     const double* weights, double max_step_sq, const MkhLadderIO* io, const MkhLadderFreeIO* fio,
+                                     const MkhLadderCertifiedIO* cio, int32_t flags, void* hip_stream) {
   if (!p) return fail(MKH_E_INVALID, "null problem");
   if (const int32_t rc = ladder_refuse(p, B, T, S, max_step_sq, who)) return rc;
   if (const int32_t rc = refuse_unwind(flags, who)) return rc;
   if (!q || !q_nodes || !tracked) return fail(MKH_E_INVALID, "%s: q, q_nodes and tracked are required", who);
   if (!io || !io->node_index || !io->n_tracked || !io->n_breaks || !io->path_length || !io->edge_break)
     return fail(MKH_E_INVALID, "%s: io and its outputs node_index, n_tracked, n_breaks, path_length, edge_break are required", who);
-  if (const int32_t rc = ladder_free_refuse(p, ck, B, T, S, n_samples, fio, who, false)) return rc;
+  if (const int32_t rc = ladder_free_refuse(p, ck, B, T, S, rule, fio, cio, who, false)) return rc;
   if (mkh::ladder_source_tile(S, p->dev.nq, p->dev.nv, p->model->njnt, nullptr, true) < 1)
     return fail(MKH_E_LIMIT, "%s: nq = %d: one destination tile and one source node with its flags do not fit 64 KB of LDS", who, p->dev.nq);
   const bool devp = (flags & MKH_FLAG_DEVICE_PTRS) != 0;
@@ -1570,7 +1657,7 @@ int32_t mkh_ladder_select_free(MkhProblem* p, MkhProblem* ck, int32_t B, int32_t
     if (const int32_t rc = ladder_weights_refuse(weights, p->dev.nv, who)) return rc;
   HIP_OK(hipSetDevice(p->model->device));
   if (const int32_t rc = ms_build_tables(p)) return rc;
-  Stager st{p, (hipStream_t)hip_stream, devp, "ladder_select_free"};
+  Stager st{p, (hipStream_t)hip_stream, devp, tag};
   const size_t Bz = B, R = Bz * T, N = R * S, nq = p->dev.nq, f8 = sizeof(double), i4 = sizeof(int32_t);
   const double* const d_q = st.up(WS_IN_Q, q, Bz * nq);
   const double* const d_nodes = st.up(WS_L_Q, q_nodes, N * nq);
@@ -1578,22 +1665,19 @@ int32_t mkh_ladder_select_free(MkhProblem* p, MkhProblem* ck, int32_t B, int32_t
   const int32_t* const d_trk = st.up_i32(WS_L_TRK, tracked, N);
   int32_t *o_node = io->node_index, *o_eb = io->edge_break, *o_nt = io->n_tracked, *o_nb = io->n_breaks;
   double *o_len = io->path_length, *o_q = io->q_path;
-  LadderFreeOut f{fio->edge_collision, fio->n_edge_collisions, fio->edge_margin, fio->edge_margin_all};
   if (!devp) {
     o_node = st.i32(WS_OUT_PICK, 2 * R + 2 * Bz); o_eb = o_node + R; o_nt = o_node + 2 * R; o_nb = o_nt + Bz;
     o_len = st.f64(WS_OUT_LEN, Bz);
     o_q = io->q_path ? st.f64(WS_OUT_Q, R * nq) : nullptr;
-    f.edge_collision = st.i32(WS_F_OUT_I, R + Bz); f.n_edge_collisions = f.edge_collision ? f.edge_collision + R : nullptr;
-    f.edge_margin = st.f64(WS_F_OUT_F, R);
-    if (f.edge_margin_all) f.edge_margin_all = st.f64(WS_F_EMARGIN, N * S);
   }
+  const LadderFreeOut f = ladder_free_out(st, B, T, S, rule, fio, cio);
   double* const d_nm = (double*)st.given_or(WS_F_NMARGIN, fio->node_margin, N * f8);
   int32_t* const d_eff = st.i32(WS_F_TRK, N);
   if (!st.ok()) return st.finish();
   // ---- the nodes' clearance, their effective flags, the edges, the search
   clearance_rows(st, ck, N, d_nodes, d_nm, nullptr, nullptr, nullptr, nullptr);
   ST_LAUNCH(st, launch_ladder_free_tracked(st.stream, d_trk, d_nm, (long long)N, d_eff));
-  ladder_search_free(st, ck, B, T, S, n_samples, d_q, d_nodes, d_eff, d_w, max_step_sq, o_node, o_nt, o_nb, o_len, o_eb, f);
+  ladder_search_free(st, ck, B, T, S, rule, d_q, d_nodes, d_eff, d_w, max_step_sq, o_node, o_nt, o_nb, o_len, o_eb, f);
   if (o_q) ST_LAUNCH(st, launch_ladder_gather(st.stream, d_nodes, o_q, o_node, (long long)R, S, (int)nq));
   if (devp) return st.finish();
   st.down(io->node_index, o_node, R * i4);
@@ -1602,12 +1686,28 @@ int32_t mkh_ladder_select_free(MkhProblem* p, MkhProblem* ck, int32_t B, int32_t
   st.down(io->n_breaks, o_nb, Bz * i4);
   st.down(io->path_length, o_len, Bz * f8);
   st.down(io->q_path, o_q, R * nq * f8);
-  st.down(fio->edge_collision, f.edge_collision, R * i4);
-  st.down(fio->n_edge_collisions, f.n_edge_collisions, Bz * i4);
-  st.down(fio->edge_margin, f.edge_margin, R * f8);
   st.down(fio->node_margin, d_nm, N * f8);
-  st.down(fio->edge_margin_all, f.edge_margin_all, N * S * f8);
+  ladder_free_out_down(st, B, T, S, f, fio, cio);
   return st.finish();
+}
+
+int32_t mkh_ladder_select_free(MkhProblem* p, MkhProblem* ck, int32_t B, int32_t T, int32_t S, const double* q, const double* q_nodes,
+                               const int32_t* tracked, const double* weights, double max_step_sq, int32_t n_samples,
+                               const MkhLadderIO* io, const MkhLadderFreeIO* fio, int32_t flags, void* hip_stream) {
+  EdgeRule rule;
+  rule.M = n_samples;
+  return ladder_select_checked("mkh_ladder_select_free", "ladder_select_free", rule, p, ck, B, T, S, q, q_nodes, tracked, weights,
+                               max_step_sq, io, fio, nullptr, flags, hip_stream);
+}
+
+int32_t mkh_ladder_select_certified(MkhProblem* p, MkhProblem* ck, int32_t B, int32_t T, int32_t S, const double* q,
+                                    const double* q_nodes, const int32_t* tracked, const double* weights, double max_step_sq,
+                                    double resolution, int32_t max_samples, int32_t edge_policy, const MkhLadderIO* io,
+                                    const MkhLadderFreeIO* fio, const MkhLadderCertifiedIO* cio, int32_t flags, void* hip_stream) {
+  EdgeRule rule;
+  rule.certified = true; rule.resolution = resolution; rule.max_samples = max_samples; rule.policy = edge_policy;
+  return ladder_select_checked("mkh_ladder_select_certified", "ladder_select_certified", rule, p, ck, B, T, S, q, q_nodes, tracked,
+                               weights, max_step_sq, io, fio, cio, flags, hip_stream);
 }
 
 // The refinement pass (include/minkhip.h "THE RULE OF THE REFINEMENT") on device arrays, into device outputs, on the call's stream:
@@ -1917,32 +2017,22 @@ static LadderCall ladder_stage(Stager& st, int B, int T, int S, int W, const dou
   return c;
 }
 
-// A checked call's part of a ladder call (ck == NULL: a plain one): the checker, the samples per edge, and the outputs.
+// A checked call's part of a ladder call (ck == NULL: a plain one): the checker, how it judges an edge, and the outputs.
 struct LadderFree {
   MkhProblem* ck = nullptr;
-  int M = 0;
+  EdgeRule rule{};
   const MkhLadderFreeIO* io = nullptr;
+  const MkhLadderCertifiedIO* cio = nullptr;       // the certified rule's outputs, else NULL
   LadderFreeOut o{};               // device arrays (ladder_free_stage)
 };
 
 // The device side of a checked call's outputs: the caller's arrays for a device-pointer call, else workspace.
 static void ladder_free_stage(Stager& st, int B, int T, int W, LadderFree& lf) {
-  if (!lf.ck) return;
-  const size_t Bz = B, R = Bz * T;
-  lf.o = LadderFreeOut{lf.io->edge_collision, lf.io->n_edge_collisions, lf.io->edge_margin, lf.io->edge_margin_all};
-  if (st.devp) return;
-  lf.o.edge_collision = st.i32(WS_F_OUT_I, R + Bz); lf.o.n_edge_collisions = lf.o.edge_collision ? lf.o.edge_collision + R : nullptr;
-  lf.o.edge_margin = st.f64(WS_F_OUT_F, R);
-  if (lf.o.edge_margin_all) lf.o.edge_margin_all = st.f64(WS_F_EMARGIN, R * W * W);
+  if (lf.ck) lf.o = ladder_free_out(st, B, T, W, lf.rule, lf.io, lf.cio);
 }
 
 static void ladder_free_down(Stager& st, int B, int T, int W, const LadderFree& lf) {
-  if (!lf.ck) return;
-  const size_t Bz = B, R = Bz * T;
-  st.down(lf.io->edge_collision, lf.o.edge_collision, R * sizeof(int32_t));
-  st.down(lf.io->n_edge_collisions, lf.o.n_edge_collisions, Bz * sizeof(int32_t));
-  st.down(lf.io->edge_margin, lf.o.edge_margin, R * sizeof(double));
-  st.down(lf.io->edge_margin_all, lf.o.edge_margin_all, R * W * W * sizeof(double));
+  if (lf.ck) ladder_free_out_down(st, B, T, W, lf.o, lf.io, lf.cio);
 }
 
 // The search on the (B, T, W) nodes — behind the sweep of their edges in a checked call —, and the chosen nodes' rows.
@@ -1950,7 +2040,7 @@ static void ladder_pick(Stager& st, int B, int T, int W, const LadderCall& c, do
   const long long R = (long long)B * T;
   const int nq = st.p->dev.nq, nv = st.p->dev.nv;
   if (lf.ck)
-    ladder_search_free(st, lf.ck, B, T, W, lf.M, c.q, c.l_q, c.l_trk, c.w, max_step_sq, c.o_node, c.o_nt, c.o_nb, c.o_len, c.o_eb, lf.o);
+    ladder_search_free(st, lf.ck, B, T, W, lf.rule, c.q, c.l_q, c.l_trk, c.w, max_step_sq, c.o_node, c.o_nt, c.o_nb, c.o_len, c.o_eb, lf.o);
   else
     ladder_search(st, B, T, W, c.q, c.l_q, c.l_trk, c.w, max_step_sq, c.o_node, c.o_nt, c.o_nb, c.o_len, c.o_eb);
   ST_LAUNCH(st, launch_ladder_gather(st.stream, c.l_q, c.o_q, c.o_node, R, W, nq));
@@ -1970,7 +2060,7 @@ static int32_t ladder_refine_qvel(Stager& st, int B, int T, int W, const LadderC
     ST_LAUNCH(st, launch_ladder_gather_i32(st.stream, c.l_trk, c.o_trk, c.o_node, (long long)B * T, W));
     const mkh::LrOut o{c.o_q, c.o_v, c.o_len, c.o_trk, c.o_rep, c.o_ref, c.o_eb, c.o_nt, c.o_nb, c.o_st, c.o_it, c.o_cv};
     // (a checked call: the pass "with a checker"; the returned path's edge outputs replace the search's)
-    const RefineFree rf{lf.ck, lf.M, nullptr, lf.o.edge_margin, lf.o.edge_collision, lf.o.n_edge_collisions};
+    const RefineFree rf{lf.ck, lf.rule.M, nullptr, lf.o.edge_margin, lf.o.edge_collision, lf.o.n_edge_collisions};
     if (const int32_t rc = refine_pass(st, B, T, c.q, c.o_q, c.o_trk, c.in.ft, c.in.pt, c.in.ct, ls, c.w, io->max_step_sq, o, flags,
                                        lf.ck ? &rf : nullptr))
       return rc;
@@ -2176,14 +2266,17 @@ static int32_t ladder_nodes_call(MkhProblem* p, LadderFree lf, const char* who, 
   return st.finish();
 }
 
-// mkh_solve_trajectory_ladder_free (refine refused) and mkh_solve_trajectory_ladder_free_refined (refine required).
+// mkh_solve_trajectory_ladder_free (refine refused), mkh_solve_trajectory_ladder_free_refined (refine required) and
+// mkh_solve_trajectory_ladder_certified (rule.certified with cio; refine refused).
 static int32_t ladder_free_call(const char* who, bool refined, MkhProblem* p, MkhProblem* ck, int32_t B, int32_t T, int32_t n_seeds,
                                 int32_t n_nodes, double min_distance, const double* q, const double* frame_targets,
                                 const double* posture_target, const double* com_target, double dt, double damping, int32_t max_iters,
-                                double pos_threshold, double ori_threshold, uint64_t rng_seed, int64_t target_index0, int32_t n_samples,
+                                double pos_threshold, double ori_threshold, uint64_t rng_seed, int64_t target_index0, const EdgeRule& rule,
                                 const MkhTrajectoryLadderIO* io, const MkhLadderNodesIO* nodes, const MkhLadderRefineIO* refine,
-                                const MkhLadderFreeIO* fio, int32_t flags, void* hip_stream) {
+                                const MkhLadderFreeIO* fio, const MkhLadderCertifiedIO* cio, int32_t flags, void* hip_stream) {
   if (!p) return fail(MKH_E_INVALID, "null problem");
+  if (rule.certified && refine)
+    return fail(MKH_E_INVALID, "%s: the refinement pass still samples its edges (certifying it is the follow-up): refine must be NULL", who);
   if (!refined && refine)
     return fail(MKH_E_INVALID, "%s: the refinement pass knows nothing of collisions: refine must be NULL", who);
   if (refined && !refine)
@@ -2193,13 +2286,13 @@ static int32_t ladder_free_call(const char* who, bool refined, MkhProblem* p, Mk
                                "the ladder on distinct nodes", who, n_nodes, nodes ? "given" : "NULL");
   const int W = n_nodes ? n_nodes : n_seeds;
   if (B < 1 || T < 1 || W < 1 || W > 256) return fail(MKH_E_INVALID, "%s: B = %d, T = %d and %d nodes per rung: B, T >= 1, 1 <= nodes <= 256", who, B, T, W);
-  if (const int32_t rc = ladder_free_refuse(p, ck, B, T, W, n_samples, fio, who, refined)) return rc;
+  if (const int32_t rc = ladder_free_refuse(p, ck, B, T, W, rule, fio, cio, who, refined)) return rc;
   if (fio->node_margin)
     return fail(MKH_E_INVALID, "%s: node_margin is mkh_ladder_select_free's output: here the nodes' verdict is MKH_ST_IN_COLLISION in status_all", who);
   if (mkh::ladder_source_tile(W, p->dev.nq, p->dev.nv, p->model->njnt, nullptr, true) < 1)
     return fail(MKH_E_LIMIT, "%s: nq = %d: one destination tile and one source node with its flags do not fit 64 KB of LDS", who, p->dev.nq);
   LadderFree lf;
-  lf.ck = ck; lf.M = n_samples; lf.io = fio;
+  lf.ck = ck; lf.rule = rule; lf.io = fio; lf.cio = cio;
   if (!n_nodes)
     return ladder_plain_call(p, lf, who, B, T, n_seeds, q, frame_targets, posture_target, com_target, dt, damping, max_iters, pos_threshold,
                              ori_threshold, rng_seed, target_index0, io, refine, flags, hip_stream);
@@ -2213,9 +2306,26 @@ int32_t mkh_solve_trajectory_ladder_free(MkhProblem* p, MkhProblem* ck, int32_t 
                                          double ori_threshold, uint64_t rng_seed, int64_t target_index0, int32_t n_samples,
                                          const MkhTrajectoryLadderIO* io, const MkhLadderNodesIO* nodes, const MkhLadderRefineIO* refine,
                                          const MkhLadderFreeIO* fio, int32_t flags, void* hip_stream) {
+  EdgeRule rule;
+  rule.M = n_samples;
   return ladder_free_call("mkh_solve_trajectory_ladder_free", false, p, ck, B, T, n_seeds, n_nodes, min_distance, q, frame_targets,
                           posture_target, com_target, dt, damping, max_iters, pos_threshold, ori_threshold, rng_seed, target_index0,
-                          n_samples, io, nodes, refine, fio, flags, hip_stream);
+                          rule, io, nodes, refine, fio, nullptr, flags, hip_stream);
+}
+
+int32_t mkh_solve_trajectory_ladder_certified(MkhProblem* p, MkhProblem* ck, int32_t B, int32_t T, int32_t n_seeds, int32_t n_nodes,
+                                              double min_distance, const double* q, const double* frame_targets,
+                                              const double* posture_target, const double* com_target, double dt, double damping,
+                                              int32_t max_iters, double pos_threshold, double ori_threshold, uint64_t rng_seed,
+                                              int64_t target_index0, double resolution, int32_t max_samples, int32_t edge_policy,
+                                              const MkhTrajectoryLadderIO* io, const MkhLadderNodesIO* nodes,
+                                              const MkhLadderRefineIO* refine, const MkhLadderFreeIO* fio,
+                                              const MkhLadderCertifiedIO* cio, int32_t flags, void* hip_stream) {
+  EdgeRule rule;
+  rule.certified = true; rule.resolution = resolution; rule.max_samples = max_samples; rule.policy = edge_policy;
+  return ladder_free_call("mkh_solve_trajectory_ladder_certified", false, p, ck, B, T, n_seeds, n_nodes, min_distance, q, frame_targets,
+                          posture_target, com_target, dt, damping, max_iters, pos_threshold, ori_threshold, rng_seed, target_index0,
+                          rule, io, nodes, refine, fio, cio, flags, hip_stream);
 }
 
 int32_t mkh_solve_trajectory_ladder_free_refined(MkhProblem* p, MkhProblem* ck, int32_t B, int32_t T, int32_t n_seeds, int32_t n_nodes,
@@ -2225,9 +2335,11 @@ int32_t mkh_solve_trajectory_ladder_free_refined(MkhProblem* p, MkhProblem* ck, 
                                                  int64_t target_index0, int32_t n_samples, const MkhTrajectoryLadderIO* io,
                                                  const MkhLadderNodesIO* nodes, const MkhLadderRefineIO* refine,
                                                  const MkhLadderFreeIO* fio, int32_t flags, void* hip_stream) {
+  EdgeRule rule;
+  rule.M = n_samples;
   return ladder_free_call("mkh_solve_trajectory_ladder_free_refined", true, p, ck, B, T, n_seeds, n_nodes, min_distance, q,
                           frame_targets, posture_target, com_target, dt, damping, max_iters, pos_threshold, ori_threshold, rng_seed,
-                          target_index0, n_samples, io, nodes, refine, fio, flags, hip_stream);
+                          target_index0, rule, io, nodes, refine, fio, nullptr, flags, hip_stream);
 }
 
 // ---- goal sets (include/minkhip.h "THE RULE OF THE GOAL SET"; kernel: goalset.hip)

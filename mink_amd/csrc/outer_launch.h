@@ -245,6 +245,12 @@ hipError_t launch_sweep(hipStream_t stream, const void* wide_problem, int nbody,
 // certified sweep (certified_sweep.hip; include/minkhip.h "THE RULE OF THE CERTIFIED SWEEP"): N edges from row e of `from` to row e
 // of `to`, each at the sample count its own motion bound asks for, on launch_sweep's geometry.  reach: the checker's
 // (n_pairs, njnt, 2) table on the device (motion_bound.h).  Every output (N,) and required.  A checker of analytic pairs only.
+// The modes of a ladder (include/minkhip.h THE RULE, "with a certifying checker"), edges and output places as launch_sweep has them:
+//   kSweepLadder N = B·(T − 1)·W·W: per edge `blocked` under `policy` (MKH_EDGE_*; required), optionally the margin (double) and
+//                the verdict (verdict_all, int8) — an edge that is not swept: 0, NaN, −1.
+//   kSweepPath   N = B·T: margin, lower_bound, n_samples and verdict per (b, t), all required — t = 0: +inf, +inf, 0, −1; an
+//                edge that is not swept: NaN, NaN, 0, −1.
+// The other outputs are kSweepPairs' and are not read in these modes.
 struct CertifiedArgs {
   long long N;
   const double *from, *to, *reach;
@@ -252,8 +258,16 @@ struct CertifiedArgs {
   int32_t max_samples;
   double *margin, *lower_bound, *motion;
   int32_t *sample, *pair, *segment, *bound_pair, *n_samples, *capped, *verdict;
+  // (behind the outputs of kSweepPairs, whose offsets in the kernel-argument segment stand)
+  int32_t mode, T, W, policy;
+  const double* nodes;
+  const int32_t *tracked, *node_index;
+  uint8_t* blocked;
+  int8_t* verdict_all;
 };
 hipError_t launch_certified_sweep(hipStream_t stream, const void* wide_problem, int nbody, int nq, int n_pairs, const CertifiedArgs& a);
+// n_certified[b] = the waypoints t >= 1 of instance b whose entry of verdict (B, T) is 1
+hipError_t launch_certified_count(hipStream_t stream, int B, int T, const int32_t* verdict, int32_t* n_certified);
 // The pre-pass of a chunk (convex_sweep.hip): the general convex distance routine on every interior sample of the chunk's swept
 // edges with finite ends, one lane per (edge, sample, general convex pair), into a.cv — which the caller passes on to launch_sweep
 // with the same SweepArgs.  C: the checker's lists of those pairs, C.n_cv = a.n_cv.

@@ -1758,6 +1758,46 @@ FreeRefinedLadderNodesResult = nat._extended(
     order, and behind them `repaired` and `refined`, as in FreeRefinedLadderResult.""", module=__name__)
 
 
+_CERTIFIED_FIELDS = ("edge_verdict", "edge_lower_bound", "edge_n_samples", "n_certified")
+CertifiedLadderPath = nat._extended(
+    "CertifiedLadderPath", FreeLadderPath, nat.LADDER_CERTIFIED_IO_FIELDS,
+    """Result of ladder_path(collision_check=..., edge_resolution=...): FreeLadderPath's fields, in its order — `edge_margin` and
+    `edge_margin_all` are the certified sweep's margins, both ends of an edge included; `edge_collision` and `n_edge_collisions`
+    say what the search counted as blocked, which with require_certified includes the undecided edges —, then of the chosen path
+    `edge_verdict` (B, T) — 2 collides, 1 proven free along the whole motion, 0 undecided, −1 not swept (waypoint 0 included) —,
+    `edge_lower_bound` (B, T) — +inf at waypoint 0, NaN where not swept —, `edge_n_samples` (B, T) — 0 where not swept —,
+    `n_certified` (B,) and `edge_verdict_all` (B, T, S, S) int8, entry [b, t, s', s].""", optional=False, module=__name__)
+CertifiedLadderResult = nat._extended(
+    "CertifiedLadderResult", FreeLadderResult, _CERTIFIED_FIELDS,
+    """Result of solve_ik_trajectory_ladder(collision_check=..., edge_resolution=...): FreeLadderResult's fields, in its order, and
+    behind them `edge_verdict`, `edge_lower_bound`, `edge_n_samples` (B, T) and `n_certified` (B,) of the chosen path, as in
+    CertifiedLadderPath.""", module=__name__)
+CertifiedLadderNodesResult = nat._extended(
+    "CertifiedLadderNodesResult", FreeLadderNodesResult, _CERTIFIED_FIELDS,
+    """Result of solve_ik_trajectory_ladder(collision_check=..., n_nodes=K, edge_resolution=...): FreeLadderNodesResult's fields, in
+    its order, and behind them `edge_verdict`, `edge_lower_bound`, `edge_n_samples`, `n_certified`, as in CertifiedLadderPath.""",
+    module=__name__)
+
+
+def _edge_rule(edge_resolution, max_edge_samples, require_certified, edge_samples, collision_check, refine):
+    """The certified edge rule of the ladder calls, judged on the host: None without `edge_resolution`, else (resolution,
+    max_samples, require_certified)."""
+    if edge_resolution is None:
+        if require_certified:
+            raise ValueError("require_certified belongs to the certified edge rule: pass edge_resolution")
+        return None
+    if collision_check is None:
+        raise ValueError("edge_resolution is the certified edge rule of a checked call: pass collision_check")
+    if int(edge_samples) != 8:
+        raise ValueError("edge_resolution and edge_samples are two rules for the same edges: the certified rule takes its sample "
+                         "counts from the motion bound (max_edge_samples caps them)")
+    if refine:
+        raise ValueError("edge_resolution together with refine: the refinement pass still samples its edges — certifying it (and "
+                         "candidate tracking) is the follow-up; refine the returned path with refine_path")
+    nat.check_edge_rule(edge_resolution, max_edge_samples)
+    return float(edge_resolution), int(max_edge_samples), bool(require_certified)
+
+
 def _max_step_sq(max_step) -> float:
     """The squared gate of the ladder's break rule from the caller's joint-space step (None: no gate)."""
     if max_step is None:
@@ -1798,7 +1838,9 @@ def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt
                                max_instances: int = 1 << 20, damping: float = 1e-12, limits: Optional[Sequence] = None,
                                safety_break: bool = False, solver: str = "mi355x", n_nodes: Optional[int] = None,
                                min_distance: float = 0.1, unwind_turns: bool = False,
-                               collision_check: Optional["CollisionChecker"] = None, edge_samples: int = 8, refine: bool = False):
+                               collision_check: Optional["CollisionChecker"] = None, edge_samples: int = 8,
+                               edge_resolution: Optional[float] = None, max_edge_samples: int = 64,
+                               require_certified: bool = False, refine: bool = False):
     """Track a time sequence of targets through a ladder graph: `n_seeds` IK solutions per waypoint, solved independently of
     each other, and a dynamic program on the device that picks one per waypoint — the path that is complete first, free of
     joint-space jumps second and shortest third (the rule in full: include/minkhip.h).  Where solve_ik_trajectory_multistart
@@ -1845,8 +1887,17 @@ def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt
     same call on the device: lost waypoints, breaks and waypoints entered by a colliding motion are re-solved from their
     neighbour on the path, a repair is taken only when it and the motion into it are free, and the path comes back only where
     its key — the checked ladder's — is strictly smaller.  The result is a FreeRefinedLadderResult /
-    FreeRefinedLadderNodesResult: the checked call's fields, all of the returned path, then `repaired` and `refined`."""
+    FreeRefinedLadderNodesResult: the checked call's fields, all of the returned path, then `repaired` and `refined`.
+
+    `edge_resolution` (metres; with collision_check, not together with a non-default edge_samples or any refine) replaces the
+    fixed sample count by CollisionChecker.certified_sweep's rule: every edge into a tracked node gets the sample count its own
+    motion bound asks for at that resolution, at most `max_edge_samples`, both of its ends are judged, and it comes out
+    colliding, proven free for the WHOLE motion, or undecided.  The search blocks the colliding edges — with
+    `require_certified` every edge that is not proven free, so that every waypoint `n_tracked` counts is entered by a proven
+    motion.  The result is a CertifiedLadderResult / CertifiedLadderNodesResult: the checked call's fields, then `edge_verdict`,
+    `edge_lower_bound`, `edge_n_samples` and `n_certified`.  A checker with general convex pairs is refused."""
     del solver
+    rule = _edge_rule(edge_resolution, max_edge_samples, require_certified, edge_samples, collision_check, refine)
     free_refine = isinstance(refine, str)
     if free_refine:
         if refine != "free":
@@ -1895,6 +1946,9 @@ def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt
     def job(handle, lo, hi):
         args = (q[lo:hi], _rows(ft, 0, lo, hi), _rows(pt, 2, lo, hi), _rows(ct, 2, lo, hi), dt, damping)
         rows = dict(target_index0=lo, seeds=_rows(seeds, 0, lo, hi), seed_table=seed_table)
+        if rule is not None:
+            return handle.solve_trajectory_ladder_certified(*args, checker=collision_check, resolution=rule[0], max_samples=rule[1],
+                                                            require_certified=rule[2], **rows, **kw)
         if collision_check is not None:
             return handle.solve_trajectory_ladder_free(*args, checker=collision_check, edge_samples=int(edge_samples),
                                                        refine=free_refine, **rows, **kw)
@@ -1903,7 +1957,7 @@ def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt
 
     # (the native result, and behind a checker the pair of it and the checker's outputs: the result types by (nodes, checker, refined))
     native = nat.TrajectoryLadderOut if K is None else nat.TrajectoryLadderNodesOut
-    res = _join(native if collision_check is None else (native, nat.LadderFreeOut),
+    res = _join(native if collision_check is None else (native, nat.LadderFreeOut if rule is None else nat.LadderCertifiedOut),
                 _chunks_and_shards(configuration, layout, handles, B, chunk, n_dev, job))
     path = res if collision_check is None else res[0]
     _status_epilogue(path.status, "solve_ik_trajectory_ladder", "chosen path(s)",
@@ -1914,6 +1968,8 @@ def solve_ik_trajectory_ladder(configuration: Configuration, tasks: Sequence, dt
     cls = {(False, False): (LadderResult, RefinedLadderResult), (True, False): (LadderNodesResult, RefinedLadderNodesResult),
            (False, True): (FreeLadderResult, FreeRefinedLadderResult),
            (True, True): (FreeLadderNodesResult, FreeRefinedLadderNodesResult)}[K is not None, collision_check is not None][bool(refine)]
+    if rule is not None:
+        cls = CertifiedLadderResult if K is None else CertifiedLadderNodesResult
     flags = ("converged", "edge_break", "converged_all") + (("refined",) if refine else ()) + \
         (("edge_collision",) if collision_check is not None else ())
     return _present(configuration, cls, res, flags)
@@ -2025,7 +2081,8 @@ def refine_path(configuration: Configuration, tasks: Sequence, dt: float, target
 
 
 def ladder_path(configuration: Configuration, q_nodes, tracked=None, max_step: Optional[float] = None, weights=None,
-                collision_check: Optional["CollisionChecker"] = None, edge_samples: int = 8) -> LadderPath:
+                collision_check: Optional["CollisionChecker"] = None, edge_samples: int = 8,
+                edge_resolution: Optional[float] = None, max_edge_samples: int = 64, require_certified: bool = False) -> LadderPath:
     """The ladder's search alone, over the caller's own rungs (closed-form IK branches, solutions of earlier calls): q_nodes
     (T, S, nq) or (B, T, S, nq), `tracked` (same leading shape, default: every node counts as tracked), the start edge from the
     configuration's q.  The rule — key (untracked, breaks, length), ties to the lowest index — is solve_ik_trajectory_ladder's;
@@ -2037,9 +2094,17 @@ def ladder_path(configuration: Configuration, q_nodes, tracked=None, max_step: O
     as lost, so the key's first component counts the waypoints that are untracked, in collision or entered through collision.
     The result is then a FreeLadderPath.  A checker with general convex pairs (cylinder-box, ellipsoids, mesh hulls) needs its
     `sweep_rows` >= edge_samples; the edges are then swept in chunks of sweep_rows // edge_samples, and the result does not
-    depend on the value.  Without collision_check the call is the one above, unchanged."""
+    depend on the value.  Without collision_check the call is the one above, unchanged.
+
+    `edge_resolution` (metres; with collision_check, not together with a non-default edge_samples) judges the edges by
+    CollisionChecker.certified_sweep's rule instead: the sample count of an edge follows from its own motion bound at that
+    resolution (at most `max_edge_samples`), both of its ends are judged — so an edge that LEAVES a colliding node collides —,
+    and its verdict is colliding, proven free along the whole motion, or undecided.  The search blocks the colliding edges, with
+    `require_certified` every edge that is not proven free.  The result is then a CertifiedLadderPath.  A checker with general
+    convex pairs is refused.  Without edge_resolution the call is the one above, unchanged."""
     from .tasks import PostureTask
 
+    rule = _edge_rule(edge_resolution, max_edge_samples, require_certified, edge_samples, collision_check, False)
     _check_collision_check(collision_check, configuration, edge_samples)
     step_sq = _max_step_sq(max_step)
     B, nq, nv = configuration.batch_size, configuration.nq, configuration.nv
@@ -2057,9 +2122,12 @@ def ladder_path(configuration: Configuration, q_nodes, tracked=None, max_step: O
         if collision_check is None:
             return _present(configuration, LadderPath, prob.ladder_select(configuration.q_batch, q_nodes, tracked, step_sq, weights),
                             flags=("edge_break",))
-        out = prob.ladder_select_free(configuration.q_batch, q_nodes, collision_check, tracked, step_sq, weights, int(edge_samples),
-                                      True)
-    return _present(configuration, FreeLadderPath, out, flags=("edge_break", "edge_collision"))
+        if rule is not None:
+            out = prob.ladder_select_certified(configuration.q_batch, q_nodes, collision_check, tracked, step_sq, weights, *rule, True)
+        else:
+            out = prob.ladder_select_free(configuration.q_batch, q_nodes, collision_check, tracked, step_sq, weights, int(edge_samples),
+                                          True)
+    return _present(configuration, FreeLadderPath if rule is None else CertifiedLadderPath, out, flags=("edge_break", "edge_collision"))
 
 
 def _chunks_and_shards(configuration: Configuration, layout, handles, B: int, chunk: int, n_dev: int, job):
