@@ -123,8 +123,12 @@ def shapes_pairs():
 def fixture(name):
     """(model, [CollisionAvoidanceLimit kwargs], q_rows) by name: ur5e_wrist, ur5e_convex, ur5e_all, g1, chain, shapes (30 pairs:
     four rows per wavefront, two trips of its 16 lanes over bodies and pairs), shapes_wide (the same pairs twice, with two
-    minimum distances: 60 pairs, one row per wavefront)."""
+    minimum distances: 60 pairs, one row per wavefront), tree_small / tree_wide / tree_convex (tests/tree_cases.py)."""
     if name in _fixtures:
+        return _fixtures[name]
+    if name.startswith("tree_"):                   # random trees with ball and stacked joints: tests/tree_cases.py
+        import tree_cases
+        _fixtures[name] = tree_cases.fixture(name)
         return _fixtures[name]
     from mink_amd import workloads
     if name in ("shapes", "shapes_wide"):

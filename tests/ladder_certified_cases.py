@@ -25,6 +25,8 @@ CASES = {
     # under REQUIRE_CERTIFIED instances 0 and 1 of the second lose waypoints that REJECT_COLLIDING keeps (n_tracked 2, 1 of 3)
     "tiny": ("ur5e_all", (3, 3, 2), 0.15, 0.04, 16, 0, 0),
     "D": ("ur5e_all", (3, 3, 2), 0.3, 0.04, 16, 0, 0),
+    # a random tree with ball and stacked joints (tests/tree_cases.py; run by tests/test_gpu_tree_checker.py)
+    "tree": ("tree_small", (2, 4, 3), 0.15, 0.05, 32, 1, 0),
 }
 _cache = {}
 

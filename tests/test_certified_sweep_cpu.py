@@ -116,7 +116,13 @@ _cases = {}
 
 
 def _case(name):
-    """(model, limits, a, b, RefCertified at resolution 0.02) of a fixture's shortened edges, computed once."""
+    """(model, limits, a, b, RefCertified at resolution 0.02) of a fixture's shortened edges, computed once.  The random trees
+    of tests/tree_cases.py (tests/test_tree_checker_cpu.py runs the two properties on them): their own 24 edges, s = 0.3, at
+    resolution 0.05."""
+    if name not in _cases and name.startswith("tree_"):
+        import tree_cases as tc
+        model, limits, (a, b) = cr.fixture(name)[0], tc.limits(name), tc.edges(name)
+        _cases[name] = (model, limits, a, b, cf.certified_sweep(model, limits, a, b, tc.RESOLUTION, 64))
     if name not in _cases:
         model, _, q = cr.fixture(name)
         n = {"ur5e_all": 40, "shapes": 12, "g1": 8}[name]

@@ -22,6 +22,7 @@ import pytest
 import certified_ref as cf
 import clearance_ref as cr
 import keyframe_ref as kf
+from tree_cases import CERTIFIED_COMPARED as TREE_N, CERTIFIED_DROPPED as TREE_DROPPED
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-9
@@ -88,6 +89,12 @@ CASES = {
     "ur5e_coarse": ("ur5e_all", slice(0, 60), slice(100, 160), 0.1, 0.05, 64, 50, 2),
     "shapes_wide": ("shapes_wide", slice(0, 20), slice(20, 40), 0.2, 0.02, 64, 16, 0),
     "g1": ("g1", slice(0, 12), slice(12, 24), 0.1, 0.02, 64, 8, 0),
+    # the random trees of tests/tree_cases.py (run by tests/test_gpu_tree_checker.py): ball and stacked joints, anchors off the body
+    # origins, slides behind rotations; at max_samples = 4 most of the edges are capped
+    "tree_small": ("tree_small", slice(0, 24), slice(24, 48), 0.3, 0.05, 64, TREE_N["tree_small"], TREE_DROPPED["tree_small"]),
+    "tree_small_capped": ("tree_small", slice(0, 24), slice(24, 48), 0.3, 0.05, 4, TREE_N["tree_small_capped"], TREE_DROPPED["tree_small_capped"]),
+    "tree_wide": ("tree_wide", slice(0, 16), slice(24, 40), 0.3, 0.05, 64, TREE_N["tree_wide"], TREE_DROPPED["tree_wide"]),
+    "tree_wide_capped": ("tree_wide", slice(0, 16), slice(24, 40), 0.3, 0.05, 4, TREE_N["tree_wide_capped"], TREE_DROPPED["tree_wide_capped"]),
 }
 _case_cache = {}
 
@@ -182,10 +189,10 @@ def test_reach_table_matches_the_reference(nat, name):
     assert (want[fin] > 0).any()
 
 
-def test_margin_is_the_devices_own_clearance_and_sweep(nat):
-    """Every candidate edge of `ur5e_fine`: min(clearance(q_from), swept_clearance at the edge's own n_samples, clearance(q_to)) is
+def margin_is_the_devices_own_clearance_and_sweep(name):
+    """Every candidate edge of a case: min(clearance(q_from), swept_clearance at the edge's own n_samples, clearance(q_to)) is
     the certified sweep's margin to 1e-9 — the edges grouped by their count."""
-    fixture, a, b, resolution, mx, _, _ = case("ur5e_fine")
+    fixture, a, b, resolution, mx, _, _ = case(name)
     ck = _checker(fixture)
     out = ck.certified_sweep(a, b, resolution, max_samples=mx)
     ends = np.minimum(ck.clearance(a).margin, ck.clearance(b).margin)
@@ -195,25 +202,33 @@ def test_margin_is_the_devices_own_clearance_and_sweep(nat):
         inner[of] = ck.swept_clearance(a[of], b[of], n_samples=int(M)).margin
     ck.close()
     err = np.abs(np.minimum(ends, inner) - out.margin).max()
-    print("%d edges, %d distinct counts: max |min(ends, sweep) - margin| %.2e" % (len(a), len(np.unique(out.n_samples)), err))
+    print("%s: %d edges, %d distinct counts: max |min(ends, sweep) - margin| %.2e" % (name, len(a), len(np.unique(out.n_samples)), err))
     assert err <= TOL
 
 
-def test_certified_edges_hold_on_dense_device_rows(nat):
-    """Device soundness: on the certified edges of `ur5e_fine`, the device's clearance of 257 numpy-blended rows never falls below
-    lower_bound - 1e-9."""
-    fixture, a, b, resolution, mx, _, _ = case("ur5e_fine")
+def test_margin_is_the_devices_own_clearance_and_sweep(nat):
+    margin_is_the_devices_own_clearance_and_sweep("ur5e_fine")
+
+
+def certified_edges_hold_on_dense_device_rows(name, at_least):
+    """Device soundness: on the certified edges of a case (`at_least` of them), the device's clearance of 257 numpy-blended rows
+    never falls below lower_bound - 1e-9."""
+    fixture, a, b, resolution, mx, _, _ = case(name)
     model, _, _ = cr.fixture(fixture)
     ck = _checker(fixture)
     out = ck.certified_sweep(a, b, resolution, max_samples=mx)
     edges = np.nonzero(out.certified)[0]
-    assert len(edges) >= 20 and (out.lower_bound[edges] >= 0.0).all()
+    assert len(edges) >= at_least and (out.lower_bound[edges] >= 0.0).all()
     rows = np.stack([kf.blend_posture(model, a[e], b[e], float(i) / 256.0) for e in edges for i in range(257)])
     dense = ck.clearance(rows).margin.reshape(len(edges), 257).min(axis=1)
     ck.close()
     slack = (dense - out.lower_bound[edges]).min()
-    print("%d certified edges x 257 rows: smallest dense margin - lower_bound = %.3e" % (len(edges), slack))
+    print("%s: %d certified edges x 257 rows: smallest dense margin - lower_bound = %.3e" % (name, len(edges), slack))
     assert slack >= -TOL
+
+
+def test_certified_edges_hold_on_dense_device_rows(nat):
+    certified_edges_hold_on_dense_device_rows("ur5e_fine", 20)
 
 
 def test_an_edge_from_a_row_to_itself(nat):

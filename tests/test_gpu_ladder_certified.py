@@ -37,10 +37,10 @@ def nat():
     return _native
 
 
-def _checker(fixture, **kw):
+def _checker(fixture, max_rows=4096, **kw):
     import mink_amd as mink
     model, _, _ = cr.fixture(fixture)
-    return mink.CollisionChecker(model, cr.fixture_limits(fixture), max_rows=4096, **kw)
+    return mink.CollisionChecker(model, cr.fixture_limits(fixture), max_rows=max_rows, **kw)
 
 
 def _close(a, b, what):
@@ -95,14 +95,14 @@ def _device_invariants(out, ck, q_nodes, resolution, mx, policy, what):
             np.testing.assert_array_equal(np.asarray(getattr(out, f))[at], getattr(cs, g), err_msg=f"{what}: {f} is certified_sweep's {g}")
 
 
-def _against_reference(name, conditions):
+def _against_reference(name, conditions, max_rows=4096):
     import mink_amd as mink
     c = lc.case(name)
     keep, st = c["keep"], c["stage"]
     conditions(c)
     q, q_nodes = c["q"][keep], c["q_nodes"][keep]
     cfg = mink.Configuration(c["model"], q.copy())
-    ck = _checker(c["fixture"])
+    ck = _checker(c["fixture"], max_rows)
     T = q_nodes.shape[1]
     for policy in (0, 1):
         want = c["select"][policy]
